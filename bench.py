@@ -8,16 +8,24 @@ every rank does that on its own 256 clips (weak scaling, weights replicated) and
 indices are all-gathered (RCCL over xGMI) inside the timed region.
 
 N = 1 workload = BASELINE config C3 (B=256, T=300, autoregressive decode, bf16 perf mode).
-Extra objects on the line: ``roofline`` (dominant kernel, timed live with HIP events) and ``cpu_baseline``
-(the CPU oracle on a bounded sample of the same workload, rank 0 at N=1 only); beside them ``parity_mode`` (the same
-workload in the f32 mode), ``cross_attn_mfma`` (the K/V projection GEMM) and ``train_step`` (the HIP training step of
-SURVEY 8 row f3, B=16) -- all measured outside the timed region of ``value``.
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds the objects measured outside the
+timed region of ``value``: ``best_of_10`` (10 samples per clip in one pass), ``roofline`` (dominant kernel, timed live
+with HIP events) and ``cpu_baseline`` (the CPU oracle on a bounded sample of the same workload, rank 0 at N=1 only);
+beside them ``parity_mode`` (the same workload in the f32 mode, with ``bf16_vs_f32``), ``cross_attn_mfma`` (the K/V
+projection GEMM), ``train_step`` (the HIP training step of SURVEY 8 row f3, B=16) and, for N > 1, ``shard_check``.
+The ``--no-*`` switches leave out single objects of a ``--full`` run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--frames 300] [--mode bf16|f32]
+``--dump-outputs DIR`` writes what the last timed step returned (decoded coefficients ``pred``, generated code indices
+``tokens``, all ranks' after the all-gather, and the ``loss``) as ``DIR/<name>.npy``; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--frames 300] [--mode bf16|f32] [--full]
+                    [--dump-outputs DIR]
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -34,6 +42,7 @@ from dimx.seq2seq_pretrain import SLMFT, mark_prefix  # noqa: E402
 
 SEED = 20260928
 GFLOP_PER_CLIP_T300 = 73.5  # SURVEY.md section 8d, necessary work
+DUMP_BYTES = 60 << 20       # --dump-outputs: at most this much array data in all (under 64 MB with the .npy headers)
 
 
 def synth_batch(B, T, device, salt):
@@ -113,7 +122,6 @@ def _cpu_worker(T, b):
 
 def cpu_baseline(T, timeout_s=300):
     """Run the CPU oracle on a bounded sample in a subprocess (hard timeout: the bench never hangs on it)."""
-    import subprocess
     try:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-worker", str(T), "8"],
                            capture_output=True, text=True, timeout=timeout_s)
@@ -231,10 +239,10 @@ def ensure_ranks(args, argv):
     """``--gpus N`` must mean N ranks, one per GPU -- or a non-zero exit, never a line that says ``n_gpus: 1``.
 
     * under torchrun (WORLD_SIZE set): WORLD_SIZE must equal N, else exit 2;
-    * plain ``python bench.py --gpus N`` with N > 1: this process becomes the launcher -- it re-executes itself as
+    * plain ``python bench.py --gpus N`` with N > 1: this process becomes the launcher -- it runs
       ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>
-      bench.py <same arguments>`` (one process per GPU, HSA_ENABLE_IPC_MODE_LEGACY=0), after checking that N GPUs are
-      visible (exit 2 with a message otherwise)."""
+      bench.py <same arguments>`` as a child (one process per GPU, HSA_ENABLE_IPC_MODE_LEGACY=0) and exits with its status,
+      after checking that N GPUs are visible (exit 2 with a message otherwise)."""
     want = max(1, args.gpus)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
@@ -253,7 +261,8 @@ def ensure_ranks(args, argv):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + list(argv)
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)      # the launcher's exit code is torchrun's
+    # a child process, never exec: counting the GPUs above may already have opened the device in this process
+    raise SystemExit(subprocess.call(cmd, env=env))      # the launcher's exit code is torchrun's
 
 
 class _StubModel:
@@ -306,6 +315,26 @@ def shard_check(make_model, device, rank, world, T=60, per_rank=8):
     return out
 
 
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs``: each array as out_dir/<name>.npy, float32 (float64 stays float64; the code indices are exact
+    in float32).  An array larger than its share of DUMP_BYTES keeps a fixed, seeded sample of its rows (leading axis:
+    clips, or generated sequences), and the sampled row numbers go to <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = np.atleast_1d(a if a.dtype == np.float64 else a.astype(np.float32))
+        if a.nbytes > share:
+            keep = max(1, share * a.shape[0] // a.nbytes)
+            rows = np.sort(np.random.default_rng(SEED).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        elif os.path.exists(os.path.join(out_dir, name + "_rows.npy")):
+            os.remove(os.path.join(out_dir, name + "_rows.npy"))      # left by an earlier run at a larger size
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     if len(sys.argv) >= 4 and sys.argv[1] == "--cpu-worker":
         _cpu_worker(int(sys.argv[2]), int(sys.argv[3]))
@@ -318,6 +347,11 @@ def main():
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--mode", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--samples", type=int, default=1, help="generations per clip in one pass (best-of-N protocol)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps also run the secondary measurements and checks (best-of-10, parity mode, "
+                         "roofline, training steps, CPU baseline, N-rank shard check); the --no-* switches leave out single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (pred, tokens, loss) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-mode-compare", action="store_true", help="skip the bf16-vs-f32 motion statistics (part of the parity-mode leg)")
@@ -367,16 +401,16 @@ def main():
         eng = model.engine(device)
 
     def step(i):
-        _, _, pred, tokens = model(v_s, v_l, v_a, mask, mode="val", seed=SEED + i + 1, return_tokens=True,
-                                   n_samples=args.samples)
+        loss, _, pred, tokens = model(v_s, v_l, v_a, mask, mode="val", seed=SEED + i + 1, return_tokens=True,
+                                      n_samples=args.samples)
         tok = tokens.reshape(-1, T - 1).to(torch.int32)
         # equal shards: ONE collective, nothing synchronises with the host first
         if args.gather == "tokens":
-            return pred, ddist.all_gather_rows(tok, [tok.shape[0]] * world)
+            return loss, pred, ddist.all_gather_rows(tok, [tok.shape[0]] * world)
         # the payload evaluate_test_epoch gathers (code/x_engine_pt.py:259-270 accumulates exactly these on the host): indices +
         # decoded coefficients, packed into one buffer (dist.pack_rows)
         buf = ddist.all_gather_rows(ddist.pack_rows(tok, pred.reshape(tok.shape[0], -1).float()), [tok.shape[0]] * world)
-        return pred, buf[:, :T - 1]      # the indices' columns of the gathered buffer (the metrics rank unpacks the rest)
+        return loss, pred, buf[:, :T - 1]      # the indices' columns of the gathered buffer (the metrics rank unpacks the rest)
 
     for i in range(args.warmup):
         step(i)
@@ -384,11 +418,13 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        pred, gathered = step(args.warmup + i)
+        loss, pred, gathered = step(args.warmup + i)
     sync()
     ddist.barrier()
     elapsed = ddist.max_over_ranks(time.perf_counter() - t0, device if (world > 1 and device.type == "cuda") else None)
     assert gathered.shape == (world * B * args.samples, T - 1) and torch.isfinite(pred).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pred": pred, "tokens": gathered, "loss": torch.as_tensor(loss)})
 
     rccl_ranks = 1
     check = None
@@ -397,7 +433,7 @@ def main():
         one = torch.ones(1, device="cpu" if tdist.get_backend() == "gloo" else device)
         tdist.all_reduce(one)                 # the collective library (RCCL on GPUs) saw this many ranks
         rccl_ranks = int(one.item())
-        if not args.no_shard_check:
+        if args.full and not args.no_shard_check:
             check = shard_check((lambda: _StubModel()) if args.stub else
                                 (lambda: SLMFT(synthetic_seed=SEED, numeric_mode=L.MODE_PARITY_F32).eval()),
                                 device, rank, world)
@@ -445,7 +481,7 @@ def main():
         return
     # batches dimx_generate had to regenerate because its XCD-local chain kernels / deferred LayerNorm reported a fault (0 expected)
     out["chain_faults"] = int(eng.chain_faults())
-    if world == 1 and args.mode == "bf16" and args.samples == 1 and not args.no_best_of_n and B * 10 <= 4096:
+    if args.full and world == 1 and args.mode == "bf16" and args.samples == 1 and not args.no_best_of_n and B * 10 <= 4096:
         # the reference's real test-time protocol draws 10 generations per clip (code/x_engine_pt.py:257): the same clips as ONE pass
         # of B x 10 sequences (shared context K/V per clip), 1 warm-up + 2 timed passes
         model(v_s, v_l, v_a, mask, mode="val", seed=SEED + 900, n_samples=10)
@@ -458,7 +494,7 @@ def main():
         out["best_of_10"] = {"value": B * 10 / dt10, "unit": "generated sequences/s", "ms_per_pass": dt10 * 1e3, "clips": B, "samples_per_clip": 10,
                              "note": "SLMFT.forward(mode='val', n_samples=10): the reference's best-of-10 evaluation draws in one pass "
                                      "(python bench.py --samples 10 times the same with the --steps / --warmup of the line)"}
-    if world == 1 and args.mode == "bf16" and not args.no_parity_mode and args.samples == 1:
+    if args.full and world == 1 and args.mode == "bf16" and not args.no_parity_mode and args.samples == 1:
         # the same workload in the mode that meets north_star's tolerance (f32 operands, exact-f32 MFMA; VQ indices
         # and generated tokens bit-identical to the oracle): 2 warm-ups + 5 timed steps
         pm = SLMFT(synthetic_seed=SEED, numeric_mode=L.MODE_PARITY_F32).eval()
@@ -485,7 +521,7 @@ def main():
                               "f32-equivalent; DIMX_NO_X3=1 = the exact-f32 MFMA kernel)",
                               "decode_gemm": "gemm_x3_kernel" if os.environ.get("DIMX_NO_X3") is None else "gemm_ws_kernel<float>"}
         eng = pm.engine(device)
-    if not args.no_roofline:   # per-GPU kernel measurement on rank 0's device (for N > 1 the other ranks have left by now)
+    if args.full and not args.no_roofline:   # per-GPU kernel measurement on rank 0's device (for N > 1 the other ranks have left by now)
         from dimx import roofline
         out["roofline"] = roofline.dominant_kernel(eng, B, T, args.mode)
         if args.mode == "bf16" and "parity_mode" in out and B <= 256:
@@ -494,9 +530,9 @@ def main():
         out["cross_attn_mfma"] = roofline.cross_kv_gemm(B, T, args.mode, device)
         if args.mode == "bf16":
             out["cross_attn_bundle"] = roofline.cross_attn_bundle(B, T, args.mode, device, out["roofline"], out["cross_attn_mfma"])
-    if world == 1 and args.mode == "bf16" and not args.no_train_step and args.samples == 1:
+    if args.full and world == 1 and args.mode == "bf16" and not args.no_train_step and args.samples == 1:
         out["train_step"] = train_step_line(device, T)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(T)
     print(json.dumps(out))
 

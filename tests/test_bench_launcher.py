@@ -21,7 +21,7 @@ def _line(stdout):
 
 
 def test_plain_python_gpus_2_launches_two_ranks_and_reports_them():
-    r = _run(["--gpus", "2", "--stub", "--steps", "2", "--warmup", "1", "--batch", "6", "--frames", "12"])
+    r = _run(["--gpus", "2", "--stub", "--full", "--steps", "2", "--warmup", "1", "--batch", "6", "--frames", "12"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert d is not None, r.stdout[-500:] + r.stderr[-1500:]
@@ -59,3 +59,48 @@ def test_single_rank_stub_line_has_the_contract_keys():
               "dtype", "data", "config", "rccl_ranks"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and "shard_check" not in d
+
+
+def _stub_last_step(B, T, steps, warmup):
+    """what the stub model returns at the last timed step of `bench.py --stub` (inputs and sampler seed as bench.py draws them)"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(bench.SEED)
+    v_s, v_l, v_a = (torch.randn(B, T, c, generator=g) for c in (56, 56, 8))
+    _, _, pred, tok = bench._StubModel()(v_s, v_l, v_a, torch.ones(B, T, dtype=torch.bool), seed=bench.SEED + warmup + steps)
+    return pred.numpy(), tok.numpy()
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: pred / tokens / loss of the LAST timed step as float32 / float64 .npy files, the same for two runs with
+    the same arguments; --steps sets the number of timed steps; a plain run leaves the --full objects out."""
+    import numpy as np
+    args = ["--stub", "--steps", "3", "--warmup", "1", "--batch", "4", "--frames", "10"]
+    dumps = []
+    for k in range(2):
+        r = _run(args + ["--dump-outputs", str(tmp_path / str(k))])
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert not {"roofline", "cpu_baseline", "parity_mode", "train_step", "best_of_10", "shard_check"} & set(d)
+        dumps.append({n: np.load(tmp_path / str(k) / (n + ".npy")) for n in ("pred", "tokens", "loss")})
+    for n, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        assert np.array_equal(a, dumps[1][n]), n
+    pred, tok = _stub_last_step(4, 10, steps=3, warmup=1)
+    assert np.array_equal(dumps[0]["pred"], pred) and np.array_equal(dumps[0]["tokens"], tok.astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "0")) == ["loss.npy", "pred.npy", "tokens.npy"]
+
+
+def test_dump_outputs_of_a_large_step_are_a_seeded_sample_under_64_mb(tmp_path):
+    import numpy as np
+    B, T = 2048, 50                     # pred alone is 22 MB, over its share of the budget
+    r = _run(["--stub", "--steps", "1", "--warmup", "0", "--batch", str(B), "--frames", str(T), "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    pred, tok = _stub_last_step(B, T, steps=1, warmup=0)
+    rows = np.load(tmp_path / "pred_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < B and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "pred.npy"), pred[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "tokens.npy"), tok.astype(np.float32))     # 0.4 MB: kept whole

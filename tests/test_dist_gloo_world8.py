@@ -121,14 +121,14 @@ def test_bench_launcher_at_8_ranks_with_c4_and_c5_shard_sizes():
     """`python bench.py --gpus 8` as the driver launches it (plain python -> self-launch of 8 ranks), stub step on gloo: the C4
     layout (256 clips per rank, global batch 2048) and the C5 layout (64 per rank, 512), the default payload of the timed
     collective (code indices + decoded coefficients, what evaluate_test_epoch gathers) and the indices-only one."""
-    r, d = _bench(["--gpus", "8", "--stub", "--steps", "2", "--warmup", "1", "--batch", "256", "--frames", "12"])
+    r, d = _bench(["--gpus", "8", "--stub", "--full", "--steps", "2", "--warmup", "1", "--batch", "256", "--frames", "12"])
     assert r.returncode == 0 and d is not None, r.stdout[-500:] + r.stderr[-2000:]
     assert d["n_gpus"] == 8 and d["rccl_ranks"] == 8 and d["config"]["global_batch"] == 2048 and d["scaling"] == "weak"
     assert d["config"]["gather"] == "tokens+coeffs" and d["config"]["gather_bytes_per_rank"] == 256 * 11 * (4 + 56 * 4)
     sc = d["shard_check"]
     assert sc["identical"] and sc["global_batch"] == 64 and sc["tokens_sha256_sharded"] == sc["tokens_sha256_one_rank"]
     assert len([ln for ln in r.stdout.splitlines() if ln.startswith("{")]) == 1
-    r, d = _bench(["--gpus", "8", "--stub", "--steps", "1", "--warmup", "0", "--batch", "64", "--frames", "10", "--gather", "tokens"])
+    r, d = _bench(["--gpus", "8", "--stub", "--full", "--steps", "1", "--warmup", "0", "--batch", "64", "--frames", "10", "--gather", "tokens"])
     assert r.returncode == 0 and d is not None, r.stdout[-500:] + r.stderr[-2000:]
     assert d["n_gpus"] == 8 and d["config"]["global_batch"] == 512 and d["config"]["gather"] == "tokens"
     assert d["config"]["gather_bytes_per_rank"] == 64 * 9 * 4 and d["shard_check"]["identical"]

@@ -18,7 +18,7 @@ def test_two_ranks_on_one_gpu_reproduce_the_single_rank_tokens():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--batch", "8", "--frames", "60",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--full", "--batch", "8", "--frames", "60",
                         "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-parity-mode", "--no-train-step"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
