@@ -556,6 +556,16 @@ static int ensure_packed(dimx_ctx* c, int need) {
     return DIMX_OK;
 }
 
+// the positional buffers of VQ-VAE slot `which` (packed on first use): the VQ-VAE training step (train.hip) adds them
+int vq_pe_buffers(dimx_ctx* c, int which, const float** pe_enc, const float** pe_dec) {
+    DIMX_REQUIRE(which == 0 || which == 1, DIMX_ERR_ARG, "vq_pe_buffers: which must be 0 or 1");
+    DIMX_HIP(hipSetDevice(c->device));
+    DIMX_TRY(ensure_packed(c, which == 0 ? COMP_VQ0 : COMP_VQ1));
+    *pe_enc = c->vq[which].pe_enc;
+    *pe_dec = c->vq[which].pe_dec;
+    return DIMX_OK;
+}
+
 // ------------------------------------------------------------------ small helpers
 static inline size_t es_of(const dimx_ctx* c) { return dtype_size(c->at); }
 static inline int tpad(int T) { return (T + 7) / 8 * 8; }

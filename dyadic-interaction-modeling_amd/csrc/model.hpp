@@ -121,6 +121,7 @@ struct GraphKey {
 }  // namespace dimx
 
 namespace dimx {
+int vq_pe_buffers(dimx_ctx* c, int which, const float** pe_enc, const float** pe_dec);   // model.hip
 void train_forget(dimx_ctx* h);   // train.hip: drop the training plan cached for a handle (dimx_destroy)
 }
 

@@ -351,6 +351,93 @@ int side_ready(TrainState& ts) {
     return DIMX_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- VQ-VAE step plan
+// The arenas of the VQ-VAE's own step (slot `which` of the handle: 0 = speaker_vq., 1 = listener_vq.): every parameter of
+// VQAutoEncoder (code/models/stage1_BIWI.py:10-20) -- encoder, decoder, codebook; the two pe buffers are not parameters.
+int build_vq_plan(dimx_handle h, int which, TrainPlan& p) {
+    DIMX_REQUIRE(which == 0 || which == 1, DIMX_ERR_ARG, "train_vq: which must be 0 (speaker_vq.) or 1 (listener_vq.)");
+    const dimx_dims& d = h->d;
+    const VQGeom& vg = h->vqg[which];
+    DIMX_REQUIRE(vg.in_dim == 56 && vg.hidden == 384 && vg.heads == 8 && vg.zdim == 128 && vg.fqn == 1 && vg.n_embed == 512 &&
+                     vg.has_decoder && d.vq_hidden == 384 && d.vq_heads == 8 && d.vq_zdim == 128,
+                 DIMX_ERR_ARG, "train_vq: slot %d is not the 56 / 384 / 8 x 48 / 128 VQ-VAE the step is written for", which);
+    const std::string pre = which == 0 ? "speaker_vq." : "listener_vq.";
+    auto add = [&](const std::string& name, int rows, int cols) -> int {
+        auto it = h->host.find(name);
+        DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "train_vq: weight %s was not loaded", name.c_str());
+        long n = 1;
+        for (auto sz : it->second.shape) n *= sz;
+        DIMX_REQUIRE(n == (long)rows * cols, DIMX_ERR_WEIGHT, "train_vq: %s has %ld elements, expected %d x %d", name.c_str(), n, rows, cols);
+        PInfo pi{name, p.total, n, rows, cols};
+        p.index[name] = (int)p.params.size();
+        p.params.push_back(pi);
+        p.total += (n + 3) / 4 * 4;  // 16-byte aligned tensors
+        return DIMX_OK;
+    };
+    const int H = d.vq_hidden, I = d.vq_inter;
+    auto blocks = [&](const std::string& net) -> int {
+        for (int i = 0; i < d.vq_layers; ++i) {
+            const std::string a = net + std::to_string(2 * i) + ".fn.";
+            const std::string m = net + std::to_string(2 * i + 1) + ".fn.";
+            DIMX_TRY(add(a + "norm.weight", 1, H));
+            DIMX_TRY(add(a + "norm.bias", 1, H));
+            DIMX_TRY(add(a + "fn.to_qkv.weight", 3 * H, H));
+            DIMX_TRY(add(a + "fn.to_out.weight", H, H));
+            DIMX_TRY(add(a + "fn.to_out.bias", 1, H));
+            DIMX_TRY(add(m + "norm.weight", 1, H));
+            DIMX_TRY(add(m + "norm.bias", 1, H));
+            DIMX_TRY(add(m + "fn.l1.weight", I, H));
+            DIMX_TRY(add(m + "fn.l1.bias", 1, I));
+            DIMX_TRY(add(m + "fn.l2.weight", H, I));
+            DIMX_TRY(add(m + "fn.l2.bias", 1, H));
+        }
+        return DIMX_OK;
+    };
+    const std::string e = pre + "encoder.", c = pre + "decoder.";
+    DIMX_TRY(add(e + "vertice_mapping.0.weight", H, vg.in_dim));
+    DIMX_TRY(add(e + "vertice_mapping.0.bias", 1, H));
+    DIMX_TRY(add(e + "squasher.0.0.weight", H, 5 * H));   // [out][in][5]: rows of in * 5 + tap
+    DIMX_TRY(add(e + "squasher.0.0.bias", 1, H));
+    DIMX_TRY(blocks(e + "encoder_transformer.net."));
+    DIMX_TRY(add(e + "encoder_linear_embedding.net.weight", H, H));
+    DIMX_TRY(add(e + "encoder_linear_embedding.net.bias", 1, H));
+    DIMX_TRY(add(e + "encoder_linear_embedding_post.net.weight", vg.zdim, H));
+    DIMX_TRY(add(e + "encoder_linear_embedding_post.net.bias", 1, vg.zdim));
+    DIMX_TRY(add(c + "expander.0.0.weight", H, 5 * H));
+    DIMX_TRY(add(c + "expander.0.0.bias", 1, H));
+    DIMX_TRY(blocks(c + "decoder_transformer.net."));
+    DIMX_TRY(add(c + "decoder_linear_embedding.net.weight", H, H));
+    DIMX_TRY(add(c + "decoder_linear_embedding.net.bias", 1, H));
+    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.weight", H, vg.zdim));
+    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
+    DIMX_TRY(add(c + "vertice_map_reverse.weight", vg.in_dim, H));
+    DIMX_TRY(add(pre + "quantize.embedding.weight", vg.n_embed, vg.zdim));
+    return DIMX_OK;
+}
+std::map<std::pair<dimx_handle, int>, TrainPlan>& vq_plans_map() {
+    static std::map<std::pair<dimx_handle, int>, TrainPlan> plans;   // erased by dimx_destroy (train_forget)
+    return plans;
+}
+TrainPlan* vq_plan_of(dimx_handle h, int which, int* rc) {
+    *rc = DIMX_OK;
+    if (!h) {
+        *rc = DIMX_ERR_ARG;
+        set_error("train_vq: null handle");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lock(g_plans_mu);
+    auto key = std::make_pair(h, which);
+    auto& plans = vq_plans_map();
+    auto it = plans.find(key);
+    if (it == plans.end()) {
+        TrainPlan p;
+        *rc = build_vq_plan(h, which, p);
+        if (*rc != DIMX_OK) return nullptr;
+        it = plans.emplace(key, std::move(p)).first;
+    }
+    return &it->second;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- step context
 struct Step {
     dimx_handle h;
@@ -990,31 +1077,23 @@ struct VqLayerSave {
     float *wq_pad, *wo_pad, *gq_pad, *go_pad;
     TrAttn shape;
 };
-struct VqDecSave {
-    std::string c;
-    Lin pre, conv, emb, rev;
-    std::vector<VqLayerSave> L;
-    float *zq, *h0, *x5, *xc, *yn, *h_out;
-    int B, n, M, H, I;
+// Dropout(p) after a positional encoding (train mode): the keep mask is regenerated from (seed, step, site), train_vq.hip
+struct VqDrop {
+    float p = 0.f;
+    uint64_t seed = 0;
+    long step = 0;
+    int site = 0;
 };
-int vqdec_fwd(Step& s, VqDecSave& V, const std::string& c, const int32_t* idx, const float* codebook, const float* pe, int B, int n, float* pred) {
+// the pre-LN blocks of a VQ-VAE Transformer (encoder_transformer / decoder_transformer; code/models/lib/base_models.py):
+// weight operand copies queued (the caller flushes), head-padded qkv / out scratch made
+int vq_blocks_prepare(Step& s, std::vector<VqLayerSave>& L, const std::string& net) {
     const dimx_dims& d = s.h->d;
-    const int H = d.vq_hidden, I = d.vq_inter, M = B * n, G = d.vq_heads;
-    DIMX_REQUIRE(H == 8 * 48 && G == 8 && d.vq_zdim == 128, DIMX_ERR_ARG, "train: the VQ decoder step is written for 8 heads of 48, 128-wide codes");
-    V.c = c; V.B = B; V.n = n; V.M = M; V.H = H; V.I = I;
-    V.pre = make_lin(s, c + "decoder_linear_embedding_pre.net.weight", c + "decoder_linear_embedding_pre.net.bias");
-    V.conv = make_lin(s, c + "expander.0.0.weight", c + "expander.0.0.bias");
-    V.emb = make_lin(s, c + "decoder_linear_embedding.net.weight", c + "decoder_linear_embedding.net.bias");
-    V.rev = make_lin(s, c + "vertice_map_reverse.weight");
-    DIMX_TRY(prep_lin(s, V.pre));
-    DIMX_TRY(prep_lin(s, V.conv));
-    DIMX_TRY(prep_lin(s, V.emb));
-    DIMX_TRY(prep_lin(s, V.rev));
-    V.L.resize(d.vq_layers);
+    const int H = d.vq_hidden, G = d.vq_heads;
+    L.resize(d.vq_layers);
     for (int i = 0; i < d.vq_layers; ++i) {
-        VqLayerSave& l = V.L[i];
-        l.a = c + "decoder_transformer.net." + std::to_string(2 * i) + ".fn.";
-        l.m = c + "decoder_transformer.net." + std::to_string(2 * i + 1) + ".fn.";
+        VqLayerSave& l = L[i];
+        l.a = net + std::to_string(2 * i) + ".fn.";
+        l.m = net + std::to_string(2 * i + 1) + ".fn.";
         l.qkv = make_lin(s, l.a + "fn.to_qkv.weight");
         l.out = make_lin(s, l.a + "fn.to_out.weight", l.a + "fn.to_out.bias");
         l.l1 = make_lin(s, l.m + "fn.l1.weight", l.m + "fn.l1.bias");
@@ -1032,22 +1111,14 @@ int vqdec_fwd(Step& s, VqDecSave& V, const std::string& c, const int32_t* idx, c
         DIMX_TRY(prep_lin(s, l.l1));
         DIMX_TRY(prep_lin(s, l.l2));
     }
-    DIMX_TRY(flush_prep(s));
-    V.zq = s.f32((size_t)M * 128);
-    V.h0 = s.f32((size_t)M * H);
-    V.x5 = s.f32((size_t)M * 5 * H);
-    V.xc = s.f32((size_t)M * H);
-    V.yn = s.f32((size_t)M * H);
-    float* h = s.f32((size_t)M * H);
-    TR(tr_gather128(codebook, idx, V.zq, M, s.st));
-    DIMX_TRY(lin_fwd(s, V.pre, V.zq, 128, M, V.h0, H));
-    TR(tr_im2col5(V.h0, V.x5, B, n, H, s.st));
-    DIMX_TRY(lin_fwd(s, V.conv, V.x5, 5 * H, M, V.xc, H));
-    TR(tr_lrelu_inorm_fwd(V.xc, V.yn, B, n, H, s.st));
-    DIMX_TRY(lin_fwd(s, V.emb, V.yn, H, M, h, H));
-    TR(tr_add_clip_rows(h, pe, h, M, n, H, s.st));
-    for (int i = 0; i < d.vq_layers; ++i) {
-        VqLayerSave& l = V.L[i];
+    return DIMX_OK;
+}
+// h [B * n, H] -> *h_out (a new buffer); the activations the backward pass needs stay in L
+int vq_blocks_fwd(Step& s, std::vector<VqLayerSave>& L, float* h, int B, int n, float** h_out) {
+    const dimx_dims& d = s.h->d;
+    const int H = d.vq_hidden, I = d.vq_inter, M = B * n, G = d.vq_heads;
+    for (size_t i = 0; i < L.size(); ++i) {
+        VqLayerSave& l = L[i];
         l.h_in = h;
         l.ya = s.f32((size_t)M * H);
         l.qkvb = s.f32((size_t)M * 3 * G * 64);
@@ -1070,17 +1141,15 @@ int vqdec_fwd(Step& s, VqDecSave& V, const std::string& c, const int32_t* idx, c
         DIMX_TRY(lin_fwd(s, l.l2, l.pre_act, I, M, h2, H, l.h_mid, H, 4));
         h = h2;
     }
-    V.h_out = h;
-    DIMX_TRY(lin_fwd(s, V.rev, h, H, M, pred, d.vq_in_dim));
+    *h_out = h;
     return DIMX_OK;
 }
-int vqdec_bwd(Step& s, VqDecSave& V, const float* dpred) {
+// dh [B * n, H]: gradient wrt the blocks' output on entry, wrt their input on return (in place)
+int vq_blocks_bwd(Step& s, std::vector<VqLayerSave>& L, float* dh, int B, int n) {
     const dimx_dims& d = s.h->d;
-    const int H = V.H, I = V.I, M = V.M, B = V.B, n = V.n, G = d.vq_heads;
-    float* dh = s.f32((size_t)M * H);
-    DIMX_TRY(lin_bwd(s, V.rev, V.h_out, H, dpred, d.vq_in_dim, M, dh, H, false));
-    for (int i = d.vq_layers - 1; i >= 0; --i) {
-        VqLayerSave& l = V.L[i];
+    const int H = d.vq_hidden, I = d.vq_inter, M = B * n, G = d.vq_heads;
+    for (int i = (int)L.size() - 1; i >= 0; --i) {
+        VqLayerSave& l = L[i];
         const size_t mark = s.ar->off;
         float* da = s.f32((size_t)M * I);
         DIMX_TRY(lin_bwd(s, l.l2, l.pre_act, I, dh, H, M, da, I, false, true));
@@ -1104,7 +1173,67 @@ int vqdec_bwd(Step& s, VqDecSave& V, const float* dpred) {
         DIMX_TRY(ln_adjoint(s, l.h_in, s.p(l.a + "norm.weight"), dy, dh, 1, M, H, s.g(l.a + "norm.weight"), s.g(l.a + "norm.bias")));
         s.ar->off = mark;
     }
-    // (+ pe: a buffer, no gradient) -> linear -> InstanceNorm / LeakyReLU -> conv -> linear; the codes carry no gradient (arg-max)
+    return DIMX_OK;
+}
+
+struct VqDecSave {
+    std::string c;
+    Lin pre, conv, emb, rev;
+    std::vector<VqLayerSave> L;
+    const float* zq;
+    float *h0, *x5, *xc, *yn, *h_out;
+    int B, n, M, H, I;
+    const VqDrop* drop;
+};
+// The decoder's input is the codebook gather of idx (legacy / SLM steps: arg-max codes, no gradient) or, when zq_in is given,
+// that latent [B * n, 128] itself (the VQ-VAE's own step: the straight-through latent, whose gradient vqdec_bwd returns).
+// drop: the PositionalEncoding's dropout (the VQ-VAE's own step in train mode); nullptr = none.
+int vqdec_fwd(Step& s, VqDecSave& V, const std::string& c, const int32_t* idx, const float* codebook, const float* pe, int B, int n, float* pred,
+              const float* zq_in = nullptr, const VqDrop* drop = nullptr) {
+    const dimx_dims& d = s.h->d;
+    const int H = d.vq_hidden, I = d.vq_inter, M = B * n, G = d.vq_heads;
+    DIMX_REQUIRE(H == 8 * 48 && G == 8 && d.vq_zdim == 128, DIMX_ERR_ARG, "train: the VQ decoder step is written for 8 heads of 48, 128-wide codes");
+    V.c = c; V.B = B; V.n = n; V.M = M; V.H = H; V.I = I; V.drop = drop;
+    V.pre = make_lin(s, c + "decoder_linear_embedding_pre.net.weight", c + "decoder_linear_embedding_pre.net.bias");
+    V.conv = make_lin(s, c + "expander.0.0.weight", c + "expander.0.0.bias");
+    V.emb = make_lin(s, c + "decoder_linear_embedding.net.weight", c + "decoder_linear_embedding.net.bias");
+    V.rev = make_lin(s, c + "vertice_map_reverse.weight");
+    DIMX_TRY(prep_lin(s, V.pre));
+    DIMX_TRY(prep_lin(s, V.conv));
+    DIMX_TRY(prep_lin(s, V.emb));
+    DIMX_TRY(prep_lin(s, V.rev));
+    DIMX_TRY(vq_blocks_prepare(s, V.L, c + "decoder_transformer.net."));
+    DIMX_TRY(flush_prep(s));
+    float* zq = zq_in ? nullptr : s.f32((size_t)M * 128);
+    V.h0 = s.f32((size_t)M * H);
+    V.x5 = s.f32((size_t)M * 5 * H);
+    V.xc = s.f32((size_t)M * H);
+    V.yn = s.f32((size_t)M * H);
+    float* h = s.f32((size_t)M * H);
+    if (!zq_in) TR(tr_gather128(codebook, idx, zq, M, s.st));
+    V.zq = zq_in ? zq_in : zq;
+    DIMX_TRY(lin_fwd(s, V.pre, V.zq, 128, M, V.h0, H));
+    TR(tr_im2col5(V.h0, V.x5, B, n, H, s.st));
+    DIMX_TRY(lin_fwd(s, V.conv, V.x5, 5 * H, M, V.xc, H));
+    TR(tr_lrelu_inorm_fwd(V.xc, V.yn, B, n, H, s.st));
+    DIMX_TRY(lin_fwd(s, V.emb, V.yn, H, M, h, H));
+    if (drop)
+        TR(tr_pe_dropout_fwd(h, pe, h, M, n, H, drop->p, drop->seed, drop->step, drop->site, s.st));
+    else
+        TR(tr_add_clip_rows(h, pe, h, M, n, H, s.st));
+    DIMX_TRY(vq_blocks_fwd(s, V.L, h, B, n, &V.h_out));
+    DIMX_TRY(lin_fwd(s, V.rev, V.h_out, H, M, pred, d.vq_in_dim));
+    return DIMX_OK;
+}
+// dzq (optional, [B * n, 128]): the gradient wrt the decoder's input latent
+int vqdec_bwd(Step& s, VqDecSave& V, const float* dpred, float* dzq = nullptr) {
+    const dimx_dims& d = s.h->d;
+    const int H = V.H, M = V.M, B = V.B, n = V.n;
+    float* dh = s.f32((size_t)M * H);
+    DIMX_TRY(lin_bwd(s, V.rev, V.h_out, H, dpred, d.vq_in_dim, M, dh, H, false));
+    DIMX_TRY(vq_blocks_bwd(s, V.L, dh, B, n));
+    // (+ pe: a buffer, no gradient; dropout: the same mask) -> linear -> InstanceNorm / LeakyReLU -> conv -> linear
+    if (V.drop) TR(tr_dropout_bwd(dh, M, n, H, V.drop->p, V.drop->seed, V.drop->step, V.drop->site, s.st));
     float* d_yn = s.f32((size_t)M * H);
     DIMX_TRY(lin_bwd(s, V.emb, V.yn, H, dh, H, M, d_yn, H, false));
     float* d_xc = s.f32((size_t)M * H);
@@ -1113,7 +1242,71 @@ int vqdec_bwd(Step& s, VqDecSave& V, const float* dpred) {
     DIMX_TRY(lin_bwd(s, V.conv, V.x5, 5 * H, d_xc, H, M, d_x5, 5 * H, false));
     float* d_h0 = s.f32((size_t)M * H);
     TR(tr_col2im5(d_x5, d_h0, B, n, H, s.st));
-    DIMX_TRY(lin_bwd(s, V.pre, V.zq, 128, d_h0, H, M, nullptr, 0, false));
+    // the legacy / SLM steps' codes carry no gradient (arg-max): dzq == nullptr there
+    DIMX_TRY(lin_bwd(s, V.pre, V.zq, 128, d_h0, H, M, dzq, 128, false));
+    return DIMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- VQ-VAE encoder
+// TransformerEncoder (code/models/stage1_BIWI.py:254-317, quant_factor 0): vertice_mapping = Linear + LeakyReLU(0.2) (in place),
+// squasher = Conv1d(k 5, replicate) + LeakyReLU + InstanceNorm (no affine), encoder_linear_embedding, + pe[clip] (then the
+// PositionalEncoding's Dropout), the pre-LN blocks (shared with the decoder), encoder_linear_embedding_post -> z [B * n, 128].
+struct VqEncSave {
+    Lin vm, conv, le, post;
+    std::vector<VqLayerSave> L;
+    const float* x;
+    float *h1, *x5, *xc, *yn, *h_out;
+    int B, n, M, H;
+    VqDrop drop;
+};
+int vqenc_fwd(Step& s, VqEncSave& E, const std::string& c, const float* x, const float* pe, const VqDrop& drop, int B, int n, float* z) {
+    const dimx_dims& d = s.h->d;
+    const int H = d.vq_hidden, M = B * n;
+    E.B = B; E.n = n; E.M = M; E.H = H; E.x = x; E.drop = drop;
+    E.vm = make_lin(s, c + "vertice_mapping.0.weight", c + "vertice_mapping.0.bias");
+    E.conv = make_lin(s, c + "squasher.0.0.weight", c + "squasher.0.0.bias");
+    E.le = make_lin(s, c + "encoder_linear_embedding.net.weight", c + "encoder_linear_embedding.net.bias");
+    E.post = make_lin(s, c + "encoder_linear_embedding_post.net.weight", c + "encoder_linear_embedding_post.net.bias");
+    DIMX_TRY(prep_lin(s, E.vm));
+    DIMX_TRY(prep_lin(s, E.conv));
+    DIMX_TRY(prep_lin(s, E.le));
+    DIMX_TRY(prep_lin(s, E.post));
+    DIMX_TRY(vq_blocks_prepare(s, E.L, c + "encoder_transformer.net."));
+    DIMX_TRY(flush_prep(s));
+    E.h1 = s.f32((size_t)M * H);
+    E.x5 = s.f32((size_t)M * 5 * H);
+    E.xc = s.f32((size_t)M * H);
+    E.yn = s.f32((size_t)M * H);
+    float* h = s.f32((size_t)M * H);
+    DIMX_TRY(lin_fwd(s, E.vm, x, d.vq_in_dim, M, E.h1, H));
+    TR(tr_lrelu(E.h1, (long)M * H, 0.2f, s.st));
+    TR(tr_im2col5(E.h1, E.x5, B, n, H, s.st));
+    DIMX_TRY(lin_fwd(s, E.conv, E.x5, 5 * H, M, E.xc, H));
+    TR(tr_lrelu_inorm_fwd(E.xc, E.yn, B, n, H, s.st));
+    DIMX_TRY(lin_fwd(s, E.le, E.yn, H, M, h, H));
+    TR(tr_pe_dropout_fwd(h, pe, h, M, n, H, drop.p, drop.seed, drop.step, drop.site, s.st));
+    DIMX_TRY(vq_blocks_fwd(s, E.L, h, B, n, &E.h_out));
+    DIMX_TRY(lin_fwd(s, E.post, E.h_out, H, M, z, d.vq_zdim));
+    return DIMX_OK;
+}
+// dz [B * n, 128] -> every encoder gradient (the input motion needs none)
+int vqenc_bwd(Step& s, VqEncSave& E, const float* dz) {
+    const dimx_dims& d = s.h->d;
+    const int H = E.H, M = E.M, B = E.B, n = E.n;
+    float* dh = s.f32((size_t)M * H);
+    DIMX_TRY(lin_bwd(s, E.post, E.h_out, H, dz, d.vq_zdim, M, dh, H, false));
+    DIMX_TRY(vq_blocks_bwd(s, E.L, dh, B, n));
+    TR(tr_dropout_bwd(dh, M, n, H, E.drop.p, E.drop.seed, E.drop.step, E.drop.site, s.st));
+    float* d_yn = s.f32((size_t)M * H);
+    DIMX_TRY(lin_bwd(s, E.le, E.yn, H, dh, H, M, d_yn, H, false));
+    float* d_xc = s.f32((size_t)M * H);
+    TR(tr_lrelu_inorm_bwd(E.xc, d_yn, d_xc, B, n, H, s.st));
+    float* d_x5 = s.f32((size_t)M * 5 * H);
+    DIMX_TRY(lin_bwd(s, E.conv, E.x5, 5 * H, d_xc, H, M, d_x5, 5 * H, false));
+    float* d_h1 = s.f32((size_t)M * H);
+    TR(tr_col2im5(d_x5, d_h1, B, n, H, s.st));
+    TR(tr_lrelu_bwd_out(E.h1, d_h1, (long)M * H, 0.2f, s.st));
+    DIMX_TRY(lin_bwd(s, E.vm, E.x, d.vq_in_dim, d_h1, H, M, nullptr, 0, false));
     return DIMX_OK;
 }
 
@@ -1122,6 +1315,8 @@ int vqdec_bwd(Step& s, VqDecSave& V, const float* dpred) {
 void train_forget(dimx_handle h) {
     std::lock_guard<std::mutex> lock(g_plans_mu);
     plans_map().erase(h);
+    vq_plans_map().erase(std::make_pair(h, 0));
+    vq_plans_map().erase(std::make_pair(h, 1));
 }
 
 }  // namespace dimx
@@ -1796,6 +1991,146 @@ int dimx_op_train_attention(int mfma, const float* q, const float* k, const floa
     DIMX_TRY(tr_attn_fwd(t, q, k, v, o, lse, st));
     if (d_o) DIMX_TRY(tr_attn_bwd(t, q, k, v, o, d_o, lse, delta, dq, H * 64, dk, H * 64, dv, H * 64, st));
     return DIMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- VQ-VAE (stage 1)
+// One forward + backward pass of the VQ-VAE's own training loop (code/train_vq.py:173-196): out, quant_loss, info = model(data);
+// loss = calc_vq_loss(out, data, quant_loss, quant_loss_weight) (code/metrics/loss.py:6-11).  Encoder -> z; the inference
+// argmin of vq.hip over a codebook copy made from the arena (same kernel, same summation order); straight-through latent; the
+// decoder on it; L1 reconstruction.  Backward: the decoder down to d z_st, + the commitment term, the encoder; the codebook
+// gradient from the codebook term alone.  Kernel by kernel on one stream (no captured graph, no side stream).
+static int vq_run(dimx_handle h, int which, const float* params, float* grads, const float* x, int B, int T, float beta, float qw, float p,
+                  uint64_t seed, long step, float* loss_out, float* pred_out, int32_t* idx_out, void* ws, size_t ws_bytes, hipStream_t st,
+                  size_t* need) {
+    int rc;
+    TrainPlan* plan = vq_plan_of(h, which, &rc);
+    if (!plan) return rc;
+    const dimx_dims& d = h->d;
+    DIMX_REQUIRE(B >= 1 && B <= 5000 && T >= 1 && T <= 65536 && (long)B * T <= (1l << 24), DIMX_ERR_ARG,
+                 "train_vq: B=%d T=%d out of range (B <= 5000 positional rows)", B, T);
+    DIMX_REQUIRE(p >= 0.f && p < 1.f && step >= 0, DIMX_ERR_ARG, "train_vq: dropout p=%g must be in [0, 1), step >= 0", p);
+    const bool live = ws != nullptr;
+    const float *pe_enc = nullptr, *pe_dec = nullptr;
+    if (live) DIMX_TRY(vq_pe_buffers(h, which, &pe_enc, &pe_dec));
+    Arena ar(ws, ws_bytes);
+    Step s;
+    s.h = h; s.plan = plan; s.P = params; s.G = grads; s.ar = &ar; s.st = st;
+    s.at = h->at;
+    s.bk = h->at == DIMX_BF16 ? 64 : 32;
+    s.B = B; s.T = T; s.M = B * T;
+    s.n = T;
+    s.Md = B * T;
+    s.prep.n = 0;
+    s.prep.total_tiles = 0;
+    const int H = d.vq_hidden, I = d.vq_inter, M = B * T, ZD = d.vq_zdim;
+    s.part = s.f32((size_t)2 * kTrSlabs * I);
+    s.ts = nullptr;
+    s.use_side = false;
+    {
+        const size_t n_ln = (size_t)(4 * 2 * d.vq_layers + 8);
+        const size_t n_b = (size_t)(3 * 2 * d.vq_layers + 12);
+        s.pool_cap = n_ln * (kLnBlocks + 4) * (size_t)H + n_b * (size_t)std::max(kTrSlabs, ceil_div(M, 32) + 1) * (size_t)I + 4096;
+        s.pool = s.f32(s.pool_cap);
+        s.pool_off = 0;
+        s.fin.n = 0;
+        s.fin.total_blocks = 0;
+    }
+    if (live) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+    const std::string pre = which == 0 ? "speaker_vq." : "listener_vq.";
+    const float* book = s.p(pre + "quantize.embedding.weight");
+    float* dbook = s.g(pre + "quantize.embedding.weight");
+
+    // ---------------- encoder, quantiser
+    VqDrop de, dd;
+    de.p = dd.p = p;
+    de.seed = dd.seed = seed;
+    de.step = dd.step = step;
+    de.site = 0;
+    dd.site = 1;
+    VqEncSave E;
+    float* z = s.f32((size_t)M * ZD);
+    DIMX_TRY(vqenc_fwd(s, E, pre + "encoder.", x, pe_enc, de, B, T, z));
+    float* Et = s.f32((size_t)ZD * d.vq_n_embed);
+    float* ee = s.f32((size_t)d.vq_n_embed);
+    int32_t* idx = idx_out ? idx_out : (int32_t*)s.take((size_t)M * 4);
+    float* zst = s.f32((size_t)M * ZD);
+    float* part_q = s.f32(kVqPart);
+    float* part_l = s.f32(kVqPart);
+    int nq = 1, nl = 1;
+    TR(tr_vq_book_prep(book, Et, ee, st));
+    TR(launch_vq_argmin(z, M, Et, ee, idx, nullptr, nullptr, st));
+    TR(tr_vq_quant_fwd(z, book, idx, zst, part_q, M, &nq, st));
+    // ---------------- decoder on the straight-through latent, L1 reconstruction, the four scalars
+    VqDecSave V;
+    float* pred = pred_out ? pred_out : s.f32((size_t)M * d.vq_in_dim);
+    DIMX_TRY(vqdec_fwd(s, V, pre + "decoder.", nullptr, nullptr, pe_dec, B, T, pred, zst, &dd));
+    float* dpred = s.f32((size_t)M * d.vq_in_dim);
+    TR(tr_l1_loss(pred, x, dpred, part_l, (long)M * d.vq_in_dim, &nl, st));
+    TR(tr_vq_finish(part_q, nq, part_l, nl, idx, M, beta, qw, loss_out, st));
+
+    // ---------------- backward
+    float* dz = s.f32((size_t)M * ZD);
+    DIMX_TRY(vqdec_bwd(s, V, dpred, dz));
+    const float inv = 2.0f / ((float)M * (float)ZD);
+    TR(tr_vq_commit_bwd(z, book, idx, dz, M, qw * beta * inv, st));
+    TR(tr_vq_book_grad(z, book, idx, dbook, M, qw * inv, st));
+    DIMX_TRY(vqenc_bwd(s, E, dz));
+    DIMX_TRY(flush_fin(s));
+    if (need) *need = s.peak + 256;
+    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_vq: the partial-row pool of the column reductions is too small");
+    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_vq: workspace %zu < required %zu", ws_bytes, s.peak);
+    return DIMX_OK;
+}
+
+int dimx_train_vq_num_params(dimx_handle h, int which) {
+    int rc;
+    TrainPlan* p = vq_plan_of(h, which, &rc);
+    return p ? (int)p->params.size() : rc;
+}
+
+int64_t dimx_train_vq_total(dimx_handle h, int which) {
+    int rc;
+    TrainPlan* p = vq_plan_of(h, which, &rc);
+    return p ? (int64_t)p->total : (int64_t)rc;
+}
+
+int dimx_train_vq_param_info(dimx_handle h, int which, int i, const char** name, int64_t* offset, int64_t* numel) {
+    int rc;
+    TrainPlan* p = vq_plan_of(h, which, &rc);
+    if (!p) return rc;
+    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "train_vq_param_info: bad index");
+    *name = p->params[i].name.c_str();
+    *offset = p->params[i].off;
+    *numel = p->params[i].numel;
+    return DIMX_OK;
+}
+
+size_t dimx_train_vq_workspace_bytes(dimx_handle h, int B, int T) {
+    if (!h || B < 1 || T < 1) return 0;
+    const int which = h->vqg[1].in_dim == 56 ? 1 : 0;   // both slots of the 56-d geometry size alike
+    size_t need = 0;
+    if (vq_run(h, which, nullptr, nullptr, nullptr, B, T, 0.25f, 1.f, 0.f, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need) !=
+        DIMX_OK)
+        return 0;
+    return need;
+}
+
+int dimx_train_vq_forward_backward(dimx_handle h, int which, const float* params, float* grads, const float* x, int B, int T, float beta,
+                                   float quant_loss_weight, float dropout_p, uint64_t dropout_seed, int64_t step, float* loss_out,
+                                   float* pred_out, int32_t* idx_out, void* ws, size_t ws_bytes, void* stream) {
+    DIMX_REQUIRE(h && params && grads && x && loss_out && ws, DIMX_ERR_ARG, "train_vq: null argument");
+    DIMX_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)x % 16) == 0,
+                 DIMX_ERR_ARG, "train_vq: workspace must be 256-byte aligned, arenas / input 16-byte aligned");
+    DIMX_HIP(hipSetDevice(h->device));
+    {
+        size_t need = 0;
+        DIMX_TRY(vq_run(h, which, nullptr, nullptr, nullptr, B, T, beta, quant_loss_weight, dropout_p, dropout_seed, (long)step, nullptr,
+                        pred_out ? (float*)0x100 : nullptr, idx_out ? (int32_t*)0x100 : nullptr, nullptr, 0, nullptr, &need));
+        DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_vq: workspace %zu < required %zu (dimx_train_vq_workspace_bytes)", ws_bytes,
+                     need);
+    }
+    return vq_run(h, which, params, grads, x, B, T, beta, quant_loss_weight, dropout_p, dropout_seed, (long)step, loss_out, pred_out, idx_out,
+                  ws, ws_bytes, (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"

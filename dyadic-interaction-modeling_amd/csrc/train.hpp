@@ -114,4 +114,19 @@ int tr_grad_norm(const float* g, long n, float max_norm, float* part, float* nor
 int tr_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd, int step,
              const float* clip, hipStream_t s);
 
+// VQ-VAE training step (stage 1) glue (train_vq.hip)
+constexpr int kVqPart = 256;  // most per-block partials of the quantiser / L1 loss reductions
+int tr_pe_dropout_fwd(const float* a, const float* pe, float* y, int M, int n, int C, float p, uint64_t seed, long step, int site,
+                      hipStream_t s);
+int tr_dropout_bwd(float* dy, int M, int n, int C, float p, uint64_t seed, long step, int site, hipStream_t s);
+int tr_lrelu(float* y, long n, float slope, hipStream_t s);
+int tr_lrelu_bwd_out(const float* y, float* dy, long n, float slope, hipStream_t s);
+int tr_vq_book_prep(const float* book, float* Et, float* ee, hipStream_t s);
+int tr_vq_quant_fwd(const float* z, const float* book, const int32_t* idx, float* zst, float* part, int M, int* n_part, hipStream_t s);
+int tr_l1_loss(const float* pred, const float* x, float* dpred, float* part, long n, int* n_part, hipStream_t s);
+int tr_vq_finish(const float* part_q, int nq, const float* part_l, int nl, const int32_t* idx, int M, float beta, float qw, float* out4,
+                 hipStream_t s);
+int tr_vq_commit_bwd(const float* z, const float* book, const int32_t* idx, float* dz, int M, float coef, hipStream_t s);
+int tr_vq_book_grad(const float* z, const float* book, const int32_t* idx, float* dbook, int M, float coef, hipStream_t s);
+
 }  // namespace dimx

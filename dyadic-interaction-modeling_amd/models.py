@@ -5,7 +5,7 @@ parameter names and method signatures (reference ``code/models/__init__.py:1-17`
 The module owns ordinary ``nn.Parameter`` / buffer objects under the reference's key names, so
 ``state_dict()``, ``load_state_dict()``, ``.to()``, ``.eval()`` and ``.parameters()`` behave as usual;
 the packed device copy inside the engine is refreshed lazily whenever the parameters changed.
-Inference only: outputs carry no autograd graph (training is out of scope).
+Inference only: outputs carry no autograd graph; the VQ-VAE trains on its own HIP step (``dimx.train_hip.VqHipTrainer``).
 """
 import torch
 import torch.nn as nn

@@ -75,3 +75,48 @@ def integers(seed: int, name: str, shape, lo: int, hi: int) -> np.ndarray:
     n = int(np.prod(shape)) if len(shape) else 1
     r = raw_u64(seed, name, n) >> np.uint64(11)
     return (lo + (r % np.uint64(hi - lo)).astype(np.int64)).reshape(shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Dropout keep-mask of the VQ-VAE training step (csrc/train_vq.hip mirrors it bit for bit)
+# ---------------------------------------------------------------------------------------------------------------------
+DROPOUT_SITE_ENCODER = 0
+DROPOUT_SITE_DECODER = 1
+
+
+def dropout_key(seed: int, step: int, site: int) -> int:
+    """key(seed, step, site) = mix(seed + (2 step + site + 1) * GOLD) (mod 2^64)."""
+    z = (int(seed) + (2 * int(step) + int(site) + 1) * 0x9E3779B97F4A7C15) & _MASK
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK
+    return z ^ (z >> 31)
+
+
+def dropout_threshold(p: float) -> int:
+    """keep iff the 24-bit draw >= floor(p * 2^24), p taken as float32 (what the C-ABI receives)."""
+    return int(float(np.float32(p)) * 16777216.0)
+
+
+def dropout_keep(seed: int, step: int, site: int, shape, p: float) -> np.ndarray:
+    """Keep-mask [B,T,C] (bool) of Dropout(p) after the positional encoding of the VQ-VAE's encoder (site 0) or decoder
+    (site 1) in training step ``step``: element (b, t, c) is kept iff
+        (mix(key(seed, step, site) + (ctr + 1) * GOLD) >> 40) >= floor(p * 2^24),   ctr = (b * 65536 + t) * 512 + c,
+    mix = splitmix64's finaliser.  Counter-based: no state, any element can be regenerated alone (the backward pass keeps
+    nothing but (seed, step)).  Needs T <= 65536 and C <= 512."""
+    B, T, C = (int(s) for s in shape)
+    assert T <= 65536 and C <= 512
+    key = np.uint64(dropout_key(seed, step, site))
+    b = np.arange(B, dtype=np.uint64)[:, None, None]
+    t = np.arange(T, dtype=np.uint64)[None, :, None]
+    c = np.arange(C, dtype=np.uint64)[None, None, :]
+    with np.errstate(over="ignore"):
+        ctr = (b * np.uint64(65536) + t) * np.uint64(512) + c
+        r = _mix(key + (ctr + np.uint64(1)) * _GOLD)
+    return (r >> np.uint64(40)) >= np.uint64(dropout_threshold(p))
+
+
+def dropout_scale_mask(seed: int, step: int, site: int, shape, p: float):
+    """float32 multiplier [B,T,C]: keep / (1 - p) (torch.nn.Dropout's scaling), 0 where dropped."""
+    keep = dropout_keep(seed, step, site, shape, p)
+    scale = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+    return np.where(keep, scale, np.float32(0.0)).astype(np.float32)

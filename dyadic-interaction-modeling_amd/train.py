@@ -139,10 +139,29 @@ def _gelu_tanh(x):
     return x * (0.5 * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x * x * x))))
 
 
-def vq_decoder(P, pre, zq, heads, layers, pe):
+def _vq_blocks(P, net, h, heads, layers):
+    """``layers`` pre-LN {attention with packed qkv and scale hidden^-0.5, tanh-GELU MLP} blocks of the VQ-VAE's Transformer
+    (reference code/models/lib/base_models.py); net: the "...transformer.net." prefix."""
+    B, n, H = h.shape
+    for i in range(layers):
+        a = "%s%d.fn." % (net, 2 * i)
+        y = F.layer_norm(h, (H,), P[a + "norm.weight"], P[a + "norm.bias"], 1e-5)
+        q, k, v = F.linear(y, P[a + "fn.to_qkv.weight"]).view(B, n, 3, heads, H // heads).permute(2, 0, 3, 1, 4)
+        att = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * (H ** -0.5), dim=-1)
+        o = torch.matmul(att, v).transpose(1, 2).reshape(B, n, H)
+        h = h + F.linear(o, P[a + "fn.to_out.weight"], P[a + "fn.to_out.bias"])
+        m = "%s%d.fn." % (net, 2 * i + 1)
+        y = F.layer_norm(h, (H,), P[m + "norm.weight"], P[m + "norm.bias"], 1e-5)
+        y = _gelu_tanh(F.linear(y, P[m + "fn.l1.weight"], P[m + "fn.l1.bias"]))
+        h = h + F.linear(y, P[m + "fn.l2.weight"], P[m + "fn.l2.bias"])
+    return h
+
+
+def vq_decoder(P, pre, zq, heads, layers, pe, drop=None):
     """Differentiable TransformerDecoder of the listener VQ-VAE (reference code/models/stage1_BIWI.py:376-393): linear,
     Conv1d(k5, replicate) + LeakyReLU(0.2) + InstanceNorm over time, linear, + pe[batch row], ``layers`` pre-LN
-    {attention with packed qkv and scale hidden^-0.5, tanh-GELU MLP} blocks, bias-free output map.  zq [B,L,128]."""
+    {attention with packed qkv and scale hidden^-0.5, tanh-GELU MLP} blocks, bias-free output map.  zq [B,L,128].
+    drop: optional [B,L,hidden] multiplier of the PositionalEncoding's dropout (train mode; None = eval)."""
     B, n, _ = zq.shape
     c = pre + "decoder."
     h = F.linear(zq, P[c + "decoder_linear_embedding_pre.net.weight"], P[c + "decoder_linear_embedding_pre.net.bias"])
@@ -150,19 +169,55 @@ def vq_decoder(P, pre, zq, heads, layers, pe):
     h = F.instance_norm(F.leaky_relu(x, 0.2), eps=1e-5).transpose(1, 2)
     h = F.linear(h, P[c + "decoder_linear_embedding.net.weight"], P[c + "decoder_linear_embedding.net.bias"])
     h = h + pe[:B]
-    H = h.shape[-1]
-    for i in range(layers):
-        a = "%sdecoder_transformer.net.%d.fn." % (c, 2 * i)
-        y = F.layer_norm(h, (H,), P[a + "norm.weight"], P[a + "norm.bias"], 1e-5)
-        q, k, v = F.linear(y, P[a + "fn.to_qkv.weight"]).view(B, n, 3, heads, H // heads).permute(2, 0, 3, 1, 4)
-        att = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * (H ** -0.5), dim=-1)
-        o = torch.matmul(att, v).transpose(1, 2).reshape(B, n, H)
-        h = h + F.linear(o, P[a + "fn.to_out.weight"], P[a + "fn.to_out.bias"])
-        m = "%sdecoder_transformer.net.%d.fn." % (c, 2 * i + 1)
-        y = F.layer_norm(h, (H,), P[m + "norm.weight"], P[m + "norm.bias"], 1e-5)
-        y = _gelu_tanh(F.linear(y, P[m + "fn.l1.weight"], P[m + "fn.l1.bias"]))
-        h = h + F.linear(y, P[m + "fn.l2.weight"], P[m + "fn.l2.bias"])
+    if drop is not None:
+        h = h * drop
+    h = _vq_blocks(P, c + "decoder_transformer.net.", h, heads, layers)
     return F.linear(h, P[c + "vertice_map_reverse.weight"])
+
+
+def vq_encoder(P, pre, x, heads, layers, pe, drop=None):
+    """Differentiable TransformerEncoder of the VQ-VAE (reference code/models/stage1_BIWI.py:254-317, quant_factor 0):
+    Linear + LeakyReLU(0.2), Conv1d(k5, replicate) + LeakyReLU + InstanceNorm over time, linear, + pe[batch row] (then the
+    PositionalEncoding's dropout multiplier ``drop``), the pre-LN blocks, linear -> z [B,L,128]."""
+    B = x.shape[0]
+    c = pre + "encoder."
+    h = F.leaky_relu(F.linear(x, P[c + "vertice_mapping.0.weight"], P[c + "vertice_mapping.0.bias"]), 0.2)
+    y = F.conv1d(F.pad(h.transpose(1, 2), (2, 2), mode="replicate"), P[c + "squasher.0.0.weight"], P[c + "squasher.0.0.bias"])
+    h = F.instance_norm(F.leaky_relu(y, 0.2), eps=1e-5).transpose(1, 2)
+    h = F.linear(h, P[c + "encoder_linear_embedding.net.weight"], P[c + "encoder_linear_embedding.net.bias"])
+    h = h + pe[:B]
+    if drop is not None:
+        h = h * drop
+    h = _vq_blocks(P, c + "encoder_transformer.net.", h, heads, layers)
+    return F.linear(h, P[c + "encoder_linear_embedding_post.net.weight"], P[c + "encoder_linear_embedding_post.net.bias"])
+
+
+def vq_loss(P, x, masks=None, beta=0.25, quant_loss_weight=1.0, pre="", heads=8, layers=6, idx=None):
+    """Differentiable stage-1 step of the reference (code/train_vq.py:173-196): ``VQAutoEncoder.forward`` (encoder, quantiser
+    code/models/lib/quantizer.py:35-66, decoder on the straight-through latent) and ``calc_vq_loss`` (code/metrics/loss.py:6-11).
+    P: {key: tensor} of one VQ-VAE (keys ``pre + "encoder."...``, its pe buffers included); x [B,T,in_dim].  masks: None (eval,
+    no dropout) or (enc, dec) [B,T,hidden] dropout multipliers (dimx.prng.dropout_scale_mask).  idx: optional [B*T] code indices
+    to use instead of the argmin (a checker that follows another implementation's choice at a near tie).
+    Returns (loss, rec_loss, quant_loss, perplexity, pred [B,T,in_dim], idx [B*T])."""
+    B, T, _ = x.shape
+    m_enc, m_dec = masks if masks is not None else (None, None)
+    z = vq_encoder(P, pre, x, heads, layers, P[pre + "encoder.encoder_pos_embedding.pe"], m_enc)
+    E = P[pre + "quantize.embedding.weight"]
+    zf = z.reshape(-1, E.shape[1])
+    if idx is None:
+        with torch.no_grad():
+            d = torch.sum(zf ** 2, dim=1, keepdim=True) + torch.sum(E ** 2, dim=1) - 2 * torch.matmul(zf, E.t())
+            idx = torch.argmin(d, dim=1)
+    idx = idx.reshape(-1).long()
+    e = E[idx].view_as(z)
+    quant = beta * torch.mean((e.detach() - z) ** 2) + torch.mean((e - z.detach()) ** 2)
+    z_st = z + (e - z).detach()
+    with torch.no_grad():
+        e_mean = torch.bincount(idx, minlength=E.shape[0]).to(z.dtype) / idx.numel()
+        perplexity = torch.exp(-torch.sum(e_mean * torch.log(e_mean + 1e-10)))
+    pred = vq_decoder(P, pre, z_st, heads, layers, P[pre + "decoder.decoder_pos_embedding.pe"], m_dec)
+    rec = F.l1_loss(pred, x)
+    return quant_loss_weight * quant + rec, rec, quant, perplexity, pred, idx
 
 
 def legacy_loss(P, dims, vq_dims, x_speaker, z_l, v_listener, mask, pe, speaker_ids=None, listener_ids=None):

@@ -31,16 +31,7 @@ class HipTrainer:
         self.lr, self.betas, self.eps, self.weight_decay, self.clip = lr, betas, eps, weight_decay, clip
         self.lib = L.load()
         self.eng = model.engine(self.device)
-        h = self.eng.h
-        n = self.lib.dimx_train_num_params(h)
-        if n <= 0:
-            L.check(n, "dimx_train_num_params")
-        self.total = int(self.lib.dimx_train_total(h))
-        self.layout = []
-        for i in range(n):
-            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            L.check(self.lib.dimx_train_param_info(h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)), "train_param_info")
-            self.layout.append((name.value.decode(), int(off.value), int(numel.value)))
+        self.total, self.layout = self._arena_layout(self.eng.h)
         kw = dict(dtype=torch.float32, device=self.device)
         self.params = torch.zeros(self.total, **kw)
         self.grads = torch.zeros(self.total, **kw)
@@ -55,6 +46,18 @@ class HipTrainer:
         if ddist.world_size() > 1:                      # every rank starts from rank 0's parameters
             import torch.distributed as dist
             dist.broadcast(self.params, 0)
+
+    def _arena_layout(self, h):
+        """(floats per arena, [(name, offset, numel)]) of the step's flat arenas, as the library lays them out"""
+        n = self.lib.dimx_train_num_params(h)
+        if n <= 0:
+            L.check(n, "dimx_train_num_params")
+        layout = []
+        for i in range(n):
+            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
+            L.check(self.lib.dimx_train_param_info(h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)), "train_param_info")
+            layout.append((name.value.decode(), int(off.value), int(numel.value)))
+        return int(self.lib.dimx_train_total(h)), layout
 
     # ------------------------------------------------------------------ arena <-> module
     def _named(self):
@@ -373,3 +376,76 @@ class SlmHipTrainer(HipTrainer):
         self.all_reduce_grads()
         self.step()
         return total, d
+
+
+class VqHipTrainer(HipTrainer):
+    """The VQ-VAE's own training step (stage 1) on the HIP kernels: reference loop code/train_vq.py:173-196 -- out, quant_loss,
+    info = model(data); calc_vq_loss; AdamW(lr 1e-4, torch's default weight decay 0.01, no clipping) -- over every parameter of
+    ``dimx.models.VQAutoEncoder`` (encoder, decoder, codebook).  Forward AND backward run in libdimx_hip.so (csrc/train.hip
+    vq_run, csrc/train_vq.hip); the module's own encode / decode stay inference-only and see the trained weights after
+    ``sync_to_model()``.  ``dropout``: the PositionalEncoding's Dropout of the reference's train mode, with a counter-based keep
+    mask of (seed, step, site, b, t, c) (``dimx.prng.dropout_keep``) instead of torch's RNG; 0 = deterministic eval-mode step.
+    Same flat arenas, AdamW, optimiser-state import / export and gradient all-reduce as HipTrainer; ``dimx.train.vq_loss``
+    (PyTorch autograd) is its checker (tests/test_gpu_train_vq.py)."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=0.0, dropout=0.1, seed=20260928,
+                 beta=0.25, quant_loss_weight=1.0, device=None):
+        self.which = int(getattr(model, "which", 1))
+        self.prefix = "listener_vq." if self.which == 1 else "speaker_vq."
+        self.dropout, self.seed = float(dropout), int(seed)
+        self.beta, self.quant_loss_weight = float(beta), float(quant_loss_weight)
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip=clip, device=device)
+        self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def _arena_layout(self, h):
+        n = self.lib.dimx_train_vq_num_params(h, self.which)
+        if n <= 0:
+            L.check(n, "dimx_train_vq_num_params")
+        layout = []
+        for i in range(n):
+            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
+            L.check(self.lib.dimx_train_vq_param_info(h, self.which, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)),
+                    "dimx_train_vq_param_info")
+            layout.append((name.value.decode(), int(off.value), int(numel.value)))
+        return int(self.lib.dimx_train_vq_total(h, self.which)), layout
+
+    def _named(self):
+        # the library names the slot's tensors with their prefix (the handle holds both VQ-VAE slots); the module's are unprefixed
+        return {self.prefix + n: p for n, p in self.model.named_parameters()}
+
+    def graph_stats(self):
+        raise L.DimxError("the VQ-VAE step is launched kernel by kernel (no captured graph)")
+
+    def forward_backward(self, x, step=None, dropout=None):
+        """x [B,T,56] -> ({loss, rec_loss, quant_loss, perplexity} device scalars, pred [B,T,56], idx [B*T] int32); gradients in
+        ``self.grads``.  step: the dropout mask's step counter (default: optimiser steps taken so far); dropout: override p."""
+        x = x.to(self.device, torch.float32).contiguous()
+        B, T, _ = x.shape
+        need = int(self.lib.dimx_train_vq_workspace_bytes(self.eng.h, B, T))
+        if need == 0:
+            raise L.DimxError("dimx_train_vq_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
+        if need > self._ws_bytes:
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            self._ws_bytes = need
+        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
+        pred = torch.empty(B, T, x.shape[-1], dtype=torch.float32, device=self.device)
+        idx = torch.empty(B * T, dtype=torch.int32, device=self.device)
+        p = self.dropout if dropout is None else float(dropout)
+        L.check(self.lib.dimx_train_vq_forward_backward(
+            self.eng.h, self.which, L.ptr(self.params), L.ptr(self.grads), L.ptr(x), B, T, self.beta, self.quant_loss_weight, p,
+            self.seed, int(self.step_count if step is None else step), L.ptr(self._loss), L.ptr(pred), L.ptr(idx), ws,
+            self._ws.numel() - 256, L.stream_ptr(self.device)), "dimx_train_vq_forward_backward")
+        out = self._loss.clone()
+        d = {"loss": out[0], "rec_loss": out[1], "quant_loss": out[2], "perplexity": out[3]}
+        return d, pred, idx
+
+    def train_step(self, x):
+        """one optimisation step of the reference loop's body; returns (out, quant_loss, info) like ``model(data)`` there, info =
+        (perplexity, one-hot codes [B*T,512], idx [B*T,1]); the losses of the step are in ``self.last``."""
+        d, pred, idx = self.forward_backward(x)
+        self.all_reduce_grads()
+        self.step()
+        self.last = d
+        onehot = torch.zeros(idx.numel(), 512, dtype=torch.float32, device=self.device)
+        onehot.scatter_(1, idx.long()[:, None], 1.0)
+        return pred, d["quant_loss"], (d["perplexity"], onehot, idx.long()[:, None])

@@ -280,6 +280,26 @@ int dimx_train_slm_forward_backward(dimx_handle h, const float* params, float* g
                                     const int32_t* z_s, const int32_t* z_l, const float* codebook_s, const float* codebook_l,
                                     const float* pe_s, const float* pe_l, int B, int T, float* loss_out, void* ws, size_t ws_bytes,
                                     void* stream);
+/* The VQ-VAE's own training step (stage 1; reference loop code/train_vq.py:173-196 over VQAutoEncoder.forward,
+ * code/models/stage1_BIWI.py:10-137, and calc_vq_loss, code/metrics/loss.py:6-11).  Slot `which` of the handle: 0 = speaker_vq.,
+ * 1 = listener_vq. (VQAutoEncoder(which=...)); only the 56 / 384 / 8 x 48 / 128 geometry is built (anything else, e.g. the
+ * legacy 824-d speaker VQ-VAE: DIMX_ERR_ARG).  The arenas follow dimx_train_vq_param_info: every parameter of the slot --
+ * <prefix>encoder.*, <prefix>decoder.*, <prefix>quantize.embedding.weight (the pe buffers are not parameters; the step reads
+ * them from the loaded weights).  AdamW: dimx_train_adamw over the same arenas. */
+int dimx_train_vq_num_params(dimx_handle h, int which);
+int64_t dimx_train_vq_total(dimx_handle h, int which);   /* floats in an arena (tensors are 16-byte aligned inside it) */
+int dimx_train_vq_param_info(dimx_handle h, int which, int i, const char** name, int64_t* offset, int64_t* numel);
+size_t dimx_train_vq_workspace_bytes(dimx_handle h, int B, int T);
+/* One forward + backward pass over x [B,T,56] f32 (B clips of one length T, no padding): encoder -> z, idx = the inference argmin
+ * (dimx_vq_encode's kernel and summation order, over the arena's codebook), straight-through latent z + sg(e - z), decoder, L1
+ * reconstruction; loss = quant_loss_weight * quant_loss + rec, quant_loss = beta mean(sg(e) - z)^2 + mean(e - sg(z))^2.  grads
+ * is overwritten.  dropout_p: the Dropout after each positional encoding (0.1 in the reference's train mode, 0 = none); its keep
+ * mask is a counter-based function of (dropout_seed, step, site 0 = encoder / 1 = decoder, b, t, c), restated by
+ * dimx.prng.dropout_keep.  loss_out: 4 device floats {loss, rec_loss, quant_loss, perplexity}; pred_out optional [B,T,56];
+ * idx_out optional [B*T] int32.  Deterministic: a rerun is bit-identical. */
+int dimx_train_vq_forward_backward(dimx_handle h, int which, const float* params, float* grads, const float* x, int B, int T, float beta,
+                                   float quant_loss_weight, float dropout_p, uint64_t dropout_seed, int64_t step, float* loss_out,
+                                   float* pred_out, int32_t* idx_out, void* ws, size_t ws_bytes, void* stream);
 /* Gradient clipping (torch.nn.utils.clip_grad_norm_, max_norm <= 0: none) + one torch.optim.AdamW step over a flat arena.
  * step: 1-based step count (bias correction).  scratch: >= 1026 device floats; scratch[1024] = gradient norm before clipping,
  * scratch[1025] = the clip coefficient applied. */
