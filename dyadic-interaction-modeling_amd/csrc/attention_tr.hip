@@ -38,6 +38,10 @@ typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 constexpr float kNegT = -0x1p126f;  // a power of two: kNegT * scale2 is exact, so a fully masked row sees exp2(0) = 1 like attention.hip
+// the slots of a tile at or past the item's key count (the tail of its last tile; they repeat row Lk - 1) are not keys at all: a score
+// below kNegT gives them exp2(-huge) = 0 even in a fully masked row, which thus averages V over its kmax keys -- the reference's softmax
+// over -FLT_MAX scores -- and not over the tile's 64 slots
+constexpr float kNegX = -0x1p127f;
 
 // Fragment reads, results waited for inside the statement (see the header).
 __device__ __forceinline__ void lds_read_4x2_b128(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, u32x4_t (&lo)[4], u32x4_t (&hi)[4]) {
@@ -365,8 +369,14 @@ __global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const 
                         nb = nvis <= 0 ? 0 : nb;
                         vm &= nb >= 32 ? ~0u : ((1u << nb) - 1u);
                     }
+                    // slots below kmax (bit order = key order, the count as for the causal bound above)
+                    const int nvk = cur.kmax - j0 - 4 * half;
+                    int remk = nvk & 7;
+                    remk = remk < 4 ? remk : 4;
+                    const int nbk = nvk <= 0 ? 0 : 4 * (nvk >> 3) + remk;
+                    const uint32_t km = nbk >= 32 ? ~0u : ((1u << nbk) - 1u);
 #pragma unroll
-                    for (int i = 0; i < 32; ++i) sc[i] = ((vm >> i) & 1u) ? sc[i] : kNegT;
+                    for (int i = 0; i < 32; ++i) sc[i] = ((vm >> i) & 1u) ? sc[i] : (((km >> i) & 1u) ? kNegT : kNegX);
                 }
                 // (four independent chains each: one chain of 32 dependent instructions is what a wave with one partner on its
                 // SIMD cannot hide)

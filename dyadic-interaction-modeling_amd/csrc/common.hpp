@@ -207,6 +207,14 @@ template <bool FAST> __device__ __forceinline__ float wave_sum_sel(float v) { re
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// split-K count that leaves no split empty: the kernels give split i the k-tiles [i*per, (i+1)*per) with per = ceil(nk / sp), so a
+// count whose last split starts past nk (nk = 49, sp = 8: per = 7, 7 splits cover it) is lowered to the count that per really needs --
+// the same per, the same partition, and no slab the kernel would leave unwritten
+inline int splitk_nonempty(int nk, int sp) {
+    if (nk < 1 || sp < 1) return 1;
+    if (sp > nk) sp = nk;
+    return ceil_div(nk, ceil_div(nk, sp));
+}
 
 // ---------------------------------------------------------------- GEMM launcher
 struct OutSeg {

@@ -167,6 +167,7 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
     DIMX_REQUIRE((a.knew == nullptr) == (a.vnew == nullptr), DIMX_ERR_ARG, "decode_attn: knew/vnew mismatch");
     DIMX_REQUIRE(a.knew == nullptr || a.step != nullptr, DIMX_ERR_ARG, "decode_attn: self attention needs a step counter");
     DIMX_REQUIRE(a.Tmax <= kMaxKeys && a.n_keys <= kMaxKeys, DIMX_ERR_ARG, "decode_attn: more than %d keys", kMaxKeys);
+    DIMX_REQUIRE(a.knew != nullptr || a.n_keys >= 1, DIMX_ERR_ARG, "decode_attn: cross attention over %d keys", a.n_keys);
     if (a.rows_per_clip > 1) {
         // multi-sample cross attention: a.B = clips, rows = B * rows_per_clip
         DIMX_REQUIRE(a.knew == nullptr, DIMX_ERR_ARG, "decode_attn: rows_per_clip applies to cross attention only");

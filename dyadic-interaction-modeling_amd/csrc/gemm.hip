@@ -1659,11 +1659,14 @@ int gemm_plan_splits(const GemmArgs& a) {
         (void)gemm_x3_plan(a, &bn, &sp);
         return sp;
     }
-    if (a.force_splitk > 0) return a.force_splitk;
-    if (!a.allow_splitk) return 1;
     const int bk = a.in_dtype == DIMX_BF16 ? 64 : 32;
     const int kext = a.kloop ? a.kloop : a.ldw;
     if (a.conv_T != 0 || a.K % bk != 0 || a.K != kext || a.force_simple) return 1;  // register-staged kernel: no split
+    const int nk = kext / bk;
+    // every count returned below goes through splitk_nonempty: the launch runs the count planned here, and a split past the last
+    // k-tile would return without writing its slab (a forced count is clamped the same way)
+    if (a.force_splitk > 0) return splitk_nonempty(nk, a.force_splitk);
+    if (!a.allow_splitk) return 1;
     int cfg = a.cfg, bm, bn;
     if (cfg == 0) cfg = (long)ceil_div(a.M, 128) * ceil_div(a.N, 128) >= 512 ? 14 : 4;
     // f32 parity mode: tile AND split count must not depend on M (a rank's shard reproduces the whole batch's rows bit for bit):
@@ -1672,7 +1675,6 @@ int gemm_plan_splits(const GemmArgs& a) {
     if (a.cfg == 0 && gemm_use_ws72(a)) cfg = 72;
     cfg_tile(cfg, bm, bn);
     const int tiles = ceil_div(a.M, bm) * ceil_div(a.N, bn);
-    const int nk = kext / bk;
     if (a.in_dtype != DIMX_BF16) {
         // f32 (exact-f32 MFMA at the vector rate): a 64 x 64 tile's k-tile is 16 dependent 32x32x2 MFMAs per wave = 0.49 us of
         // matrix time (0.6 - 0.73 us measured with the hand-off) -- the block is MFMA-bound, two blocks on a CU take twice as
@@ -1699,7 +1701,7 @@ int gemm_plan_splits(const GemmArgs& a) {
                 best = sp;
             }
         }
-        return best;
+        return splitk_nonempty(nk, best);
     }
     if (tiles >= 256) return 1;
     if (cfg == 72) {
@@ -1710,7 +1712,7 @@ int gemm_plan_splits(const GemmArgs& a) {
         const int max_sp = nk / min_nk72 > 0 ? nk / min_nk72 : 1;
         sp = sp > max_sp ? max_sp : sp;
         sp = sp > 8 ? 8 : sp;
-        return sp < 1 ? 1 : sp;
+        return splitk_nonempty(nk, sp);
     }
     // measured (tools/bench_gemm.py under rocprofv3): ~288 blocks (one per CU + a few) is the sweet spot
     static const int target = getenv("DIMX_SPLIT_TARGET") ? atoi(getenv("DIMX_SPLIT_TARGET")) : 288;
@@ -1719,7 +1721,7 @@ int gemm_plan_splits(const GemmArgs& a) {
     const int max_sp = nk / min_nk > 0 ? nk / min_nk : 1;
     sp = sp > max_sp ? max_sp : sp;
     sp = sp > 8 ? 8 : sp;
-    return sp < 1 ? 1 : sp;
+    return splitk_nonempty(nk, sp);
 }
 
 static int gemm_cfg_small() {

@@ -275,8 +275,8 @@ struct X3 {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     int off = (r & 3) + 8 * (r >> 2);
-                    off = off < mrem ? off : (mrem > 0 ? mrem - 1 : 0);
-                    rv[r] = rptr[(size_t)off * ldr];
+                    off = off < mrem ? off : mrem - 1;   // rows past M read row M - 1 (row_base + mrem - 1), also when row_base >= M
+                    rv[r] = rptr[(long)off * ldr];   // off < 0 when row_base >= M: a row before row_base
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] += rv[r];
@@ -325,8 +325,8 @@ bool gemm_x3_plan(const GemmArgs& a, int* bn_out, int* sp_out) {
         if (a.N % bn != 0) continue;
         const int tiles = 2 * (a.N / bn);
         if (tiles > 256) continue;
-        int lo = 1, hi = a.out_slabs ? 8 : 1;
-        if (a.out_slabs && a.force_splitk > 0) lo = hi = a.force_splitk;
+        int lo = 1, hi = a.out_slabs && a.allow_splitk ? 8 : 1;   // without allow_splitk one slab (DIMX_F32_NO_SPLIT=1)
+        if (a.out_slabs && a.force_splitk > 0) lo = hi = splitk_nonempty(nk, a.force_splitk);   // forced: clamped, never an empty split
         for (int sp = lo; sp <= hi; ++sp) {
             if ((sp > lo && tiles * sp > 256) || sp > nk) break;
             const float cost = (float)(((nk + sp - 1) / sp) * ncb) + 0.5f * (float)sp + ((bn == 36 || bn == 72) ? 0.25f : 0.f);
@@ -351,7 +351,8 @@ bool gemm_use_x3(const GemmArgs& a) {
     if (a.nseg != 1 || a.seg[0].sd != 1 || a.seg[0].sh != 0 || a.seg[0].sb != a.seg[0].st * (long)a.rowT || a.rowadd_mode != 0) return false;
     if (((uintptr_t)a.w3 % 16) != 0 || (a.w3_plane * 2) % 16 != 0) return false;
     int bn, sp;
-    return gemm_x3_plan(a, &bn, &sp);
+    if (!gemm_x3_plan(a, &bn, &sp)) return false;
+    return a.act == ACT_NONE || sp == 1;   // the epilogue's activation applies to a whole sum, not to one slab's partial sum
 }
 
 int launch_gemm_x3(const GemmArgs& a0, hipStream_t s) {

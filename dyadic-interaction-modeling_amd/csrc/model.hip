@@ -2428,6 +2428,14 @@ int dimx_op_gemm_x3(const float* A, int lda, const void* planes, float* C, int l
     g.slab_stride = (long)M * ldc;
     g.force_splitk = (flags >> 16) & 0xff;
     gemm_set_plain_out(g, C, ldc);
+    if (act != 0 && g.out_slabs) {   // an activation applies to the whole sum, never to one split's partial sum
+        GemmArgs g1 = g;
+        g1.act = 0;
+        int bn = 0, sp = 1;
+        DIMX_REQUIRE(!(gemm_use_x3(g1) && gemm_x3_plan(g1, &bn, &sp) && sp > 1), DIMX_ERR_ARG,
+                     "op_gemm_x3: activation %d with %d split-K slabs (M=%d N=%d K=%d): an activation needs the unsplit sum", act, sp, M,
+                     N, K);
+    }
     DIMX_REQUIRE(planes && gemm_use_x3(g), DIMX_ERR_ARG, "op_gemm_x3: M=%d N=%d K=%d is not a shape of the split-bf16 kernel (K %% 32 == 0, "
                  "N a multiple of 36 / 64 / 72 / 96)", M, N, K);
     return launch_gemm_x3(g, (hipStream_t)stream);
@@ -2638,6 +2646,56 @@ int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, v
     a.scale = scale;
     a.q_f32 = q_is_f32 ? 1 : 0;
     a.nslab = 1;
+    return launch_decode_attn(a, (hipStream_t)stream);
+}
+
+/* every decode-attention form dimx_generate launches (tests): q / knew / vnew as the cache type or as nslab f32 split-K slabs,
+ * the self form reading this step's k / v at q + H*64 / q + 2*H*64 of each slab row, the cross form with a strided key mask,
+ * several query rows per clip and a forced wave count */
+int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
+                           void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
+                           const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream) {
+    const int S = rows_per_clip > 1 ? rows_per_clip : 1;
+    DIMX_REQUIRE(B > 0 && H > 0 && Tmax > 0, DIMX_ERR_ARG, "op_decode_attn_ex: empty shape");
+    DIMX_REQUIRE(nslab >= 1 && nslab <= 8 && (nslab == 1 || q_is_f32), DIMX_ERR_ARG, "op_decode_attn_ex: nslab=%d (1..8, > 1 for f32 q only)",
+                 nslab);
+    DIMX_REQUIRE(q_ld >= (self_attn ? 3 : 1) * H * 64 && o_ld >= H * 64, DIMX_ERR_ARG, "op_decode_attn_ex: q_ld=%d o_ld=%d too small",
+                 q_ld, o_ld);
+    DIMX_REQUIRE(nslab == 1 || slab_stride >= (long)B * S * q_ld, DIMX_ERR_ARG, "op_decode_attn_ex: slabs overlap (stride %ld)",
+                 slab_stride);
+    DIMX_REQUIRE(self_attn ? (step_dev != nullptr && kmask == nullptr && S == 1) : (n_keys >= 1 && n_keys <= Tmax), DIMX_ERR_ARG,
+                 "op_decode_attn_ex: self form needs a step counter (no mask, one row per clip); cross form 1 <= n_keys (%d) <= Tmax",
+                 n_keys);
+    DIMX_REQUIRE(kmask == nullptr || kmask_ld >= n_keys, DIMX_ERR_ARG, "op_decode_attn_ex: kmask_ld=%d < n_keys=%d", kmask_ld, n_keys);
+    DecodeAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dtype;
+    a.q = q;
+    a.q_ld = q_ld;
+    a.q_f32 = q_is_f32 ? 1 : 0;
+    a.nslab = nslab;
+    a.slab_stride = slab_stride;
+    if (self_attn) {
+        const size_t es = q_is_f32 ? 4 : dtype_size(dtype);
+        a.knew = (const unsigned char*)q + (size_t)H * 64 * es;
+        a.vnew = (const unsigned char*)q + (size_t)2 * H * 64 * es;
+        a.kv_ld = q_ld;
+        a.step = step_dev;
+    } else {
+        a.n_keys = n_keys;
+        a.kmask = kmask;
+        a.kmask_ld = kmask_ld;
+    }
+    a.kcache = kcache;
+    a.vcache = vcache;
+    a.Tmax = Tmax;
+    a.out = out;
+    a.o_ld = o_ld;
+    a.B = B;
+    a.H = H;
+    a.rows_per_clip = rows_per_clip;
+    a.scale = scale;
+    a.force_nsplit = nsplit;
     return launch_decode_attn(a, (hipStream_t)stream);
 }
 

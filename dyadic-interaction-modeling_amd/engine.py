@@ -474,3 +474,27 @@ def op_decode_attn(q, kcache, vcache, n_keys, scale, kmask=None, nsplit=0):
                                     L.stream_ptr(q.device)),
             "dimx_op_decode_attn")
     return out
+
+
+def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None, kmask_ld=None, rows_per_clip=1, nsplit=0,
+                      q_f32=None):
+    """Every form of the decode step's attention as dimx_generate launches it (include/dimx.h dimx_op_decode_attn_ex).
+    q: [R, q_ld] or f32 split-K slabs [nslab, R, q_ld] (R = B * rows_per_clip); kcache / vcache [B, H, Tmax, 64] (f32 or bf16).
+    step (int32 device scalar) selects the self form: q's rows hold q | k | v, k / v are appended at *step; otherwise the cross
+    form over n_keys keys with an optional kmask [B, kmask_ld] (uint8).  q_f32: q holds f32 slabs (default: q is f32)."""
+    lib = L.load()
+    B, H, Tmax, _ = kcache.shape
+    bf = kcache.dtype == torch.bfloat16
+    qs = q if q.dim() == 3 else q.unsqueeze(0)
+    nslab, R, q_ld = qs.shape
+    if q_f32 is None:
+        q_f32 = q.dtype == torch.float32
+    S = rows_per_clip if rows_per_clip > 1 else 1
+    out = torch.empty(R, H * 64, dtype=kcache.dtype, device=q.device)
+    L.check(lib.dimx_op_decode_attn_ex(L.BF16 if bf else L.F32, L.ptr(qs), q_ld, 1 if q_f32 else 0, nslab, qs.stride(0),
+                                       1 if step is not None else 0, L.ptr(kcache), L.ptr(vcache), L.ptr(out), H * 64, B, H, Tmax,
+                                       L.ptr(step), n_keys, L.ptr(kmask),
+                                       kmask_ld if kmask_ld is not None else (kmask.shape[1] if kmask is not None else 0),
+                                       S, float(scale), nsplit, L.stream_ptr(q.device)),
+            "dimx_op_decode_attn_ex")
+    return out

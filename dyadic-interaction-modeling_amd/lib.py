@@ -118,6 +118,9 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "dimx_op_decode_attn_self": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                          c_void_p, c_float, c_int, c_void_p]),
+    "dimx_op_decode_attn_ex": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int,
+                                       c_void_p]),
     "dimx_op_mlp_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dimx_mlp_fused_packed_bytes": (c_size_t, [c_int, c_int]),
     "dimx_mlp_fused_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),

@@ -337,7 +337,11 @@ int dimx_op_split_x3(const float* w, void* planes, long n, void* stream);
 int dimx_op_gemm_x3(const float* A, int lda, const void* planes, float* C, int ldc, int M, int N, int K, const float* bias, int act,
                     const float* residual, int ldr, int flags, void* stream);
 /* split-K slabs an out_slabs dimx_op_gemm call with these arguments writes (the f32 kernels plan the count from (N, K) themselves;
- * flags as in dimx_op_gemm: bit 0 allow split-K, bit 4 the split-bf16 kernel of the f32 parity mode, bits 16..23 a forced count) */
+ * flags as in dimx_op_gemm: bit 0 allow split-K (without it one slab, the split-bf16 kernel included), bit 4 the split-bf16 kernel
+ * of the f32 parity mode, bits 16..23 a forced count).  Every reported slab is written: a count that would leave a split without
+ * k-tiles (k-tiles nk, per = ceil(nk / count), (count - 1) * per >= nk) -- forced or planned -- is CLAMPED to ceil(nk / per), the
+ * count that covers the same partition, and this function reports the clamped value.  The split-bf16 kernel rejects an
+ * activation together with more than one slab (an activation of a partial sum). */
 int dimx_op_gemm_slabs(int in_dtype, int M, int N, int K, int flags);
 /* The cross-attention K/V projection as dimx_encode_ctx(for_generate=1) launches it: [M = B*rowT, K] . W[N, K]^T, the
  * N columns being nlayers x (K | V) segments of H*64 columns; segment i goes to the i-th [B, H, Tp, 64] cache inside
@@ -379,6 +383,19 @@ int dimx_op_fused_probe(const void* A, const void* W, const float* bias, void* C
  * appends k/v at position *step_dev and attends over *step_dev + 1 keys.  out [B, H*64] in the cache type. */
 int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, void* vcache, void* out, int B, int H,
                              int Tmax, const int32_t* step_dev, float scale, int q_is_f32, void* stream);
+/* Every form of the step kernel dimx_generate launches (tests), with all of its arguments:
+ *   q [nslab][B*S, q_ld] (slab s at q + s*slab_stride elements): f32 split-K slabs summed in slab order when q_is_f32 (nslab 1..8),
+ *     else one row array in the cache type (nslab 1); head h at column h*64.
+ *   self_attn = 1: the self form of dimx_op_decode_attn_self -- this step's k / v are columns H*64 / 2*H*64 of the same rows
+ *     (q_ld >= 3*H*64), appended at position *step_dev (< Tmax) of the caches, keys = *step_dev + 1; n_keys / kmask unused.
+ *   self_attn = 0: the cross form over 1 <= n_keys <= Tmax keys, kmask optional [B, kmask_ld] (kmask_ld >= n_keys, 0 = masked;
+ *     a row with every key masked averages V over the n_keys keys, as a softmax over -FLT_MAX scores does).
+ *   rows_per_clip S in {2,4,5,8,10} (cross form only): rows b*S .. b*S+S-1 of q / out share clip b's caches and mask row;
+ *     S x n_keys beyond the kernel's LDS score buffer is rejected.  0 / 1: one row per clip.
+ *   out [B*S, o_ld] in the cache type.  nsplit: waves per (clip, head), 1 / 2 / 4, 0 = automatic. */
+int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
+                           void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
+                           const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream);
 /* Decode-step residual + pre-norm: x[M,C] += sum_s slabs[s] (fixed order), y = LayerNorm(x) * gamma (no bias). */
 /* The prefill's fused feed-forward sublayer alone (csrc/mlp_fused.hip; unit parity): x [M,C] f32 on the device is replaced by
  * x + W2 . gelu(W1 . LayerNorm(x) + b1) + b2 with bf16 operands and f32 accumulation.  w1 [F,C], b1 [F] (or NULL), w2 [C,F] are HOST

@@ -179,3 +179,50 @@ def test_split_count_of_the_parity_modes_decode_gemms_depends_on_the_projection_
             counts = {lib.dimx_op_gemm_slabs(F32, M, N, K, flags) for M in (1, 4, 32, 64, 128, 200, 256)}
             assert len(counts) == 1 and 1 <= next(iter(counts)) <= 8, (N, K, flags, counts)
         assert lib.dimx_op_gemm_slabs(F32, 256, N, K, 16 | 5 | (3 << 16)) == 3        # a forced count is honoured
+
+
+def test_split_plans_never_leave_a_slab_empty():
+    """Split i of a split-K GEMM gets the k-tiles [i*per, (i+1)*per), per = ceil(nk / splits); a split that starts past nk returns
+    without writing its slab, and the consumer then sums uninitialised memory.  So every count dimx_op_gemm_slabs reports -- planned
+    or forced (clamped, include/dimx.h) -- satisfies (sp - 1) * ceil(nk / sp) < nk, for both kernels of the f32 parity mode, the bf16
+    kernels, with and without allow-split-K.  Without allow-split-K the split-bf16 plan is one slab (DIMX_F32_NO_SPLIT=1)."""
+    from dimx import lib as L
+    lib = L.load()
+    cdiv = lambda a, b: -(-a // b)
+    Ns = (2304, 1152, 768, 4608, 512, 1536, 72, 36)
+    Ms = (1, 4, 32, 64, 128, 200, 256)
+    for dt, bk, x3s in ((L.F32, 32, (0, 16)), (L.BF16, 64, (0,))):
+        for x3 in x3s:
+            for allow in (0, 1):
+                for force in range(0, 9):
+                    for K in range(bk, 8192 + 1, bk):
+                        nk = K // bk
+                        for N in Ns:
+                            for M in Ms:
+                                f = x3 | 4 | allow | (force << 16)
+                                sp = lib.dimx_op_gemm_slabs(dt, M, N, K, f)
+                                assert 1 <= sp <= 8 and sp <= nk and (sp - 1) * cdiv(nk, sp) < nk, (dt, x3, allow, force, N, K, M, sp)
+                                if force:   # a forced count is honoured or clamped to the count that covers the same partition
+                                    assert sp == cdiv(nk, cdiv(nk, min(force, nk))), (dt, x3, allow, force, N, K, M, sp)
+    for N, K in ((2304, 1152), (1152, 768), (768, 1152), (1152, 4608), (512, 1152), (1536, 512), (512, 2048)):
+        for M in Ms:
+            assert lib.dimx_op_gemm_slabs(L.F32, M, N, K, 16 | 4) == 1, (N, K, M)   # x3, split-K not allowed
+    # the cases that used to report an empty slab: forced 7 (5) at K = 1152 / 768 (512), the bf16 automatic plan at K = 3136
+    assert lib.dimx_op_gemm_slabs(L.F32, 256, 1152, 1152, 16 | 5 | (7 << 16)) == 6
+    assert lib.dimx_op_gemm_slabs(L.F32, 256, 1152, 512, 16 | 5 | (5 << 16)) == 4
+    assert lib.dimx_op_gemm_slabs(L.BF16, 64, 1152, 3136, 5) == 7
+
+
+def test_split_counts_of_the_decoder_projections_are_pinned():
+    """The decode step's planned slab counts (f32 parity mode: split-bf16 kernel and exact-f32 kernel; bf16 mode at B = 256 and 64)
+    are part of its numbers and speed; fixing the planner's empty-split cases must not move any of them."""
+    from dimx import lib as L
+    lib = L.load()
+    want = {  # (N, K): (x3, f32, bf16 M=256, bf16 M=64)
+        (2304, 1152): (3, 3, 2, 3), (1152, 768): (6, 3, 2, 2), (768, 1152): (8, 5, 3, 3), (1152, 4608): (7, 7, 4, 8),
+        (512, 1152): (8, 8, 3, 3), (1536, 512): (8, 8, 1, 1), (512, 2048): (8, 8, 5, 5), (4608, 1152): (2, 6, 1, 3),
+        (1152, 1152): (6, 3, 3, 3)}
+    for (N, K), (x3, f32, b256, b64) in want.items():
+        got = (lib.dimx_op_gemm_slabs(L.F32, 256, N, K, 16 | 5), lib.dimx_op_gemm_slabs(L.F32, 256, N, K, 5),
+               lib.dimx_op_gemm_slabs(L.BF16, 256, N, K, 5), lib.dimx_op_gemm_slabs(L.BF16, 64, N, K, 5))
+        assert got == (x3, f32, b256, b64), (N, K, got)

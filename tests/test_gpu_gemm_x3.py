@@ -94,3 +94,69 @@ def test_x3_slabs_sum_to_the_product_and_rows_do_not_depend_on_the_batch(dev, M,
     assert part.shape[0] == slabs.shape[0] and torch.equal(part, slabs[:, lo:hi])
     one = E.op_gemm_x3(a[lo:lo + 1].contiguous(), w, slabs=True)
     assert torch.equal(one, slabs[:, lo:lo + 1])
+
+
+@pytest.mark.parametrize("M", [1, 4, 37, 129, 200])
+def test_x3_residual_at_ragged_rows(dev, M):
+    """M not a multiple of the 128-row tile: the epilogue's residual reads are clamped to row M - 1 (rows past M are not stored)"""
+    from dimx import engine as E
+    N, K = 1152, 768
+    a, w = _rand((M, K), dev, 40 + M), _rand((N, K), dev, 41, K ** -0.5)
+    bias, res = _rand((N,), dev, 42), _rand((M, N), dev, 43 + M)
+    out = E.op_gemm_x3(a, w, bias, 0, res)
+    ref = a.double() @ w.double().t() + bias.double() + res.double()
+    scale = (a.double().abs() @ w.double().abs().t()).max().item()
+    assert torch.isfinite(out).all()
+    assert (out.double() - ref).abs().max().item() / scale < 3e-7
+
+
+def _slab_sum(slabs):
+    total = slabs[0].clone()
+    for s in range(1, slabs.shape[0]):
+        total += slabs[s]
+    return total
+
+
+def test_forced_and_planned_split_counts_write_every_slab(dev):
+    """A split count whose last split would start past K used to leave its slab unwritten: x3 forced to 7 splits at K = 1152 (36
+    k-tiles: per 6, 6 splits), and the bf16 kernel's automatic plan at K = 3136 (49 k-tiles: 8 planned, per 7).  The plan is
+    clamped and reported (include/dimx.h): every reported slab is written and the slabs sum to the product."""
+    from dimx import engine as E
+    from dimx import lib as L
+    lib = L.load()
+    M, N, K = 256, 1152, 1152
+    a, w = _rand((M, K), dev, 50), _rand((N, K), dev, 51, K ** -0.5)
+    planes = E.op_split_x3(w)
+    flags = 4 | (7 << 16)
+    ns = lib.dimx_op_gemm_slabs(L.F32, M, N, K, 16 | 1 | flags)
+    assert ns == 6
+    out = torch.full((ns, M, N), float("nan"), device=dev)
+    L.check(lib.dimx_op_gemm_x3(L.ptr(a), K, L.ptr(planes), L.ptr(out), N, M, N, K, None, 0, None, 0, flags, L.stream_ptr(dev)), "x3")
+    ref = a.double() @ w.double().t()
+    scale = (a.double().abs() @ w.double().abs().t()).max().item()
+    assert torch.isfinite(out).all() and (_slab_sum(out).double() - ref).abs().max().item() / scale < 3e-7
+    # bf16 kernel, automatic plan
+    M, N, K = 64, 1152, 3136
+    ab, wb = _rand((M, K), dev, 52).bfloat16(), _rand((N, K), dev, 53, K ** -0.5).bfloat16()
+    ns = lib.dimx_op_gemm_slabs(L.BF16, M, N, K, 5)
+    assert ns == 7
+    out = torch.full((ns, M, N), float("nan"), device=dev)
+    L.check(lib.dimx_op_gemm(L.BF16, L.F32, L.ptr(ab), K, L.ptr(wb), K, L.ptr(out), N, M, N, K, None, 0, None, 0, 0, None, 5,
+                             L.stream_ptr(dev)), "gemm")
+    ref = ab.double() @ wb.double().t()
+    scale = (ab.double().abs() @ wb.double().abs().t()).max().item()
+    assert torch.isfinite(out).all() and (_slab_sum(out).double() - ref).abs().max().item() / scale < 1e-6
+
+
+def test_x3_activation_with_slabs_is_rejected(dev):
+    """An activation applies to the whole sum: with more than one split-K slab the x3 kernel refuses it"""
+    from dimx import engine as E
+    from dimx import lib as L
+    M, N, K = 256, 1152, 768
+    a, w = _rand((M, K), dev, 60), _rand((N, K), dev, 61, K ** -0.5)
+    assert L.load().dimx_op_gemm_slabs(L.F32, M, N, K, 16 | 5) > 1
+    with pytest.raises(L.DimxError):
+        E.op_gemm_x3(a, w, act=3, slabs=True)
+    out = E.op_gemm_x3(a, w, act=3)                   # no slabs: one pass, the activation applies
+    ref = ACTS[3](a.double() @ w.double().t())
+    assert (out.double() - ref).abs().max().item() < 1e-5

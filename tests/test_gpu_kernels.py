@@ -167,7 +167,7 @@ def test_conv5_gemm(dev, B, T, lens, bf16):
         assert e < (3e-3 if bf16 else 5e-5), "conv err %g (clip %d)" % (e, b)
 
 
-@pytest.mark.parametrize("C", [384, 1152])
+@pytest.mark.parametrize("C", [384, 512, 768, 1152])
 @pytest.mark.parametrize("use_beta", [True, False])
 def test_layernorm(dev, C, use_beta):
     from dimx import engine
