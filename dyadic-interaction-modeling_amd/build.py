@@ -21,8 +21,6 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # per-source additions: beside MFMAs the SLP vectoriser's v_pk_add_f32 / v_pk_mul_f32 cost more than the two scalar instructions
 # they replace (MI355X_MICROARCH.md, price of one filler beside MFMAs)
 SRC_FLAGS = {"attention_tr.hip": ["-fno-slp-vectorize"]}
-if os.environ.get("DIMX_TUNING"):   # also instantiate the measured-dead-end GEMM configurations (A/B runs; use --force)
-    FLAGS.append("-DDIMX_GEMM_TUNING")
 
 
 def _hipcc():

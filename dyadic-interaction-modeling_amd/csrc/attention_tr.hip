@@ -10,13 +10,14 @@
 // (profiles/r04_attn_*): a block that only loads Q and two tiles and exits costs 92 us at 6144 blocks -- the price is the
 // per-block launch + first-byte latency, not the arithmetic -- and a tile step whose next tile is requested one step ahead
 // waits 1.5 - 2.3 us for it whatever the step computes.  Hence:
-//   * PERSISTENT blocks (2 per CU, 4 waves x 32 queries = one 128-query item at a time) walk the (clip, head) pairs; nothing
+//   * PERSISTENT blocks (3 per CU, 4 waves x 32 queries = one 128-query item at a time) walk the (clip, head) pairs; nothing
 //     is ever requested and then waited for in the same breath: K / V tiles travel global -> LDS by LDS-DMA (global_load_lds,
-//     16 B per lane, the XOR swizzle applied to the SOURCE chunk) into a FOUR-slot ring, three tiles ahead of the one being
+//     16 B per lane, the XOR swizzle applied to the SOURCE chunk) into a two-slot ring, one tile ahead of the one being
 //     multiplied, across item boundaries; the next item's Q rows land in the wave's own LDS rows while the current item runs;
-//     the end-of-step wait is a COUNTED vmcnt (only the next tile must have landed; the two younger tiles, the next item's Q rows
-//     and the last item's output stores stay in flight); key masks arrive as 64-bit validity words through the scalar cache
-//     (a pack kernel ahead of the launch), clip lengths an item ahead;
+//     the end-of-step wait is a COUNTED vmcnt (only the next tile must have landed; the next item's Q rows and the last item's
+//     output stores stay in flight); key masks arrive as 64-bit validity words through the scalar cache (a pack kernel ahead
+//     of the launch), clip lengths an item ahead.  (A four-slot ring three tiles ahead at 2 blocks per CU hid the memory side
+//     but lost a third of the waves: docs/DESIGN_HISTORY.md, round 4.);
 //   * every LDS read is inline asm: behind a C++ LDS access hipcc waits vmcnt(0) -- it cannot tell the read from the DMA in
 //     flight -- which would park every wave until the youngest tile has landed;
 //   * V is staged row-major exactly like K and read as the A operand of O^T = V^T . P^T with gfx950's transposing LDS read
@@ -25,8 +26,6 @@
 //   * the 64^-0.5 log2(e) scale is folded into the exponent's fma, D = 48 contracts over 3 k-steps instead of a padded 4,
 //     waves above the causal diagonal skip the tile, masked tiles test one validity word per lane, the output leaves as
 //     16-byte stores (v_permlane32_swap pairs the two lane halves' 8-byte pieces).
-#include <stdlib.h>
-
 #include "common.hpp"
 
 namespace dimx {
@@ -124,10 +123,11 @@ struct AttnItem {
 };
 
 
-// DH: head width (48 / 64).  4 waves x 32 queries per item, persistent blocks (2 per CU).
+// DH: head width (48 / 64).  4 waves x 32 queries per item, persistent blocks (3 per CU).
 // kRing tile slots: one being multiplied, kRing - 1 landing; 160 KiB / (16 KiB kRing + 16 KiB) blocks per CU.
-template <int DH, int kRing>
-__global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const AttnArgs a, const int nqb, const int32_t* __restrict__ lens,
+constexpr int kRing = 2;
+template <int DH>
+__global__ __launch_bounds__(256, 3) void attn_tr_kernel(const AttnArgs a, const int nqb, const int32_t* __restrict__ lens,
                                                          const unsigned long long* __restrict__ kwords, const int nwords) {
     constexpr int NW = 4;
     constexpr int CR = DH / 8;                     // 16-byte chunks per q / k / v row
@@ -254,11 +254,11 @@ __global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const 
     const float scale2 = a.scale * 1.4426950408889634f;
 
     if (pair_of(0) < 0) return;
-    // ---- the two walkers over the block's (item, tile) sequence: `pf` requests tiles, three steps ahead of the one that computes
+    // ---- the two walkers over the block's (item, tile) sequence: `pf` requests tiles, kRing - 1 steps ahead of the one that computes
     int pf_k = 0, pf_tile = 0;
     int pf_len_next = len_of(pair_of(1));
     AttnItem pf = make_item(0, len_of(pair_of(0)));
-    int gstep = 0;                                     // tiles computed so far (ring slot = step & 3)
+    int gstep = 0;                                     // tiles computed so far (ring slot = step & (kRing - 1))
     int issued = 0;                                    // tiles requested so far
     // Counted waits.  n_ops = vector-memory operations this wave has issued (an UNDER-count is safe: it only makes a wait
     // stricter); pos1 / pos2 / pos3 = n_ops right after the request of the tile one / two / three steps ahead (-1: none).
@@ -324,10 +324,10 @@ __global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const 
                 kw_next = key_word(cur, tile + 1);
             else if (nxt.pair >= 0)
                 kw_next = key_word(nxt, 0);
-            // ---- request the tile three steps ahead into the slot every wave left at the last barrier
-            pos[kRing - 2] = (a.dbg & 1) ? -1 : request_next_tile();
+            // ---- request the tile kRing - 1 steps ahead into the slot every wave left at the last barrier
+            pos[kRing - 2] = request_next_tile();
             const bool on = wave_on && (!a.causal || j0 <= qlast);
-            if (on && !(a.dbg & 8)) {
+            if (on) {
                 // ---- S^T = K . Q^T
                 u32x4_t kf[2][4];
                 const uint32_t kb = kaddr + so;
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const 
                         float p[8];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            p[e] = (a.dbg & 2) ? sc[16 * kt + 8 * s + e] : __builtin_amdgcn_exp2f(__builtin_fmaf(sc[16 * kt + 8 * s + e], scale2, nm));
+                            p[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[16 * kt + 8 * s + e], scale2, nm));
                             ps4[e & 3] += p[e];
                         }
                         pk[kt][s] = u32x4_t{pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]), pack_bf16x2(p[4], p[5]),
@@ -416,7 +416,6 @@ __global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const 
                 l_run += (ps4[0] + ps4[1]) + (ps4[2] + ps4[3]);
 
                 // ---- O^T += V^T . P^T (one output block's eight transposing reads, then its four matrix instructions)
-                if (!(a.dbg & 4))
 #pragma unroll
                 for (int blk = 0; blk < 2; ++blk) {
                     u32x2_t t[8];
@@ -440,7 +439,7 @@ __global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const 
                 if (last_tile && nxt.pair >= 0 && n_ops - qpos < allow) allow = n_ops - qpos;
                 wait_vm_at_most(allow);
             }
-            if (!(a.dbg & 16)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             ++gstep;
             pos[0] = pos[1];
             pos[1] = pos[2];
@@ -466,12 +465,12 @@ __global__ __launch_bounds__(256, kRing == 2 ? 3 : 2) void attn_tr_kernel(const 
                     uint32_t y1 = pack_bf16x2(ot[blk][4 * g + 6] * inv, ot[blk][4 * g + 7] * inv);
                     const auto r0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
                     const auto r1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-                    if (qi < a.Lq && !(a.dbg & 32)) *(u32x4_t*)(orow + 32 * blk + 16 * gp + 8 * half) = u32x4_t{r0[0], r1[0], r0[1], r1[1]};
+                    if (qi < a.Lq) *(u32x4_t*)(orow + 32 * blk + 16 * gp + 8 * half) = u32x4_t{r0[0], r1[0], r0[1], r1[1]};
                 }
             }
         // the stores are younger than everything requested so far (a wave without a valid query issues none; under-counting what
         // may stay in flight is safe, over-counting is not)
-        if (wave_on && !(a.dbg & 32)) n_ops += NST;
+        if (wave_on) n_ops += NST;
         if (nxt.pair < 0) break;
         cur = nxt;
         ++k_item;
@@ -491,12 +490,7 @@ int launch_pack_key_words(const uint8_t* kmask, int kmask_ld, const int32_t* len
 }
 
 // bf16, D in {48, 64}, q / k / v row-major with 16-byte aligned rows.  Returns DIMX_OK after launching.
-int launch_attention_tr(const AttnArgs& a_in, hipStream_t s) {
-    static const int dbg = getenv("DIMX_ATTN_DBG") ? atoi(getenv("DIMX_ATTN_DBG")) : 0;   // ablations (tools/bench_attn.py)
-    static const int blocks_per_cu = getenv("DIMX_ATTN_BPC") ? atoi(getenv("DIMX_ATTN_BPC")) : 0;
-    static const int ring = getenv("DIMX_ATTN_RING") ? atoi(getenv("DIMX_ATTN_RING")) : 2;
-    AttnArgs a = a_in;
-    a.dbg = dbg;
+int launch_attention_tr(const AttnArgs& a, hipStream_t s) {
     DIMX_REQUIRE(a.dtype == DIMX_BF16 && (a.D == 48 || a.D == 64) && a.v_rows, DIMX_ERR_ARG, "attention_tr: bf16, D 48 / 64, row-major V");
     DIMX_REQUIRE(a.q_st % 8 == 0 && a.k_st % 8 == 0 && a.v_st % 8 == 0 && a.o_st % 8 == 0 && a.q_sh % 8 == 0 && a.k_sh % 8 == 0 &&
                      a.v_sh % 8 == 0 && a.o_sh % 8 == 0 && a.q_sb % 8 == 0 && a.k_sb % 8 == 0 && a.v_sb % 8 == 0 && a.o_sb % 8 == 0,
@@ -523,23 +517,16 @@ int launch_attention_tr(const AttnArgs& a_in, hipStream_t s) {
                                nwords, a.kwords);
         kwords = a.kwords;
     }
-    // persistent blocks, 2 per CU (80 KiB of LDS each): each walks (clip, head) pairs g, g + grid, ...
+    // persistent blocks, 3 per CU (48 KiB of LDS each): each walks (clip, head) pairs g, g + grid, ...
     const int items = a.B * a.H * nqb;
-    const int cap_blocks = n_cu * (blocks_per_cu > 0 ? blocks_per_cu : (ring == 2 ? 3 : 2));
+    const int cap_blocks = n_cu * 3;
     int nblk = items < cap_blocks ? items : cap_blocks;
     nblk = (nblk + 7) / 8 * 8;                       // the same number of blocks on every XCD
     dim3 grid(nblk), block(256);
-    if (ring == 2) {
-        if (a.D == 48)
-            hipLaunchKernelGGL((attn_tr_kernel<48, 2>), grid, block, 0, s, a, nqb, a.lens, kwords, nwords);
-        else
-            hipLaunchKernelGGL((attn_tr_kernel<64, 2>), grid, block, 0, s, a, nqb, a.lens, kwords, nwords);
-    } else {
-        if (a.D == 48)
-            hipLaunchKernelGGL((attn_tr_kernel<48, 4>), grid, block, 0, s, a, nqb, a.lens, kwords, nwords);
-        else
-            hipLaunchKernelGGL((attn_tr_kernel<64, 4>), grid, block, 0, s, a, nqb, a.lens, kwords, nwords);
-    }
+    if (a.D == 48)
+        hipLaunchKernelGGL((attn_tr_kernel<48>), grid, block, 0, s, a, nqb, a.lens, kwords, nwords);
+    else
+        hipLaunchKernelGGL((attn_tr_kernel<64>), grid, block, 0, s, a, nqb, a.lens, kwords, nwords);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

@@ -235,11 +235,6 @@ __device__ __forceinline__ void reduce_store_ln(const f32x16_t (&acc)[NCB], floa
     }
 }
 
-#define CHAIN_STAMP(i)                                                            \
-    do {                                                                          \
-        if (a.prof && threadIdx.x == 0) a.prof[blockIdx.x * 16 + (i)] = wall_clock64(); \
-    } while (0)
-
 // block barrier that orders LDS traffic only: it must NOT drain vmcnt (the loader waves have weight DMAs in flight)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -274,7 +269,6 @@ __global__ __launch_bounds__(kThreads) void xcd_chain_kernel(const ChainArgs a) 
     unsigned* ctr = a.counters + 16 * g;
     unsigned target = (unsigned)(*a.step) * (unsigned)(a.nbar * kGroupCUs);
 
-    CHAIN_STAMP(0);
     // ---- row waves: everything of the CU's own row that is already there goes into registers now (x, gamma, the
     // split-K slabs of a preceding chip-wide GEMM, all loads in flight together); only xr has to wait for barrier 1
     const bool own = !DEFER && li < nrows && wave < 4;
@@ -333,24 +327,20 @@ __global__ __launch_bounds__(kThreads) void xcd_chain_kernel(const ChainArgs a) 
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        CHAIN_STAMP(1);
         f32x16_t acc[NCB1];
 #pragma unroll
         for (int j = 0; j < NCB1; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         mfma_panel<NCB1>(lds + a.offA1, lds + a.offW1, a.g1.nkt, a.g1.rows_pad, acc, wave, lane);
-        CHAIN_STAMP(2);
         if (DEFER) {
             reduce_store_defer<NCB1>(acc, (float*)(lds + a.offRed1), xs, a.x, (bf16*)a.y, C,
                                      a.stats + ((size_t)(g * kGroupCUs + li) * kGroupRows) * 2, row0, nrows, n0, a.g1.cols, wave,
                                      lane);
-            CHAIN_STAMP(3);
             if (tid == 0 && seen_old == stamp) atomicOr(a.err, 1u);
             if (!HAS_G2) return;  // x, y and the partial sums are complete at the end of the launch: no group barrier
         } else {
             reduce_store<NCB1>(acc, (float*)(lds + a.offRed1), a.xr, a.C, row0, nrows, n0, a.g1.cols, wave, lane);
-            CHAIN_STAMP(3);
         }
         target += kGroupCUs;
         if (DEFER) {
@@ -380,7 +370,6 @@ __global__ __launch_bounds__(kThreads) void xcd_chain_kernel(const ChainArgs a) 
         } else {
             xcd_barrier(ctr, target, a.err);
         }
-        CHAIN_STAMP(4);
     }
     if (DEFER) {
         // ---- deferred form, after the only group barrier: the un-normalised rows of the group, the 32 x 32 partial sums ->
@@ -407,17 +396,14 @@ __global__ __launch_bounds__(kThreads) void xcd_chain_kernel(const ChainArgs a) 
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        CHAIN_STAMP(7);
         f32x16_t acc[NCB2];
 #pragma unroll
         for (int j = 0; j < NCB2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         mfma_panel<NCB2>(lds + a.offA2, lds + a.offW2, a.g2.nkt, a.g2.rows_pad, acc, wave, lane);
-        CHAIN_STAMP(8);
         reduce_store_ln<NCB2>(acc, (float*)(lds + a.offRed2), a.out2, a.ld_out2, row0, nrows, li * a.g2.cols, a.g2.cols, sm_mr,
                               a.colsum2, wave, lane);
-        CHAIN_STAMP(9);
         return;
     }
 
@@ -471,7 +457,6 @@ __global__ __launch_bounds__(kThreads) void xcd_chain_kernel(const ChainArgs a) 
             }
         }
     }
-    CHAIN_STAMP(5);
     if (tid == 0 && seen_old == stamp) atomicOr(a.err, 1u);  // two blocks claimed the same (XCD, slot): not a bijection
     if (!HAS_G2) return;
     // group barrier 2: only the row waves have stores to drain; the loader waves keep their DMAs in flight
@@ -491,14 +476,12 @@ __global__ __launch_bounds__(kThreads) void xcd_chain_kernel(const ChainArgs a) 
         }
     }
     lds_barrier();
-    CHAIN_STAMP(6);
 
     // ---- second projection on the normalised rows of the whole group (written by 32 CUs of this XCD: sc1)
     {
         issue_panel<AUX_SC1>((const bf16*)a.y, a.C, row0, r_last, kGroupRows, a.g2.nkt, lds + a.offA2, wave, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the rows, and on waves 4-7 the weight slice
         __syncthreads();
-        CHAIN_STAMP(7);
         f32x16_t acc[NCB2];
 #pragma unroll
         for (int j = 0; j < NCB2; ++j)
@@ -506,9 +489,7 @@ __global__ __launch_bounds__(kThreads) void xcd_chain_kernel(const ChainArgs a) 
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         mfma_panel<NCB2>(lds + a.offA2, lds + a.offW2, a.g2.nkt, a.g2.rows_pad, acc, wave, lane);
         const int n0 = li * a.g2.cols;
-        CHAIN_STAMP(8);
         reduce_store<NCB2>(acc, (float*)(lds + a.offRed2), a.out2, a.ld_out2, row0, nrows, n0, a.g2.cols, wave, lane);
-        CHAIN_STAMP(9);
     }
 }
 
@@ -679,12 +660,10 @@ __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerCha
     // ---- stage 1: self attention of this CU's clip; wave 12 requests the out-projection's weight slice meanwhile
     if (wave == kAttnWaves) {
         const int n0 = li * a.g_so.cols;
-        if (!(a.abl & 1))
         issue_panel_nw<AUX_PLAIN, 1>((const bf16*)a.g_so.W, a.g_so.ldw, n0, n0 + a.g_so.cols - 1, a.g_so.rows_pad, a.g_so.nkt, base + a.off_W1, 0,
                                      lane);
     } else if (has_clip) {
-        const int aclip = (a.perm && nrows == kGroupRows) ? row0 + ((li + wave) & (kGroupRows - 1)) : clip;
-        decode_attn_body<bf16, true, true, 1, kAttnWaves>(a.sa, aclip, sc, a.sc_stride, nullptr, nullptr, nullptr);
+        decode_attn_body<bf16, true, true, 1, kAttnWaves>(a.sa, clip, sc, a.sc_stride, nullptr, nullptr, nullptr);
     }
     LAYER_STAMP(1);
     target += kGroupCUs;
@@ -723,7 +702,6 @@ __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerCha
     layer_barrier(ctr, target, a.err, [&] {  // the cross-q weight slice goes out between the arrival and the wait, from EVERY wave:
         // one wave issuing its 54 pieces kept the whole block at the closing block barrier for ~2.5 us (profiles/r05_layer_kernel.txt)
         const int n2 = li * a.g_cq.cols;
-        if (!(a.abl & 1))
         issue_panel_nw<AUX_PLAIN, kLayerWaves>((const bf16*)a.g_cq.W, a.g_cq.ldw, n2, n2 + a.g_cq.cols - 1, a.g_cq.rows_pad, a.g_cq.nkt,
                                                base + a.off_W2, wave, lane);
     });
@@ -772,12 +750,10 @@ __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerCha
                                          // LDS traffic starts (behind a possibly pending one it would drain vmcnt in the key loop)
     if (wave == kAttnWaves) {
         const int n0 = li * a.g_co.cols;
-        if (!(a.abl & 1))
         issue_panel_nw<AUX_PLAIN, 1>((const bf16*)a.g_co.W, a.g_co.ldw, n0, n0 + a.g_co.cols - 1, a.g_co.rows_pad, a.g_co.nkt, base + a.off_W3, 0,
                                      lane);
     } else if (has_clip) {
-        const int aclip = (a.perm && nrows == kGroupRows) ? row0 + ((li + wave) & (kGroupRows - 1)) : clip;
-        decode_attn_body<bf16, false, true, 1, kAttnWaves, true>(a.ca, aclip, sc, a.sc_stride, nullptr, nullptr, nullptr);
+        decode_attn_body<bf16, false, true, 1, kAttnWaves, true>(a.ca, clip, sc, a.sc_stride, nullptr, nullptr, nullptr);
     }
     LAYER_STAMP(9);
     target += kGroupCUs;

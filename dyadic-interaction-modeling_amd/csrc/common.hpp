@@ -262,7 +262,6 @@ struct GemmArgs {
                        // reduction by the consumer kernel); requires act none, no residual/rowadd, plain output
     long slab_stride;  // elements between slabs
     int stage_out;     // set by the launcher: large-M outputs leave through LDS as 8/16-byte row-contiguous pieces
-    unsigned long long* prof;  // tuning only (tools/gemm_phases.py): per-block wall-clock stamps, ABL = 3 instantiation
     // deferred LayerNorm of the A operand (gemm_ws_kernel only; see ChainArgs.defer): A holds bf16(x) un-normalised, W the
     // gamma-scaled weights; acc <- rstd[m] * (acc - mean[m] * ln_colsum[n]) before bias / activation.  ln_stats =
     // [M / 32][32][32][2] per-slice {sum x, sum (x - slice mean)^2}, 32 equal column slices of ln_C columns.
@@ -278,8 +277,6 @@ struct GemmArgs {
     long w3_plane;     // GEMM of the DECODE STEP (x3_decode) runs on the bf16 matrix cores, f32-equivalent (gemm_x3_kernel).  Elements between planes.
     int x3_decode;     // set by the decode step (dimx_generate) and by dimx_op_gemm_x3 only: the kernel choice must not depend on M -- a
                        // rank's shard of a batch reproduces the rows of the whole batch bit for bit whatever the batch size
-    int tile_map;      // set by the launcher (prefill): 1 = every XCD works on one half of the N tiles of a quarter of the
-                       // M tiles, so that its share of W (N/2 x K) stays L2-resident while the A panels stream through
     int vt_pack4;      // set by the launcher: transposed (time-contiguous) segments take 4 packed rows per store
 };
 
@@ -287,8 +284,6 @@ void gemm_args_init(GemmArgs& a);
 // plain row-major output helper
 void gemm_set_plain_out(GemmArgs& a, void* C, int ldc);
 int launch_gemm(const GemmArgs& a, hipStream_t s);
-// true when small-M GEMMs run on the loader/consumer kernel, the only one with the deferred-LayerNorm epilogue (ln_stats)
-bool gemm_decode_has_ln_epilogue();
 // the 256 x 256 phase-pipelined prefill kernel (gemm256.hip): taken by launch_gemm when eligible
 bool gemm256_eligible(const GemmArgs& a);
 int launch_gemm256(const GemmArgs& a, hipStream_t s);
@@ -328,7 +323,6 @@ struct AttnArgs {
     const int32_t* lens;   // [B] optional
     const uint8_t* kmask;  // [B, kmask_ld] optional
     int kmask_ld;
-    int dbg;               // attention_tr.hip ablation bits (DIMX_ATTN_DBG, tuning only: results are wrong when set)
     // attention_tr.hip with a key mask: scratch for the packed 64-bit validity words, B * ceil(Lk / 64) of them, owned by the
     // CALLER (its workspace arena: one buffer per handle and call, so launches on other streams / devices never share it and
     // nothing is allocated inside a launch or a stream capture -- ADVICE round 4)
@@ -357,8 +351,6 @@ struct DecodeAttnArgs {
     int nslab;
     long slab_stride;      // elements between slabs
     int force_nsplit;      // tests: waves per (clip, head) (0 = automatic)
-    int clip_blocks;       // round 6 (two-engine experiment): one 12-wave block per clip that owns its CU (LDS request > half a CU),
-                           // the layer kernel's attention shape as a launch of its own; bf16, H == 12, f32 slab q only
     int rows_per_clip;     // cross attention with several query rows per clip (multi-sample generation):
                            // rows r*S .. r*S+S-1 of q/out share clip r's K/V cache and mask (0/1 = one row)
     const void* knew;      // self-attn: this step's k/v rows [B, *] (nullptr for cross attention)
@@ -377,8 +369,6 @@ struct DecodeAttnArgs {
     float scale;
 };
 int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
-// attention / GEMM co-residency probe (gemm.hip fused_probe_kernel; tools/attic/fuse_probe.py)
-int launch_fused_probe(const GemmArgs& g, const DecodeAttnArgs& d, int which, unsigned* hw_id, hipStream_t s);
 
 int launch_vq_argmin(const float* z, int N, const float* Et /*[128][512]*/, const float* ee /*[512]*/,
                      int32_t* idx, float* best_d, float* margin, hipStream_t s);
@@ -414,7 +404,6 @@ struct ChainArgs {
     unsigned* seen;  // [8][32] this launch site's (XCD, CU slot) claim stamps (zeroed with the counters)
     const int32_t* step;
     unsigned* err;
-    unsigned long long* prof;  // tuning only: [256 blocks][16] wall-clock stamps (100 MHz) of the phase boundaries
     // Deferred LayerNorm (defer = 1, needs g1): the CU that owns a column slice of the first projection adds the residual
     // itself, writes x (f32) and y = bf16(x) UN-normalised plus the partial row sums {sum x, sum x^2} of its columns into
     // stats[group][CU][row][2]; the consumer of y multiplies with gamma-scaled weights W' = gamma o W and corrects its
@@ -451,10 +440,6 @@ struct LayerChainArgs {
     int fault;
     unsigned long long* prof;       // tuning only: [256][16] phase stamps
     int sc_stride;                  // floats per (clip, head) score row in LDS
-    int perm;                       // round 6 experiment (DIMX_LAYER_PERM=1): wave w of CU slot i streams head w of clip (i + w) % 32 instead of
-                                    // clip i -- a static spread of every clip's 12 heads over 12 CUs of its XCD (full groups only)
-    int abl;                        // tuning only (DIMX_LAYER_ABL, dimx_op_layer_chain; results are then WRONG): bit 0 = the three weight
-                                    // slices are not fetched (round 6: what do the 8 x replicated slices cost the launch?)
     int off_base, off_A1, off_W1, off_A2, off_W2, off_W3, off_A3;  // LDS plan (bytes), set by the launcher
 };
 bool layer_chain_supported(const LayerChainArgs& a, int cu_count);

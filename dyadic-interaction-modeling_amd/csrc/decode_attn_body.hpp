@@ -1,6 +1,6 @@
 // decode_attn_body.hpp -- the one-query decode attention as a device function (see decode_attn.hip for what it computes and
 // why it is shaped the way it is).  In a header because two kernels run it: decode_attn_kernel (decode_attn.hip) and the
-// attention / GEMM co-residency probe (gemm.hip, fused_probe_kernel).
+// decoder-layer kernel (chain.hip, xcd_layer_kernel).
 #pragma once
 #include "common.hpp"
 

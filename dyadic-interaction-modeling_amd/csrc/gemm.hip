@@ -17,11 +17,9 @@
 //     can write row-major activations, head-major K/V caches or the transposed V^T the attention
 //     kernel consumes.
 #include "common.hpp"
-#include "decode_attn_body.hpp"
 
 namespace dimx {
 
-static int gemm_cfg_small();
 static bool gemm_use_ws72(const GemmArgs& a);
 
 void gemm_args_init(GemmArgs& a) {
@@ -72,7 +70,7 @@ __device__ __forceinline__ int lds_off(int row, int kc) { return row * 128 + (((
 //   * ACT is a compile-time parameter (the caller switches once, outside the element loops);
 //   * FAST (bf16 perf mode): GELU through v_exp_f32 / v_rcp_f32 approximations (error far below bf16
 //     rounding; the bare v_rcp_f32 -- __frcp_rn expands to a 12-instruction IEEE division, and the decode ff1
-//     epilogue spent 1.5 us in 16 GELUs per lane, tools/gemm_phases.py); the f32 parity mode keeps tanhf / erff;
+//     epilogue spent 1.5 us in 16 GELUs per lane, by in-kernel stamps); the f32 parity mode keeps tanhf / erff;
 //   * a plain row-major destination gets a dedicated path (one 64-bit base per column, 32-bit row offsets);
 //     the generic path handles head-major K/V caches, transposed V^T and per-row positional adds.
 // ------------------------------------------------------------------------------------------------
@@ -102,8 +100,7 @@ template <int ACT, bool FAST> __device__ __forceinline__ float act_fn(float x) {
 
 template <typename OutT, int MI, int NI, int ACT, bool FAST>
 __device__ __forceinline__ void epilogue_tile(const GemmArgs& a, const f32x16_t (&acc)[MI][NI], int m0w, int n0w,
-                                              int half, int l31, int split, unsigned long long* st = nullptr,
-                                              int n_lim = 0x7fffffff, const float* bias_pre = nullptr) {
+                                              int half, int l31, int split, int n_lim = 0x7fffffff, const float* bias_pre = nullptr) {
     // n_lim: first column the block does NOT own (gemm_ws72_kernel: a 96-wide MFMA tile holds 72 valid columns);
     // bias_pre[j]: the lane's bias values requested before the main loop (a dependent load here cost 0.5 us per launch)
     const bool first = split == 0;
@@ -115,11 +112,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& a, const f32x16_t 
         for (int j = 0; j < NI; ++j) {
             const int n = n0w + j * 32 + l31;
             if (n >= a.N || n >= n_lim) continue;
-            float bias_v = bias_pre ? bias_pre[j] : ((a.bias && first) ? a.bias[n] : 0.f);
-            if (st) {  // tools/gemm_phases.py: kernel arguments + bias in registers
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(bias_v)::"memory");
-                st[24] = wall_clock64();
-            }
+            const float bias_v = bias_pre ? bias_pre[j] : ((a.bias && first) ? a.bias[n] : 0.f);
             OutT* col = C + n;
             const float* rcol = a.residual ? a.residual + n : nullptr;
 #pragma unroll
@@ -139,11 +132,6 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& a, const f32x16_t 
 #pragma unroll
                     for (int r = 0; r < 16; ++r) vals[r] = act_fn<ACT, FAST>(acc[i][j][r] + bias_v);
                 }
-                if (st) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(vals[r]));
-                    st[25] = wall_clock64();
-                }
                 if (mb + 27 < a.M) {  // the lane's last row is mb + 27: no per-row checks for interior tiles
 #pragma unroll
                     for (int r = 0; r < 16; ++r) store_from_f32<OutT>(col + (size_t)(mb + (r & 3) + 8 * (r >> 2)) * ldc, vals[r]);
@@ -154,7 +142,6 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& a, const f32x16_t 
                         if (m < a.M) store_from_f32<OutT>(col + (size_t)m * ldc, vals[r]);
                     }
                 }
-                if (st) st[26] = wall_clock64();
             }
         }
         return;
@@ -230,14 +217,13 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& a, const f32x16_t 
 
 template <typename T, typename OutT, int MI, int NI>
 __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x16_t (&acc)[MI][NI], int m0w, int n0w, int half,
-                                         int l31, int split, unsigned long long* st = nullptr, int n_lim = 0x7fffffff,
-                                         const float* bias_pre = nullptr) {
+                                         int l31, int split, int n_lim = 0x7fffffff, const float* bias_pre = nullptr) {
     constexpr bool FAST = sizeof(T) == 2;
     switch (a.act) {
-        case ACT_LEAKY: epilogue_tile<OutT, MI, NI, ACT_LEAKY, FAST>(a, acc, m0w, n0w, half, l31, split, st, n_lim, bias_pre); break;
-        case ACT_GELU_TANH: epilogue_tile<OutT, MI, NI, ACT_GELU_TANH, FAST>(a, acc, m0w, n0w, half, l31, split, st, n_lim, bias_pre); break;
-        case ACT_GELU_ERF: epilogue_tile<OutT, MI, NI, ACT_GELU_ERF, FAST>(a, acc, m0w, n0w, half, l31, split, st, n_lim, bias_pre); break;
-        default: epilogue_tile<OutT, MI, NI, ACT_NONE, FAST>(a, acc, m0w, n0w, half, l31, split, st, n_lim, bias_pre); break;
+        case ACT_LEAKY: epilogue_tile<OutT, MI, NI, ACT_LEAKY, FAST>(a, acc, m0w, n0w, half, l31, split, n_lim, bias_pre); break;
+        case ACT_GELU_TANH: epilogue_tile<OutT, MI, NI, ACT_GELU_TANH, FAST>(a, acc, m0w, n0w, half, l31, split, n_lim, bias_pre); break;
+        case ACT_GELU_ERF: epilogue_tile<OutT, MI, NI, ACT_GELU_ERF, FAST>(a, acc, m0w, n0w, half, l31, split, n_lim, bias_pre); break;
+        default: epilogue_tile<OutT, MI, NI, ACT_NONE, FAST>(a, acc, m0w, n0w, half, l31, split, n_lim, bias_pre); break;
     }
 }
 
@@ -647,11 +633,7 @@ template <int MI, int NI> struct FragMma<float, MI, NI> {
     }
 };
 
-// ABL (ablation, tuning only): 0 normal, 1 = no MFMA/ds_read in the loop (DMA only), 2 = no DMA in the loop
-// KPI: k-tiles per loop iteration (one vmcnt wait + one barrier per KPI tiles; the ring holds STAGES groups of KPI tiles).
-// The decode GEMMs (M = batch) do 4 MFMAs per wave and k-tile, so the per-iteration wait / barrier / DMA-issue overhead
-// (~1000 cycles) is what they cost: KPI = 2 halves the number of iterations.
-template <typename T, typename OutT, int BM, int BN, int WM, int WN, int STAGES, int ABL = 0, bool STG = false, int KPI = 1>
+template <typename T, typename OutT, int BM, int BN, int WM, int WN, int STAGES, bool STG = false>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmArgs a) {
     constexpr int NW = WM * WN;
     constexpr int MI = BM / (WM * 32), NI = BN / (WN * 32);
@@ -661,9 +643,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmArgs a
     constexpr int LPT = LA + LW;
     constexpr int TILE_BYTES = (BM + BN) * 128;
     static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "tile rows must split into 8-row DMA pieces per wave");
-    static_assert(STAGES >= 1 && (STAGES - 1) * LPT * KPI < 64, "vmcnt range");
-    static_assert(KPI == 1 || (STAGES >= 2 && ABL == 0 && !STG), "KPI > 1: plain ring only");
-    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGES * KPI * TILE_BYTES];
+    static_assert(STAGES >= 1 && (STAGES - 1) * LPT < 64, "vmcnt range");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGES * TILE_BYTES];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + BM - 1) / BM;
@@ -680,14 +661,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmArgs a
     // and land on the same XCD -- its L2 then fetches every weight byte once instead of once per row tile (the A
     // panel is tiny and stays resident everywhere).  Many row tiles (prefill): m-major, A panels are the big operand.
     int tile_m, tile_n;
-    if (a.tile_map == 1) {
-        const int x = blockIdx.x & 7, i = blockIdx.x >> 3;
-        const int tq = (tiles_m + 3) >> 2, tnh = tiles_n >> 1;
-        const int im = i / tnh;
-        tile_m = (x >> 1) * tq + im;
-        tile_n = (x & 1) * tnh + (i - im * tnh);
-        if (tile_m >= tiles_m) return;
-    } else if (tiles_m <= 8) {
+    if (tiles_m <= 8) {
         tile_n = tile / tiles_m;
         tile_m = tile - tile_n * tiles_m;
     } else {
@@ -791,42 +765,11 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmArgs a
         }
     };
 
-    if constexpr (KPI > 1) {
-        // groups of KPI k-tiles: group gi = tiles [gi*KPI, gi*KPI + KPI) in ring slots (gi % STAGES)*KPI + j
-        const int ng = (nk + KPI - 1) / KPI;
-        auto issue_group = [&](int gi) {
-#pragma unroll
-            for (int jj = 0; jj < KPI; ++jj) {
-                const int kt = gi * KPI + jj;
-                issue(kt < nk ? kt : nk - 1, (gi % STAGES) * KPI + jj);  // a short last group re-reads the last tile
-            }
-        };
-#pragma unroll
-        for (int s2 = 0; s2 < STAGES - 1; ++s2)
-            if (s2 < ng) issue_group(s2);
-        for (int gi = 0; gi < ng; ++gi) {
-            if (ng - 1 - gi < STAGES - 2)
-                wait_vmcnt<0>();
-            else
-                wait_vmcnt<(STAGES - 2) * LPT * KPI>();
-            __builtin_amdgcn_s_barrier();
-            if (gi + STAGES - 1 < ng) issue_group(gi + STAGES - 1);
-#pragma unroll
-            for (int jj = 0; jj < KPI; ++jj)
-                if (gi * KPI + jj < nk) compute_tile((gi % STAGES) * KPI + jj);
-        }
-    } else {
-    auto stamp = [&](int i) {
-        if (ABL == 3 && tid == 0 && i < 32) a.prof[(size_t)blockIdx.x * 32 + i] = wall_clock64();
-    };
-    stamp(0);
 #pragma unroll
     for (int s = 0; s < STAGES - 1; ++s)
-        if (s < nk && (ABL != 2 || s == 0)) issue(s, s);
-    stamp(1);
+        if (s < nk) issue(s, s);
 
     for (int it = 0; it < nk; ++it) {
-        if (ABL == 3 && it < 24) stamp(2 + it);
         if (STAGES == 1) {
             // single LDS buffer: latency is hidden by the other resident blocks (up to 5 per CU), not by a ring
             if (it > 0) __builtin_amdgcn_s_barrier();  // everyone is done reading the previous tile
@@ -835,25 +778,18 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmArgs a
             __builtin_amdgcn_s_barrier();
         } else {
             // tile `it` has landed once at most min(STAGES-2, nk-1-it) younger tiles are still in flight
-            if (ABL == 2 || nk - 1 - it < STAGES - 2)
+            if (nk - 1 - it < STAGES - 2)
                 wait_vmcnt<0>();
             else
                 wait_vmcnt<(STAGES >= 2 ? STAGES - 2 : 0) * LPT>();
-            if (ABL == 3 && it == 8) stamp(20);
             __builtin_amdgcn_s_barrier();
-            if (ABL == 3 && it == 8) stamp(21);
-            // Measured on this sequence (tools/gemm_phases.py, tools/gemm_ab.py, same box): wave 0 spends 0.07 us in the
-            // vmcnt wait, 0.04 in the barrier, 0.14 issuing its 4 DMA pieces, 0.15 on 8 ds_reads + 4 MFMAs.  Issuing the
-            // fragment reads before the DMAs: qkv 10.3 -> 11.2 us; non-temporal DMA loads of W: ff1 13.5 -> 15.9 us (every
-            // M tile re-reads the W tile from L2); a wave-uniform branch per DMA piece: +1 us per kernel.
-            if (ABL != 2 && it + STAGES - 1 < nk) issue(it + STAGES - 1, (it + STAGES - 1) % STAGES);
-            if (ABL == 3 && it == 8) stamp(22);
+            // Measured on this sequence (in-kernel stamps and A/B runs, same box): wave 0 spends 0.07 us in the vmcnt wait,
+            // 0.04 in the barrier, 0.14 issuing its 4 DMA pieces, 0.15 on 8 ds_reads + 4 MFMAs.  Issuing the fragment reads
+            // before the DMAs: qkv 10.3 -> 11.2 us; non-temporal DMA loads of W: ff1 13.5 -> 15.9 us (every M tile re-reads
+            // the W tile from L2); a wave-uniform branch per DMA piece: +1 us per kernel.
+            if (it + STAGES - 1 < nk) issue(it + STAGES - 1, (it + STAGES - 1) % STAGES);
         }
-        if (ABL == 1) continue;
         compute_tile(it % STAGES);
-        if (ABL == 3 && it == 8) stamp(23);
-    }
-    stamp(28);
     }
 
     // ---- epilogue (split-K: this split's partial sums go to its own f32 slab)
@@ -864,10 +800,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmArgs a
         epilogue_stg<T, OutT, MI, NI>(a, acc, m0 + wm * MI * 32, n0 + wn * NI * 32, half, l31, smem + wave * SLICE);
     } else {
         epilogue<T, OutT, MI, NI>(a, acc, m0 + wm * MI * 32, n0 + wn * NI * 32, half, l31, split);
-    }
-    if (ABL == 3) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) a.prof[(size_t)blockIdx.x * 32 + 29] = wall_clock64();
     }
 }
 
@@ -885,12 +817,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmArgs a
 // (Replacing the barrier by two LDS counters -- loaders add to `landed`, consumers to `consumed`, each side polls the
 // other's -- so that loaders never wait for each other measured slower: qkv 8.6 -> 10.5 us, the polls sit on both
 // critical paths.)
-// ABLW (tuning only, tools/gemm_ab.py): 1 = consumers skip reads + MFMA, 2 = loaders issue no DMA after the prologue,
-// 3 = the W pieces are replaced by a second copy of the A pieces (every DMA an L2 hit).
-// The body as a device function (the block's index and the block count come as arguments, the LDS from the caller) so that
-// the attention / GEMM co-residency probe below can run it next to decode-attention blocks in one launch.
-template <typename T, typename OutT, int STAGES, bool PROF, int ABLW>
-__device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, int nblocks, unsigned char* smem, float* ln_sm) {
+template <typename T, typename OutT, int STAGES>
+__global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmArgs a) {
     constexpr int BM = 64, BN = 64, NL = 4;
     constexpr int EPC = Elem<T>::kPerChunk;
     constexpr int BK = 8 * EPC;
@@ -898,14 +826,16 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
     constexpr int LPT = LA + LW;
     constexpr int TILE_BYTES = (BM + BN) * 128;
     static_assert(STAGES >= 3 && (STAGES - 1) * LPT < 64, "ring depth");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGES * TILE_BYTES];
+    __shared__ __attribute__((aligned(16))) float ln_sm[128];  // deferred LayerNorm: mean[64], rstd[64] of the tile's rows
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + BM - 1) / BM;
     const int ntiles = tiles_m * tiles_n;
-    int bid = block_id;  // XCD-aware order, n-major for few row tiles: see gemm_glds_kernel
+    int bid = blockIdx.x;  // XCD-aware order, n-major for few row tiles: see gemm_glds_kernel
     {
-        const int nblk = nblocks, q = nblk >> 3, r = nblk & 7, x = bid & 7, i = bid >> 3;
+        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, x = bid & 7, i = bid >> 3;
         bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
     }
     const int split = bid / ntiles, tile = bid - split * ntiles;
@@ -924,12 +854,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
     int nk = nk_all - kt0;
     nk = nk > per ? per : nk;
     if (nk <= 0) return;
-    // PROF (tools/gemm_phases.py): 64 wall-clock stamps per block, 0-31 by consumer wave 0, 32-63 by loader wave 4
-    auto stamp = [&](int i) {
-        if (PROF && lane == 0 && (wave == 0 || wave == 4) && i < 32)
-            a.prof[(size_t)block_id * 64 + (wave == 4 ? 32 : 0) + i] = wall_clock64();
-    };
-    stamp(0);
 
     if (wave >= 4) {
         // ---------------- loader waves
@@ -955,7 +879,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
             gW[j] = W + (size_t)n * a.ldw + c * EPC + (size_t)kt0 * BK;
             if (a.w_tiled)  // block (n / 8, k-tile) = 8 rows x 128 B, contiguous; the k-tiles of a row group follow each other
                 gW[j] = W + ((size_t)(n >> 3) * (a.ldw / BK) + kt0) * (8 * BK) + (n & 7) * BK + c * EPC;
-            if (ABLW == 3) gW[j] = gA[j < LA ? j : 0];
         }
         const int wstep = a.w_tiled ? 8 * BK : BK;  // elements from one k-tile of a piece to the next
         auto issue = [&](int kt, int buf) {
@@ -984,17 +907,14 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
 #pragma unroll
         for (int st = 0; st < STAGES - 1; ++st)
             if (st < nk) issue(st, st);
-        stamp(1);
         for (int it = 0; it < nk; ++it) {
-            if (it < 12) stamp(2 + 2 * it);
             // this wave's pieces of tile `it` have landed once at most min(STAGES-2, nk-1-it) younger tiles are in flight
             if (nk - 1 - it < STAGES - 2)
                 wait_vmcnt<0>();
             else
                 wait_vmcnt<(STAGES - 2) * LPT>();
-            if (it < 12) stamp(3 + 2 * it);
             __builtin_amdgcn_s_barrier();
-            if (ABLW != 2 && it + STAGES - 1 < nk) issue(it + STAGES - 1, (it + STAGES - 1) % STAGES);
+            if (it + STAGES - 1 < nk) issue(it + STAGES - 1, (it + STAGES - 1) % STAGES);
             if (a.ln_stats && it == nk - 2) {  // vmcnt is 0 here (the wait of this iteration), nothing left to issue
                 // {sum x, M2} of 32 column slices -> mean and variance by the parallel-variance formula, two passes (no
                 // sum x^2 - mean^2 cancellation)
@@ -1025,7 +945,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // in LDS before this wave arrives at the last barrier
             }
         }
-        stamp(28);
         return;
     }
 
@@ -1047,14 +966,11 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
     float ln_cs = 0.f;
     for (int it = 0; it < nk; ++it) {
         const unsigned boff = (unsigned)((it % STAGES) * TILE_BYTES);
-        if (it < 12) stamp(2 + 2 * it);
         __builtin_amdgcn_s_barrier();
-        if (ABLW == 1) continue;
         if (it == 0 && a.ln_stats) {
             const int n = n0 + wn * 32 + l31;
             ln_cs = a.ln_colsum[n < a.N ? n : a.N - 1];
         }
-        if (it < 12) stamp(3 + 2 * it);
         u32x4_t fa[4][1], fw[4][1];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -1071,7 +987,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
             FragMma<T, 1, 1>::run(acc, fa[q], fw[q]);
         }
     }
-    stamp(28);
     if (a.ln_stats) {
         // an accumulator register group holds rows 8q + 4 half + (0..3) of the wave's 32: 8 ds_read_b128
         const float* strip = ln_sm + wm * 32;
@@ -1085,25 +1000,12 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& a, int block_id, in
             acc[0][0][4 * q + 3] = rq.w * (acc[0][0][4 * q + 3] - mq.w * ln_cs);
         }
     }
-    epilogue<T, OutT, 1, 1>(a, acc, m0 + wm * 32, n0 + wn * 32, half, l31, split,
-                            (PROF && wave == 0 && lane == 0) ? a.prof + (size_t)block_id * 64 : nullptr);
-    if (PROF) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp(29);
-    }
-}
-
-template <typename T, typename OutT, int STAGES, bool PROF = false, int ABLW = 0>
-__global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmArgs a) {
-    constexpr int TILE_BYTES = (64 + 64) * 128;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGES * TILE_BYTES];
-    __shared__ __attribute__((aligned(16))) float ln_sm[128];  // deferred LayerNorm: mean[64], rstd[64] of the tile's rows
-    gemm_ws_body<T, OutT, STAGES, PROF, ABLW>(a, blockIdx.x, gridDim.x, smem, ln_sm);
+    epilogue<T, OutT, 1, 1>(a, acc, m0 + wm * 32, n0 + wn * 32, half, l31, split);
 }
 
 // ------------------------------------------------------------------------------------------------
 // gemm_ws72_kernel (round 5): the loader/consumer decode GEMM on 64 x 72 tiles -- ONE block per CU, exactly.
-// Measured (tools/attic/r05_gemm_blocks.py, profiles/r05_gemm_blocks.txt): the three chip-wide decode GEMMs launch 288 blocks of
+// Measured (profiles/r05_gemm_blocks.txt): the three chip-wide decode GEMMs launch 288 blocks of
 // 64 x 64 tiles on 256 CUs; a CU that hosts two blocks pulls twice the operand bytes through its LDS-DMA path (55-67 GB/s
 // per CU whatever the block count) and the launch lasts as long as those 32 CUs: the same kernel at a column count that gives
 // 256 blocks runs 7.7 instead of 11.1 us (K = 4608, 4 slabs), 9.2 instead of 10.8 (ff1), 6.3 instead of 6.6 (qkv).  No
@@ -1115,30 +1017,24 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmArgs a) {
 // vmcnt waits are instantiated per loader).  The W fragment reads of the third column block run past the 72 rows that were
 // loaded (into the next ring slot / the slack behind the ring): whatever they find only reaches accumulator columns that are
 // never stored (n_lim).  bf16 operands only; M and N edges are clamped like in gemm_ws_kernel.
-// KT (round 5, second step): k-tiles per ring slot = per block barrier.  KT = 2: three slots of two k-tiles; the consumers request
-// the fragments of a slot's second k-tile before the first one's MFMAs start (its LDS latency disappears behind them) and meet
-// the loaders half as often.
-template <typename OutT, bool PROF, int KT>
+// (Two k-tiles per ring slot = per block barrier, three slots, measured slower: 1624 vs 1653 clips/s, profiles/r05_gemm_ws72.txt.)
+template <typename OutT>
 struct Ws72 {
-    static constexpr int BM = 64, BN = 72, BK = 64, STAGES = KT == 1 ? 4 : 3, NLOAD = 4, NCONS = 6;
+    static constexpr int BM = 64, BN = 72, BK = 64, STAGES = 4, NLOAD = 4, NCONS = 6;
     static constexpr int TILE_BYTES = (BM + BN) * 128;
-    static constexpr int SLOT_BYTES = KT * TILE_BYTES;
     // + the rows 72..95 read behind the last slot; and never less than 84 KiB: two blocks must NOT fit a CU.  Launched into an idle
     // GPU the 256 blocks land one per CU, but behind another kernel the dispatcher hands a CU that drained early a second block
     // while others still wait for their first (LDS and waves would allow it) -- and the doubled CUs set the launch time again:
     // 8.8 us by in-kernel stamps (isolated launches) against 10.4 us back to back (profiles/r05_gemm_ws72.txt)
-    static constexpr int RING_BYTES = STAGES * SLOT_BYTES + 24 * 128;
+    static constexpr int RING_BYTES = STAGES * TILE_BYTES + 24 * 128;
     static constexpr int SMEM_BYTES = RING_BYTES > 84 * 1024 ? RING_BYTES : 84 * 1024;
-    static_assert((STAGES - 2) * KT == 2, "the loaders' counted waits below are written for two k-tiles in flight behind the current slot");
+    static_assert(STAGES - 2 == 2, "the loaders' counted waits below are written for two k-tiles in flight behind the current slot");
 
     template <int LW>  // W pieces of this loader wave (3 for loader 0, 2 for the others)
-    static __device__ __forceinline__ void loader(const GemmArgs& a, int block_id, int lw, int lane, int m0, int n0, int kt0, int nk,
-                                                  unsigned char* smem, float* ln_sm) {
+    static __device__ __forceinline__ void loader(const GemmArgs& a, int lw, int lane, int m0, int n0, int kt0, int nk, unsigned char* smem,
+                                                  float* ln_sm) {
         constexpr int LA = 2, LPT = LA + LW;
-        static_assert((STAGES - 1) * KT * LPT < 56, "ring depth");
-        auto stamp = [&](int i) {
-            if (PROF && lane == 0 && lw == 0 && i < 32) a.prof[(size_t)block_id * 64 + 32 + i] = wall_clock64();
-        };
+        static_assert((STAGES - 1) * LPT < 56, "ring depth");
         const bf16* __restrict__ A = (const bf16*)a.A;
         const bf16* __restrict__ W = (const bf16*)a.W;
         const bf16* gA[LA];
@@ -1162,24 +1058,16 @@ struct Ws72 {
             n = n < a.N ? n : a.N - 1;
             gW[j] = W + (size_t)n * a.ldw + c * 8 + (size_t)kt0 * BK;
         }
-        const int nst = (nk + KT - 1) / KT;
-        auto issue = [&](int st, int slot) {  // the k-tiles of slot st that exist (the last slot of an odd count holds one)
+        auto issue = [&](int kt, int slot) {
+            unsigned char* base = smem + slot * TILE_BYTES;
 #pragma unroll
-            for (int t = 0; t < KT; ++t) {
-                const int kt = st * KT + t;
-                if (kt < nk) {
-                    unsigned char* base = smem + slot * SLOT_BYTES + t * TILE_BYTES;
+            for (int j = 0; j < LA; ++j)
+                __builtin_amdgcn_global_load_lds((glb_void_t*)(gA[j] + (size_t)kt * BK), (lds_void_t*)(base + pA[j] * 1024), 16, 0, 0);
 #pragma unroll
-                    for (int j = 0; j < LA; ++j)
-                        __builtin_amdgcn_global_load_lds((glb_void_t*)(gA[j] + (size_t)kt * BK), (lds_void_t*)(base + pA[j] * 1024), 16, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < LW; ++j)
-                        __builtin_amdgcn_global_load_lds((glb_void_t*)(gW[j] + (size_t)kt * BK), (lds_void_t*)(base + BM * 128 + pW[j] * 1024),
-                                                         16, 0, 0);
-                }
-            }
+            for (int j = 0; j < LW; ++j)
+                __builtin_amdgcn_global_load_lds((glb_void_t*)(gW[j] + (size_t)kt * BK), (lds_void_t*)(base + BM * 128 + pW[j] * 1024), 16, 0, 0);
         };
-        // deferred LayerNorm of the A rows: as in gemm_ws_body (loader lw reduces the partial sums of rows lw * 16 + (lane & 15))
+        // deferred LayerNorm of the A rows: as in gemm_ws_kernel (loader lw reduces the partial sums of rows lw * 16 + (lane & 15))
         float2 lp[8];
         if (a.ln_stats) {
             int m = m0 + lw * 16 + (lane & 15);
@@ -1189,14 +1077,12 @@ struct Ws72 {
             for (int i = 0; i < 8; ++i) lp[i] = sp[(size_t)i * 32];
         }
         int issued = 0;
-        for (; issued < STAGES - 1 && issued < nst; ++issued) issue(issued, issued);
-        stamp(1);
+        for (; issued < STAGES - 1 && issued < nk; ++issued) issue(issued, issued);
         int slot_next = issued % STAGES;
-        const int st_ln = nst >= 2 ? nst - 2 : 0;
-        for (int st = 0; st < nst; ++st) {
-            if (st < 12) stamp(2 + 2 * st);
-            {   // this wave's pieces of slot st have landed once no more than the pieces of the k-tiles issued BEHIND it are in flight
-                int done = (st + 1) * KT, all = issued * KT;
+        const int st_ln = nk >= 2 ? nk - 2 : 0;
+        for (int st = 0; st < nk; ++st) {
+            {   // this wave's pieces of k-tile st have landed once no more than the pieces of the k-tiles issued BEHIND it are in flight
+                int done = st + 1, all = issued;
                 done = done < nk ? done : nk;
                 all = all < nk ? all : nk;
                 const int y = all - done;  // 0, 1 or 2 k-tiles
@@ -1204,9 +1090,8 @@ struct Ws72 {
                 else if (y == 1) wait_vmcnt<LPT>();
                 else wait_vmcnt<2 * LPT>();
             }
-            if (st < 12) stamp(3 + 2 * st);
             __builtin_amdgcn_s_barrier();
-            if (issued < nst) {
+            if (issued < nk) {
                 issue(issued, slot_next);
                 ++issued;
                 slot_next = slot_next + 1 == STAGES ? 0 : slot_next + 1;
@@ -1238,7 +1123,6 @@ struct Ws72 {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
         }
-        stamp(28);
     }
 
     static __device__ __forceinline__ void body(const GemmArgs& a, int block_id, int nblocks, unsigned char* smem, float* ln_sm) {
@@ -1261,16 +1145,12 @@ struct Ws72 {
         int nk = nk_all - kt0;
         nk = nk > per ? per : nk;
         if (nk <= 0) return;
-        auto stamp = [&](int i) {
-            if (PROF && lane == 0 && wave == 0 && i < 32) a.prof[(size_t)block_id * 64 + i] = wall_clock64();
-        };
-        stamp(0);
         if (wave >= NCONS) {
             const int lw = wave - NCONS;
             if (lw == 0)
-                loader<3>(a, block_id, lw, lane, m0, n0, kt0, nk, smem, ln_sm);
+                loader<3>(a, lw, lane, m0, n0, kt0, nk, smem, ln_sm);
             else
-                loader<2>(a, block_id, lw, lane, m0, n0, kt0, nk, smem, ln_sm);
+                loader<2>(a, lw, lane, m0, n0, kt0, nk, smem, ln_sm);
             return;
         }
         // ---------------- consumer waves: 2 x 3, one 32 x 32 accumulator each
@@ -1289,7 +1169,7 @@ struct Ws72 {
         // Everything the epilogue needs is fetched NOW -- the consumers wait ~1.5 us for the first tile anyway: the lane's bias and
         // (deferred LayerNorm) column sum (as dependent loads behind the main loop they cost 0.5 us per launch), and the kernel
         // arguments of the store (destination, row stride, slab offset, activation: behind the loop their scalar loads were another
-        // 0.4 us, tools/attic/r05_gemm_stamps.py).  The kernel only takes plain row-major destinations (gemm_use_ws72), so the epilogue is
+        // 0.4 us, by in-kernel stamps).  The kernel only takes plain row-major destinations (gemm_use_ws72), so the epilogue is
         // 16 stores per lane and nothing else.
         const int n_lim = n0 + BN < a.N ? n0 + BN : a.N;
         const int ncol = n0 + wn * 32 + l31;
@@ -1305,57 +1185,26 @@ struct Ws72 {
         const int mrem = a.M - row_base;
         const int act = a.act;
         const bool has_ln = a.ln_stats != nullptr;
-        const int nst = (nk + KT - 1) / KT;
         unsigned boff = 0;
-        for (int st = 0; st < nst; ++st) {
-            if (st < 12) stamp(2 + 2 * st);
+        for (int st = 0; st < nk; ++st) {
             __builtin_amdgcn_s_barrier();
-            if (st < 12) stamp(3 + 2 * st);
-            u32x4_t fa[KT][4][1], fw[KT][4][1];
+            u32x4_t fa[4][1], fw[4][1];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                ds_read128<0>(fa[0][q][0], aoff[q] + boff);
-                ds_read128<0>(fw[0][q][0], woff[q] + boff);
+                ds_read128<0>(fa[q][0], aoff[q] + boff);
+                ds_read128<0>(fw[q][0], woff[q] + boff);
             }
-            const bool two = KT == 2 && st * KT + 1 < nk;  // wave-uniform
-            if (two) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ds_read128<0>(fa[KT - 1][q][0], aoff[q] + boff + TILE_BYTES);
-                    ds_read128<0>(fw[KT - 1][q][0], woff[q] + boff + TILE_BYTES);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (q == 0) wait_lgkm<14>();
-                    if (q == 1) wait_lgkm<12>();
-                    if (q == 2) wait_lgkm<10>();
-                    if (q == 3) wait_lgkm<8>();
-                    __builtin_amdgcn_sched_barrier(0);
-                    FragMma<bf16, 1, 1>::run(acc, fa[0][q], fw[0][q]);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (q == 0) wait_lgkm<6>();
-                    if (q == 1) wait_lgkm<4>();
-                    if (q == 2) wait_lgkm<2>();
-                    if (q == 3) wait_lgkm<0>();
-                    __builtin_amdgcn_sched_barrier(0);
-                    FragMma<bf16, 1, 1>::run(acc, fa[KT - 1][q], fw[KT - 1][q]);
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (q == 0) wait_lgkm<6>();
-                    if (q == 1) wait_lgkm<4>();
-                    if (q == 2) wait_lgkm<2>();
-                    if (q == 3) wait_lgkm<0>();
-                    __builtin_amdgcn_sched_barrier(0);
-                    FragMma<bf16, 1, 1>::run(acc, fa[0][q], fw[0][q]);
-                }
+            for (int q = 0; q < 4; ++q) {
+                if (q == 0) wait_lgkm<6>();
+                if (q == 1) wait_lgkm<4>();
+                if (q == 2) wait_lgkm<2>();
+                if (q == 3) wait_lgkm<0>();
+                __builtin_amdgcn_sched_barrier(0);
+                FragMma<bf16, 1, 1>::run(acc, fa[q], fw[q]);
             }
-            boff = boff + SLOT_BYTES == STAGES * SLOT_BYTES ? 0u : boff + SLOT_BYTES;
+            boff = boff + TILE_BYTES == STAGES * TILE_BYTES ? 0u : boff + TILE_BYTES;
         }
-        stamp(28);
         if (has_ln) {
             const float* strip = ln_sm + wm * 32;
 #pragma unroll
@@ -1368,7 +1217,6 @@ struct Ws72 {
                 acc[0][0][4 * q + 3] = rq.w * (acc[0][0][4 * q + 3] - mq.w * ln_cs);
             }
         }
-        if (PROF && wave == 0 && lane == 0) a.prof[(size_t)block_id * 64 + 24] = wall_clock64();
         float v[16];
         switch (act) {
             case ACT_GELU_ERF:
@@ -1388,7 +1236,6 @@ struct Ws72 {
                 for (int r = 0; r < 16; ++r) v[r] = acc[0][0][r] + bias_v;
                 break;
         }
-        if (PROF && wave == 0 && lane == 0) a.prof[(size_t)block_id * 64 + 25] = wall_clock64();
         if (col_ok) {
             if (rptr) {  // all residual loads in flight together; rows past M read the last valid row (never stored)
                 float rv[16];
@@ -1412,115 +1259,44 @@ struct Ws72 {
                 }
             }
         }
-        if (PROF) {
-            if (wave == 0 && lane == 0) a.prof[(size_t)block_id * 64 + 26] = wall_clock64();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            stamp(29);
-        }
     }
 };
 
-template <typename OutT, bool PROF = false, int KT = 2>
+template <typename OutT>
 __global__ __launch_bounds__(640) void gemm_ws72_kernel(const GemmArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[Ws72<OutT, PROF, KT>::SMEM_BYTES];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[Ws72<OutT>::SMEM_BYTES];
     __shared__ __attribute__((aligned(16))) float ln_sm[128];
-    Ws72<OutT, PROF, KT>::body(a, blockIdx.x, gridDim.x, smem, ln_sm);
+    Ws72<OutT>::body(a, blockIdx.x, gridDim.x, smem, ln_sm);
 }
 
 template <typename OutT> static int launch_ws72(const GemmArgs& a, hipStream_t s) {
     const int tiles = ceil_div(a.M, 64) * ceil_div(a.N, 72);
-    static const int kt_env = getenv("DIMX_WS72_KT") ? atoi(getenv("DIMX_WS72_KT")) : 1;  // k-tiles per barrier; 2 measured SLOWER (1624 vs 1653 clips/s, profiles/r05_gemm_ws72.txt)
-    // the deferred-LayerNorm epilogue writes ln_sm two stages before the last barrier: with two k-tiles per barrier a block
-    // needs at least two stages (4 k-tiles) for that barrier to exist (K = 128 raced); shorter blocks keep KT = 1
-    const int nk_blk = a.K / 64 / (a.splitk > 0 ? a.splitk : 1);
-    const int kt = (kt_env == 2 && !(a.ln_stats && nk_blk < 4)) ? 2 : 1;
-    if (a.prof) {
-        if (kt == 1) hipLaunchKernelGGL((gemm_ws72_kernel<OutT, true, 1>), dim3(tiles * a.splitk), dim3(640), 0, s, a);
-        else hipLaunchKernelGGL((gemm_ws72_kernel<OutT, true, 2>), dim3(tiles * a.splitk), dim3(640), 0, s, a);
-    } else {
-        if (kt == 1) hipLaunchKernelGGL((gemm_ws72_kernel<OutT, false, 1>), dim3(tiles * a.splitk), dim3(640), 0, s, a);
-        else hipLaunchKernelGGL((gemm_ws72_kernel<OutT, false, 2>), dim3(tiles * a.splitk), dim3(640), 0, s, a);
-    }
+    hipLaunchKernelGGL((gemm_ws72_kernel<OutT>), dim3(tiles * a.splitk), dim3(640), 0, s, a);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Attention / GEMM co-residency probe (tools/attic/fuse_probe.py; VERDICT round 2, item 2: "hide the decode step's GEMM chain
-// under its attention: horizontal fusion over two half-batches").  Streams do not overlap the decode kernels and CU masks
-// starve the HBM stream (round 2); what is left to try is ONE launch whose blocks take either role: blocks of role 0 run the
-// loader/consumer decode GEMM (gemm_ws_body, 8 waves, 64 KiB of LDS), blocks of role 1 the one-query decode attention
-// (decode_attn_body with 8 waves = 8 (clip, head) pairs per block; scores in the first 8 x npad floats of the same dynamic
-// LDS).  Both fit a CU together (2 x 64 KiB LDS, 16 waves of <= 128 VGPRs).  Roles alternate along the dispatch order of
-// an XCD and flip parity every 32 blocks, so that under breadth-first placement every CU receives one block of each kind;
-// hw_id (optional) records HW_REG_HW_ID per block so that the achieved placement can be counted, not assumed.
-template <typename OutT>
-__global__ __launch_bounds__(512) void fused_probe_kernel(const GemmArgs g, const DecodeAttnArgs d, int n_gemm, int n_attn, int npad,
-                                                         unsigned* hw_id) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
-    __shared__ __attribute__((aligned(16))) float ln_sm[128];
-    __shared__ float red_m[8], red_l[8], red_acc[8 * 64];
-    const int b = blockIdx.x;
-    const int x = b & 7, q = b >> 3;                 // XCD and position in the XCD's dispatch sequence
-    const int parity = (q ^ (q >> 5)) & 1;           // alternate roles; flip every 32 positions (one round of the XCD's CUs)
-    // the two parity classes alternate in an XCD's sequence, so q / 2 positions of either class come before position q:
-    // class-local index id in [0, grid / 2).  A class that has run out of work serves the other class's indices beyond
-    // grid / 2 (which that class's own half of the grid cannot hold); what is left over returns at once.
-    const int halfgrid = gridDim.x >> 1;
-    int role = parity, id = (q >> 1) * 8 + x;
-    {
-        const int n_role = role ? n_attn : n_gemm, n_other = role ? n_gemm : n_attn;
-        if (id >= n_role) {
-            id = halfgrid + (id - n_role);
-            role ^= 1;
-            if (id >= n_other) return;
-        }
-    }
-    if (hw_id && threadIdx.x == 0) {
-        unsigned v;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        hw_id[b] = (v & 0xffffffu) | ((xcc & 7u) << 24) | ((unsigned)role << 28);
-    }
-    if (role == 0) gemm_ws_body<bf16, OutT, 4, false, 0>(g, id, n_gemm, dyn, ln_sm);
-    else decode_attn_body<bf16, false, true, 1, 8>(d, id, (float*)dyn, npad, red_m, red_l, red_acc);
-}
-
-template <typename T, typename OutT, int STAGES, int ABLW = 0> static int launch_ws(const GemmArgs& a, hipStream_t s) {
+template <typename T, typename OutT, int STAGES> static int launch_ws(const GemmArgs& a, hipStream_t s) {
     const int tiles = ceil_div(a.M, 64) * ceil_div(a.N, 64);
-    if (a.prof && STAGES == 4)
-        hipLaunchKernelGGL((gemm_ws_kernel<T, OutT, 4, true, ABLW>), dim3(tiles * a.splitk), dim3(512), 0, s, a);
-    else
-        hipLaunchKernelGGL((gemm_ws_kernel<T, OutT, STAGES, false, ABLW>), dim3(tiles * a.splitk), dim3(512), 0, s, a);
+    hipLaunchKernelGGL((gemm_ws_kernel<T, OutT, STAGES>), dim3(tiles * a.splitk), dim3(512), 0, s, a);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
 
-template <typename T, typename OutT, int BM, int BN, int WM, int WN, int STAGES, int KPI>
-static int launch_glds_kpi(const GemmArgs& a, hipStream_t s) {
-    const int tiles = ceil_div(a.M, BM) * ceil_div(a.N, BN);
-    dim3 grid(tiles * a.splitk), block(WM * WN * 64);
-    hipLaunchKernelGGL((gemm_glds_kernel<T, OutT, BM, BN, WM, WN, STAGES, 0, false, KPI>), grid, block, 0, s, a);
-    DIMX_HIP(hipGetLastError());
-    return DIMX_OK;
-}
-
-template <typename T, typename OutT, int BM, int BN, int WM, int WN, int STAGES, int ABL = 0>
+template <typename T, typename OutT, int BM, int BN, int WM, int WN, int STAGES>
 static int launch_glds(const GemmArgs& a, hipStream_t s) {
     const int tiles = ceil_div(a.M, BM) * ceil_div(a.N, BN);
     dim3 grid(tiles * a.splitk), block(WM * WN * 64);
-    if (a.tile_map == 1) grid = dim3(8 * ((ceil_div(a.M, BM) + 3) / 4) * (ceil_div(a.N, BN) / 2));
     // one 32-row slice per wave (MI == 1) is where staging pays (128x128 on 8 waves: -12..-39 %); with two slices per
     // wave (the 4-wave 128x128 and the 256-wide tiles) it measured 30-40 % slower than direct stores
-    if constexpr (BM * BN >= 128 * 128 && ABL == 0 && BM / (WM * 32) == 1) {
+    if constexpr (BM * BN >= 128 * 128 && BM / (WM * 32) == 1) {
         if (a.stage_out) {
-            hipLaunchKernelGGL((gemm_glds_kernel<T, OutT, BM, BN, WM, WN, STAGES, ABL, true>), grid, block, 0, s, a);
+            hipLaunchKernelGGL((gemm_glds_kernel<T, OutT, BM, BN, WM, WN, STAGES, true>), grid, block, 0, s, a);
             DIMX_HIP(hipGetLastError());
             return DIMX_OK;
         }
     }
-    hipLaunchKernelGGL((gemm_glds_kernel<T, OutT, BM, BN, WM, WN, STAGES, ABL>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((gemm_glds_kernel<T, OutT, BM, BN, WM, WN, STAGES>), grid, block, 0, s, a);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
@@ -1537,36 +1313,22 @@ static int launch_cfg(const GemmArgs& a, hipStream_t s) {
     return DIMX_OK;
 }
 
-// cfg ids (GemmArgs.cfg, 0 = automatic): tile / waves / ring depth of the LDS-DMA kernel
-//  1: 128x128 2 stages   2: 128x128 3 stages   3: 64x64 4 stages   4: 64x64 3 stages   5: 64x64 2 stages
-//  6: 128x64 3 stages    7: 128x64 2 stages    8: 64x128 3 stages
+// cfg ids (GemmArgs.cfg, 0 = automatic): tile / waves / ring depth of the LDS-DMA kernels
+//  1: 128x128 4 waves 2 stages   3: 64x64 4 stages   4: 64x64 3 stages   14: 128x128 8 waves 2 stages
+// 34: 64x64 loader/consumer 4 stages   35: the same, 6 stages   72: 64x72 loader/consumer (bf16)
+// (Measured dead ends, removed: 256-row tiles, deeper 128x128 rings, two k-tiles per iteration, 5- and 8-slot loader/consumer
+// rings -- DESIGN section 6.)
 template <typename T, typename OutT> static int launch_by_cfg(const GemmArgs& a, int cfg, hipStream_t s) {
-    DIMX_REQUIRE(!a.w_tiled || (cfg >= 34 && cfg <= 40), DIMX_ERR_ARG, "gemm: block-tiled W is read by the decode kernel only (cfg %d)", cfg);
-    DIMX_REQUIRE(!a.ln_stats || (((cfg >= 34 && cfg <= 37) || cfg == 72) && a.splitk == 1 && a.ln_colsum && a.ln_C > 0 &&
+    DIMX_REQUIRE(!a.w_tiled || cfg == 34 || cfg == 35, DIMX_ERR_ARG, "gemm: block-tiled W is read by the decode kernel only (cfg %d)", cfg);
+    DIMX_REQUIRE(!a.ln_stats || ((cfg == 34 || cfg == 35 || cfg == 72) && a.splitk == 1 && a.ln_colsum && a.ln_C > 0 &&
                                  a.K >= 16 * Elem<T>::kPerChunk),
                  DIMX_ERR_ARG, "gemm: the deferred-LayerNorm epilogue exists in the decode kernel only, without split-K, from two "
                                "k-tiles up (cfg %d, K %d)", cfg, a.K);
     switch (cfg) {
         case 1: return launch_glds<T, OutT, 128, 128, 2, 2, 2>(a, s);
-        case 3:
-            if (a.prof) return launch_glds<T, OutT, 64, 64, 2, 2, 4, 3>(a, s);
-            return launch_glds<T, OutT, 64, 64, 2, 2, 4>(a, s);
+        case 3: return launch_glds<T, OutT, 64, 64, 2, 2, 4>(a, s);
         case 4: return launch_glds<T, OutT, 64, 64, 2, 2, 3>(a, s);
         case 14: return launch_glds<T, OutT, 128, 128, 4, 2, 2>(a, s);  // 8 waves
-#ifdef DIMX_GEMM_TUNING  // measured dead ends, kept for A/B runs: DIMX_TUNING=1 python __graft_entry__.py build
-        case 18: return launch_glds<T, OutT, 256, 128, 4, 2, 2>(a, s);  // 8 waves, 96 KB ring
-        case 19: return launch_glds<T, OutT, 256, 256, 4, 2, 2>(a, s);  // 8 waves, 128 KB ring
-        case 31: return launch_glds<T, OutT, 256, 128, 4, 2, 3>(a, s);  // 8 waves, 144 KB ring, 2 tiles in flight
-        case 29: return launch_glds<T, OutT, 128, 128, 4, 2, 4>(a, s);  // 8 waves, 128 KB ring, 3 tiles in flight
-        case 30: return launch_glds<T, OutT, 128, 128, 4, 2, 3>(a, s);  // 8 waves, 96 KB ring
-        case 32: return launch_glds_kpi<T, OutT, 64, 64, 2, 2, 2, 2>(a, s);  // 64x64, 2 k-tiles per iteration, 64 KB
-        case 33: return launch_glds_kpi<T, OutT, 64, 64, 2, 2, 3, 2>(a, s);  // ... 3 groups deep, 96 KB
-        case 36: return launch_ws<T, OutT, 5>(a, s);  // loader/consumer kernel, 80 KB ring (two blocks per CU just fit)
-        case 37: return launch_ws<T, OutT, 8>(a, s);  // ... 128 KB ring
-        case 38: return launch_ws<T, OutT, 4, 1>(a, s);  // ablations of 34 (wrong results by construction)
-        case 39: return launch_ws<T, OutT, 4, 2>(a, s);
-        case 40: return launch_ws<T, OutT, 4, 3>(a, s);
-#endif
         case 72:  // 64x72, 6 consumer + 4 loader waves, one block per CU (bf16 operands)
             if constexpr (sizeof(T) == 2) return launch_ws72<OutT>(a, s);
             break;
@@ -1580,12 +1342,7 @@ template <typename T, typename OutT> static int launch_by_cfg(const GemmArgs& a,
 
 static inline void cfg_tile(int cfg, int& bm, int& bn) {
     switch (cfg) {
-        case 1: case 2: case 11: case 14: case 15: case 22: case 23: case 25: case 26: case 29: case 30: bm = 128; bn = 128; break;
-        case 6: case 7: case 12: case 13: case 24: bm = 128; bn = 64; break;
-        case 16: bm = 256; bn = 64; break;
-        case 17: case 18: case 27: case 31: bm = 256; bn = 128; break;
-        case 19: case 28: bm = 256; bn = 256; break;
-        case 8: bm = 64; bn = 128; break;
+        case 1: case 14: bm = 128; bn = 128; break;
         case 72: bm = 64; bn = 72; break;
         default: bm = 64; bn = 64; break;
     }
@@ -1605,9 +1362,11 @@ template <typename T, typename OutT> static int launch_typed(const GemmArgs& a0,
     }
     int cfg = a.cfg;
     // measured on MI355X: 128x128 8-wave for large M; bf16 from 288 tiles (the dW of a 1152 x 4608 projection at 4 800 rows:
-    // 122.9 us on the 64 x 64 kernel, 80.4 on this one; 228 tiles and fewer: level or behind -- profiles/r03_train_gemm.txt)
-    if (cfg == 0) cfg = tiles128 >= (sizeof(T) == 2 ? 288 : 512) ? 14 : gemm_cfg_small();
-    if (a.cfg == 0 && sizeof(T) == 4 && a.out_slabs) cfg = gemm_cfg_small();  // f32 slabs: one tile shape whatever M is (see gemm_plan_splits)
+    // 122.9 us on the 64 x 64 kernel, 80.4 on this one; 228 tiles and fewer: level or behind -- profiles/r03_train_gemm.txt).
+    // Small M: 64x64 with a 4-deep ring, loader + consumer waves (34) over the 4-wave kernel (3): qkv 10.3 -> 8.8, ff1 13.1 ->
+    // 12.1, ff2 11.9 -> 11.0 us, +1.0..1.5 % end to end on the same box; deeper rings (5, 6, 8 slots) are slower.
+    if (cfg == 0) cfg = tiles128 >= (sizeof(T) == 2 ? 288 : 512) ? 14 : 34;
+    if (a.cfg == 0 && sizeof(T) == 4 && a.out_slabs) cfg = 34;  // f32 slabs: one tile shape whatever M is (see gemm_plan_splits)
     if (a.cfg == 0 && gemm_use_ws72(a0)) cfg = 72;
     DIMX_REQUIRE(cfg != 72 || (sizeof(T) == 2 && a.N % 72 == 0 && !a.w_tiled && a.nseg == 1 && a.seg[0].sd == 1 && a.seg[0].sh == 0 &&
                                a.seg[0].sb == a.seg[0].st * (long)a.rowT && a.rowadd_mode == 0),
@@ -1616,18 +1375,10 @@ template <typename T, typename OutT> static int launch_typed(const GemmArgs& a0,
         a.splitk = gemm_plan_splits(a0);
         a.residual = nullptr;
     }
-    static const int tile_map_env = getenv("DIMX_TILE_MAP") ? atoi(getenv("DIMX_TILE_MAP")) : 0;
-    {
-        int bm, bn;
-        cfg_tile(cfg, bm, bn);
-        const int tm = ceil_div(a.M, bm), tn = ceil_div(a.N, bn);
-        a.tile_map = (tile_map_env == 1 && a.splitk == 1 && tm >= 32 && tn >= 2 && tn % 2 == 0) ? 1 : 0;
-    }
     // large-M outputs leave through LDS as 16-byte row pieces (epilogue_staged) when the output map allows it
     a.stage_out = 0;
     a.vt_pack4 = 0;
-    static const bool no_stage = getenv("DIMX_NO_STAGE") != nullptr;
-    if (!no_stage && !a.out_slabs && a.M >= 2048 && (a.rowT == 1 || a.rowT >= 32)) {
+    if (!a.out_slabs && a.M >= 2048 && (a.rowT == 1 || a.rowT >= 32)) {
         const int epo = 16 / (int)sizeof(OutT);
         (void)epo;
         bool ok = a.N % 4 == 0 && (a.nseg == 1 || a.seg_width % 32 == 0), any_row = false, pack = true;
@@ -1707,7 +1458,7 @@ int gemm_plan_splits(const GemmArgs& a) {
     if (cfg == 72) {
         // one block per CU and no more (round 5, profiles/r05_gemm_blocks.txt): the largest split count that keeps the launch within
         // 256 blocks with at least min_nk k-tiles per block
-        static const int min_nk72 = getenv("DIMX_SPLIT_MINNK") ? atoi(getenv("DIMX_SPLIT_MINNK")) : 6;
+        constexpr int min_nk72 = 6;
         int sp = 256 / tiles;
         const int max_sp = nk / min_nk72 > 0 ? nk / min_nk72 : 1;
         sp = sp > max_sp ? max_sp : sp;
@@ -1715,8 +1466,8 @@ int gemm_plan_splits(const GemmArgs& a) {
         return splitk_nonempty(nk, sp);
     }
     // measured (tools/bench_gemm.py under rocprofv3): ~288 blocks (one per CU + a few) is the sweet spot
-    static const int target = getenv("DIMX_SPLIT_TARGET") ? atoi(getenv("DIMX_SPLIT_TARGET")) : 288;
-    static const int min_nk = getenv("DIMX_SPLIT_MINNK") ? atoi(getenv("DIMX_SPLIT_MINNK")) : 6;  // k-tiles per split at least (swept 3..9)
+    constexpr int target = 288;
+    constexpr int min_nk = 6;  // k-tiles per split at least (swept 3..9)
     int sp = (target + tiles / 2) / tiles;
     const int max_sp = nk / min_nk > 0 ? nk / min_nk : 1;
     sp = sp > max_sp ? max_sp : sp;
@@ -1724,30 +1475,16 @@ int gemm_plan_splits(const GemmArgs& a) {
     return splitk_nonempty(nk, sp);
 }
 
-static int gemm_cfg_small() {
-    // measured on MI355X: 64x64 with a 4-deep ring for decode, loader + consumer waves (34) over the 4-wave kernel (3):
-    // qkv 10.3 -> 8.8, ff1 13.1 -> 12.1, ff2 11.9 -> 11.0 us, +1.0..1.5 % end to end on the same box; deeper rings
-    // (36: 5, 35: 6, 37: 8 slots) are slower (tools/gemm_ab.py)
-    static const int cfg_small = getenv("DIMX_GEMM_CFG_SMALL") ? atoi(getenv("DIMX_GEMM_CFG_SMALL")) : 34;
-    return cfg_small;
-}
-
 // the 64 x 72 one-block-per-CU decode kernel: bf16 operands, the LDS-DMA path, a decode-sized M, N a multiple of 72 whose
-// tiles fit the chip in one round (DIMX_NO_WS72=1: the 64 x 64 kernel everywhere, for A/B runs)
+// tiles fit the chip in one round
 static bool gemm_use_ws72(const GemmArgs& a) {
-    static const bool off = getenv("DIMX_NO_WS72") != nullptr;
-    if (off || a.in_dtype != DIMX_BF16 || gemm_cfg_small() != 34) return false;
+    if (a.in_dtype != DIMX_BF16) return false;
     const int kext = a.kloop ? a.kloop : a.ldw;
     if (a.conv_T != 0 || a.K % 64 != 0 || a.K != kext || a.force_simple || a.w_tiled) return false;
     if (a.M > 256 || a.N % 72 != 0) return false;
     // its epilogue stores to a plain row-major destination only (what gemm_set_plain_out builds; the decode step's GEMMs)
     if (a.nseg != 1 || a.seg[0].sd != 1 || a.seg[0].sh != 0 || a.seg[0].sb != a.seg[0].st * (long)a.rowT || a.rowadd_mode != 0) return false;
     return ceil_div(a.M, 64) * (a.N / 72) <= 256;
-}
-
-bool gemm_decode_has_ln_epilogue() {
-    const int c = gemm_cfg_small();
-    return c >= 34 && c <= 37;
 }
 
 int launch_gemm(const GemmArgs& a, hipStream_t s) {
@@ -1790,31 +1527,6 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
     DIMX_REQUIRE(a.out_dtype == DIMX_F32, DIMX_ERR_ARG, "gemm: f32 inputs produce f32 outputs");
     if (gemm_use_x3(a)) return launch_gemm_x3(a, s);   // round 6: decode-sized f32 GEMMs on the bf16 matrix cores, f32-equivalent (gemm_x3.hip)
     return launch_typed<float, float>(a, s);
-}
-
-
-// which: 0 = both roles in one launch, 1 = GEMM blocks only, 2 = attention blocks only (same kernel, same geometry)
-int launch_fused_probe(const GemmArgs& g0, const DecodeAttnArgs& d, int which, unsigned* hw_id, hipStream_t s) {
-    GemmArgs g = g0;
-    DIMX_REQUIRE(g.in_dtype == DIMX_BF16 && d.dtype == DIMX_BF16 && d.q_f32 && !d.knew, DIMX_ERR_ARG, "fused_probe: bf16, cross form");
-    DIMX_REQUIRE(g.K % 64 == 0 && g.ldw == g.K && d.n_keys <= 2048, DIMX_ERR_ARG, "fused_probe: shape");
-    g.splitk = 1;
-    const int n_gemm = which == 2 ? 0 : ceil_div(g.M, 64) * ceil_div(g.N, 64);
-    const int n_attn = which == 1 ? 0 : ceil_div(d.B * d.H, 8);
-    const int npad = (d.n_keys + 15) / 16 * 16;
-    DIMX_REQUIRE(8 * npad * 4 <= 4 * 16384, DIMX_ERR_ARG, "fused_probe: too many keys for the shared LDS window");
-    const int total = n_gemm + n_attn;
-    const int grid = (total + 15) / 16 * 16;  // whole (XCD round, parity pair) groups: surplus blocks return at once
-    const size_t lds = 4 * 16384;
-#define FP(OT)                                                                                                      \
-    do {                                                                                                            \
-        (void)hipFuncSetAttribute((const void*)fused_probe_kernel<OT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((fused_probe_kernel<OT>), dim3(grid), dim3(512), lds, s, g, d, n_gemm, n_attn, npad, hw_id);  \
-    } while (0)
-    if (g.out_dtype == DIMX_BF16) FP(bf16); else FP(float);
-#undef FP
-    DIMX_HIP(hipGetLastError());
-    return DIMX_OK;
 }
 
 }  // namespace dimx

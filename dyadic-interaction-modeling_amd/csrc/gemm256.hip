@@ -8,11 +8,9 @@
 // phase structure in which the two waves of a SIMD alternate between a matrix segment and a load segment:
 //   * 256 x 256 block tile, BK = 64, 8 waves as 2 (M) x 4 (N); a k-tile is four 16 KiB half-tiles in LDS (A rows
 //     0-127 / 128-255, W rows 0-127 / 128-255), two k-tile buffers = 128 KiB.
-//   * a k-tile is four phases, one BLOCK quadrant (128 x 128) each; in a phase every wave multiplies its 64 x 32 piece
-//     of that quadrant over K = 64 (8 x v_mfma_f32_32x32x16_bf16).  Quadrant order (0,0) (0,1) (1,1) (1,0): the A
-//     fragments are re-read only when the row half changes and the first W half stays in registers, so a half-tile
-//     is released one per phase and re-staged one per phase (2 global_load_lds per wave), five phases ahead of its
-//     first read: 64 KiB of DMA in flight all the time, `s_waitcnt vmcnt(8)` once per phase, never vmcnt(0).
+//   * a k-tile is two phases, one BLOCK row half (two 128 x 128 quadrants) each; in a phase every wave multiplies its
+//     64 x 64 piece of that row half over K = 64 (16 x v_mfma_f32_32x32x16_bf16), and the half-tiles it has finished
+//     with are re-staged by LDS-DMA from inside the MFMA segment (gemm256p2_kernel below has the schedule).
 //   * waves 4-7 run half a phase behind waves 0-3 (one extra s_barrier at the start): on every SIMD one wave is in
 //     its MFMA segment while its partner issues ds_reads / DMA -- two raw s_barriers per phase keep them in step.
 //   * persistent blocks: a block walks its output tiles back to back, the staging cursor simply runs on into the next
@@ -34,7 +32,6 @@ typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kHalf = 16384;        // one half-tile: 128 rows x 128 B
 constexpr int kBuf = 4 * kHalf;     // one k-tile: A0h A1h B0h B1h
-constexpr int kDefaultVar = 4;  // 4 = the two-phase loop (gemm256p2_kernel); 0..3 = the four-phase loop's DMA placements (tuning)
 constexpr bool kOverlapEpi = true;
 constexpr bool kPrio = true;  // s_setprio(1) around the MFMA segments: +7 % (without it 35.8 -> 33.3 % on the fused K/V projection)
 constexpr int kLds = 2 * kBuf;
@@ -60,10 +57,6 @@ struct Big {
     OutSeg seg[8];
     int nseg, seg_width;
     int tiles_m, tiles_n, n_group, nkt;
-    unsigned long long* prof;  // tuning only (PROF instantiation): interval sums of block 0, waves 0 and 4
-    int nt_max;                // tiles of the busiest block
-    unsigned desync_slack, desync_full;  // start delay (shader cycles) spread over blocks with / without a spare tile slot
-    int abl;                   // tuning (DIMX_G256_ABL): 1 = no global stores in the epilogue, 2 = non-temporal bf16 stores
 };
 
 template <int ACT> __device__ __forceinline__ float act256(float x) {
@@ -275,7 +268,7 @@ __device__ __forceinline__ void store_chunk(const Big& a, const EpiTile<OutT>& e
                     b += 8;
                 }
             }
-            if (m >= a.M || n >= a.N || (a.abl & 1)) continue;
+            if (m >= a.M || n >= a.N) continue;
             OutT* p = pcol + off;
             if (BF) {
                 uint4 o = __builtin_bit_cast(uint4, raw[i]);
@@ -318,362 +311,19 @@ __device__ __forceinline__ void store_chunk(const Big& a, const EpiTile<OutT>& e
     }
 }
 
-// VAR = where the two LDS-DMA pieces of a phase's half-tile re-staging are issued (tools/g256_var.py measures them):
-//   0  both in the load segment (round 2)
-//   1  both inside the wave's own MFMA segment of the PREVIOUS phase (same landing distance, no DMA in the load segment)
-//   2  first piece in the load segment, second after the fourth MFMA of the same phase
-//   3  both inside the MFMA segment of the same phase (after the 2nd and the 6th MFMA)
-// A load segment that carries two DMA issues next to 4-12 ds_read_b128 is longer than the partner's 8-MFMA segment (the
-// texture addresser takes 8 wave instructions from the four loading waves at once); among bare MFMAs an issue is cheap.
-// PROF: s_memtime stamps at the three points of a phase where lgkmcnt(0) holds anyway (MFMA segment start / end, after the
-// closing barrier); block 0, waves 0 and 4 write 4 x 3 interval sums + the k-tile count to a.prof.
-template <typename OutT, int ACT, bool PLAIN, int VAR, bool PROF>
-__global__ __launch_bounds__(512) void gemm256_kernel(const Big a) {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: LDS-DMA destinations / M0 stay on the SALU
-    const int wr = wave >> 2, wc = wave & 3;
-    const int half = lane >> 5, l31 = lane & 31;
-    const int x = blockIdx.x & 7, j = blockIdx.x >> 3, nb = gridDim.x >> 3;
-
-    // ---- this block's tiles: XCD-local indices j, j + nb, ...
-    int ntiles = 0;
-    {
-        int tm, tn;
-        for (int q = j; tile_of(a, x, q, tm, tn); q += nb) ++ntiles;
-    }
-    if (ntiles == 0) return;
-    const int nkt = a.nkt;
-    const long total = (long)ntiles * nkt;  // k-tiles this block computes
-    // De-phase the blocks.  Persistent blocks of equal work run in lock step, so all 256 reach their epilogue together:
-    // a 32 MB burst of stores (every CU's 128 KiB tile) that the memory side takes ~15k cycles to absorb while no CU
-    // computes, then silence on the write path for a whole tile.  A start delay spread over one tile time turns that
-    // into a steady stream under the other CUs' MFMA work.  Blocks with a spare tile slot (fewer tiles than the busiest
-    // block) take the delay for free; the busiest blocks take desync_full (0 unless no block has slack).
-    {
-        const unsigned span = ntiles < a.nt_max ? a.desync_slack : a.desync_full;
-        if (span) {
-            const unsigned frac = ((blockIdx.x * 0x9E3779B1u) >> 16) & 0xffffu;  // well-spread over the blocks of every XCD
-            const unsigned long long wait = ((unsigned long long)span * frac) >> 16;
-            unsigned long long t0, t1;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
-            do {
-                __builtin_amdgcn_s_sleep(32);
-                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
-            } while (t1 - t0 < wait);
-        }
-    }
-
-    // ---- DMA addressing: wave w moves local rows [16w, 16w + 16) of every half-tile as two 8-row pieces.  The W
-    // half-tiles hold PERMUTED columns: local row lr of column half nh is column (lr / 32) * 64 + nh * 32 + lr % 32 of
-    // the tile, so that a wave's two 32-column blocks are adjacent in the output (64 contiguous columns per row).
-    const int r0 = 16 * wave + (lane >> 3), r1 = r0 + 8;
-    const int dc0 = ((lane & 7) ^ ((r0 >> 1) & 7)) * 8, dc1 = ((lane & 7) ^ ((r1 >> 1) & 7)) * 8;
-    const int wcol0 = (r0 >> 5) * 64 + (r0 & 31), wcol1 = (r1 >> 5) * 64 + (r1 & 31);
-    const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
-    // A staging cursor covers one row half and one column half of the k-tile it points at (hA, hB fixed per cursor);
-    // the four source pointers advance by one k-tile (128 B) per step and are rebuilt when the tile changes.
-    struct Cur {
-        int q, kt, hA, hB;
-        unsigned a0, a1, b0, b1;  // element offsets from a.A / a.W (< 2^32: checked by the launcher)
-    };
-    auto bind_tile = [&](Cur& c) {
-        int tm, tn;
-        if (!tile_of(a, x, c.q, tm, tn)) return false;  // past the end: keep the previous tile (dummy re-staging)
-        const int mo = tm * 256 + c.hA * 128, no = tn * 256 + c.hB * 32;
-        int ra = mo + r0, rb = mo + r1, na = no + wcol0, nbb = no + wcol1;
-        ra = ra < a.M ? ra : a.M - 1;
-        rb = rb < a.M ? rb : a.M - 1;
-        na = na < a.N ? na : a.N - 1;
-        nbb = nbb < a.N ? nbb : a.N - 1;
-        c.a0 = (unsigned)ra * (unsigned)a.lda + dc0;
-        c.a1 = (unsigned)rb * (unsigned)a.lda + dc1;
-        c.b0 = (unsigned)na * (unsigned)a.ldw + dc0;
-        c.b1 = (unsigned)nbb * (unsigned)a.ldw + dc1;
-        return true;
-    };
-    auto advance = [&](Cur& c) {
-        if (++c.kt == nkt) {
-            c.kt = 0;
-            c.q += nb;
-            if (!bind_tile(c)) {  // rewind the pointers of the kept tile
-                c.a0 -= (unsigned)(nkt - 1) * 64; c.a1 -= (unsigned)(nkt - 1) * 64;
-                c.b0 -= (unsigned)(nkt - 1) * 64; c.b1 -= (unsigned)(nkt - 1) * 64;
-            }
-        } else {
-            c.a0 += 64; c.a1 += 64; c.b0 += 64; c.b1 += 64;
-        }
-    };
-    // piece 0 / 1 of a half-tile's re-staging (PC = -1: both)
-    auto stage_a = [&](const Cur& c, int buf, int pc) {
-        unsigned char* dst = smem + buf * kBuf + c.hA * kHalf + wave * 2048;
-        if (pc != 1) __builtin_amdgcn_global_load_lds((glb_void_t*)(a.A + c.a0), (lds_void_t*)dst, 16, 0, 0);
-        if (pc != 0) __builtin_amdgcn_global_load_lds((glb_void_t*)(a.A + c.a1), (lds_void_t*)(dst + 1024), 16, 0, 0);
-    };
-    auto stage_b = [&](const Cur& c, int buf, int pc) {
-        unsigned char* dst = smem + buf * kBuf + (2 + c.hB) * kHalf + wave * 2048;
-        if (pc != 1) __builtin_amdgcn_global_load_lds((glb_void_t*)(a.W + c.b0), (lds_void_t*)dst, 16, 0, 0);
-        if (pc != 0) __builtin_amdgcn_global_load_lds((glb_void_t*)(a.W + c.b1), (lds_void_t*)(dst + 1024), 16, 0, 0);
-    };
-
-    // ---- fragment addressing (local row inside a half-tile; the swizzle term depends on l31 only)
-    const unsigned sw = (l31 >> 1) & 7;
-    unsigned aaddr[4], baddr[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const unsigned ko = ((unsigned)(2 * ks + half) ^ sw) << 4;
-        aaddr[ks] = lds0 + (wr * 64 + l31) * 128 + ko;
-        baddr[ks] = lds0 + 2 * kHalf + (wc * 32 + l31) * 128 + ko;
-    }
-
-    f32x16_t acc[2][2][2];  // [row half][col half][row block]
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) (&acc[0][0][0])[i][r] = 0.f;
-
-    // ---- prologue: A0h B0h B1h A1h of k-tile 0, A0h B0h of k-tile 1 (the steady-state issue order)
-    int cu_q = j, cu_kt = 0, cu_m0 = 0, cu_n0 = 0;  // compute cursor
-    {
-        int tm, tn;
-        tile_of(a, x, cu_q, tm, tn);
-        cu_m0 = tm * 256;
-        cu_n0 = tn * 256;
-    }
-    Cur c2{j, 0, 0, 0, 0u, 0u, 0u, 0u};  // halves (A0h, B0h): runs two k-tiles ahead
-    Cur c1{j, 0, 1, 1, 0u, 0u, 0u, 0u};  // halves (A1h, B1h): runs one k-tile ahead
-    bind_tile(c2);
-    bind_tile(c1);
-    stage_a(c2, 0, -1);
-    stage_b(c2, 0, -1);
-    stage_b(c1, 0, -1);
-    stage_a(c1, 0, -1);
-    advance(c2);  // -> k-tile 1
-    advance(c1);  // -> k-tile 1
-    stage_a(c2, 1, -1);
-    stage_b(c2, 1, -1);
-    advance(c2);  // -> k-tile 2
-    if (VAR == 1) {  // phase 1's re-staging is issued one phase early in this form
-        stage_b(c1, 1, -1);
-        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    }
-    raw_barrier();
-    if (wr == 1) raw_barrier();  // waves 4-7 run half a phase behind
-
-    unsigned long long psum[17];
-    unsigned long long tprev = 0;
-    if (PROF) {
-#pragma unroll
-        for (int i = 0; i < 17; ++i) psum[i] = 0;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory");
-    }
-#define G256_STAMP(SLOT)                                                                    \
-    do {                                                                                    \
-        if (PROF) {                                                                         \
-            unsigned long long tn_;                                                         \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tn_)::"memory");     \
-            psum[SLOT] += tn_ - tprev;                                                      \
-            tprev = tn_;                                                                    \
-        }                                                                                   \
-    } while (0)
-#define G256_WAIT_LOADSEG()                                                   \
-    do {                                                                      \
-        if (PROF && (a.abl & 8)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-        if (VAR == 2) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");        \
-        else if (VAR == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   \
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                 \
-    } while (0)
-// one MFMA segment: quadrant accumulators ACC[0..1] += FB[ks] x fa[rb][ks]; H1 / H2 / H3 run after the 2nd / 4th / 6th MFMA
-#define G256_MFMA_SEG(ACC, FB, H1, H2, H3)                                                                              \
-    do {                                                                                                                \
-        if (kPrio) __builtin_amdgcn_s_setprio(1);                                                                       \
-        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                              \
-            _Pragma("unroll") for (int rb = 0; rb < 2; ++rb)                                                            \
-                ACC[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, FB[ks]),                 \
-                                                                  __builtin_bit_cast(bf16x8_t, fa[rb][ks]), ACC[rb], 0, 0, 0); \
-            if (VAR != 0) {                                                                                             \
-                __builtin_amdgcn_sched_barrier(0);                                                                      \
-                if (ks == 0) { H1; }                                                                                    \
-                if (ks == 1) { H2; }                                                                                    \
-                if (ks == 2) { H3; }                                                                                    \
-                __builtin_amdgcn_sched_barrier(0);                                                                      \
-            }                                                                                                           \
-        }                                                                                                               \
-        if (kPrio) __builtin_amdgcn_s_setprio(0);                                                                       \
-    } while (0)
-#define G256_NOP ((void)0)
-
-    u32x4_t fa[2][4], fb0[4], fb1[4];
-    unsigned bo = 0;  // byte offset of the k-tile buffer being computed
-    for (long g = 0; g < total; ++g) {
-        const int buf = (int)(bo != 0);
-        // ================= phase 1: quadrant (0,0) -- read A(row half 0) and W(col half 0); stage B1h of g + 1
-        {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                if (!(PROF && (a.abl & 4))) ds_read128<0>(fb0[ks], baddr[ks] + bo);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                if (PROF && (a.abl & 16)) continue;
-                ds_read128<0>(fa[0][ks], aaddr[ks] + bo);
-                ds_read128<4096>(fa[1][ks], aaddr[ks] + bo);
-            }
-        }
-        if (VAR == 0) stage_b(c1, buf ^ 1, -1);
-        if (VAR == 2) stage_b(c1, buf ^ 1, 0);
-        if (PROF && (a.abl & 8)) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); G256_STAMP(13); }
-        G256_WAIT_LOADSEG();
-        raw_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        G256_STAMP(0);
-        if (VAR == 1) G256_MFMA_SEG(acc[0][0], fb0, stage_a(c1, buf ^ 1, 0), G256_NOP, stage_a(c1, buf ^ 1, 1));
-        else if (VAR == 2) G256_MFMA_SEG(acc[0][0], fb0, G256_NOP, stage_b(c1, buf ^ 1, 1), G256_NOP);
-        else if (VAR == 3) G256_MFMA_SEG(acc[0][0], fb0, stage_b(c1, buf ^ 1, 0), G256_NOP, stage_b(c1, buf ^ 1, 1));
-        else G256_MFMA_SEG(acc[0][0], fb0, G256_NOP, G256_NOP, G256_NOP);
-        G256_STAMP(1);
-        raw_barrier();
-        G256_STAMP(2);
-        // ================= phase 2: quadrant (0,1) -- read W(col half 1); stage A1h of g + 1
-        {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) ds_read128<kHalf>(fb1[ks], baddr[ks] + bo);
-        }
-        if (VAR == 0) stage_a(c1, buf ^ 1, -1);
-        if (VAR == 2) stage_a(c1, buf ^ 1, 0);
-        if (PROF && (a.abl & 8)) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); G256_STAMP(14); }
-        G256_WAIT_LOADSEG();
-        raw_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        G256_STAMP(3);
-        if (VAR == 1) G256_MFMA_SEG(acc[0][1], fb1, stage_a(c2, buf, 0), G256_NOP, stage_a(c2, buf, 1));
-        else if (VAR == 2) G256_MFMA_SEG(acc[0][1], fb1, G256_NOP, stage_a(c1, buf ^ 1, 1), G256_NOP);
-        else if (VAR == 3) G256_MFMA_SEG(acc[0][1], fb1, stage_a(c1, buf ^ 1, 0), G256_NOP, stage_a(c1, buf ^ 1, 1));
-        else G256_MFMA_SEG(acc[0][1], fb1, G256_NOP, G256_NOP, G256_NOP);
-        G256_STAMP(4);
-        raw_barrier();
-        G256_STAMP(5);
-        advance(c1);
-        // ================= phase 3: quadrant (1,1) -- read A(row half 1); stage A0h of g + 2
-        {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                ds_read128<kHalf>(fa[0][ks], aaddr[ks] + bo);
-                ds_read128<kHalf + 4096>(fa[1][ks], aaddr[ks] + bo);
-            }
-        }
-        if (VAR == 0) stage_a(c2, buf, -1);
-        if (VAR == 2) stage_a(c2, buf, 0);
-        if (PROF && (a.abl & 8)) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); G256_STAMP(15); }
-        G256_WAIT_LOADSEG();
-        raw_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        G256_STAMP(6);
-        if (VAR == 1) G256_MFMA_SEG(acc[1][1], fb1, stage_b(c2, buf, 0), G256_NOP, stage_b(c2, buf, 1));
-        else if (VAR == 2) G256_MFMA_SEG(acc[1][1], fb1, G256_NOP, stage_a(c2, buf, 1), G256_NOP);
-        else if (VAR == 3) G256_MFMA_SEG(acc[1][1], fb1, stage_a(c2, buf, 0), G256_NOP, stage_a(c2, buf, 1));
-        else G256_MFMA_SEG(acc[1][1], fb1, G256_NOP, G256_NOP, G256_NOP);
-        G256_STAMP(7);
-        raw_barrier();
-        G256_STAMP(8);
-        // ================= phase 4: quadrant (1,0) -- everything is in registers; stage B0h of g + 2
-        if (VAR == 0) stage_b(c2, buf, -1);
-        if (VAR == 2) stage_b(c2, buf, 0);
-        if (PROF && (a.abl & 8)) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); G256_STAMP(16); }
-        G256_WAIT_LOADSEG();
-        raw_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        G256_STAMP(9);
-        if (VAR == 1) {  // c1 already points one k-tile further (advanced after phase 2): next phase 1's B1h into THIS buffer
-            G256_MFMA_SEG(acc[1][0], fb0, stage_b(c1, buf, 0), G256_NOP, stage_b(c1, buf, 1));
-        } else if (VAR == 2) G256_MFMA_SEG(acc[1][0], fb0, G256_NOP, stage_b(c2, buf, 1), G256_NOP);
-        else if (VAR == 3) G256_MFMA_SEG(acc[1][0], fb0, stage_b(c2, buf, 0), G256_NOP, stage_b(c2, buf, 1));
-        else G256_MFMA_SEG(acc[1][0], fb0, G256_NOP, G256_NOP, G256_NOP);
-        G256_STAMP(10);
-        raw_barrier();
-        G256_STAMP(11);
-        advance(c2);
-        bo ^= (unsigned)kBuf;
-
-        // ================= end of an output tile: store, clear, move on (no barriers in here)
-        if (++cu_kt == nkt) {
-            unsigned char* scratch = smem + kLds + wave * 4096;
-            // Both wave groups store at the same time: group 0 lets group 1 finish its last MFMA segment first (one extra
-            // barrier here), group 1 pays its extra barrier after the stores -- the half-phase stagger is the same afterwards.
-            // Without the pair the stagger barriers serialise the two epilogues (group 1 waits for group 0's stores at its
-            // closing barrier, then group 0 waits for group 1's).
-            if (kOverlapEpi && wr == 0) raw_barrier();
-            const EpiTile<OutT> et = epi_tile<OutT>(a, cu_n0 + wc * 64, lane);
-            ResPiece res[2];
-            load_residual<OutT, PLAIN>(a, et, cu_m0 + wr * 64, cu_n0 + wc * 64, lane, res[0]);
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch) {
-                const int mh = ch >> 1, rb = ch & 1;
-                if (ch < 3)
-                    load_residual<OutT, PLAIN>(a, et, cu_m0 + ((ch + 1) >> 1) * 128 + wr * 64 + ((ch + 1) & 1) * 32, cu_n0 + wc * 64, lane,
-                                               res[(ch + 1) & 1]);
-                store_chunk<OutT, ACT, PLAIN>(a, et, acc[mh][0][rb], acc[mh][1][rb], cu_m0 + mh * 128 + wr * 64 + rb * 32,
-                                              cu_n0 + wc * 64, scratch, lane, res[ch & 1]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    acc[mh][0][rb][r] = 0.f;
-                    acc[mh][1][rb][r] = 0.f;
-                }
-            }
-            cu_kt = 0;
-            cu_q += nb;
-            int tm, tn;
-            if (tile_of(a, x, cu_q, tm, tn)) {
-                cu_m0 = tm * 256;
-                cu_n0 = tn * 256;
-            }
-            if (kOverlapEpi && wr == 1) raw_barrier();
-            if (PROF) {  // own epilogue in its own slot
-                unsigned long long tn_;
-                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tn_)::"memory");
-                psum[12] += tn_ - tprev;
-                tprev = tn_;
-            }
-        }
-    }
-    if (wr == 0) raw_barrier();  // balance the stagger
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // dummy stagings past the end must land before the LDS is released
-    if (PROF && a.prof && blockIdx.x == 0 && (wave == 0 || wave == 4) && lane == 0) {
-        unsigned long long* o = a.prof + (wave >> 2) * 32;
-#pragma unroll
-        for (int i = 0; i < 17; ++i) o[i] = psum[i];
-        o[17] = (unsigned long long)total;
-    }
-#undef G256_STAMP
-#undef G256_WAIT_LOADSEG
-#undef G256_MFMA_SEG
-#undef G256_NOP
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Two phases per k-tile (round 3; the default).  The four-phase loop above pays two barrier rendezvous per 8 MFMAs of a wave.
-// Here a phase is HALF a k-tile -- both column halves of one row half, 16 MFMAs per wave -- so the same rendezvous cost is
-// paid half as often:
+// Two phases per k-tile (round 3).  A four-phase loop (one quadrant, 8 MFMAs per wave and phase; rounds 2-3, since removed)
+// paid two barrier rendezvous per 8 MFMAs of a wave.  Here a phase is HALF a k-tile -- both column halves of one row half,
+// 16 MFMAs per wave -- so the same rendezvous cost is paid half as often:
 //   phase A: read W(col half 0), W(col half 1), A(row half 0)  [16 ds_read_b128];  quadrants (0,0) and (0,1)
 //   phase B: read A(row half 1)                                 [ 8 ds_read_b128];  quadrants (1,1) and (1,0)
 // Staging: the three half-tiles phase A reads are free after it and are re-staged (k-tile g + 2) inside phase B's MFMA
 // segment (6 LDS-DMA pieces per wave, one after every second MFMA); A(row half 1) is read in phase B and re-staged inside
 // the next phase A (2 pieces).  Every half-tile is issued >= 3 phases before its first read and retired by a counted
 // vmcnt one phase before it (vmcnt(6) in phase A's load segment leaves phase B's six pieces in flight, vmcnt(2) in phase
-// B's leaves phase A's two).  Waves 4-7 still run half a phase behind waves 0-3; the epilogue and the tile walk are
-// the four-phase kernel's.
-// Measured on the K/V projection (M 76800, N 6144, K 1152; tools/g256_var.py, same box, interleaved): 40.4 % of the bf16
-// peak against 39.2 % for the four-phase loop.  Forms that measured behind it: all eight pieces in the load segments
-// (4 + 4, clean 16-MFMA segments): 38.8 %; 4 + 4 inside the segments with the issue slots alternating between even and odd
-// waves (a wave-uniform branch per slot): 35.7 %.  Ablations of this loop (wrong results, stores off): no LDS-DMA 49.8 %, no
-// ds_read 55.7 %, MFMAs alone 70.7 %, the barrier / bookkeeping skeleton alone takes 348 us of the 1040; the same kernel on
-// zero-filled operands runs 36 % faster (846 vs 1149 us): with random operands the matrix pipe is power-limited to ~1.75
-// GHz, so ~72 % of the 2.4 GHz peak is all there is to reach.
+// B's leaves phase A's two).  Waves 4-7 run half a phase behind waves 0-3.
+// Measured on the K/V projection (M 76800, N 6144, K 1152; same box, interleaved): 40.4 % of the bf16 peak against 39.2 %
+// for the four-phase loop.  Forms that measured behind it: all eight pieces in the load segments
 template <typename OutT, int ACT, bool PLAIN>
 __global__ __launch_bounds__(512) void gemm256p2_kernel(const Big a) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -921,22 +571,20 @@ __global__ __launch_bounds__(512) void gemm256p2_kernel(const Big a) {
 
 // Eligible: bf16 operands, K % 64 == 0, row-contiguous destinations, enough rows to fill the chip.
 bool gemm256_eligible(const GemmArgs& g) {
-    static const bool off = getenv("DIMX_NO_G256") != nullptr;
-    if (off || g.in_dtype != DIMX_BF16 || g.conv_T != 0 || g.out_slabs || g.force_simple) return false;
+    if (g.in_dtype != DIMX_BF16 || g.conv_T != 0 || g.out_slabs || g.force_simple) return false;
     const int kext = g.kloop ? g.kloop : g.ldw;
     if (g.K % 64 != 0 || g.K != kext || g.M < 4096 || g.N < 256 || g.N % 8 != 0) return false;
     // measured (tools/bench_prefill.py, round 3, two-phase loop + scalar epilogue): ahead of the 128 x 128 kernel on every
     // prefill shape with min(N, K) >= 384 and N K >= 384 x 1536 -- (N 1536, K 384) 225 -> 199 us, (N 384, K 1536) 156 -> 128 us,
     // (N 2304, K 384) 276 -> 174 us, (N 1152, K 384: the VQ stacks' fused q/k/v, row-contiguous since V went row-major) 131 -> 85 us,
     // level from K = 1152 up; the 384 x 384 projections stay behind (76 -> 106 us here)
-    static const bool all = getenv("DIMX_G256_ALL") != nullptr;
-    if (!all && (g.K < 384 || g.N < 384 || (long)g.N * g.K < 384L * 1152L)) return false;
+    if (g.K < 384 || g.N < 384 || (long)g.N * g.K < 384L * 1152L) return false;
     // ... and only with enough 256 x 256 tiles for the 256 CUs: at 4 800 rows (a training batch, a 16-clip prefill) N 768 K 1152
     // has 57 tiles and took 29.7 us against 18.9 on the 128 x 128 kernel, N 384 K 1536 (38 tiles) 33.1 against 13.0 on the
     // 64 x 64 one, 95 tiles (N 1152) 6 - 15 % behind; N 4608 K 1152 (342 tiles) 68.9 against 85.5 stays, and so do the 114 tiles
     // of N 1536 K 384 with the GELU / bf16 epilogue (a 16-clip prefill was 0.5 ms slower without them) -- tools/
     // bench_train_gemm.py, profiles/r03_train_gemm.txt
-    if (!all && (long)ceil_div(g.M, 256) * ceil_div(g.N, 256) < 100) return false;
+    if ((long)ceil_div(g.M, 256) * ceil_div(g.N, 256) < 100) return false;
     if ((size_t)g.M * g.lda >= (1ull << 32) || (size_t)g.N * g.ldw >= (1ull << 32)) return false;  // 32-bit element offsets
     if (g.bias && ((uintptr_t)g.bias % 16)) return false;
     if (g.residual && (g.ldr % 4 || (uintptr_t)g.residual % 16)) return false;
@@ -985,8 +633,6 @@ static int launch_big(const GemmArgs& g, const OutSeg* segs, int nseg, int seg_w
     ng = ng < 1 ? 1 : (ng > a.tiles_n ? a.tiles_n : ng);
     const int ngroups = ceil_div(a.tiles_n, ng);
     a.n_group = ceil_div(a.tiles_n, ngroups);
-    static const int ng_env = getenv("DIMX_G256_NGROUP") ? atoi(getenv("DIMX_G256_NGROUP")) : 0;  // tuning
-    if (ng_env > 0) a.n_group = ng_env > a.tiles_n ? a.tiles_n : ng_env;
     static int cus = 0;
     if (!cus) {
         int dev = 0;
@@ -995,47 +641,7 @@ static int launch_big(const GemmArgs& g, const OutSeg* segs, int nseg, int seg_w
     }
     const int grid = cus / 8 * 8;
     DIMX_REQUIRE(grid >= 8, DIMX_ERR_ARG, "gemm256: device with %d CUs", cus);
-    {
-        // start-delay spans (see the kernel): one tile time ~ nkt x 2900 shader cycles (measured: 2.5 us per k-tile at
-        // ~1.8 GHz with the epilogue bursts, ~1.6 us without).  Blocks with a spare slot: a full tile time.  When every
-        // block has the same number of tiles nobody has slack: a quarter tile over all blocks still pays from ~8 tiles up.
-        const int tt = a.tiles_m * a.tiles_n, nbx = grid / 8;
-        int nt_max = 0, nt_min = 1 << 30;
-        for (int x8 = 0; x8 < 8; ++x8) {
-            const int cnt = (int)((long)tt * (x8 + 1) / 8) - (int)((long)tt * x8 / 8);
-            const int hi = ceil_div(cnt, nbx), lo = cnt / nbx;
-            nt_max = hi > nt_max ? hi : nt_max;
-            nt_min = lo < nt_min ? lo : nt_min;
-        }
-        a.nt_max = nt_max;
-        static const char* de = getenv("DIMX_G256_DESYNC");  // "slack_permille,full_permille"
-        int ps = 0, pf = 0;  // measured (round 3): any start delay costs more than it returns -- the epilogue is bound by the CU's own store path, not by a chip-wide write burst
-        if (de) {
-            ps = atoi(de);
-            const char* c = strchr(de, ',');
-            pf = c ? atoi(c + 1) : 0;
-        }
-        const double tile_cycles = (double)a.nkt * 2900.0;
-        a.desync_slack = (unsigned)(tile_cycles * ps / 1000.0);
-        a.desync_full = (unsigned)(tile_cycles * pf / 1000.0);
-        static const int abl_env = getenv("DIMX_G256_ABL") ? atoi(getenv("DIMX_G256_ABL")) : 0;
-        a.abl = abl_env;
-    }
-    // tuning (tools/g256_var.py): DMA placement variant and the in-kernel interval profile, bf16 / no-activation instantiation only
-    static const int var_env = getenv("DIMX_G256_VAR") ? atoi(getenv("DIMX_G256_VAR")) : kDefaultVar;
-    static const bool prof_env = getenv("DIMX_G256_PROF") != nullptr;
-    static unsigned long long* prof_buf = nullptr;
     const bool plain = !g.bias && !g.residual && !g.rowadd_mode;  // epilogue without bias / positional rows / residual
-    const bool tunable = g.out_dtype == DIMX_BF16 && g.act == ACT_NONE && plain;
-    const int var = tunable ? var_env : kDefaultVar;
-    const bool prof = tunable && prof_env;
-    if (prof && !prof_buf) DIMX_HIP(hipMalloc((void**)&prof_buf, 64 * sizeof(unsigned long long)));
-    a.prof = prof ? prof_buf : nullptr;
-#define G256_(OT, AC, PL, VR, PF)                                                                                           \
-    do {                                                                                                                    \
-        (void)hipFuncSetAttribute((const void*)gemm256_kernel<OT, AC, PL, VR, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal); \
-        hipLaunchKernelGGL((gemm256_kernel<OT, AC, PL, VR, PF>), dim3(grid), dim3(512), kLdsTotal, s, a);                   \
-    } while (0)
 #define G256P2_(OT, AC, PL)                                                                                             \
     do {                                                                                                                \
         (void)hipFuncSetAttribute((const void*)gemm256p2_kernel<OT, AC, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal); \
@@ -1054,20 +660,7 @@ static int launch_big(const GemmArgs& g, const OutSeg* segs, int nseg, int seg_w
             default: G256P2(OT, ACT_NONE); break;                \
         }                                                        \
     } while (0)
-    if (tunable && (var != kDefaultVar || prof)) {  // the four-phase loop's forms: A/B runs and the in-kernel profile
-        switch (var * 2 + (prof ? 1 : 0)) {
-            case 0: G256_(bf16, ACT_NONE, true, 0, false); break;
-            case 1: G256_(bf16, ACT_NONE, true, 0, true); break;
-            case 2: G256_(bf16, ACT_NONE, true, 1, false); break;
-            case 3: G256_(bf16, ACT_NONE, true, 1, true); break;
-            case 4: G256_(bf16, ACT_NONE, true, 2, false); break;
-            case 5: G256_(bf16, ACT_NONE, true, 2, true); break;
-            case 6: G256_(bf16, ACT_NONE, true, 3, false); break;
-            case 7: G256_(bf16, ACT_NONE, true, 3, true); break;
-            case 9: G256_(bf16, ACT_NONE, true, 3, true); break;  // DIMX_G256_PROF without a VAR: the four-phase loop's stamps
-            default: DIMX_REQUIRE(false, DIMX_ERR_ARG, "gemm256: DIMX_G256_VAR=%d", var);
-        }
-    } else if (g.out_dtype == DIMX_BF16) {
+    if (g.out_dtype == DIMX_BF16) {
         G256P2_ACT(bf16);
     } else {
         G256P2_ACT(float);
@@ -1075,20 +668,6 @@ static int launch_big(const GemmArgs& g, const OutSeg* segs, int nseg, int seg_w
 #undef G256P2_ACT
 #undef G256P2
 #undef G256P2_
-#undef G256_
-    if (prof) {  // tuning only: synchronous read-back of block 0's interval sums (waves 0 and 4)
-        unsigned long long hst[64];
-        DIMX_HIP(hipStreamSynchronize(s));
-        DIMX_HIP(hipMemcpy(hst, prof_buf, sizeof(hst), hipMemcpyDeviceToHost));
-        for (int w = 0; w < 2; ++w) {
-            const double n = (double)hst[w * 32 + 17];
-            fprintf(stderr, "g256prof var %d wave %d ktiles %.0f :", var, w * 4, n);
-            for (int i = 0; i < 12; ++i) fprintf(stderr, " %.0f", (double)hst[w * 32 + i] / (n > 0 ? n : 1));
-            fprintf(stderr, " | reads done");
-            for (int i = 13; i < 17; ++i) fprintf(stderr, " %.0f", (double)hst[w * 32 + i] / (n > 0 ? n : 1));
-            fprintf(stderr, " | epilogue per tile %.0f\n", (double)hst[w * 32 + 12] / (n > 0 ? n / a.nkt : 1));
-        }
-    }
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

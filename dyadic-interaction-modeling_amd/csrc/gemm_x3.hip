@@ -68,8 +68,9 @@ __device__ __forceinline__ float x3_act(int act, float x) {
     return x;
 }
 
-template <int NCB, int BN, int STAGES = 4>
+template <int NCB, int BN>
 struct X3 {
+    static constexpr int STAGES = 4;                   // ring depth in k-tiles (5 measured no faster)
     static constexpr int BM = 128, BK = 32, NCONS = 4 * NCB, THREADS = (NCONS + 4) * 64;
     static constexpr int A_BYTES = BM * 128;           // f32 rows of 32 k
     static constexpr int P_BYTES = NCB * 16 * 128;     // one W plane: NCB * 32 rows of 64 B, two per LDS row
@@ -123,10 +124,9 @@ struct X3 {
             const int y = issued - (st + 1);  // k-tiles issued behind slot st: 0 .. STAGES - 2
             if (y <= 0) wait_vmcnt<0>();
             else if (y == 1) wait_vmcnt<LPT>();
-            else if (y == 2 || STAGES < 5) wait_vmcnt<2 * LPT>();
-            else wait_vmcnt<3 * LPT>();
+            else wait_vmcnt<2 * LPT>();
             __builtin_amdgcn_s_barrier();
-            if (issued < nk && !(a.tile_map & 1)) {   // tile_map: ablation bits of tools (DIMX_X3_ABL; results are then wrong)
+            if (issued < nk) {
                 issue(issued, slot_next);
                 ++issued;
                 slot_next = slot_next + 1 == STAGES ? 0 : slot_next + 1;
@@ -219,26 +219,16 @@ struct X3 {
                          : "memory");
         };
         auto compute = [&](const Frag& f) {
-            if (a.tile_map & 2) return;   // ablation: fragments read, nothing computed
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 u32x4_t p0, p1, p2;
-                if (a.tile_map & 8) {   // ablation: no operand split (the raw fragment registers stand in for the planes; wrong results)
-                    p0 = f.a[ks][0];
-                    p1 = f.a[ks][1];
-                    p2 = f.a[ks][0];
-                } else {
-                    x3_split8(f.a[ks][0], f.a[ks][1], p0, p1, p2);
-                }
+                x3_split8(f.a[ks][0], f.a[ks][1], p0, p1, p2);
                 const bf16x8_t A0 = __builtin_bit_cast(bf16x8_t, p0), A1 = __builtin_bit_cast(bf16x8_t, p1), A2 = __builtin_bit_cast(bf16x8_t, p2);
                 // fixed order, smallest terms first: a2 w0, a1 w1, a0 w2 (2^-16), a1 w0, a0 w1 (2^-8), a0 w0
 #define DIMX_X3_MMA(AP, WPL) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AP, __builtin_bit_cast(bf16x8_t, f.w[ks][WPL]), acc, 0, 0, 0)
-                if (!(a.tile_map & 4)) {   // DIMX_X3_ABL=4 (measurement only, NOT a parity mode): the three 2^-16 terms dropped =
-                                           // two bf16 planes per operand, 16 significand bits -- what does "half the MFMAs" cost in tokens?
-                    DIMX_X3_MMA(A2, 0);
-                    DIMX_X3_MMA(A1, 1);
-                    DIMX_X3_MMA(A0, 2);
-                }
+                DIMX_X3_MMA(A2, 0);
+                DIMX_X3_MMA(A1, 1);
+                DIMX_X3_MMA(A0, 2);
                 DIMX_X3_MMA(A1, 0);
                 DIMX_X3_MMA(A0, 1);
                 DIMX_X3_MMA(A0, 0);
@@ -290,10 +280,10 @@ struct X3 {
     }
 };
 
-template <int NCB, int BN, int STAGES>
-__global__ __launch_bounds__((X3<NCB, BN, STAGES>::THREADS)) void gemm_x3_kernel(const GemmArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[X3<NCB, BN, STAGES>::SMEM_BYTES];
-    X3<NCB, BN, STAGES>::body(a, blockIdx.x, gridDim.x, smem);
+template <int NCB, int BN>
+__global__ __launch_bounds__((X3<NCB, BN>::THREADS)) void gemm_x3_kernel(const GemmArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[X3<NCB, BN>::SMEM_BYTES];
+    X3<NCB, BN>::body(a, blockIdx.x, gridDim.x, smem);
 }
 
 // W f32 -> three bf16 planes (truncation splits: p0 + p1 + p2 == w exactly)
@@ -362,20 +352,11 @@ int launch_gemm_x3(const GemmArgs& a0, hipStream_t s) {
     a.splitk = sp;
     if (a.out_slabs) a.residual = nullptr;
     const int blocks = ceil_div(a.M, 128) * (a.N / bn) * sp;
-    static const int abl = getenv("DIMX_X3_ABL") ? atoi(getenv("DIMX_X3_ABL")) : 0;       // tuning: 1 no DMA in the loop, 2 no compute, 4 three products only, 8 no operand split
-    static const int stages = getenv("DIMX_X3_STAGES") ? atoi(getenv("DIMX_X3_STAGES")) : 4; // tuning: ring depth of the two-column-block tiles (5 measured no faster)
-    a.tile_map = abl;
     switch (bn) {
-        case 96: hipLaunchKernelGGL((gemm_x3_kernel<3, 96, 4>), dim3(blocks), dim3(1024), 0, s, a); break;
-        case 72: hipLaunchKernelGGL((gemm_x3_kernel<3, 72, 4>), dim3(blocks), dim3(1024), 0, s, a); break;
-        case 64:
-            if (stages == 5) hipLaunchKernelGGL((gemm_x3_kernel<2, 64, 5>), dim3(blocks), dim3(768), 0, s, a);
-            else hipLaunchKernelGGL((gemm_x3_kernel<2, 64, 4>), dim3(blocks), dim3(768), 0, s, a);
-            break;
-        default:
-            if (stages == 5) hipLaunchKernelGGL((gemm_x3_kernel<2, 36, 5>), dim3(blocks), dim3(768), 0, s, a);
-            else hipLaunchKernelGGL((gemm_x3_kernel<2, 36, 4>), dim3(blocks), dim3(768), 0, s, a);
-            break;
+        case 96: hipLaunchKernelGGL((gemm_x3_kernel<3, 96>), dim3(blocks), dim3(1024), 0, s, a); break;
+        case 72: hipLaunchKernelGGL((gemm_x3_kernel<3, 72>), dim3(blocks), dim3(1024), 0, s, a); break;
+        case 64: hipLaunchKernelGGL((gemm_x3_kernel<2, 64>), dim3(blocks), dim3(768), 0, s, a); break;
+        default: hipLaunchKernelGGL((gemm_x3_kernel<2, 36>), dim3(blocks), dim3(768), 0, s, a); break;
     }
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;

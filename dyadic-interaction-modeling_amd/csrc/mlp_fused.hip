@@ -69,26 +69,17 @@ struct MlpArgs {
     const float* ln_g;     // [C]
     const float* ln_b;     // [C] or null
     int M, nchunk;
-    int stagger;           // start delay step in units of 64 shader cycles: block b of the first wave of blocks waits (b % 8) * stagger
-    int abl;               // tuning (DIMX_MLP_ABL): 1 = no DMA inside the loop, 2 = no GELU, 4 = no chunk loop at all
 };
 
-// ABLC (tuning, DIMX_MLP_ABL bits 8 / 16 on the tanh + beta instantiation): 8 = no fragment reads in the loop, 16 = no MFMAs in the loop
 // (The out-projection-in-the-prologue variant of round 4 measured break-even against the separate launch and was removed in
 // round 5: profiles/r04_mlp_fused_outproj.txt, git history 572449b.)
-template <int ACT, bool BETA, int ABLC = 0> __global__ __launch_bounds__(256) void mlp_fused_kernel(const MlpArgs a) {
+template <int ACT, bool BETA> __global__ __launch_bounds__(256) void mlp_fused_kernel(const MlpArgs a) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, hf = lane >> 5, l31 = lane & 31;
     const int row = blockIdx.x * 128 + wave * 32 + l31;
     const int rowc = row < a.M ? row : a.M - 1;
     const unsigned lds0 = (unsigned)(size_t)(lds_void_t*)smem;
     const unsigned char* wp = (const unsigned char*)a.wp;
-    // Every CU's first block would run its prologue (196 KB of x per block) at the same moment, and then all the epilogues collide:
-    // the first wave of blocks starts staggered so that the memory phases of different CUs fall beside each other's compute.
-    if (a.stagger > 0 && blockIdx.x < 256) {
-        const int n = (int)(blockIdx.x & 7) * a.stagger;
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1);   // 64 cycles each
-    }
 
     // The weight stream: per chunk 25 W1 pieces + 24 W2 pieces of 1 KiB, each a linear LDS-DMA (lane l moves bytes [16 l, 16 l + 16)).
     // Wave w issues pieces w, w + 4, ...; W1 and W2 have their own 2-slot rings because the pipeline below reads W1 of chunk c + 2
@@ -239,15 +230,13 @@ template <int ACT, bool BETA, int ABLC = 0> __global__ __launch_bounds__(256) vo
     // read in iteration c - 1 (W1(c), pre-loop for c = 0 .. 1; W2(c - 1)), which every wave has left once it passed this iteration's
     // barrier.  What iteration c reads was issued in the FIRST half of iteration c - 1 (W1: groups 0 .. 5) and in iteration c - 2 (W2:
     // groups 6 .. 11), so the wait at the top leaves the 6 youngest pieces in flight.
-    const int loops = (a.abl & 4) ? 0 : nch;
     int s0 = 0, s2 = 2;    // c % 3, (c + 2) % 3
-    for (int c = 0; c < loops; ++c) {
+    for (int c = 0; c < nch; ++c) {
         // in-order return: all but this wave's 6 youngest pieces -- the W2(c + 1) pieces issued in the second half of iteration
         // c - 1, not read before iteration c + 1 -- have landed
         asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         const int cw1 = wrap(c + 3), cw2 = wrap(c + 2);
-        const bool dma = !(a.abl & 1);
         const unsigned b1 = rd1 + s2 * (kW1Frags * 1024);   // W1(c + 2)
         const unsigned b2 = rd2 + s0 * (kW2Frags * 1024);   // W2(c)
 #pragma unroll
@@ -263,19 +252,17 @@ template <int ACT, bool BETA, int ABLC = 0> __global__ __launch_bounds__(256) vo
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fr[gg][q]) : "v"(b1), "i"((2 * gg + q) * 1024));
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fr[gg][2 + q]) : "v"(b2), "i"((2 * gg + q) * 1024));
             }
-        if (dma) issue_piece(12, cw1, s0, cw2, s2);
+        issue_piece(12, cw1, s0, cw2, s2);
 #pragma unroll
         for (int g = 0; g < kOB; ++g) {
             // fragments travel two groups ahead of their MFMAs (LDS returns in order)
             if (g + 2 < kOB) {
-                if (!(ABLC & 8)) {
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fr[(g + 2) % 3][q]) : "v"(b1), "i"((2 * (g + 2) + q) * 1024));
-                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fr[(g + 2) % 3][2 + q]) : "v"(b2), "i"((2 * (g + 2) + q) * 1024));
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+                for (int q = 0; q < 2; ++q) {
+                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fr[(g + 2) % 3][q]) : "v"(b1), "i"((2 * (g + 2) + q) * 1024));
+                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fr[(g + 2) % 3][2 + q]) : "v"(b2), "i"((2 * (g + 2) + q) * 1024));
                 }
+                asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
             } else if (g + 1 < kOB) {
                 asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
             } else {
@@ -283,21 +270,13 @@ template <int ACT, bool BETA, int ABLC = 0> __global__ __launch_bounds__(256) vo
             }
             __builtin_amdgcn_sched_barrier(0);
             const u32x4_t c0 = {hbc[0], hbc[1], hbc[2], hbc[3]}, c1v = {hbc[4], hbc[5], hbc[6], hbc[7]};
-            if (!(ABLC & 16)) {
-                if (g == 0) h_next = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fbias), xb[kKS], h_next, 0, 0, 0);
-                h_next = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][0]), xb[2 * g], h_next, 0, 0, 0);
-                h_next = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][1]), xb[2 * g + 1], h_next, 0, 0, 0);
-            } else {
-                h_next[g] += __builtin_bit_cast(float, fr[g % 3][0][0]) + __builtin_bit_cast(float, fr[g % 3][1][1]);
-            }
-            if (dma) issue_piece(g, cw1, s0, cw2, s2);
-            if (!(ABLC & 16)) {
-                o[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][2]), __builtin_bit_cast(bf16x8_t, c0), o[g], 0, 0, 0);
-                o[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][3]), __builtin_bit_cast(bf16x8_t, c1v), o[g], 0, 0, 0);
-            } else {
-                o[g][0] += __builtin_bit_cast(float, fr[g % 3][2][0]) + __builtin_bit_cast(float, fr[g % 3][3][1]) + __builtin_bit_cast(float, hbc[g & 7]);
-            }
-            if (g >= 2 && g < 10) hbn[g - 2] = (a.abl & 2) ? hbc[g - 2] : gelu_pair(h_mid, g - 2);
+            if (g == 0) h_next = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fbias), xb[kKS], h_next, 0, 0, 0);
+            h_next = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][0]), xb[2 * g], h_next, 0, 0, 0);
+            h_next = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][1]), xb[2 * g + 1], h_next, 0, 0, 0);
+            issue_piece(g, cw1, s0, cw2, s2);
+            o[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][2]), __builtin_bit_cast(bf16x8_t, c0), o[g], 0, 0, 0);
+            o[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fr[g % 3][3]), __builtin_bit_cast(bf16x8_t, c1v), o[g], 0, 0, 0);
+            if (g >= 2 && g < 10) hbn[g - 2] = gelu_pair(h_mid, g - 2);
         }
 #pragma unroll
         for (int r = 0; r < 8; ++r) hbc[r] = hbn[r];
@@ -373,17 +352,9 @@ int launch_mlp_fused(float* x, const void* packed, const float* b2, const float*
                  DIMX_ERR_ARG, "mlp_fused: operands must be 16-byte aligned");
     MlpArgs a;
     a.x = x; a.wp = packed; a.b2 = b2; a.ln_g = ln_g; a.ln_b = ln_b; a.M = M; a.nchunk = F / 32;
-    static const int abl = getenv("DIMX_MLP_ABL") ? atoi(getenv("DIMX_MLP_ABL")) : 0;
-    a.abl = abl;
-    static const int stagger = getenv("DIMX_MLP_STAGGER") ? atoi(getenv("DIMX_MLP_STAGGER")) : 0;
-    a.stagger = stagger;
     DIMX_REQUIRE(a.nchunk >= 3, DIMX_ERR_ARG, "mlp_fused: F = %d is too small for the three-deep pipeline", F);
     const size_t lds = (size_t)kStages * kChunkBytes;
     const dim3 grid((M + 127) / 128);
-    if (abl & 24) {
-        DIMX_HIP(hipFuncSetAttribute((const void*)mlp_fused_kernel<ACT_GELU_TANH, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DIMX_HIP(hipFuncSetAttribute((const void*)mlp_fused_kernel<ACT_GELU_TANH, true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
 #define MLP_LAUNCH(A, B)                                                                                                              \
     do {                                                                                                                              \
         /* per launch, not once per process: the attribute is per device and the call is cheap */                     \
@@ -391,9 +362,7 @@ int launch_mlp_fused(float* x, const void* packed, const float* b2, const float*
         hipLaunchKernelGGL((mlp_fused_kernel<A, B>), grid, dim3(256), lds, s, a);                                                     \
     } while (0)
     if (act == ACT_GELU_TANH) {
-        if (ln_b && (abl & 8)) hipLaunchKernelGGL((mlp_fused_kernel<ACT_GELU_TANH, true, 8>), grid, dim3(256), lds, s, a);
-        else if (ln_b && (abl & 16)) hipLaunchKernelGGL((mlp_fused_kernel<ACT_GELU_TANH, true, 16>), grid, dim3(256), lds, s, a);
-        else if (ln_b) MLP_LAUNCH(ACT_GELU_TANH, true); else MLP_LAUNCH(ACT_GELU_TANH, false);
+        if (ln_b) MLP_LAUNCH(ACT_GELU_TANH, true); else MLP_LAUNCH(ACT_GELU_TANH, false);
     } else {
         if (ln_b) MLP_LAUNCH(ACT_GELU_ERF, true); else MLP_LAUNCH(ACT_GELU_ERF, false);
     }

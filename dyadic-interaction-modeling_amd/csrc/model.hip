@@ -328,12 +328,11 @@ static int pack_linear_scaled(dimx_ctx* c, const std::string& wname, const std::
     return DIMX_OK;
 }
 
-// the feed-forward sublayer's weights as the chunk images of mlp_fused.hip (bf16 perf mode, width 384; DIMX_NO_FUSED_MLP=1 keeps
-// the LayerNorm + two-GEMM form for A/B runs)
+// the feed-forward sublayer's weights as the chunk images of mlp_fused.hip (bf16 perf mode, width 384; the f32 mode and other
+// widths keep the LayerNorm + two-GEMM form)
 static int pack_mlp(dimx_ctx* c, const std::string& w1, const std::string& b1, const std::string& w2, const void** out) {
     *out = nullptr;
-    static const bool off = getenv("DIMX_NO_FUSED_MLP") != nullptr;
-    if (off || c->at != DIMX_BF16) return DIMX_OK;
+    if (c->at != DIMX_BF16) return DIMX_OK;
     auto i1 = c->host.find(w1), ib = c->host.find(b1), i2 = c->host.find(w2);
     DIMX_REQUIRE(i1 != c->host.end() && ib != c->host.end() && i2 != c->host.end(), DIMX_ERR_WEIGHT, "missing weight %s", w1.c_str());
     const int F = (int)i1->second.shape[0], C = (int)i1->second.shape[1];
@@ -588,11 +587,10 @@ static int gemm_lin(const dimx_ctx* c, const void* A, int lda, const Linear& L, 
 }
 
 // Perf mode (round 3): V leaves the fused q/k/v projection row-major like q and k -- three row-contiguous destinations, which
-// is what the two-phase 256 x 256 GEMM stores -- and attn_kernel transposes it on the way into LDS (VROW).  The f32 parity mode
-// and the 96-column heads of the legacy speaker VQ-VAE keep the transposed destination.  DIMX_QKV_VT=1: the old form (A/B).
+// is what the two-phase 256 x 256 GEMM stores -- and the attention of attention_tr.hip reads it that way.  The f32 parity mode
+// and the 96-column heads of the legacy speaker VQ-VAE keep the transposed destination.
 static bool qkv_row_v(int at, int D) {
-    static const bool off = getenv("DIMX_QKV_VT") != nullptr;
-    return !off && at == DIMX_BF16 && D <= 64;
+    return at == DIMX_BF16 && D <= 64;
 }
 
 // q / k row-major [M, segw]; v transposed [B,H,D,Tp], or row-major too (rowv)
@@ -856,7 +854,6 @@ int dimx_create(dimx_handle* h, int device_id, const dimx_dims* dims, int numeri
     c->use_graph = (ng && ng[0] == '1') ? 0 : 1;
     const char* nc = getenv("DIMX_NO_CHAIN");
     c->use_chain = (nc && nc[0] == '1') ? 0 : 1;
-    c->defer_ln = getenv("DIMX_NO_DEFER_LN") ? 0 : 1;
     c->use_layer_chain = getenv("DIMX_NO_LAYER_CHAIN") ? 0 : 1;
     c->multi_tr = getenv("DIMX_NO_MULTI_TR") ? 0 : 1;
     if (getenv("DIMX_LAYER_PROF")) {
@@ -869,10 +866,6 @@ int dimx_create(dimx_handle* h, int device_id, const dimx_dims* dims, int numeri
     if (const char* pg = getenv("DIMX_PREFILL_GROUPS")) {
         const int v = atoi(pg);
         if (v >= 1 && v <= dimx_ctx::kPreGroups) c->prefill_groups = v;
-    }
-    if (const char* gu = getenv("DIMX_GRAPH_UNROLL")) {
-        const int u = atoi(gu);
-        if (u >= 1 && u <= 64) c->graph_unroll = u;
     }
     {
         int cus = 0;
@@ -1260,7 +1253,7 @@ int legacy_encode_ctx(dimx_handle h, const float* v_speaker, const uint8_t* mask
 // The prefill-sized stages of a forward are independent per clip, and their kernels leave CUs idle at the end of every launch (the
 // fused feed-forward kernel runs 600 blocks of 128 rows on 256 CUs: the third round is a third full; 128 x 128 and 256 x 256 GEMM
 // tiles end the same way).  As G clip groups on G streams the tails of one group's kernels are filled by another group's blocks:
-// 15.8 -> 14.2 ms for the three stages at 256 x 300 with G = 4 (tools/attic/r05_prefill_streams.py, profiles/r05_prefill_groups.txt).
+// 15.8 -> 14.2 ms for the three stages at 256 x 300 with G = 4 (profiles/r05_prefill_groups.txt).
 // Group 0 runs on the caller's stream, the others on the handle's side streams between a fork and a join event; every group
 // has its own scratch (the same arena, planned group by group).  Both numeric modes: a clip's results do not depend on the batch it is
 // computed in (the f32 mode by contract -- test_c3_batch_and_shard_invariance compares the grouped whole batch with its shards bit for bit).
@@ -1867,11 +1860,10 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     tokens += (size_t)row0 * n;
     if (logits_out) logits_out += (size_t)row0 * n * V;
     // round 4: the sampler that writes the next step's embedding row also writes the first layer's pre-norm of it, so a step
-    // starts with y = LayerNorm(x) in place (DIMX_NO_FUSE_LN0=1: the separate launch, for A/B runs)
-    static const bool fuse_ln0 = getenv("DIMX_NO_FUSE_LN0") == nullptr;
+    // starts with y = LayerNorm(x) in place
     if (embed_only) {  // step 0 input = embedding of the start token (later steps: fused into the sampler)
         DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, start, tokens, n, s.step, s.x, B, S, st, pos, pos_scale));
-        if (fuse_ln0) DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
+        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
         return DIMX_OK;
     }
     // Every projection whose output is a small [B, N] f32 matrix is a split-K GEMM writing per-split slabs;
@@ -1899,8 +1891,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     const bool chain = gen_use_chain(h, B, S, grp);
     // deferred LayerNorm (chain.hip): the two chain launches of a layer write x and bf16(x) un-normalised + partial row
     // sums; cross-q (inside chain A) and ff1 (the next launch) run on gamma-scaled weights and correct their results
-    const bool defer = chain && h->defer_ln && h->chain_stats_dev && h->dec.cross[0].q_ln.w && h->dec.ff[0].f1_ln.w &&
-                       gemm_decode_has_ln_epilogue();
+    const bool defer = chain && h->defer_ln && h->chain_stats_dev && h->dec.cross[0].q_ln.w && h->dec.ff[0].f1_ln.w;
     auto chain_site = [&](int site, const void* A1, int lda1, const Linear* W1, int nslab, const float* gamma,
                           const Linear* W2, float* out2, int ld_out2, const float* colsum2 = nullptr) -> int {
         ChainArgs c;
@@ -1972,8 +1963,6 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         lc.fault = h->chain_fault_inject > 0 ? 1 : 0;
         lc.sc_stride = (T + 15) / 16 * 16;
         lc.prof = h->layer_prof_dev ? h->layer_prof_dev + (size_t)l * 256 * 16 : nullptr;
-        static const int layer_perm = getenv("DIMX_LAYER_PERM") ? atoi(getenv("DIMX_LAYER_PERM")) : 0;
-        lc.perm = layer_perm;
         return true;
     };
     int pending = 0;  // slabs of the previous residual projection not yet folded into x
@@ -1981,7 +1970,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         GemmArgs g;
         DecodeAttnArgs a;
         int ns = 0;
-        if (l > 0 || !fuse_ln0)
+        if (l > 0)
             DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.self_[l].ln_g, B, DD, st));
         DIMX_TRY(slab_gemm(s.y, DD, h->dec.self_[l].qkv, s.qkv, s0.st_qkv, &ns));
         // the two attentions' arguments (self: q / new k / new v are the projection's split-K slabs; cross: the context K/V)
@@ -2005,8 +1994,6 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         sa.H = heads;
         sa.step = s.step;
         sa.scale = scale;
-        static const bool gen_excl = getenv("DIMX_GEN_EXCL") != nullptr;   // round 6: CU-exclusive kernels for two engines
-        sa.clip_blocks = gen_excl && S == 1 ? 1 : 0;
         memset(&ca, 0, sizeof(ca));
         ca.dtype = h->at;
         ca.q = s.qc;
@@ -2026,7 +2013,6 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         ca.kmask = ctx_mask;
         ca.kmask_ld = T;
         ca.scale = scale;
-        ca.clip_blocks = sa.clip_blocks;
         if (defer && layer_kernel) {
             // round 5: self attention -> out-projection -> cross-q -> cross attention -> out-projection as ONE XCD-local launch
             LayerChainArgs lc;
@@ -2110,7 +2096,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     }
     DIMX_TRY(launch_sample(s.logits, V, B, top_k, temperature, noise, seed, s.step, 0, tokens, n, 1, nlg, s0.st_lg,
                            logits_out, n, row0, Btot, h->dec.tok_emb, DD, s.x, s.step, (unsigned*)(s.step + 8), st, pos,
-                           pos_scale, n, s.step + 2, fuse_ln0 ? s.y : nullptr, h->dec.self_[0].ln_g, h->at));
+                           pos_scale, n, s.step + 2, s.y, h->dec.self_[0].ln_g, h->at));
     return DIMX_OK;
 }
 
@@ -2167,20 +2153,7 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
         if (!h->ev_fork) DIMX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         DIMX_HIP(hipEventRecord(h->ev_fork, st));
         for (int g = 0; g < G; ++g) {
-            if (!h->grp_stream[g]) {
-                static const bool cumask = getenv("DIMX_GEN_CUMASK") != nullptr;
-                if (cumask && h->cu_count > 0 && h->cu_count % 32 == 0) {
-                    // group g runs on its own 1/G of the CUs of every XCD (a CU mask spreads evenly over the XCDs:
-                    // tools/ubench/cumask_probe): the groups then never compete for a CU, only for HBM and L2
-                    const int words = h->cu_count / 32;
-                    std::vector<uint32_t> mask(words, 0u);
-                    const int lo = h->cu_count * g / G, hi = h->cu_count * (g + 1) / G;
-                    for (int i = lo; i < hi; ++i) mask[i >> 5] |= 1u << (i & 31);
-                    DIMX_HIP(hipExtStreamCreateWithCUMask(&h->grp_stream[g], (uint32_t)words, mask.data()));
-                } else {
-                    DIMX_HIP(hipStreamCreateWithFlags(&h->grp_stream[g], hipStreamNonBlocking));
-                }
-            }
+            if (!h->grp_stream[g]) DIMX_HIP(hipStreamCreateWithFlags(&h->grp_stream[g], hipStreamNonBlocking));
             if (!h->ev_join[g]) DIMX_HIP(hipEventCreateWithFlags(&h->ev_join[g], hipEventDisableTiming));
             gs[g] = h->grp_stream[g];
             DIMX_HIP(hipStreamWaitEvent(gs[g], h->ev_fork, 0));
@@ -2324,7 +2297,7 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
         // regenerated with the row-phase LayerNorm (chain kernels stay on).
         h->defer_ln = 0;
         fprintf(stderr, "dimx: a residual row's mean exceeds 8 standard deviations; this batch is regenerated with the row-phase "
-                        "LayerNorm and the deferred form stays off for this handle (DIMX_NO_DEFER_LN=1 avoids it from the start)\n");
+                        "LayerNorm and the deferred form stays off for this handle\n");
     }
     DIMX_TRY(generate_impl(h, start, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
                            ws_bytes, stream, &chain_used));
@@ -2383,10 +2356,6 @@ int dimx_op_gemm(int in_dtype, int out_dtype, const void* A, int lda, const void
     g.cfg = (flags >> 8) & 0xff;           /* tuning: tile/stage config id */
     g.force_splitk = (flags >> 16) & 0xff; /* tuning: split count */
     if (ldw > K && K % (in_dtype == DIMX_BF16 ? 64 : 32) == 0) g.kloop = K; /* padded row stride, exact k extent */
-    if (getenv("DIMX_GEMM_PROF") && residual && M <= 1024) {
-        g.prof = (unsigned long long*)residual; /* tools/gemm_phases.py smuggles its stamp buffer in here */
-        g.residual = nullptr;
-    }
     if (conv_T > 0) {
         g.conv_T = conv_T;
         g.conv_lens = conv_lens;
@@ -2590,40 +2559,6 @@ int dimx_op_decode_attn(int dtype, const void* q, const void* kcache, const void
     return launch_decode_attn(a, (hipStream_t)stream);
 }
 
-int dimx_op_fused_probe(const void* A, const void* W, const float* bias, void* C, int out_dtype, int M, int N, int K, int act,
-                        const void* q, const void* kcache, const void* vcache, void* out, int B, int H, int Tmax, int n_keys,
-                        float scale, const uint8_t* kmask, int which, uint32_t* hw_id, void* stream) {
-    GemmArgs g;
-    gemm_args_init(g);
-    g.in_dtype = DIMX_BF16;
-    g.out_dtype = out_dtype;
-    g.A = A; g.lda = K;
-    g.W = W; g.ldw = K;
-    g.M = M; g.N = N; g.K = K;
-    g.bias = bias;
-    g.act = act;
-    gemm_set_plain_out(g, C, N);
-    DecodeAttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dtype = DIMX_BF16;
-    a.q = q;
-    a.q_ld = H * 64;
-    a.kcache = const_cast<void*>(kcache);
-    a.vcache = const_cast<void*>(vcache);
-    a.Tmax = Tmax;
-    a.out = out;
-    a.o_ld = H * 64;
-    a.B = B;
-    a.H = H;
-    a.n_keys = n_keys;
-    a.kmask = kmask;
-    a.kmask_ld = n_keys;
-    a.scale = scale;
-    a.q_f32 = 1;
-    a.nslab = 1;
-    return launch_fused_probe(g, a, which, hw_id, (hipStream_t)stream);
-}
-
 int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, void* vcache, void* out, int B, int H,
                              int Tmax, const int32_t* step_dev, float scale, int q_is_f32, void* stream) {
     DecodeAttnArgs a;
@@ -2767,7 +2702,6 @@ int dimx_op_chain(const void* A1, int K1, const void* W1, float* x, const float*
     c.err = u + 129;
     DIMX_REQUIRE(chain_supported(c, cus), DIMX_ERR_ARG, "op_chain: shape not supported on this device (%d CUs)", cus);
     DIMX_HIP(hipMemsetAsync(u, 0, 512 * 4, (hipStream_t)stream));
-    if (getenv("DIMX_CHAIN_PROF")) c.prof = (unsigned long long*)(u + 512 + (size_t)B * C);  // tools/chain_phases.py
     return launch_chain(c, (hipStream_t)stream);
 }
 
@@ -2801,7 +2735,6 @@ int dimx_op_chain_ln(const void* A1, int K1, const void* W1, float* x, void* y, 
     c.err = u + 129;
     DIMX_REQUIRE(chain_supported(c, cus), DIMX_ERR_ARG, "op_chain_ln: shape not supported on this device (%d CUs)", cus);
     DIMX_HIP(hipMemsetAsync(u, 0, 512 * 4, (hipStream_t)stream));
-    if (getenv("DIMX_CHAIN_PROF")) c.prof = (unsigned long long*)(u + 512 + (size_t)B * C);
     return launch_chain(c, (hipStream_t)stream);
 }
 
@@ -2820,10 +2753,6 @@ int dimx_op_gemm_ln(int out_dtype, const void* A, const void* Ws, void* C, int M
     g.ln_stats = stats;
     g.ln_colsum = colsum;
     g.ln_C = K;
-    if (getenv("DIMX_GEMM_PROF")) { /* tools/gemm_phases.py: the bias argument carries the stamp buffer */
-        g.prof = (unsigned long long*)bias;
-        g.bias = nullptr;
-    }
     gemm_set_plain_out(g, C, N);
     return launch_gemm(g, (hipStream_t)stream);
 }
@@ -2862,10 +2791,6 @@ int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk,
     lc.step = nullptr;          // the counters' epoch is the call index; the self-attention reads its own step pointer (sa.step)
     lc.epoch_add = call_index;
     lc.prof = (unsigned long long*)prof;
-    static const int layer_abl = getenv("DIMX_LAYER_ABL") ? atoi(getenv("DIMX_LAYER_ABL")) : 0;   // tuning: results are wrong then
-    lc.abl = layer_abl;
-    static const int layer_perm_op = getenv("DIMX_LAYER_PERM") ? atoi(getenv("DIMX_LAYER_PERM")) : 0;
-    lc.perm = layer_perm_op;
     lc.sc_stride = ((T > n_keys ? T : n_keys) + 15) / 16 * 16;
     int cu = 0, dev = 0;
     DIMX_HIP(hipGetDevice(&dev));

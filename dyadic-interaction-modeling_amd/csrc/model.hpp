@@ -152,7 +152,7 @@ struct dimx_ctx {
     static constexpr int kMaxGroups = 8;
     hipGraphExec_t graph_exec[kMaxGroups] = {};
     hipGraphExec_t graph_multi[kMaxGroups] = {};  // the same step captured graph_unroll times back to back
-    int graph_unroll = 16;                        // DIMX_GRAPH_UNROLL (1 = one launch per step)
+    int graph_unroll = 16;                        // steps per graph_multi launch
     // prefill (VQ encode, encoders + context, VQ decode) as clip groups on several streams (round 5, bf16 mode; DIMX_PREFILL_GROUPS)
     static constexpr int kPreGroups = 4;
     int prefill_groups = 0;             // 0 = automatic, 1 = one batch on the caller's stream, 2..4
@@ -170,7 +170,7 @@ struct dimx_ctx {
     int use_chain = 1;                  // DIMX_NO_CHAIN=1 keeps the one-kernel-per-op step
     int cu_count = 0;
     float* chain_stats_dev = nullptr;   // [8][32][32][2] partial row sums of the deferred-LayerNorm chain kernels
-    int defer_ln = 1;                   // DIMX_NO_DEFER_LN=1 keeps the row-phase LayerNorm inside the chain kernels
+    int defer_ln = 1;                   // 0 (after a row failed the deferred form's range check) keeps the row-phase LayerNorm inside the chain kernels
     unsigned long long* layer_prof_dev = nullptr;  // DIMX_LAYER_PROF=1 (tuning): [8 layers][256 blocks][16] phase stamps of xcd_layer_kernel
     int multi_tr = 1;                   // round 6: several samples per clip (best-of-N), bf16: the decode cross attention on the MFMA prefill
                                         // attention kernel (attention_tr.hip) instead of the VALU multi-query kernel (DIMX_NO_MULTI_TR=1: the latter)

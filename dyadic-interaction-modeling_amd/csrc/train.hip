@@ -774,9 +774,8 @@ int attn_fwd(Step& s, AttnSave& a, const float* h_in, float* h_out, int M, int C
     a.shape.ldk = a.shape.ldv = a.ldkv;
     a.shape.ldo = inner;
     // attention and its adjoints on the matrix cores (train_attn.hip): bf16 MFMA in the perf mode, exact-f32 MFMA in the parity
-    // mode; DIMX_TRAIN_ATTN_VALU=1 keeps the one-wave-per-row f32 VALU kernels (the plain form both are checked against)
-    static const bool valu_only = getenv("DIMX_TRAIN_ATTN_VALU") && atoi(getenv("DIMX_TRAIN_ATTN_VALU")) != 0;
-    a.shape.mfma = valu_only ? 0 : (s.at == DIMX_BF16 ? 1 : 2);
+    // mode (the one-wave-per-row f32 VALU kernels both are checked against stay reachable through dimx_op_train_attention)
+    a.shape.mfma = s.at == DIMX_BF16 ? 1 : 2;
     // the pre-norm is formed inside the operand copy of its projection (a.y only names it)
     if (!cross) {
         DIMX_TRY(lin_fwd(s, a.qkv, a.y, C, M, a.qb, 3 * inner, nullptr, 0, 2, h_in, s.p(a.pre + "0.0.weight")));

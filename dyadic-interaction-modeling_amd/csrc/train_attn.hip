@@ -2,7 +2,7 @@
 // Attend (masked_fill(-max) before a float32 softmax) and its adjoint.  Two element types through one body:
 //   bf16  (perf mode)    v_mfma_f32_32x32x16_bf16, operands rounded to bf16 on the way into LDS, f32 accumulation / statistics
 //   float (parity mode)  v_mfma_f32_32x32x2_f32: exact f32 products, f32 accumulation -- the numerics of the one-wave-per-row
-//                        VALU kernels of train_kernels.hip (kept as the plain reference form, DIMX_TRAIN_ATTN_VALU=1) at a
+//                        VALU kernels of train_kernels.hip (kept as the plain reference form: dimx_op_train_attention, mfma = 0) at a
 //                        thirtieth of their time
 //
 //   forward   O = softmax(scale . Q K^T + masks) V, LSE_i = max_i + log sum_i kept for the backward pass

@@ -1301,11 +1301,9 @@ int tr_prep_fused(int out_dtype, int mode, const float* src, int lds, const floa
     // columns per block: enough blocks to fill the chip (>= ~512) when there are few rows, at most 256 columns (LayerNorm mode: the
     // row statistics are recomputed by every column chunk of a row block, so its chunks stay >= 128 wide)
     {
-        static const int force = getenv("DIMX_PREP_CHUNK") ? atoi(getenv("DIMX_PREP_CHUNK")) : 0;
         int c = (int)((long)Kp * (Mp / 32) / 512) / 64 * 64;
         c = c < 64 ? 64 : (c > 256 ? 256 : c);
         if (mode == 2 && c < 128) c = 128;
-        if (mode == 2 && force > 0) c = force;
         d.chunk = c;
     }
     if (n_part) *n_part = ceil_div(rows, 32);

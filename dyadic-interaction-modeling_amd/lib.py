@@ -114,8 +114,6 @@ SIGNATURES = {
                                        c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "dimx_op_decode_attn": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_float, c_void_p, c_int, c_int, c_void_p]),
-    "dimx_op_fused_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "dimx_op_decode_attn_self": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                          c_void_p, c_float, c_int, c_void_p]),
     "dimx_op_decode_attn_ex": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_int, c_void_p, c_void_p, c_void_p,

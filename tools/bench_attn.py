@@ -1,6 +1,5 @@
-"""Prefill attention at the C3 shapes, event-timed: the row-major-V kernel of attention_tr.hip (default) or, with
-DIMX_ATTN_OLD=1, round 3's attn_kernel<bf16, 2, 64, VROW>.
-    [DIMX_ATTN_OLD=1] python tools/bench_attn.py [B]"""
+"""Prefill attention at the C3 shapes, event-timed: the row-major-V kernel of attention_tr.hip.
+    python tools/bench_attn.py [B]"""
 import sys
 
 import torch

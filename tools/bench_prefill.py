@@ -1,5 +1,5 @@
 """Prefill GEMM shapes of the C3 workload, event-timed (kernels of 100+ us: host overhead is negligible).
-    [DIMX_TILE_MAP=1] python tools/bench_prefill.py [cfg ...]"""
+    python tools/bench_prefill.py [cfg ...]"""
 import sys
 
 import torch

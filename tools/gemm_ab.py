@@ -1,5 +1,5 @@
 """Same-box A/B of the decode GEMM shapes (M=256): average kernel time over a rotating set of weights.
-    python tools/gemm_ab.py            (run once per environment setting, e.g. DIMX_GEMM_ORDER=0 / 1)"""
+    python tools/gemm_ab.py            (run once per DIMX_LIB / GEMM_AB_TILED setting)"""
 import os
 import sys
 
@@ -56,17 +56,16 @@ def run_ln(i):
                                 L.stream_ptr(dev)), "gemm_ln")
 
 
-if os.environ.get("DIMX_GEMM_CFG_SMALL", "34") in ("34", "35", "36", "37"):   # the ln epilogue lives in the loader/consumer kernel
-    for i in range(24):
+for i in range(24):
+    run_ln(i)
+torch.cuda.synchronize()
+best = 1e9
+for rep in range(5):
+    e0.record()
+    for i in range(240):
         run_ln(i)
+    e1.record()
     torch.cuda.synchronize()
-    best = 1e9
-    for rep in range(5):
-        e0.record()
-        for i in range(240):
-            run_ln(i)
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) / 240 * 1e3)
-    res.append("ff1 + ln epilogue %.2f us" % best)
-print("tiled W=%s " % os.environ.get("GEMM_AB_TILED", "0") + "DIMX_GEMM_CFG_SMALL=%s: back-to-back launches, best of 5: %s" % (os.environ.get("DIMX_GEMM_CFG_SMALL", "default"), ", ".join(res)))
+    best = min(best, e0.elapsed_time(e1) / 240 * 1e3)
+res.append("ff1 + ln epilogue %.2f us" % best)
+print("tiled W=%s: back-to-back launches, best of 5: %s" % (os.environ.get("GEMM_AB_TILED", "0"), ", ".join(res)))

@@ -12,7 +12,7 @@ shapes = [l.strip()[len("dimx-gemm "):] for l in open(log, errors="replace") if 
 f = glob.glob(d + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-gemms = [r for r in rows if "gemm" in r["Kernel_Name"] and "fused_probe" not in r["Kernel_Name"]]
+gemms = [r for r in rows if "gemm" in r["Kernel_Name"]]
 print("log lines %d, gemm kernels in the trace %d" % (len(shapes), len(gemms)))
 agg = collections.OrderedDict()
 n = min(len(shapes), len(gemms))

@@ -1,6 +1,10 @@
-"""Fold the MFMA / TCC counter passes over the fused cross-attention K/V projection (tools/attic/r03_profiles.sh step 4) into
-profiles/pmc_gemm256_<kernel-source-hash>.json, the file dimx.roofline.cross_kv_gemm reads `pmc_mfma_busy_pct` from.
-    python tools/pmc_gemm256_record.py <pmc_summary text> <line file of the same run> <commit>"""
+"""Fold the MFMA counter pass over the fused cross-attention K/V projection into profiles/pmc_gemm256_<kernel-source-hash>.json, the
+file dimx.roofline.cross_kv_gemm reads `pmc_mfma_busy_pct` from.  The whole recipe (one counter pass, no other tracing):
+
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
+        SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE --output-format csv -d OUT/pmc_mfma -- python tools/roofline_only.py cross-kv > OUT/line.txt
+    python tools/pmc_summary.py OUT/pmc_mfma | grep -A9 gemm256p2 > OUT/pmc_mfma_cross_kv.txt
+    python tools/pmc_gemm256_record.py OUT/pmc_mfma_cross_kv.txt OUT/line.txt <commit>"""
 import json
 import os
 import re
@@ -13,7 +17,7 @@ from dimx import roofline
 txt, line_file, commit = sys.argv[1], sys.argv[2], sys.argv[3]
 vals, launches, on = {}, 0, False
 for ln in open(txt):
-    if "gemm256p2_kernel" in ln or "gemm256_kernel" in ln:
+    if "gemm256p2_kernel" in ln:
         on = True
         continue
     m = re.match(r"\s+(\w+)\s+n=\s*(\d+)\s+avg=([0-9.eE+-]+)", ln)
@@ -36,7 +40,7 @@ if us:
     rec["shader_clock_GHz_under_pmc"] = cyc / (us * 1e3)
     rec["avg_launch_us_under_pmc"] = us
 rec["note"] = ("MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (kernel cycles x 1024 SIMDs); kernel cycles = GRBM_GUI_ACTIVE / 8; source: "
-               "profiles/%s, launch time under the PMC pass from profiles/%s" % (os.path.basename(txt), os.path.basename(line_file)))
+               "%s, launch time under the PMC pass from %s (tools/pmc_gemm256_record.py has the recipe)" % (os.path.basename(txt), os.path.basename(line_file)))
 out = os.path.join(roofline.PROFILES, "pmc_gemm256_%s.json" % rec["kernel_source_sha256_12"])
 with open(out, "w") as fh:
     json.dump(rec, fh, indent=1)

@@ -1,7 +1,13 @@
-"""Fold the MFMA counter pass over one forward (tools/r05_profiles.sh step 2: SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE, ... over
-`bench.py --steps 1`) into profiles/pmc_prefill_mfma_<hash>.json, where dimx.roofline reads `pmc_mfma_busy_pct` of the prefill's two
-MFMA kernels (mlp_fused_kernel, attn_tr_kernel).  <hash> = sha256[:12] over csrc/mlp_fused.hip + csrc/attention_tr.hip.
-    python tools/pmc_prefill_record.py <pmc_summary text> <commit>"""
+"""Fold the MFMA counter pass over one forward into profiles/pmc_prefill_mfma_<hash>.json, where dimx.roofline reads
+`pmc_mfma_busy_pct` of the prefill's two MFMA kernels (mlp_fused_kernel, attn_tr_kernel).  <hash> = sha256[:12] over
+csrc/mlp_fused.hip + csrc/attention_tr.hip.  The whole recipe (one counter pass, no other tracing; one batch on one stream, so that
+no neighbouring kernel dilutes a kernel's counters):
+
+    DIMX_PREFILL_GROUPS=1 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU \
+        SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d OUT/pmc_pre -- \
+        python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity-mode --no-train-step --no-roofline --no-best-of-n
+    python tools/pmc_summary.py OUT/pmc_pre | grep -A8 "mlp_fused_kernel\|attn_tr_kernel" > OUT/pmc_mfma_prefill_kernels.txt
+    python tools/pmc_prefill_record.py OUT/pmc_mfma_prefill_kernels.txt <commit>"""
 import json
 import os
 import re
@@ -14,7 +20,7 @@ from dimx import roofline
 txt, commit = sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else None
 rec = {"commit": commit, "kernel_source_sha256_12": roofline.kernel_source_hash(roofline.PREFILL_MFMA_SOURCES), "kernels": {},
        "note": "MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (kernel cycles x 1024 SIMDs), kernel cycles = GRBM_GUI_ACTIVE / 8 (summed over the "
-               "8 XCDs); averages over the launches of one forward at B = 256, T = 300; source: profiles/%s" % os.path.basename(txt)}
+               "8 XCDs); averages over the launches of one forward at B = 256, T = 300; source: %s (recipe: tools/pmc_prefill_record.py)" % os.path.basename(txt)}
 cur = None
 for ln in open(txt):
     m = re.search(r"(mlp_fused_kernel<[^>]*>|attn_tr_kernel<[^>]*>)", ln)

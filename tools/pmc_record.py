@@ -1,9 +1,12 @@
 """Turn the two PMC passes over tools/roofline_only.py into profiles/pmc_decode_attn_<kernel-source-hash>.json, the
 file dimx.roofline.pmc_traffic reads for bench.py's `roofline.traffic`.
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python tools/roofline_only.py
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python tools/roofline_only.py
-    python tools/pmc_record.py gpurun_out/pmc_fetch gpurun_out/pmc_write [commit]
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -- python tools/roofline_only.py
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -- python tools/roofline_only.py
+    python tools/pmc_record.py OUT/pmc_fetch OUT/pmc_write [commit]
+
+Two runs because FETCH_SIZE takes three TCC counter slots and WRITE_SIZE two; each is a counter pass of its own, with no other
+tracing.  Writes profiles/pmc_decode_attn_<hash>.json and profiles/pmc_layer_chain_<hash>.json for the sources in the tree.
 
 FETCH_SIZE / WRITE_SIZE are in KB; FETCH_SIZE is doubled (16-B/lane streaming reads on gfx950 report half of the
 bytes, MI355X_MICROARCH.md section HBM)."""
