@@ -453,6 +453,14 @@ int launch_cast_pad(int out_dtype, const float* x, int ldx, const float* coladd,
                     hipStream_t s, const uint8_t* zero_rows = nullptr);
 int launch_gather_rows(int out_dtype, const float* table, int ld_table, int rows, const int32_t* idx, void* y,
                        int ldy, int M, int C, hipStream_t s);
+// One bidirectional LSTM layer, hidden 384, f32 (lstm.hip).  Weights as torch.nn.LSTM keeps them, index 0 forward / 1 reverse;
+// scratch: lstm_scratch_bytes(B, T, In) bytes, 256-byte aligned.  flags bit 0 = the safe path; cu_count != 256 takes it too.
+// The group path waits for the layer on the host (it reads the fault word) and on a fault reruns it on the safe path and
+// increments *fault_count.
+size_t lstm_scratch_bytes(int B, int T, int In);
+int lstm_layer_run(const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
+                   const float* const* b_ih, const float* const* b_hh, float* y, void* scratch, size_t scratch_bytes, int flags,
+                   int cu_count, int* fault_count, hipStream_t st);
 int launch_context_concat(int out_dtype, const float* x_s, const float* patch, const float* audio, void* ctx,
                           int M, int dim, int dim_a, hipStream_t s);
 int launch_finalize_idx(int32_t* idx, const int32_t* lens, int B, int T, int32_t pad_value, hipStream_t s,

@@ -159,6 +159,26 @@ static void slm_extra_keys(const dimx_dims& d, std::vector<KeySpec>& k, int whic
     if (which & 2) k.push_back({"decoder_joint.net.pos_emb.emb.weight", {d.max_seq_len, d.dim + d.dim_a}});
 }
 
+// converter head of SpeakerSLMFT / EmocaConverter (code/seq2seq_pretrain.py:801-819): nn.LSTM(56, 384, 2, bidirectional) and
+// Sequential(Linear(768, 768), LeakyReLU, Linear(768, mesh_dim))
+static const char* lstm_suffix(int dir) { return dir ? "_reverse" : ""; }
+static void mesh_keys(const dimx_dims& d, std::vector<KeySpec>& k) {
+    const std::string p = "vertice_map_reverse_lstm.";
+    const int64_t H = 384;
+    for (int l = 0; l < 2; ++l)
+        for (int dir = 0; dir < 2; ++dir) {
+            const std::string s = "_l" + std::to_string(l) + lstm_suffix(dir);
+            k.push_back({p + "weight_ih" + s, {4 * H, l == 0 ? (int64_t)d.vq_in_dim : 2 * H}});
+            k.push_back({p + "weight_hh" + s, {4 * H, H}});
+            k.push_back({p + "bias_ih" + s, {4 * H}});
+            k.push_back({p + "bias_hh" + s, {4 * H}});
+        }
+    k.push_back({"vertice_map_reverse.0.weight", {2 * H, 2 * H}});
+    k.push_back({"vertice_map_reverse.0.bias", {2 * H}});
+    k.push_back({"vertice_map_reverse.2.weight", {d.mesh_dim, 2 * H}});
+    k.push_back({"vertice_map_reverse.2.bias", {d.mesh_dim}});
+}
+
 static std::vector<KeySpec> all_keys(const dimx_dims& d) {
     std::vector<KeySpec> k;
     if (d.variant == 1) {
@@ -175,6 +195,7 @@ static std::vector<KeySpec> all_keys(const dimx_dims& d) {
     k.push_back({"norm_s.weight", {d.dim}});
     k.push_back({"norm_s.bias", {d.dim}});
     if (d.variant == 2) slm_extra_keys(d, k, 3);
+    if (d.mesh_dim > 0) mesh_keys(d, k);
     return k;
 }
 
@@ -204,7 +225,13 @@ static bool ignorable_key(const std::string& n) {
     static const char* pre[] = {"encoder_l.", "norm_l.", "norm.", "patch_embed_l", "patch_embed_dec_l",
                                 // legacy ListenerGenerator tensors that are not on the ids=None path
                                 "speaker_vq.decoder_v.", "speaker_vq.decoder_a.", "speaker_embeddings.",
-                                "listener_embeddings.", "fc_speaker.", "fc_listener."};
+                                "listener_embeddings.", "fc_speaker.", "fc_listener.",
+                                // SpeakerSLMFT / EmocaConverter tensors the reference's forward never applies (vertice_mapping and
+                                // squasher feed an encoding nobody reads, the _2 head is dead code, code/seq2seq_pretrain.py:712-727)
+                                // or that the host applies (speaker_embed)
+                                "vertice_mapping.", "squasher.", "vertice_map_reverse_lstm_2.", "vertice_map_reverse2.",
+                                "speaker_embed."};
+    if (n == "W") return true;
     for (const char* p : pre)
         if (n.rfind(p, 0) == 0) return true;
     return ends_with(n, ".project_out.weight") || ends_with(n, ".project_out.bias");
@@ -436,10 +463,14 @@ static void free_packed(dimx_ctx* c) {
     c->packed_mask = 0;
 }
 
-enum { COMP_VQ0 = 1, COMP_VQ1 = 2, COMP_ENC = 4, COMP_DEC = 8, COMP_ALL = 15 };
+enum { COMP_VQ0 = 1, COMP_VQ1 = 2, COMP_ENC = 4, COMP_DEC = 8, COMP_ALL = 15, COMP_MESH = 16 };
 
 static std::vector<KeySpec> comp_keys(const dimx_dims& d, int comp) {
     std::vector<KeySpec> k;
+    if (comp == COMP_MESH) {
+        mesh_keys(d, k);
+        return k;
+    }
     if (d.variant == 1) {
         if (comp == COMP_VQ0) legacy_speaker_vq_keys(d, k);
         if (comp == COMP_VQ1) vq_keys(d, 1, k);
@@ -472,7 +503,7 @@ static std::vector<KeySpec> comp_keys(const dimx_dims& d, int comp) {
 static int ensure_packed(dimx_ctx* c, int need) {
     if ((c->packed_mask & need) == need) return DIMX_OK;
     DIMX_HIP(hipSetDevice(c->device));
-    for (int comp = 1; comp <= COMP_DEC; comp <<= 1) {
+    for (int comp = 1; comp <= COMP_MESH; comp <<= 1) {
         if (!(need & comp) || (c->packed_mask & comp)) continue;
         int missing = 0;
         std::string first;
@@ -548,6 +579,19 @@ static int ensure_packed(dimx_ctx* c, int need) {
                     kv.w = (unsigned char*)all.w + (size_t)i * per * all.Kp * dtype_size(c->at);
                 }
             }
+        }
+        if (comp == COMP_MESH) {
+            const std::string p = "vertice_map_reverse_lstm.";
+            for (int l = 0; l < 2; ++l)
+                for (int dir = 0; dir < 2; ++dir) {
+                    const std::string sfx = "_l" + std::to_string(l) + lstm_suffix(dir);
+                    DIMX_TRY(upload_f32(c, p + "weight_ih" + sfx, &c->mesh.w_ih[l][dir]));
+                    DIMX_TRY(upload_f32(c, p + "weight_hh" + sfx, &c->mesh.w_hh[l][dir]));
+                    DIMX_TRY(upload_f32(c, p + "bias_ih" + sfx, &c->mesh.b_ih[l][dir]));
+                    DIMX_TRY(upload_f32(c, p + "bias_hh" + sfx, &c->mesh.b_hh[l][dir]));
+                }
+            DIMX_TRY(pack_linear(c, {"vertice_map_reverse.0.weight"}, "vertice_map_reverse.0.bias", false, &c->mesh.l1));
+            DIMX_TRY(pack_linear(c, {"vertice_map_reverse.2.weight"}, "vertice_map_reverse.2.bias", false, &c->mesh.l2));
         }
         c->packed_mask |= comp;
     }
@@ -822,6 +866,8 @@ int dimx_create(dimx_handle* h, int device_id, const dimx_dims* dims, int numeri
                          d.spk_hidden == 768 && d.spk_heads == 8 && d.spk_in_dim == 824 && d.spk_face_quan_num == 8,
                      DIMX_ERR_ARG, "dimx_create: only the legacy ListenerGenerator geometry (824/768 VQ, 512, 8x64) is built");
     }
+    DIMX_REQUIRE(d.mesh_dim == 0 || (d.variant == 2 && d.mesh_dim > 0), DIMX_ERR_ARG,
+                 "dimx_create: the mesh head (mesh_dim %d) belongs to a handle of variant 2", d.mesh_dim);
     int ndev = 0;
     DIMX_HIP(hipGetDeviceCount(&ndev));
     DIMX_REQUIRE(device_id >= 0 && device_id < ndev, DIMX_ERR_ARG, "dimx_create: device %d of %d", device_id, ndev);
@@ -1117,6 +1163,23 @@ static void plan_gen(const dimx_ctx* c, Arena& ar, int B, int T, GenScratch& s) 
 
 // SLM.forward_encoder: the encoder scratch is sized for the joint 2T pass; xs / xl keep the two first-stage
 // outputs (operand type), xj their time-concatenation, m2 the doubled padding mask
+struct MeshScratch {
+    float *y0, *y1;
+    void *a, *l1;
+    void* lstm;
+    size_t lstm_bytes;
+};
+static void plan_mesh(const dimx_ctx* c, Arena& ar, int B, int L, MeshScratch& s) {
+    const size_t M = (size_t)B * L, W = 768;
+    s.y0 = (float*)ar.take(M * W * 4);
+    s.y1 = (float*)ar.take(M * W * 4);
+    s.a = c->at == DIMX_BF16 ? ar.take(M * W * 2) : nullptr;
+    s.l1 = ar.take(M * W * dtype_size(c->at));
+    const size_t b0 = lstm_scratch_bytes(B, L, c->d.vq_in_dim), b1 = lstm_scratch_bytes(B, L, (int)W);
+    s.lstm_bytes = b0 > b1 ? b0 : b1;
+    s.lstm = ar.take(s.lstm_bytes);
+}
+
 struct SlmScratch {
     EncScratch e;
     void *xs, *xl, *xj;
@@ -1159,6 +1222,12 @@ static size_t workspace_bytes(const dimx_ctx* c, int B, int T, int S = 1) {
         Arena a(nullptr, 0);
         SlmScratch s;
         plan_slm(c, a, B, T, s);
+        scratch = a.off > scratch ? a.off : scratch;
+    }
+    if (c->d.mesh_dim > 0) {
+        Arena a(nullptr, 0);
+        MeshScratch s;
+        plan_mesh(c, a, B, T, s);
         scratch = a.off > scratch ? a.off : scratch;
     }
     if (T >= 2) {
@@ -2321,6 +2390,72 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
 }
 
 int dimx_chain_faults(dimx_handle h) { return h ? h->chain_faults : 0; }
+
+int dimx_lstm_faults(dimx_handle h) { return h ? h->lstm_faults : 0; }
+
+int dimx_mesh_head(dimx_handle h, const float* motion, const float* templ, int B, int L, float* mesh_out, int flags, void* ws,
+                   size_t ws_bytes, void* stream) {
+    DIMX_REQUIRE(h && h->d.mesh_dim > 0, DIMX_ERR_STATE, "mesh_head: the handle was created without a mesh head (dimx_dims.mesh_dim = 0)");
+    DIMX_TRY(check_common(h, B, L, ws, ws_bytes, COMP_MESH));
+    DIMX_REQUIRE(motion && mesh_out, DIMX_ERR_ARG, "mesh_head: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    Arena ar = scratch_arena(h, ws, ws_bytes, B, L, nullptr);
+    MeshScratch s;
+    plan_mesh(h, ar, B, L, s);
+    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "mesh_head: workspace overflow");
+    const MeshHead& m = h->mesh;
+    const int M = B * L, V = h->d.mesh_dim;
+    DIMX_TRY(lstm_layer_run(motion, B, L, h->d.vq_in_dim, 384, m.w_ih[0], m.w_hh[0], m.b_ih[0], m.b_hh[0], s.y0, s.lstm, s.lstm_bytes, flags,
+                            h->cu_count, &h->lstm_faults, st));
+    DIMX_TRY(lstm_layer_run(s.y0, B, L, 768, 384, m.w_ih[1], m.w_hh[1], m.b_ih[1], m.b_hh[1], s.y1, s.lstm, s.lstm_bytes, flags, h->cu_count,
+                            &h->lstm_faults, st));
+    const void* A = s.y1;
+    if (h->at == DIMX_BF16) {
+        DIMX_TRY(launch_cast_pad(h->at, s.y1, 768, nullptr, s.a, 768, M, 768, st));
+        A = s.a;
+    }
+    GemmArgs g;
+    gemm_lin(h, A, 768, m.l1, M, g);
+    g.act = ACT_LEAKY;
+    g.out_dtype = h->at;
+    gemm_set_plain_out(g, s.l1, 768);
+    DIMX_TRY(launch_gemm(g, st));
+    // N = mesh_dim is no multiple of any tile (70110 % 4 = 2): the kernels clamp the W rows they load to N - 1 and store no
+    // column >= N, the staged and 256 x 256 epilogues (N % 4 / N % 8) are not taken; the template row of the clip rides the epilogue
+    gemm_lin(h, s.l1, 768, m.l2, M, g);
+    g.out_dtype = DIMX_F32;
+    g.rowT = L;
+    if (templ) {
+        g.rowadd = templ;
+        g.ld_rowadd = V;
+        g.rowadd_mode = 2;
+        g.rowadd_off = 0;
+    }
+    gemm_set_plain_out(g, mesh_out, V);
+    DIMX_TRY(launch_gemm(g, st));
+    return DIMX_OK;
+}
+
+int dimx_op_lstm_layer(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
+                       const float* const* b_ih, const float* const* b_hh, float* y, int flags, int* faults_out, void* stream) {
+    DIMX_REQUIRE(dtype == DIMX_F32, DIMX_ERR_ARG, "lstm_layer: only the f32 recurrence is built (dtype %d)", dtype);
+    DIMX_REQUIRE(B >= 1 && T >= 1 && In >= 4, DIMX_ERR_ARG, "lstm_layer: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0, cus = 0;
+    DIMX_HIP(hipGetDevice(&dev));
+    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const size_t bytes = lstm_scratch_bytes(B, T, In);
+    void* scratch = nullptr;
+    DIMX_HIP(hipMalloc(&scratch, bytes));
+    int faults = 0;
+    const int rc = lstm_layer_run(x, B, T, In, H, w_ih, w_hh, b_ih, b_hh, y, scratch, bytes, flags, cus, &faults, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    (void)hipFree(scratch);
+    if (faults_out) *faults_out = faults;
+    DIMX_TRY(rc);
+    DIMX_HIP(e);
+    return DIMX_OK;
+}
 
 int dimx_debug_chain_fault(dimx_handle h, int n_calls) {
     DIMX_REQUIRE(h && n_calls >= 0, DIMX_ERR_ARG, "debug_chain_fault: bad argument");

@@ -69,6 +69,13 @@ struct XDec {
     Linear cross_kv_all;  // [depth * 2 * inner][Kp]: every layer's [Wk; Wv] stacked (cross[l].kv are views into it)
 };
 
+// DIM-Speaker converter head (EmocaConverter.vertice_map_reverse_lstm + vertice_map_reverse): the LSTM tensors as torch keeps
+// them (f32 in both numeric modes, lstm.hip), the two Linear layers packed like every other one
+struct MeshHead {
+    const float *w_ih[2][2], *w_hh[2][2], *b_ih[2][2], *b_hh[2][2];   // [layer][direction]
+    Linear l1, l2;
+};
+
 // geometry of the three network families of a handle (variant 0 = SLMFT, 1 = legacy ListenerGenerator,
 // 2 = SLM pre-training model: SLMFT's dims, bidirectional encoders + encoder_l, decoder with abs. pos. embedding)
 struct VQGeom {
@@ -183,4 +190,6 @@ struct dimx_ctx {
     // sampler generator window of a sharded batch (dimx_set_shard): this handle generates clips
     // [shard_row_off, shard_row_off + B) of shard_rows_total (0 = the call's own B)
     int shard_row_off = 0, shard_rows_total = 0;
+    dimx::MeshHead mesh;                // handles created with dimx_dims.mesh_dim > 0
+    int lstm_faults = 0;                // LSTM layers whose group kernel reported a fault and that were rerun on the safe path
 };

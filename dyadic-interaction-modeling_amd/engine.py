@@ -13,9 +13,10 @@ from . import lib as L
 
 
 class Engine:
-    def __init__(self, device=None, mode=L.MODE_PARITY_F32, variant="slmft"):
-        """variant: "slmft" (DIM-Listener, code/seq2seq_pretrain.py) or "legacy" (ListenerGenerator,
-        code/seq2seq.py)."""
+    def __init__(self, device=None, mode=L.MODE_PARITY_F32, variant="slmft", mesh_dim=0):
+        """variant: "slmft" (DIM-Listener, code/seq2seq_pretrain.py), "legacy" (ListenerGenerator, code/seq2seq.py),
+        "slm" (the pre-training model) or "speaker" (DIM-Speaker: the "slm" geometry plus the mesh head of width
+        ``mesh_dim``)."""
         if not torch.cuda.is_available():
             raise L.DimxError("dimx needs a ROCm GPU (torch.cuda.is_available() is False); "
                               "there is no CPU fallback")
@@ -24,9 +25,13 @@ class Engine:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.lib = L.load()
         self.mode = mode
-        assert variant in ("slmft", "legacy", "slm")
+        assert variant in ("slmft", "legacy", "slm", "speaker")
         self.variant = variant
-        self.dims = {"slmft": L.default_dims, "legacy": L.legacy_dims, "slm": L.slm_dims}[variant]()
+        if variant == "speaker":
+            assert mesh_dim > 0, "the speaker variant needs mesh_dim"
+            self.dims = L.speaker_dims(mesh_dim)
+        else:
+            self.dims = {"slmft": L.default_dims, "legacy": L.legacy_dims, "slm": L.slm_dims}[variant]()
         h = ctypes.c_void_p()
         L.check(self.lib.dimx_create(ctypes.byref(h), self.device.index, ctypes.byref(self.dims), mode),
                 "dimx_create")
@@ -246,6 +251,29 @@ class Engine:
                                        wsb, self._s()), "dimx_generate")
         return (tokens, lg) if return_logits else tokens
 
+    def mesh_head(self, motion, template=None, safe=False, out=None):
+        """EmocaConverter head: motion [B,L,56] -> mesh [B,L,V] = vertice_map_reverse(vertice_map_reverse_lstm(motion)) +
+        template[:, None] (template [B,V] or None).  ``safe``: the LSTM layers on the no-communication path.  ``out``: a
+        preallocated [B,L,V] f32 tensor to write into."""
+        B, Lq, _ = motion.shape
+        V = self.dims.mesh_dim
+        motion = motion.to(torch.float32).contiguous()
+        template = template.to(torch.float32).contiguous() if template is not None else None
+        if template is not None:
+            assert tuple(template.shape) == (B, V), "template must be [B, mesh_dim]"
+        if out is None:
+            out = torch.empty(B, Lq, V, dtype=torch.float32, device=self.device)
+        assert tuple(out.shape) == (B, Lq, V) and out.dtype == torch.float32
+        self._chk(motion, template, out)
+        ws, wsb = self.workspace(B, Lq)
+        L.check(self.lib.dimx_mesh_head(self.h, L.ptr(motion), L.ptr(template), B, Lq, L.ptr(out), 1 if safe else 0, ws, wsb,
+                                        self._s()), "dimx_mesh_head")
+        return out
+
+    def lstm_faults(self):
+        """LSTM layers of this handle whose group kernel reported a fault and that were rerun on the safe path."""
+        return int(self.lib.dimx_lstm_faults(self.h))
+
     def chain_faults(self):
         """generate() calls of this handle whose XCD-local chain kernels reported a placement / barrier fault; each was
         regenerated on the one-kernel-per-op step before generate() returned (0 = never happened)."""
@@ -329,6 +357,23 @@ def op_gemm(a, w, bias=None, act=0, residual=None, bf16=False, out_bf16=False, c
                              residual.shape[1] if residual is not None else 0, conv_T, L.ptr(conv_lens), flags,
                              L.stream_ptr(dev)), "dimx_op_gemm")
     return out
+
+
+def op_lstm_layer(x, w_ih, w_hh, b_ih, b_hh, safe=False, return_faults=False):
+    """One bidirectional LSTM layer (csrc/lstm.hip): x [B,T,In] f32; w_ih / w_hh / b_ih / b_hh: pairs (forward, reverse) of
+    tensors shaped like torch.nn.LSTM's -> y [B,T,768] f32.  ``safe``: the no-communication path (flags bit 0)."""
+    lib = L.load()
+    dev = x.device
+    B, T, In = x.shape
+    H = w_hh[0].shape[1]
+    x_ = x.float().contiguous()
+    keep = [[t.to(dev, torch.float32).contiguous() for t in pair] for pair in (w_ih, w_hh, b_ih, b_hh)]
+    arrs = [(ctypes.c_void_p * 2)(*(t.data_ptr() for t in pair)) for pair in keep]
+    y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=dev)
+    faults = ctypes.c_int(0)
+    L.check(lib.dimx_op_lstm_layer(L.F32, L.ptr(x_), B, T, In, H, arrs[0], arrs[1], arrs[2], arrs[3], L.ptr(y), 1 if safe else 0,
+                                   ctypes.byref(faults), L.stream_ptr(dev)), "dimx_op_lstm_layer")
+    return (y, faults.value) if return_faults else y
 
 
 def op_layernorm(x, gamma, beta=None, out_bf16=False):

@@ -29,7 +29,7 @@ class Dims(ctypes.Structure):
         "vq_in_dim", "vq_hidden", "vq_layers", "vq_heads", "vq_inter", "vq_n_embed", "vq_zdim",
         "dim_in", "dim", "dim_a", "enc_depth", "dec_depth", "heads", "dim_head", "num_tokens",
         "max_seq_len", "ff_mult", "variant", "spk_in_dim", "spk_hidden", "spk_heads", "spk_inter",
-        "spk_face_quan_num")]
+        "spk_face_quan_num", "mesh_dim")]
 
 
 class WeightDesc(ctypes.Structure):
@@ -96,6 +96,10 @@ SIGNATURES = {
                                         c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
     "dimx_chain_faults": (c_int, [c_void_p]),
+    "dimx_lstm_faults": (c_int, [c_void_p]),
+    "dimx_mesh_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "dimx_op_lstm_layer": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p),
+                                   POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, POINTER(c_int), c_void_p]),
     "dimx_debug_chain_fault": (c_int, [c_void_p, c_int]),
     "dimx_op_gemm_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "dimx_op_split_x3": (c_int, [c_void_p, c_void_p, ctypes.c_long, c_void_p]),
@@ -212,6 +216,14 @@ def default_dims():
 def slm_dims():
     d = default_dims()
     d.variant = 2
+    return d
+
+
+def speaker_dims(mesh_dim=70110):
+    """variant 2 (the SLM geometry: bidirectional encoders, decoder with absolute positional embedding) plus the
+    DIM-Speaker mesh head of width ``mesh_dim``."""
+    d = slm_dims()
+    d.mesh_dim = int(mesh_dim)
     return d
 
 

@@ -36,7 +36,8 @@ def build_param_tree(root: nn.Module, spec, tensors, buffers=("pe",)):
 class _EngineOwner(nn.Module):
     """Keeps one Engine per (device, numeric mode) and re-uploads weights when they changed."""
 
-    engine_variant = "slmft"     # which handle geometry the module computes on ("slmft" / "legacy")
+    engine_variant = "slmft"     # which handle geometry the module computes on ("slmft" / "legacy" / "slm" / "speaker")
+    engine_mesh_dim = 0          # "speaker" only: width of the mesh head
 
     def __init__(self, numeric_mode):
         super().__init__()
@@ -133,7 +134,7 @@ class _EngineOwner(nn.Module):
                               "(there is no CPU path; the CPU oracle under oracle/ is test infrastructure)")
         ver = self._weights_version()
         if self._engine is None or self._engine.device != device:
-            self._engine = Engine(device, self.numeric_mode, self.engine_variant)
+            self._engine = Engine(device, self.numeric_mode, self.engine_variant, mesh_dim=self.engine_mesh_dim)
             self._engine_version = None
         if self._engine_version != ver:
             self._engine.load_state_dict(self._engine_state_dict())

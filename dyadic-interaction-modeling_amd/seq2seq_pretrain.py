@@ -429,12 +429,186 @@ class SLM(_EngineOwner):
         return total_loss, d, None
 
 
-class SpeakerSLMFT(nn.Module):
-    """Import-compatibility placeholder for reference ``code/seq2seq_pretrain.py:516-757`` (``test_s2s_pretrain.py:7``
-    imports it next to SLMFT).  The speaker-generation model depends on the EMOCA->FLAME converter and BIWI templates
-    and is outside the DIM-Listener path (out of scope): constructing it fails loudly."""
+class SpeakerSLMFT(_EngineOwner):
+    """Drop-in ``SpeakerSLMFT`` (DIM-Speaker, reference ``code/seq2seq_pretrain.py:516-757``), inference only:
+    ``forward(v_speaker, v_speaker_emoca, v_audio, mask, template, mode, speaker_ids) -> (total_loss, d,
+    pred_cont_seq_s_emoca [B,T-1,56])`` on the HIP library -- the SLM-geometry decoder (absolute positional embedding,
+    context ``cat(x_l + patch_embed_dec_l, v_audio)``, teacher forcing without key masking: the reference builds its
+    AutoregressiveWrapper without ``mask_prob``, :624), the speaker VQ-VAE decoder, and the converter head
+    (``vertice_map_reverse_lstm`` + ``vertice_map_reverse``: ``dimx_mesh_head``, a HIP bidirectional LSTM).
 
-    def __init__(self, *a, **kw):
-        super().__init__()
-        raise NotImplementedError("SpeakerSLMFT is not built: only the DIM-Listener path (SLMFT, SLM, the legacy "
-                                  "ListenerGenerator and the VQ-VAEs) runs on the HIP library")
+    Deliberate differences:
+      * the reference also maps the 70110-d input through ``vertice_mapping`` / ``squasher`` and encodes it with the
+        speaker VQ-VAE (``z_s``, :712-715) and uses neither result; both are skipped here (as SLMFT's unused ``z_s``
+        is); their parameters stay in the state dict;
+      * ``mouth_map`` (vertex indices of the lip region) is a constructor argument: the reference reads
+        ``../data/CodeTalker/BIWI/regions/lve.txt`` (:627).  With a map ``d['l_cont_s']`` is
+        ``mse(mesh[..., map, :], v_speaker[:, 1:][..., map, :])`` over all clips (the reference's own indexing, :738,
+        only type-checks at B = 1, where the two agree); with ``None`` the mesh head is not run in ``forward`` and the
+        entry is 0;
+      * ``v_speaker_emoca=None`` raises ``ValueError`` (the reference's ``evaluate_epoch_biwi`` passes None and fails
+        inside ``forward_vq``);
+      * randomness is injectable like SLMFT's (``noise``, ``greedy``, ``seed``, ``temperature``), and
+        ``return_tokens`` / ``return_mesh`` append the code indices / the mesh to the result;
+      * gradients are not supported: every result is computed without an autograd graph, whatever the grad mode.
+        Training (``train_epoch_biwi``, ``train_converter.py``, the LSTM adjoint) is out of scope."""
+    engine_variant = "speaker"
+
+    def __init__(self, config_path=None, mesh_dim=70110, mouth_map=None, numeric_mode=L.MODE_PARITY_F32,
+                 synthetic_seed=20260928, vq_speaker_ckpt=None, vq_listener_ckpt=None, converter_ckpt=None):
+        super().__init__(numeric_mode)
+        config_path = config_path or ("./config.yaml" if os.path.isfile("./config.yaml") else _config.DEFAULT_CONFIG)
+        cfg = _config.load_cfg_from_cfg_file(config_path)
+        self.vq_dims = W.VQDims.from_cfg(cfg)
+        self.s2s = W.S2SDims()
+        self.mesh_dim = int(mesh_dim)
+        self.engine_mesh_dim = self.mesh_dim
+        self.speaker_face_quan_num = cfg.face_quan_num
+        self.speaker_zquant_dim = cfg.zquant_dim
+        self.mouth_map = None if mouth_map is None else [int(i) for i in mouth_map]
+        if self.mouth_map is not None:
+            assert self.mesh_dim % 3 == 0 and all(0 <= i < self.mesh_dim // 3 for i in self.mouth_map), \
+                "mouth_map holds vertex indices in [0, mesh_dim / 3)"
+        spec = W.speaker_slmft_spec(self.mesh_dim, self.vq_dims, self.s2s)
+        build_param_tree(self, spec, W.synth_state_dict(spec, synthetic_seed))
+        for pre, ck in (("speaker_vq.", vq_speaker_ckpt), ("listener_vq.", vq_listener_ckpt)):
+            if ck is not None:
+                sd = torch.load(ck, map_location="cpu")["state_dict"]
+                own = self.state_dict()
+                self.load_state_dict({pre + k.replace("module.", "", 1): v for k, v in sd.items()
+                                      if pre + k.replace("module.", "", 1) in own}, strict=False)
+        if converter_ckpt is not None:      # EmocaConverter.state_dict() (best_converter.pt, reference :549-552)
+            sd = torch.load(converter_ckpt, map_location="cpu")
+            own = self.state_dict()
+            self.load_state_dict({k: v for k, v in sd.items() if k in own and not k.startswith("speaker_vq.")}, strict=False)
+        self.eval()
+
+    def _engine_state_dict(self):
+        return self.state_dict()
+
+    # ------------------------------------------------------------------ reference sub-APIs
+    @torch.no_grad()
+    def forward_vq(self, v_speaker, v_listener, mask):
+        """reference :692-706 with the tensors ``forward`` hands it: -> (None, z_listener [B,T] int64 padded with -100), the
+        LISTENER VQ-VAE's codes of ``v_listener`` (``forward`` passes the speaker's EMOCA stream there).  The speaker
+        VQ-VAE encoding of the first argument is never used by the reference and is not computed."""
+        eng = self.engine(v_listener.device)
+        xl, lens = compact_by_mask(v_listener, mask.bool())
+        return None, eng.vq_encode(1, xl.contiguous(), lens, pe_mode=0, pad_value=-100).long()
+
+    def forward_encoder(self, v_speaker, mask):
+        """reference :638-648, never called by the reference's ``forward``.  It is encoder_s -> encoder_joint -> norm_s on
+        the speaker stream alone; the library's variant-2 encoder stage (``dimx_slm_encode``) runs encoder_joint over the
+        concatenated speaker + listener sequence, so its speaker output is a different function and this method does not
+        map onto it."""
+        raise NotImplementedError("SpeakerSLMFT.forward_encoder is not built: the reference's forward never calls it, and "
+                                  "dimx_slm_encode's joint encoder sees the listener half too")
+
+    @torch.no_grad()
+    def forward_decoder(self, x_l, z_s, x_a, mask, mode="train", noise=None, greedy=False, seed=None, temperature=1.0):
+        """reference :650-658 -> (l_ce_s, logits [B,T-1,512]) for mode 'train', (0.0, tokens [B,T-1]) otherwise."""
+        eng = self.engine(x_a.device)
+        m8 = mask.bool().to(torch.uint8).contiguous()
+        B, T = z_s.shape
+        if mode == "train":
+            eng.set_context(x_l, x_a, which_patch=1, for_generate=False)
+            logits, row_loss, _ = eng.decode_tf(z_s, m8, None)
+            n_valid = (z_s[:, 1:] != -100).sum().clamp(min=1)
+            return row_loss.sum() / n_valid, logits
+        eng.set_context(x_l, x_a, which_patch=1, for_generate=True)
+        if greedy:
+            temperature, seed_v = 0.0, 0
+        else:
+            seed_v = 0 if noise is not None else SLMFT._user_seed(seed)
+        tokens = eng.generate(z_s[:, 0], m8, T, temperature, 52, noise, seed_v)
+        return 0.0, tokens.long()
+
+    @torch.no_grad()
+    def forward_vq_decoder(self, logits_s, type="emoca", mode="train", template=None):
+        """reference :660-676: argmax (train) / tokens (val) -> SPEAKER VQ-VAE codebook + decoder -> converter head ->
+        (mesh [B,L,V], emoca [B,L,56]).  ``template`` [B,V] (optional) is added to the mesh inside the head's last GEMM
+        (the reference adds it in ``forward``, :730)."""
+        if type != "emoca":
+            raise NotImplementedError("forward_vq_decoder(type=%r): the vertice_map_reverse_lstm_2 / vertice_map_reverse2 "
+                                      "head is dead code in the reference (:728) and is not built" % (type,))
+        pred_seq_s = torch.argmax(logits_s, dim=-1) if mode == "train" else logits_s
+        eng = self.engine(pred_seq_s.device)
+        emoca = eng.vq_decode(0, pred_seq_s, 0)
+        return eng.mesh_head(emoca, template), emoca
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, v_speaker, v_speaker_emoca, v_audio, mask, template, mode="train", speaker_ids=None, noise=None,
+                greedy=False, seed=None, temperature=1.0, return_tokens=False, return_mesh=False):
+        """reference :708-757 -> (total_loss, d, pred_cont_seq_s_emoca [B,T-1,56]) (+ tokens [B,T-1], + mesh [B,T-1,V])."""
+        if v_speaker_emoca is None:
+            raise ValueError("SpeakerSLMFT.forward needs v_speaker_emoca (the EMOCA stream the codes are taken from)")
+        with torch.no_grad(), self.engine_pinned():
+            mask = mask.bool()
+            dev = v_audio.device
+            B, T = mask.shape
+            _, z = self.forward_vq(None, v_speaker_emoca, mask)
+            if speaker_ids is None:
+                x_l = torch.zeros(B, T, self.s2s.dim, device=dev)
+            else:
+                x_l = self.speaker_embed.weight[speaker_ids.long()].unsqueeze(1).repeat(1, T, 1).contiguous()
+            l_ce_s, px_s = self.forward_decoder(x_l, z, v_audio, mask, mode=mode, noise=noise, greedy=greedy, seed=seed,
+                                                temperature=temperature)
+            eng = self.engine(dev)
+            tokens = torch.argmax(px_s, dim=-1) if mode == "train" else px_s
+            pred_emoca = eng.vq_decode(0, tokens, 0)
+            mesh = None
+            l_mouth = 0
+            if self.mouth_map is not None or return_mesh:
+                mesh = eng.mesh_head(pred_emoca, template)
+            if self.mouth_map is not None:
+                idx = torch.as_tensor(self.mouth_map, device=dev, dtype=torch.long)
+                tgt = v_speaker[:, 1:, :].reshape(B, T - 1, -1, 3)[:, :, idx, :]
+                l_mouth = F.mse_loss(mesh.view(B, T - 1, -1, 3)[:, :, idx, :], tgt.to(mesh.dtype))
+            l_emoca = F.mse_loss(pred_emoca, v_speaker_emoca[:, 1:, :].to(pred_emoca.dtype))
+            total_loss = l_ce_s + l_emoca
+            d = {"l_ce_s": 0, "l_ce_l": l_ce_s, "l_cont_s": l_mouth, "l_cont_l": l_emoca, "nce": 0, "c_acc": 0}
+            out = (total_loss, d, pred_emoca)
+            if return_tokens:
+                out += (tokens,)
+            if return_mesh:
+                out += (mesh,)
+            return out
+
+
+class EmocaConverter(_EngineOwner):
+    """Drop-in ``EmocaConverter`` (reference ``code/seq2seq_pretrain.py:759-842``), inference only:
+    ``forward(inputs, template, v_speaker) -> (mesh [B,L,V], None)`` = ``vertice_map_reverse(vertice_map_reverse_lstm(
+    speaker_vq(v_speaker)[0])) + template[:, None]``; ``inputs`` is unused, as in the reference (:829-831 are commented
+    out).  The state dict has the reference's keys (``speaker_vq.*`` and the converter tensors)."""
+    engine_variant = "speaker"
+
+    def __init__(self, config_path=None, mesh_dim=70110, numeric_mode=L.MODE_PARITY_F32, synthetic_seed=20260928,
+                 vq_speaker_ckpt=None):
+        super().__init__(numeric_mode)
+        config_path = config_path or ("./config.yaml" if os.path.isfile("./config.yaml") else _config.DEFAULT_CONFIG)
+        cfg = _config.load_cfg_from_cfg_file(config_path)
+        self.vq_dims = W.VQDims.from_cfg(cfg)
+        self.mesh_dim = int(mesh_dim)
+        self.engine_mesh_dim = self.mesh_dim
+        self.speaker_face_quan_num = cfg.face_quan_num
+        self.speaker_zquant_dim = cfg.zquant_dim
+        spec = W.vq_spec(self.vq_dims, "speaker_vq.") + W.emoca_converter_spec(self.mesh_dim, self.vq_dims.in_dim)
+        build_param_tree(self, spec, W.synth_state_dict(spec, synthetic_seed))
+        if vq_speaker_ckpt is not None:
+            sd = torch.load(vq_speaker_ckpt, map_location="cpu")["state_dict"]
+            own = self.state_dict()
+            self.load_state_dict({"speaker_vq." + k.replace("module.", "", 1): v for k, v in sd.items()
+                                  if "speaker_vq." + k.replace("module.", "", 1) in own}, strict=False)
+        self.criterion = nn.MSELoss()
+        self.eval()
+
+    def _engine_state_dict(self):
+        return self.state_dict()
+
+    @torch.no_grad()
+    def forward(self, inputs, template, v_speaker):
+        with self.engine_pinned():
+            eng = self.engine(v_speaker.device)
+            idx, _ = eng.vq_encode(0, v_speaker, None, pe_mode=1, return_z=True)
+            dec = eng.vq_decode(0, idx, 0)      # VQAutoEncoder.forward: decode(quant) of the codebook rows
+            return eng.mesh_head(dec, template), None

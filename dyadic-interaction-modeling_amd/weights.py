@@ -255,9 +255,61 @@ def slm_spec(vq: VQDims = VQDims(), d: S2SDims = S2SDims()):
     return slmft_spec(vq, d) + [("decoder_joint.net.pos_emb.emb.weight", (d.max_seq_len, d.dec_dim), "pos_emb", 0)]
 
 
+def lstm_spec(prefix, in_dim, hidden=384, layers=2, kind_w="w", kind_b="b"):
+    """Keys and shapes of ``torch.nn.LSTM(in_dim, hidden, layers, bidirectional=True).state_dict()`` under ``prefix``, in
+    torch's registration order; ``fan_in = hidden`` is torch's own +-1/sqrt(hidden) initialisation."""
+    s = []
+    for l in range(layers):
+        for sfx in ("", "_reverse"):
+            k = "_l%d%s" % (l, sfx)
+            s += [(prefix + "weight_ih" + k, (4 * hidden, in_dim if l == 0 else 2 * hidden), kind_w, hidden),
+                  (prefix + "weight_hh" + k, (4 * hidden, hidden), kind_w, hidden),
+                  (prefix + "bias_ih" + k, (4 * hidden,), kind_b, hidden),
+                  (prefix + "bias_hh" + k, (4 * hidden,), kind_b, hidden)]
+    return s
+
+
+def emoca_converter_spec(mesh_dim=70110, dim=56, hidden=384):
+    """The converter tensors of ``EmocaConverter`` (reference code/seq2seq_pretrain.py:784-824) that ``SpeakerSLMFT`` adopts
+    (:563-568).  Kind ``unused``: tensors the reference's forward never applies to anything that reaches an output
+    (vertice_mapping / squasher feed an encoding nobody reads, the ``_2`` head is dead code) -- their keys and shapes are the
+    reference's, their synthetic initialisation is zeros (two of them hold 3.9 M and 53.8 M elements at mesh_dim 70110)."""
+    W2 = 2 * hidden
+    s = [("vertice_mapping.0.weight", (dim, mesh_dim), "unused", 0), ("vertice_mapping.0.bias", (dim,), "unused", 0),
+         ("squasher.0.0.weight", (dim, dim, 5), "unused", 0), ("squasher.0.0.bias", (dim,), "unused", 0),
+         ("vertice_map_reverse.0.weight", (W2, W2), "w", W2), ("vertice_map_reverse.0.bias", (W2,), "b", W2),
+         ("vertice_map_reverse.2.weight", (mesh_dim, W2), "w", W2), ("vertice_map_reverse.2.bias", (mesh_dim,), "b", W2)]
+    s += lstm_spec("vertice_map_reverse_lstm.", dim, hidden)
+    s += lstm_spec("vertice_map_reverse_lstm_2.", dim, hidden, kind_w="unused", kind_b="unused")
+    s += [("vertice_map_reverse2.0.weight", (W2, W2), "unused", 0), ("vertice_map_reverse2.0.bias", (W2,), "unused", 0),
+          ("vertice_map_reverse2.2.weight", (mesh_dim, W2), "unused", 0), ("vertice_map_reverse2.2.bias", (mesh_dim,), "unused", 0)]
+    return s
+
+
+def speaker_slmft_spec(mesh_dim=70110, vq: VQDims = VQDims(), d: S2SDims = S2SDims()):
+    """Every tensor of ``SpeakerSLMFT().state_dict()`` (reference code/seq2seq_pretrain.py:540-635): the SLM set (both
+    VQ-VAEs, the three encoders, the decoder with its absolute positional embedding), the converter tensors, ``W`` and the
+    speaker-id embedding."""
+    return (slm_spec(vq, d) + emoca_converter_spec(mesh_dim, d.dim_in, d.dim) +
+            [("W", (2,), "unused", 0), ("speaker_embed.weight", (15, d.dim), "tok_emb", 0)])
+
+
 # ----------------------------------------------------------------------------
 # synthetic initialisation
 # ----------------------------------------------------------------------------
+
+def _uniform(seed, name, shape, lo, hi, chunk=1 << 22):
+    """prng.uniform, generated in chunks of the same stream (bit-identical): its float64 temporaries exceed 1 GB for the
+    53.8 M elements of the mesh head's last projection."""
+    n = int(np.prod(shape)) if len(shape) else 1
+    if n <= chunk:
+        return prng.uniform(seed, name, shape, lo, hi)
+    out = np.empty(n, dtype=np.float32)
+    for o in range(0, n, chunk):
+        m = min(chunk, n - o)
+        out[o:o + m] = (lo + (hi - lo) * prng.uniform01(seed, name, m, o)).astype(np.float32)
+    return out.reshape(shape)
+
 
 def sinusoid_pe(max_len: int, dim: int) -> torch.Tensor:
     """The `pe` buffer of the VQ-VAE PositionalEncoding, shape [max_len,1,dim]
@@ -274,9 +326,11 @@ def sinusoid_pe(max_len: int, dim: int) -> torch.Tensor:
 def synth_tensor(seed, name, shape, kind, fan_in, plain=False):
     """One synthetic tensor.  ``plain=True`` gives the SURVEY Appendix-C flavour
     (zero biases, unit norm gains); the default exercises every bias / gain path."""
+    if kind == "unused":
+        return torch.zeros(shape)
     if kind == "w":
         b = 1.0 / math.sqrt(fan_in)
-        return torch.from_numpy(prng.uniform(seed, name, shape, -b, b))
+        return torch.from_numpy(_uniform(seed, name, shape, -b, b))
     if kind == "b":
         if plain:
             return torch.zeros(shape)

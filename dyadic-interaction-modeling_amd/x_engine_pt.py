@@ -234,6 +234,46 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     return y_trues_all, y_preds_all, x_all, data_ids_all
 
 
+# speaker id of a BIWI recording, keyed on the part of the file name before the first '_' (reference code/x_engine_pt.py:286-301)
+BIWI_SPEAKER_IDS = {"F2": 0, "F3": 1, "F4": 2, "M3": 3, "M4": 4, "M5": 5, "F1": 6, "F5": 7, "F6": 8, "F7": 9, "F8": 10, "M1": 11,
+                    "M2": 12, "M6": 13}
+
+
+def evaluate_test_epoch_biwi(model, loader, device, beam_size=10):
+    """reference code/x_engine_pt.py:279-338, restated with its quirks.  The loader yields ``(xa [B,T,768] audio, xv [B,T,V]
+    vertices, xt [B,V] template, xe [B,T,56] EMOCA, data_ids)``; the mask is all ones; the model runs ``beam_size`` times in
+    ``mode='train'`` (teacher forcing: every pass of a deterministic model gives the same prediction); per clip the candidate with
+    the smallest ``mean_t ||pred_t - true_t||_2`` is kept, a later candidate replaces it only when STRICTLY smaller.  ``y_true`` is
+    ``xe[:, 1:]`` and is cut by one more frame when stored (and so are the predictions): the stored arrays have T - 2 frames.
+    Returns ``(y_trues_all, y_preds_all, x_all, data_ids_all)``; ``x_all`` stays empty."""
+    y_trues_all, y_preds_all, x_all, data_ids_all = [], [], [], []
+    model.eval()
+    with torch.no_grad():
+        for batch in loader:
+            xa, xv, xt, xe, data_ids = batch
+            xa, xv, xt, xe = xa.to(device), xv.to(device), xt.to(device), xe.to(device)
+            y_true = xe[:, 1:, :]
+            n = xv.shape[0]
+            speaker_ids = torch.tensor([BIWI_SPEAKER_IDS[f.split("_")[0]] for f in data_ids]).long().to(device)
+            mask = torch.ones((xa.shape[0], xa.shape[1]), dtype=torch.bool).to(device)
+            for j in range(n):
+                y_trues_all.append(y_true[j, 1:, :].cpu().numpy())
+                data_ids_all.append(data_ids[j])
+            cur_best = [float("inf")] * n
+            best = [None] * n
+            for _ in range(beam_size):
+                _, _, y_preds = model(xv, xe, xa, mask, xt, mode="train", speaker_ids=speaker_ids)
+                for j in range(n):
+                    cp = y_preds[j, 1:, :].cpu().numpy()
+                    ct = y_true[j, 1:, :].cpu().numpy()
+                    distance = np.mean(np.sqrt(np.sum((cp - ct) ** 2, axis=1)))
+                    if distance < cur_best[j]:
+                        best[j] = cp
+                        cur_best[j] = distance
+            y_preds_all.extend(best)
+    return y_trues_all, y_preds_all, x_all, data_ids_all
+
+
 last_eval_report = {}
 
 

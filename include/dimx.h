@@ -66,6 +66,9 @@ typedef struct {
     int variant;
     /* speaker VQ-VAE geometry of variant 1 (reference code/config_speaker_old.yaml:15-30) */
     int spk_in_dim, spk_hidden, spk_heads, spk_inter, spk_face_quan_num;
+    /* DIM-Speaker mesh head (EmocaConverter, reference code/seq2seq_pretrain.py:759-842): output width of vertice_map_reverse
+     * (70110 in the reference); 0 = no head (dimx_default_dims / dimx_legacy_dims).  Needs variant 2. */
+    int mesh_dim;
 } dimx_dims;
 
 typedef struct {
@@ -225,6 +228,26 @@ int dimx_chain_faults(dimx_handle h);
  * (XCD, CU slot) placement (the blocks of every odd XCD claim the slots of its even neighbour). */
 int dimx_debug_chain_fault(dimx_handle h, int n_calls);
 
+/* ---- DIM-Speaker mesh head (handle of variant 2 created with dimx_dims.mesh_dim = V > 0) ---------------------------------------
+ * SpeakerSLMFT (reference code/seq2seq_pretrain.py:516-757) is the variant-2 transformer (dimx_set_context(which_patch = 1) +
+ * dimx_decode_tf(kv_mask = NULL) / dimx_generate) plus the converter head of EmocaConverter (:801-819, applied at :671-672 and
+ * :834-836).  dimx_mesh_head runs that head: mesh_out [B,L,V] f32 =
+ *   Linear(768 -> V)(LeakyReLU_0.2(Linear(768 -> 768)(LSTM_2layers_bidirectional(motion [B,L,56])))) + template[b]
+ * with template [B,V] f32 or NULL (row b is added to every frame of clip b, in the last GEMM's epilogue; ldc = V, nothing is
+ * written past mesh_out).  Like the reference the LSTM has NO per-clip lengths: it runs over all L frames of every clip, and
+ * the reverse direction starts at the last (padded) frame.  The recurrence is f32 in both numeric modes (csrc/lstm.hip); the two
+ * Linear layers use the mode's operands.  flags bit 0: run the LSTM layers on the safe path (one block per 4 clips and direction,
+ * no communication between blocks).  Otherwise, on a 256-CU device, they run on the group path, whose 256 blocks wait for each
+ * other: the call then WAITS for each LSTM layer on the host, reads its fault word, and after a fault (a bounded wait timed out)
+ * reruns the layer on the safe path and counts the event (dimx_lstm_faults; 0 = never happened); because of that wait a stream
+ * that is being captured must take flags bit 0.  Extra state-dict keys:
+ * vertice_map_reverse_lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_l{0,1}[_reverse] and vertice_map_reverse.{0,2}.{weight,bias}
+ * are required by such a handle; vertice_mapping.*, squasher.*, vertice_map_reverse_lstm_2.*, vertice_map_reverse2.*, W and
+ * speaker_embed.weight (never applied by the reference's forward, or applied on the host) are accepted and ignored by every handle. */
+int dimx_mesh_head(dimx_handle h, const float* motion, const float* templ, int B, int L, float* mesh_out, int flags, void* ws,
+                   size_t ws_bytes, void* stream);
+int dimx_lstm_faults(dimx_handle h);
+
 /* ---- training step: reference train_epoch, code/x_engine_pt.py:9-60 driven by
  * code/finetune_s2s_pretrain.py:105-143 (AdamW lr 1e-5, clip 1.0, VQ-VAEs frozen) --------------------------------------------
  * The reference differentiates SLMFT.forward(mode='train') with autograd; here forward AND backward of the teacher-forced stack
@@ -348,6 +371,14 @@ int dimx_op_gemm_slabs(int in_dtype, int M, int N, int K, int flags);
  * `out`.  bf16 with nlayers = 4 is the fused all-layers launch of the 256 x 256 kernel; f32 supports nlayers = 1. */
 int dimx_op_gemm_headmajor(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int M, int N, int K,
                            int rowT, int Tp, int nlayers, void* stream);
+/* One bidirectional LSTM layer (csrc/lstm.hip; torch.nn.LSTM(batch_first=True, bidirectional=True), eval, zero initial state, gate
+ * order i, f, g, o): x [B,T,In] f32 (In % 4 == 0), H = 384, w_ih[d] [4H,In], w_hh[d] [4H,H], b_ih[d] / b_hh[d] [4H] f32 device
+ * pointers (d = 0 forward, 1 reverse), y [B,T,2H] f32, forward half first.  No lengths: every clip runs over all T frames.
+ * dtype: DIMX_F32 (the bf16-operand recurrence is not built: DIMX_ERR_ARG).  flags bit 0 = safe path (see dimx_mesh_head).
+ * *faults_out (optional) = 1 when the group path reported a fault and the layer was rerun on the safe path, else 0.
+ * Allocates its scratch and synchronises the stream. */
+int dimx_op_lstm_layer(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
+                       const float* const* b_ih, const float* const* b_hh, float* y, int flags, int* faults_out, void* stream);
 /* y = LayerNorm(x) over the last dim (C in {384,1152}), eps 1e-5; beta optional. */
 int dimx_op_layernorm(int out_dtype, const float* x, void* y, const float* gamma, const float* beta,
                       int M, int C, void* stream);
