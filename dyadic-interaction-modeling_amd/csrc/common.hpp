@@ -456,11 +456,18 @@ int launch_gather_rows(int out_dtype, const float* table, int ld_table, int rows
 // One bidirectional LSTM layer, hidden 384, f32 (lstm.hip).  Weights as torch.nn.LSTM keeps them, index 0 forward / 1 reverse;
 // scratch: lstm_scratch_bytes(B, T, In) bytes, 256-byte aligned.  flags bit 0 = the safe path; cu_count != 256 takes it too.
 // The group path waits for the layer on the host (it reads the fault word) and on a fault reruns it on the safe path and
-// increments *fault_count.
+// increments *fault_count.  save (training forward): [B*T][2][kLstmSave][H] f32 = the post-activation gates i, f, g, o, c_t and
+// tanh c_t of every cell update, stored by the same kernels; y does not depend on it.
+constexpr int kLstmSave = 6;
 size_t lstm_scratch_bytes(int B, int T, int In);
 int lstm_layer_run(const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
                    const float* const* b_ih, const float* const* b_hh, float* y, void* scratch, size_t scratch_bytes, int flags,
-                   int cu_count, int* fault_count, hipStream_t st);
+                   int cu_count, int* fault_count, hipStream_t st, float* save = nullptr);
+// The adjoint of that recurrence (train_lstm.hip): dy [B][T][2H], save as above, w_hh [2] -> dgates [B*T][2][4H] (the gradient
+// of the gate pre-activations, i f g o).  The forward's calling convention; only the no-communication path is built.
+size_t lstm_bwd_scratch_bytes(int B, int T);
+int lstm_bwd_run(const float* dy, const float* save, const float* const* w_hh, int B, int T, float* dgates, void* scratch,
+                 size_t scratch_bytes, int flags, int cu_count, int* fault_count, hipStream_t st);
 int launch_context_concat(int out_dtype, const float* x_s, const float* patch, const float* audio, void* ctx,
                           int M, int dim, int dim_a, hipStream_t s);
 int launch_finalize_idx(int32_t* idx, const int32_t* lens, int B, int T, int32_t pad_value, hipStream_t s,

@@ -65,8 +65,24 @@ struct LstmArgs {
     int b0, nb;            // group path: the clips [b0, b0 + nb) of this launch, nb <= 128
     u64* xch;              // [8 groups][2 directions][2 parities][16 clips][H] granules, zeroed before every launch
     unsigned* err;         // bit 1: a poll timed out
+    float* save;           // training forward (kSave): [B*T][2][kLstmSave][H] = i, f, g, o (post-activation), c_t, tanh c_t
 };
 
+// what the adjoint (train_lstm.hip) needs of one cell update; the arithmetic of y does not depend on kSave
+template <bool kSave>
+__device__ __forceinline__ void lstm_save(const LstmArgs& a, size_t row, int dir, int unit, float gi, float gf, float gg, float go, float c,
+                                          float tc) {
+    if (!kSave) return;
+    float* sp = a.save + (row * 2 + dir) * (size_t)(kLstmSave * kH) + unit;
+    sp[0] = gi;
+    sp[kH] = gf;
+    sp[2 * kH] = gg;
+    sp[3 * kH] = go;
+    sp[4 * kH] = c;
+    sp[5 * kH] = tc;
+}
+
+template <bool kSave>
 __global__ __launch_bounds__(kGroupThreads) void lstm_group_kernel(const LstmArgs a) {
     __shared__ __attribute__((aligned(16))) float sh_h[kGroupClips][kH];
     __shared__ float sh_g[kGroupClips][kRows];
@@ -158,9 +174,12 @@ __global__ __launch_bounds__(kGroupThreads) void lstm_group_kernel(const LstmArg
                 p_g += gp[2];
                 p_o += gp[3];
             }
-            c = sigmoid_f(p_f) * c + sigmoid_f(p_i) * tanhf(p_g);
-            const float h = sigmoid_f(p_o) * tanhf(c);
+            const float gi = sigmoid_f(p_i), gf = sigmoid_f(p_f), gg = tanhf(p_g), go = sigmoid_f(p_o);
+            c = gf * c + gi * gg;
+            const float tc = tanhf(c);
+            const float h = go * tc;
             a.y[((size_t)(c0 + cu_b) * T + t) * (2 * kH) + dir * kH + unit] = h;
+            lstm_save<kSave>(a, (size_t)(c0 + cu_b) * T + t, dir, unit, gi, gf, gg, go, c, tc);
             if (s + 1 < T)
                 __hip_atomic_store(xbase + ((size_t)(s & 1) * kGroupClips + cu_b) * kH + unit,
                                    ((u64)(unsigned)(s + 1) << 32) | __float_as_uint(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -168,6 +187,7 @@ __global__ __launch_bounds__(kGroupThreads) void lstm_group_kernel(const LstmArg
     }
 }
 
+template <bool kSave>
 __global__ __launch_bounds__(kSafeThreads) void lstm_safe_kernel(const LstmArgs a) {
     __shared__ __attribute__((aligned(16))) float sh_h[kSafeClips][kH];
     __shared__ float sh_g[kSafeClips][kG4];
@@ -218,9 +238,12 @@ __global__ __launch_bounds__(kSafeThreads) void lstm_safe_kernel(const LstmArgs 
                 p_g += sh_g[b][2 * kH + u];
                 p_o += sh_g[b][3 * kH + u];
             }
-            c[i] = sigmoid_f(p_f) * c[i] + sigmoid_f(p_i) * tanhf(p_g);
-            const float h = sigmoid_f(p_o) * tanhf(c[i]);
+            const float gi = sigmoid_f(p_i), gf = sigmoid_f(p_f), gg = tanhf(p_g), go = sigmoid_f(p_o);
+            c[i] = gf * c[i] + gi * gg;
+            const float tc = tanhf(c[i]);
+            const float h = go * tc;
             a.y[((size_t)(c0 + b) * T + t) * (2 * kH) + dir * kH + u] = h;
+            lstm_save<kSave>(a, (size_t)(c0 + b) * T + t, dir, u, gi, gf, gg, go, c[i], tc);
             sh_h[b][u] = h;   // read by the next step's products, behind its first barrier
         }
     }
@@ -279,10 +302,11 @@ size_t lstm_scratch_bytes(int B, int T, int In) { return plan_scratch(B, T, In).
 
 // One layer.  x [B*T][In] f32, weights as torch.nn.LSTM keeps them (w_ih [4H][In], w_hh [4H][H], biases [4H]; index 0
 // forward, 1 reverse), y [B][T][2H].  flags bit 0: safe path.  On the group path the call WAITS for the layer (it reads
-// the fault word); *fault_count is incremented when the layer had to be rerun on the safe path.
+// the fault word); *fault_count is incremented when the layer had to be rerun on the safe path.  save (optional): the
+// training forward -- the same kernels also store [B*T][2][kLstmSave][H] for the adjoint; y is what it is without.
 int lstm_layer_run(const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
                    const float* const* b_ih, const float* const* b_hh, float* y, void* scratch, size_t scratch_bytes, int flags,
-                   int cu_count, int* fault_count, hipStream_t st) {
+                   int cu_count, int* fault_count, hipStream_t st, float* save) {
     DIMX_REQUIRE(H == kH, DIMX_ERR_ARG, "lstm: only hidden size %d is built (H=%d)", kH, H);
     DIMX_REQUIRE(x && y && scratch && w_ih && w_hh && b_ih && b_hh && B >= 1 && T >= 1 && In >= 4 && In % 4 == 0, DIMX_ERR_ARG,
                  "lstm: null argument or bad shape (B=%d T=%d In=%d)", B, T, In);
@@ -334,6 +358,7 @@ int lstm_layer_run(const float* x, int B, int T, int In, int H, const float* con
     a.T = T;
     a.xch = (u64*)(sb + p.off_xch);
     a.err = err;
+    a.save = save;
     bool safe = (flags & 1) != 0 || cu_count != kGridBlocks;
     if (!safe) {
         DIMX_HIP(hipMemsetAsync(err, 0, kErrBytes, st));
@@ -341,7 +366,8 @@ int lstm_layer_run(const float* x, int B, int T, int In, int H, const float* con
             a.b0 = b0;
             a.nb = B - b0 < kGroups * kGroupClips ? B - b0 : kGroups * kGroupClips;
             DIMX_HIP(hipMemsetAsync(a.xch, 0, kXchGranules * 8, st));
-            hipLaunchKernelGGL(lstm_group_kernel, dim3(kGridBlocks), dim3(kGroupThreads), 0, st, a);
+            if (save) hipLaunchKernelGGL(lstm_group_kernel<true>, dim3(kGridBlocks), dim3(kGroupThreads), 0, st, a);
+            else hipLaunchKernelGGL(lstm_group_kernel<false>, dim3(kGridBlocks), dim3(kGroupThreads), 0, st, a);
             DIMX_HIP(hipGetLastError());
         }
         unsigned host_err = 0;
@@ -357,7 +383,8 @@ int lstm_layer_run(const float* x, int B, int T, int In, int H, const float* con
         DIMX_HIP(hipGetLastError());
         a.b0 = 0;
         a.nb = B;
-        hipLaunchKernelGGL(lstm_safe_kernel, dim3(2 * ceil_div(B, kSafeClips)), dim3(kSafeThreads), 0, st, a);
+        if (save) hipLaunchKernelGGL(lstm_safe_kernel<true>, dim3(2 * ceil_div(B, kSafeClips)), dim3(kSafeThreads), 0, st, a);
+        else hipLaunchKernelGGL(lstm_safe_kernel<false>, dim3(2 * ceil_div(B, kSafeClips)), dim3(kSafeThreads), 0, st, a);
         DIMX_HIP(hipGetLastError());
     }
     return DIMX_OK;

@@ -1309,6 +1309,123 @@ int vqenc_bwd(Step& s, VqEncSave& E, const float* dz) {
     return DIMX_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------- converter head
+// The arenas of the DIM-Speaker converter's step: the head of EmocaConverter that dimx_mesh_head runs (code/seq2seq_pretrain.py:
+// 801-819), in state-dict order.  Every tensor is padded to 16 bytes inside the arena; the V-wide bias relies on that pad (conv_run).
+struct LstmLayerP {
+    Lin ih[2], hh[2];   // [direction]; the bias of ih is bias_ih, the bias of hh is bias_hh (their gradients are equal)
+    int In = 0;
+};
+int build_conv_plan(dimx_handle h, TrainPlan& p) {
+    DIMX_REQUIRE(h->d.mesh_dim > 0, DIMX_ERR_STATE, "train_conv: the handle was created without a mesh head (dimx_dims.mesh_dim = 0)");
+    DIMX_REQUIRE(h->d.mesh_dim % 3 == 0 && h->d.vq_in_dim % 4 == 0, DIMX_ERR_ARG, "train_conv: mesh_dim %d must be 3 x vertices", h->d.mesh_dim);
+    auto add = [&](const std::string& name, int rows, int cols) -> int {
+        auto it = h->host.find(name);
+        DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "train_conv: weight %s was not loaded", name.c_str());
+        long n = 1;
+        for (auto sz : it->second.shape) n *= sz;
+        DIMX_REQUIRE(n == (long)rows * cols, DIMX_ERR_WEIGHT, "train_conv: %s has %ld elements, expected %d x %d", name.c_str(), n, rows, cols);
+        PInfo pi{name, p.total, n, rows, cols};
+        p.index[name] = (int)p.params.size();
+        p.params.push_back(pi);
+        p.total += (n + 3) / 4 * 4;
+        return DIMX_OK;
+    };
+    const std::string l = "vertice_map_reverse_lstm.";
+    for (int layer = 0; layer < 2; ++layer)
+        for (int dir = 0; dir < 2; ++dir) {
+            const std::string sfx = "_l" + std::to_string(layer) + (dir ? "_reverse" : "");
+            DIMX_TRY(add(l + "weight_ih" + sfx, 1536, layer ? 768 : h->d.vq_in_dim));
+            DIMX_TRY(add(l + "weight_hh" + sfx, 1536, 384));
+            DIMX_TRY(add(l + "bias_ih" + sfx, 1, 1536));
+            DIMX_TRY(add(l + "bias_hh" + sfx, 1, 1536));
+        }
+    DIMX_TRY(add("vertice_map_reverse.0.weight", 768, 768));
+    DIMX_TRY(add("vertice_map_reverse.0.bias", 1, 768));
+    DIMX_TRY(add("vertice_map_reverse.2.weight", h->d.mesh_dim, 768));
+    DIMX_TRY(add("vertice_map_reverse.2.bias", 1, h->d.mesh_dim));
+    return DIMX_OK;
+}
+TrainPlan* conv_plan_of(dimx_handle h, int* rc) {
+    *rc = DIMX_OK;
+    if (!h) {
+        *rc = DIMX_ERR_ARG;
+        set_error("train_conv: null handle");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lock(g_plans_mu);
+    auto key = std::make_pair(h, 2);   // beside the two VQ-VAE slots
+    auto& plans = vq_plans_map();
+    auto it = plans.find(key);
+    if (it == plans.end()) {
+        TrainPlan p;
+        *rc = build_conv_plan(h, p);
+        if (*rc != DIMX_OK) return nullptr;
+        it = plans.emplace(key, std::move(p)).first;
+    }
+    return &it->second;
+}
+LstmLayerP make_lstm_layer(const Step& s, int layer) {
+    LstmLayerP L;
+    const std::string l = "vertice_map_reverse_lstm.";
+    for (int dir = 0; dir < 2; ++dir) {
+        const std::string sfx = "_l" + std::to_string(layer) + (dir ? "_reverse" : "");
+        L.ih[dir] = make_lin(s, l + "weight_ih" + sfx, l + "bias_ih" + sfx);
+        L.hh[dir] = make_lin(s, l + "weight_hh" + sfx, l + "bias_hh" + sfx);
+    }
+    L.In = L.ih[0].K;
+    return L;
+}
+// the training forward of one layer: lstm.hip's own call (same kernels, same y) with the save switch
+int lstm_layer_fwd(Step& s, const LstmLayerP& L, const float* x, float* y, float* save, void* scr, size_t scr_bytes, int flags, int cu,
+                   int* faults) {
+    if (!s.live()) return DIMX_OK;
+    const float *w_ih[2], *w_hh[2], *b_ih[2], *b_hh[2];
+    for (int d = 0; d < 2; ++d) {
+        w_ih[d] = s.P + L.ih[d].w;
+        w_hh[d] = s.P + L.hh[d].w;
+        b_ih[d] = s.P + L.ih[d].b;
+        b_hh[d] = s.P + L.hh[d].b;
+    }
+    return lstm_layer_run(x, s.B, s.T, L.In, 384, w_ih, w_hh, b_ih, b_hh, y, scr, scr_bytes, flags, cu, faults, s.st, save);
+}
+// its adjoint: the recurrence leaves dG [M][2][4H]; per direction dW_ih = dG^T x, dW_hh = dG^T h_prev, d bias = colsum(dG),
+// dx (+)= dG W_ih on the library's GEMM.  dx may be null (the first layer's input carries no gradient).
+int lstm_layer_bwd(Step& s, const LstmLayerP& L, const float* x, const float* y, const float* save, const float* dy, float* dx, void* scr,
+                   size_t scr_bytes, int flags, int cu, int* faults) {
+    const int M = s.M, G4 = 1536;
+    float* dG = s.f32((size_t)M * 2 * G4);
+    float* hp = s.f32((size_t)M * 768);
+    if (s.live()) {
+        const float* w_hh[2] = {s.P + L.hh[0].w, s.P + L.hh[1].w};
+        DIMX_TRY(lstm_bwd_run(dy, save, w_hh, s.B, s.T, dG, scr, scr_bytes, flags, cu, faults, s.st));
+        DIMX_TRY(tr_lstm_hprev(y, hp, s.B, s.T, s.st));
+    }
+    for (int d = 0; d < 2; ++d) {
+        DIMX_TRY(lin_bwd(s, L.ih[d], x, L.In, dG + d * G4, 2 * G4, M, dx, L.In, d == 1));
+        DIMX_TRY(lin_bwd(s, L.hh[d], hp + d * 384, 768, dG + d * G4, 2 * G4, M, nullptr, 0, false));
+    }
+    return DIMX_OK;
+}
+size_t lstm_train_scratch_bytes(int B, int T, int In) {
+    return std::max(std::max(lstm_scratch_bytes(B, T, In), lstm_scratch_bytes(B, T, 768)), lstm_bwd_scratch_bytes(B, T));
+}
+void conv_step_init(Step& s, dimx_handle h, const TrainPlan* plan, const float* P, float* G, Arena* ar, hipStream_t st, int at, int B, int T) {
+    s.h = h; s.plan = plan; s.P = P; s.G = G; s.ar = ar; s.st = st;
+    s.at = at;
+    s.bk = at == DIMX_BF16 ? 64 : 32;
+    s.B = B; s.T = T; s.M = B * T;
+    s.n = T;
+    s.Md = B * T;
+    s.prep.n = 0;
+    s.prep.total_tiles = 0;
+    s.ts = nullptr;
+    s.use_side = false;
+    s.fin.n = 0;
+    s.fin.total_blocks = 0;
+    s.part = nullptr;
+}
 }  // namespace
 
 void train_forget(dimx_handle h) {
@@ -1316,6 +1433,7 @@ void train_forget(dimx_handle h) {
     plans_map().erase(h);
     vq_plans_map().erase(std::make_pair(h, 0));
     vq_plans_map().erase(std::make_pair(h, 1));
+    vq_plans_map().erase(std::make_pair(h, 2));   // the converter head's plan
 }
 
 }  // namespace dimx
@@ -2130,6 +2248,303 @@ int dimx_train_vq_forward_backward(dimx_handle h, int which, const float* params
     }
     return vq_run(h, which, params, grads, x, B, T, beta, quant_loss_weight, dropout_p, dropout_seed, (long)step, loss_out, pred_out, idx_out,
                   ws, ws_bytes, (hipStream_t)stream, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- DIM-Speaker converter
+// One forward + loss + backward pass of EmocaConverter's head (code/seq2seq_pretrain.py:801-842 under code/train_converter.py:
+// 17-96).  Forward: lstm.hip's layers with the save switch, then the two GEMMs of dimx_mesh_head with the same arguments (the f32
+// mode's mesh is that call's bit for bit).  The loss kernel leaves dY [M][Vp], Vp = V rounded up to 4 with zero pad columns (V =
+// 70110 is no multiple of 4; the operand copies move 16-byte groups).  Backward: the V-wide Linear by hand (its input adjoint
+// contracts over V in deterministic split-K slabs), the rest through lin_bwd.  want_bwd / have_mesh stand for grads / mesh_out in
+// the sizing pass.
+static int conv_run(dimx_handle h, const float* params, float* grads, const float* motion, const float* templ, const float* target,
+                    const float* vert_w, int n_mouth, int B, int T, int flags, float* loss_out, float* mesh_out, bool want_bwd, bool have_mesh,
+                    void* ws, size_t ws_bytes, hipStream_t st, size_t* need) {
+    int rc;
+    TrainPlan* plan = conv_plan_of(h, &rc);
+    if (!plan) return rc;
+    DIMX_REQUIRE(B >= 1 && T >= 1 && T <= 65536 && (long)B * T <= (1l << 20), DIMX_ERR_ARG, "train_conv: B=%d T=%d out of range", B, T);
+    const int V = h->d.mesh_dim, Vp = pad_to(V, 4), M = B * T;
+    Arena ar(ws, ws_bytes);
+    Step s;
+    conv_step_init(s, h, plan, params, grads, &ar, st, h->at, B, T);
+    const int Np = pad_to(V, s.bk), Mp = pad_to(M, s.bk);
+    s.pool_cap = want_bwd ? (size_t)8 * (ceil_div(M, 32) + 1) * 1536 + (size_t)(ceil_div(M, 32) + 1) * 768 + (size_t)kTrSlabs * Vp + 4096 : 64;
+    s.pool = s.f32(s.pool_cap);
+    s.pool_off = 0;
+
+    LstmLayerP L0 = make_lstm_layer(s, 0), L1 = make_lstm_layer(s, 1);
+    Lin l1 = make_lin(s, "vertice_map_reverse.0.weight", "vertice_map_reverse.0.bias");
+    Lin l2 = make_lin(s, "vertice_map_reverse.2.weight", "vertice_map_reverse.2.bias");
+    DIMX_TRY(prep_lin(s, l1));
+    DIMX_TRY(prep_lin(s, l2));
+    if (want_bwd) {
+        DIMX_TRY(prep_lin(s, L1.ih[0]));   // their transposed copies carry dG back to the first layer's output
+        DIMX_TRY(prep_lin(s, L1.ih[1]));
+    }
+    DIMX_TRY(flush_prep(s));
+
+    // ---------------- forward
+    const size_t scr_bytes = lstm_train_scratch_bytes(B, T, L0.In);
+    void* scr = s.take(scr_bytes);
+    float* y0 = s.f32((size_t)M * 768);
+    float* y1 = s.f32((size_t)M * 768);
+    const size_t n_save = (size_t)M * 2 * kLstmSave * 384;
+    float* save0 = want_bwd ? s.f32(n_save) : nullptr;
+    float* save1 = want_bwd ? s.f32(n_save) : nullptr;
+    DIMX_TRY(lstm_layer_fwd(s, L0, motion, y0, save0, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
+    DIMX_TRY(lstm_layer_fwd(s, L1, y0, y1, save1, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
+    float* a1 = s.f32((size_t)M * 768);
+    float* mesh = have_mesh ? mesh_out : s.f32((size_t)M * V);
+    const Step::OpCopy *c1, *c2;
+    DIMX_TRY(fwd_operands(s, y1, 768, M, 768, &c1));
+    if (s.live()) {
+        GemmArgs g;
+        gemm_args_init(g);
+        g.in_dtype = s.at;
+        g.out_dtype = DIMX_F32;
+        g.A = c1->o;
+        g.lda = c1->Kp;
+        g.W = l1.w_op;
+        g.ldw = c1->Kp;
+        g.M = M;
+        g.N = 768;
+        g.K = 768;
+        g.bias = s.P + l1.b;
+        g.act = ACT_LEAKY;
+        gemm_set_plain_out(g, a1, 768);
+        DIMX_TRY(launch_gemm(g, st));
+    }
+    DIMX_TRY(fwd_operands(s, a1, 768, M, 768, &c2));
+    if (s.live()) {
+        // N = mesh_dim is no multiple of any tile: the kernels clamp the W rows they load to N - 1 and store no column >= N
+        // (dimx_mesh_head); the template row of the clip rides the epilogue
+        GemmArgs g;
+        gemm_args_init(g);
+        g.in_dtype = s.at;
+        g.out_dtype = DIMX_F32;
+        g.A = c2->o;
+        g.lda = c2->Kp;
+        g.W = l2.w_op;
+        g.ldw = c2->Kp;
+        g.M = M;
+        g.N = V;
+        g.K = 768;
+        g.bias = s.P + l2.b;
+        g.rowT = T;
+        if (templ) {
+            g.rowadd = templ;
+            g.ld_rowadd = V;
+            g.rowadd_mode = 2;
+            g.rowadd_off = 0;
+        }
+        gemm_set_plain_out(g, mesh, V);
+        DIMX_TRY(launch_gemm(g, st));
+    }
+    float* lpart = s.f32((size_t)2 * tr_mesh_loss_parts(M, Vp));
+    float* dY = want_bwd ? s.f32((size_t)M * Vp) : nullptr;
+    TR(tr_mesh_loss(mesh, target, vert_w, n_mouth, M, V, Vp, dY, lpart, loss_out, st));
+
+    if (want_bwd) {
+        // ---------------- backward
+        if (s.live()) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+        float* da1 = s.f32((size_t)M * 768);
+        {
+            const size_t mark = ar.off;
+            void* dyo = s.take((size_t)M * Np * s.es());
+            void* dyT = s.take((size_t)Vp * Mp * s.es());
+            TR(tr_prep_fused(s.at, 0, dY, Vp, nullptr, 0, nullptr, M, Vp, dyo, Np, dyT, Mp, nullptr, nullptr, st));
+            // d bias [V]: Vp columns are summed (the pad columns of dY are zero) into the tensor's 16-byte pad inside the arena
+            {
+                float* part = s.pool_f32((size_t)kTrSlabs * Vp);
+                int n = M < kTrSlabs * 8 ? 1 : kTrSlabs;
+                if (s.live()) DIMX_TRY(tr_colsum_partial(dY, M, Vp, part, &n, st));
+                DIMX_TRY(queue_fin(s, part, s.G + l2.b, Vp, n));
+            }
+            // dW2 [V][768] = dY^T . A1 (contraction over the zero-padded rows)
+            DIMX_TRY(gemm_f32(s, dyT, Mp, c2->t, V, 768, Mp, s.G + l2.w, 768, nullptr, nullptr, 0));
+            // dA1 [M][768] = dY . W2: K = V.  Split into slabs of plain stores, added in slab order (no float atomics)
+            constexpr int kSplit = 8;
+            float* slabs = s.f32((size_t)kSplit * M * 768);
+            if (s.live()) {
+                GemmArgs g;
+                gemm_args_init(g);
+                g.in_dtype = s.at;
+                g.out_dtype = DIMX_F32;
+                g.A = dyo;
+                g.lda = Np;
+                g.W = l2.wt_op;
+                g.ldw = Np;
+                g.M = M;
+                g.N = 768;
+                g.K = Np;
+                g.out_slabs = 1;
+                g.force_splitk = kSplit;
+                g.slab_stride = (long)M * 768;
+                gemm_set_plain_out(g, slabs, 768);
+                const int sp = gemm_plan_splits(g);
+                DIMX_REQUIRE(sp >= 1 && sp <= kSplit, DIMX_ERR_STATE, "train_conv: %d split-K slabs planned", sp);
+                DIMX_TRY(launch_gemm(g, st));
+                DIMX_TRY(tr_sum_slabs(slabs, sp, (long)M * 768, da1, (long)M * 768, st));
+            }
+            ar.off = mark;
+        }
+        TR(tr_lrelu_bwd_out(a1, da1, (long)M * 768, 0.2f, st));
+        float* dy1 = s.f32((size_t)M * 768);
+        DIMX_TRY(lin_bwd(s, l1, y1, 768, da1, 768, M, dy1, 768, false));
+        float* dy0 = s.f32((size_t)M * 768);
+        DIMX_TRY(lstm_layer_bwd(s, L1, y0, y1, save1, dy1, dy0, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
+        DIMX_TRY(lstm_layer_bwd(s, L0, motion, y0, save0, dy0, nullptr, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
+        DIMX_TRY(flush_fin(s));
+    }
+    if (need) *need = s.peak + 256;
+    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_conv: the partial-row pool of the column reductions is too small");
+    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_conv: workspace %zu < required %zu", ws_bytes, s.peak);
+    return DIMX_OK;
+}
+
+int dimx_train_conv_num_params(dimx_handle h) {
+    int rc;
+    TrainPlan* p = conv_plan_of(h, &rc);
+    return p ? (int)p->params.size() : rc;
+}
+
+int64_t dimx_train_conv_total(dimx_handle h) {
+    int rc;
+    TrainPlan* p = conv_plan_of(h, &rc);
+    return p ? (int64_t)p->total : (int64_t)rc;
+}
+
+int dimx_train_conv_param_info(dimx_handle h, int i, const char** name, int64_t* offset, int64_t* numel) {
+    int rc;
+    TrainPlan* p = conv_plan_of(h, &rc);
+    if (!p) return rc;
+    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "train_conv_param_info: bad index");
+    *name = p->params[i].name.c_str();
+    *offset = p->params[i].off;
+    *numel = p->params[i].numel;
+    return DIMX_OK;
+}
+
+size_t dimx_train_conv_workspace_bytes(dimx_handle h, int B, int T) {
+    if (!h || B < 1 || T < 1) return 0;
+    size_t need = 0;
+    if (conv_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, T, 0, nullptr, nullptr, true, false, nullptr, 0, nullptr, &need) !=
+        DIMX_OK)
+        return 0;
+    return need;
+}
+
+int dimx_train_conv_forward_backward(dimx_handle h, const float* params, float* grads, const float* motion, const float* templ,
+                                     const float* target, const float* vert_w, int n_mouth, int B, int T, int flags, float* loss_out,
+                                     float* mesh_out, void* ws, size_t ws_bytes, void* stream) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "train_conv: null handle");
+    DIMX_REQUIRE(h->d.mesh_dim > 0, DIMX_ERR_STATE, "train_conv: the handle was created without a mesh head (dimx_dims.mesh_dim = 0)");
+    DIMX_REQUIRE(params && motion && target && loss_out && ws, DIMX_ERR_ARG, "train_conv: null argument");
+    DIMX_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)motion % 16) == 0,
+                 DIMX_ERR_ARG, "train_conv: workspace must be 256-byte aligned, arenas / input 16-byte aligned");
+    DIMX_REQUIRE(!vert_w || n_mouth >= 1, DIMX_ERR_ARG, "train_conv: vert_w needs n_mouth >= 1 (%d)", n_mouth);
+    DIMX_HIP(hipSetDevice(h->device));
+    {
+        size_t need = 0;
+        DIMX_TRY(conv_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, T, flags, nullptr, nullptr, grads != nullptr,
+                          mesh_out != nullptr, nullptr, 0, nullptr, &need));
+        DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_conv: workspace %zu < required %zu (dimx_train_conv_workspace_bytes)",
+                     ws_bytes, need);
+    }
+    return conv_run(h, params, grads, motion, templ, target, vert_w, n_mouth, B, T, flags, loss_out, mesh_out, grads != nullptr,
+                    mesh_out != nullptr, ws, ws_bytes, (hipStream_t)stream, nullptr);
+}
+
+int dimx_op_lstm_layer_bwd(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
+                           const float* const* b_ih, const float* const* b_hh, const float* dy, float* dx, float* const* dw_ih,
+                           float* const* dw_hh, float* const* db, int flags, int* faults_out, void* stream) {
+    DIMX_REQUIRE(dtype == DIMX_F32, DIMX_ERR_ARG, "lstm_layer_bwd: only the f32 recurrence is built (dtype %d)", dtype);
+    DIMX_REQUIRE(H == 384 && B >= 1 && T >= 1 && In >= 4 && In % 4 == 0 && (long)B * T <= (1l << 20), DIMX_ERR_ARG,
+                 "lstm_layer_bwd: bad shape (B=%d T=%d In=%d H=%d)", B, T, In, H);
+    DIMX_REQUIRE(x && dy && w_ih && w_hh && b_ih && b_hh && dw_ih && dw_hh && db, DIMX_ERR_ARG, "lstm_layer_bwd: null argument");
+    for (int d = 0; d < 2; ++d)
+        DIMX_REQUIRE(w_ih[d] && w_hh[d] && b_ih[d] && b_hh[d] && dw_ih[d] && dw_hh[d] && db[d], DIMX_ERR_ARG,
+                     "lstm_layer_bwd: null tensor (direction %d)", d);
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0, cus = 0;
+    DIMX_HIP(hipGetDevice(&dev));
+    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    // a one-layer plan over temporary arenas: the step's own helpers do the rest
+    TrainPlan plan;
+    LstmLayerP L;
+    L.In = In;
+    for (int d = 0; d < 2; ++d) {
+        const long sizes[4] = {1536l * In, 1536l * 384, 1536, 1536};
+        long offs[4];
+        for (int k = 0; k < 4; ++k) {
+            offs[k] = plan.total;
+            plan.total += (sizes[k] + 3) / 4 * 4;
+        }
+        L.ih[d].w = offs[0]; L.ih[d].N = 1536; L.ih[d].K = In; L.ih[d].b = offs[2];
+        L.hh[d].w = offs[1]; L.hh[d].N = 1536; L.hh[d].K = 384; L.hh[d].b = offs[3];
+    }
+    const int M = B * T;
+    int faults = 0;
+    float *P = nullptr, *G = nullptr;
+    void* ws = nullptr;
+    auto run = [&](Arena& ar, size_t* need) -> int {
+        Step s;
+        conv_step_init(s, nullptr, &plan, P, G, &ar, st, DIMX_F32, B, T);
+        s.pool_cap = (size_t)4 * (ceil_div(M, 32) + 1) * 1536 + 4096;
+        s.pool = s.f32(s.pool_cap);
+        s.pool_off = 0;
+        LstmLayerP Lr = L;
+        DIMX_TRY(prep_lin(s, Lr.ih[0]));
+        DIMX_TRY(prep_lin(s, Lr.ih[1]));
+        DIMX_TRY(flush_prep(s));
+        const size_t scr_bytes = lstm_train_scratch_bytes(B, T, In);
+        void* scr = s.take(scr_bytes);
+        float* y = s.f32((size_t)M * 768);
+        float* save = s.f32((size_t)M * 2 * kLstmSave * 384);
+        DIMX_TRY(lstm_layer_fwd(s, Lr, x, y, save, scr, scr_bytes, flags, cus, &faults));
+        DIMX_TRY(lstm_layer_bwd(s, Lr, x, y, save, dy, dx, scr, scr_bytes, flags, cus, &faults));
+        DIMX_TRY(flush_fin(s));
+        if (need) *need = s.peak + 256;
+        DIMX_REQUIRE(!s.pool_overflow && !ar.overflow, DIMX_ERR_WORKSPACE, "lstm_layer_bwd: scratch overflow");
+        return DIMX_OK;
+    };
+    size_t need = 0;
+    {
+        Arena dry(nullptr, 0);
+        DIMX_TRY(run(dry, &need));
+    }
+    hipError_t e = hipMalloc((void**)&P, (size_t)plan.total * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&G, (size_t)plan.total * 4);
+    if (e == hipSuccess) e = hipMalloc(&ws, need);
+    int rc = DIMX_OK;
+    if (e == hipSuccess) {
+        for (int d = 0; d < 2 && e == hipSuccess; ++d) {
+            e = hipMemcpyAsync(P + L.ih[d].w, w_ih[d], (size_t)1536 * In * 4, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(P + L.hh[d].w, w_hh[d], (size_t)1536 * 384 * 4, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(P + L.ih[d].b, b_ih[d], 1536 * 4, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(P + L.hh[d].b, b_hh[d], 1536 * 4, hipMemcpyDeviceToDevice, st);
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(G, 0, (size_t)plan.total * 4, st);
+        if (e == hipSuccess) {
+            Arena ar(ws, need);
+            rc = run(ar, nullptr);
+        }
+        for (int d = 0; d < 2 && e == hipSuccess && rc == DIMX_OK; ++d) {
+            e = hipMemcpyAsync(dw_ih[d], G + L.ih[d].w, (size_t)1536 * In * 4, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(dw_hh[d], G + L.hh[d].w, (size_t)1536 * 384 * 4, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(db[d], G + L.ih[d].b, 1536 * 4, hipMemcpyDeviceToDevice, st);
+        }
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (P) (void)hipFree(P);
+    if (G) (void)hipFree(G);
+    if (ws) (void)hipFree(ws);
+    if (faults_out) *faults_out = faults;
+    DIMX_TRY(rc);
+    DIMX_HIP(e);
+    DIMX_HIP(e2);
+    return DIMX_OK;
 }
 
 }  // extern "C"

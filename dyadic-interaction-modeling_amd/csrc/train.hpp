@@ -129,4 +129,12 @@ int tr_vq_finish(const float* part_q, int nq, const float* part_l, int nl, const
 int tr_vq_commit_bwd(const float* z, const float* book, const int32_t* idx, float* dz, int M, float coef, hipStream_t s);
 int tr_vq_book_grad(const float* z, const float* book, const int32_t* idx, float* dbook, int M, float coef, hipStream_t s);
 
+
+// DIM-Speaker converter step glue (train_lstm.hip)
+int tr_lstm_hprev(const float* y, float* hp, int B, int T, hipStream_t s);
+int tr_mesh_loss_parts(int M, int Vp);   // floats / 2 of the partial buffer tr_mesh_loss needs
+int tr_mesh_loss(const float* mesh, const float* target, const float* vert_w, int n_mouth, int M, int V, int Vp, float* dY, float* part,
+                 float* loss_out, hipStream_t s);
+int tr_sum_slabs(const float* slabs, int n, long stride, float* out, long count, hipStream_t s);
+
 }  // namespace dimx

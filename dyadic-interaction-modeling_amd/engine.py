@@ -376,6 +376,28 @@ def op_lstm_layer(x, w_ih, w_hh, b_ih, b_hh, safe=False, return_faults=False):
     return (y, faults.value) if return_faults else y
 
 
+def op_lstm_layer_bwd(x, w_ih, w_hh, b_ih, b_hh, dy, safe=False, need_dx=True, return_faults=False):
+    """The adjoint of one bidirectional LSTM layer (csrc/train_lstm.hip): x [B,T,In], dy [B,T,768] f32 and the weight pairs of
+    ``op_lstm_layer`` -> (dx [B,T,In] or None, dw_ih pair, dw_hh pair, db pair); db is the gradient of bias_ih and of bias_hh."""
+    lib = L.load()
+    dev = x.device
+    B, T, In = x.shape
+    H = w_hh[0].shape[1]
+    x_ = x.float().contiguous()
+    dy_ = dy.to(dev, torch.float32).contiguous()
+    keep = [[t.to(dev, torch.float32).contiguous() for t in pair] for pair in (w_ih, w_hh, b_ih, b_hh)]
+    arrs = [(ctypes.c_void_p * 2)(*(t.data_ptr() for t in pair)) for pair in keep]
+    outs = [[torch.empty_like(t) for t in keep[i]] for i in (0, 1, 2)]
+    oarrs = [(ctypes.c_void_p * 2)(*(t.data_ptr() for t in pair)) for pair in outs]
+    dx = torch.empty_like(x_) if need_dx else None
+    faults = ctypes.c_int(0)
+    L.check(lib.dimx_op_lstm_layer_bwd(L.F32, L.ptr(x_), B, T, In, H, arrs[0], arrs[1], arrs[2], arrs[3], L.ptr(dy_), L.ptr(dx),
+                                       oarrs[0], oarrs[1], oarrs[2], 1 if safe else 0, ctypes.byref(faults), L.stream_ptr(dev)),
+            "dimx_op_lstm_layer_bwd")
+    out = (dx, tuple(outs[0]), tuple(outs[1]), tuple(outs[2]))
+    return out + (faults.value,) if return_faults else out
+
+
 def op_layernorm(x, gamma, beta=None, out_bf16=False):
     lib = L.load()
     M, C = x.shape

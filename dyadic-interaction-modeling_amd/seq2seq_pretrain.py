@@ -451,7 +451,9 @@ class SpeakerSLMFT(_EngineOwner):
       * randomness is injectable like SLMFT's (``noise``, ``greedy``, ``seed``, ``temperature``), and
         ``return_tokens`` / ``return_mesh`` append the code indices / the mesh to the result;
       * gradients are not supported: every result is computed without an autograd graph, whatever the grad mode.
-        Training (``train_epoch_biwi``, ``train_converter.py``, the LSTM adjoint) is out of scope."""
+        Training this model (``train_epoch_biwi``) is out of scope; its converter head is trained through
+        ``EmocaConverter`` (``dimx.train_hip.ConverterHipTrainer``, examples/train_converter.py), whose ``best_converter.pt``
+        is what ``converter_ckpt`` loads."""
     engine_variant = "speaker"
 
     def __init__(self, config_path=None, mesh_dim=70110, mouth_map=None, numeric_mode=L.MODE_PARITY_F32,
@@ -576,10 +578,12 @@ class SpeakerSLMFT(_EngineOwner):
 
 
 class EmocaConverter(_EngineOwner):
-    """Drop-in ``EmocaConverter`` (reference ``code/seq2seq_pretrain.py:759-842``), inference only:
+    """Drop-in ``EmocaConverter`` (reference ``code/seq2seq_pretrain.py:759-842``):
     ``forward(inputs, template, v_speaker) -> (mesh [B,L,V], None)`` = ``vertice_map_reverse(vertice_map_reverse_lstm(
     speaker_vq(v_speaker)[0])) + template[:, None]``; ``inputs`` is unused, as in the reference (:829-831 are commented
-    out).  The state dict has the reference's keys (``speaker_vq.*`` and the converter tensors)."""
+    out).  The state dict has the reference's keys (``speaker_vq.*`` and the converter tensors).  ``forward`` builds no
+    autograd graph; the head is trained by ``dimx.train_hip.ConverterHipTrainer`` (forward and backward on the HIP library)
+    over ``dimx_trainable_parameters()``."""
     engine_variant = "speaker"
 
     def __init__(self, config_path=None, mesh_dim=70110, numeric_mode=L.MODE_PARITY_F32, synthetic_seed=20260928,
@@ -604,6 +608,12 @@ class EmocaConverter(_EngineOwner):
 
     def _engine_state_dict(self):
         return self.state_dict()
+
+    def dimx_trainable_parameters(self):
+        """the 20 tensors the reference's loop gives a gradient (``vertice_map_reverse_lstm.*``, ``vertice_map_reverse.*``), in
+        state-dict order: what ``ConverterHipTrainer`` keeps in its arenas.  ``speaker_vq.*`` is frozen."""
+        return [p for n, p in self.named_parameters()
+                if n.startswith("vertice_map_reverse_lstm.") or n.startswith("vertice_map_reverse.")]
 
     @torch.no_grad()
     def forward(self, inputs, template, v_speaker):

@@ -220,6 +220,53 @@ def vq_loss(P, x, masks=None, beta=0.25, quant_loss_weight=1.0, pre="", heads=8,
     return quant_loss_weight * quant + rec, rec, quant, perplexity, pred, idx
 
 
+def converter_head(P, motion):
+    """``vertice_map_reverse(vertice_map_reverse_lstm(motion))`` of EmocaConverter (reference code/seq2seq_pretrain.py:801-819,
+    applied at :834-836) with stock torch modules loaded from the state dict P: motion [B,T,56] -> [B,T,V], differentiable in P."""
+    pre = "vertice_map_reverse_lstm."
+    w0 = P[pre + "weight_ih_l0"]
+    lstm = torch.nn.LSTM(w0.shape[1], w0.shape[0] // 4, 2, batch_first=True, bidirectional=True).to(device=w0.device, dtype=w0.dtype)
+    flat = []
+    for layer in range(2):
+        for sfx in ("", "_reverse"):
+            flat += [P[pre + "%s_l%d%s" % (n, layer, sfx)] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    names = [n for n, _ in lstm.named_parameters()]
+    y, _ = torch.func.functional_call(lstm, dict(zip(names, flat)), (motion,))
+    a1 = F.leaky_relu(F.linear(y, P["vertice_map_reverse.0.weight"], P["vertice_map_reverse.0.bias"]), 0.2)
+    return F.linear(a1, P["vertice_map_reverse.2.weight"], P["vertice_map_reverse.2.bias"])
+
+
+def mouth_vertex_weights(mouth_map, n_vertices, device=None):
+    """[n_vertices] f32: how often each vertex occurs in ``mouth_map`` (duplicates count, as fancy indexing counts them)"""
+    idx = torch.as_tensor([int(i) for i in mouth_map], dtype=torch.long)
+    assert idx.numel() > 0 and int(idx.min()) >= 0 and int(idx.max()) < n_vertices, "mouth_map holds vertex indices in [0, V / 3)"
+    return torch.bincount(idx, minlength=n_vertices).to(torch.float32).to(device or "cpu")
+
+
+def converter_loss(model_or_sd, vertices, template, emoca, mouth_map=None, motion=None, vq_heads=8, vq_layers=6):
+    """Differentiable step of the reference's converter loop (code/train_converter.py:25-33 over EmocaConverter.forward,
+    code/seq2seq_pretrain.py:826-842): the PyTorch-autograd CHECKER of ``ConverterHipTrainer``.
+    model_or_sd: the module or {key: tensor}; vertices [B,T,V] (target), template [B,V] or None, emoca [B,T,56].  The frozen
+    speaker VQ-VAE runs without a graph in eval arithmetic (``motion`` [B,T,56] may be handed in instead, e.g. the HIP engine's);
+    the head is stock ``nn.LSTM`` / ``F.linear`` / ``F.leaky_relu``.  loss = mse + 5 * mse over ``mouth_map`` (mean over all B
+    clips; the reference's ``reshape(1, -1, V/3, 3)`` is B = 1, where the two agree).  Returns (loss, mse, mouth, mesh)."""
+    P = model_or_sd if isinstance(model_or_sd, dict) else dict(model_or_sd.state_dict(keep_vars=True))
+    if motion is None:
+        with torch.no_grad():
+            Pd = {k: v.detach() for k, v in P.items() if k.startswith("speaker_vq.")}
+            motion = vq_loss(Pd, emoca, pre="speaker_vq.", heads=vq_heads, layers=vq_layers)[4]
+    mesh = converter_head(P, motion.detach())
+    if template is not None:
+        mesh = mesh + template[:, None, :]
+    B, T, V = mesh.shape
+    mse = F.mse_loss(mesh, vertices)
+    mouth = mesh.new_zeros(())
+    if mouth_map is not None:
+        idx = torch.as_tensor([int(i) for i in mouth_map], dtype=torch.long, device=mesh.device)
+        mouth = F.mse_loss(mesh.reshape(B, T, V // 3, 3)[:, :, idx, :], vertices.reshape(B, T, V // 3, 3)[:, :, idx, :])
+    return mse + 5 * mouth, mse, mouth, mesh
+
+
 def legacy_loss(P, dims, vq_dims, x_speaker, z_l, v_listener, mask, pe, speaker_ids=None, listener_ids=None):
     """Differentiable ``ListenerGenerator.forward`` (reference code/seq2seq.py:235-278 with Transformer.forward :46-67).
     x_speaker [B,T,1024] and z_l [B,T] (-100 on padding) come from the frozen VQ-VAEs (HIP engine, no graph); ``pe`` is

@@ -449,3 +449,108 @@ class VqHipTrainer(HipTrainer):
         onehot = torch.zeros(idx.numel(), 512, dtype=torch.float32, device=self.device)
         onehot.scatter_(1, idx.long()[:, None], 1.0)
         return pred, d["quant_loss"], (d["perplexity"], onehot, idx.long()[:, None])
+
+
+class ConverterHipTrainer(HipTrainer):
+    """The DIM-Speaker converter's training step on the HIP kernels: reference loop code/train_converter.py:17-96 over
+    ``EmocaConverter.forward`` (code/seq2seq_pretrain.py:826-842) -- ``loss = mse(mesh, vertices) + 5 mse`` over the mouth vertices,
+    AdamW(lr 1e-5, torch's defaults otherwise).  What trains is the head ``dimx_mesh_head`` runs (20 tensors:
+    ``vertice_map_reverse_lstm.*`` and ``vertice_map_reverse.*``); forward, the LSTM's back-propagation through time and every
+    weight gradient run in libdimx_hip.so (csrc/train.hip conv_run, csrc/lstm.hip, csrc/train_lstm.hip).  The frozen speaker
+    VQ-VAE runs through the inference engine exactly as ``EmocaConverter.forward`` does (``vq_encode(0, ..., pe_mode=1)`` then
+    ``vq_decode``); its result is the head's input.  Same flat arenas, AdamW, optimiser-state import / export, ``sync_to_model()``
+    and ``all_reduce_grads()`` as HipTrainer; ``dimx.train.converter_loss`` (PyTorch autograd) is its checker
+    (tests/test_gpu_train_converter.py).
+
+    Reference behaviour kept, and deliberate differences:
+      * clipping: the reference calls ``clip_grad_norm_`` BEFORE ``backward()``, right after ``zero_grad()``
+        (train_converter.py:22,35-37); with its torch the gradients are None there, so its ``clip=1.0`` clips nothing.  The
+        drop-in default is therefore ``clip=0.0``; ``clip > 0`` clips the real gradients and is an opt-in;
+      * the reference's optimiser also holds ``vertice_mapping.*``, ``squasher.*``, ``vertice_map_reverse_lstm_2.*`` and
+        ``vertice_map_reverse2.*``; they never receive a gradient, so AdamW skips them (weight decay included).  They are not in
+        the arena and come back untouched from ``sync_to_model()``; ``speaker_vq.*`` is frozen;
+      * ``model.train()`` in the reference loop also flips the frozen VQ-VAE into train mode, so its two ``Dropout(0.1)`` fire
+        during training -- an accident of calling ``.train()`` on the parent.  Here the frozen VQ-VAE runs in eval arithmetic in
+        ``train_step`` and in ``evaluate``;
+      * batch size: the reference reshapes with a leading 1 (B = 1 only); here the loss is the mean over all B clips (equal at B = 1);
+      * ``mouth_map`` is passed in (the reference reads ``../data/CodeTalker/BIWI/regions/lve.txt``);
+      * the adjoint recurrence runs on the no-communication safe path on every device (the weight-stationary group kernel
+        exists for the forward only); ``flags`` bit 0 puts the forward on that path too."""
+
+    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=0.0, device=None):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip=clip, device=device)
+        self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._vw = {}
+
+    def _arena_layout(self, h):
+        n = self.lib.dimx_train_conv_num_params(h)
+        if n <= 0:
+            L.check(n, "dimx_train_conv_num_params")
+        layout = []
+        for i in range(n):
+            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
+            L.check(self.lib.dimx_train_conv_param_info(h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)),
+                    "dimx_train_conv_param_info")
+            layout.append((name.value.decode(), int(off.value), int(numel.value)))
+        return int(self.lib.dimx_train_conv_total(h)), layout
+
+    def graph_stats(self):
+        raise L.DimxError("the converter step is launched kernel by kernel (no captured graph)")
+
+    def vertex_weights(self, mouth_map):
+        """(the [V/3] f32 multiplicity vector of ``mouth_map`` on the device, len(mouth_map)); cached per map"""
+        from .train import mouth_vertex_weights
+        key = tuple(int(i) for i in mouth_map)
+        if key not in self._vw:
+            if len(self._vw) >= 4:
+                self._vw.pop(next(iter(self._vw)))
+            self._vw[key] = mouth_vertex_weights(key, self.model.mesh_dim // 3, self.device).contiguous()
+        return self._vw[key], len(key)
+
+    @torch.no_grad()
+    def motion(self, emoca):
+        """the frozen speaker VQ-VAE's reconstruction of ``emoca`` [B,T,56], as EmocaConverter.forward computes it"""
+        with self.model.engine_pinned():
+            eng = self.model.engine(self.device)
+            idx, _ = eng.vq_encode(0, emoca.to(self.device, torch.float32).contiguous(), None, pe_mode=1, return_z=True)
+            return eng.vq_decode(0, idx, 0).to(torch.float32).contiguous()
+
+    def _run(self, vertices, template, emoca, mouth_map, flags, with_grads, motion=None):
+        motion = self.motion(emoca) if motion is None else motion.to(self.device, torch.float32).contiguous()
+        B, T, _ = motion.shape
+        V = self.model.mesh_dim
+        target = vertices.to(self.device, torch.float32).reshape(B, T, V).contiguous()
+        templ = template.to(self.device, torch.float32).reshape(B, V).contiguous() if template is not None else None
+        vw, n_mouth = (None, 0) if mouth_map is None else self.vertex_weights(mouth_map)
+        need = int(self.lib.dimx_train_conv_workspace_bytes(self.eng.h, B, T))
+        if need == 0:
+            raise L.DimxError("dimx_train_conv_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
+        if need > self._ws_bytes:
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            self._ws_bytes = need
+        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
+        mesh = torch.empty(B, T, V, dtype=torch.float32, device=self.device)
+        L.check(self.lib.dimx_train_conv_forward_backward(
+            self.eng.h, L.ptr(self.params), L.ptr(self.grads) if with_grads else None, L.ptr(motion), L.ptr(templ), L.ptr(target),
+            L.ptr(vw), n_mouth, B, T, int(flags), L.ptr(self._loss), L.ptr(mesh), ws, self._ws.numel() - 256,
+            L.stream_ptr(self.device)), "dimx_train_conv_forward_backward")
+        out = self._loss.clone()
+        return {"loss": out[0], "mse": out[1], "mouth": out[2]}, mesh
+
+    def forward_backward(self, vertices, template, emoca, mouth_map=None, flags=0, motion=None):
+        """vertices [B,T,V] (target), template [B,V] or None, emoca [B,T,56] -> ({loss, mse, mouth} device scalars, mesh [B,T,V]);
+        gradients in ``self.grads``.  flags bit 0: the safe LSTM path."""
+        return self._run(vertices, template, emoca, mouth_map, flags, True, motion)
+
+    def evaluate(self, vertices, template, emoca, mouth_map=None, flags=0, motion=None):
+        """forward and loss only (the reference's evaluate_epoch body); ``self.grads`` is not touched"""
+        return self._run(vertices, template, emoca, mouth_map, flags, False, motion)
+
+    def train_step(self, vertices, template, emoca, mouth_map=None, flags=0):
+        """one optimisation step of the reference loop's body; returns (loss, mesh) like ``loss, vertices_pred`` there; the three
+        losses of the step are in ``self.last``."""
+        d, mesh = self.forward_backward(vertices, template, emoca, mouth_map=mouth_map, flags=flags)
+        self.all_reduce_grads()
+        self.step()
+        self.last = d
+        return d["loss"], mesh

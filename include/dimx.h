@@ -323,6 +323,36 @@ size_t dimx_train_vq_workspace_bytes(dimx_handle h, int B, int T);
 int dimx_train_vq_forward_backward(dimx_handle h, int which, const float* params, float* grads, const float* x, int B, int T, float beta,
                                    float quant_loss_weight, float dropout_p, uint64_t dropout_seed, int64_t step, float* loss_out,
                                    float* pred_out, int32_t* idx_out, void* ws, size_t ws_bytes, void* stream);
+/* ---- DIM-Speaker converter training step: reference EmocaConverter (code/seq2seq_pretrain.py:759-842) under the loop of
+ * code/train_converter.py:17-96.  What trains is the head of dimx_mesh_head -- the 2-layer bidirectional LSTM(384),
+ * Linear(768,768), LeakyReLU(0.2), Linear(768,V) -- 20 tensors under their state-dict names
+ * vertice_map_reverse_lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_l{0,1}[_reverse] and vertice_map_reverse.{0,2}.{weight,bias}, in
+ * flat f32 arenas (tensors 16-byte aligned) as for the other steps.  The handle must be a speaker handle with mesh_dim > 0
+ * (DIMX_ERR_STATE otherwise).  The frozen speaker VQ-VAE is NOT part of the call: motion is its output (dimx_vq_encode /
+ * dimx_vq_decode), as EmocaConverter.forward computes it. */
+int dimx_train_conv_num_params(dimx_handle h);
+int64_t dimx_train_conv_total(dimx_handle h);
+int dimx_train_conv_param_info(dimx_handle h, int i, const char** name, int64_t* offset, int64_t* numel);
+size_t dimx_train_conv_workspace_bytes(dimx_handle h, int B, int T);
+/* One forward + loss + backward pass.  motion [B,T,56], templ [B,V] or NULL, target [B,T,V], all f32.
+ *   mesh = head(motion) + templ;  loss = mse(mesh, target) + 5 mse over the mouth vertices
+ * vert_w [V/3] f32 or NULL: entry v = how often vertex v occurs in the mouth map (duplicates count, as the reference's fancy
+ * indexing counts them), n_mouth = the length of that map; NULL = no mouth term.  The mean runs over all B clips (the reference
+ * is written for B = 1, where the two agree).  loss_out: 3 device floats {total, full-mesh mse, mouth mse}.  grads == NULL:
+ * forward and loss only (the reference's evaluate_epoch).  mesh_out optional [B,T,V]; in the f32 mode it equals
+ * dimx_mesh_head's result on the same path bit for bit.  flags bit 0 = the safe LSTM path (see dimx_mesh_head).  The LSTM
+ * recurrences, forward and adjoint, are f32 in both numeric modes; the Linear layers and every weight-gradient product take the
+ * handle's operand type.  Launched kernel by kernel, no captured graph; the forward group path WAITS on the host for its fault
+ * word like dimx_mesh_head (reruns are counted in dimx_lstm_faults).  Deterministic: no float atomics, a rerun is bit-identical. */
+int dimx_train_conv_forward_backward(dimx_handle h, const float* params, float* grads, const float* motion, const float* templ,
+                                     const float* target, const float* vert_w, int n_mouth, int B, int T, int flags, float* loss_out,
+                                     float* mesh_out, void* ws, size_t ws_bytes, void* stream);
+/* The adjoint of one bidirectional LSTM layer alone (unit parity): x [B,T,In], the four weight sets as dimx_op_lstm_layer takes
+ * them, dy [B,T,2H] -> dx [B,T,In] (optional), dw_ih[d] [4H,In], dw_hh[d] [4H,H], db[d] [4H] (= d bias_ih = d bias_hh).  f32
+ * only.  It runs the training forward first.  Allocates its scratch and synchronises the stream. */
+int dimx_op_lstm_layer_bwd(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
+                           const float* const* b_ih, const float* const* b_hh, const float* dy, float* dx, float* const* dw_ih,
+                           float* const* dw_hh, float* const* db, int flags, int* faults_out, void* stream);
 /* Gradient clipping (torch.nn.utils.clip_grad_norm_, max_norm <= 0: none) + one torch.optim.AdamW step over a flat arena.
  * step: 1-based step count (bias correction).  scratch: >= 1026 device floats; scratch[1024] = gradient norm before clipping,
  * scratch[1025] = the clip coefficient applied. */
