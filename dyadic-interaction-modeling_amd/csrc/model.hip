@@ -1017,6 +1017,9 @@ int dimx_load_weights(dimx_handle h, const dimx_weight_desc* descs, int n) {
                 continue;
             }
             DIMX_REQUIRE(ignorable_key(name), DIMX_ERR_WEIGHT, "unknown weight key %s", w.name);
+            // the speaker-id embedding stays on the host side of inference; only its row count is kept (dimx_train_spk_*)
+            if (name == "speaker_embed.weight" && w.ndim == 2 && w.shape[1] == h->d.dim && w.shape[0] >= 1 && w.shape[0] <= (1 << 20))
+                h->spk_embed_rows = (int)w.shape[0];
             continue;
         }
         DIMX_REQUIRE((int)it->second.size() == w.ndim, DIMX_ERR_WEIGHT, "%s: rank %d, expected %d", w.name, w.ndim,

@@ -192,4 +192,6 @@ struct dimx_ctx {
     int shard_row_off = 0, shard_rows_total = 0;
     dimx::MeshHead mesh;                // handles created with dimx_dims.mesh_dim > 0
     int lstm_faults = 0;                // LSTM layers whose group kernel reported a fault and that were rerun on the safe path
+    int spk_embed_rows = 0;             // rows of speaker_embed.weight as last loaded (the host applies it in inference; the
+                                        // DIM-Speaker training step lays its arena out by it); 0 = never loaded
 };

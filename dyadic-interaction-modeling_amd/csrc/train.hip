@@ -1411,6 +1411,108 @@ int lstm_layer_bwd(Step& s, const LstmLayerP& L, const float* x, const float* y,
 size_t lstm_train_scratch_bytes(int B, int T, int In) {
     return std::max(std::max(lstm_scratch_bytes(B, T, In), lstm_scratch_bytes(B, T, 768)), lstm_bwd_scratch_bytes(B, T));
 }
+// ---------------------------------------------------------------------------------------------------------------- DIM-Speaker step plan
+// The arenas of the DIM-Speaker fine-tuning step: what SpeakerSLMFT.forward(mode='train') (code/seq2seq_pretrain.py:708-757) leaves a
+// gradient on -- the cross entropy reaches decoder_joint.* (positional table included), patch_embed_dec_l and speaker_embed.weight
+// (dense: AdamW decays the rows no clip names too), the EMOCA loss reaches speaker_vq.decoder.* only (the arg-max cuts the graph).
+// Everything else keeps grad = None in the reference (its AdamW and its clip norm skip those tensors) and is not in the arena.
+int build_spk_plan(dimx_handle h, TrainPlan& p) {
+    const dimx_dims& d = h->d;
+    DIMX_REQUIRE(h->variant == 2 && d.mesh_dim > 0, DIMX_ERR_STATE,
+                 "train_spk: the handle is not a speaker handle (variant 2 with dimx_dims.mesh_dim > 0)");
+    DIMX_REQUIRE(h->spk_embed_rows > 0, DIMX_ERR_WEIGHT, "train_spk: speaker_embed.weight [rows, %d] was not loaded", d.dim);
+    for (const auto& kv : h->host) {
+        const std::string& nm = kv.first;
+        const bool opt = nm.size() > 16 && (nm.compare(nm.size() - 15, 15, "project_in.bias") == 0 || nm.compare(nm.size() - 14, 14, "to_logits.bias") == 0);
+        DIMX_REQUIRE(!opt, DIMX_ERR_STATE, "train_spk: %s is loaded; the training step implements the bias-free project_in / to_logits only", nm.c_str());
+    }
+    auto add = [&](const std::string& name, int rows, int cols, bool held = true) -> int {
+        const long n = (long)rows * cols;
+        if (held) {
+            auto it = h->host.find(name);
+            DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "train_spk: weight %s was not loaded", name.c_str());
+            long have = 1;
+            for (auto sz : it->second.shape) have *= sz;
+            DIMX_REQUIRE(have == n, DIMX_ERR_WEIGHT, "train_spk: %s has %ld elements, expected %d x %d", name.c_str(), have, rows, cols);
+        }
+        PInfo pi{name, p.total, n, rows, cols};
+        p.index[name] = (int)p.params.size();
+        p.params.push_back(pi);
+        p.total += (n + 3) / 4 * 4;  // 16-byte aligned tensors
+        return DIMX_OK;
+    };
+    const int inner = d.heads * d.dim_head, DD = d.dim + d.dim_a, H = d.vq_hidden, I = d.vq_inter;
+    DIMX_TRY(add("patch_embed_dec_l", 1, d.dim));
+    const std::string dn = "decoder_joint.net.";
+    DIMX_TRY(add(dn + "token_emb.emb.weight", d.num_tokens, DD));
+    DIMX_TRY(add(dn + "pos_emb.emb.weight", d.max_seq_len, DD));
+    for (int i = 0; i < d.dec_depth; ++i) {
+        for (int k = 0; k < 2; ++k) {
+            const std::string la = dn + "attn_layers.layers." + std::to_string(3 * i + k) + ".";
+            DIMX_TRY(add(la + "0.0.weight", 1, DD));
+            DIMX_TRY(add(la + "1.to_q.weight", inner, DD));
+            DIMX_TRY(add(la + "1.to_k.weight", inner, DD));
+            DIMX_TRY(add(la + "1.to_v.weight", inner, DD));
+            DIMX_TRY(add(la + "1.to_out.weight", DD, inner));
+        }
+        const std::string lf = dn + "attn_layers.layers." + std::to_string(3 * i + 2) + ".";
+        DIMX_TRY(add(lf + "0.0.weight", 1, DD));
+        DIMX_TRY(add(lf + "1.ff.0.0.weight", DD * d.ff_mult, DD));
+        DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, DD * d.ff_mult));
+        DIMX_TRY(add(lf + "1.ff.2.weight", DD, DD * d.ff_mult));
+        DIMX_TRY(add(lf + "1.ff.2.bias", 1, DD));
+    }
+    DIMX_TRY(add(dn + "attn_layers.final_norm.weight", 1, DD));
+    DIMX_TRY(add(dn + "to_logits.weight", d.num_tokens, DD));
+    const std::string c = "speaker_vq.decoder.";
+    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.weight", H, d.vq_zdim));
+    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
+    DIMX_TRY(add(c + "expander.0.0.weight", H, 5 * H));
+    DIMX_TRY(add(c + "expander.0.0.bias", 1, H));
+    DIMX_TRY(add(c + "decoder_linear_embedding.net.weight", H, H));
+    DIMX_TRY(add(c + "decoder_linear_embedding.net.bias", 1, H));
+    for (int i = 0; i < d.vq_layers; ++i) {
+        const std::string a = c + "decoder_transformer.net." + std::to_string(2 * i) + ".fn.";
+        const std::string m = c + "decoder_transformer.net." + std::to_string(2 * i + 1) + ".fn.";
+        DIMX_TRY(add(a + "norm.weight", 1, H));
+        DIMX_TRY(add(a + "norm.bias", 1, H));
+        DIMX_TRY(add(a + "fn.to_qkv.weight", 3 * H, H));
+        DIMX_TRY(add(a + "fn.to_out.weight", H, H));
+        DIMX_TRY(add(a + "fn.to_out.bias", 1, H));
+        DIMX_TRY(add(m + "norm.weight", 1, H));
+        DIMX_TRY(add(m + "norm.bias", 1, H));
+        DIMX_TRY(add(m + "fn.l1.weight", I, H));
+        DIMX_TRY(add(m + "fn.l1.bias", 1, I));
+        DIMX_TRY(add(m + "fn.l2.weight", H, I));
+        DIMX_TRY(add(m + "fn.l2.bias", 1, H));
+    }
+    DIMX_TRY(add(c + "vertice_map_reverse.weight", d.vq_in_dim, H));
+    DIMX_TRY(add("speaker_embed.weight", h->spk_embed_rows, d.dim, false));   // not held by the engine: the shape it was loaded with
+    return DIMX_OK;
+}
+TrainPlan* spk_plan_of(dimx_handle h, int* rc) {
+    *rc = DIMX_OK;
+    if (!h) {
+        *rc = DIMX_ERR_ARG;
+        set_error("train_spk: null handle");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lock(g_plans_mu);
+    auto key = std::make_pair(h, 3);   // beside the two VQ-VAE slots and the converter head
+    auto& plans = vq_plans_map();
+    auto it = plans.find(key);
+    if (it != plans.end() && it->second.params.back().rows != h->spk_embed_rows) {   // the embedding was reloaded with another row count
+        plans.erase(it);
+        it = plans.end();
+    }
+    if (it == plans.end()) {
+        TrainPlan p;
+        *rc = build_spk_plan(h, p);
+        if (*rc != DIMX_OK) return nullptr;
+        it = plans.emplace(key, std::move(p)).first;
+    }
+    return &it->second;
+}
 void conv_step_init(Step& s, dimx_handle h, const TrainPlan* plan, const float* P, float* G, Arena* ar, hipStream_t st, int at, int B, int T) {
     s.h = h; s.plan = plan; s.P = P; s.G = G; s.ar = ar; s.st = st;
     s.at = at;
@@ -1434,6 +1536,7 @@ void train_forget(dimx_handle h) {
     vq_plans_map().erase(std::make_pair(h, 0));
     vq_plans_map().erase(std::make_pair(h, 1));
     vq_plans_map().erase(std::make_pair(h, 2));   // the converter head's plan
+    vq_plans_map().erase(std::make_pair(h, 3));   // the DIM-Speaker step's plan
 }
 
 }  // namespace dimx
@@ -2454,6 +2557,155 @@ int dimx_train_conv_forward_backward(dimx_handle h, const float* params, float* 
     }
     return conv_run(h, params, grads, motion, templ, target, vert_w, n_mouth, B, T, flags, loss_out, mesh_out, grads != nullptr,
                     mesh_out != nullptr, ws, ws_bytes, (hipStream_t)stream, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- DIM-Speaker fine-tuning
+// One forward + backward pass of SpeakerSLMFT.forward(mode='train') as the reference's speaker branch differentiates it
+// (code/finetune_s2s_pretrain.py -> train_epoch_biwi, code/x_engine_pt.py:62-132, over code/seq2seq_pretrain.py:708-757): the
+// context cat(speaker_embed[id] + patch_embed_dec_l, audio), the teacher-forced decoder with absolute positions and no key masking,
+// cross entropy over the listener VQ-VAE's codes of the EMOCA stream, and the mean squared error of the decoded arg-max codes
+// through the SPEAKER VQ-VAE's decoder, which it trains.  The mesh head is not part of the step: it only reports a metric and no
+// gradient reaches it.  Launched kernel by kernel on the caller's stream (no side stream, no captured graph).
+static int spk_run(dimx_handle h, const float* params, float* grads, const float* v_emoca, const float* v_audio, const uint8_t* mask,
+                   const int32_t* z, const int32_t* speaker_ids, const float* codebook_s, const float* pe_s, int B, int T, float* loss_out,
+                   float* logits_out, int32_t* idx_out, float* pred_out, void* ws, size_t ws_bytes, hipStream_t st, size_t* need) {
+    int rc;
+    TrainPlan* plan = spk_plan_of(h, &rc);
+    if (!plan) return rc;
+    const dimx_dims& d = h->d;
+    DIMX_REQUIRE(B >= 1 && T >= 2 && T - 1 <= d.max_seq_len, DIMX_ERR_ARG, "train_spk: B=%d T=%d out of range (T - 1 <= %d)", B, T, d.max_seq_len);
+    DIMX_REQUIRE(d.num_tokens == 512 && d.vq_in_dim == 56 && d.dim % 4 == 0 && d.dim_a % 4 == 0 && d.dim_a > 0, DIMX_ERR_ARG,
+                 "train_spk: 512 codes, 56 coefficients, an audio stream");
+    Arena ar(ws, ws_bytes);
+    Step s;
+    s.h = h; s.plan = plan; s.P = params; s.G = grads; s.ar = &ar; s.st = st;
+    s.at = h->at;
+    s.bk = h->at == DIMX_BF16 ? 64 : 32;
+    s.B = B; s.T = T; s.M = B * T;
+    s.n = T - 1;
+    s.Md = B * (T - 1);
+    s.prep.n = 0;
+    s.prep.total_tiles = 0;
+    s.ts = nullptr;
+    s.use_side = false;
+    const int C = d.dim, DD = d.dim + d.dim_a, F = std::max(DD * d.ff_mult, d.vq_inter), n = T - 1, BT = B * T;
+    const int rows = plan->params[plan->index.at("speaker_embed.weight")].rows;
+    s.part = s.f32((size_t)2 * kTrSlabs * F);
+    {   // partial rows of the deferred column reductions
+        const size_t n_ln_c = (size_t)(4 * d.vq_layers + 8), n_ln_dd = (size_t)(3 * d.dec_depth + 2);
+        const size_t n_b = (size_t)(2 * d.dec_depth + 3 * d.vq_layers + 16);
+        s.pool_cap = n_ln_c * (kLnBlocks + 4) * (size_t)std::max(C, d.vq_hidden) + n_ln_dd * (kLnBlocks + 4) * (size_t)DD +
+                     n_b * (size_t)std::max(kTrSlabs, ceil_div(BT, 32) + 1) * (size_t)F + 4096;
+        s.pool = s.f32(s.pool_cap);
+        s.pool_off = 0;
+        s.fin.n = 0;
+        s.fin.total_blocks = 0;
+    }
+    const bool live = ws != nullptr;
+    if (live) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+
+    // ---------------- context, tokens
+    float* ctx = s.f32((size_t)BT * DD);
+    TR(tr_spk_context(s.p("speaker_embed.weight"), speaker_ids, s.p("patch_embed_dec_l"), v_audio, ctx, B, T, C, d.dim_a, st));
+    int32_t* inp = (int32_t*)s.take((size_t)B * n * 4);
+    int32_t* tgt = (int32_t*)s.take((size_t)B * n * 4);
+    TR(launch_shift_tokens(z, inp, tgt, B, T, st));
+    DecSave D;
+    DIMX_TRY(dec_prepare(s, D, "decoder_joint.net.", d.dec_depth));
+    DIMX_TRY(flush_prep(s));
+    float* logits = logits_out ? logits_out : s.f32((size_t)B * n * d.num_tokens);
+    DIMX_TRY(dec_fwd(s, D, inp, B, n, ctx, T, DD, mask, nullptr, true, logits));
+    float* dlogits = s.f32((size_t)B * n * d.num_tokens);
+    float* row_loss = s.f32((size_t)B * n);
+    TR(tr_cross_entropy(logits, tgt, row_loss, dlogits, B * n, loss_out, st));
+    // ---------------- decoded arg-max codes -> the speaker VQ-VAE's decoder -> mean squared error against v_emoca[:, 1:], padded frames included
+    int32_t* idx = idx_out ? idx_out : (int32_t*)s.take((size_t)B * n * 4);
+    TR(tr_argmax512(logits, idx, B, n, n, 0, st));
+    float* pred = pred_out ? pred_out : s.f32((size_t)B * n * d.vq_in_dim);
+    VqDecSave V;
+    DIMX_TRY(vqdec_fwd(s, V, "speaker_vq.decoder.", idx, codebook_s, pe_s, B, n, pred));
+    float* dpred = s.f32((size_t)B * n * d.vq_in_dim);
+    float* mse_part = s.f32((size_t)kSpkMseParts);
+    TR(tr_spk_mse(pred, v_emoca, dpred, B, T, d.vq_in_dim, mse_part, loss_out + 2, st));
+
+    // ---------------- backward
+    DIMX_TRY(vqdec_bwd(s, V, dpred));
+    float* dctx = s.f32((size_t)BT * DD);
+    if (live) DIMX_HIP(hipMemsetAsync(dctx, 0, (size_t)BT * DD * sizeof(float), st));
+    DIMX_TRY(dec_bwd(s, D, dlogits, dctx));
+    // the audio columns of the context have no parameters behind them; the first dim columns are the embedding row + the patch
+    float* cpart = s.f32(tr_spk_context_bwd_floats(B, C));
+    TR(tr_spk_context_bwd(dctx, speaker_ids, s.g("speaker_embed.weight"), s.g("patch_embed_dec_l"), cpart, B, T, C, DD, rows, st));
+    DIMX_TRY(flush_fin(s));
+    if (need) *need = s.peak + 256;
+    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_spk: the partial-row pool of the column reductions is too small");
+    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_spk: workspace %zu < required %zu", ws_bytes, s.peak);
+    return DIMX_OK;
+}
+
+int dimx_train_spk_num_params(dimx_handle h) {
+    int rc;
+    TrainPlan* p = spk_plan_of(h, &rc);
+    return p ? (int)p->params.size() : rc;
+}
+
+int64_t dimx_train_spk_total(dimx_handle h) {
+    int rc;
+    TrainPlan* p = spk_plan_of(h, &rc);
+    return p ? (int64_t)p->total : (int64_t)rc;
+}
+
+int dimx_train_spk_param_info(dimx_handle h, int i, const char** name, int64_t* offset, int64_t* numel) {
+    int rc;
+    TrainPlan* p = spk_plan_of(h, &rc);
+    if (!p) return rc;
+    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "train_spk_param_info: bad index");
+    *name = p->params[i].name.c_str();
+    *offset = p->params[i].off;
+    *numel = p->params[i].numel;
+    return DIMX_OK;
+}
+
+size_t dimx_train_spk_workspace_bytes(dimx_handle h, int B, int T) {
+    if (!h || B < 1 || T < 2) return 0;
+    size_t need = 0;
+    if (spk_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr, nullptr, nullptr, nullptr,
+                nullptr, 0, nullptr, &need) != DIMX_OK)
+        return 0;
+    return need;
+}
+
+int dimx_train_spk_forward_backward(dimx_handle h, const float* params, float* grads, const float* v_emoca, const float* v_audio,
+                                    const uint8_t* mask, const int32_t* z, const int32_t* speaker_ids, const float* codebook_s,
+                                    const float* pe_s, int B, int T, float* loss_out, float* logits_out, int32_t* idx_out, float* pred_out,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    DIMX_REQUIRE(h && params && grads && v_emoca && v_audio && mask && z && codebook_s && pe_s && loss_out && ws, DIMX_ERR_ARG,
+                 "train_spk: null argument");
+    DIMX_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)v_emoca % 16) == 0 &&
+                     ((uintptr_t)v_audio % 16) == 0 && ((uintptr_t)codebook_s % 16) == 0 && ((uintptr_t)pe_s % 16) == 0 &&
+                     ((uintptr_t)pred_out % 16) == 0,
+                 DIMX_ERR_ARG, "train_spk: workspace must be 256-byte aligned, arenas / inputs / codebook / pe / pred_out 16-byte aligned");
+    DIMX_HIP(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    size_t need = 0;
+    // the sizing pass walks the live pass's allocations: an output handed in replaces its workspace buffer there too
+    DIMX_TRY(spk_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr,
+                     logits_out ? (float*)0x100 : nullptr, idx_out ? (int32_t*)0x100 : nullptr, pred_out ? (float*)0x100 : nullptr, nullptr, 0,
+                     nullptr, &need));
+    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_spk: workspace %zu < required %zu (dimx_train_spk_workspace_bytes)", ws_bytes, need);
+    if (speaker_ids) {   // an id outside the table is refused here, on the host: the kernels index with it unchecked
+        int rc;
+        TrainPlan* plan = spk_plan_of(h, &rc);
+        if (!plan) return rc;
+        const int rows = plan->params[plan->index.at("speaker_embed.weight")].rows;
+        std::vector<int32_t> ids((size_t)B);
+        DIMX_HIP(hipMemcpyAsync(ids.data(), speaker_ids, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        DIMX_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < B; ++b)
+            DIMX_REQUIRE(ids[b] >= 0 && ids[b] < rows, DIMX_ERR_ARG, "train_spk: speaker_ids[%d] = %d is outside [0, %d)", b, ids[b], rows);
+    }
+    return spk_run(h, params, grads, v_emoca, v_audio, mask, z, speaker_ids, codebook_s, pe_s, B, T, loss_out, logits_out, idx_out, pred_out, ws,
+                   ws_bytes, st, nullptr);
 }
 
 int dimx_op_lstm_layer_bwd(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,

@@ -137,4 +137,19 @@ int tr_mesh_loss(const float* mesh, const float* target, const float* vert_w, in
                  float* loss_out, hipStream_t s);
 int tr_sum_slabs(const float* slabs, int n, long stride, float* out, long count, hipStream_t s);
 
+// DIM-Speaker fine-tuning step glue (train_spk.hip)
+constexpr int kSpkSlices = 8;      // time slices of the context adjoint's per-clip sums
+constexpr int kSpkMseParts = 256;  // most per-block partials of the EMOCA loss
+// ctx [B*T][C + A] = cat(embed[ids[b]] (zero when ids == NULL) + patch, audio [B*T][A]); C, A multiples of 4, 16-byte aligned operands
+int tr_spk_context(const float* embed, const int32_t* ids, const float* patch, const float* audio, float* ctx, int B, int T, int C, int A,
+                   hipStream_t s);
+size_t tr_spk_context_bwd_floats(int B, int C);   // floats of `part` below
+// columns [0, C) of dctx [B*T][DD] -> d_patch [C] and the dense d_embed [rows][C] (d_embed may be NULL with rows = 0; ids == NULL
+// leaves every row zero)
+int tr_spk_context_bwd(const float* dctx, const int32_t* ids, float* d_embed, float* d_patch, float* part, int B, int T, int C, int DD,
+                       int rows, hipStream_t s);
+// out2 = {mean((pred - tgt[:, 1:])^2), 1 / elements}, dpred = 2 / elements (pred - tgt[:, 1:]); pred / dpred [B][T-1][F], tgt [B][T][F];
+// part: kSpkMseParts floats
+int tr_spk_mse(const float* pred, const float* tgt, float* dpred, int B, int T, int F, float* part, float* out2, hipStream_t s);
+
 }  // namespace dimx

@@ -96,6 +96,12 @@ SIGNATURES = {
     "dimx_train_conv_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "dimx_train_conv_forward_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                                  c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dimx_train_spk_num_params": (c_int, [c_void_p]),
+    "dimx_train_spk_total": (c_int64, [c_void_p]),
+    "dimx_train_spk_param_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),
+    "dimx_train_spk_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "dimx_train_spk_forward_backward": (c_int, [c_void_p] + [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_size_t, c_void_p]),
     "dimx_op_lstm_layer_bwd": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p),
                                        POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p),
                                        POINTER(c_void_p), c_int, POINTER(c_int), c_void_p]),

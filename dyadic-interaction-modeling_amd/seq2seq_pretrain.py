@@ -430,7 +430,7 @@ class SLM(_EngineOwner):
 
 
 class SpeakerSLMFT(_EngineOwner):
-    """Drop-in ``SpeakerSLMFT`` (DIM-Speaker, reference ``code/seq2seq_pretrain.py:516-757``), inference only:
+    """Drop-in ``SpeakerSLMFT`` (DIM-Speaker, reference ``code/seq2seq_pretrain.py:516-757``):
     ``forward(v_speaker, v_speaker_emoca, v_audio, mask, template, mode, speaker_ids) -> (total_loss, d,
     pred_cont_seq_s_emoca [B,T-1,56])`` on the HIP library -- the SLM-geometry decoder (absolute positional embedding,
     context ``cat(x_l + patch_embed_dec_l, v_audio)``, teacher forcing without key masking: the reference builds its
@@ -450,10 +450,12 @@ class SpeakerSLMFT(_EngineOwner):
         inside ``forward_vq``);
       * randomness is injectable like SLMFT's (``noise``, ``greedy``, ``seed``, ``temperature``), and
         ``return_tokens`` / ``return_mesh`` append the code indices / the mesh to the result;
-      * gradients are not supported: every result is computed without an autograd graph, whatever the grad mode.
-        Training this model (``train_epoch_biwi``) is out of scope; its converter head is trained through
-        ``EmocaConverter`` (``dimx.train_hip.ConverterHipTrainer``, examples/train_converter.py), whose ``best_converter.pt``
-        is what ``converter_ckpt`` loads."""
+      * ``forward`` builds no autograd graph, whatever the grad mode.  Training lives beside it: the fine-tuning step of
+        the reference's ``train_epoch_biwi`` is ``dimx.train_hip.SpeakerHipTrainer`` (forward and backward on the HIP
+        library, over ``dimx_trainable_parameters()``), driven by ``dimx.x_engine_pt.train_epoch_biwi``;
+        ``dimx.train.speaker_loss`` is its PyTorch-autograd checker.  The converter head receives no gradient there; it is
+        trained through ``EmocaConverter`` (``dimx.train_hip.ConverterHipTrainer``, examples/train_converter.py), whose
+        ``best_converter.pt`` is what ``converter_ckpt`` loads."""
     engine_variant = "speaker"
 
     def __init__(self, config_path=None, mesh_dim=70110, mouth_map=None, numeric_mode=L.MODE_PARITY_F32,
@@ -487,6 +489,13 @@ class SpeakerSLMFT(_EngineOwner):
 
     def _engine_state_dict(self):
         return self.state_dict()
+
+    def dimx_trainable_parameters(self):
+        """(name, parameter) of what the reference's fine-tuning step gives a gradient, in state-dict order:
+        ``decoder_joint.*``, ``patch_embed_dec_l``, ``speaker_embed.weight`` and ``speaker_vq.decoder.*`` -- what
+        ``SpeakerHipTrainer`` keeps in its arenas.  Everything else keeps ``grad = None`` in the reference."""
+        from . import train as T
+        return T.speaker_trainable_parameters(self)
 
     # ------------------------------------------------------------------ reference sub-APIs
     @torch.no_grad()

@@ -157,6 +157,15 @@ def _vq_blocks(P, net, h, heads, layers):
     return h
 
 
+def _instance_norm(x, eps=1e-5):
+    """F.instance_norm over the last dim of [B,C,n]; torch refuses a single frame (n = 1), where the definition still holds
+    (mean = x, biased variance 0: the output is zero and passes no gradient)"""
+    if x.shape[-1] > 1:
+        return F.instance_norm(x, eps=eps)
+    xm = x - x.mean(-1, keepdim=True)
+    return xm * torch.rsqrt(x.var(-1, unbiased=False, keepdim=True) + eps)
+
+
 def vq_decoder(P, pre, zq, heads, layers, pe, drop=None):
     """Differentiable TransformerDecoder of the listener VQ-VAE (reference code/models/stage1_BIWI.py:376-393): linear,
     Conv1d(k5, replicate) + LeakyReLU(0.2) + InstanceNorm over time, linear, + pe[batch row], ``layers`` pre-LN
@@ -166,7 +175,7 @@ def vq_decoder(P, pre, zq, heads, layers, pe, drop=None):
     c = pre + "decoder."
     h = F.linear(zq, P[c + "decoder_linear_embedding_pre.net.weight"], P[c + "decoder_linear_embedding_pre.net.bias"])
     x = F.conv1d(F.pad(h.transpose(1, 2), (2, 2), mode="replicate"), P[c + "expander.0.0.weight"], P[c + "expander.0.0.bias"])
-    h = F.instance_norm(F.leaky_relu(x, 0.2), eps=1e-5).transpose(1, 2)
+    h = _instance_norm(F.leaky_relu(x, 0.2)).transpose(1, 2)
     h = F.linear(h, P[c + "decoder_linear_embedding.net.weight"], P[c + "decoder_linear_embedding.net.bias"])
     h = h + pe[:B]
     if drop is not None:
@@ -363,6 +372,80 @@ def slm_loss(P, dims, vq_dims, v_speaker, v_listener, v_audio, mask, mask_speake
         out["l_cont_" + tag] = _masked_pairwise(pred, tgt, msk)
     out["nce"], out["c_acc"] = nce, c_acc
     return out["l_ce_s"] + out["l_ce_l"] + out["l_cont_s"] + out["l_cont_l"] + nce, out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# DIM-Speaker fine-tuning (reference code/seq2seq_pretrain.py:708-757) -- what code/finetune_s2s_pretrain.py trains with
+# x_engine_pt.train_epoch_biwi
+# ---------------------------------------------------------------------------------------------------------------------
+SPEAKER_TRAINABLE_PREFIXES = ("decoder_joint.", "speaker_vq.decoder.")
+SPEAKER_TRAINABLE_NAMES = ("patch_embed_dec_l", "speaker_embed.weight")
+
+
+def speaker_trainable_parameters(model):
+    """(name, parameter) of what ``SpeakerSLMFT.forward(mode='train')`` leaves a gradient on in the reference, in state-dict
+    order: the cross entropy reaches ``decoder_joint.*``, ``patch_embed_dec_l`` and ``speaker_embed.weight``; the EMOCA loss
+    reaches ``speaker_vq.decoder.*`` only (the arg-max cuts the graph).  Every other parameter keeps ``grad = None`` there, so
+    the reference's AdamW and its clip norm skip it."""
+    return [(n, p) for n, p in model.named_parameters()
+            if n.startswith(SPEAKER_TRAINABLE_PREFIXES) or n in SPEAKER_TRAINABLE_NAMES]
+
+
+def set_speaker_trainable(model, flag=True):
+    for _, p in speaker_trainable_parameters(model):
+        p.requires_grad_(flag)
+    return model
+
+
+def speaker_loss(P, dims, vq_dims, v_emoca, v_audio, mask, z, pe_s, speaker_ids=None, tokens=None):
+    """Differentiable ``SpeakerSLMFT.forward(mode='train')`` (reference :708-757): the PyTorch-autograd CHECKER of
+    ``SpeakerHipTrainer``.  P: {key: tensor} (parameters carry the graph); v_emoca [B,T,56]; v_audio [B,T,768]; mask [B,T] bool;
+    z [B,T]: the listener VQ-VAE's codes of v_emoca with -100 on padding (from the frozen VQ-VAE, no graph); pe_s: the speaker
+    VQ-VAE decoder's positional buffer; speaker_ids [B] long or None (a zero embedding row).  tokens [B,T-1]: code indices to
+    decode instead of this function's own arg-max (a checker that follows another implementation's choice at a near tie).
+    The codebook is frozen (no gradient through the lookup); the mean squared error runs over all B (T-1) 56 elements, padded
+    frames included, as the reference's does.  Returns (total = l_ce + l_emoca, {l_ce, l_emoca, logits, tokens, pred})."""
+    B, T = z.shape
+    patch = P["patch_embed_dec_l"].reshape(1, 1, -1)
+    if speaker_ids is None:
+        x_l = torch.zeros(B, T, patch.shape[-1], dtype=v_audio.dtype, device=v_audio.device)
+    else:
+        x_l = P["speaker_embed.weight"][speaker_ids.long()][:, None, :].expand(B, T, -1)
+    ctx = torch.cat([x_l + patch, v_audio], dim=-1)
+    logits = xt_decoder_logits(P, "decoder_joint.net.", z[:, :-1].clamp(min=0), ctx, mask, None, dims.dec_depth, dims.heads, pos_emb=True)
+    l_ce = F.cross_entropy(logits.reshape(-1, logits.shape[-1]), z[:, 1:].reshape(-1), ignore_index=-100)
+    tok = logits.detach().argmax(-1) if tokens is None else tokens.reshape(B, T - 1).long()
+    zq = P["speaker_vq.quantize.embedding.weight"].detach()[tok]
+    pred = vq_decoder(P, "speaker_vq.", zq, vq_dims.heads, vq_dims.layers, pe_s)
+    l_emoca = F.mse_loss(pred, v_emoca[:, 1:, :].to(pred.dtype))
+    return l_ce + l_emoca, {"l_ce": l_ce, "l_emoca": l_emoca, "logits": logits, "tokens": tok, "pred": pred}
+
+
+def speaker_context_adjoint(dctx, ids, rows, slices=8):
+    """Host restatement of the context adjoint of csrc/train_spk.hip in ITS summation order: dctx [B,T,C] (the first C columns of
+    the context gradient) -> (d patch_embed_dec_l [C], d speaker_embed.weight [rows,C]).  Per clip the frames are added in
+    ascending t inside ``slices`` time slices and the slices in ascending order; the patch gradient adds the clips in ascending b;
+    table row r adds the clips with ids[b] == r in ascending b (a gather per row: duplicated ids need no scatter), rows no clip
+    names stay zero, ids None leaves the whole table zero."""
+    B, T, C = dctx.shape
+    per = -(-T // slices)
+    clip = torch.zeros(B, C, dtype=dctx.dtype)
+    for b in range(B):
+        for s in range(slices):
+            part = torch.zeros(C, dtype=dctx.dtype)
+            for t in range(s * per, min(T, (s + 1) * per)):
+                part = part + dctx[b, t]
+            clip[b] = clip[b] + part
+    d_patch = torch.zeros(C, dtype=dctx.dtype)
+    for b in range(B):
+        d_patch = d_patch + clip[b]
+    d_embed = torch.zeros(rows, C, dtype=dctx.dtype)
+    if ids is not None:
+        for r in range(rows):
+            for b in range(B):
+                if int(ids[b]) == r:
+                    d_embed[r] = d_embed[r] + clip[b]
+    return d_patch, d_embed
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -554,3 +554,120 @@ class ConverterHipTrainer(HipTrainer):
         self.step()
         self.last = d
         return d["loss"], mesh
+
+
+class SpeakerHipTrainer(HipTrainer):
+    """The DIM-Speaker fine-tuning step on the HIP kernels: reference loop ``train_epoch_biwi`` (code/x_engine_pt.py:62-132) over
+    ``SpeakerSLMFT.forward(mode='train')`` (code/seq2seq_pretrain.py:708-757) as code/finetune_s2s_pretrain.py's speaker branch
+    drives it -- AdamW(lr 1e-5, torch's defaults otherwise), ``clip=1.0``, batch size 1.  ``total = l_ce + l_emoca``: the cross
+    entropy of the teacher-forced decoder over the listener VQ-VAE's codes of the EMOCA stream, and the mean squared error of the
+    decoded arg-max codes through the speaker VQ-VAE's decoder.  What trains is what that forward leaves a gradient on
+    (``SpeakerSLMFT.dimx_trainable_parameters()``): ``decoder_joint.*`` (positional table included), ``patch_embed_dec_l`` and
+    ``speaker_embed.weight`` through the cross entropy, ``speaker_vq.decoder.*`` through the EMOCA loss (the arg-max cuts the
+    graph in front of it).  ``speaker_embed.weight`` gets a dense gradient: rows no clip names get zeros, and AdamW still decays
+    them, as torch's does.  Forward and backward run in libdimx_hip.so (csrc/train.hip spk_run, csrc/train_spk.hip); the frozen
+    listener VQ-VAE encodes through the inference engine exactly as ``SpeakerSLMFT.forward`` does.  Same flat arenas, clip +
+    AdamW, optimiser-state import / export, ``sync_to_model()`` and ``all_reduce_grads()`` as HipTrainer;
+    ``dimx.train.speaker_loss`` (PyTorch autograd) is its checker (tests/test_gpu_train_speaker.py).
+
+    Reference behaviour kept, and deliberate differences:
+      * clipping: here the reference clips AFTER ``backward()`` (x_engine_pt.py:108-110), so its ``clip=1.0`` really clips: the
+        global norm runs over the whole arena, which is exactly the set of tensors that have a gradient in the reference;
+      * everything outside the arena (the three encoders, ``norm*``, ``W``, the LSTM head ``vertice_map_reverse*``,
+        ``vertice_mapping``, ``squasher``, the ``_2`` head, ``patch_embed_{s,l,dec_s}``, both VQ encoders and codebooks, the
+        listener VQ-VAE) keeps ``grad = None`` in the reference: AdamW skips it (weight decay included) and it comes back
+        untouched from ``sync_to_model()``.  The converter head only REPORTS ``d['l_cont_s']``; it adds nothing to ``total``;
+      * ``model.train()`` in the reference loop also flips the VQ-VAEs into train mode, so the ``Dropout(0.1)`` behind their
+        positional encodings fires during training -- an accident of calling ``.train()`` on the parent.  Here both VQ-VAEs run
+        in eval arithmetic;
+      * batch size: the reference's mouth indexing only type-checks at B = 1; here every mean runs over all B clips (equal at
+        B = 1);
+      * ``mouth_map`` is a constructor argument (default: the model's; the reference reads
+        ``../data/CodeTalker/BIWI/regions/lve.txt``).  Without a map ``d['l_cont_s']`` is 0 and the mesh head is not launched;
+      * the reference's ``evaluate_epoch_biwi`` passes ``v_speaker_emoca=None`` and fails inside ``forward_vq``; it is not
+        built (``SpeakerSLMFT.forward`` raises ``ValueError`` for None) and the driver never calls it."""
+
+    _MODEL_MAP = object()
+
+    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=1.0, mouth_map=_MODEL_MAP, device=None):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip=clip, device=device)
+        self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+        mm = getattr(model, "mouth_map", None) if mouth_map is SpeakerHipTrainer._MODEL_MAP else mouth_map
+        self.mouth_map = None if mm is None else [int(i) for i in mm]
+        if self.mouth_map is not None:
+            assert all(0 <= i < model.mesh_dim // 3 for i in self.mouth_map), "mouth_map holds vertex indices in [0, mesh_dim / 3)"
+        self.last_out = {}
+
+    def _arena_layout(self, h):
+        n = self.lib.dimx_train_spk_num_params(h)
+        if n <= 0:
+            L.check(n, "dimx_train_spk_num_params")
+        layout = []
+        for i in range(n):
+            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
+            L.check(self.lib.dimx_train_spk_param_info(h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)),
+                    "dimx_train_spk_param_info")
+            layout.append((name.value.decode(), int(off.value), int(numel.value)))
+        return int(self.lib.dimx_train_spk_total(h)), layout
+
+    def graph_stats(self):
+        raise L.DimxError("the DIM-Speaker step is launched kernel by kernel (no captured graph)")
+
+    def _mouth(self, pred, vertices, template):
+        """the reported mouth term of ``SpeakerSLMFT.forward``: mse over the map's vertices of the mesh head's output (no graph)"""
+        import torch.nn.functional as F
+        with torch.no_grad(), self.model.engine_pinned():
+            B, n, _ = pred.shape
+            templ = template.to(self.device, torch.float32).contiguous() if template is not None else None
+            mesh = self.model.engine(self.device).mesh_head(pred, templ)
+            idx = torch.as_tensor(self.mouth_map, device=self.device, dtype=torch.long)
+            tgt = vertices.to(self.device)[:, 1:, :].reshape(B, n, -1, 3)[:, :, idx, :]
+            return F.mse_loss(mesh.view(B, n, -1, 3)[:, :, idx, :], tgt.to(mesh.dtype))
+
+    def forward_backward(self, vertices, emoca, audio, mask, template, speaker_ids=None, z=None, return_logits=False):
+        """vertices [B,T,V], emoca [B,T,56], audio [B,T,768], mask [B,T] bool, template [B,V] or None, speaker_ids [B] or None ->
+        (total = l_ce + l_emoca, d with the reference's six keys) as device scalars; gradients in ``self.grads``.  z [B,T]: the
+        listener VQ-VAE's codes of ``emoca`` (-100 on padding; default: ``model.forward_vq``).  The step's code indices
+        [B*(T-1)] int32, decoded coefficients [B,T-1,56] and (``return_logits``) logits [B,T-1,512] are left in ``self.last_out``.
+        ``vertices`` / ``template`` only feed the reported mouth term and may be None without a ``mouth_map``."""
+        m = self.model
+        mask = mask.bool()
+        B, T = mask.shape
+        if z is None:
+            with torch.no_grad():
+                _, z = m.forward_vq(None, emoca.to(self.device), mask.to(self.device))
+        f = lambda t: t.detach().to(self.device, torch.float32).contiguous()
+        v_e, v_a = f(emoca), f(audio)
+        m8 = mask.to(self.device).to(torch.uint8).contiguous()
+        z32 = z.to(self.device).to(torch.int32).contiguous()
+        ids = speaker_ids.to(self.device).to(torch.int32).contiguous() if speaker_ids is not None else None
+        book, pe = f(m.speaker_vq.quantize.embedding.weight), f(m.speaker_vq.decoder.decoder_pos_embedding.pe)
+        need = int(self.lib.dimx_train_spk_workspace_bytes(self.eng.h, B, T))
+        if need == 0:
+            raise L.DimxError("dimx_train_spk_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
+        if need > self._ws_bytes:
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            self._ws_bytes = need
+        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
+        kw = dict(device=self.device)
+        logits = torch.empty(B, T - 1, 512, dtype=torch.float32, **kw) if return_logits else None
+        idx = torch.empty(B * (T - 1), dtype=torch.int32, **kw)
+        pred = torch.empty(B, T - 1, 56, dtype=torch.float32, **kw)
+        L.check(self.lib.dimx_train_spk_forward_backward(
+            self.eng.h, L.ptr(self.params), L.ptr(self.grads), L.ptr(v_e), L.ptr(v_a), L.ptr(m8), L.ptr(z32), L.ptr(ids), L.ptr(book),
+            L.ptr(pe), B, T, L.ptr(self._loss), L.ptr(logits), L.ptr(idx), L.ptr(pred), ws, self._ws.numel() - 256,
+            L.stream_ptr(self.device)), "dimx_train_spk_forward_backward")
+        out = self._loss.clone()
+        l_ce, l_emoca = out[0], out[2]
+        l_mouth = self._mouth(pred, vertices, template) if self.mouth_map is not None else 0
+        self.last_out = {"idx": idx, "pred": pred, "logits": logits}
+        d = {"l_ce_s": 0, "l_ce_l": l_ce, "l_cont_s": l_mouth, "l_cont_l": l_emoca, "nce": 0, "c_acc": 0}
+        return l_ce + l_emoca, d
+
+    def train_step(self, vertices, emoca, audio, mask, template, speaker_ids=None, z=None):
+        """one optimisation step of the reference loop's body; returns (total, d) like ``model(xv, xe, xa, mask, xt,
+        speaker_ids=...)`` there (its third value is ``self.last_out['pred']``)."""
+        total, d = self.forward_backward(vertices, emoca, audio, mask, template, speaker_ids=speaker_ids, z=z)
+        self.all_reduce_grads()
+        self.step()
+        return total, d

@@ -372,14 +372,17 @@ def _no_hip_step(model, what, log):
 def _hip_trainer_for(model, optimizer, device, log):
     """The HIP trainer that stands in for ``optimizer`` (a torch.optim.AdamW over this module's parameters), or None when the
     reference call cannot be mapped onto a HIP step (the reason is left in ``_hip_trainer_for.last_reason``; see _no_hip_step).
-    SLMFT -> HipTrainer, SLM -> SlmHipTrainer, the legacy ListenerGenerator -> LegacyHipTrainer (dimx.x_engine.train_epoch).
+    SLMFT -> HipTrainer, SLM -> SlmHipTrainer, the legacy ListenerGenerator -> LegacyHipTrainer (dimx.x_engine.train_epoch),
+    SpeakerSLMFT -> SpeakerHipTrainer (train_epoch_biwi).
     Cached on the module per optimizer object: the AdamW moments and the step count live in the trainer's flat arenas between
     epochs and are exported into ``optimizer.state`` at the end of every epoch (``optimizer.state_dict()`` stays meaningful)."""
     from . import train_hip
     inner = getattr(model, "module", model)
     why = None
-    cls = {"slmft": train_hip.HipTrainer, "slm": train_hip.SlmHipTrainer, "legacy": train_hip.LegacyHipTrainer}.get(
-        getattr(inner, "engine_variant", None))
+    cls = {"slmft": train_hip.HipTrainer, "slm": train_hip.SlmHipTrainer, "legacy": train_hip.LegacyHipTrainer,
+           "speaker": train_hip.SpeakerHipTrainer}.get(getattr(inner, "engine_variant", None))
+    if cls is train_hip.SpeakerHipTrainer and not hasattr(inner, "speaker_embed"):
+        cls = None      # EmocaConverter shares the engine variant; its own loop is ConverterHipTrainer's (examples/train_converter.py)
     if cls is None or not hasattr(inner, "engine"):
         why = "no HIP training step for %s" % type(inner).__name__
     elif type(optimizer) is not torch.optim.AdamW:
@@ -526,6 +529,174 @@ def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, pri
         if i % print_freq == 0:
             log("Epoch %d Batch %d:\tLoss %.4f\t" % (epoch, i, float(np.mean(losses))) +
                 "\t".join("%s %.4f" % (k, d[k] / print_freq) for k in d))
+            d = {k: 0.0 for k in d}
+            losses = []
+    return float(np.mean(all_losses)) if all_losses else float("nan")
+
+
+_BIWI_KEYS = ("l_ce_s", "l_ce_l", "l_cont_s", "l_cont_l", "nce", "c_acc")
+_BIWI_LABELS = ("CE_s", "CE_l", "Cont_s", "Cont_l", "NCE", "C_acc")
+
+
+def _biwi_line(epoch, i, loss, d):
+    """the reference loop's progress line (code/x_engine_pt.py:124)"""
+    return "Epoch %d Batch %d:\tLoss %.4f\t" % (epoch, i, loss) + "\t".join("%s %.4f" % (lab, d[k]) for lab, k in zip(_BIWI_LABELS, _BIWI_KEYS))
+
+
+def _biwi_batch(batch, device):
+    xa, xv, xt, xe, fnames = batch
+    xa, xv, xt, xe = (t.to(device, non_blocking=True) for t in (xa, xv, xt, xe))
+    speaker_ids = torch.tensor([BIWI_SPEAKER_IDS[f.split("_")[0]] for f in fnames], dtype=torch.long).to(device)
+    mask = torch.ones((xa.shape[0], xa.shape[1]), dtype=torch.bool, device=device)
+    return xa, xv, xt, xe, speaker_ids, mask
+
+
+def _train_epoch_biwi_hip(model, loader, trainer, device, scheduler, print_freq, epoch, log, clip=None, optimizer=None):
+    """train_epoch_biwi on the hand-written HIP step (dimx.train_hip.SpeakerHipTrainer); same hand-over of hyper-parameters,
+    optimiser state and trained weights as _train_epoch_hip."""
+    model.train()
+    changed = trainer.refresh_from_model_if_changed()
+    if changed:
+        log("train_epoch_biwi: the module's parameters changed since the HIP trainer last synchronised (load_state_dict?): arena reloaded from the module")
+    if optimizer is not None and type(optimizer) is torch.optim.AdamW and (changed or trainer.optimizer_state_changed(optimizer)):
+        trainer.import_optimizer_state(optimizer)
+        log("train_epoch_biwi: the optimizer's state changed since the HIP trainer last exported it: moments and step count re-imported")
+    if clip is not None:
+        trainer.clip = float(clip)
+    if scheduler is not None and optimizer is None:
+        optimizer = getattr(scheduler, "optimizer", None)
+        if optimizer is None or not hasattr(optimizer, "param_groups"):
+            raise L.DimxError("train_epoch_biwi: a scheduler needs a torch optimizer whose param_groups carry the learning rate; "
+                              "build it on torch.optim.AdamW and pass that optimizer, or set trainer.lr yourself")
+    if ddist.world_size() > 1 and hasattr(loader, "__len__"):
+        ddist.assert_same_batch_count(len(loader), device)
+    _set_epoch(loader, epoch)
+    losses, parts, all_losses = [], {k: [] for k in _BIWI_KEYS}, []
+    for i, batch in enumerate(loader):
+        xa, xv, xt, xe, speaker_ids, mask = _biwi_batch(batch, device)
+        if optimizer is not None:
+            _adopt_hyperparameters(trainer, optimizer)
+            optimizer._opt_called = True      # the trainer steps in its place (silences torch's scheduler-before-optimizer warning)
+        loss, d_step = trainer.train_step(xv, xe, xa, mask, xt, speaker_ids=speaker_ids)
+        if scheduler is not None:
+            scheduler.step()
+        losses.append(loss)                      # device scalars: no host synchronisation per batch
+        for k in _BIWI_KEYS:
+            if torch.is_tensor(d_step[k]):
+                parts[k].append(d_step[k])
+        if i % print_freq == 0:
+            vals = [float(v) for v in torch.stack(losses).cpu()]
+            all_losses += vals
+            # the reference divides its running sums by print_freq, whatever the number of batches behind them
+            log(_biwi_line(epoch, i, float(np.mean(vals)), {k: (float(torch.stack(v).sum()) / print_freq if v else 0.0) for k, v in parts.items()}))
+            losses, parts = [], {k: [] for k in _BIWI_KEYS}
+    if losses:
+        all_losses += [float(v) for v in torch.stack(losses).cpu()]
+    trainer.sync_to_model()
+    if optimizer is not None and type(optimizer) is torch.optim.AdamW:
+        trainer.export_optimizer_state(optimizer)
+    return float(np.mean(all_losses)) if all_losses else float("nan")
+
+
+def _speaker_codes(model, P, xe, mask):
+    """[B,T] codes of the frozen listener VQ-VAE for the autograd route: the HIP engine's on a GPU (what SpeakerSLMFT.forward
+    uses), the torch restatement of the same encoder on the CPU (each clip alone, as the reference encodes them)"""
+    from . import train as T
+    if xe.is_cuda:
+        return model.forward_vq(None, xe, mask)[1]
+    B, Tn = mask.shape
+    z = torch.full((B, Tn), -100, dtype=torch.long)
+    Pd = {k: v.detach() for k, v in P.items() if k.startswith("listener_vq.")}
+    for b in range(B):
+        n = int(mask[b].sum())
+        z[b, :n] = T.vq_loss(Pd, xe[b:b + 1, :n].float(), pre="listener_vq.", heads=model.vq_dims.heads, layers=model.vq_dims.layers)[5]
+    return z
+
+
+def train_epoch_biwi(model, loader, optimizer, device, scheduler=None, clip=0.0, print_freq=2000, epoch=0, log=print, backward="auto"):
+    """reference code/x_engine_pt.py:62-132: one pass of the DIM-Speaker fine-tuning over a loader that yields ``(xa [B,T,768]
+    audio, xv [B,T,V] vertices, xt [B,V] template, xe [B,T,56] EMOCA, file names)``; the mask is all ones and the speaker ids
+    come from the file-name prefix (``BIWI_SPEAKER_IDS``).  Per batch: zero_grad / ``model(xv, xe, xa, mask, xt,
+    speaker_ids=...)`` / backward / clip (after backward, so it really clips) / step, and the reference's progress line.
+
+    ``optimizer`` is a ``torch.optim.AdamW`` over the model's parameters (the reference's call: a ``SpeakerHipTrainer`` then
+    stands in for it exactly as ``train_epoch`` arranges it for SLMFT) or a ``SpeakerHipTrainer``.  ``backward="auto"`` /
+    ``"hip"`` RAISE when a model of this package cannot be stepped by the HIP kernels; ``backward="autograd"`` runs the
+    PyTorch-autograd restatement ``dimx.train.speaker_loss`` (the checker of the HIP step) on purpose.  Deliberate differences
+    from the reference are listed in ``SpeakerHipTrainer``'s docstring; the reference's ``evaluate_epoch_biwi`` is not built."""
+    from .train_hip import HipTrainer
+    if isinstance(optimizer, HipTrainer):
+        return _train_epoch_biwi_hip(model, loader, optimizer, device, scheduler, print_freq, epoch, log, clip=clip)
+    if backward not in ("auto", "hip", "autograd"):
+        raise ValueError("backward must be 'auto', 'hip' or 'autograd'")
+    inner = getattr(model, "module", model)
+    if backward != "autograd":
+        tr = _hip_trainer_for(model, optimizer, device, log) if hasattr(inner, "speaker_embed") else None
+        if tr is not None:
+            return _train_epoch_biwi_hip(model, loader, tr, device, scheduler, print_freq, epoch, log, clip=clip, optimizer=optimizer)
+        if not hasattr(inner, "speaker_embed"):
+            _hip_trainer_for.last_reason = "no HIP fine-tuning step for %s (train_epoch_biwi steps a SpeakerSLMFT)" % type(inner).__name__
+        if backward == "hip":
+            raise L.DimxError("train_epoch_biwi(backward='hip'): %s" % _hip_trainer_for.last_reason)
+        _no_hip_step(model, "train_epoch_biwi", log)     # raises for a dimx model: the autograd route is an explicit opt-in
+    from . import train as T
+    import torch.nn.functional as F
+    _set_epoch(loader, epoch)
+    model.train()
+    if not _is_dimx_model(model):                        # any other nn.Module: the reference's loop as it stands, on torch
+        losses = []
+        for i, batch in enumerate(loader):
+            xa, xv, xt, xe, speaker_ids, mask = _biwi_batch(batch, device)
+            optimizer.zero_grad()
+            loss, d_step, _ = model(xv, xe, xa, mask, xt, speaker_ids=speaker_ids)
+            loss.mean().backward()
+            if clip > 0:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+            optimizer.step()
+            if scheduler is not None:
+                scheduler.step()
+            losses.append(float(loss.mean()))
+            if i % print_freq == 0:
+                log(_biwi_line(epoch, i, float(np.mean(losses)), {k: (float(torch.as_tensor(d_step.get(k, 0)).float().mean()) / print_freq) for k in _BIWI_KEYS}))
+        return float(np.mean(losses)) if losses else float("nan")
+    if not hasattr(inner, "speaker_embed"):
+        raise L.DimxError("train_epoch_biwi(backward='autograd'): dimx.train.speaker_loss restates SpeakerSLMFT, not %s" % type(inner).__name__)
+    named = inner.dimx_trainable_parameters()
+    for _, p in named:
+        p.requires_grad_(True)
+    params = [p for _, p in named]
+    d = {k: 0.0 for k in _BIWI_KEYS}
+    losses, all_losses = [], []
+    for i, batch in enumerate(loader):
+        xa, xv, xt, xe, speaker_ids, mask = _biwi_batch(batch, device)
+        P = dict(inner.state_dict(keep_vars=True))
+        with torch.no_grad():
+            z = _speaker_codes(inner, P, xe, mask).to(xe.device)
+        optimizer.zero_grad()
+        with torch.enable_grad():
+            loss, o = T.speaker_loss(P, inner.s2s, inner.vq_dims, xe.float(), xa.float(), mask, z, P["speaker_vq.decoder.decoder_pos_embedding.pe"],
+                                     speaker_ids=speaker_ids)
+            loss.backward()
+        T.all_reduce_grads(params)
+        if clip > 0:
+            torch.nn.utils.clip_grad_norm_(params, clip)
+        optimizer.step()
+        if scheduler is not None:
+            scheduler.step()
+        l_mouth = 0.0
+        if inner.mouth_map is not None:     # the reported mouth term: the converter head on the decoded coefficients, no graph
+            with torch.no_grad():
+                mesh = T.converter_head({k: v.detach() for k, v in P.items()}, o["pred"].detach()) + xt[:, None, :]
+                B, n = mesh.shape[:2]
+                idx = torch.as_tensor(inner.mouth_map, device=mesh.device, dtype=torch.long)
+                l_mouth = float(F.mse_loss(mesh.view(B, n, -1, 3)[:, :, idx, :], xv[:, 1:].reshape(B, n, -1, 3)[:, :, idx, :].to(mesh.dtype)))
+        d["l_ce_l"] += float(o["l_ce"].detach())
+        d["l_cont_l"] += float(o["l_emoca"].detach())
+        d["l_cont_s"] += l_mouth
+        losses.append(float(loss.detach()))
+        all_losses.append(losses[-1])
+        if i % print_freq == 0:
+            log(_biwi_line(epoch, i, float(np.mean(losses)), {k: d[k] / print_freq for k in d}))
             d = {k: 0.0 for k in d}
             losses = []
     return float(np.mean(all_losses)) if all_losses else float("nan")

@@ -6,6 +6,15 @@ The training step -- forward, backward, clip, AdamW -- runs on the hand-written 
 `--backward autograd` selects the PyTorch-autograd restatement that serves as its checker.
 
     python examples/finetune_s2s_pretrain.py [--epochs 2] [--clips 64] [--batch 4] [--max-len 120] [--backward hip|autograd]
+
+``--mode speaker --synthetic`` is the reference's SPEAKER branch (DIM-Speaker): ``SpeakerSLMFT`` under ``train_epoch_biwi`` at
+batch size 1 (AdamW lr 1e-5, clip 1.0) on the HIP step ``dimx.train_hip.SpeakerHipTrainer``; every tenth epoch
+``evaluate_test_epoch_biwi(beam_size=2)`` and the best model by mean squared vertex error saved as
+``best_model_biwi_finetune1.pt`` (what examples/test_biwi.py loads).  The BIWI data set is not available: the clips are the
+synthetic BIWI-shaped loader of examples/test_biwi.py.  ``--init`` names a checkpoint to start from (the reference's
+``gamma`` / ``beta`` LayerNorm keys are renamed to ``weight`` / ``bias``, the load is non-strict).
+
+    python examples/finetune_s2s_pretrain.py --mode speaker --synthetic [--epochs 20] [--clips 4] [--frames 60] [--mesh-dim 70110]
 """
 import argparse
 import os
@@ -22,8 +31,53 @@ from dimx.seq2seq_pretrain import SLMFT  # noqa: E402
 from dimx.x_engine_pt import evaluate_finetune_epoch, train_epoch  # noqa: E402
 
 
+def speaker_main(args):
+    """the reference's speaker branch on the synthetic BIWI-shaped loader"""
+    import numpy as np
+    from dimx.seq2seq_pretrain import SpeakerSLMFT
+    from dimx.x_engine_pt import evaluate_test_epoch_biwi, train_epoch_biwi
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_biwi import synthetic_biwi_loader
+    if not args.synthetic:
+        sys.exit("the BIWI loader (reference code/dataset/biwi.py) needs the data set and s3prl, which are not available: "
+                 "run with --synthetic")
+    device = torch.device("cuda:0")
+    torch.cuda.set_device(device)
+    model = SpeakerSLMFT(mesh_dim=args.mesh_dim).to(device)
+    if args.init:
+        sd = torch.load(args.init, map_location="cpu")
+        sd = {k.replace(".gamma", ".weight").replace(".beta", ".bias"): v for k, v in sd.items()}
+        missing, unexpected = model.load_state_dict(sd, strict=False)
+        print("loaded %s: %d keys missing, %d unexpected" % (args.init, len(missing), len(unexpected)))
+    # the reference's own lines: train_epoch_biwi maps this AdamW onto the HIP fine-tuning step
+    optimizer = torch.optim.AdamW(model.parameters(), lr=1e-5)
+    clips = 4 if args.clips == 64 else args.clips
+    train_loader = synthetic_biwi_loader(clips, args.frames, args.mesh_dim)
+    test_loader = synthetic_biwi_loader(max(1, clips // 2), args.frames, args.mesh_dim, seed=12)
+    out = "best_model_biwi_finetune1.pt" if args.out == "best_vico_causal.pt" else args.out
+    best = float("inf")
+    for epoch in range(args.epochs):
+        loss = train_epoch_biwi(model, train_loader, optimizer, device, scheduler=None, clip=1.0, print_freq=100, epoch=epoch,
+                                backward="auto" if args.backward == "hip" else args.backward)
+        if epoch % 10 == 0:
+            y_true, y_pred, _, _ = evaluate_test_epoch_biwi(model, test_loader, device, beam_size=2)
+            lve = float(np.mean([np.mean((p - t) ** 2) for p, t in zip(y_pred, y_true)]))
+            print("epoch %d: mean loss %.4f, mean squared error of the predicted coefficients %.6f (SYNTHETIC clips: not BIWI results)" % (
+                epoch, loss, lve))
+            if lve < best:
+                best = lve
+                torch.save(model.state_dict(), out)
+                print("saved %s" % out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", default="listener", choices=["listener", "speaker"],
+                    help="listener: SLMFT under train_epoch (the default, as before); speaker: SpeakerSLMFT under train_epoch_biwi")
+    ap.add_argument("--synthetic", action="store_true", help="speaker mode: synthetic BIWI-shaped clips (the only loader available)")
+    ap.add_argument("--frames", type=int, default=60, help="speaker mode: frames per synthetic clip")
+    ap.add_argument("--mesh-dim", type=int, default=70110, help="speaker mode: 3 x vertices of the mesh")
+    ap.add_argument("--init", default=None, help="speaker mode: checkpoint to start from (non-strict load)")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--clips", type=int, default=64)
     ap.add_argument("--batch", type=int, default=4)
@@ -32,6 +86,8 @@ def main():
     ap.add_argument("--backward", default="hip", choices=["hip", "autograd"],
                     help="hip: forward + backward + clip + AdamW on csrc/train*.hip; autograd: the PyTorch restatement (checker)")
     args = ap.parse_args()
+    if args.mode == "speaker":
+        return speaker_main(args)
     rank, world, local = ddist.init_from_env()
     device = torch.device("cuda:{}".format(local))
     torch.cuda.set_device(device)

@@ -347,6 +347,35 @@ size_t dimx_train_conv_workspace_bytes(dimx_handle h, int B, int T);
 int dimx_train_conv_forward_backward(dimx_handle h, const float* params, float* grads, const float* motion, const float* templ,
                                      const float* target, const float* vert_w, int n_mouth, int B, int T, int flags, float* loss_out,
                                      float* mesh_out, void* ws, size_t ws_bytes, void* stream);
+/* ---- DIM-Speaker fine-tuning step: reference SpeakerSLMFT.forward(mode='train') (code/seq2seq_pretrain.py:708-757) under the
+ * loop train_epoch_biwi (code/x_engine_pt.py:62-132; AdamW lr 1e-5, clip 1.0, batch size 1).  The handle must be a speaker handle
+ * (variant 2 with mesh_dim > 0; DIMX_ERR_STATE otherwise) whose weights were loaded with speaker_embed.weight among them.  What
+ * trains is what that forward leaves a gradient on, in flat f32 arenas (tensors 16-byte aligned) as for the other steps:
+ * patch_embed_dec_l, decoder_joint.* (its absolute positional table included), speaker_vq.decoder.* and speaker_embed.weight
+ * [rows, 384] (dense: rows no clip names get a zero gradient and are still decayed by AdamW).  The encoders, the norms, the
+ * converter head and the frozen halves of the VQ-VAEs receive no gradient in the reference and are not in the arenas. */
+int dimx_train_spk_num_params(dimx_handle h);
+int64_t dimx_train_spk_total(dimx_handle h);   /* floats in an arena */
+int dimx_train_spk_param_info(dimx_handle h, int i, const char** name, int64_t* offset, int64_t* numel);
+size_t dimx_train_spk_workspace_bytes(dimx_handle h, int B, int T);
+/* One forward + backward pass.  v_emoca [B,T,56], v_audio [B,T,768] f32; mask [B,T] uint8 (1 = valid frame: the cross-attention's
+ * key mask); z [B,T] int32: the LISTENER VQ-VAE's codes of v_emoca, -100 on padding (dimx_vq_encode); speaker_ids [B] int32 on the
+ * device or NULL (NULL: a zero embedding row, and speaker_embed.weight's gradient is zero); codebook_s [512,128] and pe_s [>= B
+ * rows of 384]: the speaker VQ-VAE's frozen codebook and its decoder's positional buffer.
+ *   ctx = cat(speaker_embed[ids] + patch_embed_dec_l, v_audio);  logits = decoder_joint(z[:, :-1], ctx, mask) (no key masking of
+ *   the self-attention);  l_ce = cross entropy against z[:, 1:] (ignore -100);  idx = argmax(logits) (first index on ties);
+ *   pred = speaker_vq.decode(codebook_s[idx]);  l_emoca = mean((pred - v_emoca[:, 1:])^2) over all B (T-1) 56 elements, padded
+ *   frames included;  grads (overwritten) = d(l_ce + l_emoca): l_emoca reaches speaker_vq.decoder.* only, the arg-max cuts the rest.
+ * loss_out: 4 device floats {l_ce, 1 / valid targets, l_emoca, 1 / elements}.  Optional outputs: logits_out [B,T-1,512], idx_out
+ * [B (T-1)] int32, pred_out [B,T-1,56] (16-byte aligned).  The mesh head is not part of the call (it reports a metric and takes no
+ * gradient): run dimx_mesh_head or dimx_train_conv_forward_backward(grads = NULL) on pred_out.  A speaker id outside [0, rows) is
+ * DIMX_ERR_ARG: the ids are read back and checked on the host before the first launch (one stream synchronisation when ids are
+ * given).  Launched kernel by kernel on `stream`, no captured graph.  Deterministic: no float atomics, every sum in a fixed order
+ * (the embedding gradient adds its clips in ascending b per table row), a rerun is bit-identical. */
+int dimx_train_spk_forward_backward(dimx_handle h, const float* params, float* grads, const float* v_emoca, const float* v_audio,
+                                    const uint8_t* mask, const int32_t* z, const int32_t* speaker_ids, const float* codebook_s,
+                                    const float* pe_s, int B, int T, float* loss_out, float* logits_out, int32_t* idx_out, float* pred_out,
+                                    void* ws, size_t ws_bytes, void* stream);
 /* The adjoint of one bidirectional LSTM layer alone (unit parity): x [B,T,In], the four weight sets as dimx_op_lstm_layer takes
  * them, dy [B,T,2H] -> dx [B,T,In] (optional), dw_ih[d] [4H,In], dw_hh[d] [4H,H], db[d] [4H] (= d bias_ih = d bias_hh).  f32
  * only.  It runs the training forward first.  Allocates its scratch and synchronises the stream. */
