@@ -565,3 +565,68 @@ def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None,
                                        S, float(scale), nsplit, L.stream_ptr(q.device)),
             "dimx_op_decode_attn_ex")
     return out
+
+
+_FD_WS = {}     # device index -> uint8 workspace of op_fd_select (grown on demand, never shrunk)
+
+
+def _fd_workspace(device, need):
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    ws = _FD_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _FD_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def op_fd_select(y_true, y_pred, lens, cols=(0, None), want_best=True):
+    """Best-of-S selection by Frechet distance (dimx_op_fd_select, csrc/fd_select.hip): y_true [B, L, W] f32, y_pred [B, S, L, W]
+    f32 on one GPU, lens[j] = valid frames of clip j, cols = (c0, c1) the columns that enter the distance (None = the row's
+    end) -> (fd [B, S] f64, win [B] int32, ok [B] uint8, best [B, L, W] f32 or None).  The clip / sample / frame strides are taken
+    from the tensors (views such as ``tgt[lo:hi, 1:]`` are passed as they are); only a feature stride other than 1 is copied.
+    Asynchronous on the current stream.  CPU tensors raise: there is no CPU fallback."""
+    if not (torch.is_tensor(y_true) and torch.is_tensor(y_pred) and y_true.is_cuda and y_pred.is_cuda):
+        raise L.DimxError("op_fd_select runs on the GPU only: y_true / y_pred must be CUDA tensors (no CPU fallback)")
+    if y_true.dim() != 3 or y_pred.dim() != 4 or y_pred.shape[0] != y_true.shape[0] or y_pred.shape[2] != y_true.shape[1] \
+            or y_pred.shape[3] != y_true.shape[2] or y_pred.device != y_true.device:
+        raise L.DimxError("op_fd_select: y_true [B, L, W] and y_pred [B, S, L, W] expected, got %s and %s" % (tuple(y_true.shape),
+                                                                                                           tuple(y_pred.shape)))
+    lib = L.load()
+    dev = y_pred.device
+    B, S, Ln, W = y_pred.shape
+    y_true = y_true if y_true.dtype == torch.float32 else y_true.float()
+    y_pred = y_pred if y_pred.dtype == torch.float32 else y_pred.float()
+    if W > 1 and y_true.stride(2) != 1:
+        y_true = y_true.contiguous()
+    if W > 1 and y_pred.stride(3) != 1:
+        y_pred = y_pred.contiguous()
+    c0 = int(cols[0])
+    F = (W if cols[1] is None else int(cols[1])) - c0
+    if torch.is_tensor(lens):
+        lens_d = lens.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_d = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(dev)
+    if lens_d.numel() != B:
+        raise L.DimxError("op_fd_select: %d lens for %d clips" % (lens_d.numel(), B))
+    fd = torch.empty(B, S, dtype=torch.float64, device=dev)
+    win = torch.empty(B, dtype=torch.int32, device=dev)
+    ok = torch.empty(B, dtype=torch.uint8, device=dev)
+    best = torch.empty(B, Ln, W, dtype=torch.float32, device=dev) if want_best else None
+    need = int(lib.dimx_op_fd_select_ws_bytes(B, S, F))
+    ws = _fd_workspace(dev, max(need, 8))
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_fd_select(ctypes.c_void_p(y_true.data_ptr()), y_true.stride(0), y_true.stride(1),
+                                      ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1), y_pred.stride(2),
+                                      L.ptr(lens_d), B, S, Ln, W, c0, F, L.ptr(fd), L.ptr(win), L.ptr(ok), L.ptr(best),
+                                      ctypes.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(dev)), "dimx_op_fd_select")
+    return fd, win, ok, best
+
+
+def fd_select_sweeps(device, B, S, F):
+    """Jacobi sweeps of the last op_fd_select(B, S, F) call on ``device``, read from its workspace: (target factorisations [B],
+    (clip, try) problems [B, S]) as int32 tensors (include/dimx.h: the last B + B*S int32 of the workspace)."""
+    lib = L.load()
+    need = int(lib.dimx_op_fd_select_ws_bytes(B, S, F))
+    device = torch.device(device)
+    ws = _FD_WS[device.index if device.index is not None else torch.cuda.current_device()]
+    sw = ws[need - 4 * (B + B * S):need].view(torch.int32)
+    return sw[:B].clone(), sw[B:].reshape(B, S).clone()

@@ -153,6 +153,10 @@ SIGNATURES = {
                                     c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "dimx_op_gemm_ln": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                 c_void_p, c_void_p]),
+    "dimx_op_fd_select_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dimx_op_fd_select": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_void_p,
+                                  c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
 }

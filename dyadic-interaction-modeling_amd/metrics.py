@@ -1,6 +1,7 @@
 """Host-side metrics of the evaluation step (numpy/scipy, float64), restating
 reference code/metrics/eval_utils.py:6-91.  They consume the per-clip arrays the engine returns after the
-(all-gathered) generation; they are not on the GPU path (excluded from clips/s)."""
+(all-gathered) generation; they are not on the GPU path (excluded from clips/s).  ``frechet_distances_hip`` is the exception: the
+best-of-N selection's distances from the HIP library."""
 import numpy as np
 from scipy import linalg
 
@@ -62,6 +63,15 @@ def frechet_distances_torch(y_true, y_pred, lens):
     diff = mu1[:, None] - mu2
     tr = lambda t: torch.diagonal(t, dim1=-2, dim2=-1).sum(-1)
     return (diff * diff).sum(-1) + tr(s1)[:, None] + tr(s2) - 2.0 * tr_sqrt
+
+
+def frechet_distances_hip(y_true, y_pred, lens, cols=(0, None)):
+    """The same distances from the project's own kernel (dimx_op_fd_select, csrc/fd_select.hip; float64 throughout, Jacobi
+    eigenvalues in LDS, padded frames never read): y_true [B, L, W], y_pred [B, S, L, W] on a GPU, lens[j] = valid frames of
+    clip j, cols = (c0, c1) the columns that enter the distance -> fd [B, S] float64 on that GPU.  CPU tensors raise
+    lib.DimxError: there is no CPU fallback (frechet_distances_torch and clip_fd above are the host forms)."""
+    from .engine import op_fd_select
+    return op_fd_select(y_true, y_pred, lens, cols=cols, want_best=False)[0]
 
 
 def calculate_variance(activations):

@@ -135,6 +135,20 @@ def _select_device(y_true, y_preds, lens, world, device, total=None):
     return best
 
 
+def _select_hip(y_true, y_preds, lens, world, device, total=None):
+    """fd_backend="hip": distances, winner and gather in the HIP library (dimx.engine.op_fd_select, csrc/fd_select.hip) on the
+    stream the generation ran on; only the winners' frames and the ok flags cross to the host.  A clip without a finite distance
+    keeps None, as in _select_device."""
+    from .engine import op_fd_select
+    _, _, ok, best = op_fd_select(y_true, y_preds, lens)
+    ok = ok.cpu().tolist()
+    chosen = best.cpu().numpy()
+    best = [chosen[j][:lens[j]].copy() if ok[j] else None for j in range(len(lens))]
+    if world > 1:
+        best = _gather_ragged(best, len(lens), y_preds.shape[2], y_preds.shape[3], device, total)
+    return best
+
+
 def _select(pending, skip_degenerate, world, device):
     """Best of the tries per clip, in the reference's order of evaluation (try-major, clip-minor; a candidate replaces the
     current best only when its distance is strictly smaller; the first ValueError in that order propagates unless
@@ -178,8 +192,15 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     1.4 ms per (clip, try) of single-threaded scipy (it does not scale over threads): 3.6 s for 256 clips x 10 tries against
     0.7 s of generation.  ``fd_backend="device"`` computes the same quantity for the whole batch in torch float64 on the GPU
     (dimx.metrics.frechet_distances_torch: eigenvalues instead of scipy's sqrtm, so the last digits differ and rank-deficient
-    clips do not raise) and brings only the winners to the host."""
-    assert fd_backend in ("reference", "device")
+    clips do not raise) and brings only the winners to the host.  ``fd_backend="hip"`` follows the same path with the distances,
+    the winner and the gather of the winning sequences all in the project's own kernels (dimx.engine.op_fd_select, csrc/fd_select.hip;
+    GPU only: a CPU device raises lib.DimxError)."""
+    assert fd_backend in ("reference", "device", "hip")
+    if fd_backend == "hip" and torch.device(device).type != "cuda":
+        raise L.DimxError("evaluate_test_epoch(fd_backend='hip') runs on a ROCm GPU only (device %s): there is no CPU fallback; "
+                          "fd_backend='reference' and 'device' run there" % (device,))
+    on_device = fd_backend in ("device", "hip")
+    select_on_device = _select_hip if fd_backend == "hip" else _select_device
     y_trues_all, y_preds_all, x_all, data_ids_all = [], [], [], []
     model.eval()
     batched = batched_samples and beam_size in BATCHED_SAMPLE_COUNTS
@@ -209,16 +230,16 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
                     _, _, y_preds = model(sl[0], sl[1], sl[2], sl[3], mode="val", n_samples=beam_size, **kw)
                 else:
                     y_preds = torch.stack([model(sl[0], sl[1], sl[2], sl[3], mode="val", **kw)[2] for _ in range(beam_size)], 1)
-                if fd_backend == "device":      # [nl, S, T-1, 56] stays on the device; only the winners travel
+                if on_device:                   # [nl, S, T-1, 56] stays on the device; only the winners travel
                     if pending is not None:
                         y_preds_all.extend(_select(pending, skip_degenerate, world, device))
                         pending = None
-                    y_preds_all.extend(_select_device(tgt[lo:hi, 1:], y_preds, [src_len[lo + j] - 1 for j in range(nl)], world,
-                                                      device, B))
+                    y_preds_all.extend(select_on_device(tgt[lo:hi, 1:], y_preds, [src_len[lo + j] - 1 for j in range(nl)], world,
+                                                        device, B))
                     continue
                 yp_all = y_preds.cpu().numpy()
                 samples = [yp_all[:, s_i] for s_i in range(beam_size)]
-            elif fd_backend == "device":
+            elif on_device:
                 y_preds_all.extend(_gather_ragged([], 0, tgt.shape[1] - 1, tgt.shape[2], device, B) if world > 1 else [])
                 continue
             # this batch's distances go to the worker threads; the PREVIOUS batch's are collected now, after this batch's

@@ -530,6 +530,24 @@ int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk,
                         int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
                         const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
                         int call_index, float scale, void* scratch, void* prof, void* stream);
+/* Best-of-S selection by Frechet distance, the selection step of the test-time protocol (csrc/fd_select.hip; reference
+ * code/x_engine_pt.py:255-270 around code/metrics/eval_utils.py:6-46).  All pointers are device memory.
+ *   y_true f32 [B, L, .]: clip j, frame t starts at y_true + j*yt_clip_stride + t*yt_frame_stride (elements; feature stride 1)
+ *   y_pred f32 [B, S, L, W]: clip j, try s, frame t starts at y_pred + j*yp_clip_stride + s*yp_sample_stride + t*yp_frame_stride
+ *   lens int32 [B]: valid frames per clip (clamped to 0..L); frames t >= lens[j] are never read
+ *   columns [c0, c0 + F) of the rows enter the distance, 1 <= F <= 64, c0 + F <= W
+ *   fd f64 [B, S] = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2), mean and unbiased covariance over the valid frames, float64
+ *       throughout; NaN for every try of a clip with fewer than 2 valid frames
+ *   win int32 [B]: first minimum of the row, NaN counting as +inf;  ok uint8 [B]: 0 when no try of the clip has a finite distance
+ *   best f32 [B, L, W] or NULL: the winning try's full rows, zero for t >= lens[j] and for clips with ok = 0
+ *   workspace: dimx_op_fd_select_ws_bytes(B, S, F) bytes, 8-byte aligned.  After the call its last (B + B*S) int32 hold the Jacobi
+ *       sweeps of each clip's target factorisation and of each (clip, try) (diagnostic; the loop is bounded at 30).
+ * Asynchronous on `stream`: no allocation, no host synchronisation, no atomics (bit-reproducible).  DIMX_ERR_ARG for F outside
+ * 1..64, a window that leaves the row, a null pointer (best excepted), a short or misaligned workspace; nothing is enqueued then. */
+size_t dimx_op_fd_select_ws_bytes(int B, int S, int F);
+int dimx_op_fd_select(const float* y_true, long yt_clip_stride, long yt_frame_stride, const float* y_pred, long yp_clip_stride,
+                      long yp_sample_stride, long yp_frame_stride, const int32_t* lens, int B, int S, int L, int W, int c0, int F,
+                      double* fd, int32_t* win, uint8_t* ok, float* best, void* workspace, size_t workspace_bytes, void* stream);
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
