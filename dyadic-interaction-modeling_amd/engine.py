@@ -630,3 +630,115 @@ def fd_select_sweeps(device, B, S, F):
     ws = _FD_WS[device.index if device.index is not None else torch.cuda.current_device()]
     sw = ws[need - 4 * (B + B * S):need].view(torch.int32)
     return sw[:B].clone(), sw[B:].reshape(B, S).clone()
+
+
+_MM_WS = {}      # device index -> uint8 workspace of op_mesh_metrics (grown on demand, never shrunk)
+_MM_MAPS = {}    # (device index, n_vert, sorted map bytes) -> MeshMap; keyed on content
+_MM_LENS = {}    # device index -> the host lens array of the last call (kept until the next call has replaced it)
+
+
+class MeshMap:
+    """A validated vertex map on a device (mesh_map): the sorted int32 copy the kernel reads, its length, and the mesh it was checked
+    against.  op_mesh_metrics takes one in place of a host sequence and then skips validation, sort and cache lookup."""
+    __slots__ = ("data", "n", "n_vert", "device_key")
+
+    def __init__(self, data, n, n_vert, device_key):
+        self.data, self.n, self.n_vert, self.device_key = data, n, n_vert, device_key
+
+
+def _mm_device_key(device):
+    device = torch.device(device)
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+def mesh_map(seq, n_vert, device, what="map"):
+    """Validate a vertex map on the host (every index in [0, n_vert), DimxError otherwise) and return its MeshMap on ``device``: the
+    SORTED copy is uploaded once per (device, n_vert, content) and cached."""
+    if isinstance(seq, MeshMap):
+        if seq.n_vert != n_vert or seq.device_key != _mm_device_key(device):
+            raise L.DimxError("op_mesh_metrics: %s was prepared for %d vertices on device %d" % (what, seq.n_vert, seq.device_key))
+        return seq
+    if torch.is_tensor(seq):
+        seq = seq.detach().cpu().numpy()
+    arr = np.asarray(seq if seq is not None else [])
+    if arr.size and not np.issubdtype(arr.dtype, np.integer):
+        raise L.DimxError("op_mesh_metrics: %s holds non-integer entries" % what)
+    arr = arr.astype(np.int64).reshape(-1)
+    if arr.size and (arr.min() < 0 or arr.max() >= n_vert):
+        raise L.DimxError("op_mesh_metrics: %s holds an index outside [0, %d) (min %d, max %d)" % (what, n_vert, arr.min(), arr.max()))
+    srt = np.sort(arr).astype(np.int32)
+    key = _mm_device_key(device)
+    ck = (key, int(n_vert), srt.tobytes())
+    hit = _MM_MAPS.get(ck)
+    if hit is None:
+        if len(_MM_MAPS) >= 16:      # a handful of maps per process is the use; never grow without bound
+            _MM_MAPS.pop(next(iter(_MM_MAPS)))
+        hit = _MM_MAPS[ck] = MeshMap(torch.from_numpy(srt).to(device) if srt.size else None, int(srt.size), int(n_vert), key)
+    return hit
+
+
+def op_mesh_metrics(y_true, y_pred, lens, template, mouth_map, upper_map, want_frames=False, return_status=False):
+    """Lip Vertex Error / upper-Face Dynamics Deviation partials (dimx_op_mesh_metrics, csrc/mesh_metrics.hip): y_true [B, Lt, 3*Nv],
+    y_pred [B, Lp, 3*Nv] f32 on one GPU (Lt, Lp >= max(lens); only the first lens[b] frames of clip b are read), lens[b] = valid
+    frames (host sequence; a CUDA tensor is read back first), template [B, 3*Nv] or [3*Nv] or None (zero), mouth_map / upper_map
+    host sequences of vertex indices (or their MeshMap from ``mesh_map``) -> (clip [B, 4] f64 = {sum_t max_m d, frames, sigma_gt, sigma_pred}, frame_max [B, L] f64 or
+    None, with L = min(Lt, Lp)).  Clip and frame strides are taken from the tensors (``v_speaker[:, 1:]`` is passed as it is); only
+    an element stride other than 1 is copied.  The maps are validated here, before any launch, and uploaded once per content as
+    sorted copies.  Asynchronous on the current stream.  CPU tensors raise: there is no CPU fallback.  ``return_status=True`` appends
+    the call's device status word (int32 [1]: 0; 1 = the kernel met an index outside the mesh, which the host check makes
+    unreachable)."""
+    if not (torch.is_tensor(y_true) and torch.is_tensor(y_pred) and y_true.is_cuda and y_pred.is_cuda):
+        raise L.DimxError("op_mesh_metrics runs on the GPU only: y_true / y_pred must be CUDA tensors (no CPU fallback)")
+    if y_true.dim() != 3 or y_pred.dim() != 3 or y_pred.shape[0] != y_true.shape[0] or y_pred.shape[2] != y_true.shape[2] \
+            or y_pred.device != y_true.device:
+        raise L.DimxError("op_mesh_metrics: y_true [B, L, 3*Nv] and y_pred [B, L', 3*Nv] on one device expected, got %s and %s"
+                          % (tuple(y_true.shape), tuple(y_pred.shape)))
+    B, V = int(y_true.shape[0]), int(y_true.shape[2])
+    if V % 3 != 0 or V < 3:
+        raise L.DimxError("op_mesh_metrics: rows of %d floats are not xyz triples" % V)
+    n_vert = V // 3
+    Ln = int(min(y_true.shape[1], y_pred.shape[1]))
+    lib = L.load()
+    dev = y_pred.device
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    y_true = y_true if y_true.dtype == torch.float32 else y_true.float()
+    y_pred = y_pred if y_pred.dtype == torch.float32 else y_pred.float()
+    if y_true.stride(2) != 1:
+        y_true = y_true.contiguous()
+    if y_pred.stride(2) != 1:
+        y_pred = y_pred.contiguous()
+    templ, templ_cs = None, 0
+    if template is not None:
+        if not (torch.is_tensor(template) and template.is_cuda and template.device == dev):
+            raise L.DimxError("op_mesh_metrics: template must be a CUDA tensor on the meshes' device")
+        templ = template if template.dtype == torch.float32 else template.float()
+        if templ.dim() == 1:
+            templ = templ[None].expand(B, V)
+        if tuple(templ.shape) != (B, V):
+            raise L.DimxError("op_mesh_metrics: template %s for meshes [%d, ., %d]" % (tuple(template.shape), B, V))
+        if templ.stride(1) != 1:
+            templ = templ.contiguous()
+        templ_cs = templ.stride(0)
+    lens_h = [int(n) for n in (lens.tolist() if torch.is_tensor(lens) else lens)]
+    if len(lens_h) != B:
+        raise L.DimxError("op_mesh_metrics: %d lens for %d clips" % (len(lens_h), B))
+    if B < 1 or Ln < 1:
+        raise L.DimxError("op_mesh_metrics: B=%d L=%d must be positive" % (B, Ln))
+    mouth, upper = mesh_map(mouth_map, n_vert, dev, "mouth_map"), mesh_map(upper_map, n_vert, dev, "upper_map")
+    mouth_d, n_mouth, upper_d, n_upper = mouth.data, mouth.n, upper.data, upper.n
+    lens_c = (ctypes.c_int32 * B)(*lens_h)
+    clip = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    frames = torch.empty(B, Ln, dtype=torch.float64, device=dev) if want_frames else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    need = int(lib.dimx_op_mesh_metrics_ws_bytes(B, Ln, n_mouth, n_upper))
+    ws = _MM_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _MM_WS[key] = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_mesh_metrics(ctypes.c_void_p(y_true.data_ptr()), y_true.stride(0), y_true.stride(1),
+                                         ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1),
+                                         None if templ is None else ctypes.c_void_p(templ.data_ptr()), templ_cs, lens_c, B, Ln, n_vert,
+                                         L.ptr(mouth_d), n_mouth, L.ptr(upper_d), n_upper, L.ptr(clip), L.ptr(frames), L.ptr(status),
+                                         ctypes.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(dev)), "dimx_op_mesh_metrics")
+    _MM_LENS[key] = lens_c
+    return (clip, frames, status) if return_status else (clip, frames)

@@ -101,3 +101,45 @@ def summarize(y_trues, y_preds):
         out[name] = {"fd": float(np.mean(fds)), "mse": float(np.mean(mses)), "var": float(np.mean(vars_)),
                      "sts": float(np.mean(stss))}
     return out
+
+
+class BiwiMeshMetrics:
+    """Device-side accumulator of the DIM-Speaker mesh metrics (reference print_biwi_metrics, code/mymetrics.py:122-182) over the
+    batches of an evaluation epoch: ``update`` runs dimx_op_mesh_metrics (csrc/mesh_metrics.hip, float64) on the meshes where they
+    lie and adds into float64 state on that GPU -- no mesh crosses to the host and nothing is synchronised; ``result`` does the one
+    readback.  CPU tensors raise lib.DimxError (mymetrics.compute_biwi_metrics is the host form)."""
+
+    def __init__(self, mouth_map, upper_map):
+        self.mouth_map = [int(i) for i in mouth_map]
+        self.upper_map = [int(i) for i in upper_map]
+        self._maps = {}        # (device, row width) -> the two MeshMaps
+        self._state = None     # f64 [5]: sum of frame maxima, frames, sum of (sigma_gt - sigma_pred), clips, status
+
+    def update(self, y_true, y_pred, lens, template):
+        """y_true [B, Lt, 3*Nv], y_pred [B, Lp, 3*Nv] on one GPU, lens[b] valid frames (host sequence), template [B, 3*Nv] or None."""
+        import torch
+        from .engine import mesh_map, op_mesh_metrics
+        n_vert, key = int(y_pred.shape[-1]) // 3, (str(getattr(y_pred, "device", None)), int(y_pred.shape[-1]))
+        if getattr(y_pred, "is_cuda", False) and key not in self._maps:      # validated and uploaded once per (device, mesh)
+            self._maps[key] = (mesh_map(self.mouth_map, n_vert, y_pred.device, "mouth_map"),
+                               mesh_map(self.upper_map, n_vert, y_pred.device, "upper_map"))
+        mouth, upper = self._maps.get(key, (self.mouth_map, self.upper_map))
+        clip, _, status = op_mesh_metrics(y_true, y_pred, lens, template, mouth, upper, return_status=True)
+        add = torch.cat([clip[:, 0].sum(0, keepdim=True), clip[:, 1].sum(0, keepdim=True), (clip[:, 2] - clip[:, 3]).sum(0, keepdim=True),
+                         torch.full((1,), float(clip.shape[0]), dtype=torch.float64, device=clip.device), status.to(torch.float64)])
+        if self._state is None:
+            self._state = add
+        else:
+            if self._state.device != add.device:
+                raise ValueError("BiwiMeshMetrics: updates from %s and %s" % (self._state.device, add.device))
+            self._state = torch.cat([self._state[:4] + add[:4], torch.maximum(self._state[4:], add[4:])])
+        return self
+
+    def result(self):
+        """-> (lve, fdd) as Python floats: frames weigh equally in lve, clips in fdd."""
+        if self._state is None:
+            raise ValueError("BiwiMeshMetrics.result() before any update()")
+        s_max, frames, s_diff, clips, status = self._state.tolist()
+        if status != 0:
+            raise RuntimeError("BiwiMeshMetrics: a map index outside the mesh reached the kernel and was skipped")
+        return s_max / frames, s_diff / clips

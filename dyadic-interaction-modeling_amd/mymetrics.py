@@ -6,7 +6,13 @@ speaker motion ``x[i]`` ``[len_i-1, >=56]`` (numpy).  Host-side numpy/scipy/skle
 the per-clip double loop of the reference's ``sts`` is vectorised (same value).  Both functions also RETURN what
 they print (the reference returns only ``(fid_pose, fid_exp)`` from ``print_metrics``; that pair stays the return
 value, the full dict is available through ``compute_metrics``).
+
+``print_biwi_metrics`` (reference ``code/mymetrics.py:122-182``, what ``test_biwi.py`` and ``finetune_s2s_pretrain.py`` import) is
+restated at the end: Lip Vertex Error and upper-Face Dynamics Deviation of vertex clips, in the inputs' own dtype.
 """
+import os
+import pickle
+
 import numpy as np
 
 from .metrics import calculate_activation_statistics, calculate_frechet_distance, sts
@@ -100,3 +106,93 @@ def print_metrics_full(y_true, y_pred, x):
     print("mse: ", m["mse"])
     print("var: ", *m["var"])
     return m
+
+
+# ---------------------------------------------------------------- BIWI mesh metrics (reference code/mymetrics.py:122-182)
+BIWI_TEMPLATES_PATH = "../data/BIWI_data/templates.pkl"
+BIWI_REGION_PATH = "../data/CodeTalker/BIWI/regions/"
+
+
+def read_region_map(path):
+    """``lve.txt`` / ``fdd.txt``: vertex indices separated by ``", "`` (reference :128-134)."""
+    with open(path) as f:
+        return [int(i) for i in f.read().split(", ")]
+
+
+def read_biwi_templates(path):
+    """``templates.pkl``: {subject: [Nv, 3] array}, a Python-2 pickle read with ``encoding='latin1'`` (reference :125-126)."""
+    with open(path, "rb") as fin:
+        return pickle.load(fin, encoding="latin1")
+
+
+def _clip_template(templates, i, file_names):
+    if templates is None:
+        return None
+    if isinstance(templates, dict):
+        return np.asarray(templates[file_names[i].split("_")[0]])
+    return np.asarray(templates[i])
+
+
+def compute_biwi_metrics(y_true, y_pred, file_names, templates, mouth_map, upper_map):
+    """The values ``print_biwi_metrics`` prints, vectorised, in the dtype numpy gives the inputs (float32 clips stay float32, as in
+    the reference; nothing is upcast).  ``y_true[i]`` ``[Tg_i, 3*Nv]`` (or ``[Tg_i, Nv, 3]``), ``y_pred[i]`` with at least ``Tg_i``
+    frames, of which the first ``Tg_i`` count; ``templates`` a dict keyed on the subject ``file_names[i].split("_")[0]`` (the
+    reference's), a per-clip sequence, or None (zero template); the maps are vertex indices, duplicates counting as numpy fancy
+    indexing counts them.  Nv comes from the data (the reference hard-codes 23370).
+
+        lve = mean over all frames of all clips of max_m |gt - pred|^2
+        fdd = mean over clips of sigma_gt - sigma_pred,  sigma_x = mean_u std_t |x - template|^2   (population std)
+
+    Returns a dict: ``lve``, ``fdd``, ``fdd_scale`` = mean over clips of (sigma_gt + sigma_pred) (what an error of fdd is relative
+    to: fdd itself is a difference and may be near 0), and the per-clip arrays ``frame_max`` (list of [Tg_i]), ``frames``,
+    ``sigma_gt``, ``sigma_pred``."""
+    mouth = np.asarray(mouth_map, dtype=np.int64).reshape(-1)
+    upper = np.asarray(upper_map, dtype=np.int64).reshape(-1)
+    frame_max, frames, sig_gt, sig_pred, diffs = [], [], [], [], []
+    for i in range(len(y_true)):
+        gt = np.asarray(y_true[i])
+        gt = gt.reshape(gt.shape[0], -1, 3)
+        nv = gt.shape[1]
+        pred = np.asarray(y_pred[i])
+        pred = pred.reshape(pred.shape[0], -1, 3)
+        if pred.shape[0] < gt.shape[0] or pred.shape[1] != nv:
+            raise ValueError("clip %d: prediction %s against ground truth %s (at least as many frames and the same vertices are needed)"
+                             % (i, pred.shape, gt.shape))
+        for name, mp in (("mouth_map", mouth), ("upper_map", upper)):
+            if mp.size and (mp.min() < 0 or mp.max() >= nv):
+                raise ValueError("%s holds an index outside [0, %d)" % (name, nv))
+        pred = pred[:gt.shape[0]]
+        t = _clip_template(templates, i, file_names)
+        sig = []
+        for x in (gt, pred):
+            xu = x[:, upper, :]
+            motion = xu if t is None else xu - t.reshape(1, nv, 3)[:, upper, :]
+            s = np.sum(np.square(motion), axis=2)                    # [T, n_upper]
+            sig.append(np.mean(np.std(s, axis=0)) if upper.size else s.dtype.type(0))
+        sig_gt.append(sig[0])
+        sig_pred.append(sig[1])
+        diffs.append(sig[0] - sig[1])
+        d = np.sum(np.square(gt[:, mouth, :] - pred[:, mouth, :]), axis=2)   # [T, n_mouth]
+        frame_max.append(np.max(d, axis=1) if mouth.size else np.zeros(gt.shape[0], d.dtype))
+        frames.append(gt.shape[0])
+    lve = np.mean(np.concatenate(frame_max))
+    fdd = sum(diffs) / len(diffs)
+    scale = sum(a + b for a, b in zip(sig_gt, sig_pred)) / len(diffs)
+    return {"lve": lve, "fdd": fdd, "fdd_scale": scale, "frame_max": frame_max, "frames": np.asarray(frames),
+            "sigma_gt": np.asarray(sig_gt), "sigma_pred": np.asarray(sig_pred)}
+
+
+def print_biwi_metrics(y_true, y_pred, file_names, templates=None, mouth_map=None, upper_map=None,
+                       templates_path=BIWI_TEMPLATES_PATH, region_path=BIWI_REGION_PATH):
+    """reference :122-182: prints ``Lip Vertex Error`` and ``FDD`` and returns ``(lve, fdd)``.  ``templates`` / ``mouth_map`` /
+    ``upper_map`` left None are read from the reference's files (``templates.pkl``, ``lve.txt``, ``fdd.txt``)."""
+    if templates is None:
+        templates = read_biwi_templates(templates_path)
+    if mouth_map is None:
+        mouth_map = read_region_map(os.path.join(region_path, "lve.txt"))
+    if upper_map is None:
+        upper_map = read_region_map(os.path.join(region_path, "fdd.txt"))
+    m = compute_biwi_metrics(y_true, y_pred, file_names, templates, mouth_map, upper_map)
+    print('Lip Vertex Error: {:.4e}'.format(m["lve"]))
+    print('FDD: {:.4e}'.format(m["fdd"]))
+    return m["lve"], m["fdd"]

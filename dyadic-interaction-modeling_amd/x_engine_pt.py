@@ -295,6 +295,60 @@ def evaluate_test_epoch_biwi(model, loader, device, beam_size=10):
     return y_trues_all, y_preds_all, x_all, data_ids_all
 
 
+MESH_METRIC_BACKENDS = ("hip", "reference")
+
+
+def evaluate_mesh_epoch(mesh_fn, loader, mouth_map, upper_map, backend="hip"):
+    """Lip Vertex Error and upper-Face Dynamics Deviation (reference print_biwi_metrics, code/mymetrics.py:122-182) of whatever
+    produces meshes: ``mesh_fn(batch) -> (y_true [B,Lt,3*Nv], y_pred [B,Lp,3*Nv], lens, template [B,3*Nv] or None)`` on a GPU, the
+    first ``lens[b]`` frames of clip b counting.  ``backend="hip"``: dimx.metrics.BiwiMeshMetrics -- the meshes stay on the GPU,
+    float64, one readback at the end.  ``backend="reference"``: every mesh is copied to the host and
+    dimx.mymetrics.compute_biwi_metrics runs on float64 copies of the f32 values -- what the operator is defined as; the slow
+    check.  Any other value raises ValueError.
+    Returns ``(lve, fdd)`` as floats."""
+    if backend not in MESH_METRIC_BACKENDS:
+        raise ValueError("backend=%r: one of %s" % (backend, ", ".join(MESH_METRIC_BACKENDS)))
+    if backend == "hip":
+        from .metrics import BiwiMeshMetrics
+        acc = BiwiMeshMetrics(mouth_map, upper_map)
+        for batch in loader:
+            acc.update(*mesh_fn(batch))
+        return acc.result()
+    from .mymetrics import compute_biwi_metrics
+    gts, preds, templs = [], [], []
+    for batch in loader:
+        y_true, y_pred, lens, template = mesh_fn(batch)
+        for j, n in enumerate(lens):
+            gts.append(y_true[j, :int(n)].cpu().double().numpy())
+            preds.append(y_pred[j, :int(n)].cpu().double().numpy())
+            templs.append(None if template is None else template[j].cpu().double().numpy())
+    if all(t is None for t in templs):
+        templs = None
+    m = compute_biwi_metrics(gts, preds, None, templs, mouth_map, upper_map)
+    return float(m["lve"]), float(m["fdd"])
+
+
+def evaluate_mesh_epoch_biwi(model, loader, device, mouth_map, upper_map, backend="hip"):
+    """The mesh metrics of a ``SpeakerSLMFT`` over the BIWI batches ``evaluate_test_epoch_biwi`` takes (``(xa, xv, xt, xe, ids)``):
+    one teacher-forced ``forward(..., mode="train", return_mesh=True)`` per batch (the model is deterministic: no beam), the mesh
+    [B,T-1,V] against ``xv[:, 1:]`` (a view, not a copy) with the template ``xt`` -> ``(lve, fdd)``; backends as
+    ``evaluate_mesh_epoch``."""
+    if backend not in MESH_METRIC_BACKENDS:
+        raise ValueError("backend=%r: one of %s" % (backend, ", ".join(MESH_METRIC_BACKENDS)))
+    model.eval()
+
+    def mesh_fn(batch):
+        xa, xv, xt, xe, data_ids = batch
+        xa, xv, xt, xe = xa.to(device), xv.to(device), xt.to(device), xe.to(device)
+        speaker_ids = torch.tensor([BIWI_SPEAKER_IDS[f.split("_")[0]] for f in data_ids]).long().to(device)
+        mask = torch.ones((xa.shape[0], xa.shape[1]), dtype=torch.bool).to(device)
+        mesh = model(xv, xe, xa, mask, xt, mode="train", speaker_ids=speaker_ids, return_mesh=True)[-1]
+        return xv[:, 1:], mesh, [mesh.shape[1]] * mesh.shape[0], xt
+
+    with torch.no_grad():
+        return evaluate_mesh_epoch(mesh_fn, loader, mouth_map, upper_map, backend=backend)
+
+
 last_eval_report = {}
 
 

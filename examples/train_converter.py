@@ -7,10 +7,14 @@ BIWI-shaped loader of examples/test_biwi.py.
 
     python examples/train_converter.py --synthetic [--epochs 2] [--clips 4] [--frames 60] [--mesh-dim 70110] [--bf16]
                                        [--safe] [--mouth-map FILE] [--clip 0.0] [--out best_converter.pt]
+                                       [--mesh-metrics [--upper-map FILE]]
 
 ``--mouth-map FILE``: comma-separated vertex indices (the reference's ``regions/lve.txt``); without it the synthetic run takes
 every 5th vertex.  ``--clip``: 0 by default -- the reference passes 1.0 but clips before ``backward()``, i.e. nothing
-(see ConverterHipTrainer)."""
+(see ConverterHipTrainer).  ``--mesh-metrics`` (off by default; without it the output is unchanged) adds one line per epoch: the
+validation Lip Vertex Error and FDD of the reference's ``print_biwi_metrics``, from the meshes the validation pass leaves on the
+GPU (``dimx.x_engine_pt.evaluate_mesh_epoch``); ``--upper-map FILE`` is the reference's ``regions/fdd.txt``, without it every 3rd
+vertex of the upper half of the index range (synthetic)."""
 import argparse
 import os
 import sys
@@ -46,23 +50,38 @@ def train_epoch(trainer, loader, device, mouth_map=None, clip=0.0, epoch=0, flag
     return float(np.mean(losses))
 
 
-def evaluate_epoch(trainer, loader, device, mouth_map=None, flags=0):
+def evaluate_epoch(trainer, loader, device, mouth_map=None, flags=0, upper_map=None):
+    """mean validation loss; with an ``upper_map`` also ``(lve, fdd)`` of the same meshes (-> (loss, (lve, fdd)))"""
     losses = []
-    for batch in loader:
+
+    def mesh_fn(batch):
         xv, xt, xe, _ = batch
-        d, _ = trainer.evaluate(xv.to(device), xt.to(device), xe.to(device), mouth_map=mouth_map, flags=flags)
+        xv, xt = xv.to(device), xt.to(device)
+        d, mesh = trainer.evaluate(xv, xt, xe.to(device), mouth_map=mouth_map, flags=flags)
         losses.append(float(d["loss"]))
-    return float(np.mean(losses))
+        return xv, mesh, [xv.shape[1]] * xv.shape[0], xt
+
+    if upper_map is None:
+        for batch in loader:
+            mesh_fn(batch)
+        return float(np.mean(losses))
+    from dimx.x_engine_pt import evaluate_mesh_epoch
+    mesh = evaluate_mesh_epoch(mesh_fn, loader, mouth_map, upper_map, backend="hip")
+    return float(np.mean(losses)), mesh
 
 
-def fit(trainer, model, train_loader, val_loader, device, num_epochs, out_path, mouth_map=None, clip=0.0, flags=0):
+def fit(trainer, model, train_loader, val_loader, device, num_epochs, out_path, mouth_map=None, clip=0.0, flags=0, upper_map=None):
     """the reference's epoch loop; returns the best validation loss"""
     best = 10000
     print(f'training for {num_epochs} epochs')
     for epoch in range(num_epochs):
         train_epoch(trainer, train_loader, device, mouth_map=mouth_map, clip=clip, epoch=epoch, flags=flags)
-        val_loss = evaluate_epoch(trainer, val_loader, device, mouth_map=mouth_map, flags=flags)
+        val_loss = evaluate_epoch(trainer, val_loader, device, mouth_map=mouth_map, flags=flags, upper_map=upper_map)
+        if upper_map is not None:
+            val_loss, (lve, fdd) = val_loss
         print(f'Epoch {epoch} val loss: {val_loss}')
+        if upper_map is not None:
+            print('Epoch {} val Lip Vertex Error: {:.4e} FDD: {:.4e}'.format(epoch, lve, fdd))
         if val_loss < best:
             best = val_loss
             trainer.sync_to_model()
@@ -83,6 +102,8 @@ def main(argv=None):
     ap.add_argument("--clip", type=float, default=0.0)
     ap.add_argument("--lr", type=float, default=1e-5)
     ap.add_argument("--out", default="best_converter.pt")
+    ap.add_argument("--mesh-metrics", action="store_true", help="print the validation LVE / FDD (dimx_op_mesh_metrics) per epoch")
+    ap.add_argument("--upper-map", default=None, help="file of comma-separated upper-face vertex indices (regions/fdd.txt)")
     args = ap.parse_args(argv)
     if not args.synthetic:
         sys.exit("the BIWI loader (reference code/dataset/biwi.py) needs the data set, which is not available: run with --synthetic")
@@ -100,13 +121,17 @@ def main(argv=None):
         mouth_map = read_mouth_map(args.mouth_map)
     else:
         mouth_map = list(range(0, args.mesh_dim // 3, 5))
+    upper_map = None
+    if args.mesh_metrics:
+        n_vert = args.mesh_dim // 3
+        upper_map = read_mouth_map(args.upper_map) if args.upper_map else list(range(n_vert // 2, n_vert, 3))
     trainer = ConverterHipTrainer(model, lr=args.lr, clip=args.clip)
 
     # batch_size=1, as the reference trains
     train_loader = converter_batches(synthetic_biwi_loader(args.clips, args.frames, args.mesh_dim))
     val_loader = train_loader
     best = fit(trainer, model, train_loader, val_loader, device, args.epochs, args.out, mouth_map=mouth_map, clip=args.clip,
-               flags=1 if args.safe else 0)
+               flags=1 if args.safe else 0, upper_map=upper_map)
     print("best val loss %g -> %s (SYNTHETIC data: not BIWI results)" % (best, args.out))
 
 

@@ -548,6 +548,33 @@ size_t dimx_op_fd_select_ws_bytes(int B, int S, int F);
 int dimx_op_fd_select(const float* y_true, long yt_clip_stride, long yt_frame_stride, const float* y_pred, long yp_clip_stride,
                       long yp_sample_stride, long yp_frame_stride, const int32_t* lens, int B, int S, int L, int W, int c0, int F,
                       double* fd, int32_t* win, uint8_t* ok, float* best, void* workspace, size_t workspace_bytes, void* stream);
+/* The DIM-Speaker mesh metrics, Lip Vertex Error and upper-Face Dynamics Deviation (csrc/mesh_metrics.hip; reference
+ * print_biwi_metrics, code/mymetrics.py:122-182), as the float64 value of the reference's formulas on f32 meshes.
+ *   y_true / y_pred f32: clip b, frame t is a row of 3*n_vert floats (xyz per vertex, element stride 1) starting at
+ *       y + b*clip_stride + t*frame_stride (elements, taken as long: views such as v_speaker[:, 1:] are passed as they are and a
+ *       buffer may exceed 2^32 bytes).  A row needs 4-byte alignment only.
+ *   templ f32 [B, 3*n_vert] (row b at templ + b*templ_clip_stride) or NULL = the zero template
+ *   lens int32 [B] in HOST memory: valid frames per clip, 1..L.  They are checked here and copied into the workspace on `stream`
+ *       (a pageable array is staged before the call returns).  Frames t >= lens[b] are never read.
+ *   mouth int32 [n_mouth], upper int32 [n_upper] in device memory: vertex indices, in any order, duplicates count.  The result
+ *       does not depend on the order beyond float64 rounding (the Python layer uploads sorted copies: neighbouring lanes then read
+ *       neighbouring vertices).  An index outside [0, n_vert) is skipped and sets *status; n_mouth = 0 / n_upper = 0 skips that
+ *       half and leaves its outputs 0.
+ *   clip_out f64 [B, 4] = {sum_t max_m d(b,t,m), lens[b], sigma_gt(b), sigma_pred(b)} with d = |gt - pred|^2 of a vertex,
+ *       s_x = |x - templ|^2, sigma_x = mean_u std_t s_x (population standard deviation, two-pass per chunk of 8 frames and Chan's
+ *       merge over the chunks: no E[s^2] - E[s]^2).  LVE = sum_b clip_out[b][0] / sum_b clip_out[b][1], FDD = mean_b
+ *       (clip_out[b][2] - clip_out[b][3]).
+ *   frame_max f64 [B, L] or NULL: max_m d per valid frame, 0 for t >= lens[b]
+ *   status int32, one device word: 0, or 1 when an index outside [0, n_vert) was met
+ *   workspace: dimx_op_mesh_metrics_ws_bytes(B, L, n_mouth, n_upper) bytes, 8-byte aligned.
+ * Asynchronous on `stream`: three launches, no allocation, no host synchronisation, no atomics (bit-reproducible).  DIMX_ERR_ARG
+ * for B, L or n_vert < 1, a lens[b] outside 1..L, a null operand (templ and frame_max excepted), a short or misaligned workspace;
+ * nothing is enqueued then. */
+size_t dimx_op_mesh_metrics_ws_bytes(int B, int L, int n_mouth, int n_upper);
+int dimx_op_mesh_metrics(const float* y_true, long yt_clip_stride, long yt_frame_stride, const float* y_pred, long yp_clip_stride,
+                         long yp_frame_stride, const float* templ, long templ_clip_stride, const int32_t* lens, int B, int L, int n_vert,
+                         const int32_t* mouth, int n_mouth, const int32_t* upper, int n_upper, double* clip_out, double* frame_max,
+                         int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
