@@ -54,89 +54,85 @@ struct TrainPlan {
     long total = 0;
 };
 
-// every tensor the reference's optimiser would update with a non-zero gradient on this path, in state-dict order of the
-// stack (deterministic: the caller's arenas are laid out by it)
-int build_plan(dimx_handle h, TrainPlan& p) {
-    const dimx_dims& d = h->d;
-    // the optional tensors of another x-transformers release (model.hip: optional_key) are on the inference path only: the step
-    // below has no gradient for them, so it refuses them instead of training around them
-    for (const auto& kv : h->host) {
-        const std::string& nm = kv.first;
-        const bool opt = nm.size() > 16 && (nm.compare(nm.size() - 15, 15, "project_in.bias") == 0 || nm.compare(nm.size() - 14, 14, "to_logits.bias") == 0);
-        DIMX_REQUIRE(!opt, DIMX_ERR_STATE, "train: %s is loaded; the training step implements the bias-free project_in / to_logits only", nm.c_str());
-    }
-    // a tensor the engine itself does not hold (the id-conditioning tables of the legacy generator are training-only): fixed shape
-    auto add_free = [&](const std::string& name, int rows, int cols) -> int {
-        PInfo pi{name, p.total, (long)rows * cols, rows, cols};
+// ---------------------------------------------------------------------------------------------------------------- plan builder
+// Lays a step's tensors out in its flat arenas in the order they are added (deterministic: the caller's arenas follow it).  `tag`
+// is the step's prefix in error messages.  Name lists that several steps share are written here once.
+struct PlanBuilder {
+    TrainPlan& p;
+    dimx_handle h;
+    const char* tag;
+    const dimx_dims& d;
+    PlanBuilder(TrainPlan& p_, dimx_handle h_, const char* tag_) : p(p_), h(h_), tag(tag_), d(h_->d) {}
+
+    // held = false: a tensor the engine itself does not hold (training-only tables), laid out at the shape given
+    int add(const std::string& name, int rows, int cols, bool held = true) {
+        const long n = (long)rows * cols;
+        if (held) {
+            auto it = h->host.find(name);
+            DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "%s: weight %s was not loaded", tag, name.c_str());
+            long have = 1;
+            for (auto sz : it->second.shape) have *= sz;
+            DIMX_REQUIRE(have == n, DIMX_ERR_WEIGHT, "%s: %s has %ld elements, expected %d x %d", tag, name.c_str(), have, rows, cols);
+        }
         p.index[name] = (int)p.params.size();
-        p.params.push_back(pi);
-        p.total += ((long)rows * cols + 3) / 4 * 4;
-        return DIMX_OK;
-    };
-    auto add = [&](const std::string& name, int rows, int cols) -> int {
-        auto it = h->host.find(name);
-        DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "train: weight %s was not loaded", name.c_str());
-        long n = 1;
-        for (auto s : it->second.shape) n *= s;
-        DIMX_REQUIRE(n == (long)rows * cols, DIMX_ERR_WEIGHT, "train: %s has %ld elements, expected %d x %d", name.c_str(), n, rows, cols);
-        PInfo pi{name, p.total, n, rows, cols};
-        p.index[name] = (int)p.params.size();
-        p.params.push_back(pi);
+        p.params.push_back(PInfo{name, p.total, n, rows, cols});
         p.total += (n + 3) / 4 * 4;  // 16-byte aligned tensors
         return DIMX_OK;
-    };
-    const int inner = d.heads * d.dim_head;
-    if (d.variant == 1) {
-        // legacy ListenerGenerator (code/seq2seq.py:165-176): the generator, the listener VQ-VAE's DECODER and the id-conditioning
-        // layers train; both VQ encoders / codebooks are frozen
-        const std::string e = "generator.encoder.", dn = "generator.decoder.net.", c = "listener_vq.decoder.";
-        const int DDl = d.dim + d.dim_a, H = d.vq_hidden, I = d.vq_inter;
-        DIMX_TRY(add(e + "project_in.weight", d.dim, d.spk_face_quan_num * d.vq_zdim));
+    }
+    // the optional tensors of another x-transformers release (model.hip: optional_key) are on the inference path only: the steps
+    // have no gradient for them, so they refuse them instead of training around them
+    int refuse_optional_biases() {
+        for (const auto& kv : h->host) {
+            const std::string& nm = kv.first;
+            const bool opt = nm.size() > 16 && (nm.compare(nm.size() - 15, 15, "project_in.bias") == 0 || nm.compare(nm.size() - 14, 14, "to_logits.bias") == 0);
+            DIMX_REQUIRE(!opt, DIMX_ERR_STATE, "%s: %s is loaded; the training step implements the bias-free project_in / to_logits only", tag, nm.c_str());
+        }
+        return DIMX_OK;
+    }
+    // x-transformers sublayers of width C: pre-norm gain + attention, pre-norm gain + feed-forward
+    int xt_attn(const std::string& l, int C) {
+        const int inner = d.heads * d.dim_head;
+        DIMX_TRY(add(l + "0.0.weight", 1, C));
+        DIMX_TRY(add(l + "1.to_q.weight", inner, C));
+        DIMX_TRY(add(l + "1.to_k.weight", inner, C));
+        DIMX_TRY(add(l + "1.to_v.weight", inner, C));
+        return add(l + "1.to_out.weight", C, inner);
+    }
+    int xt_ff(const std::string& l, int C) {
+        DIMX_TRY(add(l + "0.0.weight", 1, C));
+        DIMX_TRY(add(l + "1.ff.0.0.weight", C * d.ff_mult, C));
+        DIMX_TRY(add(l + "1.ff.0.0.bias", 1, C * d.ff_mult));
+        DIMX_TRY(add(l + "1.ff.2.weight", C, C * d.ff_mult));
+        return add(l + "1.ff.2.bias", 1, C);
+    }
+    // an encoder (width d.dim, layers: self, ff) over inputs of in_cols columns
+    int xt_encoder(const std::string& e, int in_cols) {
+        DIMX_TRY(add(e + "project_in.weight", d.dim, in_cols));
         DIMX_TRY(add(e + "pos_emb.emb.weight", d.max_seq_len, d.dim));
         for (int i = 0; i < d.enc_depth; ++i) {
-            const std::string la = e + "attn_layers.layers." + std::to_string(2 * i) + ".";
-            const std::string lf = e + "attn_layers.layers." + std::to_string(2 * i + 1) + ".";
-            DIMX_TRY(add(la + "0.0.weight", 1, d.dim));
-            DIMX_TRY(add(la + "1.to_q.weight", inner, d.dim));
-            DIMX_TRY(add(la + "1.to_k.weight", inner, d.dim));
-            DIMX_TRY(add(la + "1.to_v.weight", inner, d.dim));
-            DIMX_TRY(add(la + "1.to_out.weight", d.dim, inner));
-            DIMX_TRY(add(lf + "0.0.weight", 1, d.dim));
-            DIMX_TRY(add(lf + "1.ff.0.0.weight", d.dim * d.ff_mult, d.dim));
-            DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, d.dim * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.weight", d.dim, d.dim * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.bias", 1, d.dim));
+            DIMX_TRY(xt_attn(e + "attn_layers.layers." + std::to_string(2 * i) + ".", d.dim));
+            DIMX_TRY(xt_ff(e + "attn_layers.layers." + std::to_string(2 * i + 1) + ".", d.dim));
         }
-        DIMX_TRY(add(e + "attn_layers.final_norm.weight", 1, d.dim));
-        DIMX_TRY(add(dn + "token_emb.emb.weight", d.num_tokens, DDl));
-        DIMX_TRY(add(dn + "pos_emb.emb.weight", d.max_seq_len, DDl));
+        return add(e + "attn_layers.final_norm.weight", 1, d.dim);
+    }
+    // a decoder (width DD = context width, layers: self, cross, ff); abs_pos: it has an absolute positional table
+    int xt_decoder(const std::string& dn, int DD, bool abs_pos) {
+        DIMX_TRY(add(dn + "token_emb.emb.weight", d.num_tokens, DD));
+        if (abs_pos) DIMX_TRY(add(dn + "pos_emb.emb.weight", d.max_seq_len, DD));
         for (int i = 0; i < d.dec_depth; ++i) {
-            for (int k = 0; k < 2; ++k) {
-                const std::string la = dn + "attn_layers.layers." + std::to_string(3 * i + k) + ".";
-                DIMX_TRY(add(la + "0.0.weight", 1, DDl));
-                DIMX_TRY(add(la + "1.to_q.weight", inner, DDl));
-                DIMX_TRY(add(la + "1.to_k.weight", inner, DDl));
-                DIMX_TRY(add(la + "1.to_v.weight", inner, DDl));
-                DIMX_TRY(add(la + "1.to_out.weight", DDl, inner));
-            }
-            const std::string lf = dn + "attn_layers.layers." + std::to_string(3 * i + 2) + ".";
-            DIMX_TRY(add(lf + "0.0.weight", 1, DDl));
-            DIMX_TRY(add(lf + "1.ff.0.0.weight", DDl * d.ff_mult, DDl));
-            DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, DDl * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.weight", DDl, DDl * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.bias", 1, DDl));
+            DIMX_TRY(xt_attn(dn + "attn_layers.layers." + std::to_string(3 * i) + ".", DD));
+            DIMX_TRY(xt_attn(dn + "attn_layers.layers." + std::to_string(3 * i + 1) + ".", DD));
+            DIMX_TRY(xt_ff(dn + "attn_layers.layers." + std::to_string(3 * i + 2) + ".", DD));
         }
-        DIMX_TRY(add(dn + "attn_layers.final_norm.weight", 1, DDl));
-        DIMX_TRY(add(dn + "to_logits.weight", d.num_tokens, DDl));
-        DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.weight", H, d.vq_zdim));
-        DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
-        DIMX_TRY(add(c + "expander.0.0.weight", H, 5 * H));   // [out][in][5]: rows of in * 5 + tap
-        DIMX_TRY(add(c + "expander.0.0.bias", 1, H));
-        DIMX_TRY(add(c + "decoder_linear_embedding.net.weight", H, H));
-        DIMX_TRY(add(c + "decoder_linear_embedding.net.bias", 1, H));
+        DIMX_TRY(add(dn + "attn_layers.final_norm.weight", 1, DD));
+        return add(dn + "to_logits.weight", d.num_tokens, DD);
+    }
+    // the transformer blocks of a VQ-VAE half (net = "...encoder_transformer.net." / "...decoder_transformer.net.")
+    int vq_blocks(const std::string& net) {
+        const int H = d.vq_hidden, I = d.vq_inter;
         for (int i = 0; i < d.vq_layers; ++i) {
-            const std::string a = c + "decoder_transformer.net." + std::to_string(2 * i) + ".fn.";
-            const std::string m = c + "decoder_transformer.net." + std::to_string(2 * i + 1) + ".fn.";
+            const std::string a = net + std::to_string(2 * i) + ".fn.";
+            const std::string m = net + std::to_string(2 * i + 1) + ".fn.";
             DIMX_TRY(add(a + "norm.weight", 1, H));
             DIMX_TRY(add(a + "norm.bias", 1, H));
             DIMX_TRY(add(a + "fn.to_qkv.weight", 3 * H, H));
@@ -149,138 +145,134 @@ int build_plan(dimx_handle h, TrainPlan& p) {
             DIMX_TRY(add(m + "fn.l2.weight", H, I));
             DIMX_TRY(add(m + "fn.l2.bias", 1, H));
         }
-        DIMX_TRY(add(c + "vertice_map_reverse.weight", d.vq_in_dim, H));
-        DIMX_TRY(add_free("listener_embeddings.weight", 100, 256));   // code/seq2seq.py:205-210
-        DIMX_TRY(add_free("fc_listener.weight", d.dim, 256));
-        DIMX_TRY(add_free("fc_listener.bias", 1, d.dim));
         return DIMX_OK;
+    }
+    // a VQ-VAE decoder that trains behind a frozen codebook (c = "speaker_vq.decoder." / "listener_vq.decoder."), state-dict order
+    int vq_decoder(const std::string& c) {
+        const int H = d.vq_hidden;
+        DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.weight", H, d.vq_zdim));
+        DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
+        DIMX_TRY(add(c + "expander.0.0.weight", H, 5 * H));   // [out][in][5]: rows of in * 5 + tap
+        DIMX_TRY(add(c + "expander.0.0.bias", 1, H));
+        DIMX_TRY(add(c + "decoder_linear_embedding.net.weight", H, H));
+        DIMX_TRY(add(c + "decoder_linear_embedding.net.bias", 1, H));
+        DIMX_TRY(vq_blocks(c + "decoder_transformer.net."));
+        return add(c + "vertice_map_reverse.weight", d.vq_in_dim, H);
+    }
+};
+
+// The DIM-Listener steps (fine-tuning, legacy generator, SLM pre-training: one per handle variant): every tensor the reference's
+// optimiser would update with a non-zero gradient on that path, in state-dict order of the stack
+int build_plan(dimx_handle h, TrainPlan& p) {
+    PlanBuilder b(p, h, "train");
+    const dimx_dims& d = h->d;
+    DIMX_TRY(b.refuse_optional_biases());
+    const int DD = d.dim + d.dim_a;  // decoder width = context width
+    if (d.variant == 1) {
+        // legacy ListenerGenerator (code/seq2seq.py:165-176): the generator, the listener VQ-VAE's DECODER and the id-conditioning
+        // layers train; both VQ encoders / codebooks are frozen
+        DIMX_TRY(b.xt_encoder("generator.encoder.", d.spk_face_quan_num * d.vq_zdim));
+        DIMX_TRY(b.xt_decoder("generator.decoder.net.", DD, true));
+        DIMX_TRY(b.vq_decoder("listener_vq.decoder."));
+        // the id-conditioning tables are training-only (the engine does not hold them): fixed shape, code/seq2seq.py:205-210
+        DIMX_TRY(b.add("listener_embeddings.weight", 100, 256, false));
+        DIMX_TRY(b.add("fc_listener.weight", d.dim, 256, false));
+        return b.add("fc_listener.bias", 1, d.dim, false);
     }
     if (d.variant == 2) {
         // SLM pre-training (code/seq2seq_pretrain.py:98-113): everything but the VQ-VAEs' encoders and codebooks trains -- the three
         // encoders, the decoder with its absolute positional table, the stream norms / patch embeddings and BOTH VQ-VAE decoders
         // (project_out of the encoders is never called: no gradient, not in the arena)
-        const int DD2 = d.dim + d.dim_a, H = d.vq_hidden, I = d.vq_inter;
-        for (const char* n : {"patch_embed_s", "patch_embed_l"}) DIMX_TRY(add(n, 1, d.dim_in));
+        for (const char* n : {"patch_embed_s", "patch_embed_l"}) DIMX_TRY(b.add(n, 1, d.dim_in));
         for (const char* n : {"patch_embed_dec_s", "patch_embed_dec_l", "norm_s.weight", "norm_s.bias", "norm_l.weight", "norm_l.bias", "norm.weight",
                               "norm.bias"})
-            DIMX_TRY(add(n, 1, d.dim));
-        for (const char* enc : {"encoder_s.", "encoder_l.", "encoder_joint."}) {
-            const std::string e(enc);
-            DIMX_TRY(add(e + "project_in.weight", d.dim, e == "encoder_joint." ? d.dim : d.dim_in));
-            DIMX_TRY(add(e + "pos_emb.emb.weight", d.max_seq_len, d.dim));
-            for (int i = 0; i < d.enc_depth; ++i) {
-                const std::string la = e + "attn_layers.layers." + std::to_string(2 * i) + ".";
-                const std::string lf = e + "attn_layers.layers." + std::to_string(2 * i + 1) + ".";
-                DIMX_TRY(add(la + "0.0.weight", 1, d.dim));
-                DIMX_TRY(add(la + "1.to_q.weight", inner, d.dim));
-                DIMX_TRY(add(la + "1.to_k.weight", inner, d.dim));
-                DIMX_TRY(add(la + "1.to_v.weight", inner, d.dim));
-                DIMX_TRY(add(la + "1.to_out.weight", d.dim, inner));
-                DIMX_TRY(add(lf + "0.0.weight", 1, d.dim));
-                DIMX_TRY(add(lf + "1.ff.0.0.weight", d.dim * d.ff_mult, d.dim));
-                DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, d.dim * d.ff_mult));
-                DIMX_TRY(add(lf + "1.ff.2.weight", d.dim, d.dim * d.ff_mult));
-                DIMX_TRY(add(lf + "1.ff.2.bias", 1, d.dim));
-            }
-            DIMX_TRY(add(e + "attn_layers.final_norm.weight", 1, d.dim));
-        }
-        const std::string dn = "decoder_joint.net.";
-        DIMX_TRY(add(dn + "token_emb.emb.weight", d.num_tokens, DD2));
-        DIMX_TRY(add(dn + "pos_emb.emb.weight", d.max_seq_len, DD2));
-        for (int i = 0; i < d.dec_depth; ++i) {
-            for (int k = 0; k < 2; ++k) {
-                const std::string la = dn + "attn_layers.layers." + std::to_string(3 * i + k) + ".";
-                DIMX_TRY(add(la + "0.0.weight", 1, DD2));
-                DIMX_TRY(add(la + "1.to_q.weight", inner, DD2));
-                DIMX_TRY(add(la + "1.to_k.weight", inner, DD2));
-                DIMX_TRY(add(la + "1.to_v.weight", inner, DD2));
-                DIMX_TRY(add(la + "1.to_out.weight", DD2, inner));
-            }
-            const std::string lf = dn + "attn_layers.layers." + std::to_string(3 * i + 2) + ".";
-            DIMX_TRY(add(lf + "0.0.weight", 1, DD2));
-            DIMX_TRY(add(lf + "1.ff.0.0.weight", DD2 * d.ff_mult, DD2));
-            DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, DD2 * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.weight", DD2, DD2 * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.bias", 1, DD2));
-        }
-        DIMX_TRY(add(dn + "attn_layers.final_norm.weight", 1, DD2));
-        DIMX_TRY(add(dn + "to_logits.weight", d.num_tokens, DD2));
-        for (const char* vq : {"speaker_vq.decoder.", "listener_vq.decoder."}) {
-            const std::string c(vq);
-            DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.weight", H, d.vq_zdim));
-            DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
-            DIMX_TRY(add(c + "expander.0.0.weight", H, 5 * H));
-            DIMX_TRY(add(c + "expander.0.0.bias", 1, H));
-            DIMX_TRY(add(c + "decoder_linear_embedding.net.weight", H, H));
-            DIMX_TRY(add(c + "decoder_linear_embedding.net.bias", 1, H));
-            for (int i = 0; i < d.vq_layers; ++i) {
-                const std::string a = c + "decoder_transformer.net." + std::to_string(2 * i) + ".fn.";
-                const std::string m = c + "decoder_transformer.net." + std::to_string(2 * i + 1) + ".fn.";
-                DIMX_TRY(add(a + "norm.weight", 1, H));
-                DIMX_TRY(add(a + "norm.bias", 1, H));
-                DIMX_TRY(add(a + "fn.to_qkv.weight", 3 * H, H));
-                DIMX_TRY(add(a + "fn.to_out.weight", H, H));
-                DIMX_TRY(add(a + "fn.to_out.bias", 1, H));
-                DIMX_TRY(add(m + "norm.weight", 1, H));
-                DIMX_TRY(add(m + "norm.bias", 1, H));
-                DIMX_TRY(add(m + "fn.l1.weight", I, H));
-                DIMX_TRY(add(m + "fn.l1.bias", 1, I));
-                DIMX_TRY(add(m + "fn.l2.weight", H, I));
-                DIMX_TRY(add(m + "fn.l2.bias", 1, H));
-            }
-            DIMX_TRY(add(c + "vertice_map_reverse.weight", d.vq_in_dim, H));
-        }
-        return DIMX_OK;
+            DIMX_TRY(b.add(n, 1, d.dim));
+        DIMX_TRY(b.xt_encoder("encoder_s.", d.dim_in));
+        DIMX_TRY(b.xt_encoder("encoder_l.", d.dim_in));
+        DIMX_TRY(b.xt_encoder("encoder_joint.", d.dim));
+        DIMX_TRY(b.xt_decoder("decoder_joint.net.", DD, true));
+        DIMX_TRY(b.vq_decoder("speaker_vq.decoder."));
+        return b.vq_decoder("listener_vq.decoder.");
     }
-    DIMX_TRY(add("patch_embed_s", 1, d.dim_in));
-    DIMX_TRY(add("patch_embed_dec_s", 1, d.dim));
-    DIMX_TRY(add("norm_s.weight", 1, d.dim));
-    DIMX_TRY(add("norm_s.bias", 1, d.dim));
-    for (const char* enc : {"encoder_s.", "encoder_joint."}) {
-        const std::string e(enc);
-        DIMX_TRY(add(e + "project_in.weight", d.dim, e == "encoder_s." ? d.dim_in : d.dim));
-        DIMX_TRY(add(e + "pos_emb.emb.weight", d.max_seq_len, d.dim));
-        for (int i = 0; i < d.enc_depth; ++i) {
-            const std::string la = e + "attn_layers.layers." + std::to_string(2 * i) + ".";
-            const std::string lf = e + "attn_layers.layers." + std::to_string(2 * i + 1) + ".";
-            DIMX_TRY(add(la + "0.0.weight", 1, d.dim));
-            DIMX_TRY(add(la + "1.to_q.weight", inner, d.dim));
-            DIMX_TRY(add(la + "1.to_k.weight", inner, d.dim));
-            DIMX_TRY(add(la + "1.to_v.weight", inner, d.dim));
-            DIMX_TRY(add(la + "1.to_out.weight", d.dim, inner));
-            DIMX_TRY(add(lf + "0.0.weight", 1, d.dim));
-            DIMX_TRY(add(lf + "1.ff.0.0.weight", d.dim * d.ff_mult, d.dim));
-            DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, d.dim * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.weight", d.dim, d.dim * d.ff_mult));
-            DIMX_TRY(add(lf + "1.ff.2.bias", 1, d.dim));
-        }
-        DIMX_TRY(add(e + "attn_layers.final_norm.weight", 1, d.dim));
-    }
-    const int DD = d.dim + d.dim_a;  // decoder width = context width
-    const std::string dn = "decoder_joint.net.";
-    DIMX_TRY(add(dn + "token_emb.emb.weight", d.num_tokens, DD));
-    for (int i = 0; i < d.dec_depth; ++i) {
-        for (int k = 0; k < 2; ++k) {  // self, cross
-            const std::string la = dn + "attn_layers.layers." + std::to_string(3 * i + k) + ".";
-            DIMX_TRY(add(la + "0.0.weight", 1, DD));
-            DIMX_TRY(add(la + "1.to_q.weight", inner, DD));
-            DIMX_TRY(add(la + "1.to_k.weight", inner, DD));
-            DIMX_TRY(add(la + "1.to_v.weight", inner, DD));
-            DIMX_TRY(add(la + "1.to_out.weight", DD, inner));
-        }
-        const std::string lf = dn + "attn_layers.layers." + std::to_string(3 * i + 2) + ".";
-        DIMX_TRY(add(lf + "0.0.weight", 1, DD));
-        DIMX_TRY(add(lf + "1.ff.0.0.weight", DD * d.ff_mult, DD));
-        DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, DD * d.ff_mult));
-        DIMX_TRY(add(lf + "1.ff.2.weight", DD, DD * d.ff_mult));
-        DIMX_TRY(add(lf + "1.ff.2.bias", 1, DD));
-    }
-    DIMX_TRY(add(dn + "attn_layers.final_norm.weight", 1, DD));
-    DIMX_TRY(add(dn + "to_logits.weight", d.num_tokens, DD));
-    return DIMX_OK;
+    DIMX_TRY(b.add("patch_embed_s", 1, d.dim_in));
+    DIMX_TRY(b.add("patch_embed_dec_s", 1, d.dim));
+    DIMX_TRY(b.add("norm_s.weight", 1, d.dim));
+    DIMX_TRY(b.add("norm_s.bias", 1, d.dim));
+    DIMX_TRY(b.xt_encoder("encoder_s.", d.dim_in));
+    DIMX_TRY(b.xt_encoder("encoder_joint.", d.dim));
+    return b.xt_decoder("decoder_joint.net.", DD, false);
 }
 
-// Per-handle training state: the parameter plan, the side stream the weight-gradient GEMMs run on, and the captured step.
+// The VQ-VAE's own step (slot `which` of the handle: 0 = speaker_vq., 1 = listener_vq.): every parameter of VQAutoEncoder
+// (code/models/stage1_BIWI.py:10-20) -- encoder, decoder, codebook; the two pe buffers are not parameters.
+int build_vq_plan(dimx_handle h, int which, TrainPlan& p) {
+    const dimx_dims& d = h->d;
+    const VQGeom& vg = h->vqg[which];
+    DIMX_REQUIRE(vg.in_dim == 56 && vg.hidden == 384 && vg.heads == 8 && vg.zdim == 128 && vg.fqn == 1 && vg.n_embed == 512 &&
+                     vg.has_decoder && d.vq_hidden == 384 && d.vq_heads == 8 && d.vq_zdim == 128,
+                 DIMX_ERR_ARG, "train_vq: slot %d is not the 56 / 384 / 8 x 48 / 128 VQ-VAE the step is written for", which);
+    PlanBuilder b(p, h, "train_vq");
+    const int H = d.vq_hidden;
+    const std::string pre = which == 0 ? "speaker_vq." : "listener_vq.", e = pre + "encoder.", c = pre + "decoder.";
+    DIMX_TRY(b.add(e + "vertice_mapping.0.weight", H, vg.in_dim));
+    DIMX_TRY(b.add(e + "vertice_mapping.0.bias", 1, H));
+    DIMX_TRY(b.add(e + "squasher.0.0.weight", H, 5 * H));   // [out][in][5]: rows of in * 5 + tap
+    DIMX_TRY(b.add(e + "squasher.0.0.bias", 1, H));
+    DIMX_TRY(b.vq_blocks(e + "encoder_transformer.net."));
+    DIMX_TRY(b.add(e + "encoder_linear_embedding.net.weight", H, H));
+    DIMX_TRY(b.add(e + "encoder_linear_embedding.net.bias", 1, H));
+    DIMX_TRY(b.add(e + "encoder_linear_embedding_post.net.weight", vg.zdim, H));
+    DIMX_TRY(b.add(e + "encoder_linear_embedding_post.net.bias", 1, vg.zdim));
+    DIMX_TRY(b.add(c + "expander.0.0.weight", H, 5 * H));
+    DIMX_TRY(b.add(c + "expander.0.0.bias", 1, H));
+    DIMX_TRY(b.vq_blocks(c + "decoder_transformer.net."));
+    DIMX_TRY(b.add(c + "decoder_linear_embedding.net.weight", H, H));
+    DIMX_TRY(b.add(c + "decoder_linear_embedding.net.bias", 1, H));
+    DIMX_TRY(b.add(c + "decoder_linear_embedding_pre.net.weight", H, vg.zdim));
+    DIMX_TRY(b.add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
+    DIMX_TRY(b.add(c + "vertice_map_reverse.weight", vg.in_dim, H));
+    return b.add(pre + "quantize.embedding.weight", vg.n_embed, vg.zdim);
+}
+
+// The DIM-Speaker converter's step: the head of EmocaConverter that dimx_mesh_head runs (code/seq2seq_pretrain.py:801-819), in
+// state-dict order.  Every tensor is padded to 16 bytes inside the arena; the V-wide bias relies on that pad (conv_run).
+int build_conv_plan(dimx_handle h, TrainPlan& p) {
+    DIMX_REQUIRE(h->d.mesh_dim > 0, DIMX_ERR_STATE, "train_conv: the handle was created without a mesh head (dimx_dims.mesh_dim = 0)");
+    DIMX_REQUIRE(h->d.mesh_dim % 3 == 0 && h->d.vq_in_dim % 4 == 0, DIMX_ERR_ARG, "train_conv: mesh_dim %d must be 3 x vertices", h->d.mesh_dim);
+    PlanBuilder b(p, h, "train_conv");
+    const std::string l = "vertice_map_reverse_lstm.";
+    for (int layer = 0; layer < 2; ++layer)
+        for (int dir = 0; dir < 2; ++dir) {
+            const std::string sfx = "_l" + std::to_string(layer) + (dir ? "_reverse" : "");
+            DIMX_TRY(b.add(l + "weight_ih" + sfx, 1536, layer ? 768 : h->d.vq_in_dim));
+            DIMX_TRY(b.add(l + "weight_hh" + sfx, 1536, 384));
+            DIMX_TRY(b.add(l + "bias_ih" + sfx, 1, 1536));
+            DIMX_TRY(b.add(l + "bias_hh" + sfx, 1, 1536));
+        }
+    DIMX_TRY(b.add("vertice_map_reverse.0.weight", 768, 768));
+    DIMX_TRY(b.add("vertice_map_reverse.0.bias", 1, 768));
+    DIMX_TRY(b.add("vertice_map_reverse.2.weight", h->d.mesh_dim, 768));
+    return b.add("vertice_map_reverse.2.bias", 1, h->d.mesh_dim);
+}
+
+// The DIM-Speaker fine-tuning step: what SpeakerSLMFT.forward(mode='train') (code/seq2seq_pretrain.py:708-757) leaves a gradient
+// on -- the cross entropy reaches decoder_joint.* (positional table included), patch_embed_dec_l and speaker_embed.weight (dense:
+// AdamW decays the rows no clip names too), the EMOCA loss reaches speaker_vq.decoder.* only (the arg-max cuts the graph).
+// Everything else keeps grad = None in the reference (its AdamW and its clip norm skip those tensors) and is not in the arena.
+int build_spk_plan(dimx_handle h, TrainPlan& p) {
+    const dimx_dims& d = h->d;
+    DIMX_REQUIRE(h->variant == 2 && d.mesh_dim > 0, DIMX_ERR_STATE,
+                 "train_spk: the handle is not a speaker handle (variant 2 with dimx_dims.mesh_dim > 0)");
+    DIMX_REQUIRE(h->spk_embed_rows > 0, DIMX_ERR_WEIGHT, "train_spk: speaker_embed.weight [rows, %d] was not loaded", d.dim);
+    PlanBuilder b(p, h, "train_spk");
+    DIMX_TRY(b.refuse_optional_biases());
+    DIMX_TRY(b.add("patch_embed_dec_l", 1, d.dim));
+    DIMX_TRY(b.xt_decoder("decoder_joint.net.", d.dim + d.dim_a, true));
+    DIMX_TRY(b.vq_decoder("speaker_vq.decoder."));
+    return b.add("speaker_embed.weight", h->spk_embed_rows, d.dim, false);   // not held by the engine: the shape it was loaded with
+}
+
+// State of a handle's DIM-Listener steps: the side stream the weight-gradient GEMMs run on, and the captured step.
 constexpr int kSideSlots = 3;
 struct StepGraphKey {
     const void *params, *grads, *v_speaker, *v_audio, *mask, *z_l, *kv_mask, *loss_out, *logits_out, *ws;
@@ -293,7 +285,7 @@ struct StepGraphKey {
     }
 };
 struct TrainState {
-    TrainPlan plan;
+    const TrainPlan* plan = nullptr;   // the handle's kPlanMain plan
     hipStream_t side = nullptr, cap = nullptr;
     hipEvent_t ev_main[kSideSlots] = {}, ev_side[kSideSlots] = {}, ev_join = nullptr;
     StepGraphKey last_key{}, graph_key{};
@@ -316,29 +308,6 @@ struct TrainState {
     }
 };
 
-std::mutex g_plans_mu;
-std::map<dimx_handle, TrainState>& plans_map() {
-    static std::map<dimx_handle, TrainState> plans;  // handles are few and long-lived; erased by dimx_destroy (train_forget)
-    return plans;
-}
-TrainState* state_of(dimx_handle h, int* rc) {
-    std::lock_guard<std::mutex> lock(g_plans_mu);
-    auto& plans = plans_map();
-    auto it = plans.find(h);
-    if (it == plans.end()) {
-        TrainPlan p;
-        *rc = build_plan(h, p);
-        if (*rc != DIMX_OK) return nullptr;
-        it = plans.emplace(std::piecewise_construct, std::forward_as_tuple(h), std::forward_as_tuple()).first;
-        it->second.plan = std::move(p);
-    }
-    *rc = DIMX_OK;
-    return &it->second;
-}
-TrainPlan* plan_of(dimx_handle h, int* rc) {
-    TrainState* ts = state_of(h, rc);
-    return ts ? &ts->plan : nullptr;
-}
 // the side stream and its events (first live step of a handle)
 int side_ready(TrainState& ts) {
     if (ts.side) return DIMX_OK;
@@ -351,91 +320,73 @@ int side_ready(TrainState& ts) {
     return DIMX_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- VQ-VAE step plan
-// The arenas of the VQ-VAE's own step (slot `which` of the handle: 0 = speaker_vq., 1 = listener_vq.): every parameter of
-// VQAutoEncoder (code/models/stage1_BIWI.py:10-20) -- encoder, decoder, codebook; the two pe buffers are not parameters.
-int build_vq_plan(dimx_handle h, int which, TrainPlan& p) {
-    DIMX_REQUIRE(which == 0 || which == 1, DIMX_ERR_ARG, "train_vq: which must be 0 (speaker_vq.) or 1 (listener_vq.)");
-    const dimx_dims& d = h->d;
-    const VQGeom& vg = h->vqg[which];
-    DIMX_REQUIRE(vg.in_dim == 56 && vg.hidden == 384 && vg.heads == 8 && vg.zdim == 128 && vg.fqn == 1 && vg.n_embed == 512 &&
-                     vg.has_decoder && d.vq_hidden == 384 && d.vq_heads == 8 && d.vq_zdim == 128,
-                 DIMX_ERR_ARG, "train_vq: slot %d is not the 56 / 384 / 8 x 48 / 128 VQ-VAE the step is written for", which);
-    const std::string pre = which == 0 ? "speaker_vq." : "listener_vq.";
-    auto add = [&](const std::string& name, int rows, int cols) -> int {
-        auto it = h->host.find(name);
-        DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "train_vq: weight %s was not loaded", name.c_str());
-        long n = 1;
-        for (auto sz : it->second.shape) n *= sz;
-        DIMX_REQUIRE(n == (long)rows * cols, DIMX_ERR_WEIGHT, "train_vq: %s has %ld elements, expected %d x %d", name.c_str(), n, rows, cols);
-        PInfo pi{name, p.total, n, rows, cols};
-        p.index[name] = (int)p.params.size();
-        p.params.push_back(pi);
-        p.total += (n + 3) / 4 * 4;  // 16-byte aligned tensors
-        return DIMX_OK;
-    };
-    const int H = d.vq_hidden, I = d.vq_inter;
-    auto blocks = [&](const std::string& net) -> int {
-        for (int i = 0; i < d.vq_layers; ++i) {
-            const std::string a = net + std::to_string(2 * i) + ".fn.";
-            const std::string m = net + std::to_string(2 * i + 1) + ".fn.";
-            DIMX_TRY(add(a + "norm.weight", 1, H));
-            DIMX_TRY(add(a + "norm.bias", 1, H));
-            DIMX_TRY(add(a + "fn.to_qkv.weight", 3 * H, H));
-            DIMX_TRY(add(a + "fn.to_out.weight", H, H));
-            DIMX_TRY(add(a + "fn.to_out.bias", 1, H));
-            DIMX_TRY(add(m + "norm.weight", 1, H));
-            DIMX_TRY(add(m + "norm.bias", 1, H));
-            DIMX_TRY(add(m + "fn.l1.weight", I, H));
-            DIMX_TRY(add(m + "fn.l1.bias", 1, I));
-            DIMX_TRY(add(m + "fn.l2.weight", H, I));
-            DIMX_TRY(add(m + "fn.l2.bias", 1, H));
-        }
-        return DIMX_OK;
-    };
-    const std::string e = pre + "encoder.", c = pre + "decoder.";
-    DIMX_TRY(add(e + "vertice_mapping.0.weight", H, vg.in_dim));
-    DIMX_TRY(add(e + "vertice_mapping.0.bias", 1, H));
-    DIMX_TRY(add(e + "squasher.0.0.weight", H, 5 * H));   // [out][in][5]: rows of in * 5 + tap
-    DIMX_TRY(add(e + "squasher.0.0.bias", 1, H));
-    DIMX_TRY(blocks(e + "encoder_transformer.net."));
-    DIMX_TRY(add(e + "encoder_linear_embedding.net.weight", H, H));
-    DIMX_TRY(add(e + "encoder_linear_embedding.net.bias", 1, H));
-    DIMX_TRY(add(e + "encoder_linear_embedding_post.net.weight", vg.zdim, H));
-    DIMX_TRY(add(e + "encoder_linear_embedding_post.net.bias", 1, vg.zdim));
-    DIMX_TRY(add(c + "expander.0.0.weight", H, 5 * H));
-    DIMX_TRY(add(c + "expander.0.0.bias", 1, H));
-    DIMX_TRY(blocks(c + "decoder_transformer.net."));
-    DIMX_TRY(add(c + "decoder_linear_embedding.net.weight", H, H));
-    DIMX_TRY(add(c + "decoder_linear_embedding.net.bias", 1, H));
-    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.weight", H, vg.zdim));
-    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
-    DIMX_TRY(add(c + "vertice_map_reverse.weight", vg.in_dim, H));
-    DIMX_TRY(add(pre + "quantize.embedding.weight", vg.n_embed, vg.zdim));
-    return DIMX_OK;
+// ---------------------------------------------------------------------------------------------------------------- per-handle registry
+// Everything the training steps keep for a handle: the plans of the steps it was asked for (built on first use) and the state of
+// the DIM-Listener steps.  Handles are few and long-lived; dimx_destroy erases the entry (train_forget).
+enum PlanKind { kPlanMain, kPlanVqSpeaker, kPlanVqListener, kPlanConv, kPlanSpk, kPlanVqNoSlot /* a `which` that names no slot */ };
+inline PlanKind vq_plan_kind(int which) { return which == 0 ? kPlanVqSpeaker : which == 1 ? kPlanVqListener : kPlanVqNoSlot; }
+const char* const kPlanTag[] = {"train", "train_vq", "train_vq", "train_conv", "train_spk", "train_vq"};   // a kind's prefix in messages
+struct HandleTrain {
+    std::map<int, TrainPlan> plans;   // by PlanKind
+    TrainState state;
+};
+std::mutex g_plans_mu;
+std::map<dimx_handle, HandleTrain>& train_map() {
+    static std::map<dimx_handle, HandleTrain> m;
+    return m;
 }
-std::map<std::pair<dimx_handle, int>, TrainPlan>& vq_plans_map() {
-    static std::map<std::pair<dimx_handle, int>, TrainPlan> plans;   // erased by dimx_destroy (train_forget)
-    return plans;
-}
-TrainPlan* vq_plan_of(dimx_handle h, int which, int* rc) {
-    *rc = DIMX_OK;
-    if (!h) {
-        *rc = DIMX_ERR_ARG;
-        set_error("train_vq: null handle");
-        return nullptr;
-    }
+int plan_of(dimx_handle h, PlanKind kind, TrainPlan** out) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "%s: null handle", kPlanTag[kind]);
+    DIMX_REQUIRE(kind != kPlanVqNoSlot, DIMX_ERR_ARG, "train_vq: which must be 0 (speaker_vq.) or 1 (listener_vq.)");
     std::lock_guard<std::mutex> lock(g_plans_mu);
-    auto key = std::make_pair(h, which);
-    auto& plans = vq_plans_map();
-    auto it = plans.find(key);
+    auto& plans = train_map()[h].plans;
+    auto it = plans.find(kind);
+    // the DIM-Speaker plan ends with speaker_embed.weight at the row count it was loaded with: a reload with another count replaces it
+    if (it != plans.end() && kind == kPlanSpk && it->second.params.back().rows != h->spk_embed_rows) {
+        plans.erase(it);
+        it = plans.end();
+    }
     if (it == plans.end()) {
         TrainPlan p;
-        *rc = build_vq_plan(h, which, p);
-        if (*rc != DIMX_OK) return nullptr;
-        it = plans.emplace(key, std::move(p)).first;
+        switch (kind) {
+            case kPlanMain: DIMX_TRY(build_plan(h, p)); break;
+            case kPlanConv: DIMX_TRY(build_conv_plan(h, p)); break;
+            case kPlanSpk: DIMX_TRY(build_spk_plan(h, p)); break;
+            default: DIMX_TRY(build_vq_plan(h, kind == kPlanVqListener ? 1 : 0, p)); break;
+        }
+        it = plans.emplace(kind, std::move(p)).first;
     }
-    return &it->second;
+    *out = &it->second;
+    return DIMX_OK;
+}
+int state_of(dimx_handle h, TrainState** out) {
+    TrainPlan* plan;
+    DIMX_TRY(plan_of(h, kPlanMain, &plan));
+    std::lock_guard<std::mutex> lock(g_plans_mu);
+    TrainState& ts = train_map()[h].state;
+    ts.plan = plan;
+    *out = &ts;
+    return DIMX_OK;
+}
+// one body each behind the dimx_<tag>_num_params / _total / _param_info entry points
+int layout_num_params(dimx_handle h, PlanKind kind) {
+    TrainPlan* p;
+    const int rc = plan_of(h, kind, &p);
+    return rc == DIMX_OK ? (int)p->params.size() : rc;
+}
+int64_t layout_total(dimx_handle h, PlanKind kind) {
+    TrainPlan* p;
+    const int rc = plan_of(h, kind, &p);
+    return rc == DIMX_OK ? (int64_t)p->total : (int64_t)rc;
+}
+int layout_param_info(dimx_handle h, PlanKind kind, int i, const char** name, int64_t* offset, int64_t* numel) {
+    TrainPlan* p;
+    DIMX_TRY(plan_of(h, kind, &p));
+    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "%s_param_info: bad index", kPlanTag[kind]);
+    *name = p->params[i].name.c_str();
+    *offset = p->params[i].off;
+    *numel = p->params[i].numel;
+    return DIMX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- step context
@@ -448,7 +399,6 @@ struct Step {
     hipStream_t st;
     int at;          // operand type of the GEMMs
     int bk;          // k-tile of the operand type (64 bf16 / 32 f32)
-    float* part;     // column-reduction scratch: max(2 * kLnBlocks * 1152, 2 * kTrSlabs * maxC) floats
     FinTable fin;    // column reductions whose partial rows are added by ONE launch at the end of the backward pass
     float* pool = nullptr;   // their partial rows: a region of its own (they outlive the sublayers' rolled-back scratch)
     size_t pool_off = 0, pool_cap = 0;
@@ -487,6 +437,37 @@ struct Step {
         int Kp, Mp;
     };
     std::map<std::tuple<const float*, int, int, int>, OpCopy> ops;
+
+    // n: rows per clip on the decoder side (T - 1 for the teacher-forced steps)
+    Step(dimx_handle h_, const TrainPlan* plan_, const float* P_, float* G_, Arena* ar_, hipStream_t st_, int at_, int B_, int T_, int n_)
+        : h(h_), plan(plan_), P(P_), G(G_), ar(ar_), st(st_), at(at_), bk(at_ == DIMX_BF16 ? 64 : 32), B(B_), T(T_), M(B_ * T_), n(n_), Md(B_ * n_) {
+        fin.n = 0;
+        fin.total_blocks = 0;
+        prep.n = 0;
+        prep.total_tiles = 0;
+    }
+    // What a step allocates before its first layer, in this order (the sizing pass and the captured graph depend on the sequence):
+    // 2 * kTrSlabs rows of its widest activation -- the column-reduction scratch of the first kernels; nothing reads it any more,
+    // it stays because the workspace sizes callers see must not move
+    void reserve_part(int width) { (void)f32((size_t)2 * kTrSlabs * width); }
+    // the rotating dy^T buffers of the side stream, for the step's widest weight gradient ([widest][rows])
+    int use_side_stream(TrainState& ts_, int widest, int rows) {
+        ts = &ts_;
+        use_side = true;
+        const size_t slot = (size_t)widest * pad_to(rows, bk) * es();
+        for (int i = 0; i < kSideSlots; ++i) slot_buf[i] = take(slot);
+        return live() ? side_ready(ts_) : DIMX_OK;
+    }
+    // the pool of the deferred column reductions' partial rows (the capacity formula is each step's own knowledge)
+    void alloc_pool(size_t cap) {
+        pool_cap = cap;
+        pool = f32(cap);
+        pool_off = 0;
+    }
+    int zero_grads() {
+        if (live()) DIMX_HIP(hipMemsetAsync(G, 0, (size_t)plan->total * sizeof(float), st));
+        return DIMX_OK;
+    }
 
     bool live() const { return ar->base != nullptr; }
     size_t es() const { return dtype_size(at); }
@@ -1311,61 +1292,10 @@ int vqenc_bwd(Step& s, VqEncSave& E, const float* dz) {
 
 
 // ---------------------------------------------------------------------------------------------------------------- converter head
-// The arenas of the DIM-Speaker converter's step: the head of EmocaConverter that dimx_mesh_head runs (code/seq2seq_pretrain.py:
-// 801-819), in state-dict order.  Every tensor is padded to 16 bytes inside the arena; the V-wide bias relies on that pad (conv_run).
 struct LstmLayerP {
     Lin ih[2], hh[2];   // [direction]; the bias of ih is bias_ih, the bias of hh is bias_hh (their gradients are equal)
     int In = 0;
 };
-int build_conv_plan(dimx_handle h, TrainPlan& p) {
-    DIMX_REQUIRE(h->d.mesh_dim > 0, DIMX_ERR_STATE, "train_conv: the handle was created without a mesh head (dimx_dims.mesh_dim = 0)");
-    DIMX_REQUIRE(h->d.mesh_dim % 3 == 0 && h->d.vq_in_dim % 4 == 0, DIMX_ERR_ARG, "train_conv: mesh_dim %d must be 3 x vertices", h->d.mesh_dim);
-    auto add = [&](const std::string& name, int rows, int cols) -> int {
-        auto it = h->host.find(name);
-        DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "train_conv: weight %s was not loaded", name.c_str());
-        long n = 1;
-        for (auto sz : it->second.shape) n *= sz;
-        DIMX_REQUIRE(n == (long)rows * cols, DIMX_ERR_WEIGHT, "train_conv: %s has %ld elements, expected %d x %d", name.c_str(), n, rows, cols);
-        PInfo pi{name, p.total, n, rows, cols};
-        p.index[name] = (int)p.params.size();
-        p.params.push_back(pi);
-        p.total += (n + 3) / 4 * 4;
-        return DIMX_OK;
-    };
-    const std::string l = "vertice_map_reverse_lstm.";
-    for (int layer = 0; layer < 2; ++layer)
-        for (int dir = 0; dir < 2; ++dir) {
-            const std::string sfx = "_l" + std::to_string(layer) + (dir ? "_reverse" : "");
-            DIMX_TRY(add(l + "weight_ih" + sfx, 1536, layer ? 768 : h->d.vq_in_dim));
-            DIMX_TRY(add(l + "weight_hh" + sfx, 1536, 384));
-            DIMX_TRY(add(l + "bias_ih" + sfx, 1, 1536));
-            DIMX_TRY(add(l + "bias_hh" + sfx, 1, 1536));
-        }
-    DIMX_TRY(add("vertice_map_reverse.0.weight", 768, 768));
-    DIMX_TRY(add("vertice_map_reverse.0.bias", 1, 768));
-    DIMX_TRY(add("vertice_map_reverse.2.weight", h->d.mesh_dim, 768));
-    DIMX_TRY(add("vertice_map_reverse.2.bias", 1, h->d.mesh_dim));
-    return DIMX_OK;
-}
-TrainPlan* conv_plan_of(dimx_handle h, int* rc) {
-    *rc = DIMX_OK;
-    if (!h) {
-        *rc = DIMX_ERR_ARG;
-        set_error("train_conv: null handle");
-        return nullptr;
-    }
-    std::lock_guard<std::mutex> lock(g_plans_mu);
-    auto key = std::make_pair(h, 2);   // beside the two VQ-VAE slots
-    auto& plans = vq_plans_map();
-    auto it = plans.find(key);
-    if (it == plans.end()) {
-        TrainPlan p;
-        *rc = build_conv_plan(h, p);
-        if (*rc != DIMX_OK) return nullptr;
-        it = plans.emplace(key, std::move(p)).first;
-    }
-    return &it->second;
-}
 LstmLayerP make_lstm_layer(const Step& s, int layer) {
     LstmLayerP L;
     const std::string l = "vertice_map_reverse_lstm.";
@@ -1411,132 +1341,39 @@ int lstm_layer_bwd(Step& s, const LstmLayerP& L, const float* x, const float* y,
 size_t lstm_train_scratch_bytes(int B, int T, int In) {
     return std::max(std::max(lstm_scratch_bytes(B, T, In), lstm_scratch_bytes(B, T, 768)), lstm_bwd_scratch_bytes(B, T));
 }
-// ---------------------------------------------------------------------------------------------------------------- DIM-Speaker step plan
-// The arenas of the DIM-Speaker fine-tuning step: what SpeakerSLMFT.forward(mode='train') (code/seq2seq_pretrain.py:708-757) leaves a
-// gradient on -- the cross entropy reaches decoder_joint.* (positional table included), patch_embed_dec_l and speaker_embed.weight
-// (dense: AdamW decays the rows no clip names too), the EMOCA loss reaches speaker_vq.decoder.* only (the arg-max cuts the graph).
-// Everything else keeps grad = None in the reference (its AdamW and its clip norm skip those tensors) and is not in the arena.
-int build_spk_plan(dimx_handle h, TrainPlan& p) {
-    const dimx_dims& d = h->d;
-    DIMX_REQUIRE(h->variant == 2 && d.mesh_dim > 0, DIMX_ERR_STATE,
-                 "train_spk: the handle is not a speaker handle (variant 2 with dimx_dims.mesh_dim > 0)");
-    DIMX_REQUIRE(h->spk_embed_rows > 0, DIMX_ERR_WEIGHT, "train_spk: speaker_embed.weight [rows, %d] was not loaded", d.dim);
-    for (const auto& kv : h->host) {
-        const std::string& nm = kv.first;
-        const bool opt = nm.size() > 16 && (nm.compare(nm.size() - 15, 15, "project_in.bias") == 0 || nm.compare(nm.size() - 14, 14, "to_logits.bias") == 0);
-        DIMX_REQUIRE(!opt, DIMX_ERR_STATE, "train_spk: %s is loaded; the training step implements the bias-free project_in / to_logits only", nm.c_str());
+// ---------------------------------------------------------------------------------------------------------------- step scaffold
+// The end of every step: the queued column reductions, the join of the side stream (in order: its last event covers every weight
+// gradient), the arena's high-water mark for the sizing pass, and the two overflow checks.
+int step_finish(Step& s, const char* tag, size_t* need) {
+    DIMX_TRY(flush_fin(s));   // every queued column reduction: one launch
+    if (s.use_side && s.live() && s.slot_n > 0) {
+        DIMX_HIP(hipEventRecord(s.ts->ev_join, s.ts->side));
+        DIMX_HIP(hipStreamWaitEvent(s.st, s.ts->ev_join, 0));
     }
-    auto add = [&](const std::string& name, int rows, int cols, bool held = true) -> int {
-        const long n = (long)rows * cols;
-        if (held) {
-            auto it = h->host.find(name);
-            DIMX_REQUIRE(it != h->host.end(), DIMX_ERR_WEIGHT, "train_spk: weight %s was not loaded", name.c_str());
-            long have = 1;
-            for (auto sz : it->second.shape) have *= sz;
-            DIMX_REQUIRE(have == n, DIMX_ERR_WEIGHT, "train_spk: %s has %ld elements, expected %d x %d", name.c_str(), have, rows, cols);
-        }
-        PInfo pi{name, p.total, n, rows, cols};
-        p.index[name] = (int)p.params.size();
-        p.params.push_back(pi);
-        p.total += (n + 3) / 4 * 4;  // 16-byte aligned tensors
-        return DIMX_OK;
-    };
-    const int inner = d.heads * d.dim_head, DD = d.dim + d.dim_a, H = d.vq_hidden, I = d.vq_inter;
-    DIMX_TRY(add("patch_embed_dec_l", 1, d.dim));
-    const std::string dn = "decoder_joint.net.";
-    DIMX_TRY(add(dn + "token_emb.emb.weight", d.num_tokens, DD));
-    DIMX_TRY(add(dn + "pos_emb.emb.weight", d.max_seq_len, DD));
-    for (int i = 0; i < d.dec_depth; ++i) {
-        for (int k = 0; k < 2; ++k) {
-            const std::string la = dn + "attn_layers.layers." + std::to_string(3 * i + k) + ".";
-            DIMX_TRY(add(la + "0.0.weight", 1, DD));
-            DIMX_TRY(add(la + "1.to_q.weight", inner, DD));
-            DIMX_TRY(add(la + "1.to_k.weight", inner, DD));
-            DIMX_TRY(add(la + "1.to_v.weight", inner, DD));
-            DIMX_TRY(add(la + "1.to_out.weight", DD, inner));
-        }
-        const std::string lf = dn + "attn_layers.layers." + std::to_string(3 * i + 2) + ".";
-        DIMX_TRY(add(lf + "0.0.weight", 1, DD));
-        DIMX_TRY(add(lf + "1.ff.0.0.weight", DD * d.ff_mult, DD));
-        DIMX_TRY(add(lf + "1.ff.0.0.bias", 1, DD * d.ff_mult));
-        DIMX_TRY(add(lf + "1.ff.2.weight", DD, DD * d.ff_mult));
-        DIMX_TRY(add(lf + "1.ff.2.bias", 1, DD));
-    }
-    DIMX_TRY(add(dn + "attn_layers.final_norm.weight", 1, DD));
-    DIMX_TRY(add(dn + "to_logits.weight", d.num_tokens, DD));
-    const std::string c = "speaker_vq.decoder.";
-    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.weight", H, d.vq_zdim));
-    DIMX_TRY(add(c + "decoder_linear_embedding_pre.net.bias", 1, H));
-    DIMX_TRY(add(c + "expander.0.0.weight", H, 5 * H));
-    DIMX_TRY(add(c + "expander.0.0.bias", 1, H));
-    DIMX_TRY(add(c + "decoder_linear_embedding.net.weight", H, H));
-    DIMX_TRY(add(c + "decoder_linear_embedding.net.bias", 1, H));
-    for (int i = 0; i < d.vq_layers; ++i) {
-        const std::string a = c + "decoder_transformer.net." + std::to_string(2 * i) + ".fn.";
-        const std::string m = c + "decoder_transformer.net." + std::to_string(2 * i + 1) + ".fn.";
-        DIMX_TRY(add(a + "norm.weight", 1, H));
-        DIMX_TRY(add(a + "norm.bias", 1, H));
-        DIMX_TRY(add(a + "fn.to_qkv.weight", 3 * H, H));
-        DIMX_TRY(add(a + "fn.to_out.weight", H, H));
-        DIMX_TRY(add(a + "fn.to_out.bias", 1, H));
-        DIMX_TRY(add(m + "norm.weight", 1, H));
-        DIMX_TRY(add(m + "norm.bias", 1, H));
-        DIMX_TRY(add(m + "fn.l1.weight", I, H));
-        DIMX_TRY(add(m + "fn.l1.bias", 1, I));
-        DIMX_TRY(add(m + "fn.l2.weight", H, I));
-        DIMX_TRY(add(m + "fn.l2.bias", 1, H));
-    }
-    DIMX_TRY(add(c + "vertice_map_reverse.weight", d.vq_in_dim, H));
-    DIMX_TRY(add("speaker_embed.weight", h->spk_embed_rows, d.dim, false));   // not held by the engine: the shape it was loaded with
+    if (need) *need = s.peak + 256;
+    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "%s: the partial-row pool of the column reductions is too small", tag);
+    DIMX_REQUIRE(!s.ar->overflow, DIMX_ERR_WORKSPACE, "%s: workspace %zu < required %zu", tag, s.ar->cap, s.peak);
     return DIMX_OK;
 }
-TrainPlan* spk_plan_of(dimx_handle h, int* rc) {
-    *rc = DIMX_OK;
-    if (!h) {
-        *rc = DIMX_ERR_ARG;
-        set_error("train_spk: null handle");
-        return nullptr;
-    }
-    std::lock_guard<std::mutex> lock(g_plans_mu);
-    auto key = std::make_pair(h, 3);   // beside the two VQ-VAE slots and the converter head
-    auto& plans = vq_plans_map();
-    auto it = plans.find(key);
-    if (it != plans.end() && it->second.params.back().rows != h->spk_embed_rows) {   // the embedding was reloaded with another row count
-        plans.erase(it);
-        it = plans.end();
-    }
-    if (it == plans.end()) {
-        TrainPlan p;
-        *rc = build_spk_plan(h, p);
-        if (*rc != DIMX_OK) return nullptr;
-        it = plans.emplace(key, std::move(p)).first;
-    }
-    return &it->second;
+// The arena is planned while kernels are being launched, so every entry point first walks its step without a workspace -- a pure
+// host walk of the same allocation sequence with the same arguments, nothing launched -- and checks the caller's workspace against
+// it: an undersized workspace used to be reported only after kernels had written past its end.
+// run(ws, ws_bytes, stream, need) is the step with every other argument bound.
+template <class Run>
+int check_workspace(const char* tag, size_t ws_bytes, Run run) {
+    size_t need = 0;
+    DIMX_TRY(run(nullptr, 0, nullptr, &need));
+    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "%s: workspace %zu < required %zu (dimx_%s_workspace_bytes)", tag, ws_bytes, need, tag);
+    return DIMX_OK;
 }
-void conv_step_init(Step& s, dimx_handle h, const TrainPlan* plan, const float* P, float* G, Arena* ar, hipStream_t st, int at, int B, int T) {
-    s.h = h; s.plan = plan; s.P = P; s.G = G; s.ar = ar; s.st = st;
-    s.at = at;
-    s.bk = at == DIMX_BF16 ? 64 : 32;
-    s.B = B; s.T = T; s.M = B * T;
-    s.n = T;
-    s.Md = B * T;
-    s.prep.n = 0;
-    s.prep.total_tiles = 0;
-    s.ts = nullptr;
-    s.use_side = false;
-    s.fin.n = 0;
-    s.fin.total_blocks = 0;
-    s.part = nullptr;
-}
+// dimx_*_workspace_bytes has no arguments to walk with: an optional input or output it sizes for stands in as this never
+// dereferenced address (the steps only ask whether it is there)
+template <class T> T* present() { return (T*)0x100; }
 }  // namespace
 
 void train_forget(dimx_handle h) {
     std::lock_guard<std::mutex> lock(g_plans_mu);
-    plans_map().erase(h);
-    vq_plans_map().erase(std::make_pair(h, 0));
-    vq_plans_map().erase(std::make_pair(h, 1));
-    vq_plans_map().erase(std::make_pair(h, 2));   // the converter head's plan
-    vq_plans_map().erase(std::make_pair(h, 3));   // the DIM-Speaker step's plan
+    train_map().erase(h);
 }
 
 }  // namespace dimx
@@ -1545,76 +1382,32 @@ using namespace dimx;
 
 extern "C" {
 
-int dimx_train_num_params(dimx_handle h) {
-    int rc;
-    TrainPlan* p = plan_of(h, &rc);
-    return p ? (int)p->params.size() : rc;
-}
-
-int64_t dimx_train_total(dimx_handle h) {
-    int rc;
-    TrainPlan* p = plan_of(h, &rc);
-    return p ? (int64_t)p->total : (int64_t)rc;
-}
-
+int dimx_train_num_params(dimx_handle h) { return layout_num_params(h, kPlanMain); }
+int64_t dimx_train_total(dimx_handle h) { return layout_total(h, kPlanMain); }
 int dimx_train_param_info(dimx_handle h, int i, const char** name, int64_t* offset, int64_t* numel) {
-    int rc;
-    TrainPlan* p = plan_of(h, &rc);
-    if (!p) return rc;
-    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "train_param_info: bad index");
-    *name = p->params[i].name.c_str();
-    *offset = p->params[i].off;
-    *numel = p->params[i].numel;
-    return DIMX_OK;
+    return layout_param_info(h, kPlanMain, i, name, offset, numel);
 }
 
 static int train_run(dimx_handle h, const float* params, float* grads, const float* v_speaker, const float* v_audio, const uint8_t* mask,
                      const int32_t* z_l, const uint8_t* kv_mask, int B, int T, float* loss_out, float* logits_out, void* ws,
                      size_t ws_bytes, hipStream_t st, size_t* need, bool use_side) {
-    int rc;
-    TrainState* ts = state_of(h, &rc);
-    if (!ts) return rc;
-    TrainPlan* plan = &ts->plan;
+    TrainState* ts;
+    DIMX_TRY(state_of(h, &ts));
     const dimx_dims& d = h->d;
     DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "train: only the SLMFT variant is trained");
     DIMX_REQUIRE(B >= 1 && T >= 2 && T <= d.max_seq_len, DIMX_ERR_ARG, "train: B=%d T=%d out of range", B, T);
     Arena ar(ws, ws_bytes);
-    Step s;
-    s.h = h;
-    s.plan = plan;
-    s.P = params;
-    s.G = grads;
-    s.ar = &ar;
-    s.st = st;
-    s.at = h->at;
-    s.bk = h->at == DIMX_BF16 ? 64 : 32;
-    s.B = B;
-    s.T = T;
-    s.M = B * T;
-    s.n = T - 1;
-    s.Md = B * (T - 1);
-    s.prep.n = 0;
-    s.prep.total_tiles = 0;
+    Step s(h, ts->plan, params, grads, &ar, st, h->at, B, T, T - 1);
     const int DD = d.dim + d.dim_a, F = DD * d.ff_mult, inner = d.heads * d.dim_head;
-    s.part = s.f32((size_t)2 * kTrSlabs * F);
-    s.ts = ts;
-    s.use_side = use_side;
-    if (use_side) {   // the widest dy^T of the step: ff1's [F][rows]
-        const size_t slot = (size_t)std::max(F, 3 * inner) * pad_to(s.M, s.bk) * s.es();
-        for (int i = 0; i < kSideSlots; ++i) s.slot_buf[i] = s.take(slot);
-        if (ws != nullptr) DIMX_TRY(side_ready(*ts));
-    }
+    s.reserve_part(F);
+    if (use_side) DIMX_TRY(s.use_side_stream(*ts, std::max(F, 3 * inner), s.M));   // the widest dy^T of the step: ff1's [F][rows]
     {   // partial rows of the deferred column reductions: LayerNorm adjoints (<= kLnBlocks + 3 rows of <= DD each, two for norm_s) and
         // bias / patch-embedding gradients (<= kTrSlabs rows of <= F)
         const size_t n_ln = (size_t)(4 * d.enc_depth + 3 * d.dec_depth + 12), n_b = (size_t)(4 * d.enc_depth + 2 * d.dec_depth + 4);
-        s.pool_cap = n_ln * (kLnBlocks + 4) * (size_t)DD + n_b * (size_t)std::max(kTrSlabs, ceil_div(s.M, 32) + 1) * (size_t)F + 4096;
-        s.pool = s.f32(s.pool_cap);
-        s.pool_off = 0;
-        s.fin.n = 0;
-        s.fin.total_blocks = 0;
+        s.alloc_pool(n_ln * (kLnBlocks + 4) * (size_t)DD + n_b * (size_t)std::max(kTrSlabs, ceil_div(s.M, 32) + 1) * (size_t)F + 4096);
     }
     const bool live = ws != nullptr;
-    if (live) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+    DIMX_TRY(s.zero_grads());
 
     // ---------------- encoders: x0 = v_speaker + patch_embed_s -> encoder_s -> encoder_joint -> norm_s
     float* x0 = s.f32((size_t)s.M * d.dim_in);
@@ -1705,16 +1498,7 @@ static int train_run(dimx_handle h, const float* params, float* grads, const flo
     DIMX_TRY(enc_bwd(s, ej, d_ej, d_es));
     DIMX_TRY(enc_bwd(s, es, d_es, d_x0));
     DIMX_TRY(bias_adjoint(s, d_x0, s.g("patch_embed_s"), s.M, d.dim_in));
-    DIMX_TRY(flush_fin(s));   // every queued column reduction: one launch
-    if (use_side && live && s.slot_n > 0) {   // join: the side stream is in order, its last event covers every weight gradient
-        DIMX_HIP(hipEventRecord(ts->ev_join, ts->side));
-        DIMX_HIP(hipStreamWaitEvent(st, ts->ev_join, 0));
-    }
-    (void)inner;
-    if (need) *need = s.peak + 256;
-    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train: the partial-row pool of the column reductions is too small");
-    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train: workspace %zu < required %zu", ws_bytes, s.peak);
-    return DIMX_OK;
+    return step_finish(s, "train", need);
 }
 
 // How a step is launched (measured on MI355X, profiles/r04_train_step.txt): the step is GPU-bound at every batch size (B = 2: 5.2 ms
@@ -1744,47 +1528,27 @@ static bool train_use_side(int rows) {
 static int legacy_run(dimx_handle h, const float* params, float* grads, const float* x_speaker, const int32_t* z_l, const float* v_listener,
                       const uint8_t* mask, const int32_t* listener_ids, const float* codebook, const float* pe, int B, int T, float* loss_out,
                       float* pred_out, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st, size_t* need, bool use_side) {
-    int rc;
-    TrainState* ts = state_of(h, &rc);
-    if (!ts) return rc;
-    TrainPlan* plan = &ts->plan;
+    TrainState* ts;
+    DIMX_TRY(state_of(h, &ts));
     const dimx_dims& d = h->d;
     DIMX_REQUIRE(h->variant == 1, DIMX_ERR_ARG, "train_legacy: the handle is not the legacy variant");
     DIMX_REQUIRE(B >= 1 && T >= 2 && T + 1 <= d.max_seq_len, DIMX_ERR_ARG, "train_legacy: B=%d T=%d out of range", B, T);
     DIMX_REQUIRE(d.num_tokens == 512 && d.dim_a == 0, DIMX_ERR_ARG, "train_legacy: 512 codes, no audio stream");
     Arena ar(ws, ws_bytes);
-    Step s;
-    s.h = h; s.plan = plan; s.P = params; s.G = grads; s.ar = &ar; s.st = st;
-    s.at = h->at;
-    s.bk = h->at == DIMX_BF16 ? 64 : 32;
-    s.B = B; s.T = T; s.M = B * T;
-    s.n = T - 1;
-    s.Md = B * (T - 1);
-    s.prep.n = 0;
-    s.prep.total_tiles = 0;
+    Step s(h, ts->plan, params, grads, &ar, st, h->at, B, T, T - 1);
     const bool ids = listener_ids != nullptr;
     const int DD = d.dim, F = std::max(DD * d.ff_mult, d.vq_inter), inner = d.heads * d.dim_head, H = d.vq_hidden;
     const int Lk = ids ? T + 1 : T, nd = ids ? T : T - 1, n = T - 1, E = 256;
     const int rows_max = B * (T + 1);
-    s.part = s.f32((size_t)2 * kTrSlabs * F);
-    s.ts = ts;
-    s.use_side = use_side;
-    if (use_side) {
-        const size_t slot = (size_t)std::max(F, 3 * inner) * pad_to(rows_max, s.bk) * s.es();
-        for (int i = 0; i < kSideSlots; ++i) s.slot_buf[i] = s.take(slot);
-        if (ws != nullptr) DIMX_TRY(side_ready(*ts));
-    }
+    s.reserve_part(F);
+    if (use_side) DIMX_TRY(s.use_side_stream(*ts, std::max(F, 3 * inner), rows_max));   // the widest dy^T of the step: ff1's [F][rows]
     {
         const size_t n_ln = (size_t)(2 * d.enc_depth + 3 * d.dec_depth + 4 * d.vq_layers + 8);
         const size_t n_b = (size_t)(2 * d.enc_depth + 2 * d.dec_depth + 3 * d.vq_layers + 8);
-        s.pool_cap = n_ln * (kLnBlocks + 4) * (size_t)DD + n_b * (size_t)std::max(kTrSlabs, ceil_div(rows_max, 32) + 1) * (size_t)F + 4096;
-        s.pool = s.f32(s.pool_cap);
-        s.pool_off = 0;
-        s.fin.n = 0;
-        s.fin.total_blocks = 0;
+        s.alloc_pool(n_ln * (kLnBlocks + 4) * (size_t)DD + n_b * (size_t)std::max(kTrSlabs, ceil_div(rows_max, 32) + 1) * (size_t)F + 4096);
     }
     const bool live = ws != nullptr;
-    if (live) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+    DIMX_TRY(s.zero_grads());
 
     // ---------------- encoder (mask-only attention: Encoder, not causal) over x_speaker [B, T, 8 x 128]
     EncSave e;
@@ -1850,25 +1614,14 @@ static int legacy_run(dimx_handle h, const float* params, float* grads, const fl
         TR(tr_emb_relu_bwd(s.p("listener_embeddings.weight"), listener_ids, d_e, s.g("listener_embeddings.weight"), B, E, st));
     }
     DIMX_TRY(enc_bwd(s, e, d_enc, nullptr));
-    DIMX_TRY(flush_fin(s));
-    if (use_side && live && s.slot_n > 0) {
-        DIMX_HIP(hipEventRecord(ts->ev_join, ts->side));
-        DIMX_HIP(hipStreamWaitEvent(st, ts->ev_join, 0));
-    }
-    if (need) *need = s.peak + 256;
-    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_legacy: the partial-row pool of the column reductions is too small");
-    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_legacy: workspace %zu < required %zu", ws_bytes, s.peak);
-    return DIMX_OK;
+    return step_finish(s, "train_legacy", need);
 }
 
 size_t dimx_train_legacy_workspace_bytes(dimx_handle h, int B, int T) {
     if (!h || B < 1 || T < 2) return 0;
-    size_t need = 0;
-    const uint8_t* tok = (const uint8_t*)0x100;
-    if (legacy_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, tok, (const int32_t*)tok, nullptr, nullptr, B, T, nullptr, nullptr, nullptr,
-                   nullptr, 0, nullptr, &need, true) != DIMX_OK)
-        return 0;
-    return need;
+    size_t need = 0;   // sized with the listener-id row and the side stream's slots: the branches that allocate the most
+    return legacy_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, present<const uint8_t>(), present<const int32_t>(), nullptr, nullptr, B, T,
+                      nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need, true) == DIMX_OK ? need : 0;
 }
 
 int dimx_train_legacy_forward_backward(dimx_handle h, const float* params, float* grads, const float* x_speaker, const int32_t* z_l,
@@ -1882,16 +1635,12 @@ int dimx_train_legacy_forward_backward(dimx_handle h, const float* params, float
                  DIMX_ERR_ARG, "train_legacy: workspace must be 256-byte aligned, arenas / inputs 16-byte aligned");
     DIMX_HIP(hipSetDevice(h->device));
     const bool side = train_use_side(B * T);
-    {
-        size_t need = 0;
-        const uint8_t* tok = (const uint8_t*)0x100;
-        DIMX_TRY(legacy_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, tok, listener_ids ? (const int32_t*)tok : nullptr, nullptr, nullptr, B,
-                            T, nullptr, pred_out ? (float*)0x100 : nullptr, logits_out ? (float*)0x100 : nullptr, nullptr, 0, nullptr, &need, side));
-        DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_legacy: workspace %zu < required %zu (dimx_train_legacy_workspace_bytes)",
-                     ws_bytes, need);
-    }
-    return legacy_run(h, params, grads, x_speaker, z_l, v_listener, mask, listener_ids, codebook, pe, B, T, loss_out, pred_out, logits_out, ws,
-                      ws_bytes, (hipStream_t)stream, nullptr, side);
+    auto run = [&](void* w, size_t w_bytes, hipStream_t st, size_t* need) {
+        return legacy_run(h, params, grads, x_speaker, z_l, v_listener, mask, listener_ids, codebook, pe, B, T, loss_out, pred_out, logits_out, w,
+                          w_bytes, st, need, side);
+    };
+    DIMX_TRY(check_workspace("train_legacy", ws_bytes, run));
+    return run(ws, ws_bytes, (hipStream_t)stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- SLM pre-training
@@ -1906,46 +1655,26 @@ static int slm_run(dimx_handle h, const float* params, float* grads, const float
                    const uint8_t* mask, const uint8_t* mask_speaker, const uint8_t* mask_listener, const int32_t* z_s, const int32_t* z_l,
                    const float* codebook_s, const float* codebook_l, const float* pe_s, const float* pe_l, int B, int T, float* loss_out, void* ws,
                    size_t ws_bytes, hipStream_t st, size_t* need, bool use_side) {
-    int rc;
-    TrainState* ts = state_of(h, &rc);
-    if (!ts) return rc;
-    TrainPlan* plan = &ts->plan;
+    TrainState* ts;
+    DIMX_TRY(state_of(h, &ts));
     const dimx_dims& d = h->d;
     DIMX_REQUIRE(h->variant == 2, DIMX_ERR_ARG, "train_slm: the handle is not the SLM variant");
     DIMX_REQUIRE(B >= 1 && T >= 2 && 2 * T <= d.max_seq_len, DIMX_ERR_ARG, "train_slm: B=%d T=%d out of range (2 T <= %d)", B, T, d.max_seq_len);
     DIMX_REQUIRE(d.num_tokens == 512 && d.vq_in_dim == 56 && d.dim_in == 56, DIMX_ERR_ARG, "train_slm: 512 codes, 56 coefficients");
     Arena ar(ws, ws_bytes);
-    Step s;
-    s.h = h; s.plan = plan; s.P = params; s.G = grads; s.ar = &ar; s.st = st;
-    s.at = h->at;
-    s.bk = h->at == DIMX_BF16 ? 64 : 32;
-    s.B = B; s.T = T; s.M = B * T;
-    s.n = T - 1;
-    s.Md = B * (T - 1);
-    s.prep.n = 0;
-    s.prep.total_tiles = 0;
+    Step s(h, ts->plan, params, grads, &ar, st, h->at, B, T, T - 1);
     const int C = d.dim, DD = d.dim + d.dim_a, F = std::max(DD * d.ff_mult, d.vq_inter), inner = d.heads * d.dim_head, n = T - 1;
     const int BT = B * T, rows_max = 4 * BT;
-    s.part = s.f32((size_t)2 * kTrSlabs * F);
-    s.ts = ts;
-    s.use_side = use_side;
-    if (use_side) {
-        const size_t slot = (size_t)std::max(F, 3 * inner) * pad_to(rows_max, s.bk) * s.es();
-        for (int i = 0; i < kSideSlots; ++i) s.slot_buf[i] = s.take(slot);
-        if (ws != nullptr) DIMX_TRY(side_ready(*ts));
-    }
+    s.reserve_part(F);
+    if (use_side) DIMX_TRY(s.use_side_stream(*ts, std::max(F, 3 * inner), rows_max));   // the widest dy^T of the step: ff1's [F][rows]
     {   // partial rows of the deferred column reductions
         const size_t n_ln_c = (size_t)(3 * (2 * d.enc_depth + 1) + 6 + 2 * 4 * d.vq_layers + 8), n_ln_dd = (size_t)(3 * d.dec_depth + 2);
         const size_t n_b = (size_t)(3 * 2 * d.enc_depth + 2 * d.dec_depth + 2 * 3 * d.vq_layers + 16);
-        s.pool_cap = n_ln_c * (kLnBlocks + 4) * (size_t)std::max(C, d.vq_hidden) + n_ln_dd * (kLnBlocks + 4) * (size_t)DD +
-                     n_b * (size_t)std::max(kTrSlabs, ceil_div(rows_max, 32) + 1) * (size_t)F + 4096;
-        s.pool = s.f32(s.pool_cap);
-        s.pool_off = 0;
-        s.fin.n = 0;
-        s.fin.total_blocks = 0;
+        s.alloc_pool(n_ln_c * (kLnBlocks + 4) * (size_t)std::max(C, d.vq_hidden) + n_ln_dd * (kLnBlocks + 4) * (size_t)DD +
+                     n_b * (size_t)std::max(kTrSlabs, ceil_div(rows_max, 32) + 1) * (size_t)F + 4096);
     }
     const bool live = ws != nullptr;
-    if (live) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+    DIMX_TRY(s.zero_grads());
 
     // ---------------- masks: keep-masks of the masked-out input rows, the joint encoder's key masks
     uint8_t* keep_s = (uint8_t*)s.take((size_t)BT);
@@ -2051,24 +1780,14 @@ static int slm_run(dimx_handle h, const float* params, float* grads, const float
     TR(tr_zero_rows(d_x0l, keep_l, BT, d.dim_in, st));
     DIMX_TRY(bias_adjoint(s, d_x0s, s.g("patch_embed_s"), BT, d.dim_in));
     DIMX_TRY(bias_adjoint(s, d_x0l, s.g("patch_embed_l"), BT, d.dim_in));
-    DIMX_TRY(flush_fin(s));
-    if (use_side && live && s.slot_n > 0) {
-        DIMX_HIP(hipEventRecord(ts->ev_join, ts->side));
-        DIMX_HIP(hipStreamWaitEvent(st, ts->ev_join, 0));
-    }
-    if (need) *need = s.peak + 256;
-    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_slm: the partial-row pool of the column reductions is too small");
-    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_slm: workspace %zu < required %zu", ws_bytes, s.peak);
-    return DIMX_OK;
+    return step_finish(s, "train_slm", need);
 }
 
 size_t dimx_train_slm_workspace_bytes(dimx_handle h, int B, int T) {
     if (!h || B < 1 || T < 2) return 0;
     size_t need = 0;
-    if (slm_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T,
-                nullptr, nullptr, 0, nullptr, &need, true) != DIMX_OK)
-        return 0;
-    return need;
+    return slm_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T,
+                   nullptr, nullptr, 0, nullptr, &need, true) == DIMX_OK ? need : 0;
 }
 
 int dimx_train_slm_forward_backward(dimx_handle h, const float* params, float* grads, const float* v_speaker, const float* v_listener,
@@ -2083,26 +1802,19 @@ int dimx_train_slm_forward_backward(dimx_handle h, const float* params, float* g
                  DIMX_ERR_ARG, "train_slm: workspace must be 256-byte aligned, arenas / codebooks / pe 16-byte aligned");
     DIMX_HIP(hipSetDevice(h->device));
     const bool side = train_use_side(4 * B * T);
-    {
-        size_t need = 0;
-        DIMX_TRY(slm_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B,
-                         T, nullptr, nullptr, 0, nullptr, &need, side));
-        DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_slm: workspace %zu < required %zu (dimx_train_slm_workspace_bytes)", ws_bytes, need);
-    }
-    return slm_run(h, params, grads, v_speaker, v_listener, v_audio, mask, mask_speaker, mask_listener, z_s, z_l, codebook_s, codebook_l, pe_s, pe_l,
-                   B, T, loss_out, ws, ws_bytes, (hipStream_t)stream, nullptr, side);
+    auto run = [&](void* w, size_t w_bytes, hipStream_t st, size_t* need) {
+        return slm_run(h, params, grads, v_speaker, v_listener, v_audio, mask, mask_speaker, mask_listener, z_s, z_l, codebook_s, codebook_l, pe_s,
+                       pe_l, B, T, loss_out, w, w_bytes, st, need, side);
+    };
+    DIMX_TRY(check_workspace("train_slm", ws_bytes, run));
+    return run(ws, ws_bytes, (hipStream_t)stream, nullptr);
 }
 
 size_t dimx_train_workspace_bytes(dimx_handle h, int B, int T) {
     if (!h || B < 1 || T < 2) return 0;
-    size_t need = 0;
-    // the sizing pass walks the allocation sequence of a live call without launching anything: optional inputs are given as
-    // non-null sentinels (never dereferenced) so that it takes the branches that allocate the most
-    const uint8_t* some_mask = (const uint8_t*)0x100;
-    if (train_run(h, nullptr, nullptr, nullptr, nullptr, some_mask, nullptr, some_mask, B, T, nullptr, nullptr, nullptr, 0, nullptr, &need,
-                  true) != DIMX_OK)   // sized with the side stream's slots: the choice may differ between calls
-        return 0;
-    return need;
+    size_t need = 0;   // sized with both masks and the side stream's slots (that choice may differ between calls): the most a call takes
+    return train_run(h, nullptr, nullptr, nullptr, nullptr, present<const uint8_t>(), nullptr, present<const uint8_t>(), B, T, nullptr, nullptr,
+                     nullptr, 0, nullptr, &need, true) == DIMX_OK ? need : 0;
 }
 
 // The step as a hipGraph.  Shapes are static per (B, T) and the step reads nothing from the host, so a call whose arguments
@@ -2118,19 +1830,12 @@ int dimx_train_forward_backward(dimx_handle h, const float* params, float* grads
                  "train: workspace must be 256-byte aligned, arenas 16-byte aligned");
     DIMX_HIP(hipSetDevice(h->device));
     const bool side = train_use_side(B * T);
-    // the arena is planned while kernels are being launched: check the caller's workspace against the sizing pass FIRST (a pure
-    // host walk of the same allocation sequence) -- an undersized workspace used to be reported only after kernels had written
-    // past its end
-    {
-        size_t need = 0;
-        const uint8_t* some_mask = (const uint8_t*)0x100;
-        DIMX_TRY(train_run(h, nullptr, nullptr, nullptr, nullptr, some_mask, nullptr, kv_mask ? some_mask : nullptr, B, T, nullptr,
-                           logits_out ? (float*)0x100 : nullptr, nullptr, 0, nullptr, &need, side));
-        DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train: workspace %zu < required %zu (dimx_train_workspace_bytes)", ws_bytes, need);
-    }
-    int rc;
-    TrainState* ts = state_of(h, &rc);
-    if (!ts) return rc;
+    auto run = [&](void* w, size_t w_bytes, hipStream_t on, size_t* need) {
+        return train_run(h, params, grads, v_speaker, v_audio, mask, z_l, kv_mask, B, T, loss_out, logits_out, w, w_bytes, on, need, side);
+    };
+    DIMX_TRY(check_workspace("train", ws_bytes, run));
+    TrainState* ts;
+    DIMX_TRY(state_of(h, &ts));
     hipStream_t st = (hipStream_t)stream;
     const StepGraphKey key{params, grads, v_speaker, v_audio, mask, z_l, kv_mask, loss_out, logits_out, ws, ws_bytes, B, T, h->at, side ? 1 : 0};
     if (train_use_graph(B * T)) {
@@ -2144,8 +1849,7 @@ int dimx_train_forward_backward(dimx_handle h, const float* params, float* grads
             if (!ts->cap) DIMX_HIP(hipStreamCreateWithFlags(&ts->cap, hipStreamNonBlocking));
             hipGraph_t graph = nullptr;
             DIMX_HIP(hipStreamBeginCapture(ts->cap, hipStreamCaptureModeThreadLocal));
-            const int rc2 = train_run(h, params, grads, v_speaker, v_audio, mask, z_l, kv_mask, B, T, loss_out, logits_out, ws, ws_bytes, ts->cap,
-                                      nullptr, side);
+            const int rc2 = run(ws, ws_bytes, ts->cap, nullptr);
             const hipError_t ce = hipStreamEndCapture(ts->cap, &graph);
             if (rc2 != DIMX_OK || ce != hipSuccess) {
                 if (graph) (void)hipGraphDestroy(graph);
@@ -2170,15 +1874,14 @@ int dimx_train_forward_backward(dimx_handle h, const float* params, float* grads
     ts->last_key = key;
     ts->have_last = true;
     ++ts->eager_runs;
-    return train_run(h, params, grads, v_speaker, v_audio, mask, z_l, kv_mask, B, T, loss_out, logits_out, ws, ws_bytes, st, nullptr, side);
+    return run(ws, ws_bytes, st, nullptr);
 }
 
 // {graph launches, kernel-by-kernel runs, nodes of the captured step} of this handle's training steps
 int dimx_train_graph_stats(dimx_handle h, int64_t* out3) {
     DIMX_REQUIRE(h && out3, DIMX_ERR_ARG, "train_graph_stats: null argument");
-    int rc;
-    TrainState* ts = state_of(h, &rc);
-    if (!ts) return rc;
+    TrainState* ts;
+    DIMX_TRY(state_of(h, &ts));
     out3[0] = ts->graph_launches;
     out3[1] = ts->eager_runs;
     out3[2] = ts->graph_nodes;
@@ -2222,9 +1925,8 @@ int dimx_op_train_attention(int mfma, const float* q, const float* k, const floa
 static int vq_run(dimx_handle h, int which, const float* params, float* grads, const float* x, int B, int T, float beta, float qw, float p,
                   uint64_t seed, long step, float* loss_out, float* pred_out, int32_t* idx_out, void* ws, size_t ws_bytes, hipStream_t st,
                   size_t* need) {
-    int rc;
-    TrainPlan* plan = vq_plan_of(h, which, &rc);
-    if (!plan) return rc;
+    TrainPlan* plan;
+    DIMX_TRY(plan_of(h, vq_plan_kind(which), &plan));
     const dimx_dims& d = h->d;
     DIMX_REQUIRE(B >= 1 && B <= 5000 && T >= 1 && T <= 65536 && (long)B * T <= (1l << 24), DIMX_ERR_ARG,
                  "train_vq: B=%d T=%d out of range (B <= 5000 positional rows)", B, T);
@@ -2233,29 +1935,15 @@ static int vq_run(dimx_handle h, int which, const float* params, float* grads, c
     const float *pe_enc = nullptr, *pe_dec = nullptr;
     if (live) DIMX_TRY(vq_pe_buffers(h, which, &pe_enc, &pe_dec));
     Arena ar(ws, ws_bytes);
-    Step s;
-    s.h = h; s.plan = plan; s.P = params; s.G = grads; s.ar = &ar; s.st = st;
-    s.at = h->at;
-    s.bk = h->at == DIMX_BF16 ? 64 : 32;
-    s.B = B; s.T = T; s.M = B * T;
-    s.n = T;
-    s.Md = B * T;
-    s.prep.n = 0;
-    s.prep.total_tiles = 0;
+    Step s(h, plan, params, grads, &ar, st, h->at, B, T, T);
     const int H = d.vq_hidden, I = d.vq_inter, M = B * T, ZD = d.vq_zdim;
-    s.part = s.f32((size_t)2 * kTrSlabs * I);
-    s.ts = nullptr;
-    s.use_side = false;
+    s.reserve_part(I);
     {
         const size_t n_ln = (size_t)(4 * 2 * d.vq_layers + 8);
         const size_t n_b = (size_t)(3 * 2 * d.vq_layers + 12);
-        s.pool_cap = n_ln * (kLnBlocks + 4) * (size_t)H + n_b * (size_t)std::max(kTrSlabs, ceil_div(M, 32) + 1) * (size_t)I + 4096;
-        s.pool = s.f32(s.pool_cap);
-        s.pool_off = 0;
-        s.fin.n = 0;
-        s.fin.total_blocks = 0;
+        s.alloc_pool(n_ln * (kLnBlocks + 4) * (size_t)H + n_b * (size_t)std::max(kTrSlabs, ceil_div(M, 32) + 1) * (size_t)I + 4096);
     }
-    if (live) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+    DIMX_TRY(s.zero_grads());
     const std::string pre = which == 0 ? "speaker_vq." : "listener_vq.";
     const float* book = s.p(pre + "quantize.embedding.weight");
     float* dbook = s.g(pre + "quantize.embedding.weight");
@@ -2295,44 +1983,22 @@ static int vq_run(dimx_handle h, int which, const float* params, float* grads, c
     TR(tr_vq_commit_bwd(z, book, idx, dz, M, qw * beta * inv, st));
     TR(tr_vq_book_grad(z, book, idx, dbook, M, qw * inv, st));
     DIMX_TRY(vqenc_bwd(s, E, dz));
-    DIMX_TRY(flush_fin(s));
-    if (need) *need = s.peak + 256;
-    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_vq: the partial-row pool of the column reductions is too small");
-    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_vq: workspace %zu < required %zu", ws_bytes, s.peak);
-    return DIMX_OK;
+    return step_finish(s, "train_vq", need);
 }
 
-int dimx_train_vq_num_params(dimx_handle h, int which) {
-    int rc;
-    TrainPlan* p = vq_plan_of(h, which, &rc);
-    return p ? (int)p->params.size() : rc;
-}
-
-int64_t dimx_train_vq_total(dimx_handle h, int which) {
-    int rc;
-    TrainPlan* p = vq_plan_of(h, which, &rc);
-    return p ? (int64_t)p->total : (int64_t)rc;
-}
-
+int dimx_train_vq_num_params(dimx_handle h, int which) { return layout_num_params(h, vq_plan_kind(which)); }
+int64_t dimx_train_vq_total(dimx_handle h, int which) { return layout_total(h, vq_plan_kind(which)); }
 int dimx_train_vq_param_info(dimx_handle h, int which, int i, const char** name, int64_t* offset, int64_t* numel) {
-    int rc;
-    TrainPlan* p = vq_plan_of(h, which, &rc);
-    if (!p) return rc;
-    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "train_vq_param_info: bad index");
-    *name = p->params[i].name.c_str();
-    *offset = p->params[i].off;
-    *numel = p->params[i].numel;
-    return DIMX_OK;
+    return layout_param_info(h, vq_plan_kind(which), i, name, offset, numel);
 }
 
 size_t dimx_train_vq_workspace_bytes(dimx_handle h, int B, int T) {
     if (!h || B < 1 || T < 1) return 0;
     const int which = h->vqg[1].in_dim == 56 ? 1 : 0;   // both slots of the 56-d geometry size alike
     size_t need = 0;
-    if (vq_run(h, which, nullptr, nullptr, nullptr, B, T, 0.25f, 1.f, 0.f, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need) !=
-        DIMX_OK)
-        return 0;
-    return need;
+    return vq_run(h, which, nullptr, nullptr, nullptr, B, T, 0.25f, 1.f, 0.f, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need) == DIMX_OK
+               ? need
+               : 0;
 }
 
 int dimx_train_vq_forward_backward(dimx_handle h, int which, const float* params, float* grads, const float* x, int B, int T, float beta,
@@ -2342,15 +2008,12 @@ int dimx_train_vq_forward_backward(dimx_handle h, int which, const float* params
     DIMX_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)x % 16) == 0,
                  DIMX_ERR_ARG, "train_vq: workspace must be 256-byte aligned, arenas / input 16-byte aligned");
     DIMX_HIP(hipSetDevice(h->device));
-    {
-        size_t need = 0;
-        DIMX_TRY(vq_run(h, which, nullptr, nullptr, nullptr, B, T, beta, quant_loss_weight, dropout_p, dropout_seed, (long)step, nullptr,
-                        pred_out ? (float*)0x100 : nullptr, idx_out ? (int32_t*)0x100 : nullptr, nullptr, 0, nullptr, &need));
-        DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_vq: workspace %zu < required %zu (dimx_train_vq_workspace_bytes)", ws_bytes,
-                     need);
-    }
-    return vq_run(h, which, params, grads, x, B, T, beta, quant_loss_weight, dropout_p, dropout_seed, (long)step, loss_out, pred_out, idx_out,
-                  ws, ws_bytes, (hipStream_t)stream, nullptr);
+    auto run = [&](void* w, size_t w_bytes, hipStream_t st, size_t* need) {
+        return vq_run(h, which, params, grads, x, B, T, beta, quant_loss_weight, dropout_p, dropout_seed, (long)step, loss_out, pred_out, idx_out, w,
+                      w_bytes, st, need);
+    };
+    DIMX_TRY(check_workspace("train_vq", ws_bytes, run));
+    return run(ws, ws_bytes, (hipStream_t)stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- DIM-Speaker converter
@@ -2358,23 +2021,20 @@ int dimx_train_vq_forward_backward(dimx_handle h, int which, const float* params
 // 17-96).  Forward: lstm.hip's layers with the save switch, then the two GEMMs of dimx_mesh_head with the same arguments (the f32
 // mode's mesh is that call's bit for bit).  The loss kernel leaves dY [M][Vp], Vp = V rounded up to 4 with zero pad columns (V =
 // 70110 is no multiple of 4; the operand copies move 16-byte groups).  Backward: the V-wide Linear by hand (its input adjoint
-// contracts over V in deterministic split-K slabs), the rest through lin_bwd.  want_bwd / have_mesh stand for grads / mesh_out in
-// the sizing pass.
+// contracts over V in deterministic split-K slabs), the rest through lin_bwd.  grads == NULL: forward and
+// loss only; mesh_out == NULL: the mesh stays in the workspace.
 static int conv_run(dimx_handle h, const float* params, float* grads, const float* motion, const float* templ, const float* target,
-                    const float* vert_w, int n_mouth, int B, int T, int flags, float* loss_out, float* mesh_out, bool want_bwd, bool have_mesh,
-                    void* ws, size_t ws_bytes, hipStream_t st, size_t* need) {
-    int rc;
-    TrainPlan* plan = conv_plan_of(h, &rc);
-    if (!plan) return rc;
+                    const float* vert_w, int n_mouth, int B, int T, int flags, float* loss_out, float* mesh_out, void* ws, size_t ws_bytes,
+                    hipStream_t st, size_t* need) {
+    TrainPlan* plan;
+    DIMX_TRY(plan_of(h, kPlanConv, &plan));
     DIMX_REQUIRE(B >= 1 && T >= 1 && T <= 65536 && (long)B * T <= (1l << 20), DIMX_ERR_ARG, "train_conv: B=%d T=%d out of range", B, T);
     const int V = h->d.mesh_dim, Vp = pad_to(V, 4), M = B * T;
+    const bool want_bwd = grads != nullptr;
     Arena ar(ws, ws_bytes);
-    Step s;
-    conv_step_init(s, h, plan, params, grads, &ar, st, h->at, B, T);
+    Step s(h, plan, params, grads, &ar, st, h->at, B, T, T);
     const int Np = pad_to(V, s.bk), Mp = pad_to(M, s.bk);
-    s.pool_cap = want_bwd ? (size_t)8 * (ceil_div(M, 32) + 1) * 1536 + (size_t)(ceil_div(M, 32) + 1) * 768 + (size_t)kTrSlabs * Vp + 4096 : 64;
-    s.pool = s.f32(s.pool_cap);
-    s.pool_off = 0;
+    s.alloc_pool(want_bwd ? (size_t)8 * (ceil_div(M, 32) + 1) * 1536 + (size_t)(ceil_div(M, 32) + 1) * 768 + (size_t)kTrSlabs * Vp + 4096 : 64);
 
     LstmLayerP L0 = make_lstm_layer(s, 0), L1 = make_lstm_layer(s, 1);
     Lin l1 = make_lin(s, "vertice_map_reverse.0.weight", "vertice_map_reverse.0.bias");
@@ -2398,7 +2058,7 @@ static int conv_run(dimx_handle h, const float* params, float* grads, const floa
     DIMX_TRY(lstm_layer_fwd(s, L0, motion, y0, save0, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
     DIMX_TRY(lstm_layer_fwd(s, L1, y0, y1, save1, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
     float* a1 = s.f32((size_t)M * 768);
-    float* mesh = have_mesh ? mesh_out : s.f32((size_t)M * V);
+    float* mesh = mesh_out ? mesh_out : s.f32((size_t)M * V);
     const Step::OpCopy *c1, *c2;
     DIMX_TRY(fwd_operands(s, y1, 768, M, 768, &c1));
     if (s.live()) {
@@ -2450,7 +2110,7 @@ static int conv_run(dimx_handle h, const float* params, float* grads, const floa
 
     if (want_bwd) {
         // ---------------- backward
-        if (s.live()) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+        DIMX_TRY(s.zero_grads());
         float* da1 = s.f32((size_t)M * 768);
         {
             const size_t mark = ar.off;
@@ -2498,44 +2158,22 @@ static int conv_run(dimx_handle h, const float* params, float* grads, const floa
         float* dy0 = s.f32((size_t)M * 768);
         DIMX_TRY(lstm_layer_bwd(s, L1, y0, y1, save1, dy1, dy0, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
         DIMX_TRY(lstm_layer_bwd(s, L0, motion, y0, save0, dy0, nullptr, scr, scr_bytes, flags, h->cu_count, &h->lstm_faults));
-        DIMX_TRY(flush_fin(s));
     }
-    if (need) *need = s.peak + 256;
-    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_conv: the partial-row pool of the column reductions is too small");
-    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_conv: workspace %zu < required %zu", ws_bytes, s.peak);
-    return DIMX_OK;
+    return step_finish(s, "train_conv", need);
 }
 
-int dimx_train_conv_num_params(dimx_handle h) {
-    int rc;
-    TrainPlan* p = conv_plan_of(h, &rc);
-    return p ? (int)p->params.size() : rc;
-}
-
-int64_t dimx_train_conv_total(dimx_handle h) {
-    int rc;
-    TrainPlan* p = conv_plan_of(h, &rc);
-    return p ? (int64_t)p->total : (int64_t)rc;
-}
-
+int dimx_train_conv_num_params(dimx_handle h) { return layout_num_params(h, kPlanConv); }
+int64_t dimx_train_conv_total(dimx_handle h) { return layout_total(h, kPlanConv); }
 int dimx_train_conv_param_info(dimx_handle h, int i, const char** name, int64_t* offset, int64_t* numel) {
-    int rc;
-    TrainPlan* p = conv_plan_of(h, &rc);
-    if (!p) return rc;
-    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "train_conv_param_info: bad index");
-    *name = p->params[i].name.c_str();
-    *offset = p->params[i].off;
-    *numel = p->params[i].numel;
-    return DIMX_OK;
+    return layout_param_info(h, kPlanConv, i, name, offset, numel);
 }
 
 size_t dimx_train_conv_workspace_bytes(dimx_handle h, int B, int T) {
     if (!h || B < 1 || T < 1) return 0;
-    size_t need = 0;
-    if (conv_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, T, 0, nullptr, nullptr, true, false, nullptr, 0, nullptr, &need) !=
-        DIMX_OK)
-        return 0;
-    return need;
+    size_t need = 0;   // sized for a step with gradients that keeps the mesh in the workspace
+    return conv_run(h, nullptr, present<float>(), nullptr, nullptr, nullptr, nullptr, 0, B, T, 0, nullptr, nullptr, nullptr, 0, nullptr, &need) == DIMX_OK
+               ? need
+               : 0;
 }
 
 int dimx_train_conv_forward_backward(dimx_handle h, const float* params, float* grads, const float* motion, const float* templ,
@@ -2548,15 +2186,11 @@ int dimx_train_conv_forward_backward(dimx_handle h, const float* params, float* 
                  DIMX_ERR_ARG, "train_conv: workspace must be 256-byte aligned, arenas / input 16-byte aligned");
     DIMX_REQUIRE(!vert_w || n_mouth >= 1, DIMX_ERR_ARG, "train_conv: vert_w needs n_mouth >= 1 (%d)", n_mouth);
     DIMX_HIP(hipSetDevice(h->device));
-    {
-        size_t need = 0;
-        DIMX_TRY(conv_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, T, flags, nullptr, nullptr, grads != nullptr,
-                          mesh_out != nullptr, nullptr, 0, nullptr, &need));
-        DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_conv: workspace %zu < required %zu (dimx_train_conv_workspace_bytes)",
-                     ws_bytes, need);
-    }
-    return conv_run(h, params, grads, motion, templ, target, vert_w, n_mouth, B, T, flags, loss_out, mesh_out, grads != nullptr,
-                    mesh_out != nullptr, ws, ws_bytes, (hipStream_t)stream, nullptr);
+    auto run = [&](void* w, size_t w_bytes, hipStream_t st, size_t* need) {
+        return conv_run(h, params, grads, motion, templ, target, vert_w, n_mouth, B, T, flags, loss_out, mesh_out, w, w_bytes, st, need);
+    };
+    DIMX_TRY(check_workspace("train_conv", ws_bytes, run));
+    return run(ws, ws_bytes, (hipStream_t)stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- DIM-Speaker fine-tuning
@@ -2569,40 +2203,25 @@ int dimx_train_conv_forward_backward(dimx_handle h, const float* params, float* 
 static int spk_run(dimx_handle h, const float* params, float* grads, const float* v_emoca, const float* v_audio, const uint8_t* mask,
                    const int32_t* z, const int32_t* speaker_ids, const float* codebook_s, const float* pe_s, int B, int T, float* loss_out,
                    float* logits_out, int32_t* idx_out, float* pred_out, void* ws, size_t ws_bytes, hipStream_t st, size_t* need) {
-    int rc;
-    TrainPlan* plan = spk_plan_of(h, &rc);
-    if (!plan) return rc;
+    TrainPlan* plan;
+    DIMX_TRY(plan_of(h, kPlanSpk, &plan));
     const dimx_dims& d = h->d;
     DIMX_REQUIRE(B >= 1 && T >= 2 && T - 1 <= d.max_seq_len, DIMX_ERR_ARG, "train_spk: B=%d T=%d out of range (T - 1 <= %d)", B, T, d.max_seq_len);
     DIMX_REQUIRE(d.num_tokens == 512 && d.vq_in_dim == 56 && d.dim % 4 == 0 && d.dim_a % 4 == 0 && d.dim_a > 0, DIMX_ERR_ARG,
                  "train_spk: 512 codes, 56 coefficients, an audio stream");
     Arena ar(ws, ws_bytes);
-    Step s;
-    s.h = h; s.plan = plan; s.P = params; s.G = grads; s.ar = &ar; s.st = st;
-    s.at = h->at;
-    s.bk = h->at == DIMX_BF16 ? 64 : 32;
-    s.B = B; s.T = T; s.M = B * T;
-    s.n = T - 1;
-    s.Md = B * (T - 1);
-    s.prep.n = 0;
-    s.prep.total_tiles = 0;
-    s.ts = nullptr;
-    s.use_side = false;
+    Step s(h, plan, params, grads, &ar, st, h->at, B, T, T - 1);
     const int C = d.dim, DD = d.dim + d.dim_a, F = std::max(DD * d.ff_mult, d.vq_inter), n = T - 1, BT = B * T;
     const int rows = plan->params[plan->index.at("speaker_embed.weight")].rows;
-    s.part = s.f32((size_t)2 * kTrSlabs * F);
+    s.reserve_part(F);
     {   // partial rows of the deferred column reductions
         const size_t n_ln_c = (size_t)(4 * d.vq_layers + 8), n_ln_dd = (size_t)(3 * d.dec_depth + 2);
         const size_t n_b = (size_t)(2 * d.dec_depth + 3 * d.vq_layers + 16);
-        s.pool_cap = n_ln_c * (kLnBlocks + 4) * (size_t)std::max(C, d.vq_hidden) + n_ln_dd * (kLnBlocks + 4) * (size_t)DD +
-                     n_b * (size_t)std::max(kTrSlabs, ceil_div(BT, 32) + 1) * (size_t)F + 4096;
-        s.pool = s.f32(s.pool_cap);
-        s.pool_off = 0;
-        s.fin.n = 0;
-        s.fin.total_blocks = 0;
+        s.alloc_pool(n_ln_c * (kLnBlocks + 4) * (size_t)std::max(C, d.vq_hidden) + n_ln_dd * (kLnBlocks + 4) * (size_t)DD +
+                     n_b * (size_t)std::max(kTrSlabs, ceil_div(BT, 32) + 1) * (size_t)F + 4096);
     }
     const bool live = ws != nullptr;
-    if (live) DIMX_HIP(hipMemsetAsync(grads, 0, (size_t)plan->total * sizeof(float), st));
+    DIMX_TRY(s.zero_grads());
 
     // ---------------- context, tokens
     float* ctx = s.f32((size_t)BT * DD);
@@ -2636,43 +2255,20 @@ static int spk_run(dimx_handle h, const float* params, float* grads, const float
     // the audio columns of the context have no parameters behind them; the first dim columns are the embedding row + the patch
     float* cpart = s.f32(tr_spk_context_bwd_floats(B, C));
     TR(tr_spk_context_bwd(dctx, speaker_ids, s.g("speaker_embed.weight"), s.g("patch_embed_dec_l"), cpart, B, T, C, DD, rows, st));
-    DIMX_TRY(flush_fin(s));
-    if (need) *need = s.peak + 256;
-    DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_STATE, "train_spk: the partial-row pool of the column reductions is too small");
-    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "train_spk: workspace %zu < required %zu", ws_bytes, s.peak);
-    return DIMX_OK;
+    return step_finish(s, "train_spk", need);
 }
 
-int dimx_train_spk_num_params(dimx_handle h) {
-    int rc;
-    TrainPlan* p = spk_plan_of(h, &rc);
-    return p ? (int)p->params.size() : rc;
-}
-
-int64_t dimx_train_spk_total(dimx_handle h) {
-    int rc;
-    TrainPlan* p = spk_plan_of(h, &rc);
-    return p ? (int64_t)p->total : (int64_t)rc;
-}
-
+int dimx_train_spk_num_params(dimx_handle h) { return layout_num_params(h, kPlanSpk); }
+int64_t dimx_train_spk_total(dimx_handle h) { return layout_total(h, kPlanSpk); }
 int dimx_train_spk_param_info(dimx_handle h, int i, const char** name, int64_t* offset, int64_t* numel) {
-    int rc;
-    TrainPlan* p = spk_plan_of(h, &rc);
-    if (!p) return rc;
-    DIMX_REQUIRE(i >= 0 && i < (int)p->params.size() && name && offset && numel, DIMX_ERR_ARG, "train_spk_param_info: bad index");
-    *name = p->params[i].name.c_str();
-    *offset = p->params[i].off;
-    *numel = p->params[i].numel;
-    return DIMX_OK;
+    return layout_param_info(h, kPlanSpk, i, name, offset, numel);
 }
 
 size_t dimx_train_spk_workspace_bytes(dimx_handle h, int B, int T) {
     if (!h || B < 1 || T < 2) return 0;
     size_t need = 0;
-    if (spk_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr, nullptr, nullptr, nullptr,
-                nullptr, 0, nullptr, &need) != DIMX_OK)
-        return 0;
-    return need;
+    return spk_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr, nullptr, nullptr, nullptr,
+                   nullptr, 0, nullptr, &need) == DIMX_OK ? need : 0;
 }
 
 int dimx_train_spk_forward_backward(dimx_handle h, const float* params, float* grads, const float* v_emoca, const float* v_audio,
@@ -2687,16 +2283,14 @@ int dimx_train_spk_forward_backward(dimx_handle h, const float* params, float* g
                  DIMX_ERR_ARG, "train_spk: workspace must be 256-byte aligned, arenas / inputs / codebook / pe / pred_out 16-byte aligned");
     DIMX_HIP(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    size_t need = 0;
-    // the sizing pass walks the live pass's allocations: an output handed in replaces its workspace buffer there too
-    DIMX_TRY(spk_run(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr,
-                     logits_out ? (float*)0x100 : nullptr, idx_out ? (int32_t*)0x100 : nullptr, pred_out ? (float*)0x100 : nullptr, nullptr, 0,
-                     nullptr, &need));
-    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "train_spk: workspace %zu < required %zu (dimx_train_spk_workspace_bytes)", ws_bytes, need);
+    auto run = [&](void* w, size_t w_bytes, hipStream_t on, size_t* need) {
+        return spk_run(h, params, grads, v_emoca, v_audio, mask, z, speaker_ids, codebook_s, pe_s, B, T, loss_out, logits_out, idx_out, pred_out, w,
+                       w_bytes, on, need);
+    };
+    DIMX_TRY(check_workspace("train_spk", ws_bytes, run));
     if (speaker_ids) {   // an id outside the table is refused here, on the host: the kernels index with it unchecked
-        int rc;
-        TrainPlan* plan = spk_plan_of(h, &rc);
-        if (!plan) return rc;
+        TrainPlan* plan;
+        DIMX_TRY(plan_of(h, kPlanSpk, &plan));
         const int rows = plan->params[plan->index.at("speaker_embed.weight")].rows;
         std::vector<int32_t> ids((size_t)B);
         DIMX_HIP(hipMemcpyAsync(ids.data(), speaker_ids, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -2704,8 +2298,7 @@ int dimx_train_spk_forward_backward(dimx_handle h, const float* params, float* g
         for (int b = 0; b < B; ++b)
             DIMX_REQUIRE(ids[b] >= 0 && ids[b] < rows, DIMX_ERR_ARG, "train_spk: speaker_ids[%d] = %d is outside [0, %d)", b, ids[b], rows);
     }
-    return spk_run(h, params, grads, v_emoca, v_audio, mask, z, speaker_ids, codebook_s, pe_s, B, T, loss_out, logits_out, idx_out, pred_out, ws,
-                   ws_bytes, st, nullptr);
+    return run(ws, ws_bytes, st, nullptr);
 }
 
 int dimx_op_lstm_layer_bwd(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
@@ -2741,11 +2334,8 @@ int dimx_op_lstm_layer_bwd(int dtype, const float* x, int B, int T, int In, int 
     float *P = nullptr, *G = nullptr;
     void* ws = nullptr;
     auto run = [&](Arena& ar, size_t* need) -> int {
-        Step s;
-        conv_step_init(s, nullptr, &plan, P, G, &ar, st, DIMX_F32, B, T);
-        s.pool_cap = (size_t)4 * (ceil_div(M, 32) + 1) * 1536 + 4096;
-        s.pool = s.f32(s.pool_cap);
-        s.pool_off = 0;
+        Step s(nullptr, &plan, P, G, &ar, st, DIMX_F32, B, T, T);
+        s.alloc_pool((size_t)4 * (ceil_div(M, 32) + 1) * 1536 + 4096);
         LstmLayerP Lr = L;
         DIMX_TRY(prep_lin(s, Lr.ih[0]));
         DIMX_TRY(prep_lin(s, Lr.ih[1]));

@@ -22,6 +22,12 @@ from . import lib as L
 
 
 class HipTrainer:
+    # what a step's trainer states about its entry points in libdimx_hip.so (include/dimx.h)
+    _ABI = "dimx_train"                          # <_ABI>_num_params / _param_info / _total report the arena layout
+    _SIZER = "dimx_train_workspace_bytes"        # the step's sizing function
+    _LOSS_FLOATS = 2                             # floats the step writes to loss_out
+    _UNGRAPHED = None                            # name of a step that is launched kernel by kernel (no graph_stats)
+
     def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=1.0, device=None):
         """AdamW defaults are torch.optim.AdamW's (the reference passes only lr, code/finetune_s2s_pretrain.py:119)."""
         self.model = model
@@ -38,7 +44,7 @@ class HipTrainer:
         self.exp_avg = torch.zeros(self.total, **kw)
         self.exp_avg_sq = torch.zeros(self.total, **kw)
         self._scratch = torch.zeros(1026, **kw)
-        self._loss = torch.zeros(2, **kw)
+        self._loss = torch.zeros(self._LOSS_FLOATS, **kw)
         self._ws, self._ws_bytes = None, 0
         self._stage = {}
         self.step_count = 0
@@ -47,17 +53,23 @@ class HipTrainer:
             import torch.distributed as dist
             dist.broadcast(self.params, 0)
 
+    def _abi_args(self):
+        """what the layout functions take after the handle"""
+        return ()
+
     def _arena_layout(self, h):
         """(floats per arena, [(name, offset, numel)]) of the step's flat arenas, as the library lays them out"""
-        n = self.lib.dimx_train_num_params(h)
+        args = (h,) + self._abi_args()
+        n = getattr(self.lib, self._ABI + "_num_params")(*args)
         if n <= 0:
-            L.check(n, "dimx_train_num_params")
+            L.check(n, self._ABI + "_num_params")
+        param_info = getattr(self.lib, self._ABI + "_param_info")
         layout = []
         for i in range(n):
             name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            L.check(self.lib.dimx_train_param_info(h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)), "train_param_info")
+            L.check(param_info(*args, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)), self._ABI + "_param_info")
             layout.append((name.value.decode(), int(off.value), int(numel.value)))
-        return int(self.lib.dimx_train_total(h)), layout
+        return int(getattr(self.lib, self._ABI + "_total")(*args)), layout
 
     # ------------------------------------------------------------------ arena <-> module
     def _named(self):
@@ -159,9 +171,10 @@ class HipTrainer:
 
     # ------------------------------------------------------------------ one step
     def _workspace(self, B, T):
-        need = int(self.lib.dimx_train_workspace_bytes(self.eng.h, B, T))
+        """(256-byte aligned workspace pointer, its bytes) for one step at (B, T); grown when the step needs more"""
+        need = int(getattr(self.lib, self._SIZER)(self.eng.h, B, T))
         if need == 0:
-            raise L.DimxError("dimx_train_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
+            raise L.DimxError("%s(B=%d, T=%d) = 0: %s" % (self._SIZER, B, T, (self.lib.dimx_last_error() or b"").decode()))
         if need > self._ws_bytes:
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
             self._ws_bytes = need
@@ -189,6 +202,8 @@ class HipTrainer:
 
     def graph_stats(self):
         """(steps replayed from the captured hipGraph, steps launched kernel by kernel, nodes of the captured graph)"""
+        if self._UNGRAPHED:
+            raise L.DimxError("the %s step is launched kernel by kernel (no captured graph)" % self._UNGRAPHED)
         out = (ctypes.c_int64 * 3)()
         L.check(self.lib.dimx_train_graph_stats(self.eng.h, ctypes.cast(out, ctypes.c_void_p)), "dimx_train_graph_stats")
         return int(out[0]), int(out[1]), int(out[2])
@@ -272,6 +287,9 @@ class LegacyHipTrainer(HipTrainer):
     flat arenas, clip + AdamW and gradient all-reduce as HipTrainer; ``dimx.train.legacy_loss`` (PyTorch autograd) is its checker
     (tests/test_gpu_train_legacy.py)."""
 
+    _SIZER = "dimx_train_legacy_workspace_bytes"
+    _LOSS_FLOATS = 4
+
     def forward_backward(self, v_speaker, v_listener, mask, listener_ids=None, return_logits=False):
         """-> (total loss = cross entropy + continuous loss, dict, pred [B,T-1,56][, logits]); gradients in ``self.grads``."""
         m = self.model
@@ -288,18 +306,10 @@ class LegacyHipTrainer(HipTrainer):
         nd = T if ids is not None else T - 1
         pred = torch.empty(B, T - 1, 56, dtype=torch.float32, device=self.device)
         logits = torch.empty(B, nd, 512, dtype=torch.float32, device=self.device) if return_logits else None
-        need = int(self.lib.dimx_train_legacy_workspace_bytes(self.eng.h, B, T))
-        if need == 0:
-            raise L.DimxError("dimx_train_legacy_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
-        if need > self._ws_bytes:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
-        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
-        if self._loss.numel() < 4:
-            self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+        ws, wsb = self._workspace(B, T)
         L.check(self.lib.dimx_train_legacy_forward_backward(
             self.eng.h, L.ptr(self.params), L.ptr(self.grads), L.ptr(x_speaker), L.ptr(z_l), L.ptr(v_l), L.ptr(m8), L.ptr(ids), L.ptr(book),
-            L.ptr(pe), B, T, L.ptr(self._loss), L.ptr(pred), L.ptr(logits), ws, self._ws.numel() - 256, L.stream_ptr(self.device)),
+            L.ptr(pe), B, T, L.ptr(self._loss), L.ptr(pred), L.ptr(logits), ws, wsb, L.stream_ptr(self.device)),
             "dimx_train_legacy_forward_backward")
         l_ce, l_cont = self._loss[0].clone(), self._loss[2].clone()
         out = (l_ce + l_cont, {"l_ce": l_ce, "l_cont": l_cont}, pred)
@@ -321,6 +331,8 @@ class SlmHipTrainer(HipTrainer):
     engine.  Same flat arenas, clip + AdamW and gradient all-reduce as HipTrainer; ``dimx.train.slm_loss`` (PyTorch autograd) is
     its checker (tests/test_gpu_train_slm.py)."""
 
+    _SIZER = "dimx_train_slm_workspace_bytes"
+    _LOSS_FLOATS = 10
     KEYS = ("l_ce_s", "l_ce_l", "l_cont_s", "l_cont_l", "nce", "c_acc")
 
     def _frozen(self):
@@ -353,19 +365,11 @@ class SlmHipTrainer(HipTrainer):
         v_s, v_l, v_a = f(v_speaker), f(v_listener), f(v_audio)
         m8, ms8, ml8, zs, zl = u8(mask), u8(mask_speaker), u8(mask_listener), i32(z_s), i32(z_l)
         book_s, book_l, pe_s, pe_l = self._frozen()
-        need = int(self.lib.dimx_train_slm_workspace_bytes(self.eng.h, B, T))
-        if need == 0:
-            raise L.DimxError("dimx_train_slm_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
-        if need > self._ws_bytes:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
-        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
-        if self._loss.numel() < 10:
-            self._loss = torch.zeros(10, dtype=torch.float32, device=self.device)
+        ws, wsb = self._workspace(B, T)
         L.check(self.lib.dimx_train_slm_forward_backward(
             self.eng.h, L.ptr(self.params), L.ptr(self.grads), L.ptr(v_s), L.ptr(v_l), L.ptr(v_a), L.ptr(m8), L.ptr(ms8), L.ptr(ml8),
-            L.ptr(zs), L.ptr(zl), L.ptr(book_s), L.ptr(book_l), L.ptr(pe_s), L.ptr(pe_l), B, T, L.ptr(self._loss), ws,
-            self._ws.numel() - 256, L.stream_ptr(self.device)), "dimx_train_slm_forward_backward")
+            L.ptr(zs), L.ptr(zl), L.ptr(book_s), L.ptr(book_l), L.ptr(pe_s), L.ptr(pe_l), B, T, L.ptr(self._loss), ws, wsb,
+            L.stream_ptr(self.device)), "dimx_train_slm_forward_backward")
         out = self._loss.clone()
         d = {"l_ce_s": out[0], "l_ce_l": out[2], "l_cont_s": out[4], "l_cont_l": out[6], "nce": out[8], "c_acc": out[9]}
         return out[0] + out[2] + out[4] + out[6] + out[8], d
@@ -388,6 +392,11 @@ class VqHipTrainer(HipTrainer):
     Same flat arenas, AdamW, optimiser-state import / export and gradient all-reduce as HipTrainer; ``dimx.train.vq_loss``
     (PyTorch autograd) is its checker (tests/test_gpu_train_vq.py)."""
 
+    _ABI = "dimx_train_vq"
+    _SIZER = "dimx_train_vq_workspace_bytes"
+    _LOSS_FLOATS = 4
+    _UNGRAPHED = "VQ-VAE"
+
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=0.0, dropout=0.1, seed=20260928,
                  beta=0.25, quant_loss_weight=1.0, device=None):
         self.which = int(getattr(model, "which", 1))
@@ -395,46 +404,27 @@ class VqHipTrainer(HipTrainer):
         self.dropout, self.seed = float(dropout), int(seed)
         self.beta, self.quant_loss_weight = float(beta), float(quant_loss_weight)
         super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip=clip, device=device)
-        self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
 
-    def _arena_layout(self, h):
-        n = self.lib.dimx_train_vq_num_params(h, self.which)
-        if n <= 0:
-            L.check(n, "dimx_train_vq_num_params")
-        layout = []
-        for i in range(n):
-            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            L.check(self.lib.dimx_train_vq_param_info(h, self.which, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)),
-                    "dimx_train_vq_param_info")
-            layout.append((name.value.decode(), int(off.value), int(numel.value)))
-        return int(self.lib.dimx_train_vq_total(h, self.which)), layout
+    def _abi_args(self):
+        return (self.which,)
 
     def _named(self):
         # the library names the slot's tensors with their prefix (the handle holds both VQ-VAE slots); the module's are unprefixed
         return {self.prefix + n: p for n, p in self.model.named_parameters()}
-
-    def graph_stats(self):
-        raise L.DimxError("the VQ-VAE step is launched kernel by kernel (no captured graph)")
 
     def forward_backward(self, x, step=None, dropout=None):
         """x [B,T,56] -> ({loss, rec_loss, quant_loss, perplexity} device scalars, pred [B,T,56], idx [B*T] int32); gradients in
         ``self.grads``.  step: the dropout mask's step counter (default: optimiser steps taken so far); dropout: override p."""
         x = x.to(self.device, torch.float32).contiguous()
         B, T, _ = x.shape
-        need = int(self.lib.dimx_train_vq_workspace_bytes(self.eng.h, B, T))
-        if need == 0:
-            raise L.DimxError("dimx_train_vq_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
-        if need > self._ws_bytes:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
-        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
+        ws, wsb = self._workspace(B, T)
         pred = torch.empty(B, T, x.shape[-1], dtype=torch.float32, device=self.device)
         idx = torch.empty(B * T, dtype=torch.int32, device=self.device)
         p = self.dropout if dropout is None else float(dropout)
         L.check(self.lib.dimx_train_vq_forward_backward(
             self.eng.h, self.which, L.ptr(self.params), L.ptr(self.grads), L.ptr(x), B, T, self.beta, self.quant_loss_weight, p,
-            self.seed, int(self.step_count if step is None else step), L.ptr(self._loss), L.ptr(pred), L.ptr(idx), ws,
-            self._ws.numel() - 256, L.stream_ptr(self.device)), "dimx_train_vq_forward_backward")
+            self.seed, int(self.step_count if step is None else step), L.ptr(self._loss), L.ptr(pred), L.ptr(idx), ws, wsb,
+            L.stream_ptr(self.device)), "dimx_train_vq_forward_backward")
         out = self._loss.clone()
         d = {"loss": out[0], "rec_loss": out[1], "quant_loss": out[2], "perplexity": out[3]}
         return d, pred, idx
@@ -477,25 +467,14 @@ class ConverterHipTrainer(HipTrainer):
       * the adjoint recurrence runs on the no-communication safe path on every device (the weight-stationary group kernel
         exists for the forward only); ``flags`` bit 0 puts the forward on that path too."""
 
+    _ABI = "dimx_train_conv"
+    _SIZER = "dimx_train_conv_workspace_bytes"
+    _LOSS_FLOATS = 4
+    _UNGRAPHED = "converter"
+
     def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=0.0, device=None):
         super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip=clip, device=device)
-        self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._vw = {}
-
-    def _arena_layout(self, h):
-        n = self.lib.dimx_train_conv_num_params(h)
-        if n <= 0:
-            L.check(n, "dimx_train_conv_num_params")
-        layout = []
-        for i in range(n):
-            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            L.check(self.lib.dimx_train_conv_param_info(h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)),
-                    "dimx_train_conv_param_info")
-            layout.append((name.value.decode(), int(off.value), int(numel.value)))
-        return int(self.lib.dimx_train_conv_total(h)), layout
-
-    def graph_stats(self):
-        raise L.DimxError("the converter step is launched kernel by kernel (no captured graph)")
 
     def vertex_weights(self, mouth_map):
         """(the [V/3] f32 multiplicity vector of ``mouth_map`` on the device, len(mouth_map)); cached per map"""
@@ -522,17 +501,11 @@ class ConverterHipTrainer(HipTrainer):
         target = vertices.to(self.device, torch.float32).reshape(B, T, V).contiguous()
         templ = template.to(self.device, torch.float32).reshape(B, V).contiguous() if template is not None else None
         vw, n_mouth = (None, 0) if mouth_map is None else self.vertex_weights(mouth_map)
-        need = int(self.lib.dimx_train_conv_workspace_bytes(self.eng.h, B, T))
-        if need == 0:
-            raise L.DimxError("dimx_train_conv_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
-        if need > self._ws_bytes:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
-        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
+        ws, wsb = self._workspace(B, T)
         mesh = torch.empty(B, T, V, dtype=torch.float32, device=self.device)
         L.check(self.lib.dimx_train_conv_forward_backward(
             self.eng.h, L.ptr(self.params), L.ptr(self.grads) if with_grads else None, L.ptr(motion), L.ptr(templ), L.ptr(target),
-            L.ptr(vw), n_mouth, B, T, int(flags), L.ptr(self._loss), L.ptr(mesh), ws, self._ws.numel() - 256,
+            L.ptr(vw), n_mouth, B, T, int(flags), L.ptr(self._loss), L.ptr(mesh), ws, wsb,
             L.stream_ptr(self.device)), "dimx_train_conv_forward_backward")
         out = self._loss.clone()
         return {"loss": out[0], "mse": out[1], "mouth": out[2]}, mesh
@@ -587,31 +560,19 @@ class SpeakerHipTrainer(HipTrainer):
       * the reference's ``evaluate_epoch_biwi`` passes ``v_speaker_emoca=None`` and fails inside ``forward_vq``; it is not
         built (``SpeakerSLMFT.forward`` raises ``ValueError`` for None) and the driver never calls it."""
 
+    _ABI = "dimx_train_spk"
+    _SIZER = "dimx_train_spk_workspace_bytes"
+    _LOSS_FLOATS = 4
+    _UNGRAPHED = "DIM-Speaker"
     _MODEL_MAP = object()
 
     def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=1.0, mouth_map=_MODEL_MAP, device=None):
         super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip=clip, device=device)
-        self._loss = torch.zeros(4, dtype=torch.float32, device=self.device)
         mm = getattr(model, "mouth_map", None) if mouth_map is SpeakerHipTrainer._MODEL_MAP else mouth_map
         self.mouth_map = None if mm is None else [int(i) for i in mm]
         if self.mouth_map is not None:
             assert all(0 <= i < model.mesh_dim // 3 for i in self.mouth_map), "mouth_map holds vertex indices in [0, mesh_dim / 3)"
         self.last_out = {}
-
-    def _arena_layout(self, h):
-        n = self.lib.dimx_train_spk_num_params(h)
-        if n <= 0:
-            L.check(n, "dimx_train_spk_num_params")
-        layout = []
-        for i in range(n):
-            name, off, numel = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
-            L.check(self.lib.dimx_train_spk_param_info(h, i, ctypes.byref(name), ctypes.byref(off), ctypes.byref(numel)),
-                    "dimx_train_spk_param_info")
-            layout.append((name.value.decode(), int(off.value), int(numel.value)))
-        return int(self.lib.dimx_train_spk_total(h)), layout
-
-    def graph_stats(self):
-        raise L.DimxError("the DIM-Speaker step is launched kernel by kernel (no captured graph)")
 
     def _mouth(self, pred, vertices, template):
         """the reported mouth term of ``SpeakerSLMFT.forward``: mse over the map's vertices of the mesh head's output (no graph)"""
@@ -642,20 +603,14 @@ class SpeakerHipTrainer(HipTrainer):
         z32 = z.to(self.device).to(torch.int32).contiguous()
         ids = speaker_ids.to(self.device).to(torch.int32).contiguous() if speaker_ids is not None else None
         book, pe = f(m.speaker_vq.quantize.embedding.weight), f(m.speaker_vq.decoder.decoder_pos_embedding.pe)
-        need = int(self.lib.dimx_train_spk_workspace_bytes(self.eng.h, B, T))
-        if need == 0:
-            raise L.DimxError("dimx_train_spk_workspace_bytes(B=%d, T=%d) = 0: %s" % (B, T, (self.lib.dimx_last_error() or b"").decode()))
-        if need > self._ws_bytes:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = need
-        ws = ctypes.c_void_p((self._ws.data_ptr() + 255) // 256 * 256)
+        ws, wsb = self._workspace(B, T)
         kw = dict(device=self.device)
         logits = torch.empty(B, T - 1, 512, dtype=torch.float32, **kw) if return_logits else None
         idx = torch.empty(B * (T - 1), dtype=torch.int32, **kw)
         pred = torch.empty(B, T - 1, 56, dtype=torch.float32, **kw)
         L.check(self.lib.dimx_train_spk_forward_backward(
             self.eng.h, L.ptr(self.params), L.ptr(self.grads), L.ptr(v_e), L.ptr(v_a), L.ptr(m8), L.ptr(z32), L.ptr(ids), L.ptr(book),
-            L.ptr(pe), B, T, L.ptr(self._loss), L.ptr(logits), L.ptr(idx), L.ptr(pred), ws, self._ws.numel() - 256,
+            L.ptr(pe), B, T, L.ptr(self._loss), L.ptr(logits), L.ptr(idx), L.ptr(pred), ws, wsb,
             L.stream_ptr(self.device)), "dimx_train_spk_forward_backward")
         out = self._loss.clone()
         l_ce, l_emoca = out[0], out[2]
