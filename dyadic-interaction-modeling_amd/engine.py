@@ -742,3 +742,67 @@ def op_mesh_metrics(y_true, y_pred, lens, template, mouth_map, upper_map, want_f
                                          ctypes.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(dev)), "dimx_op_mesh_metrics")
     _MM_LENS[key] = lens_c
     return (clip, frames, status) if return_status else (clip, frames)
+
+
+# the column windows of print_metrics / print_metrics_full (reference code/mymetrics.py:7-120) as (xc0, xF, yc0, yF): the operand
+# rows are [x[:, xc0:xc0+xF] | y[:, yc0:yc0+yF]]
+LISTENER_WINDOWS = (("fid_pose", (0, 0, 0, 6)), ("fid_exp", (0, 0, 6, 50)), ("pfid_pose", (0, 6, 0, 6)), ("pfid_exp", (6, 50, 6, 50)),
+                    ("fid", (0, 0, 0, 56)), ("pfid", (0, 56, 0, 56)))
+LM_ROW = 133     # DIMX_LM_ROW of include/dimx.h
+_LM_WS = {}      # device index -> uint8 workspace of op_listener_metrics (grown on demand, never shrunk)
+
+
+def op_listener_metrics(y_true, y_pred, x, lens, windows=tuple(w for _, w in LISTENER_WINDOWS)):
+    """The listener evaluation metrics per clip (dimx_op_listener_metrics, csrc/listener_metrics.hip): y_true, y_pred [B, L, >=56],
+    x [B, L', >=56] (the speaker motion) f32 on one GPU, lens[b] = valid frames of clip b, windows = rows (xc0, xF, yc0, yF)
+    -> (fd [B, n_win] f64, moments [B, 133] f64; the row layout is include/dimx.h's).  Only the first min(L, L', ...) frames of
+    each tensor can count.  The clip and frame strides are taken from the tensors (views such as ``tgt[:, 1:]`` are passed as they
+    are); only a feature stride other than 1 is copied.  Asynchronous on the current stream.  CPU tensors raise: there is no CPU
+    fallback (dimx.mymetrics.compute_metrics is the host form)."""
+    ts = (y_true, y_pred, x)
+    if not all(torch.is_tensor(t) and t.is_cuda for t in ts):
+        raise L.DimxError("op_listener_metrics runs on the GPU only: y_true / y_pred / x must be CUDA tensors (no CPU fallback)")
+    if any(t.dim() != 3 or t.shape[0] != y_pred.shape[0] or t.device != y_pred.device for t in ts) or y_true.shape[2] != y_pred.shape[2]:
+        raise L.DimxError("op_listener_metrics: y_true, y_pred [B, L, W] and x [B, L, Wx] on one device expected, got %s, %s and %s"
+                          % tuple(tuple(t.shape) for t in ts))
+    lib = L.load()
+    dev = y_pred.device
+    B, Ln = int(y_pred.shape[0]), int(min(t.shape[1] for t in ts))
+    y_true, y_pred, x = [t if t.dtype == torch.float32 else t.float() for t in ts]
+    y_true, y_pred, x = [t if t.stride(2) == 1 else t.contiguous() for t in (y_true, y_pred, x)]
+    win = [tuple(int(v) for v in w) for w in windows]
+    if any(len(w) != 4 for w in win):
+        raise L.DimxError("op_listener_metrics: windows are rows (xc0, xF, yc0, yF), got %r" % (windows,))
+    n_win = len(win)
+    win_c = (ctypes.c_int32 * (4 * max(n_win, 1)))(*[v for w in win for v in w])
+    if torch.is_tensor(lens):
+        lens_d = lens.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens_d = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(dev)
+    if lens_d.numel() != B:
+        raise L.DimxError("op_listener_metrics: %d lens for %d clips" % (lens_d.numel(), B))
+    fd = torch.empty(B, n_win, dtype=torch.float64, device=dev)
+    mom = torch.empty(B, LM_ROW, dtype=torch.float64, device=dev)
+    need = int(lib.dimx_op_listener_metrics_ws_bytes(B, n_win, max([w[1] + w[3] for w in win] or [0])))
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    ws = _LM_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _LM_WS[key] = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_listener_metrics(ctypes.c_void_p(y_true.data_ptr()), y_true.stride(0), y_true.stride(1),
+                                             ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1),
+                                             ctypes.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), L.ptr(lens_d), B, Ln,
+                                             int(y_pred.shape[2]), int(x.shape[2]), win_c, n_win, L.ptr(fd), L.ptr(mom),
+                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(dev)), "dimx_op_listener_metrics")
+    return fd, mom
+
+
+def listener_metrics_sweeps(device, B, n_win, F):
+    """Jacobi sweeps of the last op_listener_metrics call of these sizes on ``device`` (F = its widest window), read from its
+    workspace: (target factorisations, candidate problems), each int32 [n_win, B] (include/dimx.h)."""
+    lib = L.load()
+    need = int(lib.dimx_op_listener_metrics_ws_bytes(B, n_win, F))
+    device = torch.device(device)
+    ws = _LM_WS[device.index if device.index is not None else torch.cuda.current_device()]
+    sw = ws[need - 8 * B * n_win:need].view(torch.int32).reshape(2, n_win, B)
+    return sw[0].clone(), sw[1].clone()

@@ -161,6 +161,10 @@ SIGNATURES = {
     "dimx_op_mesh_metrics": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long,
                                      POINTER(c_int32), c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),
+    "dimx_op_listener_metrics_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dimx_op_listener_metrics": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long,
+                                         ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
 }

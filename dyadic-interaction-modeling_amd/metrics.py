@@ -143,3 +143,131 @@ class BiwiMeshMetrics:
         if status != 0:
             raise RuntimeError("BiwiMeshMetrics: a map index outside the mesh reached the kernel and was skipped")
         return s_max / frames, s_diff / clips
+
+
+class ListenerMetrics:
+    """Device-side accumulator of the listener metrics (reference print_metrics / print_metrics_full, code/mymetrics.py:7-120) over
+    the batches of an evaluation epoch: ``update`` runs dimx_op_listener_metrics (csrc/listener_metrics.hip, float64) on the
+    tensors where they lie and merges its per-clip rows into float64 state on that GPU -- nothing crosses to the host and nothing
+    is synchronised; ``result`` does the one readback.  Clips count in update order: the reference's ``sts`` runs over the
+    concatenation of all clips, so the step from a clip's last frame to the next clip's first frame is part of it, across batches
+    too.  SID stays on the host (``print``).  CPU tensors raise lib.DimxError (mymetrics.compute_metrics is the host form).
+    Every clip of every batch counts as a clip, as every list entry does in the reference: a clip with fewer than 2 valid frames has
+    no covariance, its distances are NaN (the reference's np.cov gives NaN there too) and ``result`` raises ValueError rather than
+    return distance means that one such clip has turned into NaN; an empty clip also adds nothing to the MSE means' numerators
+    while it counts in their denominator.  Pass only clips with at least 2 valid frames."""
+
+    GROUPS = (("pose", 6), ("exp", 50))
+
+    def __init__(self):
+        from .engine import LISTENER_WINDOWS
+        self.windows = LISTENER_WINDOWS
+        self._s = None
+
+    @staticmethod
+    def _merge(na, a, nb, b):
+        """Chan's merge of (mean gt, m2 gt, mean pred, m2 pred, mean x, m2 x, c(gt,x), c(pred,x)) over na and nb elements"""
+        import torch
+        n = na + nb
+        f = na * nb / n.clamp(min=1.0)
+        w = nb / n.clamp(min=1.0)
+        dg, dp, dx = b[0] - a[0], b[2] - a[2], b[4] - a[4]
+        return torch.stack([a[0] + dg * w, a[1] + b[1] + dg * dg * f, a[2] + dp * w, a[3] + b[3] + dp * dp * f,
+                            a[4] + dx * w, a[5] + b[5] + dx * dx * f, a[6] + b[6] + dg * dx * f, a[7] + b[7] + dp * dx * f])
+
+    def update(self, y_true, y_pred, x, lens):
+        """y_true, y_pred [B, L, 56], x [B, L', >=56] on one GPU, lens[b] = valid frames of clip b (a sequence or a tensor)."""
+        import torch
+        from .engine import op_listener_metrics
+        fd, mom = op_listener_metrics(y_true, y_pred, x, lens, windows=tuple(w for _, w in self.windows))
+        dev, B = mom.device, mom.shape[0]
+        n = mom[:, 0]                                              # [B] valid frames
+        s = {"clips": (self._s["clips"] if self._s else 0) + B, "fd": fd.sum(0)}
+        d_first, d_last = mom[:, 21:77], mom[:, 77:133]
+        # the step from the previous non-empty clip's last row of d = gt - pred to this clip's first (empty clips are transparent)
+        rows = torch.cat([self._s["last"][None] if self._s else torch.zeros(1, 56, dtype=torch.float64, device=dev), d_last])
+        valid = torch.cat([self._s["has_last"][None] if self._s else torch.zeros(1, dtype=torch.bool, device=dev), n > 0])
+        idx = torch.where(valid, torch.arange(B + 1, device=dev), torch.full((B + 1,), -1, device=dev)).cummax(0)[0]
+        prev = idx[:-1]                                            # per clip: index into rows of the last non-empty clip before it
+        step = (d_first - rows[prev.clamp(min=0)]) ** 2
+        step = torch.where(((prev >= 0) & (n > 0))[:, None], step, torch.zeros_like(step))
+        s["last"], s["has_last"] = rows[idx[-1].clamp(min=0)], idx[-1] >= 0
+        nn = n.clamp(min=1.0)
+        mse, sts_, stat, cnt = [], [], [], []
+        for g, (name, cols) in enumerate(self.GROUPS):
+            o = 1 + 10 * g
+            lo = 0 if g == 0 else 6
+            mse.append((mom[:, o] / (nn * cols)).sum())
+            sts_.append(mom[:, o + 9].sum() + step[:, lo:lo + cols].sum())
+            ne = n * cols                                          # elements per clip
+            tot = ne.sum()
+            t1 = tot.clamp(min=1.0)
+            mg, mp, mx = [(ne * mom[:, o + k]).sum() / t1 for k in (1, 3, 5)]
+            dg, dp, dx = mom[:, o + 1] - mg, mom[:, o + 3] - mp, mom[:, o + 5] - mx
+            stat.append(torch.stack([mg, mom[:, o + 2].sum() + (ne * dg * dg).sum(), mp, mom[:, o + 4].sum() + (ne * dp * dp).sum(),
+                                     mx, mom[:, o + 6].sum() + (ne * dx * dx).sum(), mom[:, o + 7].sum() + (ne * dg * dx).sum(),
+                                     mom[:, o + 8].sum() + (ne * dp * dx).sum()]))
+            cnt.append(tot)
+        mse.append(((mom[:, 1] + mom[:, 11]) / (nn * 56)).sum())
+        s["mse"], s["sts"], s["cnt"] = torch.stack(mse), torch.stack(sts_), torch.stack(cnt)
+        if self._s is None:
+            s["stat"] = stat
+        else:
+            if self._s["fd"].device != dev:
+                raise ValueError("ListenerMetrics: updates from %s and %s" % (self._s["fd"].device, dev))
+            for k in ("fd", "mse", "sts"):
+                s[k] = self._s[k] + s[k]
+            s["stat"] = [self._merge(self._s["cnt"][g], self._s["stat"][g], s["cnt"][g], stat[g]) for g in range(2)]
+            s["cnt"] = self._s["cnt"] + s["cnt"]
+        self._s = s
+        return self
+
+    def result(self):
+        """-> the dict of mymetrics.compute_metrics(with_sid=False) merged with mymetrics.compute_metrics_full: floats, and
+        (gt, pred) pairs for the var_* entries.  The one readback."""
+        import torch
+        if self._s is None:
+            raise ValueError("ListenerMetrics.result() before any update()")
+        s = self._s
+        flat = torch.cat([s["fd"], s["mse"], s["sts"], s["cnt"], s["stat"][0], s["stat"][1]]).tolist()
+        nw = len(self.windows)
+        clips = float(s["clips"])
+        fd, mse, sts_, cnt = flat[:nw], flat[nw:nw + 3], flat[nw + 3:nw + 5], flat[nw + 5:nw + 7]
+        st = [flat[nw + 7:nw + 15], flat[nw + 15:nw + 23]]
+        if any(v != v for v in fd):
+            raise ValueError("ListenerMetrics: a clip with fewer than 2 valid frames was passed to update(): its Frechet distances "
+                             "are NaN and so is every distance mean of the epoch")
+        out = {name: v / clips for (name, _), v in zip(self.windows, fd)}
+        out["mse_pose"], out["mse_exp"], out["mse"] = mse[0] / clips, mse[1] / clips, mse[2] / clips
+        for g, (name, _) in enumerate(self.GROUPS):
+            mg, m2g, mp, m2p, mx, m2x, cgx, cpx = st[g]
+            out["var_" + name] = (m2g / cnt[g], m2p / cnt[g])
+            out["rpcc_" + name] = float(abs(cgx / np.sqrt(m2g * m2x) - cpx / np.sqrt(m2p * m2x)))
+            out["sts_" + name] = float(np.sqrt(sts_[g] / 0.1))
+        # all 56 columns: Chan's merge of the two groups
+        n, f = cnt[0] + cnt[1], cnt[0] * cnt[1] / (cnt[0] + cnt[1])
+        out["var"] = tuple((st[0][k] + st[1][k] + (st[1][k - 1] - st[0][k - 1]) ** 2 * f) / n for k in (1, 3))
+        return out
+
+    def print(self, y_true=None, y_pred=None):
+        """The lines of print_metrics and then print_metrics_full, in their order and format.  The two SID lines need the per-clip
+        lists (host KMeans, mymetrics.calcuate_sid) and are left out without them.  Returns the dict of ``result``."""
+        from .mymetrics import calcuate_sid
+        m = self.result()
+        for k in ("fid_pose", "fid_exp", "pfid_pose", "pfid_exp", "mse_pose", "mse_exp"):
+            print(k + ": ", m[k])
+        if y_true is not None and y_pred is not None:
+            for t in ("pose", "exp"):
+                m["sid_" + t] = (calcuate_sid(y_true, y_pred, t), calcuate_sid(y_true, y_true, t))
+                print("sid_%s: " % t, *m["sid_" + t])
+        print("var_pose: ", *m["var_pose"])
+        print("var_exp: ", *m["var_exp"])
+        print("rpcc pose: ", m["rpcc_pose"])
+        print("rpcc exp: ", m["rpcc_exp"])
+        print("sts pose: ", m["sts_pose"])
+        print("sts exp: ", m["sts_exp"])
+        print("fid: ", m["fid"])
+        print("pfid: ", m["pfid"])
+        print("mse: ", m["mse"])
+        print("var: ", *m["var"])
+        return m

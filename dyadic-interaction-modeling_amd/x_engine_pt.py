@@ -135,12 +135,14 @@ def _select_device(y_true, y_preds, lens, world, device, total=None):
     return best
 
 
-def _select_hip(y_true, y_preds, lens, world, device, total=None):
+def _select_hip(y_true, y_preds, lens, world, device, total=None, metrics=None, x=None):
     """fd_backend="hip": distances, winner and gather in the HIP library (dimx.engine.op_fd_select, csrc/fd_select.hip) on the
     stream the generation ran on; only the winners' frames and the ok flags cross to the host.  A clip without a finite distance
     keeps None, as in _select_device."""
     from .engine import op_fd_select
     _, _, ok, best = op_fd_select(y_true, y_preds, lens)
+    if metrics is not None:      # the winners where they lie: enqueued behind the selection, nothing is synchronised
+        metrics.update(y_true, best, x, lens)
     ok = ok.cpu().tolist()
     chosen = best.cpu().numpy()
     best = [chosen[j][:lens[j]].copy() if ok[j] else None for j in range(len(lens))]
@@ -171,7 +173,7 @@ def _select(pending, skip_degenerate, world, device):
 
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
-                        fd_backend="reference", **forward_kw):
+                        fd_backend="reference", metrics=None, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -194,8 +196,22 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     (dimx.metrics.frechet_distances_torch: eigenvalues instead of scipy's sqrtm, so the last digits differ and rank-deficient
     clips do not raise) and brings only the winners to the host.  ``fd_backend="hip"`` follows the same path with the distances,
     the winner and the gather of the winning sequences all in the project's own kernels (dimx.engine.op_fd_select, csrc/fd_select.hip;
-    GPU only: a CPU device raises lib.DimxError)."""
+    GPU only: a CPU device raises lib.DimxError).
+
+    ``metrics``: a dimx.metrics.ListenerMetrics that is updated per batch with the device-resident winners, ``tgt[:, 1:]``, the
+    speaker motion and the lens right after the selection (dimx_op_listener_metrics, csrc/listener_metrics.hip), so that
+    print_metrics / print_metrics_full need no host pass over the returned lists.  It needs ``fd_backend="hip"``, a GPU and one
+    process; anything else raises.  The default None leaves every path as it is."""
     assert fd_backend in ("reference", "device", "hip")
+    if metrics is not None:
+        if fd_backend != "hip":
+            raise ValueError("evaluate_test_epoch(metrics=...) needs fd_backend='hip' (got %r): the accumulator reads the winners "
+                             "the HIP selection leaves on the device" % (fd_backend,))
+        if torch.device(device).type != "cuda":
+            raise L.DimxError("evaluate_test_epoch(metrics=...) runs on a ROCm GPU only (device %s): there is no CPU fallback; "
+                              "dimx.mymetrics.print_metrics is the host form" % (device,))
+        if ddist.world_size() > 1:
+            raise ValueError("evaluate_test_epoch(metrics=...) accumulates on one process; world_size is %d" % ddist.world_size())
     if fd_backend == "hip" and torch.device(device).type != "cuda":
         raise L.DimxError("evaluate_test_epoch(fd_backend='hip') runs on a ROCm GPU only (device %s): there is no CPU fallback; "
                           "fd_backend='reference' and 'device' run there" % (device,))
@@ -234,8 +250,9 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
                     if pending is not None:
                         y_preds_all.extend(_select(pending, skip_degenerate, world, device))
                         pending = None
+                    extra = dict(metrics=metrics, x=src_s_v[lo:hi]) if metrics is not None else {}
                     y_preds_all.extend(select_on_device(tgt[lo:hi, 1:], y_preds, [src_len[lo + j] - 1 for j in range(nl)], world,
-                                                        device, B))
+                                                        device, B, **extra))
                     continue
                 yp_all = y_preds.cpu().numpy()
                 samples = [yp_all[:, s_i] for s_i in range(beam_size)]

@@ -575,6 +575,42 @@ int dimx_op_mesh_metrics(const float* y_true, long yt_clip_stride, long yt_frame
                          long yp_frame_stride, const float* templ, long templ_clip_stride, const int32_t* lens, int B, int L, int n_vert,
                          const int32_t* mouth, int n_mouth, const int32_t* upper, int n_upper, double* clip_out, double* frame_max,
                          int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The listener evaluation metrics, print_metrics / print_metrics_full (csrc/listener_metrics.hip; reference code/mymetrics.py:7-120
+ * around code/metrics/eval_utils.py:6-46,85-91): per clip the Frechet distances of up to 8 column windows and the moments every
+ * other printed scalar is made of, as float64 values of the reference's formulas on the f32 inputs.
+ *   y_true / y_pred f32 [B, L, Wy], x f32 [B, L, Wx] (the speaker motion), Wy, Wx >= 56: clip b, frame t of a tensor starts at
+ *       base + b*clip_stride + t*frame_stride (elements, taken as long; feature stride 1: views such as tgt[:, 1:] are passed as
+ *       they are)
+ *   lens int32 [B] in device memory: valid frames per clip (clamped to 0..L); frames t >= lens[b] are never read
+ *   windows int32 [n_win][4] in HOST memory, 1 <= n_win <= 8, rows (xc0, xF, yc0, yF): the operand rows of window w are
+ *       [x[:, xc0:xc0+xF] | y[:, yc0:yc0+yF]] with y = y_true on the target side and y = y_pred on the candidate side;
+ *       F = xF + yF, 1 <= F <= 112, xF = 0 is the plain distance, xc0 + xF <= Wx, yc0 + yF <= Wy.  The table is read before the
+ *       call returns.
+ *   fd f64 [B, n_win] = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2), mean and unbiased covariance over the valid frames,
+ *       float64 throughout, tr sqrt(S1 S2) = sum of the square roots of the r = min(F, n - 1) largest eigenvalues of A^T S2 A
+ *       with S1 = A A^T (one-sided Jacobi, as dimx_op_fd_select); NaN for a clip with fewer than 2 valid frames
+ *   moments f64 [B, DIMX_LM_ROW]: row b holds, with d = gt - pred and the groups g = 0 (pose, columns 0:6) and g = 1 (exp,
+ *       columns 6:56), every sum running over the n * cols elements of the group's valid frames:
+ *         [0]               n, the valid frames
+ *         [1 + 10 g + 0]    sum d^2
+ *         [1 + 10 g + 1, 2] mean of gt, sum (gt - mean)^2         [.. + 3, 4] the same of pred        [.. + 5, 6] the same of x
+ *         [1 + 10 g + 7]    sum (gt - mean_gt)(x - mean_x)        [.. + 8]    sum (pred - mean_pred)(x - mean_x)
+ *         [1 + 10 g + 9]    sum over t >= 1 of ((gt_t - gt_{t-1}) - (pred_t - pred_{t-1}))^2   (the STS sum inside the clip)
+ *         [21 .. 77)        d of the first valid frame, 56 columns    [77 .. 133) d of the last valid frame
+ *       Two passes (the means first, then the centred sums): no E[v^2] - E[v]^2.  A clip with n = 0 leaves a row of zeros.
+ *   workspace: dimx_op_listener_metrics_ws_bytes(B, n_win, F) bytes with F the largest window, 8-byte aligned.  After the call
+ *       its last 2 * B * n_win int32 hold the Jacobi sweeps of each (window, clip): the target factorisations [n_win][B], then
+ *       the candidate problems [n_win][B] (diagnostic; the loop is bounded at 30).
+ * Asynchronous on `stream`: two launches, no allocation, no host synchronisation, no atomics, a fixed summation order
+ * (bit-reproducible).  DIMX_ERR_ARG for a null operand, B or L < 1, n_win outside 1..8, Wy or Wx < 56, an F outside 1..112, a
+ * window that leaves its row, a negative stride, a short or misaligned workspace; nothing is enqueued then.  _ws_bytes returns 0
+ * for B < 1, n_win outside 1..8 and F outside 1..112. */
+#define DIMX_LM_ROW 133
+size_t dimx_op_listener_metrics_ws_bytes(int B, int n_win, int F);
+int dimx_op_listener_metrics(const float* y_true, long yt_clip_stride, long yt_frame_stride, const float* y_pred, long yp_clip_stride,
+                             long yp_frame_stride, const float* x, long x_clip_stride, long x_frame_stride, const int32_t* lens, int B,
+                             int L, int Wy, int Wx, const int32_t* windows, int n_win, double* fd, double* moments, void* workspace,
+                             size_t workspace_bytes, void* stream);
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
