@@ -806,3 +806,88 @@ def listener_metrics_sweeps(device, B, n_win, F):
     ws = _LM_WS[device.index if device.index is not None else torch.cuda.current_device()]
     sw = ws[need - 8 * B * n_win:need].view(torch.int32).reshape(2, n_win, B)
     return sw[0].clone(), sw[1].clone()
+
+
+# ---------------------------------------------------------------- SID: float64 KMeans fit + assign (csrc/kmeans_sid.hip)
+_KM_WS = {}      # device index -> uint8 workspace of op_kmeans_fit (grown on demand, never shrunk)
+
+
+def _km_frames(frames, cols, what):
+    if not (torch.is_tensor(frames) and frames.is_cuda):
+        raise L.DimxError("%s runs on the GPU only: frames must be a CUDA tensor (no CPU fallback; dimx.mymetrics.sid_f64 is the "
+                          "host form)" % what)
+    if frames.dim() != 2:
+        raise L.DimxError("%s: frames [N, W] expected, got %s" % (what, tuple(frames.shape)))
+    frames = frames if frames.dtype == torch.float32 else frames.float()
+    if frames.stride(1) != 1 or (frames.shape[0] > 1 and frames.stride(0) < frames.shape[1]):
+        frames = frames.contiguous()
+    c0 = int(cols[0])
+    c1 = int(frames.shape[1]) if cols[1] is None else int(cols[1])
+    return frames, c0, c1 - c0
+
+
+def kmeans_empty_cluster_error(status, what="op_kmeans_fit"):
+    return L.DimxError("%s: a cluster was left without a frame at Lloyd iteration %d; scikit-learn relocates such a centre and the "
+                       "operator does not restate that -- the host form is dimx.mymetrics.calcuate_sid" % (what, int(status)))
+
+
+def op_kmeans_fit(frames, k, cols=(0, None), seed=0, tol=1e-4, max_iter=300, want_labels=False, check=True):
+    """KMeans(k, random_state=seed, n_init='auto').fit of scikit-learn on float64 copies of the f32 frames (dimx_op_kmeans_fit,
+    csrc/kmeans_sid.hip; the definition is dimx.mymetrics.kmeans_fit_f64): frames [N, W] f32 on a GPU (the row stride is taken from
+    the tensor), cols = (c0, c1) the columns that enter -> (centers [k, c1 - c0] f64 on that GPU, n_iter).  The random numbers of the
+    initialisation are drawn here (mymetrics.kmeans_draws) and uploaded; the fit itself is enqueued as a whole on the current
+    stream.  ``check=True`` reads the status word back (one synchronisation) and raises DimxError when a cluster was left empty;
+    ``check=False`` returns (centers, info) with info = int32 [2] {n_iter, status} on the GPU and synchronises nothing.
+    ``want_labels=True`` appends the int32 [N] assignment the returned means were taken over.  CPU tensors raise: no CPU fallback."""
+    from .mymetrics import kmeans_draws
+    frames, c0, F = _km_frames(frames, cols, "op_kmeans_fit")
+    lib = L.load()
+    dev = frames.device
+    N, W, k = int(frames.shape[0]), int(frames.shape[1]), int(k)
+    if k < 1 or N < k:
+        raise L.DimxError("op_kmeans_fit: %d frames for %d clusters" % (N, k))
+    first, U = kmeans_draws(N, k, seed)
+    U_d = torch.from_numpy(np.ascontiguousarray(U)).to(dev) if U.size else None
+    centers = torch.empty(k, max(F, 0), dtype=torch.float64, device=dev)
+    info = torch.zeros(2, dtype=torch.int32, device=dev)
+    labels = torch.empty(N, dtype=torch.int32, device=dev) if want_labels else None
+    need = int(lib.dimx_op_kmeans_fit_ws_bytes(N, k, F))
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    ws = _KM_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _KM_WS[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_kmeans_fit(ctypes.c_void_p(frames.data_ptr()), frames.stride(0) if N > 1 else W, N, W, c0, F, k, first,
+                                       L.ptr(U_d), int(U.shape[1]), float(tol), int(max_iter), L.ptr(centers),
+                                       ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(info.data_ptr() + 4), L.ptr(labels),
+                                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(dev)), "dimx_op_kmeans_fit")
+    if check:
+        n_iter, status = info.tolist()
+        if status:
+            raise kmeans_empty_cluster_error(status)
+        info = n_iter
+    return (centers, info, labels) if want_labels else (centers, info)
+
+
+def op_sid_assign(frames, centers, cols=(0, None), want_labels=False):
+    """Nearest centre (the first index on ties) of every frame, the histogram and its entropy (dimx_op_sid_assign,
+    csrc/kmeans_sid.hip): frames [M, W] f32 on a GPU, centers [K, c1 - c0] f64 on it, cols = (c0, c1) -> (hist int64 [K],
+    sid f64 [1] = -sum h log2(h + 1e-6)), with ``want_labels`` also the int32 [M] labels.  Asynchronous on the current stream.  CPU
+    tensors raise: there is no CPU fallback."""
+    frames, c0, F = _km_frames(frames, cols, "op_sid_assign")
+    if not (torch.is_tensor(centers) and centers.is_cuda and centers.device == frames.device and centers.dim() == 2):
+        raise L.DimxError("op_sid_assign: centers [K, F] must be a CUDA tensor on the frames' device")
+    if centers.shape[1] != F:
+        raise L.DimxError("op_sid_assign: centers of %d columns for a window of %d" % (centers.shape[1], F))
+    lib = L.load()
+    dev = frames.device
+    M, W, K = int(frames.shape[0]), int(frames.shape[1]), int(centers.shape[0])
+    centers = centers.to(torch.float64).contiguous()
+    hist = torch.empty(K, dtype=torch.int64, device=dev)
+    sid = torch.empty(1, dtype=torch.float64, device=dev)
+    labels = torch.empty(M, dtype=torch.int32, device=dev) if want_labels else None
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_sid_assign(ctypes.c_void_p(frames.data_ptr()), frames.stride(0) if M > 1 else W, M, W, c0, F,
+                                       L.ptr(centers), K, L.ptr(hist), L.ptr(sid), L.ptr(labels), L.stream_ptr(dev)),
+                "dimx_op_sid_assign")
+    return (hist, sid, labels) if want_labels else (hist, sid)

@@ -165,6 +165,11 @@ SIGNATURES = {
     "dimx_op_listener_metrics": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long,
                                          ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_void_p,
                                          c_void_p, c_size_t, c_void_p]),
+    "dimx_op_kmeans_fit_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dimx_op_kmeans_fit": (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, ctypes.c_double,
+                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dimx_op_sid_assign": (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
 }

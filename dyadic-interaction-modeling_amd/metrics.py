@@ -74,6 +74,32 @@ def frechet_distances_hip(y_true, y_pred, lens, cols=(0, None)):
     return op_fd_select(y_true, y_pred, lens, cols=cols, want_best=False)[0]
 
 
+def sid_device(gt_frames, pred_frames, type="exp"):
+    """One fit and two assigns on the GPU, nothing read back: -> f64 [4] on the frames' device = {sid_pred, sid_gt, n_iter, status}
+    (status: 0, or the Lloyd iteration at which a cluster was left empty -- the two SID values mean nothing then)."""
+    import torch
+    from .engine import op_kmeans_fit, op_sid_assign
+    from .mymetrics import SID_GROUPS
+    k, c0, F = SID_GROUPS[type]
+    centers, info = op_kmeans_fit(gt_frames, k, cols=(c0, c0 + F), check=False)
+    sid_p = op_sid_assign(pred_frames, centers, cols=(c0, c0 + F))[1]
+    sid_g = op_sid_assign(gt_frames, centers, cols=(c0, c0 + F))[1]
+    return torch.cat([sid_p, sid_g, info.to(torch.float64)])
+
+
+def sid_hip(gt_frames, pred_frames, type="exp"):
+    """calcuate_sid(gt, pred, type) and calcuate_sid(gt, gt, type) from ONE fit in the HIP library (csrc/kmeans_sid.hip; float64 on
+    the f32 values, the definition is mymetrics.sid_f64): gt_frames [N, 56], pred_frames [M, 56] f32 on one GPU, the concatenated
+    valid frames of the epoch in clip order (the first centre is an index into that order) -> (sid_pred, sid_gt).  One readback.
+    scikit-learn computes in the dtype it is given and the reference hands it float32: this is scikit-learn's value on float64
+    copies of the same numbers.  A cluster left empty raises lib.DimxError; CPU tensors raise it too."""
+    from .engine import kmeans_empty_cluster_error
+    sid_p, sid_g, n_iter, status = sid_device(gt_frames, pred_frames, type).tolist()
+    if status:
+        raise kmeans_empty_cluster_error(status, "sid_hip(%s)" % type)
+    return sid_p, sid_g
+
+
 def calculate_variance(activations):
     """eval_utils.py:48-49."""
     return np.sum(np.var(activations, axis=0))
@@ -151,7 +177,11 @@ class ListenerMetrics:
     tensors where they lie and merges its per-clip rows into float64 state on that GPU -- nothing crosses to the host and nothing
     is synchronised; ``result`` does the one readback.  Clips count in update order: the reference's ``sts`` runs over the
     concatenation of all clips, so the step from a clip's last frame to the next clip's first frame is part of it, across batches
-    too.  SID stays on the host (``print``).  CPU tensors raise lib.DimxError (mymetrics.compute_metrics is the host form).
+    too.  SID stays on the host (``print``) unless the accumulator is built with ``sid=True``: ``update`` then also appends the valid
+    frames of y_true and y_pred (56 columns, f32) to buffers on the GPU, in update order (the first KMeans centre is an index into
+    that concatenation), and ``result`` runs the fits and assignments there (sid_device, csrc/kmeans_sid.hip) inside its one
+    readback.  The gather is built from ``lens``: a host sequence costs no synchronisation, a device tensor is read back once per
+    update (the number of valid frames sizes the buffer).  CPU tensors raise lib.DimxError (mymetrics.compute_metrics is the host form).
     Every clip of every batch counts as a clip, as every list entry does in the reference: a clip with fewer than 2 valid frames has
     no covariance, its distances are NaN (the reference's np.cov gives NaN there too) and ``result`` raises ValueError rather than
     return distance means that one such clip has turned into NaN; an empty clip also adds nothing to the MSE means' numerators
@@ -159,10 +189,25 @@ class ListenerMetrics:
 
     GROUPS = (("pose", 6), ("exp", 50))
 
-    def __init__(self):
+    def __init__(self, sid=False):
         from .engine import LISTENER_WINDOWS
         self.windows = LISTENER_WINDOWS
         self._s = None
+        self.sid = bool(sid)
+        self._frames = ([], [])    # sid: per update the valid frames [n, 56] f32 of y_true / y_pred
+        self._sid_cache = None     # (updates seen, f64 [8] on the GPU)
+
+    def _append_frames(self, y_true, y_pred, lens):
+        """the valid frames of the batch in clip order, gathered on the GPU by an index built from lens"""
+        import torch
+        dev = y_pred.device
+        lens_h = [int(n) for n in (lens.tolist() if torch.is_tensor(lens) else lens)]
+        Ln = int(min(y_true.shape[1], y_pred.shape[1]))
+        lens_h = [min(max(n, 0), Ln) for n in lens_h]
+        b_idx = torch.from_numpy(np.repeat(np.arange(len(lens_h), dtype=np.int64), lens_h)).to(dev)
+        t_idx = torch.from_numpy(np.concatenate([np.arange(n, dtype=np.int64) for n in lens_h] or [np.zeros(0, np.int64)])).to(dev)
+        for buf, y in zip(self._frames, (y_true, y_pred)):
+            buf.append(y[b_idx, t_idx, :56].float())
 
     @staticmethod
     def _merge(na, a, nb, b):
@@ -180,6 +225,8 @@ class ListenerMetrics:
         import torch
         from .engine import op_listener_metrics
         fd, mom = op_listener_metrics(y_true, y_pred, x, lens, windows=tuple(w for _, w in self.windows))
+        if self.sid:
+            self._append_frames(y_true, y_pred, lens)
         dev, B = mom.device, mom.shape[0]
         n = mom[:, 0]                                              # [B] valid frames
         s = {"clips": (self._s["clips"] if self._s else 0) + B, "fd": fd.sum(0)}
@@ -229,7 +276,13 @@ class ListenerMetrics:
         if self._s is None:
             raise ValueError("ListenerMetrics.result() before any update()")
         s = self._s
-        flat = torch.cat([s["fd"], s["mse"], s["sts"], s["cnt"], s["stat"][0], s["stat"][1]]).tolist()
+        parts = [s["fd"], s["mse"], s["sts"], s["cnt"], s["stat"][0], s["stat"][1]]
+        if self.sid:
+            if self._sid_cache is None or self._sid_cache[0] != len(self._frames[0]):
+                gt, pr = (torch.cat(buf) for buf in self._frames)
+                self._sid_cache = (len(self._frames[0]), torch.cat([sid_device(gt, pr, t) for t in ("pose", "exp")]))
+            parts.append(self._sid_cache[1])
+        flat = torch.cat(parts).tolist()
         nw = len(self.windows)
         clips = float(s["clips"])
         fd, mse, sts_, cnt = flat[:nw], flat[nw:nw + 3], flat[nw + 3:nw + 5], flat[nw + 5:nw + 7]
@@ -247,16 +300,27 @@ class ListenerMetrics:
         # all 56 columns: Chan's merge of the two groups
         n, f = cnt[0] + cnt[1], cnt[0] * cnt[1] / (cnt[0] + cnt[1])
         out["var"] = tuple((st[0][k] + st[1][k] + (st[1][k - 1] - st[0][k - 1]) ** 2 * f) / n for k in (1, 3))
+        if self.sid:
+            from .engine import kmeans_empty_cluster_error
+            for i, t in enumerate(("pose", "exp")):
+                sid_p, sid_g, _, status = flat[nw + 23 + 4 * i:nw + 27 + 4 * i]
+                if status:
+                    raise kmeans_empty_cluster_error(status, "ListenerMetrics(sid=True), sid_%s" % t)
+                out["sid_" + t] = (sid_p, sid_g)
         return out
 
     def print(self, y_true=None, y_pred=None):
-        """The lines of print_metrics and then print_metrics_full, in their order and format.  The two SID lines need the per-clip
-        lists (host KMeans, mymetrics.calcuate_sid) and are left out without them.  Returns the dict of ``result``."""
+        """The lines of print_metrics and then print_metrics_full, in their order and format.  The two SID lines come from the GPU
+        when the accumulator was built with ``sid=True``; otherwise they need the per-clip lists (host KMeans,
+        mymetrics.calcuate_sid) and are left out without them.  Returns the dict of ``result``."""
         from .mymetrics import calcuate_sid
         m = self.result()
         for k in ("fid_pose", "fid_exp", "pfid_pose", "pfid_exp", "mse_pose", "mse_exp"):
             print(k + ": ", m[k])
-        if y_true is not None and y_pred is not None:
+        if self.sid:
+            for t in ("pose", "exp"):
+                print("sid_%s: " % t, *m["sid_" + t])
+        elif y_true is not None and y_pred is not None:
             for t in ("pose", "exp"):
                 m["sid_" + t] = (calcuate_sid(y_true, y_pred, t), calcuate_sid(y_true, y_true, t))
                 print("sid_%s: " % t, *m["sid_" + t])

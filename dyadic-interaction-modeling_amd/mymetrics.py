@@ -196,3 +196,93 @@ def print_biwi_metrics(y_true, y_pred, file_names, templates=None, mouth_map=Non
     print('Lip Vertex Error: {:.4e}'.format(m["lve"]))
     print('FDD: {:.4e}'.format(m["fdd"]))
     return m["lve"], m["fdd"]
+
+
+# ---------------------------------------------------------------- SID without scikit-learn (reference code/metrics/eval_utils.py:51-83)
+# The definition of the HIP operator (csrc/kmeans_sid.hip): KMeans(k, random_state=0, n_init='auto') as scikit-learn's lloyd path
+# computes it on float64 inputs, restated in numpy.  calcuate_sid above stays the reference's own call.
+SID_GROUPS = {"pose": (20, 0, 6), "exp": (40, 6, 50)}     # type -> (k, first column, columns)
+
+
+def kmeans_draws(n, k, seed=0):
+    """The random numbers KMeans(random_state=seed, n_init='auto', init='k-means++') consumes for n samples and k clusters, in its
+    order; none depends on the data: one ``choice(n, p=uniform)`` (the first centre), then per further centre one
+    ``uniform(size=2 + int(ln k))``.  -> (first_index, U [(k - 1), trials] float64)."""
+    rs = np.random.RandomState(seed)
+    trials = 2 + int(np.log(k))
+    first = int(rs.choice(n, p=np.full(n, 1.0) / float(n)))
+    u = np.empty((max(k - 1, 0), trials), dtype=np.float64)
+    for c in range(k - 1):
+        u[c] = rs.uniform(size=trials)
+    return first, u
+
+
+def _sq_dist_rows(c, X):
+    """[len(c), N] squared distances, summed over the columns directly (no |x|^2 - 2 x.c + |c|^2 cancellation)."""
+    return np.stack([np.sum((X - row) ** 2, axis=1) for row in c])
+
+
+def kmeans_assign_f64(X, centers):
+    """Nearest centre per row of X, the first index on ties; scikit-learn's lloyd form argmin_k (|c_k|^2 - 2 x.c_k)."""
+    X, centers = np.asarray(X, dtype=np.float64), np.asarray(centers, dtype=np.float64)
+    return np.argmin(np.sum(centers * centers, axis=1)[None, :] - 2.0 * (X @ centers.T), axis=1)
+
+
+def kmeans_fit_f64(X, k, draws, tol=1e-4, max_iter=300):
+    """scikit-learn's KMeans fit (init='k-means++', one initialisation, algorithm='lloyd') in float64 with the random numbers of
+    ``kmeans_draws`` -> (centers [k, F], n_iter, status).  status 0, or the (1-based) iteration at which a cluster was left without
+    points: scikit-learn relocates such a centre, this restatement and the operator stop there and say so."""
+    X = np.asarray(X, dtype=np.float64)
+    n, F = X.shape
+    first, U = draws
+    if n < k:
+        raise ValueError("kmeans_fit_f64: %d samples for %d clusters" % (n, k))
+    tol_abs = tol * float(np.mean(np.var(X, axis=0)))
+    mean = X.mean(axis=0)
+    X = X - mean
+    centers = np.empty((k, F), dtype=np.float64)
+    centers[0] = X[first]
+    closest = _sq_dist_rows(centers[:1], X)[0]
+    for c in range(1, k):
+        pot = float(np.sum(closest))
+        ids = np.searchsorted(np.cumsum(closest), U[c - 1] * pot)
+        np.clip(ids, None, n - 1, out=ids)
+        cand = np.minimum(closest[None, :], _sq_dist_rows(X[ids], X))
+        best = int(np.argmin(cand.sum(axis=1)))
+        centers[c], closest = X[ids[best]], cand[best]
+    labels_old = np.full(n, -1, dtype=np.int64)
+    n_iter, status = 0, 0
+    for it in range(max_iter):
+        labels = kmeans_assign_f64(X, centers)
+        counts = np.bincount(labels, minlength=k)
+        sums = np.stack([np.bincount(labels, weights=X[:, c], minlength=k) for c in range(F)], axis=1)
+        n_iter = it + 1
+        if (counts == 0).any():
+            status = n_iter
+            break
+        new = sums * (1.0 / counts)[:, None]
+        shift = np.sqrt(np.sum((new - centers) ** 2, axis=1))
+        centers = new
+        if np.array_equal(labels, labels_old) or float(np.sum(shift ** 2)) <= tol_abs:
+            break
+        labels_old = labels
+    return centers + mean, n_iter, status
+
+
+def sid_entropy(labels, k):
+    hist = np.bincount(labels, minlength=k).astype(np.float64)
+    hist = hist / hist.sum()
+    return float(-np.sum(hist * np.log2(hist + 1e-6)))
+
+
+def sid_f64(gt_frames, pred_frames, type="exp"):
+    """calcuate_sid(gt, pred, type) and calcuate_sid(gt, gt, type) from ONE fit, float64 on the values given: gt_frames / pred_frames
+    are the concatenated frames [N, 56] / [M, 56] (or per-clip lists) -> (sid_pred, sid_gt).  An empty cluster raises ValueError."""
+    k, c0, F = SID_GROUPS[type]
+    cat = lambda a: np.concatenate(a, axis=0) if isinstance(a, (list, tuple)) else np.asarray(a)
+    g = cat(gt_frames)[:, c0:c0 + F].astype(np.float64)
+    p = cat(pred_frames)[:, c0:c0 + F].astype(np.float64)
+    centers, n_iter, status = kmeans_fit_f64(g, k, kmeans_draws(g.shape[0], k))
+    if status:
+        raise ValueError("sid_f64: a cluster was left empty at iteration %d (scikit-learn would relocate it: mymetrics.calcuate_sid)" % status)
+    return sid_entropy(kmeans_assign_f64(p, centers), k), sid_entropy(kmeans_assign_f64(g, centers), k)

@@ -1,6 +1,7 @@
 """The listener test protocol with selection AND metrics in the HIP library: ``evaluate_test_epoch(fd_backend="hip", metrics=acc)``
-followed by ``ListenerMetrics.print`` in place of print_metrics / print_metrics_full on the host (examples/test_s2s_pretrain.py is
-the reference's driver on its host path and stays as it is).  Without the ViCo files / checkpoint it runs on synthetic clips and weights.
+followed by ``ListenerMetrics(sid=True).print`` in place of print_metrics / print_metrics_full on the host, the two SID lines
+included (examples/test_s2s_pretrain.py is the reference's driver on its host path and stays as it is).  Without the ViCo files /
+checkpoint it runs on synthetic clips and weights.
 
     python examples/eval_s2s_pretrain_hip.py [--clips 32] [--batch 8] [--beam 10] [--bf16] [--ckpt best_vico_causal.pt] [--no-sid]
                                             [--out l2l_listener_predictions.pkl]
@@ -31,7 +32,7 @@ def main():
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--ckpt", default="best_vico_causal.pt")
     ap.add_argument("--out", default="l2l_listener_predictions.pkl")
-    ap.add_argument("--no-sid", action="store_true", help="leave out the two SID lines (host KMeans)")
+    ap.add_argument("--no-sid", action="store_true", help="leave out the two SID lines")
     args = ap.parse_args()
 
     device = torch.device("cuda:0")
@@ -46,16 +47,13 @@ def main():
     dataset = get_vico_dataloaders(batch_size=args.batch,
                                    synthetic=None if have_vico else {"n_clips": args.clips, "max_len": args.max_len, "min_len": 24})
 
-    acc = ListenerMetrics()
+    acc = ListenerMetrics(sid=not args.no_sid)    # SID on the GPU too (csrc/kmeans_sid.hip): no per-clip list is needed to print
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d in %.2f s" % (len(y_true), args.beam, time.time() - t0))
     t0 = time.time()
-    if args.no_sid:
-        acc.print()
-    else:
-        acc.print(y_true, y_pred)
+    acc.print()
     print("metrics printed in %.3f s" % (time.time() - t0))
 
     d = {"y_true": y_true, "y_pred": y_pred, "data_ids": data_ids, "synthetic": not have_vico}    # what postprocess2emoca reads

@@ -611,6 +611,34 @@ int dimx_op_listener_metrics(const float* y_true, long yt_clip_stride, long yt_f
                              long yp_frame_stride, const float* x, long x_clip_stride, long x_frame_stride, const int32_t* lens, int B,
                              int L, int Wy, int Wx, const int32_t* windows, int n_win, double* fd, double* moments, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* The SID diversity metric, calcuate_sid (csrc/kmeans_sid.hip; reference code/metrics/eval_utils.py:51-83): a KMeans fit on the
+ * ground-truth frames and the entropy of the histogram of frames over its centres, as the float64 value of scikit-learn's
+ * KMeans(K, random_state, n_init='auto') (k-means++ init, lloyd) on float64 copies of the f32 inputs; the definition is
+ * dimx.mymetrics.kmeans_fit_f64.  All pointers are device memory.
+ *   frames f32: row i starts at frames + i*frame_stride (elements, taken as long); its columns [c0, c0 + F) enter, c0 + F <= W,
+ *       W <= frame_stride, F <= 64, K * F <= 2048 (the centres lie in LDS).  Only rows 0 .. N - 1 (M - 1) are read.
+ * dimx_op_kmeans_fit:
+ *   first_index, U f64 [(K - 1), trials]: the random numbers of the initialisation, drawn on the host (they do not depend on the
+ *       data): the first centre's row and per further centre `trials` uniforms (dimx.mymetrics.kmeans_draws), trials <= 16
+ *   tol, max_iter: scikit-learn's (1e-4, 300); the threshold is tol * mean of the column variances
+ *   centers f64 [K, F]; n_iter int32: Lloyd iterations run; status int32: 0, or the (1-based) iteration at which a cluster was left
+ *       without a frame -- the fit stops there (scikit-learn relocates such a centre; that is not restated) and centers is not a
+ *       result;  labels int32 [N] or NULL: the assignment the returned means were taken over
+ *   workspace: dimx_op_kmeans_fit_ws_bytes(N, K, F) bytes, 256-byte aligned.
+ *   The whole fit is enqueued at once: 5 + 4 (K - 1) + 3 max_iter launches; convergence is a device word and every launch after it
+ *   is set returns at once.  No host synchronisation, no floating-point atomics, fixed summation orders (bit-reproducible).
+ * dimx_op_sid_assign:
+ *   hist int64 [K]: frames per nearest centre (the first index on ties);  sid f64: -sum h log2(h + 1e-6), h = hist / M;
+ *   labels int32 [M] or NULL.  Two launches and a memset; integer atomics only.
+ * DIMX_ERR_ARG for a null operand (labels excepted), N < K, F or K * F beyond the LDS plan, a window that leaves the row, a frame
+ * stride below W, first_index outside [0, N), trials outside 1..16, a short or misaligned workspace; nothing is enqueued then.
+ * _ws_bytes returns 0 for N < 1 and shapes beyond the LDS plan. */
+size_t dimx_op_kmeans_fit_ws_bytes(int N, int K, int F);
+int dimx_op_kmeans_fit(const float* frames, long frame_stride, int N, int W, int c0, int F, int K, int first_index, const double* U,
+                       int trials, double tol, int max_iter, double* centers, int32_t* n_iter, int32_t* status, int32_t* labels,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int dimx_op_sid_assign(const float* frames, long frame_stride, int M, int W, int c0, int F, const double* centers, int K, int64_t* hist,
+                       double* sid, int32_t* labels, void* stream);
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
