@@ -11,36 +11,26 @@
 //   lm_moments_kernel (one block of 256 per clip): two passes over the clip's valid frames -- the means first, then the centred
 //       sums, the squared error and the STS sum -- and the first and last row of gt - pred.  A lane owns one column and every
 //       fourth frame; the per-lane partials are summed in lane order by one thread per quantity.
-//   lm_fd_kernel (one block of 512 per (window, clip), the widest windows first): the arithmetic of fd_select.hip with F up to 112.
-//       S1 -> one-sided Jacobi -> A = G Lambda^-1/2 (S1 = A A^T) -> workspace;  S2;  T = S2 A;  M = A^T T;  the same Jacobi on M;
-//       tr sqrt(S1 S2) = sum of the square roots of the r = min(F, n - 1) largest eigenvalues of M (the rank rule of fd_select.hip).
-// LDS: ONE F x F float64 matrix (column stride F | 1: 112 x 113 x 8 = 101 248 B) plus a 16-row panel (16 x 113 x 8 = 14 464 B) that
-// is the frame tile of the covariance pass and the k-panel of A in the two products.  S1, S2, T and M take turns in the one matrix;
-// A is the only second operand and comes back from the workspace, panel by panel, through L2 (the block wrote it itself: a
-// workgroup-scope fence and the barrier order the write before the reads).  Two matrices of this size do not fit the 160 KiB of a CU.
-// Block shape: 512 threads.  A Jacobi step rotates m/2 <= 56 disjoint column pairs with 8 lanes each = 448 lanes, so the step stays
-// one round of LDS traffic and one barrier as in fd_select.hip; a lane holds F/8 <= 14 rows of its two columns.  The products and the
-// covariance use the 512 threads as 16 x 32 with a 7 x 4 register tile.  The sweep loop is bounded (kLmMaxSweeps).
+//   lm_fd_kernel (one block of 512 per (window, clip), the widest windows first): the Frechet distance of frechet.hpp with F up
+//       to 112, both sides in one block.  The factor A of the target side goes to the workspace and comes back, panel by panel,
+//       through L2 (the block wrote it itself: a workgroup-scope fence and the barrier order the write before the reads): two
+//       112 x 113 float64 matrices (101 248 B each) do not fit the 160 KiB of a CU.
 // Every sum has a fixed order that depends on the shapes only: two calls on the same inputs are bit-identical.
 // Frames t >= lens[b] are never loaded.  All address arithmetic is 64-bit.
-#include "common.hpp"
+#include "frechet.hpp"
 
 namespace dimx {
 namespace {
 
-constexpr int kLmThreads = 512;
+using LmT = frechet::Traits<512, 112>;
+constexpr int kLmThreads = LmT::THREADS;
 constexpr int kLmMomThreads = 256;
-constexpr int kLmMaxF = 112;
+constexpr int kLmMaxF = LmT::MAXF;
 constexpr int kLmMaxWin = 8;
-constexpr int kLmTile = 16;               // rows of the panel: frames of the covariance pass, k of the products
-constexpr int kLmTileLd = kLmMaxF + 1;    // panel row stride (doubles)
-constexpr int kLmMaxSweeps = 30;
 constexpr int kLmCols = 56, kLmPose = 6;
 constexpr int kLmGroup = 10;              // moments per group, include/dimx.h
 constexpr int kLmEdge = 1 + 2 * kLmGroup; // first column of the edge block
 static_assert(kLmEdge + 2 * kLmCols == DIMX_LM_ROW, "moment row layout");
-
-__host__ __device__ inline int lm_ld(int F) { return F | 1; }   // odd column stride, as fd_select.hip
 
 struct LmArgs {
     const float* yt;
@@ -60,16 +50,11 @@ struct LmArgs {
     int32_t* wsSweeps;       // [2][n_win][B]
 };
 
-__device__ __forceinline__ int lm_valid_frames(const LmArgs& a, int b) {
-    const int n = a.lens[b];
-    return n < 0 ? 0 : (n > a.L ? a.L : n);
-}
-
 // ------------------------------------------------------------------------------------------------ moments
 __global__ __launch_bounds__(kLmMomThreads) void lm_moments_kernel(LmArgs a) {
     __shared__ double part[7][kLmMomThreads];
     __shared__ double mean[2][3];
-    const int b = blockIdx.x, n = lm_valid_frames(a, b);
+    const int b = blockIdx.x, n = frechet::valid_frames(a.lens, a.L, b);
     double* out = a.mom + (size_t)b * DIMX_LM_ROW;
     if (n < 1) {
         for (int e = threadIdx.x; e < DIMX_LM_ROW; e += kLmMomThreads) out[e] = 0.0;
@@ -148,14 +133,6 @@ __global__ __launch_bounds__(kLmMomThreads) void lm_moments_kernel(LmArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ distances
-struct LmSmem {
-    double red[4][128];      // partial sums of lm_mean; red[0] is reused as the keep flags of lm_top_r
-    double mu[kLmMaxF];
-    double mu1[kLmMaxF];
-    double sig[kLmMaxF];
-    double scal[4];          // tr S1, tr S2, |mu1 - mu2|^2
-};
-
 // the operand rows [x[:, xc0:xc0+xF] | y[:, yc0:yc0+yF]] of one clip
 struct LmRows {
     const float* x;
@@ -168,240 +145,12 @@ struct LmRows {
     }
 };
 
-// mean over the n valid frames of the F operand columns -> sm.mu
-__device__ void lm_mean(const LmRows& rw, int n, int F, LmSmem& sm) {
-    const int c = threadIdx.x & 127, g = threadIdx.x >> 7;
-    double acc = 0.0;
-    if (c < F)
-        for (int t = g; t < n; t += 4) acc += rw.at(t, c);
-    sm.red[g][c] = acc;
-    __syncthreads();
-    if (threadIdx.x < F) sm.mu[c] = (((sm.red[0][c] + sm.red[1][c]) + sm.red[2][c]) + sm.red[3][c]) / (double)n;
-    __syncthreads();
-}
-
-// the 16 x 32 thread grid of the covariance and of the products: rows ti + 16 p (p < 7), columns tj + 32 q (q < 4), clamped to F - 1
-struct LmTileIdx {
-    int ti, tj, ri[7], cj[4], np, nq;
-    __device__ explicit LmTileIdx(int F) {
-        ti = threadIdx.x >> 5, tj = threadIdx.x & 31;
-        np = (F + 15) >> 4, nq = (F + 31) >> 5;   // register tiles that hold a column of the window at all (block-uniform)
-#pragma unroll
-        for (int p = 0; p < 7; ++p) ri[p] = min(ti + 16 * p, F - 1);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cj[q] = min(tj + 32 * q, F - 1);
-    }
-};
-
-__device__ __forceinline__ void lm_acc_zero(double (&acc)[7][4]) {
-#pragma unroll
-    for (int p = 0; p < 7; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-}
-
-__device__ __forceinline__ void lm_acc_fma(const LmTileIdx& ix, const double (&u)[7], const double (&v)[4], double (&acc)[7][4]) {
-#pragma unroll
-    for (int p = 0; p < 7; ++p)
-        if (p < ix.np)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (q < ix.nq) acc[p][q] = fma(u[p], v[q], acc[p][q]);
-}
-
-// acc -> out[j * ld + i] * scale for the entries of the window; the caller has synchronised the readers of out
-__device__ __forceinline__ void lm_acc_store(const LmTileIdx& ix, int F, const double (&acc)[7][4], double scale, double* out, int ld) {
-#pragma unroll
-    for (int p = 0; p < 7; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (ix.ti + 16 * p < F && ix.tj + 32 * q < F) out[ix.cj[q] * ld + ix.ri[p]] = acc[p][q] * scale;
-    __syncthreads();
-}
-
-// unbiased covariance of the centred frames -> out (column-major, stride ld); tile is the panel and does not alias out
-__device__ void lm_cov(const LmRows& rw, int n, int F, const LmSmem& sm, const LmTileIdx& ix, double* tile, double* out, int ld) {
-    double acc[7][4];
-    lm_acc_zero(acc);
-    for (int t0 = 0; t0 < n; t0 += kLmTile) {
-        for (int e = threadIdx.x; e < kLmTile * 128; e += kLmThreads) {
-            const int tt = e >> 7, c = e & 127;
-            if (c < F) tile[tt * kLmTileLd + c] = t0 + tt < n ? rw.at(t0 + tt, c) - sm.mu[c] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int tt = 0; tt < kLmTile; ++tt) {
-            double u[7], v[4];
-#pragma unroll
-            for (int p = 0; p < 7; ++p) u[p] = tile[tt * kLmTileLd + ix.ri[p]];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = tile[tt * kLmTileLd + ix.cj[q]];
-            lm_acc_fma(ix, u, v, acc);
-        }
-        __syncthreads();
-    }
-    lm_acc_store(ix, F, acc, 1.0 / (double)(n - 1), out, ld);
-}
-
-// rows [k0, k0 + 16) of A (global, column-major, dense stride F) -> tile[kk][j]; a column's 16 values are one 128-byte run
-__device__ __forceinline__ void lm_stage_a(const double* A, int F, int k0, double* tile) {
-    for (int e = threadIdx.x; e < kLmTile * F; e += kLmThreads) {
-        const int j = e >> 4, kk = e & 15;
-        tile[kk * kLmTileLd + j] = k0 + kk < F ? A[(size_t)j * F + k0 + kk] : 0.0;
-    }
-    __syncthreads();
-}
-
-// G <- S A   (S = G on entry, symmetric: S[i][k] is read as G[k * ld + i])
-// G <- A^T G (second = true)
-__device__ void lm_product(const double* A, int F, const LmTileIdx& ix, double* tile, double* G, int ld, bool second) {
-    double acc[7][4];
-    lm_acc_zero(acc);
-    for (int k0 = 0; k0 < F; k0 += kLmTile) {
-        lm_stage_a(A, F, k0, tile);
-        const int kn = min(kLmTile, F - k0);
-        for (int kk = 0; kk < kn; ++kk) {
-            const int k = k0 + kk;
-            double u[7], v[4];
-            if (!second) {
-#pragma unroll
-                for (int p = 0; p < 7; ++p) u[p] = G[k * ld + ix.ri[p]];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = tile[kk * kLmTileLd + ix.cj[q]];
-            } else {
-#pragma unroll
-                for (int p = 0; p < 7; ++p) u[p] = tile[kk * kLmTileLd + ix.ri[p]];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = G[ix.cj[q] * ld + k];
-            }
-            lm_acc_fma(ix, u, v, acc);
-        }
-        __syncthreads();
-    }
-    lm_acc_store(ix, F, acc, 1.0, G, ld);
-}
-
-// trace of the F x F matrix m (stride ld), summed in index order -> sm.scal[slot]
-__device__ void lm_trace(const double* m, int F, int ld, LmSmem& sm, int slot) {
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < F; ++i) t += m[i * ld + i];
-        sm.scal[slot] = t;
-    }
-    __syncthreads();
-}
-
-// squared column norms of g -> sm.sig (thread c owns column c)
-__device__ void lm_col_norms2(const double* g, int F, int ld, LmSmem& sm) {
-    if (threadIdx.x < F) {
-        double s = 0.0;
-        for (int r = 0; r < F; ++r) s = fma(g[threadIdx.x * ld + r], g[threadIdx.x * ld + r], s);
-        sm.sig[threadIdx.x] = s;
-    }
-    __syncthreads();
-}
-
-// One-sided cyclic Jacobi on the columns of g (F x F, column-major, stride ld), F <= 8 * NK: fd_select.hip's, with NK rows per lane.
-// On return the columns are mutually orthogonal (g <- g V): for a symmetric positive semi-definite input their norms are its
-// eigenvalues.  Returns the sweeps done.
-template <int NK>
-__device__ int lm_jacobi(double* g, int F, int ld, LmSmem& sm) {
-    lm_col_norms2(g, F, ld, sm);
-    double fro2 = 0.0;
-    for (int c = 0; c < F; ++c) fro2 += sm.sig[c];
-    const double tiny = 1e-28 * fro2;   // columns whose product is below this are orthogonal as far as the result can tell
-    const int m = (F + 1) & ~1, pairs = m >> 1, pi = threadIdx.x >> 3, sub = threadIdx.x & 7;
-    int sweeps = 0;
-    for (int sw = 0; sw < kLmMaxSweeps; ++sw) {
-        int rotated = 0;
-        for (int r = 0; r < m - 1; ++r) {
-            int p = 0, q = 0;
-            bool live = pi < pairs;
-            if (live) {
-                if (pi == 0) {
-                    p = m - 1;
-                    q = r;
-                } else {
-                    p = (r + pi) % (m - 1);
-                    q = (r - pi + (m - 1)) % (m - 1);
-                }
-                live = p < F && q < F;   // m - 1 is the bye of an odd F
-            }
-            double gp[NK], gq[NK];
-            double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                const int row = sub + 8 * k;
-                const bool in = live && row < F;
-                gp[k] = in ? g[p * ld + row] : 0.0;
-                gq[k] = in ? g[q * ld + row] : 0.0;
-                al = fma(gp[k], gp[k], al);
-                be = fma(gq[k], gq[k], be);
-                ga = fma(gp[k], gq[k], ga);
-            }
-#pragma unroll
-            for (int o = 1; o < 8; o <<= 1) {   // butterfly over the pair's 8 lanes: every lane ends with the same bits
-                al += __shfl_xor(al, o);
-                be += __shfl_xor(be, o);
-                ga += __shfl_xor(ga, o);
-            }
-            const double aga = fabs(ga);
-            if (live && aga > tiny && aga * aga > 1e-26 * al * be) {
-                const double zeta = (be - al) / (2.0 * ga);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) {
-                    const int row = sub + 8 * k;
-                    if (row < F) {
-                        g[p * ld + row] = c * gp[k] - s * gq[k];
-                        g[q * ld + row] = s * gp[k] + c * gq[k];
-                    }
-                }
-                rotated = 1;
-            }
-            __syncthreads();
-        }
-        ++sweeps;
-        if (!__syncthreads_or(rotated)) break;
-    }
-    return sweeps;
-}
-
-__device__ int lm_jacobi_any(double* g, int F, int ld, LmSmem& sm) {
-    if (F <= 8) return lm_jacobi<1>(g, F, ld, sm);
-    if (F <= 64) return lm_jacobi<8>(g, F, ld, sm);
-    return lm_jacobi<14>(g, F, ld, sm);
-}
-
-// sm.sig holds F non-negative values; sm.red[0][c] = 1 when sig[c] is among the r largest (ties: the lower index first)
-__device__ void lm_top_r(int F, int r, LmSmem& sm) {
-    if (threadIdx.x < F) {
-        const int c = threadIdx.x;
-        const double v = sm.sig[c];
-        int rank = 0;
-        for (int d = 0; d < F; ++d) rank += (sm.sig[d] > v || (sm.sig[d] == v && d < c)) ? 1 : 0;
-        sm.red[0][c] = rank < r ? 1.0 : 0.0;
-    }
-    __syncthreads();
-}
-
-// eigenvalues of the symmetric positive semi-definite g (Jacobi in place) -> sm.sig, keep flags of the r largest -> sm.red[0]
-__device__ int lm_eigen(double* g, int F, int ld, int r, LmSmem& sm) {
-    const int sweeps = lm_jacobi_any(g, F, ld, sm);
-    lm_col_norms2(g, F, ld, sm);
-    if (threadIdx.x < F) sm.sig[threadIdx.x] = sqrt(sm.sig[threadIdx.x]);
-    __syncthreads();
-    lm_top_r(F, r, sm);
-    return sweeps;
-}
-
 __global__ __launch_bounds__(kLmThreads) void lm_fd_kernel(LmArgs a) {
     extern __shared__ double lm_dyn[];
-    __shared__ LmSmem sm;
+    __shared__ frechet::Smem<LmT> sm;
     const int pos = blockIdx.x / a.B, b = blockIdx.x - pos * a.B, w = a.order[pos];
-    const int xc0 = a.win[w][0], xF = a.win[w][1], yc0 = a.win[w][2], F = xF + a.win[w][3], ld = lm_ld(F);
-    const int n = lm_valid_frames(a, b);
+    const int xc0 = a.win[w][0], xF = a.win[w][1], yc0 = a.win[w][2], F = xF + a.win[w][3], ld = LmT::ld(F);
+    const int n = frechet::valid_frames(a.lens, a.L, b);
     const size_t slot = (size_t)w * a.B + b;
     if (n < 2) {   // no covariance: nothing of the inputs or of the workspace is read
         if (threadIdx.x == 0) {
@@ -411,47 +160,34 @@ __global__ __launch_bounds__(kLmThreads) void lm_fd_kernel(LmArgs a) {
         }
         return;
     }
-    double* tile = lm_dyn;                         // kLmTile x kLmTileLd
-    double* G = lm_dyn + kLmTile * kLmTileLd;      // F x ld: S1, then S2, T, M
+    double* tile = lm_dyn;                                  // kTile x kTileLd
+    double* G = lm_dyn + frechet::kTile * LmT::kTileLd;     // F x ld: S1, then S2, T, M
     double* A = a.wsA + slot * a.a_stride;
-    const LmTileIdx ix(F);
+    const frechet::TileIdx<LmT> ix(F);
     const int r = min(F, n - 1);
     LmRows rw;
     rw.x = a.x + (size_t)b * a.x_cs + xc0, rw.x_fs = a.x_fs, rw.xF = xF;
     // target side: mu1, tr S1, A
     rw.y = a.yt + (size_t)b * a.yt_cs + yc0, rw.y_fs = a.yt_fs;
-    lm_mean(rw, n, F, sm);
-    lm_cov(rw, n, F, sm, ix, tile, G, ld);
-    lm_trace(G, F, ld, sm, 0);
+    frechet::mean<LmT>(rw, n, F, sm);
+    frechet::cov<LmT>(rw, n, F, sm, ix, tile, G, ld);
+    frechet::trace<LmT>(G, F, ld, sm, 0);
     if (threadIdx.x < F) sm.mu1[threadIdx.x] = sm.mu[threadIdx.x];
-    const int sweeps1 = lm_eigen(G, F, ld, r, sm);   // sm.sig = lambda_i, columns of G = lambda_i v_i
-    for (int e = threadIdx.x; e < F * F; e += kLmThreads) {
-        const int c = e / F, rr = e - c * F;
-        const double lam = sm.sig[c];
-        A[e] = (sm.red[0][c] != 0.0 && lam > 0.0) ? G[c * ld + rr] / sqrt(lam) : 0.0;
-    }
+    const int sweeps1 = frechet::eigen<LmT>(G, F, ld, r, sm);
+    frechet::write_factor<LmT>(G, F, ld, sm, A);
     __threadfence_block();   // A is read back by this block only
     __syncthreads();
     // candidate side: mu2, S2, T = S2 A, M = A^T T
     rw.y = a.yp + (size_t)b * a.yp_cs + yc0, rw.y_fs = a.yp_fs;
-    lm_mean(rw, n, F, sm);
-    lm_cov(rw, n, F, sm, ix, tile, G, ld);
-    lm_trace(G, F, ld, sm, 1);
-    if (threadIdx.x == 0) {   // |mu1 - mu2|^2 in column order
-        double d2 = 0.0;
-        for (int c = 0; c < F; ++c) {
-            const double d = sm.mu1[c] - sm.mu[c];
-            d2 = fma(d, d, d2);
-        }
-        sm.scal[2] = d2;
-    }
-    lm_product(A, F, ix, tile, G, ld, false);
-    lm_product(A, F, ix, tile, G, ld, true);
-    const int sweeps2 = lm_eigen(G, F, ld, r, sm);
+    frechet::mean<LmT>(rw, n, F, sm);
+    frechet::cov<LmT>(rw, n, F, sm, ix, tile, G, ld);
+    frechet::trace<LmT>(G, F, ld, sm, 1);
+    frechet::mean_diff2<LmT>(F, sm);
+    frechet::product<LmT>(A, F, ix, tile, G, ld, false);
+    frechet::product<LmT>(A, F, ix, tile, G, ld, true);
+    const int sweeps2 = frechet::eigen<LmT>(G, F, ld, r, sm);
     if (threadIdx.x == 0) {
-        double trs = 0.0;
-        for (int c = 0; c < F; ++c) trs += sm.red[0][c] != 0.0 ? sqrt(sm.sig[c]) : 0.0;
-        a.fd[(size_t)b * a.n_win + w] = sm.scal[2] + sm.scal[0] + sm.scal[1] - 2.0 * trs;
+        a.fd[(size_t)b * a.n_win + w] = frechet::distance<LmT>(F, sm, sm.scal[0]);
         a.wsSweeps[slot] = sweeps1;
         a.wsSweeps[(size_t)a.n_win * a.B + slot] = sweeps2;
     }
@@ -520,11 +256,9 @@ int dimx_op_listener_metrics(const float* y_true, long yt_clip_stride, long yt_f
     a.a_stride = (size_t)Fmax * Fmax;
     a.wsSweeps = (int32_t*)(a.wsA + (size_t)B * n_win * a.a_stride);
     hipStream_t s = (hipStream_t)stream;
-    const size_t lds = ((size_t)kLmTile * kLmTileLd + (size_t)Fmax * lm_ld(Fmax)) * sizeof(double);
-    // the attribute belongs to (function, device): always the size of the widest window the kernel takes, never this call's own, so
-    // that calls from several host threads cannot lower it under one another; the call is cheap
-    const size_t lds_max = ((size_t)kLmTile * kLmTileLd + (size_t)kLmMaxF * lm_ld(kLmMaxF)) * sizeof(double);
-    DIMX_HIP(hipFuncSetAttribute((const void*)lm_fd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+    const size_t lds = LmT::lds_bytes(Fmax);
+    // never this call's own size: frechet.hpp, Traits::lds_bytes
+    DIMX_HIP(hipFuncSetAttribute((const void*)lm_fd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LmT::lds_bytes(kLmMaxF)));
     hipLaunchKernelGGL(lm_moments_kernel, dim3(B), dim3(kLmMomThreads), 0, s, a);
     DIMX_HIP(hipGetLastError());
     hipLaunchKernelGGL(lm_fd_kernel, dim3(B * n_win), dim3(kLmThreads), lds, s, a);

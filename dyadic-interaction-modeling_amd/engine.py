@@ -567,15 +567,40 @@ def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None,
     return out
 
 
-_FD_WS = {}     # device index -> uint8 workspace of op_fd_select (grown on demand, never shrunk)
+# ---------------------------------------------------------------- host plumbing of the metric operators
+def _device_key(device):
+    device = torch.device(device)
+    return device.index if device.index is not None else torch.cuda.current_device()
 
 
-def _fd_workspace(device, need):
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    ws = _FD_WS.get(key)
+def _workspace(cache, device, need, floor=8):
+    """The uint8 workspace of one operator on ``device``: ``cache`` maps device index -> tensor, grown on demand and never shrunk.
+    One dict per operator: the operators may be in flight together on one stream, and the *_sweeps readers take the last call's."""
+    key = _device_key(device)
+    ws = cache.get(key)
     if ws is None or ws.numel() < need:
-        ws = _FD_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+        ws = cache[key] = torch.empty(max(need, floor), dtype=torch.uint8, device=device)
     return ws
+
+
+def _lens_i32(lens, device, B, what):
+    """lens (tensor or host sequence) -> int32 [B] on ``device``."""
+    if torch.is_tensor(lens):
+        lens_d = lens.to(device=device, dtype=torch.int32).contiguous()
+    else:
+        lens_d = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(device)
+    if lens_d.numel() != B:
+        raise L.DimxError("%s: %d lens for %d clips" % (what, lens_d.numel(), B))
+    return lens_d
+
+
+def _f32_rows(t, copy_strided=True):
+    """float32 with a feature (last) stride of 1: every other stride is passed to the kernel as it is."""
+    t = t if t.dtype == torch.float32 else t.float()
+    return t.contiguous() if copy_strided and t.stride(-1) != 1 else t
+
+
+_FD_WS = {}     # device index -> uint8 workspace of op_fd_select
 
 
 def op_fd_select(y_true, y_pred, lens, cols=(0, None), want_best=True):
@@ -593,26 +618,16 @@ def op_fd_select(y_true, y_pred, lens, cols=(0, None), want_best=True):
     lib = L.load()
     dev = y_pred.device
     B, S, Ln, W = y_pred.shape
-    y_true = y_true if y_true.dtype == torch.float32 else y_true.float()
-    y_pred = y_pred if y_pred.dtype == torch.float32 else y_pred.float()
-    if W > 1 and y_true.stride(2) != 1:
-        y_true = y_true.contiguous()
-    if W > 1 and y_pred.stride(3) != 1:
-        y_pred = y_pred.contiguous()
+    y_true, y_pred = _f32_rows(y_true, W > 1), _f32_rows(y_pred, W > 1)
     c0 = int(cols[0])
     F = (W if cols[1] is None else int(cols[1])) - c0
-    if torch.is_tensor(lens):
-        lens_d = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_d = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(dev)
-    if lens_d.numel() != B:
-        raise L.DimxError("op_fd_select: %d lens for %d clips" % (lens_d.numel(), B))
+    lens_d = _lens_i32(lens, dev, B, "op_fd_select")
     fd = torch.empty(B, S, dtype=torch.float64, device=dev)
     win = torch.empty(B, dtype=torch.int32, device=dev)
     ok = torch.empty(B, dtype=torch.uint8, device=dev)
     best = torch.empty(B, Ln, W, dtype=torch.float32, device=dev) if want_best else None
     need = int(lib.dimx_op_fd_select_ws_bytes(B, S, F))
-    ws = _fd_workspace(dev, max(need, 8))
+    ws = _workspace(_FD_WS, dev, need)
     with torch.cuda.device(dev):
         L.check(lib.dimx_op_fd_select(ctypes.c_void_p(y_true.data_ptr()), y_true.stride(0), y_true.stride(1),
                                       ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1), y_pred.stride(2),
@@ -626,13 +641,12 @@ def fd_select_sweeps(device, B, S, F):
     (clip, try) problems [B, S]) as int32 tensors (include/dimx.h: the last B + B*S int32 of the workspace)."""
     lib = L.load()
     need = int(lib.dimx_op_fd_select_ws_bytes(B, S, F))
-    device = torch.device(device)
-    ws = _FD_WS[device.index if device.index is not None else torch.cuda.current_device()]
+    ws = _FD_WS[_device_key(device)]
     sw = ws[need - 4 * (B + B * S):need].view(torch.int32)
     return sw[:B].clone(), sw[B:].reshape(B, S).clone()
 
 
-_MM_WS = {}      # device index -> uint8 workspace of op_mesh_metrics (grown on demand, never shrunk)
+_MM_WS = {}      # device index -> uint8 workspace of op_mesh_metrics
 _MM_MAPS = {}    # (device index, n_vert, sorted map bytes) -> MeshMap; keyed on content
 _MM_LENS = {}    # device index -> the host lens array of the last call (kept until the next call has replaced it)
 
@@ -646,16 +660,11 @@ class MeshMap:
         self.data, self.n, self.n_vert, self.device_key = data, n, n_vert, device_key
 
 
-def _mm_device_key(device):
-    device = torch.device(device)
-    return device.index if device.index is not None else torch.cuda.current_device()
-
-
 def mesh_map(seq, n_vert, device, what="map"):
     """Validate a vertex map on the host (every index in [0, n_vert), DimxError otherwise) and return its MeshMap on ``device``: the
     SORTED copy is uploaded once per (device, n_vert, content) and cached."""
     if isinstance(seq, MeshMap):
-        if seq.n_vert != n_vert or seq.device_key != _mm_device_key(device):
+        if seq.n_vert != n_vert or seq.device_key != _device_key(device):
             raise L.DimxError("op_mesh_metrics: %s was prepared for %d vertices on device %d" % (what, seq.n_vert, seq.device_key))
         return seq
     if torch.is_tensor(seq):
@@ -667,7 +676,7 @@ def mesh_map(seq, n_vert, device, what="map"):
     if arr.size and (arr.min() < 0 or arr.max() >= n_vert):
         raise L.DimxError("op_mesh_metrics: %s holds an index outside [0, %d) (min %d, max %d)" % (what, n_vert, arr.min(), arr.max()))
     srt = np.sort(arr).astype(np.int32)
-    key = _mm_device_key(device)
+    key = _device_key(device)
     ck = (key, int(n_vert), srt.tobytes())
     hit = _MM_MAPS.get(ck)
     if hit is None:
@@ -700,13 +709,8 @@ def op_mesh_metrics(y_true, y_pred, lens, template, mouth_map, upper_map, want_f
     Ln = int(min(y_true.shape[1], y_pred.shape[1]))
     lib = L.load()
     dev = y_pred.device
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    y_true = y_true if y_true.dtype == torch.float32 else y_true.float()
-    y_pred = y_pred if y_pred.dtype == torch.float32 else y_pred.float()
-    if y_true.stride(2) != 1:
-        y_true = y_true.contiguous()
-    if y_pred.stride(2) != 1:
-        y_pred = y_pred.contiguous()
+    key = _device_key(dev)
+    y_true, y_pred = _f32_rows(y_true), _f32_rows(y_pred)
     templ, templ_cs = None, 0
     if template is not None:
         if not (torch.is_tensor(template) and template.is_cuda and template.device == dev):
@@ -731,9 +735,7 @@ def op_mesh_metrics(y_true, y_pred, lens, template, mouth_map, upper_map, want_f
     frames = torch.empty(B, Ln, dtype=torch.float64, device=dev) if want_frames else None
     status = torch.empty(1, dtype=torch.int32, device=dev)
     need = int(lib.dimx_op_mesh_metrics_ws_bytes(B, Ln, n_mouth, n_upper))
-    ws = _MM_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _MM_WS[key] = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    ws = _workspace(_MM_WS, dev, need)
     with torch.cuda.device(dev):
         L.check(lib.dimx_op_mesh_metrics(ctypes.c_void_p(y_true.data_ptr()), y_true.stride(0), y_true.stride(1),
                                          ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1),
@@ -749,7 +751,7 @@ def op_mesh_metrics(y_true, y_pred, lens, template, mouth_map, upper_map, want_f
 LISTENER_WINDOWS = (("fid_pose", (0, 0, 0, 6)), ("fid_exp", (0, 0, 6, 50)), ("pfid_pose", (0, 6, 0, 6)), ("pfid_exp", (6, 50, 6, 50)),
                     ("fid", (0, 0, 0, 56)), ("pfid", (0, 56, 0, 56)))
 LM_ROW = 133     # DIMX_LM_ROW of include/dimx.h
-_LM_WS = {}      # device index -> uint8 workspace of op_listener_metrics (grown on demand, never shrunk)
+_LM_WS = {}      # device index -> uint8 workspace of op_listener_metrics
 
 
 def op_listener_metrics(y_true, y_pred, x, lens, windows=tuple(w for _, w in LISTENER_WINDOWS)):
@@ -768,26 +770,17 @@ def op_listener_metrics(y_true, y_pred, x, lens, windows=tuple(w for _, w in LIS
     lib = L.load()
     dev = y_pred.device
     B, Ln = int(y_pred.shape[0]), int(min(t.shape[1] for t in ts))
-    y_true, y_pred, x = [t if t.dtype == torch.float32 else t.float() for t in ts]
-    y_true, y_pred, x = [t if t.stride(2) == 1 else t.contiguous() for t in (y_true, y_pred, x)]
+    y_true, y_pred, x = [_f32_rows(t) for t in ts]
     win = [tuple(int(v) for v in w) for w in windows]
     if any(len(w) != 4 for w in win):
         raise L.DimxError("op_listener_metrics: windows are rows (xc0, xF, yc0, yF), got %r" % (windows,))
     n_win = len(win)
     win_c = (ctypes.c_int32 * (4 * max(n_win, 1)))(*[v for w in win for v in w])
-    if torch.is_tensor(lens):
-        lens_d = lens.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        lens_d = torch.tensor([int(n) for n in lens], dtype=torch.int32).to(dev)
-    if lens_d.numel() != B:
-        raise L.DimxError("op_listener_metrics: %d lens for %d clips" % (lens_d.numel(), B))
+    lens_d = _lens_i32(lens, dev, B, "op_listener_metrics")
     fd = torch.empty(B, n_win, dtype=torch.float64, device=dev)
     mom = torch.empty(B, LM_ROW, dtype=torch.float64, device=dev)
     need = int(lib.dimx_op_listener_metrics_ws_bytes(B, n_win, max([w[1] + w[3] for w in win] or [0])))
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    ws = _LM_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _LM_WS[key] = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    ws = _workspace(_LM_WS, dev, need)
     with torch.cuda.device(dev):
         L.check(lib.dimx_op_listener_metrics(ctypes.c_void_p(y_true.data_ptr()), y_true.stride(0), y_true.stride(1),
                                              ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1),
@@ -802,14 +795,13 @@ def listener_metrics_sweeps(device, B, n_win, F):
     workspace: (target factorisations, candidate problems), each int32 [n_win, B] (include/dimx.h)."""
     lib = L.load()
     need = int(lib.dimx_op_listener_metrics_ws_bytes(B, n_win, F))
-    device = torch.device(device)
-    ws = _LM_WS[device.index if device.index is not None else torch.cuda.current_device()]
+    ws = _LM_WS[_device_key(device)]
     sw = ws[need - 8 * B * n_win:need].view(torch.int32).reshape(2, n_win, B)
     return sw[0].clone(), sw[1].clone()
 
 
 # ---------------------------------------------------------------- SID: float64 KMeans fit + assign (csrc/kmeans_sid.hip)
-_KM_WS = {}      # device index -> uint8 workspace of op_kmeans_fit (grown on demand, never shrunk)
+_KM_WS = {}      # device index -> uint8 workspace of op_kmeans_fit
 
 
 def _km_frames(frames, cols, what):
@@ -852,10 +844,7 @@ def op_kmeans_fit(frames, k, cols=(0, None), seed=0, tol=1e-4, max_iter=300, wan
     info = torch.zeros(2, dtype=torch.int32, device=dev)
     labels = torch.empty(N, dtype=torch.int32, device=dev) if want_labels else None
     need = int(lib.dimx_op_kmeans_fit_ws_bytes(N, k, F))
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    ws = _KM_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _KM_WS[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    ws = _workspace(_KM_WS, dev, need, floor=256)
     with torch.cuda.device(dev):
         L.check(lib.dimx_op_kmeans_fit(ctypes.c_void_p(frames.data_ptr()), frames.stride(0) if N > 1 else W, N, W, c0, F, k, first,
                                        L.ptr(U_d), int(U.shape[1]), float(tol), int(max_iter), L.ptr(centers),

@@ -25,16 +25,23 @@ CASES = {
     "B": (11, 4, 3, 70, [70, 57, 64, 61], [(0, 56), (0, 6), (6, 50)]),
     "C": (12, 3, 10, 40, [40, 20, 2], [(0, 56)]),
     "D": (13, 2, 10, 330, [330, 299], [(0, 56)]),
+    # the boundaries of the shared templates (csrc/frechet.hpp), rows of 64 columns, every clip full rank: F = 64 the operator's
+    # maximum (every pair lane live, full register tile); 7 odd (the bye pair) in the one-row-per-lane Jacobi, c0 > 0; 8 the last F
+    # of that Jacobi; 9 the first of the eight-row one, odd; 1 no pair at all
+    "E": (14, 2, 2, 80, [80, 66], [(0, 64), (3, 10), (0, 8), (0, 9), (5, 6)]),
 }
-CASE_WINDOWS = [(k, w) for k, v in CASES.items() for w in v[5]]
+WIDTH = {"E": 64}
+CASE_WINDOWS = [(k, w) for k, v in CASES.items() if k != "E" for w in v[5]]
+EDGE_WINDOWS = CASES["E"][5]
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(name):
     seed, B, S, L, lens, _ = CASES[name]
     g = torch.Generator().manual_seed(seed)
-    yt = torch.randn(B, L, 56, generator=g)
-    yp = 0.6 * yt[:, None] + 0.5 * torch.randn(B, S, L, 56, generator=g)
+    W = WIDTH.get(name, 56)
+    yt = torch.randn(B, L, W, generator=g)
+    yp = 0.6 * yt[:, None] + 0.5 * torch.randn(B, S, L, W, generator=g)
     return yt, yp, list(lens)
 
 
@@ -68,8 +75,7 @@ def _clean_b():
     return _run(yt.to(_dev()), yp.to(_dev()), lens)
 
 
-@pytest.mark.parametrize("name,window", CASE_WINDOWS, ids=["%s-%d-%d" % (k, w[0], w[1]) for k, w in CASE_WINDOWS])
-def test_distances_winner_and_gather_match_the_reference_arithmetic(name, window):
+def _check_distances_winner_and_gather(name, window):
     from dimx import metrics
     yt, yp, lens = _inputs(name)
     ref = _reference(name, window)
@@ -96,8 +102,30 @@ def test_distances_winner_and_gather_match_the_reference_arithmetic(name, window
     assert win.tolist() == ref.argmin(1).tolist()
     assert ok.tolist() == [1] * B
     for j in range(B):
-        assert torch.equal(best[j, :lens[j]], yp[j, int(win[j]), :lens[j]])      # full width 56, also for the sliced windows
+        assert torch.equal(best[j, :lens[j]], yp[j, int(win[j]), :lens[j]])      # the full row, also for the sliced windows
         assert not best[j, lens[j]:].any()
+
+
+@pytest.mark.parametrize("name,window", CASE_WINDOWS, ids=["%s-%d-%d" % (k, w[0], w[1]) for k, w in CASE_WINDOWS])
+def test_distances_winner_and_gather_match_the_reference_arithmetic(name, window):
+    _check_distances_winner_and_gather(name, window)
+
+
+@pytest.mark.parametrize("window", EDGE_WINDOWS, ids=["E-%d-%d" % w for w in EDGE_WINDOWS])
+def test_template_boundaries_match_the_reference_arithmetic(window):
+    from dimx.engine import fd_select_sweeps
+    _, B, S, _, lens, _ = CASES["E"]
+    F = window[1] - window[0]
+    assert min(lens) >= F + 1                                  # full rank: the 1e-6 bound applies to every clip
+    ref = _reference("E", window)
+    assert np.isfinite(ref).all() and (ref > 0).all()          # the bound is not met vacuously
+    _check_distances_winner_and_gather("E", window)
+    sw_t, sw_c = (t.cpu() for t in fd_select_sweeps(_dev(), B, S, F))
+    print("window %s F=%d sweeps: target %d..%d, candidate %d..%d" % (window, F, int(sw_t.min()), int(sw_t.max()), int(sw_c.min()),
+                                                                     int(sw_c.max())))
+    assert tuple(sw_t.shape) == (B,) and tuple(sw_c.shape) == (B, S)
+    assert int(sw_t.min()) >= 1 and int(sw_c.min()) >= 1
+    assert int(sw_t.max()) < 30 and int(sw_c.max()) < 30
 
 
 def test_padding_is_never_read():

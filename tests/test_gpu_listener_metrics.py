@@ -148,6 +148,38 @@ def test_sweep_counts_stay_below_the_bound():
     assert int(sw_t.max()) < 30 and int(sw_c.max()) < 30
 
 
+# the boundaries of the shared templates (csrc/frechet.hpp), every clip full rank (lens >= 113): F = 64 the last of the eight-row
+# Jacobi; 65 the first of the fourteen-row one, odd; 57 odd; 1 no pair at all; 112 the operator's maximum
+SEED2, B2, L2, LENS2 = 22, 2, 130, [130, 114]
+EDGE_WINDOWS = ((0, 8, 0, 56), (0, 9, 0, 56), (0, 1, 0, 56), (0, 0, 0, 1), (0, 56, 0, 56))
+
+
+def test_template_boundaries_match_the_reference_arithmetic():
+    from dimx import metrics
+    from dimx.engine import listener_metrics_sweeps, op_listener_metrics
+    g = torch.Generator().manual_seed(SEED2)
+    yt = torch.randn(B2, L2, 56, generator=g)
+    yp = 0.6 * yt + 0.5 * torch.randn(B2, L2, 56, generator=g)
+    x = torch.randn(B2, L2, 56, generator=g)
+    fd = op_listener_metrics(yt.to(_dev()), yp.to(_dev()), x.to(_dev()), LENS2, windows=EDGE_WINDOWS)[0].cpu().numpy()
+    sw_t, sw_c = (t.cpu() for t in listener_metrics_sweeps(_dev(), B2, len(EDGE_WINDOWS), 112))
+    failures = []
+    for w, win in enumerate(EDGE_WINDOWS):
+        F = win[1] + win[3]
+        for b, n in enumerate(LENS2):
+            assert n >= F + 1                                  # full rank: the 1e-6 bound applies
+            ref = metrics.clip_fd(*(t.numpy() for t in _operands(yt[b], yp[b], x[b], n, win)))
+            assert np.isfinite(ref) and ref > 0                # the bound is not met vacuously
+            err = abs(fd[b, w] - ref) / abs(ref)
+            print("window %s F=%3d clip %d (n=%3d): kernel rel err %.3e, sweeps %d / %d" % (win, F, b, n, err, int(sw_t[w, b]),
+                                                                                            int(sw_c[w, b])))
+            if not err <= 1e-6:
+                failures.append((win, b, err))
+    assert not failures, failures
+    assert int(sw_t.min()) >= 1 and int(sw_c.min()) >= 1
+    assert int(sw_t.max()) < 30 and int(sw_c.max()) < 30
+
+
 # ------------------------------------------------------------------------------------------------ 2. epoch parity
 def _parse(text):
     got = {}
