@@ -481,7 +481,15 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
                   int rows_total, const float* emb_table, int emb_C, float* x_next, int32_t* step_rw, unsigned* done_ctr,
                   hipStream_t s, const float* pos_table = nullptr, float pos_scale = 0.f, int pos_rows = 0,
                   const int32_t* dev_params = nullptr,
-                  void* y_next = nullptr, const float* y_gamma = nullptr, int y_dtype = DIMX_F32);
+                  void* y_next = nullptr, const float* y_gamma = nullptr, int y_dtype = DIMX_F32,
+                  const float* qkv0_table = nullptr, float* qkv0_out = nullptr, int qkv0_N = 0);
+// the first decoder layer's q/k/v as a table over the token ids (model.hip qkv0_table_build): id list of the build rounds,
+// slab-order sum of a round's projection into the table rows, and step 0's rows by start token
+int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s);
+int launch_sum_slabs_rows(const float* slabs, int nslab, long slab_stride, float* table, int id0, int rows, int M, int N,
+                          hipStream_t s);
+int launch_gather_start_rows(const float* table, int N, int rows, const int32_t* start, int start_div, float* out, int B,
+                             hipStream_t s);
 // generate(): zero the per-group step / done counters and store temperature + seed next to them (read by the sampler)
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
                       hipStream_t s);

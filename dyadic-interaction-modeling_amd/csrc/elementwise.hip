@@ -132,7 +132,8 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                                                      const float* __restrict__ pos_table, float pos_scale,
                                                      int pos_rows, const int32_t* __restrict__ dev_params,
                                                      void* __restrict__ y_next, const float* __restrict__ y_gamma,
-                                                     int y_bf16) {
+                                                     int y_bf16, const float* __restrict__ qkv0_table,
+                                                     float* __restrict__ qkv0_out, int qkv0_N) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint64_t step = step_dev ? (uint64_t)*step_dev : step_host;
     if (dev_params) {  // generate(): temperature / seed live in device memory so that the captured step graph
@@ -288,6 +289,26 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                 const int i = lane + 64 * k;
                 v[k] = src[i < nv ? i : nv - 1];
             }
+            if (qkv0_table) {
+                // the first layer's q/k/v of this token is a row of a table (no positional term in this decoder: the layer's
+                // input depends on the token alone).  Its loads go out with the embedding row's, behind the same dependent
+                // hop on the token, and land in slab 0 of the step's q/k/v buffer (the launcher checks qkv0_N <= 12 * 256).
+                const float4* qs = (const float4*)(qkv0_table + (size_t)tok * qkv0_N);
+                float4* qd = (float4*)(qkv0_out + (size_t)row * qkv0_N);
+                const int nq = qkv0_N / 4;
+                float4 w[12];
+#pragma unroll
+                for (int k = 0; k < 12; ++k) {
+                    const int i = lane + 64 * k;
+                    w[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (i < nq) w[k] = qs[i];
+                }
+#pragma unroll
+                for (int k = 0; k < 12; ++k) {
+                    const int i = lane + 64 * k;
+                    if (i < nq) qd[i] = w[k];
+                }
+            }
             if (with_pos) {
                 float2 q[16];
 #pragma unroll
@@ -383,6 +404,42 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const float* __restrict
     } else {
         for (int i = threadIdx.x; i < C / 4; i += blockDim.x) dst[i] = src[i];
     }
+}
+
+// ids[i] = min(i, rows - 1): the token ids of the q/k/v table's build rounds (the last round repeats the last id)
+__global__ void iota_clamp_kernel(int32_t* __restrict__ ids, int n, int rows) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ids[i] = i < rows ? i : rows - 1;
+}
+
+// table[id0 + m, :] = slab 0 + slab 1 + ... of row m of a split-K projection, added in slab order exactly as the
+// projection's consumers add them (load_f32_slabs, decode_attn_body.hpp); rows at or past `rows` (padding) are skipped
+__global__ __launch_bounds__(256) void sum_slabs_rows_kernel(const float* __restrict__ slabs, int nslab, long slab_stride,
+                                                             float* __restrict__ table, int id0, int rows, int M, int N) {
+    const int m = blockIdx.x;
+    if (m >= M || id0 + m >= rows) return;
+    const float4* src = (const float4*)(slabs + (size_t)m * N);
+    float4* dst = (float4*)(table + (size_t)(id0 + m) * N);
+    for (int i = threadIdx.x; i < N / 4; i += blockDim.x) {
+        float4 v = src[i];
+        for (int s = 1; s < nslab; ++s) {
+            const float4 t = *(const float4*)(slabs + (size_t)s * slab_stride + (size_t)m * N + 4 * i);
+            v.x = __fadd_rn(v.x, t.x); v.y = __fadd_rn(v.y, t.y); v.z = __fadd_rn(v.z, t.z); v.w = __fadd_rn(v.w, t.w);
+        }
+        dst[i] = v;
+    }
+}
+
+// out[b, :] = table[clamp(start[b / start_div]), :]: step 0's first-layer q/k/v (the clamp of embed_step_kernel)
+__global__ __launch_bounds__(256) void gather_start_rows_kernel(const float* __restrict__ table, int N, int rows,
+                                                                const int32_t* __restrict__ start, int start_div,
+                                                                float* __restrict__ out) {
+    const int b = blockIdx.x;
+    int tok = start[b / start_div];
+    tok = tok < 0 ? 0 : (tok >= rows ? rows - 1 : tok);
+    const float4* src = (const float4*)(table + (size_t)tok * N);
+    float4* dst = (float4*)(out + (size_t)b * N);
+    for (int i = threadIdx.x; i < N / 4; i += blockDim.x) dst[i] = src[i];
 }
 
 // x[b*n + t, :] += pos[t, :] * scale   (TransformerWrapper abs. positional embedding of the legacy decoder,
@@ -539,15 +596,19 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
                   int tok_col_from_step, int nslab, long slab_stride, float* logits_out, int logits_out_ld, int row0,
                   int rows_total, const float* emb_table, int emb_C, float* x_next, int32_t* step_rw, unsigned* done_ctr,
                   hipStream_t s, const float* pos_table, float pos_scale, int pos_rows, const int32_t* dev_params,
-                  void* y_next, const float* y_gamma, int y_dtype) {
+                  void* y_next, const float* y_gamma, int y_dtype, const float* qkv0_table, float* qkv0_out, int qkv0_N) {
     DIMX_REQUIRE(logits && tokens && R > 0, DIMX_ERR_ARG, "sample: bad arguments");
+    DIMX_REQUIRE(!qkv0_table || (x_next && qkv0_out && !pos_table && emb_C / 2 <= 16 * 64 && qkv0_N % 4 == 0 && qkv0_N > 0 &&
+                                 qkv0_N <= 12 * 256),
+                 DIMX_ERR_ARG, "sample: the q/k/v table rides on the fused embedding (no positional table) and holds rows of k * 4 <= 3072");
     DIMX_REQUIRE(!y_next || (x_next && y_gamma && emb_C % 128 == 0 && emb_C <= 2048), DIMX_ERR_ARG,
                  "sample: the fused pre-norm needs the fused embedding and a width of k * 128 <= 2048");
     const int wpb = R <= 1024 ? 1 : 4;  // one row per block for decode-sized batches: all CUs busy
     hipLaunchKernelGGL(sample_kernel, dim3(ceil_div(R, wpb)), dim3(64 * wpb), 0, s, logits, ld_logits, R, top_k,
                        temperature, noise, seed, step_dev, step_host, tokens, tok_ld, tok_col_from_step, nslab < 1 ? 1 : nslab,
                        slab_stride, logits_out, logits_out_ld, row0, rows_total, emb_table, emb_C, x_next, step_rw, done_ctr,
-                       pos_table, pos_scale, pos_rows, dev_params, y_next, y_gamma, y_dtype == DIMX_BF16 ? 1 : 0);
+                       pos_table, pos_scale, pos_rows, dev_params, y_next, y_gamma, y_dtype == DIMX_BF16 ? 1 : 0, qkv0_table,
+                       qkv0_out, qkv0_N);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
@@ -565,6 +626,30 @@ int launch_embed_step(const float* table, int C, int rows, const int32_t* start,
     DIMX_REQUIRE(C % 4 == 0, DIMX_ERR_ARG, "embed_step: C %% 4");
     hipLaunchKernelGGL(embed_step_kernel, dim3(B), dim3(256), 0, s, table, C, start, tokens, tok_ld, step_dev, x,
                        rows, start_div < 1 ? 1 : start_div, pos_table, pos_scale);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s) {
+    DIMX_REQUIRE(ids && n > 0 && rows > 0, DIMX_ERR_ARG, "iota_clamp: bad arguments");
+    hipLaunchKernelGGL(iota_clamp_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, ids, n, rows);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+int launch_sum_slabs_rows(const float* slabs, int nslab, long slab_stride, float* table, int id0, int rows, int M, int N,
+                          hipStream_t s) {
+    DIMX_REQUIRE(slabs && table && nslab >= 1 && M > 0 && N > 0 && N % 4 == 0 && slab_stride % 4 == 0 && id0 >= 0, DIMX_ERR_ARG,
+                 "sum_slabs_rows: bad arguments");
+    hipLaunchKernelGGL(sum_slabs_rows_kernel, dim3(M), dim3(256), 0, s, slabs, nslab, slab_stride, table, id0, rows, M, N);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+int launch_gather_start_rows(const float* table, int N, int rows, const int32_t* start, int start_div, float* out, int B,
+                             hipStream_t s) {
+    DIMX_REQUIRE(table && start && out && B > 0 && N > 0 && N % 4 == 0 && rows > 0, DIMX_ERR_ARG, "gather_start_rows: bad arguments");
+    hipLaunchKernelGGL(gather_start_rows_kernel, dim3(B), dim3(256), 0, s, table, N, rows, start, start_div < 1 ? 1 : start_div, out);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

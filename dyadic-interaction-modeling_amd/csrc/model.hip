@@ -461,6 +461,7 @@ static void free_packed(dimx_ctx* c) {
     for (void* p : c->dev_allocs) (void)hipFree(p);
     c->dev_allocs.clear();
     c->packed_mask = 0;
+    ++c->dec_epoch;   // every path that rewrites decoder weights on the device comes through here and re-packs (qkv0 table)
 }
 
 enum { COMP_VQ0 = 1, COMP_VQ1 = 2, COMP_ENC = 4, COMP_DEC = 8, COMP_ALL = 15, COMP_MESH = 16 };
@@ -594,6 +595,7 @@ static int ensure_packed(dimx_ctx* c, int need) {
             DIMX_TRY(pack_linear(c, {"vertice_map_reverse.2.weight"}, "vertice_map_reverse.2.bias", false, &c->mesh.l2));
         }
         c->packed_mask |= comp;
+        if (comp == COMP_DEC) ++c->dec_epoch;
     }
     c->graph_valid = false;
     return DIMX_OK;
@@ -902,6 +904,7 @@ int dimx_create(dimx_handle* h, int device_id, const dimx_dims* dims, int numeri
     c->use_chain = (nc && nc[0] == '1') ? 0 : 1;
     c->use_layer_chain = getenv("DIMX_NO_LAYER_CHAIN") ? 0 : 1;
     c->multi_tr = getenv("DIMX_NO_MULTI_TR") ? 0 : 1;
+    c->use_qkv0_table = getenv("DIMX_NO_QKV0_TABLE") ? 0 : 1;
     if (getenv("DIMX_LAYER_PROF")) {
         void* p = nullptr;
         if (hipMalloc(&p, (size_t)8 * 256 * 16 * 8) == hipSuccess) {
@@ -943,6 +946,7 @@ int dimx_destroy(dimx_handle h) {
     if (h->chain_err_dev) (void)hipFree(h->chain_err_dev);
     if (h->chain_stats_dev) (void)hipFree(h->chain_stats_dev);
     if (h->layer_prof_dev) (void)hipFree(h->layer_prof_dev);
+    if (h->qkv0_table) (void)hipFree(h->qkv0_table);
     if (h->chain_err_host) (void)hipHostFree(h->chain_err_host);
     free_packed(h);
     train_forget(h);   // the training plan cached for this handle (a later handle may reuse the address)
@@ -1900,12 +1904,73 @@ static bool gen_multi_tr(dimx_handle h, int S) {
     return S > 1 && h->multi_tr && h->at == DIMX_BF16 && h->decg.dim_head == 64;
 }
 
+// Every projection of the decode step whose output is a small [B, N] f32 matrix is a split-K GEMM writing per-split slabs;
+// the consumer (LayerNorm / attention / sampler) adds the slabs in order: deterministic, no atomics, and
+// the residual add rides along in the pre-norm kernel.
+static int slab_gemm_rows(dimx_handle h, int B, hipStream_t st, const void* A, int lda, const Linear& L, float* out, long stride,
+                          int* nsl) {
+    GemmArgs g;
+    gemm_lin(h, A, lda, L, B, g);
+    g.x3_decode = 1;   // f32 parity mode: the split-bf16 kernel, whatever B is
+    g.out_dtype = DIMX_F32;
+    g.out_slabs = 1;
+    // round 4: the f32 parity mode splits K too.  Slabs are plain stores added in slab order by the consumer -- deterministic,
+    // no atomics -- which is all "fixed summation order" asks for; without the split the mode's 64 x 64 tiles left most of
+    // the chip idle (M = 256: 72 blocks for the 1152-wide projections, 48 for cross-q, 32 for the logits; the K = 4608
+    // feed-forward projection ran 144 k-tiles on 72 CUs = 70 us): 261 of the mode's 505 ms per batch (profiles/r04_parity_*).
+    static const bool f32_split = getenv("DIMX_F32_NO_SPLIT") == nullptr;
+    if (f32_split) g.allow_splitk = 1;
+    g.slab_stride = stride;
+    gemm_set_plain_out(g, out, L.N);
+    *nsl = gemm_plan_splits(g);
+    g.force_splitk = *nsl;
+    return launch_gemm(g, st);
+}
+
+// May the first layer's q/k/v come from the table?  Only a decoder whose layer-0 input is the token embedding alone.
+static bool qkv0_table_supported(dimx_handle h) {
+    const DecGeom& dg = h->decg;
+    const int N = 3 * dg.heads * dg.dim_head;
+    return h->use_qkv0_table && !dg.abs_pos && h->dec.self_[0].qkv.N == N && N % 4 == 0 && N <= 12 * 256 && dg.dim % 4 == 0 &&
+           dg.dim / 2 <= 16 * 64;
+}
+
+// The table for projection launches of M rows: ceil(num_tokens / M) rounds of {embedding rows of the next M ids, the first layer's
+// pre-norm, the step's own q/k/v projection at M rows, slabs added in order into the table rows}; the last round (and M >
+// num_tokens) is padded by repeating the last id.  M is the step's M because the split count, hence the summation order,
+// follows from it (gemm_plan_splits).  Runs on the generation scratch, which is free before step 0; s.step must read 0.
+static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream_t st) {
+    const DecGeom& dg = h->decg;
+    const int DD = dg.dim, V = dg.num_tokens, N = h->dec.self_[0].qkv.N;
+    if (h->qkv0_table && h->qkv0_M == M && h->qkv0_at == h->at && h->qkv0_epoch == h->dec_epoch) return DIMX_OK;
+    if (!h->qkv0_table) {
+        DIMX_HIP(hipMalloc((void**)&h->qkv0_table, (size_t)V * N * sizeof(float)));
+        h->graph_valid = false;
+    }
+    h->qkv0_epoch = 0;
+    const int rounds = (V + M - 1) / M;
+    int32_t* ids = (int32_t*)s.logits;   // rounds * M < V + M ids; the logits slabs hold 8 * M * V words
+    DIMX_TRY(launch_iota_clamp(ids, rounds * M, V, st));
+    for (int r = 0; r < rounds; ++r) {
+        int ns = 0;
+        DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, ids + (size_t)r * M, nullptr, 0, s.step, s.x, M, 1, st));
+        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s.st_xr, s.y, h->dec.self_[0].ln_g, M, DD, st));
+        DIMX_TRY(slab_gemm_rows(h, M, st, s.y, DD, h->dec.self_[0].qkv, s.qkv, s.st_qkv, &ns));
+        DIMX_TRY(launch_sum_slabs_rows(s.qkv, ns, s.st_qkv, h->qkv0_table, r * M, V, M, N, st));
+    }
+    h->qkv0_M = M;
+    h->qkv0_at = h->at;
+    h->qkv0_epoch = h->dec_epoch;
+    ++h->qkv0_builds;
+    return DIMX_OK;
+}
+
 // one decoder step for the clip group [row0, row0 + B) of a batch of Btot clips:
 // x = emb(token) -> 4 x {self, cross, ff} -> logits -> sample -> step += 1
 static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, const int32_t* start,
                     const uint8_t* ctx_mask, int row0, int B, int Btot, int grp, int T, float temperature, int top_k,
                     const float* noise, uint64_t seed, int32_t* tokens, float* logits_out, hipStream_t st,
-                    bool embed_only = false, int S = 1) {
+                    bool embed_only = false, int S = 1, const float* qkv0 = nullptr) {
     const DecGeom& dg = h->decg;
     const int DD = dg.dim, heads = dg.heads, D = dg.dim_head, inner = heads * D;
     const int V = dg.num_tokens, n = gen_steps(h, T), Tp = tpad(T);
@@ -1932,32 +1997,18 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     tokens += (size_t)row0 * n;
     if (logits_out) logits_out += (size_t)row0 * n * V;
     // round 4: the sampler that writes the next step's embedding row also writes the first layer's pre-norm of it, so a step
-    // starts with y = LayerNorm(x) in place
+    // starts with y = LayerNorm(x) in place.  With the first layer's q/k/v table (qkv0) both write the token's table row into slab 0
+    // of s.qkv instead, and layer 0 starts at its attention.
     if (embed_only) {  // step 0 input = embedding of the start token (later steps: fused into the sampler)
         DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, start, tokens, n, s.step, s.x, B, S, st, pos, pos_scale));
-        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
+        if (qkv0)   // the first layer's q/k/v of the start token: a table row into slab 0 (nothing reads y before the layer rewrites it)
+            DIMX_TRY(launch_gather_start_rows(qkv0, 3 * inner, V, start, S, s.qkv, B, st));
+        else
+            DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
         return DIMX_OK;
     }
-    // Every projection whose output is a small [B, N] f32 matrix is a split-K GEMM writing per-split slabs;
-    // the consumer (LayerNorm / attention / sampler) adds the slabs in order: deterministic, no atomics, and
-    // the residual add rides along in the pre-norm kernel.
     auto slab_gemm = [&](const void* A, int lda, const Linear& L, float* out, long stride, int* nsl) -> int {
-        GemmArgs g;
-        gemm_lin(h, A, lda, L, B, g);
-        g.x3_decode = 1;   // f32 parity mode: the split-bf16 kernel, whatever B is
-        g.out_dtype = DIMX_F32;
-        g.out_slabs = 1;
-        // round 4: the f32 parity mode splits K too.  Slabs are plain stores added in slab order by the consumer -- deterministic,
-        // no atomics -- which is all "fixed summation order" asks for; without the split the mode's 64 x 64 tiles left most of
-        // the chip idle (M = 256: 72 blocks for the 1152-wide projections, 48 for cross-q, 32 for the logits; the K = 4608
-        // feed-forward projection ran 144 k-tiles on 72 CUs = 70 us): 261 of the mode's 505 ms per batch (profiles/r04_parity_*).
-        static const bool f32_split = getenv("DIMX_F32_NO_SPLIT") == nullptr;
-        if (f32_split) g.allow_splitk = 1;
-        g.slab_stride = stride;
-        gemm_set_plain_out(g, out, L.N);
-        *nsl = gemm_plan_splits(g);
-        g.force_splitk = *nsl;
-        return launch_gemm(g, st);
+        return slab_gemm_rows(h, B, st, A, lda, L, out, stride, nsl);
     };
     // XCD-local chain kernels (chain.hip) replace {projection, residual + LayerNorm, projection} triples by one launch
     const bool chain = gen_use_chain(h, B, S, grp);
@@ -2044,7 +2095,10 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         int ns = 0;
         if (l > 0)
             DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.self_[l].ln_g, B, DD, st));
-        DIMX_TRY(slab_gemm(s.y, DD, h->dec.self_[l].qkv, s.qkv, s0.st_qkv, &ns));
+        if (l == 0 && qkv0)
+            ns = 1;   // slab 0 already holds this token's q/k/v (the sampler / the start-token step copied the table row)
+        else
+            DIMX_TRY(slab_gemm(s.y, DD, h->dec.self_[l].qkv, s.qkv, s0.st_qkv, &ns));
         // the two attentions' arguments (self: q / new k / new v are the projection's split-K slabs; cross: the context K/V)
         DecodeAttnArgs sa, ca;
         memset(&sa, 0, sizeof(sa));
@@ -2168,7 +2222,8 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     }
     DIMX_TRY(launch_sample(s.logits, V, B, top_k, temperature, noise, seed, s.step, 0, tokens, n, 1, nlg, s0.st_lg,
                            logits_out, n, row0, Btot, h->dec.tok_emb, DD, s.x, s.step, (unsigned*)(s.step + 8), st, pos,
-                           pos_scale, n, s.step + 2, s.y, h->dec.self_[0].ln_g, h->at));
+                           pos_scale, n, s.step + 2, qkv0 ? nullptr : s.y, qkv0 ? nullptr : h->dec.self_[0].ln_g, h->at, qkv0,
+                           s.qkv, 3 * inner));
     return DIMX_OK;
 }
 
@@ -2216,6 +2271,12 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
     int G = h->gen_groups < 1 ? 1 : h->gen_groups;
     if (G > B) G = B;
     if (S > 1) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
+    // one group: every projection launch of the generation has R rows, and so has the table's build
+    const float* qkv0 = nullptr;
+    if (G == 1 && qkv0_table_supported(h)) {
+        DIMX_TRY(qkv0_table_build(h, s, R, st));
+        qkv0 = h->qkv0_table;
+    }
     int lo[dimx_ctx::kMaxGroups + 1];
     for (int g = 0; g <= G; ++g) lo[g] = (int)((long)R * g / G);
     hipStream_t gs[dimx_ctx::kMaxGroups];
@@ -2233,15 +2294,15 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
     }
     for (int g = 0; g < G; ++g)
         DIMX_TRY(gen_step(h, cp, s, start, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k, exp_noise,
-                          seed, tokens, logits_out, gs[g], true, S));
+                          seed, tokens, logits_out, gs[g], true, S, qkv0));
     if (!h->use_graph) {
         for (int t = 0; t < n; ++t)
             for (int g = 0; g < G; ++g)
                 DIMX_TRY(gen_step(h, cp, s, start, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
-                                  exp_noise, seed, tokens, logits_out, gs[g], false, S));
+                                  exp_noise, seed, tokens, logits_out, gs[g], false, S, qkv0));
     } else {
         // greedy vs sampling is decided from the device-side parameters; only shapes and pointers key the graph
-        GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0)};
+        GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0)};
         if (!(h->graph_valid && h->graph_key == key)) {
             h->graph_valid = false;
             if (!h->cap_stream) DIMX_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -2268,7 +2329,7 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
                     int rc = DIMX_OK;
                     for (int r = 0; r < reps && rc == DIMX_OK; ++r)
                         rc = gen_step(h, cp, s, start, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
-                                      exp_noise, seed, tokens, logits_out, h->cap_stream, false, S);
+                                      exp_noise, seed, tokens, logits_out, h->cap_stream, false, S, qkv0);
                     const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
                     if (rc != DIMX_OK) {
                         if (graph) (void)hipGraphDestroy(graph);
@@ -2393,6 +2454,7 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
 }
 
 int dimx_chain_faults(dimx_handle h) { return h ? h->chain_faults : 0; }
+int dimx_qkv0_table_builds(dimx_handle h) { return h ? h->qkv0_builds : 0; }
 
 int dimx_lstm_faults(dimx_handle h) { return h ? h->lstm_faults : 0; }
 

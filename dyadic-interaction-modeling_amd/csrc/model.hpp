@@ -187,6 +187,15 @@ struct dimx_ctx {
     hipEvent_t chain_err_ev = nullptr;
     int chain_faults = 0;               // generate calls whose chain kernels reported a fault and that were re-run without them
     int chain_fault_inject = 0;         // test hook: that many of the next generate calls launch the chain kernels with fault = 1
+    // The first decoder layer's q/k/v as a table over the token ids (decoders without positional embedding: the layer's input is
+    // LayerNorm(token_emb[tok]), one of num_tokens rows): built with the decode step's own kernels at the step's row count, read by
+    // the sampler and the start-token step instead of a projection GEMM per token (DIMX_NO_QKV0_TABLE=1: the GEMM, for A/B runs)
+    int use_qkv0_table = 1;
+    float* qkv0_table = nullptr;        // [num_tokens][3 * heads * dim_head] f32, slabs already added in slab order
+    int qkv0_M = 0, qkv0_at = -1;       // rows per projection launch and operand type the table was built at
+    uint64_t qkv0_epoch = 0;            // dec_epoch the table was built at (0 = never)
+    uint64_t dec_epoch = 1;             // bumped whenever the decoder's device weights are released or packed
+    int qkv0_builds = 0;
     // sampler generator window of a sharded batch (dimx_set_shard): this handle generates clips
     // [shard_row_off, shard_row_off + B) of shard_rows_total (0 = the call's own B)
     int shard_row_off = 0, shard_rows_total = 0;

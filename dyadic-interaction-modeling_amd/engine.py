@@ -279,6 +279,11 @@ class Engine:
         regenerated on the one-kernel-per-op step before generate() returned (0 = never happened)."""
         return int(self.lib.dimx_chain_faults(self.h))
 
+    def qkv0_table_builds(self):
+        """how often this handle built the first decoder layer's q/k/v table (once per rows-per-call, numeric mode and set
+        of decoder weights; 0 = generate() projects q/k/v at every step)."""
+        return int(self.lib.dimx_qkv0_table_builds(self.h))
+
     def debug_chain_fault(self, n_calls=1):
         """test hook: the next n_calls generate() calls run their chain kernels on a non-bijective placement."""
         L.check(self.lib.dimx_debug_chain_fault(self.h, int(n_calls)), "dimx_debug_chain_fault")

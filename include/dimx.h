@@ -224,6 +224,12 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
  * LayerNorm's precision guard (a residual row whose |mean| exceeds 8 standard deviations: the batch is regenerated with the
  * row-phase LayerNorm, the deferred form stays off for the handle, the event is counted here too). */
 int dimx_chain_faults(dimx_handle h);
+/* Decoders without positional embedding (variant 0): the first layer's q/k/v depend on the input token alone, so dimx_generate
+ * reads them from a table over the token ids instead of projecting them at every step.  The table is built with the decode
+ * step's own kernels (bit-identical rows) on first use and whenever the rows per call, the numeric mode or the decoder weights
+ * changed; this counts the builds of a handle (0 = the table is not in use: other variants, several generation groups, or
+ * DIMX_NO_QKV0_TABLE=1 in the environment at dimx_create). */
+int dimx_qkv0_table_builds(dimx_handle h);
 /* Test hook: the next n_calls dimx_generate calls launch their chain kernels with a deliberately non-bijective
  * (XCD, CU slot) placement (the blocks of every odd XCD claim the slots of its even neighbour). */
 int dimx_debug_chain_fault(dimx_handle h, int n_calls);
