@@ -482,20 +482,34 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
                   hipStream_t s, const float* pos_table = nullptr, float pos_scale = 0.f, int pos_rows = 0,
                   const int32_t* dev_params = nullptr,
                   void* y_next = nullptr, const float* y_gamma = nullptr, int y_dtype = DIMX_F32,
-                  const float* qkv0_table = nullptr, float* qkv0_out = nullptr, int qkv0_N = 0);
+                  const float* qkv0_table = nullptr, float* qkv0_out = nullptr, int qkv0_N = 0,
+                  // prompted generation: rows whose next position lies inside their clip's prompt [clips, prompt_ld] take its token
+                  // (clip = row / prompt_div; length clamp(prompt_len, dev_params[8] + 1, prompt_max), NULL = prompt_max);
+                  // epoch_rw: a second counter advanced with the step counter (steps done in this call)
+                  const int32_t* prompt = nullptr, int prompt_ld = 0, int prompt_max = 0, const int32_t* prompt_len = nullptr,
+                  int prompt_div = 1, int32_t* epoch_rw = nullptr);
 // the first decoder layer's q/k/v as a table over the token ids (model.hip qkv0_table_build): id list of the build rounds,
 // slab-order sum of a round's projection into the table rows, and step 0's rows by start token
 int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s);
 int launch_sum_slabs_rows(const float* slabs, int nslab, long slab_stride, float* table, int id0, int rows, int M, int N,
                           hipStream_t s);
 int launch_gather_start_rows(const float* table, int N, int rows, const int32_t* start, int start_div, float* out, int B,
-                             hipStream_t s);
-// generate(): zero the per-group step / done counters and store temperature + seed next to them (read by the sampler)
+                             hipStream_t s, int start_ld = 1);
+// generate(): the per-group step counters = step0, done counters = 0, and temperature + seed next to them (read by the sampler)
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
-                      hipStream_t s);
+                      hipStream_t s, int step0 = 0);
 int launch_embed_step(const float* table, int C, int rows, const int32_t* start, const int32_t* tokens, int tok_ld,
                       const int32_t* step_dev, float* x, int B, int start_div, hipStream_t s,
-                      const float* pos_table = nullptr, float pos_scale = 0.f);
+                      const float* pos_table = nullptr, float pos_scale = 0.f, int start_ld = 1, int start_step = 0);
+// prompted generation's prefill (kv_prefill.hip): head rows [B, n, H*64] -> the generation cache [B*S, H, T, 64] (clip rows
+// broadcast to the S samples; positions >= n untouched); the f32 mode's V^T [B*H, 64, ld_t] -> the same cache; a
+// channel-contiguous V [B*H, ld_rows, 64] -> V^T [B*H, 64, ld_t] (positions n .. ld_t written as 0); the prompt's input ids of
+// the prefilled positions + its own tokens into the output columns < n0
+int launch_kv_rows_to_cache(int dtype, const void* src, void* cache, int B, int n, int H, int T, int S, hipStream_t st);
+int launch_kv_vt_to_cache(const float* vt, int ld_t, float* cache, int B, int n, int H, int T, int S, hipStream_t st);
+int launch_kv_rows_to_vt(const float* v_rows, int ld_rows, float* vt, int ld_t, int B, int n, int H, hipStream_t st);
+int launch_prompt_rows(const int32_t* prompt, int ld, int B, int n0, int V, int S, int32_t* inp, int32_t* tokens, int tok_ld,
+                       hipStream_t st);
 int launch_add_pos_rows(float* x, const float* pos, int M, int n, int C, float scale, hipStream_t s);
 int launch_mask_lens(const uint8_t* mask, int32_t* lens, int B, int T, hipStream_t s);
 int launch_legacy_scramble(int out_dtype, const float* E, const int32_t* idx, const int32_t* lens, void* out, int B,

@@ -114,6 +114,8 @@ __device__ __forceinline__ uint64_t splitmix(uint64_t key, uint64_t ctr) {
     return z ^ (z >> 31);
 }
 
+constexpr int kSampleVocab = 512;   // rows of the logits / embedding table the sampler is written for (8 x 64 lanes)
+
 // Sampler of AutoregressiveWrapper.generate: top-k filter (k = 52), softmax(T), multinomial.
 // torch.multinomial(p, 1) == argmax(p / q), q ~ Exp(1) (tests/golden/sampler_multinomial.npz), so the
 // noise is an input: injected (parity) or drawn from a counter-based splitmix64 stream (production).
@@ -133,7 +135,10 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                                                      int pos_rows, const int32_t* __restrict__ dev_params,
                                                      void* __restrict__ y_next, const float* __restrict__ y_gamma,
                                                      int y_bf16, const float* __restrict__ qkv0_table,
-                                                     float* __restrict__ qkv0_out, int qkv0_N) {
+                                                     float* __restrict__ qkv0_out, int qkv0_N,
+                                                     const int32_t* __restrict__ prompt, int prompt_ld, int prompt_max,
+                                                     const int32_t* __restrict__ prompt_len, int prompt_div,
+                                                     int32_t* __restrict__ epoch_rw) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint64_t step = step_dev ? (uint64_t)*step_dev : step_host;
     if (dev_params) {  // generate(): temperature / seed live in device memory so that the captured step graph
@@ -175,9 +180,27 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
 #pragma unroll
         for (int c = 0; c < 8; ++c) lo[lane + 64 * c] = v[c];
     }
+    // Prompted generation (dimx_generate_prompted): while the next position still lies inside this clip's prompt the row
+    // takes the prompt's token instead of a sampled one -- before the token, the embedding row, the pre-norm and the q/k/v
+    // table row below are written.  plen = clamp(prompt_len, P0, Pmax), P0 - 1 = dev_params[8] (word 10 of the parameter block: the call's first step).
+    // One wave per row: the branch is wave-uniform, and a forced row skips the arg-max, top-k, softmax and noise work.
+    bool forced = false;
+    int tok = 0;
+    if (prompt) {
+        const int clip = row / prompt_div;
+        int plen = prompt_len ? prompt_len[clip] : prompt_max;
+        const int p0 = dev_params ? dev_params[8] + 1 : 1;
+        plen = plen < p0 ? p0 : (plen > prompt_max ? prompt_max : plen);
+        if ((int)step + 1 < plen) {
+            forced = true;
+            tok = prompt[(size_t)clip * prompt_ld + step + 1];
+            tok = tok < 0 ? 0 : (tok >= kSampleVocab ? kSampleVocab - 1 : tok);   // the clamp of embed_step_kernel
+        }
+    }
+    if (!forced) {
     wave_argmax(mx, mi);
     const bool greedy = temperature <= 0.f || (noise == nullptr && seed == 0);
-    int tok = mi;
+    tok = mi;
     if (!greedy) {
         uint32_t key[8];
 #pragma unroll
@@ -273,6 +296,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
         wave_argmax(best, bi);
         tok = bi;
     }
+    }  // !forced
     if (lane == 0) tokens[(size_t)row * tok_ld + (tok_col_from_step ? (int)step : 0)] = tok;
     if (x_next) {  // next step's decoder input: token embedding row (fused embed_step)
         const float2* src = (const float2*)(emb_table + (size_t)tok * emb_C);
@@ -376,21 +400,24 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
             if (prev == gridDim.x - 1) {
                 *done_ctr = 0u;
                 *step_rw = (int32_t)step + 1;
+                if (epoch_rw) *epoch_rw += 1;   // steps done in this call: the chain kernels' counter epoch
             }
         }
     }
 }
 
-// x[b, :] = token_emb[tok_b], tok_b = start[b] at step 0 else the token sampled at the previous step
+// x[b, :] = token_emb[tok_b], tok_b = start[b] (row stride start_ld) at the call's first step (start_step: 0, or P0 - 1 of a
+// prompted generation) else the token sampled at the previous step
 __global__ __launch_bounds__(256) void embed_step_kernel(const float* __restrict__ table, int C,
                                                          const int32_t* __restrict__ start,
                                                          const int32_t* __restrict__ tokens, int tok_ld,
                                                          const int32_t* __restrict__ step_dev, float* __restrict__ x,
                                                          int rows, int start_div,
-                                                         const float* __restrict__ pos_table, float pos_scale) {
+                                                         const float* __restrict__ pos_table, float pos_scale, int start_ld,
+                                                         int start_step) {
     const int b = blockIdx.x;
     const int step = *step_dev;
-    int tok = step == 0 ? start[b / start_div] : tokens[(size_t)b * tok_ld + step - 1];
+    int tok = step == start_step ? start[(size_t)(b / start_div) * start_ld] : tokens[(size_t)b * tok_ld + step - 1];
     tok = tok < 0 ? 0 : (tok >= rows ? rows - 1 : tok);
     const float4* src = (const float4*)(table + (size_t)tok * C);
     float4* dst = (float4*)(x + (size_t)b * C);
@@ -433,9 +460,9 @@ __global__ __launch_bounds__(256) void sum_slabs_rows_kernel(const float* __rest
 // out[b, :] = table[clamp(start[b / start_div]), :]: step 0's first-layer q/k/v (the clamp of embed_step_kernel)
 __global__ __launch_bounds__(256) void gather_start_rows_kernel(const float* __restrict__ table, int N, int rows,
                                                                 const int32_t* __restrict__ start, int start_div,
-                                                                float* __restrict__ out) {
+                                                                float* __restrict__ out, int start_ld) {
     const int b = blockIdx.x;
-    int tok = start[b / start_div];
+    int tok = start[(size_t)(b / start_div) * start_ld];
     tok = tok < 0 ? 0 : (tok >= rows ? rows - 1 : tok);
     const float4* src = (const float4*)(table + (size_t)tok * N);
     float4* dst = (float4*)(out + (size_t)b * N);
@@ -490,15 +517,19 @@ __global__ void legacy_scramble_kernel(const float* __restrict__ E, const int32_
 
 __global__ void step_inc_kernel(int32_t* step) { *step += 1; }
 
-// per clip group: [0] step counter = 0, [8] done counter = 0, [2] temperature bits, [4..5] seed, [6] global row
-// offset and [7] global row count of the sampler's counter-based generator (generate())
+// per clip group: [0] step counter = step0 (0, or P0 - 1 of a prompted generation), [8] done counter = 0, [2] temperature
+// bits, [4..5] seed, [6] global row offset and [7] global row count of the sampler's counter-based generator (generate()),
+// [9] steps done in this call = 0 (the chain kernels' counter epoch), [10] step0 again, constant over the call (the sampler's
+// clamp of the prompt lengths)
 __global__ void gen_params_kernel(int32_t* base, int groups, float temperature, uint64_t seed, int row_off,
-                                  int rows_total) {
+                                  int rows_total, int step0) {
     const int g = threadIdx.x;
     if (g >= groups) return;
     int32_t* p = base + 16 * g;
-    p[0] = 0;
+    p[0] = step0;
     p[8] = 0;
+    p[9] = 0;
+    p[10] = step0;
     p[2] = __builtin_bit_cast(int32_t, temperature);
     *(uint64_t*)(p + 4) = seed;
     p[6] = row_off;
@@ -596,8 +627,12 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
                   int tok_col_from_step, int nslab, long slab_stride, float* logits_out, int logits_out_ld, int row0,
                   int rows_total, const float* emb_table, int emb_C, float* x_next, int32_t* step_rw, unsigned* done_ctr,
                   hipStream_t s, const float* pos_table, float pos_scale, int pos_rows, const int32_t* dev_params,
-                  void* y_next, const float* y_gamma, int y_dtype, const float* qkv0_table, float* qkv0_out, int qkv0_N) {
+                  void* y_next, const float* y_gamma, int y_dtype, const float* qkv0_table, float* qkv0_out, int qkv0_N,
+                  const int32_t* prompt, int prompt_ld, int prompt_max, const int32_t* prompt_len, int prompt_div,
+                  int32_t* epoch_rw) {
     DIMX_REQUIRE(logits && tokens && R > 0, DIMX_ERR_ARG, "sample: bad arguments");
+    DIMX_REQUIRE(!prompt || (step_dev && tok_col_from_step && prompt_max >= 1 && prompt_ld >= prompt_max && prompt_div >= 1),
+                 DIMX_ERR_ARG, "sample: a prompt needs the device step counter, 1 <= prompt_max <= prompt_ld and rows per clip >= 1");
     DIMX_REQUIRE(!qkv0_table || (x_next && qkv0_out && !pos_table && emb_C / 2 <= 16 * 64 && qkv0_N % 4 == 0 && qkv0_N > 0 &&
                                  qkv0_N <= 12 * 256),
                  DIMX_ERR_ARG, "sample: the q/k/v table rides on the fused embedding (no positional table) and holds rows of k * 4 <= 3072");
@@ -608,24 +643,25 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
                        temperature, noise, seed, step_dev, step_host, tokens, tok_ld, tok_col_from_step, nslab < 1 ? 1 : nslab,
                        slab_stride, logits_out, logits_out_ld, row0, rows_total, emb_table, emb_C, x_next, step_rw, done_ctr,
                        pos_table, pos_scale, pos_rows, dev_params, y_next, y_gamma, y_dtype == DIMX_BF16 ? 1 : 0, qkv0_table,
-                       qkv0_out, qkv0_N);
+                       qkv0_out, qkv0_N, prompt, prompt_ld, prompt_max, prompt_len, prompt_div < 1 ? 1 : prompt_div, epoch_rw);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
 
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
-                      hipStream_t s) {
-    hipLaunchKernelGGL(gen_params_kernel, dim3(1), dim3(64), 0, s, base, groups, temperature, seed, row_off, rows_total);
+                      hipStream_t s, int step0) {
+    DIMX_REQUIRE(step0 >= 0, DIMX_ERR_ARG, "gen_params: negative first step");
+    hipLaunchKernelGGL(gen_params_kernel, dim3(1), dim3(64), 0, s, base, groups, temperature, seed, row_off, rows_total, step0);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
 
 int launch_embed_step(const float* table, int C, int rows, const int32_t* start, const int32_t* tokens, int tok_ld,
                       const int32_t* step_dev, float* x, int B, int start_div, hipStream_t s, const float* pos_table,
-                      float pos_scale) {
-    DIMX_REQUIRE(C % 4 == 0, DIMX_ERR_ARG, "embed_step: C %% 4");
+                      float pos_scale, int start_ld, int start_step) {
+    DIMX_REQUIRE(C % 4 == 0 && start_ld >= 1 && start_step >= 0, DIMX_ERR_ARG, "embed_step: C %% 4, start stride or step");
     hipLaunchKernelGGL(embed_step_kernel, dim3(B), dim3(256), 0, s, table, C, start, tokens, tok_ld, step_dev, x,
-                       rows, start_div < 1 ? 1 : start_div, pos_table, pos_scale);
+                       rows, start_div < 1 ? 1 : start_div, pos_table, pos_scale, start_ld, start_step);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
@@ -647,9 +683,11 @@ int launch_sum_slabs_rows(const float* slabs, int nslab, long slab_stride, float
 }
 
 int launch_gather_start_rows(const float* table, int N, int rows, const int32_t* start, int start_div, float* out, int B,
-                             hipStream_t s) {
-    DIMX_REQUIRE(table && start && out && B > 0 && N > 0 && N % 4 == 0 && rows > 0, DIMX_ERR_ARG, "gather_start_rows: bad arguments");
-    hipLaunchKernelGGL(gather_start_rows_kernel, dim3(B), dim3(256), 0, s, table, N, rows, start, start_div < 1 ? 1 : start_div, out);
+                             hipStream_t s, int start_ld) {
+    DIMX_REQUIRE(table && start && out && B > 0 && N > 0 && N % 4 == 0 && rows > 0 && start_ld >= 1, DIMX_ERR_ARG,
+                 "gather_start_rows: bad arguments");
+    hipLaunchKernelGGL(gather_start_rows_kernel, dim3(B), dim3(256), 0, s, table, N, rows, start, start_div < 1 ? 1 : start_div, out,
+                       start_ld);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

@@ -1168,6 +1168,40 @@ static void plan_gen(const dimx_ctx* c, Arena& ar, int B, int T, GenScratch& s) 
     s.kw = (unsigned long long*)ar.take(s.kw_cap * 8);
 }
 
+// Prompted generation (dimx_generate_prompted): the prompt of a call and the teacher-forced scratch of its prefill.
+// dimx_generate is the ld = Pmax = 1, step0 = 0 case.
+struct GenPrompt {
+    const int32_t* tok;  // [B, ld] the prompt's tokens, one row per CLIP
+    int ld, Pmax;
+    const int32_t* len;  // [B] prompt lengths (clamped to [step0 + 1, Pmax] by the sampler) or nullptr = Pmax
+    int step0;           // P0 - 1: positions 0 .. step0 - 1 are prefilled, the first decode step is step0
+};
+struct PrefillScratch {
+    void *y, *q, *k, *vt, *o, *f;
+    float* h;
+    float* cvt;          // f32 mode: one layer's context V transposed to [B,H,64,Tp] (the f32 prefill attention reads V^T)
+    int32_t* inp;
+    unsigned long long* kw;
+    size_t kw_cap;
+};
+// The scratch is sized for the WHOLE batch (B clips x n0 positions), not for a chunk of clips, and lies behind the generation
+// scratch: the prefill writes the K/V cache, which must outlive it, and nothing else of the generation scratch.
+static void plan_prefill(const dimx_ctx* c, Arena& ar, int B, int n0, int T, PrefillScratch& s) {
+    const size_t M = (size_t)B * n0, es = es_of(c);
+    const int D = c->decg.dim, inner = c->decg.heads * c->decg.dim_head, np = tpad(n0);
+    s.h = (float*)ar.take(M * D * 4);
+    s.y = ar.take(M * D * es);
+    s.q = ar.take(M * inner * es);
+    s.k = ar.take(M * inner * es);
+    s.vt = ar.take((size_t)B * inner * np * es);
+    s.o = ar.take(M * inner * es);
+    s.f = ar.take(M * D * c->decg.ff_mult * es);
+    s.inp = (int32_t*)ar.take(M * 4);
+    s.kw_cap = (size_t)B * ((T + 63) / 64);
+    s.kw = (unsigned long long*)ar.take(s.kw_cap * 8);
+    s.cvt = c->at == DIMX_BF16 ? nullptr : (float*)ar.take((size_t)B * inner * tpad(T) * 4);
+}
+
 // SLM.forward_encoder: the encoder scratch is sized for the joint 2T pass; xs / xl keep the two first-stage
 // outputs (operand type), xj their time-concatenation, m2 the doubled padding mask
 struct MeshScratch {
@@ -1249,6 +1283,23 @@ static size_t workspace_bytes(const dimx_ctx* c, int B, int T, int S = 1) {
     }
     // + 64 KiB: the prefill stages plan their scratch once per clip group (ClipGroups below), every buffer 256-byte aligned
     return persist + align_up(scratch, 256) + 4096 + 65536;
+}
+
+// workspace of dimx_encode_ctx(for_generate = 1) + a prompted generation that prefills P0 - 1 positions: the generation
+// scratch and the prefill scratch behind it
+static size_t workspace_bytes_prompt(const dimx_ctx* c, int B, int T, int S, int P0) {
+    const size_t base = workspace_bytes(c, B, T, S);
+    if (P0 <= 1 || T < 2) return base;
+    Arena p(nullptr, 0);
+    CtxPersist cp;
+    plan_persist(c, p, B, T, cp);
+    Arena g(nullptr, 0);
+    GenScratch gs;
+    plan_gen(c, g, B * S, T, gs);
+    PrefillScratch ps;
+    plan_prefill(c, g, B, P0 - 1, T, ps);
+    const size_t need = align_up(p.off, 256) + align_up(g.off, 256) + 4096 + 65536;
+    return need > base ? need : base;
 }
 
 // x-transformers encoder stack (ContinuousTransformerWrapper, return_embeddings=True)
@@ -1418,6 +1469,11 @@ size_t dimx_workspace_bytes(dimx_handle h, int B, int T) {
 size_t dimx_workspace_bytes_samples(dimx_handle h, int B, int T, int n_samples) {
     if (!h || B < 1 || T < 1 || n_samples < 1 || T > h->d.max_seq_len) return 0;
     return workspace_bytes(h, B, T, n_samples);
+}
+
+size_t dimx_workspace_bytes_prompt(dimx_handle h, int B, int T, int n_samples, int P0) {
+    if (!h || B < 1 || T < 1 || n_samples < 1 || T > h->d.max_seq_len || P0 < 1 || P0 > (T > 1 ? T - 1 : 1)) return 0;
+    return workspace_bytes_prompt(h, B, T, n_samples, P0);
 }
 
 int dimx_vq_argmin(dimx_handle h, int which, const float* z, int N, int32_t* idx, float* best_d, float* margin,
@@ -1938,8 +1994,8 @@ static bool qkv0_table_supported(dimx_handle h) {
 // The table for projection launches of M rows: ceil(num_tokens / M) rounds of {embedding rows of the next M ids, the first layer's
 // pre-norm, the step's own q/k/v projection at M rows, slabs added in order into the table rows}; the last round (and M >
 // num_tokens) is padded by repeating the last id.  M is the step's M because the split count, hence the summation order,
-// follows from it (gemm_plan_splits).  Runs on the generation scratch, which is free before step 0; s.step must read 0.
-static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream_t st) {
+// follows from it (gemm_plan_splits).  Runs on the generation scratch, which is free before the first step; s.step must read step0.
+static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream_t st, int step0 = 0) {
     const DecGeom& dg = h->decg;
     const int DD = dg.dim, V = dg.num_tokens, N = h->dec.self_[0].qkv.N;
     if (h->qkv0_table && h->qkv0_M == M && h->qkv0_at == h->at && h->qkv0_epoch == h->dec_epoch) return DIMX_OK;
@@ -1953,7 +2009,7 @@ static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream
     DIMX_TRY(launch_iota_clamp(ids, rounds * M, V, st));
     for (int r = 0; r < rounds; ++r) {
         int ns = 0;
-        DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, ids + (size_t)r * M, nullptr, 0, s.step, s.x, M, 1, st));
+        DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, ids + (size_t)r * M, nullptr, 0, s.step, s.x, M, 1, st, nullptr, 0.f, 1, step0));
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s.st_xr, s.y, h->dec.self_[0].ln_g, M, DD, st));
         DIMX_TRY(slab_gemm_rows(h, M, st, s.y, DD, h->dec.self_[0].qkv, s.qkv, s.st_qkv, &ns));
         DIMX_TRY(launch_sum_slabs_rows(s.qkv, ns, s.st_qkv, h->qkv0_table, r * M, V, M, N, st));
@@ -1967,7 +2023,7 @@ static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream
 
 // one decoder step for the clip group [row0, row0 + B) of a batch of Btot clips:
 // x = emb(token) -> 4 x {self, cross, ff} -> logits -> sample -> step += 1
-static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, const int32_t* start,
+static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, const GenPrompt& pr,
                     const uint8_t* ctx_mask, int row0, int B, int Btot, int grp, int T, float temperature, int top_k,
                     const float* noise, uint64_t seed, int32_t* tokens, float* logits_out, hipStream_t st,
                     bool embed_only = false, int S = 1, const float* qkv0 = nullptr) {
@@ -1992,7 +2048,10 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     s.step = s0.step + 16 * grp;
     // with S samples per clip, rows are samples (row = clip * S + sample); start / mask / cross K/V are per clip
     const int clip0 = row0 / S, nclip = B / S;
-    start += clip0;
+    // the first step's input is column step0 of the prompt; later steps inside a clip's prompt are forced by the sampler
+    const int32_t* start = pr.tok + (size_t)clip0 * pr.ld + pr.step0;
+    const int32_t* forced = pr.Pmax > 1 ? pr.tok + (size_t)clip0 * pr.ld : nullptr;
+    const int32_t* forced_len = pr.len ? pr.len + clip0 : nullptr;
     ctx_mask += (size_t)clip0 * T;
     tokens += (size_t)row0 * n;
     if (logits_out) logits_out += (size_t)row0 * n * V;
@@ -2000,9 +2059,9 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     // starts with y = LayerNorm(x) in place.  With the first layer's q/k/v table (qkv0) both write the token's table row into slab 0
     // of s.qkv instead, and layer 0 starts at its attention.
     if (embed_only) {  // step 0 input = embedding of the start token (later steps: fused into the sampler)
-        DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, start, tokens, n, s.step, s.x, B, S, st, pos, pos_scale));
+        DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, start, tokens, n, s.step, s.x, B, S, st, pos, pos_scale, pr.ld, pr.step0));
         if (qkv0)   // the first layer's q/k/v of the start token: a table row into slab 0 (nothing reads y before the layer rewrites it)
-            DIMX_TRY(launch_gather_start_rows(qkv0, 3 * inner, V, start, S, s.qkv, B, st));
+            DIMX_TRY(launch_gather_start_rows(qkv0, 3 * inner, V, start, S, s.qkv, B, st, pr.ld));
         else
             DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
         return DIMX_OK;
@@ -2051,7 +2110,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         }
         c.counters = s0.chain_ctr + (size_t)site * kChainSiteWords;
         c.seen = c.counters + 8 * 16;
-        c.step = s.step;
+        c.step = s.step + 9;   // steps done in this call (== the step counter unless a prompt was prefilled)
         c.err = h->chain_err_dev;
         c.fault = h->chain_fault_inject > 0 ? 1 : 0;
         return launch_chain(c, st);
@@ -2081,7 +2140,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         lc.ld_qc = inner;
         lc.counters = s0.chain_ctr + (size_t)(3 * dg.depth + 1 + l) * kChainSiteWords;
         lc.seen = lc.counters + 8 * 16;
-        lc.step = s.step;
+        lc.step = s.step + 9;
         lc.err = h->chain_err_dev;
         lc.fault = h->chain_fault_inject > 0 ? 1 : 0;
         lc.sc_stride = (T + 15) / 16 * 16;
@@ -2223,7 +2282,97 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     DIMX_TRY(launch_sample(s.logits, V, B, top_k, temperature, noise, seed, s.step, 0, tokens, n, 1, nlg, s0.st_lg,
                            logits_out, n, row0, Btot, h->dec.tok_emb, DD, s.x, s.step, (unsigned*)(s.step + 8), st, pos,
                            pos_scale, n, s.step + 2, qkv0 ? nullptr : s.y, qkv0 ? nullptr : h->dec.self_[0].ln_g, h->at, qkv0,
-                           s.qkv, 3 * inner));
+                           s.qkv, 3 * inner, forced, pr.ld, pr.Pmax, forced_len, S, s.step + 9));
+    return DIMX_OK;
+}
+
+// Prefill of a prompted generation: the teacher-forced decoder stack of dimx_decode_tf over the positions 0 .. n0 - 1 of every
+// clip (no key mask), every layer's self-attention K / V stored into the generation cache [B*S, H, T, 64] (kv_prefill.hip), no
+// output head, and the last layer stops after its q/k/v projection -- its attentions and feed-forward feed nothing.
+// Cross attention reads the context K / V where dimx_encode_ctx(for_generate = 1) left them, [B, H, Tp, 64]: the bf16
+// attention takes that layout as it is (row-major V); the f32 attention reads V^T, so the f32 mode transposes one layer's V
+// into scratch first (a copy, not a second projection of the context).
+static int gen_prefill(dimx_handle h, const CtxPersist& cp, const GenScratch& gs, const PrefillScratch& s, const GenPrompt& pr,
+                       const uint8_t* ctx_mask, int B, int T, int S, int32_t* tokens, hipStream_t st) {
+    const DecGeom& dg = h->decg;
+    const int n0 = pr.step0, M = B * n0, DD = dg.dim, heads = dg.heads, D = dg.dim_head;
+    const int inner = heads * D, np = tpad(n0), Tp = tpad(T), V = dg.num_tokens;
+    DIMX_TRY(launch_prompt_rows(pr.tok, pr.ld, B, n0, V, S, s.inp, tokens, gen_steps(h, T), st));
+    DIMX_TRY(launch_gather_rows(DIMX_F32, h->dec.tok_emb, DD, V, s.inp, s.h, DD, M, DD, st));
+    const float scale = 1.0f / sqrtf((float)D);
+    const bool rowv = qkv_row_v(h->at, D);
+    for (int l = 0; l < dg.depth; ++l) {
+        GemmArgs g;
+        AttnArgs a;
+        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.self_[l].ln_g, nullptr, M, DD, st));
+        gemm_lin(h, s.y, DD, h->dec.self_[l].qkv, M, g);
+        g.out_dtype = h->at;
+        set_qkv_out(g, s.q, s.k, s.vt, n0, heads, D, np, rowv);
+        DIMX_TRY(launch_gemm(g, st));
+        DIMX_TRY(launch_kv_rows_to_cache(h->at, s.k, gs.sk[l], B, n0, heads, T, S, st));
+        if (rowv)
+            DIMX_TRY(launch_kv_rows_to_cache(h->at, s.vt, gs.sv[l], B, n0, heads, T, S, st));
+        else
+            DIMX_TRY(launch_kv_vt_to_cache((const float*)s.vt, np, (float*)gs.sv[l], B, n0, heads, T, S, st));
+        if (l == dg.depth - 1) break;
+        set_attn_packed(a, h->at, s.q, s.k, s.vt, s.o, B, heads, n0, n0, D, np, rowv);
+        a.scale = scale;
+        a.causal = 1;
+        a.kwords = s.kw;
+        a.kwords_cap = s.kw_cap;
+        DIMX_TRY(launch_attention(a, st));
+        gemm_lin(h, s.o, inner, h->dec.self_[l].out, M, g);
+        g.out_dtype = DIMX_F32;
+        g.residual = s.h;
+        g.ldr = DD;
+        gemm_set_plain_out(g, s.h, DD);
+        DIMX_TRY(launch_gemm(g, st));
+        // cross attention over the context K / V of the generation layout
+        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.cross[l].ln_g, nullptr, M, DD, st));
+        gemm_lin(h, s.y, DD, h->dec.cross[l].qkv, M, g);
+        g.out_dtype = h->at;
+        gemm_set_plain_out(g, s.q, inner);
+        DIMX_TRY(launch_gemm(g, st));
+        const void* cv = cp.cv[l];
+        if (!rowv) {
+            DIMX_TRY(launch_kv_rows_to_vt((const float*)cp.cv[l], Tp, s.cvt, Tp, B, T, heads, st));
+            cv = s.cvt;
+        }
+        set_attn_packed(a, h->at, s.q, cp.ck[l], cv, s.o, B, heads, n0, T, D, Tp, rowv);
+        a.k_sb = (long)heads * Tp * D;
+        a.k_sh = (long)Tp * D;
+        a.k_st = D;
+        if (rowv) {
+            a.v_sb = (long)heads * Tp * D;
+            a.v_sh = (long)Tp * D;
+            a.v_st = D;
+        }
+        a.scale = scale;
+        a.kmask = ctx_mask;
+        a.kmask_ld = T;
+        a.kwords = s.kw;
+        a.kwords_cap = s.kw_cap;
+        DIMX_TRY(launch_attention(a, st));
+        gemm_lin(h, s.o, inner, h->dec.cross[l].out, M, g);
+        g.out_dtype = DIMX_F32;
+        g.residual = s.h;
+        g.ldr = DD;
+        gemm_set_plain_out(g, s.h, DD);
+        DIMX_TRY(launch_gemm(g, st));
+        // feed forward
+        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.ff[l].ln_g, nullptr, M, DD, st));
+        gemm_lin(h, s.y, DD, h->dec.ff[l].f1, M, g);
+        g.out_dtype = h->at;
+        g.act = ACT_GELU_ERF;
+        gemm_set_plain_out(g, s.f, DD * dg.ff_mult);
+        DIMX_TRY(launch_gemm(g, st));
+        gemm_lin(h, s.f, DD * dg.ff_mult, h->dec.ff[l].f2, M, g);
+        g.out_dtype = DIMX_F32;
+        g.residual = s.h;
+        g.ldr = DD;
+        gemm_set_plain_out(g, s.h, DD);
+        DIMX_TRY(launch_gemm(g, st));
+    }
     return DIMX_OK;
 }
 
@@ -2231,9 +2380,13 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
 
 extern "C" {
 
-static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, int B, int T, int n_samples,
+// One implementation for dimx_generate (pr = {start, 1, 1, NULL, 0}) and dimx_generate_prompted.  keep_prefill: the call repeats
+// a generation whose prefill already ran in this workspace (the regeneration after a chain fault): the decode steps write cache
+// positions >= step0 and token / logit columns >= step0 only, so the prefix is intact and only the counters start over.
+static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_prefill, const uint8_t* ctx_mask, int B, int T, int n_samples,
                          float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens,
-                         float* logits_out, void* ws, size_t ws_bytes, void* stream, bool* chain_used) {
+                         float* logits_out, void* ws, size_t ws_bytes, void* stream, bool* chain_used, bool prefill_only = false) {
+    const int32_t* start = pr.tok;
     const int S = n_samples < 1 ? 1 : n_samples;
     DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
                  "generate: n_samples %d not in {1,2,4,5,8,10}", n_samples);
@@ -2247,8 +2400,11 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
     GenScratch s;
     const int R = B * S;  // sequences generated in this call
     plan_gen(h, ar, R, T, s);
+    PrefillScratch ps;
+    if (pr.step0 > 0) plan_prefill(h, ar, B, pr.step0, T, ps);
     DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "generate: workspace overflow");
     const int n = gen_steps(h, T);
+    const int nrun = n - pr.step0;   // decode steps of this call
     if (h->use_chain && h->at == DIMX_BF16 && !h->chain_err_dev) {
         DIMX_HIP(hipMalloc((void**)&h->chain_err_dev, 64));
         DIMX_HIP(hipMemset(h->chain_err_dev, 0, 64));
@@ -2262,7 +2418,7 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
     // step / done counters = 0; temperature, seed and the sampler's global row window go to device memory so that
     // the captured step graph is independent of them
     DIMX_TRY(launch_gen_params(s.step, dimx_ctx::kMaxGroups, temperature, seed, h->shard_row_off * S,
-                               h->shard_rows_total * S, st));
+                               h->shard_rows_total * S, st, pr.step0));
     if (gen_multi_tr(h, S)) DIMX_TRY(launch_pack_key_words(ctx_mask, T, nullptr, B, T, s.kw, s.kw_cap, st));
     // Independent clip groups run as separate step graphs on separate streams: every decode kernel is
     // latency-bound at these sizes, so two groups in flight let one group's GEMM/LayerNorm chain overlap the
@@ -2274,8 +2430,18 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
     // one group: every projection launch of the generation has R rows, and so has the table's build
     const float* qkv0 = nullptr;
     if (G == 1 && qkv0_table_supported(h)) {
-        DIMX_TRY(qkv0_table_build(h, s, R, st));
+        DIMX_TRY(qkv0_table_build(h, s, R, st, pr.step0));
         qkv0 = h->qkv0_table;
+    }
+    if (pr.step0 > 0 && !keep_prefill) {
+        // the prefill forms no logits: those columns of logits_out read zero
+        if (logits_out)
+            DIMX_HIP(hipMemset2DAsync(logits_out, (size_t)n * h->decg.num_tokens * 4, 0, (size_t)pr.step0 * h->decg.num_tokens * 4, R, st));
+        DIMX_TRY(gen_prefill(h, cp, s, ps, pr, ctx_mask, B, T, S, tokens, st));
+    }
+    if (prefill_only) {   // tools/bench_prompt.py: the prefill stage alone
+        *chain_used = false;
+        return DIMX_OK;
     }
     int lo[dimx_ctx::kMaxGroups + 1];
     for (int g = 0; g <= G; ++g) lo[g] = (int)((long)R * g / G);
@@ -2293,16 +2459,19 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
         }
     }
     for (int g = 0; g < G; ++g)
-        DIMX_TRY(gen_step(h, cp, s, start, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k, exp_noise,
+        DIMX_TRY(gen_step(h, cp, s, pr, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k, exp_noise,
                           seed, tokens, logits_out, gs[g], true, S, qkv0));
     if (!h->use_graph) {
-        for (int t = 0; t < n; ++t)
+        for (int t = 0; t < nrun; ++t)
             for (int g = 0; g < G; ++g)
-                DIMX_TRY(gen_step(h, cp, s, start, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
+                DIMX_TRY(gen_step(h, cp, s, pr, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
                                   exp_noise, seed, tokens, logits_out, gs[g], false, S, qkv0));
     } else {
-        // greedy vs sampling is decided from the device-side parameters; only shapes and pointers key the graph
-        GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0)};
+        // greedy vs sampling is decided from the device-side parameters; only shapes and pointers key the graph.  The prompt's
+        // pointers, row stride and width are kernel arguments of the sampler; P0 is not (the counters' start value and the
+        // number of launches below), so a call with another P0 replays the same graphs.
+        GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0),
+                     pr.len, pr.ld, pr.Pmax};
         if (!(h->graph_valid && h->graph_key == key)) {
             h->graph_valid = false;
             if (!h->cap_stream) DIMX_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -2328,7 +2497,7 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
                     DIMX_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
                     int rc = DIMX_OK;
                     for (int r = 0; r < reps && rc == DIMX_OK; ++r)
-                        rc = gen_step(h, cp, s, start, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
+                        rc = gen_step(h, cp, s, pr, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
                                       exp_noise, seed, tokens, logits_out, h->cap_stream, false, S, qkv0);
                     const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
                     if (rc != DIMX_OK) {
@@ -2346,12 +2515,12 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
         {
             const int U = h->graph_unroll;
             int t = 0;
-            for (; U > 1 && t + U <= n; t += U)
+            for (; U > 1 && t + U <= nrun; t += U)
                 for (int g = 0; g < G; ++g)
                     if (h->graph_multi[g]) DIMX_HIP(hipGraphLaunch(h->graph_multi[g], gs[g]));
                     else
                         for (int r = 0; r < U; ++r) DIMX_HIP(hipGraphLaunch(h->graph_exec[g], gs[g]));
-            for (; t < n; ++t)
+            for (; t < nrun; ++t)
                 for (int g = 0; g < G; ++g) DIMX_HIP(hipGraphLaunch(h->graph_exec[g], gs[g]));
         }
     }
@@ -2374,11 +2543,11 @@ static int generate_impl(dimx_handle h, const int32_t* start, const uint8_t* ctx
 // repair it, so the call that used them checks their flags before it returns: it waits for its own generation (the caller
 // is about to read the tokens anyway) and, on a fault, regenerates the same batch on the one-kernel-per-op step and keeps
 // the chain path off for this handle.  Round 2 reported the fault one call late.
-int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, int B, int T, int n_samples,
-                  float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out,
-                  void* ws, size_t ws_bytes, void* stream) {
+static int generate_checked(dimx_handle h, const dimx::GenPrompt& pr, const uint8_t* ctx_mask, int B, int T, int n_samples,
+                            float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out,
+                            void* ws, size_t ws_bytes, void* stream) {
     bool chain_used = false;
-    DIMX_TRY(generate_impl(h, start, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
+    DIMX_TRY(generate_impl(h, pr, false, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
                            ws_bytes, stream, &chain_used));
     if (h->chain_fault_inject > 0) --h->chain_fault_inject;
     if (!chain_used) return DIMX_OK;
@@ -2432,7 +2601,7 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
         fprintf(stderr, "dimx: a residual row's mean exceeds 8 standard deviations; this batch is regenerated with the row-phase "
                         "LayerNorm and the deferred form stays off for this handle\n");
     }
-    DIMX_TRY(generate_impl(h, start, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
+    DIMX_TRY(generate_impl(h, pr, true, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
                            ws_bytes, stream, &chain_used));
     if (!chain_used) return DIMX_OK;
     // the regeneration may still have run chain kernels (the bit-2 case keeps them on): it answers for its own flags too
@@ -2447,10 +2616,49 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
     h->use_chain = 0;
     fprintf(stderr, "dimx: the regenerated batch reported chain flags 0x%x again; regenerating on the one-kernel-per-op step, the "
                     "chain path stays off for this handle\n", e2);
-    DIMX_TRY(generate_impl(h, start, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
+    DIMX_TRY(generate_impl(h, pr, true, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
                            ws_bytes, stream, &chain_used));
     DIMX_REQUIRE(!chain_used, DIMX_ERR_STATE, "generate: the chain path is still active after it was switched off");
     return DIMX_OK;
+}
+
+int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, int B, int T, int n_samples,
+                  float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out,
+                  void* ws, size_t ws_bytes, void* stream) {
+    const dimx::GenPrompt pr{start, 1, 1, nullptr, 0};
+    return generate_checked(h, pr, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws, ws_bytes,
+                            stream);
+}
+
+int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
+                           const uint8_t* ctx_mask, int B, int T, int n_samples, float temperature, int top_k,
+                           const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out, int flags, void* ws,
+                           size_t ws_bytes, void* stream) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_prompted: prompts are implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    DIMX_REQUIRE(prompt && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
+                 "generate_prompted: need 1 <= Pmax <= T - 1 and ld_prompt >= Pmax (Pmax=%d T=%d ld_prompt=%d)", Pmax, T, ld_prompt);
+    DIMX_REQUIRE(P0 >= 1 && P0 <= Pmax, DIMX_ERR_ARG, "generate_prompted: need 1 <= P0 <= Pmax (P0=%d Pmax=%d)", P0, Pmax);
+    DIMX_REQUIRE((flags & ~3) == 0, DIMX_ERR_ARG, "generate_prompted: unknown flags 0x%x", flags);
+    const int S = n_samples < 1 ? 1 : n_samples;
+    const int p0 = (flags & 1) ? 1 : P0;   // bit 0: no prefill, the whole prompt goes through forced decode steps
+    // bit 1 is not part of the public flag set: tools/bench_prompt.py times the prefill stage alone with it
+    DIMX_REQUIRE(!(flags & 2) || p0 >= 2, DIMX_ERR_ARG, "generate_prompted: flags bit 1 (the prefill stage alone) without a prefill (P0=%d, flags 0x%x)",
+                 P0, flags);
+    DIMX_REQUIRE(p0 == 1 || h->decg.dim_head == 64, DIMX_ERR_ARG, "generate_prompted: the prefill needs 64-wide heads");
+    DIMX_REQUIRE(B >= 1 && T <= h->d.max_seq_len, DIMX_ERR_ARG, "B=%d T=%d out of range (T <= %d)", B, T, h->d.max_seq_len);
+    const size_t need = dimx::workspace_bytes_prompt(h, B, T, S, p0);
+    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "generate_prompted: workspace %zu < required %zu (dimx_workspace_bytes_prompt)",
+                 ws_bytes, need);
+    const dimx::GenPrompt pr{prompt, ld_prompt, Pmax, prompt_len, p0 - 1};
+    if (flags & 2) {   // the prefill stage alone, nothing is generated
+        bool chain_used = false;
+        return generate_impl(h, pr, false, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
+                             ws_bytes, stream, &chain_used, true);
+    }
+    return generate_checked(h, pr, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws, ws_bytes,
+                            stream);
 }
 
 int dimx_chain_faults(dimx_handle h) { return h ? h->chain_faults : 0; }

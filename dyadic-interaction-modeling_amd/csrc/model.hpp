@@ -118,8 +118,10 @@ struct GraphKey {
     uint64_t seed;
     const void *start, *mask, *tokens, *logits_out;
     int groups;
+    const void* prompt_len;   // prompted generation: the sampler's other prompt arguments (`start` is the prompt itself)
+    int ld_prompt, Pmax;
     bool operator==(const GraphKey& o) const {
-        return groups == o.groups && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
+        return groups == o.groups && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
                noise == o.noise && seed == o.seed && start == o.start && mask == o.mask && tokens == o.tokens &&
                logits_out == o.logits_out;
     }

@@ -76,8 +76,12 @@ class Engine:
         return self.lib.dimx_missing_weights(self.h)
 
     # ------------------------------------------------------------------ workspace
-    def workspace(self, B, T, n_samples=1):
-        need = self.lib.dimx_workspace_bytes_samples(self.h, B, T, n_samples)
+    def workspace(self, B, T, n_samples=1, prompt_frames=1):
+        """``prompt_frames`` P0 > 1: room for the prefill of a prompted generation too (dimx_workspace_bytes_prompt)."""
+        if prompt_frames > 1:
+            need = self.lib.dimx_workspace_bytes_prompt(self.h, B, T, n_samples, int(prompt_frames))
+        else:
+            need = self.lib.dimx_workspace_bytes_samples(self.h, B, T, n_samples)
         if need == 0:
             raise L.DimxError("dimx_workspace_bytes(%d,%d) = 0" % (B, T))
         if self._ws is None or self._ws_bytes < need:
@@ -156,7 +160,7 @@ class Engine:
         sampler's counter-based generator depends on it); (0, 0) = unsharded."""
         L.check(self.lib.dimx_set_shard(self.h, int(row_offset), int(rows_total)), "dimx_set_shard")
 
-    def encode_ctx(self, v_speaker, v_audio, mask_u8, for_generate, return_x_s=False, n_samples=1):
+    def encode_ctx(self, v_speaker, v_audio, mask_u8, for_generate, return_x_s=False, n_samples=1, prompt_frames=1):
         B, T, _ = v_speaker.shape
         v_speaker = v_speaker.to(torch.float32).contiguous()
         v_audio = v_audio.to(torch.float32).contiguous() if v_audio is not None else None
@@ -164,7 +168,7 @@ class Engine:
             raise L.DimxError("encode_ctx: the SLMFT variant needs v_audio")
         self._chk(v_speaker, v_audio, mask_u8)
         x_s = torch.empty(B, T, self.dims.dim, dtype=torch.float32, device=self.device) if return_x_s else None
-        ws, wsb = self.workspace(B, T, n_samples)   # the generate call that follows must see the same workspace
+        ws, wsb = self.workspace(B, T, n_samples, prompt_frames)   # the generate call that follows must see the same workspace
         L.check(self.lib.dimx_encode_ctx(self.h, L.ptr(v_speaker), L.ptr(v_audio), L.ptr(mask_u8), B, T,
                                          1 if for_generate else 0, L.ptr(x_s), ws, wsb, self._s()),
                 "dimx_encode_ctx")
@@ -186,7 +190,7 @@ class Engine:
                                          L.ptr(x_j), ws, wsb, self._s()), "dimx_slm_encode")
         return x_s, x_l, x_j
 
-    def set_context(self, x, v_audio, which_patch=0, for_generate=False, T=None, n_samples=1):
+    def set_context(self, x, v_audio, which_patch=0, for_generate=False, T=None, n_samples=1, prompt_frames=1):
         """context = cat(x[:, :T] + patch_embed_dec_{s|l}, v_audio) + cross K/V; x [B, rows>=T, dim] f32."""
         B, rows, _ = x.shape
         T = T or rows
@@ -194,7 +198,7 @@ class Engine:
         v_audio = v_audio.to(torch.float32).contiguous()
         assert x.stride(2) == 1 and x.stride(1) == x.shape[2], "x rows must be dense"
         ldx_rows = x.stride(0) // x.shape[2]
-        ws, wsb = self.workspace(B, T, n_samples)
+        ws, wsb = self.workspace(B, T, n_samples, prompt_frames)
         L.check(self.lib.dimx_set_context(self.h, ctypes.c_void_p(x.data_ptr()), ldx_rows, which_patch, L.ptr(v_audio),
                                           B, T, 1 if for_generate else 0, ws, wsb, self._s()), "dimx_set_context")
 
@@ -231,8 +235,19 @@ class Engine:
         return logits, row_loss, amax
 
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
-                 n_samples=1):
-        """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V."""
+                 n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False):
+        """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
+
+        ``prompt`` [B,Pmax] (1 <= Pmax <= T-1; ``start`` is then ignored and may be None): continue the given tokens
+        (dimx_generate_prompted, include/dimx.h).  ``prompt_len`` [B] int32 on the device: per-clip prompt lengths, clamped to
+        [prefill, Pmax]; None = Pmax.  ``prefill`` is P0, the prefix that is prefilled by one teacher-forced pass (default:
+        Pmax when ``prompt_len`` is None, else 1); the context must have been built with ``prompt_frames >= prefill`` (a
+        workspace grown in between invalidates it).  ``no_prefill``: the whole prompt goes through forced decode steps.
+        Returned tokens keep their shape: column c is position c+1, columns < plen-1 repeat the prompt; with
+        ``return_logits`` the columns < P0-1 are zero."""
+        if prompt is not None:
+            return self._generate_prompted(prompt, prompt_len, prefill, no_prefill, mask_u8, T, temperature, top_k, noise, seed,
+                                           return_logits, n_samples)
         B = start.shape[0]
         R = B * n_samples
         start = start.to(torch.int32).contiguous()
@@ -249,6 +264,29 @@ class Engine:
                                        int(top_k),
                                        L.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(tokens), L.ptr(lg), ws,
                                        wsb, self._s()), "dimx_generate")
+        return (tokens, lg) if return_logits else tokens
+
+    def _generate_prompted(self, prompt, prompt_len, prefill, no_prefill, mask_u8, T, temperature, top_k, noise, seed,
+                           return_logits, n_samples):
+        B, Pmax = prompt.shape
+        R = B * n_samples
+        prompt = prompt.to(torch.int32).contiguous()
+        prompt_len = prompt_len.to(torch.int32).contiguous() if prompt_len is not None else None
+        P0 = int(prefill) if prefill is not None else (Pmax if prompt_len is None else 1)
+        if noise is not None:
+            noise = noise.to(torch.float32).contiguous()
+            assert tuple(noise.shape) == (self.n_gen(T), R, self.dims.num_tokens)
+        self._chk(prompt, prompt_len, mask_u8, noise)
+        n = self.n_gen(T)
+        tokens = torch.empty(R, n, dtype=torch.int32, device=self.device)
+        lg = torch.empty(R, n, self.dims.num_tokens, dtype=torch.float32, device=self.device) if return_logits else None
+        # the workspace the context was built in, never grown here (that would drop the context): the library refuses a
+        # prefill it is too small for (DIMX_ERR_WORKSPACE, before any launch) -- build the context with prompt_frames >= prefill
+        ws, wsb = self.workspace(B, T, n_samples)
+        L.check(self.lib.dimx_generate_prompted(self.h, L.ptr(prompt), int(prompt.stride(0)), L.ptr(prompt_len), int(Pmax), P0,
+                                                L.ptr(mask_u8), B, T, int(n_samples), float(temperature), int(top_k), L.ptr(noise),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(tokens), L.ptr(lg), 1 if no_prefill else 0,
+                                                ws, wsb, self._s()), "dimx_generate_prompted")
         return (tokens, lg) if return_logits else tokens
 
     def mesh_head(self, motion, template=None, safe=False, out=None):

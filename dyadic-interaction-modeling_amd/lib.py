@@ -72,6 +72,9 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_size_t, c_void_p]),
     "dimx_generate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_uint64,
                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dimx_workspace_bytes_prompt": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "dimx_generate_prompted": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float,
+                                       c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dimx_train_num_params": (c_int, [c_void_p]),
     "dimx_train_total": (c_int64, [c_void_p]),
     "dimx_train_param_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),

@@ -61,6 +61,30 @@ def compact_by_mask(x, mask):
     return torch.where(prefix[..., None], xc, torch.zeros((), dtype=x.dtype, device=x.device)), lens
 
 
+def prompt_lengths(mask, prompt_frames, lengths=None):
+    """Prompted generation from a validity mask [B,T]: ``prompt_len`` [B] int32 on the mask's device =
+    clamp(valid frames per clip, 1, prompt_frames), and the host integer ``P0`` = the prefix every clip has, which is the part
+    that is prefilled: min(prompt_frames, min(lengths)) when the caller knows the clip lengths on the host (``lengths``, a
+    list of ints: the engine loops have ``src_len``), else the minimum of ``prompt_len`` -- ONE ``.item()``, a host
+    synchronisation per call."""
+    prompt_frames = int(prompt_frames)
+    plen = mask.bool().sum(1).clamp(1, prompt_frames).to(torch.int32)
+    if lengths is not None:
+        p0 = min(prompt_frames, min(int(n) for n in lengths))
+    else:
+        p0 = int(plen.min().item())
+    return plen, max(1, p0)
+
+
+def _check_prompt_frames(prompt_frames, T):
+    prompt_frames = int(prompt_frames)
+    if prompt_frames == 1:
+        return 1
+    if prompt_frames < 1 or prompt_frames >= T:
+        raise ValueError("prompt_frames=%d: a prompt holds 1 .. T-1 = %d frames (T=%d frames per clip)" % (prompt_frames, T - 1, T))
+    return prompt_frames
+
+
 class SLMFT(_EngineOwner):
     def __init__(self, config_path=None, vq_speaker_ckpt=None, vq_listener_ckpt=None,
                  synthetic_seed=20260928, numeric_mode=L.MODE_PARITY_F32):
@@ -109,14 +133,14 @@ class SLMFT(_EngineOwner):
         """reference :431-442 -> x_s [B,T,384] (rows of padded frames are unspecified)."""
         return self.engine(v_speaker.device).encode_speaker(v_speaker, self._mask8(mask.bool()))
 
-    def _build_context(self, eng, x_s, v_speaker, x_a, m8, for_generate, n_samples=1):
+    def _build_context(self, eng, x_s, v_speaker, x_a, m8, for_generate, n_samples=1, prompt_frames=1):
         # x_s given (the reference's call shape): context straight from it; x_s None + v_speaker: the fused stage that
         # keeps the encoder output inside the workspace (what forward() uses)
         if x_s is not None:
-            eng.set_context(x_s, x_a, which_patch=0, for_generate=for_generate, n_samples=n_samples)
+            eng.set_context(x_s, x_a, which_patch=0, for_generate=for_generate, n_samples=n_samples, prompt_frames=prompt_frames)
         else:
             assert v_speaker is not None, "forward_decoder needs x_s (reference call) or v_speaker= (fused path)"
-            eng.encode_ctx(v_speaker, x_a, m8, for_generate, n_samples=n_samples)
+            eng.encode_ctx(v_speaker, x_a, m8, for_generate, n_samples=n_samples, prompt_frames=prompt_frames)
 
     @staticmethod
     def _user_seed(seed):
@@ -128,10 +152,17 @@ class SLMFT(_EngineOwner):
 
     @torch.no_grad()
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
-                        seed=None, temperature=1.0, n_samples=1):
+                        seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
-        encoder output inside the engine workspace (no round trip through a tensor)."""
+        encoder output inside the engine workspace (no round trip through a tensor).
+
+        ``prompt_frames`` P > 1 (mode 'val'): the generation continues the ground-truth listener codes ``z_l[:, :P]``
+        instead of starting from ``z_l[:, 0]`` alone (the reference edit: ``decoder_joint.generate(z_l[:, :P], seq_len=T-P,
+        ...)``); a clip with fewer than P valid frames is prompted with the frames it has.  ``lengths`` (host list of the
+        clips' valid frame counts) spares the one ``.item()`` that otherwise finds the common prefix (``prompt_lengths``).
+        The returned tokens keep the shape [B*S, T-1]: their first plen-1 columns repeat ``z_l[:, 1:plen]``."""
+        prompt_frames = _check_prompt_frames(prompt_frames, z_l.shape[1])
         dev = (x_s if x_s is not None else v_speaker).device
         eng = self.engine(dev)
         m8 = self._mask8(mask.bool())
@@ -145,12 +176,17 @@ class SLMFT(_EngineOwner):
             logits, row_loss, _ = eng.decode_tf(z_l, m8, self._mask8(kv_mask) if kv_mask is not None else None)
             n_valid = (z_l[:, 1:] != -100).sum().clamp(min=1)
             return row_loss.sum() / n_valid, logits
-        self._build_context(eng, x_s, v_speaker, x_a, m8, True, n_samples=n_samples)
+        plen, p0 = prompt_lengths(mask, prompt_frames, lengths) if prompt_frames > 1 else (None, 1)
+        self._build_context(eng, x_s, v_speaker, x_a, m8, True, n_samples=n_samples, prompt_frames=p0)
         if greedy:
             temperature, seed_v = 0.0, 0
         else:
             seed_v = 0 if noise is not None else self._user_seed(seed)
-        tokens = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples)
+        if prompt_frames > 1:
+            tokens = eng.generate(None, m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
+                                  prompt=z_l[:, :prompt_frames], prompt_len=plen, prefill=p0)
+        else:
+            tokens = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples)
         return 0.0, tokens.long()
 
     def draw_kv_mask(self, B, T, device, generator=None):
@@ -221,9 +257,17 @@ class SLMFT(_EngineOwner):
     # ------------------------------------------------------------------ forward
     def forward(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
-                return_tokens=False, n_samples=1, shard=None, z_l=None):
+                return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
-        teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path."""
+        teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
+
+        ``prompt_frames`` P > 1 (mode 'val'): continue the clip's first P ground-truth listener codes (see
+        ``forward_decoder``; ``lengths`` = host list of valid frames per clip, optional).  ``pred`` keeps its shape
+        [B,T-1,56]: its first plen-1 frames are the VQ decoder's rendering of the ground-truth codes, the rest is
+        generated.  P >= T raises ValueError."""
+        prompt_frames = _check_prompt_frames(prompt_frames, mask.shape[1])
+        if prompt_frames > 1 and mode != "val":
+            raise ValueError("prompt_frames applies to mode='val'")
         if self._wants_grad(mode):
             return self._forward_autograd(v_speaker, v_listener, v_audio, mask, kv_mask=kv_mask, z_l=z_l,
                                           return_tokens=return_tokens)
@@ -231,12 +275,12 @@ class SLMFT(_EngineOwner):
             return self._forward_nograd(v_speaker, v_listener, v_audio, mask, mode=mode, noise=noise, kv_mask=kv_mask,
                                         greedy=greedy, seed=seed, temperature=temperature,
                                         batch_row_offset=batch_row_offset, return_tokens=return_tokens,
-                                        n_samples=n_samples, shard=shard)
+                                        n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
-                        return_tokens=False, n_samples=1, shard=None):
+                        return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -253,7 +297,7 @@ class SLMFT(_EngineOwner):
         try:
             l_ce_l, px_l = self.forward_decoder(None, z_l, v_audio, mask, mode, v_speaker=v_speaker, noise=noise,
                                                 kv_mask=kv_mask, greedy=greedy, seed=seed, temperature=temperature,
-                                                n_samples=S)
+                                                n_samples=S, prompt_frames=prompt_frames, lengths=lengths)
         finally:
             eng.set_shard(0, 0)
         pred = self.forward_vq_decoder(px_l, mode=mode, batch_row_offset=batch_row_offset, rows_per_clip=S)

@@ -173,7 +173,7 @@ def _select(pending, skip_degenerate, world, device):
 
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
-                        fd_backend="reference", metrics=None, **forward_kw):
+                        fd_backend="reference", metrics=None, prompt_frames=1, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -197,6 +197,9 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     clips do not raise) and brings only the winners to the host.  ``fd_backend="hip"`` follows the same path with the distances,
     the winner and the gather of the winning sequences all in the project's own kernels (dimx.engine.op_fd_select, csrc/fd_select.hip;
     GPU only: a CPU device raises lib.DimxError).
+
+    ``prompt_frames`` P > 1: every generation continues the clip's first P ground-truth listener codes (SLMFT.forward
+    ``prompt_frames``, with the batch's ``src_len`` as ``lengths``); selection and the returned lists stay over the whole clip.
 
     ``metrics``: a dimx.metrics.ListenerMetrics that is updated per batch with the device-resident winners, ``tgt[:, 1:]``, the
     speaker motion and the lens right after the selection (dimx_op_listener_metrics, csrc/listener_metrics.hip), so that
@@ -241,6 +244,8 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
                 kw = dict(forward_kw)
                 if world > 1:
                     kw.update(batch_row_offset=lo, shard=(lo, B))
+                if prompt_frames != 1:
+                    kw.update(prompt_frames=prompt_frames, lengths=src_len[lo:hi])
                 sl = [t[lo:hi].contiguous() for t in (src_s_v, tgt, src_s_a, mask)]
                 if batched:
                     _, _, y_preds = model(sl[0], sl[1], sl[2], sl[3], mode="val", n_samples=beam_size, **kw)

@@ -216,6 +216,39 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
                   float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens,
                   float* logits_out, void* ws, size_t ws_bytes, void* stream);
 
+/* Prompted generation: continue a sequence whose first tokens are given (AutoregressiveWrapper.generate(prompts, seq_len, ...)
+ * with a prompt of any length; dimx_generate is the one-token case and shares the implementation).  Variant 0 (SLMFT) only: a
+ * handle of variant 1 or 2 returns DIMX_ERR_ARG.
+ * Positions are 0 .. T-1; step t consumes the token at position t and produces position t+1.
+ *   prompt      [B, ld_prompt] int32, the first Pmax columns are used, 1 <= Pmax <= T-1, one row per CLIP (also with n_samples > 1).
+ *               A negative entry (the -100 padding of forward_vq) counts as token 0, as dimx_decode_tf treats it.
+ *   prompt_len  [B] int32 device, or NULL = Pmax for every clip.  Clip b's effective length is
+ *               plen[b] = clamp(prompt_len[b], P0, Pmax).
+ *   P0          host integer, 1 <= P0 <= Pmax: the prefix every clip certainly has (it comes from the host so that no device value
+ *               is read back).  Positions 0 .. P0-2 are PREFILLED: the teacher-forced decoder stack runs over them once and
+ *               writes every layer's self-attention K/V into the generation cache (no logits are formed).  The first decode step
+ *               is t = P0-1 with input prompt[:, P0-1]; from then on a step runs as in dimx_generate, except that while
+ *               t+1 < plen[b] the sampler's result of row b is replaced by prompt[b][t+1] (this is what makes ragged prompt
+ *               lengths work).  P0 is not part of what keys the captured step graph.
+ *   tokens      [B*S, T-1] as in dimx_generate: column c is position c+1; columns < plen-1 hold the prompt's own tokens, the rest
+ *               are generated.
+ *   logits_out  (optional) [B*S, T-1, 512]: columns < P0-1 are zero-filled by the call (the prefill forms no logits), every later
+ *               column holds that step's raw logits.
+ *   exp_noise / seed stay indexed by (step, global row): a prompted call draws at step t what dimx_generate draws at step t.
+ *   flags       bit 0 = no prefill: the call behaves as if P0 = 1 and forces the whole prompt through decode steps (for the tests
+ *               and measurements, like dimx_mesh_head's bit 0; not a tuning knob).  Other bits are reserved.
+ * Pmax = P0 = 1 is dimx_generate, bit for bit.  The context must have been built with dimx_encode_ctx(for_generate = 1) in the
+ * same ws; dimx_workspace_bytes_prompt(h, B, T, S, P0) sizes ws for both calls (for P0 = 1 it equals
+ * dimx_workspace_bytes_samples, and it does not shrink as P0 grows; 0 = shape not supported).  The prefill's teacher-forced scratch
+ * is sized for the WHOLE batch, B x (P0-1) rows, behind the generation scratch (no clip chunks); a smaller workspace returns
+ * DIMX_ERR_WORKSPACE before anything is launched.  Chain faults are answered as in dimx_generate (below); the regeneration keeps
+ * the prefilled cache prefix. */
+size_t dimx_workspace_bytes_prompt(dimx_handle h, int B, int T, int n_samples, int P0);
+int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
+                           const uint8_t* ctx_mask, int B, int T, int n_samples, float temperature, int top_k,
+                           const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out, int flags, void* ws,
+                           size_t ws_bytes, void* stream);
+
 /* In the bf16 mode dimx_generate runs part of the decode step as XCD-local chain kernels (B <= 256, one sample per clip,
  * 256-CU device) that rely on their 256 blocks being co-resident, one per CU.  They verify that and dimx_generate checks
  * their flags BEFORE it returns: with the chain path active the call therefore waits for its own generation to finish
