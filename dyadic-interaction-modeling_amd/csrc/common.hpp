@@ -475,6 +475,13 @@ int launch_finalize_idx(int32_t* idx, const int32_t* lens, int B, int T, int32_t
 int launch_shift_tokens(const int32_t* z, int32_t* inp, int32_t* tgt, int B, int T, hipStream_t s);
 int launch_ce_argmax(const float* logits, const int32_t* target, float* row_loss, int32_t* argmax_tok, int R,
                      int V, hipStream_t s);
+// sampler filter of a launch (DIMX_FILTER_*): kind 0 = the launch's top_k.  a / b are read from the launch only when there
+// is no device parameter block (dimx_op_sample_filtered); keep_out [R, 512]: the kept set the launch used (optional)
+struct SampleFilter {
+    int kind = 0;
+    float a = 0.f, b = 0.f;
+    uint8_t* keep_out = nullptr;
+};
 int launch_sample(const float* logits, int ld_logits, int R, int top_k, float temperature, const float* noise,
                   uint64_t seed, const int32_t* step_dev, uint64_t step_host, int32_t* tokens, int tok_ld,
                   int tok_col_from_step, int nslab, long slab_stride, float* logits_out, int logits_out_ld, int row0,
@@ -487,7 +494,7 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
                   // (clip = row / prompt_div; length clamp(prompt_len, dev_params[8] + 1, prompt_max), NULL = prompt_max);
                   // epoch_rw: a second counter advanced with the step counter (steps done in this call)
                   const int32_t* prompt = nullptr, int prompt_ld = 0, int prompt_max = 0, const int32_t* prompt_len = nullptr,
-                  int prompt_div = 1, int32_t* epoch_rw = nullptr);
+                  int prompt_div = 1, int32_t* epoch_rw = nullptr, const SampleFilter& filt = SampleFilter());
 // the first decoder layer's q/k/v as a table over the token ids (model.hip qkv0_table_build): id list of the build rounds,
 // slab-order sum of a round's projection into the table rows, and step 0's rows by start token
 int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s);
@@ -497,7 +504,7 @@ int launch_gather_start_rows(const float* table, int N, int rows, const int32_t*
                              hipStream_t s, int start_ld = 1);
 // generate(): the per-group step counters = step0, done counters = 0, and temperature + seed next to them (read by the sampler)
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
-                      hipStream_t s, int step0 = 0);
+                      hipStream_t s, int step0 = 0, float filter_a = 0.f, float filter_b = 0.f);
 int launch_embed_step(const float* table, int C, int rows, const int32_t* start, const int32_t* tokens, int tok_ld,
                       const int32_t* step_dev, float* x, int B, int start_div, hipStream_t s,
                       const float* pos_table = nullptr, float pos_scale = 0.f, int start_ld = 1, int start_step = 0);

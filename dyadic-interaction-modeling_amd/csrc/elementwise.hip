@@ -116,11 +116,33 @@ __device__ __forceinline__ uint64_t splitmix(uint64_t key, uint64_t ctr) {
 
 constexpr int kSampleVocab = 512;   // rows of the logits / embedding table the sampler is written for (8 x 64 lanes)
 
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    uint32_t o;
+    o = (uint32_t)xor_lane_i32<32>((int)v); v = o < v ? o : v;
+    o = (uint32_t)xor_lane_i32<16>((int)v); v = o < v ? o : v;
+    o = (uint32_t)xor_lane_i32<8>((int)v);  v = o < v ? o : v;
+    o = (uint32_t)xor_lane_i32<4>((int)v);  v = o < v ? o : v;
+    o = (uint32_t)xor_lane_i32<2>((int)v);  v = o < v ? o : v;
+    o = (uint32_t)xor_lane_i32<1>((int)v);  v = o < v ? o : v;
+    return v;
+}
+
 // Sampler of AutoregressiveWrapper.generate: top-k filter (k = 52), softmax(T), multinomial.
 // torch.multinomial(p, 1) == argmax(p / q), q ~ Exp(1) (tests/golden/sampler_multinomial.npz), so the
 // noise is an input: injected (parity) or drawn from a counter-based splitmix64 stream (production).
 // One wave per row; the k-th largest logit is found by a 32-step bitwise search on the order-preserving
 // integer image of the floats, counting with ballots.
+//
+// KIND selects the filter (DIMX_FILTER_*).  KIND 0 is the top-k search above, untouched.  The other three kept sets are
+// thresholds on the same integer keys, so they only replace the search and hand `thr` to the same survivor code:
+//   top_p  keep i iff mass(l_j > l_i) <= thres * Z: the smallest key c* with mass(key > c*) <= thres * Z, found by the same
+//          32-step bitwise search with a masked wave sum for the ballots.  The masked sum always adds the same 512 slots in the
+//          same order (zeros for the excluded ones), so it is non-increasing in c in float32 too and the search is exact for it.
+//   min_p  keep i iff e_i >= min_p, e_i = exp(l_i - max) (e_max = 1, no partition sum)
+//   top_a  keep i iff e_i >= ratio * Z^(1 - pow)
+// thres >= 1 and min_p <= 0 keep everything; the arg-max is always kept.  fa / fb come from the parameter block (words
+// 9 / 10 behind dev_params) when there is one: the captured step graph does not depend on them.
+template <int KIND>
 __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, int ld, int R, int top_k,
                                                      float temperature, const float* __restrict__ noise,
                                                      uint64_t seed, const int32_t* __restrict__ step_dev,
@@ -138,13 +160,18 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                                                      float* __restrict__ qkv0_out, int qkv0_N,
                                                      const int32_t* __restrict__ prompt, int prompt_ld, int prompt_max,
                                                      const int32_t* __restrict__ prompt_len, int prompt_div,
-                                                     int32_t* __restrict__ epoch_rw) {
+                                                     int32_t* __restrict__ epoch_rw, float fa, float fb,
+                                                     uint8_t* __restrict__ keep_out) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint64_t step = step_dev ? (uint64_t)*step_dev : step_host;
     if (dev_params) {  // generate(): temperature / seed live in device memory so that the captured step graph
                        // does not depend on them (a new seed per batch must not force a re-capture)
         temperature = __builtin_bit_cast(float, dev_params[0]);
         seed = *(const uint64_t*)(dev_params + 2);
+        if constexpr (KIND != DIMX_FILTER_TOP_K) {
+            fa = __builtin_bit_cast(float, dev_params[9]);
+            fb = __builtin_bit_cast(float, dev_params[10]);
+        }
     }
     // counter of the on-device generator: (step, GLOBAL sequence row, code) -- a rank that generates rows
     // [off, off + R) of a sharded batch of `tot` sequences draws what the single-process batch would draw
@@ -201,12 +228,42 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
     wave_argmax(mx, mi);
     const bool greedy = temperature <= 0.f || (noise == nullptr && seed == 0);
     tok = mi;
-    if (!greedy) {
+    if (!greedy || keep_out) {
         uint32_t key[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) key[c] = f32_order_key(v[c]);
+        for (int c = 0; c < 8; ++c) key[c] = f32_order_key(KIND == DIMX_FILTER_TOP_K ? v[c] : v[c] + 0.f);   // + 0: -0 ties with +0
         uint32_t thr = 0;
-        if (top_k > 0 && top_k < 512) {
+        if constexpr (KIND != DIMX_FILTER_TOP_K) {
+            float e[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) e[c] = expf(v[c] - mx);
+            // mass of the keys above cnd: slot c of lane l always enters at the same place of the same sum
+            auto mass_above = [&](uint32_t cnd) {
+                float m = 0.f;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) m += key[c] > cnd ? e[c] : 0.f;
+                return wave_sum(m);
+            };
+            if constexpr (KIND == DIMX_FILTER_TOP_P) {
+                if (fa < 1.0f) {
+                    const float lim = fa * mass_above(0u);   // no finite float has key 0: this is Z
+                    uint32_t lo = 0;                         // the largest c whose mass above still exceeds the limit
+                    for (int bit = 31; bit >= 0; --bit) {
+                        const uint32_t cand = lo | (1u << bit);
+                        if (mass_above(cand) > lim) lo = cand;
+                    }
+                    thr = lo + 1u;   // mass above the largest key is 0 <= lim, so lo < 2^32 - 1
+                }
+            } else {
+                float lim = fa;
+                if constexpr (KIND == DIMX_FILTER_TOP_A) lim = fb * powf(mass_above(0u), 1.0f - fa);
+                uint32_t kmin = f32_order_key(mx + 0.f);   // the arg-max stays, whatever the limit
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    if (e[c] >= lim && key[c] < kmin) kmin = key[c];
+                thr = wave_min_u32(kmin);
+            }
+        } else if (top_k > 0 && top_k < 512) {
             for (int bit = 31; bit >= 0; --bit) {
                 const uint32_t cand = thr | (1u << bit);
                 int cnt = 0;
@@ -220,6 +277,11 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                 }
             }
         }
+        if (keep_out) {   // dimx_op_sample_filtered: the kept set as this launch decided it
+#pragma unroll
+            for (int c = 0; c < 8; ++c) keep_out[(size_t)row * 512 + lane + 64 * c] = key[c] >= thr ? 1 : 0;
+        }
+        if (!greedy) {
         // Only the <= top_k (+ ties) survivors need a probability and a noise draw: compact them to one per lane
         // (2 rounds cover up to 128 survivors; more than that -- massive ties -- falls back to the per-element loop).
         const float inv_t = 1.0f / temperature;
@@ -295,6 +357,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
         }
         wave_argmax(best, bi);
         tok = bi;
+        }  // !greedy
     }
     }  // !forced
     if (lane == 0) tokens[(size_t)row * tok_ld + (tok_col_from_step ? (int)step : 0)] = tok;
@@ -520,9 +583,9 @@ __global__ void step_inc_kernel(int32_t* step) { *step += 1; }
 // per clip group: [0] step counter = step0 (0, or P0 - 1 of a prompted generation), [8] done counter = 0, [2] temperature
 // bits, [4..5] seed, [6] global row offset and [7] global row count of the sampler's counter-based generator (generate()),
 // [9] steps done in this call = 0 (the chain kernels' counter epoch), [10] step0 again, constant over the call (the sampler's
-// clamp of the prompt lengths)
+// clamp of the prompt lengths), [11] / [12] the sampler filter's real-valued parameters (thres | min_p | min_p_pow, min_p_ratio)
 __global__ void gen_params_kernel(int32_t* base, int groups, float temperature, uint64_t seed, int row_off,
-                                  int rows_total, int step0) {
+                                  int rows_total, int step0, float filter_a, float filter_b) {
     const int g = threadIdx.x;
     if (g >= groups) return;
     int32_t* p = base + 16 * g;
@@ -534,6 +597,8 @@ __global__ void gen_params_kernel(int32_t* base, int groups, float temperature, 
     *(uint64_t*)(p + 4) = seed;
     p[6] = row_off;
     p[7] = rows_total;
+    p[11] = __builtin_bit_cast(int32_t, filter_a);
+    p[12] = __builtin_bit_cast(int32_t, filter_b);
 }
 
 // dst[b, step, :] = src[b, :]  (optional per-step logits dump of generate)
@@ -629,8 +694,10 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
                   hipStream_t s, const float* pos_table, float pos_scale, int pos_rows, const int32_t* dev_params,
                   void* y_next, const float* y_gamma, int y_dtype, const float* qkv0_table, float* qkv0_out, int qkv0_N,
                   const int32_t* prompt, int prompt_ld, int prompt_max, const int32_t* prompt_len, int prompt_div,
-                  int32_t* epoch_rw) {
+                  int32_t* epoch_rw, const SampleFilter& filt) {
     DIMX_REQUIRE(logits && tokens && R > 0, DIMX_ERR_ARG, "sample: bad arguments");
+    DIMX_REQUIRE(filt.kind >= DIMX_FILTER_TOP_K && filt.kind <= DIMX_FILTER_TOP_A, DIMX_ERR_ARG, "sample: unknown filter kind %d", filt.kind);
+    DIMX_REQUIRE(!filt.keep_out || !prompt, DIMX_ERR_ARG, "sample: keep_out is not written for prompted rows");
     DIMX_REQUIRE(!prompt || (step_dev && tok_col_from_step && prompt_max >= 1 && prompt_ld >= prompt_max && prompt_div >= 1),
                  DIMX_ERR_ARG, "sample: a prompt needs the device step counter, 1 <= prompt_max <= prompt_ld and rows per clip >= 1");
     DIMX_REQUIRE(!qkv0_table || (x_next && qkv0_out && !pos_table && emb_C / 2 <= 16 * 64 && qkv0_N % 4 == 0 && qkv0_N > 0 &&
@@ -639,19 +706,25 @@ int launch_sample(const float* logits, int ld_logits, int R, int top_k, float te
     DIMX_REQUIRE(!y_next || (x_next && y_gamma && emb_C % 128 == 0 && emb_C <= 2048), DIMX_ERR_ARG,
                  "sample: the fused pre-norm needs the fused embedding and a width of k * 128 <= 2048");
     const int wpb = R <= 1024 ? 1 : 4;  // one row per block for decode-sized batches: all CUs busy
-    hipLaunchKernelGGL(sample_kernel, dim3(ceil_div(R, wpb)), dim3(64 * wpb), 0, s, logits, ld_logits, R, top_k,
+    auto kern = filt.kind == DIMX_FILTER_TOP_P   ? sample_kernel<DIMX_FILTER_TOP_P>
+                : filt.kind == DIMX_FILTER_MIN_P ? sample_kernel<DIMX_FILTER_MIN_P>
+                : filt.kind == DIMX_FILTER_TOP_A ? sample_kernel<DIMX_FILTER_TOP_A>
+                                                 : sample_kernel<DIMX_FILTER_TOP_K>;
+    hipLaunchKernelGGL(kern, dim3(ceil_div(R, wpb)), dim3(64 * wpb), 0, s, logits, ld_logits, R, top_k,
                        temperature, noise, seed, step_dev, step_host, tokens, tok_ld, tok_col_from_step, nslab < 1 ? 1 : nslab,
                        slab_stride, logits_out, logits_out_ld, row0, rows_total, emb_table, emb_C, x_next, step_rw, done_ctr,
                        pos_table, pos_scale, pos_rows, dev_params, y_next, y_gamma, y_dtype == DIMX_BF16 ? 1 : 0, qkv0_table,
-                       qkv0_out, qkv0_N, prompt, prompt_ld, prompt_max, prompt_len, prompt_div < 1 ? 1 : prompt_div, epoch_rw);
+                       qkv0_out, qkv0_N, prompt, prompt_ld, prompt_max, prompt_len, prompt_div < 1 ? 1 : prompt_div, epoch_rw,
+                       filt.a, filt.b, filt.keep_out);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
 
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
-                      hipStream_t s, int step0) {
+                      hipStream_t s, int step0, float filter_a, float filter_b) {
     DIMX_REQUIRE(step0 >= 0, DIMX_ERR_ARG, "gen_params: negative first step");
-    hipLaunchKernelGGL(gen_params_kernel, dim3(1), dim3(64), 0, s, base, groups, temperature, seed, row_off, rows_total, step0);
+    hipLaunchKernelGGL(gen_params_kernel, dim3(1), dim3(64), 0, s, base, groups, temperature, seed, row_off, rows_total, step0,
+                       filter_a, filter_b);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

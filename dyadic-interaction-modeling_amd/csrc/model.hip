@@ -2282,7 +2282,8 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     DIMX_TRY(launch_sample(s.logits, V, B, top_k, temperature, noise, seed, s.step, 0, tokens, n, 1, nlg, s0.st_lg,
                            logits_out, n, row0, Btot, h->dec.tok_emb, DD, s.x, s.step, (unsigned*)(s.step + 8), st, pos,
                            pos_scale, n, s.step + 2, qkv0 ? nullptr : s.y, qkv0 ? nullptr : h->dec.self_[0].ln_g, h->at, qkv0,
-                           s.qkv, 3 * inner, forced, pr.ld, pr.Pmax, forced_len, S, s.step + 9));
+                           s.qkv, 3 * inner, forced, pr.ld, pr.Pmax, forced_len, S, s.step + 9,
+                           SampleFilter{h->filter_kind, 0.f, 0.f, nullptr}));   // a / b: words 11 / 12 of the parameter block
     return DIMX_OK;
 }
 
@@ -2388,6 +2389,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
                          float* logits_out, void* ws, size_t ws_bytes, void* stream, bool* chain_used, bool prefill_only = false) {
     const int32_t* start = pr.tok;
     const int S = n_samples < 1 ? 1 : n_samples;
+    if (h && h->filter_kind != DIMX_FILTER_TOP_K) top_k = 0;   // the other kinds ignore the call's k (and it keys the step graph)
     DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
                  "generate: n_samples %d not in {1,2,4,5,8,10}", n_samples);
     DIMX_TRY(check_common(h, B, T, ws, ws_bytes, COMP_DEC, S));
@@ -2418,7 +2420,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
     // step / done counters = 0; temperature, seed and the sampler's global row window go to device memory so that
     // the captured step graph is independent of them
     DIMX_TRY(launch_gen_params(s.step, dimx_ctx::kMaxGroups, temperature, seed, h->shard_row_off * S,
-                               h->shard_rows_total * S, st, pr.step0));
+                               h->shard_rows_total * S, st, pr.step0, h->filter_a, h->filter_b));
     if (gen_multi_tr(h, S)) DIMX_TRY(launch_pack_key_words(ctx_mask, T, nullptr, B, T, s.kw, s.kw_cap, st));
     // Independent clip groups run as separate step graphs on separate streams: every decode kernel is
     // latency-bound at these sizes, so two groups in flight let one group's GEMM/LayerNorm chain overlap the
@@ -2471,7 +2473,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
         // pointers, row stride and width are kernel arguments of the sampler; P0 is not (the counters' start value and the
         // number of launches below), so a call with another P0 replays the same graphs.
         GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0),
-                     pr.len, pr.ld, pr.Pmax};
+                     pr.len, pr.ld, pr.Pmax, h->filter_kind};
         if (!(h->graph_valid && h->graph_key == key)) {
             h->graph_valid = false;
             if (!h->cap_stream) DIMX_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -2659,6 +2661,27 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
     }
     return generate_checked(h, pr, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws, ws_bytes,
                             stream);
+}
+
+// x-transformers' own parameter ranges; the kernel treats thres >= 1 and min_p = 0 as "keep everything"
+static int check_sampler_filter(int kind, float a, float b) {
+    DIMX_REQUIRE(kind >= DIMX_FILTER_TOP_K && kind <= DIMX_FILTER_TOP_A, DIMX_ERR_ARG, "sampler filter: unknown kind %d", kind);
+    if (kind == DIMX_FILTER_TOP_K) return DIMX_OK;
+    DIMX_REQUIRE(a == a && (kind != DIMX_FILTER_TOP_A || b == b), DIMX_ERR_ARG, "sampler filter: NaN parameter");
+    if (kind == DIMX_FILTER_TOP_P) DIMX_REQUIRE(a >= 0.f, DIMX_ERR_ARG, "sampler filter: top_p thres %g < 0", (double)a);
+    if (kind == DIMX_FILTER_MIN_P) DIMX_REQUIRE(a >= 0.f && a <= 1.f, DIMX_ERR_ARG, "sampler filter: min_p %g outside [0, 1]", (double)a);
+    if (kind == DIMX_FILTER_TOP_A)
+        DIMX_REQUIRE(a >= 0.f && b >= 0.f, DIMX_ERR_ARG, "sampler filter: top_a min_p_pow %g or min_p_ratio %g < 0", (double)a, (double)b);
+    return DIMX_OK;
+}
+
+int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_TRY(check_sampler_filter(kind, a, b));
+    h->filter_kind = kind;
+    h->filter_a = kind == DIMX_FILTER_TOP_K ? 0.f : a;
+    h->filter_b = kind == DIMX_FILTER_TOP_A ? b : 0.f;
+    return DIMX_OK;
 }
 
 int dimx_chain_faults(dimx_handle h) { return h ? h->chain_faults : 0; }
@@ -3212,6 +3235,16 @@ int dimx_op_sample(const float* logits, int R, int top_k, float temperature, con
     // exp_noise here is the [R,512] slice of this step (step only salts the on-device generator)
     return launch_sample(logits, 512, R, top_k, temperature, exp_noise, seed, nullptr, exp_noise ? 0 : step, tokens, 1,
                          0, 1, 0, nullptr, 0, 0, R, nullptr, 0, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int dimx_op_sample_filtered(const float* logits, int R, int kind, int top_k, float a, float b, float temperature,
+                            const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens, uint8_t* keep_out,
+                            void* stream) {
+    DIMX_TRY(check_sampler_filter(kind, a, b));
+    return launch_sample(logits, 512, R, kind == DIMX_FILTER_TOP_K ? top_k : 0, temperature, exp_noise, seed, nullptr,
+                         exp_noise ? 0 : step, tokens, 1, 0, 1, 0, nullptr, 0, 0, R, nullptr, 0, nullptr, nullptr, nullptr,
+                         (hipStream_t)stream, nullptr, 0.f, 0, nullptr, nullptr, nullptr, DIMX_F32, nullptr, nullptr, 0, nullptr, 0,
+                         0, nullptr, 1, nullptr, SampleFilter{kind, a, b, keep_out});
 }
 
 }  // extern "C"

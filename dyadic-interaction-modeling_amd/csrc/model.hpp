@@ -120,8 +120,9 @@ struct GraphKey {
     int groups;
     const void* prompt_len;   // prompted generation: the sampler's other prompt arguments (`start` is the prompt itself)
     int ld_prompt, Pmax;
+    int filter_kind;          // the sampler kernel's instantiation; the filter's real-valued parameters live in device memory
     bool operator==(const GraphKey& o) const {
-        return groups == o.groups && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
+        return groups == o.groups && filter_kind == o.filter_kind && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
                noise == o.noise && seed == o.seed && start == o.start && mask == o.mask && tokens == o.tokens &&
                logits_out == o.logits_out;
     }
@@ -201,6 +202,9 @@ struct dimx_ctx {
     // sampler generator window of a sharded batch (dimx_set_shard): this handle generates clips
     // [shard_row_off, shard_row_off + B) of shard_rows_total (0 = the call's own B)
     int shard_row_off = 0, shard_rows_total = 0;
+    // sampler filter of generate (dimx_set_sampler_filter): kind 0 = the call's top_k
+    int filter_kind = 0;
+    float filter_a = 0.f, filter_b = 0.f;
     dimx::MeshHead mesh;                // handles created with dimx_dims.mesh_dim > 0
     int lstm_faults = 0;                // LSTM layers whose group kernel reported a fault and that were rerun on the safe path
     int spk_embed_rows = 0;             // rows of speaker_embed.weight as last loaded (the host applies it in inference; the

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import sampling
 
 
 class Engine:
@@ -234,9 +235,19 @@ class Engine:
                                         L.ptr(row_loss), L.ptr(amax), ws, wsb, self._s()), "dimx_decode_tf")
         return logits, row_loss, amax
 
+    def set_sampler_filter(self, kind=0, a=0.0, b=0.0):
+        """The handle's sampler filter (dimx_set_sampler_filter): kind 0 = the call's top_k.  ``generate`` sets and restores it
+        around a call with ``filter_logits_fn``; an invalid setting raises and leaves the previous one in force."""
+        L.check(self.lib.dimx_set_sampler_filter(self.h, int(kind), float(a), float(b)), "dimx_set_sampler_filter")
+
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
-                 n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False):
+                 n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False, filter_logits_fn=None,
+                 filter_kwargs=None):
         """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
+
+        ``filter_logits_fn`` / ``filter_kwargs``: the sampler filter of AutoregressiveWrapper.generate -- ``top_k``, ``top_p``,
+        ``min_p`` or ``top_a`` of dimx.sampling, as the object or its name, with that function's keyword arguments.  None is
+        top-k with the given ``top_k``.  The filter holds for this call only.
 
         ``prompt`` [B,Pmax] (1 <= Pmax <= T-1; ``start`` is then ignored and may be None): continue the given tokens
         (dimx_generate_prompted, include/dimx.h).  ``prompt_len`` [B] int32 on the device: per-clip prompt lengths, clamped to
@@ -245,6 +256,15 @@ class Engine:
         workspace grown in between invalidates it).  ``no_prefill``: the whole prompt goes through forced decode steps.
         Returned tokens keep their shape: column c is position c+1, columns < plen-1 repeat the prompt; with
         ``return_logits`` the columns < P0-1 are zero."""
+        if filter_logits_fn is not None or filter_kwargs:
+            kind, top_k, fa, fb = sampling.resolve(filter_logits_fn, filter_kwargs, top_k)
+            if kind != 0:
+                self.set_sampler_filter(kind, fa, fb)
+                try:
+                    return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt,
+                                         prompt_len, prefill, no_prefill)
+                finally:
+                    self.set_sampler_filter(0)
         if prompt is not None:
             return self._generate_prompted(prompt, prompt_len, prefill, no_prefill, mask_u8, T, temperature, top_k, noise, seed,
                                            return_logits, n_samples)
@@ -506,10 +526,20 @@ def op_train_attention(q, k, v, scale, d_o=None, causal=False, kmask=None, kmask
     return (o, lse) if d_o is None else (o, lse, dq, dk, dv)
 
 
-def op_sample(logits, top_k=52, temperature=1.0, noise=None, seed=0, step=0):
+def op_sample(logits, top_k=52, temperature=1.0, noise=None, seed=0, step=0, filter_logits_fn=None, filter_kwargs=None,
+              return_keep=False):
+    """One sampler launch on logits [R,512].  ``filter_logits_fn`` / ``filter_kwargs`` as in Engine.generate (None: top-k with
+    ``top_k``, the dimx_op_sample launch); ``return_keep``: also the kept set the kernel used, bool [R,512]."""
     lib = L.load()
     R = logits.shape[0]
     tok = torch.empty(R, dtype=torch.int32, device=logits.device)
+    if filter_logits_fn is not None or filter_kwargs or return_keep:
+        kind, top_k, fa, fb = sampling.resolve(filter_logits_fn, filter_kwargs, top_k)
+        keep = torch.empty(R, 512, dtype=torch.uint8, device=logits.device) if return_keep else None
+        L.check(lib.dimx_op_sample_filtered(L.ptr(logits.contiguous()), R, kind, int(top_k), fa, fb, float(temperature),
+                                            L.ptr(noise), int(seed), int(step), L.ptr(tok), L.ptr(keep),
+                                            L.stream_ptr(logits.device)), "dimx_op_sample_filtered")
+        return (tok, keep.bool()) if return_keep else tok
     L.check(lib.dimx_op_sample(L.ptr(logits.contiguous()), R, top_k, float(temperature), L.ptr(noise), int(seed),
                                int(step), L.ptr(tok), L.stream_ptr(logits.device)), "dimx_op_sample")
     return tok

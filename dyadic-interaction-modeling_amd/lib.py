@@ -60,6 +60,7 @@ SIGNATURES = {
     "dimx_encode_speaker": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
     "dimx_set_shard": (c_int, [c_void_p, c_int, c_int]),
+    "dimx_set_sampler_filter": (c_int, [c_void_p, c_int, c_float, c_float]),
     "dimx_encode_ctx": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
     "dimx_legacy_speaker_features": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
@@ -176,6 +177,8 @@ SIGNATURES = {
                                    c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
+    "dimx_op_sample_filtered": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_uint64, c_uint64,
+                                        c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

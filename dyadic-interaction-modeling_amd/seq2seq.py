@@ -158,8 +158,9 @@ class ListenerGenerator(_EngineOwner):
 
     @torch.no_grad()
     def generate(self, v_speaker, v_listener, mask, noise=None, greedy=False, seed=None, temperature=1.0,
-                 n_samples=1):
-        """reference :280-306 -> (z_listener_pred [B,T] (or [B,S,T]), z_listener [B,T])."""
+                 n_samples=1, filter_logits_fn=None, filter_kwargs=None):
+        """reference :280-306 -> (z_listener_pred [B,T] (or [B,S,T]), z_listener [B,T]).  ``filter_logits_fn`` /
+        ``filter_kwargs``: the sampler filter (dimx.sampling; default top_k with k = 52, the reference's call)."""
         eng, xs, xl, lens, m8 = self._prepare(v_speaker, v_listener, mask)
         z_l = eng.vq_encode(1, xl, lens, pe_mode=0, pad_value=-100).long()
         eng.encode_ctx(xs, None, m8, True, n_samples=n_samples)
@@ -170,7 +171,8 @@ class ListenerGenerator(_EngineOwner):
             from .seq2seq_pretrain import SLMFT as _S
             seed_v = 0 if noise is not None else _S._user_seed(seed)
         T = z_l.shape[1]
-        tok = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples).long()
+        tok = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
+                           filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs).long()
         if n_samples > 1:
             tok = tok.view(z_l.shape[0], n_samples, T)
         return tok, z_l

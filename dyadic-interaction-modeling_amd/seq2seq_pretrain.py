@@ -152,7 +152,8 @@ class SLMFT(_EngineOwner):
 
     @torch.no_grad()
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
-                        seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None):
+                        seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
+                        filter_kwargs=None):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -161,7 +162,11 @@ class SLMFT(_EngineOwner):
         instead of starting from ``z_l[:, 0]`` alone (the reference edit: ``decoder_joint.generate(z_l[:, :P], seq_len=T-P,
         ...)``); a clip with fewer than P valid frames is prompted with the frames it has.  ``lengths`` (host list of the
         clips' valid frame counts) spares the one ``.item()`` that otherwise finds the common prefix (``prompt_lengths``).
-        The returned tokens keep the shape [B*S, T-1]: their first plen-1 columns repeat ``z_l[:, 1:plen]``."""
+        The returned tokens keep the shape [B*S, T-1]: their first plen-1 columns repeat ``z_l[:, 1:plen]``.
+
+        ``filter_logits_fn`` / ``filter_kwargs`` (mode 'val'): the sampler filter, as AutoregressiveWrapper.generate takes it --
+        ``top_k``, ``top_p``, ``min_p`` or ``top_a`` of dimx.sampling (object or name).  The default is the reference's call:
+        top_k with k = ceil(0.1 * 512) = 52."""
         prompt_frames = _check_prompt_frames(prompt_frames, z_l.shape[1])
         dev = (x_s if x_s is not None else v_speaker).device
         eng = self.engine(dev)
@@ -184,9 +189,11 @@ class SLMFT(_EngineOwner):
             seed_v = 0 if noise is not None else self._user_seed(seed)
         if prompt_frames > 1:
             tokens = eng.generate(None, m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
-                                  prompt=z_l[:, :prompt_frames], prompt_len=plen, prefill=p0)
+                                  prompt=z_l[:, :prompt_frames], prompt_len=plen, prefill=p0,
+                                  filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
         else:
-            tokens = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples)
+            tokens = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
+                                  filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
         return 0.0, tokens.long()
 
     def draw_kv_mask(self, B, T, device, generator=None):
@@ -257,14 +264,17 @@ class SLMFT(_EngineOwner):
     # ------------------------------------------------------------------ forward
     def forward(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
-                return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None):
+                return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
+                filter_kwargs=None):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
         ``prompt_frames`` P > 1 (mode 'val'): continue the clip's first P ground-truth listener codes (see
         ``forward_decoder``; ``lengths`` = host list of valid frames per clip, optional).  ``pred`` keeps its shape
         [B,T-1,56]: its first plen-1 frames are the VQ decoder's rendering of the ground-truth codes, the rest is
-        generated.  P >= T raises ValueError."""
+        generated.  P >= T raises ValueError.
+
+        ``filter_logits_fn`` / ``filter_kwargs`` (mode 'val'): the sampler filter (see ``forward_decoder``)."""
         prompt_frames = _check_prompt_frames(prompt_frames, mask.shape[1])
         if prompt_frames > 1 and mode != "val":
             raise ValueError("prompt_frames applies to mode='val'")
@@ -275,12 +285,14 @@ class SLMFT(_EngineOwner):
             return self._forward_nograd(v_speaker, v_listener, v_audio, mask, mode=mode, noise=noise, kv_mask=kv_mask,
                                         greedy=greedy, seed=seed, temperature=temperature,
                                         batch_row_offset=batch_row_offset, return_tokens=return_tokens,
-                                        n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths)
+                                        n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths,
+                                        filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
-                        return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None):
+                        return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
+                        filter_kwargs=None):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -297,7 +309,8 @@ class SLMFT(_EngineOwner):
         try:
             l_ce_l, px_l = self.forward_decoder(None, z_l, v_audio, mask, mode, v_speaker=v_speaker, noise=noise,
                                                 kv_mask=kv_mask, greedy=greedy, seed=seed, temperature=temperature,
-                                                n_samples=S, prompt_frames=prompt_frames, lengths=lengths)
+                                                n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
+                                                filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
         finally:
             eng.set_shard(0, 0)
         pred = self.forward_vq_decoder(px_l, mode=mode, batch_row_offset=batch_row_offset, rows_per_clip=S)
@@ -560,8 +573,10 @@ class SpeakerSLMFT(_EngineOwner):
                                   "dimx_slm_encode's joint encoder sees the listener half too")
 
     @torch.no_grad()
-    def forward_decoder(self, x_l, z_s, x_a, mask, mode="train", noise=None, greedy=False, seed=None, temperature=1.0):
-        """reference :650-658 -> (l_ce_s, logits [B,T-1,512]) for mode 'train', (0.0, tokens [B,T-1]) otherwise."""
+    def forward_decoder(self, x_l, z_s, x_a, mask, mode="train", noise=None, greedy=False, seed=None, temperature=1.0,
+                        filter_logits_fn=None, filter_kwargs=None):
+        """reference :650-658 -> (l_ce_s, logits [B,T-1,512]) for mode 'train', (0.0, tokens [B,T-1]) otherwise.
+        ``filter_logits_fn`` / ``filter_kwargs``: the sampler filter of the generation (SLMFT.forward_decoder)."""
         eng = self.engine(x_a.device)
         m8 = mask.bool().to(torch.uint8).contiguous()
         B, T = z_s.shape
@@ -575,7 +590,8 @@ class SpeakerSLMFT(_EngineOwner):
             temperature, seed_v = 0.0, 0
         else:
             seed_v = 0 if noise is not None else SLMFT._user_seed(seed)
-        tokens = eng.generate(z_s[:, 0], m8, T, temperature, 52, noise, seed_v)
+        tokens = eng.generate(z_s[:, 0], m8, T, temperature, 52, noise, seed_v, filter_logits_fn=filter_logits_fn,
+                              filter_kwargs=filter_kwargs)
         return 0.0, tokens.long()
 
     @torch.no_grad()
@@ -593,7 +609,8 @@ class SpeakerSLMFT(_EngineOwner):
 
     # ------------------------------------------------------------------ forward
     def forward(self, v_speaker, v_speaker_emoca, v_audio, mask, template, mode="train", speaker_ids=None, noise=None,
-                greedy=False, seed=None, temperature=1.0, return_tokens=False, return_mesh=False):
+                greedy=False, seed=None, temperature=1.0, return_tokens=False, return_mesh=False, filter_logits_fn=None,
+                filter_kwargs=None):
         """reference :708-757 -> (total_loss, d, pred_cont_seq_s_emoca [B,T-1,56]) (+ tokens [B,T-1], + mesh [B,T-1,V])."""
         if v_speaker_emoca is None:
             raise ValueError("SpeakerSLMFT.forward needs v_speaker_emoca (the EMOCA stream the codes are taken from)")
@@ -607,7 +624,8 @@ class SpeakerSLMFT(_EngineOwner):
             else:
                 x_l = self.speaker_embed.weight[speaker_ids.long()].unsqueeze(1).repeat(1, T, 1).contiguous()
             l_ce_s, px_s = self.forward_decoder(x_l, z, v_audio, mask, mode=mode, noise=noise, greedy=greedy, seed=seed,
-                                                temperature=temperature)
+                                                temperature=temperature, filter_logits_fn=filter_logits_fn,
+                                                filter_kwargs=filter_kwargs)
             eng = self.engine(dev)
             tokens = torch.argmax(px_s, dim=-1) if mode == "train" else px_s
             pred_emoca = eng.vq_decode(0, tokens, 0)

@@ -173,7 +173,8 @@ def _select(pending, skip_degenerate, world, device):
 
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
-                        fd_backend="reference", metrics=None, prompt_frames=1, **forward_kw):
+                        fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
+                        **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -204,7 +205,13 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     ``metrics``: a dimx.metrics.ListenerMetrics that is updated per batch with the device-resident winners, ``tgt[:, 1:]``, the
     speaker motion and the lens right after the selection (dimx_op_listener_metrics, csrc/listener_metrics.hip), so that
     print_metrics / print_metrics_full need no host pass over the returned lists.  It needs ``fd_backend="hip"``, a GPU and one
-    process; anything else raises.  The default None leaves every path as it is."""
+    process; anything else raises.  The default None leaves every path as it is.
+
+    ``filter_logits_fn`` / ``filter_kwargs``: the sampler filter of every generation (AutoregressiveWrapper.generate's arguments:
+    ``top_k``, ``top_p``, ``min_p`` or ``top_a`` of dimx.sampling, object or name); None is the reference's top-k 52.  A rank
+    of a sharded batch filters and draws exactly what the single-process batch would: the filter acts on a row's own logits."""
+    if filter_logits_fn is not None or filter_kwargs:
+        forward_kw = dict(forward_kw, filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
     assert fd_backend in ("reference", "device", "hip")
     if metrics is not None:
         if fd_backend != "hip":
@@ -282,13 +289,16 @@ BIWI_SPEAKER_IDS = {"F2": 0, "F3": 1, "F4": 2, "M3": 3, "M4": 4, "M5": 5, "F1": 
                     "M2": 12, "M6": 13}
 
 
-def evaluate_test_epoch_biwi(model, loader, device, beam_size=10):
+def evaluate_test_epoch_biwi(model, loader, device, beam_size=10, filter_logits_fn=None, filter_kwargs=None):
     """reference code/x_engine_pt.py:279-338, restated with its quirks.  The loader yields ``(xa [B,T,768] audio, xv [B,T,V]
     vertices, xt [B,V] template, xe [B,T,56] EMOCA, data_ids)``; the mask is all ones; the model runs ``beam_size`` times in
     ``mode='train'`` (teacher forcing: every pass of a deterministic model gives the same prediction); per clip the candidate with
     the smallest ``mean_t ||pred_t - true_t||_2`` is kept, a later candidate replaces it only when STRICTLY smaller.  ``y_true`` is
     ``xe[:, 1:]`` and is cut by one more frame when stored (and so are the predictions): the stored arrays have T - 2 frames.
-    Returns ``(y_trues_all, y_preds_all, x_all, data_ids_all)``; ``x_all`` stays empty."""
+    Returns ``(y_trues_all, y_preds_all, x_all, data_ids_all)``; ``x_all`` stays empty.  ``filter_logits_fn`` /
+    ``filter_kwargs`` are handed to the model (SpeakerSLMFT.forward); the teacher-forced pass of this protocol samples nothing, so
+    they change its result only for a model that generates."""
+    fkw = dict(filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs) if (filter_logits_fn is not None or filter_kwargs) else {}
     y_trues_all, y_preds_all, x_all, data_ids_all = [], [], [], []
     model.eval()
     with torch.no_grad():
@@ -305,7 +315,7 @@ def evaluate_test_epoch_biwi(model, loader, device, beam_size=10):
             cur_best = [float("inf")] * n
             best = [None] * n
             for _ in range(beam_size):
-                _, _, y_preds = model(xv, xe, xa, mask, xt, mode="train", speaker_ids=speaker_ids)
+                _, _, y_preds = model(xv, xe, xa, mask, xt, mode="train", speaker_ids=speaker_ids, **fkw)
                 for j in range(n):
                     cp = y_preds[j, 1:, :].cpu().numpy()
                     ct = y_true[j, 1:, :].cpu().numpy()
@@ -399,7 +409,9 @@ def generate_sharded(model, v_speaker, v_listener, v_audio, mask, **forward_kw):
     decoded coefficients are all-gathered (RCCL over xGMI on GPUs).  The shard is run with
     ``batch_row_offset=lo`` (the VQ decoder's batch-row positional quirk) and ``shard=(lo, B)`` (the sampler's
     counter-based generator is indexed by the global row), so the gathered result equals the single-process
-    result for the same seed / injected noise.  Returns (tokens [B,T-1] int32, pred [B,T-1,56]) on every rank."""
+    result for the same seed / injected noise.  ``filter_logits_fn`` / ``filter_kwargs`` (the sampler filter, SLMFT.forward)
+    travel in ``forward_kw`` like every other argument of the forward pass: the filter acts on a row's own logits, so a rank
+    filters what the single-process batch would.  Returns (tokens [B,T-1] int32, pred [B,T-1,56]) on every rank."""
     pre_sharded = forward_kw.pop("pre_sharded", False)
     rank, world = ddist.rank(), ddist.world_size()
     if pre_sharded:

@@ -20,6 +20,7 @@ from dimx import lib as L  # noqa: E402
 from dimx.dataset.data_loader import get_vico_dataloaders  # noqa: E402   (was: from dataset.data_loader import ...)
 from dimx.mymetrics import print_metrics, print_metrics_full  # noqa: E402 (was: from mymetrics import ...)
 from dimx.seq2seq_pretrain import SLMFT  # noqa: E402                     (was: from seq2seq_pretrain import SLMFT)
+from dimx import sampling  # noqa: E402
 from dimx.x_engine_pt import evaluate_test_epoch  # noqa: E402            (was: from x_engine_pt import ...)
 
 
@@ -34,7 +35,11 @@ def main():
     ap.add_argument("--out", default="l2l_listener_continuations.pkl")
     ap.add_argument("--prompt-frames", type=int, default=30,
                     help="continue the first N ground-truth listener frames of every clip instead of starting from frame 0 alone")
+    sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
+    sampler = sampling.filter_from_args(args)
+    if sampler:
+        print("sampler filter: %s %s" % (sampler["filter_logits_fn"], sampler["filter_kwargs"] or "(defaults)"))
 
     crank = 0
     device = torch.device("cuda:{}".format(crank))
@@ -54,7 +59,7 @@ def main():
 
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, val_loader, device, beam_size=args.beam,
-                                                        prompt_frames=args.prompt_frames)
+                                                        prompt_frames=args.prompt_frames, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d in %.2f s" % (len(y_true), args.beam, time.time() - t0))
     print_metrics(y_true, y_pred, x)

@@ -20,6 +20,7 @@ from dimx import lib as L  # noqa: E402
 from dimx.dataset.data_loader import get_vico_dataloaders  # noqa: E402
 from dimx.metrics import ListenerMetrics  # noqa: E402
 from dimx.seq2seq_pretrain import SLMFT  # noqa: E402
+from dimx import sampling  # noqa: E402
 from dimx.x_engine_pt import evaluate_test_epoch  # noqa: E402
 
 
@@ -33,7 +34,11 @@ def main():
     ap.add_argument("--ckpt", default="best_vico_causal.pt")
     ap.add_argument("--out", default="l2l_listener_predictions.pkl")
     ap.add_argument("--no-sid", action="store_true", help="leave out the two SID lines")
+    sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
+    sampler = sampling.filter_from_args(args)
+    if sampler:
+        print("sampler filter: %s %s" % (sampler["filter_logits_fn"], sampler["filter_kwargs"] or "(defaults)"))
 
     device = torch.device("cuda:0")
     model = SLMFT(numeric_mode=L.MODE_PERF_BF16 if args.bf16 else L.MODE_PARITY_F32).to(device)
@@ -49,7 +54,8 @@ def main():
 
     acc = ListenerMetrics(sid=not args.no_sid)    # SID on the GPU too (csrc/kmeans_sid.hip): no per-clip list is needed to print
     t0 = time.time()
-    y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc)
+    y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc,
+                                                        **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d in %.2f s" % (len(y_true), args.beam, time.time() - t0))
     t0 = time.time()

@@ -257,6 +257,25 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
  * LayerNorm's precision guard (a residual row whose |mean| exceeds 8 standard deviations: the batch is regenerated with the
  * row-phase LayerNorm, the deferred form stays off for the handle, the event is counted here too). */
 int dimx_chain_faults(dimx_handle h);
+
+/* Sampler filters of AutoregressiveWrapper.generate(filter_logits_fn, filter_kwargs).  All act on the raw logits of a row,
+ * p = softmax(logits) over the 512 entries, temperature afterwards; the definition is dimx/sampling.py (float64):
+ *   TOP_K  the call's top_k argument (the k-th largest logit and everything tied with it); the state after dimx_create
+ *   TOP_P  a = thres: keep i iff the probability mass ranked strictly above i is <= thres (thres >= 1: everything)
+ *   MIN_P  a = min_p: keep i iff p_i >= min_p * p_max (min_p = 0: everything)
+ *   TOP_A  a = min_p_pow, b = min_p_ratio: keep i iff p_i >= p_max^a * b
+ * Equal logits are kept or dropped together and the arg-max always stays. */
+typedef enum {
+    DIMX_FILTER_TOP_K = 0,
+    DIMX_FILTER_TOP_P = 1,
+    DIMX_FILTER_MIN_P = 2,
+    DIMX_FILTER_TOP_A = 3
+} dimx_filter_kind;
+/* The filter of this handle's dimx_generate / dimx_generate_prompted calls, until it is set again.  Kind 0: the call's top_k
+ * (a, b ignored); the other kinds ignore the call's top_k.  DIMX_ERR_ARG (setting unchanged) for an unknown kind, a NaN,
+ * thres < 0, min_p outside [0, 1], min_p_pow or min_p_ratio < 0.  a and b reach the sampler through device memory: another
+ * value replays the captured step graph, another kind captures a new one. */
+int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b);
 /* Decoders without positional embedding (variant 0): the first layer's q/k/v depend on the input token alone, so dimx_generate
  * reads them from a table over the token ids instead of projecting them at every step.  The table is built with the decode
  * step's own kernels (bit-identical rows) on first use and whenever the rows per call, the numeric mode or the decoder weights
@@ -681,6 +700,11 @@ int dimx_op_sid_assign(const float* frames, long frame_stride, int M, int W, int
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
+/* The same launch with a filter kind (dimx_set_sampler_filter; kind 0 uses top_k, the others a / b).  keep_out (optional,
+ * [R,512] uint8): the kept set the kernel used, also for a greedy launch.  Invalid settings: DIMX_ERR_ARG. */
+int dimx_op_sample_filtered(const float* logits, int R, int kind, int top_k, float a, float b, float temperature,
+                            const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens, uint8_t* keep_out,
+                            void* stream);
 
 #ifdef __cplusplus
 }

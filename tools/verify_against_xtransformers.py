@@ -10,7 +10,8 @@ The fixtures are consumed by tests/test_oracle_xt_golden.py (oracle vs library) 
 path vs library); both skip while the files are absent.  Covered: the two SLMFT encoder stacks (causal attn_mask +
 padding mask), AutoregressiveWrapper.forward incl. its mask_prob=0.15 self-attention key mask and loss, generate
 (greedy and multinomial with injected Exp(1) noise), and the legacy ListenerGenerator encoder / decoder (absolute
-positional embedding, no causal mask in the encoder).  Randomness is captured, not replayed: torch.randn (key mask) is
+positional embedding, no causal mask in the encoder), and the kept sets of the four sampler filters (top_k, top_p, min_p,
+top_a) of dimx.sampling against the wheel's functions of the same names (printed only, no fixture).  Randomness is captured, not replayed: torch.randn (key mask) is
 wrapped to record what the library drew, torch.multinomial is replaced by argmax(p / q) with q from dimx.prng
 (tests/golden/sampler_multinomial.npz shows the two are the same function of (p, q)).
 """
@@ -154,6 +155,28 @@ def legacy_case(xt, write):
                             tf_logits=logits.numpy(), tf_loss=loss.item(), gen_sampled=sampled.numpy())
 
 
+def filters_case(xt):
+    """the four filter bodies of dimx.sampling (the definition the HIP sampler is tested against) against the wheel's own
+    functions, on untied rows (with ties the wheel's top_p follows the order of torch's sort)"""
+    from dimx import sampling
+    arw = getattr(xt, "autoregressive_wrapper", xt)
+    cases = [("top_k", {}), ("top_k", {"k": 5}), ("top_p", {}), ("top_p", {"thres": 0.5}), ("min_p", {}), ("min_p", {"min_p": 0.02}),
+             ("top_a", {}), ("top_a", {"min_p_pow": 1.5, "min_p_ratio": 0.2})]
+    for scale in (1, 3, 6):
+        pool = prng.normal(SEED, "xt.filters.%d" % scale, (128, 512)).astype(np.float64) * scale
+        l = pool[[len(np.unique(r)) == 512 for r in pool]][:64]
+        for name, kw in cases:
+            fn = getattr(arw, name, None)
+            if fn is None:
+                print("filters: %s is not in this wheel" % name)
+                continue
+            lib_keep = torch.isfinite(fn(torch.from_numpy(l.copy()), **kw)).numpy()
+            edge = sampling.undecidable(l, name, 1e-12, **kw)
+            bad = int((lib_keep[~edge] != sampling.keep_mask(l, name, **kw)[~edge]).any(axis=1).sum())
+            print("filters: %-6s %-44s scale %d: rows that differ %d of %d (%d at a float64 knife edge left out)"
+                  % (name, kw or "(defaults)", scale, bad, int((~edge).sum()), int(edge.sum())))
+
+
 def main():
     try:
         import x_transformers as xt
@@ -164,6 +187,7 @@ def main():
     write = "--write-golden" in sys.argv
     slmft_case(xt, write)
     legacy_case(xt, write)
+    filters_case(xt)
     return 0
 
 
