@@ -7,6 +7,7 @@
 //   fd_try_kernel   (one block per (clip, try)): mu2, S2, M = A^T S2 A with A read back from the workspace, and the scalar fd.
 //   fd_pick_kernel  (one block per clip): first minimum of the row (NaN counts as +inf), ok flag, gather of the winner.
 #include "frechet.hpp"
+#include "pick_gather.hpp"
 
 namespace dimx {
 namespace {
@@ -120,12 +121,7 @@ __global__ __launch_bounds__(kFdThreads) void fd_pick_kernel(FdArgs a) {
     if (!a.best) return;
     const int n = sh_ok ? frechet::valid_frames(a.lens, a.L, j) : 0;
     const float* src = a.yp + (size_t)j * a.yp_cs + (size_t)sh_win * a.yp_ss;
-    float* dst = a.best + (size_t)j * a.L * a.W;
-    const int total = a.L * a.W;
-    for (int e = threadIdx.x; e < total; e += kFdThreads) {
-        const int t = e / a.W, c = e - t * a.W;
-        dst[e] = t < n ? src[(size_t)t * a.yp_fs + c] : 0.f;
-    }
+    gather_winner_rows<kFdThreads>(src, a.yp_fs, a.best + (size_t)j * a.L * a.W, a.L, a.W, n);
 }
 
 size_t fd_ws_doubles(int B, int F) { return (size_t)B * ((size_t)F * F + F + 1); }

@@ -242,8 +242,14 @@ class Engine:
 
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
                  n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False, filter_logits_fn=None,
-                 filter_kwargs=None):
+                 filter_kwargs=None, return_scores=False):
         """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
+
+        ``return_scores``: the return value gains a trailing dimx.scoring.SeqScores (score f64, count int32, both [B*S]): the
+        log-likelihood of every sampled sequence under softmax(raw logits) over the columns dimx.scoring.scored_columns names
+        (positions inside the clip's length and past its prompt), by dimx_op_seq_logprob on this call's logits dump.  The dump is
+        requested internally whether or not ``return_logits`` is set and costs R x n x 2 KiB of device memory for the call -- 1.57 GB
+        at 256 clips x 10 tries x 300 frames; lengths and prompt lengths are derived on the device, nothing is read back.
 
         ``filter_logits_fn`` / ``filter_kwargs``: the sampler filter of AutoregressiveWrapper.generate -- ``top_k``, ``top_p``,
         ``min_p`` or ``top_a`` of dimx.sampling, as the object or its name, with that function's keyword arguments.  None is
@@ -262,12 +268,12 @@ class Engine:
                 self.set_sampler_filter(kind, fa, fb)
                 try:
                     return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt,
-                                         prompt_len, prefill, no_prefill)
+                                         prompt_len, prefill, no_prefill, return_scores=return_scores)
                 finally:
                     self.set_sampler_filter(0)
         if prompt is not None:
             return self._generate_prompted(prompt, prompt_len, prefill, no_prefill, mask_u8, T, temperature, top_k, noise, seed,
-                                           return_logits, n_samples)
+                                           return_logits, n_samples, return_scores)
         B = start.shape[0]
         R = B * n_samples
         start = start.to(torch.int32).contiguous()
@@ -278,16 +284,25 @@ class Engine:
         n = self.n_gen(T)
         tokens = torch.empty(R, n, dtype=torch.int32, device=self.device)
         lg = torch.empty(R, n, self.dims.num_tokens, dtype=torch.float32, device=self.device) \
-            if return_logits else None
+            if (return_logits or return_scores) else None
         ws, wsb = self.workspace(B, T, n_samples)
         L.check(self.lib.dimx_generate(self.h, L.ptr(start), L.ptr(mask_u8), B, T, int(n_samples), float(temperature),
                                        int(top_k),
                                        L.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(tokens), L.ptr(lg), ws,
                                        wsb, self._s()), "dimx_generate")
-        return (tokens, lg) if return_logits else tokens
+        return self._generated(tokens, lg, mask_u8, T, n_samples, None, return_logits, return_scores)
+
+    def _generated(self, tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores):
+        """generate()'s return value: tokens[, logits][, SeqScores of the sampled columns (``plen``: effective prompt lengths)]"""
+        out = (tokens, lg) if return_logits else (tokens,)
+        if return_scores:
+            from .scoring import scored_columns
+            first, last = scored_columns(T, tokens.shape[1], mask_u8.sum(1, dtype=torch.int32), plen)
+            out += (op_seq_logprob(lg, tokens, first, last, rows_per_clip=n_samples),)
+        return out if len(out) > 1 else out[0]
 
     def _generate_prompted(self, prompt, prompt_len, prefill, no_prefill, mask_u8, T, temperature, top_k, noise, seed,
-                           return_logits, n_samples):
+                           return_logits, n_samples, return_scores=False):
         B, Pmax = prompt.shape
         R = B * n_samples
         prompt = prompt.to(torch.int32).contiguous()
@@ -299,7 +314,7 @@ class Engine:
         self._chk(prompt, prompt_len, mask_u8, noise)
         n = self.n_gen(T)
         tokens = torch.empty(R, n, dtype=torch.int32, device=self.device)
-        lg = torch.empty(R, n, self.dims.num_tokens, dtype=torch.float32, device=self.device) if return_logits else None
+        lg = torch.empty(R, n, self.dims.num_tokens, dtype=torch.float32, device=self.device) if (return_logits or return_scores) else None
         # the workspace the context was built in, never grown here (that would drop the context): the library refuses a
         # prefill it is too small for (DIMX_ERR_WORKSPACE, before any launch) -- build the context with prompt_frames >= prefill
         ws, wsb = self.workspace(B, T, n_samples)
@@ -307,7 +322,11 @@ class Engine:
                                                 L.ptr(mask_u8), B, T, int(n_samples), float(temperature), int(top_k), L.ptr(noise),
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(tokens), L.ptr(lg), 1 if no_prefill else 0,
                                                 ws, wsb, self._s()), "dimx_generate_prompted")
-        return (tokens, lg) if return_logits else tokens
+        plen = None
+        if return_scores:    # the library's clamp (include/dimx.h): prompt_len into [P0, Pmax] (no prefill: P0 = 1), no prompt_len = Pmax
+            plen = prompt_len.clamp(1 if no_prefill else P0, Pmax) if prompt_len is not None \
+                else torch.full((B,), Pmax, dtype=torch.int32, device=self.device)
+        return self._generated(tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores)
 
     def mesh_head(self, motion, template=None, safe=False, out=None):
         """EmocaConverter head: motion [B,L,56] -> mesh [B,L,V] = vertice_map_reverse(vertice_map_reverse_lstm(motion)) +
@@ -707,6 +726,81 @@ def op_fd_select(y_true, y_pred, lens, cols=(0, None), want_best=True):
                                       L.ptr(lens_d), B, S, Ln, W, c0, F, L.ptr(fd), L.ptr(win), L.ptr(ok), L.ptr(best),
                                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(dev)), "dimx_op_fd_select")
     return fd, win, ok, best
+
+
+def op_seq_logprob(logits, tokens, first=None, last=None, rows_per_clip=1, want_tokens=False):
+    """Sequence log-likelihoods over dumped logits (dimx_op_seq_logprob, csrc/seq_score.hip; the definition is dimx.scoring):
+    logits [R, n, 512] f32 and tokens [R, n] on one GPU, first / last [R / rows_per_clip] (tensors or host sequences; None = 0 / n)
+    -> SeqScores(score f64 [R], count int32 [R]); with ``want_tokens`` (SeqScores, per-token f64 [R, n]).  Strided views of ``logits``
+    and ``tokens`` are passed as they are: only the innermost stride must be 1 (tokens of another dtype than int32 are converted).
+    Asynchronous on the current stream.  CPU tensors raise: there is no CPU fallback (dimx.scoring.sequence_scores is the host form)."""
+    from .scoring import VOCAB, SeqScores
+    if not (torch.is_tensor(logits) and torch.is_tensor(tokens) and logits.is_cuda and tokens.is_cuda):
+        raise L.DimxError("op_seq_logprob runs on the GPU only: logits / tokens must be CUDA tensors (no CPU fallback)")
+    if logits.dim() != 3 or logits.shape[2] != VOCAB or tuple(tokens.shape) != tuple(logits.shape[:2]) or tokens.device != logits.device:
+        raise L.DimxError("op_seq_logprob: logits [R, n, %d] and tokens [R, n] on one device expected, got %s and %s"
+                          % (VOCAB, tuple(logits.shape), tuple(tokens.shape)))
+    lib = L.load()
+    dev = logits.device
+    R, n = int(logits.shape[0]), int(logits.shape[1])
+    rpc = int(rows_per_clip)
+    logits = logits if logits.dtype == torch.float32 else logits.float()
+    if logits.stride(2) != 1:
+        logits = logits.contiguous()
+    tokens = tokens if tokens.dtype == torch.int32 else tokens.to(torch.int32)
+    if tokens.stride(1) != 1 and n > 1:
+        tokens = tokens.contiguous()
+    clips = R // rpc if rpc >= 1 and R % rpc == 0 else -1      # the library refuses the call; no lens are uploaded for it
+    first_d = _lens_i32(first, dev, clips, "op_seq_logprob(first)") if first is not None and clips >= 0 else None
+    last_d = _lens_i32(last, dev, clips, "op_seq_logprob(last)") if last is not None and clips >= 0 else None
+    score = torch.empty(R, dtype=torch.float64, device=dev)
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    tok_lp = torch.empty(R, n, dtype=torch.float64, device=dev) if want_tokens else None
+    step_stride = logits.stride(1) if n > 1 else VOCAB     # a dimension of one entry has no meaningful stride
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_seq_logprob(ctypes.c_void_p(logits.data_ptr()), logits.stride(0), step_stride,
+                                        ctypes.c_void_p(tokens.data_ptr()), tokens.stride(0), L.ptr(first_d), L.ptr(last_d), rpc, R, n,
+                                        L.ptr(tok_lp), L.ptr(score), L.ptr(count), L.stream_ptr(dev)), "dimx_op_seq_logprob")
+    out = SeqScores(score, count)
+    return (out, tok_lp) if want_tokens else out
+
+
+def op_score_select(score, y_pred, lens, tokens=None):
+    """Best-of-S selection by sequence log-likelihood (dimx_op_score_select, csrc/seq_score.hip): score [B, S] f64 (or [B*S]),
+    y_pred [B, S, L, W] f32 on the same GPU, lens[j] = valid frames of clip j, tokens [B*S, n] (optional)
+    -> (win [B] int32, ok [B] uint8, best [B, L, W] f32[, best_tokens [B, n] int32]): the first maximum of each row (NaN
+    counts as -inf), ok = 0 when no try of the clip has a finite score, the winner's rows (zero for t >= lens[j] and for ok = 0) and
+    its token row (-100 for ok = 0).  Strides as in op_fd_select.  Asynchronous on the current stream.  CPU tensors raise."""
+    if not (torch.is_tensor(score) and torch.is_tensor(y_pred) and score.is_cuda and y_pred.is_cuda):
+        raise L.DimxError("op_score_select runs on the GPU only: score / y_pred must be CUDA tensors (no CPU fallback)")
+    if y_pred.dim() != 4 or score.numel() != y_pred.shape[0] * y_pred.shape[1] or score.device != y_pred.device:
+        raise L.DimxError("op_score_select: score [B, S] and y_pred [B, S, L, W] on one device expected, got %s and %s"
+                          % (tuple(score.shape), tuple(y_pred.shape)))
+    lib = L.load()
+    dev = y_pred.device
+    B, S, Ln, W = (int(v) for v in y_pred.shape)
+    score = score.to(torch.float64).reshape(B, S).contiguous()
+    y_pred = _f32_rows(y_pred, W > 1)
+    lens_d = _lens_i32(lens, dev, B, "op_score_select")
+    n, tok_rs = 0, 0
+    if tokens is not None:
+        if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.device == dev and tokens.dim() == 2 and tokens.shape[0] == B * S):
+            raise L.DimxError("op_score_select: tokens [B*S, n] on the scores' device expected")
+        tokens = tokens if tokens.dtype == torch.int32 else tokens.to(torch.int32)
+        n = int(tokens.shape[1])
+        if tokens.stride(1) != 1 and n > 1:
+            tokens = tokens.contiguous()
+        tok_rs = tokens.stride(0)
+    win = torch.empty(B, dtype=torch.int32, device=dev)
+    ok = torch.empty(B, dtype=torch.uint8, device=dev)
+    best = torch.empty(B, Ln, W, dtype=torch.float32, device=dev)
+    best_tok = torch.empty(B, n, dtype=torch.int32, device=dev) if tokens is not None else None
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_score_select(L.ptr(score), ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1),
+                                         y_pred.stride(2), L.ptr(lens_d), None if tokens is None else ctypes.c_void_p(tokens.data_ptr()),
+                                         tok_rs, B, S, Ln, W, n, L.ptr(win), L.ptr(ok), L.ptr(best), L.ptr(best_tok), L.stream_ptr(dev)),
+                "dimx_op_score_select")
+    return (win, ok, best) if tokens is None else (win, ok, best, best_tok)
 
 
 def fd_select_sweeps(device, B, S, F):

@@ -175,6 +175,10 @@ SIGNATURES = {
                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dimx_op_sid_assign": (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "dimx_op_seq_logprob": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_int,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dimx_op_score_select": (c_int, [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, ctypes.c_long,
+                                     c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
     "dimx_op_sample_filtered": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_uint64, c_uint64,

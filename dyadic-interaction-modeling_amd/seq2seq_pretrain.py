@@ -153,7 +153,7 @@ class SLMFT(_EngineOwner):
     @torch.no_grad()
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
                         seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None):
+                        filter_kwargs=None, return_scores=False):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -166,7 +166,11 @@ class SLMFT(_EngineOwner):
 
         ``filter_logits_fn`` / ``filter_kwargs`` (mode 'val'): the sampler filter, as AutoregressiveWrapper.generate takes it --
         ``top_k``, ``top_p``, ``min_p`` or ``top_a`` of dimx.sampling (object or name).  The default is the reference's call:
-        top_k with k = ceil(0.1 * 512) = 52."""
+        top_k with k = ceil(0.1 * 512) = 52.
+
+        ``return_scores`` (mode 'val'): a third value, the SeqScores [B*S] of the sampled sequences (Engine.generate)."""
+        if return_scores and mode != "val":
+            raise ValueError("return_scores applies to mode='val' (SLMFT.score is the teacher-forced form)")
         prompt_frames = _check_prompt_frames(prompt_frames, z_l.shape[1])
         dev = (x_s if x_s is not None else v_speaker).device
         eng = self.engine(dev)
@@ -188,13 +192,15 @@ class SLMFT(_EngineOwner):
         else:
             seed_v = 0 if noise is not None else self._user_seed(seed)
         if prompt_frames > 1:
-            tokens = eng.generate(None, m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
-                                  prompt=z_l[:, :prompt_frames], prompt_len=plen, prefill=p0,
-                                  filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
+            out = eng.generate(None, m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
+                               prompt=z_l[:, :prompt_frames], prompt_len=plen, prefill=p0,
+                               filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores)
         else:
-            tokens = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
-                                  filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
-        return 0.0, tokens.long()
+            out = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
+                               filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores)
+        if return_scores:
+            return 0.0, out[0].long(), out[1]
+        return 0.0, out.long()
 
     def draw_kv_mask(self, B, T, device, generator=None):
         """AutoregressiveWrapper(mask_prob=0.15) key mask (reference ctor :419): keep-mask [B,T-1]."""
@@ -265,7 +271,7 @@ class SLMFT(_EngineOwner):
     def forward(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                 return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                filter_kwargs=None):
+                filter_kwargs=None, return_scores=False):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
@@ -274,10 +280,16 @@ class SLMFT(_EngineOwner):
         [B,T-1,56]: its first plen-1 frames are the VQ decoder's rendering of the ground-truth codes, the rest is
         generated.  P >= T raises ValueError.
 
-        ``filter_logits_fn`` / ``filter_kwargs`` (mode 'val'): the sampler filter (see ``forward_decoder``)."""
+        ``filter_logits_fn`` / ``filter_kwargs`` (mode 'val'): the sampler filter (see ``forward_decoder``).
+
+        ``return_scores`` (mode 'val'; any other mode raises ValueError): the log-likelihood of every generated sequence under the
+        model (dimx.scoring.SeqScores: score f64 and count int32, [B] or [B,S]) is appended after ``pred``, or after ``tokens``
+        with ``return_tokens``.  Cost and scored columns: ``Engine.generate``."""
         prompt_frames = _check_prompt_frames(prompt_frames, mask.shape[1])
         if prompt_frames > 1 and mode != "val":
             raise ValueError("prompt_frames applies to mode='val'")
+        if return_scores and mode != "val":
+            raise ValueError("return_scores applies to mode='val' (SLMFT.score is the teacher-forced form)")
         if self._wants_grad(mode):
             return self._forward_autograd(v_speaker, v_listener, v_audio, mask, kv_mask=kv_mask, z_l=z_l,
                                           return_tokens=return_tokens)
@@ -286,13 +298,13 @@ class SLMFT(_EngineOwner):
                                         greedy=greedy, seed=seed, temperature=temperature,
                                         batch_row_offset=batch_row_offset, return_tokens=return_tokens,
                                         n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths,
-                                        filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
+                                        filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                         return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None):
+                        filter_kwargs=None, return_scores=False):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -307,10 +319,11 @@ class SLMFT(_EngineOwner):
         eng = self.engine(v_speaker.device)
         eng.set_shard(*(shard if shard is not None else (0, 0)))
         try:
-            l_ce_l, px_l = self.forward_decoder(None, z_l, v_audio, mask, mode, v_speaker=v_speaker, noise=noise,
-                                                kv_mask=kv_mask, greedy=greedy, seed=seed, temperature=temperature,
-                                                n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
-                                                filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
+            l_ce_l, px_l, *scores = self.forward_decoder(None, z_l, v_audio, mask, mode, v_speaker=v_speaker, noise=noise,
+                                                         kv_mask=kv_mask, greedy=greedy, seed=seed, temperature=temperature,
+                                                         n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
+                                                         filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs,
+                                                         return_scores=return_scores)
         finally:
             eng.set_shard(0, 0)
         pred = self.forward_vq_decoder(px_l, mode=mode, batch_row_offset=batch_row_offset, rows_per_clip=S)
@@ -322,12 +335,37 @@ class SLMFT(_EngineOwner):
             l_cont_l = self.forward_continuous_loss(pred, v_listener, mask)
         total_loss = l_ce_l + l_cont_l
         d = {"l_ce_s": 0, "l_ce_l": l_ce_l, "l_cont_s": 0, "l_cont_l": l_cont_l, "nce": 0, "c_acc": 0}
+        out = (total_loss, d, pred)
         if return_tokens:
             tokens = px_l if mode != "train" else torch.argmax(px_l, dim=-1)
             if S > 1:
                 tokens = tokens.view(mask.shape[0], S, -1)
-            return total_loss, d, pred, tokens
-        return total_loss, d, pred
+            out += (tokens,)
+        if return_scores:
+            shape = (mask.shape[0], S) if S > 1 else (mask.shape[0],)
+            out += (type(scores[0])(scores[0].score.view(shape), scores[0].count.view(shape)),)
+        return out
+
+
+    @torch.no_grad()
+    def score(self, v_speaker, v_listener, v_audio, mask, z_l=None):
+        """Teacher-forced log-likelihood of the clip's own listener codes (``forward_vq`` of ``v_listener``) or of given codes
+        ``z_l`` [B,T] under the model: one ``decode_tf`` pass with NO random key mask, then dimx_op_seq_logprob on its logits with the
+        tokens ``z_l[:, 1:]`` over the columns inside each clip's length -> dimx.scoring.SeqScores [B] (score f64, count int32).
+        ``dimx.scoring.perplexity`` of it is the model's perplexity on these codes."""
+        from .engine import op_seq_logprob
+        from .scoring import scored_columns
+        with self.engine_pinned():
+            mask = mask.bool()
+            eng = self.engine(v_speaker.device)
+            if z_l is None:
+                _, z_l = self.forward_vq(v_speaker, v_listener, mask, with_speaker=False)
+            m8 = self._mask8(mask)
+            T = mask.shape[1]
+            self._build_context(eng, None, v_speaker, v_audio, m8, False)
+            logits, _, _ = eng.decode_tf(z_l, m8, None)
+            first, last = scored_columns(T, T - 1, mask.sum(1, dtype=torch.int32))
+            return op_seq_logprob(logits, z_l[:, 1:], first, last)
 
 
 class SLM(_EngineOwner):

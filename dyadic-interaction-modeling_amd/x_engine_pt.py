@@ -141,6 +141,20 @@ def _select_hip(y_true, y_preds, lens, world, device, total=None, metrics=None, 
     keeps None, as in _select_device."""
     from .engine import op_fd_select
     _, _, ok, best = op_fd_select(y_true, y_preds, lens)
+    return _winners_to_host(y_true, y_preds, ok, best, lens, world, device, total, metrics, x)
+
+
+def _select_likelihood(y_true, y_preds, scores, lens, world, device, total=None, metrics=None, x=None):
+    """select="likelihood": the try the model itself scores highest (dimx.engine.op_score_select, csrc/seq_score.hip, on the
+    generation's own SeqScores); no distance is computed and ``y_true`` is read by ``metrics`` only.  A clip with nothing to score
+    has all scores 0.0: try 0 wins with ok = 1 and the clip keeps an empty array."""
+    from .engine import op_score_select
+    _, ok, best = op_score_select(scores.score, y_preds, lens)
+    return _winners_to_host(y_true, y_preds, ok, best, lens, world, device, total, metrics, x)
+
+
+def _winners_to_host(y_true, y_preds, ok, best, lens, world, device, total, metrics, x):
+    """the tail of a selection in the HIP library: ``best`` [nl, L, W] and ``ok`` [nl] lie on the device"""
     if metrics is not None:      # the winners where they lie: enqueued behind the selection, nothing is synchronised
         metrics.update(y_true, best, x, lens)
     ok = ok.cpu().tolist()
@@ -174,7 +188,7 @@ def _select(pending, skip_degenerate, world, device):
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
-                        **forward_kw):
+                        select="fd", **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -209,9 +223,27 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
 
     ``filter_logits_fn`` / ``filter_kwargs``: the sampler filter of every generation (AutoregressiveWrapper.generate's arguments:
     ``top_k``, ``top_p``, ``min_p`` or ``top_a`` of dimx.sampling, object or name); None is the reference's top-k 52.  A rank
-    of a sharded batch filters and draws exactly what the single-process batch would: the filter acts on a row's own logits."""
+    of a sharded batch filters and draws exactly what the single-process batch would: the filter acts on a row's own logits.
+
+    ``select``: "fd" (default) is the protocol above.  "likelihood" keeps, per clip, the try with the largest log-likelihood under
+    the model itself (``SLMFT.forward(return_scores=True)`` + dimx.engine.op_score_select): the selection that needs no ground
+    truth, for conversations without a recorded listener.  ``fd_backend`` is not consulted, no distance is computed and ``tgt`` is
+    used for the returned lists (and by ``metrics``) only; the winners stay on the device, so ``metrics`` works as with
+    ``fd_backend="hip"``.  It needs a batched sample count (BATCHED_SAMPLE_COUNTS, ValueError otherwise) and a ROCm GPU (a CPU
+    device raises lib.DimxError: there is no CPU fallback).  Any other value raises ValueError."""
     if filter_logits_fn is not None or filter_kwargs:
         forward_kw = dict(forward_kw, filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
+    if select not in ("fd", "likelihood"):
+        raise ValueError("select=%r: one of 'fd', 'likelihood'" % (select,))
+    by_likelihood = select == "likelihood"
+    if by_likelihood:
+        if torch.device(device).type != "cuda":
+            raise L.DimxError("evaluate_test_epoch(select='likelihood') runs on a ROCm GPU only (device %s): there is no CPU fallback; "
+                              "select='fd' with fd_backend='reference' or 'device' runs there" % (device,))
+        if not (batched_samples and beam_size in BATCHED_SAMPLE_COUNTS):
+            raise ValueError("evaluate_test_epoch(select='likelihood') scores the tries of one batched generation: beam_size must be "
+                             "one of %s with batched_samples (got %d)" % (BATCHED_SAMPLE_COUNTS, beam_size))
+        fd_backend = "hip"      # not consulted for the selection: the winners are handled where the HIP selection leaves its own
     assert fd_backend in ("reference", "device", "hip")
     if metrics is not None:
         if fd_backend != "hip":
@@ -254,6 +286,12 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
                 if prompt_frames != 1:
                     kw.update(prompt_frames=prompt_frames, lengths=src_len[lo:hi])
                 sl = [t[lo:hi].contiguous() for t in (src_s_v, tgt, src_s_a, mask)]
+                if by_likelihood:
+                    _, _, y_preds, scores = model(sl[0], sl[1], sl[2], sl[3], mode="val", n_samples=beam_size, return_scores=True, **kw)
+                    extra = dict(metrics=metrics, x=src_s_v[lo:hi]) if metrics is not None else {}
+                    y_preds_all.extend(_select_likelihood(tgt[lo:hi, 1:], y_preds, scores, [src_len[lo + j] - 1 for j in range(nl)],
+                                                          world, device, B, **extra))
+                    continue
                 if batched:
                     _, _, y_preds = model(sl[0], sl[1], sl[2], sl[3], mode="val", n_samples=beam_size, **kw)
                 else:
@@ -280,7 +318,7 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
             pending = (futs, samples, lens, nl, tgt.shape[1] - 1, tgt.shape[2], B)
         if pending is not None:
             y_preds_all.extend(_select(pending, skip_degenerate, world, device))
-    _report_epoch(model, device, "evaluate_test_epoch", len(y_trues_all), fd_backend)
+    _report_epoch(model, device, "evaluate_test_epoch", len(y_trues_all), None if by_likelihood else fd_backend)
     return y_trues_all, y_preds_all, x_all, data_ids_all
 
 

@@ -5,6 +5,10 @@ seq_len=T-N, ...)).  Selection and metrics stay over the whole clip.  Without th
 clips and weights.
 
     python examples/continue_s2s_pretrain.py --prompt-frames 30 [--clips 32] [--batch 8] [--beam 10] [--bf16] [--ckpt best_vico_causal.pt]
+                                            [--select {fd,likelihood}]
+
+--select likelihood keeps the continuation the model itself scores highest (the log-likelihood of its sampled tokens past the
+prompt) instead of the one nearest to the ground truth: beyond the prompt a deployed continuation has no ground truth to select with.
 """
 import argparse
 import os
@@ -35,6 +39,8 @@ def main():
     ap.add_argument("--out", default="l2l_listener_continuations.pkl")
     ap.add_argument("--prompt-frames", type=int, default=30,
                     help="continue the first N ground-truth listener frames of every clip instead of starting from frame 0 alone")
+    ap.add_argument("--select", choices=("fd", "likelihood"), default="fd",
+                    help="best-of-N by Frechet distance to the ground truth (the reference's protocol) or by the model's own log-likelihood")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -59,9 +65,9 @@ def main():
 
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, val_loader, device, beam_size=args.beam,
-                                                        prompt_frames=args.prompt_frames, **sampler)
+                                                        prompt_frames=args.prompt_frames, select=args.select, **sampler)
     torch.cuda.synchronize()
-    print("generated %d clips x best-of-%d in %.2f s" % (len(y_true), args.beam, time.time() - t0))
+    print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     print_metrics(y_true, y_pred, x)
     print_metrics_full(y_true, y_pred, x)
 

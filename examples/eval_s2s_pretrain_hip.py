@@ -4,7 +4,11 @@ included (examples/test_s2s_pretrain.py is the reference's driver on its host pa
 checkpoint it runs on synthetic clips and weights.
 
     python examples/eval_s2s_pretrain_hip.py [--clips 32] [--batch 8] [--beam 10] [--bf16] [--ckpt best_vico_causal.pt] [--no-sid]
-                                            [--out l2l_listener_predictions.pkl]
+                                            [--select {fd,likelihood}] [--out l2l_listener_predictions.pkl]
+
+--select likelihood keeps, per clip, the try the model itself scores highest (its log-likelihood, csrc/seq_score.hip) instead of the
+try nearest to the ground truth: the selection a conversation without a recorded listener allows.  For either selection the
+perplexity of the ground-truth listener codes over the epoch is printed (SLMFT.score, teacher-forced).
 """
 import argparse
 import os
@@ -19,9 +23,10 @@ import dimx  # noqa: E402,F401
 from dimx import lib as L  # noqa: E402
 from dimx.dataset.data_loader import get_vico_dataloaders  # noqa: E402
 from dimx.metrics import ListenerMetrics  # noqa: E402
+from dimx.scoring import SeqScores, perplexity  # noqa: E402
 from dimx.seq2seq_pretrain import SLMFT  # noqa: E402
 from dimx import sampling  # noqa: E402
-from dimx.x_engine_pt import evaluate_test_epoch  # noqa: E402
+from dimx.x_engine_pt import _prepare, evaluate_test_epoch  # noqa: E402
 
 
 def main():
@@ -34,6 +39,8 @@ def main():
     ap.add_argument("--ckpt", default="best_vico_causal.pt")
     ap.add_argument("--out", default="l2l_listener_predictions.pkl")
     ap.add_argument("--no-sid", action="store_true", help="leave out the two SID lines")
+    ap.add_argument("--select", choices=("fd", "likelihood"), default="fd",
+                    help="best-of-N by Frechet distance to the ground truth (the reference's protocol) or by the model's own log-likelihood")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -55,9 +62,15 @@ def main():
     acc = ListenerMetrics(sid=not args.no_sid)    # SID on the GPU too (csrc/kmeans_sid.hip): no per-clip list is needed to print
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc,
-                                                        **sampler)
+                                                        select=args.select, **sampler)
     torch.cuda.synchronize()
-    print("generated %d clips x best-of-%d in %.2f s" % (len(y_true), args.beam, time.time() - t0))
+    print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
+    parts = []
+    for batch in dataset["valid"]:      # teacher-forced: what the model thinks of the ground-truth listener codes
+        src_s_v, src_s_a, tgt, mask, _, _ = _prepare(batch, device)
+        parts.append(model.score(src_s_v, tgt, src_s_a, mask))
+    gt = SeqScores(torch.cat([p.score for p in parts]), torch.cat([p.count for p in parts]))
+    print("perplexity of the ground-truth listener codes: %.3f over %d tokens" % (perplexity(gt), int(gt.count.sum())))
     t0 = time.time()
     acc.print()
     print("metrics printed in %.3f s" % (time.time() - t0))

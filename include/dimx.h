@@ -697,6 +697,39 @@ int dimx_op_kmeans_fit(const float* frames, long frame_stride, int N, int W, int
                        void* workspace, size_t workspace_bytes, void* stream);
 int dimx_op_sid_assign(const float* frames, long frame_stride, int M, int W, int c0, int F, const double* centers, int K, int64_t* hist,
                        double* sid, int32_t* labels, void* stream);
+/* Sequence log-likelihoods over dumped logits and the best-of-S pick by them (csrc/seq_score.hip; the definition is
+ * dimx/scoring.py): the model's own verdict on a sampled (or given) token sequence, the selection criterion that needs no ground
+ * truth.  All pointers are device memory; the vocabulary is the sampler's 512 entries.
+ * dimx_op_seq_logprob:
+ *   logits f32: row r, column c holds 512 entries (element stride 1) starting at logits + r*row_stride + c*step_stride (elements,
+ *       taken as long; step_stride >= 512): the logits_out dump of dimx_generate / dimx_generate_prompted, the logits of
+ *       dimx_decode_tf, or a view of either
+ *   tokens int32: row r, column c at tokens + r*tok_row_stride + c.  A token outside [0, 512) (the -100 padding of forward_vq) is
+ *       skipped and not counted, as ce_argmax_kernel skips it; its column's logits are never read
+ *   first / last int32 [R / rows_per_clip] or NULL (= 0 / n): row r belongs to clip r / rows_per_clip and sums the columns
+ *       clamp(first[clip], 0, n) <= c < clamp(last[clip], 0, n); columns outside are never read
+ *   score f64 [R] = sum over the summed columns of logits[tok] - logsumexp(logits), float64 throughout (exact f32 row maximum, exp of
+ *       the double difference, double sums and log);  count int32 [R]: the columns summed.  An empty range gives (0.0, 0)
+ *   tok_logprob f64 [R, n] or NULL: the per-column terms, 0 outside the range and for skipped tokens.  (f64, not f32: a term is the
+ *       float64 value of the definition like the sums)
+ * dimx_op_score_select:
+ *   score f64 [B, S];  win int32 [B]: first maximum of the row, NaN counting as -inf;  ok uint8 [B]: 0 when no try of the clip has a
+ *       finite score
+ *   y_pred f32 [B, S, L, W], lens int32 [B], best f32 [B, L, W] or NULL: the winning try's rows with the clip / sample / frame strides
+ *       and the lens clamp of dimx_op_fd_select, zero for t >= lens[b] and for clips with ok = 0.  y_pred and lens may be NULL when
+ *       best is
+ *   tokens int32 (row b*S + s at tokens + (b*S + s)*tok_row_stride), best_tokens int32 [B, n] or NULL: the winner's token row, -100
+ *       for clips with ok = 0.  tokens may be NULL when best_tokens is
+ * Asynchronous on `stream`: one launch each, no workspace, no allocation, no host synchronisation, no atomics, fixed summation
+ * orders (bit-reproducible).  DIMX_ERR_ARG for a null required pointer, n, B, S or rows_per_clip below 1, a negative R or stride,
+ * step_stride < 512, an R that is not a multiple of rows_per_clip, L or W below 1 with best; nothing is enqueued then.  R = 0 with
+ * valid arguments is a no-op that returns 0. */
+int dimx_op_seq_logprob(const float* logits, long row_stride, long step_stride, const int32_t* tokens, long tok_row_stride,
+                        const int32_t* first, const int32_t* last, int rows_per_clip, int R, int n, double* tok_logprob, double* score,
+                        int32_t* count, void* stream);
+int dimx_op_score_select(const double* score, const float* y_pred, long yp_clip_stride, long yp_sample_stride, long yp_frame_stride,
+                         const int32_t* lens, const int32_t* tokens, long tok_row_stride, int B, int S, int L, int W, int n,
+                         int32_t* win, uint8_t* ok, float* best, int32_t* best_tokens, void* stream);
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
