@@ -482,19 +482,46 @@ struct SampleFilter {
     float a = 0.f, b = 0.f;
     uint8_t* keep_out = nullptr;
 };
-int launch_sample(const float* logits, int ld_logits, int R, int top_k, float temperature, const float* noise,
-                  uint64_t seed, const int32_t* step_dev, uint64_t step_host, int32_t* tokens, int tok_ld,
-                  int tok_col_from_step, int nslab, long slab_stride, float* logits_out, int logits_out_ld, int row0,
-                  int rows_total, const float* emb_table, int emb_C, float* x_next, int32_t* step_rw, unsigned* done_ctr,
-                  hipStream_t s, const float* pos_table = nullptr, float pos_scale = 0.f, int pos_rows = 0,
-                  const int32_t* dev_params = nullptr,
-                  void* y_next = nullptr, const float* y_gamma = nullptr, int y_dtype = DIMX_F32,
-                  const float* qkv0_table = nullptr, float* qkv0_out = nullptr, int qkv0_N = 0,
-                  // prompted generation: rows whose next position lies inside their clip's prompt [clips, prompt_ld] take its token
-                  // (clip = row / prompt_div; length clamp(prompt_len, dev_params[8] + 1, prompt_max), NULL = prompt_max);
-                  // epoch_rw: a second counter advanced with the step counter (steps done in this call)
-                  const int32_t* prompt = nullptr, int prompt_ld = 0, int prompt_max = 0, const int32_t* prompt_len = nullptr,
-                  int prompt_div = 1, int32_t* epoch_rw = nullptr, const SampleFilter& filt = SampleFilter());
+// one sampler launch (sample_kernel's arguments, in its order); a caller names the fields it sets
+struct SampleArgs {
+    const float* logits = nullptr;
+    int ld_logits = 0, R = 0, top_k = 0;
+    float temperature = 0.f;
+    const float* noise = nullptr;
+    uint64_t seed = 0;
+    const int32_t* step_dev = nullptr;
+    uint64_t step_host = 0;
+    int32_t* tokens = nullptr;
+    int tok_ld = 0, tok_col_from_step = 0, nslab = 0;
+    long slab_stride = 0;
+    float* logits_out = nullptr;
+    int logits_out_ld = 0, row0 = 0, rows_total = 0;
+    const float* emb_table = nullptr;
+    int emb_C = 0;
+    float* x_next = nullptr;
+    int32_t* step_rw = nullptr;
+    unsigned* done_ctr = nullptr;
+    const float* pos_table = nullptr;
+    float pos_scale = 0.f;
+    int pos_rows = 0;
+    const int32_t* dev_params = nullptr;
+    void* y_next = nullptr;
+    const float* y_gamma = nullptr;
+    int y_dtype = DIMX_F32;
+    const float* qkv0_table = nullptr;
+    float* qkv0_out = nullptr;
+    int qkv0_N = 0;
+    // prompted generation: rows whose next position lies inside their clip's prompt [clips, prompt_ld] take its token
+    // (clip = row / prompt_div; length clamp(prompt_len, dev_params[8] + 1, prompt_max), NULL = prompt_max);
+    // epoch_rw: a second counter advanced with the step counter (steps done in this call)
+    const int32_t* prompt = nullptr;
+    int prompt_ld = 0, prompt_max = 0;
+    const int32_t* prompt_len = nullptr;
+    int prompt_div = 1;
+    int32_t* epoch_rw = nullptr;
+    SampleFilter filt;
+};
+int launch_sample(const SampleArgs& a, hipStream_t s);
 // the first decoder layer's q/k/v as a table over the token ids (model.hip qkv0_table_build): id list of the build rounds,
 // slab-order sum of a round's projection into the table rows, and step 0's rows by start token
 int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s);

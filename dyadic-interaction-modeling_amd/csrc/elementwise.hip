@@ -687,35 +687,29 @@ int launch_ce_argmax(const float* logits, const int32_t* target, float* row_loss
     return DIMX_OK;
 }
 
-int launch_sample(const float* logits, int ld_logits, int R, int top_k, float temperature, const float* noise,
-                  uint64_t seed, const int32_t* step_dev, uint64_t step_host, int32_t* tokens, int tok_ld,
-                  int tok_col_from_step, int nslab, long slab_stride, float* logits_out, int logits_out_ld, int row0,
-                  int rows_total, const float* emb_table, int emb_C, float* x_next, int32_t* step_rw, unsigned* done_ctr,
-                  hipStream_t s, const float* pos_table, float pos_scale, int pos_rows, const int32_t* dev_params,
-                  void* y_next, const float* y_gamma, int y_dtype, const float* qkv0_table, float* qkv0_out, int qkv0_N,
-                  const int32_t* prompt, int prompt_ld, int prompt_max, const int32_t* prompt_len, int prompt_div,
-                  int32_t* epoch_rw, const SampleFilter& filt) {
-    DIMX_REQUIRE(logits && tokens && R > 0, DIMX_ERR_ARG, "sample: bad arguments");
+int launch_sample(const SampleArgs& a, hipStream_t s) {
+    const SampleFilter& filt = a.filt;
+    DIMX_REQUIRE(a.logits && a.tokens && a.R > 0, DIMX_ERR_ARG, "sample: bad arguments");
     DIMX_REQUIRE(filt.kind >= DIMX_FILTER_TOP_K && filt.kind <= DIMX_FILTER_TOP_A, DIMX_ERR_ARG, "sample: unknown filter kind %d", filt.kind);
-    DIMX_REQUIRE(!filt.keep_out || !prompt, DIMX_ERR_ARG, "sample: keep_out is not written for prompted rows");
-    DIMX_REQUIRE(!prompt || (step_dev && tok_col_from_step && prompt_max >= 1 && prompt_ld >= prompt_max && prompt_div >= 1),
+    DIMX_REQUIRE(!filt.keep_out || !a.prompt, DIMX_ERR_ARG, "sample: keep_out is not written for prompted rows");
+    DIMX_REQUIRE(!a.prompt || (a.step_dev && a.tok_col_from_step && a.prompt_max >= 1 && a.prompt_ld >= a.prompt_max && a.prompt_div >= 1),
                  DIMX_ERR_ARG, "sample: a prompt needs the device step counter, 1 <= prompt_max <= prompt_ld and rows per clip >= 1");
-    DIMX_REQUIRE(!qkv0_table || (x_next && qkv0_out && !pos_table && emb_C / 2 <= 16 * 64 && qkv0_N % 4 == 0 && qkv0_N > 0 &&
-                                 qkv0_N <= 12 * 256),
+    DIMX_REQUIRE(!a.qkv0_table || (a.x_next && a.qkv0_out && !a.pos_table && a.emb_C / 2 <= 16 * 64 && a.qkv0_N % 4 == 0 && a.qkv0_N > 0 &&
+                                   a.qkv0_N <= 12 * 256),
                  DIMX_ERR_ARG, "sample: the q/k/v table rides on the fused embedding (no positional table) and holds rows of k * 4 <= 3072");
-    DIMX_REQUIRE(!y_next || (x_next && y_gamma && emb_C % 128 == 0 && emb_C <= 2048), DIMX_ERR_ARG,
+    DIMX_REQUIRE(!a.y_next || (a.x_next && a.y_gamma && a.emb_C % 128 == 0 && a.emb_C <= 2048), DIMX_ERR_ARG,
                  "sample: the fused pre-norm needs the fused embedding and a width of k * 128 <= 2048");
-    const int wpb = R <= 1024 ? 1 : 4;  // one row per block for decode-sized batches: all CUs busy
+    const int wpb = a.R <= 1024 ? 1 : 4;  // one row per block for decode-sized batches: all CUs busy
     auto kern = filt.kind == DIMX_FILTER_TOP_P   ? sample_kernel<DIMX_FILTER_TOP_P>
                 : filt.kind == DIMX_FILTER_MIN_P ? sample_kernel<DIMX_FILTER_MIN_P>
                 : filt.kind == DIMX_FILTER_TOP_A ? sample_kernel<DIMX_FILTER_TOP_A>
                                                  : sample_kernel<DIMX_FILTER_TOP_K>;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(R, wpb)), dim3(64 * wpb), 0, s, logits, ld_logits, R, top_k,
-                       temperature, noise, seed, step_dev, step_host, tokens, tok_ld, tok_col_from_step, nslab < 1 ? 1 : nslab,
-                       slab_stride, logits_out, logits_out_ld, row0, rows_total, emb_table, emb_C, x_next, step_rw, done_ctr,
-                       pos_table, pos_scale, pos_rows, dev_params, y_next, y_gamma, y_dtype == DIMX_BF16 ? 1 : 0, qkv0_table,
-                       qkv0_out, qkv0_N, prompt, prompt_ld, prompt_max, prompt_len, prompt_div < 1 ? 1 : prompt_div, epoch_rw,
-                       filt.a, filt.b, filt.keep_out);
+    hipLaunchKernelGGL(kern, dim3(ceil_div(a.R, wpb)), dim3(64 * wpb), 0, s, a.logits, a.ld_logits, a.R, a.top_k,
+                       a.temperature, a.noise, a.seed, a.step_dev, a.step_host, a.tokens, a.tok_ld, a.tok_col_from_step,
+                       a.nslab < 1 ? 1 : a.nslab, a.slab_stride, a.logits_out, a.logits_out_ld, a.row0, a.rows_total, a.emb_table,
+                       a.emb_C, a.x_next, a.step_rw, a.done_ctr, a.pos_table, a.pos_scale, a.pos_rows, a.dev_params, a.y_next,
+                       a.y_gamma, a.y_dtype == DIMX_BF16 ? 1 : 0, a.qkv0_table, a.qkv0_out, a.qkv0_N, a.prompt, a.prompt_ld,
+                       a.prompt_max, a.prompt_len, a.prompt_div < 1 ? 1 : a.prompt_div, a.epoch_rw, filt.a, filt.b, filt.keep_out);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

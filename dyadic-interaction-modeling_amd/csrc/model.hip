@@ -696,10 +696,83 @@ static void set_attn_packed(AttnArgs& a, int dtype, const void* q, const void* k
     a.D = D;
 }
 
+// ------------------------------------------------------------------ sublayers of a transformer block
+// The four stacks (run_vq_blocks, run_xenc, dimx_decode_tf, gen_prefill) are sequences of these calls.  The buffers of a block, the
+// base of every stack's scratch struct: the f32 residual stream h [M, C]; in the operand type the LayerNorm output y, q / k / v(t),
+// the attention output o and the feed-forward hidden f; kw: the packed key-mask words of the prefill attention (AttnArgs.kwords)
+struct BlockBufs {
+    float* h;
+    void *y, *q, *k, *vt, *o, *f;
+    unsigned long long* kw = nullptr;   // the VQ stacks have none
+    size_t kw_cap = 0;
+};
+
+// out[M, ldo] = act(A . W^T + bias) (+ residual [M, ldo], f32) as plain rows of out_dtype
+static int linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, int out_dtype, void* out, int ldo, hipStream_t st,
+                  int act = ACT_NONE, const float* residual = nullptr) {
+    GemmArgs g;
+    gemm_lin(c, A, lda, L, M, g);
+    g.out_dtype = out_dtype; g.act = act;
+    g.residual = residual; g.ldr = residual ? ldo : 0;
+    gemm_set_plain_out(g, out, ldo);
+    return launch_gemm(g, st);
+}
+// h[M, ld] += A . W^T (+ bias), f32
+static int residual_linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, float* h, int ld, hipStream_t st) {
+    return linear(c, A, lda, L, M, DIMX_F32, h, ld, st, ACT_NONE, h);
+}
+
+// below this many rows a fused-MLP launch leaves most CUs idle (one block = 128 rows): the GEMM form's 64 x 64 tiles spread better
+constexpr int kFusedMlpMinRows = 8192;
+
+// h += f2(act(f1(LayerNorm(h)))); with mlp (the weights as mlp_fused.hip chunk images; the decoder stacks pass nullptr) and
+// kFusedMlpMinRows rows the whole sublayer is one launch
+static int ff_sublayer(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& f1,
+                       const Linear& f2, const void* mlp, int act, int M, int C, hipStream_t st) {
+    if (mlp && M >= kFusedMlpMinRows) return launch_mlp_fused(b.h, mlp, f2.bias, ln_g, ln_b, M, C, f1.N, act, st);
+    DIMX_TRY(launch_layernorm(c->at, b.h, b.y, ln_g, ln_b, M, C, st));
+    DIMX_TRY(linear(c, b.y, C, f1, M, c->at, b.f, f1.N, st, act));
+    return residual_linear(c, b.f, f1.N, f2, M, b.h, C, st);
+}
+
+// Self attention, first half: LayerNorm -> fused q/k/v projection into b.q / b.k / b.vt.  `a` leaves as the attention over them;
+// the caller adds scale and its stack's mask fields (lens, kmask / kmask_ld, causal) and hands it to attn_out.
+static int self_attn_qkv(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& qkv, int B,
+                         int T, int C, int heads, int D, AttnArgs& a, hipStream_t st) {
+    const bool rowv = qkv_row_v(c->at, D);
+    DIMX_TRY(launch_layernorm(c->at, b.h, b.y, ln_g, ln_b, B * T, C, st));
+    GemmArgs g;
+    gemm_lin(c, b.y, C, qkv, B * T, g);
+    g.out_dtype = c->at;
+    set_qkv_out(g, b.q, b.k, b.vt, T, heads, D, tpad(T), rowv);
+    DIMX_TRY(launch_gemm(g, st));
+    set_attn_packed(a, c->at, b.q, b.k, b.vt, b.o, B, heads, T, T, D, tpad(T), rowv);
+    return DIMX_OK;
+}
+
+// second half of both attentions: attention `a` (output b.o) -> h += o . Wout^T (+ bias)
+static int attn_out(const dimx_ctx* c, const BlockBufs& b, AttnArgs& a, const Linear& out, int C, hipStream_t st) {
+    a.kwords = b.kw; a.kwords_cap = b.kw_cap;
+    DIMX_TRY(launch_attention(a, st));
+    return residual_linear(c, b.o, a.H * a.D, out, a.B * a.Lq, b.h, C, st);
+}
+
+// Cross attention of the decoder stacks: LayerNorm -> q projection into b.q -> attention over the context K / V, which the caller
+// describes in `a` -> out-projection.  v_rows (gen_prefill, f32): V [B*H, Tp, 64] to transpose into the scratch a.vt before the attention.
+static int cross_attn_sublayer(const dimx_ctx* c, const BlockBufs& b, const XAttn& x, AttnArgs& a, const uint8_t* ctx_mask, int C,
+                               hipStream_t st, const float* v_rows = nullptr) {
+    const int M = a.B * a.Lq, Tp = tpad(a.Lk);
+    DIMX_TRY(launch_layernorm(c->at, b.h, b.y, x.ln_g, nullptr, M, C, st));
+    DIMX_TRY(linear(c, b.y, C, x.qkv, M, c->at, b.q, a.H * a.D, st));
+    if (v_rows) DIMX_TRY(launch_kv_rows_to_vt(v_rows, Tp, (float*)a.vt, Tp, a.B, a.Lk, a.H, st));
+    a.scale = 1.0f / sqrtf((float)a.D); a.kmask = ctx_mask; a.kmask_ld = a.Lk;
+    return attn_out(c, b, a, x.out, C, st);
+}
+
 // ------------------------------------------------------------------ VQ-VAE stacks
-struct VQScratch {
-    void *xa, *h1, *y, *q, *k, *vt, *o, *f;
-    float *conv, *h, *z;
+struct VQScratch : BlockBufs {
+    void *xa, *h1;
+    float *conv, *z;
     int32_t* idx_tmp;
 };
 
@@ -720,49 +793,17 @@ static void plan_vq(const dimx_ctx* c, const VQGeom& vg, Arena& ar, int B, int T
     s.idx_tmp = (int32_t*)ar.take(M * vg.fqn * 4);
 }
 
-// below this many rows a fused-MLP launch leaves most CUs idle (one block = 128 rows): the GEMM form's 64 x 64 tiles spread better
-constexpr int kFusedMlpMinRows = 8192;
-
 static int run_vq_blocks(const dimx_ctx* c, const VQGeom& vg, const VQBlock* blk, VQScratch& s, int B, int T,
                          const int32_t* lens, hipStream_t st) {
-    const int M = B * T, Hd = vg.hidden, heads = vg.heads, D = Hd / heads, Tp = tpad(T);
+    const int M = B * T, Hd = vg.hidden, heads = vg.heads, D = Hd / heads;
     const float scale = 1.0f / sqrtf((float)Hd);  // hidden^-0.5 (code/models/lib/base_models.py:116)
     for (int l = 0; l < vg.layers; ++l) {
         const VQBlock& b = blk[l];
-        GemmArgs g;
-        DIMX_TRY(launch_layernorm(c->at, s.h, s.y, b.ln1_g, b.ln1_b, M, Hd, st));
-        gemm_lin(c, s.y, Hd, b.qkv, M, g);
-        g.out_dtype = c->at;
-        const bool rowv = qkv_row_v(c->at, D);
-        set_qkv_out(g, s.q, s.k, s.vt, T, heads, D, Tp, rowv);
-        DIMX_TRY(launch_gemm(g, st));
         AttnArgs a;
-        set_attn_packed(a, c->at, s.q, s.k, s.vt, s.o, B, heads, T, T, D, Tp, rowv);
-        a.scale = scale;
-        a.lens = lens;
-        DIMX_TRY(launch_attention(a, st));
-        gemm_lin(c, s.o, Hd, b.out, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = Hd;
-        gemm_set_plain_out(g, s.h, Hd);
-        DIMX_TRY(launch_gemm(g, st));
-        if (b.mlp && M >= kFusedMlpMinRows) {   // the whole MLP sublayer in one launch (mlp_fused.hip)
-            DIMX_TRY(launch_mlp_fused(s.h, b.mlp, b.l2.bias, b.ln2_g, b.ln2_b, M, Hd, vg.inter, ACT_GELU_TANH, st));
-            continue;
-        }
-        DIMX_TRY(launch_layernorm(c->at, s.h, s.y, b.ln2_g, b.ln2_b, M, Hd, st));
-        gemm_lin(c, s.y, Hd, b.l1, M, g);
-        g.out_dtype = c->at;
-        g.act = ACT_GELU_TANH;
-        gemm_set_plain_out(g, s.f, vg.inter);
-        DIMX_TRY(launch_gemm(g, st));
-        gemm_lin(c, s.f, vg.inter, b.l2, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = Hd;
-        gemm_set_plain_out(g, s.h, Hd);
-        DIMX_TRY(launch_gemm(g, st));
+        DIMX_TRY(self_attn_qkv(c, s, b.ln1_g, b.ln1_b, b.qkv, B, T, Hd, heads, D, a, st));
+        a.scale = scale; a.lens = lens;
+        DIMX_TRY(attn_out(c, s, a, b.out, Hd, st));
+        DIMX_TRY(ff_sublayer(c, s, b.ln2_g, b.ln2_b, b.l1, b.l2, b.mlp, ACT_GELU_TANH, M, Hd, st));
     }
     return DIMX_OK;
 }
@@ -803,20 +844,12 @@ static int run_vq_encode(const dimx_ctx* c, int which, const float* x, const int
     const VQNet& v = c->vq[which];
     const int M = B * T, Hd = vg.hidden;
     DIMX_TRY(launch_cast_pad(c->at, x, vg.in_dim, nullptr, s.xa, vg.in_pad, M, vg.in_dim, st));
-    GemmArgs g;
-    gemm_lin(c, s.xa, vg.in_pad, v.vm, M, g);
-    g.out_dtype = c->at;
-    g.act = ACT_LEAKY;
-    gemm_set_plain_out(g, s.h1, Hd);
-    DIMX_TRY(launch_gemm(g, st));
+    DIMX_TRY(linear(c, s.xa, vg.in_pad, v.vm, M, c->at, s.h1, Hd, st, ACT_LEAKY));
     DIMX_TRY(run_vq_front(c, vg, s.h1, Hd, v.conv, v.le, v.pe_enc, pe_mode, row_off, s, B, T, lens, st));
     DIMX_TRY(run_vq_blocks(c, vg, v.enc, s, B, T, lens, st));
     // post projection consumes the f32 residual stream directly (no final norm in this stack)
     DIMX_TRY(launch_cast_pad(c->at, s.h, Hd, nullptr, s.y, Hd, M, Hd, st));
-    gemm_lin(c, s.y, Hd, v.post, M, g);
-    g.out_dtype = DIMX_F32;
-    gemm_set_plain_out(g, z, vg.out_dim);
-    DIMX_TRY(launch_gemm(g, st));
+    DIMX_TRY(linear(c, s.y, Hd, v.post, M, DIMX_F32, z, vg.out_dim, st));
     DIMX_TRY(launch_vq_argmin(z, M * vg.fqn, v.Et, v.ee, idx, nullptr, nullptr, st));
     return DIMX_OK;
 }
@@ -1061,23 +1094,17 @@ int dimx_missing_weights(dimx_handle h) {
 // ====================================================================== stages
 namespace dimx {
 
-struct EncScratch {
-    void *xa, *y, *q, *k, *vt, *o, *f;
-    float *h, *tmp;
-    unsigned long long* kw;  // packed key-mask words of the prefill attention (AttnArgs.kwords)
-    size_t kw_cap;
+struct EncScratch : BlockBufs {
+    void* xa;
+    float* tmp;
 };
 struct CtxPersist {
     void* ck[8];
     void* cv[8];
 };
-struct DecScratch {
-    void *y, *q, *k, *vt, *o, *f;
-    float* h;
+struct DecScratch : BlockBufs {
     int32_t *inp, *tgt;
     uint8_t* kvm;
-    unsigned long long* kw;  // packed key-mask words of the prefill attention (AttnArgs.kwords)
-    size_t kw_cap;
 };
 struct GenScratch {
     void* sk[8];
@@ -1176,13 +1203,9 @@ struct GenPrompt {
     const int32_t* len;  // [B] prompt lengths (clamped to [step0 + 1, Pmax] by the sampler) or nullptr = Pmax
     int step0;           // P0 - 1: positions 0 .. step0 - 1 are prefilled, the first decode step is step0
 };
-struct PrefillScratch {
-    void *y, *q, *k, *vt, *o, *f;
-    float* h;
+struct PrefillScratch : BlockBufs {
     float* cvt;          // f32 mode: one layer's context V transposed to [B,H,64,Tp] (the f32 prefill attention reads V^T)
     int32_t* inp;
-    unsigned long long* kw;
-    size_t kw_cap;
 };
 // The scratch is sized for the WHOLE batch (B clips x n0 positions), not for a chunk of clips, and lies behind the generation
 // scratch: the prefill writes the K/V cache, which must outlive it, and nothing else of the generation scratch.
@@ -1305,7 +1328,7 @@ static size_t workspace_bytes_prompt(const dimx_ctx* c, int B, int T, int S, int
 // x-transformers encoder stack (ContinuousTransformerWrapper, return_embeddings=True)
 static int run_xenc(const dimx_ctx* c, const EncGeom& eg, const XEnc& e, const void* x_in, int ld_in, EncScratch& s,
                     int B, int T, const uint8_t* mask, int out_dtype, void* out, hipStream_t st) {
-    const int M = B * T, dim = eg.dim, heads = eg.heads, D = eg.dim_head, inner = heads * D, Tp = tpad(T);
+    const int M = B * T, dim = eg.dim, heads = eg.heads, D = eg.dim_head;
     GemmArgs g;
     gemm_lin(c, x_in, ld_in, e.proj_in, M, g);
     g.out_dtype = DIMX_F32;
@@ -1317,43 +1340,11 @@ static int run_xenc(const dimx_ctx* c, const EncGeom& eg, const XEnc& e, const v
     gemm_set_plain_out(g, s.h, dim);
     DIMX_TRY(launch_gemm(g, st));
     for (int l = 0; l < eg.depth; ++l) {
-        DIMX_TRY(launch_layernorm(c->at, s.h, s.y, e.attn[l].ln_g, nullptr, M, dim, st));
-        gemm_lin(c, s.y, dim, e.attn[l].qkv, M, g);
-        g.out_dtype = c->at;
-        const bool rowv = qkv_row_v(c->at, D);
-        set_qkv_out(g, s.q, s.k, s.vt, T, heads, D, Tp, rowv);
-        DIMX_TRY(launch_gemm(g, st));
         AttnArgs a;
-        set_attn_packed(a, c->at, s.q, s.k, s.vt, s.o, B, heads, T, T, D, Tp, rowv);
-        a.scale = 1.0f / sqrtf((float)D);
-        a.causal = eg.causal;
-        a.kmask = mask;
-        a.kmask_ld = T;
-        a.kwords = s.kw;
-        a.kwords_cap = s.kw_cap;
-        DIMX_TRY(launch_attention(a, st));
-        gemm_lin(c, s.o, inner, e.attn[l].out, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = dim;
-        gemm_set_plain_out(g, s.h, dim);
-        DIMX_TRY(launch_gemm(g, st));
-        if (e.ff[l].mlp && M >= kFusedMlpMinRows) {
-            DIMX_TRY(launch_mlp_fused(s.h, e.ff[l].mlp, e.ff[l].f2.bias, e.ff[l].ln_g, nullptr, M, dim, dim * eg.ff_mult, ACT_GELU_ERF, st));
-            continue;
-        }
-        DIMX_TRY(launch_layernorm(c->at, s.h, s.y, e.ff[l].ln_g, nullptr, M, dim, st));
-        gemm_lin(c, s.y, dim, e.ff[l].f1, M, g);
-        g.out_dtype = c->at;
-        g.act = ACT_GELU_ERF;
-        gemm_set_plain_out(g, s.f, dim * eg.ff_mult);
-        DIMX_TRY(launch_gemm(g, st));
-        gemm_lin(c, s.f, dim * eg.ff_mult, e.ff[l].f2, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = dim;
-        gemm_set_plain_out(g, s.h, dim);
-        DIMX_TRY(launch_gemm(g, st));
+        DIMX_TRY(self_attn_qkv(c, s, e.attn[l].ln_g, nullptr, e.attn[l].qkv, B, T, dim, heads, D, a, st));
+        a.scale = 1.0f / sqrtf((float)D); a.causal = eg.causal; a.kmask = mask; a.kmask_ld = T;
+        DIMX_TRY(attn_out(c, s, a, e.attn[l].out, dim, st));
+        DIMX_TRY(ff_sublayer(c, s, e.ff[l].ln_g, nullptr, e.ff[l].f1, e.ff[l].f2, e.ff[l].mlp, ACT_GELU_ERF, M, dim, st));
     }
     DIMX_TRY(launch_layernorm(out_dtype, s.h, out, e.final_g, nullptr, M, dim, st));
     return DIMX_OK;
@@ -1552,18 +1543,11 @@ static int vq_decode_impl(dimx_handle h, int which, const int32_t* idx, const fl
             DIMX_TRY(launch_gather_rows(h->at, v.E, zd, vg.n_embed, idx + r0, s.xa, zd, M, zd, gs));
         else
             DIMX_TRY(launch_cast_pad(h->at, z + r0 * zd, zd, nullptr, s.xa, zd, M, zd, gs));
-        GemmArgs g;
-        gemm_lin(h, s.xa, zd, v.pre, M, g);
-        g.out_dtype = h->at;
-        gemm_set_plain_out(g, s.h1, Hd);
-        DIMX_TRY(launch_gemm(g, gs));
+        DIMX_TRY(linear(h, s.xa, zd, v.pre, M, h->at, s.h1, Hd, gs));
         DIMX_TRY(run_vq_front(h, vg, s.h1, Hd, v.dconv, v.dle, v.pe_dec, 1, batch_row_offset + b0, s, nb, L, nullptr, gs, rows_per_clip));
         DIMX_TRY(run_vq_blocks(h, vg, v.dec, s, nb, L, nullptr, gs));
         DIMX_TRY(launch_cast_pad(h->at, s.h, Hd, nullptr, s.y, Hd, M, Hd, gs));
-        gemm_lin(h, s.y, Hd, v.rev, M, g);
-        g.out_dtype = DIMX_F32;
-        gemm_set_plain_out(g, out + r0 * vg.in_dim, vg.in_dim);
-        DIMX_TRY(launch_gemm(g, gs));
+        DIMX_TRY(linear(h, s.y, Hd, v.rev, M, DIMX_F32, out + r0 * vg.in_dim, vg.in_dim, gs));
     }
     return DIMX_OK;
     }();
@@ -1859,74 +1843,23 @@ int dimx_decode_tf(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, c
     DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "decode_tf: workspace overflow");
     const DecGeom& dg = h->decg;
     const int n = T - 1, M = B * n, DD = dg.dim, heads = dg.heads, D = dg.dim_head;
-    const int inner = heads * D, np = tpad(n), Tp = tpad(T), V = dg.num_tokens;
+    const int Tp = tpad(T), V = dg.num_tokens;
     DIMX_TRY(launch_shift_tokens(z_l, s.inp, s.tgt, B, T, st));
     DIMX_TRY(launch_gather_rows(DIMX_F32, h->dec.tok_emb, DD, V, s.inp, s.h, DD, M, DD, st));
     if (dg.abs_pos) DIMX_TRY(launch_add_pos_rows(s.h, h->dec.pos_emb, M, n, DD, 1.0f / sqrtf((float)DD), st));
-    const float scale = 1.0f / sqrtf((float)D);
     for (int l = 0; l < dg.depth; ++l) {
-        GemmArgs g;
         AttnArgs a;
         // causal self attention (+ AutoregressiveWrapper's random key mask)
-        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.self_[l].ln_g, nullptr, M, DD, st));
-        gemm_lin(h, s.y, DD, h->dec.self_[l].qkv, M, g);
-        g.out_dtype = h->at;
-        const bool rowv = qkv_row_v(h->at, D);
-        set_qkv_out(g, s.q, s.k, s.vt, n, heads, D, np, rowv);
-        DIMX_TRY(launch_gemm(g, st));
-        set_attn_packed(a, h->at, s.q, s.k, s.vt, s.o, B, heads, n, n, D, np, rowv);
-        a.scale = scale;
-        a.causal = 1;
-        a.kmask = kv_mask;
-        a.kmask_ld = n;
-        a.kwords = s.kw;
-        a.kwords_cap = s.kw_cap;
-        DIMX_TRY(launch_attention(a, st));
-        gemm_lin(h, s.o, inner, h->dec.self_[l].out, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = DD;
-        gemm_set_plain_out(g, s.h, DD);
-        DIMX_TRY(launch_gemm(g, st));
-        // cross attention over the speaker context
-        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.cross[l].ln_g, nullptr, M, DD, st));
-        gemm_lin(h, s.y, DD, h->dec.cross[l].qkv, M, g);
-        g.out_dtype = h->at;
-        gemm_set_plain_out(g, s.q, inner);
-        DIMX_TRY(launch_gemm(g, st));
+        DIMX_TRY(self_attn_qkv(h, s, h->dec.self_[l].ln_g, nullptr, h->dec.self_[l].qkv, B, n, DD, heads, D, a, st));
+        a.scale = 1.0f / sqrtf((float)D); a.causal = 1; a.kmask = kv_mask; a.kmask_ld = n;
+        DIMX_TRY(attn_out(h, s, a, h->dec.self_[l].out, DD, st));
+        // cross attention over the speaker context: K row-major [B,T,inner], V transposed [B,H,64,Tp] (project_cross_kv)
         set_attn_packed(a, h->at, s.q, cp.ck[l], cp.cv[l], s.o, B, heads, n, T, D, Tp);
-        a.scale = scale;
-        a.kmask = ctx_mask;
-        a.kmask_ld = T;
-        a.kwords = s.kw;
-        a.kwords_cap = s.kw_cap;
-        DIMX_TRY(launch_attention(a, st));
-        gemm_lin(h, s.o, inner, h->dec.cross[l].out, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = DD;
-        gemm_set_plain_out(g, s.h, DD);
-        DIMX_TRY(launch_gemm(g, st));
-        // feed forward
-        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.ff[l].ln_g, nullptr, M, DD, st));
-        gemm_lin(h, s.y, DD, h->dec.ff[l].f1, M, g);
-        g.out_dtype = h->at;
-        g.act = ACT_GELU_ERF;
-        gemm_set_plain_out(g, s.f, DD * dg.ff_mult);
-        DIMX_TRY(launch_gemm(g, st));
-        gemm_lin(h, s.f, DD * dg.ff_mult, h->dec.ff[l].f2, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = DD;
-        gemm_set_plain_out(g, s.h, DD);
-        DIMX_TRY(launch_gemm(g, st));
+        DIMX_TRY(cross_attn_sublayer(h, s, h->dec.cross[l], a, ctx_mask, DD, st));
+        DIMX_TRY(ff_sublayer(h, s, h->dec.ff[l].ln_g, nullptr, h->dec.ff[l].f1, h->dec.ff[l].f2, nullptr, ACT_GELU_ERF, M, DD, st));
     }
     DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.final_g, nullptr, M, DD, st));
-    GemmArgs g;
-    gemm_lin(h, s.y, DD, h->dec.logits, M, g);
-    g.out_dtype = DIMX_F32;
-    gemm_set_plain_out(g, logits, V);
-    DIMX_TRY(launch_gemm(g, st));
+    DIMX_TRY(linear(h, s.y, DD, h->dec.logits, M, DIMX_F32, logits, V, st));
     if (row_loss || argmax_tok) DIMX_TRY(launch_ce_argmax(logits, s.tgt, row_loss, argmax_tok, M, V, st));
     return DIMX_OK;
 }
@@ -1934,6 +1867,8 @@ int dimx_decode_tf(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, c
 }  // extern "C"
 
 namespace dimx {
+
+static void chain_desc(ChainGemmDesc& d, const Linear& L) { d.W = L.w; d.N = L.N; d.K = L.K; d.ldw = L.Kp; }
 
 // The chain kernels run when: bf16 operands, one sample per clip, a single clip group, <= 256 rows, a 256-CU device on
 // which the placement probe passed, and every launch site's LDS plan fits.
@@ -1946,11 +1881,11 @@ static bool gen_use_chain(dimx_handle h, int B, int S, int grp) {
     c.C = dg.dim;
     const XAttn& sa = h->dec.self_[0];
     const XAttn& ca = h->dec.cross[0];
-    c.g1.W = sa.out.w; c.g1.N = sa.out.N; c.g1.K = sa.out.K; c.g1.ldw = sa.out.Kp;
+    chain_desc(c.g1, sa.out);
     c.lda1 = dg.heads * dg.dim_head;
-    c.g2.W = ca.qkv.w; c.g2.N = ca.qkv.N; c.g2.K = ca.qkv.K; c.g2.ldw = ca.qkv.Kp;
+    chain_desc(c.g2, ca.qkv);
     if (!chain_supported(c, h->cu_count)) return false;
-    c.g2.W = h->dec.logits.w; c.g2.N = h->dec.logits.N; c.g2.K = h->dec.logits.K; c.g2.ldw = h->dec.logits.Kp;
+    chain_desc(c.g2, h->dec.logits);
     c.g1.W = nullptr;
     return chain_supported(c, h->cu_count) && 3 * dg.depth + 1 <= kChainSites;
 }
@@ -2021,12 +1956,30 @@ static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream
     return DIMX_OK;
 }
 
-// one decoder step for the clip group [row0, row0 + B) of a batch of Btot clips:
+// what every gen_step of one generate call shares (built once in generate_impl)
+struct GenCall {
+    const CtxPersist& cp;
+    const GenScratch& s;
+    const GenPrompt& pr;
+    const uint8_t* ctx_mask;
+    int Btot, T, S, top_k;   // sequences of the batch, frames, samples per clip
+    float temperature;
+    const float* noise;
+    uint64_t seed;
+    int32_t* tokens;
+    float* logits_out;
+    const float* qkv0;   // the first layer's q/k/v table or nullptr
+};
+
+// one decoder step for the clip group `grp` = rows [row0, row0 + B) of a batch of gc.Btot sequences:
 // x = emb(token) -> 4 x {self, cross, ff} -> logits -> sample -> step += 1
-static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, const GenPrompt& pr,
-                    const uint8_t* ctx_mask, int row0, int B, int Btot, int grp, int T, float temperature, int top_k,
-                    const float* noise, uint64_t seed, int32_t* tokens, float* logits_out, hipStream_t st,
-                    bool embed_only = false, int S = 1, const float* qkv0 = nullptr) {
+static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, hipStream_t st, bool embed_only) {
+    const GenScratch& s0 = gc.s;
+    const GenPrompt& pr = gc.pr;
+    const int T = gc.T, S = gc.S;
+    const uint8_t* ctx_mask = gc.ctx_mask;   // advanced to this group's rows below, like tokens and logits_out
+    int32_t* tokens = gc.tokens;
+    float* logits_out = gc.logits_out;
     const DecGeom& dg = h->decg;
     const int DD = dg.dim, heads = dg.heads, D = dg.dim_head, inner = heads * D;
     const int V = dg.num_tokens, n = gen_steps(h, T), Tp = tpad(T);
@@ -2056,12 +2009,12 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
     tokens += (size_t)row0 * n;
     if (logits_out) logits_out += (size_t)row0 * n * V;
     // round 4: the sampler that writes the next step's embedding row also writes the first layer's pre-norm of it, so a step
-    // starts with y = LayerNorm(x) in place.  With the first layer's q/k/v table (qkv0) both write the token's table row into slab 0
+    // starts with y = LayerNorm(x) in place.  With the first layer's q/k/v table (gc.qkv0) both write the token's table row into slab 0
     // of s.qkv instead, and layer 0 starts at its attention.
     if (embed_only) {  // step 0 input = embedding of the start token (later steps: fused into the sampler)
         DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, start, tokens, n, s.step, s.x, B, S, st, pos, pos_scale, pr.ld, pr.step0));
-        if (qkv0)   // the first layer's q/k/v of the start token: a table row into slab 0 (nothing reads y before the layer rewrites it)
-            DIMX_TRY(launch_gather_start_rows(qkv0, 3 * inner, V, start, S, s.qkv, B, st, pr.ld));
+        if (gc.qkv0)   // the first layer's q/k/v of the start token: a table row into slab 0 (nothing reads y before the layer rewrites it)
+            DIMX_TRY(launch_gather_start_rows(gc.qkv0, 3 * inner, V, start, S, s.qkv, B, st, pr.ld));
         else
             DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
         return DIMX_OK;
@@ -2085,10 +2038,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
             c.colsum2 = colsum2;
         }
         if (W1) {
-            c.g1.W = W1->w;
-            c.g1.N = W1->N;
-            c.g1.K = W1->K;
-            c.g1.ldw = W1->Kp;
+            chain_desc(c.g1, *W1);
             c.A1 = A1;
             c.lda1 = lda1;
             c.xr = s.xr;
@@ -2101,10 +2051,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         c.y = s.y;
         c.gamma = gamma;
         if (W2) {
-            c.g2.W = W2->w;
-            c.g2.N = W2->N;
-            c.g2.K = W2->K;
-            c.g2.ldw = W2->Kp;
+            chain_desc(c.g2, *W2);
             c.out2 = out2;
             c.ld_out2 = ld_out2;
         }
@@ -2127,9 +2074,9 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         lc.C = DD;
         lc.sa = sa;
         lc.ca = ca;
-        lc.g_so.W = so.w; lc.g_so.N = so.N; lc.g_so.K = so.K; lc.g_so.ldw = so.Kp;
-        lc.g_cq.W = cq.w; lc.g_cq.N = cq.N; lc.g_cq.K = cq.K; lc.g_cq.ldw = cq.Kp;
-        lc.g_co.W = co.w; lc.g_co.N = co.N; lc.g_co.K = co.K; lc.g_co.ldw = co.Kp;
+        chain_desc(lc.g_so, so);
+        chain_desc(lc.g_cq, cq);
+        chain_desc(lc.g_co, co);
         lc.o = s.o;
         lc.ld_o = inner;
         lc.x = s.x;
@@ -2154,7 +2101,7 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         int ns = 0;
         if (l > 0)
             DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.self_[l].ln_g, B, DD, st));
-        if (l == 0 && qkv0)
+        if (l == 0 && gc.qkv0)
             ns = 1;   // slab 0 already holds this token's q/k/v (the sampler / the start-token step copied the table row)
         else
             DIMX_TRY(slab_gemm(s.y, DD, h->dec.self_[l].qkv, s.qkv, s0.st_qkv, &ns));
@@ -2186,8 +2133,8 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         ca.q_f32 = 1;
         ca.nslab = 1;
         ca.slab_stride = s0.st_qc;
-        ca.kcache = (unsigned char*)cp.ck[l] + (size_t)clip0 * heads * Tp * 64 * es;
-        ca.vcache = (unsigned char*)cp.cv[l] + (size_t)clip0 * heads * Tp * 64 * es;
+        ca.kcache = (unsigned char*)gc.cp.ck[l] + (size_t)clip0 * heads * Tp * 64 * es;
+        ca.vcache = (unsigned char*)gc.cp.cv[l] + (size_t)clip0 * heads * Tp * 64 * es;
         ca.Tmax = Tp;
         ca.out = s.o;
         ca.o_ld = inner;
@@ -2279,12 +2226,17 @@ static int gen_step(dimx_handle h, const CtxPersist& cp, const GenScratch& s0, c
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.final_g, B, DD, st));
         DIMX_TRY(slab_gemm(s.y, DD, h->dec.logits, s.logits, s0.st_lg, &nlg));
     }
-    DIMX_TRY(launch_sample(s.logits, V, B, top_k, temperature, noise, seed, s.step, 0, tokens, n, 1, nlg, s0.st_lg,
-                           logits_out, n, row0, Btot, h->dec.tok_emb, DD, s.x, s.step, (unsigned*)(s.step + 8), st, pos,
-                           pos_scale, n, s.step + 2, qkv0 ? nullptr : s.y, qkv0 ? nullptr : h->dec.self_[0].ln_g, h->at, qkv0,
-                           s.qkv, 3 * inner, forced, pr.ld, pr.Pmax, forced_len, S, s.step + 9,
-                           SampleFilter{h->filter_kind, 0.f, 0.f, nullptr}));   // a / b: words 11 / 12 of the parameter block
-    return DIMX_OK;
+    SampleArgs sm;
+    sm.logits = s.logits; sm.ld_logits = V; sm.R = B; sm.nslab = nlg; sm.slab_stride = s0.st_lg; sm.row0 = row0; sm.rows_total = gc.Btot;
+    sm.top_k = gc.top_k; sm.noise = gc.noise; sm.filt.kind = h->filter_kind;
+    sm.temperature = gc.temperature; sm.seed = gc.seed;   // read from the parameter block (dev_params) instead, like filt.a / b
+    sm.step_dev = s.step; sm.step_rw = s.step; sm.dev_params = s.step + 2; sm.done_ctr = (unsigned*)(s.step + 8); sm.epoch_rw = s.step + 9;
+    sm.tokens = tokens; sm.tok_ld = n; sm.tok_col_from_step = 1; sm.logits_out = logits_out; sm.logits_out_ld = n;
+    sm.emb_table = h->dec.tok_emb; sm.emb_C = DD; sm.x_next = s.x; sm.pos_table = pos; sm.pos_scale = pos_scale; sm.pos_rows = n;
+    sm.y_next = gc.qkv0 ? nullptr : s.y; sm.y_gamma = gc.qkv0 ? nullptr : h->dec.self_[0].ln_g; sm.y_dtype = h->at;
+    sm.qkv0_table = gc.qkv0; sm.qkv0_out = s.qkv; sm.qkv0_N = 3 * inner;
+    sm.prompt = forced; sm.prompt_ld = pr.ld; sm.prompt_max = pr.Pmax; sm.prompt_len = forced_len; sm.prompt_div = S;
+    return launch_sample(sm, st);
 }
 
 // Prefill of a prompted generation: the teacher-forced decoder stack of dimx_decode_tf over the positions 0 .. n0 - 1 of every
@@ -2297,82 +2249,27 @@ static int gen_prefill(dimx_handle h, const CtxPersist& cp, const GenScratch& gs
                        const uint8_t* ctx_mask, int B, int T, int S, int32_t* tokens, hipStream_t st) {
     const DecGeom& dg = h->decg;
     const int n0 = pr.step0, M = B * n0, DD = dg.dim, heads = dg.heads, D = dg.dim_head;
-    const int inner = heads * D, np = tpad(n0), Tp = tpad(T), V = dg.num_tokens;
+    const int np = tpad(n0), Tp = tpad(T), V = dg.num_tokens;
     DIMX_TRY(launch_prompt_rows(pr.tok, pr.ld, B, n0, V, S, s.inp, tokens, gen_steps(h, T), st));
     DIMX_TRY(launch_gather_rows(DIMX_F32, h->dec.tok_emb, DD, V, s.inp, s.h, DD, M, DD, st));
-    const float scale = 1.0f / sqrtf((float)D);
     const bool rowv = qkv_row_v(h->at, D);
     for (int l = 0; l < dg.depth; ++l) {
-        GemmArgs g;
         AttnArgs a;
-        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.self_[l].ln_g, nullptr, M, DD, st));
-        gemm_lin(h, s.y, DD, h->dec.self_[l].qkv, M, g);
-        g.out_dtype = h->at;
-        set_qkv_out(g, s.q, s.k, s.vt, n0, heads, D, np, rowv);
-        DIMX_TRY(launch_gemm(g, st));
+        DIMX_TRY(self_attn_qkv(h, s, h->dec.self_[l].ln_g, nullptr, h->dec.self_[l].qkv, B, n0, DD, heads, D, a, st));
         DIMX_TRY(launch_kv_rows_to_cache(h->at, s.k, gs.sk[l], B, n0, heads, T, S, st));
         if (rowv)
             DIMX_TRY(launch_kv_rows_to_cache(h->at, s.vt, gs.sv[l], B, n0, heads, T, S, st));
         else
             DIMX_TRY(launch_kv_vt_to_cache((const float*)s.vt, np, (float*)gs.sv[l], B, n0, heads, T, S, st));
         if (l == dg.depth - 1) break;
-        set_attn_packed(a, h->at, s.q, s.k, s.vt, s.o, B, heads, n0, n0, D, np, rowv);
-        a.scale = scale;
-        a.causal = 1;
-        a.kwords = s.kw;
-        a.kwords_cap = s.kw_cap;
-        DIMX_TRY(launch_attention(a, st));
-        gemm_lin(h, s.o, inner, h->dec.self_[l].out, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = DD;
-        gemm_set_plain_out(g, s.h, DD);
-        DIMX_TRY(launch_gemm(g, st));
-        // cross attention over the context K / V of the generation layout
-        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.cross[l].ln_g, nullptr, M, DD, st));
-        gemm_lin(h, s.y, DD, h->dec.cross[l].qkv, M, g);
-        g.out_dtype = h->at;
-        gemm_set_plain_out(g, s.q, inner);
-        DIMX_TRY(launch_gemm(g, st));
-        const void* cv = cp.cv[l];
-        if (!rowv) {
-            DIMX_TRY(launch_kv_rows_to_vt((const float*)cp.cv[l], Tp, s.cvt, Tp, B, T, heads, st));
-            cv = s.cvt;
-        }
-        set_attn_packed(a, h->at, s.q, cp.ck[l], cv, s.o, B, heads, n0, T, D, Tp, rowv);
-        a.k_sb = (long)heads * Tp * D;
-        a.k_sh = (long)Tp * D;
-        a.k_st = D;
-        if (rowv) {
-            a.v_sb = (long)heads * Tp * D;
-            a.v_sh = (long)Tp * D;
-            a.v_st = D;
-        }
-        a.scale = scale;
-        a.kmask = ctx_mask;
-        a.kmask_ld = T;
-        a.kwords = s.kw;
-        a.kwords_cap = s.kw_cap;
-        DIMX_TRY(launch_attention(a, st));
-        gemm_lin(h, s.o, inner, h->dec.cross[l].out, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = DD;
-        gemm_set_plain_out(g, s.h, DD);
-        DIMX_TRY(launch_gemm(g, st));
-        // feed forward
-        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.ff[l].ln_g, nullptr, M, DD, st));
-        gemm_lin(h, s.y, DD, h->dec.ff[l].f1, M, g);
-        g.out_dtype = h->at;
-        g.act = ACT_GELU_ERF;
-        gemm_set_plain_out(g, s.f, DD * dg.ff_mult);
-        DIMX_TRY(launch_gemm(g, st));
-        gemm_lin(h, s.f, DD * dg.ff_mult, h->dec.ff[l].f2, M, g);
-        g.out_dtype = DIMX_F32;
-        g.residual = s.h;
-        g.ldr = DD;
-        gemm_set_plain_out(g, s.h, DD);
-        DIMX_TRY(launch_gemm(g, st));
+        a.scale = 1.0f / sqrtf((float)D); a.causal = 1;
+        DIMX_TRY(attn_out(h, s, a, h->dec.self_[l].out, DD, st));
+        // cross attention over the context K / V of the generation layout [B,H,Tp,64]; the f32 attention reads V^T from s.cvt
+        set_attn_packed(a, h->at, s.q, cp.ck[l], rowv ? cp.cv[l] : s.cvt, s.o, B, heads, n0, T, D, Tp, rowv);
+        a.k_sb = (long)heads * Tp * D; a.k_sh = (long)Tp * D; a.k_st = D;
+        if (rowv) { a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_st = D; }
+        DIMX_TRY(cross_attn_sublayer(h, s, h->dec.cross[l], a, ctx_mask, DD, st, rowv ? nullptr : (const float*)cp.cv[l]));
+        DIMX_TRY(ff_sublayer(h, s, h->dec.ff[l].ln_g, nullptr, h->dec.ff[l].f1, h->dec.ff[l].f2, nullptr, ACT_GELU_ERF, M, DD, st));
     }
     return DIMX_OK;
 }
@@ -2460,14 +2357,11 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
             DIMX_HIP(hipStreamWaitEvent(gs[g], h->ev_fork, 0));
         }
     }
-    for (int g = 0; g < G; ++g)
-        DIMX_TRY(gen_step(h, cp, s, pr, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k, exp_noise,
-                          seed, tokens, logits_out, gs[g], true, S, qkv0));
+    const GenCall gc{cp, s, pr, ctx_mask, R, T, S, top_k, temperature, exp_noise, seed, tokens, logits_out, qkv0};
+    for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, gs[g], true));
     if (!h->use_graph) {
         for (int t = 0; t < nrun; ++t)
-            for (int g = 0; g < G; ++g)
-                DIMX_TRY(gen_step(h, cp, s, pr, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
-                                  exp_noise, seed, tokens, logits_out, gs[g], false, S, qkv0));
+            for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, gs[g], false));
     } else {
         // greedy vs sampling is decided from the device-side parameters; only shapes and pointers key the graph.  The prompt's
         // pointers, row stride and width are kernel arguments of the sampler; P0 is not (the counters' start value and the
@@ -2499,8 +2393,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
                     DIMX_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
                     int rc = DIMX_OK;
                     for (int r = 0; r < reps && rc == DIMX_OK; ++r)
-                        rc = gen_step(h, cp, s, pr, ctx_mask, lo[g], lo[g + 1] - lo[g], R, g, T, temperature, top_k,
-                                      exp_noise, seed, tokens, logits_out, h->cap_stream, false, S, qkv0);
+                        rc = gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, h->cap_stream, false);
                     const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
                     if (rc != DIMX_OK) {
                         if (graph) (void)hipGraphDestroy(graph);
@@ -2540,6 +2433,53 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
     return DIMX_OK;
 }
 
+// DIMX_LAYER_PROF=1 (tuning): the phase stamps of the LAST step's layer launches (100 MHz wall clock), mean / max over blocks
+static int print_layer_prof(dimx_handle h) {
+    DIMX_HIP(hipEventSynchronize(h->chain_err_ev));
+    static const char* names[13] = {"start", "self attention done", "barrier 1", "rows + W1 landed", "out-proj stored", "barrier 2",
+                                    "y rows + W2 landed", "cross-q stored", "barrier 3", "cross attention done", "barrier 4",
+                                    "rows + W3 landed", "out-proj stored"};
+    std::vector<unsigned long long> hp((size_t)8 * 256 * 16);
+    DIMX_HIP(hipMemcpy(hp.data(), h->layer_prof_dev, hp.size() * 8, hipMemcpyDeviceToHost));
+    for (int l = 0; l < h->decg.depth; ++l) {
+        const unsigned long long* p = hp.data() + (size_t)l * 256 * 16;
+        unsigned long long t0 = ~0ull;
+        for (int b = 0; b < 256; ++b)
+            if (p[b * 16] && p[b * 16] < t0) t0 = p[b * 16];
+        if (t0 == ~0ull) continue;
+        fprintf(stderr, "dimx layer-kernel stamps, layer %d (us after the first block's start; mean / max over blocks)\n", l);
+        double prev = 0;
+        for (int i = 0; i < 13; ++i) {
+            double sum = 0, mx = 0;
+            int n = 0;
+            for (int b = 0; b < 256; ++b)
+                if (p[b * 16 + i]) {
+                    const double v = (double)(p[b * 16 + i] - t0) / 100.0;
+                    sum += v;
+                    mx = v > mx ? v : mx;
+                    ++n;
+                }
+            if (!n) continue;
+            fprintf(stderr, "  %-24s %7.2f / %7.2f  (+%.2f)\n", names[i], sum / n, mx, sum / n - prev);
+            prev = sum / n;
+        }
+    }
+    return DIMX_OK;
+}
+
+// Waits for the generation that ran chain kernels and returns its flag word (or a negative DIMX_ERR_*).  Non-zero flags are
+// cleared on both sides, the step graph is dropped and the fault is counted: the caller regenerates the batch.
+static int take_chain_flags(dimx_handle h, void* stream) {
+    DIMX_HIP(hipEventSynchronize(h->chain_err_ev));
+    const unsigned e = *h->chain_err_host;
+    if (!e) return 0;
+    *h->chain_err_host = 0;
+    DIMX_HIP(hipMemsetAsync(h->chain_err_dev, 0, 64, (hipStream_t)stream));
+    h->graph_valid = false;
+    ++h->chain_faults;
+    return (int)e;
+}
+
 // The XCD-local chain kernels need their 256 blocks co-resident, one per CU, on the XCD whose rows they own; another
 // process, handle or stream on the same GPU can break that.  They detect it (claim stamps, bounded barriers) but cannot
 // repair it, so the call that used them checks their flags before it returns: it waits for its own generation (the caller
@@ -2549,48 +2489,17 @@ static int generate_checked(dimx_handle h, const dimx::GenPrompt& pr, const uint
                             float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out,
                             void* ws, size_t ws_bytes, void* stream) {
     bool chain_used = false;
-    DIMX_TRY(generate_impl(h, pr, false, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
-                           ws_bytes, stream, &chain_used));
+    auto run = [&](bool keep_prefill) {
+        return generate_impl(h, pr, keep_prefill, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
+                             ws_bytes, stream, &chain_used);
+    };
+    DIMX_TRY(run(false));
     if (h->chain_fault_inject > 0) --h->chain_fault_inject;
     if (!chain_used) return DIMX_OK;
-    DIMX_HIP(hipEventSynchronize(h->chain_err_ev));
-    if (h->layer_prof_dev) {  // tuning: the phase stamps of the LAST step's layer launches (100 MHz wall clock), mean / max over blocks
-        static const char* names[13] = {"start", "self attention done", "barrier 1", "rows + W1 landed", "out-proj stored", "barrier 2",
-                                        "y rows + W2 landed", "cross-q stored", "barrier 3", "cross attention done", "barrier 4",
-                                        "rows + W3 landed", "out-proj stored"};
-        std::vector<unsigned long long> hp((size_t)8 * 256 * 16);
-        DIMX_HIP(hipMemcpy(hp.data(), h->layer_prof_dev, hp.size() * 8, hipMemcpyDeviceToHost));
-        for (int l = 0; l < h->decg.depth; ++l) {
-            const unsigned long long* p = hp.data() + (size_t)l * 256 * 16;
-            unsigned long long t0 = ~0ull;
-            for (int b = 0; b < 256; ++b)
-                if (p[b * 16] && p[b * 16] < t0) t0 = p[b * 16];
-            if (t0 == ~0ull) continue;
-            fprintf(stderr, "dimx layer-kernel stamps, layer %d (us after the first block's start; mean / max over blocks)\n", l);
-            double prev = 0;
-            for (int i = 0; i < 13; ++i) {
-                double sum = 0, mx = 0;
-                int n = 0;
-                for (int b = 0; b < 256; ++b)
-                    if (p[b * 16 + i]) {
-                        const double v = (double)(p[b * 16 + i] - t0) / 100.0;
-                        sum += v;
-                        mx = v > mx ? v : mx;
-                        ++n;
-                    }
-                if (!n) continue;
-                fprintf(stderr, "  %-24s %7.2f / %7.2f  (+%.2f)\n", names[i], sum / n, mx, sum / n - prev);
-                prev = sum / n;
-            }
-        }
-    }
-    const unsigned e = *h->chain_err_host;
-    if (!e) return DIMX_OK;
-    *h->chain_err_host = 0;
-    DIMX_HIP(hipMemsetAsync(h->chain_err_dev, 0, 64, (hipStream_t)stream));
-    h->graph_valid = false;
-    ++h->chain_faults;
-    if (e & 3u) {
+    if (h->layer_prof_dev) DIMX_TRY(print_layer_prof(h));
+    const int e = take_chain_flags(h, stream);
+    if (e <= 0) return e;
+    if (e & 3) {
         h->use_chain = 0;
         fprintf(stderr, "dimx: the XCD-local chain kernels reported %s%s; this batch is regenerated on the one-kernel-per-op "
                         "step and the chain path stays off for this handle (DIMX_NO_CHAIN=1 avoids it from the start)\n",
@@ -2603,23 +2512,16 @@ static int generate_checked(dimx_handle h, const dimx::GenPrompt& pr, const uint
         fprintf(stderr, "dimx: a residual row's mean exceeds 8 standard deviations; this batch is regenerated with the row-phase "
                         "LayerNorm and the deferred form stays off for this handle\n");
     }
-    DIMX_TRY(generate_impl(h, pr, true, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
-                           ws_bytes, stream, &chain_used));
+    DIMX_TRY(run(true));
     if (!chain_used) return DIMX_OK;
     // the regeneration may still have run chain kernels (the bit-2 case keeps them on): it answers for its own flags too
     //  -- a second fault takes the chain path off and regenerates once more on the one-kernel-per-op step
-    DIMX_HIP(hipEventSynchronize(h->chain_err_ev));
-    const unsigned e2 = *h->chain_err_host;
-    if (!e2) return DIMX_OK;
-    *h->chain_err_host = 0;
-    DIMX_HIP(hipMemsetAsync(h->chain_err_dev, 0, 64, (hipStream_t)stream));
-    h->graph_valid = false;
-    ++h->chain_faults;
+    const int e2 = take_chain_flags(h, stream);
+    if (e2 <= 0) return e2;
     h->use_chain = 0;
     fprintf(stderr, "dimx: the regenerated batch reported chain flags 0x%x again; regenerating on the one-kernel-per-op step, the "
                     "chain path stays off for this handle\n", e2);
-    DIMX_TRY(generate_impl(h, pr, true, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
-                           ws_bytes, stream, &chain_used));
+    DIMX_TRY(run(true));
     DIMX_REQUIRE(!chain_used, DIMX_ERR_STATE, "generate: the chain path is still active after it was switched off");
     return DIMX_OK;
 }
@@ -2711,11 +2613,7 @@ int dimx_mesh_head(dimx_handle h, const float* motion, const float* templ, int B
         A = s.a;
     }
     GemmArgs g;
-    gemm_lin(h, A, 768, m.l1, M, g);
-    g.act = ACT_LEAKY;
-    g.out_dtype = h->at;
-    gemm_set_plain_out(g, s.l1, 768);
-    DIMX_TRY(launch_gemm(g, st));
+    DIMX_TRY(linear(h, A, 768, m.l1, M, h->at, s.l1, 768, st, ACT_LEAKY));
     // N = mesh_dim is no multiple of any tile (70110 % 4 = 2): the kernels clamp the W rows they load to N - 1 and store no
     // column >= N, the staged and 256 x 256 epilogues (N % 4 / N % 8) are not taken; the template row of the clip rides the epilogue
     gemm_lin(h, s.l1, 768, m.l2, M, g);
@@ -3232,19 +3130,20 @@ int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk,
 
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise, uint64_t seed,
                    uint64_t step, int32_t* tokens, void* stream) {
-    // exp_noise here is the [R,512] slice of this step (step only salts the on-device generator)
-    return launch_sample(logits, 512, R, top_k, temperature, exp_noise, seed, nullptr, exp_noise ? 0 : step, tokens, 1,
-                         0, 1, 0, nullptr, 0, 0, R, nullptr, 0, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return dimx_op_sample_filtered(logits, R, DIMX_FILTER_TOP_K, top_k, 0.f, 0.f, temperature, exp_noise, seed, step, tokens, nullptr,
+                                   stream);
 }
 
 int dimx_op_sample_filtered(const float* logits, int R, int kind, int top_k, float a, float b, float temperature,
                             const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens, uint8_t* keep_out,
                             void* stream) {
     DIMX_TRY(check_sampler_filter(kind, a, b));
-    return launch_sample(logits, 512, R, kind == DIMX_FILTER_TOP_K ? top_k : 0, temperature, exp_noise, seed, nullptr,
-                         exp_noise ? 0 : step, tokens, 1, 0, 1, 0, nullptr, 0, 0, R, nullptr, 0, nullptr, nullptr, nullptr,
-                         (hipStream_t)stream, nullptr, 0.f, 0, nullptr, nullptr, nullptr, DIMX_F32, nullptr, nullptr, 0, nullptr, 0,
-                         0, nullptr, 1, nullptr, SampleFilter{kind, a, b, keep_out});
+    SampleArgs sm;
+    sm.logits = logits; sm.ld_logits = 512; sm.R = R; sm.nslab = 1; sm.rows_total = R; sm.tokens = tokens; sm.tok_ld = 1;
+    sm.top_k = kind == DIMX_FILTER_TOP_K ? top_k : 0; sm.temperature = temperature; sm.seed = seed;
+    sm.noise = exp_noise; sm.step_host = exp_noise ? 0 : step;   // the [R,512] slice of this step (step only salts the generator)
+    sm.filt = SampleFilter{kind, a, b, keep_out};
+    return launch_sample(sm, (hipStream_t)stream);
 }
 
 }  // extern "C"
