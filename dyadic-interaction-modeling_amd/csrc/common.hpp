@@ -204,6 +204,21 @@ __device__ __forceinline__ float wave_sum_fast(float v) {
     return (lane_f32(v, 0) + lane_f32(v, 16)) + (lane_f32(v, 32) + lane_f32(v, 48));
 }
 template <bool FAST> __device__ __forceinline__ float wave_sum_sel(float v) { return FAST ? wave_sum_fast(v) : wave_sum(v); }
+template <int O> __device__ __forceinline__ double xor_lane_f64(double v) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)xor_lane_i32<O>((int)(unsigned)u), hi = (unsigned)xor_lane_i32<O>((int)(unsigned)(u >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// the xor 32, 16, ... 1 butterfly in double: every lane ends with the same bits.  All 64 lanes must be active.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v += xor_lane_f64<32>(v);
+    v += xor_lane_f64<16>(v);
+    v += xor_lane_f64<8>(v);
+    v += xor_lane_f64<4>(v);
+    v += xor_lane_f64<2>(v);
+    v += xor_lane_f64<1>(v);
+    return v;
+}
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -522,6 +537,60 @@ struct SampleArgs {
     SampleFilter filt;
 };
 int launch_sample(const SampleArgs& a, hipStream_t s);
+// Beam search (beam.hip; the definition is dimx/beam.py).  One selection launch: rows clip * W + w of `logits` (split-K slabs, added
+// in slab order like the sampler) are the W beams of a clip; column c = *step_dev (or step_host).  The mode of a clip is
+// forced while c + 1 < clamp(prompt_len, dev_params[8] + 1, prompt_max) (the sampler's rule), frozen when c >= lens[clip] - len_off,
+// live otherwise -- or mode[clip] (0 live, 1 forced with forced_tok[clip], 2 frozen) when `mode` is given (dimx_op_beam_step).
+// cum_in / cum_out may be the same buffer.  step_rw / done_ctr / epoch_rw advance the step word as the sampler does.
+struct BeamSelectArgs {
+    const float* logits = nullptr;
+    int nslab = 1;
+    long slab_stride = 0;
+    int nclip = 0, W = 0;
+    const int32_t* step_dev = nullptr;
+    int step_host = 0;
+    int32_t* step_rw = nullptr;
+    unsigned* done_ctr = nullptr;
+    int32_t* epoch_rw = nullptr;
+    const int32_t* dev_params = nullptr;
+    const int32_t* prompt = nullptr;
+    int prompt_ld = 0, prompt_max = 0;
+    const int32_t* prompt_len = nullptr;
+    const int32_t* lens = nullptr;
+    int len_off = 0;
+    const int32_t* mode = nullptr;
+    const int32_t* forced_tok = nullptr;
+    const double* cum_in = nullptr;
+    double* cum_out = nullptr;
+    int32_t* parent = nullptr;
+    int32_t* tokens = nullptr;     // [R, tok_ld], column c (column 0 without step_dev)
+    int32_t* backptr = nullptr;    // [R, tok_ld] or nullptr
+    int tok_ld = 1;
+    float* logits_out = nullptr;   // [R, tok_ld, 512] or nullptr
+    const float* emb_table = nullptr;   // next step's input row x_next[row] = emb_table[token] (emb_C % 4 == 0) or nullptr
+    int emb_C = 0;
+    float* x_next = nullptr;
+    const float* qkv0_table = nullptr;  // and the first layer's q/k/v table row into qkv0_out[row] (qkv0_N % 4 == 0) or nullptr
+    float* qkv0_out = nullptr;
+    int qkv0_N = 0;
+};
+bool beam_width_supported(int W);   // {1, 2, 4, 5, 8, 10}: the rows per clip generate_impl accepts
+int launch_beam_select(const BeamSelectArgs& a, hipStream_t s);
+// In-place permutation of nbuf caches [nclip * W, H, T, 64] (element size es) by parent beam, positions 0 .. c, and of the token /
+// back-pointer columns 0 .. c - 1; c = *step_dev - step_back (the selection has advanced the word already) or c_host.
+struct BeamReorderArgs {
+    void* buf[16] = {};
+    int nbuf = 0, es = 4, nclip = 0, W = 0, H = 0, T = 0;
+    const int32_t* parent = nullptr;
+    const int32_t* step_dev = nullptr;
+    int step_back = 0, c_host = 0;
+    int32_t* tokens = nullptr;
+    int32_t* backptr = nullptr;
+    int tok_ld = 0;
+};
+int launch_beam_reorder(const BeamReorderArgs& a, hipStream_t s);
+// cum[r] = 0 for beam 0 of a clip, -inf for the others; parent[r] = r % W
+int launch_beam_init(double* cum, int32_t* parent, int R, int W, hipStream_t s);
 // the first decoder layer's q/k/v as a table over the token ids (model.hip qkv0_table_build): id list of the build rounds,
 // slab-order sum of a round's projection into the table rows, and step 0's rows by start token
 int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s);

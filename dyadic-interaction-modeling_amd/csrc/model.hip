@@ -1969,6 +1969,7 @@ struct GenCall {
     int32_t* tokens;
     float* logits_out;
     const float* qkv0;   // the first layer's q/k/v table or nullptr
+    const BeamCall* beam = nullptr;   // beam search: the selection and the cache reorder end the step in the sampler's place
 };
 
 // one decoder step for the clip group `grp` = rows [row0, row0 + B) of a batch of gc.Btot sequences:
@@ -2226,6 +2227,32 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.final_g, B, DD, st));
         DIMX_TRY(slab_gemm(s.y, DD, h->dec.logits, s.logits, s0.st_lg, &nlg));
     }
+    if (gc.beam) {
+        // Beam search (beam.hip): rows clip * S + w are the S hypotheses of a clip.  The selection writes column c of the token rows in
+        // the new order, the next step's embedding / q/k/v table rows, and advances the step word; the reorder then permutes cache
+        // positions 0 .. c and token columns < c by parent beam, reading c as the advanced word - 1.
+        const BeamCall& bm = *gc.beam;
+        BeamSelectArgs bs;
+        bs.logits = s.logits; bs.nslab = nlg; bs.slab_stride = s0.st_lg; bs.nclip = nclip; bs.W = S;
+        bs.step_dev = s.step; bs.step_rw = s.step; bs.done_ctr = (unsigned*)(s.step + 8); bs.epoch_rw = s.step + 9; bs.dev_params = s.step + 2;
+        bs.prompt = forced; bs.prompt_ld = pr.ld; bs.prompt_max = pr.Pmax; bs.prompt_len = forced_len;
+        bs.lens = bm.lens ? bm.lens + clip0 : nullptr; bs.len_off = T - n;
+        bs.cum_in = bm.cum + row0; bs.cum_out = bm.cum + row0; bs.parent = bm.parent + row0;
+        bs.tokens = tokens; bs.backptr = bm.backptr ? bm.backptr + (size_t)row0 * n : nullptr; bs.tok_ld = n; bs.logits_out = logits_out;
+        bs.emb_table = h->dec.tok_emb; bs.emb_C = DD; bs.x_next = s.x;
+        bs.qkv0_table = gc.qkv0; bs.qkv0_out = s.qkv; bs.qkv0_N = 3 * inner;
+        DIMX_TRY(launch_beam_select(bs, st));
+        if (!gc.qkv0) DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
+        BeamReorderArgs br;
+        for (int l = 0; l < dg.depth; ++l) {
+            br.buf[2 * l] = boff(s0.sk[l], (size_t)heads * T * 64 * es);
+            br.buf[2 * l + 1] = boff(s0.sv[l], (size_t)heads * T * 64 * es);
+        }
+        br.nbuf = 2 * dg.depth; br.es = (int)es; br.nclip = nclip; br.W = S; br.H = heads; br.T = T;
+        br.parent = bs.parent; br.step_dev = s.step; br.step_back = 1;
+        br.tokens = tokens; br.backptr = bs.backptr; br.tok_ld = n;
+        return launch_beam_reorder(br, st);
+    }
     SampleArgs sm;
     sm.logits = s.logits; sm.ld_logits = V; sm.R = B; sm.nslab = nlg; sm.slab_stride = s0.st_lg; sm.row0 = row0; sm.rows_total = gc.Btot;
     sm.top_k = gc.top_k; sm.noise = gc.noise; sm.filt.kind = h->filter_kind;
@@ -2283,7 +2310,8 @@ extern "C" {
 // positions >= step0 and token / logit columns >= step0 only, so the prefix is intact and only the counters start over.
 static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_prefill, const uint8_t* ctx_mask, int B, int T, int n_samples,
                          float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens,
-                         float* logits_out, void* ws, size_t ws_bytes, void* stream, bool* chain_used, bool prefill_only = false) {
+                         float* logits_out, void* ws, size_t ws_bytes, void* stream, bool* chain_used, bool prefill_only = false,
+                         const dimx::BeamCall* beam = nullptr) {
     const int32_t* start = pr.tok;
     const int S = n_samples < 1 ? 1 : n_samples;
     if (h && h->filter_kind != DIMX_FILTER_TOP_K) top_k = 0;   // the other kinds ignore the call's k (and it keys the step graph)
@@ -2319,13 +2347,20 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
     DIMX_TRY(launch_gen_params(s.step, dimx_ctx::kMaxGroups, temperature, seed, h->shard_row_off * S,
                                h->shard_rows_total * S, st, pr.step0, h->filter_a, h->filter_b));
     if (gen_multi_tr(h, S)) DIMX_TRY(launch_pack_key_words(ctx_mask, T, nullptr, B, T, s.kw, s.kw_cap, st));
+    if (beam) {   // every run of the call (a regeneration after a chain fault too) starts the search over
+        DIMX_REQUIRE(h->decg.dim_head == 64 && h->decg.depth <= 8 && !h->decg.abs_pos, DIMX_ERR_ARG,
+                     "generate_beam: needs 64-wide heads, at most 8 layers and a decoder without positional embedding");
+        DIMX_TRY(launch_beam_init(beam->cum, beam->parent, R, S, st));
+        if (beam->backptr && pr.step0 > 0)   // no step ran on the prefilled columns: -1
+            DIMX_HIP(hipMemset2DAsync(beam->backptr, (size_t)n * 4, 0xFF, (size_t)pr.step0 * 4, R, st));
+    }
     // Independent clip groups run as separate step graphs on separate streams: every decode kernel is
     // latency-bound at these sizes, so two groups in flight let one group's GEMM/LayerNorm chain overlap the
     // other group's HBM-bound attention.  Results do not depend on the grouping (per-clip state only; the
     // sampler's noise / counter-based RNG is indexed by the global clip row).
     int G = h->gen_groups < 1 ? 1 : h->gen_groups;
     if (G > B) G = B;
-    if (S > 1) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
+    if (S > 1 || beam) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
     // one group: every projection launch of the generation has R rows, and so has the table's build
     const float* qkv0 = nullptr;
     if (G == 1 && qkv0_table_supported(h)) {
@@ -2357,7 +2392,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
             DIMX_HIP(hipStreamWaitEvent(gs[g], h->ev_fork, 0));
         }
     }
-    const GenCall gc{cp, s, pr, ctx_mask, R, T, S, top_k, temperature, exp_noise, seed, tokens, logits_out, qkv0};
+    const GenCall gc{cp, s, pr, ctx_mask, R, T, S, top_k, temperature, exp_noise, seed, tokens, logits_out, qkv0, beam};
     for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, gs[g], true));
     if (!h->use_graph) {
         for (int t = 0; t < nrun; ++t)
@@ -2367,7 +2402,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
         // pointers, row stride and width are kernel arguments of the sampler; P0 is not (the counters' start value and the
         // number of launches below), so a call with another P0 replays the same graphs.
         GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0),
-                     pr.len, pr.ld, pr.Pmax, h->filter_kind};
+                     pr.len, pr.ld, pr.Pmax, h->filter_kind, beam ? *beam : dimx::BeamCall{}};
         if (!(h->graph_valid && h->graph_key == key)) {
             h->graph_valid = false;
             if (!h->cap_stream) DIMX_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -2487,11 +2522,11 @@ static int take_chain_flags(dimx_handle h, void* stream) {
 // the chain path off for this handle.  Round 2 reported the fault one call late.
 static int generate_checked(dimx_handle h, const dimx::GenPrompt& pr, const uint8_t* ctx_mask, int B, int T, int n_samples,
                             float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out,
-                            void* ws, size_t ws_bytes, void* stream) {
+                            void* ws, size_t ws_bytes, void* stream, const dimx::BeamCall* beam = nullptr) {
     bool chain_used = false;
     auto run = [&](bool keep_prefill) {
         return generate_impl(h, pr, keep_prefill, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
-                             ws_bytes, stream, &chain_used);
+                             ws_bytes, stream, &chain_used, false, beam);
     };
     DIMX_TRY(run(false));
     if (h->chain_fault_inject > 0) --h->chain_fault_inject;
@@ -2563,6 +2598,38 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
     }
     return generate_checked(h, pr, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws, ws_bytes,
                             stream);
+}
+
+int dimx_generate_beam(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
+                       const uint8_t* ctx_mask, const int32_t* lens, int B, int T, int beam_width, int32_t* tokens, double* scores,
+                       int32_t* backptr, float* logits_out, void* beam_state, size_t beam_state_bytes, int flags, void* ws, size_t ws_bytes,
+                       void* stream) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_beam: beam search is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    DIMX_REQUIRE(dimx::beam_width_supported(beam_width), DIMX_ERR_ARG, "generate_beam: beam_width %d not in {1,2,4,5,8,10}", beam_width);
+    DIMX_REQUIRE(prompt && scores && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
+                 "generate_beam: need scores, 1 <= Pmax <= T - 1 and ld_prompt >= Pmax (Pmax=%d T=%d ld_prompt=%d)", Pmax, T, ld_prompt);
+    DIMX_REQUIRE(P0 >= 1 && P0 <= Pmax, DIMX_ERR_ARG, "generate_beam: need 1 <= P0 <= Pmax (P0=%d Pmax=%d)", P0, Pmax);
+    DIMX_REQUIRE((flags & ~1) == 0, DIMX_ERR_ARG, "generate_beam: unknown flags 0x%x", flags);
+    DIMX_REQUIRE(B >= 1 && T <= h->d.max_seq_len, DIMX_ERR_ARG, "B=%d T=%d out of range (T <= %d)", B, T, h->d.max_seq_len);
+    const size_t R = (size_t)B * beam_width;
+    DIMX_REQUIRE(beam_state && ((uintptr_t)beam_state % 8) == 0 && beam_state_bytes >= DIMX_BEAM_STATE_BYTES(B, beam_width), DIMX_ERR_ARG,
+                 "generate_beam: the beam state needs %zu bytes, 8-byte aligned (DIMX_BEAM_STATE_BYTES); got %zu", (size_t)DIMX_BEAM_STATE_BYTES(B, beam_width),
+                 beam_state_bytes);
+    const int p0 = (flags & 1) ? 1 : P0;
+    DIMX_REQUIRE(p0 == 1 || h->decg.dim_head == 64, DIMX_ERR_ARG, "generate_beam: the prefill needs 64-wide heads");
+    const size_t need = dimx::workspace_bytes_prompt(h, B, T, beam_width, p0);
+    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "generate_beam: workspace %zu < required %zu (dimx_workspace_bytes_prompt)", ws_bytes, need);
+    const dimx::GenPrompt pr{prompt, ld_prompt, Pmax, prompt_len, p0 - 1};
+    dimx::BeamCall bm;
+    bm.cum = (double*)beam_state;
+    bm.parent = (int32_t*)((double*)beam_state + R);
+    bm.backptr = backptr;
+    bm.lens = lens;
+    DIMX_TRY(generate_checked(h, pr, ctx_mask, B, T, beam_width, 0.f, 0, nullptr, 0, tokens, logits_out, ws, ws_bytes, stream, &bm));
+    DIMX_HIP(hipMemcpyAsync(scores, bm.cum, R * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DIMX_OK;
 }
 
 // x-transformers' own parameter ranges; the kernel treats thres >= 1 and min_p = 0 as "keep everything"

@@ -110,6 +110,15 @@ struct Arena {
     }
 };
 
+// Beam search (dimx_generate_beam): what the step's two beam kernels read and write beside the generation's own buffers
+struct BeamCall {
+    double* cum = nullptr;         // [B*W] running scores
+    int32_t* parent = nullptr;     // [B*W] the last selection's parent beams
+    int32_t* backptr = nullptr;    // [B*W, n] or nullptr
+    const int32_t* lens = nullptr; // [B] or nullptr: clip lengths (columns at or past len - (T - n) are frozen)
+    bool operator==(const BeamCall& o) const { return cum == o.cum && parent == o.parent && backptr == o.backptr && lens == o.lens; }
+};
+
 struct GraphKey {
     void* ws;
     int B, T, top_k;
@@ -121,8 +130,9 @@ struct GraphKey {
     const void* prompt_len;   // prompted generation: the sampler's other prompt arguments (`start` is the prompt itself)
     int ld_prompt, Pmax;
     int filter_kind;          // the sampler kernel's instantiation; the filter's real-valued parameters live in device memory
+    BeamCall beam;            // beam search: the selection / reorder kernels' buffers, all null = the sampler ends the step
     bool operator==(const GraphKey& o) const {
-        return groups == o.groups && filter_kind == o.filter_kind && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
+        return beam == o.beam && groups == o.groups && filter_kind == o.filter_kind && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
                noise == o.noise && seed == o.seed && start == o.start && mask == o.mask && tokens == o.tokens &&
                logits_out == o.logits_out;
     }

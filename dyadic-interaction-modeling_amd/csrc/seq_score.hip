@@ -32,22 +32,6 @@ struct SeqArgs {
     int32_t* count;
 };
 
-template <int O> __device__ __forceinline__ double xor_lane_f64(double v) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)xor_lane_i32<O>((int)(unsigned)u), hi = (unsigned)xor_lane_i32<O>((int)(unsigned)(u >> 32));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-// the xor 32, 16, ... 1 butterfly in double: every lane ends with the same bits.  All 64 lanes must be active.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    v += xor_lane_f64<32>(v);
-    v += xor_lane_f64<16>(v);
-    v += xor_lane_f64<8>(v);
-    v += xor_lane_f64<4>(v);
-    v += xor_lane_f64<2>(v);
-    v += xor_lane_f64<1>(v);
-    return v;
-}
-
 __device__ __forceinline__ int clamp_col(int c, int n) { return c < 0 ? 0 : (c > n ? n : c); }
 
 __global__ __launch_bounds__(kSeqThreads) void seq_logprob_kernel(SeqArgs a) {

@@ -328,6 +328,37 @@ class Engine:
                 else torch.full((B,), Pmax, dtype=torch.int32, device=self.device)
         return self._generated(tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores)
 
+    def generate_beam(self, start, mask_u8, T, beam_width, prompt=None, prompt_len=None, prefill=None, return_logits=False,
+                      return_backptr=False):
+        """Beam search (dimx_generate_beam, csrc/beam.hip; the definition is dimx.beam): W = ``beam_width`` hypotheses per clip in
+        one pass (rows b*W + w, sharing the clip's context K/V like ``n_samples``), deterministic, no temperature / filter / seed.
+        -> (tokens [B*W, n] int32 -- whole hypotheses, row b*W the best --, scores f64 [B*W], descending within a clip[, logits
+        [B*W, n, 512] in the row order each step ran in][, backptr [B*W, n] int32: the row that ran step c on the hypothesis's path]).
+        The scored columns are those of dimx.scoring.scored_columns (inside the clip's length, past its prompt); the lengths come
+        from ``mask_u8`` on the device.  ``prompt`` / ``prompt_len`` / ``prefill`` as in ``generate``; the context must have been
+        built with ``n_samples=beam_width`` (and ``prompt_frames >= prefill``)."""
+        W = int(beam_width)
+        if prompt is None:
+            prompt, prompt_len, prefill = start.reshape(-1, 1), None, 1
+        B, Pmax = prompt.shape
+        R = B * W
+        prompt = prompt.to(torch.int32).contiguous()
+        prompt_len = prompt_len.to(torch.int32).contiguous() if prompt_len is not None else None
+        P0 = int(prefill) if prefill is not None else (Pmax if prompt_len is None else 1)
+        lens = mask_u8.sum(1, dtype=torch.int32)
+        self._chk(prompt, prompt_len, mask_u8)
+        n = self.n_gen(T)
+        tokens = torch.empty(R, n, dtype=torch.int32, device=self.device)
+        scores = torch.empty(R, dtype=torch.float64, device=self.device)
+        lg = torch.empty(R, n, self.dims.num_tokens, dtype=torch.float32, device=self.device) if return_logits else None
+        bp = torch.empty(R, n, dtype=torch.int32, device=self.device) if return_backptr else None
+        state = torch.empty(2 * R, dtype=torch.float64, device=self.device)    # DIMX_BEAM_STATE_BYTES = 16 * B * W
+        ws, wsb = self.workspace(B, T, W)   # the workspace the context was built in, never grown here (see _generate_prompted)
+        L.check(self.lib.dimx_generate_beam(self.h, L.ptr(prompt), int(prompt.stride(0)), L.ptr(prompt_len), int(Pmax), P0,
+                                            L.ptr(mask_u8), L.ptr(lens), B, T, W, L.ptr(tokens), L.ptr(scores), L.ptr(bp), L.ptr(lg),
+                                            L.ptr(state), state.numel() * 8, 0, ws, wsb, self._s()), "dimx_generate_beam")
+        return (tokens, scores) + ((lg,) if return_logits else ()) + ((bp,) if return_backptr else ())
+
     def mesh_head(self, motion, template=None, safe=False, out=None):
         """EmocaConverter head: motion [B,L,56] -> mesh [B,L,V] = vertice_map_reverse(vertice_map_reverse_lstm(motion)) +
         template[:, None] (template [B,V] or None).  ``safe``: the LSTM layers on the no-communication path.  ``out``: a
@@ -763,6 +794,45 @@ def op_seq_logprob(logits, tokens, first=None, last=None, rows_per_clip=1, want_
                                         L.ptr(tok_lp), L.ptr(score), L.ptr(count), L.stream_ptr(dev)), "dimx_op_seq_logprob")
     out = SeqScores(score, count)
     return (out, tok_lp) if want_tokens else out
+
+
+def op_beam_step(logits, cum, mode, forced_tok=None, beam_width=1):
+    """One beam-search selection (dimx_op_beam_step, csrc/beam.hip; the definition is dimx.beam.beam_step): logits [B*W, 512] f32,
+    cum [B*W] f64, mode [B] (dimx.beam.LIVE / FORCED / FROZEN), forced_tok [B] or None -> (parent int32 [B*W], token int32 [B*W],
+    cum' f64 [B*W]).  Asynchronous on the current stream.  CPU tensors raise: dimx.beam.beam_step is the host form."""
+    if not (torch.is_tensor(logits) and logits.is_cuda and torch.is_tensor(cum) and cum.is_cuda):
+        raise L.DimxError("op_beam_step runs on the GPU only: logits / cum must be CUDA tensors (no CPU fallback)")
+    W, dev = int(beam_width), logits.device
+    if logits.dim() != 2 or logits.shape[1] != 512 or W < 1 or logits.shape[0] % W or cum.numel() != logits.shape[0]:
+        raise L.DimxError("op_beam_step: logits [B*W, 512] and cum [B*W] expected, got %s and %s" % (tuple(logits.shape), tuple(cum.shape)))
+    R = int(logits.shape[0])
+    B = R // W
+    logits = logits.to(torch.float32).contiguous()
+    cum = cum.to(torch.float64).contiguous()
+    mode_d = _lens_i32(mode, dev, B, "op_beam_step(mode)")
+    forced_d = _lens_i32(forced_tok, dev, B, "op_beam_step(forced_tok)") if forced_tok is not None else None
+    parent = torch.empty(R, dtype=torch.int32, device=dev)
+    token = torch.empty(R, dtype=torch.int32, device=dev)
+    out = torch.empty(R, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().dimx_op_beam_step(L.ptr(logits), L.ptr(cum), L.ptr(mode_d), L.ptr(forced_d), B, W, L.ptr(parent), L.ptr(token),
+                                           L.ptr(out), L.stream_ptr(dev)), "dimx_op_beam_step")
+    return parent, token, out
+
+
+def op_beam_reorder(cache, parent, c, beam_width):
+    """In-place reorder of a self-attention cache by parent beam (dimx_op_beam_reorder, csrc/beam.hip): cache [R, H, T, 64] f32 or
+    bf16, contiguous, parent [R] int32 -> cache[clip*W + w, :, :c+1] = old cache[clip*W + parent[w], :, :c+1]; returns ``cache``."""
+    if not (torch.is_tensor(cache) and cache.is_cuda and cache.is_contiguous() and cache.dim() == 4 and cache.shape[3] == 64
+            and cache.dtype in (torch.float32, torch.bfloat16)):
+        raise L.DimxError("op_beam_reorder: a contiguous CUDA cache [R, H, T, 64] of float32 or bfloat16 expected")
+    dev = cache.device
+    R, H, T, _ = (int(v) for v in cache.shape)
+    parent_d = _lens_i32(parent, dev, R, "op_beam_reorder(parent)")
+    with torch.cuda.device(dev):
+        L.check(L.load().dimx_op_beam_reorder(L.ptr(cache), L.BF16 if cache.dtype == torch.bfloat16 else L.F32, L.ptr(parent_d), R,
+                                              int(beam_width), H, T, int(c), L.stream_ptr(dev)), "dimx_op_beam_reorder")
+    return cache
 
 
 def op_score_select(score, y_pred, lens, tokens=None):

@@ -76,6 +76,8 @@ SIGNATURES = {
     "dimx_workspace_bytes_prompt": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "dimx_generate_prompted": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float,
                                        c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "dimx_generate_beam": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
     "dimx_train_num_params": (c_int, [c_void_p]),
     "dimx_train_total": (c_int64, [c_void_p]),
     "dimx_train_param_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),
@@ -179,6 +181,8 @@ SIGNATURES = {
                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dimx_op_score_select": (c_int, [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, ctypes.c_long,
                                      c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dimx_op_beam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dimx_op_beam_reorder": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
     "dimx_op_sample_filtered": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_uint64, c_uint64,

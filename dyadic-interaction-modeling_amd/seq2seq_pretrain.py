@@ -153,7 +153,7 @@ class SLMFT(_EngineOwner):
     @torch.no_grad()
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
                         seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False):
+                        filter_kwargs=None, return_scores=False, beam_width=0):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -168,7 +168,13 @@ class SLMFT(_EngineOwner):
         ``top_k``, ``top_p``, ``min_p`` or ``top_a`` of dimx.sampling (object or name).  The default is the reference's call:
         top_k with k = ceil(0.1 * 512) = 52.
 
-        ``return_scores`` (mode 'val'): a third value, the SeqScores [B*S] of the sampled sequences (Engine.generate)."""
+        ``return_scores`` (mode 'val'): a third value, the SeqScores [B*S] of the sampled sequences (Engine.generate).
+
+        ``beam_width`` W >= 1 (mode 'val'): beam search instead of sampling (Engine.generate_beam; ``n_samples`` must be W, the
+        sampler's arguments are not used): tokens [B*W, T-1], whole hypotheses, row b*W the best; the SeqScores are the search's
+        own running scores and the number of scored columns."""
+        if beam_width and (mode != "val" or int(n_samples) != int(beam_width)):
+            raise ValueError("beam_width applies to mode='val' with n_samples == beam_width")
         if return_scores and mode != "val":
             raise ValueError("return_scores applies to mode='val' (SLMFT.score is the teacher-forced form)")
         prompt_frames = _check_prompt_frames(prompt_frames, z_l.shape[1])
@@ -187,6 +193,16 @@ class SLMFT(_EngineOwner):
             return row_loss.sum() / n_valid, logits
         plen, p0 = prompt_lengths(mask, prompt_frames, lengths) if prompt_frames > 1 else (None, 1)
         self._build_context(eng, x_s, v_speaker, x_a, m8, True, n_samples=n_samples, prompt_frames=p0)
+        if beam_width:
+            from .scoring import SeqScores, scored_columns
+            tokens, score = eng.generate_beam(z_l[:, 0], m8, T, int(beam_width), prompt=z_l[:, :prompt_frames] if prompt_frames > 1 else None,
+                                              prompt_len=plen, prefill=p0)
+            if not return_scores:
+                return 0.0, tokens.long()
+            n = tokens.shape[1]
+            first, last = scored_columns(T, n, m8.sum(1, dtype=torch.int32), plen)
+            count = (last.clamp(0, n) - (first + torch.zeros_like(last)).clamp(0, n)).clamp(min=0).to(torch.int32)
+            return 0.0, tokens.long(), SeqScores(score, count.repeat_interleave(int(beam_width)))
         if greedy:
             temperature, seed_v = 0.0, 0
         else:
@@ -271,7 +287,7 @@ class SLMFT(_EngineOwner):
     def forward(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                 return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                filter_kwargs=None, return_scores=False):
+                filter_kwargs=None, return_scores=False, beam_width=None, num_return=1):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
@@ -284,7 +300,15 @@ class SLMFT(_EngineOwner):
 
         ``return_scores`` (mode 'val'; any other mode raises ValueError): the log-likelihood of every generated sequence under the
         model (dimx.scoring.SeqScores: score f64 and count int32, [B] or [B,S]) is appended after ``pred``, or after ``tokens``
-        with ``return_tokens``.  Cost and scored columns: ``Engine.generate``."""
+        with ``return_tokens``.  Cost and scored columns: ``Engine.generate``.
+
+        ``beam_width`` W in {1, 2, 4, 5, 8, 10} (mode 'val'): beam search (dimx.beam, ``Engine.generate_beam``) instead of sampling --
+        deterministic, ``noise`` / ``greedy`` / ``seed`` / ``temperature`` / the filter / ``n_samples`` are not used.  ``num_return``
+        = 1: the best hypothesis, shapes as without the argument; ``num_return`` = W: all W, best first, shapes as with
+        ``n_samples=W`` (pred [B,W,T-1,56]).  With ``return_scores`` the SeqScores hold the search's own scores."""
+        if beam_width is not None:
+            if mode != "val" or int(num_return) not in (1, int(beam_width)):
+                raise ValueError("beam_width applies to mode='val' with num_return 1 or beam_width")
         prompt_frames = _check_prompt_frames(prompt_frames, mask.shape[1])
         if prompt_frames > 1 and mode != "val":
             raise ValueError("prompt_frames applies to mode='val'")
@@ -298,20 +322,22 @@ class SLMFT(_EngineOwner):
                                         greedy=greedy, seed=seed, temperature=temperature,
                                         batch_row_offset=batch_row_offset, return_tokens=return_tokens,
                                         n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths,
-                                        filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores)
+                                        filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
+                                        beam_width=beam_width, num_return=num_return)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                         return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False):
+                        filter_kwargs=None, return_scores=False, beam_width=None, num_return=1):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
         reference's evaluation loop obtains from S separate forward calls (code/x_engine_pt.py:257) -- sharing the
         VQ encode, the encoder stack and the context K/V stream; pred is then [B,S,T-1,56], tokens [B,S,T-1]."""
         mask = mask.bool()
-        S = int(n_samples)
+        W = int(beam_width or 0)
+        S = W if W else int(n_samples)
         assert S == 1 or mode != "train", "n_samples applies to mode='val'"
         _, z_l = self.forward_vq(v_speaker, v_listener, mask, with_speaker=False)
         # shard = (first clip row, clips in the whole batch) when this call is one rank's slice of a batch: together
@@ -323,9 +349,13 @@ class SLMFT(_EngineOwner):
                                                          kv_mask=kv_mask, greedy=greedy, seed=seed, temperature=temperature,
                                                          n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
                                                          filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs,
-                                                         return_scores=return_scores)
+                                                         return_scores=return_scores, beam_width=W)
         finally:
             eng.set_shard(0, 0)
+        if W and int(num_return) == 1:    # the best hypothesis is row 0 of its clip
+            px_l = px_l.view(mask.shape[0], W, -1)[:, 0].contiguous()
+            scores = [type(sc)(sc.score.view(-1, W)[:, 0], sc.count.view(-1, W)[:, 0]) for sc in scores]
+            S = 1
         pred = self.forward_vq_decoder(px_l, mode=mode, batch_row_offset=batch_row_offset, rows_per_clip=S)
         if S > 1:
             B, T = mask.shape

@@ -188,7 +188,7 @@ def _select(pending, skip_degenerate, world, device):
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
-                        select="fd", **forward_kw):
+                        select="fd", decode="sample", beam_width=None, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -230,7 +230,25 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     truth, for conversations without a recorded listener.  ``fd_backend`` is not consulted, no distance is computed and ``tgt`` is
     used for the returned lists (and by ``metrics``) only; the winners stay on the device, so ``metrics`` works as with
     ``fd_backend="hip"``.  It needs a batched sample count (BATCHED_SAMPLE_COUNTS, ValueError otherwise) and a ROCm GPU (a CPU
-    device raises lib.DimxError: there is no CPU fallback).  Any other value raises ValueError."""
+    device raises lib.DimxError: there is no CPU fallback).  Any other value raises ValueError.
+
+    ``decode``: "sample" (default) is the protocol above; ``beam_size`` is, as in the reference, the NUMBER OF TRIES of a clip --
+    independent samples, not a beam.  "beam" replaces the tries by the ``beam_width`` final hypotheses of ONE beam search per clip
+    (``SLMFT.forward(beam_width=W, num_return=W)``, dimx.beam; W in BATCHED_SAMPLE_COUNTS, default ``beam_size``): a deterministic
+    n-best list, best first, that goes through the same ``select`` ("likelihood" picks by the search's own scores, that is row 0).
+    ``beam_size``, ``batched_samples`` and the sampler filter are not consulted then.  It needs a ROCm GPU."""
+    if decode not in ("sample", "beam"):
+        raise ValueError("decode=%r: one of 'sample', 'beam'" % (decode,))
+    if decode == "beam":
+        beam_size = int(beam_width if beam_width is not None else beam_size)
+        if beam_size not in BATCHED_SAMPLE_COUNTS:
+            raise ValueError("evaluate_test_epoch(decode='beam'): beam_width must be one of %s (got %d)" % (BATCHED_SAMPLE_COUNTS, beam_size))
+        if torch.device(device).type != "cuda":
+            raise L.DimxError("evaluate_test_epoch(decode='beam') runs on a ROCm GPU only (device %s): there is no CPU fallback" % (device,))
+        batched_samples, filter_logits_fn, filter_kwargs = True, None, None
+        tries_kw = dict(beam_width=beam_size, num_return=beam_size)
+    else:
+        tries_kw = dict(n_samples=beam_size)
     if filter_logits_fn is not None or filter_kwargs:
         forward_kw = dict(forward_kw, filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
     if select not in ("fd", "likelihood"):
@@ -287,13 +305,13 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
                     kw.update(prompt_frames=prompt_frames, lengths=src_len[lo:hi])
                 sl = [t[lo:hi].contiguous() for t in (src_s_v, tgt, src_s_a, mask)]
                 if by_likelihood:
-                    _, _, y_preds, scores = model(sl[0], sl[1], sl[2], sl[3], mode="val", n_samples=beam_size, return_scores=True, **kw)
+                    _, _, y_preds, scores = model(sl[0], sl[1], sl[2], sl[3], mode="val", return_scores=True, **tries_kw, **kw)
                     extra = dict(metrics=metrics, x=src_s_v[lo:hi]) if metrics is not None else {}
                     y_preds_all.extend(_select_likelihood(tgt[lo:hi, 1:], y_preds, scores, [src_len[lo + j] - 1 for j in range(nl)],
                                                           world, device, B, **extra))
                     continue
                 if batched:
-                    _, _, y_preds = model(sl[0], sl[1], sl[2], sl[3], mode="val", n_samples=beam_size, **kw)
+                    _, _, y_preds = model(sl[0], sl[1], sl[2], sl[3], mode="val", **tries_kw, **kw)
                 else:
                     y_preds = torch.stack([model(sl[0], sl[1], sl[2], sl[3], mode="val", **kw)[2] for _ in range(beam_size)], 1)
                 if on_device:                   # [nl, S, T-1, 56] stays on the device; only the winners travel

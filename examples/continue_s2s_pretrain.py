@@ -41,6 +41,10 @@ def main():
                     help="continue the first N ground-truth listener frames of every clip instead of starting from frame 0 alone")
     ap.add_argument("--select", choices=("fd", "likelihood"), default="fd",
                     help="best-of-N by Frechet distance to the ground truth (the reference's protocol) or by the model's own log-likelihood")
+    ap.add_argument("--decode", choices=("sample", "beam"), default="sample",
+                    help="the tries of a clip: --beam independent samples (the reference's protocol; its 'beam' is a number of tries) or "
+                         "the final hypotheses of one beam search of --beam-width (deterministic)")
+    ap.add_argument("--beam-width", type=int, default=None, help="hypotheses of --decode beam (1 < W <= 10; default: --beam)")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -65,7 +69,8 @@ def main():
 
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, val_loader, device, beam_size=args.beam,
-                                                        prompt_frames=args.prompt_frames, select=args.select, **sampler)
+                                                        prompt_frames=args.prompt_frames, select=args.select, decode=args.decode,
+                                                        beam_width=args.beam_width, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     print_metrics(y_true, y_pred, x)

@@ -249,6 +249,37 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
                            const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out, int flags, void* ws,
                            size_t ws_bytes, void* stream);
 
+/* Beam search: the deterministic decoder.  W = beam_width hypotheses per clip (1, 2, 4, 5, 8, 10; 1 is greedy decoding, bit for
+ * bit) are extended one position per step; of the W x 512 candidates cum[w] + log softmax(raw logits[w])[v] the W largest survive,
+ * in descending order, ties to the smaller w * 512 + v (the definition is dimx/beam.py, float64; csrc/beam.hip).  There is no
+ * temperature, filter, noise or seed, no end token and no length penalty.  Variant 0 (SLMFT) only: another variant, and a width
+ * outside the set, return DIMX_ERR_ARG.
+ * The call mirrors dimx_generate_prompted with beam_width in place of n_samples: rows b*W + w belong to clip b and share its
+ * context K/V; prompt / prompt_len / Pmax / P0 / flags bit 0 as there (Pmax = P0 = 1, ld_prompt = 1: prompt is start[B]); the
+ * prefill is broadcast to the W rows and ragged prompts finish by forced steps.  Per clip and column c (position c + 1):
+ *   c < plen - 1              forced: every hypothesis takes the prompt's token, scores unchanged
+ *   c >= lens[b] - 1          frozen: every hypothesis takes its own arg-max, scores unchanged (lens NULL: never) -- the columns
+ *                             dimx_op_seq_logprob does not score (dimx.scoring.scored_columns)
+ *   otherwise                 live: the selection above; the search starts from scores (0, -inf, ...), so the first live step
+ *                             expands hypothesis 0 alone
+ * After a live step the self-attention cache rows and the token rows of the clip are permuted by parent hypothesis, so
+ *   tokens   [B*W, T-1] int32 holds whole hypotheses, row b*W the best;
+ *   scores   [B*W] f64, descending within a clip: the sum of the live columns' log-probabilities;
+ *   backptr  (optional) [B*W, T-1] int32: backptr[r][c] = the row (0 .. W-1 within the clip) that ran step c on hypothesis r's path,
+ *            -1 in the prefilled columns < P0-1;
+ *   logits_out (optional) [B*W, T-1, 512] f32: every step's raw logits in the row order the step ran in (it is NOT permuted: follow
+ *            backptr), zero in the prefilled columns.
+ *   lens     [B] int32 device or NULL.
+ *   beam_state: device memory of at least DIMX_BEAM_STATE_BYTES(B, W) bytes, 8-byte aligned, owned by the call while it runs (running
+ *            scores f64 [B*W], then parents int32 [B*W]).  It is the caller's so that the three workspace queries return what they
+ *            returned before: ws comes from dimx_workspace_bytes_prompt(h, B, T, W, P0) as for W samples.
+ * Chain faults (W = 1, bf16) are answered as in dimx_generate; the regeneration starts the search over. */
+#define DIMX_BEAM_STATE_BYTES(B, W) ((size_t)16 * (size_t)(B) * (size_t)(W))
+int dimx_generate_beam(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
+                       const uint8_t* ctx_mask, const int32_t* lens, int B, int T, int beam_width, int32_t* tokens, double* scores,
+                       int32_t* backptr, float* logits_out, void* beam_state, size_t beam_state_bytes, int flags, void* ws, size_t ws_bytes,
+                       void* stream);
+
 /* In the bf16 mode dimx_generate runs part of the decode step as XCD-local chain kernels (B <= 256, one sample per clip,
  * 256-CU device) that rely on their 256 blocks being co-resident, one per CU.  They verify that and dimx_generate checks
  * their flags BEFORE it returns: with the chain path active the call therefore waits for its own generation to finish
@@ -730,6 +761,18 @@ int dimx_op_seq_logprob(const float* logits, long row_stride, long step_stride, 
 int dimx_op_score_select(const double* score, const float* y_pred, long yp_clip_stride, long yp_sample_stride, long yp_frame_stride,
                          const int32_t* lens, const int32_t* tokens, long tok_row_stride, int B, int S, int L, int W, int n,
                          int32_t* win, uint8_t* ok, float* best, int32_t* best_tokens, void* stream);
+/* The two kernels of dimx_generate_beam on their own (csrc/beam.hip).  All pointers are device memory.
+ * dimx_op_beam_step: logits f32 [B*W, 512], cum f64 [B*W], mode int32 [B] (0 live, 2 frozen, anything else forced with
+ *   forced_tok[B], clamped to [0, 512); forced_tok may be NULL = token 0) -> parent int32 [B*W], token int32 [B*W], cum_out f64 [B*W]
+ *   (cum_out may be cum).  One launch of B blocks.
+ * dimx_op_beam_reorder: cache [R, H, T, 64] of DIMX_F32 or DIMX_BF16 elements, 16-byte aligned, parent int32 [R] (entries 0 .. W-1,
+ *   rows r = clip*W + w): cache[clip*W + w, :, 0..c, :] = old cache[clip*W + parent[w], :, 0..c, :] in place; positions > c and clips
+ *   whose parents are the identity (or out of range) are not touched.  One launch; W = 1 launches nothing.
+ * DIMX_ERR_ARG for a null operand, W outside {1,2,4,5,8,10}, B < 1, R not a positive multiple of W, c outside [0, T), a misaligned
+ * cache; nothing is enqueued then. */
+int dimx_op_beam_step(const float* logits, const double* cum, const int32_t* mode, const int32_t* forced_tok, int B, int W,
+                      int32_t* parent, int32_t* token, double* cum_out, void* stream);
+int dimx_op_beam_reorder(void* cache, int dtype, const int32_t* parent, int R, int W, int H, int T, int c, void* stream);
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
