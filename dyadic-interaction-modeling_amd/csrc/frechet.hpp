@@ -1,4 +1,4 @@
-// frechet.hpp -- the float64 Frechet distance of one clip, shared by fd_select.hip and listener_metrics.hip.
+// frechet.hpp -- the float64 Frechet distance of one clip, shared by fd_select.hip, listener_metrics.hip and consensus.hip.
 //
 // Reference: calculate_activation_statistics / calculate_frechet_distance, code/metrics/eval_utils.py:6-46:
 //     mu, S  = mean and unbiased covariance over the valid frames,   fd = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2)
@@ -320,6 +320,26 @@ __device__ void write_factor(const double* G, int F, int ld, const Smem<T>& sm, 
         const double lam = sm.sig[c];
         A[e] = (sm.red[0][c] != 0.0 && lam > 0.0) ? G[c * ld + r] / sqrt(lam) : 0.0;
     }
+}
+
+// the F x F matrix m (LDS, stride ld) -> dense (global, column-major, stride F), for a later block to read back with load_dense.
+// No barrier: m is only read.
+template <class T>
+__device__ void store_dense(const double* m, int F, int ld, double* dense) {
+    for (int e = threadIdx.x; e < F * F; e += T::THREADS) {
+        const int c = e / F, r = e - c * F;
+        dense[e] = m[c * ld + r];
+    }
+}
+
+// dense (global, column-major, stride F) -> the LDS matrix m (stride ld)
+template <class T>
+__device__ void load_dense(const double* dense, int F, int ld, double* m) {
+    for (int e = threadIdx.x; e < F * F; e += T::THREADS) {
+        const int c = e / F, r = e - c * F;
+        m[c * ld + r] = dense[e];
+    }
+    __syncthreads();
 }
 
 // |mu1 - mu2|^2 in column order -> sm.scal[2].  No barrier: thread 0 writes it and thread 0 reads it in the epilogue.

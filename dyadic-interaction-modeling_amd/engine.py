@@ -883,6 +883,74 @@ def fd_select_sweeps(device, B, S, F):
     return sw[:B].clone(), sw[B:].reshape(B, S).clone()
 
 
+_CS_WS = {}     # device index -> uint8 workspace of op_consensus_select
+
+
+def op_consensus_select(y_pred, lens, cols=(0, None), distance="fd", tokens=None, want_best=True, want_dist=False):
+    """Consensus (minimum-Bayes-risk) best-of-S selection (dimx_op_consensus_select, csrc/consensus.hip; the definition is
+    dimx.consensus): y_pred [B, S, L, W] f32 on a GPU, lens[j] = valid frames of clip j, cols = (c0, c1) the columns that enter the
+    distance (None = the row's end), distance "fd" (the Frechet distance of op_fd_select between tries) or "l2", tokens [B*S, n]
+    (optional) -> (risk [B, S] f64, win [B] int32, ok [B] uint8, best [B, L, W] f32 or None[, best_tokens [B, n] int32][, dist
+    [B, S, S] f64]): per clip the try with the smallest summed distance to the others (the first minimum, NaN counting as +inf),
+    ok = 0 when no risk of the clip is finite, the winner's rows (zero for t >= lens[j] and for ok = 0) and its token row (-100 for
+    ok = 0).  Strides as in op_fd_select: views are passed as they are.  Asynchronous on the current stream.  CPU tensors raise:
+    there is no CPU fallback (dimx.consensus.select is the host form)."""
+    from .consensus import kind_index
+    kind = kind_index(distance)
+    if not (torch.is_tensor(y_pred) and y_pred.is_cuda):
+        raise L.DimxError("op_consensus_select runs on the GPU only: y_pred must be a CUDA tensor (no CPU fallback)")
+    if y_pred.dim() != 4:
+        raise L.DimxError("op_consensus_select: y_pred [B, S, L, W] expected, got %s" % (tuple(y_pred.shape),))
+    lib = L.load()
+    dev = y_pred.device
+    B, S, Ln, W = (int(v) for v in y_pred.shape)
+    y_pred = _f32_rows(y_pred, W > 1)
+    c0 = int(cols[0])
+    F = (W if cols[1] is None else int(cols[1])) - c0
+    lens_d = _lens_i32(lens, dev, B, "op_consensus_select")
+    n, tok_rs = 0, 0
+    if tokens is not None:
+        if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.device == dev and tokens.dim() == 2 and tokens.shape[0] == B * S):
+            raise L.DimxError("op_consensus_select: tokens [B*S, n] on the tries' device expected")
+        tokens = tokens if tokens.dtype == torch.int32 else tokens.to(torch.int32)
+        n = int(tokens.shape[1])
+        if tokens.stride(1) != 1 and n > 1:
+            tokens = tokens.contiguous()
+        tok_rs = tokens.stride(0)
+    dist = torch.empty(B, S, S, dtype=torch.float64, device=dev) if want_dist else None
+    risk = torch.empty(B, S, dtype=torch.float64, device=dev)
+    win = torch.empty(B, dtype=torch.int32, device=dev)
+    ok = torch.empty(B, dtype=torch.uint8, device=dev)
+    best = torch.empty(B, Ln, W, dtype=torch.float32, device=dev) if want_best else None
+    best_tok = torch.empty(B, n, dtype=torch.int32, device=dev) if tokens is not None else None
+    need = int(lib.dimx_op_consensus_select_ws_bytes(B, S, F, kind))
+    ws = _workspace(_CS_WS, dev, need)
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_consensus_select(ctypes.c_void_p(y_pred.data_ptr()), y_pred.stride(0), y_pred.stride(1), y_pred.stride(2),
+                                             L.ptr(lens_d), B, S, Ln, W, c0, F, kind, L.ptr(dist), L.ptr(risk), L.ptr(win), L.ptr(ok),
+                                             L.ptr(best), None if tokens is None else ctypes.c_void_p(tokens.data_ptr()), tok_rs, n,
+                                             L.ptr(best_tok), ctypes.c_void_p(ws.data_ptr()), ws.numel(), L.stream_ptr(dev)),
+                "dimx_op_consensus_select")
+    out = (risk, win, ok, best)
+    if tokens is not None:
+        out += (best_tok,)
+    if want_dist:
+        out += (dist,)
+    return out
+
+
+def consensus_select_sweeps(device, B, S, F):
+    """Jacobi sweeps of the last op_consensus_select(B, S, F, distance="fd") call on ``device``, read from its workspace: (try
+    factorisations [B, S], pair problems [B, S*(S-1)/2] in the order (0,1), (0,2), .., (1,2), ..) as int32 tensors (include/dimx.h:
+    the last B*S + B*S*(S-1)/2 int32 of the workspace)."""
+    lib = L.load()
+    need = int(lib.dimx_op_consensus_select_ws_bytes(B, S, F, 0))
+    ws = _CS_WS[_device_key(device)]
+    P = S * (S - 1) // 2
+    sw = ws[need - 4 * (B * S + B * P):need].view(torch.int32)
+    return sw[:B * S].reshape(B, S).clone(), sw[B * S:].reshape(B, P).clone()
+
+
 _MM_WS = {}      # device index -> uint8 workspace of op_mesh_metrics
 _MM_MAPS = {}    # (device index, n_vert, sorted map bytes) -> MeshMap; keyed on content
 _MM_LENS = {}    # device index -> the host lens array of the last call (kept until the next call has replaced it)

@@ -74,6 +74,14 @@ def frechet_distances_hip(y_true, y_pred, lens, cols=(0, None)):
     return op_fd_select(y_true, y_pred, lens, cols=cols, want_best=False)[0]
 
 
+def consensus_distances_hip(y_pred, lens, cols=(0, None), distance="fd"):
+    """The pairwise distances among the tries of each clip from the project's own kernel (dimx_op_consensus_select,
+    csrc/consensus.hip; the definition is dimx.consensus.pairwise_fd / pairwise_l2): y_pred [B, S, L, W] on a GPU -> dist
+    [B, S, S] float64 on that GPU, symmetric with a zero diagonal.  CPU tensors raise lib.DimxError."""
+    from .engine import op_consensus_select
+    return op_consensus_select(y_pred, lens, cols=cols, distance=distance, want_best=False, want_dist=True)[-1]
+
+
 def sid_device(gt_frames, pred_frames, type="exp"):
     """One fit and two assigns on the GPU, nothing read back: -> f64 [4] on the frames' device = {sid_pred, sid_gt, n_iter, status}
     (status: 0, or the Lloyd iteration at which a cluster was left empty -- the two SID values mean nothing then)."""

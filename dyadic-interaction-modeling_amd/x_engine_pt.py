@@ -153,6 +153,15 @@ def _select_likelihood(y_true, y_preds, scores, lens, world, device, total=None,
     return _winners_to_host(y_true, y_preds, ok, best, lens, world, device, total, metrics, x)
 
 
+def _select_consensus(y_true, y_preds, distance, lens, world, device, total=None, metrics=None, x=None):
+    """select="consensus": the try with the smallest summed distance to the clip's other tries (dimx.engine.op_consensus_select,
+    csrc/consensus.hip; the definition is dimx.consensus); ``y_true`` is read by ``metrics`` only.  A clip with fewer than 2
+    valid frames has no distances and keeps None."""
+    from .engine import op_consensus_select
+    _, _, ok, best = op_consensus_select(y_preds, lens, distance=distance)
+    return _winners_to_host(y_true, y_preds, ok, best, lens, world, device, total, metrics, x)
+
+
 def _winners_to_host(y_true, y_preds, ok, best, lens, world, device, total, metrics, x):
     """the tail of a selection in the HIP library: ``best`` [nl, L, W] and ``ok`` [nl] lie on the device"""
     if metrics is not None:      # the winners where they lie: enqueued behind the selection, nothing is synchronised
@@ -188,7 +197,7 @@ def _select(pending, skip_degenerate, world, device):
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
-                        select="fd", decode="sample", beam_width=None, **forward_kw):
+                        select="fd", decode="sample", beam_width=None, consensus_distance="fd", **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -230,12 +239,18 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     truth, for conversations without a recorded listener.  ``fd_backend`` is not consulted, no distance is computed and ``tgt`` is
     used for the returned lists (and by ``metrics``) only; the winners stay on the device, so ``metrics`` works as with
     ``fd_backend="hip"``.  It needs a batched sample count (BATCHED_SAMPLE_COUNTS, ValueError otherwise) and a ROCm GPU (a CPU
-    device raises lib.DimxError: there is no CPU fallback).  Any other value raises ValueError.
+    device raises lib.DimxError: there is no CPU fallback).  "consensus" keeps, per clip, the try with the smallest total distance
+    to the clip's other tries (minimum Bayes risk, the medoid; dimx.engine.op_consensus_select, definition dimx.consensus): it needs
+    no ground truth either and does not share the likelihood pick's preference for the modal, low-motion sequence.
+    ``consensus_distance`` is "fd" (default: the protocol's own Frechet distance, between tries) or "l2".  The same conditions hold as
+    for "likelihood": ``tgt`` is not read for the selection, the winners stay on the device (``metrics`` works), a batched sample
+    count and a ROCm GPU are needed.  Any other value of ``select`` or ``consensus_distance`` raises ValueError.
 
     ``decode``: "sample" (default) is the protocol above; ``beam_size`` is, as in the reference, the NUMBER OF TRIES of a clip --
     independent samples, not a beam.  "beam" replaces the tries by the ``beam_width`` final hypotheses of ONE beam search per clip
     (``SLMFT.forward(beam_width=W, num_return=W)``, dimx.beam; W in BATCHED_SAMPLE_COUNTS, default ``beam_size``): a deterministic
-    n-best list, best first, that goes through the same ``select`` ("likelihood" picks by the search's own scores, that is row 0).
+    n-best list, best first, that goes through the same ``select`` ("likelihood" picks by the search's own scores, that is row 0;
+    "consensus" picks the hypothesis the rest of the list agrees with most).
     ``beam_size``, ``batched_samples`` and the sampler filter are not consulted then.  It needs a ROCm GPU."""
     if decode not in ("sample", "beam"):
         raise ValueError("decode=%r: one of 'sample', 'beam'" % (decode,))
@@ -251,16 +266,19 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
         tries_kw = dict(n_samples=beam_size)
     if filter_logits_fn is not None or filter_kwargs:
         forward_kw = dict(forward_kw, filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs)
-    if select not in ("fd", "likelihood"):
-        raise ValueError("select=%r: one of 'fd', 'likelihood'" % (select,))
-    by_likelihood = select == "likelihood"
-    if by_likelihood:
+    if select not in ("fd", "likelihood", "consensus"):
+        raise ValueError("select=%r: one of 'fd', 'likelihood', 'consensus'" % (select,))
+    if consensus_distance not in ("fd", "l2"):
+        raise ValueError("consensus_distance=%r: one of 'fd', 'l2'" % (consensus_distance,))
+    by_likelihood, by_consensus = select == "likelihood", select == "consensus"
+    if by_likelihood or by_consensus:
         if torch.device(device).type != "cuda":
-            raise L.DimxError("evaluate_test_epoch(select='likelihood') runs on a ROCm GPU only (device %s): there is no CPU fallback; "
-                              "select='fd' with fd_backend='reference' or 'device' runs there" % (device,))
+            raise L.DimxError("evaluate_test_epoch(select='%s') runs on a ROCm GPU only (device %s): there is no CPU fallback; "
+                              "select='fd' with fd_backend='reference' or 'device' runs there" % (select, device))
         if not (batched_samples and beam_size in BATCHED_SAMPLE_COUNTS):
-            raise ValueError("evaluate_test_epoch(select='likelihood') scores the tries of one batched generation: beam_size must be "
-                             "one of %s with batched_samples (got %d)" % (BATCHED_SAMPLE_COUNTS, beam_size))
+            raise ValueError("evaluate_test_epoch(select='%s') %s the tries of one batched generation: beam_size must be "
+                             "one of %s with batched_samples (got %d)" % (select, "scores" if by_likelihood else "compares",
+                                                                          BATCHED_SAMPLE_COUNTS, beam_size))
         fd_backend = "hip"      # not consulted for the selection: the winners are handled where the HIP selection leaves its own
     assert fd_backend in ("reference", "device", "hip")
     if metrics is not None:
@@ -310,6 +328,12 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
                     y_preds_all.extend(_select_likelihood(tgt[lo:hi, 1:], y_preds, scores, [src_len[lo + j] - 1 for j in range(nl)],
                                                           world, device, B, **extra))
                     continue
+                if by_consensus:
+                    _, _, y_preds = model(sl[0], sl[1], sl[2], sl[3], mode="val", **tries_kw, **kw)
+                    extra = dict(metrics=metrics, x=src_s_v[lo:hi]) if metrics is not None else {}
+                    y_preds_all.extend(_select_consensus(tgt[lo:hi, 1:], y_preds, consensus_distance,
+                                                         [src_len[lo + j] - 1 for j in range(nl)], world, device, B, **extra))
+                    continue
                 if batched:
                     _, _, y_preds = model(sl[0], sl[1], sl[2], sl[3], mode="val", **tries_kw, **kw)
                 else:
@@ -336,7 +360,7 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
             pending = (futs, samples, lens, nl, tgt.shape[1] - 1, tgt.shape[2], B)
         if pending is not None:
             y_preds_all.extend(_select(pending, skip_degenerate, world, device))
-    _report_epoch(model, device, "evaluate_test_epoch", len(y_trues_all), None if by_likelihood else fd_backend)
+    _report_epoch(model, device, "evaluate_test_epoch", len(y_trues_all), None if by_likelihood or by_consensus else fd_backend)
     return y_trues_all, y_preds_all, x_all, data_ids_all
 
 

@@ -5,7 +5,7 @@ seq_len=T-N, ...)).  Selection and metrics stay over the whole clip.  Without th
 clips and weights.
 
     python examples/continue_s2s_pretrain.py --prompt-frames 30 [--clips 32] [--batch 8] [--beam 10] [--bf16] [--ckpt best_vico_causal.pt]
-                                            [--select {fd,likelihood}]
+                                            [--select {fd,likelihood,consensus}] [--consensus-distance {fd,l2}]
 
 --select likelihood keeps the continuation the model itself scores highest (the log-likelihood of its sampled tokens past the
 prompt) instead of the one nearest to the ground truth: beyond the prompt a deployed continuation has no ground truth to select with.
@@ -39,8 +39,11 @@ def main():
     ap.add_argument("--out", default="l2l_listener_continuations.pkl")
     ap.add_argument("--prompt-frames", type=int, default=30,
                     help="continue the first N ground-truth listener frames of every clip instead of starting from frame 0 alone")
-    ap.add_argument("--select", choices=("fd", "likelihood"), default="fd",
-                    help="best-of-N by Frechet distance to the ground truth (the reference's protocol) or by the model's own log-likelihood")
+    ap.add_argument("--select", choices=("fd", "likelihood", "consensus"), default="fd",
+                    help="best-of-N by Frechet distance to the ground truth (the reference's protocol), by the model's own log-likelihood, "
+                         "or by consensus: the try nearest to the clip's other tries (minimum Bayes risk; no ground truth either)")
+    ap.add_argument("--consensus-distance", choices=("fd", "l2"), default="fd",
+                    help="the distance between tries of --select consensus: the protocol's Frechet distance or the mean squared difference")
     ap.add_argument("--decode", choices=("sample", "beam"), default="sample",
                     help="the tries of a clip: --beam independent samples (the reference's protocol; its 'beam' is a number of tries) or "
                          "the final hypotheses of one beam search of --beam-width (deterministic)")
@@ -69,7 +72,8 @@ def main():
 
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, val_loader, device, beam_size=args.beam,
-                                                        prompt_frames=args.prompt_frames, select=args.select, decode=args.decode,
+                                                        prompt_frames=args.prompt_frames, select=args.select,
+                                                        consensus_distance=args.consensus_distance, decode=args.decode,
                                                         beam_width=args.beam_width, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))

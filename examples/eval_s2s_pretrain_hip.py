@@ -4,10 +4,13 @@ included (examples/test_s2s_pretrain.py is the reference's driver on its host pa
 checkpoint it runs on synthetic clips and weights.
 
     python examples/eval_s2s_pretrain_hip.py [--clips 32] [--batch 8] [--beam 10] [--bf16] [--ckpt best_vico_causal.pt] [--no-sid]
-                                            [--select {fd,likelihood}] [--out l2l_listener_predictions.pkl]
+                                            [--select {fd,likelihood,consensus}] [--consensus-distance {fd,l2}]
+                                            [--out l2l_listener_predictions.pkl]
 
 --select likelihood keeps, per clip, the try the model itself scores highest (its log-likelihood, csrc/seq_score.hip) instead of the
-try nearest to the ground truth: the selection a conversation without a recorded listener allows.  For either selection the
+try nearest to the ground truth: the selection a conversation without a recorded listener allows.  --select consensus keeps the
+try with the smallest total distance to the clip's other tries (minimum Bayes risk, csrc/consensus.hip): no ground truth either,
+and no preference for the modal, low-motion sequence.  For every selection the
 perplexity of the ground-truth listener codes over the epoch is printed (SLMFT.score, teacher-forced).
 """
 import argparse
@@ -39,8 +42,11 @@ def main():
     ap.add_argument("--ckpt", default="best_vico_causal.pt")
     ap.add_argument("--out", default="l2l_listener_predictions.pkl")
     ap.add_argument("--no-sid", action="store_true", help="leave out the two SID lines")
-    ap.add_argument("--select", choices=("fd", "likelihood"), default="fd",
-                    help="best-of-N by Frechet distance to the ground truth (the reference's protocol) or by the model's own log-likelihood")
+    ap.add_argument("--select", choices=("fd", "likelihood", "consensus"), default="fd",
+                    help="best-of-N by Frechet distance to the ground truth (the reference's protocol), by the model's own log-likelihood, "
+                         "or by consensus: the try nearest to the clip's other tries (minimum Bayes risk; no ground truth either)")
+    ap.add_argument("--consensus-distance", choices=("fd", "l2"), default="fd",
+                    help="the distance between tries of --select consensus: the protocol's Frechet distance or the mean squared difference")
     ap.add_argument("--decode", choices=("sample", "beam"), default="sample",
                     help="the tries of a clip: --beam independent samples (the reference's protocol; its 'beam' is a number of tries) or "
                          "the final hypotheses of one beam search of --beam-width (deterministic)")
@@ -66,7 +72,8 @@ def main():
     acc = ListenerMetrics(sid=not args.no_sid)    # SID on the GPU too (csrc/kmeans_sid.hip): no per-clip list is needed to print
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc,
-                                                        select=args.select, decode=args.decode, beam_width=args.beam_width, **sampler)
+                                                        select=args.select, consensus_distance=args.consensus_distance,
+                                                        decode=args.decode, beam_width=args.beam_width, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     parts = []

@@ -761,6 +761,34 @@ int dimx_op_seq_logprob(const float* logits, long row_stride, long step_stride, 
 int dimx_op_score_select(const double* score, const float* y_pred, long yp_clip_stride, long yp_sample_stride, long yp_frame_stride,
                          const int32_t* lens, const int32_t* tokens, long tok_row_stride, int B, int S, int L, int W, int n,
                          int32_t* win, uint8_t* ok, float* best, int32_t* best_tokens, void* stream);
+/* Consensus (minimum-Bayes-risk, medoid) best-of-S selection: per clip the try with the smallest total distance to the other
+ * S - 1 tries (csrc/consensus.hip; the definition is dimx/consensus.py).  No ground truth enters.  All pointers are device memory.
+ *   y_pred f32 [B, S, L, W], lens int32 [B], the window [c0, c0 + F): as dimx_op_fd_select (1 <= F <= 64, c0 + F <= W; frames
+ *       t >= lens[b] are never read).  S is any value >= 1, not only a batched sample count.
+ *   kind 0 (fd): dist[b, i, j] for i < j is the Frechet distance of dimx_op_fd_select with try i as its first operand (S_i = A A^T
+ *       is factorised once per try, M = A^T S_j A per pair; the r = min(F, n - 1) largest eigenvalues are kept; no clamp at 0).
+ *   kind 1 (l2): dist[b, i, j] for i < j is the mean over the valid frames and the window's columns of (x_i - x_j)^2, float64.
+ *   dist f64 [B, S, S] or NULL: dist[b, j, i] = dist[b, i, j] (the same bits), dist[b, i, i] = 0; NaN off the diagonal for a clip
+ *       with fewer than 2 valid frames
+ *   risk f64 [B, S]: risk[b, i] = sum over j != i of dist[b, i, j], in ascending j from zero
+ *   win int32 [B]: first minimum of the risks, NaN counting as +inf;  ok uint8 [B]: 0 when no risk of the clip is finite.  S = 1
+ *       gives risk 0, win 0, ok 1
+ *   best f32 [B, L, W] or NULL, tokens int32 (row b*S + s at tokens + (b*S + s)*tok_row_stride), best_tokens int32 [B, n_tok] or
+ *       NULL: the winner's rows and token row as dimx_op_score_select leaves them (zero / -100 for clips with ok = 0).  tokens may
+ *       be NULL when best_tokens is
+ *   workspace: dimx_op_consensus_select_ws_bytes(B, S, F, kind) bytes, 8-byte aligned.  After a call of kind 0 its last
+ *       (B*S + B*S*(S-1)/2) int32 hold the Jacobi sweeps of each try's factorisation [B, S] and of each pair [B, S*(S-1)/2] (pairs
+ *       in the order (0,1), (0,2), .., (1,2), ..; diagnostic; the loop is bounded at 30).
+ * Asynchronous on `stream`: three launches for kind 0 (try factorisations, pairs, pick), two for kind 1, no allocation, no host
+ * synchronisation, no atomics, fixed summation orders: repeated calls and identical tries give identical bits.  DIMX_ERR_ARG for F
+ * outside 1..64, a window that leaves the row, an unknown kind, B, S, L or W below 1, more than 2^31 - 1 pairs, a negative stride, a
+ * null required pointer, a short or misaligned workspace; nothing is enqueued then.  _ws_bytes returns 0 for such shapes. */
+size_t dimx_op_consensus_select_ws_bytes(int B, int S, int F, int kind);
+int dimx_op_consensus_select(const float* y_pred, long yp_clip_stride, long yp_sample_stride, long yp_frame_stride,
+                             const int32_t* lens, int B, int S, int L, int W, int c0, int F, int kind /* 0 = fd, 1 = l2 */,
+                             double* dist /* [B,S,S] or NULL */, double* risk /* [B,S] */, int32_t* win, uint8_t* ok,
+                             float* best /* [B,L,W] or NULL */, const int32_t* tokens, long tok_row_stride, int n_tok,
+                             int32_t* best_tokens /* or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 /* The two kernels of dimx_generate_beam on their own (csrc/beam.hip).  All pointers are device memory.
  * dimx_op_beam_step: logits f32 [B*W, 512], cum f64 [B*W], mode int32 [B] (0 live, 2 frozen, anything else forced with
  *   forced_tok[B], clamped to [0, 512); forced_tok may be NULL = token 0) -> parent int32 [B*W], token int32 [B*W], cum_out f64 [B*W]
