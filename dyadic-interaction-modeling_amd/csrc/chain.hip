@@ -631,7 +631,9 @@ __device__ __forceinline__ void layer_barrier(unsigned* ctr, unsigned target, un
         if (a.prof && threadIdx.x == 0) a.prof[blockIdx.x * 16 + (i)] = wall_clock64(); \
     } while (0)
 
-template <int NCB_SO, int NCB_CQ, int NCB_CO>
+// TAB0: the first layer's launch when its self attention reads K / V from the table over the token ids (decode_attn_body.hpp,
+// TAB) -- an instantiation of its own, not a branch around two inlined bodies: 13 waves per CU leave no register room for both
+template <int NCB_SO, int NCB_CQ, int NCB_CO, bool TAB0 = false>
 __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ float sm_mr[2 * kGroupRows];
@@ -663,7 +665,7 @@ __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerCha
         issue_panel_nw<AUX_PLAIN, 1>((const bf16*)a.g_so.W, a.g_so.ldw, n0, n0 + a.g_so.cols - 1, a.g_so.rows_pad, a.g_so.nkt, base + a.off_W1, 0,
                                      lane);
     } else if (has_clip) {
-        decode_attn_body<bf16, true, true, 1, kAttnWaves>(a.sa, clip, sc, a.sc_stride, nullptr, nullptr, nullptr);
+        decode_attn_body<bf16, true, true, 1, kAttnWaves, false, TAB0>(a.sa, clip, sc, a.sc_stride, nullptr, nullptr, nullptr);
     }
     LAYER_STAMP(1);
     target += kGroupCUs;
@@ -950,6 +952,18 @@ int launch_layer_chain(const LayerChainArgs& a0, hipStream_t s) {
                  "layer_chain: null operand");
     const size_t lds = layer_plan(a);
     DIMX_REQUIRE(lds <= kMaxDynLds, DIMX_ERR_ARG, "layer_chain: LDS plan %zu bytes", lds);
+    if (a.sa.tab) {   // the table form keeps its token ids in registers: the LDS plan is the cache form's
+        DIMX_REQUIRE(a.sa.hist && a.sa.hist_ld >= a.sa.Tmax && a.sa.Tmax >= 1 && a.sa.tab_rows >= 1 && a.sa.tab_ld % 8 == 0 &&
+                         a.sa.tab_koff % 8 == 0 && a.sa.tab_voff % 8 == 0 && a.sa.tab_koff >= 0 && a.sa.tab_voff >= 0 &&
+                         a.sa.tab_koff + kAttnWaves * 64 <= a.sa.tab_ld && a.sa.tab_voff + kAttnWaves * 64 <= a.sa.tab_ld &&
+                         (uintptr_t)a.sa.tab % 16 == 0,
+                     DIMX_ERR_ARG, "layer_chain: table form with rows of %d, K at %d, V at %d, history stride %d", a.sa.tab_ld, a.sa.tab_koff,
+                     a.sa.tab_voff, a.sa.hist_ld);
+        (void)hipFuncSetAttribute((const void*)xcd_layer_kernel<2, 1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
+        hipLaunchKernelGGL((xcd_layer_kernel<2, 1, 2, true>), dim3(8 * kGroupCUs), dim3(kLayerThreads), lds, s, a);
+        DIMX_HIP(hipGetLastError());
+        return DIMX_OK;
+    }
     (void)hipFuncSetAttribute((const void*)xcd_layer_kernel<2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
     hipLaunchKernelGGL((xcd_layer_kernel<2, 1, 2>), dim3(8 * kGroupCUs), dim3(kLayerThreads), lds, s, a);
     DIMX_HIP(hipGetLastError());

@@ -382,6 +382,12 @@ struct DecodeAttnArgs {
     const uint8_t* kmask;  // cross: [B, kmask_ld] optional
     int kmask_ld;
     float scale;
+    // self attention of the first decoder layer in its table form (tab != nullptr; decode_attn_body.hpp, TAB): the K / V row of
+    // position j is a row of a table over the token ids, picked by the row's token history, and no cache is read or written
+    const void* tab;       // [tab_rows, tab_ld] in the storage type: K of head h at tab_koff + h*64, V at tab_voff + h*64
+    int tab_ld, tab_koff, tab_voff, tab_rows;
+    const int32_t* hist;   // [B, hist_ld] the layer's input token of every position so far (hist_ld >= Tmax)
+    int hist_ld;
 };
 int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
 
@@ -535,6 +541,9 @@ struct SampleArgs {
     int prompt_div = 1;
     int32_t* epoch_rw = nullptr;
     SampleFilter filt;
+    // the first layer's token history [R, hist_ld]: position step + 1 takes the (clamped) token of this launch (needs step_dev)
+    int32_t* hist = nullptr;
+    int hist_ld = 0;
 };
 int launch_sample(const SampleArgs& a, hipStream_t s);
 // Beam search (beam.hip; the definition is dimx/beam.py).  One selection launch: rows clip * W + w of `logits` (split-K slabs, added
@@ -597,7 +606,9 @@ int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s);
 int launch_sum_slabs_rows(const float* slabs, int nslab, long slab_stride, float* table, int id0, int rows, int M, int N,
                           hipStream_t s);
 int launch_gather_start_rows(const float* table, int N, int rows, const int32_t* start, int start_div, float* out, int B,
-                             hipStream_t s, int start_ld = 1);
+                             hipStream_t s, int start_ld = 1, int32_t* hist = nullptr, int hist_ld = 0);
+// the K / V columns [col0, col0 + W) of that table as a bf16 image [rows][W] (the bits the decode cache append would store)
+int launch_kv0_image(const float* table, int ld, int rows, int col0, int W, void* image, hipStream_t s);
 // generate(): the per-group step counters = step0, done counters = 0, and temperature + seed next to them (read by the sampler)
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
                       hipStream_t s, int step0 = 0, float filter_a = 0.f, float filter_b = 0.f);

@@ -14,13 +14,14 @@
 namespace dimx {
 namespace {
 
-template <typename T, bool SELF, bool QF32, int NSPLIT>
+// TAB: the first layer's table form (decode_attn_body.hpp) -- K / V rows from the table over the token ids, no cache
+template <typename T, bool SELF, bool QF32, int NSPLIT, bool TAB = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const DecodeAttnArgs a) {
     constexpr int PPB = 4 / NSPLIT;  // (clip, head) pairs per block
     __shared__ float sc[PPB][kMaxKeys];
     __shared__ float red_m[4], red_l[4];
     __shared__ float red_acc[4][64];
-    decode_attn_body<T, SELF, QF32, NSPLIT, 4>(a, blockIdx.x, &sc[0][0], kMaxKeys, red_m, red_l, &red_acc[0][0]);
+    decode_attn_body<T, SELF, QF32, NSPLIT, 4, false, TAB>(a, blockIdx.x, &sc[0][0], kMaxKeys, red_m, red_l, &red_acc[0][0]);
 }
 
 // Multi-sample cross attention: SQ query rows (independent samples of the same clip) share one pass over
@@ -157,6 +158,14 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
     DIMX_REQUIRE(a.knew == nullptr || a.step != nullptr, DIMX_ERR_ARG, "decode_attn: self attention needs a step counter");
     DIMX_REQUIRE(a.Tmax <= kMaxKeys && a.n_keys <= kMaxKeys, DIMX_ERR_ARG, "decode_attn: more than %d keys", kMaxKeys);
     DIMX_REQUIRE(a.knew != nullptr || a.n_keys >= 1, DIMX_ERR_ARG, "decode_attn: cross attention over %d keys", a.n_keys);
+    if (a.tab) {
+        const int epc = a.dtype == DIMX_BF16 ? 8 : 4;
+        DIMX_REQUIRE(a.knew && a.q_f32 && a.hist && a.hist_ld >= a.Tmax && a.Tmax >= 1 && a.tab_rows >= 1, DIMX_ERR_ARG,
+                     "decode_attn: the table form is self attention on f32 slabs with a token history of at least Tmax entries per row");
+        DIMX_REQUIRE(a.tab_ld % epc == 0 && a.tab_koff % epc == 0 && a.tab_voff % epc == 0 && a.tab_koff >= 0 && a.tab_voff >= 0 &&
+                         a.tab_koff + a.H * 64 <= a.tab_ld && a.tab_voff + a.H * 64 <= a.tab_ld && (uintptr_t)a.tab % 16 == 0,
+                     DIMX_ERR_ARG, "decode_attn: table rows of %d with K at %d and V at %d", a.tab_ld, a.tab_koff, a.tab_voff);
+    }
     if (a.rows_per_clip > 1) {
         // multi-sample cross attention: a.B = clips, rows = B * rows_per_clip
         DIMX_REQUIRE(a.knew == nullptr, DIMX_ERR_ARG, "decode_attn: rows_per_clip applies to cross attention only");
@@ -211,13 +220,22 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
         else if (nsplit == 2) DA_LAUNCH(TT, SS, QQ, 2); \
         else DA_LAUNCH(TT, SS, QQ, 1);             \
     } while (0)
-    if (a.dtype == DIMX_BF16) {
+#define DA_TAB(TT)                                                                                  \
+    do {                                                                                            \
+        if (nsplit == 4) hipLaunchKernelGGL((decode_attn_kernel<TT, true, true, 4, true>), grid, block, 0, s, a);      \
+        else if (nsplit == 2) hipLaunchKernelGGL((decode_attn_kernel<TT, true, true, 2, true>), grid, block, 0, s, a); \
+        else hipLaunchKernelGGL((decode_attn_kernel<TT, true, true, 1, true>), grid, block, 0, s, a);                  \
+    } while (0)
+    if (a.tab) {
+        if (a.dtype == DIMX_BF16) DA_TAB(bf16); else DA_TAB(float);
+    } else if (a.dtype == DIMX_BF16) {
         if (a.q_f32) { if (self) DA_NS(bf16, true, true); else DA_NS(bf16, false, true); }
         else { if (self) DA_NS(bf16, true, false); else DA_NS(bf16, false, false); }
     } else {
         if (a.q_f32) { if (self) DA_NS(float, true, true); else DA_NS(float, false, true); }
         else { if (self) DA_NS(float, true, false); else DA_NS(float, false, false); }
     }
+#undef DA_TAB
 #undef DA_NS
 #undef DA_LAUNCH
     DIMX_HIP(hipGetLastError());

@@ -93,7 +93,14 @@ template <int EPC> __device__ __forceinline__ void load_f32_slabs(const float* p
 // block that take part (4 in decode_attn_kernel; 8 when a 512-thread launch shares its CUs with GEMM blocks, the fusion
 // probe of gemm.hip); the LDS arrays come from the caller: sc [NW / NSPLIT][sc_stride] scores, red_m / red_l [NW],
 // red_acc [NW][64].
-template <typename T, bool SELF, bool QF32, int NSPLIT, int NW, bool QSC1 = false>
+//
+// TAB (self attention of the FIRST decoder layer, decoders without positional embedding): that layer's k / v depend on the
+// input token alone, so the cached row of position j is row hist[b][j] of a table over the token ids (model.hip kv0 image: the
+// bits the cache append would have stored).  The rows come from that table -- about 1.5 MB, shared by every wave of the chip,
+// resident in each XCD's L2 -- through plain cache-allocating loads, and nothing is appended.  The token ids are read two
+// batches ahead of the rows they address, so the dependent hop stays off the key loop's critical path and two row batches
+// stay in flight as in the cache form.  Key order, fmaf chains, butterflies and softmax are the cache form's: same bits.
+template <typename T, bool SELF, bool QF32, int NSPLIT, int NW, bool QSC1 = false, bool TAB = false>
 __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int block_id, float* sc, int sc_stride, float* red_m,
                                                  float* red_l, float* red_acc) {
     constexpr int EPC = 16 / sizeof(T);
@@ -102,6 +109,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
     constexpr int U = 4;            // key groups per batch (8 measured no faster on MI355X)
     constexpr int KB = U * KPI;     // keys per batch
     constexpr int PPB = NW / NSPLIT; // (clip, head) pairs per block
+    static_assert(!TAB || SELF, "the table form is a self-attention form");
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pib = wave / NSPLIT, part = wave % NSPLIT;
@@ -113,6 +121,22 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
     // rows.  At step 0 the kernel is nothing but its dependent-load chain (step counter -> cache address -> q -> new k/v ->
     // store: 8.2 us per launch in round 2, four launches per decode step); issued here the three loads overlap the
     // counter read and each other.
+    const int jfirst = part * KB, jstep = NSPLIT * KB;  // this wave's key batches: jfirst, jfirst + jstep, ...
+    // TAB: ids of the positions of a key batch (any position of the history row may be read: the launcher checks hist_ld >= Tmax;
+    // entries at or past the step counter are stale, their rows are loaded like the cache form's clamped ones and not used)
+    auto load_ids = [&](int j0, int (&id)[U]) {
+        const int32_t* hrow = a.hist + (size_t)b * a.hist_ld;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * KPI + sub;
+            id[u] = hrow[j < a.Tmax ? j : a.Tmax - 1];
+        }
+    };
+    int ida[U] = {}, idb[U] = {}, idc[U] = {};
+    if constexpr (TAB) {
+        load_ids(jfirst, ida);
+        load_ids(jfirst + jstep, idb);
+    }
     float qv[EPC], knv[EPC], vnv[EPC];
     if (QSC1)  // one f32 slab, written by other CUs of this XCD during this launch
         load_f32_chunk_sc1<EPC>((const float*)a.q + (size_t)b * a.q_ld + h * 64 + ch * EPC, qv);
@@ -145,12 +169,26 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
             r[u] = ld_stream(base + (size_t)(j < n ? j : (n > 0 ? n - 1 : 0)) * 64);
         }
     };
-    const int jfirst = part * KB, jstep = NSPLIT * KB;  // this wave's key batches: jfirst, jfirst + jstep, ...
+    // TAB: the table rows of a batch of ids (an id outside the table cannot leave it: unsigned clamp to the last row)
+    const T* tk = (const T*)a.tab + a.tab_koff + h * 64 + ch * EPC;
+    const T* tv = (const T*)a.tab + a.tab_voff + h * 64 + ch * EPC;
+    auto load_tab = [&](const T* base, const int (&id)[U], uint4 (&r)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned t = (unsigned)id[u] < (unsigned)a.tab_rows ? (unsigned)id[u] : (unsigned)a.tab_rows - 1u;
+            r[u] = *(const uint4*)(base + (size_t)t * a.tab_ld);
+        }
+    };
 
     uint4 cur[U], nxt[U], vfirst[U];
     if (jfirst < n) {
-        load_batch(kc, jfirst, cur);
-        load_batch(vc, jfirst, vfirst);  // the first V batch rides along: short contexts are one latency hop shorter
+        if constexpr (TAB) {
+            load_tab(tk, ida, cur);
+            load_tab(tv, ida, vfirst);
+        } else {
+            load_batch(kc, jfirst, cur);
+            load_batch(vc, jfirst, vfirst);  // the first V batch rides along: short contexts are one latency hop shorter
+        }
     }
     // key mask -> additive bias in LDS (cross-attention): coalesced byte loads, once per launch
     if (masked) {
@@ -162,7 +200,12 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
     // ---- phase 1: scores
     float mx = kNegD;
     for (int j0 = jfirst; j0 < n; j0 += jstep) {
-        if (j0 + jstep < n) load_batch(kc, j0 + jstep, nxt);
+        if constexpr (TAB) {
+            if (j0 + 2 * jstep < n) load_ids(j0 + 2 * jstep, idc);
+            if (j0 + jstep < n) load_tab(tk, idb, nxt);
+        } else {
+            if (j0 + jstep < n) load_batch(kc, j0 + jstep, nxt);
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u * KPI + sub;
@@ -181,9 +224,16 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        if constexpr (TAB) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) idb[u] = idc[u];
+        }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) cur[u] = vfirst[u];
+    if constexpr (TAB) {  // the value pass walks the same positions: its second batch's ids go out before the softmax
+        if (jfirst + jstep < n) load_ids(jfirst + jstep, idb);
+    }
     int total = n;
     if (SELF) {
         float d = 0.f;
@@ -195,7 +245,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
         if (part == 0) {  // the new key belongs to the first wave of the pair
             if (lane == 0) s[n] = sv;
             mx = fmaxf(mx, sv);
-            if (active && sub == 0) {  // append to the cache for the following steps
+            if (!TAB && active && sub == 0) {  // append to the cache for the following steps (TAB: the table has the row)
                 store_chunk<T, EPC>((T*)a.kcache + ((size_t)(b * a.H + h) * a.Tmax + n) * 64 + ch * EPC, knv);
                 store_chunk<T, EPC>((T*)a.vcache + ((size_t)(b * a.H + h) * a.Tmax + n) * 64 + ch * EPC, vnv);
             }
@@ -230,7 +280,12 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
 #pragma unroll
     for (int e = 0; e < EPC; ++e) acc[e] = 0.f;
     for (int j0 = jfirst; j0 < n; j0 += jstep) {
-        if (j0 + jstep < n) load_batch(vc, j0 + jstep, nxt);
+        if constexpr (TAB) {
+            if (j0 + 2 * jstep < n) load_ids(j0 + 2 * jstep, idc);
+            if (j0 + jstep < n) load_tab(tv, idb, nxt);
+        } else {
+            if (j0 + jstep < n) load_batch(vc, j0 + jstep, nxt);
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u * KPI + sub;
@@ -242,6 +297,10 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        if constexpr (TAB) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) idb[u] = idc[u];
+        }
     }
     if (SELF && part == 0 && sub == 0) {
         const float p = s[n];

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                                                      const int32_t* __restrict__ prompt, int prompt_ld, int prompt_max,
                                                      const int32_t* __restrict__ prompt_len, int prompt_div,
                                                      int32_t* __restrict__ epoch_rw, float fa, float fb,
-                                                     uint8_t* __restrict__ keep_out) {
+                                                     uint8_t* __restrict__ keep_out, int32_t* __restrict__ hist, int hist_ld) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint64_t step = step_dev ? (uint64_t)*step_dev : step_host;
     if (dev_params) {  // generate(): temperature / seed live in device memory so that the captured step graph
@@ -361,6 +361,9 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
     }
     }  // !forced
     if (lane == 0) tokens[(size_t)row * tok_ld + (tok_col_from_step ? (int)step : 0)] = tok;
+    // the first layer's token history (its self attention in the table form, decode_attn_body.hpp): the next position's input
+    if (hist && lane == 0 && (int)step + 1 < hist_ld)
+        hist[(size_t)row * hist_ld + step + 1] = tok < 0 ? 0 : (tok >= kSampleVocab ? kSampleVocab - 1 : tok);
     if (x_next) {  // next step's decoder input: token embedding row (fused embed_step)
         const float2* src = (const float2*)(emb_table + (size_t)tok * emb_C);
         float2* dst = (float2*)(x_next + (size_t)row * emb_C);
@@ -523,13 +526,27 @@ __global__ __launch_bounds__(256) void sum_slabs_rows_kernel(const float* __rest
 // out[b, :] = table[clamp(start[b / start_div]), :]: step 0's first-layer q/k/v (the clamp of embed_step_kernel)
 __global__ __launch_bounds__(256) void gather_start_rows_kernel(const float* __restrict__ table, int N, int rows,
                                                                 const int32_t* __restrict__ start, int start_div,
-                                                                float* __restrict__ out, int start_ld) {
+                                                                float* __restrict__ out, int start_ld,
+                                                                int32_t* __restrict__ hist, int hist_ld) {
     const int b = blockIdx.x;
     int tok = start[(size_t)(b / start_div) * start_ld];
     tok = tok < 0 ? 0 : (tok >= rows ? rows - 1 : tok);
+    if (hist && threadIdx.x == 0) hist[(size_t)b * hist_ld] = tok;   // position 0 of the row's token history
     const float4* src = (const float4*)(table + (size_t)tok * N);
     float4* dst = (float4*)(out + (size_t)b * N);
     for (int i = threadIdx.x; i < N / 4; i += blockDim.x) dst[i] = src[i];
+}
+
+// image[r, :] = bf16(table[r, col0 : col0 + W]): the K / V columns of the first layer's q/k/v table in the operand type, rounded
+// as the cache append rounds them (store_chunk<bf16>: pack_bf16x2), so a row holds the bits the cache would hold
+__global__ __launch_bounds__(256) void kv0_image_kernel(const float* __restrict__ table, int ld, int col0, int W,
+                                                        uint32_t* __restrict__ image) {
+    const float2* src = (const float2*)(table + (size_t)blockIdx.x * ld + col0);
+    uint32_t* dst = image + (size_t)blockIdx.x * (W / 2);
+    for (int i = threadIdx.x; i < W / 2; i += blockDim.x) {
+        const float2 v = src[i];
+        dst[i] = pack_bf16x2(v.x, v.y);
+    }
 }
 
 // x[b*n + t, :] += pos[t, :] * scale   (TransformerWrapper abs. positional embedding of the legacy decoder,
@@ -697,6 +714,7 @@ int launch_sample(const SampleArgs& a, hipStream_t s) {
     DIMX_REQUIRE(!a.qkv0_table || (a.x_next && a.qkv0_out && !a.pos_table && a.emb_C / 2 <= 16 * 64 && a.qkv0_N % 4 == 0 && a.qkv0_N > 0 &&
                                    a.qkv0_N <= 12 * 256),
                  DIMX_ERR_ARG, "sample: the q/k/v table rides on the fused embedding (no positional table) and holds rows of k * 4 <= 3072");
+    DIMX_REQUIRE(!a.hist || (a.step_dev && a.hist_ld >= 1), DIMX_ERR_ARG, "sample: the token history needs the device step counter");
     DIMX_REQUIRE(!a.y_next || (a.x_next && a.y_gamma && a.emb_C % 128 == 0 && a.emb_C <= 2048), DIMX_ERR_ARG,
                  "sample: the fused pre-norm needs the fused embedding and a width of k * 128 <= 2048");
     const int wpb = a.R <= 1024 ? 1 : 4;  // one row per block for decode-sized batches: all CUs busy
@@ -709,7 +727,8 @@ int launch_sample(const SampleArgs& a, hipStream_t s) {
                        a.nslab < 1 ? 1 : a.nslab, a.slab_stride, a.logits_out, a.logits_out_ld, a.row0, a.rows_total, a.emb_table,
                        a.emb_C, a.x_next, a.step_rw, a.done_ctr, a.pos_table, a.pos_scale, a.pos_rows, a.dev_params, a.y_next,
                        a.y_gamma, a.y_dtype == DIMX_BF16 ? 1 : 0, a.qkv0_table, a.qkv0_out, a.qkv0_N, a.prompt, a.prompt_ld,
-                       a.prompt_max, a.prompt_len, a.prompt_div < 1 ? 1 : a.prompt_div, a.epoch_rw, filt.a, filt.b, filt.keep_out);
+                       a.prompt_max, a.prompt_len, a.prompt_div < 1 ? 1 : a.prompt_div, a.epoch_rw, filt.a, filt.b, filt.keep_out,
+                       a.hist, a.hist_ld);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
@@ -750,11 +769,19 @@ int launch_sum_slabs_rows(const float* slabs, int nslab, long slab_stride, float
 }
 
 int launch_gather_start_rows(const float* table, int N, int rows, const int32_t* start, int start_div, float* out, int B,
-                             hipStream_t s, int start_ld) {
-    DIMX_REQUIRE(table && start && out && B > 0 && N > 0 && N % 4 == 0 && rows > 0 && start_ld >= 1, DIMX_ERR_ARG,
+                             hipStream_t s, int start_ld, int32_t* hist, int hist_ld) {
+    DIMX_REQUIRE(table && start && out && B > 0 && N > 0 && N % 4 == 0 && rows > 0 && start_ld >= 1 && (!hist || hist_ld >= 1), DIMX_ERR_ARG,
                  "gather_start_rows: bad arguments");
     hipLaunchKernelGGL(gather_start_rows_kernel, dim3(B), dim3(256), 0, s, table, N, rows, start, start_div < 1 ? 1 : start_div, out,
-                       start_ld);
+                       start_ld, hist, hist_ld);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+int launch_kv0_image(const float* table, int ld, int rows, int col0, int W, void* image, hipStream_t s) {
+    DIMX_REQUIRE(table && image && rows > 0 && W > 0 && W % 2 == 0 && col0 >= 0 && col0 % 2 == 0 && ld % 2 == 0 && col0 + W <= ld, DIMX_ERR_ARG,
+                 "kv0_image: bad arguments");
+    hipLaunchKernelGGL(kv0_image_kernel, dim3(rows), dim3(256), 0, s, table, ld, col0, W, (uint32_t*)image);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

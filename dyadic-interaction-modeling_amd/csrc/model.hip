@@ -938,6 +938,7 @@ int dimx_create(dimx_handle* h, int device_id, const dimx_dims* dims, int numeri
     c->use_layer_chain = getenv("DIMX_NO_LAYER_CHAIN") ? 0 : 1;
     c->multi_tr = getenv("DIMX_NO_MULTI_TR") ? 0 : 1;
     c->use_qkv0_table = getenv("DIMX_NO_QKV0_TABLE") ? 0 : 1;
+    c->use_kv0_table = getenv("DIMX_NO_KV0_TABLE") ? 0 : 1;
     if (getenv("DIMX_LAYER_PROF")) {
         void* p = nullptr;
         if (hipMalloc(&p, (size_t)8 * 256 * 16 * 8) == hipSuccess) {
@@ -980,6 +981,7 @@ int dimx_destroy(dimx_handle h) {
     if (h->chain_stats_dev) (void)hipFree(h->chain_stats_dev);
     if (h->layer_prof_dev) (void)hipFree(h->layer_prof_dev);
     if (h->qkv0_table) (void)hipFree(h->qkv0_table);
+    if (h->kv0_image) (void)hipFree(h->kv0_image);
     if (h->chain_err_host) (void)hipHostFree(h->chain_err_host);
     free_packed(h);
     train_forget(h);   // the training plan cached for this handle (a later handle may reuse the address)
@@ -1118,6 +1120,7 @@ struct GenScratch {
     void* qcb;                 // several samples per clip, bf16: the cross-attention queries [rows, inner] in the operand type
     unsigned long long* kw;    // ... and the context mask as 64-bit validity words [clips][ceil(T / 64)] (attention_tr.hip)
     size_t kw_cap;
+    int32_t* hist;             // [rows][T] the first layer's input token of every position (its self attention's table form)
 };
 constexpr int kChainSites = 32;
 constexpr int kChainSiteWords = 8 * 16 + 8 * 32;  // arrival counters [8][16] + claim stamps [8][32]
@@ -1193,6 +1196,7 @@ static void plan_gen(const dimx_ctx* c, Arena& ar, int B, int T, GenScratch& s) 
     s.qcb = ar.take((size_t)B * inner * es);
     s.kw_cap = (size_t)B * ((T + 63) / 64);
     s.kw = (unsigned long long*)ar.take(s.kw_cap * 8);
+    s.hist = (int32_t*)ar.take((size_t)B * T * 4);
 }
 
 // Prompted generation (dimx_generate_prompted): the prompt of a call and the teacher-forced scratch of its prefill.
@@ -1949,6 +1953,16 @@ static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream
         DIMX_TRY(slab_gemm_rows(h, M, st, s.y, DD, h->dec.self_[0].qkv, s.qkv, s.st_qkv, &ns));
         DIMX_TRY(launch_sum_slabs_rows(s.qkv, ns, s.st_qkv, h->qkv0_table, r * M, V, M, N, st));
     }
+    // the K / V columns in the operand type for the first layer's self attention in the table form (bf16 mode; the f32 mode reads
+    // the table): same key and invalidation as the table, because it is rebuilt whenever the table is
+    if (h->use_kv0_table && h->at == DIMX_BF16) {
+        const int inner = N / 3;
+        if (!h->kv0_image) {
+            DIMX_HIP(hipMalloc(&h->kv0_image, (size_t)V * 2 * inner * sizeof(bf16)));
+            h->graph_valid = false;
+        }
+        DIMX_TRY(launch_kv0_image(h->qkv0_table, N, V, inner, 2 * inner, h->kv0_image, st));
+    }
     h->qkv0_M = M;
     h->qkv0_at = h->at;
     h->qkv0_epoch = h->dec_epoch;
@@ -1970,6 +1984,8 @@ struct GenCall {
     float* logits_out;
     const float* qkv0;   // the first layer's q/k/v table or nullptr
     const BeamCall* beam = nullptr;   // beam search: the selection and the cache reorder end the step in the sampler's place
+    const void* kv0 = nullptr;        // the first layer's K / V table (the bf16 image, or the q/k/v table itself in the f32 mode): its self
+                                      // attention reads rows of it through s.hist and keeps no cache; nullptr = the cache
 };
 
 // one decoder step for the clip group `grp` = rows [row0, row0 + B) of a batch of gc.Btot sequences:
@@ -2000,6 +2016,7 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
     s.f = boff(s0.f, (size_t)DD * dg.ff_mult * es);
     s.logits = s0.logits + (size_t)row0 * V;
     s.step = s0.step + 16 * grp;
+    s.hist = s0.hist + (size_t)row0 * T;
     // with S samples per clip, rows are samples (row = clip * S + sample); start / mask / cross K/V are per clip
     const int clip0 = row0 / S, nclip = B / S;
     // the first step's input is column step0 of the prompt; later steps inside a clip's prompt are forced by the sampler
@@ -2015,7 +2032,7 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
     if (embed_only) {  // step 0 input = embedding of the start token (later steps: fused into the sampler)
         DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, start, tokens, n, s.step, s.x, B, S, st, pos, pos_scale, pr.ld, pr.step0));
         if (gc.qkv0)   // the first layer's q/k/v of the start token: a table row into slab 0 (nothing reads y before the layer rewrites it)
-            DIMX_TRY(launch_gather_start_rows(gc.qkv0, 3 * inner, V, start, S, s.qkv, B, st, pr.ld));
+            DIMX_TRY(launch_gather_start_rows(gc.qkv0, 3 * inner, V, start, S, s.qkv, B, st, pr.ld, gc.kv0 ? s.hist : nullptr, T));
         else
             DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
         return DIMX_OK;
@@ -2127,6 +2144,14 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
         sa.H = heads;
         sa.step = s.step;
         sa.scale = scale;
+        if (l == 0 && gc.kv0) {   // K / V of position j = the table row of the row's j-th input token; no append
+            sa.tab = gc.kv0;
+            sa.tab_rows = V;
+            if (h->at == DIMX_BF16) { sa.tab_ld = 2 * inner; sa.tab_koff = 0; sa.tab_voff = inner; }
+            else { sa.tab_ld = 3 * inner; sa.tab_koff = inner; sa.tab_voff = 2 * inner; }
+            sa.hist = s.hist;
+            sa.hist_ld = T;
+        }
         memset(&ca, 0, sizeof(ca));
         ca.dtype = h->at;
         ca.q = s.qc;
@@ -2262,6 +2287,7 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
     sm.emb_table = h->dec.tok_emb; sm.emb_C = DD; sm.x_next = s.x; sm.pos_table = pos; sm.pos_scale = pos_scale; sm.pos_rows = n;
     sm.y_next = gc.qkv0 ? nullptr : s.y; sm.y_gamma = gc.qkv0 ? nullptr : h->dec.self_[0].ln_g; sm.y_dtype = h->at;
     sm.qkv0_table = gc.qkv0; sm.qkv0_out = s.qkv; sm.qkv0_N = 3 * inner;
+    if (gc.kv0) { sm.hist = s.hist; sm.hist_ld = T; }
     sm.prompt = forced; sm.prompt_ld = pr.ld; sm.prompt_max = pr.Pmax; sm.prompt_len = forced_len; sm.prompt_div = S;
     return launch_sample(sm, st);
 }
@@ -2367,6 +2393,13 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
         DIMX_TRY(qkv0_table_build(h, s, R, st, pr.step0));
         qkv0 = h->qkv0_table;
     }
+    // the first layer's self attention from the table: no beam search (the cache reorder would have to permute the history) and
+    // no prompt (a prefill fills the cache, not the history); any number of samples per clip: rows are samples
+    const void* kv0 = nullptr;
+    if (qkv0 && h->use_kv0_table && !beam && pr.step0 == 0 && pr.Pmax <= 1 && h->decg.dim_head == 64 && h->decg.num_tokens <= 512) {
+        kv0 = h->at == DIMX_BF16 ? h->kv0_image : (const void*)h->qkv0_table;
+        if (kv0) ++h->kv0_generations;
+    }
     if (pr.step0 > 0 && !keep_prefill) {
         // the prefill forms no logits: those columns of logits_out read zero
         if (logits_out)
@@ -2392,7 +2425,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
             DIMX_HIP(hipStreamWaitEvent(gs[g], h->ev_fork, 0));
         }
     }
-    const GenCall gc{cp, s, pr, ctx_mask, R, T, S, top_k, temperature, exp_noise, seed, tokens, logits_out, qkv0, beam};
+    const GenCall gc{cp, s, pr, ctx_mask, R, T, S, top_k, temperature, exp_noise, seed, tokens, logits_out, qkv0, beam, kv0};
     for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, gs[g], true));
     if (!h->use_graph) {
         for (int t = 0; t < nrun; ++t)
@@ -2401,7 +2434,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
         // greedy vs sampling is decided from the device-side parameters; only shapes and pointers key the graph.  The prompt's
         // pointers, row stride and width are kernel arguments of the sampler; P0 is not (the counters' start value and the
         // number of launches below), so a call with another P0 replays the same graphs.
-        GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0),
+        GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0) + (kv0 ? 8000 : 0),
                      pr.len, pr.ld, pr.Pmax, h->filter_kind, beam ? *beam : dimx::BeamCall{}};
         if (!(h->graph_valid && h->graph_key == key)) {
             h->graph_valid = false;
@@ -2655,6 +2688,7 @@ int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b) {
 
 int dimx_chain_faults(dimx_handle h) { return h ? h->chain_faults : 0; }
 int dimx_qkv0_table_builds(dimx_handle h) { return h ? h->qkv0_builds : 0; }
+int dimx_kv0_table_generations(dimx_handle h) { return h ? h->kv0_generations : 0; }
 
 int dimx_lstm_faults(dimx_handle h) { return h ? h->lstm_faults : 0; }
 

@@ -209,6 +209,14 @@ struct dimx_ctx {
     uint64_t qkv0_epoch = 0;            // dec_epoch the table was built at (0 = never)
     uint64_t dec_epoch = 1;             // bumped whenever the decoder's device weights are released or packed
     int qkv0_builds = 0;
+    // The first layer's self attention in its table form (decode_attn_body.hpp, TAB): that layer's cached K / V of a position are
+    // columns [inner, 3 * inner) of the table row of the position's input token, so the step reads them from the table through a
+    // per-row token history instead of appending to and streaming a per-clip cache (DIMX_NO_KV0_TABLE=1: the cache, for A/B runs).
+    // bf16 mode reads kv0_image, the table's K / V columns in the operand type, built and invalidated with the table; the f32 mode
+    // reads the table itself.  Generations without beam search and without a prompt prefill only.
+    int use_kv0_table = 1;
+    void* kv0_image = nullptr;          // [num_tokens][2 * heads * dim_head] bf16
+    int kv0_generations = 0;            // generate calls (regenerations included) that ran the table form
     // sampler generator window of a sharded batch (dimx_set_shard): this handle generates clips
     // [shard_row_off, shard_row_off + B) of shard_rows_total (0 = the call's own B)
     int shard_row_off = 0, shard_rows_total = 0;

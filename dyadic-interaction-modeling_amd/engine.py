@@ -392,6 +392,11 @@ class Engine:
         of decoder weights; 0 = generate() projects q/k/v at every step)."""
         return int(self.lib.dimx_qkv0_table_builds(self.h))
 
+    def kv0_table_generations(self):
+        """how many generations of this handle read the first decoder layer's self-attention K/V from the token table
+        instead of that layer's cache (0 = the cache: beam search, a prompt, no q/k/v table, or DIMX_NO_KV0_TABLE=1)."""
+        return int(self.lib.dimx_kv0_table_generations(self.h))
+
     def debug_chain_fault(self, n_calls=1):
         """test hook: the next n_calls generate() calls run their chain kernels on a non-bijective placement."""
         L.check(self.lib.dimx_debug_chain_fault(self.h, int(n_calls)), "dimx_debug_chain_fault")

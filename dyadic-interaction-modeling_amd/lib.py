@@ -118,6 +118,7 @@ SIGNATURES = {
                                         c_void_p]),
     "dimx_chain_faults": (c_int, [c_void_p]),
     "dimx_qkv0_table_builds": (c_int, [c_void_p]),
+    "dimx_kv0_table_generations": (c_int, [c_void_p]),
     "dimx_lstm_faults": (c_int, [c_void_p]),
     "dimx_mesh_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dimx_op_lstm_layer": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p),

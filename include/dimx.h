@@ -313,6 +313,11 @@ int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b);
  * changed; this counts the builds of a handle (0 = the table is not in use: other variants, several generation groups, or
  * DIMX_NO_QKV0_TABLE=1 in the environment at dimx_create). */
 int dimx_qkv0_table_builds(dimx_handle h);
+/* The same fact makes that layer's K/V cache redundant: the cached K / V of a position are columns of the table row of the
+ * position's input token.  With the table in use, generations without beam search and without a prompt read those rows through
+ * a per-row token history instead of appending to and streaming the layer's cache (same bits); this counts the generations of a
+ * handle that did (0 = the cache: see above, or DIMX_NO_KV0_TABLE=1 in the environment at dimx_create). */
+int dimx_kv0_table_generations(dimx_handle h);
 /* Test hook: the next n_calls dimx_generate calls launch their chain kernels with a deliberately non-bijective
  * (XCD, CU slot) placement (the blocks of every odd XCD claim the slots of its even neighbour). */
 int dimx_debug_chain_fault(dimx_handle h, int n_calls);
