@@ -956,6 +956,98 @@ def consensus_select_sweeps(device, B, S, F):
     return sw[:B * S].reshape(B, S).clone(), sw[B * S:].reshape(B, P).clone()
 
 
+_NS_WS = {}     # device index -> uint8 workspace of op_nn_search
+
+
+def op_pool_desc(x, lens, kind):
+    """Clip descriptors of the retrieval baselines (dimx_op_pool_desc, csrc/retrieval.hip; the definition is dimx.retrieval.pool):
+    x [N, T, D] f32 on a GPU, lens[i] = valid frames of clip i, kind "max" (per-dimension maximum over time: NN audio) or "mean"
+    (NN motion) -> (desc [N, D] f64, norm [N] f64).  The clip and frame strides are taken from the tensor (views such as
+    ``src[:, :, 56:]`` are passed as they are); only a feature stride other than 1 is copied.  Asynchronous on the current stream.
+    CPU tensors raise: there is no CPU fallback (dimx.retrieval.pool_batch is the host form)."""
+    from .retrieval import kind_index
+    k = kind_index(kind)
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise L.DimxError("op_pool_desc runs on the GPU only: x must be a CUDA tensor (no CPU fallback)")
+    if x.dim() != 3:
+        raise L.DimxError("op_pool_desc: x [N, T, D] expected, got %s" % (tuple(x.shape),))
+    dev = x.device
+    N, T, D = (int(v) for v in x.shape)
+    x = _f32_rows(x, D > 1)
+    lens_d = _lens_i32(lens, dev, N, "op_pool_desc")
+    desc = torch.empty(N, D, dtype=torch.float64, device=dev)
+    norm = torch.empty(N, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().dimx_op_pool_desc(ctypes.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), L.ptr(lens_d), N, T, D, k,
+                                           L.ptr(desc), L.ptr(norm), L.stream_ptr(dev)), "dimx_op_pool_desc")
+    return desc, norm
+
+
+def _f64_rows(t):
+    t = t if t.dtype == torch.float64 else t.double()
+    return t.contiguous() if t.shape[-1] > 1 and t.stride(-1) != 1 else t
+
+
+def op_nn_search(q_desc, q_norm, x_desc, x_norm, k, want_sim=False):
+    """Cosine k-nearest-neighbour search (dimx_op_nn_search, csrc/retrieval.hip; the definition is dimx.retrieval.search):
+    q_desc [Q, D] / q_norm [Q] and x_desc [N, D] / x_norm [N] f64 on one GPU, 1 <= k <= 16 -> (idx [Q, k] int32, sim [Q, k] f64,
+    found [Q] int32[, sim_all [Q, N] f64 with ``want_sim``]): the k library entries of largest similarity, ties to the smaller index;
+    NaN and similarities <= -1 are not eligible, unfilled slots hold -1 / NaN.  Row-strided views (``x_desc[5:30]``) are passed as
+    they are.  Asynchronous on the current stream.  CPU tensors raise: there is no CPU fallback."""
+    ts = (q_desc, q_norm, x_desc, x_norm)
+    if not all(torch.is_tensor(t) and t.is_cuda for t in ts):
+        raise L.DimxError("op_nn_search runs on the GPU only: descriptors and norms must be CUDA tensors (no CPU fallback)")
+    if q_desc.dim() != 2 or x_desc.dim() != 2 or q_desc.shape[1] != x_desc.shape[1] or q_norm.numel() != q_desc.shape[0] \
+            or x_norm.numel() != x_desc.shape[0] or any(t.device != q_desc.device for t in ts):
+        raise L.DimxError("op_nn_search: q_desc [Q, D], q_norm [Q], x_desc [N, D], x_norm [N] on one device expected, got %s"
+                          % ([tuple(t.shape) for t in ts],))
+    lib = L.load()
+    dev = q_desc.device
+    Q, D = (int(v) for v in q_desc.shape)
+    N, K = int(x_desc.shape[0]), int(k)
+    q_desc, x_desc = _f64_rows(q_desc), _f64_rows(x_desc)
+    q_norm, x_norm = q_norm.to(torch.float64).contiguous(), x_norm.to(torch.float64).contiguous()
+    idx = torch.empty(Q, max(K, 0), dtype=torch.int32, device=dev)
+    sim = torch.empty(Q, max(K, 0), dtype=torch.float64, device=dev)
+    found = torch.empty(Q, dtype=torch.int32, device=dev)
+    sim_all = torch.empty(Q, N, dtype=torch.float64, device=dev) if want_sim else None
+    ws = _workspace(_NS_WS, dev, int(lib.dimx_op_nn_search_ws_bytes(Q, N, D, K)))
+    with torch.cuda.device(dev):
+        L.check(lib.dimx_op_nn_search(ctypes.c_void_p(q_desc.data_ptr()), q_desc.stride(0) if Q > 1 else D, L.ptr(q_norm),
+                                      ctypes.c_void_p(x_desc.data_ptr()), x_desc.stride(0) if N > 1 else D, L.ptr(x_norm), Q, N, D, K,
+                                      L.ptr(idx), L.ptr(sim), L.ptr(found), L.ptr(sim_all), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                      L.stream_ptr(dev)), "dimx_op_nn_search")
+    return (idx, sim, found, sim_all) if want_sim else (idx, sim, found)
+
+
+def op_nn_gather(lib_seq, lib_lens, idx, q_lens, L=None):
+    """The retrieved sequences (dimx_op_nn_gather, csrc/retrieval.hip; the definition is dimx.retrieval.gather): lib_seq [N, Lmax, W]
+    f32 on a GPU, lib_lens [N], idx [Q, k] int32 (-1 = no entry), q_lens [Q], L = output frames (default Lmax) -> (out [Q, k, L, W]
+    f32, out_len [Q, k] int32) with out_len = min(q_lens[q], lib_lens[idx]) and zero rows at and beyond it.  Strided library views
+    (a slice of a longer or wider buffer) are passed as they are.  Asynchronous on the current stream.  CPU tensors raise."""
+    from . import lib as _L
+    if not (torch.is_tensor(lib_seq) and lib_seq.is_cuda and torch.is_tensor(idx) and idx.is_cuda and idx.device == lib_seq.device):
+        raise _L.DimxError("op_nn_gather runs on the GPU only: lib_seq / idx must be CUDA tensors on one device (no CPU fallback)")
+    if lib_seq.dim() != 3 or idx.dim() != 2:
+        raise _L.DimxError("op_nn_gather: lib_seq [N, Lmax, W] and idx [Q, k] expected, got %s and %s" % (tuple(lib_seq.shape),
+                                                                                                         tuple(idx.shape)))
+    dev = lib_seq.device
+    N, Lmax, W = (int(v) for v in lib_seq.shape)
+    Q, K = (int(v) for v in idx.shape)
+    Lo = Lmax if L is None else int(L)
+    lib_seq = _f32_rows(lib_seq, W > 1)
+    idx = idx.to(torch.int32).contiguous()
+    ll = _lens_i32(lib_lens, dev, N, "op_nn_gather(lib_lens)")
+    ql = _lens_i32(q_lens, dev, Q, "op_nn_gather(q_lens)")
+    out = torch.empty(Q, K, max(Lo, 0), W, dtype=torch.float32, device=dev)
+    out_len = torch.empty(Q, K, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _L.check(_L.load().dimx_op_nn_gather(_L.ptr(idx), ctypes.c_void_p(lib_seq.data_ptr()), lib_seq.stride(0), lib_seq.stride(1),
+                                             _L.ptr(ll), _L.ptr(ql), Q, K, N, Lmax, Lo, W, _L.ptr(out), _L.ptr(out_len),
+                                             _L.stream_ptr(dev)), "dimx_op_nn_gather")
+    return out, out_len
+
+
 _MM_WS = {}      # device index -> uint8 workspace of op_mesh_metrics
 _MM_MAPS = {}    # (device index, n_vert, sorted map bytes) -> MeshMap; keyed on content
 _MM_LENS = {}    # device index -> the host lens array of the last call (kept until the next call has replaced it)

@@ -186,6 +186,13 @@ SIGNATURES = {
     "dimx_op_consensus_select": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dimx_op_pool_desc": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
+    "dimx_op_nn_search_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dimx_op_nn_search": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dimx_op_nn_gather": (c_int, [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dimx_op_beam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dimx_op_beam_reorder": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,

@@ -364,6 +364,103 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     return y_trues_all, y_preds_all, x_all, data_ids_all
 
 
+def _baseline_features(library, src_s_v, src_s_a):
+    return src_s_a if library.kind == "audio" else src_s_v
+
+
+def fill_retrieval_library(library, loader, device):
+    """The training split into a dimx.retrieval.RetrievalLibrary, batch by batch in the protocol of evaluate_test_epoch: a clip is
+    described by all ``src_len`` frames of its audio features (kind "audio") or speaker motion ("motion"), and what it offers as a
+    prediction are the listener frames the protocol scores, ``tgt[:, 1:]`` cut to ``src_len - 1``.  Returns the library."""
+    if torch.device(device).type != "cuda":
+        raise L.DimxError("fill_retrieval_library runs on a ROCm GPU only (device %s): there is no CPU fallback" % (device,))
+    for batch in loader:
+        src_s_v, src_s_a, tgt, _, src_len, _ = _prepare(batch, device)
+        library.add(_baseline_features(library, src_s_v, src_s_a), tgt[:, 1:], src_len, listener_lens=[n - 1 for n in src_len])
+    return library
+
+
+def evaluate_baseline_epoch(library, loader, device, k=1, select=None, consensus_distance="fd", metrics=None, strict_len=False,
+                            random_seed=None, random_first=None):
+    """The retrieval baselines of reference code/baselines.py:30-103 over a test loader, with the batch and mask protocol of
+    evaluate_test_epoch: per test clip the listener sequence of the nearest training clip of ``library`` (a filled
+    dimx.retrieval.RetrievalLibrary: "audio" = NN audio, "motion" = NN motion), cut to the shorter of the two clips.  Returns
+    ``(y_trues, y_preds, x, data_ids)`` like evaluate_test_epoch, every array cut to the length of the clip's prediction.  A clip
+    for which no library entry is eligible (a zero descriptor) gets training clip 0, as the reference's ``best_index = 0`` does.
+
+    ``k`` = 1 is the reference baseline.  ``k`` > 1 retrieves the k nearest clips as an n-best list and hands it to the selectors of
+    evaluate_test_epoch: ``select="fd"`` (the oracle pick by Frechet distance to the ground truth, dimx.engine.op_fd_select) or
+    ``"consensus"`` (dimx.engine.op_consensus_select with ``consensus_distance``); the clip's length is then the minimum length of
+    its list, and a clip whose list has fewer than k entries raises ValueError.  ``select="likelihood"`` raises ValueError:
+    retrieved sequences have no model score.  ``random_seed`` (an int) replaces the search by the Random baseline: one host-drawn
+    training clip per test clip (``random_first=5`` draws from the first five, the checked-in script's leftover).
+    ``strict_len=True`` drops the clips whose retrieved clip has another length than their own, as the reference's ``== 64`` test
+    does.  ``metrics``: a dimx.metrics.ListenerMetrics, updated per batch with the device-resident predictions (it needs every kept
+    clip to have at least 2 frames).  GPU only: a CPU device raises lib.DimxError."""
+    if select == "likelihood":
+        raise ValueError("evaluate_baseline_epoch(select='likelihood'): retrieved sequences have no model score")
+    if select not in (None, "fd", "consensus"):
+        raise ValueError("select=%r: one of None, 'fd', 'consensus'" % (select,))
+    if consensus_distance not in ("fd", "l2"):
+        raise ValueError("consensus_distance=%r: one of 'fd', 'l2'" % (consensus_distance,))
+    k = int(k)
+    if k > 1 and select is None:
+        raise ValueError("evaluate_baseline_epoch(k=%d) needs select='fd' or 'consensus' to pick one of the k retrieved clips" % k)
+    if random_seed is not None and k != 1:
+        raise ValueError("evaluate_baseline_epoch(random_seed=...) draws one clip per test clip: k must be 1")
+    if torch.device(device).type != "cuda":
+        raise L.DimxError("evaluate_baseline_epoch runs on a ROCm GPU only (device %s): there is no CPU fallback; dimx.retrieval holds "
+                          "the host definition" % (device,))
+    from .engine import op_nn_gather
+    y_trues_all, y_preds_all, x_all, data_ids_all = [], [], [], []
+    _, _, lib_seq, lib_lens = library.buffers()
+    with torch.no_grad():
+        for n_batch, batch in enumerate(loader):
+            src_s_v, src_s_a, tgt, _, src_len, data_ids = _prepare(batch, device)
+            B, Lo = src_s_v.shape[0], tgt.shape[1] - 1
+            lens = [n - 1 for n in src_len]
+            y_true = tgt[:, 1:]
+            if random_seed is not None:
+                idx, y_list, out_len = library.query_random(B, lens, int(random_seed) + n_batch, first=random_first, L=Lo)
+            else:
+                idx, _, found, y_list, out_len = library.query(_baseline_features(library, src_s_v, src_s_a), src_len, k=k,
+                                                               out_lens=lens, L=Lo)
+                found_h = found.cpu().tolist()
+                if k > 1 and min(found_h) < k:
+                    raise ValueError("evaluate_baseline_epoch(k=%d): a clip of batch %d has only %d eligible library entries"
+                                     % (k, n_batch, min(found_h)))
+                if min(found_h) == 0:      # k = 1: the reference keeps best_index = 0 (dimx.retrieval.reference_index)
+                    idx = idx.clamp(min=0)
+                    y_list, out_len = op_nn_gather(lib_seq, lib_lens, idx, lens, L=Lo)
+            n_h = out_len.min(dim=1)[0].cpu().tolist()
+            keep = list(range(B))
+            if strict_len:
+                same = (lib_lens[idx.long()] == torch.tensor(lens, dtype=torch.int32, device=idx.device)[:, None]).all(dim=1).cpu().tolist()
+                keep = [j for j in keep if same[j]]
+            if not keep:
+                continue
+            if len(keep) < B:
+                kj = torch.tensor(keep, device=y_list.device)
+                y_true, y_list, x = y_true[kj], y_list[kj], src_s_v[kj]
+            else:
+                x = src_s_v
+            n_k = [n_h[j] for j in keep]
+            if k == 1:
+                ok = torch.ones(len(keep), dtype=torch.uint8, device=y_list.device)
+                best = _winners_to_host(y_true, y_list, ok, y_list[:, 0], n_k, 1, device, None, metrics, x)
+            elif select == "fd":
+                best = _select_hip(y_true, y_list, n_k, 1, device, None, metrics=metrics, x=x)
+            else:
+                best = _select_consensus(y_true, y_list, consensus_distance, n_k, 1, device, None, metrics=metrics, x=x)
+            yt, xs = y_true.cpu().numpy(), x.cpu().numpy()
+            for i, j in enumerate(keep):
+                y_trues_all.append(yt[i][:n_k[i]])
+                y_preds_all.append(best[i])
+                x_all.append(xs[i][:n_k[i]])
+                data_ids_all.append(data_ids[j])
+    return y_trues_all, y_preds_all, x_all, data_ids_all
+
+
 # speaker id of a BIWI recording, keyed on the part of the file name before the first '_' (reference code/x_engine_pt.py:286-301)
 BIWI_SPEAKER_IDS = {"F2": 0, "F3": 1, "F4": 2, "M3": 3, "M4": 4, "M5": 5, "F1": 6, "F5": 7, "F6": 8, "F7": 9, "F8": 10, "M1": 11,
                     "M2": 12, "M6": 13}

@@ -794,6 +794,42 @@ int dimx_op_consensus_select(const float* y_pred, long yp_clip_stride, long yp_s
                              double* dist /* [B,S,S] or NULL */, double* risk /* [B,S] */, int32_t* win, uint8_t* ok,
                              float* best /* [B,L,W] or NULL */, const int32_t* tokens, long tok_row_stride, int n_tok,
                              int32_t* best_tokens /* or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+/* Retrieval baselines (reference code/baselines.py:30-103: NN audio, NN motion, Random; csrc/retrieval.hip; the definition is
+ * dimx/retrieval.py).  All pointers are device memory.
+ * dimx_op_pool_desc: clip descriptors.
+ *   x f32: frame t of clip i holds D entries (element stride 1) at x + i*clip_stride + t*frame_stride (elements); lens int32 [N],
+ *       clamped to [0, T]: frames t >= lens[i] are never read
+ *   kind 0 (max): desc[i, d] = the maximum over the valid frames of the f32 values, widened (exact);  kind 1 (mean): the float64 sum
+ *       in frame order from zero, divided by the number of valid frames.  A clip without valid frames gets a zero descriptor
+ *   desc f64 [N, D] dense, norm f64 [N] = sqrt(sum of squares), summed in an order that depends on D alone
+ * dimx_op_nn_search: per query the K library entries of largest cosine similarity.
+ *   q_desc f64 (row q at q_desc + q*q_row_stride), q_norm f64 [Q], x_desc / x_row_stride / x_norm [N] likewise; 1 <= D <= 960
+ *   sim(q, i) = dot(q_desc[q], x_desc[i]) / (q_norm[q] * x_norm[i]) in float64; the dot product's summation order depends on D alone,
+ *       so the value is a function of the two descriptors and norms only, not of Q, N or the pair's position: identical entries tie
+ *       bit for bit and a search of a slice of the library returns the same bits for its entries.  A zero norm gives NaN (0 / 0)
+ *   idx int32 [Q, K], sim f64 [Q, K]: the K best entries under the total order (similarity descending, index ascending); an entry is
+ *       eligible only if its similarity is not NaN and is > -1 (the reference's strict '>' from best_sim = -1).  Unfilled slots hold
+ *       -1 / NaN;  found int32 [Q]: the filled slots.  (The reference keeps index 0 where found is 0.)
+ *   sim_out f64 [Q, N] or NULL: every similarity (tests and margins; the matrix is not materialised otherwise)
+ *   workspace: dimx_op_nn_search_ws_bytes(Q, N, D, K) bytes, 8-byte aligned: the per-(query, chunk of 256 entries) partial lists
+ *       [Q][chunks][K] f64 then [Q][chunks][K] int32.  _ws_bytes returns 0 for shapes the call refuses
+ * dimx_op_nn_gather: the retrieved sequences.
+ *   idx int32 [Q, K] (entries outside [0, N) = no entry), lib_seq f32: frame t of entry i holds W entries at lib_seq + i*clip_stride +
+ *       t*frame_stride; lib_lens int32 [N] clamped to [0, Lmax], q_lens int32 [Q] clamped to [0, L]
+ *   out f32 [Q, K, L, W], out_len int32 [Q, K]: out_len[q, s] = min(q_lens[q], lib_lens[idx[q, s]], L), the entry's first out_len
+ *       frames, zero at and beyond; no entry gives zeros and length 0.  Frames t >= out_len and entries >= N are never read
+ * Asynchronous on `stream`: one launch (pool, gather) or two (search: partial lists, merge), no allocation, no host synchronisation,
+ * no atomics, fixed summation orders (bit-reproducible).  DIMX_ERR_ARG for K outside 1..16, D < 1 (search: D > 960), N, Q, T, L, Lmax
+ * or W below 1, an unknown kind, a negative stride, a null operand (sim_out excepted), a misaligned workspace; DIMX_ERR_WORKSPACE for
+ * a workspace that is too small; nothing is enqueued then. */
+int dimx_op_pool_desc(const float* x, long clip_stride, long frame_stride, const int32_t* lens, int N, int T, int D,
+                      int kind /* 0 = max, 1 = mean */, double* desc, double* norm, void* stream);
+size_t dimx_op_nn_search_ws_bytes(int Q, int N, int D, int K);
+int dimx_op_nn_search(const double* q_desc, long q_row_stride, const double* q_norm, const double* x_desc, long x_row_stride,
+                      const double* x_norm, int Q, int N, int D, int K, int32_t* idx, double* sim, int32_t* found,
+                      double* sim_out /* [Q,N] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+int dimx_op_nn_gather(const int32_t* idx, const float* lib_seq, long clip_stride, long frame_stride, const int32_t* lib_lens,
+                      const int32_t* q_lens, int Q, int K, int N, int Lmax, int L, int W, float* out, int32_t* out_len, void* stream);
 /* The two kernels of dimx_generate_beam on their own (csrc/beam.hip).  All pointers are device memory.
  * dimx_op_beam_step: logits f32 [B*W, 512], cum f64 [B*W], mode int32 [B] (0 live, 2 frozen, anything else forced with
  *   forced_tok[B], clamped to [0, 512); forced_tok may be NULL = token 0) -> parent int32 [B*W], token int32 [B*W], cum_out f64 [B*W]
