@@ -1891,6 +1891,9 @@ int dimx_train_graph_stats(dimx_handle h, int64_t* out3) {
 int dimx_train_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int step, float max_norm, float* scratch, void* stream) {
     DIMX_REQUIRE(params && grads && exp_avg && exp_avg_sq && scratch && n > 0 && step >= 1, DIMX_ERR_ARG, "train_adamw: bad argument");
+    // adamw_kernel reads all four arenas as float4 (tr_grad_norm checks grads once more): refused before any launch
+    DIMX_REQUIRE(((uintptr_t)params % 16) == 0 && ((uintptr_t)grads % 16) == 0 && ((uintptr_t)exp_avg % 16) == 0 && ((uintptr_t)exp_avg_sq % 16) == 0,
+                 DIMX_ERR_ARG, "train_adamw: params, grads, exp_avg and exp_avg_sq must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     DIMX_TRY(tr_grad_norm(grads, (long)n, max_norm, scratch, scratch + 1024, st));
     return tr_adamw(params, grads, exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, step, scratch + 1024, st);
@@ -1914,6 +1917,68 @@ int dimx_op_train_attention(int mfma, const float* q, const float* k, const floa
     DIMX_TRY(tr_attn_fwd(t, q, k, v, o, lse, st));
     if (d_o) DIMX_TRY(tr_attn_bwd(t, q, k, v, o, d_o, lse, delta, dq, H * 64, dk, H * 64, dv, H * 64, st));
     return DIMX_OK;
+}
+
+}  // extern "C"
+
+// The row-count-dependent operators of the step alone (unit parity).  Each entry builds a Step over the caller's scratch and calls
+// the step's own helper (ln_adjoint, bias_adjoint, tr_prep_fused with the padding of fwd_operands / lin_bwd, tr_cross_entropy), so
+// rows per block, slab counts, chunk widths and the deferred multi_finish are planned by the code the training step runs.
+// walk(s): the helper calls, made twice -- without memory first (nothing launched: an undersized scratch is refused before a kernel
+// writes), then live.
+template <class Walk>
+static int op_with_pool(const char* tag, int at, float* scratch, size_t scratch_floats, hipStream_t st, Walk walk) {
+    DIMX_REQUIRE(scratch && ((uintptr_t)scratch % 256) == 0, DIMX_ERR_ARG, "%s: scratch must be 256-byte aligned", tag);
+    for (int pass = 0; pass < 2; ++pass) {
+        Arena ar(pass ? (void*)scratch : nullptr, pass ? scratch_floats * sizeof(float) : 0);
+        Step s(nullptr, nullptr, nullptr, nullptr, &ar, st, at, 1, 1, 1);
+        s.alloc_pool(scratch_floats);
+        DIMX_TRY(walk(s));
+        DIMX_TRY(flush_fin(s));
+        DIMX_REQUIRE(!s.pool_overflow, DIMX_ERR_WORKSPACE, "%s: scratch of %zu floats is too small", tag, scratch_floats);
+    }
+    return DIMX_OK;
+}
+
+extern "C" {
+
+int dimx_op_train_layernorm_bwd(const float* x, const float* gamma, const float* dy, float* dx, int accumulate, int M, int C, float* dgamma,
+                                float* dbeta, float* scratch, size_t scratch_floats, void* stream) {
+    DIMX_REQUIRE(x && gamma && dy && dx && dgamma && M >= 1, DIMX_ERR_ARG, "op_train_layernorm_bwd: bad argument");
+    DIMX_REQUIRE(C == 384 || C == 512 || C == 768 || C == 1152, DIMX_ERR_ARG, "op_train_layernorm_bwd: C=%d (384, 512, 768 or 1152)", C);
+    return op_with_pool("op_train_layernorm_bwd", DIMX_F32, scratch, scratch_floats, (hipStream_t)stream,
+                        [&](Step& s) { return ln_adjoint(s, x, gamma, dy, dx, accumulate ? 1 : 0, M, C, dgamma, dbeta); });
+}
+
+int dimx_op_train_colsum(const float* dy, int M, int C, float* out, float* scratch, size_t scratch_floats, void* stream) {
+    DIMX_REQUIRE(dy && out && M >= 1 && C >= 1, DIMX_ERR_ARG, "op_train_colsum: bad argument");
+    return op_with_pool("op_train_colsum", DIMX_F32, scratch, scratch_floats, (hipStream_t)stream,
+                        [&](Step& s) { return bias_adjoint(s, dy, out, M, C); });
+}
+
+int dimx_op_train_prep(int dtype, int mode, const float* src, int lds, const float* src2, int lds2, const float* gamma, const float* beta,
+                       int rows, int cols, void* o, size_t o_elems, void* t, size_t t_elems, float* colpart, size_t colpart_floats,
+                       int* dims3, void* stream) {
+    DIMX_REQUIRE(dtype == DIMX_F32 || dtype == DIMX_BF16, DIMX_ERR_ARG, "op_train_prep: operand type %d", dtype);
+    DIMX_REQUIRE(src && o && t && dims3 && rows >= 1 && cols >= 1 && lds >= cols, DIMX_ERR_ARG, "op_train_prep: bad argument");
+    Arena none(nullptr, 0);
+    Step s(nullptr, nullptr, nullptr, nullptr, &none, (hipStream_t)stream, dtype, 1, rows, rows);
+    const int Kp = pad_to(cols, s.bk), Mp = pad_to(rows, s.bk);   // fwd_operands: c.Kp / c.Mp; lin_bwd: Np / Mp
+    int n_part = ceil_div(rows, 32);                               // lin_bwd: the rows of bias_part
+    DIMX_REQUIRE(o_elems >= (size_t)rows * Kp && t_elems >= (size_t)cols * Mp && (!colpart || colpart_floats >= (size_t)n_part * cols),
+                 DIMX_ERR_WORKSPACE, "op_train_prep: o needs %zu, t %zu elements, colpart %zu floats", (size_t)rows * Kp, (size_t)cols * Mp,
+                 (size_t)n_part * cols);
+    DIMX_TRY(tr_prep_fused(dtype, mode, src, lds, src2, lds2, gamma, rows, cols, o, Kp, t, Mp, colpart, &n_part, s.st, beta));
+    dims3[0] = Kp;
+    dims3[1] = Mp;
+    dims3[2] = n_part;
+    return DIMX_OK;
+}
+
+int dimx_op_train_cross_entropy(const float* logits, const int32_t* targets, int R, float* row_loss, float* dlogits, float* loss_out2,
+                                void* stream) {
+    DIMX_REQUIRE(logits && targets && row_loss && dlogits && loss_out2 && R >= 1, DIMX_ERR_ARG, "op_train_cross_entropy: bad argument");
+    return tr_cross_entropy(logits, targets, row_loss, dlogits, R, loss_out2, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- VQ-VAE (stage 1)

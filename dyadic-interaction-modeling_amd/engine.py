@@ -581,6 +581,84 @@ def op_train_attention(q, k, v, scale, d_o=None, causal=False, kmask=None, kmask
     return (o, lse) if d_o is None else (o, lse, dq, dk, dv)
 
 
+def _nan(shape, device, dtype=torch.float32):
+    return torch.full(shape, float("nan"), dtype=dtype, device=device)
+
+
+def op_train_layernorm_bwd(x, gamma, dy, dx=None, with_beta=True):
+    """The training step's LayerNorm adjoint alone (ln_adjoint -> tr_layernorm_bwd_fused + tr_multi_finish): x, dy [M,C] f32,
+    gamma [C] -> (dx, d gamma, d beta or None).  ``dx`` given: the adjoint is ADDED to it in place (the residual stream's
+    accumulate form).  Outputs start as NaN, so an element the kernels leave unwritten shows."""
+    lib = L.load()
+    M, C = x.shape
+    dev = x.device
+    x, gamma, dy = x.float().contiguous(), gamma.float().contiguous(), dy.float().contiguous()
+    accumulate = dx is not None
+    if dx is None:
+        dx = _nan((M, C), dev)
+    dg = _nan((C,), dev)
+    db = _nan((C,), dev) if with_beta else None
+    scratch = _nan((2 * (600 * C + 64),), dev)
+    L.check(lib.dimx_op_train_layernorm_bwd(L.ptr(x), L.ptr(gamma), L.ptr(dy), L.ptr(dx), 1 if accumulate else 0, M, C, L.ptr(dg),
+                                            L.ptr(db), L.ptr(scratch), scratch.numel(), L.stream_ptr(dev)),
+            "dimx_op_train_layernorm_bwd")
+    return dx, dg, db
+
+
+def op_train_colsum(dy):
+    """Column sums of dy [M,C] f32 as the training step forms a bias gradient (bias_adjoint -> tr_colsum_partial +
+    tr_multi_finish) -> [C]."""
+    lib = L.load()
+    M, C = dy.shape
+    dy = dy.float().contiguous()
+    out = _nan((C,), dy.device)
+    scratch = _nan((32 * C + 64,), dy.device)
+    L.check(lib.dimx_op_train_colsum(L.ptr(dy), M, C, L.ptr(out), L.ptr(scratch), scratch.numel(), L.stream_ptr(dy.device)),
+            "dimx_op_train_colsum")
+    return out
+
+
+def op_train_prep(src, mode=0, bf16=False, src2=None, gamma=None, beta=None, colpart=False):
+    """The operand copy in front of every training GEMM (tr_prep_fused): src [rows,cols] f32, last dimension contiguous, any row
+    stride (a column slice of a wider buffer is passed as it lies) -> (o [rows,Kp], t [cols,Mp], colpart [n_part,cols] or None) in
+    the operand type; Kp / Mp are cols / rows padded to its k-tile.  Modes as in include/dimx.h.  Outputs start as NaN."""
+    lib = L.load()
+    assert src.dtype == torch.float32 and src.dim() == 2 and src.stride(1) == 1
+    assert src2 is None or (src2.dtype == torch.float32 and src2.stride(1) == 1 and src2.shape == src.shape)
+    rows, cols = src.shape
+    dev = src.device
+    dt = torch.bfloat16 if bf16 else torch.float32
+    bk = 64 if bf16 else 32
+    Kp, Mp, n_part = -(-cols // bk) * bk, -(-rows // bk) * bk, -(-rows // 32)
+    o, t = _nan((rows, Kp), dev, dt), _nan((cols, Mp), dev, dt)
+    part = _nan((n_part, cols), dev) if colpart else None
+    f = lambda v: None if v is None else v.float().contiguous()
+    gamma, beta = f(gamma), f(beta)
+    dims = (ctypes.c_int * 3)()
+    raw = lambda v: None if v is None else ctypes.c_void_p(v.data_ptr())      # row-strided views: L.ptr takes contiguous tensors only
+    L.check(lib.dimx_op_train_prep(L.BF16 if bf16 else L.F32, mode, raw(src), src.stride(0), raw(src2),
+                                   src2.stride(0) if src2 is not None else 0, L.ptr(gamma), L.ptr(beta), rows, cols, L.ptr(o), o.numel(),
+                                   L.ptr(t), t.numel(), L.ptr(part), part.numel() if colpart else 0, dims, L.stream_ptr(dev)),
+            "dimx_op_train_prep")
+    if tuple(dims) != (Kp, Mp, n_part):
+        raise L.DimxError("dimx_op_train_prep planned (Kp, Mp, n_part) = %s, expected %s" % (tuple(dims), (Kp, Mp, n_part)))
+    return o, t, part
+
+
+def op_train_cross_entropy(logits, targets):
+    """The training step's cross entropy (tr_cross_entropy): logits [R,512] f32, targets [R] (a value outside [0, 512), e.g. -100,
+    is ignored) -> (mean loss over the valid targets, 1 / max(count, 1), d logits [R,512])."""
+    lib = L.load()
+    R = logits.shape[0]
+    dev = logits.device
+    logits = logits.float().contiguous()
+    targets = targets.to(torch.int32).contiguous()
+    row_loss, dlogits, out2 = _nan((R,), dev), _nan((R, 512), dev), _nan((2,), dev)
+    L.check(lib.dimx_op_train_cross_entropy(L.ptr(logits), L.ptr(targets), R, L.ptr(row_loss), L.ptr(dlogits), L.ptr(out2),
+                                            L.stream_ptr(dev)), "dimx_op_train_cross_entropy")
+    return out2[0], out2[1], dlogits
+
+
 def op_sample(logits, top_k=52, temperature=1.0, noise=None, seed=0, step=0, filter_logits_fn=None, filter_kwargs=None,
               return_keep=False):
     """One sampler launch on logits [R,512].  ``filter_logits_fn`` / ``filter_kwargs`` as in Engine.generate (None: top-k with

@@ -116,6 +116,12 @@ SIGNATURES = {
     "dimx_op_train_attention": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "dimx_op_train_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
+    "dimx_op_train_colsum": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dimx_op_train_prep": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t,
+                                   c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_int), c_void_p]),
+    "dimx_op_train_cross_entropy": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dimx_chain_faults": (c_int, [c_void_p]),
     "dimx_qkv0_table_builds": (c_int, [c_void_p]),
     "dimx_kv0_table_generations": (c_int, [c_void_p]),

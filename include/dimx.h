@@ -478,7 +478,8 @@ int dimx_op_lstm_layer_bwd(int dtype, const float* x, int B, int T, int In, int 
                            float* const* dw_hh, float* const* db, int flags, int* faults_out, void* stream);
 /* Gradient clipping (torch.nn.utils.clip_grad_norm_, max_norm <= 0: none) + one torch.optim.AdamW step over a flat arena.
  * step: 1-based step count (bias correction).  scratch: >= 1026 device floats; scratch[1024] = gradient norm before clipping,
- * scratch[1025] = the clip coefficient applied. */
+ * scratch[1025] = the clip coefficient applied.  params, grads, exp_avg and exp_avg_sq must be 16-byte aligned (the kernels read
+ * them as float4): DIMX_ERR_ARG before any launch otherwise. */
 int dimx_train_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int step, float max_norm, float* scratch, void* stream);
 /* The attention operator of the training step alone (unit parity): q [B,Lq,H*64], k / v [B,Lk,H*64] f32, head h at columns
@@ -489,6 +490,29 @@ int dimx_train_adamw(float* params, const float* grads, float* exp_avg, float* e
 int dimx_op_train_attention(int mfma, const float* q, const float* k, const float* v, const float* d_o, const uint8_t* kmask,
                             const uint8_t* kmask2, int B, int H, int Lq, int Lk, int causal, float scale, float* o, float* lse,
                             float* delta, float* dq, float* dk, float* dv, void* stream);
+/* The operators of the training step whose launch plan depends on the row count alone (unit parity).  Each runs the step's own
+ * helper over caller scratch, so rows per block, slab counts, chunk widths and the deferred column-sum finish are the step's.
+ * scratch: 256-byte aligned device floats for the partial rows; too little is DIMX_ERR_WORKSPACE before any launch.
+ * dimx_op_train_layernorm_bwd: x, dy [M,C] f32, gamma [C], C in {384, 512, 768, 1152} -> dx [M,C] (accumulate: dx += ...), dgamma [C],
+ *   dbeta [C] (optional).  roundup4(ceil(M / 600)) rows per block; scratch >= 2 * (600 * C + 64) floats is always enough.
+ * dimx_op_train_colsum: dy [M,C] f32 -> out [C] = column sums (a bias gradient); 1 slab of rows below 256 rows, 32 from 256 up;
+ *   scratch >= 32 * C + 64 floats.
+ * dimx_op_train_prep: the operand copy in front of every training GEMM.  dtype: DIMX_F32 / DIMX_BF16 operand type; src [rows,cols]
+ *   f32 with row stride lds; mode 0 copy, 1 erf-GELU(src), 2 LayerNorm(src) * gamma (+ beta), 3 src * erf-GELU'(src2), 4 / 5 = 1 / 3
+ *   with tanh-GELU (src2 [rows,cols] with row stride lds2: modes 3 and 5).  Writes o [rows,Kp] and t [cols,Mp] (the transpose),
+ *   Kp / Mp = cols / rows padded to the operand type's k-tile (64 bf16, 32 f32) with exact zeros, and (optional) colpart
+ *   [n_part,cols] f32: row i = column sums of rows 32 i .. 32 i + 31 of what was cast.  dims3 (host) = {Kp, Mp, n_part}.  o_elems,
+ *   t_elems, colpart_floats: what the buffers hold; too little is DIMX_ERR_WORKSPACE.  cols, lds, lds2 multiples of 4, 16-byte aligned.
+ * dimx_op_train_cross_entropy: logits [R,512] f32, targets [R] int32 (outside [0, 512): ignored) -> row_loss [R], dlogits [R,512]
+ *   = d loss / d logits, loss_out2 = {mean loss over the valid targets, 1 / max(count, 1)} (no valid target: loss 0, dlogits 0). */
+int dimx_op_train_layernorm_bwd(const float* x, const float* gamma, const float* dy, float* dx, int accumulate, int M, int C, float* dgamma,
+                                float* dbeta, float* scratch, size_t scratch_floats, void* stream);
+int dimx_op_train_colsum(const float* dy, int M, int C, float* out, float* scratch, size_t scratch_floats, void* stream);
+int dimx_op_train_prep(int dtype, int mode, const float* src, int lds, const float* src2, int lds2, const float* gamma, const float* beta,
+                       int rows, int cols, void* o, size_t o_elems, void* t, size_t t_elems, float* colpart, size_t colpart_floats,
+                       int* dims3, void* stream);
+int dimx_op_train_cross_entropy(const float* logits, const int32_t* targets, int R, float* row_loss, float* dlogits, float* loss_out2,
+                                void* stream);
 
 /* ---- kernel-level entry points (unit parity tests) -------------------------------------- */
 

@@ -69,6 +69,47 @@ def test_gradients_match_autograd_over_the_oracle():
     assert checked > 100
 
 
+def test_batch_gradient_is_the_count_weighted_sum_of_its_groups_gradients_f64():
+    """The identity tests/test_gpu_train_rows.py rests on, checked on the oracle in float64: the loss is the mean cross entropy
+    over the valid targets and clips do not interact, so for a batch split into groups g with n_g valid targets
+        loss(batch) = sum_g n_g loss(g) / sum_g n_g,    grad(batch) = sum_g n_g grad(g) / sum_g n_g.
+    B = 4, T = 12, ragged (one clip of length 2), a kv_mask row per clip, against its two B = 2 halves: 1e-10 relative."""
+    sys.path.insert(0, ROOT)
+    import dimx  # noqa: F401
+    from dimx import prng, weights as W
+    from oracle import ref_cpu
+    B, T = 4, 12
+    v_s = torch.from_numpy(prng.normal(41, "split.vs", (B, T, 56))).double()
+    v_a = torch.from_numpy(prng.normal(41, "split.va", (B, T, 768))).double()
+    z = torch.from_numpy(prng.integers(41, "split.z", (B, T), 0, 512))
+    mask = torch.ones(B, T, dtype=torch.bool)
+    mask[1, 9:] = False
+    mask[2, 2:] = False
+    z = torch.where(mask, z, torch.full_like(z, -100))
+    kv = torch.from_numpy(prng.integers(41, "split.kv", (B, T - 1), 0, 8)) != 0
+    kv[:, 0] = True
+    sd0 = {k: (v.double() if v.dtype.is_floating_point else v) for k, v in W.synth_state_dict(W.slmft_spec(), 20260928).items()}
+
+    def run(lo, hi):
+        with torch.enable_grad():
+            sd = {k: v.detach().clone().requires_grad_(v.dtype.is_floating_point) for k, v in sd0.items()}
+            x_s = ref_cpu.slmft_forward_encoder(sd, v_s[lo:hi], mask[lo:hi])
+            ctx = ref_cpu.slmft_context(sd, x_s, v_a[lo:hi])
+            loss, _ = ref_cpu.ar_forward(sd, z[lo:hi], ctx, mask[lo:hi], kv[lo:hi])
+            loss.backward()
+        n = int((z[lo:hi, 1:] >= 0).sum())
+        return n, loss.detach(), {k: v.grad for k, v in sd.items() if v.grad is not None}
+
+    n_all, loss_all, g_all = run(0, 4)
+    parts = [run(0, 2), run(2, 4)]
+    assert loss_all.dtype == torch.float64 and n_all == sum(n for n, _, _ in parts) and min(n for n, _, _ in parts) > 0
+    assert abs(sum(n * l for n, l, _ in parts).item() / n_all - loss_all.item()) <= 1e-10 * abs(loss_all.item())
+    assert len(g_all) > 100 and all(set(g) == set(g_all) for _, _, g in parts)
+    for k, g in g_all.items():
+        s = sum(n * gp[k] for n, _, gp in parts) / n_all
+        assert (s - g).abs().max().item() <= 1e-10 * max(g.abs().max().item(), 1e-300), k
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
