@@ -388,6 +388,9 @@ struct DecodeAttnArgs {
     int tab_ld, tab_koff, tab_voff, tab_rows;
     const int32_t* hist;   // [B, hist_ld] the layer's input token of every position so far (hist_ld >= Tmax)
     int hist_ld;
+    // cross attention in its windowed (online) form (win != 0; decode_attn_body.hpp, WIN): the query of decode step t = *step sees
+    // the keys j < clamp(t + 2 + lookahead, 1, n_keys) only -- the speaker frames that exist when frame t + 1 is produced
+    int win, lookahead;
 };
 int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
 

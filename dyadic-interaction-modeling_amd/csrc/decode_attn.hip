@@ -15,20 +15,22 @@ namespace dimx {
 namespace {
 
 // TAB: the first layer's table form (decode_attn_body.hpp) -- K / V rows from the table over the token ids, no cache
-template <typename T, bool SELF, bool QF32, int NSPLIT, bool TAB = false>
+// WIN: the windowed cross form (decode_attn_body.hpp) -- the step counter bounds the keys
+template <typename T, bool SELF, bool QF32, int NSPLIT, bool TAB = false, bool WIN = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const DecodeAttnArgs a) {
     constexpr int PPB = 4 / NSPLIT;  // (clip, head) pairs per block
     __shared__ float sc[PPB][kMaxKeys];
     __shared__ float red_m[4], red_l[4];
     __shared__ float red_acc[4][64];
-    decode_attn_body<T, SELF, QF32, NSPLIT, 4, false, TAB>(a, blockIdx.x, &sc[0][0], kMaxKeys, red_m, red_l, &red_acc[0][0]);
+    decode_attn_body<T, SELF, QF32, NSPLIT, 4, false, TAB, WIN>(a, blockIdx.x, &sc[0][0], kMaxKeys, red_m, red_l, &red_acc[0][0]);
 }
 
 // Multi-sample cross attention: SQ query rows (independent samples of the same clip) share one pass over
 // the clip's K/V cache -- the reference's best-of-10 protocol (code/x_engine_pt.py:257) re-reads the same
 // context ten times; here the cache is streamed once per (clip, head) and every key is scored against all SQ
 // queries.  q/out rows of clip b are b*SQ .. b*SQ+SQ-1; scores live in LDS as [SQ][n].
-template <typename T, int SQ, bool QF32>
+// WIN: the windowed form, as in decode_attn_body -- n below is what the step may see; the launcher sizes the LDS for n_keys.
+template <typename T, int SQ, bool QF32, bool WIN = false>
 __global__ __launch_bounds__(256) void decode_attn_multi_kernel(const DecodeAttnArgs a) {
     constexpr int EPC = 16 / sizeof(T);
     constexpr int LPK = 64 / EPC;
@@ -42,7 +44,8 @@ __global__ __launch_bounds__(256) void decode_attn_multi_kernel(const DecodeAttn
     const bool active = pair < a.B * a.H;
     const int b = active ? pair / a.H : 0, h = active ? pair % a.H : 0;   // b = clip
     const int sub = lane / LPK, ch = lane % LPK;
-    const int n = a.n_keys;
+    int n = a.n_keys;
+    if constexpr (WIN) n = win_keys(*a.step, a.lookahead, a.n_keys);
     const int npad = (n + 3) & ~3;
     const float scale2 = a.scale * 1.4426950408889634f;
     const T* kc = (const T*)a.kcache + ((size_t)(b * a.H + h) * a.Tmax) * 64 + ch * EPC;
@@ -166,6 +169,8 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
                          a.tab_koff + a.H * 64 <= a.tab_ld && a.tab_voff + a.H * 64 <= a.tab_ld && (uintptr_t)a.tab % 16 == 0,
                      DIMX_ERR_ARG, "decode_attn: table rows of %d with K at %d and V at %d", a.tab_ld, a.tab_koff, a.tab_voff);
     }
+    DIMX_REQUIRE(!a.win || (a.knew == nullptr && a.step != nullptr && !a.tab), DIMX_ERR_ARG,
+                 "decode_attn: the windowed form is cross attention with a step counter");
     if (a.rows_per_clip > 1) {
         // multi-sample cross attention: a.B = clips, rows = B * rows_per_clip
         DIMX_REQUIRE(a.knew == nullptr, DIMX_ERR_ARG, "decode_attn: rows_per_clip applies to cross attention only");
@@ -175,11 +180,16 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
         DIMX_REQUIRE(lds <= 150 * 1024, DIMX_ERR_ARG, "decode_attn: %d samples x %d keys do not fit the LDS score buffer", S,
                      a.n_keys);
         dim3 grid(ceil_div(a.B * a.H, 4)), block(256);
-#define DM(TT, SS, QQ)                                                                                          \
+#define DM_W(TT, SS, QQ, WW)                                                                                    \
     do {                                                                                                        \
-        (void)hipFuncSetAttribute((const void*)decode_attn_multi_kernel<TT, SS, QQ>,                            \
+        (void)hipFuncSetAttribute((const void*)decode_attn_multi_kernel<TT, SS, QQ, WW>,                        \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
-        hipLaunchKernelGGL((decode_attn_multi_kernel<TT, SS, QQ>), grid, block, lds, s, a);                     \
+        hipLaunchKernelGGL((decode_attn_multi_kernel<TT, SS, QQ, WW>), grid, block, lds, s, a);                 \
+    } while (0)
+#define DM(TT, SS, QQ)                        \
+    do {                                      \
+        if (a.win) DM_W(TT, SS, QQ, true);    \
+        else DM_W(TT, SS, QQ, false);         \
     } while (0)
 #define DM_S(TT, QQ)                         \
     do {                                     \
@@ -198,6 +208,7 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
         else { if (a.q_f32) DM_S(float, true); else DM_S(float, false); }
 #undef DM_S
 #undef DM
+#undef DM_W
         DIMX_HIP(hipGetLastError());
         return DIMX_OK;
     }
@@ -226,8 +237,17 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
         else if (nsplit == 2) hipLaunchKernelGGL((decode_attn_kernel<TT, true, true, 2, true>), grid, block, 0, s, a); \
         else hipLaunchKernelGGL((decode_attn_kernel<TT, true, true, 1, true>), grid, block, 0, s, a);                  \
     } while (0)
+#define DA_WIN(TT, QQ)                                                                              \
+    do {                                                                                            \
+        if (nsplit == 4) hipLaunchKernelGGL((decode_attn_kernel<TT, false, QQ, 4, false, true>), grid, block, 0, s, a);      \
+        else if (nsplit == 2) hipLaunchKernelGGL((decode_attn_kernel<TT, false, QQ, 2, false, true>), grid, block, 0, s, a); \
+        else hipLaunchKernelGGL((decode_attn_kernel<TT, false, QQ, 1, false, true>), grid, block, 0, s, a);                  \
+    } while (0)
     if (a.tab) {
         if (a.dtype == DIMX_BF16) DA_TAB(bf16); else DA_TAB(float);
+    } else if (a.win) {
+        if (a.dtype == DIMX_BF16) { if (a.q_f32) DA_WIN(bf16, true); else DA_WIN(bf16, false); }
+        else { if (a.q_f32) DA_WIN(float, true); else DA_WIN(float, false); }
     } else if (a.dtype == DIMX_BF16) {
         if (a.q_f32) { if (self) DA_NS(bf16, true, true); else DA_NS(bf16, false, true); }
         else { if (self) DA_NS(bf16, true, false); else DA_NS(bf16, false, false); }
@@ -235,6 +255,7 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
         if (a.q_f32) { if (self) DA_NS(float, true, true); else DA_NS(float, false, true); }
         else { if (self) DA_NS(float, true, false); else DA_NS(float, false, false); }
     }
+#undef DA_WIN
 #undef DA_TAB
 #undef DA_NS
 #undef DA_LAUNCH

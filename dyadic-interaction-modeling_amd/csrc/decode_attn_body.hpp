@@ -15,6 +15,14 @@ template <typename P> __device__ __forceinline__ uint4 ld_stream(const P* p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// keys visible to the cross attention of decode step `step` under a look-ahead of `lookahead` frames: the step produces frame
+// step + 1, so frames 0 .. step + 1 + lookahead exist; never fewer than one key (no empty softmax), never more than n_keys.
+// In 64 bits: step + 2 + lookahead of two ints may not wrap.
+__device__ __forceinline__ int win_keys(int step, int lookahead, int n_keys) {
+    const long long v = (long long)step + 2 + lookahead;
+    return v < 1 ? 1 : (v > n_keys ? n_keys : (int)v);
+}
+
 constexpr int kMaxKeys = 2048;  // x-transformers max_seq_len of the decoder (code/seq2seq_pretrain.py:381)
 constexpr float kNegD = -3.0e38f;
 
@@ -100,7 +108,12 @@ template <int EPC> __device__ __forceinline__ void load_f32_slabs(const float* p
 // resident in each XCD's L2 -- through plain cache-allocating loads, and nothing is appended.  The token ids are read two
 // batches ahead of the rows they address, so the dependent hop stays off the key loop's critical path and two row batches
 // stay in flight as in the cache form.  Key order, fmaf chains, butterflies and softmax are the cache form's: same bits.
-template <typename T, bool SELF, bool QF32, int NSPLIT, int NW, bool QSC1 = false, bool TAB = false>
+//
+// WIN (cross attention of an online generation): the key count is not the fixed n_keys but what the step may see,
+// win_keys(step counter, lookahead, n_keys).  Everything below runs on that n as the plain cross form would with n_keys = n --
+// rows at or past n are never addressed (load_batch clamps to n - 1), the mask bias, the wave split and the sums are the same
+// code -- so the result has the bits of the plain form called with n_keys = n.
+template <typename T, bool SELF, bool QF32, int NSPLIT, int NW, bool QSC1 = false, bool TAB = false, bool WIN = false>
 __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int block_id, float* sc, int sc_stride, float* red_m,
                                                  float* red_l, float* red_acc) {
     constexpr int EPC = 16 / sizeof(T);
@@ -110,6 +123,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
     constexpr int KB = U * KPI;     // keys per batch
     constexpr int PPB = NW / NSPLIT; // (clip, head) pairs per block
     static_assert(!TAB || SELF, "the table form is a self-attention form");
+    static_assert(!WIN || !SELF, "the windowed form is a cross-attention form");
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pib = wave / NSPLIT, part = wave % NSPLIT;
@@ -155,6 +169,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
     }
     int n = a.n_keys;
     if (SELF) n = *a.step;  // keys already in the cache
+    if constexpr (WIN) n = win_keys(*a.step, a.lookahead, a.n_keys);
     const float scale2 = a.scale * 1.4426950408889634f;
 
     const T* kc = (const T*)a.kcache + ((size_t)(b * a.H + h) * a.Tmax) * 64 + ch * EPC;

@@ -2082,7 +2082,10 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
     };
     // round 5: the attention half of a layer as one XCD-local launch (chain.hip xcd_layer_kernel; DIMX_NO_LAYER_CHAIN=1: the four
     // launches, for A/B runs)
-    const bool layer_kernel = h->use_layer_chain && chain && defer && S == 1 && 4 * dg.depth + 1 <= kChainSites;
+    // Online generation: the cross attention's key count follows the step counter.  Only the one-query kernels of decode_attn.hip
+    // have that form, so the layer kernel and the MFMA multi-query route below are not taken.
+    const bool win = h->xwin_on != 0;
+    const bool layer_kernel = h->use_layer_chain && chain && defer && S == 1 && 4 * dg.depth + 1 <= kChainSites && !win;
     auto layer_args = [&](int l, const DecodeAttnArgs& sa, const DecodeAttnArgs& ca, LayerChainArgs& lc) -> bool {
         const Linear& so = h->dec.self_[l].out;
         const Linear& cq = h->dec.cross[l].q_ln;
@@ -2171,6 +2174,11 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
         ca.kmask = ctx_mask;
         ca.kmask_ld = T;
         ca.scale = scale;
+        if (win) {
+            ca.win = 1;
+            ca.lookahead = h->xwin_lookahead;
+            ca.step = s.step;
+        }
         if (defer && layer_kernel) {
             // round 5: self attention -> out-projection -> cross-q -> cross attention -> out-projection as ONE XCD-local launch
             LayerChainArgs lc;
@@ -2192,7 +2200,7 @@ static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, 
         } else {
             DIMX_TRY(slab_gemm(s.o, inner, h->dec.self_[l].out, s.xr, s0.st_xr, &pending));
             DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.cross[l].ln_g, B, DD, st));
-            if (gen_multi_tr(h, S)) {
+            if (gen_multi_tr(h, S) && !win) {
                 // round 6, best-of-N in one pass (code/x_engine_pt.py:257), bf16: the S queries of a clip against its context K/V on the
                 // matrix cores -- the prefill attention kernel with Lq = S (one 128-query item per (clip, head), K / V streamed once),
                 // queries in the operand type from a plain projection (rows = clips x S: no split-K needed).  The VALU multi-query
@@ -2435,7 +2443,7 @@ static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_pre
         // pointers, row stride and width are kernel arguments of the sampler; P0 is not (the counters' start value and the
         // number of launches below), so a call with another P0 replays the same graphs.
         GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0) + (kv0 ? 8000 : 0),
-                     pr.len, pr.ld, pr.Pmax, h->filter_kind, beam ? *beam : dimx::BeamCall{}};
+                     pr.len, pr.ld, pr.Pmax, h->filter_kind, beam ? *beam : dimx::BeamCall{}, h->xwin_on, h->xwin_on ? h->xwin_lookahead : 0};
         if (!(h->graph_valid && h->graph_key == key)) {
             h->graph_valid = false;
             if (!h->cap_stream) DIMX_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -2614,7 +2622,9 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
     DIMX_REQUIRE(P0 >= 1 && P0 <= Pmax, DIMX_ERR_ARG, "generate_prompted: need 1 <= P0 <= Pmax (P0=%d Pmax=%d)", P0, Pmax);
     DIMX_REQUIRE((flags & ~3) == 0, DIMX_ERR_ARG, "generate_prompted: unknown flags 0x%x", flags);
     const int S = n_samples < 1 ? 1 : n_samples;
-    const int p0 = (flags & 1) ? 1 : P0;   // bit 0: no prefill, the whole prompt goes through forced decode steps
+    // bit 0: no prefill, the whole prompt goes through forced decode steps.  Online generation (dimx_set_cross_lookahead) too: the
+    // prefill's attention has no per-query key bound, the decode step's has
+    const int p0 = ((flags & 1) || h->xwin_on) ? 1 : P0;
     // bit 1 is not part of the public flag set: tools/bench_prompt.py times the prefill stage alone with it
     DIMX_REQUIRE(!(flags & 2) || p0 >= 2, DIMX_ERR_ARG, "generate_prompted: flags bit 1 (the prefill stage alone) without a prefill (P0=%d, flags 0x%x)",
                  P0, flags);
@@ -2640,6 +2650,7 @@ int dimx_generate_beam(dimx_handle h, const int32_t* prompt, int ld_prompt, cons
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
     DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_beam: beam search is implemented for variant 0 (SLMFT) only; this handle is variant %d",
                  h->variant);
+    DIMX_REQUIRE(!h->xwin_on, DIMX_ERR_ARG, "generate_beam: not available while the cross-attention window is on (dimx_set_cross_lookahead)");
     DIMX_REQUIRE(dimx::beam_width_supported(beam_width), DIMX_ERR_ARG, "generate_beam: beam_width %d not in {1,2,4,5,8,10}", beam_width);
     DIMX_REQUIRE(prompt && scores && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
                  "generate_beam: need scores, 1 <= Pmax <= T - 1 and ld_prompt >= Pmax (Pmax=%d T=%d ld_prompt=%d)", Pmax, T, ld_prompt);
@@ -2683,6 +2694,22 @@ int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b) {
     h->filter_kind = kind;
     h->filter_a = kind == DIMX_FILTER_TOP_K ? 0.f : a;
     h->filter_b = kind == DIMX_FILTER_TOP_A ? b : 0.f;
+    return DIMX_OK;
+}
+
+int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_cross_lookahead: online generation is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    h->xwin_on = on ? 1 : 0;
+    h->xwin_lookahead = on ? lookahead : 0;
+    return DIMX_OK;
+}
+
+int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    if (on) *on = h->xwin_on;
+    if (lookahead) *lookahead = h->xwin_lookahead;
     return DIMX_OK;
 }
 
@@ -3017,9 +3044,10 @@ int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, v
 /* every decode-attention form dimx_generate launches (tests): q / knew / vnew as the cache type or as nslab f32 split-K slabs,
  * the self form reading this step's k / v at q + H*64 / q + 2*H*64 of each slab row, the cross form with a strided key mask,
  * several query rows per clip and a forced wave count */
-int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
-                           void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
-                           const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream) {
+static int op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
+                             void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
+                             const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, int win, int lookahead,
+                             void* stream) {
     const int S = rows_per_clip > 1 ? rows_per_clip : 1;
     DIMX_REQUIRE(B > 0 && H > 0 && Tmax > 0, DIMX_ERR_ARG, "op_decode_attn_ex: empty shape");
     DIMX_REQUIRE(nslab >= 1 && nslab <= 8 && (nslab == 1 || q_is_f32), DIMX_ERR_ARG, "op_decode_attn_ex: nslab=%d (1..8, > 1 for f32 q only)",
@@ -3061,7 +3089,28 @@ int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int
     a.rows_per_clip = rows_per_clip;
     a.scale = scale;
     a.force_nsplit = nsplit;
+    if (win) {
+        a.win = 1;
+        a.lookahead = lookahead;
+        a.step = step_dev;
+    }
     return launch_decode_attn(a, (hipStream_t)stream);
+}
+
+int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
+                           void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
+                           const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream) {
+    return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, self_attn, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, n_keys,
+                             kmask, kmask_ld, rows_per_clip, scale, nsplit, 0, 0, stream);
+}
+
+/* the windowed cross form: the keys j < clamp(*step_dev + 2 + lookahead, 1, n_keys) */
+int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
+                            void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys, const uint8_t* kmask,
+                            int kmask_ld, int rows_per_clip, float scale, int nsplit, int lookahead, void* stream) {
+    DIMX_REQUIRE(step_dev != nullptr, DIMX_ERR_ARG, "op_decode_attn_win: the windowed form needs a step counter");
+    return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, 0, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, n_keys, kmask,
+                             kmask_ld, rows_per_clip, scale, nsplit, 1, lookahead, stream);
 }
 
 size_t dimx_mlp_fused_packed_bytes(int C, int F) { return mlp_fused_packed_bytes(C, F); }

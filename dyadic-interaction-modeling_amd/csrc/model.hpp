@@ -131,8 +131,9 @@ struct GraphKey {
     int ld_prompt, Pmax;
     int filter_kind;          // the sampler kernel's instantiation; the filter's real-valued parameters live in device memory
     BeamCall beam;            // beam search: the selection / reorder kernels' buffers, all null = the sampler ends the step
+    int xwin_on, xwin_lookahead;   // online generation (dimx_set_cross_lookahead): other launches, and the look-ahead is a kernel argument
     bool operator==(const GraphKey& o) const {
-        return beam == o.beam && groups == o.groups && filter_kind == o.filter_kind && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
+        return xwin_on == o.xwin_on && xwin_lookahead == o.xwin_lookahead && beam == o.beam && groups == o.groups && filter_kind == o.filter_kind && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
                noise == o.noise && seed == o.seed && start == o.start && mask == o.mask && tokens == o.tokens &&
                logits_out == o.logits_out;
     }
@@ -223,6 +224,9 @@ struct dimx_ctx {
     // sampler filter of generate (dimx_set_sampler_filter): kind 0 = the call's top_k
     int filter_kind = 0;
     float filter_a = 0.f, filter_b = 0.f;
+    // online generation (dimx_set_cross_lookahead): decode step t's cross attention sees the context rows
+    // j < clamp(t + 2 + lookahead, 1, T) only; off = every row, as the reference generates
+    int xwin_on = 0, xwin_lookahead = 0;
     dimx::MeshHead mesh;                // handles created with dimx_dims.mesh_dim > 0
     int lstm_faults = 0;                // LSTM layers whose group kernel reported a fault and that were rerun on the safe path
     int spk_embed_rows = 0;             // rows of speaker_embed.weight as last loaded (the host applies it in inference; the

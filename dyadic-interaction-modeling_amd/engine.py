@@ -240,9 +240,22 @@ class Engine:
         around a call with ``filter_logits_fn``; an invalid setting raises and leaves the previous one in force."""
         L.check(self.lib.dimx_set_sampler_filter(self.h, int(kind), float(a), float(b)), "dimx_set_sampler_filter")
 
+    def set_cross_lookahead(self, lookahead=None):
+        """Online generation (dimx_set_cross_lookahead; the definition is dimx.online): with an integer ``lookahead`` L the cross
+        attention of decode step t sees the context rows j < clamp(t + 2 + L, 1, T) only; None switches the window off (every
+        row, the reference's behaviour).  Holds for this engine's generate calls until it is set again."""
+        L.check(self.lib.dimx_set_cross_lookahead(self.h, 0 if lookahead is None else 1, 0 if lookahead is None else int(lookahead)),
+                "dimx_set_cross_lookahead")
+
+    def cross_lookahead(self):
+        """The engine's cross-attention window: the look-ahead, or None while it is off."""
+        on, la = ctypes.c_int(0), ctypes.c_int(0)
+        L.check(self.lib.dimx_cross_lookahead(self.h, ctypes.byref(on), ctypes.byref(la)), "dimx_cross_lookahead")
+        return la.value if on.value else None
+
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
                  n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False, filter_logits_fn=None,
-                 filter_kwargs=None, return_scores=False):
+                 filter_kwargs=None, return_scores=False, lookahead=None):
         """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
 
         ``return_scores``: the return value gains a trailing dimx.scoring.SeqScores (score f64, count int32, both [B*S]): the
@@ -261,7 +274,18 @@ class Engine:
         Pmax when ``prompt_len`` is None, else 1); the context must have been built with ``prompt_frames >= prefill`` (a
         workspace grown in between invalidates it).  ``no_prefill``: the whole prompt goes through forced decode steps.
         Returned tokens keep their shape: column c is position c+1, columns < plen-1 repeat the prompt; with
-        ``return_logits`` the columns < P0-1 are zero."""
+        ``return_logits`` the columns < P0-1 are zero.
+
+        ``lookahead``: online generation for this call (``set_cross_lookahead``; the previous setting is restored afterwards).
+        None leaves the engine's setting as it is.  With the window on, a prompt is never prefilled (as ``no_prefill``)."""
+        if lookahead is not None:
+            prev = self.cross_lookahead()
+            self.set_cross_lookahead(lookahead)
+            try:
+                return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt, prompt_len,
+                                     prefill, no_prefill, filter_logits_fn, filter_kwargs, return_scores)
+            finally:
+                self.set_cross_lookahead(prev)
         if filter_logits_fn is not None or filter_kwargs:
             kind, top_k, fa, fb = sampling.resolve(filter_logits_fn, filter_kwargs, top_k)
             if kind != 0:
@@ -324,6 +348,7 @@ class Engine:
                                                 ws, wsb, self._s()), "dimx_generate_prompted")
         plen = None
         if return_scores:    # the library's clamp (include/dimx.h): prompt_len into [P0, Pmax] (no prefill: P0 = 1), no prompt_len = Pmax
+            no_prefill = no_prefill or self.cross_lookahead() is not None
             plen = prompt_len.clamp(1 if no_prefill else P0, Pmax) if prompt_len is not None \
                 else torch.full((B,), Pmax, dtype=torch.int32, device=self.device)
         return self._generated(tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores)
@@ -750,11 +775,13 @@ def op_decode_attn(q, kcache, vcache, n_keys, scale, kmask=None, nsplit=0):
 
 
 def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None, kmask_ld=None, rows_per_clip=1, nsplit=0,
-                      q_f32=None):
+                      q_f32=None, lookahead=None):
     """Every form of the decode step's attention as dimx_generate launches it (include/dimx.h dimx_op_decode_attn_ex).
     q: [R, q_ld] or f32 split-K slabs [nslab, R, q_ld] (R = B * rows_per_clip); kcache / vcache [B, H, Tmax, 64] (f32 or bf16).
     step (int32 device scalar) selects the self form: q's rows hold q | k | v, k / v are appended at *step; otherwise the cross
-    form over n_keys keys with an optional kmask [B, kmask_ld] (uint8).  q_f32: q holds f32 slabs (default: q is f32)."""
+    form over n_keys keys with an optional kmask [B, kmask_ld] (uint8).  q_f32: q holds f32 slabs (default: q is f32).
+    lookahead (int): the windowed cross form of an online generation (dimx_op_decode_attn_win) -- step is then the decode step
+    counter and the keys are j < dimx.online.visible(*step, lookahead, n_keys)."""
     lib = L.load()
     B, H, Tmax, _ = kcache.shape
     bf = kcache.dtype == torch.bfloat16
@@ -764,11 +791,16 @@ def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None,
         q_f32 = q.dtype == torch.float32
     S = rows_per_clip if rows_per_clip > 1 else 1
     out = torch.empty(R, H * 64, dtype=kcache.dtype, device=q.device)
+    kld = kmask_ld if kmask_ld is not None else (kmask.shape[1] if kmask is not None else 0)
+    if lookahead is not None:
+        L.check(lib.dimx_op_decode_attn_win(L.BF16 if bf else L.F32, L.ptr(qs), q_ld, 1 if q_f32 else 0, nslab, qs.stride(0),
+                                            L.ptr(kcache), L.ptr(vcache), L.ptr(out), H * 64, B, H, Tmax, L.ptr(step), n_keys,
+                                            L.ptr(kmask), kld, S, float(scale), nsplit, int(lookahead), L.stream_ptr(q.device)),
+                "dimx_op_decode_attn_win")
+        return out
     L.check(lib.dimx_op_decode_attn_ex(L.BF16 if bf else L.F32, L.ptr(qs), q_ld, 1 if q_f32 else 0, nslab, qs.stride(0),
                                        1 if step is not None else 0, L.ptr(kcache), L.ptr(vcache), L.ptr(out), H * 64, B, H, Tmax,
-                                       L.ptr(step), n_keys, L.ptr(kmask),
-                                       kmask_ld if kmask_ld is not None else (kmask.shape[1] if kmask is not None else 0),
-                                       S, float(scale), nsplit, L.stream_ptr(q.device)),
+                                       L.ptr(step), n_keys, L.ptr(kmask), kld, S, float(scale), nsplit, L.stream_ptr(q.device)),
             "dimx_op_decode_attn_ex")
     return out
 

@@ -61,6 +61,8 @@ SIGNATURES = {
                                     c_void_p]),
     "dimx_set_shard": (c_int, [c_void_p, c_int, c_int]),
     "dimx_set_sampler_filter": (c_int, [c_void_p, c_int, c_float, c_float]),
+    "dimx_set_cross_lookahead": (c_int, [c_void_p, c_int, c_int]),
+    "dimx_cross_lookahead": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "dimx_encode_ctx": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
     "dimx_legacy_speaker_features": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
@@ -152,6 +154,9 @@ SIGNATURES = {
     "dimx_op_decode_attn_ex": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_int, c_void_p, c_void_p, c_void_p,
                                        c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int,
                                        c_void_p]),
+    "dimx_op_decode_attn_win": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int,
+                                        c_int, c_void_p]),
     "dimx_op_mlp_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dimx_mlp_fused_packed_bytes": (c_size_t, [c_int, c_int]),
     "dimx_mlp_fused_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),

@@ -153,7 +153,7 @@ class SLMFT(_EngineOwner):
     @torch.no_grad()
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
                         seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False, beam_width=0):
+                        filter_kwargs=None, return_scores=False, beam_width=0, lookahead=None):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -172,9 +172,15 @@ class SLMFT(_EngineOwner):
 
         ``beam_width`` W >= 1 (mode 'val'): beam search instead of sampling (Engine.generate_beam; ``n_samples`` must be W, the
         sampler's arguments are not used): tokens [B*W, T-1], whole hypotheses, row b*W the best; the SeqScores are the search's
-        own running scores and the number of scored columns."""
+        own running scores and the number of scored columns.
+
+        ``lookahead`` L (mode 'val', no beam search): online generation (dimx.online) -- the step that produces frame t+1 sees the
+        speaker frames below clamp(t + 2 + L, 1, T) only; a prompt then runs through forced decode steps instead of a prefill.
+        None: the whole clip is visible, as in the reference."""
         if beam_width and (mode != "val" or int(n_samples) != int(beam_width)):
             raise ValueError("beam_width applies to mode='val' with n_samples == beam_width")
+        if lookahead is not None and (mode != "val" or beam_width):
+            raise ValueError("lookahead applies to mode='val' without beam search")
         if return_scores and mode != "val":
             raise ValueError("return_scores applies to mode='val' (SLMFT.score is the teacher-forced form)")
         prompt_frames = _check_prompt_frames(prompt_frames, z_l.shape[1])
@@ -210,10 +216,12 @@ class SLMFT(_EngineOwner):
         if prompt_frames > 1:
             out = eng.generate(None, m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
                                prompt=z_l[:, :prompt_frames], prompt_len=plen, prefill=p0,
-                               filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores)
+                               filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
+                               lookahead=lookahead)
         else:
             out = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
-                               filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores)
+                               filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
+                               lookahead=lookahead)
         if return_scores:
             return 0.0, out[0].long(), out[1]
         return 0.0, out.long()
@@ -287,7 +295,7 @@ class SLMFT(_EngineOwner):
     def forward(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                 return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                filter_kwargs=None, return_scores=False, beam_width=None, num_return=1):
+                filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
@@ -305,7 +313,13 @@ class SLMFT(_EngineOwner):
         ``beam_width`` W in {1, 2, 4, 5, 8, 10} (mode 'val'): beam search (dimx.beam, ``Engine.generate_beam``) instead of sampling --
         deterministic, ``noise`` / ``greedy`` / ``seed`` / ``temperature`` / the filter / ``n_samples`` are not used.  ``num_return``
         = 1: the best hypothesis, shapes as without the argument; ``num_return`` = W: all W, best first, shapes as with
-        ``n_samples=W`` (pred [B,W,T-1,56]).  With ``return_scores`` the SeqScores hold the search's own scores."""
+        ``n_samples=W`` (pred [B,W,T-1,56]).  With ``return_scores`` the SeqScores hold the search's own scores.
+
+        ``lookahead`` L (mode 'val', no beam search): online generation (dimx.online; ``forward_decoder``) -- the listener token of
+        frame t+1 is drawn from the speaker frames below clamp(t + 2 + L, 1, T).  The tokens are causal in the speaker; ``pred`` is
+        still the VQ decoder's rendering of the whole token sequence."""
+        if lookahead is not None and (mode != "val" or beam_width is not None):
+            raise ValueError("lookahead applies to mode='val' without beam search")
         if beam_width is not None:
             if mode != "val" or int(num_return) not in (1, int(beam_width)):
                 raise ValueError("beam_width applies to mode='val' with num_return 1 or beam_width")
@@ -323,13 +337,13 @@ class SLMFT(_EngineOwner):
                                         batch_row_offset=batch_row_offset, return_tokens=return_tokens,
                                         n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths,
                                         filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
-                                        beam_width=beam_width, num_return=num_return)
+                                        beam_width=beam_width, num_return=num_return, lookahead=lookahead)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                         return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False, beam_width=None, num_return=1):
+                        filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -349,7 +363,7 @@ class SLMFT(_EngineOwner):
                                                          kv_mask=kv_mask, greedy=greedy, seed=seed, temperature=temperature,
                                                          n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
                                                          filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs,
-                                                         return_scores=return_scores, beam_width=W)
+                                                         return_scores=return_scores, beam_width=W, lookahead=lookahead)
         finally:
             eng.set_shard(0, 0)
         if W and int(num_return) == 1:    # the best hypothesis is row 0 of its clip
@@ -378,11 +392,15 @@ class SLMFT(_EngineOwner):
 
 
     @torch.no_grad()
-    def score(self, v_speaker, v_listener, v_audio, mask, z_l=None):
+    def score(self, v_speaker, v_listener, v_audio, mask, z_l=None, lookahead=None):
         """Teacher-forced log-likelihood of the clip's own listener codes (``forward_vq`` of ``v_listener``) or of given codes
         ``z_l`` [B,T] under the model: one ``decode_tf`` pass with NO random key mask, then dimx_op_seq_logprob on its logits with the
         tokens ``z_l[:, 1:]`` over the columns inside each clip's length -> dimx.scoring.SeqScores [B] (score f64, count int32).
-        ``dimx.scoring.perplexity`` of it is the model's perplexity on these codes."""
+        ``dimx.scoring.perplexity`` of it is the model's perplexity on these codes.
+
+        ``lookahead`` L: the same log-likelihood under online visibility (dimx.online) -- position t+1 is predicted from the
+        speaker frames below clamp(t + 2 + L, 1, T).  The logits then come from a generation whose every token is forced to ``z_l``
+        (a prompt of T-1 tokens through decode steps, no prefill), scored over the same columns."""
         from .engine import op_seq_logprob
         from .scoring import scored_columns
         with self.engine_pinned():
@@ -392,8 +410,13 @@ class SLMFT(_EngineOwner):
                 _, z_l = self.forward_vq(v_speaker, v_listener, mask, with_speaker=False)
             m8 = self._mask8(mask)
             T = mask.shape[1]
-            self._build_context(eng, None, v_speaker, v_audio, m8, False)
-            logits, _, _ = eng.decode_tf(z_l, m8, None)
+            if lookahead is not None:
+                self._build_context(eng, None, v_speaker, v_audio, m8, True)
+                _, logits = eng.generate(None, m8, T, 0.0, 52, None, 0, return_logits=True, prompt=z_l[:, :T - 1], prefill=1,
+                                         no_prefill=True, lookahead=lookahead)
+            else:
+                self._build_context(eng, None, v_speaker, v_audio, m8, False)
+                logits, _, _ = eng.decode_tf(z_l, m8, None)
             first, last = scored_columns(T, T - 1, mask.sum(1, dtype=torch.int32))
             return op_seq_logprob(logits, z_l[:, 1:], first, last)
 

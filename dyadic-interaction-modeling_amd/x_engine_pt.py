@@ -197,7 +197,7 @@ def _select(pending, skip_degenerate, world, device):
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
-                        select="fd", decode="sample", beam_width=None, consensus_distance="fd", **forward_kw):
+                        select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -251,9 +251,17 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     (``SLMFT.forward(beam_width=W, num_return=W)``, dimx.beam; W in BATCHED_SAMPLE_COUNTS, default ``beam_size``): a deterministic
     n-best list, best first, that goes through the same ``select`` ("likelihood" picks by the search's own scores, that is row 0;
     "consensus" picks the hypothesis the rest of the list agrees with most).
-    ``beam_size``, ``batched_samples`` and the sampler filter are not consulted then.  It needs a ROCm GPU."""
+    ``beam_size``, ``batched_samples`` and the sampler filter are not consulted then.  It needs a ROCm GPU.
+
+    ``lookahead`` L: every generation is an online one (dimx.online, ``SLMFT.forward(lookahead=L)``): the listener token of frame
+    t+1 is drawn from the speaker frames below clamp(t + 2 + L, 1, T).  Selection, metrics and the returned lists are unchanged.
+    None (default) is the reference's offline protocol.  Not with ``decode="beam"`` (ValueError)."""
     if decode not in ("sample", "beam"):
         raise ValueError("decode=%r: one of 'sample', 'beam'" % (decode,))
+    if lookahead is not None:
+        if decode == "beam":
+            raise ValueError("evaluate_test_epoch(lookahead=...) applies to decode='sample': beam search has no online form")
+        forward_kw = dict(forward_kw, lookahead=int(lookahead))
     if decode == "beam":
         beam_size = int(beam_width if beam_width is not None else beam_size)
         if beam_size not in BATCHED_SAMPLE_COUNTS:

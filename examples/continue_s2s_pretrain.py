@@ -48,6 +48,9 @@ def main():
                     help="the tries of a clip: --beam independent samples (the reference's protocol; its 'beam' is a number of tries) or "
                          "the final hypotheses of one beam search of --beam-width (deterministic)")
     ap.add_argument("--beam-width", type=int, default=None, help="hypotheses of --decode beam (1 < W <= 10; default: --beam)")
+    ap.add_argument("--lookahead", type=int, default=None,
+                    help="online generation: the token of frame t+1 is drawn from the speaker frames below t + 2 + L (0: up to the frame being "
+                         "produced, < 0: a reaction delay, > 0: a look-ahead buffer; default: the whole clip is visible, as in the reference)")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -74,7 +77,7 @@ def main():
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, val_loader, device, beam_size=args.beam,
                                                         prompt_frames=args.prompt_frames, select=args.select,
                                                         consensus_distance=args.consensus_distance, decode=args.decode,
-                                                        beam_width=args.beam_width, **sampler)
+                                                        beam_width=args.beam_width, lookahead=args.lookahead, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     print_metrics(y_true, y_pred, x)

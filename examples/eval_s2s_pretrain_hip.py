@@ -12,6 +12,9 @@ try nearest to the ground truth: the selection a conversation without a recorded
 try with the smallest total distance to the clip's other tries (minimum Bayes risk, csrc/consensus.hip): no ground truth either,
 and no preference for the modal, low-motion sequence.  For every selection the
 perplexity of the ground-truth listener codes over the epoch is printed (SLMFT.score, teacher-forced).
+
+--lookahead L generates online (dimx.online): the listener token of frame t+1 is drawn from the speaker frames below t + 2 + L only.
+The perplexity of the ground-truth codes under that visibility is then printed next to the offline one.
 """
 import argparse
 import os
@@ -51,6 +54,9 @@ def main():
                     help="the tries of a clip: --beam independent samples (the reference's protocol; its 'beam' is a number of tries) or "
                          "the final hypotheses of one beam search of --beam-width (deterministic)")
     ap.add_argument("--beam-width", type=int, default=None, help="hypotheses of --decode beam (1 < W <= 10; default: --beam)")
+    ap.add_argument("--lookahead", type=int, default=None,
+                    help="online generation: the token of frame t+1 is drawn from the speaker frames below t + 2 + L (0: up to the frame being "
+                         "produced, < 0: a reaction delay, > 0: a look-ahead buffer; default: the whole clip is visible, as in the reference)")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -73,15 +79,21 @@ def main():
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc,
                                                         select=args.select, consensus_distance=args.consensus_distance,
-                                                        decode=args.decode, beam_width=args.beam_width, **sampler)
+                                                        decode=args.decode, beam_width=args.beam_width, lookahead=args.lookahead, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
-    parts = []
+    parts, parts_online = [], []
     for batch in dataset["valid"]:      # teacher-forced: what the model thinks of the ground-truth listener codes
         src_s_v, src_s_a, tgt, mask, _, _ = _prepare(batch, device)
         parts.append(model.score(src_s_v, tgt, src_s_a, mask))
+        if args.lookahead is not None:  # the same codes with the speaker's future withheld
+            parts_online.append(model.score(src_s_v, tgt, src_s_a, mask, lookahead=args.lookahead))
     gt = SeqScores(torch.cat([p.score for p in parts]), torch.cat([p.count for p in parts]))
     print("perplexity of the ground-truth listener codes: %.3f over %d tokens" % (perplexity(gt), int(gt.count.sum())))
+    if parts_online:
+        on = SeqScores(torch.cat([p.score for p in parts_online]), torch.cat([p.count for p in parts_online]))
+        print("perplexity of the ground-truth listener codes, online with lookahead %d: %.3f (offline %.3f)"
+              % (args.lookahead, perplexity(on), perplexity(gt)))
     t0 = time.time()
     acc.print()
     print("metrics printed in %.3f s" % (time.time() - t0))

@@ -198,7 +198,8 @@ int dimx_legacy_speaker_features(dimx_handle h, const float* v_speaker, const ui
 /* Teacher-forced decoder pass.  z_l [B,T] int32 (-100 = ignore), ctx_mask [B,T] uint8,
  * kv_mask [B,T-1] uint8 keep-mask for self-attention keys (NULL = keep all).
  * logits [B,T-1,512] f32; row_loss (optional) [B,T-1] f32 = per-position cross entropy (0 where the
- * target is -100); argmax_tok (optional) [B,T-1] int32. */
+ * target is -100); argmax_tok (optional) [B,T-1] int32.
+ * dimx_set_cross_lookahead does not apply here: every position attends over the whole (masked) context. */
 int dimx_decode_tf(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, const uint8_t* kv_mask,
                    int B, int T, float* logits, float* row_loss, int32_t* argmax_tok, void* ws,
                    size_t ws_bytes, void* stream);
@@ -242,7 +243,9 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
  * dimx_workspace_bytes_samples, and it does not shrink as P0 grows; 0 = shape not supported).  The prefill's teacher-forced scratch
  * is sized for the WHOLE batch, B x (P0-1) rows, behind the generation scratch (no clip chunks); a smaller workspace returns
  * DIMX_ERR_WORKSPACE before anything is launched.  Chain faults are answered as in dimx_generate (below); the regeneration keeps
- * the prefilled cache prefix. */
+ * the prefilled cache prefix.
+ * Online generation (dimx_set_cross_lookahead, on): there is no prefill -- the call behaves as with flags bit 0 whatever P0 is, so
+ * that every prompt position's cross attention runs under its own key bound; the columns < P0-1 of logits_out then hold logits. */
 size_t dimx_workspace_bytes_prompt(dimx_handle h, int B, int T, int n_samples, int P0);
 int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
                            const uint8_t* ctx_mask, int B, int T, int n_samples, float temperature, int top_k,
@@ -307,6 +310,28 @@ typedef enum {
  * thres < 0, min_p outside [0, 1], min_p_pow or min_p_ratio < 0.  a and b reach the sampler through device memory: another
  * value replays the captured step graph, another kind captures a new one. */
 int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b);
+
+/* Online generation: decode steps see only the speaker frames that exist so far.  Handle state, like the sampler filter; variant
+ * 0 (SLMFT) only, a handle of variant 1 or 2 returns DIMX_ERR_ARG.  With on != 0, step t of clip b (it consumes the token at
+ * position t and produces position t+1, as in dimx_generate_prompted) attends in every layer's CROSS attention over the context rows
+ *     j < vis(t) = clamp(t + 2 + lookahead, 1, T)        (and ctx_mask[b][j] != 0, as always)
+ * lookahead = 0: the frame being produced and everything before it; < 0: a reaction delay of -lookahead frames; > 0: a buffer of
+ * look-ahead frames; lookahead >= T-2 computes what on = 0 computes.  Row 0 is always visible.  Past positions are not
+ * recomputed: the self-attention K/V a step cached under its own visibility stay, which is what a running system has (it equals a
+ * decoder whose cross attention carries the per-query mask j < vis(i)).  The speaker encoder is causal already, so the context rows
+ * below a frame do not depend on that frame: the tokens of dimx_generate / dimx_generate_prompted (any n_samples) are causal in the
+ * speaker.  The definition is dimx/online.py.
+ *   - on = 0 restores the offline behaviour bit for bit.  on and lookahead are part of what keys the captured step graph: a new
+ *     value captures a new graph, never replays another one's.
+ *   - With the window on the decode step runs the one-query attention kernels (csrc/decode_attn.hip) for every cross attention:
+ *     not the decoder-layer kernel and not the matrix-core multi-sample route, which have no windowed form.
+ *   - dimx_generate_prompted forces the whole prompt through decode steps, as its flags bit 0 does (the prefill's attention has no
+ *     per-query key bound); P0 still sizes nothing less: dimx_workspace_bytes_prompt(h, B, T, S, 1) suffices.
+ *   - dimx_generate_beam returns DIMX_ERR_ARG while the window is on.
+ *   - dimx_decode_tf is unaffected: the teacher-forced pass always sees the whole context. */
+int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead);
+/* The handle's current setting (either pointer may be NULL). */
+int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
 /* Decoders without positional embedding (variant 0): the first layer's q/k/v depend on the input token alone, so dimx_generate
  * reads them from a table over the token ids instead of projecting them at every step.  The table is built with the decode
  * step's own kernels (bit-identical rows) on first use and whenever the rows per call, the numeric mode or the decoder weights
@@ -597,6 +622,12 @@ int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, v
 int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
                            void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
                            const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream);
+/* The windowed cross form of an online generation (dimx_set_cross_lookahead): the arguments of dimx_op_decode_attn_ex's cross form
+ * plus lookahead; step_dev is required and the keys are j < clamp(*step_dev + 2 + lookahead, 1, n_keys).  K / V rows at or past that
+ * bound are never read, and the result has the bits of dimx_op_decode_attn_ex called with n_keys = that bound. */
+int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
+                            void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys, const uint8_t* kmask,
+                            int kmask_ld, int rows_per_clip, float scale, int nsplit, int lookahead, void* stream);
 /* Decode-step residual + pre-norm: x[M,C] += sum_s slabs[s] (fixed order), y = LayerNorm(x) * gamma (no bias). */
 /* The prefill's fused feed-forward sublayer alone (csrc/mlp_fused.hip; unit parity): x [M,C] f32 on the device is replaced by
  * x + W2 . gelu(W1 . LayerNorm(x) + b1) + b2 with bf16 operands and f32 accumulation.  w1 [F,C], b1 [F] (or NULL), w2 [C,F] are HOST
