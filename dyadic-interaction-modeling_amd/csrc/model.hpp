@@ -227,7 +227,10 @@ struct dimx_ctx {
     // online generation (dimx_set_cross_lookahead): decode step t's cross attention sees the context rows
     // j < clamp(t + 2 + lookahead, 1, T) only; off = every row, as the reference generates
     int xwin_on = 0, xwin_lookahead = 0;
-    dimx::MeshHead mesh;                // handles created with dimx_dims.mesh_dim > 0
+    // online fine-tuning (dimx_set_train_lookahead): the same visibility in the decoder cross attention of
+    // dimx_train_forward_backward, query row i = step t.  Independent of xwin_*.
+    int twin_on = 0, twin_lookahead = 0;
+    dimx::MeshHead mesh;               // handles created with dimx_dims.mesh_dim > 0
     int lstm_faults = 0;                // LSTM layers whose group kernel reported a fault and that were rerun on the safe path
     int spk_embed_rows = 0;             // rows of speaker_embed.weight as last loaded (the host applies it in inference; the
                                         // DIM-Speaker training step lays its arena out by it); 0 = never loaded

@@ -278,10 +278,11 @@ struct StepGraphKey {
     const void *params, *grads, *v_speaker, *v_audio, *mask, *z_l, *kv_mask, *loss_out, *logits_out, *ws;
     size_t ws_bytes;
     int B, T, at, side;
+    int win_on, win_lookahead;   // dimx_set_train_lookahead: a step captured under one setting is never replayed under another
     bool operator==(const StepGraphKey& o) const {
         return params == o.params && grads == o.grads && v_speaker == o.v_speaker && v_audio == o.v_audio && mask == o.mask && z_l == o.z_l &&
                kv_mask == o.kv_mask && loss_out == o.loss_out && logits_out == o.logits_out && ws == o.ws && ws_bytes == o.ws_bytes &&
-               B == o.B && T == o.T && at == o.at && side == o.side;
+               B == o.B && T == o.T && at == o.at && side == o.side && win_on == o.win_on && win_lookahead == o.win_lookahead;
     }
 };
 struct TrainState {
@@ -1451,6 +1452,9 @@ static int train_run(dimx_handle h, const float* params, float* grads, const flo
     cross_sh.causal = 0;
     cross_sh.kmask = mask;
     cross_sh.kmask2 = nullptr;
+    // online fine-tuning (dimx_set_train_lookahead): decoder row i is generation step t = i and sees the context rows
+    // j < clamp(i + 2 + L, 1, T); the adjoints read the same shape back from the AttnSave
+    tr_attn_window(cross_sh, h->twin_on, h->twin_lookahead);
     for (int i = 0; i < d.dec_depth; ++i) {
         DIMX_TRY(attn_fwd(s, sa[i], hd[3 * i], hd[3 * i + 1], s.Md, DD, false, nullptr, 0, 0, self_sh, nullptr));
         DIMX_TRY(attn_fwd(s, ca[i], hd[3 * i + 1], hd[3 * i + 2], s.Md, DD, true, ctx, s.M, DD, cross_sh, nullptr));
@@ -1837,7 +1841,8 @@ int dimx_train_forward_backward(dimx_handle h, const float* params, float* grads
     TrainState* ts;
     DIMX_TRY(state_of(h, &ts));
     hipStream_t st = (hipStream_t)stream;
-    const StepGraphKey key{params, grads, v_speaker, v_audio, mask, z_l, kv_mask, loss_out, logits_out, ws, ws_bytes, B, T, h->at, side ? 1 : 0};
+    const StepGraphKey key{params, grads, v_speaker, v_audio, mask, z_l, kv_mask, loss_out, logits_out, ws, ws_bytes, B, T, h->at, side ? 1 : 0,
+                           h->twin_on, h->twin_lookahead};
     if (train_use_graph(B * T)) {
         if (ts->exec && ts->graph_key == key) {
             ++ts->graph_launches;
@@ -1899,10 +1904,33 @@ int dimx_train_adamw(float* params, const float* grads, float* exp_avg, float* e
     return tr_adamw(params, grads, exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, step, scratch + 1024, st);
 }
 
+int dimx_set_train_lookahead(dimx_handle h, int on, int lookahead) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_train_lookahead: online fine-tuning is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    h->twin_on = on ? 1 : 0;
+    h->twin_lookahead = on ? lookahead : 0;
+    return DIMX_OK;
+}
+
+int dimx_train_lookahead(dimx_handle h, int* on, int* lookahead) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    if (on) *on = h->twin_on;
+    if (lookahead) *lookahead = h->twin_lookahead;
+    return DIMX_OK;
+}
+
 int dimx_op_train_attention(int mfma, const float* q, const float* k, const float* v, const float* d_o, const uint8_t* kmask,
                             const uint8_t* kmask2, int B, int H, int Lq, int Lk, int causal, float scale, float* o, float* lse,
                             float* delta, float* dq, float* dk, float* dv, void* stream) {
+    return dimx_op_train_attention_win(mfma, q, k, v, d_o, kmask, kmask2, B, H, Lq, Lk, causal, scale, 0, 0, o, lse, delta, dq, dk, dv, stream);
+}
+
+int dimx_op_train_attention_win(int mfma, const float* q, const float* k, const float* v, const float* d_o, const uint8_t* kmask,
+                                const uint8_t* kmask2, int B, int H, int Lq, int Lk, int causal, float scale, int win, int lookahead,
+                                float* o, float* lse, float* delta, float* dq, float* dk, float* dv, void* stream) {
     DIMX_REQUIRE(q && k && v && o && lse && B > 0 && H > 0 && Lq > 0 && Lk > 0, DIMX_ERR_ARG, "op_train_attention: bad argument");
+    DIMX_REQUIRE(!(win && causal), DIMX_ERR_ARG, "op_train_attention: the window replaces causal; set one of them");
     DIMX_REQUIRE(!d_o || (delta && dq && dk && dv), DIMX_ERR_ARG, "op_train_attention: the backward pass needs delta, dq, dk, dv");
     TrAttn t;
     memset(&t, 0, sizeof(t));
@@ -1910,6 +1938,7 @@ int dimx_op_train_attention(int mfma, const float* q, const float* k, const floa
     t.ldq = t.ldk = t.ldv = t.ldo = H * 64;
     t.scale = scale;
     t.causal = causal;
+    tr_attn_window(t, win, lookahead);
     t.kmask = kmask;
     t.kmask2 = kmask2;
     t.mfma = mfma < 0 ? 0 : (mfma > 2 ? 2 : mfma);

@@ -12,10 +12,24 @@ struct TrAttn {
     int ldq, ldk, ldv, ldo;  // row strides of the [B, L, *] f32 operands; head h at column h * 64 (dim_head 64)
     float scale;
     int causal;
+    // online window (tr_attn_window): query i keeps key j iff j <= max(i + win_diag, 0).  causal is the same bound with
+    // win_diag = 0 (max(i, 0) = i); when win is set it replaces causal.  win_diag is clamped to [-Lq, Lk] by the host, so
+    // i + win_diag never wraps
+    int win, win_diag;
     const uint8_t* kmask;    // [B, Lk] keep-mask (padding), optional
     const uint8_t* kmask2;   // [B, Lk] second keep-mask (the mask_prob draw), optional
     int mfma;                // train_attn.hip on the matrix cores: 1 = bf16 operands (perf mode), 2 = exact f32 (parity mode); 0 = the f32 VALU kernels
 };
+// the window of dimx.online on t (Lq, Lk set): key j < clamp(i + 2 + lookahead, 1, Lk), i.e. j <= max(i + 1 + lookahead, 0).
+// The diagonal is formed in 64 bits and clamped to [-Lq, Lk]: below -Lq + 1 every query sees key 0 only, from Lk - 1 on
+// every key, so no lookahead (INT32_MIN, INT32_MAX) wraps in the kernels.
+inline void tr_attn_window(TrAttn& t, int on, int lookahead) {
+    long long dg = (long long)lookahead + 1;
+    if (dg < -(long long)t.Lq) dg = -(long long)t.Lq;
+    if (dg > (long long)t.Lk) dg = (long long)t.Lk;
+    t.win = on ? 1 : 0;
+    t.win_diag = on ? (int)dg : 0;
+}
 
 // operand copies of up to kPrepMax weight matrices in ONE launch: for each [N][K] f32 source the cast [N][Kp] (zero columns
 // K..Kp) and the transposed cast [K][Np] (zero columns N..Np)

@@ -191,6 +191,10 @@ __device__ __forceinline__ void key_bits(const TrAttn& a, int b, int k0, int lan
     valid = __ballot(v);
 }
 
+// last key query i keeps under a diagonal bound: causal (diag = 0) or the online window (TrAttn::win_diag = 1 + lookahead,
+// clamped by the host so that i + diag cannot wrap).  Key 0 is always inside.
+__device__ __forceinline__ int key_bound(int i, int diag) { return max(i + diag, 0); }
+
 // ------------------------------------------------------------------------------------------------ forward
 template <typename T>
 __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(TrAttn a, const float* __restrict__ q, const float* __restrict__ k,
@@ -205,6 +209,9 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(TrAttn a, const floa
     const int h = blockIdx.y, b = blockIdx.z;
     const int q0b = blockIdx.x * 128, q0w = q0b + 32 * w, qi = q0w + l31;
     const bool wave_on = q0w < a.Lq, q_ok = qi < a.Lq;
+    const bool bounded = a.causal || a.win;
+    const int diag = a.win ? a.win_diag : 0;
+    const int kb_q = key_bound(qi, diag), kb_wave = key_bound(q0w + 31, diag);   // last key of this query / of the wave's last query
     uint4 Qf[NS];
     frag_rows_global<T>(Qf, q + ((size_t)b * a.Lq + (q_ok ? qi : 0)) * a.ldq + h * 64, q_ok, hl);
     const float* kb = k + (size_t)b * a.Lk * a.ldk + h * 64;
@@ -214,7 +221,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(TrAttn a, const floa
     for (int i = 0; i < 16; ++i) accO[0][i] = accO[1][i] = 0.f;
     float m = kNegMaxF, lsum = 0.f;
     int nkt = (a.Lk + 63) >> 6;
-    if (a.causal) nkt = min(nkt, (min(q0b + 127, a.Lq - 1) >> 6) + 1);
+    if (bounded) nkt = min(nkt, (key_bound(min(q0b + 127, a.Lq - 1), diag) >> 6) + 1);   // the bound of the block's last query
     RowsReg kr;
     ColsReg vr;
     if (nkt > 0) {
@@ -232,7 +239,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(TrAttn a, const floa
             load_rows(kr, kb, a.ldk, (kt + 1) * 64, a.Lk, tid);
             load_cols(vr, vb, a.ldv, (kt + 1) * 64, a.Lk, tid);
         }
-        if (!wave_on || (a.causal && kt * 64 > q0w + 31)) continue;
+        if (!wave_on || (bounded && kt * 64 > kb_wave)) continue;
         f32x16_t st[2];
 #pragma unroll
         for (int kb2 = 0; kb2 < 2; ++kb2) {
@@ -247,7 +254,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(TrAttn a, const floa
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int kl = 32 * kb2 + 8 * (i >> 2) + 4 * hl + (i & 3);
-                const bool kp = ((keep >> kl) & 1) && !(a.causal && kt * 64 + kl > qi);
+                const bool kp = ((keep >> kl) & 1) && !(bounded && kt * 64 + kl > kb_q);
                 const bool vd = (valid >> kl) & 1;
                 const float s = vd ? (kp ? st[kb2][i] * a.scale : kNegMaxF) : -kInf;
                 st[kb2][i] = s;
@@ -309,6 +316,9 @@ __global__ __launch_bounds__(256) void attn_dq_mfma_kernel(TrAttn a, const float
     const int h = blockIdx.y, b = blockIdx.z;
     const int q0b = blockIdx.x * 128, q0w = q0b + 32 * w, qi = q0w + l31;
     const bool wave_on = q0w < a.Lq, q_ok = qi < a.Lq;
+    const bool bounded = a.causal || a.win;
+    const int diag = a.win ? a.win_diag : 0;
+    const int kb_q = key_bound(qi, diag), kb_wave = key_bound(q0w + 31, diag);   // last key of this query / of the wave's last query
     uint4 Qf[NS], Gf[NS];
     frag_rows_global<T>(Qf, q + ((size_t)b * a.Lq + (q_ok ? qi : 0)) * a.ldq + h * 64, q_ok, hl);
     frag_rows_global<T>(Gf, d_o + ((size_t)b * a.Lq + (q_ok ? qi : 0)) * a.ldo + h * 64, q_ok, hl);
@@ -332,7 +342,7 @@ __global__ __launch_bounds__(256) void attn_dq_mfma_kernel(TrAttn a, const float
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[0][i] = acc[1][i] = 0.f;
     int nkt = (a.Lk + 63) >> 6;
-    if (a.causal) nkt = min(nkt, (min(q0b + 127, a.Lq - 1) >> 6) + 1);
+    if (bounded) nkt = min(nkt, (key_bound(min(q0b + 127, a.Lq - 1), diag) >> 6) + 1);   // the bound of the block's last query
     RowsReg kr, vr;
     ColsReg kc;
     if (nkt > 0) {
@@ -353,7 +363,7 @@ __global__ __launch_bounds__(256) void attn_dq_mfma_kernel(TrAttn a, const float
             load_rows(vr, vb, a.ldv, (kt + 1) * 64, a.Lk, tid);
             load_cols(kc, kb, a.ldk, (kt + 1) * 64, a.Lk, tid);
         }
-        if (!wave_on || (a.causal && kt * 64 > q0w + 31)) continue;
+        if (!wave_on || (bounded && kt * 64 > kb_wave)) continue;
         f32x16_t st[2], dp[2];
 #pragma unroll
         for (int kb2 = 0; kb2 < 2; ++kb2) {
@@ -370,7 +380,7 @@ __global__ __launch_bounds__(256) void attn_dq_mfma_kernel(TrAttn a, const float
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int kl = 32 * kb2 + 8 * (i >> 2) + 4 * hl + (i & 3);
-                const bool kp = ((keep >> kl) & 1) && !(a.causal && kt * 64 + kl > qi);
+                const bool kp = ((keep >> kl) & 1) && !(bounded && kt * 64 + kl > kb_q);
                 const float p = kp ? __expf(st[kb2][i] * a.scale - L) : 0.f;  // a masked score has no gradient (masked_fill)
                 st[kb2][i] = p * (dp[kb2][i] - dl) * a.scale;
             }
@@ -421,7 +431,13 @@ __global__ __launch_bounds__(256) void attn_dkv_mfma_kernel(TrAttn a, const floa
 #pragma unroll
     for (int i = 0; i < 16; ++i) accK[0][i] = accK[1][i] = accV[0][i] = accV[1][i] = 0.f;
     const int nqt = (a.Lq + 63) >> 6;
-    const int qt0 = a.causal ? min(k0b >> 6, nqt) : 0;  // a causal query tile below the block's first key sees none of its keys
+    const bool bounded = a.causal || a.win;
+    const int diag = a.win ? a.win_diag : 0;
+    // key j is seen by the queries i >= j - diag, and key 0 by EVERY query (the floor of the bound): a query tile below
+    // first_query(first key) sees none of the block's / the wave's keys -- unless they include key 0
+    const int qt0 = bounded && k0b > 0 ? min(max(k0b - diag, 0) >> 6, nqt) : 0;
+    const int q_first_w = k0w > 0 ? k0w - diag : 0;
+    const int q_first = kj > 0 ? kj - diag : 0;   // kj > key_bound(i, diag)  <=>  i < q_first
     RowsReg qr, gr;
     ColsReg qc, gc;
     float lreg = kInf, dreg = 0.f;
@@ -449,7 +465,7 @@ __global__ __launch_bounds__(256) void attn_dkv_mfma_kernel(TrAttn a, const floa
         }
         __syncthreads();
         if (qt + 1 < nqt) load_tile(qt + 1);
-        if (!wave_on || (a.causal && qt * 64 + 63 < k0w)) continue;
+        if (!wave_on || (bounded && qt * 64 + 63 < q_first_w)) continue;
         f32x16_t st[2], dp[2];
 #pragma unroll
         for (int qb2 = 0; qb2 < 2; ++qb2) {
@@ -471,7 +487,7 @@ __global__ __launch_bounds__(256) void attn_dkv_mfma_kernel(TrAttn a, const floa
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int i = 4 * g + r;
-                    const bool kp = kept && !(a.causal && kj > qt * 64 + ql + r);
+                    const bool kp = kept && !(bounded && qt * 64 + ql + r < q_first);
                     const float p = kp ? __expf(st[qb2][i] * a.scale - Lr[r]) : 0.f;
                     st[qb2][i] = p;
                     dp[qb2][i] = p * (dp[qb2][i] - Dr[r]) * a.scale;

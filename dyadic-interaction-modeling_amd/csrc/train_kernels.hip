@@ -231,13 +231,13 @@ struct AttnShape {
     int B, H, Lq, Lk;       // D = 64
     int ldq, ldk, ldv, ldo; // row strides (elements) of the [B, L, *] operands; head h at column h * 64
     float scale;
-    int causal;
+    int bounded, diag;      // causal or the online window: query i keeps key j iff j <= max(i + diag, 0) (causal: diag = 0)
     const uint8_t* kmask;   // [B, Lk] 1 = keep (padding mask), optional
     const uint8_t* kmask2;  // [B, Lk] second keep-mask (AutoregressiveWrapper's mask_prob draw), optional
 };
 
 __device__ __forceinline__ bool key_kept(const AttnShape& a, int b, int i, int j) {
-    if (a.causal && j > i) return false;
+    if (a.bounded && j > max(i + a.diag, 0)) return false;
     if (a.kmask && !a.kmask[(size_t)b * a.Lk + j]) return false;
     if (a.kmask2 && !a.kmask2[(size_t)b * a.Lk + j]) return false;
     return true;
@@ -1319,7 +1319,8 @@ static AttnShape make_shape(const TrAttn& t) {
     a.B = t.B; a.H = t.H; a.Lq = t.Lq; a.Lk = t.Lk;
     a.ldq = t.ldq; a.ldk = t.ldk; a.ldv = t.ldv; a.ldo = t.ldo;
     a.scale = t.scale;
-    a.causal = t.causal;
+    a.bounded = (t.causal || t.win) ? 1 : 0;
+    a.diag = t.win ? t.win_diag : 0;
     a.kmask = t.kmask;
     a.kmask2 = t.kmask2;
     return a;

@@ -87,6 +87,8 @@ SIGNATURES = {
     "dimx_train_forward_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                             c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dimx_train_graph_stats": (c_int, [c_void_p, c_void_p]),
+    "dimx_set_train_lookahead": (c_int, [c_void_p, c_int, c_int]),
+    "dimx_train_lookahead": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "dimx_train_legacy_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "dimx_train_legacy_forward_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -118,6 +120,9 @@ SIGNATURES = {
     "dimx_op_train_attention": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "dimx_op_train_attention_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                            c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
     "dimx_op_train_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                             c_size_t, c_void_p]),
     "dimx_op_train_colsum": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

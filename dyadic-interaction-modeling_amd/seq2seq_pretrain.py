@@ -263,9 +263,11 @@ class SLMFT(_EngineOwner):
         self.listener_vq.eval()
         return self
 
-    def _forward_autograd(self, v_speaker, v_listener, v_audio, mask, kv_mask=None, z_l=None, return_tokens=False):
+    def _forward_autograd(self, v_speaker, v_listener, v_audio, mask, kv_mask=None, z_l=None, return_tokens=False, lookahead=None):
         """mode='train' with a graph: differentiable cross entropy (dimx.train.slmft_loss on this module's own
-        parameters); listener codes and decoded motion come from the HIP engine without a graph."""
+        parameters); listener codes and decoded motion come from the HIP engine without a graph.
+        ``lookahead`` L: online fine-tuning -- the decoder's cross attention of row t sees the context rows below
+        clamp(t + 2 + L, 1, T) only (dimx.online); ``x_engine_pt.train_epoch(lookahead=L)`` is what passes it."""
         from . import train as T
         mask = mask.bool()
         B, Tn = mask.shape
@@ -279,7 +281,7 @@ class SLMFT(_EngineOwner):
             kv_mask = None
         P = dict(self.named_parameters())
         l_ce_l, logits = T.slmft_loss(P, self.s2s, v_speaker.float(), v_audio.float(), mask, z_l.long(),
-                                      kv_mask.bool() if kv_mask is not None else None)
+                                      kv_mask.bool() if kv_mask is not None else None, lookahead=lookahead)
         pred, l_cont_l = None, torch.zeros((), device=v_speaker.device)
         if on_gpu:     # the continuous loss has no gradient path in the reference either (argmax -> one-hot, :454-464)
             with torch.no_grad():

@@ -84,8 +84,10 @@ def _self(h, P, L, li, heads, key_mask, attn_mask):
     return _attention(y, y, P, L + "%d.1." % li, heads, key_mask, attn_mask)
 
 
-def xt_decoder_logits(P, pre, tokens, context, context_mask, self_kv_mask, depth, heads, pos_emb=False):
-    """TransformerWrapper(num_tokens, attn_layers=Decoder(cross_attend=True)) on a token prefix -> logits."""
+def xt_decoder_logits(P, pre, tokens, context, context_mask, self_kv_mask, depth, heads, pos_emb=False, cross_attn_mask=None):
+    """TransformerWrapper(num_tokens, attn_layers=Decoder(cross_attend=True)) on a token prefix -> logits.
+    cross_attn_mask: bool, broadcastable to [B, heads, n, keys]; False entries of every layer's cross attention are filled like
+    masked keys (``online_cross_mask``: the visibility of an online generation)."""
     n = tokens.shape[1]
     h = P[pre + "token_emb.emb.weight"][tokens]
     if pos_emb:
@@ -95,23 +97,35 @@ def xt_decoder_logits(P, pre, tokens, context, context_mask, self_kv_mask, depth
     for i in range(depth):
         h = h + _self(h, P, L, 3 * i, heads, self_kv_mask, causal)
         y = _ln(h, P[L + "%d.0.0.weight" % (3 * i + 1)])
-        h = h + _attention(y, context, P, L + "%d.1." % (3 * i + 1), heads, context_mask, None)
+        h = h + _attention(y, context, P, L + "%d.1." % (3 * i + 1), heads, context_mask, cross_attn_mask)
         h = h + _ff(_ln(h, P[L + "%d.0.0.weight" % (3 * i + 2)]), P, L + "%d.1." % (3 * i + 2))
     h = _ln(h, P[pre + "attn_layers.final_norm.weight"])
     return F.linear(h, P[pre + "to_logits.weight"], P.get(pre + "to_logits.bias"))
 
 
-def slmft_loss(P, dims, v_speaker, v_audio, mask, z_l, kv_mask=None):
+def online_cross_mask(mask, lookahead):
+    """[B, T-1, T] bool: decoder row t (it consumes token t and predicts t+1: step t of dimx.online) keeps context row j iff
+    j < visible(t, lookahead, T) and ``mask`` [B, T] keeps j -- ``dimx.online.visible_mask`` on the device of ``mask``."""
+    from .online import visible
+    T = mask.shape[1]
+    vis = torch.as_tensor(visible(range(T - 1), lookahead, T), device=mask.device)                   # [T-1]
+    return (torch.arange(T, device=mask.device)[None, :] < vis[:, None])[None] & mask.bool()[:, None, :]
+
+
+def slmft_loss(P, dims, v_speaker, v_audio, mask, z_l, kv_mask=None, lookahead=None):
     """Differentiable l_ce_l of SLMFT.forward(mode='train').  P: {key: tensor} (parameters carry the graph); z_l [B,T]
     listener codes with -100 on padding (from the frozen VQ-VAE); kv_mask [B,T-1] keep-mask (AutoregressiveWrapper's
-    mask_prob draw) or None.  Returns (loss, logits)."""
+    mask_prob draw) or None.  lookahead: an integer L trains under the visibility of an online generation (``online_cross_mask``
+    on the decoder's cross attention; the checker of dimx_set_train_lookahead), None = the reference's offline step.
+    Returns (loss, logits)."""
     x = v_speaker + P["patch_embed_s"]
     x = xt_encoder(P, "encoder_s.", x, mask, True, dims.enc_depth, dims.heads)
     x = xt_encoder(P, "encoder_joint.", x, mask, True, dims.enc_depth, dims.heads)
     x_s = _ln(x, P["norm_s.weight"], P["norm_s.bias"])
     ctx = torch.cat([x_s + P["patch_embed_dec_s"], v_audio], dim=-1)
     inp = z_l[:, :-1].clamp(min=0)                                   # pad_value 0 where the target is ignored
-    logits = xt_decoder_logits(P, "decoder_joint.net.", inp, ctx, mask, kv_mask, dims.dec_depth, dims.heads)
+    cam = None if lookahead is None else online_cross_mask(mask, lookahead)[:, None]
+    logits = xt_decoder_logits(P, "decoder_joint.net.", inp, ctx, mask, kv_mask, dims.dec_depth, dims.heads, cross_attn_mask=cam)
     loss = F.cross_entropy(logits.reshape(-1, logits.shape[-1]), z_l[:, 1:].reshape(-1), ignore_index=-100)
     return loss, logits
 

@@ -28,9 +28,11 @@ class HipTrainer:
     _LOSS_FLOATS = 2                             # floats the step writes to loss_out
     _UNGRAPHED = None                            # name of a step that is launched kernel by kernel (no graph_stats)
 
-    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=1.0, device=None):
-        """AdamW defaults are torch.optim.AdamW's (the reference passes only lr, code/finetune_s2s_pretrain.py:119)."""
+    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=1.0, device=None, lookahead=None):
+        """AdamW defaults are torch.optim.AdamW's (the reference passes only lr, code/finetune_s2s_pretrain.py:119).
+        lookahead: online fine-tuning (``set_lookahead``); None = the offline step of the reference."""
         self.model = model
+        self.lookahead = None
         self.device = torch.device(device if device is not None else next(model.parameters()).device)
         if self.device.type != "cuda":
             raise L.DimxError("HipTrainer needs the module on a ROCm GPU (model.to('cuda:0')); there is no CPU path")
@@ -49,6 +51,8 @@ class HipTrainer:
         self._stage = {}
         self.step_count = 0
         self.load_from_model()
+        if lookahead is not None:
+            self.set_lookahead(lookahead)
         if ddist.world_size() > 1:                      # every rank starts from rank 0's parameters
             import torch.distributed as dist
             dist.broadcast(self.params, 0)
@@ -200,6 +204,22 @@ class HipTrainer:
             self._stage[(B, T, d_s, d_a)] = st
         return st
 
+    def set_lookahead(self, lookahead=None):
+        """Online fine-tuning (dimx_set_train_lookahead; the definition is dimx.online): with an integer ``lookahead`` L the
+        decoder's cross attention of every following step lets row t see the context rows j < visible(t, L, T) only -- what an
+        online generation with the same L (``SLMFT.generate(lookahead=L)``) shows step t.  None: the offline step.  The setting is
+        the trainer's; it is written to the engine handle before each step, so trainers that share a model do not disturb each
+        other.  Only the SLMFT step (this class itself) takes it."""
+        if lookahead is not None and type(self) is not HipTrainer:
+            raise L.DimxError("set_lookahead: only the SLMFT fine-tuning step (HipTrainer) trains under the online window")
+        if lookahead is not None:                       # refused by the library for a handle of another variant
+            L.check(self.lib.dimx_set_train_lookahead(self.eng.h, 1, int(lookahead)), "dimx_set_train_lookahead")
+        self.lookahead = None if lookahead is None else int(lookahead)
+
+    def _apply_lookahead(self):
+        la = self.lookahead
+        L.check(self.lib.dimx_set_train_lookahead(self.eng.h, 0 if la is None else 1, 0 if la is None else la), "dimx_set_train_lookahead")
+
     def graph_stats(self):
         """(steps replayed from the captured hipGraph, steps launched kernel by kernel, nodes of the captured graph)"""
         if self._UNGRAPHED:
@@ -237,6 +257,7 @@ class HipTrainer:
             kv8.copy_(kv_mask, non_blocking=True)
         logits = st["logits"]() if return_logits else None
         ws, wsb = self._workspace(B, T)
+        self._apply_lookahead()
         L.check(self.lib.dimx_train_forward_backward(self.eng.h, L.ptr(self.params), L.ptr(self.grads), L.ptr(v_s), L.ptr(v_a),
                                                      L.ptr(m8), L.ptr(z32), L.ptr(kv8), B, T, L.ptr(self._loss), L.ptr(logits), ws,
                                                      wsb, L.stream_ptr(self.device)), "dimx_train_forward_backward")

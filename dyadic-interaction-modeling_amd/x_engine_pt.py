@@ -760,7 +760,8 @@ def _train_epoch_hip(model, loader, trainer, device, scheduler, print_freq, epoc
     return float(np.mean(all_losses)) if all_losses else float("nan")
 
 
-def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, print_freq=2000, epoch=0, log=print, backward="auto"):
+def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, print_freq=2000, epoch=0, log=print, backward="auto",
+                lookahead=None):
     """reference code/x_engine_pt.py:9-60: one pass over the loader with zero_grad / forward(mode='train') / backward /
     clip / step (``clip`` None = the reference's default 0., no clipping).
 
@@ -772,15 +773,28 @@ def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, pri
     of this package cannot be stepped by the HIP kernels (another optimiser class, amsgrad, unequal param_groups, CPU tensors):
     the PyTorch-autograd restatement (dimx.train) is the checker of the HIP path and runs only with ``backward="autograd"``.  For N > 1 processes the gradients are averaged over RCCL before
     clipping; every rank feeds its own loader shard (get_vico_dataloaders shards the training loaders by rank; the sampler is
-    told the epoch here); the ranks must see the same number of batches (checked) and start from rank 0's parameters."""
+    told the epoch here); the ranks must see the same number of batches (checked) and start from rank 0's parameters.
+
+    ``lookahead`` L (SLMFT only): online fine-tuning -- every step trains under the visibility of an online generation with the
+    same L (dimx.online: decoder row t sees the context rows below clamp(t + 2 + L, 1, T)), on the HIP step
+    (``HipTrainer.set_lookahead``) and on the autograd route (``dimx.train.slmft_loss(lookahead=L)``) alike.  None: the
+    reference's offline step; a ``HipTrainer`` passed as ``optimizer`` then keeps its own setting."""
+    from .seq2seq_pretrain import SLMFT
     from .train_hip import HipTrainer
+    inner = getattr(model, "module", model)
+    if lookahead is not None and not isinstance(inner, SLMFT):
+        raise L.DimxError("train_epoch(lookahead=...): online fine-tuning is built for SLMFT, not %s" % type(inner).__name__)
     if isinstance(optimizer, HipTrainer):
+        if lookahead is not None:
+            optimizer.set_lookahead(lookahead)
         return _train_epoch_hip(model, loader, optimizer, device, scheduler, print_freq, epoch, log, clip=clip)
     if backward not in ("auto", "hip", "autograd"):
         raise ValueError("backward must be 'auto', 'hip' or 'autograd'")
     if backward != "autograd":
         tr = _hip_trainer_for(model, optimizer, device, log)
         if tr is not None:
+            if type(tr) is HipTrainer:        # the cached stand-in follows this call's argument, None included
+                tr.set_lookahead(lookahead)
             return _train_epoch_hip(model, loader, tr, device, scheduler, print_freq, epoch, log,
                                     clip=0.0 if clip is None else clip, optimizer=optimizer)
         if backward == "hip":
@@ -790,7 +804,6 @@ def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, pri
     clip = 0.0 if clip is None else clip
     _set_epoch(loader, epoch)
     model.train()
-    inner = getattr(model, "module", model)
     # what the reference trains differs per model: SLMFT freezes both VQ-VAEs (:348-366), SLM only their encoders + codebooks (:98-113)
     named = inner.dimx_trainable_parameters() if hasattr(inner, "dimx_trainable_parameters") else T.trainable_parameters(model)
     for _, p in named:
@@ -807,7 +820,10 @@ def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, pri
     for i, batch in enumerate(loader):
         src_s_v, src_s_a, tgt, mask, _, _ = _prepare(batch, device)
         optimizer.zero_grad()
-        loss, d_step, _ = model(src_s_v, tgt, src_s_a, mask, mode="train")
+        if lookahead is None:
+            loss, d_step, _ = model(src_s_v, tgt, src_s_a, mask, mode="train")
+        else:      # the windowed teacher-forced pass exists with a graph only (SLMFT.forward keeps lookahead for mode='val')
+            loss, d_step, _ = inner._forward_autograd(src_s_v, tgt, src_s_a, mask, lookahead=int(lookahead))
         loss.mean().backward()
         T.all_reduce_grads(params)
         if clip > 0:

@@ -6,6 +6,13 @@ The training step -- forward, backward, clip, AdamW -- runs on the hand-written 
 `--backward autograd` selects the PyTorch-autograd restatement that serves as its checker.
 
     python examples/finetune_s2s_pretrain.py [--epochs 2] [--clips 64] [--batch 4] [--max-len 120] [--backward hip|autograd]
+                                             [--lookahead L]
+
+``--lookahead L`` (listener mode) fine-tunes for ONLINE generation (dimx/online.py): every step trains with the
+decoder's cross attention of row t limited to the speaker frames below clamp(t + 2 + L, 1, T), the visibility
+``SLMFT.forward(mode='val', lookahead=L)`` generates under.  After each epoch the validation perplexity under that same
+visibility (``SLMFT.score(lookahead=L)``) is printed next to the offline one.  The reference's report
+(evaluate_finetune_epoch + print_metrics, a teacher-forced pass over the whole context) and the checkpoint rule are unchanged.
 
 ``--mode speaker --synthetic`` is the reference's SPEAKER branch (DIM-Speaker): ``SpeakerSLMFT`` under ``train_epoch_biwi`` at
 batch size 1 (AdamW lr 1e-5, clip 1.0) on the HIP step ``dimx.train_hip.SpeakerHipTrainer``; every tenth epoch
@@ -70,6 +77,21 @@ def speaker_main(args):
                 print("saved %s" % out)
 
 
+def validation_perplexity(model, loader, device, lookahead=None):
+    """teacher-forced perplexity of the validation clips' own listener codes, offline (lookahead None) or under the visibility of
+    an online generation (SLMFT.score)"""
+    from dimx.scoring import SeqScores, perplexity
+    from dimx.x_engine_pt import _prepare
+    model.eval()
+    score, count = [], []
+    for batch in loader:
+        src_s_v, src_s_a, tgt, mask, _, _ = _prepare(batch, device)
+        sc = model.score(src_s_v, tgt, src_s_a, mask, lookahead=lookahead)
+        score.append(sc.score.cpu())
+        count.append(sc.count.cpu())
+    return perplexity(SeqScores(torch.cat(score), torch.cat(count))) if score else float("nan")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="listener", choices=["listener", "speaker"],
@@ -85,7 +107,12 @@ def main():
     ap.add_argument("--out", default="best_vico_causal.pt")
     ap.add_argument("--backward", default="hip", choices=["hip", "autograd"],
                     help="hip: forward + backward + clip + AdamW on csrc/train*.hip; autograd: the PyTorch restatement (checker)")
+    ap.add_argument("--lookahead", type=int, default=None,
+                    help="listener mode: fine-tune under the visibility of an online generation with this look-ahead "
+                         "(0: the frame being produced and its past; negative: a reaction delay; default: offline, the reference)")
     args = ap.parse_args()
+    if args.mode == "speaker" and args.lookahead is not None:
+        ap.error("--lookahead applies to --mode listener: the DIM-Speaker step has no online window")
     if args.mode == "speaker":
         return speaker_main(args)
     rank, world, local = ddist.init_from_env()
@@ -103,11 +130,16 @@ def main():
     best = float("inf")
     for epoch in range(args.epochs):
         loss = train_epoch(model, dataset["train"], optimizer, device, scheduler=None, clip=1.0, print_freq=100,
-                           epoch=epoch, log=print if rank == 0 else (lambda *_: None), backward=args.backward)
+                           epoch=epoch, log=print if rank == 0 else (lambda *_: None), backward=args.backward,
+                           lookahead=args.lookahead)
         y_true, y_pred, x, _ = evaluate_finetune_epoch(model, dataset["valid"], device)
         if rank == 0:
             a, b = print_metrics(y_true, y_pred, x)
             print("epoch %d: mean loss %.4f, FD pose %.4f + exp %.4f" % (epoch, loss, a, b))
+            if args.lookahead is not None:
+                print("epoch %d: validation perplexity under lookahead %d: %.3f (offline: %.3f)" % (
+                    epoch, args.lookahead, validation_perplexity(model, dataset["valid"], device, args.lookahead),
+                    validation_perplexity(model, dataset["valid"], device)))
             if a + b < best:
                 best = a + b
                 torch.save(model.state_dict(), args.out)

@@ -393,6 +393,21 @@ int dimx_train_forward_backward(dimx_handle h, const float* params, float* grads
  * weight-gradient GEMMs on a side stream (the faster choice there: csrc/train.hip).  DIMX_TRAIN_GRAPH=0|1 / DIMX_TRAIN_SIDE=0|1
  * force either; results are bit-identical in every combination. */
 int dimx_train_graph_stats(dimx_handle h, int64_t* out3);
+/* Online fine-tuning: train under the visibility an online generation runs with (dimx_set_cross_lookahead; the definition is
+ * dimx/online.py).  With on != 0, dimx_train_forward_backward masks the decoder's cross attention, in every layer, forward and
+ * both adjoints, in both numeric modes and on both launch paths: query row i (it consumes token i and predicts token i + 1, so
+ * it is generation step t = i) keeps context row j iff j < clamp(i + 2 + lookahead, 1, T) and mask keeps j.  loss_out /
+ * logits_out are the windowed model's.
+ *   - Row 0 is always inside the window; lookahead >= T - 2 is the offline form, bit for bit; any int is accepted.
+ *   - A query whose every in-window row is dropped by mask is outside the contract.  The step never produces one for a clip with
+ *     at least one valid frame (valid frames are a prefix, so row 0 is valid).
+ *   - Handle state of variant 0 only (DIMX_ERR_ARG on a handle of variant 1 or 2); on = 0 resets lookahead to 0.  on and
+ *     lookahead key the captured step graph: a step captured under one setting is never replayed under another.
+ *   - Independent of dimx_set_cross_lookahead: generation and dimx_decode_tf do not read this setting, the step does not read
+ *     that one.  The legacy, SLM, VQ-VAE, converter and speaker steps do not take it. */
+int dimx_set_train_lookahead(dimx_handle h, int on, int lookahead);
+/* The handle's current setting (either pointer may be NULL). */
+int dimx_train_lookahead(dimx_handle h, int* on, int* lookahead);
 /* The legacy generator's training step (reference loop code/x_engine.py:8-36 over ListenerGenerator.forward,
  * code/seq2seq.py:235-278): handle of variant 1.  The arenas follow dimx_train_param_info of that handle: generator.*, the
  * listener VQ-VAE's DECODER (listener_vq.decoder.*) and the listener-id conditioning (listener_embeddings.weight [100,256],
@@ -515,6 +530,16 @@ int dimx_train_adamw(float* params, const float* grads, float* exp_avg, float* e
 int dimx_op_train_attention(int mfma, const float* q, const float* k, const float* v, const float* d_o, const uint8_t* kmask,
                             const uint8_t* kmask2, int B, int H, int Lq, int Lk, int causal, float scale, float* o, float* lse,
                             float* delta, float* dq, float* dk, float* dv, void* stream);
+/* The same operator with the online window (dimx/online.py; what dimx_set_train_lookahead puts on the step's cross attention):
+ * win != 0: query i keeps key j iff j < clamp(i + 2 + lookahead, 1, Lk) and the keep-masks keep j.  Key 0 is always inside the
+ * window; lookahead >= Lk - 2 is the window off, bit for bit.  Any int is a valid lookahead (the diagonal is formed in 64 bits
+ * and clamped on the host).  A masked key has probability exactly 0 and gets no gradient.  win and causal together are
+ * DIMX_ERR_ARG; win = 0 is dimx_op_train_attention.  A query whose every in-window key is dropped by kmask / kmask2 is outside
+ * the contract (its row is then a softmax over filled scores, as x-transformers' would be, but over the key tiles the kernels
+ * did not skip only). */
+int dimx_op_train_attention_win(int mfma, const float* q, const float* k, const float* v, const float* d_o, const uint8_t* kmask,
+                                const uint8_t* kmask2, int B, int H, int Lq, int Lk, int causal, float scale, int win, int lookahead,
+                                float* o, float* lse, float* delta, float* dq, float* dk, float* dv, void* stream);
 /* The operators of the training step whose launch plan depends on the row count alone (unit parity).  Each runs the step's own
  * helper over caller scratch, so rows per block, slab counts, chunk widths and the deferred column-sum finish are the step's.
  * scratch: 256-byte aligned device floats for the partial rows; too little is DIMX_ERR_WORKSPACE before any launch.
