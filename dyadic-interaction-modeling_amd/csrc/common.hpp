@@ -603,7 +603,7 @@ struct BeamReorderArgs {
 int launch_beam_reorder(const BeamReorderArgs& a, hipStream_t s);
 // cum[r] = 0 for beam 0 of a clip, -inf for the others; parent[r] = r % W
 int launch_beam_init(double* cum, int32_t* parent, int R, int W, hipStream_t s);
-// the first decoder layer's q/k/v as a table over the token ids (model.hip qkv0_table_build): id list of the build rounds,
+// the first decoder layer's q/k/v as a table over the token ids (generate.hip qkv0_table_build): id list of the build rounds,
 // slab-order sum of a round's projection into the table rows, and step 0's rows by start token
 int launch_iota_clamp(int32_t* ids, int n, int rows, hipStream_t s);
 int launch_sum_slabs_rows(const float* slabs, int nslab, long slab_stride, float* table, int id0, int rows, int M, int N,

@@ -103,7 +103,7 @@ template <int EPC> __device__ __forceinline__ void load_f32_slabs(const float* p
 // red_acc [NW][64].
 //
 // TAB (self attention of the FIRST decoder layer, decoders without positional embedding): that layer's k / v depend on the
-// input token alone, so the cached row of position j is row hist[b][j] of a table over the token ids (model.hip kv0 image: the
+// input token alone, so the cached row of position j is row hist[b][j] of a table over the token ids (generate.hip kv0 image: the
 // bits the cache append would have stored).  The rows come from that table -- about 1.5 MB, shared by every wave of the chip,
 // resident in each XCD's L2 -- through plain cache-allocating loads, and nothing is appended.  The token ids are read two
 // batches ahead of the rows they address, so the dependent hop stays off the key loop's critical path and two row batches

@@ -1,4 +1,4 @@
-// kv_prefill.hip -- the layout moves of a prompted generation's prefill (dimx_generate_prompted, model.hip):
+// kv_prefill.hip -- the layout moves of a prompted generation's prefill (dimx_generate_prompted, generate.hip):
 //   * kv_rows_kernel: head rows that are contiguous on both sides -- the teacher-forced pass's self-attention K (and, in the
 //     bf16 mode, V) [B, n, H*64] row-major -> the generation cache [B*S, H, T, 64], every clip's rows broadcast to its S samples;
 //   * kv_tr_kernel (f32 mode only): a 64 x 64 transpose through LDS between a key-contiguous image [B, H, 64, ld_t] and a

@@ -1,4 +1,5 @@
-// model.hip -- handle, weight packing and the stage-level entry points of libdimx_hip.
+// model.hip -- handle, weight packing and the stage-level entry points of libdimx_hip (generation: generate.hip; the kernel-level
+// entry points: ops.hip; what the three share: stages.hpp).
 //
 // Stage <-> reference map (paths relative to /root/reference):
 //   vq_encode   : SLMFT.forward_vq / VQAutoEncoder.encode      code/seq2seq_pretrain.py:480-494,
@@ -16,7 +17,7 @@
 #include <stdlib.h>
 #include <set>
 
-#include "model.hpp"
+#include "stages.hpp"
 
 namespace dimx {
 
@@ -464,7 +465,6 @@ static void free_packed(dimx_ctx* c) {
     ++c->dec_epoch;   // every path that rewrites decoder weights on the device comes through here and re-packs (qkv0 table)
 }
 
-enum { COMP_VQ0 = 1, COMP_VQ1 = 2, COMP_ENC = 4, COMP_DEC = 8, COMP_ALL = 15, COMP_MESH = 16 };
 
 static std::vector<KeySpec> comp_keys(const dimx_dims& d, int comp) {
     std::vector<KeySpec> k;
@@ -612,10 +612,8 @@ int vq_pe_buffers(dimx_ctx* c, int which, const float** pe_enc, const float** pe
 }
 
 // ------------------------------------------------------------------ small helpers
-static inline size_t es_of(const dimx_ctx* c) { return dtype_size(c->at); }
-static inline int tpad(int T) { return (T + 7) / 8 * 8; }
 
-static int gemm_lin(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, GemmArgs& g) {
+int gemm_lin(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, GemmArgs& g) {
     gemm_args_init(g);
     g.in_dtype = c->at;
     g.A = A;
@@ -635,7 +633,7 @@ static int gemm_lin(const dimx_ctx* c, const void* A, int lda, const Linear& L, 
 // Perf mode (round 3): V leaves the fused q/k/v projection row-major like q and k -- three row-contiguous destinations, which
 // is what the two-phase 256 x 256 GEMM stores -- and the attention of attention_tr.hip reads it that way.  The f32 parity mode
 // and the 96-column heads of the legacy speaker VQ-VAE keep the transposed destination.
-static bool qkv_row_v(int at, int D) {
+bool qkv_row_v(int at, int D) {
     return at == DIMX_BF16 && D <= 64;
 }
 
@@ -662,8 +660,8 @@ static void set_qkv_out(GemmArgs& g, void* q, void* k, void* vt, int T, int H, i
     g.seg[2].D = D;
 }
 
-static void set_attn_packed(AttnArgs& a, int dtype, const void* q, const void* k, const void* vt, void* o, int B,
-                            int H, int Lq, int Lk, int D, int Tp_k, bool rowv = false) {
+void set_attn_packed(AttnArgs& a, int dtype, const void* q, const void* k, const void* vt, void* o, int B,
+                            int H, int Lq, int Lk, int D, int Tp_k, bool rowv) {
     memset(&a, 0, sizeof(a));
     const int segw = H * D;
     a.dtype = dtype;
@@ -697,15 +695,8 @@ static void set_attn_packed(AttnArgs& a, int dtype, const void* q, const void* k
 }
 
 // ------------------------------------------------------------------ sublayers of a transformer block
-// The four stacks (run_vq_blocks, run_xenc, dimx_decode_tf, gen_prefill) are sequences of these calls.  The buffers of a block, the
-// base of every stack's scratch struct: the f32 residual stream h [M, C]; in the operand type the LayerNorm output y, q / k / v(t),
-// the attention output o and the feed-forward hidden f; kw: the packed key-mask words of the prefill attention (AttnArgs.kwords)
-struct BlockBufs {
-    float* h;
-    void *y, *q, *k, *vt, *o, *f;
-    unsigned long long* kw = nullptr;   // the VQ stacks have none
-    size_t kw_cap = 0;
-};
+// The four stacks (run_vq_blocks, run_xenc, dimx_decode_tf, generate.hip's gen_prefill) are sequences of these calls over the
+// buffers of a block (BlockBufs, stages.hpp).
 
 // out[M, ldo] = act(A . W^T + bias) (+ residual [M, ldo], f32) as plain rows of out_dtype
 static int linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, int out_dtype, void* out, int ldo, hipStream_t st,
@@ -727,7 +718,7 @@ constexpr int kFusedMlpMinRows = 8192;
 
 // h += f2(act(f1(LayerNorm(h)))); with mlp (the weights as mlp_fused.hip chunk images; the decoder stacks pass nullptr) and
 // kFusedMlpMinRows rows the whole sublayer is one launch
-static int ff_sublayer(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& f1,
+int ff_sublayer(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& f1,
                        const Linear& f2, const void* mlp, int act, int M, int C, hipStream_t st) {
     if (mlp && M >= kFusedMlpMinRows) return launch_mlp_fused(b.h, mlp, f2.bias, ln_g, ln_b, M, C, f1.N, act, st);
     DIMX_TRY(launch_layernorm(c->at, b.h, b.y, ln_g, ln_b, M, C, st));
@@ -737,7 +728,7 @@ static int ff_sublayer(const dimx_ctx* c, const BlockBufs& b, const float* ln_g,
 
 // Self attention, first half: LayerNorm -> fused q/k/v projection into b.q / b.k / b.vt.  `a` leaves as the attention over them;
 // the caller adds scale and its stack's mask fields (lens, kmask / kmask_ld, causal) and hands it to attn_out.
-static int self_attn_qkv(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& qkv, int B,
+int self_attn_qkv(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& qkv, int B,
                          int T, int C, int heads, int D, AttnArgs& a, hipStream_t st) {
     const bool rowv = qkv_row_v(c->at, D);
     DIMX_TRY(launch_layernorm(c->at, b.h, b.y, ln_g, ln_b, B * T, C, st));
@@ -751,7 +742,7 @@ static int self_attn_qkv(const dimx_ctx* c, const BlockBufs& b, const float* ln_
 }
 
 // second half of both attentions: attention `a` (output b.o) -> h += o . Wout^T (+ bias)
-static int attn_out(const dimx_ctx* c, const BlockBufs& b, AttnArgs& a, const Linear& out, int C, hipStream_t st) {
+int attn_out(const dimx_ctx* c, const BlockBufs& b, AttnArgs& a, const Linear& out, int C, hipStream_t st) {
     a.kwords = b.kw; a.kwords_cap = b.kw_cap;
     DIMX_TRY(launch_attention(a, st));
     return residual_linear(c, b.o, a.H * a.D, out, a.B * a.Lq, b.h, C, st);
@@ -759,8 +750,8 @@ static int attn_out(const dimx_ctx* c, const BlockBufs& b, AttnArgs& a, const Li
 
 // Cross attention of the decoder stacks: LayerNorm -> q projection into b.q -> attention over the context K / V, which the caller
 // describes in `a` -> out-projection.  v_rows (gen_prefill, f32): V [B*H, Tp, 64] to transpose into the scratch a.vt before the attention.
-static int cross_attn_sublayer(const dimx_ctx* c, const BlockBufs& b, const XAttn& x, AttnArgs& a, const uint8_t* ctx_mask, int C,
-                               hipStream_t st, const float* v_rows = nullptr) {
+int cross_attn_sublayer(const dimx_ctx* c, const BlockBufs& b, const XAttn& x, AttnArgs& a, const uint8_t* ctx_mask, int C,
+                               hipStream_t st, const float* v_rows) {
     const int M = a.B * a.Lq, Tp = tpad(a.Lk);
     DIMX_TRY(launch_layernorm(c->at, b.h, b.y, x.ln_g, nullptr, M, C, st));
     DIMX_TRY(linear(c, b.y, C, x.qkv, M, c->at, b.q, a.H * a.D, st));
@@ -1100,30 +1091,10 @@ struct EncScratch : BlockBufs {
     void* xa;
     float* tmp;
 };
-struct CtxPersist {
-    void* ck[8];
-    void* cv[8];
-};
 struct DecScratch : BlockBufs {
     int32_t *inp, *tgt;
     uint8_t* kvm;
 };
-struct GenScratch {
-    void* sk[8];
-    void* sv[8];
-    float *x, *logits;
-    void *y, *o, *f;
-    float *qkv, *qc, *xr;  // f32 split-K slabs [kMaxSlabs][B, N] of the qkv / cross-q / residual projections
-    long st_qkv, st_qc, st_xr, st_lg;  // slab strides (elements)
-    int32_t* step;
-    unsigned* chain_ctr;  // [kChainSites][8][16] per-XCD arrival counters of the chain launch sites
-    void* qcb;                 // several samples per clip, bf16: the cross-attention queries [rows, inner] in the operand type
-    unsigned long long* kw;    // ... and the context mask as 64-bit validity words [clips][ceil(T / 64)] (attention_tr.hip)
-    size_t kw_cap;
-    int32_t* hist;             // [rows][T] the first layer's input token of every position (its self attention's table form)
-};
-constexpr int kChainSites = 32;
-constexpr int kChainSiteWords = 8 * 16 + 8 * 32;  // arrival counters [8][16] + claim stamps [8][32]
 
 static void plan_persist(const dimx_ctx* c, Arena& ar, int B, int T, CtxPersist& p) {
     const size_t es = es_of(c);
@@ -1150,9 +1121,6 @@ static void plan_enc(const dimx_ctx* c, Arena& ar, int B, int T, EncScratch& s) 
     s.kw_cap = (size_t)B * ((T + 63) / 64);
     s.kw = (unsigned long long*)ar.take(s.kw_cap * 8);
 }
-// number of decoder positions: SLMFT feeds / generates T-1 tokens (code/seq2seq_pretrain.py:469,500);
-// the legacy generator is teacher-forced on T-1 tokens but generates seq_len = T (code/seq2seq.py:256,300)
-static inline int gen_steps(const dimx_ctx* c, int T) { return c->variant == 1 ? T : T - 1; }
 static void plan_dec(const dimx_ctx* c, Arena& ar, int B, int T, DecScratch& s) {
     const int n = T - 1;
     const size_t M = (size_t)B * n, es = es_of(c);
@@ -1170,7 +1138,7 @@ static void plan_dec(const dimx_ctx* c, Arena& ar, int B, int T, DecScratch& s) 
     s.kw_cap = (size_t)B * ((T + 63) / 64);
     s.kw = (unsigned long long*)ar.take(s.kw_cap * 8);
 }
-static void plan_gen(const dimx_ctx* c, Arena& ar, int B, int T, GenScratch& s) {
+void plan_gen(const dimx_ctx* c, Arena& ar, int B, int T, GenScratch& s) {
     const size_t es = es_of(c);
     const int D = c->decg.dim, inner = c->decg.heads * c->decg.dim_head;
     const size_t per = (size_t)B * inner * T * es;
@@ -1199,21 +1167,9 @@ static void plan_gen(const dimx_ctx* c, Arena& ar, int B, int T, GenScratch& s) 
     s.hist = (int32_t*)ar.take((size_t)B * T * 4);
 }
 
-// Prompted generation (dimx_generate_prompted): the prompt of a call and the teacher-forced scratch of its prefill.
-// dimx_generate is the ld = Pmax = 1, step0 = 0 case.
-struct GenPrompt {
-    const int32_t* tok;  // [B, ld] the prompt's tokens, one row per CLIP
-    int ld, Pmax;
-    const int32_t* len;  // [B] prompt lengths (clamped to [step0 + 1, Pmax] by the sampler) or nullptr = Pmax
-    int step0;           // P0 - 1: positions 0 .. step0 - 1 are prefilled, the first decode step is step0
-};
-struct PrefillScratch : BlockBufs {
-    float* cvt;          // f32 mode: one layer's context V transposed to [B,H,64,Tp] (the f32 prefill attention reads V^T)
-    int32_t* inp;
-};
 // The scratch is sized for the WHOLE batch (B clips x n0 positions), not for a chunk of clips, and lies behind the generation
 // scratch: the prefill writes the K/V cache, which must outlive it, and nothing else of the generation scratch.
-static void plan_prefill(const dimx_ctx* c, Arena& ar, int B, int n0, int T, PrefillScratch& s) {
+void plan_prefill(const dimx_ctx* c, Arena& ar, int B, int n0, int T, PrefillScratch& s) {
     const size_t M = (size_t)B * n0, es = es_of(c);
     const int D = c->decg.dim, inner = c->decg.heads * c->decg.dim_head, np = tpad(n0);
     s.h = (float*)ar.take(M * D * 4);
@@ -1314,7 +1270,7 @@ static size_t workspace_bytes(const dimx_ctx* c, int B, int T, int S = 1) {
 
 // workspace of dimx_encode_ctx(for_generate = 1) + a prompted generation that prefills P0 - 1 positions: the generation
 // scratch and the prefill scratch behind it
-static size_t workspace_bytes_prompt(const dimx_ctx* c, int B, int T, int S, int P0) {
+size_t workspace_bytes_prompt(const dimx_ctx* c, int B, int T, int S, int P0) {
     const size_t base = workspace_bytes(c, B, T, S);
     if (P0 <= 1 || T < 2) return base;
     Arena p(nullptr, 0);
@@ -1354,7 +1310,7 @@ static int run_xenc(const dimx_ctx* c, const EncGeom& eg, const XEnc& e, const v
     return DIMX_OK;
 }
 
-static int check_common(dimx_handle h, int B, int T, void* ws, size_t ws_bytes, int need, int S = 1) {
+int check_common(dimx_handle h, int B, int T, void* ws, size_t ws_bytes, int need, int S) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
     DIMX_REQUIRE(B >= 1 && T >= 1 && T <= h->d.max_seq_len, DIMX_ERR_ARG, "B=%d T=%d out of range (T <= %d)", B, T,
                  h->d.max_seq_len);
@@ -1444,7 +1400,7 @@ static int clip_groups_close(dimx_handle h, const ClipGroups& cg, int rc) {
     return rc != DIMX_OK ? rc : jrc;
 }
 
-static Arena scratch_arena(const dimx_ctx* c, void* ws, size_t ws_bytes, int B, int T, CtxPersist* cp) {
+Arena scratch_arena(const dimx_ctx* c, void* ws, size_t ws_bytes, int B, int T, CtxPersist* cp) {
     Arena p(ws, ws_bytes);
     CtxPersist tmp;
     plan_persist(c, p, B, T, cp ? *cp : tmp);
@@ -1868,854 +1824,6 @@ int dimx_decode_tf(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, c
     return DIMX_OK;
 }
 
-}  // extern "C"
-
-namespace dimx {
-
-static void chain_desc(ChainGemmDesc& d, const Linear& L) { d.W = L.w; d.N = L.N; d.K = L.K; d.ldw = L.Kp; }
-
-// The chain kernels run when: bf16 operands, one sample per clip, a single clip group, <= 256 rows, a 256-CU device on
-// which the placement probe passed, and every launch site's LDS plan fits.
-static bool gen_use_chain(dimx_handle h, int B, int S, int grp) {
-    if (!h->use_chain || h->at != DIMX_BF16 || S != 1 || grp != 0 || h->gen_groups > 1 || !h->chain_err_dev) return false;
-    const DecGeom& dg = h->decg;
-    ChainArgs c;
-    memset(&c, 0, sizeof(c));
-    c.B = B;
-    c.C = dg.dim;
-    const XAttn& sa = h->dec.self_[0];
-    const XAttn& ca = h->dec.cross[0];
-    chain_desc(c.g1, sa.out);
-    c.lda1 = dg.heads * dg.dim_head;
-    chain_desc(c.g2, ca.qkv);
-    if (!chain_supported(c, h->cu_count)) return false;
-    chain_desc(c.g2, h->dec.logits);
-    c.g1.W = nullptr;
-    return chain_supported(c, h->cu_count) && 3 * dg.depth + 1 <= kChainSites;
-}
-
-// several samples per clip in the bf16 mode: the decode cross attention runs on attention_tr.hip (64-wide heads)
-static bool gen_multi_tr(dimx_handle h, int S) {
-    return S > 1 && h->multi_tr && h->at == DIMX_BF16 && h->decg.dim_head == 64;
-}
-
-// Every projection of the decode step whose output is a small [B, N] f32 matrix is a split-K GEMM writing per-split slabs;
-// the consumer (LayerNorm / attention / sampler) adds the slabs in order: deterministic, no atomics, and
-// the residual add rides along in the pre-norm kernel.
-static int slab_gemm_rows(dimx_handle h, int B, hipStream_t st, const void* A, int lda, const Linear& L, float* out, long stride,
-                          int* nsl) {
-    GemmArgs g;
-    gemm_lin(h, A, lda, L, B, g);
-    g.x3_decode = 1;   // f32 parity mode: the split-bf16 kernel, whatever B is
-    g.out_dtype = DIMX_F32;
-    g.out_slabs = 1;
-    // round 4: the f32 parity mode splits K too.  Slabs are plain stores added in slab order by the consumer -- deterministic,
-    // no atomics -- which is all "fixed summation order" asks for; without the split the mode's 64 x 64 tiles left most of
-    // the chip idle (M = 256: 72 blocks for the 1152-wide projections, 48 for cross-q, 32 for the logits; the K = 4608
-    // feed-forward projection ran 144 k-tiles on 72 CUs = 70 us): 261 of the mode's 505 ms per batch (profiles/r04_parity_*).
-    static const bool f32_split = getenv("DIMX_F32_NO_SPLIT") == nullptr;
-    if (f32_split) g.allow_splitk = 1;
-    g.slab_stride = stride;
-    gemm_set_plain_out(g, out, L.N);
-    *nsl = gemm_plan_splits(g);
-    g.force_splitk = *nsl;
-    return launch_gemm(g, st);
-}
-
-// May the first layer's q/k/v come from the table?  Only a decoder whose layer-0 input is the token embedding alone.
-static bool qkv0_table_supported(dimx_handle h) {
-    const DecGeom& dg = h->decg;
-    const int N = 3 * dg.heads * dg.dim_head;
-    return h->use_qkv0_table && !dg.abs_pos && h->dec.self_[0].qkv.N == N && N % 4 == 0 && N <= 12 * 256 && dg.dim % 4 == 0 &&
-           dg.dim / 2 <= 16 * 64;
-}
-
-// The table for projection launches of M rows: ceil(num_tokens / M) rounds of {embedding rows of the next M ids, the first layer's
-// pre-norm, the step's own q/k/v projection at M rows, slabs added in order into the table rows}; the last round (and M >
-// num_tokens) is padded by repeating the last id.  M is the step's M because the split count, hence the summation order,
-// follows from it (gemm_plan_splits).  Runs on the generation scratch, which is free before the first step; s.step must read step0.
-static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream_t st, int step0 = 0) {
-    const DecGeom& dg = h->decg;
-    const int DD = dg.dim, V = dg.num_tokens, N = h->dec.self_[0].qkv.N;
-    if (h->qkv0_table && h->qkv0_M == M && h->qkv0_at == h->at && h->qkv0_epoch == h->dec_epoch) return DIMX_OK;
-    if (!h->qkv0_table) {
-        DIMX_HIP(hipMalloc((void**)&h->qkv0_table, (size_t)V * N * sizeof(float)));
-        h->graph_valid = false;
-    }
-    h->qkv0_epoch = 0;
-    const int rounds = (V + M - 1) / M;
-    int32_t* ids = (int32_t*)s.logits;   // rounds * M < V + M ids; the logits slabs hold 8 * M * V words
-    DIMX_TRY(launch_iota_clamp(ids, rounds * M, V, st));
-    for (int r = 0; r < rounds; ++r) {
-        int ns = 0;
-        DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, ids + (size_t)r * M, nullptr, 0, s.step, s.x, M, 1, st, nullptr, 0.f, 1, step0));
-        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s.st_xr, s.y, h->dec.self_[0].ln_g, M, DD, st));
-        DIMX_TRY(slab_gemm_rows(h, M, st, s.y, DD, h->dec.self_[0].qkv, s.qkv, s.st_qkv, &ns));
-        DIMX_TRY(launch_sum_slabs_rows(s.qkv, ns, s.st_qkv, h->qkv0_table, r * M, V, M, N, st));
-    }
-    // the K / V columns in the operand type for the first layer's self attention in the table form (bf16 mode; the f32 mode reads
-    // the table): same key and invalidation as the table, because it is rebuilt whenever the table is
-    if (h->use_kv0_table && h->at == DIMX_BF16) {
-        const int inner = N / 3;
-        if (!h->kv0_image) {
-            DIMX_HIP(hipMalloc(&h->kv0_image, (size_t)V * 2 * inner * sizeof(bf16)));
-            h->graph_valid = false;
-        }
-        DIMX_TRY(launch_kv0_image(h->qkv0_table, N, V, inner, 2 * inner, h->kv0_image, st));
-    }
-    h->qkv0_M = M;
-    h->qkv0_at = h->at;
-    h->qkv0_epoch = h->dec_epoch;
-    ++h->qkv0_builds;
-    return DIMX_OK;
-}
-
-// what every gen_step of one generate call shares (built once in generate_impl)
-struct GenCall {
-    const CtxPersist& cp;
-    const GenScratch& s;
-    const GenPrompt& pr;
-    const uint8_t* ctx_mask;
-    int Btot, T, S, top_k;   // sequences of the batch, frames, samples per clip
-    float temperature;
-    const float* noise;
-    uint64_t seed;
-    int32_t* tokens;
-    float* logits_out;
-    const float* qkv0;   // the first layer's q/k/v table or nullptr
-    const BeamCall* beam = nullptr;   // beam search: the selection and the cache reorder end the step in the sampler's place
-    const void* kv0 = nullptr;        // the first layer's K / V table (the bf16 image, or the q/k/v table itself in the f32 mode): its self
-                                      // attention reads rows of it through s.hist and keeps no cache; nullptr = the cache
-};
-
-// one decoder step for the clip group `grp` = rows [row0, row0 + B) of a batch of gc.Btot sequences:
-// x = emb(token) -> 4 x {self, cross, ff} -> logits -> sample -> step += 1
-static int gen_step(dimx_handle h, const GenCall& gc, int row0, int B, int grp, hipStream_t st, bool embed_only) {
-    const GenScratch& s0 = gc.s;
-    const GenPrompt& pr = gc.pr;
-    const int T = gc.T, S = gc.S;
-    const uint8_t* ctx_mask = gc.ctx_mask;   // advanced to this group's rows below, like tokens and logits_out
-    int32_t* tokens = gc.tokens;
-    float* logits_out = gc.logits_out;
-    const DecGeom& dg = h->decg;
-    const int DD = dg.dim, heads = dg.heads, D = dg.dim_head, inner = heads * D;
-    const int V = dg.num_tokens, n = gen_steps(h, T), Tp = tpad(T);
-    const float* pos = dg.abs_pos ? h->dec.pos_emb : nullptr;
-    const float pos_scale = 1.0f / sqrtf((float)DD);
-    const size_t es = es_of(h);
-    const float scale = 1.0f / sqrtf((float)D);
-    // this group's slices of every per-clip buffer
-    GenScratch s = s0;
-    auto boff = [&](void* p, size_t per_row_bytes) { return (void*)((unsigned char*)p + (size_t)row0 * per_row_bytes); };
-    s.x = s0.x + (size_t)row0 * DD;
-    s.y = boff(s0.y, DD * es);
-    s.qkv = s0.qkv + (size_t)row0 * 3 * inner;
-    s.qc = s0.qc + (size_t)row0 * inner;
-    s.xr = s0.xr + (size_t)row0 * DD;
-    s.o = boff(s0.o, inner * es);
-    s.f = boff(s0.f, (size_t)DD * dg.ff_mult * es);
-    s.logits = s0.logits + (size_t)row0 * V;
-    s.step = s0.step + 16 * grp;
-    s.hist = s0.hist + (size_t)row0 * T;
-    // with S samples per clip, rows are samples (row = clip * S + sample); start / mask / cross K/V are per clip
-    const int clip0 = row0 / S, nclip = B / S;
-    // the first step's input is column step0 of the prompt; later steps inside a clip's prompt are forced by the sampler
-    const int32_t* start = pr.tok + (size_t)clip0 * pr.ld + pr.step0;
-    const int32_t* forced = pr.Pmax > 1 ? pr.tok + (size_t)clip0 * pr.ld : nullptr;
-    const int32_t* forced_len = pr.len ? pr.len + clip0 : nullptr;
-    ctx_mask += (size_t)clip0 * T;
-    tokens += (size_t)row0 * n;
-    if (logits_out) logits_out += (size_t)row0 * n * V;
-    // round 4: the sampler that writes the next step's embedding row also writes the first layer's pre-norm of it, so a step
-    // starts with y = LayerNorm(x) in place.  With the first layer's q/k/v table (gc.qkv0) both write the token's table row into slab 0
-    // of s.qkv instead, and layer 0 starts at its attention.
-    if (embed_only) {  // step 0 input = embedding of the start token (later steps: fused into the sampler)
-        DIMX_TRY(launch_embed_step(h->dec.tok_emb, DD, V, start, tokens, n, s.step, s.x, B, S, st, pos, pos_scale, pr.ld, pr.step0));
-        if (gc.qkv0)   // the first layer's q/k/v of the start token: a table row into slab 0 (nothing reads y before the layer rewrites it)
-            DIMX_TRY(launch_gather_start_rows(gc.qkv0, 3 * inner, V, start, S, s.qkv, B, st, pr.ld, gc.kv0 ? s.hist : nullptr, T));
-        else
-            DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
-        return DIMX_OK;
-    }
-    auto slab_gemm = [&](const void* A, int lda, const Linear& L, float* out, long stride, int* nsl) -> int {
-        return slab_gemm_rows(h, B, st, A, lda, L, out, stride, nsl);
-    };
-    // XCD-local chain kernels (chain.hip) replace {projection, residual + LayerNorm, projection} triples by one launch
-    const bool chain = gen_use_chain(h, B, S, grp);
-    // deferred LayerNorm (chain.hip): the two chain launches of a layer write x and bf16(x) un-normalised + partial row
-    // sums; cross-q (inside chain A) and ff1 (the next launch) run on gamma-scaled weights and correct their results
-    const bool defer = chain && h->defer_ln && h->chain_stats_dev && h->dec.cross[0].q_ln.w && h->dec.ff[0].f1_ln.w;
-    auto chain_site = [&](int site, const void* A1, int lda1, const Linear* W1, int nslab, const float* gamma,
-                          const Linear* W2, float* out2, int ld_out2, const float* colsum2 = nullptr) -> int {
-        ChainArgs c;
-        memset(&c, 0, sizeof(c));
-        c.B = B;
-        if (defer && W1) {
-            c.defer = 1;
-            c.stats = h->chain_stats_dev;
-            c.colsum2 = colsum2;
-        }
-        if (W1) {
-            chain_desc(c.g1, *W1);
-            c.A1 = A1;
-            c.lda1 = lda1;
-            c.xr = s.xr;
-        }
-        c.x = s.x;
-        c.C = DD;
-        c.slabs = nslab ? s.xr : nullptr;
-        c.nslab = nslab;
-        c.slab_stride = s0.st_xr;
-        c.y = s.y;
-        c.gamma = gamma;
-        if (W2) {
-            chain_desc(c.g2, *W2);
-            c.out2 = out2;
-            c.ld_out2 = ld_out2;
-        }
-        c.counters = s0.chain_ctr + (size_t)site * kChainSiteWords;
-        c.seen = c.counters + 8 * 16;
-        c.step = s.step + 9;   // steps done in this call (== the step counter unless a prompt was prefilled)
-        c.err = h->chain_err_dev;
-        c.fault = h->chain_fault_inject > 0 ? 1 : 0;
-        return launch_chain(c, st);
-    };
-    // round 5: the attention half of a layer as one XCD-local launch (chain.hip xcd_layer_kernel; DIMX_NO_LAYER_CHAIN=1: the four
-    // launches, for A/B runs)
-    // Online generation: the cross attention's key count follows the step counter.  Only the one-query kernels of decode_attn.hip
-    // have that form, so the layer kernel and the MFMA multi-query route below are not taken.
-    const bool win = h->xwin_on != 0;
-    const bool layer_kernel = h->use_layer_chain && chain && defer && S == 1 && 4 * dg.depth + 1 <= kChainSites && !win;
-    auto layer_args = [&](int l, const DecodeAttnArgs& sa, const DecodeAttnArgs& ca, LayerChainArgs& lc) -> bool {
-        const Linear& so = h->dec.self_[l].out;
-        const Linear& cq = h->dec.cross[l].q_ln;
-        const Linear& co = h->dec.cross[l].out;
-        if (!so.w || !cq.w || !co.w || !h->dec.cross[l].q_ln_colsum) return false;
-        lc.B = B;
-        lc.C = DD;
-        lc.sa = sa;
-        lc.ca = ca;
-        chain_desc(lc.g_so, so);
-        chain_desc(lc.g_cq, cq);
-        chain_desc(lc.g_co, co);
-        lc.o = s.o;
-        lc.ld_o = inner;
-        lc.x = s.x;
-        lc.y = s.y;
-        lc.stats = h->chain_stats_dev;
-        lc.colsum_cq = h->dec.cross[l].q_ln_colsum;
-        lc.qc = s.qc;
-        lc.ld_qc = inner;
-        lc.counters = s0.chain_ctr + (size_t)(3 * dg.depth + 1 + l) * kChainSiteWords;
-        lc.seen = lc.counters + 8 * 16;
-        lc.step = s.step + 9;
-        lc.err = h->chain_err_dev;
-        lc.fault = h->chain_fault_inject > 0 ? 1 : 0;
-        lc.sc_stride = (T + 15) / 16 * 16;
-        lc.prof = h->layer_prof_dev ? h->layer_prof_dev + (size_t)l * 256 * 16 : nullptr;
-        return true;
-    };
-    int pending = 0;  // slabs of the previous residual projection not yet folded into x
-    for (int l = 0; l < dg.depth; ++l) {
-        GemmArgs g;
-        DecodeAttnArgs a;
-        int ns = 0;
-        if (l > 0)
-            DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.self_[l].ln_g, B, DD, st));
-        if (l == 0 && gc.qkv0)
-            ns = 1;   // slab 0 already holds this token's q/k/v (the sampler / the start-token step copied the table row)
-        else
-            DIMX_TRY(slab_gemm(s.y, DD, h->dec.self_[l].qkv, s.qkv, s0.st_qkv, &ns));
-        // the two attentions' arguments (self: q / new k / new v are the projection's split-K slabs; cross: the context K/V)
-        DecodeAttnArgs sa, ca;
-        memset(&sa, 0, sizeof(sa));
-        sa.dtype = h->at;
-        sa.q = s.qkv;
-        sa.q_ld = 3 * inner;
-        sa.q_f32 = 1;
-        sa.nslab = ns;
-        sa.slab_stride = s0.st_qkv;
-        sa.knew = s.qkv + inner;
-        sa.vnew = s.qkv + 2 * inner;
-        sa.kv_ld = 3 * inner;
-        sa.kcache = boff(s0.sk[l], (size_t)heads * T * 64 * es);
-        sa.vcache = boff(s0.sv[l], (size_t)heads * T * 64 * es);
-        sa.Tmax = T;
-        sa.out = s.o;
-        sa.o_ld = inner;
-        sa.B = B;
-        sa.H = heads;
-        sa.step = s.step;
-        sa.scale = scale;
-        if (l == 0 && gc.kv0) {   // K / V of position j = the table row of the row's j-th input token; no append
-            sa.tab = gc.kv0;
-            sa.tab_rows = V;
-            if (h->at == DIMX_BF16) { sa.tab_ld = 2 * inner; sa.tab_koff = 0; sa.tab_voff = inner; }
-            else { sa.tab_ld = 3 * inner; sa.tab_koff = inner; sa.tab_voff = 2 * inner; }
-            sa.hist = s.hist;
-            sa.hist_ld = T;
-        }
-        memset(&ca, 0, sizeof(ca));
-        ca.dtype = h->at;
-        ca.q = s.qc;
-        ca.q_ld = inner;
-        ca.q_f32 = 1;
-        ca.nslab = 1;
-        ca.slab_stride = s0.st_qc;
-        ca.kcache = (unsigned char*)gc.cp.ck[l] + (size_t)clip0 * heads * Tp * 64 * es;
-        ca.vcache = (unsigned char*)gc.cp.cv[l] + (size_t)clip0 * heads * Tp * 64 * es;
-        ca.Tmax = Tp;
-        ca.out = s.o;
-        ca.o_ld = inner;
-        ca.B = S > 1 ? nclip : B;
-        ca.rows_per_clip = S;
-        ca.H = heads;
-        ca.n_keys = T;
-        ca.kmask = ctx_mask;
-        ca.kmask_ld = T;
-        ca.scale = scale;
-        if (win) {
-            ca.win = 1;
-            ca.lookahead = h->xwin_lookahead;
-            ca.step = s.step;
-        }
-        if (defer && layer_kernel) {
-            // round 5: self attention -> out-projection -> cross-q -> cross attention -> out-projection as ONE XCD-local launch
-            LayerChainArgs lc;
-            memset(&lc, 0, sizeof(lc));
-            if (layer_args(l, sa, ca, lc) && layer_chain_supported(lc, h->cu_count)) {
-                DIMX_TRY(launch_layer_chain(lc, st));
-                goto feed_forward;
-            }
-        }
-        DIMX_TRY(launch_decode_attn(sa, st));
-        if (chain) {  // self out-projection -> x += . -> LayerNorm -> cross q-projection
-            if (defer)
-                DIMX_TRY(chain_site(3 * l, s.o, inner, &h->dec.self_[l].out, 0, h->dec.cross[l].ln_g, &h->dec.cross[l].q_ln,
-                                    s.qc, inner, h->dec.cross[l].q_ln_colsum));
-            else
-                DIMX_TRY(chain_site(3 * l, s.o, inner, &h->dec.self_[l].out, 0, h->dec.cross[l].ln_g, &h->dec.cross[l].qkv,
-                                    s.qc, inner));
-            ns = 1;
-        } else {
-            DIMX_TRY(slab_gemm(s.o, inner, h->dec.self_[l].out, s.xr, s0.st_xr, &pending));
-            DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.cross[l].ln_g, B, DD, st));
-            if (gen_multi_tr(h, S) && !win) {
-                // round 6, best-of-N in one pass (code/x_engine_pt.py:257), bf16: the S queries of a clip against its context K/V on the
-                // matrix cores -- the prefill attention kernel with Lq = S (one 128-query item per (clip, head), K / V streamed once),
-                // queries in the operand type from a plain projection (rows = clips x S: no split-K needed).  The VALU multi-query
-                // kernel it replaces ran 118 us per launch at 256 clips x 10 samples, 3 x its HBM floor (profiles/r06_samples10.txt).
-                gemm_lin(h, s.y, DD, h->dec.cross[l].qkv, B, g);
-                g.out_dtype = h->at;
-                gemm_set_plain_out(g, (unsigned char*)s0.qcb + (size_t)row0 * inner * es, inner);
-                DIMX_TRY(launch_gemm(g, st));
-                AttnArgs ta;
-                memset(&ta, 0, sizeof(ta));
-                ta.dtype = h->at;
-                ta.q = (unsigned char*)s0.qcb + (size_t)row0 * inner * es;
-                ta.q_sb = (long)S * inner; ta.q_st = inner; ta.q_sh = D;
-                ta.k = ca.kcache; ta.k_sb = (long)heads * Tp * D; ta.k_sh = (long)Tp * D; ta.k_st = D;
-                ta.vt = ca.vcache; ta.v_rows = 1; ta.v_sb = (long)heads * Tp * D; ta.v_sh = (long)Tp * D; ta.v_st = D;
-                ta.o = s.o; ta.o_sb = (long)S * inner; ta.o_st = inner; ta.o_sh = D;
-                ta.B = nclip; ta.H = heads; ta.Lq = S; ta.Lk = T; ta.D = D;
-                ta.scale = scale;
-                ta.kmask = ctx_mask; ta.kmask_ld = T;
-                ta.kwords = s0.kw + (size_t)clip0 * ((T + 63) / 64); ta.kwords_cap = s0.kw_cap - (size_t)clip0 * ((T + 63) / 64);
-                ta.kwords_ready = 1;   // packed once per generation (generate_impl)
-                DIMX_TRY(launch_attention_tr(ta, st));
-                goto cross_out;
-            }
-            DIMX_TRY(slab_gemm(s.y, DD, h->dec.cross[l].qkv, s.qc, s0.st_qc, &ns));
-        }
-        ca.nslab = ns;
-        DIMX_TRY(launch_decode_attn(ca, st));
-    cross_out:
-        if (chain) {  // cross out-projection -> x += . -> LayerNorm (feed-forward input)
-            DIMX_TRY(chain_site(3 * l + 1, s.o, inner, &h->dec.cross[l].out, 0, h->dec.ff[l].ln_g, nullptr, nullptr, 0));
-        } else {
-            DIMX_TRY(slab_gemm(s.o, inner, h->dec.cross[l].out, s.xr, s0.st_xr, &pending));
-            DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.ff[l].ln_g, B, DD, st));
-        }
-    feed_forward:
-        gemm_lin(h, s.y, DD, defer ? h->dec.ff[l].f1_ln : h->dec.ff[l].f1, B, g);
-        g.x3_decode = 1;
-        if (defer) {
-            g.ln_stats = h->chain_stats_dev;
-            g.ln_err = h->chain_err_dev;
-            g.ln_colsum = h->dec.ff[l].f1_ln_colsum;
-            g.ln_C = DD;
-        }
-        g.out_dtype = h->at;
-        g.act = ACT_GELU_ERF;
-        gemm_set_plain_out(g, s.f, DD * dg.ff_mult);
-        DIMX_TRY(launch_gemm(g, st));
-        DIMX_TRY(slab_gemm(s.f, DD * dg.ff_mult, h->dec.ff[l].f2, s.xr, s0.st_xr, &pending));
-    }
-    int nlg = 0;
-    if (chain && !h->dec.logits.bias) {  // x += feed-forward slabs -> final LayerNorm -> logits (the chain kernel has no bias input:
-                                         // a checkpoint with the optional to_logits.bias takes the two launches below)
-        DIMX_TRY(chain_site(3 * dg.depth, nullptr, 0, nullptr, pending, h->dec.final_g, &h->dec.logits, s.logits, V));
-        nlg = 1;
-    } else {
-        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, pending, s0.st_xr, s.y, h->dec.final_g, B, DD, st));
-        DIMX_TRY(slab_gemm(s.y, DD, h->dec.logits, s.logits, s0.st_lg, &nlg));
-    }
-    if (gc.beam) {
-        // Beam search (beam.hip): rows clip * S + w are the S hypotheses of a clip.  The selection writes column c of the token rows in
-        // the new order, the next step's embedding / q/k/v table rows, and advances the step word; the reorder then permutes cache
-        // positions 0 .. c and token columns < c by parent beam, reading c as the advanced word - 1.
-        const BeamCall& bm = *gc.beam;
-        BeamSelectArgs bs;
-        bs.logits = s.logits; bs.nslab = nlg; bs.slab_stride = s0.st_lg; bs.nclip = nclip; bs.W = S;
-        bs.step_dev = s.step; bs.step_rw = s.step; bs.done_ctr = (unsigned*)(s.step + 8); bs.epoch_rw = s.step + 9; bs.dev_params = s.step + 2;
-        bs.prompt = forced; bs.prompt_ld = pr.ld; bs.prompt_max = pr.Pmax; bs.prompt_len = forced_len;
-        bs.lens = bm.lens ? bm.lens + clip0 : nullptr; bs.len_off = T - n;
-        bs.cum_in = bm.cum + row0; bs.cum_out = bm.cum + row0; bs.parent = bm.parent + row0;
-        bs.tokens = tokens; bs.backptr = bm.backptr ? bm.backptr + (size_t)row0 * n : nullptr; bs.tok_ld = n; bs.logits_out = logits_out;
-        bs.emb_table = h->dec.tok_emb; bs.emb_C = DD; bs.x_next = s.x;
-        bs.qkv0_table = gc.qkv0; bs.qkv0_out = s.qkv; bs.qkv0_N = 3 * inner;
-        DIMX_TRY(launch_beam_select(bs, st));
-        if (!gc.qkv0) DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s0.st_xr, s.y, h->dec.self_[0].ln_g, B, DD, st));
-        BeamReorderArgs br;
-        for (int l = 0; l < dg.depth; ++l) {
-            br.buf[2 * l] = boff(s0.sk[l], (size_t)heads * T * 64 * es);
-            br.buf[2 * l + 1] = boff(s0.sv[l], (size_t)heads * T * 64 * es);
-        }
-        br.nbuf = 2 * dg.depth; br.es = (int)es; br.nclip = nclip; br.W = S; br.H = heads; br.T = T;
-        br.parent = bs.parent; br.step_dev = s.step; br.step_back = 1;
-        br.tokens = tokens; br.backptr = bs.backptr; br.tok_ld = n;
-        return launch_beam_reorder(br, st);
-    }
-    SampleArgs sm;
-    sm.logits = s.logits; sm.ld_logits = V; sm.R = B; sm.nslab = nlg; sm.slab_stride = s0.st_lg; sm.row0 = row0; sm.rows_total = gc.Btot;
-    sm.top_k = gc.top_k; sm.noise = gc.noise; sm.filt.kind = h->filter_kind;
-    sm.temperature = gc.temperature; sm.seed = gc.seed;   // read from the parameter block (dev_params) instead, like filt.a / b
-    sm.step_dev = s.step; sm.step_rw = s.step; sm.dev_params = s.step + 2; sm.done_ctr = (unsigned*)(s.step + 8); sm.epoch_rw = s.step + 9;
-    sm.tokens = tokens; sm.tok_ld = n; sm.tok_col_from_step = 1; sm.logits_out = logits_out; sm.logits_out_ld = n;
-    sm.emb_table = h->dec.tok_emb; sm.emb_C = DD; sm.x_next = s.x; sm.pos_table = pos; sm.pos_scale = pos_scale; sm.pos_rows = n;
-    sm.y_next = gc.qkv0 ? nullptr : s.y; sm.y_gamma = gc.qkv0 ? nullptr : h->dec.self_[0].ln_g; sm.y_dtype = h->at;
-    sm.qkv0_table = gc.qkv0; sm.qkv0_out = s.qkv; sm.qkv0_N = 3 * inner;
-    if (gc.kv0) { sm.hist = s.hist; sm.hist_ld = T; }
-    sm.prompt = forced; sm.prompt_ld = pr.ld; sm.prompt_max = pr.Pmax; sm.prompt_len = forced_len; sm.prompt_div = S;
-    return launch_sample(sm, st);
-}
-
-// Prefill of a prompted generation: the teacher-forced decoder stack of dimx_decode_tf over the positions 0 .. n0 - 1 of every
-// clip (no key mask), every layer's self-attention K / V stored into the generation cache [B*S, H, T, 64] (kv_prefill.hip), no
-// output head, and the last layer stops after its q/k/v projection -- its attentions and feed-forward feed nothing.
-// Cross attention reads the context K / V where dimx_encode_ctx(for_generate = 1) left them, [B, H, Tp, 64]: the bf16
-// attention takes that layout as it is (row-major V); the f32 attention reads V^T, so the f32 mode transposes one layer's V
-// into scratch first (a copy, not a second projection of the context).
-static int gen_prefill(dimx_handle h, const CtxPersist& cp, const GenScratch& gs, const PrefillScratch& s, const GenPrompt& pr,
-                       const uint8_t* ctx_mask, int B, int T, int S, int32_t* tokens, hipStream_t st) {
-    const DecGeom& dg = h->decg;
-    const int n0 = pr.step0, M = B * n0, DD = dg.dim, heads = dg.heads, D = dg.dim_head;
-    const int np = tpad(n0), Tp = tpad(T), V = dg.num_tokens;
-    DIMX_TRY(launch_prompt_rows(pr.tok, pr.ld, B, n0, V, S, s.inp, tokens, gen_steps(h, T), st));
-    DIMX_TRY(launch_gather_rows(DIMX_F32, h->dec.tok_emb, DD, V, s.inp, s.h, DD, M, DD, st));
-    const bool rowv = qkv_row_v(h->at, D);
-    for (int l = 0; l < dg.depth; ++l) {
-        AttnArgs a;
-        DIMX_TRY(self_attn_qkv(h, s, h->dec.self_[l].ln_g, nullptr, h->dec.self_[l].qkv, B, n0, DD, heads, D, a, st));
-        DIMX_TRY(launch_kv_rows_to_cache(h->at, s.k, gs.sk[l], B, n0, heads, T, S, st));
-        if (rowv)
-            DIMX_TRY(launch_kv_rows_to_cache(h->at, s.vt, gs.sv[l], B, n0, heads, T, S, st));
-        else
-            DIMX_TRY(launch_kv_vt_to_cache((const float*)s.vt, np, (float*)gs.sv[l], B, n0, heads, T, S, st));
-        if (l == dg.depth - 1) break;
-        a.scale = 1.0f / sqrtf((float)D); a.causal = 1;
-        DIMX_TRY(attn_out(h, s, a, h->dec.self_[l].out, DD, st));
-        // cross attention over the context K / V of the generation layout [B,H,Tp,64]; the f32 attention reads V^T from s.cvt
-        set_attn_packed(a, h->at, s.q, cp.ck[l], rowv ? cp.cv[l] : s.cvt, s.o, B, heads, n0, T, D, Tp, rowv);
-        a.k_sb = (long)heads * Tp * D; a.k_sh = (long)Tp * D; a.k_st = D;
-        if (rowv) { a.v_sb = a.k_sb; a.v_sh = a.k_sh; a.v_st = D; }
-        DIMX_TRY(cross_attn_sublayer(h, s, h->dec.cross[l], a, ctx_mask, DD, st, rowv ? nullptr : (const float*)cp.cv[l]));
-        DIMX_TRY(ff_sublayer(h, s, h->dec.ff[l].ln_g, nullptr, h->dec.ff[l].f1, h->dec.ff[l].f2, nullptr, ACT_GELU_ERF, M, DD, st));
-    }
-    return DIMX_OK;
-}
-
-}  // namespace dimx
-
-extern "C" {
-
-// One implementation for dimx_generate (pr = {start, 1, 1, NULL, 0}) and dimx_generate_prompted.  keep_prefill: the call repeats
-// a generation whose prefill already ran in this workspace (the regeneration after a chain fault): the decode steps write cache
-// positions >= step0 and token / logit columns >= step0 only, so the prefix is intact and only the counters start over.
-static int generate_impl(dimx_handle h, const dimx::GenPrompt& pr, bool keep_prefill, const uint8_t* ctx_mask, int B, int T, int n_samples,
-                         float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens,
-                         float* logits_out, void* ws, size_t ws_bytes, void* stream, bool* chain_used, bool prefill_only = false,
-                         const dimx::BeamCall* beam = nullptr) {
-    const int32_t* start = pr.tok;
-    const int S = n_samples < 1 ? 1 : n_samples;
-    if (h && h->filter_kind != DIMX_FILTER_TOP_K) top_k = 0;   // the other kinds ignore the call's k (and it keys the step graph)
-    DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
-                 "generate: n_samples %d not in {1,2,4,5,8,10}", n_samples);
-    DIMX_TRY(check_common(h, B, T, ws, ws_bytes, COMP_DEC, S));
-    DIMX_REQUIRE(start && ctx_mask && tokens && T >= 2, DIMX_ERR_ARG, "generate: null argument or T < 2");
-    DIMX_REQUIRE(h->ctx_ready && h->ctx_B == B && h->ctx_T == T && h->ctx_ws == ws && h->ctx_for_generate,
-                 DIMX_ERR_STATE, "generate: call dimx_encode_ctx(for_generate=1) with the same B, T, ws first");
-    hipStream_t st = (hipStream_t)stream;
-    CtxPersist cp;
-    Arena ar = scratch_arena(h, ws, ws_bytes, B, T, &cp);
-    GenScratch s;
-    const int R = B * S;  // sequences generated in this call
-    plan_gen(h, ar, R, T, s);
-    PrefillScratch ps;
-    if (pr.step0 > 0) plan_prefill(h, ar, B, pr.step0, T, ps);
-    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "generate: workspace overflow");
-    const int n = gen_steps(h, T);
-    const int nrun = n - pr.step0;   // decode steps of this call
-    if (h->use_chain && h->at == DIMX_BF16 && !h->chain_err_dev) {
-        DIMX_HIP(hipMalloc((void**)&h->chain_err_dev, 64));
-        DIMX_HIP(hipMemset(h->chain_err_dev, 0, 64));
-        DIMX_HIP(hipMalloc((void**)&h->chain_stats_dev, 8 * 32 * 32 * 2 * sizeof(float)));
-        DIMX_HIP(hipMemset(h->chain_stats_dev, 0, 8 * 32 * 32 * 2 * sizeof(float)));
-        DIMX_HIP(hipHostMalloc((void**)&h->chain_err_host, 64, hipHostMallocDefault));
-        *h->chain_err_host = 0;
-        DIMX_HIP(hipEventCreateWithFlags(&h->chain_err_ev, hipEventDisableTiming));
-    }
-    DIMX_HIP(hipMemsetAsync(s.chain_ctr, 0, (size_t)kChainSites * kChainSiteWords * 4, st));
-    // step / done counters = 0; temperature, seed and the sampler's global row window go to device memory so that
-    // the captured step graph is independent of them
-    DIMX_TRY(launch_gen_params(s.step, dimx_ctx::kMaxGroups, temperature, seed, h->shard_row_off * S,
-                               h->shard_rows_total * S, st, pr.step0, h->filter_a, h->filter_b));
-    if (gen_multi_tr(h, S)) DIMX_TRY(launch_pack_key_words(ctx_mask, T, nullptr, B, T, s.kw, s.kw_cap, st));
-    if (beam) {   // every run of the call (a regeneration after a chain fault too) starts the search over
-        DIMX_REQUIRE(h->decg.dim_head == 64 && h->decg.depth <= 8 && !h->decg.abs_pos, DIMX_ERR_ARG,
-                     "generate_beam: needs 64-wide heads, at most 8 layers and a decoder without positional embedding");
-        DIMX_TRY(launch_beam_init(beam->cum, beam->parent, R, S, st));
-        if (beam->backptr && pr.step0 > 0)   // no step ran on the prefilled columns: -1
-            DIMX_HIP(hipMemset2DAsync(beam->backptr, (size_t)n * 4, 0xFF, (size_t)pr.step0 * 4, R, st));
-    }
-    // Independent clip groups run as separate step graphs on separate streams: every decode kernel is
-    // latency-bound at these sizes, so two groups in flight let one group's GEMM/LayerNorm chain overlap the
-    // other group's HBM-bound attention.  Results do not depend on the grouping (per-clip state only; the
-    // sampler's noise / counter-based RNG is indexed by the global clip row).
-    int G = h->gen_groups < 1 ? 1 : h->gen_groups;
-    if (G > B) G = B;
-    if (S > 1 || beam) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
-    // one group: every projection launch of the generation has R rows, and so has the table's build
-    const float* qkv0 = nullptr;
-    if (G == 1 && qkv0_table_supported(h)) {
-        DIMX_TRY(qkv0_table_build(h, s, R, st, pr.step0));
-        qkv0 = h->qkv0_table;
-    }
-    // the first layer's self attention from the table: no beam search (the cache reorder would have to permute the history) and
-    // no prompt (a prefill fills the cache, not the history); any number of samples per clip: rows are samples
-    const void* kv0 = nullptr;
-    if (qkv0 && h->use_kv0_table && !beam && pr.step0 == 0 && pr.Pmax <= 1 && h->decg.dim_head == 64 && h->decg.num_tokens <= 512) {
-        kv0 = h->at == DIMX_BF16 ? h->kv0_image : (const void*)h->qkv0_table;
-        if (kv0) ++h->kv0_generations;
-    }
-    if (pr.step0 > 0 && !keep_prefill) {
-        // the prefill forms no logits: those columns of logits_out read zero
-        if (logits_out)
-            DIMX_HIP(hipMemset2DAsync(logits_out, (size_t)n * h->decg.num_tokens * 4, 0, (size_t)pr.step0 * h->decg.num_tokens * 4, R, st));
-        DIMX_TRY(gen_prefill(h, cp, s, ps, pr, ctx_mask, B, T, S, tokens, st));
-    }
-    if (prefill_only) {   // tools/bench_prompt.py: the prefill stage alone
-        *chain_used = false;
-        return DIMX_OK;
-    }
-    int lo[dimx_ctx::kMaxGroups + 1];
-    for (int g = 0; g <= G; ++g) lo[g] = (int)((long)R * g / G);
-    hipStream_t gs[dimx_ctx::kMaxGroups];
-    if (G == 1) {
-        gs[0] = st;
-    } else {
-        if (!h->ev_fork) DIMX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        DIMX_HIP(hipEventRecord(h->ev_fork, st));
-        for (int g = 0; g < G; ++g) {
-            if (!h->grp_stream[g]) DIMX_HIP(hipStreamCreateWithFlags(&h->grp_stream[g], hipStreamNonBlocking));
-            if (!h->ev_join[g]) DIMX_HIP(hipEventCreateWithFlags(&h->ev_join[g], hipEventDisableTiming));
-            gs[g] = h->grp_stream[g];
-            DIMX_HIP(hipStreamWaitEvent(gs[g], h->ev_fork, 0));
-        }
-    }
-    const GenCall gc{cp, s, pr, ctx_mask, R, T, S, top_k, temperature, exp_noise, seed, tokens, logits_out, qkv0, beam, kv0};
-    for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, gs[g], true));
-    if (!h->use_graph) {
-        for (int t = 0; t < nrun; ++t)
-            for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, gs[g], false));
-    } else {
-        // greedy vs sampling is decided from the device-side parameters; only shapes and pointers key the graph.  The prompt's
-        // pointers, row stride and width are kernel arguments of the sampler; P0 is not (the counters' start value and the
-        // number of launches below), so a call with another P0 replays the same graphs.
-        GraphKey key{ws, B, T, top_k, 0.f, exp_noise, 0, start, ctx_mask, tokens, logits_out, G * 100 + S + (h->use_chain ? 1000 : 0) + (h->chain_fault_inject > 0 ? 2000 : 0) + (qkv0 ? 4000 : 0) + (kv0 ? 8000 : 0),
-                     pr.len, pr.ld, pr.Pmax, h->filter_kind, beam ? *beam : dimx::BeamCall{}, h->xwin_on, h->xwin_on ? h->xwin_lookahead : 0};
-        if (!(h->graph_valid && h->graph_key == key)) {
-            h->graph_valid = false;
-            if (!h->cap_stream) DIMX_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-            for (int g = 0; g < dimx_ctx::kMaxGroups; ++g) {
-                if (h->graph_exec[g]) {
-                    (void)hipGraphExecDestroy(h->graph_exec[g]);
-                    h->graph_exec[g] = nullptr;
-                }
-                if (h->graph_multi[g]) {
-                    (void)hipGraphExecDestroy(h->graph_multi[g]);
-                    h->graph_multi[g] = nullptr;
-                }
-            }
-            // The step does not depend on the step index (it lives in device memory), so the same launches can be captured
-            // several times in a row: consecutive graph launches leave ~8 us of idle GPU between them (kernel trace of
-            // round 2: 299 gaps = 2.5 ms per batch), kernels inside one graph follow each other without a gap.  `reps` = 1
-            // for the remainder steps, graph_unroll for the bulk.
-            for (int g = 0; g < G; ++g) {
-                for (int pass = 0; pass < 2; ++pass) {
-                    const int reps = pass == 0 ? 1 : h->graph_unroll;
-                    if (pass == 1 && (reps <= 1 || n < reps)) continue;
-                    hipGraph_t graph = nullptr;
-                    DIMX_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-                    int rc = DIMX_OK;
-                    for (int r = 0; r < reps && rc == DIMX_OK; ++r)
-                        rc = gen_step(h, gc, lo[g], lo[g + 1] - lo[g], g, h->cap_stream, false);
-                    const hipError_t ce = hipStreamEndCapture(h->cap_stream, &graph);
-                    if (rc != DIMX_OK) {
-                        if (graph) (void)hipGraphDestroy(graph);
-                        return rc;
-                    }
-                    DIMX_HIP(ce);
-                    DIMX_HIP(hipGraphInstantiate(pass == 0 ? &h->graph_exec[g] : &h->graph_multi[g], graph, nullptr, nullptr, 0));
-                    (void)hipGraphDestroy(graph);
-                }
-            }
-            h->graph_key = key;
-            h->graph_valid = true;
-        }
-        {
-            const int U = h->graph_unroll;
-            int t = 0;
-            for (; U > 1 && t + U <= nrun; t += U)
-                for (int g = 0; g < G; ++g)
-                    if (h->graph_multi[g]) DIMX_HIP(hipGraphLaunch(h->graph_multi[g], gs[g]));
-                    else
-                        for (int r = 0; r < U; ++r) DIMX_HIP(hipGraphLaunch(h->graph_exec[g], gs[g]));
-            for (; t < nrun; ++t)
-                for (int g = 0; g < G; ++g) DIMX_HIP(hipGraphLaunch(h->graph_exec[g], gs[g]));
-        }
-    }
-    if (G > 1) {
-        for (int g = 0; g < G; ++g) {
-            DIMX_HIP(hipEventRecord(h->ev_join[g], gs[g]));
-            DIMX_HIP(hipStreamWaitEvent(st, h->ev_join[g], 0));
-        }
-    }
-    *chain_used = G == 1 && gen_use_chain(h, lo[1] - lo[0], S, 0);
-    if (*chain_used) {
-        DIMX_HIP(hipMemcpyAsync(h->chain_err_host, h->chain_err_dev, 4, hipMemcpyDeviceToHost, st));
-        DIMX_HIP(hipEventRecord(h->chain_err_ev, st));
-    }
-    return DIMX_OK;
-}
-
-// DIMX_LAYER_PROF=1 (tuning): the phase stamps of the LAST step's layer launches (100 MHz wall clock), mean / max over blocks
-static int print_layer_prof(dimx_handle h) {
-    DIMX_HIP(hipEventSynchronize(h->chain_err_ev));
-    static const char* names[13] = {"start", "self attention done", "barrier 1", "rows + W1 landed", "out-proj stored", "barrier 2",
-                                    "y rows + W2 landed", "cross-q stored", "barrier 3", "cross attention done", "barrier 4",
-                                    "rows + W3 landed", "out-proj stored"};
-    std::vector<unsigned long long> hp((size_t)8 * 256 * 16);
-    DIMX_HIP(hipMemcpy(hp.data(), h->layer_prof_dev, hp.size() * 8, hipMemcpyDeviceToHost));
-    for (int l = 0; l < h->decg.depth; ++l) {
-        const unsigned long long* p = hp.data() + (size_t)l * 256 * 16;
-        unsigned long long t0 = ~0ull;
-        for (int b = 0; b < 256; ++b)
-            if (p[b * 16] && p[b * 16] < t0) t0 = p[b * 16];
-        if (t0 == ~0ull) continue;
-        fprintf(stderr, "dimx layer-kernel stamps, layer %d (us after the first block's start; mean / max over blocks)\n", l);
-        double prev = 0;
-        for (int i = 0; i < 13; ++i) {
-            double sum = 0, mx = 0;
-            int n = 0;
-            for (int b = 0; b < 256; ++b)
-                if (p[b * 16 + i]) {
-                    const double v = (double)(p[b * 16 + i] - t0) / 100.0;
-                    sum += v;
-                    mx = v > mx ? v : mx;
-                    ++n;
-                }
-            if (!n) continue;
-            fprintf(stderr, "  %-24s %7.2f / %7.2f  (+%.2f)\n", names[i], sum / n, mx, sum / n - prev);
-            prev = sum / n;
-        }
-    }
-    return DIMX_OK;
-}
-
-// Waits for the generation that ran chain kernels and returns its flag word (or a negative DIMX_ERR_*).  Non-zero flags are
-// cleared on both sides, the step graph is dropped and the fault is counted: the caller regenerates the batch.
-static int take_chain_flags(dimx_handle h, void* stream) {
-    DIMX_HIP(hipEventSynchronize(h->chain_err_ev));
-    const unsigned e = *h->chain_err_host;
-    if (!e) return 0;
-    *h->chain_err_host = 0;
-    DIMX_HIP(hipMemsetAsync(h->chain_err_dev, 0, 64, (hipStream_t)stream));
-    h->graph_valid = false;
-    ++h->chain_faults;
-    return (int)e;
-}
-
-// The XCD-local chain kernels need their 256 blocks co-resident, one per CU, on the XCD whose rows they own; another
-// process, handle or stream on the same GPU can break that.  They detect it (claim stamps, bounded barriers) but cannot
-// repair it, so the call that used them checks their flags before it returns: it waits for its own generation (the caller
-// is about to read the tokens anyway) and, on a fault, regenerates the same batch on the one-kernel-per-op step and keeps
-// the chain path off for this handle.  Round 2 reported the fault one call late.
-static int generate_checked(dimx_handle h, const dimx::GenPrompt& pr, const uint8_t* ctx_mask, int B, int T, int n_samples,
-                            float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out,
-                            void* ws, size_t ws_bytes, void* stream, const dimx::BeamCall* beam = nullptr) {
-    bool chain_used = false;
-    auto run = [&](bool keep_prefill) {
-        return generate_impl(h, pr, keep_prefill, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
-                             ws_bytes, stream, &chain_used, false, beam);
-    };
-    DIMX_TRY(run(false));
-    if (h->chain_fault_inject > 0) --h->chain_fault_inject;
-    if (!chain_used) return DIMX_OK;
-    if (h->layer_prof_dev) DIMX_TRY(print_layer_prof(h));
-    const int e = take_chain_flags(h, stream);
-    if (e <= 0) return e;
-    if (e & 3) {
-        h->use_chain = 0;
-        fprintf(stderr, "dimx: the XCD-local chain kernels reported %s%s; this batch is regenerated on the one-kernel-per-op "
-                        "step and the chain path stays off for this handle (DIMX_NO_CHAIN=1 avoids it from the start)\n",
-                (e & 1) ? "two blocks on one (XCD, CU slot) " : "", (e & 2) ? "a group-barrier timeout" : "");
-    } else {
-        // bit 2 alone: a residual row with |mean| > 8 standard deviations -- the deferred LayerNorm multiplies bf16(x), not
-        // bf16(x - mean), and its rounding noise is no longer small against the row's spread.  Same repair: the batch is
-        // regenerated with the row-phase LayerNorm (chain kernels stay on).
-        h->defer_ln = 0;
-        fprintf(stderr, "dimx: a residual row's mean exceeds 8 standard deviations; this batch is regenerated with the row-phase "
-                        "LayerNorm and the deferred form stays off for this handle\n");
-    }
-    DIMX_TRY(run(true));
-    if (!chain_used) return DIMX_OK;
-    // the regeneration may still have run chain kernels (the bit-2 case keeps them on): it answers for its own flags too
-    //  -- a second fault takes the chain path off and regenerates once more on the one-kernel-per-op step
-    const int e2 = take_chain_flags(h, stream);
-    if (e2 <= 0) return e2;
-    h->use_chain = 0;
-    fprintf(stderr, "dimx: the regenerated batch reported chain flags 0x%x again; regenerating on the one-kernel-per-op step, the "
-                    "chain path stays off for this handle\n", e2);
-    DIMX_TRY(run(true));
-    DIMX_REQUIRE(!chain_used, DIMX_ERR_STATE, "generate: the chain path is still active after it was switched off");
-    return DIMX_OK;
-}
-
-int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, int B, int T, int n_samples,
-                  float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out,
-                  void* ws, size_t ws_bytes, void* stream) {
-    const dimx::GenPrompt pr{start, 1, 1, nullptr, 0};
-    return generate_checked(h, pr, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws, ws_bytes,
-                            stream);
-}
-
-int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
-                           const uint8_t* ctx_mask, int B, int T, int n_samples, float temperature, int top_k,
-                           const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out, int flags, void* ws,
-                           size_t ws_bytes, void* stream) {
-    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
-    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_prompted: prompts are implemented for variant 0 (SLMFT) only; this handle is variant %d",
-                 h->variant);
-    DIMX_REQUIRE(prompt && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
-                 "generate_prompted: need 1 <= Pmax <= T - 1 and ld_prompt >= Pmax (Pmax=%d T=%d ld_prompt=%d)", Pmax, T, ld_prompt);
-    DIMX_REQUIRE(P0 >= 1 && P0 <= Pmax, DIMX_ERR_ARG, "generate_prompted: need 1 <= P0 <= Pmax (P0=%d Pmax=%d)", P0, Pmax);
-    DIMX_REQUIRE((flags & ~3) == 0, DIMX_ERR_ARG, "generate_prompted: unknown flags 0x%x", flags);
-    const int S = n_samples < 1 ? 1 : n_samples;
-    // bit 0: no prefill, the whole prompt goes through forced decode steps.  Online generation (dimx_set_cross_lookahead) too: the
-    // prefill's attention has no per-query key bound, the decode step's has
-    const int p0 = ((flags & 1) || h->xwin_on) ? 1 : P0;
-    // bit 1 is not part of the public flag set: tools/bench_prompt.py times the prefill stage alone with it
-    DIMX_REQUIRE(!(flags & 2) || p0 >= 2, DIMX_ERR_ARG, "generate_prompted: flags bit 1 (the prefill stage alone) without a prefill (P0=%d, flags 0x%x)",
-                 P0, flags);
-    DIMX_REQUIRE(p0 == 1 || h->decg.dim_head == 64, DIMX_ERR_ARG, "generate_prompted: the prefill needs 64-wide heads");
-    DIMX_REQUIRE(B >= 1 && T <= h->d.max_seq_len, DIMX_ERR_ARG, "B=%d T=%d out of range (T <= %d)", B, T, h->d.max_seq_len);
-    const size_t need = dimx::workspace_bytes_prompt(h, B, T, S, p0);
-    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "generate_prompted: workspace %zu < required %zu (dimx_workspace_bytes_prompt)",
-                 ws_bytes, need);
-    const dimx::GenPrompt pr{prompt, ld_prompt, Pmax, prompt_len, p0 - 1};
-    if (flags & 2) {   // the prefill stage alone, nothing is generated
-        bool chain_used = false;
-        return generate_impl(h, pr, false, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws,
-                             ws_bytes, stream, &chain_used, true);
-    }
-    return generate_checked(h, pr, ctx_mask, B, T, n_samples, temperature, top_k, exp_noise, seed, tokens, logits_out, ws, ws_bytes,
-                            stream);
-}
-
-int dimx_generate_beam(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
-                       const uint8_t* ctx_mask, const int32_t* lens, int B, int T, int beam_width, int32_t* tokens, double* scores,
-                       int32_t* backptr, float* logits_out, void* beam_state, size_t beam_state_bytes, int flags, void* ws, size_t ws_bytes,
-                       void* stream) {
-    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
-    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_beam: beam search is implemented for variant 0 (SLMFT) only; this handle is variant %d",
-                 h->variant);
-    DIMX_REQUIRE(!h->xwin_on, DIMX_ERR_ARG, "generate_beam: not available while the cross-attention window is on (dimx_set_cross_lookahead)");
-    DIMX_REQUIRE(dimx::beam_width_supported(beam_width), DIMX_ERR_ARG, "generate_beam: beam_width %d not in {1,2,4,5,8,10}", beam_width);
-    DIMX_REQUIRE(prompt && scores && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
-                 "generate_beam: need scores, 1 <= Pmax <= T - 1 and ld_prompt >= Pmax (Pmax=%d T=%d ld_prompt=%d)", Pmax, T, ld_prompt);
-    DIMX_REQUIRE(P0 >= 1 && P0 <= Pmax, DIMX_ERR_ARG, "generate_beam: need 1 <= P0 <= Pmax (P0=%d Pmax=%d)", P0, Pmax);
-    DIMX_REQUIRE((flags & ~1) == 0, DIMX_ERR_ARG, "generate_beam: unknown flags 0x%x", flags);
-    DIMX_REQUIRE(B >= 1 && T <= h->d.max_seq_len, DIMX_ERR_ARG, "B=%d T=%d out of range (T <= %d)", B, T, h->d.max_seq_len);
-    const size_t R = (size_t)B * beam_width;
-    DIMX_REQUIRE(beam_state && ((uintptr_t)beam_state % 8) == 0 && beam_state_bytes >= DIMX_BEAM_STATE_BYTES(B, beam_width), DIMX_ERR_ARG,
-                 "generate_beam: the beam state needs %zu bytes, 8-byte aligned (DIMX_BEAM_STATE_BYTES); got %zu", (size_t)DIMX_BEAM_STATE_BYTES(B, beam_width),
-                 beam_state_bytes);
-    const int p0 = (flags & 1) ? 1 : P0;
-    DIMX_REQUIRE(p0 == 1 || h->decg.dim_head == 64, DIMX_ERR_ARG, "generate_beam: the prefill needs 64-wide heads");
-    const size_t need = dimx::workspace_bytes_prompt(h, B, T, beam_width, p0);
-    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "generate_beam: workspace %zu < required %zu (dimx_workspace_bytes_prompt)", ws_bytes, need);
-    const dimx::GenPrompt pr{prompt, ld_prompt, Pmax, prompt_len, p0 - 1};
-    dimx::BeamCall bm;
-    bm.cum = (double*)beam_state;
-    bm.parent = (int32_t*)((double*)beam_state + R);
-    bm.backptr = backptr;
-    bm.lens = lens;
-    DIMX_TRY(generate_checked(h, pr, ctx_mask, B, T, beam_width, 0.f, 0, nullptr, 0, tokens, logits_out, ws, ws_bytes, stream, &bm));
-    DIMX_HIP(hipMemcpyAsync(scores, bm.cum, R * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return DIMX_OK;
-}
-
-// x-transformers' own parameter ranges; the kernel treats thres >= 1 and min_p = 0 as "keep everything"
-static int check_sampler_filter(int kind, float a, float b) {
-    DIMX_REQUIRE(kind >= DIMX_FILTER_TOP_K && kind <= DIMX_FILTER_TOP_A, DIMX_ERR_ARG, "sampler filter: unknown kind %d", kind);
-    if (kind == DIMX_FILTER_TOP_K) return DIMX_OK;
-    DIMX_REQUIRE(a == a && (kind != DIMX_FILTER_TOP_A || b == b), DIMX_ERR_ARG, "sampler filter: NaN parameter");
-    if (kind == DIMX_FILTER_TOP_P) DIMX_REQUIRE(a >= 0.f, DIMX_ERR_ARG, "sampler filter: top_p thres %g < 0", (double)a);
-    if (kind == DIMX_FILTER_MIN_P) DIMX_REQUIRE(a >= 0.f && a <= 1.f, DIMX_ERR_ARG, "sampler filter: min_p %g outside [0, 1]", (double)a);
-    if (kind == DIMX_FILTER_TOP_A)
-        DIMX_REQUIRE(a >= 0.f && b >= 0.f, DIMX_ERR_ARG, "sampler filter: top_a min_p_pow %g or min_p_ratio %g < 0", (double)a, (double)b);
-    return DIMX_OK;
-}
-
-int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b) {
-    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
-    DIMX_TRY(check_sampler_filter(kind, a, b));
-    h->filter_kind = kind;
-    h->filter_a = kind == DIMX_FILTER_TOP_K ? 0.f : a;
-    h->filter_b = kind == DIMX_FILTER_TOP_A ? b : 0.f;
-    return DIMX_OK;
-}
-
-int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead) {
-    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
-    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_cross_lookahead: online generation is implemented for variant 0 (SLMFT) only; this handle is variant %d",
-                 h->variant);
-    h->xwin_on = on ? 1 : 0;
-    h->xwin_lookahead = on ? lookahead : 0;
-    return DIMX_OK;
-}
-
-int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead) {
-    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
-    if (on) *on = h->xwin_on;
-    if (lookahead) *lookahead = h->xwin_lookahead;
-    return DIMX_OK;
-}
-
-int dimx_chain_faults(dimx_handle h) { return h ? h->chain_faults : 0; }
-int dimx_qkv0_table_builds(dimx_handle h) { return h ? h->qkv0_builds : 0; }
-int dimx_kv0_table_generations(dimx_handle h) { return h ? h->kv0_generations : 0; }
 
 int dimx_lstm_faults(dimx_handle h) { return h ? h->lstm_faults : 0; }
 
@@ -2756,544 +1864,6 @@ int dimx_mesh_head(dimx_handle h, const float* motion, const float* templ, int B
     gemm_set_plain_out(g, mesh_out, V);
     DIMX_TRY(launch_gemm(g, st));
     return DIMX_OK;
-}
-
-int dimx_op_lstm_layer(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
-                       const float* const* b_ih, const float* const* b_hh, float* y, int flags, int* faults_out, void* stream) {
-    DIMX_REQUIRE(dtype == DIMX_F32, DIMX_ERR_ARG, "lstm_layer: only the f32 recurrence is built (dtype %d)", dtype);
-    DIMX_REQUIRE(B >= 1 && T >= 1 && In >= 4, DIMX_ERR_ARG, "lstm_layer: bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    int dev = 0, cus = 0;
-    DIMX_HIP(hipGetDevice(&dev));
-    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const size_t bytes = lstm_scratch_bytes(B, T, In);
-    void* scratch = nullptr;
-    DIMX_HIP(hipMalloc(&scratch, bytes));
-    int faults = 0;
-    const int rc = lstm_layer_run(x, B, T, In, H, w_ih, w_hh, b_ih, b_hh, y, scratch, bytes, flags, cus, &faults, st);
-    const hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(scratch);
-    if (faults_out) *faults_out = faults;
-    DIMX_TRY(rc);
-    DIMX_HIP(e);
-    return DIMX_OK;
-}
-
-int dimx_debug_chain_fault(dimx_handle h, int n_calls) {
-    DIMX_REQUIRE(h && n_calls >= 0, DIMX_ERR_ARG, "debug_chain_fault: bad argument");
-    h->chain_fault_inject = n_calls;
-    h->graph_valid = false;
-    return DIMX_OK;
-}
-
-// ---------------------------------------------------------------- kernel-level entry points
-int dimx_op_gemm(int in_dtype, int out_dtype, const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M,
-                 int N, int K, const float* bias, int act, const float* residual, int ldr, int conv_T,
-                 const int32_t* conv_lens, int flags, void* stream) {
-    GemmArgs g;
-    gemm_args_init(g);
-    g.in_dtype = in_dtype;
-    g.out_dtype = out_dtype;
-    g.A = A;
-    g.lda = lda;
-    g.W = W;
-    g.ldw = ldw;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.bias = bias;
-    g.act = act;
-    g.residual = residual;
-    g.ldr = ldr;
-    g.allow_splitk = flags & 1;
-    g.force_simple = (flags >> 1) & 1;
-    g.out_slabs = (flags >> 2) & 1;        /* C = [splits][M, ldc] f32 slabs (split count = flags bits 16..23) */
-    g.w_tiled = (flags >> 3) & 1;          /* W in 8-row x 128-byte blocks (tools/gemm_ab.py; N % 8 == 0) */
-    g.slab_stride = (long)M * ldc;
-    g.cfg = (flags >> 8) & 0xff;           /* tuning: tile/stage config id */
-    g.force_splitk = (flags >> 16) & 0xff; /* tuning: split count */
-    if (ldw > K && K % (in_dtype == DIMX_BF16 ? 64 : 32) == 0) g.kloop = K; /* padded row stride, exact k extent */
-    if (conv_T > 0) {
-        g.conv_T = conv_T;
-        g.conv_lens = conv_lens;
-        g.conv_C = K / 5;
-    }
-    gemm_set_plain_out(g, C, ldc);
-    return launch_gemm(g, (hipStream_t)stream);
-}
-
-/* the f32 parity mode's split-bf16 decode GEMM alone (csrc/gemm_x3.hip): dimx_op_split_x3 makes the three bf16 planes of an f32 matrix
- * (what the weight packing does once per Linear), dimx_op_gemm_x3 multiplies f32 activations with them */
-int dimx_op_split_x3(const float* w, void* planes, long n, void* stream) {
-    DIMX_REQUIRE(n > 0, DIMX_ERR_ARG, "op_split_x3: empty matrix");
-    return launch_split_x3(w, planes, (size_t)n, (hipStream_t)stream);
-}
-
-int dimx_op_gemm_x3(const float* A, int lda, const void* planes, float* C, int ldc, int M, int N, int K, const float* bias, int act,
-                    const float* residual, int ldr, int flags, void* stream) {
-    GemmArgs g;
-    gemm_args_init(g);
-    g.in_dtype = DIMX_F32;
-    g.out_dtype = DIMX_F32;
-    g.A = A;
-    g.lda = lda;
-    g.W = planes;   /* the f32 matrix itself is not needed by this kernel */
-    g.w3 = planes;
-    g.w3_plane = (long)N * K;
-    g.x3_decode = 1;
-    g.ldw = K;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.bias = bias;
-    g.act = act;
-    g.residual = residual;
-    g.ldr = ldr;
-    g.allow_splitk = 1;
-    g.out_slabs = (flags >> 2) & 1;
-    g.slab_stride = (long)M * ldc;
-    g.force_splitk = (flags >> 16) & 0xff;
-    gemm_set_plain_out(g, C, ldc);
-    if (act != 0 && g.out_slabs) {   // an activation applies to the whole sum, never to one split's partial sum
-        GemmArgs g1 = g;
-        g1.act = 0;
-        int bn = 0, sp = 1;
-        DIMX_REQUIRE(!(gemm_use_x3(g1) && gemm_x3_plan(g1, &bn, &sp) && sp > 1), DIMX_ERR_ARG,
-                     "op_gemm_x3: activation %d with %d split-K slabs (M=%d N=%d K=%d): an activation needs the unsplit sum", act, sp, M,
-                     N, K);
-    }
-    DIMX_REQUIRE(planes && gemm_use_x3(g), DIMX_ERR_ARG, "op_gemm_x3: M=%d N=%d K=%d is not a shape of the split-bf16 kernel (K %% 32 == 0, "
-                 "N a multiple of 36 / 64 / 72 / 96)", M, N, K);
-    return launch_gemm_x3(g, (hipStream_t)stream);
-}
-
-/* number of split-K slabs an out_slabs dimx_op_gemm call with these arguments writes (tests: the f32 kernels plan it themselves) */
-int dimx_op_gemm_slabs(int in_dtype, int M, int N, int K, int flags) {
-    GemmArgs g;
-    gemm_args_init(g);
-    g.in_dtype = in_dtype;
-    g.out_dtype = DIMX_F32;
-    g.A = g.W = (const void*)16;
-    g.lda = g.ldw = K;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.allow_splitk = flags & 1;
-    g.out_slabs = 1;
-    g.force_splitk = (flags >> 16) & 0xff;
-    if ((flags >> 4) & 1) {
-        g.w3 = (const void*)16;
-        g.w3_plane = (long)N * K;
-        g.x3_decode = 1;
-    }
-    float dummy;
-    gemm_set_plain_out(g, &dummy, N);
-    return gemm_plan_splits(g);
-}
-
-int dimx_op_gemm_headmajor(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int M, int N, int K,
-                           int rowT, int Tp, int nlayers, void* stream) {
-    DIMX_REQUIRE(nlayers >= 1 && nlayers <= 4 && N % (nlayers * 128) == 0, DIMX_ERR_ARG, "op_gemm_headmajor: bad shape");
-    GemmArgs g;
-    gemm_args_init(g);
-    g.in_dtype = dtype;
-    g.out_dtype = dtype;
-    g.A = A;
-    g.lda = lda;
-    g.W = W;
-    g.ldw = ldw;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.rowT = rowT;
-    // column segments K_0 | V_0 | K_1 | V_1 ... each a [B, H, Tp, 64] cache (project_cross_kv's for_generate layout)
-    const int nseg = 2 * nlayers, segw = N / nseg, H = segw / 64;
-    OutSeg segs[8];
-    for (int i = 0; i < nseg; ++i) {
-        segs[i].ptr = (unsigned char*)out + (size_t)i * (M / rowT) * H * Tp * 64 * dtype_size(dtype);
-        segs[i].sb = (long)H * Tp * 64;
-        segs[i].sh = (long)Tp * 64;
-        segs[i].st = 64;
-        segs[i].sd = 1;
-        segs[i].D = 64;
-    }
-    GemmArgs probe = g;
-    gemm_set_plain_out(probe, out, N);
-    if (dtype == DIMX_BF16 && gemm256_eligible(probe)) return launch_gemm256_segs(g, segs, nseg, segw, (hipStream_t)stream);
-    DIMX_REQUIRE(nlayers == 1, DIMX_ERR_ARG, "op_gemm_headmajor: the fused multi-layer form needs the bf16 256-tile kernel");
-    g.nseg = 2;
-    g.seg_width = segw;
-    g.seg[0] = segs[0];
-    g.seg[1] = segs[1];
-    return launch_gemm(g, (hipStream_t)stream);
-}
-
-int dimx_op_layernorm(int out_dtype, const float* x, void* y, const float* gamma, const float* beta, int M, int C,
-                      void* stream) {
-    return launch_layernorm(out_dtype, x, y, gamma, beta, M, C, (hipStream_t)stream);
-}
-
-int dimx_op_instnorm(int out_dtype, const float* x, void* y, const int32_t* lens, int B, int T, int C, void* stream) {
-    return launch_instnorm(out_dtype, x, y, lens, B, T, C, (hipStream_t)stream);
-}
-
-// operator entry points (tests / tools): the key-mask scratch of attention_tr.hip is a stream-ordered allocation around the call
-static int op_attention_with_scratch(AttnArgs& a, hipStream_t st) {
-    void* kw = nullptr;
-    if (a.kmask && a.v_rows && a.dtype == DIMX_BF16) {
-        a.kwords_cap = (size_t)a.B * ((a.Lk + 63) / 64);
-        DIMX_HIP(hipMallocAsync(&kw, a.kwords_cap * 8, st));
-        a.kwords = (unsigned long long*)kw;
-    }
-    const int rc = launch_attention(a, st);
-    if (kw) DIMX_HIP(hipFreeAsync(kw, st));
-    return rc;
-}
-
-int dimx_op_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int H, int Lq, int Lk,
-                      int D, int ldq, int ldk, int ld_vt, int ldo, float scale, int causal, const int32_t* lens,
-                      const uint8_t* kmask, void* stream) {
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dtype = dtype;
-    a.q = q; a.k = k; a.vt = vt; a.o = out;
-    a.q_sb = (long)Lq * ldq; a.q_st = ldq; a.q_sh = D;
-    a.k_sb = (long)Lk * ldk; a.k_st = ldk; a.k_sh = D;
-    a.v_sb = (long)H * D * ld_vt; a.v_sh = (long)D * ld_vt; a.v_sd = ld_vt;
-    a.o_sb = (long)Lq * ldo; a.o_st = ldo; a.o_sh = D;
-    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.D = D;
-    a.scale = scale;
-    a.causal = causal;
-    a.lens = lens;
-    a.kmask = kmask;
-    a.kmask_ld = Lk;
-    return op_attention_with_scratch(a, (hipStream_t)stream);
-}
-
-int dimx_op_attention_rowv(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk, int D, int ldq,
-                           int ldk, int ldv, int ldo, float scale, int causal, const int32_t* lens, const uint8_t* kmask,
-                           void* stream) {
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dtype = DIMX_BF16;
-    a.q = q; a.k = k; a.vt = v; a.o = out;
-    a.q_sb = (long)Lq * ldq; a.q_st = ldq; a.q_sh = D;
-    a.k_sb = (long)Lk * ldk; a.k_st = ldk; a.k_sh = D;
-    a.v_rows = 1;
-    a.v_sb = (long)Lk * ldv; a.v_st = ldv; a.v_sh = D;
-    a.o_sb = (long)Lq * ldo; a.o_st = ldo; a.o_sh = D;
-    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.D = D;
-    a.scale = scale;
-    a.causal = causal;
-    a.lens = lens;
-    a.kmask = kmask;
-    a.kmask_ld = Lk;
-    return op_attention_with_scratch(a, (hipStream_t)stream);
-}
-
-int dimx_op_decode_attn(int dtype, const void* q, const void* kcache, const void* vcache, void* out, int B, int H,
-                        int Tmax, int n_keys, float scale, const uint8_t* kmask, int nsplit, int q_is_f32,
-                        void* stream) {
-    DecodeAttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dtype = dtype;
-    a.q = q;
-    a.q_ld = H * 64;
-    a.kcache = const_cast<void*>(kcache);
-    a.vcache = const_cast<void*>(vcache);
-    a.Tmax = Tmax;
-    a.out = out;
-    a.o_ld = H * 64;
-    a.B = B;
-    a.H = H;
-    a.n_keys = n_keys;
-    a.kmask = kmask;
-    a.kmask_ld = n_keys;
-    a.scale = scale;
-    a.force_nsplit = nsplit;
-    a.q_f32 = q_is_f32 ? 1 : 0;
-    a.nslab = 1;
-    return launch_decode_attn(a, (hipStream_t)stream);
-}
-
-int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, void* vcache, void* out, int B, int H,
-                             int Tmax, const int32_t* step_dev, float scale, int q_is_f32, void* stream) {
-    DecodeAttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dtype = dtype;
-    const size_t es = q_is_f32 ? 4 : dtype_size(dtype);
-    a.q = qkv;
-    a.q_ld = ld;
-    a.knew = (const unsigned char*)qkv + (size_t)H * 64 * es;
-    a.vnew = (const unsigned char*)qkv + (size_t)2 * H * 64 * es;
-    a.kv_ld = ld;
-    a.kcache = kcache;
-    a.vcache = vcache;
-    a.Tmax = Tmax;
-    a.out = out;
-    a.o_ld = H * 64;
-    a.B = B;
-    a.H = H;
-    a.step = step_dev;
-    a.scale = scale;
-    a.q_f32 = q_is_f32 ? 1 : 0;
-    a.nslab = 1;
-    return launch_decode_attn(a, (hipStream_t)stream);
-}
-
-/* every decode-attention form dimx_generate launches (tests): q / knew / vnew as the cache type or as nslab f32 split-K slabs,
- * the self form reading this step's k / v at q + H*64 / q + 2*H*64 of each slab row, the cross form with a strided key mask,
- * several query rows per clip and a forced wave count */
-static int op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
-                             void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
-                             const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, int win, int lookahead,
-                             void* stream) {
-    const int S = rows_per_clip > 1 ? rows_per_clip : 1;
-    DIMX_REQUIRE(B > 0 && H > 0 && Tmax > 0, DIMX_ERR_ARG, "op_decode_attn_ex: empty shape");
-    DIMX_REQUIRE(nslab >= 1 && nslab <= 8 && (nslab == 1 || q_is_f32), DIMX_ERR_ARG, "op_decode_attn_ex: nslab=%d (1..8, > 1 for f32 q only)",
-                 nslab);
-    DIMX_REQUIRE(q_ld >= (self_attn ? 3 : 1) * H * 64 && o_ld >= H * 64, DIMX_ERR_ARG, "op_decode_attn_ex: q_ld=%d o_ld=%d too small",
-                 q_ld, o_ld);
-    DIMX_REQUIRE(nslab == 1 || slab_stride >= (long)B * S * q_ld, DIMX_ERR_ARG, "op_decode_attn_ex: slabs overlap (stride %ld)",
-                 slab_stride);
-    DIMX_REQUIRE(self_attn ? (step_dev != nullptr && kmask == nullptr && S == 1) : (n_keys >= 1 && n_keys <= Tmax), DIMX_ERR_ARG,
-                 "op_decode_attn_ex: self form needs a step counter (no mask, one row per clip); cross form 1 <= n_keys (%d) <= Tmax",
-                 n_keys);
-    DIMX_REQUIRE(kmask == nullptr || kmask_ld >= n_keys, DIMX_ERR_ARG, "op_decode_attn_ex: kmask_ld=%d < n_keys=%d", kmask_ld, n_keys);
-    DecodeAttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dtype = dtype;
-    a.q = q;
-    a.q_ld = q_ld;
-    a.q_f32 = q_is_f32 ? 1 : 0;
-    a.nslab = nslab;
-    a.slab_stride = slab_stride;
-    if (self_attn) {
-        const size_t es = q_is_f32 ? 4 : dtype_size(dtype);
-        a.knew = (const unsigned char*)q + (size_t)H * 64 * es;
-        a.vnew = (const unsigned char*)q + (size_t)2 * H * 64 * es;
-        a.kv_ld = q_ld;
-        a.step = step_dev;
-    } else {
-        a.n_keys = n_keys;
-        a.kmask = kmask;
-        a.kmask_ld = kmask_ld;
-    }
-    a.kcache = kcache;
-    a.vcache = vcache;
-    a.Tmax = Tmax;
-    a.out = out;
-    a.o_ld = o_ld;
-    a.B = B;
-    a.H = H;
-    a.rows_per_clip = rows_per_clip;
-    a.scale = scale;
-    a.force_nsplit = nsplit;
-    if (win) {
-        a.win = 1;
-        a.lookahead = lookahead;
-        a.step = step_dev;
-    }
-    return launch_decode_attn(a, (hipStream_t)stream);
-}
-
-int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
-                           void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
-                           const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream) {
-    return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, self_attn, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, n_keys,
-                             kmask, kmask_ld, rows_per_clip, scale, nsplit, 0, 0, stream);
-}
-
-/* the windowed cross form: the keys j < clamp(*step_dev + 2 + lookahead, 1, n_keys) */
-int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
-                            void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys, const uint8_t* kmask,
-                            int kmask_ld, int rows_per_clip, float scale, int nsplit, int lookahead, void* stream) {
-    DIMX_REQUIRE(step_dev != nullptr, DIMX_ERR_ARG, "op_decode_attn_win: the windowed form needs a step counter");
-    return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, 0, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, n_keys, kmask,
-                             kmask_ld, rows_per_clip, scale, nsplit, 1, lookahead, stream);
-}
-
-size_t dimx_mlp_fused_packed_bytes(int C, int F) { return mlp_fused_packed_bytes(C, F); }
-
-int dimx_mlp_fused_pack(const float* w1_host, const float* b1_host, const float* w2_host, int C, int F, void* out_host, size_t out_bytes) {
-    DIMX_REQUIRE(w1_host && w2_host && out_host, DIMX_ERR_ARG, "mlp_fused_pack: null argument");
-    DIMX_REQUIRE(mlp_fused_packed_bytes(C, F) > 0 && out_bytes >= mlp_fused_packed_bytes(C, F), DIMX_ERR_ARG,
-                 "mlp_fused_pack: C = %d F = %d unsupported or the output buffer is too small", C, F);
-    return mlp_fused_pack(w1_host, b1_host, w2_host, C, F, (uint16_t*)out_host);
-}
-
-int dimx_op_mlp_fused_packed(float* x, const void* packed, const float* b2, const float* ln_g, const float* ln_b, int M, int C, int F, int act,
-                             void* stream) {
-    return launch_mlp_fused(x, packed, b2, ln_g, ln_b, M, C, F, act, (hipStream_t)stream);
-}
-
-int dimx_op_mlp_fused(float* x, const float* w1_host, const float* b1_host, const float* w2_host, const float* b2, const float* ln_g,
-                      const float* ln_b, int M, int C, int F, int act, void* stream) {
-    DIMX_REQUIRE(x && w1_host && w2_host && b2 && ln_g && M > 0, DIMX_ERR_ARG, "op_mlp_fused: null argument");
-    const size_t bytes = mlp_fused_packed_bytes(C, F);
-    DIMX_REQUIRE(bytes > 0, DIMX_ERR_ARG, "op_mlp_fused: C = %d F = %d not supported", C, F);
-    std::vector<uint16_t> img(bytes / 2);
-    DIMX_TRY(mlp_fused_pack(w1_host, b1_host, w2_host, C, F, img.data()));
-    void* p = nullptr;
-    DIMX_HIP(hipMalloc(&p, bytes));
-    int rc = DIMX_OK;
-    if (hipMemcpy(p, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) rc = DIMX_ERR_HIP;
-    if (rc == DIMX_OK) rc = launch_mlp_fused(x, p, b2, ln_g, ln_b, M, C, F, act, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == DIMX_OK) rc = DIMX_ERR_HIP;
-    (void)hipFree(p);
-    return rc;
-}
-
-int dimx_op_add_slabs_layernorm(int out_dtype, float* x, const float* slabs, int nslab, long slab_stride, void* y,
-                                const float* gamma, int M, int C, void* stream) {
-    return launch_add_slabs_layernorm(out_dtype, x, slabs, nslab, slab_stride, y, gamma, M, C, (hipStream_t)stream);
-}
-
-int dimx_op_chain(const void* A1, int K1, const void* W1, float* x, const float* slabs, int nslab, const float* gamma,
-                  void* y, const void* W2, int N2, float* out2, int B, int C, void* scratch, void* stream) {
-    DIMX_REQUIRE(scratch && x && y && gamma, DIMX_ERR_ARG, "op_chain: null argument");
-    int dev = 0, cus = 0;
-    DIMX_HIP(hipGetDevice(&dev));
-    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ChainArgs c;
-    memset(&c, 0, sizeof(c));
-    unsigned* u = (unsigned*)scratch;  // [0..127] counters, [128] step, [129] error flags, [256..511] claim stamps, then xr
-    c.B = B;
-    c.C = C;
-    if (W1) {
-        c.g1.W = W1; c.g1.N = C; c.g1.K = K1; c.g1.ldw = K1;
-        c.A1 = A1; c.lda1 = K1;
-        c.xr = (float*)(u + 512);
-    }
-    c.x = x;
-    c.slabs = slabs;
-    c.nslab = nslab;
-    c.slab_stride = (long)B * C;
-    c.y = y;
-    c.gamma = gamma;
-    if (W2) {
-        c.g2.W = W2; c.g2.N = N2; c.g2.K = C; c.g2.ldw = C;
-        c.out2 = out2; c.ld_out2 = N2;
-    }
-    c.counters = u;
-    c.seen = u + 256;
-    c.step = (const int32_t*)(u + 128);
-    c.err = u + 129;
-    DIMX_REQUIRE(chain_supported(c, cus), DIMX_ERR_ARG, "op_chain: shape not supported on this device (%d CUs)", cus);
-    DIMX_HIP(hipMemsetAsync(u, 0, 512 * 4, (hipStream_t)stream));
-    return launch_chain(c, (hipStream_t)stream);
-}
-
-int dimx_op_chain_ln(const void* A1, int K1, const void* W1, float* x, void* y, float* stats, const void* W2s,
-                     const float* colsum2, int N2, float* out2, int B, int C, void* scratch, void* stream) {
-    DIMX_REQUIRE(scratch && x && y && stats && A1 && W1, DIMX_ERR_ARG, "op_chain_ln: null argument");
-    int dev = 0, cus = 0;
-    DIMX_HIP(hipGetDevice(&dev));
-    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ChainArgs c;
-    memset(&c, 0, sizeof(c));
-    unsigned* u = (unsigned*)scratch;
-    c.B = B;
-    c.C = C;
-    c.g1.W = W1; c.g1.N = C; c.g1.K = K1; c.g1.ldw = K1;
-    c.A1 = A1; c.lda1 = K1;
-    c.xr = (float*)(u + 512);
-    c.x = x;
-    c.y = y;
-    c.gamma = (const float*)x;  /* unused by the deferred form, must be non-null */
-    c.defer = 1;
-    c.stats = stats;
-    if (W2s) {
-        c.g2.W = W2s; c.g2.N = N2; c.g2.K = C; c.g2.ldw = C;
-        c.out2 = out2; c.ld_out2 = N2;
-        c.colsum2 = colsum2;
-    }
-    c.counters = u;
-    c.seen = u + 256;
-    c.step = (const int32_t*)(u + 128);
-    c.err = u + 129;
-    DIMX_REQUIRE(chain_supported(c, cus), DIMX_ERR_ARG, "op_chain_ln: shape not supported on this device (%d CUs)", cus);
-    DIMX_HIP(hipMemsetAsync(u, 0, 512 * 4, (hipStream_t)stream));
-    return launch_chain(c, (hipStream_t)stream);
-}
-
-int dimx_op_gemm_ln(int out_dtype, const void* A, const void* Ws, void* C, int M, int N, int K, const float* bias, int act,
-                    const float* stats, const float* colsum, void* stream) {
-    DIMX_REQUIRE(A && Ws && C && stats && colsum && M >= 1 && M <= 256, DIMX_ERR_ARG, "op_gemm_ln: bad argument");
-    GemmArgs g;
-    gemm_args_init(g);
-    g.in_dtype = DIMX_BF16;
-    g.out_dtype = out_dtype;
-    g.A = A; g.lda = K;
-    g.W = Ws; g.ldw = K;
-    g.M = M; g.N = N; g.K = K;
-    g.bias = bias;
-    g.act = act;
-    g.ln_stats = stats;
-    g.ln_colsum = colsum;
-    g.ln_C = K;
-    gemm_set_plain_out(g, C, N);
-    return launch_gemm(g, (hipStream_t)stream);
-}
-
-int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
-                        int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
-                        const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
-                        int call_index, float scale, void* scratch, void* prof, void* stream) {
-    DIMX_REQUIRE(qkv && sk && sv && ck && cv && w_so && w_cq && colsum_cq && w_co && x && y && o && qc && stats && step && scratch,
-                 DIMX_ERR_ARG, "op_layer_chain: null argument");
-    constexpr int H = 12, D = 64, inner = H * D, C = 1152;
-    LayerChainArgs lc;
-    memset(&lc, 0, sizeof(lc));
-    lc.B = B;
-    lc.C = C;
-    DecodeAttnArgs& sa = lc.sa;
-    sa.dtype = DIMX_BF16;
-    sa.q = qkv; sa.q_ld = 3 * inner; sa.q_f32 = 1; sa.nslab = nslab; sa.slab_stride = slab_stride;
-    sa.knew = qkv + inner; sa.vnew = qkv + 2 * inner; sa.kv_ld = 3 * inner;
-    sa.kcache = sk; sa.vcache = sv; sa.Tmax = T;
-    sa.out = o; sa.o_ld = inner; sa.B = B; sa.H = H; sa.step = step; sa.scale = scale;
-    DecodeAttnArgs& ca = lc.ca;
-    ca.dtype = DIMX_BF16;
-    ca.q = qc; ca.q_ld = inner; ca.q_f32 = 1; ca.nslab = 1; ca.slab_stride = (long)B * inner;
-    ca.kcache = (void*)ck; ca.vcache = (void*)cv; ca.Tmax = Tp;
-    ca.out = o; ca.o_ld = inner; ca.B = B; ca.H = H; ca.n_keys = n_keys; ca.kmask = kmask; ca.kmask_ld = n_keys; ca.scale = scale;
-    lc.g_so.W = w_so; lc.g_so.N = C; lc.g_so.K = inner; lc.g_so.ldw = inner;
-    lc.g_cq.W = w_cq; lc.g_cq.N = inner; lc.g_cq.K = C; lc.g_cq.ldw = C;
-    lc.g_co.W = w_co; lc.g_co.N = C; lc.g_co.K = inner; lc.g_co.ldw = inner;
-    lc.o = o; lc.ld_o = inner;
-    lc.x = x; lc.y = y; lc.stats = stats; lc.colsum_cq = colsum_cq;
-    lc.qc = qc; lc.ld_qc = inner;
-    lc.counters = (unsigned*)scratch;
-    lc.seen = lc.counters + 8 * 16;
-    lc.err = lc.counters + 768;
-    lc.step = nullptr;          // the counters' epoch is the call index; the self-attention reads its own step pointer (sa.step)
-    lc.epoch_add = call_index;
-    lc.prof = (unsigned long long*)prof;
-    lc.sc_stride = ((T > n_keys ? T : n_keys) + 15) / 16 * 16;
-    int cu = 0, dev = 0;
-    DIMX_HIP(hipGetDevice(&dev));
-    DIMX_HIP(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
-    DIMX_REQUIRE(layer_chain_supported(lc, cu), DIMX_ERR_ARG, "op_layer_chain: not supported here (B = %d needs 129..256 clips, a 256-CU device)", B);
-    return launch_layer_chain(lc, (hipStream_t)stream);
-}
-
-int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise, uint64_t seed,
-                   uint64_t step, int32_t* tokens, void* stream) {
-    return dimx_op_sample_filtered(logits, R, DIMX_FILTER_TOP_K, top_k, 0.f, 0.f, temperature, exp_noise, seed, step, tokens, nullptr,
-                                   stream);
-}
-
-int dimx_op_sample_filtered(const float* logits, int R, int kind, int top_k, float a, float b, float temperature,
-                            const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens, uint8_t* keep_out,
-                            void* stream) {
-    DIMX_TRY(check_sampler_filter(kind, a, b));
-    SampleArgs sm;
-    sm.logits = logits; sm.ld_logits = 512; sm.R = R; sm.nslab = 1; sm.rows_total = R; sm.tokens = tokens; sm.tok_ld = 1;
-    sm.top_k = kind == DIMX_FILTER_TOP_K ? top_k : 0; sm.temperature = temperature; sm.seed = seed;
-    sm.noise = exp_noise; sm.step_host = exp_noise ? 0 : step;   // the [R,512] slice of this step (step only salts the generator)
-    sm.filt = SampleFilter{kind, a, b, keep_out};
-    return launch_sample(sm, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -119,23 +119,45 @@ struct BeamCall {
     bool operator==(const BeamCall& o) const { return cum == o.cum && parent == o.parent && backptr == o.backptr && lens == o.lens; }
 };
 
+// What the decode steps of one generate call launch (generate.hip resolve_route): decided once per call, read by the step, the
+// key-word packing, the table counters, the graph key and the chain flag check after the call.
+struct StepRoute {
+    bool chain = false;            // the XCD-local chain kernels replace the projection / LayerNorm triples
+    bool defer = false;            // ... in their deferred-LayerNorm form
+    bool layer_kernel[8] = {};     // layer l's attention half is the one layer-kernel launch
+    bool logits_chain = false;     // chain && no to_logits.bias: the final LayerNorm + logits is a chain site too
+    bool multi_tr = false;         // several samples per clip, bf16: cross attention on the matrix cores (per-op branch, no window)
+    bool win = false;              // online generation: the cross attention's key count follows the step counter
+    int lookahead = 0;
+    const float* qkv0 = nullptr;   // the first layer's q/k/v table or nullptr
+    const void* kv0 = nullptr;     // the first layer's K / V table (the bf16 image, or the q/k/v table itself in the f32 mode): its self
+                                   // attention reads rows of it through the token history and keeps no cache; nullptr = the cache
+    const BeamCall* beam = nullptr;
+    bool fault_inject = false;     // test hook: the chain kernels are launched with fault = 1
+    int G = 1, S = 1;              // clip groups, samples per clip
+};
+
+// Everything a captured step bakes in: the call's pointers and shapes, and the route.  Equality is memberwise.
 struct GraphKey {
     void* ws;
     int B, T, top_k;
-    float temperature;
-    const void* noise;
-    uint64_t seed;
-    const void *start, *mask, *tokens, *logits_out;
-    int groups;
+    const void *noise, *start, *mask, *tokens, *logits_out;
+    int G, S;
+    bool chain, defer, logits_chain, multi_tr, fault_inject;
+    unsigned layer_kernel;    // bit l = StepRoute::layer_kernel[l]
+    const void *qkv0, *kv0;
     const void* prompt_len;   // prompted generation: the sampler's other prompt arguments (`start` is the prompt itself)
     int ld_prompt, Pmax;
     int filter_kind;          // the sampler kernel's instantiation; the filter's real-valued parameters live in device memory
     BeamCall beam;            // beam search: the selection / reorder kernels' buffers, all null = the sampler ends the step
     int xwin_on, xwin_lookahead;   // online generation (dimx_set_cross_lookahead): other launches, and the look-ahead is a kernel argument
     bool operator==(const GraphKey& o) const {
-        return xwin_on == o.xwin_on && xwin_lookahead == o.xwin_lookahead && beam == o.beam && groups == o.groups && filter_kind == o.filter_kind && prompt_len == o.prompt_len && ld_prompt == o.ld_prompt && Pmax == o.Pmax && ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && temperature == o.temperature &&
-               noise == o.noise && seed == o.seed && start == o.start && mask == o.mask && tokens == o.tokens &&
-               logits_out == o.logits_out;
+        return ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && noise == o.noise && start == o.start && mask == o.mask &&
+               tokens == o.tokens && logits_out == o.logits_out && G == o.G && S == o.S && chain == o.chain && defer == o.defer &&
+               logits_chain == o.logits_chain && multi_tr == o.multi_tr && fault_inject == o.fault_inject &&
+               layer_kernel == o.layer_kernel && qkv0 == o.qkv0 && kv0 == o.kv0 && prompt_len == o.prompt_len &&
+               ld_prompt == o.ld_prompt && Pmax == o.Pmax && filter_kind == o.filter_kind && beam == o.beam && xwin_on == o.xwin_on &&
+               xwin_lookahead == o.xwin_lookahead;
     }
 };
 

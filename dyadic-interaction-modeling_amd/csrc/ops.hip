@@ -1,0 +1,540 @@
+// ops.hip -- the kernel-level entry points of libdimx_hip (dimx_op_*, dimx_mlp_fused_pack): one kernel or launcher each, for the
+// unit tests and the tuning tools; no handle.
+#include "stages.hpp"
+
+using namespace dimx;
+
+extern "C" {
+
+int dimx_op_lstm_layer(int dtype, const float* x, int B, int T, int In, int H, const float* const* w_ih, const float* const* w_hh,
+                       const float* const* b_ih, const float* const* b_hh, float* y, int flags, int* faults_out, void* stream) {
+    DIMX_REQUIRE(dtype == DIMX_F32, DIMX_ERR_ARG, "lstm_layer: only the f32 recurrence is built (dtype %d)", dtype);
+    DIMX_REQUIRE(B >= 1 && T >= 1 && In >= 4, DIMX_ERR_ARG, "lstm_layer: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0, cus = 0;
+    DIMX_HIP(hipGetDevice(&dev));
+    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const size_t bytes = lstm_scratch_bytes(B, T, In);
+    void* scratch = nullptr;
+    DIMX_HIP(hipMalloc(&scratch, bytes));
+    int faults = 0;
+    const int rc = lstm_layer_run(x, B, T, In, H, w_ih, w_hh, b_ih, b_hh, y, scratch, bytes, flags, cus, &faults, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    (void)hipFree(scratch);
+    if (faults_out) *faults_out = faults;
+    DIMX_TRY(rc);
+    DIMX_HIP(e);
+    return DIMX_OK;
+}
+
+// ---------------------------------------------------------------- kernel-level entry points
+int dimx_op_gemm(int in_dtype, int out_dtype, const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M,
+                 int N, int K, const float* bias, int act, const float* residual, int ldr, int conv_T,
+                 const int32_t* conv_lens, int flags, void* stream) {
+    GemmArgs g;
+    gemm_args_init(g);
+    g.in_dtype = in_dtype;
+    g.out_dtype = out_dtype;
+    g.A = A;
+    g.lda = lda;
+    g.W = W;
+    g.ldw = ldw;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.bias = bias;
+    g.act = act;
+    g.residual = residual;
+    g.ldr = ldr;
+    g.allow_splitk = flags & 1;
+    g.force_simple = (flags >> 1) & 1;
+    g.out_slabs = (flags >> 2) & 1;        /* C = [splits][M, ldc] f32 slabs (split count = flags bits 16..23) */
+    g.w_tiled = (flags >> 3) & 1;          /* W in 8-row x 128-byte blocks (tools/gemm_ab.py; N % 8 == 0) */
+    g.slab_stride = (long)M * ldc;
+    g.cfg = (flags >> 8) & 0xff;           /* tuning: tile/stage config id */
+    g.force_splitk = (flags >> 16) & 0xff; /* tuning: split count */
+    if (ldw > K && K % (in_dtype == DIMX_BF16 ? 64 : 32) == 0) g.kloop = K; /* padded row stride, exact k extent */
+    if (conv_T > 0) {
+        g.conv_T = conv_T;
+        g.conv_lens = conv_lens;
+        g.conv_C = K / 5;
+    }
+    gemm_set_plain_out(g, C, ldc);
+    return launch_gemm(g, (hipStream_t)stream);
+}
+
+/* the f32 parity mode's split-bf16 decode GEMM alone (csrc/gemm_x3.hip): dimx_op_split_x3 makes the three bf16 planes of an f32 matrix
+ * (what the weight packing does once per Linear), dimx_op_gemm_x3 multiplies f32 activations with them */
+int dimx_op_split_x3(const float* w, void* planes, long n, void* stream) {
+    DIMX_REQUIRE(n > 0, DIMX_ERR_ARG, "op_split_x3: empty matrix");
+    return launch_split_x3(w, planes, (size_t)n, (hipStream_t)stream);
+}
+
+int dimx_op_gemm_x3(const float* A, int lda, const void* planes, float* C, int ldc, int M, int N, int K, const float* bias, int act,
+                    const float* residual, int ldr, int flags, void* stream) {
+    GemmArgs g;
+    gemm_args_init(g);
+    g.in_dtype = DIMX_F32;
+    g.out_dtype = DIMX_F32;
+    g.A = A;
+    g.lda = lda;
+    g.W = planes;   /* the f32 matrix itself is not needed by this kernel */
+    g.w3 = planes;
+    g.w3_plane = (long)N * K;
+    g.x3_decode = 1;
+    g.ldw = K;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.bias = bias;
+    g.act = act;
+    g.residual = residual;
+    g.ldr = ldr;
+    g.allow_splitk = 1;
+    g.out_slabs = (flags >> 2) & 1;
+    g.slab_stride = (long)M * ldc;
+    g.force_splitk = (flags >> 16) & 0xff;
+    gemm_set_plain_out(g, C, ldc);
+    if (act != 0 && g.out_slabs) {   // an activation applies to the whole sum, never to one split's partial sum
+        GemmArgs g1 = g;
+        g1.act = 0;
+        int bn = 0, sp = 1;
+        DIMX_REQUIRE(!(gemm_use_x3(g1) && gemm_x3_plan(g1, &bn, &sp) && sp > 1), DIMX_ERR_ARG,
+                     "op_gemm_x3: activation %d with %d split-K slabs (M=%d N=%d K=%d): an activation needs the unsplit sum", act, sp, M,
+                     N, K);
+    }
+    DIMX_REQUIRE(planes && gemm_use_x3(g), DIMX_ERR_ARG, "op_gemm_x3: M=%d N=%d K=%d is not a shape of the split-bf16 kernel (K %% 32 == 0, "
+                 "N a multiple of 36 / 64 / 72 / 96)", M, N, K);
+    return launch_gemm_x3(g, (hipStream_t)stream);
+}
+
+/* number of split-K slabs an out_slabs dimx_op_gemm call with these arguments writes (tests: the f32 kernels plan it themselves) */
+int dimx_op_gemm_slabs(int in_dtype, int M, int N, int K, int flags) {
+    GemmArgs g;
+    gemm_args_init(g);
+    g.in_dtype = in_dtype;
+    g.out_dtype = DIMX_F32;
+    g.A = g.W = (const void*)16;
+    g.lda = g.ldw = K;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.allow_splitk = flags & 1;
+    g.out_slabs = 1;
+    g.force_splitk = (flags >> 16) & 0xff;
+    if ((flags >> 4) & 1) {
+        g.w3 = (const void*)16;
+        g.w3_plane = (long)N * K;
+        g.x3_decode = 1;
+    }
+    float dummy;
+    gemm_set_plain_out(g, &dummy, N);
+    return gemm_plan_splits(g);
+}
+
+int dimx_op_gemm_headmajor(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int M, int N, int K,
+                           int rowT, int Tp, int nlayers, void* stream) {
+    DIMX_REQUIRE(nlayers >= 1 && nlayers <= 4 && N % (nlayers * 128) == 0, DIMX_ERR_ARG, "op_gemm_headmajor: bad shape");
+    GemmArgs g;
+    gemm_args_init(g);
+    g.in_dtype = dtype;
+    g.out_dtype = dtype;
+    g.A = A;
+    g.lda = lda;
+    g.W = W;
+    g.ldw = ldw;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.rowT = rowT;
+    // column segments K_0 | V_0 | K_1 | V_1 ... each a [B, H, Tp, 64] cache (project_cross_kv's for_generate layout)
+    const int nseg = 2 * nlayers, segw = N / nseg, H = segw / 64;
+    OutSeg segs[8];
+    for (int i = 0; i < nseg; ++i) {
+        segs[i].ptr = (unsigned char*)out + (size_t)i * (M / rowT) * H * Tp * 64 * dtype_size(dtype);
+        segs[i].sb = (long)H * Tp * 64;
+        segs[i].sh = (long)Tp * 64;
+        segs[i].st = 64;
+        segs[i].sd = 1;
+        segs[i].D = 64;
+    }
+    GemmArgs probe = g;
+    gemm_set_plain_out(probe, out, N);
+    if (dtype == DIMX_BF16 && gemm256_eligible(probe)) return launch_gemm256_segs(g, segs, nseg, segw, (hipStream_t)stream);
+    DIMX_REQUIRE(nlayers == 1, DIMX_ERR_ARG, "op_gemm_headmajor: the fused multi-layer form needs the bf16 256-tile kernel");
+    g.nseg = 2;
+    g.seg_width = segw;
+    g.seg[0] = segs[0];
+    g.seg[1] = segs[1];
+    return launch_gemm(g, (hipStream_t)stream);
+}
+
+int dimx_op_layernorm(int out_dtype, const float* x, void* y, const float* gamma, const float* beta, int M, int C,
+                      void* stream) {
+    return launch_layernorm(out_dtype, x, y, gamma, beta, M, C, (hipStream_t)stream);
+}
+
+int dimx_op_instnorm(int out_dtype, const float* x, void* y, const int32_t* lens, int B, int T, int C, void* stream) {
+    return launch_instnorm(out_dtype, x, y, lens, B, T, C, (hipStream_t)stream);
+}
+
+// operator entry points (tests / tools): the key-mask scratch of attention_tr.hip is a stream-ordered allocation around the call
+static int op_attention_with_scratch(AttnArgs& a, hipStream_t st) {
+    void* kw = nullptr;
+    if (a.kmask && a.v_rows && a.dtype == DIMX_BF16) {
+        a.kwords_cap = (size_t)a.B * ((a.Lk + 63) / 64);
+        DIMX_HIP(hipMallocAsync(&kw, a.kwords_cap * 8, st));
+        a.kwords = (unsigned long long*)kw;
+    }
+    const int rc = launch_attention(a, st);
+    if (kw) DIMX_HIP(hipFreeAsync(kw, st));
+    return rc;
+}
+
+int dimx_op_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int H, int Lq, int Lk,
+                      int D, int ldq, int ldk, int ld_vt, int ldo, float scale, int causal, const int32_t* lens,
+                      const uint8_t* kmask, void* stream) {
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dtype;
+    a.q = q; a.k = k; a.vt = vt; a.o = out;
+    a.q_sb = (long)Lq * ldq; a.q_st = ldq; a.q_sh = D;
+    a.k_sb = (long)Lk * ldk; a.k_st = ldk; a.k_sh = D;
+    a.v_sb = (long)H * D * ld_vt; a.v_sh = (long)D * ld_vt; a.v_sd = ld_vt;
+    a.o_sb = (long)Lq * ldo; a.o_st = ldo; a.o_sh = D;
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.D = D;
+    a.scale = scale;
+    a.causal = causal;
+    a.lens = lens;
+    a.kmask = kmask;
+    a.kmask_ld = Lk;
+    return op_attention_with_scratch(a, (hipStream_t)stream);
+}
+
+int dimx_op_attention_rowv(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk, int D, int ldq,
+                           int ldk, int ldv, int ldo, float scale, int causal, const int32_t* lens, const uint8_t* kmask,
+                           void* stream) {
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = DIMX_BF16;
+    a.q = q; a.k = k; a.vt = v; a.o = out;
+    a.q_sb = (long)Lq * ldq; a.q_st = ldq; a.q_sh = D;
+    a.k_sb = (long)Lk * ldk; a.k_st = ldk; a.k_sh = D;
+    a.v_rows = 1;
+    a.v_sb = (long)Lk * ldv; a.v_st = ldv; a.v_sh = D;
+    a.o_sb = (long)Lq * ldo; a.o_st = ldo; a.o_sh = D;
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.D = D;
+    a.scale = scale;
+    a.causal = causal;
+    a.lens = lens;
+    a.kmask = kmask;
+    a.kmask_ld = Lk;
+    return op_attention_with_scratch(a, (hipStream_t)stream);
+}
+
+int dimx_op_decode_attn(int dtype, const void* q, const void* kcache, const void* vcache, void* out, int B, int H,
+                        int Tmax, int n_keys, float scale, const uint8_t* kmask, int nsplit, int q_is_f32,
+                        void* stream) {
+    DecodeAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dtype;
+    a.q = q;
+    a.q_ld = H * 64;
+    a.kcache = const_cast<void*>(kcache);
+    a.vcache = const_cast<void*>(vcache);
+    a.Tmax = Tmax;
+    a.out = out;
+    a.o_ld = H * 64;
+    a.B = B;
+    a.H = H;
+    a.n_keys = n_keys;
+    a.kmask = kmask;
+    a.kmask_ld = n_keys;
+    a.scale = scale;
+    a.force_nsplit = nsplit;
+    a.q_f32 = q_is_f32 ? 1 : 0;
+    a.nslab = 1;
+    return launch_decode_attn(a, (hipStream_t)stream);
+}
+
+int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, void* vcache, void* out, int B, int H,
+                             int Tmax, const int32_t* step_dev, float scale, int q_is_f32, void* stream) {
+    DecodeAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dtype;
+    const size_t es = q_is_f32 ? 4 : dtype_size(dtype);
+    a.q = qkv;
+    a.q_ld = ld;
+    a.knew = (const unsigned char*)qkv + (size_t)H * 64 * es;
+    a.vnew = (const unsigned char*)qkv + (size_t)2 * H * 64 * es;
+    a.kv_ld = ld;
+    a.kcache = kcache;
+    a.vcache = vcache;
+    a.Tmax = Tmax;
+    a.out = out;
+    a.o_ld = H * 64;
+    a.B = B;
+    a.H = H;
+    a.step = step_dev;
+    a.scale = scale;
+    a.q_f32 = q_is_f32 ? 1 : 0;
+    a.nslab = 1;
+    return launch_decode_attn(a, (hipStream_t)stream);
+}
+
+/* every decode-attention form dimx_generate launches (tests): q / knew / vnew as the cache type or as nslab f32 split-K slabs,
+ * the self form reading this step's k / v at q + H*64 / q + 2*H*64 of each slab row, the cross form with a strided key mask,
+ * several query rows per clip and a forced wave count */
+static int op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
+                             void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
+                             const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, int win, int lookahead,
+                             void* stream) {
+    const int S = rows_per_clip > 1 ? rows_per_clip : 1;
+    DIMX_REQUIRE(B > 0 && H > 0 && Tmax > 0, DIMX_ERR_ARG, "op_decode_attn_ex: empty shape");
+    DIMX_REQUIRE(nslab >= 1 && nslab <= 8 && (nslab == 1 || q_is_f32), DIMX_ERR_ARG, "op_decode_attn_ex: nslab=%d (1..8, > 1 for f32 q only)",
+                 nslab);
+    DIMX_REQUIRE(q_ld >= (self_attn ? 3 : 1) * H * 64 && o_ld >= H * 64, DIMX_ERR_ARG, "op_decode_attn_ex: q_ld=%d o_ld=%d too small",
+                 q_ld, o_ld);
+    DIMX_REQUIRE(nslab == 1 || slab_stride >= (long)B * S * q_ld, DIMX_ERR_ARG, "op_decode_attn_ex: slabs overlap (stride %ld)",
+                 slab_stride);
+    DIMX_REQUIRE(self_attn ? (step_dev != nullptr && kmask == nullptr && S == 1) : (n_keys >= 1 && n_keys <= Tmax), DIMX_ERR_ARG,
+                 "op_decode_attn_ex: self form needs a step counter (no mask, one row per clip); cross form 1 <= n_keys (%d) <= Tmax",
+                 n_keys);
+    DIMX_REQUIRE(kmask == nullptr || kmask_ld >= n_keys, DIMX_ERR_ARG, "op_decode_attn_ex: kmask_ld=%d < n_keys=%d", kmask_ld, n_keys);
+    DecodeAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dtype;
+    a.q = q;
+    a.q_ld = q_ld;
+    a.q_f32 = q_is_f32 ? 1 : 0;
+    a.nslab = nslab;
+    a.slab_stride = slab_stride;
+    if (self_attn) {
+        const size_t es = q_is_f32 ? 4 : dtype_size(dtype);
+        a.knew = (const unsigned char*)q + (size_t)H * 64 * es;
+        a.vnew = (const unsigned char*)q + (size_t)2 * H * 64 * es;
+        a.kv_ld = q_ld;
+        a.step = step_dev;
+    } else {
+        a.n_keys = n_keys;
+        a.kmask = kmask;
+        a.kmask_ld = kmask_ld;
+    }
+    a.kcache = kcache;
+    a.vcache = vcache;
+    a.Tmax = Tmax;
+    a.out = out;
+    a.o_ld = o_ld;
+    a.B = B;
+    a.H = H;
+    a.rows_per_clip = rows_per_clip;
+    a.scale = scale;
+    a.force_nsplit = nsplit;
+    if (win) {
+        a.win = 1;
+        a.lookahead = lookahead;
+        a.step = step_dev;
+    }
+    return launch_decode_attn(a, (hipStream_t)stream);
+}
+
+int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
+                           void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
+                           const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream) {
+    return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, self_attn, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, n_keys,
+                             kmask, kmask_ld, rows_per_clip, scale, nsplit, 0, 0, stream);
+}
+
+/* the windowed cross form: the keys j < clamp(*step_dev + 2 + lookahead, 1, n_keys) */
+int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
+                            void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys, const uint8_t* kmask,
+                            int kmask_ld, int rows_per_clip, float scale, int nsplit, int lookahead, void* stream) {
+    DIMX_REQUIRE(step_dev != nullptr, DIMX_ERR_ARG, "op_decode_attn_win: the windowed form needs a step counter");
+    return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, 0, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, n_keys, kmask,
+                             kmask_ld, rows_per_clip, scale, nsplit, 1, lookahead, stream);
+}
+
+size_t dimx_mlp_fused_packed_bytes(int C, int F) { return mlp_fused_packed_bytes(C, F); }
+
+int dimx_mlp_fused_pack(const float* w1_host, const float* b1_host, const float* w2_host, int C, int F, void* out_host, size_t out_bytes) {
+    DIMX_REQUIRE(w1_host && w2_host && out_host, DIMX_ERR_ARG, "mlp_fused_pack: null argument");
+    DIMX_REQUIRE(mlp_fused_packed_bytes(C, F) > 0 && out_bytes >= mlp_fused_packed_bytes(C, F), DIMX_ERR_ARG,
+                 "mlp_fused_pack: C = %d F = %d unsupported or the output buffer is too small", C, F);
+    return mlp_fused_pack(w1_host, b1_host, w2_host, C, F, (uint16_t*)out_host);
+}
+
+int dimx_op_mlp_fused_packed(float* x, const void* packed, const float* b2, const float* ln_g, const float* ln_b, int M, int C, int F, int act,
+                             void* stream) {
+    return launch_mlp_fused(x, packed, b2, ln_g, ln_b, M, C, F, act, (hipStream_t)stream);
+}
+
+int dimx_op_mlp_fused(float* x, const float* w1_host, const float* b1_host, const float* w2_host, const float* b2, const float* ln_g,
+                      const float* ln_b, int M, int C, int F, int act, void* stream) {
+    DIMX_REQUIRE(x && w1_host && w2_host && b2 && ln_g && M > 0, DIMX_ERR_ARG, "op_mlp_fused: null argument");
+    const size_t bytes = mlp_fused_packed_bytes(C, F);
+    DIMX_REQUIRE(bytes > 0, DIMX_ERR_ARG, "op_mlp_fused: C = %d F = %d not supported", C, F);
+    std::vector<uint16_t> img(bytes / 2);
+    DIMX_TRY(mlp_fused_pack(w1_host, b1_host, w2_host, C, F, img.data()));
+    void* p = nullptr;
+    DIMX_HIP(hipMalloc(&p, bytes));
+    int rc = DIMX_OK;
+    if (hipMemcpy(p, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) rc = DIMX_ERR_HIP;
+    if (rc == DIMX_OK) rc = launch_mlp_fused(x, p, b2, ln_g, ln_b, M, C, F, act, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == DIMX_OK) rc = DIMX_ERR_HIP;
+    (void)hipFree(p);
+    return rc;
+}
+
+int dimx_op_add_slabs_layernorm(int out_dtype, float* x, const float* slabs, int nslab, long slab_stride, void* y,
+                                const float* gamma, int M, int C, void* stream) {
+    return launch_add_slabs_layernorm(out_dtype, x, slabs, nslab, slab_stride, y, gamma, M, C, (hipStream_t)stream);
+}
+
+int dimx_op_chain(const void* A1, int K1, const void* W1, float* x, const float* slabs, int nslab, const float* gamma,
+                  void* y, const void* W2, int N2, float* out2, int B, int C, void* scratch, void* stream) {
+    DIMX_REQUIRE(scratch && x && y && gamma, DIMX_ERR_ARG, "op_chain: null argument");
+    int dev = 0, cus = 0;
+    DIMX_HIP(hipGetDevice(&dev));
+    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    ChainArgs c;
+    memset(&c, 0, sizeof(c));
+    unsigned* u = (unsigned*)scratch;  // [0..127] counters, [128] step, [129] error flags, [256..511] claim stamps, then xr
+    c.B = B;
+    c.C = C;
+    if (W1) {
+        c.g1.W = W1; c.g1.N = C; c.g1.K = K1; c.g1.ldw = K1;
+        c.A1 = A1; c.lda1 = K1;
+        c.xr = (float*)(u + 512);
+    }
+    c.x = x;
+    c.slabs = slabs;
+    c.nslab = nslab;
+    c.slab_stride = (long)B * C;
+    c.y = y;
+    c.gamma = gamma;
+    if (W2) {
+        c.g2.W = W2; c.g2.N = N2; c.g2.K = C; c.g2.ldw = C;
+        c.out2 = out2; c.ld_out2 = N2;
+    }
+    c.counters = u;
+    c.seen = u + 256;
+    c.step = (const int32_t*)(u + 128);
+    c.err = u + 129;
+    DIMX_REQUIRE(chain_supported(c, cus), DIMX_ERR_ARG, "op_chain: shape not supported on this device (%d CUs)", cus);
+    DIMX_HIP(hipMemsetAsync(u, 0, 512 * 4, (hipStream_t)stream));
+    return launch_chain(c, (hipStream_t)stream);
+}
+
+int dimx_op_chain_ln(const void* A1, int K1, const void* W1, float* x, void* y, float* stats, const void* W2s,
+                     const float* colsum2, int N2, float* out2, int B, int C, void* scratch, void* stream) {
+    DIMX_REQUIRE(scratch && x && y && stats && A1 && W1, DIMX_ERR_ARG, "op_chain_ln: null argument");
+    int dev = 0, cus = 0;
+    DIMX_HIP(hipGetDevice(&dev));
+    DIMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    ChainArgs c;
+    memset(&c, 0, sizeof(c));
+    unsigned* u = (unsigned*)scratch;
+    c.B = B;
+    c.C = C;
+    c.g1.W = W1; c.g1.N = C; c.g1.K = K1; c.g1.ldw = K1;
+    c.A1 = A1; c.lda1 = K1;
+    c.xr = (float*)(u + 512);
+    c.x = x;
+    c.y = y;
+    c.gamma = (const float*)x;  /* unused by the deferred form, must be non-null */
+    c.defer = 1;
+    c.stats = stats;
+    if (W2s) {
+        c.g2.W = W2s; c.g2.N = N2; c.g2.K = C; c.g2.ldw = C;
+        c.out2 = out2; c.ld_out2 = N2;
+        c.colsum2 = colsum2;
+    }
+    c.counters = u;
+    c.seen = u + 256;
+    c.step = (const int32_t*)(u + 128);
+    c.err = u + 129;
+    DIMX_REQUIRE(chain_supported(c, cus), DIMX_ERR_ARG, "op_chain_ln: shape not supported on this device (%d CUs)", cus);
+    DIMX_HIP(hipMemsetAsync(u, 0, 512 * 4, (hipStream_t)stream));
+    return launch_chain(c, (hipStream_t)stream);
+}
+
+int dimx_op_gemm_ln(int out_dtype, const void* A, const void* Ws, void* C, int M, int N, int K, const float* bias, int act,
+                    const float* stats, const float* colsum, void* stream) {
+    DIMX_REQUIRE(A && Ws && C && stats && colsum && M >= 1 && M <= 256, DIMX_ERR_ARG, "op_gemm_ln: bad argument");
+    GemmArgs g;
+    gemm_args_init(g);
+    g.in_dtype = DIMX_BF16;
+    g.out_dtype = out_dtype;
+    g.A = A; g.lda = K;
+    g.W = Ws; g.ldw = K;
+    g.M = M; g.N = N; g.K = K;
+    g.bias = bias;
+    g.act = act;
+    g.ln_stats = stats;
+    g.ln_colsum = colsum;
+    g.ln_C = K;
+    gemm_set_plain_out(g, C, N);
+    return launch_gemm(g, (hipStream_t)stream);
+}
+
+int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
+                        int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
+                        const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
+                        int call_index, float scale, void* scratch, void* prof, void* stream) {
+    DIMX_REQUIRE(qkv && sk && sv && ck && cv && w_so && w_cq && colsum_cq && w_co && x && y && o && qc && stats && step && scratch,
+                 DIMX_ERR_ARG, "op_layer_chain: null argument");
+    constexpr int H = 12, D = 64, inner = H * D, C = 1152;
+    LayerChainArgs lc;
+    memset(&lc, 0, sizeof(lc));
+    lc.B = B;
+    lc.C = C;
+    DecodeAttnArgs& sa = lc.sa;
+    sa.dtype = DIMX_BF16;
+    sa.q = qkv; sa.q_ld = 3 * inner; sa.q_f32 = 1; sa.nslab = nslab; sa.slab_stride = slab_stride;
+    sa.knew = qkv + inner; sa.vnew = qkv + 2 * inner; sa.kv_ld = 3 * inner;
+    sa.kcache = sk; sa.vcache = sv; sa.Tmax = T;
+    sa.out = o; sa.o_ld = inner; sa.B = B; sa.H = H; sa.step = step; sa.scale = scale;
+    DecodeAttnArgs& ca = lc.ca;
+    ca.dtype = DIMX_BF16;
+    ca.q = qc; ca.q_ld = inner; ca.q_f32 = 1; ca.nslab = 1; ca.slab_stride = (long)B * inner;
+    ca.kcache = (void*)ck; ca.vcache = (void*)cv; ca.Tmax = Tp;
+    ca.out = o; ca.o_ld = inner; ca.B = B; ca.H = H; ca.n_keys = n_keys; ca.kmask = kmask; ca.kmask_ld = n_keys; ca.scale = scale;
+    lc.g_so.W = w_so; lc.g_so.N = C; lc.g_so.K = inner; lc.g_so.ldw = inner;
+    lc.g_cq.W = w_cq; lc.g_cq.N = inner; lc.g_cq.K = C; lc.g_cq.ldw = C;
+    lc.g_co.W = w_co; lc.g_co.N = C; lc.g_co.K = inner; lc.g_co.ldw = inner;
+    lc.o = o; lc.ld_o = inner;
+    lc.x = x; lc.y = y; lc.stats = stats; lc.colsum_cq = colsum_cq;
+    lc.qc = qc; lc.ld_qc = inner;
+    lc.counters = (unsigned*)scratch;
+    lc.seen = lc.counters + 8 * 16;
+    lc.err = lc.counters + 768;
+    lc.step = nullptr;          // the counters' epoch is the call index; the self-attention reads its own step pointer (sa.step)
+    lc.epoch_add = call_index;
+    lc.prof = (unsigned long long*)prof;
+    lc.sc_stride = ((T > n_keys ? T : n_keys) + 15) / 16 * 16;
+    int cu = 0, dev = 0;
+    DIMX_HIP(hipGetDevice(&dev));
+    DIMX_HIP(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
+    DIMX_REQUIRE(layer_chain_supported(lc, cu), DIMX_ERR_ARG, "op_layer_chain: not supported here (B = %d needs 129..256 clips, a 256-CU device)", B);
+    return launch_layer_chain(lc, (hipStream_t)stream);
+}
+
+int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise, uint64_t seed,
+                   uint64_t step, int32_t* tokens, void* stream) {
+    return dimx_op_sample_filtered(logits, R, DIMX_FILTER_TOP_K, top_k, 0.f, 0.f, temperature, exp_noise, seed, step, tokens, nullptr,
+                                   stream);
+}
+
+int dimx_op_sample_filtered(const float* logits, int R, int kind, int top_k, float a, float b, float temperature,
+                            const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens, uint8_t* keep_out,
+                            void* stream) {
+    DIMX_TRY(check_sampler_filter(kind, a, b));
+    SampleArgs sm;
+    sm.logits = logits; sm.ld_logits = 512; sm.R = R; sm.nslab = 1; sm.rows_total = R; sm.tokens = tokens; sm.tok_ld = 1;
+    sm.top_k = kind == DIMX_FILTER_TOP_K ? top_k : 0; sm.temperature = temperature; sm.seed = seed;
+    sm.noise = exp_noise; sm.step_host = exp_noise ? 0 : step;   // the [R,512] slice of this step (step only salts the generator)
+    sm.filt = SampleFilter{kind, a, b, keep_out};
+    return launch_sample(sm, (hipStream_t)stream);
+}
+
+}  // extern "C"

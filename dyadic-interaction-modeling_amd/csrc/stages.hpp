@@ -1,0 +1,79 @@
+// stages.hpp -- what generate.hip and ops.hip share with model.hip: the scratch layouts of a generate call and their planners,
+// the argument checks and the sublayer helpers of the transformer stacks (all defined in model.hip unless noted).
+#pragma once
+#include "model.hpp"
+
+namespace dimx {
+
+enum { COMP_VQ0 = 1, COMP_VQ1 = 2, COMP_ENC = 4, COMP_DEC = 8, COMP_ALL = 15, COMP_MESH = 16 };   // packed components (ensure_packed)
+
+static inline size_t es_of(const dimx_ctx* c) { return dtype_size(c->at); }
+static inline int tpad(int T) { return (T + 7) / 8 * 8; }
+// number of decoder positions: SLMFT feeds / generates T-1 tokens (code/seq2seq_pretrain.py:469,500);
+// the legacy generator is teacher-forced on T-1 tokens but generates seq_len = T (code/seq2seq.py:256,300)
+static inline int gen_steps(const dimx_ctx* c, int T) { return c->variant == 1 ? T : T - 1; }
+
+int gemm_lin(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, GemmArgs& g);
+bool qkv_row_v(int at, int D);
+void set_attn_packed(AttnArgs& a, int dtype, const void* q, const void* k, const void* vt, void* o, int B, int H, int Lq, int Lk, int D,
+                     int Tp_k, bool rowv = false);
+
+// The buffers of a block, the base of every stack's scratch struct: the f32 residual stream h [M, C]; in the operand type the
+// LayerNorm output y, q / k / v(t), the attention output o and the feed-forward hidden f; kw: the packed key-mask words of the
+// prefill attention (AttnArgs.kwords)
+struct BlockBufs {
+    float* h;
+    void *y, *q, *k, *vt, *o, *f;
+    unsigned long long* kw = nullptr;   // the VQ stacks have none
+    size_t kw_cap = 0;
+};
+int ff_sublayer(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& f1, const Linear& f2,
+                const void* mlp, int act, int M, int C, hipStream_t st);
+int self_attn_qkv(const dimx_ctx* c, const BlockBufs& b, const float* ln_g, const float* ln_b, const Linear& qkv, int B, int T, int C,
+                  int heads, int D, AttnArgs& a, hipStream_t st);
+int attn_out(const dimx_ctx* c, const BlockBufs& b, AttnArgs& a, const Linear& out, int C, hipStream_t st);
+int cross_attn_sublayer(const dimx_ctx* c, const BlockBufs& b, const XAttn& x, AttnArgs& a, const uint8_t* ctx_mask, int C, hipStream_t st,
+                        const float* v_rows = nullptr);
+
+struct CtxPersist {
+    void* ck[8];
+    void* cv[8];
+};
+struct GenScratch {
+    void* sk[8];
+    void* sv[8];
+    float *x, *logits;
+    void *y, *o, *f;
+    float *qkv, *qc, *xr;  // f32 split-K slabs [kMaxSlabs][B, N] of the qkv / cross-q / residual projections
+    long st_qkv, st_qc, st_xr, st_lg;  // slab strides (elements)
+    int32_t* step;
+    unsigned* chain_ctr;  // [kChainSites][8][16] per-XCD arrival counters of the chain launch sites
+    void* qcb;                 // several samples per clip, bf16: the cross-attention queries [rows, inner] in the operand type
+    unsigned long long* kw;    // ... and the context mask as 64-bit validity words [clips][ceil(T / 64)] (attention_tr.hip)
+    size_t kw_cap;
+    int32_t* hist;             // [rows][T] the first layer's input token of every position (its self attention's table form)
+};
+constexpr int kChainSites = 32;
+constexpr int kChainSiteWords = 8 * 16 + 8 * 32;  // arrival counters [8][16] + claim stamps [8][32]
+
+// Prompted generation (dimx_generate_prompted): the prompt of a call and the teacher-forced scratch of its prefill.
+// dimx_generate is the ld = Pmax = 1, step0 = 0 case.
+struct GenPrompt {
+    const int32_t* tok;  // [B, ld] the prompt's tokens, one row per CLIP
+    int ld, Pmax;
+    const int32_t* len;  // [B] prompt lengths (clamped to [step0 + 1, Pmax] by the sampler) or nullptr = Pmax
+    int step0;           // P0 - 1: positions 0 .. step0 - 1 are prefilled, the first decode step is step0
+};
+struct PrefillScratch : BlockBufs {
+    float* cvt;          // f32 mode: one layer's context V transposed to [B,H,64,Tp] (the f32 prefill attention reads V^T)
+    int32_t* inp;
+};
+void plan_gen(const dimx_ctx* c, Arena& ar, int B, int T, GenScratch& s);
+void plan_prefill(const dimx_ctx* c, Arena& ar, int B, int n0, int T, PrefillScratch& s);
+size_t workspace_bytes_prompt(const dimx_ctx* c, int B, int T, int S, int P0);
+Arena scratch_arena(const dimx_ctx* c, void* ws, size_t ws_bytes, int B, int T, CtxPersist* cp);
+int check_common(dimx_handle h, int B, int T, void* ws, size_t ws_bytes, int need, int S = 1);
+
+int check_sampler_filter(int kind, float a, float b);   // generate.hip
+
+}  // namespace dimx

@@ -235,6 +235,68 @@ def test_graph_replay_never_reuses_another_setting(full_sd, short):
         e.close()
 
 
+# ---- 5b: the same rule across everything that selects the step's route (csrc/generate.hip resolve_route, GraphKey)
+def _route_calls(B, T, lens):
+    v_s, v_a, z, mask = _case(B, T, list(lens))
+    v_s, v_a, m8 = v_s.cuda(), v_a.cuda(), mask.to(torch.uint8).cuda()
+    start = z[:, 0].cuda()
+    prompt = z[:, :5].to(torch.int32).cuda().contiguous()
+    plen = torch.tensor([5, 4, 3], dtype=torch.int32).cuda()
+
+    def plain(e, **kw):
+        e.encode_ctx(v_s, v_a, m8, True)
+        return e.generate(start, m8, T, 1.0, 52, None, seed=2024, return_logits=True, **kw)
+
+    def samples(e):
+        e.encode_ctx(v_s, v_a, m8, True, n_samples=4)
+        return e.generate(start, m8, T, 1.0, 52, None, seed=2024, return_logits=True, n_samples=4)
+
+    def prompted(e):
+        e.encode_ctx(v_s, v_a, m8, True, prompt_frames=3)
+        return e.generate(None, m8, T, 1.0, 52, None, seed=2024, return_logits=True, prompt=prompt, prompt_len=plen, prefill=3)
+
+    def beam(e):
+        e.encode_ctx(v_s, v_a, m8, True, n_samples=4)
+        return e.generate_beam(start, m8, T, 4, return_logits=True, return_backptr=True)
+
+    def window_on(e):
+        e.set_cross_lookahead(1)
+        return plain(e)
+
+    def window_off(e):
+        e.set_cross_lookahead(None)
+        return plain(e)
+
+    def top_p(e):
+        return plain(e, filter_logits_fn="top_p", filter_kwargs={"thres": 0.8})
+
+    return [("seeded", plain), ("n_samples 4", samples), ("prompted", prompted), ("beam", beam), ("window on", window_on),
+            ("window off", window_off), ("top_p", top_p), ("top_k again", plain), ("seeded again", plain)]
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_graph_replay_never_belongs_to_another_route(full_sd, mode):
+    calls = _route_calls(3, 12, (12, 9, 5))
+    fresh = {}
+    for _, fn in calls:
+        if fn not in fresh:
+            e = _engine(full_sd, mode)
+            fresh[fn] = [t.cpu() for t in fn(e)]
+            e.close()
+    e = _engine(full_sd, mode)
+    try:
+        got = [[t.cpu() for t in fn(e)] for _, fn in calls]
+    finally:
+        e.close()
+    for (name, fn), out in zip(calls, got):
+        assert len(out) == len(fresh[fn])
+        for i, (a, b) in enumerate(zip(out, fresh[fn])):
+            assert torch.equal(a, b), "%s after the calls before it: output %d differs from a fresh engine's" % (name, i)
+    for a, b in zip(got[-1], got[0]):
+        assert torch.equal(a, b)
+    assert not torch.equal(got[0][0], got[4][0]) or not torch.equal(got[0][1], got[4][1])   # the window changes the result
+
+
 # ---- 6
 def test_samples_match_the_checker_row_by_row(eng, full_sd):
     import online_ref

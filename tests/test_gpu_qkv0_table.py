@@ -1,4 +1,4 @@
-"""GPU: the first decoder layer's q/k/v from a table over the 512 token ids (csrc/model.hip qkv0_table_build) against the
+"""GPU: the first decoder layer's q/k/v from a table over the 512 token ids (csrc/generate.hip qkv0_table_build) against the
 projection GEMM per token that it replaces (DIMX_NO_QKV0_TABLE=1).  The SLMFT decoder has no positional embedding, so layer 0's
 input is LayerNorm(token_emb[tok]); the table is built with the decode step's own kernels at the step's row count, hence
 "equal" below is torch.equal on the tokens AND on the per-step logits, greedy and sampled with injected noise, in both modes."""
