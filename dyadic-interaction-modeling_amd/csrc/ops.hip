@@ -282,13 +282,26 @@ int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, v
     return launch_decode_attn(a, (hipStream_t)stream);
 }
 
+/* the table form's arguments of the first layer's self attention (DecodeAttnArgs.tab .. hist_ld, as self_args of generate.hip sets them) */
+struct OpTabArgs {
+    const void* tab;
+    int tab_ld, tab_koff, tab_voff, tab_rows;
+    const int32_t* hist;
+    int hist_ld;
+};
+static void set_tab(DecodeAttnArgs& a, const OpTabArgs& t) {
+    a.tab = t.tab; a.tab_rows = t.tab_rows;
+    a.tab_ld = t.tab_ld; a.tab_koff = t.tab_koff; a.tab_voff = t.tab_voff;
+    a.hist = t.hist; a.hist_ld = t.hist_ld;
+}
+
 /* every decode-attention form dimx_generate launches (tests): q / knew / vnew as the cache type or as nslab f32 split-K slabs,
  * the self form reading this step's k / v at q + H*64 / q + 2*H*64 of each slab row, the cross form with a strided key mask,
  * several query rows per clip and a forced wave count */
 static int op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
                              void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
                              const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, int win, int lookahead,
-                             void* stream) {
+                             void* stream, const OpTabArgs* tab = nullptr) {
     const int S = rows_per_clip > 1 ? rows_per_clip : 1;
     DIMX_REQUIRE(B > 0 && H > 0 && Tmax > 0, DIMX_ERR_ARG, "op_decode_attn_ex: empty shape");
     DIMX_REQUIRE(nslab >= 1 && nslab <= 8 && (nslab == 1 || q_is_f32), DIMX_ERR_ARG, "op_decode_attn_ex: nslab=%d (1..8, > 1 for f32 q only)",
@@ -335,6 +348,7 @@ static int op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, i
         a.lookahead = lookahead;
         a.step = step_dev;
     }
+    if (tab) set_tab(a, *tab);
     return launch_decode_attn(a, (hipStream_t)stream);
 }
 
@@ -343,6 +357,15 @@ int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int
                            const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream) {
     return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, self_attn, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, n_keys,
                              kmask, kmask_ld, rows_per_clip, scale, nsplit, 0, 0, stream);
+}
+
+/* the self form with the first layer's table arguments: K / V of position j are row hist[b][j] of tab, nothing is appended */
+int dimx_op_decode_attn_tab(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
+                            void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, float scale, int nsplit, const void* tab,
+                            int tab_ld, int tab_koff, int tab_voff, int tab_rows, const int32_t* hist, int hist_ld, void* stream) {
+    const OpTabArgs t = {tab, tab_ld, tab_koff, tab_voff, tab_rows, hist, hist_ld};
+    return op_decode_attn_ex(dtype, q, q_ld, q_is_f32, nslab, slab_stride, 1, kcache, vcache, out, o_ld, B, H, Tmax, step_dev, 0, nullptr, 0,
+                             1, scale, nsplit, 0, 0, stream, &t);
 }
 
 /* the windowed cross form: the keys j < clamp(*step_dev + 2 + lookahead, 1, n_keys) */
@@ -477,10 +500,10 @@ int dimx_op_gemm_ln(int out_dtype, const void* A, const void* Ws, void* C, int M
     return launch_gemm(g, (hipStream_t)stream);
 }
 
-int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
-                        int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
-                        const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
-                        int call_index, float scale, void* scratch, void* prof, void* stream) {
+static int op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
+                          int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
+                          const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
+                          int call_index, float scale, void* scratch, void* prof, void* stream, const OpTabArgs* tab) {
     DIMX_REQUIRE(qkv && sk && sv && ck && cv && w_so && w_cq && colsum_cq && w_co && x && y && o && qc && stats && step && scratch,
                  DIMX_ERR_ARG, "op_layer_chain: null argument");
     constexpr int H = 12, D = 64, inner = H * D, C = 1152;
@@ -494,6 +517,7 @@ int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk,
     sa.knew = qkv + inner; sa.vnew = qkv + 2 * inner; sa.kv_ld = 3 * inner;
     sa.kcache = sk; sa.vcache = sv; sa.Tmax = T;
     sa.out = o; sa.o_ld = inner; sa.B = B; sa.H = H; sa.step = step; sa.scale = scale;
+    if (tab) set_tab(sa, *tab);   // launch_layer_chain then takes the table instantiation
     DecodeAttnArgs& ca = lc.ca;
     ca.dtype = DIMX_BF16;
     ca.q = qc; ca.q_ld = inner; ca.q_f32 = 1; ca.nslab = 1; ca.slab_stride = (long)B * inner;
@@ -517,6 +541,25 @@ int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk,
     DIMX_HIP(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
     DIMX_REQUIRE(layer_chain_supported(lc, cu), DIMX_ERR_ARG, "op_layer_chain: not supported here (B = %d needs 129..256 clips, a 256-CU device)", B);
     return launch_layer_chain(lc, (hipStream_t)stream);
+}
+
+int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
+                        int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
+                        const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
+                        int call_index, float scale, void* scratch, void* prof, void* stream) {
+    return op_layer_chain(qkv, nslab, slab_stride, sk, sv, T, ck, cv, Tp, n_keys, kmask, w_so, w_cq, colsum_cq, w_co, x, y, o, qc, stats, B,
+                          step, call_index, scale, scratch, prof, stream, nullptr);
+}
+
+/* the first layer's launch: the self attention reads K / V from the table over the token history (sk / sv are not touched) */
+int dimx_op_layer_chain_tab(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
+                            int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
+                            const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
+                            int call_index, float scale, void* scratch, void* prof, const void* tab, int tab_ld, int tab_koff,
+                            int tab_voff, int tab_rows, const int32_t* hist, int hist_ld, void* stream) {
+    const OpTabArgs t = {tab, tab_ld, tab_koff, tab_voff, tab_rows, hist, hist_ld};
+    return op_layer_chain(qkv, nslab, slab_stride, sk, sv, T, ck, cv, Tp, n_keys, kmask, w_so, w_cq, colsum_cq, w_co, x, y, o, qc, stats, B,
+                          step, call_index, scale, scratch, prof, stream, &t);
 }
 
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise, uint64_t seed,

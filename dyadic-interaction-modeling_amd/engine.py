@@ -782,13 +782,16 @@ def op_decode_attn(q, kcache, vcache, n_keys, scale, kmask=None, nsplit=0):
 
 
 def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None, kmask_ld=None, rows_per_clip=1, nsplit=0,
-                      q_f32=None, lookahead=None):
+                      q_f32=None, lookahead=None, tab=None, hist=None, tab_koff=0, tab_voff=0, tab_rows=None):
     """Every form of the decode step's attention as dimx_generate launches it (include/dimx.h dimx_op_decode_attn_ex).
     q: [R, q_ld] or f32 split-K slabs [nslab, R, q_ld] (R = B * rows_per_clip); kcache / vcache [B, H, Tmax, 64] (f32 or bf16).
     step (int32 device scalar) selects the self form: q's rows hold q | k | v, k / v are appended at *step; otherwise the cross
     form over n_keys keys with an optional kmask [B, kmask_ld] (uint8).  q_f32: q holds f32 slabs (default: q is f32).
     lookahead (int): the windowed cross form of an online generation (dimx_op_decode_attn_win) -- step is then the decode step
-    counter and the keys are j < dimx.online.visible(*step, lookahead, n_keys)."""
+    counter and the keys are j < dimx.online.visible(*step, lookahead, n_keys).
+    tab [rows, tab_ld] (cache type) with hist [B, hist_ld] int32: the table form of the self form (dimx_op_decode_attn_tab) -- the
+    cached K / V row of position j is row hist[b, j] of tab (K of head h at column tab_koff + h*64, V at tab_voff + h*64; ids are
+    clamped to tab_rows - 1, default the table's row count), nothing is appended and kcache / vcache are not touched."""
     lib = L.load()
     B, H, Tmax, _ = kcache.shape
     bf = kcache.dtype == torch.bfloat16
@@ -799,6 +802,13 @@ def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None,
     S = rows_per_clip if rows_per_clip > 1 else 1
     out = torch.empty(R, H * 64, dtype=kcache.dtype, device=q.device)
     kld = kmask_ld if kmask_ld is not None else (kmask.shape[1] if kmask is not None else 0)
+    if tab is not None:
+        L.check(lib.dimx_op_decode_attn_tab(L.BF16 if bf else L.F32, L.ptr(qs), q_ld, 1 if q_f32 else 0, nslab, qs.stride(0),
+                                            L.ptr(kcache), L.ptr(vcache), L.ptr(out), H * 64, B, H, Tmax, L.ptr(step), float(scale),
+                                            nsplit, L.ptr(tab), tab.stride(0), int(tab_koff), int(tab_voff),
+                                            tab.shape[0] if tab_rows is None else int(tab_rows), L.ptr(hist), hist.stride(0),
+                                            L.stream_ptr(q.device)), "dimx_op_decode_attn_tab")
+        return out
     if lookahead is not None:
         L.check(lib.dimx_op_decode_attn_win(L.BF16 if bf else L.F32, L.ptr(qs), q_ld, 1 if q_f32 else 0, nslab, qs.stride(0),
                                             L.ptr(kcache), L.ptr(vcache), L.ptr(out), H * 64, B, H, Tmax, L.ptr(step), n_keys,
@@ -810,6 +820,41 @@ def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None,
                                        L.ptr(step), n_keys, L.ptr(kmask), kld, S, float(scale), nsplit, L.stream_ptr(q.device)),
             "dimx_op_decode_attn_ex")
     return out
+
+
+def op_layer_chain(qkv, sk, sv, ck, cv, n_keys, kmask, w_so, w_cq, colsum_cq, w_co, x, step, B=None, call_index=0, scale=0.125,
+                   o=None, qc=None, y=None, stats=None, scratch=None, prof=None, tab=None, hist=None, tab_koff=0, tab_voff=768,
+                   tab_rows=None):
+    """The attention half of one decoder layer as one launch (csrc/chain.hip xcd_layer_kernel; include/dimx.h dimx_op_layer_chain):
+    qkv f32 slabs [nslab, rows, 2304]; sk / sv [rows, 12, T, 64] and ck / cv [rows, 12, Tp, 64] bf16; kmask [rows, n_keys] uint8 or
+    None; w_so / w_co [1152, 768], w_cq [768, 1152] bf16 (w_cq = gamma o Wq) with colsum_cq its f32 row sums; x [rows, 1152] f32 is
+    updated in place; step an int32 device scalar (cached self-attention keys).  B clips (default: the rows of x; buffers may carry
+    more rows, which the launch leaves alone).  o [rows, 768] bf16, qc [rows, 768] f32, y [rows, 1152] bf16, stats [8, 32, 32, 2] f32
+    and a zeroed 1024-word int32 scratch are allocated unless passed; call_index = 0, 1, 2, ... for consecutive calls on one
+    scratch.  tab / hist: the table form of the self attention (dimx_op_layer_chain_tab; arguments as op_decode_attn_ex).
+    Synchronises and returns (y, o, qc, stats, flags) with flags = scratch[768] (0 = ok, 1 = an (XCD, slot) claimed twice, 2 = a
+    group barrier timed out, 4 = precision guard: some row's |mean| > 8 std)."""
+    lib = L.load()
+    dev = x.device
+    rows = x.shape[0]
+    B = rows if B is None else int(B)
+    qs = qkv if qkv.dim() == 3 else qkv.unsqueeze(0)
+    o = torch.empty(rows, 768, dtype=torch.bfloat16, device=dev) if o is None else o
+    qc = torch.empty(rows, 768, dtype=torch.float32, device=dev) if qc is None else qc
+    y = torch.empty(rows, 1152, dtype=torch.bfloat16, device=dev) if y is None else y
+    stats = torch.zeros(8, 32, 32, 2, dtype=torch.float32, device=dev) if stats is None else stats
+    scratch = torch.zeros(1024, dtype=torch.int32, device=dev) if scratch is None else scratch
+    args = [L.ptr(qs), qs.shape[0], qs.stride(0), L.ptr(sk), L.ptr(sv), sk.shape[2], L.ptr(ck), L.ptr(cv), ck.shape[2], int(n_keys),
+            L.ptr(kmask), L.ptr(w_so), L.ptr(w_cq), L.ptr(colsum_cq), L.ptr(w_co), L.ptr(x), L.ptr(y), L.ptr(o), L.ptr(qc),
+            L.ptr(stats), B, L.ptr(step), int(call_index), float(scale), L.ptr(scratch), L.ptr(prof)]
+    if tab is not None:
+        L.check(lib.dimx_op_layer_chain_tab(*args, L.ptr(tab), tab.stride(0), int(tab_koff), int(tab_voff),
+                                            tab.shape[0] if tab_rows is None else int(tab_rows), L.ptr(hist), hist.stride(0),
+                                            L.stream_ptr(dev)), "dimx_op_layer_chain_tab")
+    else:
+        L.check(lib.dimx_op_layer_chain(*args, L.stream_ptr(dev)), "dimx_op_layer_chain")
+    torch.cuda.synchronize(dev)
+    return y, o, qc, stats, int(scratch[768].item())
 
 
 # ---------------------------------------------------------------- host plumbing of the metric operators

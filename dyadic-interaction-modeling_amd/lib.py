@@ -162,6 +162,9 @@ SIGNATURES = {
     "dimx_op_decode_attn_win": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int,
                                         c_int, c_void_p]),
+    "dimx_op_decode_attn_tab": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                        c_int, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                        c_void_p]),
     "dimx_op_mlp_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dimx_mlp_fused_packed_bytes": (c_size_t, [c_int, c_int]),
     "dimx_mlp_fused_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t]),
@@ -175,6 +178,10 @@ SIGNATURES = {
     "dimx_op_layer_chain": (c_int, [c_void_p, c_int, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "dimx_op_layer_chain_tab": (c_int, [c_void_p, c_int, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                        c_int, c_void_p]),
     "dimx_op_gemm_ln": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "dimx_op_fd_select_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -647,6 +647,15 @@ int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, v
 int dimx_op_decode_attn_ex(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, int self_attn, void* kcache,
                            void* vcache, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys,
                            const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit, void* stream);
+/* The table form of the self attention (tests; what dimx_generate launches for the first decoder layer when its k / v come from the
+ * table over the token ids): dimx_op_decode_attn_ex's self form (q must be f32 slabs) plus the table arguments.  The cached K / V
+ * row of position j < *step_dev of row b is row hist[b][j] of tab [tab_rows, tab_ld] (cache type; K of head h at column
+ * tab_koff + h*64, V at tab_voff + h*64; ids outside the table are clamped to its last row); hist [B, hist_ld] int32, hist_ld >= Tmax,
+ * entries at or past *step_dev are not used.  Nothing is appended: kcache / vcache are not touched (they must be non-null).  The
+ * result has the bits of the cache form run on caches gathered from the table. */
+int dimx_op_decode_attn_tab(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
+                            void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, float scale, int nsplit, const void* tab,
+                            int tab_ld, int tab_koff, int tab_voff, int tab_rows, const int32_t* hist, int hist_ld, void* stream);
 /* The windowed cross form of an online generation (dimx_set_cross_lookahead): the arguments of dimx_op_decode_attn_ex's cross form
  * plus lookahead; step_dev is required and the keys are j < clamp(*step_dev + 2 + lookahead, 1, n_keys).  K / V rows at or past that
  * bound are never read, and the result has the bits of dimx_op_decode_attn_ex called with n_keys = that bound. */
@@ -704,6 +713,14 @@ int dimx_op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk,
                         int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
                         const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
                         int call_index, float scale, void* scratch, void* prof, void* stream);
+/* dimx_op_layer_chain with the self attention in its table form (tests; the first decoder layer's launch): the arguments of
+ * dimx_op_layer_chain plus the table arguments of dimx_op_decode_attn_tab (bf16 table, hist [B, hist_ld >= T]); sk / sv are not
+ * touched. */
+int dimx_op_layer_chain_tab(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
+                            int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
+                            const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
+                            int call_index, float scale, void* scratch, void* prof, const void* tab, int tab_ld, int tab_koff,
+                            int tab_voff, int tab_rows, const int32_t* hist, int hist_ld, void* stream);
 /* Best-of-S selection by Frechet distance, the selection step of the test-time protocol (csrc/fd_select.hip; reference
  * code/x_engine_pt.py:255-270 around code/metrics/eval_utils.py:6-46).  All pointers are device memory.
  *   y_true f32 [B, L, .]: clip j, frame t starts at y_true + j*yt_clip_stride + t*yt_frame_stride (elements; feature stride 1)

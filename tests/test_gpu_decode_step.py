@@ -2,8 +2,9 @@
 
 One-query attention (csrc/decode_attn.hip, csrc/decode_attn_body.hpp) through dimx_op_decode_attn_ex: the cross form with f32
 split-K q slabs, a strided key mask and every wave count; the self form with its cache append; the multi-sample form; the parity
-mode's shard invariance.  The reference has the model's mask semantics: a masked score is -finfo.max, so a row with every key masked
-is the plain mean of V over the n keys.  Then the residual + pre-norm of every decoder layer (dimx_op_add_slabs_layernorm).
+mode's shard invariance; the table form of the first layer's self attention (dimx_op_decode_attn_tab).  The reference has the
+model's mask semantics: a masked score is -finfo.max, so a row with every key masked is the plain mean of V over the n keys.
+Then the residual + pre-norm of every decoder layer (dimx_op_add_slabs_layernorm).
 
 Every attention case also checks its own tolerance: it must be smaller than what dropping one key or shifting the keys by one does
 to the float64 reference, so a tolerance loose enough to pass an off-by-one fails the test itself."""
@@ -179,6 +180,105 @@ def test_self_attention_appends_one_row_and_attends_over_step_plus_one_keys(dev,
                                                              torch.cat([data_v[:, :, 1:step + 1].double(), vn.double()], 2)).view(B, hd)))
                 alts.append(("one key dropped", ref_attn(q4, k_all[:, :, 1:], v_all[:, :, 1:]).view(B, hd)))
             check(out.float(), ref, bf, alts, "step=%d nsplit=%d" % (step, nsplit))
+
+
+# ---------------------------------------------------------------- the table form of the first layer's self attention
+
+def _table(B, H, Tmax, dt, g):
+    """A [512 + 8, ld] table in the layout generate's self_args sets (bf16: K | V, f32: q | K | V), its 8 spare rows NaN; a token
+    history [B, Tmax + 1] with repeated ids; the K / V rows it addresses as [B, H, Tmax + 1, 64]"""
+    hd = H * 64
+    ld, koff, voff = (2 * hd, 0, hd) if dt == torch.bfloat16 else (3 * hd, hd, 2 * hd)
+    tab = torch.randn(520, ld, generator=g).to(dt)
+    tab[512:] = float("nan")
+    hist = torch.randint(0, 512, (B, Tmax + 1), generator=g, dtype=torch.int32)
+    hist[:, 9] = hist[:, 5]      # repeats, clear of positions 0 / 1: at step 1 "keys shifted by one" must differ from the right keys
+    hist[:, 17] = hist[:, 3]
+    rows = tab[hist.long()]
+    data_k, data_v = (rows[..., off:off + hd].reshape(B, Tmax + 1, H, 64).permute(0, 2, 1, 3).contiguous() for off in (koff, voff))
+    return tab, koff, voff, hist, data_k, data_v
+
+
+def _table_case(dev, tab_d, koff, voff, hist, data_k, data_v, Tmax, step, nsplit, g):
+    """one launch of the table form at `step`: caches untouched, the bits of the cache form on gathered caches, float64"""
+    from dimx import engine as E
+    dt = data_k.dtype
+    bf = dt == torch.bfloat16
+    B, H = data_k.shape[:2]
+    hd = H * 64
+    qkv = torch.randn(2, B, 3 * hd, generator=g) / 2 ** 0.5
+    eff = qkv[0] + qkv[1]
+    qe, kn, vn = (eff[:, i * hd:(i + 1) * hd].reshape(B, H, 1, 64) for i in range(3))
+    h = hist[:, :Tmax].clone()
+    h[:, step:] = (512 + torch.arange(Tmax - step) % 8).to(torch.int32)    # stale ids past the table: clamped, loaded, not used
+    nan_c = torch.full((B, H, Tmax, 64), float("nan"), dtype=dt)
+    kcd, vcd = nan_c.to(dev), nan_c.to(dev)
+    step_d = torch.tensor([step], dtype=torch.int32, device=dev)
+    out = E.op_decode_attn_ex(qkv.to(dev), kcd, vcd, SCALE, step=step_d, nsplit=nsplit, q_f32=True, tab=tab_d, hist=h.to(dev),
+                              tab_koff=koff, tab_voff=voff, tab_rows=512)
+    iv = torch.int16 if bf else torch.int32
+    assert torch.equal(kcd.cpu().view(iv), nan_c.view(iv)) and torch.equal(vcd.cpu().view(iv), nan_c.view(iv)), "the table form appends nothing"
+    kc, vc = nan_c.clone(), nan_c.clone()
+    kc[:, :, :step], vc[:, :, :step] = data_k[:, :, :step], data_v[:, :, :step]
+    cache_form = E.op_decode_attn_ex(qkv.to(dev), kc.to(dev), vc.to(dev), SCALE, step=step_d, nsplit=nsplit, q_f32=True)
+    assert torch.equal(out.view(iv), cache_form.view(iv)), "table form != cache form on gathered caches (step=%d nsplit=%d)" % (step, nsplit)
+    q4 = qe.view(B, 1, H, 64)
+    k_all = torch.cat([data_k[:, :, :step].double(), kn.double()], 2)
+    v_all = torch.cat([data_v[:, :, :step].double(), vn.double()], 2)
+    ref = ref_attn(q4, k_all, v_all).view(B, hd)
+    alts = []
+    if step > 0:
+        alts.append(("keys shifted by one", ref_attn(q4, torch.cat([data_k[:, :, 1:step + 1].double(), kn.double()], 2),
+                                                     torch.cat([data_v[:, :, 1:step + 1].double(), vn.double()], 2)).view(B, hd)))
+        alts.append(("one key dropped", ref_attn(q4, k_all[:, :, 1:], v_all[:, :, 1:]).view(B, hd)))
+    return check(out.float(), ref, bf, alts, "table form step=%d nsplit=%d" % (step, nsplit))
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_table_form_self_attention(dev, dtype):
+    """decode_attn_body<.., TAB> through dimx_op_decode_attn_tab, every wave count of both types: B * H = 15 pairs run 4 waves per
+    pair on their own (bf16), Tmax = 320 runs 1 (f32)"""
+    dt = torch.bfloat16 if dtype == "bf16" else torch.float32
+    B, H, Tmax = 5, 3, 320
+    g = _gen(4000 + (dtype == "bf16"))
+    tab, koff, voff, hist, data_k, data_v = _table(B, H, Tmax, dt, g)
+    tab_d = tab.to(dev)
+    worst = 0.0
+    for step in (0, 1, 15, 31, 32, 63, 299, Tmax - 1):
+        for nsplit in (0, 1, 2, 4):
+            worst = max(worst, _table_case(dev, tab_d, koff, voff, hist, data_k, data_v, Tmax, step, nsplit, g))
+    print("table form %s: worst |err| %.3g" % (dtype, worst))
+
+
+@pytest.mark.parametrize("Tmax", [512, 1024])
+def test_table_form_f32_takes_its_wave_count_from_the_cache_length(dev, Tmax):
+    """nsplit = 0 in f32: 2 waves per pair from Tmax = 512, 4 from 1024 (launch_decode_attn) -- the table instantiations of both"""
+    B, H = 5, 3
+    g = _gen(Tmax + 1)
+    tab, koff, voff, hist, data_k, data_v = _table(B, H, Tmax, torch.float32, g)
+    _table_case(dev, tab.to(dev), koff, voff, hist, data_k, data_v, Tmax, Tmax - 1, 0, g)
+
+
+def test_table_form_rejects_misuse_before_the_launch(dev):
+    from dimx import engine as E
+    from dimx import lib as L
+    B, H, Tmax = 2, 3, 40
+    hd = H * 64
+    step = torch.zeros(1, dtype=torch.int32, device=dev)
+    hist = torch.zeros(B, Tmax, dtype=torch.int32, device=dev)
+    for dt, ld, koff, voff, bad in ((torch.float32, 3 * hd, hd, 2 * hd, 2), (torch.bfloat16, 2 * hd, 0, hd, 4)):
+        kc = torch.zeros(B, H, Tmax, 64, dtype=dt, device=dev)
+        tab = torch.zeros(16, ld, dtype=dt, device=dev)
+        q = torch.zeros(B, 3 * hd, device=dev)
+        ok = dict(step=step, q_f32=True, tab=tab, hist=hist, tab_koff=koff, tab_voff=voff)
+        E.op_decode_attn_ex(q, kc, kc.clone(), SCALE, **ok)
+        for kw in (dict(ok, hist=hist[:, :Tmax - 1].contiguous()),            # a history row shorter than Tmax
+                   dict(ok, tab_koff=koff + bad), dict(ok, tab_voff=voff - bad),  # offsets off the 16-byte chunk
+                   dict(ok, tab_voff=ld - hd + 16)):                           # V past the end of the table row
+            with pytest.raises(L.DimxError):
+                E.op_decode_attn_ex(q, kc, kc.clone(), SCALE, **kw)
+        with pytest.raises(L.DimxError):                                       # q in the cache type: the table form takes f32 slabs only
+            E.op_decode_attn_ex(q.to(dt) if dt == torch.bfloat16 else q, kc, kc.clone(), SCALE, **dict(ok, q_f32=False))
 
 
 @pytest.mark.parametrize("S", [2, 4, 5, 8, 10])
