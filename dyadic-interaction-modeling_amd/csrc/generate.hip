@@ -149,6 +149,7 @@ struct StepCtx {
     int row0, B, grp;
     int clip0, nclip;   // with S samples per clip, rows are samples (row = clip * S + sample)
     int T, S, DD, heads, D, inner, V, n, Tp;
+    int n_keys;   // the cross attention's key bound: T, or what a streaming session sets (gen_run_set_keys)
     size_t es;
     float scale, pos_scale;
     const float* pos;   // the legacy decoder's positional embedding or nullptr
@@ -171,7 +172,7 @@ static StepCtx step_ctx(dimx_handle h, const GenCall& gc, const StepRoute& r, in
     c.T = q.T; c.S = q.S;
     c.clip0 = row0 / c.S; c.nclip = B / c.S;
     c.DD = dg.dim; c.heads = dg.heads; c.D = dg.dim_head; c.inner = c.heads * c.D;
-    c.V = dg.num_tokens; c.n = gen_steps(h, c.T); c.Tp = tpad(c.T);
+    c.V = dg.num_tokens; c.n = gen_steps(h, c.T); c.Tp = tpad(c.T); c.n_keys = c.T;
     c.es = es_of(h); c.scale = 1.0f / sqrtf((float)c.D);
     c.pos = dg.abs_pos ? h->dec.pos_emb : nullptr; c.pos_scale = 1.0f / sqrtf((float)c.DD);
     const int T = c.T, DD = c.DD, heads = c.heads, inner = c.inner;
@@ -282,7 +283,7 @@ static DecodeAttnArgs cross_args(const StepCtx& c, int l) {
     ca.q = s.qc; ca.q_ld = c.inner; ca.q_f32 = 1; ca.nslab = 1; ca.slab_stride = s.st_qc;
     ca.kcache = (void*)c.ck[l]; ca.vcache = (void*)c.cv[l]; ca.Tmax = c.Tp;
     ca.out = s.o; ca.o_ld = c.inner; ca.B = c.S > 1 ? c.nclip : c.B; ca.rows_per_clip = c.S; ca.H = c.heads;
-    ca.n_keys = c.T; ca.kmask = c.ctx_mask; ca.kmask_ld = c.T; ca.scale = c.scale;
+    ca.n_keys = c.n_keys; ca.kmask = c.ctx_mask; ca.kmask_ld = c.T; ca.scale = c.scale;
     if (c.r->win) { ca.win = 1; ca.lookahead = c.r->lookahead; ca.step = s.step; }
     return ca;
 }
@@ -701,44 +702,73 @@ static int gen_parameters(dimx_handle h, const GenCall& gc, const StepRoute& rou
     return DIMX_OK;
 }
 
-// One implementation for dimx_generate (pr = {start, 1, 1, NULL, 0}), dimx_generate_prompted and dimx_generate_beam; *ran is the
-// route its steps took.  keep_prefill: the call repeats a generation whose prefill already ran in this workspace (the regeneration
-// after a chain fault): the decode steps write cache positions >= step0 and token / logit columns >= step0 only, so the prefix is
-// intact and only the counters start over.  prefill_only (tools/bench_prompt.py): the prefill stage alone.
-static int generate_impl(dimx_handle h, const GenRequest& q, bool keep_prefill, bool prefill_only, StepRoute* ran) {
+// A generation from its plan to its last step: what generate_impl builds once per call, kept in one place so that the start and the
+// steps can be driven across calls (a streaming session, stream.hip).  The steps' contexts point into it: it is never copied.
+struct GenRun {
+    GenRequest q;
+    CtxPersist cp;
+    GenScratch s;
+    GenCall gc;
+    StepRoute route;
+    StepCtx ctx[dimx_ctx::kMaxGroups];
+    hipStream_t gs[dimx_ctx::kMaxGroups];
+    int G = 1, n = 0, nrun = 0;
+    bool graphs = true;   // replay the handle's step graphs where use_graph is on (a session launches its steps directly)
+    explicit GenRun(const GenRequest& r) : q(r), cp{}, s{}, gc{q, cp, s, 0, 0} {}
+    GenRun(const GenRun&) = delete;
+};
+
+// plan, route, parameters, tables, prefill, start.  keep_prefill: the call repeats a generation whose prefill already ran in this
+// workspace (the regeneration after a chain fault): the decode steps write cache positions >= step0 and token / logit columns >=
+// step0 only, so the prefix is intact and only the counters start over.  prefill_only (tools/bench_prompt.py): the prefill stage
+// alone.  sess: a streaming session's generation -- the context K / V are the session's (appended push by push, no
+// dimx_encode_ctx), one clip group, the per-op step with the cross-attention window on, no step graphs.
+int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, const GenSessionSpec* sess) {
+    const GenRequest& q = run.q;
     const GenPrompt& pr = q.pr;
     const int B = q.B, T = q.T, S = q.S;
     hipStream_t st = q.st;
-    *ran = StepRoute{};
     // the other kinds ignore the call's k (and it keys the step graph)
     const int top_k = h && h->filter_kind != DIMX_FILTER_TOP_K ? 0 : q.top_k;
     DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
                  "generate: n_samples %d not in {1,2,4,5,8,10}", S);
     DIMX_TRY(check_common(h, B, T, q.ws, q.ws_bytes, COMP_DEC, S));
     DIMX_REQUIRE(pr.tok && q.ctx_mask && q.tokens && T >= 2, DIMX_ERR_ARG, "generate: null argument or T < 2");
-    DIMX_REQUIRE(h->ctx_ready && h->ctx_B == B && h->ctx_T == T && h->ctx_ws == q.ws && h->ctx_for_generate,
+    DIMX_REQUIRE(sess || (h->ctx_ready && h->ctx_B == B && h->ctx_T == T && h->ctx_ws == q.ws && h->ctx_for_generate),
                  DIMX_ERR_STATE, "generate: call dimx_encode_ctx(for_generate=1) with the same B, T, ws first");
     // plan
-    CtxPersist cp;
+    CtxPersist& cp = run.cp;
     Arena ar = scratch_arena(h, q.ws, q.ws_bytes, B, T, &cp);
-    GenScratch s;
+    GenScratch& s = run.s;
     const int R = B * S;  // sequences generated in this call
     plan_gen(h, ar, R, T, s);
     PrefillScratch ps;
     if (pr.step0 > 0) plan_prefill(h, ar, B, pr.step0, T, ps);
     DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "generate: workspace overflow");
     const int n = gen_steps(h, T);
-    const int nrun = n - pr.step0;   // decode steps of this call
+    run.n = n;
+    run.nrun = n - pr.step0;   // decode steps of this call
     DIMX_TRY(chain_state_ensure(h));
     int G = h->gen_groups < 1 ? 1 : h->gen_groups;
     if (G > B) G = B;
-    if (S > 1 || q.beam) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
+    if (S > 1 || q.beam || sess) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
+    run.G = G;
     int lo[dimx_ctx::kMaxGroups + 1];
     for (int g = 0; g <= G; ++g) lo[g] = (int)((long)R * g / G);
     // route
-    const GenCall gc{q, cp, s, R, top_k};
-    StepRoute route;
+    run.gc.R = R;
+    run.gc.top_k = top_k;
+    const GenCall& gc = run.gc;
+    StepRoute& route = run.route;
     DIMX_TRY(resolve_route(h, gc, G, lo[1] - lo[0], route));
+    if (sess) {
+        // the chain kernels answer a fault by a regeneration of the whole call, which a session cannot offer
+        route.chain = route.defer = route.logits_chain = route.multi_tr = false;
+        for (bool& lk : route.layer_kernel) lk = false;
+        route.win = true;
+        route.lookahead = sess->lookahead;
+        run.graphs = false;
+    }
     // parameters
     DIMX_TRY(gen_parameters(h, gc, route, n));
     // tables
@@ -753,28 +783,56 @@ static int generate_impl(dimx_handle h, const GenRequest& q, bool keep_prefill, 
     }
     if (prefill_only) return DIMX_OK;
     // start
-    hipStream_t gs[dimx_ctx::kMaxGroups];
-    DIMX_TRY(gen_groups_fork(h, G, st, gs));
-    StepCtx ctx[dimx_ctx::kMaxGroups];
+    DIMX_TRY(gen_groups_fork(h, G, st, run.gs));
     for (int g = 0; g < G; ++g) {
-        ctx[g] = step_ctx(h, gc, route, lo[g], lo[g + 1] - lo[g], g, gs[g]);
-        DIMX_TRY(gen_start(ctx[g]));
+        run.ctx[g] = step_ctx(h, gc, route, lo[g], lo[g + 1] - lo[g], g, run.gs[g]);
+        if (sess) run.ctx[g].n_keys = sess->n_keys;
+        DIMX_TRY(gen_start(run.ctx[g]));
     }
-    // steps
-    if (!h->use_graph) {
-        for (int t = 0; t < nrun; ++t)
-            for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(ctx[g]));
+    return DIMX_OK;
+}
+
+// the next nsteps steps of every group
+int gen_run_steps(dimx_handle h, GenRun& run, int nsteps) {
+    const int G = run.G;
+    if (!h->use_graph || !run.graphs) {
+        for (int t = 0; t < nsteps; ++t)
+            for (int g = 0; g < G; ++g) DIMX_TRY(gen_step(run.ctx[g]));
     } else {
-        DIMX_TRY(step_graphs_ensure(h, graph_key(h, gc, route), ctx, G, n));
-        DIMX_TRY(step_graphs_replay(h, nrun, G, gs));
+        DIMX_TRY(step_graphs_ensure(h, graph_key(h, run.gc, run.route), run.ctx, G, run.n));
+        DIMX_TRY(step_graphs_replay(h, nsteps, G, run.gs));
     }
+    return DIMX_OK;
+}
+
+void gen_run_set_keys(GenRun& run, int n_keys, hipStream_t st) {
+    run.ctx[0].n_keys = n_keys;
+    run.ctx[0].st = run.gs[0] = st;
+}
+
+GenRun* gen_run_new(const int32_t* start, const uint8_t* ctx_mask, int B, int T, float temperature, int top_k, const float* noise,
+                    uint64_t seed, int32_t* tokens, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st) {
+    const GenRequest q{{start, 1, 1, nullptr, 0}, ctx_mask, B, T, 1, temperature, top_k, noise, seed, tokens, logits_out, ws, ws_bytes, st, nullptr};
+    return new GenRun(q);
+}
+void gen_run_free(GenRun* r) { delete r; }
+
+// One implementation for dimx_generate (pr = {start, 1, 1, NULL, 0}), dimx_generate_prompted and dimx_generate_beam: open, every
+// step, join; *ran is the route its steps took.
+static int generate_impl(dimx_handle h, const GenRequest& q, bool keep_prefill, bool prefill_only, StepRoute* ran) {
+    *ran = StepRoute{};
+    GenRun run(q);
+    DIMX_TRY(gen_open(h, run, keep_prefill, prefill_only, nullptr));
+    if (prefill_only) return DIMX_OK;
+    // steps
+    DIMX_TRY(gen_run_steps(h, run, run.nrun));
     // join
-    DIMX_TRY(gen_groups_join(h, G, st, gs));
-    if (route.chain && G == 1) {
-        DIMX_HIP(hipMemcpyAsync(h->chain_err_host, h->chain_err_dev, 4, hipMemcpyDeviceToHost, st));
-        DIMX_HIP(hipEventRecord(h->chain_err_ev, st));
+    DIMX_TRY(gen_groups_join(h, run.G, q.st, run.gs));
+    if (run.route.chain && run.G == 1) {
+        DIMX_HIP(hipMemcpyAsync(h->chain_err_host, h->chain_err_dev, 4, hipMemcpyDeviceToHost, q.st));
+        DIMX_HIP(hipEventRecord(h->chain_err_ev, q.st));
     }
-    *ran = route;
+    *ran = run.route;
     return DIMX_OK;
 }
 
@@ -889,6 +947,7 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
                   void* ws, size_t ws_bytes, void* stream) {
     const GenRequest q{{start, 1, 1, nullptr, 0}, ctx_mask, B, T, n_samples < 1 ? 1 : n_samples, temperature, top_k, exp_noise, seed,
                        tokens, logits_out, ws, ws_bytes, (hipStream_t)stream, nullptr};
+    DIMX_NO_SESSION(h, "generate");
     return generate_checked(h, q);
 }
 
@@ -897,6 +956,7 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
                            const float* exp_noise, uint64_t seed, int32_t* tokens, float* logits_out, int flags, void* ws,
                            size_t ws_bytes, void* stream) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_NO_SESSION(h, "generate_prompted");
     DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_prompted: prompts are implemented for variant 0 (SLMFT) only; this handle is variant %d",
                  h->variant);
     DIMX_REQUIRE(prompt && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
@@ -929,6 +989,7 @@ int dimx_generate_beam(dimx_handle h, const int32_t* prompt, int ld_prompt, cons
                        int32_t* backptr, float* logits_out, void* beam_state, size_t beam_state_bytes, int flags, void* ws, size_t ws_bytes,
                        void* stream) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_NO_SESSION(h, "generate_beam");
     DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_beam: beam search is implemented for variant 0 (SLMFT) only; this handle is variant %d",
                  h->variant);
     DIMX_REQUIRE(!h->xwin_on, DIMX_ERR_ARG, "generate_beam: not available while the cross-attention window is on (dimx_set_cross_lookahead)");
@@ -969,6 +1030,7 @@ int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b) {
 
 int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_NO_SESSION(h, "set_cross_lookahead");
     DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_cross_lookahead: online generation is implemented for variant 0 (SLMFT) only; this handle is variant %d",
                  h->variant);
     h->xwin_on = on ? 1 : 0;

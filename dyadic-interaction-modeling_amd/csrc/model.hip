@@ -699,8 +699,8 @@ void set_attn_packed(AttnArgs& a, int dtype, const void* q, const void* k, const
 // buffers of a block (BlockBufs, stages.hpp).
 
 // out[M, ldo] = act(A . W^T + bias) (+ residual [M, ldo], f32) as plain rows of out_dtype
-static int linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, int out_dtype, void* out, int ldo, hipStream_t st,
-                  int act = ACT_NONE, const float* residual = nullptr) {
+int linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, int out_dtype, void* out, int ldo, hipStream_t st, int act,
+           const float* residual) {
     GemmArgs g;
     gemm_lin(c, A, lda, L, M, g);
     g.out_dtype = out_dtype; g.act = act;
@@ -709,7 +709,7 @@ static int linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, in
     return launch_gemm(g, st);
 }
 // h[M, ld] += A . W^T (+ bias), f32
-static int residual_linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, float* h, int ld, hipStream_t st) {
+int residual_linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, float* h, int ld, hipStream_t st) {
     return linear(c, A, lda, L, M, DIMX_F32, h, ld, st, ACT_NONE, h);
 }
 
@@ -975,6 +975,7 @@ int dimx_destroy(dimx_handle h) {
     if (h->kv0_image) (void)hipFree(h->kv0_image);
     if (h->chain_err_host) (void)hipHostFree(h->chain_err_host);
     free_packed(h);
+    stream_forget(h);  // an open streaming session
     train_forget(h);   // the training plan cached for this handle (a later handle may reuse the address)
     delete h;
     return DIMX_OK;
@@ -1548,6 +1549,7 @@ int dimx_encode_speaker(dimx_handle h, const float* v_speaker, const uint8_t* ma
 
 int dimx_encode_ctx(dimx_handle h, const float* v_speaker, const float* v_audio, const uint8_t* mask, int B, int T,
                     int for_generate, float* x_s_out, void* ws, size_t ws_bytes, void* stream) {
+    DIMX_NO_SESSION(h, "encode_ctx");
     DIMX_REQUIRE(!h || h->variant != 2, DIMX_ERR_ARG,
                  "encode_ctx: the SLM variant builds its contexts with dimx_slm_encode + dimx_set_context");
     if (h && h->variant == 1)
@@ -1651,6 +1653,7 @@ int dimx_slm_encode(dimx_handle h, const float* v_speaker, const float* v_listen
 // (SLM.forward_decoder, code/seq2seq_pretrain.py:223-229; SLMFT :445-446).  x: [B,T,dim] f32 with row stride ldx.
 int dimx_set_context(dimx_handle h, const float* x, int ldx_rows, int which_patch, const float* v_audio, int B, int T,
                      int for_generate, void* ws, size_t ws_bytes, void* stream) {
+    DIMX_NO_SESSION(h, "set_context");
     DIMX_REQUIRE(h && h->variant != 1, DIMX_ERR_ARG, "set_context: not available for the legacy variant");
     DIMX_TRY(check_common(h, B, T, ws, ws_bytes, COMP_ENC | COMP_DEC));
     DIMX_REQUIRE(x && v_audio && (which_patch == 0 || (which_patch == 1 && h->variant == 2)) && ldx_rows >= T,
@@ -1791,6 +1794,7 @@ extern "C" {
 
 int dimx_decode_tf(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, const uint8_t* kv_mask, int B, int T,
                    float* logits, float* row_loss, int32_t* argmax_tok, void* ws, size_t ws_bytes, void* stream) {
+    DIMX_NO_SESSION(h, "decode_tf");
     DIMX_TRY(check_common(h, B, T, ws, ws_bytes, COMP_DEC));
     DIMX_REQUIRE(z_l && ctx_mask && logits && T >= 2, DIMX_ERR_ARG, "decode_tf: null argument or T < 2");
     DIMX_REQUIRE(h->ctx_ready && h->ctx_B == B && h->ctx_T == T && h->ctx_ws == ws && !h->ctx_for_generate,

@@ -166,6 +166,7 @@ struct GraphKey {
 namespace dimx {
 int vq_pe_buffers(dimx_ctx* c, int which, const float** pe_enc, const float** pe_dec);   // model.hip
 void train_forget(dimx_ctx* h);   // train.hip: drop the training plan cached for a handle (dimx_destroy)
+void stream_forget(dimx_ctx* h);  // stream.hip: drop the handle's streaming session (dimx_destroy)
 }
 
 struct dimx_ctx {
@@ -252,7 +253,10 @@ struct dimx_ctx {
     // online fine-tuning (dimx_set_train_lookahead): the same visibility in the decoder cross attention of
     // dimx_train_forward_backward, query row i = step t.  Independent of xwin_*.
     int twin_on = 0, twin_lookahead = 0;
-    dimx::MeshHead mesh;               // handles created with dimx_dims.mesh_dim > 0
+    // streaming session (stream.hip, dimx_stream_begin .. dimx_stream_end / dimx_stream_abort): one per handle; while it is
+    // open the stages that rebuild the context or generate return DIMX_ERR_STATE
+    void* stream_sess = nullptr;
+    dimx::MeshHead mesh;              // handles created with dimx_dims.mesh_dim > 0
     int lstm_faults = 0;                // LSTM layers whose group kernel reported a fault and that were rerun on the safe path
     int spk_embed_rows = 0;             // rows of speaker_embed.weight as last loaded (the host applies it in inference; the
                                         // DIM-Speaker training step lays its arena out by it); 0 = never loaded

@@ -282,6 +282,20 @@ int dimx_op_decode_attn_self(int dtype, const void* qkv, int ld, void* kcache, v
     return launch_decode_attn(a, (hipStream_t)stream);
 }
 
+int dimx_op_append_attn(int dtype, const float* qkv, int ld, void* kcache, void* vcache, void* out, int B, int H, int Tmax, int n0, int c,
+                        float scale, void* stream) {
+    DIMX_REQUIRE(qkv && H >= 1 && ld >= 3 * H * 64, DIMX_ERR_ARG, "append_attn: qkv rows of %d for %d heads", ld, H);
+    AppendAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dtype;
+    a.q = qkv; a.k = qkv + (size_t)H * 64; a.v = qkv + (size_t)2 * H * 64; a.ld = ld;
+    a.kcache = kcache; a.vcache = vcache; a.Tmax = Tmax;
+    a.out = out; a.o_ld = H * 64;
+    a.B = B; a.H = H; a.n0 = n0; a.c = c;
+    a.scale = scale;
+    return launch_append_attn(a, (hipStream_t)stream);
+}
+
 /* the table form's arguments of the first layer's self attention (DecodeAttnArgs.tab .. hist_ld, as self_args of generate.hip sets them) */
 struct OpTabArgs {
     const void* tab;

@@ -76,4 +76,44 @@ int check_common(dimx_handle h, int B, int T, void* ws, size_t ws_bytes, int nee
 
 int check_sampler_filter(int kind, float a, float b);   // generate.hip
 
+// out[M, ldo] = act(A . W^T + bias) (+ residual) as plain rows of out_dtype, and h[M, ld] += A . W^T (+ bias) in f32 (model.hip)
+int linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, int out_dtype, void* out, int ldo, hipStream_t st,
+           int act = ACT_NONE, const float* residual = nullptr);
+int residual_linear(const dimx_ctx* c, const void* A, int lda, const Linear& L, int M, float* h, int ld, hipStream_t st);
+
+// Append attention (stream_attn.hip): the c new rows of every clip against one encoder layer's K / V cache.  q / k / v: f32 rows
+// [B * c, ld] (row b * c + i, head h at column h * 64); the k / v rows become cache rows [n0, n0 + c) in the cache type, query i
+// attends over the rows 0 .. n0 + i; out [B * c, o_ld] in the cache type.
+constexpr int kAppendMaxRows = 16;
+struct AppendAttnArgs {
+    int dtype;            // the cache's and the output's type
+    const float *q, *k, *v;
+    int ld;
+    void *kcache, *vcache;   // [B, H, Tmax, 64]
+    int Tmax;
+    void* out;
+    int o_ld;
+    int B, H, n0, c;
+    float scale;
+};
+int launch_append_attn(const AppendAttnArgs& a, hipStream_t s);
+
+// A generation whose start and steps are driven across calls (generate.hip).  generate_impl opens one, runs all its steps and joins;
+// a streaming session (stream.hip) keeps one open between its pushes.
+struct GenRun;
+struct GenSessionSpec {   // what a session asks of gen_open in place of the handle's settings
+    int lookahead;        // the cross-attention window is on, with this look-ahead
+    int n_keys;           // ... and this key bound (the cache length while the session is open)
+};
+GenRun* gen_run_new(const int32_t* start, const uint8_t* ctx_mask, int B, int T, float temperature, int top_k, const float* noise,
+                    uint64_t seed, int32_t* tokens, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st);
+void gen_run_free(GenRun* r);
+int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, const GenSessionSpec* sess);
+int gen_run_steps(dimx_handle h, GenRun& run, int nsteps);          // the next nsteps steps of every group
+void gen_run_set_keys(GenRun& run, int n_keys, hipStream_t st);     // the cross attention's key bound and stream of the steps to come
+
+// no stage that rebuilds the context or generates may run on a handle whose streaming session is open
+#define DIMX_NO_SESSION(h, what) \
+    DIMX_REQUIRE(!(h) || !(h)->stream_sess, DIMX_ERR_STATE, what ": a streaming session is open on this handle (dimx_stream_end / dimx_stream_abort first)")
+
 }  // namespace dimx

@@ -316,6 +316,12 @@ class Engine:
                                        wsb, self._s()), "dimx_generate")
         return self._generated(tokens, lg, mask_u8, T, n_samples, None, return_logits, return_scores)
 
+    def stream(self, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0):
+        """Open a streaming session (dimx_stream_begin, include/dimx.h): B clips in lockstep, at most ``Tmax`` frames,
+        ``start`` [B] the listener's first codes, the sampler's arguments as ``generate`` takes them (``noise`` [Tmax-1, B, 512]).
+        Returns a StreamSession with a workspace of its own; one session per engine at a time."""
+        return StreamSession(self, B, Tmax, start, lookahead, temperature, top_k, noise, seed)
+
     def _generated(self, tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores):
         """generate()'s return value: tokens[, logits][, SeqScores of the sampled columns (``plen``: effective prompt lengths)]"""
         out = (tokens, lg) if return_logits else (tokens,)
@@ -428,6 +434,147 @@ class Engine:
 
 
 # ---------------------------------------------------------------------- kernel-level wrappers (tests)
+class StreamSession:
+    """One streaming session of an Engine (Engine.stream): push speaker frames in pieces, receive the listener tokens that are due.
+    A context manager; ``close()`` aborts a session that is still open.  ``tokens`` are all tokens so far [B, steps].  After
+    ``end`` or ``close`` the object may ``begin`` another clip in the same workspace."""
+
+    def __init__(self, eng, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0):
+        self.eng, self.B, self.Tmax, self.lookahead = eng, int(B), int(Tmax), int(lookahead)
+        self._open = False
+        lib, dev = eng.lib, eng.device
+        need = lib.dimx_stream_workspace_bytes(eng.h, self.B, self.Tmax)
+        if need == 0:
+            raise L.DimxError("dimx_stream_workspace_bytes(%d,%d) = 0: sessions need the SLMFT variant and 2 <= Tmax <= 2048" % (B, Tmax))
+        self._ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)   # the library needs no initialised workspace
+        self._V = eng.dims.num_tokens
+        self._tok = torch.zeros(self.B, self.Tmax - 1, dtype=torch.int32, device=dev)
+        self._lg = None
+        self.begin(start, temperature, top_k, noise, seed)
+
+    def _ws_ptr(self):
+        base = self._ws.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        return ctypes.c_void_p(aligned), self._ws.numel() - (aligned - base)
+
+    def begin(self, start, temperature=1.0, top_k=52, noise=None, seed=0):
+        """Start (another) clip: the arguments of Engine.stream; B, Tmax and the look-ahead are the session's."""
+        if self._open:
+            raise L.DimxError("StreamSession.begin: the session is open (end() or close() first)")
+        start = start.to(torch.int32).contiguous()
+        if noise is not None:
+            noise = noise.to(torch.float32).contiguous()
+            assert tuple(noise.shape) == (self.Tmax - 1, self.B, self._V)
+        self.eng._chk(start, noise)
+        assert tuple(start.shape) == (self.B,)
+        self._noise = noise    # the session reads it at every step
+        self._last = (0, 0)    # token columns the last push (or end) emitted
+        ws, wsb = self._ws_ptr()
+        L.check(self.eng.lib.dimx_stream_begin(self.eng.h, L.ptr(start), self.B, self.Tmax, self.lookahead, float(temperature), int(top_k),
+                                               L.ptr(self._noise), int(seed) & 0xFFFFFFFFFFFFFFFF, ws, wsb, self.eng._s()),
+                "dimx_stream_begin")
+        self._open = True
+        self.frames = 0
+        self.steps = 0
+
+    def _logits(self):
+        if self._lg is None:
+            self._lg = torch.zeros(self.B, self.Tmax - 1, self._V, dtype=torch.float32, device=self.eng.device)
+        return self._lg
+
+    def _took(self, n_new, return_logits, extra=()):
+        lo, hi = self.steps, self.steps + n_new
+        self.steps = hi
+        self._last = (lo, hi)
+        out = (self._tok[:, lo:hi],)
+        if return_logits:
+            out += (self._lg[:, lo:hi],)
+        out += tuple(extra)
+        return out if len(out) > 1 else out[0]
+
+    def push(self, v_speaker, v_audio, return_logits=False, return_x_s=False):
+        """v_speaker [B, c, 56], v_audio [B, c, 768]: the next c >= 1 frames of every clip -> the new tokens [B, n_new] (views of
+        the session's token rows)[, their logits [B, n_new, 512]][, the c new encoder rows x_s [B, c, 384]]."""
+        if not self._open:
+            raise L.DimxError("StreamSession.push: the session is closed")
+        B, c, _ = v_speaker.shape
+        v_speaker = v_speaker.to(torch.float32).contiguous()
+        v_audio = v_audio.to(torch.float32).contiguous()
+        self.eng._chk(v_speaker, v_audio)
+        assert B == self.B and v_audio.shape[:2] == (B, c)
+        x_s = torch.empty(B, c, self.eng.dims.dim, dtype=torch.float32, device=self.eng.device) if return_x_s else None
+        lg = self._logits() if return_logits else None
+        n_new = ctypes.c_int(0)
+        L.check(self.eng.lib.dimx_stream_push(self.eng.h, L.ptr(v_speaker), L.ptr(v_audio), c, L.ptr(self._tok), self.Tmax - 1, L.ptr(lg),
+                                              L.ptr(x_s), ctypes.byref(n_new), self.eng._s()), "dimx_stream_push")
+        self.frames += c
+        return self._took(n_new.value, return_logits, (x_s,) if return_x_s else ())
+
+    def end(self, return_logits=False):
+        """The clip is over: T = the frames pushed.  Runs the remaining steps, returns their tokens and closes the session."""
+        if not self._open:
+            raise L.DimxError("StreamSession.end: the session is closed")
+        lg = self._logits() if return_logits else None
+        n_new = ctypes.c_int(0)
+        L.check(self.eng.lib.dimx_stream_end(self.eng.h, L.ptr(self._tok), self.Tmax - 1, L.ptr(lg), ctypes.byref(n_new), self.eng._s()),
+                "dimx_stream_end")
+        self._open = False
+        return self._took(n_new.value, return_logits)
+
+    @property
+    def tokens(self):
+        return self._tok[:, :self.steps]
+
+    @property
+    def is_open(self):
+        return self._open
+
+    def state(self):
+        """(frames, steps, open) as the library holds them (dimx_stream_state)."""
+        f, s, o = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        L.check(self.eng.lib.dimx_stream_state(self.eng.h, ctypes.byref(f), ctypes.byref(s), ctypes.byref(o)), "dimx_stream_state")
+        return f.value, s.value, bool(o.value)
+
+    def set_events(self, events):
+        """Measurement: four recorded ``torch.cuda.Event(enable_timing=True)`` (or None to stop) that every later push records at
+        its start, after the encoder increment, after the cross K/V append and after the decode steps (dimx_stream_set_events)."""
+        self._events = events      # kept alive: the library holds their handles
+        hs = [ctypes.c_void_p(e.cuda_event) for e in events] if events else [None] * 4
+        L.check(self.eng.lib.dimx_stream_set_events(self.eng.h, *hs), "dimx_stream_set_events")
+
+    def motion(self, window=None, all_rows=False):
+        """Chunked VQ decode: ``Engine.vq_decode(1, tokens[:, lo:hi])`` with hi = the tokens so far and lo = hi - ``window`` (0 for
+        None), positions restarting at the slice; returns the rows [B, n_new, 56] of the tokens the last push (or ``end``) emitted
+        -- the slice is widened to hold them all -- or, with ``all_rows``, every row of the slice.  A windowed decode is another
+        function of the tokens than the whole-clip decode, and nothing was trained for it; after ``end``,
+        ``motion(None, all_rows=True)`` is the whole-clip decode."""
+        lo_new, hi = self._last
+        lo = 0 if window is None else max(hi - int(window), 0)
+        lo = min(lo, lo_new)
+        if hi == lo or (hi == lo_new and not all_rows):
+            return torch.empty(self.B, 0, self.eng.dims.vq_in_dim, dtype=torch.float32, device=self.eng.device)
+        out = self.eng.vq_decode(1, self._tok[:, lo:hi].contiguous())
+        return out if all_rows else out[:, lo_new - lo:]
+
+    def close(self):
+        if self._open and getattr(self.eng, "h", None):
+            self.eng.lib.dimx_stream_abort(self.eng.h)
+        self._open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _pad_k(w, mult):
     N, K = w.shape
     Kp = (K + mult - 1) // mult * mult
@@ -778,6 +925,21 @@ def op_decode_attn(q, kcache, vcache, n_keys, scale, kmask=None, nsplit=0):
                                     Tmax, n_keys, float(scale), L.ptr(kmask), nsplit, 1 if q_f32 else 0,
                                     L.stream_ptr(q.device)),
             "dimx_op_decode_attn")
+    return out
+
+
+def op_append_attn(qkv, kcache, vcache, n0, scale):
+    """Append attention (dimx_op_append_attn): qkv [B, c, 3*H*64] f32 (q | k | v of the c new rows of every clip), kcache / vcache
+    [B, H, Tmax, 64] (f32 or bf16) holding n0 rows.  The k / v rows become cache rows [n0, n0 + c) (in place), query i attends over
+    the rows 0 .. n0 + i -> [B, c, H*64] in the cache type."""
+    lib = L.load()
+    B, H, Tmax, _ = kcache.shape
+    Bq, c, ld = qkv.shape
+    assert Bq == B and qkv.dtype == torch.float32 and qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
+    bf = kcache.dtype == torch.bfloat16
+    out = torch.empty(B, c, H * 64, dtype=kcache.dtype, device=qkv.device)
+    L.check(lib.dimx_op_append_attn(L.BF16 if bf else L.F32, L.ptr(qkv), ld, L.ptr(kcache), L.ptr(vcache), L.ptr(out), B, H, Tmax,
+                                    int(n0), c, float(scale), L.stream_ptr(qkv.device)), "dimx_op_append_attn")
     return out
 
 

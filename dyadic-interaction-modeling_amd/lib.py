@@ -63,6 +63,14 @@ SIGNATURES = {
     "dimx_set_sampler_filter": (c_int, [c_void_p, c_int, c_float, c_float]),
     "dimx_set_cross_lookahead": (c_int, [c_void_p, c_int, c_int]),
     "dimx_cross_lookahead": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "dimx_stream_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "dimx_stream_begin": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_uint64, c_void_p, c_size_t,
+                                  c_void_p]),
+    "dimx_stream_push": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
+    "dimx_stream_end": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
+    "dimx_stream_abort": (c_int, [c_void_p]),
+    "dimx_stream_state": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "dimx_stream_set_events": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dimx_encode_ctx": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
     "dimx_legacy_speaker_features": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
@@ -154,6 +162,8 @@ SIGNATURES = {
                                        c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "dimx_op_decode_attn": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_float, c_void_p, c_int, c_int, c_void_p]),
+    "dimx_op_append_attn": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                    c_void_p]),
     "dimx_op_decode_attn_self": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                          c_void_p, c_float, c_int, c_void_p]),
     "dimx_op_decode_attn_ex": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_int, c_void_p, c_void_p, c_void_p,

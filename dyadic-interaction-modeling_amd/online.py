@@ -13,6 +13,8 @@ the speaker frames below vis(t) and nothing else.
 
 What the mode does not make causal: the audio features are whatever the caller's extractor produced, and the listener VQ-VAE
 decoder runs over the whole token sequence.  The guarantee is about the tokens.
+
+This module says what a step may read; *when* a step runs as the frames arrive is dimx/stream.py (streaming sessions).
 """
 import numpy as np
 

@@ -226,6 +226,19 @@ class SLMFT(_EngineOwner):
             return 0.0, out[0].long(), out[1]
         return 0.0, out.long()
 
+    @torch.no_grad()
+    def stream(self, B, Tmax, start, lookahead=0, greedy=False, noise=None, seed=None, temperature=1.0, top_k=52):
+        """A streaming session (dimx.engine.StreamSession; dimx.stream is the schedule): push the speaker's motion and audio
+        frames in pieces, receive the listener tokens as they fall due.  ``start`` [B]: the listener's first codes, the caller's --
+        a live system has no ground-truth first code.  The sampler arguments are ``forward_decoder``'s.  Fed a whole clip, the
+        session emits the tokens of ``forward(mode='val', lookahead=lookahead)`` with ``start`` = that clip's first code."""
+        eng = self.engine(start.device)
+        if greedy:
+            temperature, seed_v = 0.0, 0
+        else:
+            seed_v = 0 if noise is not None else self._user_seed(seed)
+        return eng.stream(B, Tmax, start, lookahead, temperature, top_k, noise, seed_v)
+
     def draw_kv_mask(self, B, T, device, generator=None):
         """AutoregressiveWrapper(mask_prob=0.15) key mask (reference ctor :419): keep-mask [B,T-1]."""
         n = T - 1

@@ -1,0 +1,74 @@
+"""Streaming DIM-Listener: feed a dyad clip to the model in chunks of speaker frames, as a live system would, and receive the
+listener tokens (and their decoded motion) as they fall due (SLMFT.stream; the schedule is dimx/stream.py).
+
+    python examples/stream_s2s_pretrain.py --synthetic --chunk 8 --lookahead 0 [--frames 120] [--batch 2] [--window 32] [--bf16]
+
+Prints, per push, the frames in, the tokens out and the device-event time of the push; at the end, whether the session's tokens
+equal ``forward(mode="val", lookahead=L)`` on the whole clip.  Without ``--synthetic`` a checkpoint is loaded from ``--ckpt``; the
+clip itself is synthetic either way (a live source is the caller's).
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import dimx  # noqa: E402,F401
+from dimx import lib as L  # noqa: E402
+from dimx import prng, stream  # noqa: E402
+from dimx.seq2seq_pretrain import SLMFT  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--synthetic", action="store_true", help="synthetic weights (no checkpoint)")
+    ap.add_argument("--ckpt", default="best_vico_causal.pt")
+    ap.add_argument("--chunk", type=int, default=8, help="speaker frames per push")
+    ap.add_argument("--lookahead", type=int, default=0, help="L of dimx.online: < 0 a reaction delay, > 0 a look-ahead buffer")
+    ap.add_argument("--frames", type=int, default=120)
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--window", type=int, default=32, help="tokens the chunked VQ decode sees (0: all so far)")
+    ap.add_argument("--bf16", action="store_true")
+    args = ap.parse_args()
+    torch.set_grad_enabled(False)
+    dev = torch.device("cuda:0")
+    model = SLMFT(numeric_mode=L.MODE_PERF_BF16 if args.bf16 else L.MODE_PARITY_F32).eval()
+    if not args.synthetic:
+        if not os.path.isfile(args.ckpt):
+            sys.exit("no checkpoint at %s (pass --synthetic for synthetic weights)" % args.ckpt)
+        model.load_state_dict(torch.load(args.ckpt, map_location="cpu")["state_dict"])
+    B, T, Lh = args.batch, args.frames, args.lookahead
+    v_s = torch.from_numpy(prng.normal(5, "stream.vs", (B, T, 56))).to(dev)
+    v_l = torch.from_numpy(prng.normal(5, "stream.vl", (B, T, 56))).to(dev)
+    v_a = torch.from_numpy(prng.normal(5, "stream.va", (B, T, 768))).to(dev)
+    mask = torch.ones(B, T, dtype=torch.bool, device=dev)
+    # the whole-clip call starts from the ground-truth first listener code; the session is given the same one
+    _, z_l = model.forward_vq(v_s, v_l, mask, with_speaker=False)
+    window = args.window or None
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    total = 0.0
+    with model.stream(B, T, z_l[:, 0], lookahead=Lh, greedy=True) as s:
+        for c in stream.chunks(T, args.chunk):
+            n = s.frames
+            e0.record()
+            new = s.push(v_s[:, n:n + c], v_a[:, n:n + c])
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1)
+            total += ms
+            motion = s.motion(window)
+            print("frames %4d -> %4d   tokens out %3d (steps %4d)   motion rows %3d   push %.3f ms" % (n, s.frames, new.shape[1], s.steps, motion.shape[1], ms))
+        tail = s.end()
+        print("end: %d more tokens, %d in all; pushes took %.1f ms = %.3f ms per frame" % (tail.shape[1], s.steps, total, total / T))
+        tokens = s.tokens.long()
+    _, _, _, ref = model(v_s, v_l, v_a, mask, mode="val", greedy=True, lookahead=Lh, return_tokens=True)
+    same = bool(torch.equal(tokens, ref))
+    print("session tokens equal forward(mode='val', lookahead=%d) on the whole clip: %s" % (Lh, same))
+    if not same:
+        first = (tokens != ref).long().argmax(1).tolist()
+        print("first differing step per clip: %s (a near-tie of two logits may fall either way between two launch shapes)" % first)
+
+
+if __name__ == "__main__":
+    main()

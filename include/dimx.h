@@ -332,6 +332,47 @@ int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b);
 int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead);
 /* The handle's current setting (either pointer may be NULL). */
 int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
+/* Streaming sessions (csrc/stream.hip; the schedule is dimx/stream.py): the speaker arrives in pieces, the listener's
+ * tokens leave as soon as they are due.  A session fed a clip in pieces computes what dimx_encode_ctx + dimx_generate under
+ * dimx_set_cross_lookahead(1, lookahead) compute on the whole clip: the speaker encoders are causal, so the context rows of the new
+ * frames are computed from those frames and per-layer K / V caches alone (dimx_op_append_attn), and decode step t (it produces
+ * listener position t + 1) runs as soon as the frames 0 .. t + 1 + max(lookahead, 0) exist.  Variant 0, one sample per clip, the B
+ * clips in lockstep, every pushed frame valid.  One open session per handle.
+ *   dimx_stream_workspace_bytes: bytes of the session's workspace (a dimx_generate workspace for (B, Tmax), the encoder caches, the
+ *     token and logit rows of all Tmax - 1 steps, the scratch of a 16-row encoder increment); 0 for an unsupported shape
+ *     (variant != 0, B < 1, Tmax outside [2, min(2048, max_seq_len)]).  The caller need not initialise it.
+ *   dimx_stream_begin: start [B] int32 (device; copied), noise [Tmax-1, B, 512] or NULL and the sampler arguments as dimx_generate
+ *     takes them (the handle's sampler filter applies; dimx_set_cross_lookahead's setting is neither read nor changed).  ws stays
+ *     the session's until it closes.  DIMX_ERR_STATE when a session is open, DIMX_ERR_ARG for a handle of variant 1 / 2 or a shape
+ *     outside the ranges above, DIMX_ERR_WORKSPACE for too small a workspace; nothing is launched in those cases.
+ *   dimx_stream_push: c >= 1 new frames of every clip, v_speaker [B, c, 56], v_audio [B, c, 768] (device f32).  Runs the encoder
+ *     increment (launches of at most 16 rows per clip), appends the cross K / V rows, runs the steps now due.  The new tokens land
+ *     in columns [done, done + *n_new) of tokens_out [B, ld_tok] (done = the steps run before the call), their logits, when
+ *     logits_out is given, in the same columns of logits_out [B, ld_tok, 512]; x_s_out, when given, receives the c new encoder
+ *     rows [B, c, 384] (the rows dimx_encode_ctx returns).  DIMX_ERR_STATE without an open session (before begin, after end);
+ *     DIMX_ERR_ARG for c < 1, frames past Tmax, a null argument or ld_tok below the columns written; nothing is launched then and
+ *     the session stays as it was.
+ *   dimx_stream_end: T := the frames pushed (>= 2, else DIMX_ERR_ARG and the session stays open); runs the remaining steps up to
+ *     T - 1 with the key bound T and closes the session.
+ *   dimx_stream_abort: closes the session, if any, without running anything.
+ *   dimx_stream_state: frames pushed, steps run, open (0 / 1); any pointer may be NULL; zeros without a session.
+ * While a session is open dimx_encode_ctx, dimx_set_context, dimx_generate, dimx_generate_prompted, dimx_generate_beam, dimx_decode_tf
+ * and dimx_set_cross_lookahead return DIMX_ERR_STATE; the VQ stages and the dimx_op_* calls stay usable.  The steps run on the
+ * one-kernel-per-op route without the captured step graphs: the chain kernels answer a placement fault by regenerating the whole
+ * call, which a session cannot offer.  All calls of a session go to one stream (or are ordered by the caller). */
+size_t dimx_stream_workspace_bytes(dimx_handle h, int B, int Tmax);
+int dimx_stream_begin(dimx_handle h, const int32_t* start, int B, int Tmax, int lookahead, float temperature, int top_k, const float* noise,
+                      uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+int dimx_stream_push(dimx_handle h, const float* v_speaker, const float* v_audio, int c, int32_t* tokens_out, int ld_tok, float* logits_out,
+                     float* x_s_out, int* n_new, void* stream);
+int dimx_stream_end(dimx_handle h, int32_t* tokens_out, int ld_tok, float* logits_out, int* n_new, void* stream);
+int dimx_stream_abort(dimx_handle h);
+int dimx_stream_state(dimx_handle h, int* frames, int* steps, int* open);
+/* Measurement (tools/bench_stream.py): four hipEvent_t of the caller's (any may be NULL) that every later push of the open session
+ * records on its stream -- at its start, after the encoder increment, after the cross K / V append, after the decode steps and the
+ * copy of their tokens.  A push of more than 16 frames interleaves the first two parts per launch group; the second event is then
+ * the last group's.  The events must outlive the session or be replaced by NULL.  DIMX_ERR_STATE without an open session. */
+int dimx_stream_set_events(dimx_handle h, void* ev_start, void* ev_encoded, void* ev_appended, void* ev_stepped);
 /* Decoders without positional embedding (variant 0): the first layer's q/k/v depend on the input token alone, so dimx_generate
  * reads them from a table over the token ids instead of projecting them at every step.  The table is built with the decode
  * step's own kernels (bit-identical rows) on first use and whenever the rows per call, the numeric mode or the decoder weights
@@ -662,6 +703,17 @@ int dimx_op_decode_attn_tab(int dtype, const void* q, int q_ld, int q_is_f32, in
 int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
                             void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys, const uint8_t* kmask,
                             int kmask_ld, int rows_per_clip, float scale, int nsplit, int lookahead, void* stream);
+/* Append attention (csrc/stream_attn.hip; what a streaming session launches for every encoder layer): the self attention of the c
+ * new rows of every clip over a growing K / V cache.  qkv [B*c, ld] f32 (row b*c + i; q | k | v at columns 0, H*64, 2*H*64, ld >= 3*H*64,
+ * the layout the q/k/v projection writes), kcache / vcache [B, H, Tmax, 64] of dtype (DIMX_F32 / DIMX_BF16), n0 rows already cached,
+ * 1 <= c <= 16, n0 + c <= Tmax <= 2048.  The k / v rows are rounded to dtype and stored as cache rows [n0, n0 + c); query i attends
+ * over the cache rows 0 .. n0 + i -- the new ones as stored -- with scale * q.k, softmax in f32; out [B*c, H*64] in dtype.
+ *   - The output row of a query has the same bits whether the row arrives alone (c = 1) or anywhere inside a chunk.
+ *   - Cache rows at or past n0 + c are never read; rows outside [n0, n0 + c) are never written.
+ * One launch, no atomics, fixed orders.  DIMX_ERR_ARG (nothing launched) for a null or misaligned (16 bytes) operand or a shape outside
+ * the ranges above. */
+int dimx_op_append_attn(int dtype, const float* qkv, int ld, void* kcache, void* vcache, void* out, int B, int H, int Tmax, int n0, int c,
+                        float scale, void* stream);
 /* Decode-step residual + pre-norm: x[M,C] += sum_s slabs[s] (fixed order), y = LayerNorm(x) * gamma (no bias). */
 /* The prefill's fused feed-forward sublayer alone (csrc/mlp_fused.hip; unit parity): x [M,C] f32 on the device is replaced by
  * x + W2 . gelu(W1 . LayerNorm(x) + b1) + b2 with bf16 operands and f32 accumulation.  w1 [F,C], b1 [F] (or NULL), w2 [C,F] are HOST
