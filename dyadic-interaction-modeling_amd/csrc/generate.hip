@@ -551,8 +551,11 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
 // Cross attention reads the context K / V where dimx_encode_ctx(for_generate = 1) left them, [B, H, Tp, 64]: the bf16
 // attention takes that layout as it is (row-major V); the f32 attention reads V^T, so the f32 mode transposes one layer's V
 // into scratch first (a copy, not a second projection of the context).
+// win (pr.win): the cross attention is the windowed one (win_attn.hip) -- row t sees the keys below clamp(t + 2 + *win, 1, n_keys),
+// what decode step t reads; f32 queries, V row-major as it lies, no transpose.
 static int gen_prefill(dimx_handle h, const CtxPersist& cp, const GenScratch& gs, const PrefillScratch& s, const GenPrompt& pr,
-                       const uint8_t* ctx_mask, int B, int T, int S, int32_t* tokens, hipStream_t st) {
+                       const uint8_t* ctx_mask, int B, int T, int S, int32_t* tokens, hipStream_t st, const int* win = nullptr,
+                       int n_keys = 0) {
     const DecGeom& dg = h->decg;
     const int n0 = pr.step0, M = B * n0, DD = dg.dim, heads = dg.heads, D = dg.dim_head;
     const int np = tpad(n0), Tp = tpad(T), V = dg.num_tokens;
@@ -570,6 +573,25 @@ static int gen_prefill(dimx_handle h, const CtxPersist& cp, const GenScratch& gs
         if (l == dg.depth - 1) break;
         a.scale = 1.0f / sqrtf((float)D); a.causal = 1;
         DIMX_TRY(attn_out(h, s, a, h->dec.self_[l].out, DD, st));
+        if (win) {
+            const XAttn& x = h->dec.cross[l];
+            float* qf = win_q_rows(s, B, n0, heads * D, es_of(h));
+            DIMX_REQUIRE(qf, DIMX_ERR_WORKSPACE, "generate: no room for the windowed prefill's f32 queries");
+            DIMX_TRY(launch_layernorm(h->at, s.h, s.y, x.ln_g, nullptr, M, DD, st));
+            DIMX_TRY(linear(h, s.y, DD, x.qkv, M, DIMX_F32, qf, heads * D, st));
+            WinAttnArgs w;
+            w.dtype = h->at;
+            w.q = qf; w.ld = heads * D;
+            w.kcache = cp.ck[l]; w.vcache = cp.cv[l]; w.Tp = Tp;
+            w.out = s.o; w.o_ld = heads * D;
+            w.B = B; w.H = heads; w.Lq = n0; w.t0 = 0; w.n_keys = n_keys; w.lookahead = *win;
+            w.kmask = ctx_mask; w.kmask_ld = T;
+            w.scale = 1.0f / sqrtf((float)D);
+            DIMX_TRY(launch_win_attn(w, st));
+            DIMX_TRY(residual_linear(h, s.o, heads * D, x.out, M, s.h, DD, st));
+            DIMX_TRY(ff_sublayer(h, s, h->dec.ff[l].ln_g, nullptr, h->dec.ff[l].f1, h->dec.ff[l].f2, nullptr, ACT_GELU_ERF, M, DD, st));
+            continue;
+        }
         // cross attention over the context K / V of the generation layout [B,H,Tp,64]; the f32 attention reads V^T from s.cvt
         set_attn_packed(a, h->at, s.q, cp.ck[l], rowv ? cp.cv[l] : s.cvt, s.o, B, heads, n0, T, D, Tp, rowv);
         a.k_sb = (long)heads * Tp * D; a.k_sh = (long)Tp * D; a.k_st = D;
@@ -779,7 +801,8 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         // the prefill forms no logits: those columns of logits_out read zero
         if (q.logits_out)
             DIMX_HIP(hipMemset2DAsync(q.logits_out, (size_t)n * h->decg.num_tokens * 4, 0, (size_t)pr.step0 * h->decg.num_tokens * 4, R, st));
-        DIMX_TRY(gen_prefill(h, cp, s, ps, pr, q.ctx_mask, B, T, S, q.tokens, st));
+        DIMX_REQUIRE(!pr.win || route.win, DIMX_ERR_STATE, "generate: a windowed prefill without the cross-attention window");
+        DIMX_TRY(gen_prefill(h, cp, s, ps, pr, q.ctx_mask, B, T, S, q.tokens, st, pr.win ? &route.lookahead : nullptr, sess ? sess->n_keys : T));
     }
     if (prefill_only) return DIMX_OK;
     // start
@@ -811,8 +834,8 @@ void gen_run_set_keys(GenRun& run, int n_keys, hipStream_t st) {
 }
 
 GenRun* gen_run_new(const int32_t* start, const uint8_t* ctx_mask, int B, int T, float temperature, int top_k, const float* noise,
-                    uint64_t seed, int32_t* tokens, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st) {
-    const GenRequest q{{start, 1, 1, nullptr, 0}, ctx_mask, B, T, 1, temperature, top_k, noise, seed, tokens, logits_out, ws, ws_bytes, st, nullptr};
+                    uint64_t seed, int32_t* tokens, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st, int ld_prompt, int P) {
+    const GenRequest q{{start, ld_prompt, P, nullptr, P - 1, P > 1}, ctx_mask, B, T, 1, temperature, top_k, noise, seed, tokens, logits_out, ws, ws_bytes, st, nullptr};
     return new GenRun(q);
 }
 void gen_run_free(GenRun* r) { delete r; }
@@ -962,22 +985,23 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
     DIMX_REQUIRE(prompt && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
                  "generate_prompted: need 1 <= Pmax <= T - 1 and ld_prompt >= Pmax (Pmax=%d T=%d ld_prompt=%d)", Pmax, T, ld_prompt);
     DIMX_REQUIRE(P0 >= 1 && P0 <= Pmax, DIMX_ERR_ARG, "generate_prompted: need 1 <= P0 <= Pmax (P0=%d Pmax=%d)", P0, Pmax);
-    DIMX_REQUIRE((flags & ~3) == 0, DIMX_ERR_ARG, "generate_prompted: unknown flags 0x%x", flags);
+    DIMX_REQUIRE((flags & ~7) == 0, DIMX_ERR_ARG, "generate_prompted: unknown flags 0x%x", flags);
     const int S = n_samples < 1 ? 1 : n_samples;
-    // bit 0: no prefill, the whole prompt goes through forced decode steps.  Online generation (dimx_set_cross_lookahead) too: the
-    // prefill's attention has no per-query key bound, the decode step's has
-    const int p0 = ((flags & 1) || h->xwin_on) ? 1 : P0;
-    // bit 1 is not part of the public flag set: tools/bench_prompt.py times the prefill stage alone with it
-    DIMX_REQUIRE(!(flags & 2) || p0 >= 2, DIMX_ERR_ARG, "generate_prompted: flags bit 1 (the prefill stage alone) without a prefill (P0=%d, flags 0x%x)",
+    // bit 0: no prefill, the whole prompt goes through forced decode steps.  Online generation (dimx_set_cross_lookahead) too, unless
+    // bit 1 asks for the windowed prefill (win_attn.hip): the offline prefill's attention has no per-query key bound
+    const bool win_prefill = h->xwin_on && (flags & 2) && !(flags & 1);
+    const int p0 = ((flags & 1) || (h->xwin_on && !win_prefill)) ? 1 : P0;
+    // bit 2 is not part of the public flag set: tools/bench_prompt.py times the prefill stage alone with it
+    DIMX_REQUIRE(!(flags & 4) || p0 >= 2, DIMX_ERR_ARG, "generate_prompted: flags bit 2 (the prefill stage alone) without a prefill (P0=%d, flags 0x%x)",
                  P0, flags);
     DIMX_REQUIRE(p0 == 1 || h->decg.dim_head == 64, DIMX_ERR_ARG, "generate_prompted: the prefill needs 64-wide heads");
     DIMX_REQUIRE(B >= 1 && T <= h->d.max_seq_len, DIMX_ERR_ARG, "B=%d T=%d out of range (T <= %d)", B, T, h->d.max_seq_len);
     const size_t need = workspace_bytes_prompt(h, B, T, S, p0);
     DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "generate_prompted: workspace %zu < required %zu (dimx_workspace_bytes_prompt)",
                  ws_bytes, need);
-    const GenRequest q{{prompt, ld_prompt, Pmax, prompt_len, p0 - 1}, ctx_mask, B, T, S, temperature, top_k, exp_noise, seed,
+    const GenRequest q{{prompt, ld_prompt, Pmax, prompt_len, p0 - 1, win_prefill && p0 >= 2}, ctx_mask, B, T, S, temperature, top_k, exp_noise, seed,
                        tokens, logits_out, ws, ws_bytes, (hipStream_t)stream, nullptr};
-    if (flags & 2) {   // the prefill stage alone, nothing is generated
+    if (flags & 4) {   // the prefill stage alone, nothing is generated
         StepRoute route;
         return generate_impl(h, q, false, true, &route);
     }

@@ -760,6 +760,14 @@ int cross_attn_sublayer(const dimx_ctx* c, const BlockBufs& b, const XAttn& x, A
     return attn_out(c, b, a, x.out, C, st);
 }
 
+// The f32 query rows [B * n, inner] of a windowed cross attention (win_attn.hip) in a decoder stack's block buffers: the self
+// attention's k | vt, which a layer's cross attention no longer needs and which lie back to back in the arena (k: B * n rows, vt:
+// B * tpad(n)), hold two operand-type rows per query row -- one f32 row.  nullptr if a plan ever stops laying them out that way.
+float* win_q_rows(const BlockBufs& b, int B, int n, int inner, size_t es) {
+    const unsigned char *lo = (const unsigned char*)b.k, *hi = (const unsigned char*)b.vt + (size_t)B * inner * tpad(n) * es;
+    return lo && b.vt && lo < hi && (size_t)(hi - lo) >= (size_t)B * n * inner * 4 ? (float*)b.k : nullptr;
+}
+
 // ------------------------------------------------------------------ VQ-VAE stacks
 struct VQScratch : BlockBufs {
     void *xa, *h1;
@@ -1828,6 +1836,55 @@ int dimx_decode_tf(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, c
     return DIMX_OK;
 }
 
+int dimx_decode_tf_win(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, int B, int T, int lookahead, float* logits,
+                       float* row_loss, int32_t* argmax_tok, void* ws, size_t ws_bytes, void* stream) {
+    DIMX_NO_SESSION(h, "decode_tf_win");
+    DIMX_TRY(check_common(h, B, T, ws, ws_bytes, COMP_DEC));
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "decode_tf_win: implemented for variant 0 (SLMFT) only; this handle is variant %d", h->variant);
+    DIMX_REQUIRE(z_l && ctx_mask && logits && T >= 2, DIMX_ERR_ARG, "decode_tf_win: null argument or T < 2");
+    DIMX_REQUIRE(h->ctx_ready && h->ctx_B == B && h->ctx_T == T && h->ctx_ws == ws && h->ctx_for_generate, DIMX_ERR_STATE,
+                 "decode_tf_win: call dimx_encode_ctx(for_generate=1) with the same B, T, ws first");
+    hipStream_t st = (hipStream_t)stream;
+    CtxPersist cp;
+    Arena ar = scratch_arena(h, ws, ws_bytes, B, T, &cp);
+    DecScratch s;
+    plan_dec(h, ar, B, T, s);
+    const DecGeom& dg = h->decg;
+    const int n = T - 1, M = B * n, DD = dg.dim, heads = dg.heads, D = dg.dim_head, inner = heads * D;
+    const int V = dg.num_tokens;
+    DIMX_REQUIRE(!ar.overflow, DIMX_ERR_WORKSPACE, "decode_tf_win: workspace overflow");
+    float* qf = win_q_rows(s, B, n, inner, es_of(h));
+    DIMX_REQUIRE(qf, DIMX_ERR_WORKSPACE, "decode_tf_win: no room for the f32 queries");
+    DIMX_REQUIRE(D == 64, DIMX_ERR_ARG, "decode_tf_win: needs 64-wide heads (dim_head %d)", D);
+    DIMX_TRY(launch_shift_tokens(z_l, s.inp, s.tgt, B, T, st));
+    DIMX_TRY(launch_gather_rows(DIMX_F32, h->dec.tok_emb, DD, V, s.inp, s.h, DD, M, DD, st));
+    if (dg.abs_pos) DIMX_TRY(launch_add_pos_rows(s.h, h->dec.pos_emb, M, n, DD, 1.0f / sqrtf((float)DD), st));
+    for (int l = 0; l < dg.depth; ++l) {
+        AttnArgs a;
+        DIMX_TRY(self_attn_qkv(h, s, h->dec.self_[l].ln_g, nullptr, h->dec.self_[l].qkv, B, n, DD, heads, D, a, st));
+        a.scale = 1.0f / sqrtf((float)D); a.causal = 1;
+        DIMX_TRY(attn_out(h, s, a, h->dec.self_[l].out, DD, st));
+        // cross attention under the window: f32 queries against the generation-layout K / V [B,H,Tp,64] (win_attn.hip)
+        const XAttn& x = h->dec.cross[l];
+        DIMX_TRY(launch_layernorm(h->at, s.h, s.y, x.ln_g, nullptr, M, DD, st));
+        DIMX_TRY(linear(h, s.y, DD, x.qkv, M, DIMX_F32, qf, inner, st));
+        WinAttnArgs w;
+        w.dtype = h->at;
+        w.q = qf; w.ld = inner;
+        w.kcache = cp.ck[l]; w.vcache = cp.cv[l]; w.Tp = tpad(T);
+        w.out = s.o; w.o_ld = inner;
+        w.B = B; w.H = heads; w.Lq = n; w.t0 = 0; w.n_keys = T; w.lookahead = lookahead;
+        w.kmask = ctx_mask; w.kmask_ld = T;
+        w.scale = 1.0f / sqrtf((float)D);
+        DIMX_TRY(launch_win_attn(w, st));
+        DIMX_TRY(residual_linear(h, s.o, inner, x.out, M, s.h, DD, st));
+        DIMX_TRY(ff_sublayer(h, s, h->dec.ff[l].ln_g, nullptr, h->dec.ff[l].f1, h->dec.ff[l].f2, nullptr, ACT_GELU_ERF, M, DD, st));
+    }
+    DIMX_TRY(launch_layernorm(h->at, s.h, s.y, h->dec.final_g, nullptr, M, DD, st));
+    DIMX_TRY(linear(h, s.y, DD, h->dec.logits, M, DIMX_F32, logits, V, st));
+    if (row_loss || argmax_tok) DIMX_TRY(launch_ce_argmax(logits, s.tgt, row_loss, argmax_tok, M, V, st));
+    return DIMX_OK;
+}
 
 int dimx_lstm_faults(dimx_handle h) { return h ? h->lstm_faults : 0; }
 

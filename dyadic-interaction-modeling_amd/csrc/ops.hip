@@ -391,6 +391,21 @@ int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, in
                              kmask_ld, rows_per_clip, scale, nsplit, 1, lookahead, stream);
 }
 
+/* windowed cross attention for many queries (win_attn.hip): query row i at position t0 + i, keys j < clamp(t0 + i + 2 + lookahead, 1, n_keys) */
+int dimx_op_cross_attn_win(int dtype, const float* q, int ld, const void* kcache, const void* vcache, int Tp, void* out, int o_ld, int B, int H,
+                           int Lq, int t0, int n_keys, int lookahead, const uint8_t* kmask, int kmask_ld, float scale, void* stream) {
+    WinAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dtype;
+    a.q = q; a.ld = ld;
+    a.kcache = kcache; a.vcache = vcache; a.Tp = Tp;
+    a.out = out; a.o_ld = o_ld;
+    a.B = B; a.H = H; a.Lq = Lq; a.t0 = t0; a.n_keys = n_keys; a.lookahead = lookahead;
+    a.kmask = kmask; a.kmask_ld = kmask_ld;
+    a.scale = scale;
+    return launch_win_attn(a, (hipStream_t)stream);
+}
+
 size_t dimx_mlp_fused_packed_bytes(int C, int F) { return mlp_fused_packed_bytes(C, F); }
 
 int dimx_mlp_fused_pack(const float* w1_host, const float* b1_host, const float* w2_host, int C, int F, void* out_host, size_t out_bytes) {

@@ -35,6 +35,8 @@ int attn_out(const dimx_ctx* c, const BlockBufs& b, AttnArgs& a, const Linear& o
 int cross_attn_sublayer(const dimx_ctx* c, const BlockBufs& b, const XAttn& x, AttnArgs& a, const uint8_t* ctx_mask, int C, hipStream_t st,
                         const float* v_rows = nullptr);
 
+float* win_q_rows(const BlockBufs& b, int B, int n, int inner, size_t es);
+
 struct CtxPersist {
     void* ck[8];
     void* cv[8];
@@ -63,6 +65,7 @@ struct GenPrompt {
     int ld, Pmax;
     const int32_t* len;  // [B] prompt lengths (clamped to [step0 + 1, Pmax] by the sampler) or nullptr = Pmax
     int step0;           // P0 - 1: positions 0 .. step0 - 1 are prefilled, the first decode step is step0
+    bool win = false;    // the prefill runs under the cross-attention window of the call's route (win_attn.hip)
 };
 struct PrefillScratch : BlockBufs {
     float* cvt;          // f32 mode: one layer's context V transposed to [B,H,64,Tp] (the f32 prefill attention reads V^T)
@@ -98,6 +101,24 @@ struct AppendAttnArgs {
 };
 int launch_append_attn(const AppendAttnArgs& a, hipStream_t s);
 
+// Windowed cross attention for many queries (win_attn.hip): query row i of a clip (f32 rows [B * Lq, ld], head h at column h * 64)
+// has position t0 + i and attends over the keys j < clamp(t0 + i + 2 + lookahead, 1, n_keys) that the clip's keep-mask keeps; K / V
+// [B, H, Tp, 64] in the cache type (the generation layout); out [B * Lq, o_ld] in the cache type.
+struct WinAttnArgs {
+    int dtype;            // the caches' and the output's type
+    const float* q;
+    int ld;
+    const void *kcache, *vcache;
+    int Tp;
+    void* out;
+    int o_ld;
+    int B, H, Lq, t0, n_keys, lookahead;
+    const uint8_t* kmask;    // [B, kmask_ld] or nullptr
+    int kmask_ld;
+    float scale;
+};
+int launch_win_attn(const WinAttnArgs& a, hipStream_t s);
+
 // A generation whose start and steps are driven across calls (generate.hip).  generate_impl opens one, runs all its steps and joins;
 // a streaming session (stream.hip) keeps one open between its pushes.
 struct GenRun;
@@ -105,8 +126,10 @@ struct GenSessionSpec {   // what a session asks of gen_open in place of the han
     int lookahead;        // the cross-attention window is on, with this look-ahead
     int n_keys;           // ... and this key bound (the cache length while the session is open)
 };
+// start [B, ld_prompt]: the first P codes of every clip; P > 1: positions 0 .. P - 2 are prefilled under the session's window
 GenRun* gen_run_new(const int32_t* start, const uint8_t* ctx_mask, int B, int T, float temperature, int top_k, const float* noise,
-                    uint64_t seed, int32_t* tokens, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st);
+                    uint64_t seed, int32_t* tokens, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st, int ld_prompt = 1,
+                    int P = 1);
 void gen_run_free(GenRun* r);
 int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, const GenSessionSpec* sess);
 int gen_run_steps(dimx_handle h, GenRun& run, int nsteps);          // the next nsteps steps of every group

@@ -10,6 +10,10 @@
 //      exist.  The window bounds every read below the frames pushed.
 // dimx_stream_end fixes T = the frames pushed and runs the remaining steps with the key bound T.
 //
+// dimx_stream_begin_prompted opens a session in the state another one was in after F frames: the encoder increments and the K / V
+// append of the F given frames, one windowed prefill (generate.hip gen_prefill, win_attn.hip) over the positions 0 .. P - 2 of the
+// P given codes, and the step counter at P - 1.  Its generate part is sized with the prefill scratch for Tmax - 1 positions.
+//
 // The generation is generate.hip's (gen_open / gen_run_steps): the same start, step and sampler launches, on the per-op route.
 // The session's workspace is a dimx_generate workspace for (B, Tmax) followed by the session's own buffers.
 #include "stages.hpp"
@@ -38,14 +42,17 @@ struct StreamSession {
     hipEvent_t evt[4] = {};       // dimx_stream_set_events: recorded by every push at its start and after each of its three parts
 };
 
-static size_t gen_part_bytes(const dimx_ctx* c, int B, int Tmax) { return align_up(workspace_bytes_prompt(c, B, Tmax, 1, 1), 256); }
+// prompted: with the prefill scratch of the longest prompt a session of Tmax frames can start from
+static size_t gen_part_bytes(const dimx_ctx* c, int B, int Tmax, bool prompted = false) {
+    return align_up(workspace_bytes_prompt(c, B, Tmax, 1, prompted ? Tmax : 1), 256);
+}
 
-// the session's own buffers behind the generate workspace; base == nullptr sizes them
-static size_t plan_stream(const dimx_ctx* c, void* base, size_t cap, int B, int Tmax, StreamSession& s) {
+// the session's own buffers behind the generate workspace; base == nullptr sizes them.  prompted: `start` holds [B, Tmax] codes
+static size_t plan_stream(const dimx_ctx* c, void* base, size_t cap, int B, int Tmax, StreamSession& s, bool prompted = false) {
     Arena ar(base, cap);
     const size_t es = es_of(c);
     const int n = Tmax - 1, V = c->decg.num_tokens;
-    s.start = (int32_t*)ar.take((size_t)B * 4);
+    s.start = (int32_t*)ar.take((size_t)B * (prompted ? Tmax : 1) * 4);
     s.mask = (uint8_t*)ar.take((size_t)B * Tmax);
     s.tokens = (int32_t*)ar.take((size_t)B * n * 4);
     s.logits = (float*)ar.take((size_t)B * n * V * 4);
@@ -203,36 +210,59 @@ size_t dimx_stream_workspace_bytes(dimx_handle h, int B, int Tmax) {
     return gen_part_bytes(h, B, Tmax) + plan_stream(h, nullptr, 0, B, Tmax, s);
 }
 
-int dimx_stream_begin(dimx_handle h, const int32_t* start, int B, int Tmax, int lookahead, float temperature, int top_k, const float* noise,
-                      uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+// dimx_stream_begin (P = 1, F = 0: `prompt` is start [B]) and dimx_stream_begin_prompted.  Every check comes before the first launch.
+static int stream_open(dimx_handle h, const char* what, bool prompted, const int32_t* prompt, int ld_prompt, int P, const float* v_speaker,
+                       const float* v_audio, int F, int B, int Tmax, int lookahead, float temperature, int top_k, const float* noise,
+                       uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
-    DIMX_REQUIRE(!h->stream_sess, DIMX_ERR_STATE, "stream_begin: a session is already open on this handle");
-    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "stream_begin: sessions are implemented for variant 0 (SLMFT) only; this handle is variant %d",
+    DIMX_REQUIRE(!h->stream_sess, DIMX_ERR_STATE, "%s: a session is already open on this handle", what);
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "%s: sessions are implemented for variant 0 (SLMFT) only; this handle is variant %d", what,
                  h->variant);
     DIMX_REQUIRE(B >= 1 && Tmax >= 2 && Tmax <= 2048 && Tmax <= h->d.max_seq_len, DIMX_ERR_ARG,
-                 "stream_begin: B=%d Tmax=%d out of range (2 <= Tmax <= %d)", B, Tmax, h->d.max_seq_len < 2048 ? h->d.max_seq_len : 2048);
-    DIMX_REQUIRE(start, DIMX_ERR_ARG, "stream_begin: null start tokens");
+                 "%s: B=%d Tmax=%d out of range (2 <= Tmax <= %d)", what, B, Tmax, h->d.max_seq_len < 2048 ? h->d.max_seq_len : 2048);
+    DIMX_REQUIRE(prompt, DIMX_ERR_ARG, "%s: null start tokens", what);
+    if (prompted) {
+        DIMX_REQUIRE(v_speaker && v_audio, DIMX_ERR_ARG, "%s: null frames", what);
+        // teacher-forced row P - 2 reads the keys below P + lookahead: they must be among the F frames given (dimx/stream.py prompt_fits)
+        DIMX_REQUIRE(P >= 1 && F <= Tmax && (long)P + (lookahead > 0 ? lookahead : 0) <= (long)F && ld_prompt >= P, DIMX_ERR_ARG,
+                     "%s: need 1 <= P, P + max(lookahead, 0) <= F <= Tmax and ld_prompt >= P (P=%d lookahead=%d F=%d Tmax=%d ld_prompt=%d)", what,
+                     P, lookahead, F, Tmax, ld_prompt);
+    }
     DIMX_REQUIRE(h->encg[0].causal && h->encg[1].causal && h->encg[0].dim_head == 64 && h->encg[1].dim_head == 64 && h->decg.dim_head == 64 &&
                      h->encg[0].dim == h->encg[1].dim && h->encg[0].heads == h->encg[1].heads && h->encg[0].depth <= 8 && h->encg[1].depth <= 8,
-                 DIMX_ERR_ARG, "stream_begin: needs causal encoders of one width with 64-wide heads");
-    const size_t gen_bytes = gen_part_bytes(h, B, Tmax);
+                 DIMX_ERR_ARG, "%s: needs causal encoders of one width with 64-wide heads", what);
+    const size_t gen_bytes = gen_part_bytes(h, B, Tmax, prompted);
     StreamSession* S = new StreamSession;
-    const size_t own = plan_stream(h, nullptr, 0, B, Tmax, *S);
+    const size_t own = plan_stream(h, nullptr, 0, B, Tmax, *S, prompted);
     if (ws_bytes < gen_bytes + own) {
         delete S;
-        DIMX_REQUIRE(false, DIMX_ERR_WORKSPACE, "stream_begin: workspace %zu < required %zu (dimx_stream_workspace_bytes)", ws_bytes, gen_bytes + own);
+        DIMX_REQUIRE(false, DIMX_ERR_WORKSPACE, "%s: workspace %zu < required %zu (%s)", what, ws_bytes, gen_bytes + own,
+                     prompted ? "dimx_stream_workspace_bytes_prompt" : "dimx_stream_workspace_bytes");
     }
     const int rc = [&]() -> int {
         DIMX_TRY(check_common(h, B, Tmax, ws, gen_bytes, COMP_ENC | COMP_DEC));
         hipStream_t st = (hipStream_t)stream;
-        plan_stream(h, (unsigned char*)ws + gen_bytes, ws_bytes - gen_bytes, B, Tmax, *S);
+        plan_stream(h, (unsigned char*)ws + gen_bytes, ws_bytes - gen_bytes, B, Tmax, *S, prompted);
         S->B = B; S->Tmax = Tmax; S->lookahead = lookahead; S->ws = ws; S->gen_bytes = gen_bytes;
         (void)scratch_arena(h, ws, gen_bytes, B, Tmax, &S->cp);
         DIMX_HIP(hipMemsetAsync(S->mask, 1, (size_t)B * Tmax, st));   // every pushed frame is a context row
-        DIMX_HIP(hipMemcpyAsync(S->start, start, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-        S->run = gen_run_new(S->start, S->mask, B, Tmax, temperature, top_k, noise, seed, S->tokens, S->logits, ws, gen_bytes, st);
+        const int ld = prompted ? Tmax : 1;
+        if (prompted)
+            DIMX_HIP(hipMemcpy2DAsync(S->start, (size_t)ld * 4, prompt, (size_t)ld_prompt * 4, (size_t)P * 4, B, hipMemcpyDeviceToDevice, st));
+        else
+            DIMX_HIP(hipMemcpyAsync(S->start, prompt, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+        // the given frames: the encoder increments and the K / V append of a push of F frames
+        const int dim_in = h->d.dim_in, dim_a = h->d.dim_a;
+        for (int o = 0; o < F; o += kAppendMaxRows) {
+            const int cc = F - o < kAppendMaxRows ? F - o : kAppendMaxRows;
+            DIMX_TRY(push_rows(h, *S, v_speaker + (size_t)o * dim_in, v_audio + (size_t)o * dim_a, F, cc, o, nullptr, st));
+        }
+        S->frames = F;
+        S->run = gen_run_new(S->start, S->mask, B, Tmax, temperature, top_k, noise, seed, S->tokens, S->logits, ws, gen_bytes, st, ld, P);
         const GenSessionSpec spec{lookahead, Tmax};
-        return gen_open(h, *S->run, false, false, &spec);
+        DIMX_TRY(gen_open(h, *S->run, false, false, &spec));   // P > 1: with the windowed prefill of the positions 0 .. P - 2
+        S->steps = P - 1;
+        return DIMX_OK;
     }();
     if (rc != DIMX_OK) {
         gen_run_free(S->run);
@@ -242,6 +272,25 @@ int dimx_stream_begin(dimx_handle h, const int32_t* start, int B, int Tmax, int 
     if (h->ctx_ws == ws) h->ctx_ready = false;   // the session's caches replace a context built in the same workspace
     h->stream_sess = S;
     return DIMX_OK;
+}
+
+int dimx_stream_begin(dimx_handle h, const int32_t* start, int B, int Tmax, int lookahead, float temperature, int top_k, const float* noise,
+                      uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    return stream_open(h, "stream_begin", false, start, 1, 1, nullptr, nullptr, 0, B, Tmax, lookahead, temperature, top_k, noise, seed, ws,
+                       ws_bytes, stream);
+}
+
+size_t dimx_stream_workspace_bytes_prompt(dimx_handle h, int B, int Tmax) {
+    if (!stream_shape_ok(h, B, Tmax)) return 0;   // 0 = shape not supported
+    StreamSession s;
+    return gen_part_bytes(h, B, Tmax, true) + plan_stream(h, nullptr, 0, B, Tmax, s, true);
+}
+
+int dimx_stream_begin_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, int P, const float* v_speaker, const float* v_audio, int F,
+                               int B, int Tmax, int lookahead, float temperature, int top_k, const float* noise, uint64_t seed, void* ws,
+                               size_t ws_bytes, void* stream) {
+    return stream_open(h, "stream_begin_prompted", true, prompt, ld_prompt, P, v_speaker, v_audio, F, B, Tmax, lookahead, temperature, top_k,
+                       noise, seed, ws, ws_bytes, stream);
 }
 
 int dimx_stream_push(dimx_handle h, const float* v_speaker, const float* v_audio, int c, int32_t* tokens_out, int ld_tok, float* logits_out,

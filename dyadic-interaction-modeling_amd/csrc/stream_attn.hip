@@ -19,61 +19,11 @@
 //     any chunk and at any place in it: same bits.  The instantiations for 1 / 4 / 16 queries share one per-query body.
 //   * no read past the frontier.  A load of key j >= n0 + c is redirected to row n0 + c - 1, and what a lane holds of a key
 //     j > n0 + i never reaches query i.
-#include "decode_attn_body.hpp"
+#include "online_softmax_body.hpp"   // QState, query_batch: the per-query body, shared with win_attn.hip
 #include "stages.hpp"
 
 namespace dimx {
 namespace {
-
-// per-query running state of the online softmax
-template <int EPC> struct QState {
-    float m, l;
-    float acc[EPC];
-};
-
-// Query `qrow` (f32 row in LDS, this lane's chunk at qrow + ch * EPC) against one key batch held in registers.  lim = the last
-// key the query may see; keys of the batch past it are left out of everything.  The caller guarantees j0 <= lim, so the batch
-// has at least one visible key and the new maximum is finite.
-template <typename T, int EPC, int LPK, int KPI, int U>
-__device__ __forceinline__ void query_batch(QState<EPC>& st, const float* qrow, const uint4 (&kb)[U], const uint4 (&vb)[U], int j0, int sub,
-                                            int lim, float scale2) {
-    float qv[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) qv[e] = qrow[e];
-    float sv[U];
-    float bm = kNegD;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        float kv[EPC];
-        cvt_chunk<T, EPC>(kb[u], kv);
-        float d = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) d = fmaf(qv[e], kv[e], d);
-        d = LPK == 8 ? group8_sum(d) : row16_sum(d);
-        const int j = j0 + u * KPI + sub;
-        sv[u] = j <= lim ? d * scale2 : kNegD;
-        bm = fmaxf(bm, sv[u]);
-    }
-    bm = wave_max(bm);
-    const float mn = fmaxf(st.m, bm);
-    const float alpha = exp2f(st.m - mn);   // first batch: st.m = kNegD -> 0, and l / acc are 0 anyway
-    st.m = mn;
-    st.l *= alpha;
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) st.acc[e] *= alpha;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int j = j0 + u * KPI + sub;
-        if (j <= lim) {
-            float vv[EPC];
-            cvt_chunk<T, EPC>(vb[u], vv);
-            const float p = exp2f(sv[u] - mn);
-            st.l += p;
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) st.acc[e] = fmaf(p, vv[e], st.acc[e]);
-        }
-    }
-}
 
 // QM: the most queries per (clip, head) this instantiation holds state for (c <= QM)
 template <typename T, int QM> __global__ __launch_bounds__(256) void append_attn_kernel(const AppendAttnArgs a) {

@@ -222,7 +222,10 @@ class Engine:
         """tokens generated per sequence: T-1 (SLMFT) / T (legacy, code/seq2seq.py:300)."""
         return T if self.variant == "legacy" else T - 1
 
-    def decode_tf(self, z_l, mask_u8, kv_mask_u8=None):
+    def decode_tf(self, z_l, mask_u8, kv_mask_u8=None, lookahead=None):
+        """Teacher-forced decoder pass -> (logits [B,T-1,V], row_loss, argmax).  With an integer ``lookahead`` L the pass runs under
+        online visibility (dimx_decode_tf_win; the definition is dimx.online): row t sees the context rows below
+        clamp(t + 2 + L, 1, T).  That form reads a context built with ``for_generate=True`` and takes no random key mask."""
         B, T = z_l.shape
         z_l = z_l.to(torch.int32).contiguous()
         self._chk(z_l, mask_u8, kv_mask_u8)
@@ -231,6 +234,12 @@ class Engine:
         row_loss = torch.empty(B, n, dtype=torch.float32, device=self.device)
         amax = torch.empty(B, n, dtype=torch.int32, device=self.device)
         ws, wsb = self.workspace(B, T)
+        if lookahead is not None:
+            if kv_mask_u8 is not None:
+                raise L.DimxError("decode_tf(lookahead=): the windowed pass takes no random key mask")
+            L.check(self.lib.dimx_decode_tf_win(self.h, L.ptr(z_l), L.ptr(mask_u8), B, T, int(lookahead), L.ptr(logits), L.ptr(row_loss),
+                                                L.ptr(amax), ws, wsb, self._s()), "dimx_decode_tf_win")
+            return logits, row_loss, amax
         L.check(self.lib.dimx_decode_tf(self.h, L.ptr(z_l), L.ptr(mask_u8), L.ptr(kv_mask_u8), B, T, L.ptr(logits),
                                         L.ptr(row_loss), L.ptr(amax), ws, wsb, self._s()), "dimx_decode_tf")
         return logits, row_loss, amax
@@ -277,7 +286,10 @@ class Engine:
         ``return_logits`` the columns < P0-1 are zero.
 
         ``lookahead``: online generation for this call (``set_cross_lookahead``; the previous setting is restored afterwards).
-        None leaves the engine's setting as it is.  With the window on, a prompt is never prefilled (as ``no_prefill``)."""
+        None leaves the engine's setting as it is.  With the window on, a prompt goes through forced decode steps (as
+        ``no_prefill``) unless ``prefill`` is ``"window"`` (P0 by the default rule above) or ``("window", P0)``: then the first P0
+        codes are prefilled by one teacher-forced pass under the window (flags bit 1 of dimx_generate_prompted).  With
+        the window off that spelling is the plain prefill."""
         if lookahead is not None:
             prev = self.cross_lookahead()
             self.set_cross_lookahead(lookahead)
@@ -316,11 +328,15 @@ class Engine:
                                        wsb, self._s()), "dimx_generate")
         return self._generated(tokens, lg, mask_u8, T, n_samples, None, return_logits, return_scores)
 
-    def stream(self, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0):
+    def stream(self, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0, prompt=None, v_speaker=None,
+               v_audio=None):
         """Open a streaming session (dimx_stream_begin, include/dimx.h): B clips in lockstep, at most ``Tmax`` frames,
         ``start`` [B] the listener's first codes, the sampler's arguments as ``generate`` takes them (``noise`` [Tmax-1, B, 512]).
-        Returns a StreamSession with a workspace of its own; one session per engine at a time."""
-        return StreamSession(self, B, Tmax, start, lookahead, temperature, top_k, noise, seed)
+        Returns a StreamSession with a workspace of its own; one session per engine at a time.
+
+        ``prompt`` [B, P] with ``v_speaker`` [B, F, 56] and ``v_audio`` [B, F, 768] (``start`` is then ignored and may be None): the
+        session starts from its first P codes and F frames (dimx_stream_begin_prompted; ``dimx.stream.prompt_fits``)."""
+        return StreamSession(self, B, Tmax, start, lookahead, temperature, top_k, noise, seed, prompt, v_speaker, v_audio)
 
     def _generated(self, tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores):
         """generate()'s return value: tokens[, logits][, SeqScores of the sampled columns (``plen``: effective prompt lengths)]"""
@@ -337,6 +353,12 @@ class Engine:
         R = B * n_samples
         prompt = prompt.to(torch.int32).contiguous()
         prompt_len = prompt_len.to(torch.int32).contiguous() if prompt_len is not None else None
+        window = False
+        if isinstance(prefill, str) or isinstance(prefill, tuple):
+            kind, prefill = (prefill, None) if isinstance(prefill, str) else prefill
+            if kind != "window":
+                raise ValueError("prefill=%r: an integer P0, 'window' or ('window', P0)" % (kind,))
+            window = True
         P0 = int(prefill) if prefill is not None else (Pmax if prompt_len is None else 1)
         if noise is not None:
             noise = noise.to(torch.float32).contiguous()
@@ -350,11 +372,11 @@ class Engine:
         ws, wsb = self.workspace(B, T, n_samples)
         L.check(self.lib.dimx_generate_prompted(self.h, L.ptr(prompt), int(prompt.stride(0)), L.ptr(prompt_len), int(Pmax), P0,
                                                 L.ptr(mask_u8), B, T, int(n_samples), float(temperature), int(top_k), L.ptr(noise),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(tokens), L.ptr(lg), 1 if no_prefill else 0,
-                                                ws, wsb, self._s()), "dimx_generate_prompted")
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(tokens), L.ptr(lg),
+                                                (1 if no_prefill else 0) | (2 if window else 0), ws, wsb, self._s()), "dimx_generate_prompted")
         plen = None
         if return_scores:    # the library's clamp (include/dimx.h): prompt_len into [P0, Pmax] (no prefill: P0 = 1), no prompt_len = Pmax
-            no_prefill = no_prefill or self.cross_lookahead() is not None
+            no_prefill = no_prefill or (self.cross_lookahead() is not None and not window)
             plen = prompt_len.clamp(1 if no_prefill else P0, Pmax) if prompt_len is not None \
                 else torch.full((B,), Pmax, dtype=torch.int32, device=self.device)
         return self._generated(tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores)
@@ -439,7 +461,8 @@ class StreamSession:
     A context manager; ``close()`` aborts a session that is still open.  ``tokens`` are all tokens so far [B, steps].  After
     ``end`` or ``close`` the object may ``begin`` another clip in the same workspace."""
 
-    def __init__(self, eng, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0):
+    def __init__(self, eng, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0, prompt=None, v_speaker=None,
+                 v_audio=None):
         self.eng, self.B, self.Tmax, self.lookahead = eng, int(B), int(Tmax), int(lookahead)
         self._open = False
         lib, dev = eng.lib, eng.device
@@ -450,21 +473,23 @@ class StreamSession:
         self._V = eng.dims.num_tokens
         self._tok = torch.zeros(self.B, self.Tmax - 1, dtype=torch.int32, device=dev)
         self._lg = None
-        self.begin(start, temperature, top_k, noise, seed)
+        self.begin(start, temperature, top_k, noise, seed, prompt, v_speaker, v_audio)
 
     def _ws_ptr(self):
         base = self._ws.data_ptr()
         aligned = (base + 255) // 256 * 256
         return ctypes.c_void_p(aligned), self._ws.numel() - (aligned - base)
 
-    def begin(self, start, temperature=1.0, top_k=52, noise=None, seed=0):
+    def begin(self, start=None, temperature=1.0, top_k=52, noise=None, seed=0, prompt=None, v_speaker=None, v_audio=None):
         """Start (another) clip: the arguments of Engine.stream; B, Tmax and the look-ahead are the session's."""
         if self._open:
             raise L.DimxError("StreamSession.begin: the session is open (end() or close() first)")
-        start = start.to(torch.int32).contiguous()
         if noise is not None:
             noise = noise.to(torch.float32).contiguous()
             assert tuple(noise.shape) == (self.Tmax - 1, self.B, self._V)
+        if prompt is not None:
+            return self._begin_prompted(prompt, v_speaker, v_audio, temperature, top_k, noise, seed)
+        start = start.to(torch.int32).contiguous()
         self.eng._chk(start, noise)
         assert tuple(start.shape) == (self.B,)
         self._noise = noise    # the session reads it at every step
@@ -476,6 +501,38 @@ class StreamSession:
         self._open = True
         self.frames = 0
         self.steps = 0
+
+    def _begin_prompted(self, prompt, v_speaker, v_audio, temperature, top_k, noise, seed):
+        """The first P codes and F frames are given: encoder increments and K / V append of the frames, one windowed prefill of the
+        positions 0 .. P - 2, the step counter at P - 1.  Token columns below P - 1 repeat the prompt, their logits read zero; the
+        steps the F frames make due beyond P - 1 run with the next push (or ``end``)."""
+        from . import stream as _stream
+        prompt = prompt.to(torch.int32).contiguous()
+        v_speaker = v_speaker.to(torch.float32).contiguous()
+        v_audio = v_audio.to(torch.float32).contiguous()
+        self.eng._chk(prompt, v_speaker, v_audio, noise)
+        B, P = prompt.shape
+        F = v_speaker.shape[1]
+        assert B == self.B and v_speaker.shape[0] == B and tuple(v_audio.shape[:2]) == (B, F)
+        if not _stream.prompt_fits(P, self.lookahead, F, self.Tmax):
+            raise ValueError("a session cannot start from P=%d codes and F=%d frames: need 1 <= P and P + max(lookahead, 0) = %d <= F <= Tmax = %d"
+                             % (P, F, P + max(self.lookahead, 0), self.Tmax))
+        need = self.eng.lib.dimx_stream_workspace_bytes_prompt(self.eng.h, self.B, self.Tmax)
+        if self._ws.numel() < need + 256:     # the generate part holds the prefill scratch too
+            self._ws = None
+            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.eng.device)
+        self._noise = noise
+        ws, wsb = self._ws_ptr()
+        L.check(self.eng.lib.dimx_stream_begin_prompted(self.eng.h, L.ptr(prompt), P, P, L.ptr(v_speaker), L.ptr(v_audio), F, self.B, self.Tmax,
+                                                        self.lookahead, float(temperature), int(top_k), L.ptr(self._noise),
+                                                        int(seed) & 0xFFFFFFFFFFFFFFFF, ws, wsb, self.eng._s()), "dimx_stream_begin_prompted")
+        self._open = True
+        self.frames = F
+        self.steps = P - 1
+        self._last = (P - 1, P - 1)
+        self._tok[:, :P - 1] = prompt[:, 1:]
+        if self._lg is not None:
+            self._lg[:, :P - 1] = 0
 
     def _logits(self):
         if self._lg is None:
@@ -940,6 +997,27 @@ def op_append_attn(qkv, kcache, vcache, n0, scale):
     out = torch.empty(B, c, H * 64, dtype=kcache.dtype, device=qkv.device)
     L.check(lib.dimx_op_append_attn(L.BF16 if bf else L.F32, L.ptr(qkv), ld, L.ptr(kcache), L.ptr(vcache), L.ptr(out), B, H, Tmax,
                                     int(n0), c, float(scale), L.stream_ptr(qkv.device)), "dimx_op_append_attn")
+    return out
+
+
+def op_cross_attn_win(q, kcache, vcache, lookahead, scale, t0=0, n_keys=None, kmask=None, out=None):
+    """Windowed cross attention for many queries (dimx_op_cross_attn_win): q [B, Lq, H*64] f32, query row i of a clip at position
+    t0 + i; kcache / vcache [B, H, Tp, 64] (f32 or bf16), of which the first ``n_keys`` rows are keys (default Tp); kmask [B, >= n_keys]
+    uint8 keep-mask or None.  Row i attends over the kept keys j < clamp(t0 + i + 2 + lookahead, 1, n_keys) (dimx.online)
+    -> [B, Lq, H*64] in the cache type (``out``: a contiguous tensor of that shape and type to write into)."""
+    lib = L.load()
+    B, H, Tp, _ = kcache.shape
+    Bq, Lq, ld = q.shape
+    assert Bq == B and q.dtype == torch.float32 and q.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
+    assert kmask is None or (kmask.dtype == torch.uint8 and kmask.is_contiguous() and kmask.shape[0] == B)
+    bf = kcache.dtype == torch.bfloat16
+    if out is None:
+        out = torch.empty(B, Lq, H * 64, dtype=kcache.dtype, device=q.device)
+    assert tuple(out.shape) == (B, Lq, H * 64) and out.dtype == kcache.dtype and out.is_contiguous()
+    L.check(lib.dimx_op_cross_attn_win(L.BF16 if bf else L.F32, L.ptr(q), ld, L.ptr(kcache), L.ptr(vcache), Tp, L.ptr(out), H * 64, B, H, Lq,
+                                       int(t0), Tp if n_keys is None else int(n_keys), int(lookahead), L.ptr(kmask),
+                                       kmask.shape[1] if kmask is not None else 0, float(scale), L.stream_ptr(q.device)),
+            "dimx_op_cross_attn_win")
     return out
 
 

@@ -66,6 +66,9 @@ SIGNATURES = {
     "dimx_stream_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "dimx_stream_begin": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_uint64, c_void_p, c_size_t,
                                   c_void_p]),
+    "dimx_stream_workspace_bytes_prompt": (c_size_t, [c_void_p, c_int, c_int]),
+    "dimx_stream_begin_prompted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
+                                           c_void_p, c_uint64, c_void_p, c_size_t, c_void_p]),
     "dimx_stream_push": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
     "dimx_stream_end": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "dimx_stream_abort": (c_int, [c_void_p]),
@@ -81,6 +84,8 @@ SIGNATURES = {
                                  c_void_p]),
     "dimx_decode_tf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dimx_decode_tf_win": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
     "dimx_generate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_uint64,
                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dimx_workspace_bytes_prompt": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
@@ -164,6 +169,8 @@ SIGNATURES = {
                                     c_float, c_void_p, c_int, c_int, c_void_p]),
     "dimx_op_append_attn": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                     c_void_p]),
+    "dimx_op_cross_attn_win": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_int, c_void_p, c_int, c_float, c_void_p]),
     "dimx_op_decode_attn_self": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                          c_void_p, c_float, c_int, c_void_p]),
     "dimx_op_decode_attn_ex": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_int, c_void_p, c_void_p, c_void_p,

@@ -153,7 +153,7 @@ class SLMFT(_EngineOwner):
     @torch.no_grad()
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
                         seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False, beam_width=0, lookahead=None):
+                        filter_kwargs=None, return_scores=False, beam_width=0, lookahead=None, window_prefill=False):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -175,8 +175,9 @@ class SLMFT(_EngineOwner):
         own running scores and the number of scored columns.
 
         ``lookahead`` L (mode 'val', no beam search): online generation (dimx.online) -- the step that produces frame t+1 sees the
-        speaker frames below clamp(t + 2 + L, 1, T) only; a prompt then runs through forced decode steps instead of a prefill.
-        None: the whole clip is visible, as in the reference."""
+        speaker frames below clamp(t + 2 + L, 1, T) only; a prompt then runs through forced decode steps instead of a prefill,
+        unless ``window_prefill`` asks for the prefill under the window (``Engine.generate(prefill="window")``; same definition,
+        other kernels).  None: the whole clip is visible, as in the reference."""
         if beam_width and (mode != "val" or int(n_samples) != int(beam_width)):
             raise ValueError("beam_width applies to mode='val' with n_samples == beam_width")
         if lookahead is not None and (mode != "val" or beam_width):
@@ -215,7 +216,8 @@ class SLMFT(_EngineOwner):
             seed_v = 0 if noise is not None else self._user_seed(seed)
         if prompt_frames > 1:
             out = eng.generate(None, m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
-                               prompt=z_l[:, :prompt_frames], prompt_len=plen, prefill=p0,
+                               prompt=z_l[:, :prompt_frames], prompt_len=plen,
+                               prefill=("window", p0) if (window_prefill and lookahead is not None) else p0,
                                filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
                                lookahead=lookahead)
         else:
@@ -227,17 +229,21 @@ class SLMFT(_EngineOwner):
         return 0.0, out.long()
 
     @torch.no_grad()
-    def stream(self, B, Tmax, start, lookahead=0, greedy=False, noise=None, seed=None, temperature=1.0, top_k=52):
+    def stream(self, B, Tmax, start, lookahead=0, greedy=False, noise=None, seed=None, temperature=1.0, top_k=52, prompt=None,
+               v_speaker=None, v_audio=None):
         """A streaming session (dimx.engine.StreamSession; dimx.stream is the schedule): push the speaker's motion and audio
         frames in pieces, receive the listener tokens as they fall due.  ``start`` [B]: the listener's first codes, the caller's --
         a live system has no ground-truth first code.  The sampler arguments are ``forward_decoder``'s.  Fed a whole clip, the
-        session emits the tokens of ``forward(mode='val', lookahead=lookahead)`` with ``start`` = that clip's first code."""
+        session emits the tokens of ``forward(mode='val', lookahead=lookahead)`` with ``start`` = that clip's first code.
+        ``prompt`` [B, P] codes with ``v_speaker`` / ``v_audio`` [B, F, .]: the session starts from its first P codes and F frames
+        (``Engine.stream``; ``start`` is ignored) -- how a conversation that outlasts a session carries on in the next one.  Nothing
+        was trained on restarted clips: what such a session emits is a definition, not a claim about quality."""
         eng = self.engine(start.device)
         if greedy:
             temperature, seed_v = 0.0, 0
         else:
             seed_v = 0 if noise is not None else self._user_seed(seed)
-        return eng.stream(B, Tmax, start, lookahead, temperature, top_k, noise, seed_v)
+        return eng.stream(B, Tmax, start, lookahead, temperature, top_k, noise, seed_v, prompt, v_speaker, v_audio)
 
     def draw_kv_mask(self, B, T, device, generator=None):
         """AutoregressiveWrapper(mask_prob=0.15) key mask (reference ctor :419): keep-mask [B,T-1]."""
@@ -310,7 +316,7 @@ class SLMFT(_EngineOwner):
     def forward(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                 return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None):
+                filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
@@ -332,7 +338,8 @@ class SLMFT(_EngineOwner):
 
         ``lookahead`` L (mode 'val', no beam search): online generation (dimx.online; ``forward_decoder``) -- the listener token of
         frame t+1 is drawn from the speaker frames below clamp(t + 2 + L, 1, T).  The tokens are causal in the speaker; ``pred`` is
-        still the VQ decoder's rendering of the whole token sequence."""
+        still the VQ decoder's rendering of the whole token sequence.  ``window_prefill`` (with ``prompt_frames`` and ``lookahead``): the
+        prompt is prefilled in one pass under the window instead of running through forced decode steps (``forward_decoder``)."""
         if lookahead is not None and (mode != "val" or beam_width is not None):
             raise ValueError("lookahead applies to mode='val' without beam search")
         if beam_width is not None:
@@ -352,13 +359,14 @@ class SLMFT(_EngineOwner):
                                         batch_row_offset=batch_row_offset, return_tokens=return_tokens,
                                         n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths,
                                         filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
-                                        beam_width=beam_width, num_return=num_return, lookahead=lookahead)
+                                        beam_width=beam_width, num_return=num_return, lookahead=lookahead,
+                                        window_prefill=window_prefill)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                         return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None):
+                        filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -378,7 +386,8 @@ class SLMFT(_EngineOwner):
                                                          kv_mask=kv_mask, greedy=greedy, seed=seed, temperature=temperature,
                                                          n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
                                                          filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs,
-                                                         return_scores=return_scores, beam_width=W, lookahead=lookahead)
+                                                         return_scores=return_scores, beam_width=W, lookahead=lookahead,
+                                                         window_prefill=window_prefill)
         finally:
             eng.set_shard(0, 0)
         if W and int(num_return) == 1:    # the best hypothesis is row 0 of its clip
@@ -407,7 +416,27 @@ class SLMFT(_EngineOwner):
 
 
     @torch.no_grad()
-    def score(self, v_speaker, v_listener, v_audio, mask, z_l=None, lookahead=None):
+    def forward_online_tf(self, v_speaker, v_listener, v_audio, mask, lookahead, z_l=None):
+        """The teacher-forced forward under online visibility, without a graph: ``forward(mode='train')``'s return values
+        (total_loss, dict, pred [B,T-1,56]) with the decoder's cross attention of row t bounded to the context rows below
+        clamp(t + 2 + L, 1, T) -- one ``decode_tf(lookahead=L)`` pass (dimx_decode_tf_win), no random key mask.  The validation
+        counterpart of an online fine-tuning (``x_engine_pt.evaluate_finetune_epoch(lookahead=L)``)."""
+        with self.engine_pinned():
+            mask = mask.bool()
+            eng = self.engine(v_speaker.device)
+            if z_l is None:
+                _, z_l = self.forward_vq(v_speaker, v_listener, mask, with_speaker=False)
+            m8 = self._mask8(mask)
+            self._build_context(eng, None, v_speaker, v_audio, m8, True)
+            logits, row_loss, _ = eng.decode_tf(z_l, m8, None, lookahead=int(lookahead))
+            l_ce_l = row_loss.sum() / (z_l[:, 1:] != -100).sum().clamp(min=1)
+            pred = self.forward_vq_decoder(logits, mode="train")
+            l_cont_l = self.forward_continuous_loss(pred, v_listener, mask)
+            d = {"l_ce_s": 0, "l_ce_l": l_ce_l, "l_cont_s": 0, "l_cont_l": l_cont_l, "nce": 0, "c_acc": 0}
+            return l_ce_l + l_cont_l, d, pred
+
+    @torch.no_grad()
+    def score(self, v_speaker, v_listener, v_audio, mask, z_l=None, lookahead=None, one_pass=False):
         """Teacher-forced log-likelihood of the clip's own listener codes (``forward_vq`` of ``v_listener``) or of given codes
         ``z_l`` [B,T] under the model: one ``decode_tf`` pass with NO random key mask, then dimx_op_seq_logprob on its logits with the
         tokens ``z_l[:, 1:]`` over the columns inside each clip's length -> dimx.scoring.SeqScores [B] (score f64, count int32).
@@ -415,7 +444,9 @@ class SLMFT(_EngineOwner):
 
         ``lookahead`` L: the same log-likelihood under online visibility (dimx.online) -- position t+1 is predicted from the
         speaker frames below clamp(t + 2 + L, 1, T).  The logits then come from a generation whose every token is forced to ``z_l``
-        (a prompt of T-1 tokens through decode steps, no prefill), scored over the same columns."""
+        (a prompt of T-1 tokens through decode steps, no prefill), scored over the same columns.  ``one_pass=True`` takes them from
+        one teacher-forced pass under the window instead (``decode_tf(lookahead=L)``, dimx_decode_tf_win): the same definition through
+        other kernels, so the same score within the decode steps' tolerance, not the same bits."""
         from .engine import op_seq_logprob
         from .scoring import scored_columns
         with self.engine_pinned():
@@ -427,8 +458,11 @@ class SLMFT(_EngineOwner):
             T = mask.shape[1]
             if lookahead is not None:
                 self._build_context(eng, None, v_speaker, v_audio, m8, True)
-                _, logits = eng.generate(None, m8, T, 0.0, 52, None, 0, return_logits=True, prompt=z_l[:, :T - 1], prefill=1,
-                                         no_prefill=True, lookahead=lookahead)
+                if one_pass:
+                    logits, _, _ = eng.decode_tf(z_l, m8, None, lookahead=lookahead)
+                else:
+                    _, logits = eng.generate(None, m8, T, 0.0, 52, None, 0, return_logits=True, prompt=z_l[:, :T - 1], prefill=1,
+                                             no_prefill=True, lookahead=lookahead)
             else:
                 self._build_context(eng, None, v_speaker, v_audio, m8, False)
                 logits, _, _ = eng.decode_tf(z_l, m8, None)

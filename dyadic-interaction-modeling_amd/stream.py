@@ -8,19 +8,35 @@ before frame t+1 is there.  With L < 0 the step runs at the same moment as with 
 ``online.visible`` gives it.  ``end`` fixes T = the frames pushed, and every remaining step up to T - 2 runs.
 
 A session fed a clip in pieces, in any chunking, emits the tokens of ``Engine.generate(lookahead=L)`` on the whole clip.
+
+A session may also start from a prompt (dimx_stream_begin_prompted): its first F frames and first P listener codes are given, the
+positions 0 .. P - 2 are prefilled in one teacher-forced pass under the window, and the first decode step is P - 1
+(``done0`` below).  Teacher-forced row P - 2 reads the keys below P + L, which must be among the F frames: ``prompt_fits``.  That
+is the state a session with look-ahead L >= 0 is in after F frames (F - L codes known), so carrying the last K frames and their
+K - max(L, 0) codes into a new session is always a valid start.  Such a session emits the tokens of
+``Engine.generate(prompt=codes[:, :P], lookahead=L)`` on the clip of the frames given plus the frames pushed.
 """
 import numpy as np
 
 
-def steps_due(n_frames, lookahead, ended=False, T=None):
-    """Decode steps that must have run once ``n_frames`` speaker frames are pushed: the steps 0 .. steps_due - 1.
+def steps_due(n_frames, lookahead, ended=False, T=None, done0=0):
+    """Decode steps that must have run once ``n_frames`` speaker frames are there: the steps 0 .. steps_due - 1.
     Open session: clamp(n_frames - 1 - max(L, 0), 0, n_frames - 1).  After ``end`` (``T`` = the frames pushed, default
-    ``n_frames``): T - 1."""
+    ``n_frames``): T - 1.  ``done0`` = P - 1 for a session begun from a prompt of P codes: the positions below it were
+    prefilled, never fewer steps count as done."""
     n = int(n_frames)
     if ended:
-        return max(int(n if T is None else T) - 1, 0)
+        return max(int(done0), int(n if T is None else T) - 1, 0)
     hi = max(n - 1, 0)
-    return int(np.clip(n - 1 - max(int(lookahead), 0), 0, hi))
+    return max(int(done0), int(np.clip(n - 1 - max(int(lookahead), 0), 0, hi)))
+
+
+def prompt_fits(P, lookahead, F, Tmax=None):
+    """May a session start from ``P`` codes and ``F`` frames?  1 <= P and P + max(L, 0) <= F (<= ``Tmax``): every key the
+    prefilled rows 0 .. P - 2 read under ``dimx.online.visible`` is one of the frames given, and the prompt's last code is of a
+    frame that exists."""
+    P, F = int(P), int(F)
+    return P >= 1 and P + max(int(lookahead), 0) <= F and (Tmax is None or F <= int(Tmax))
 
 
 def chunks(T, pattern):
@@ -39,13 +55,14 @@ def chunks(T, pattern):
     return out
 
 
-def schedule(chunking, lookahead):
-    """[(frames after the push, first step, one past the last step)] for every push of ``chunking``, then the same for ``end``."""
-    out, n, done = [], 0, 0
+def schedule(chunking, lookahead, F=0, P=1):
+    """[(frames after the push, first step, one past the last step)] for every push of ``chunking``, then the same for ``end``.
+    ``F``, ``P``: the session was begun from F frames and P codes (``prompt_fits``)."""
+    out, n, done = [], int(F), int(P) - 1
     for c in chunking:
         n += int(c)
-        due = steps_due(n, lookahead)
+        due = steps_due(n, lookahead, done0=P - 1)
         out.append((n, done, due))
         done = due
-    out.append((n, done, steps_due(n, lookahead, ended=True)))
+    out.append((n, done, steps_due(n, lookahead, ended=True, done0=P - 1)))
     return out

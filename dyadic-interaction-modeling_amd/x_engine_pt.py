@@ -80,14 +80,25 @@ def evaluate_epoch(model, loader, device, log=print):
     return float(np.mean(losses)) if losses else float("nan")
 
 
-def evaluate_finetune_epoch(model, loader, device):
-    """reference code/x_engine_pt.py:201-230 (teacher-forced forward, mode='train')."""
+def evaluate_finetune_epoch(model, loader, device, lookahead=None):
+    """reference code/x_engine_pt.py:201-230 (teacher-forced forward, mode='train').
+
+    ``lookahead`` L (SLMFT): the validation epoch of an online fine-tuning (``train_epoch(lookahead=L)``) -- the same
+    teacher-forced pass under the visibility the model was trained with (``SLMFT.forward_online_tf``: one windowed pass per batch,
+    no random key mask).  The return value then gains a fifth entry, the epoch's validation loss: the mean over the batches of the
+    batch's cross entropy (row losses summed over the valid targets / their number, as ``forward(mode='train')`` forms ``l_ce_l``).
+    None (default) is the reference's offline epoch and its four lists."""
     y_trues_all, y_preds_all, x_all, data_ids_all = [], [], [], []
+    losses = []
     model.eval()
     with torch.no_grad():
         for batch in loader:
             src_s_v, src_s_a, tgt, mask, src_len, data_ids = _prepare(batch, device)
-            _, _, y_preds = model(src_s_v, tgt, src_s_a, mask, mode="train")
+            if lookahead is None:
+                _, _, y_preds = model(src_s_v, tgt, src_s_a, mask, mode="train")
+            else:
+                _, d_val, y_preds = getattr(model, "module", model).forward_online_tf(src_s_v, tgt, src_s_a, mask, int(lookahead))
+                losses.append(d_val["l_ce_l"])
             y_true = tgt[:, 1:, :]
             yp, yt, xs = y_preds.cpu().numpy(), y_true.cpu().numpy(), src_s_v.cpu().numpy()
             for j in range(len(yp)):
@@ -96,6 +107,8 @@ def evaluate_finetune_epoch(model, loader, device):
                 y_trues_all.append(yt[j][:n])
                 x_all.append(xs[j][:n])
                 data_ids_all.append(data_ids[j])
+    if lookahead is not None:
+        return y_trues_all, y_preds_all, x_all, data_ids_all, float(torch.stack(losses).mean()) if losses else float("nan")
     return y_trues_all, y_preds_all, x_all, data_ids_all
 
 
@@ -197,7 +210,7 @@ def _select(pending, skip_degenerate, world, device):
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
-                        select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, **forward_kw):
+                        select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, window_prefill=False, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -255,13 +268,17 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
 
     ``lookahead`` L: every generation is an online one (dimx.online, ``SLMFT.forward(lookahead=L)``): the listener token of frame
     t+1 is drawn from the speaker frames below clamp(t + 2 + L, 1, T).  Selection, metrics and the returned lists are unchanged.
-    None (default) is the reference's offline protocol.  Not with ``decode="beam"`` (ValueError)."""
+    None (default) is the reference's offline protocol.  Not with ``decode="beam"`` (ValueError).  ``window_prefill`` (with
+    ``prompt_frames`` and ``lookahead``): the prompts are prefilled in one pass under the window instead of running through forced
+    decode steps (``SLMFT.forward(window_prefill=True)``)."""
     if decode not in ("sample", "beam"):
         raise ValueError("decode=%r: one of 'sample', 'beam'" % (decode,))
     if lookahead is not None:
         if decode == "beam":
             raise ValueError("evaluate_test_epoch(lookahead=...) applies to decode='sample': beam search has no online form")
         forward_kw = dict(forward_kw, lookahead=int(lookahead))
+        if window_prefill:
+            forward_kw["window_prefill"] = True
     if decode == "beam":
         beam_size = int(beam_width if beam_width is not None else beam_size)
         if beam_size not in BATCHED_SAMPLE_COUNTS:

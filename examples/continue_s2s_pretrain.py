@@ -6,6 +6,7 @@ clips and weights.
 
     python examples/continue_s2s_pretrain.py --prompt-frames 30 [--clips 32] [--batch 8] [--beam 10] [--bf16] [--ckpt best_vico_causal.pt]
                                             [--select {fd,likelihood,consensus}] [--consensus-distance {fd,l2}]
+                                            [--lookahead L [--window-prefill]]
 
 --select likelihood keeps the continuation the model itself scores highest (the log-likelihood of its sampled tokens past the
 prompt) instead of the one nearest to the ground truth: beyond the prompt a deployed continuation has no ground truth to select with.
@@ -51,8 +52,13 @@ def main():
     ap.add_argument("--lookahead", type=int, default=None,
                     help="online generation: the token of frame t+1 is drawn from the speaker frames below t + 2 + L (0: up to the frame being "
                          "produced, < 0: a reaction delay, > 0: a look-ahead buffer; default: the whole clip is visible, as in the reference)")
+    ap.add_argument("--window-prefill", action="store_true",
+                    help="with --lookahead: prefill the prompt in one teacher-forced pass under the window instead of running it through "
+                         "forced decode steps (the same definition through other kernels)")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
+    if args.window_prefill and args.lookahead is None:
+        ap.error("--window-prefill applies to --lookahead: offline, a prompt is always prefilled")
     sampler = sampling.filter_from_args(args)
     if sampler:
         print("sampler filter: %s %s" % (sampler["filter_logits_fn"], sampler["filter_kwargs"] or "(defaults)"))
@@ -77,7 +83,8 @@ def main():
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, val_loader, device, beam_size=args.beam,
                                                         prompt_frames=args.prompt_frames, select=args.select,
                                                         consensus_distance=args.consensus_distance, decode=args.decode,
-                                                        beam_width=args.beam_width, lookahead=args.lookahead, **sampler)
+                                                        beam_width=args.beam_width, lookahead=args.lookahead,
+                                                        window_prefill=args.window_prefill, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     print_metrics(y_true, y_pred, x)

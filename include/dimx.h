@@ -204,6 +204,17 @@ int dimx_decode_tf(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, c
                    int B, int T, float* logits, float* row_loss, int32_t* argmax_tok, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* The teacher-forced decoder pass under online visibility (the definition is dimx/online.py): dimx_decode_tf's stack with
+ * every layer's cross attention bounded per query -- row t (it consumes position t and predicts position t+1) attends over the
+ * context rows j < clamp(t + 2 + lookahead, 1, T) with ctx_mask[b][j] != 0, what decode step t of an online generation reads.  One
+ * pass gives the logits a generation with every token forced gives step by step (other kernels: equal within the decode steps'
+ * tolerance, not bit for bit).  The cross attention is csrc/win_attn.hip over the generation-layout K / V, so the context must
+ * have been built with dimx_encode_ctx(for_generate = 1) in the same ws (DIMX_ERR_STATE otherwise).  No kv_mask: the random key
+ * mask is a training device.  lookahead is this call's argument (any int; >= T-2 is the whole context) and independent of
+ * dimx_set_cross_lookahead.  Variant 0 only; DIMX_ERR_STATE while a streaming session is open.  Outputs as dimx_decode_tf. */
+int dimx_decode_tf_win(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mask, int B, int T, int lookahead, float* logits,
+                       float* row_loss, int32_t* argmax_tok, void* ws, size_t ws_bytes, void* stream);
+
 /* Autoregressive generation of T-1 tokens from start[B] with KV cache.
  * temperature <= 0 or exp_noise == NULL && seed == 0 -> greedy argmax.
  * exp_noise: [T-1,B,512] f32 Exp(1) samples (token = argmax softmax(top_k(logits)/temp)/noise);
@@ -237,15 +248,21 @@ int dimx_generate(dimx_handle h, const int32_t* start, const uint8_t* ctx_mask, 
  *               column holds that step's raw logits.
  *   exp_noise / seed stay indexed by (step, global row): a prompted call draws at step t what dimx_generate draws at step t.
  *   flags       bit 0 = no prefill: the call behaves as if P0 = 1 and forces the whole prompt through decode steps (for the tests
- *               and measurements, like dimx_mesh_head's bit 0; not a tuning knob).  Other bits are reserved.
+ *               and measurements, like dimx_mesh_head's bit 0; not a tuning knob).
+ *               bit 1 = windowed prefill: read only while online generation is on (below) and bit 0 is clear.  Other bits are
+ *               reserved.
  * Pmax = P0 = 1 is dimx_generate, bit for bit.  The context must have been built with dimx_encode_ctx(for_generate = 1) in the
  * same ws; dimx_workspace_bytes_prompt(h, B, T, S, P0) sizes ws for both calls (for P0 = 1 it equals
  * dimx_workspace_bytes_samples, and it does not shrink as P0 grows; 0 = shape not supported).  The prefill's teacher-forced scratch
  * is sized for the WHOLE batch, B x (P0-1) rows, behind the generation scratch (no clip chunks); a smaller workspace returns
  * DIMX_ERR_WORKSPACE before anything is launched.  Chain faults are answered as in dimx_generate (below); the regeneration keeps
  * the prefilled cache prefix.
- * Online generation (dimx_set_cross_lookahead, on): there is no prefill -- the call behaves as with flags bit 0 whatever P0 is, so
- * that every prompt position's cross attention runs under its own key bound; the columns < P0-1 of logits_out then hold logits. */
+ * Online generation (dimx_set_cross_lookahead, on): without flags bit 1 there is no prefill -- the call behaves as with flags bit 0
+ * whatever P0 is, so that every prompt position's cross attention runs under its own key bound; the columns < P0-1 of logits_out
+ * then hold logits.  With flags bit 1 the positions 0 .. P0-2 are prefilled as above by a teacher-forced pass whose cross attention
+ * carries that bound per query (csrc/win_attn.hip): the same definition through other kernels, so tokens and logits
+ * agree with the forced-step form within the decode steps' tolerance, not bit for bit; logits_out and the workspace are those of
+ * the offline prefill (columns < P0-1 zero, dimx_workspace_bytes_prompt(h, B, T, S, P0)). */
 size_t dimx_workspace_bytes_prompt(dimx_handle h, int B, int T, int n_samples, int P0);
 int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, int P0,
                            const uint8_t* ctx_mask, int B, int T, int n_samples, float temperature, int top_k,
@@ -325,10 +342,11 @@ int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b);
  *     value captures a new graph, never replays another one's.
  *   - With the window on the decode step runs the one-query attention kernels (csrc/decode_attn.hip) for every cross attention:
  *     not the decoder-layer kernel and not the matrix-core multi-sample route, which have no windowed form.
- *   - dimx_generate_prompted forces the whole prompt through decode steps, as its flags bit 0 does (the prefill's attention has no
- *     per-query key bound); P0 still sizes nothing less: dimx_workspace_bytes_prompt(h, B, T, S, 1) suffices.
+ *   - dimx_generate_prompted forces the whole prompt through decode steps, as its flags bit 0 does (the offline prefill's attention
+ *     has no per-query key bound; dimx_workspace_bytes_prompt(h, B, T, S, 1) suffices), unless its flags bit 1 asks for the windowed
+ *     prefill.
  *   - dimx_generate_beam returns DIMX_ERR_ARG while the window is on.
- *   - dimx_decode_tf is unaffected: the teacher-forced pass always sees the whole context. */
+ *   - dimx_decode_tf is unaffected: the teacher-forced pass always sees the whole context (dimx_decode_tf_win is the bounded one). */
 int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead);
 /* The handle's current setting (either pointer may be NULL). */
 int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
@@ -356,6 +374,18 @@ int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
  *     T - 1 with the key bound T and closes the session.
  *   dimx_stream_abort: closes the session, if any, without running anything.
  *   dimx_stream_state: frames pushed, steps run, open (0 / 1); any pointer may be NULL; zeros without a session.
+ *   dimx_stream_begin_prompted: a session whose first F frames (v_speaker [B, F, 56], v_audio [B, F, 768]) and first P listener codes
+ *     (prompt [B, ld_prompt] int32, copied) are given -- the state a session with lookahead L >= 0 is in after F frames with its
+ *     F - L codes, so a conversation that outlasts Tmax carries the last K frames and their K - max(L, 0) codes into a new session.
+ *     It runs the encoder increments and the K / V append of a push of F frames, one windowed prefill (dimx_generate_prompted's flags
+ *     bit 1) over the positions 0 .. P - 2 and sets the step counter to P - 1; no token is produced by the call: steps the F frames
+ *     make due beyond P - 1 run with the next push or end, whose token columns start at P - 1 (the columns below repeat the prompt
+ *     for the caller to fill; their logits are not formed).  Needs 1 <= P, P + max(lookahead, 0) <= F <= Tmax and ld_prompt >= P --
+ *     teacher-forced row P - 2 reads the keys below P + lookahead, and they must exist -- DIMX_ERR_ARG otherwise, the other
+ *     refusals as dimx_stream_begin, nothing launched.  P = 1 is dimx_stream_begin followed by a push of F frames.  What the session
+ *     emits is dimx_generate_prompted(prompt, Pmax = P0 = P, flags bit 1) under the lookahead on the clip of the frames given plus
+ *     the frames pushed.  ws comes from dimx_stream_workspace_bytes_prompt (the session workspace with the prefill scratch for
+ *     Tmax - 1 positions in its generate part); one P for all clips.
  * While a session is open dimx_encode_ctx, dimx_set_context, dimx_generate, dimx_generate_prompted, dimx_generate_beam, dimx_decode_tf
  * and dimx_set_cross_lookahead return DIMX_ERR_STATE; the VQ stages and the dimx_op_* calls stay usable.  The steps run on the
  * one-kernel-per-op route without the captured step graphs: the chain kernels answer a placement fault by regenerating the whole
@@ -363,6 +393,10 @@ int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
 size_t dimx_stream_workspace_bytes(dimx_handle h, int B, int Tmax);
 int dimx_stream_begin(dimx_handle h, const int32_t* start, int B, int Tmax, int lookahead, float temperature, int top_k, const float* noise,
                       uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+size_t dimx_stream_workspace_bytes_prompt(dimx_handle h, int B, int Tmax);
+int dimx_stream_begin_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, int P, const float* v_speaker, const float* v_audio, int F,
+                               int B, int Tmax, int lookahead, float temperature, int top_k, const float* noise, uint64_t seed, void* ws,
+                               size_t ws_bytes, void* stream);
 int dimx_stream_push(dimx_handle h, const float* v_speaker, const float* v_audio, int c, int32_t* tokens_out, int ld_tok, float* logits_out,
                      float* x_s_out, int* n_new, void* stream);
 int dimx_stream_end(dimx_handle h, int32_t* tokens_out, int ld_tok, float* logits_out, int* n_new, void* stream);
@@ -714,6 +748,22 @@ int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, in
  * the ranges above. */
 int dimx_op_append_attn(int dtype, const float* qkv, int ld, void* kcache, void* vcache, void* out, int B, int H, int Tmax, int n0, int c,
                         float scale, void* stream);
+/* Windowed cross attention for many queries (csrc/win_attn.hip; what dimx_decode_tf_win, the windowed prefill of
+ * dimx_generate_prompted and dimx_stream_begin_prompted launch for every decoder layer).  q [B*Lq, ld] f32 (row b*Lq + i, head h at
+ * column h*64, ld >= H*64, ld % 4 == 0); kcache / vcache [B, H, Tp, 64] of dtype (DIMX_F32 / DIMX_BF16), the layout
+ * dimx_encode_ctx(for_generate = 1) writes, of which rows 0 .. n_keys - 1 are keys (1 <= n_keys <= min(Tp, 2048)); kmask [B, kmask_ld]
+ * uint8 keep-mask (kmask_ld >= n_keys) or NULL.  Query row i of a clip has position t = t0 + i (t0 >= 0) and attends over the keys
+ *     j < clamp(t + 2 + lookahead, 1, n_keys)   with kmask[b][j] != 0
+ * (dimx/online.py; any int is a valid lookahead, the bound is formed in 64 bits) with scale * q.k, softmax in f32; out [B*Lq, o_ld]
+ * in dtype (o_ld >= H*64, o_ld % 8 == 0).  Nothing is written to the caches.
+ *   - The output row of a query has the same bits whatever Lq is, however t0 + i splits into t0 and i, and wherever the row lies
+ *     in a launch.
+ *   - K / V rows at or past the bound of the launch's last query are never read; nor are q rows outside [0, B*Lq).
+ *   - A row whose visible keys are all masked is zero.
+ * One launch, no atomics, fixed orders.  DIMX_ERR_ARG (nothing launched) for a null or misaligned (16 bytes) operand or a shape outside
+ * the ranges above. */
+int dimx_op_cross_attn_win(int dtype, const float* q, int ld, const void* kcache, const void* vcache, int Tp, void* out, int o_ld, int B, int H,
+                           int Lq, int t0, int n_keys, int lookahead, const uint8_t* kmask, int kmask_ld, float scale, void* stream);
 /* Decode-step residual + pre-norm: x[M,C] += sum_s slabs[s] (fixed order), y = LayerNorm(x) * gamma (no bias). */
 /* The prefill's fused feed-forward sublayer alone (csrc/mlp_fused.hip; unit parity): x [M,C] f32 on the device is replaced by
  * x + W2 . gelu(W1 . LayerNorm(x) + b1) + b2 with bf16 operands and f32 accumulation.  w1 [F,C], b1 [F] (or NULL), w2 [C,F] are HOST

@@ -4,7 +4,7 @@
 One MI355X, B = 256, T = 300.  Per numeric mode and prompt length P (Pmax = P0 = P, no prompt_len), after a warm-up,
 median of 5 calls with the range:
   (a) dimx_generate_prompted with the prefill, (b) with flags bit 0 (the whole prompt through forced decode steps),
-  (c) the prefill stage alone (flags bit 1, a hook for this tool outside the documented flag set).
+  (c) the prefill stage alone (flags bit 2, a hook for this tool outside the documented flag set).
 For P = 1 also dimx_generate of this tree and -- with --parent-lib, a libdimx_hip.so built from the parent commit -- of the
 parent: two handles of each build, all four with the same workspace size, created and called in interleaved order (tree, parent,
 parent, tree), 10 timed calls per handle.  Two handles of the same code show what a handle (its allocations, its graphs) is
@@ -143,7 +143,7 @@ def main():
 
                 def pre():
                     L.check(e.lib.dimx_generate_prompted(e.h, L.ptr(prompt), P, None, P, P, L.ptr(m8), B, T, 1, 1.0, 52, None, 5,
-                                                         L.ptr(tokens), None, 2, ws, wsb, e._s()), "prefill only")
+                                                         L.ptr(tokens), None, 4, ws, wsb, e._s()), "prefill only")
                 row += "  (c) %s" % fmt(timed(pre))
                 row += "  (a) < (b): %s" % (statistics.median(a) < statistics.median(b))
             lines.append(row)
