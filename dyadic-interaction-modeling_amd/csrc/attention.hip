@@ -40,6 +40,10 @@ template <> struct MmaT<float> {
 };
 
 constexpr float kNeg = -3.0e38f;
+// A row without a visible key never raises its running maximum above kNeg: every slot of every tile weighs exp2(0) = 1.  The V^T
+// tile is zero at and past the block's key count kmax (those keys weigh 0 in every other row of the block, so nothing else
+// changes) and such a row is divided by kmax instead of its 64 slots per tile: the mean of V over its kmax keys -- the reference's
+// softmax over equal -FLT_MAX scores, and what attention_tr.hip and the decode-step kernels give.
 
 // bf16 perf mode: the bare v_exp_f32 (arguments are <= 0, results that underflow flush to 0, which is what a
 // softmax wants); f32 parity mode keeps exp2f
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnArgs a) {
             const int idx = tid + i * NT;
             const int d = idx / CPR, c = idx % CPR;
             const int jj = j0 + c * EPC;
-            vreg[i] = (d < a.D && a.Lk - jj > 0) ? *(const uint4*)(Vt + (size_t)d * a.v_sd + jj) : make_uint4(0, 0, 0, 0);
+            vreg[i] = (d < a.D && kmax - jj > 0) ? *(const uint4*)(Vt + (size_t)d * a.v_sd + jj) : make_uint4(0, 0, 0, 0);
         }
     };
     // bf16 only: in the f32 parity mode the 16 extra 16-byte registers cost a wave of occupancy (248 -> 314 VGPRs)
@@ -149,9 +153,9 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnArgs a) {
             {
                 const int d = row;
                 const int jj = j0 + c * EPC;
-                const int nvalid = a.Lk - jj;
+                const int nvalid = kmax - jj;
                 uint4 v = vreg[i];
-                if (d < a.D && nvalid > 0 && nvalid < EPC) {  // zero the keys beyond Lk: 0 * garbage must stay 0
+                if (d < a.D && nvalid > 0 && nvalid < EPC) {  // zero the keys beyond kmax (<= Lk): 0 * garbage must stay 0
                     if (ES == 2) {
                         uint16_t e[8];
                         *(uint4*)e = v;
@@ -296,7 +300,7 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(const AttnArgs a) {
 
     // ---- finish: combine the two lane halves' row sums, normalise, store O[q][d]
     const float l_tot = l_run + xor_lane_f32<32>(l_run);
-    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+    const float inv = l_tot > 0.f ? 1.0f / (m_run == kNeg ? (float)kmax : l_tot) : 0.f;
     if (qi < a.Lq) {
         T* orow = (T*)a.o + (size_t)b * a.o_sb + (size_t)qi * a.o_st + (size_t)h * a.o_sh;
 #pragma unroll

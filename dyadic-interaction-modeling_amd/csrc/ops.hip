@@ -179,14 +179,20 @@ int dimx_op_instnorm(int out_dtype, const float* x, void* y, const int32_t* lens
 }
 
 // operator entry points (tests / tools): the key-mask scratch of attention_tr.hip is a stream-ordered allocation around the call
-static int op_attention_with_scratch(AttnArgs& a, hipStream_t st) {
+// (prepack: the key words are packed here, ahead of the launch, and handed over as ready -- the decode loop's order)
+static int op_attention_with_scratch(AttnArgs& a, hipStream_t st, bool prepack = false) {
     void* kw = nullptr;
     if (a.kmask && a.v_rows && a.dtype == DIMX_BF16) {
         a.kwords_cap = (size_t)a.B * ((a.Lk + 63) / 64);
         DIMX_HIP(hipMallocAsync(&kw, a.kwords_cap * 8, st));
         a.kwords = (unsigned long long*)kw;
     }
-    const int rc = launch_attention(a, st);
+    int rc = DIMX_OK;
+    if (kw && prepack) {
+        rc = launch_pack_key_words(a.kmask, a.kmask_ld, a.lens, a.B, a.Lk, a.kwords, a.kwords_cap, st);
+        a.kwords_ready = 1;
+    }
+    if (rc == DIMX_OK) rc = launch_attention(a, st);
     if (kw) DIMX_HIP(hipFreeAsync(kw, st));
     return rc;
 }
@@ -230,6 +236,33 @@ int dimx_op_attention_rowv(const void* q, const void* k, const void* v, void* ou
     a.kmask = kmask;
     a.kmask_ld = Lk;
     return op_attention_with_scratch(a, (hipStream_t)stream);
+}
+
+// attention_tr.hip with every AttnArgs stride given (tests: the head-major cross-attention caches, an output wider than H * D, a key
+// mask with a row stride of its own, key words packed ahead of the launch)
+int dimx_op_attention_strided(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk, int D,
+                              const long* q_str, const long* k_str, const long* v_str, const long* o_str, float scale, int causal,
+                              const int32_t* lens, const uint8_t* kmask, int kmask_ld, int prepacked, void* stream) {
+    DIMX_REQUIRE(q_str && k_str && v_str && o_str, DIMX_ERR_ARG, "op_attention_strided: strides are (batch, row, head) triples");
+    DIMX_REQUIRE(!kmask || kmask_ld >= Lk, DIMX_ERR_ARG, "op_attention_strided: kmask_ld %d below Lk %d", kmask_ld, Lk);
+    for (int i = 0; i < 3; ++i)
+        DIMX_REQUIRE(q_str[i] > 0 && k_str[i] > 0 && v_str[i] > 0 && o_str[i] > 0, DIMX_ERR_ARG, "op_attention_strided: stride <= 0");
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = DIMX_BF16;
+    a.q = q; a.k = k; a.vt = v; a.o = out;
+    a.q_sb = q_str[0]; a.q_st = q_str[1]; a.q_sh = q_str[2];
+    a.k_sb = k_str[0]; a.k_st = k_str[1]; a.k_sh = k_str[2];
+    a.v_rows = 1;
+    a.v_sb = v_str[0]; a.v_st = v_str[1]; a.v_sh = v_str[2];
+    a.o_sb = o_str[0]; a.o_st = o_str[1]; a.o_sh = o_str[2];
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.D = D;
+    a.scale = scale;
+    a.causal = causal;
+    a.lens = lens;
+    a.kmask = kmask;
+    a.kmask_ld = kmask_ld;
+    return op_attention_with_scratch(a, (hipStream_t)stream, prepacked != 0);
 }
 
 int dimx_op_decode_attn(int dtype, const void* q, const void* kcache, const void* vcache, void* out, int B, int H,

@@ -763,9 +763,58 @@ def op_instnorm(x, lens=None, out_bf16=False):
     return y
 
 
-def op_attention(q, k, v, scale, causal=False, lens=None, kmask=None, bf16=False, row_v=False):
+ATTN_CANARY = -7.0   # what op_attention(layout=...) leaves where the kernel must not write
+
+
+def _op_attention_strided(q, k, v, scale, causal, lens, kmask, layout, tp, ld_o, prepacked, kmask_ld, return_buffer):
+    """The test entry with every stride given (bf16, row-major v).  Everything the kernel must not read is NaN, everything it must
+    not write ATTN_CANARY: packed -- q / k / v [B,L,H*D] followed by eight NaN rows; headmajor -- k / v as the cross-attention
+    caches [B,H,tp,D] with rows Lk..tp-1 NaN.  The output buffer is [B, Lq + 2, ld_o]; kmask rows are kmask_ld apart (ones past Lk)."""
+    lib = L.load()
+    B, Lq, H, D = q.shape
+    Lk = k.shape[1]
+    dev, bf, nan = q.device, torch.bfloat16, float("nan")
+    ld_o = H * D if ld_o is None else ld_o
+
+    def packed(t, n):
+        buf = torch.full((B * n + 8, H * D), nan, dtype=bf, device=dev)
+        buf[:B * n] = t.to(bf).reshape(B * n, H * D)
+        return buf, (n * H * D, H * D, D)
+
+    q_, q_str = packed(q, Lq)
+    if layout == "packed":
+        (k_, k_str), (v_, v_str) = packed(k, Lk), packed(v, Lk)
+    elif layout == "headmajor":
+        tp = Lk if tp is None else tp
+        assert tp >= Lk
+        k_, v_ = (torch.full((B, H, tp, D), nan, dtype=bf, device=dev) for _ in range(2))
+        k_[:, :, :Lk] = k.to(bf).permute(0, 2, 1, 3)
+        v_[:, :, :Lk] = v.to(bf).permute(0, 2, 1, 3)
+        k_str = v_str = (H * tp * D, D, tp * D)
+    else:
+        raise ValueError("op_attention: layout %r" % (layout,))
+    out = torch.full((B, Lq + 2, ld_o), ATTN_CANARY, dtype=bf, device=dev)
+    o_str = ((Lq + 2) * ld_o, ld_o, D)
+    km = None
+    if kmask is not None:
+        kmask_ld = Lk if kmask_ld is None else kmask_ld
+        km = torch.ones(B, kmask_ld, dtype=torch.uint8, device=dev)
+        km[:, :Lk] = kmask
+    arr = lambda s: (ctypes.c_long * 3)(*s)
+    L.check(lib.dimx_op_attention_strided(L.ptr(q_), L.ptr(k_), L.ptr(v_), L.ptr(out), B, H, Lq, Lk, D, arr(q_str), arr(k_str),
+                                          arr(v_str), arr(o_str), float(scale), 1 if causal else 0, L.ptr(lens), L.ptr(km),
+                                          kmask_ld if km is not None else 0, 1 if prepacked else 0, L.stream_ptr(dev)),
+            "dimx_op_attention_strided")
+    res = out[:, :Lq, :H * D].reshape(B, Lq, H, D)
+    return (res, out) if return_buffer else res
+
+
+def op_attention(q, k, v, scale, causal=False, lens=None, kmask=None, bf16=False, row_v=False, layout=None, tp=None, ld_o=None,
+                 prepacked=False, kmask_ld=None, return_buffer=False):
     """q [B,Lq,H,D], k/v [B,Lk,H,D] -> [B,Lq,H,D]; v is transposed to [B,H,D,Lk_pad] here, or (row_v, bf16) handed over
-    row-major like k."""
+    row-major like k.  layout "packed" / "headmajor" (tests): the strided entry of the row-major-v kernel."""
+    if layout is not None:
+        return _op_attention_strided(q, k, v, scale, causal, lens, kmask, layout, tp, ld_o, prepacked, kmask_ld, return_buffer)
     lib = L.load()
     B, Lq, H, D = q.shape
     Lk = k.shape[1]

@@ -165,6 +165,9 @@ SIGNATURES = {
                                   c_void_p]),
     "dimx_op_attention_rowv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "dimx_op_attention_strided": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                          POINTER(ctypes.c_long), POINTER(ctypes.c_long), POINTER(ctypes.c_long), POINTER(ctypes.c_long),
+                                          c_float, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dimx_op_decode_attn": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_float, c_void_p, c_int, c_int, c_void_p]),
     "dimx_op_append_attn": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,

@@ -697,6 +697,13 @@ int dimx_op_attention(int dtype, const void* q, const void* k, const void* vt, v
 int dimx_op_attention_rowv(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk, int D, int ldq,
                            int ldk, int ldv, int ldo, float scale, int causal, const int32_t* lens, const uint8_t* kmask,
                            void* stream);
+/* Test entry: the row-major-v attention with every stride given.  q_str / k_str / v_str / o_str are host arrays of three element
+ * strides (batch, row, head): element (b, i, h, d) of q at q + b q_str[0] + i q_str[1] + h q_str[2] + d, likewise k, v, out; all
+ * multiples of 8.  kmask [B, kmask_ld], kmask_ld >= Lk.  prepacked != 0 packs the key validity words in a launch of its own ahead
+ * of the attention (the decode loop's order) instead of inside the attention launch.  bf16, D in {48,64}. */
+int dimx_op_attention_strided(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk, int D,
+                              const long* q_str, const long* k_str, const long* v_str, const long* o_str, float scale, int causal,
+                              const int32_t* lens, const uint8_t* kmask, int kmask_ld, int prepacked, void* stream);
 /* One-query (autoregressive step) attention over a [B,H,Tmax,64] K/V cache, n_keys keys per (clip,head);
  * q/out are [B,H*64].  kmask optional [B,n_keys].  Cross-attention form (no cache append).
  * nsplit: waves per (clip, head) sharing the keys (1, 2, 4; 0 = automatic).  q_is_f32: q is a single f32 slab
