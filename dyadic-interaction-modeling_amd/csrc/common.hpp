@@ -549,6 +549,17 @@ struct SampleArgs {
     int hist_ld = 0;
 };
 int launch_sample(const SampleArgs& a, hipStream_t s);
+// Classifier-free guidance (sample_guided_kernel; the definition is dimx/guidance.py): what the guided sampler takes beside a
+// SampleArgs of R = clips rows.  The row sampled is c + (scale - 1) * (c - u), c / u = row r of a.logits / logits_u (same leading
+// dimension, slab count and slab stride); every per-row output is written for rows r and r + R.  The scale is read from word 11
+// behind a.dev_params when there is a parameter block.  a.logits_out takes the guided rows.
+struct GuidedArgs {
+    const float* logits_u = nullptr;
+    float scale = 1.f;
+    float* branch_out = nullptr;    // [2, R, a.logits_out_ld, 512]: c and u as summed (optional)
+    int32_t* tokens_u = nullptr;    // [R, a.tok_ld]: the token once more, for the unconditional rows (optional)
+};
+int launch_sample_guided(const SampleArgs& a, const GuidedArgs& g, hipStream_t s);
 // Beam search (beam.hip; the definition is dimx/beam.py).  One selection launch: rows clip * W + w of `logits` (split-K slabs, added
 // in slab order like the sampler) are the W beams of a clip; column c = *step_dev (or step_host).  The mode of a clip is
 // forced while c + 1 < clamp(prompt_len, dev_params[8] + 1, prompt_max) (the sampler's rule), frozen when c >= lens[clip] - len_off,
@@ -614,7 +625,7 @@ int launch_gather_start_rows(const float* table, int N, int rows, const int32_t*
 int launch_kv0_image(const float* table, int ld, int rows, int col0, int W, void* image, hipStream_t s);
 // generate(): the per-group step counters = step0, done counters = 0, and temperature + seed next to them (read by the sampler)
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
-                      hipStream_t s, int step0 = 0, float filter_a = 0.f, float filter_b = 0.f);
+                      hipStream_t s, int step0 = 0, float filter_a = 0.f, float filter_b = 0.f, float guidance = 1.f);
 int launch_embed_step(const float* table, int C, int rows, const int32_t* start, const int32_t* tokens, int tok_ld,
                       const int32_t* step_dev, float* x, int B, int start_div, hipStream_t s,
                       const float* pos_table = nullptr, float pos_scale = 0.f, int start_ld = 1, int start_step = 0);

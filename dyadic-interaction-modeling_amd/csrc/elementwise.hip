@@ -142,26 +142,36 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 //   top_a  keep i iff e_i >= ratio * Z^(1 - pow)
 // thres >= 1 and min_p <= 0 keep everything; the arg-max is always kept.  fa / fb come from the parameter block (words
 // 9 / 10 behind dev_params) when there is one: the captured step graph does not depend on them.
-template <int KIND>
-__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, int ld, int R, int top_k,
-                                                     float temperature, const float* __restrict__ noise,
-                                                     uint64_t seed, const int32_t* __restrict__ step_dev,
-                                                     uint64_t step_host, int32_t* __restrict__ tokens, int tok_ld,
-                                                     int tok_col_from_step, int nslab, long slab_stride,
-                                                     float* __restrict__ logits_out, int logits_out_ld, int row0,
-                                                     int rows_total,
-                                                     const float* __restrict__ emb_table, int emb_C,
-                                                     float* __restrict__ x_next, int32_t* __restrict__ step_rw,
-                                                     unsigned* __restrict__ done_ctr,
-                                                     const float* __restrict__ pos_table, float pos_scale,
-                                                     int pos_rows, const int32_t* __restrict__ dev_params,
-                                                     void* __restrict__ y_next, const float* __restrict__ y_gamma,
-                                                     int y_bf16, const float* __restrict__ qkv0_table,
-                                                     float* __restrict__ qkv0_out, int qkv0_N,
-                                                     const int32_t* __restrict__ prompt, int prompt_ld, int prompt_max,
-                                                     const int32_t* __restrict__ prompt_len, int prompt_div,
-                                                     int32_t* __restrict__ epoch_rw, float fa, float fb,
-                                                     uint8_t* __restrict__ keep_out, int32_t* __restrict__ hist, int hist_ld) {
+//
+// GUIDED (sample_guided_kernel, classifier-free guidance; the definition is dimx/guidance.py): the row sampled is
+// g = c + (s - 1) * (c - u) in f32, three roundings and that of s - 1, c = row `row` of `logits` and u = row `row` of `logits_u`,
+// each summed over its slabs in the order above.  Everything after that -- filter, temperature, noise, arg-max, forced token --
+// is the code of the plain sampler on g, with the noise row and the generator counter of row `row` of an R-row launch.  What the
+// plain sampler writes for its row is written twice, for row `row` and for row `row + R` (the unconditional half of a 2R-row
+// step); tokens_u [R, tok_ld] takes the second copy of the token (optional).  s is word 11 of the parameter block when there is one.
+// logits_out takes g; branch_out [2, R, logits_out_ld, 512] takes c and u (optional).
+template <int KIND, bool GUIDED>
+__device__ __forceinline__ void sample_body(const float* __restrict__ logits, int ld, int R, int top_k,
+                                            float temperature, const float* __restrict__ noise,
+                                            uint64_t seed, const int32_t* __restrict__ step_dev,
+                                            uint64_t step_host, int32_t* __restrict__ tokens, int tok_ld,
+                                            int tok_col_from_step, int nslab, long slab_stride,
+                                            float* __restrict__ logits_out, int logits_out_ld, int row0,
+                                            int rows_total,
+                                            const float* __restrict__ emb_table, int emb_C,
+                                            float* __restrict__ x_next, int32_t* __restrict__ step_rw,
+                                            unsigned* __restrict__ done_ctr,
+                                            const float* __restrict__ pos_table, float pos_scale,
+                                            int pos_rows, const int32_t* __restrict__ dev_params,
+                                            void* __restrict__ y_next, const float* __restrict__ y_gamma,
+                                            int y_bf16, const float* __restrict__ qkv0_table,
+                                            float* __restrict__ qkv0_out, int qkv0_N,
+                                            const int32_t* __restrict__ prompt, int prompt_ld, int prompt_max,
+                                            const int32_t* __restrict__ prompt_len, int prompt_div,
+                                            int32_t* __restrict__ epoch_rw, float fa, float fb,
+                                            uint8_t* __restrict__ keep_out, int32_t* __restrict__ hist, int hist_ld,
+                                            const float* __restrict__ logits_u, float scale,
+                                            float* __restrict__ branch_out, int32_t* __restrict__ tokens_u) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint64_t step = step_dev ? (uint64_t)*step_dev : step_host;
     if (dev_params) {  // generate(): temperature / seed live in device memory so that the captured step graph
@@ -197,13 +207,26 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
     for (int c = 0; c < 8; ++c) {
         v[c] = lr[lane + 64 * c];
         for (int sidx = 1; sidx < nslab; ++sidx) v[c] += lr[(size_t)sidx * slab_stride + lane + 64 * c];  // split-K slabs
+        if constexpr (GUIDED) {
+            const float* ur = logits_u + (size_t)row * ld;
+            float u = ur[lane + 64 * c];
+            for (int sidx = 1; sidx < nslab; ++sidx) u += ur[(size_t)sidx * slab_stride + lane + 64 * c];
+            if (branch_out) {   // both raw rows: [2, R, steps, 512]
+                const size_t at = ((size_t)row * logits_out_ld + (tok_col_from_step ? step : 0)) * 512 + lane + 64 * c;
+                branch_out[at] = v[c];
+                branch_out[(size_t)R * logits_out_ld * 512 + at] = u;
+            }
+            // s - 1 == 0 returns c itself (no c + 0 * inf, no -0 + 0); otherwise three separate roundings, never an fma
+            const float sm1 = __fsub_rn(dev_params ? __builtin_bit_cast(float, dev_params[11]) : scale, 1.0f);
+            if (sm1 != 0.f) v[c] = __fadd_rn(v[c], __fmul_rn(sm1, __fsub_rn(v[c], u)));
+        }
         if (v[c] > mx) {
             mx = v[c];
             mi = lane + 64 * c;
         }
     }
     if (logits_out) {  // per-step dump of the raw logits: [rows, steps, 512]
-        float* lo = logits_out + ((size_t)row * logits_out_ld + step) * 512;
+        float* lo = logits_out + ((size_t)row * logits_out_ld + (GUIDED && !tok_col_from_step ? 0 : step)) * 512;
 #pragma unroll
         for (int c = 0; c < 8; ++c) lo[lane + 64 * c] = v[c];
     }
@@ -361,9 +384,14 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
     }
     }  // !forced
     if (lane == 0) tokens[(size_t)row * tok_ld + (tok_col_from_step ? (int)step : 0)] = tok;
+    if constexpr (GUIDED)
+        if (tokens_u && lane == 0) tokens_u[(size_t)row * tok_ld + (tok_col_from_step ? (int)step : 0)] = tok;
     // the first layer's token history (its self attention in the table form, decode_attn_body.hpp): the next position's input
     if (hist && lane == 0 && (int)step + 1 < hist_ld)
         hist[(size_t)row * hist_ld + step + 1] = tok < 0 ? 0 : (tok >= kSampleVocab ? kSampleVocab - 1 : tok);
+    if constexpr (GUIDED)
+        if (hist && lane == 0 && (int)step + 1 < hist_ld)
+            hist[(size_t)(row + R) * hist_ld + step + 1] = tok < 0 ? 0 : (tok >= kSampleVocab ? kSampleVocab - 1 : tok);
     if (x_next) {  // next step's decoder input: token embedding row (fused embed_step)
         const float2* src = (const float2*)(emb_table + (size_t)tok * emb_C);
         float2* dst = (float2*)(x_next + (size_t)row * emb_C);
@@ -398,6 +426,14 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                     const int i = lane + 64 * k;
                     if (i < nq) qd[i] = w[k];
                 }
+                if constexpr (GUIDED) {
+                    float4* qd2 = (float4*)(qkv0_out + (size_t)(row + R) * qkv0_N);
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) {
+                        const int i = lane + 64 * k;
+                        if (i < nq) qd2[i] = w[k];
+                    }
+                }
             }
             if (with_pos) {
                 float2 q[16];
@@ -414,6 +450,14 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
             for (int k = 0; k < 16; ++k) {
                 const int i = lane + 64 * k;
                 if (i < nv) dst[i] = v[k];
+            }
+            if constexpr (GUIDED) {
+                float2* dst2 = (float2*)(x_next + (size_t)(row + R) * emb_C);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int i = lane + 64 * k;
+                    if (i < nv) dst2[i] = v[k];
+                }
             }
             if (y_next) {
                 // round 4: the first decoder layer's pre-norm of this row rides along (y = LayerNorm(x) * gamma, no bias) -- one
@@ -443,6 +487,12 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                             *(uint32_t*)((bf16*)y_next + (size_t)row * emb_C + 2 * i) = pack_bf16x2(o0, o1);
                         else
                             *(float2*)((float*)y_next + (size_t)row * emb_C + 2 * i) = make_float2(o0, o1);
+                        if constexpr (GUIDED) {
+                            if (y_bf16)
+                                *(uint32_t*)((bf16*)y_next + (size_t)(row + R) * emb_C + 2 * i) = pack_bf16x2(o0, o1);
+                            else
+                                *(float2*)((float*)y_next + (size_t)(row + R) * emb_C + 2 * i) = make_float2(o0, o1);
+                        }
                     }
                 }
             }
@@ -454,6 +504,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
                     e = make_float2(__fadd_rn(e.x, __fmul_rn(q.x, pos_scale)), __fadd_rn(e.y, __fmul_rn(q.y, pos_scale)));
                 }
                 dst[i] = e;
+                if constexpr (GUIDED) ((float2*)(x_next + (size_t)(row + R) * emb_C))[i] = e;
             }
         }
     }
@@ -470,6 +521,34 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
             }
         }
     }
+}
+
+#define DIMX_SAMPLE_PARAMS                                                                                                             \
+    const float *__restrict__ logits, int ld, int R, int top_k, float temperature, const float *__restrict__ noise, uint64_t seed,     \
+        const int32_t *__restrict__ step_dev, uint64_t step_host, int32_t *__restrict__ tokens, int tok_ld, int tok_col_from_step,     \
+        int nslab, long slab_stride, float *__restrict__ logits_out, int logits_out_ld, int row0, int rows_total,                      \
+        const float *__restrict__ emb_table, int emb_C, float *__restrict__ x_next, int32_t *__restrict__ step_rw,                     \
+        unsigned *__restrict__ done_ctr, const float *__restrict__ pos_table, float pos_scale, int pos_rows,                           \
+        const int32_t *__restrict__ dev_params, void *__restrict__ y_next, const float *__restrict__ y_gamma, int y_bf16,              \
+        const float *__restrict__ qkv0_table, float *__restrict__ qkv0_out, int qkv0_N, const int32_t *__restrict__ prompt,            \
+        int prompt_ld, int prompt_max, const int32_t *__restrict__ prompt_len, int prompt_div, int32_t *__restrict__ epoch_rw,         \
+        float fa, float fb, uint8_t *__restrict__ keep_out, int32_t *__restrict__ hist, int hist_ld
+#define DIMX_SAMPLE_ARGS                                                                                                               \
+    logits, ld, R, top_k, temperature, noise, seed, step_dev, step_host, tokens, tok_ld, tok_col_from_step, nslab, slab_stride,        \
+        logits_out, logits_out_ld, row0, rows_total, emb_table, emb_C, x_next, step_rw, done_ctr, pos_table, pos_scale, pos_rows,      \
+        dev_params, y_next, y_gamma, y_bf16, qkv0_table, qkv0_out, qkv0_N, prompt, prompt_ld, prompt_max, prompt_len, prompt_div,      \
+        epoch_rw, fa, fb, keep_out, hist, hist_ld
+
+template <int KIND>
+__global__ __launch_bounds__(256) void sample_kernel(DIMX_SAMPLE_PARAMS) {
+    sample_body<KIND, false>(DIMX_SAMPLE_ARGS, nullptr, 1.0f, nullptr, nullptr);
+}
+
+// the guided sampler: one wave per CLIP, rows b (conditional) and b + R (unconditional) of a 2R-row decode step
+template <int KIND>
+__global__ __launch_bounds__(256) void sample_guided_kernel(DIMX_SAMPLE_PARAMS, const float* __restrict__ logits_u, float scale,
+                                                            float* __restrict__ branch_out, int32_t* __restrict__ tokens_u) {
+    sample_body<KIND, true>(DIMX_SAMPLE_ARGS, logits_u, scale, branch_out, tokens_u);
 }
 
 // x[b, :] = token_emb[tok_b], tok_b = start[b] (row stride start_ld) at the call's first step (start_step: 0, or P0 - 1 of a
@@ -601,8 +680,9 @@ __global__ void step_inc_kernel(int32_t* step) { *step += 1; }
 // bits, [4..5] seed, [6] global row offset and [7] global row count of the sampler's counter-based generator (generate()),
 // [9] steps done in this call = 0 (the chain kernels' counter epoch), [10] step0 again, constant over the call (the sampler's
 // clamp of the prompt lengths), [11] / [12] the sampler filter's real-valued parameters (thres | min_p | min_p_pow, min_p_ratio)
+// [13] the guidance scale of a guided generation (sample_guided_kernel; 1 otherwise)
 __global__ void gen_params_kernel(int32_t* base, int groups, float temperature, uint64_t seed, int row_off,
-                                  int rows_total, int step0, float filter_a, float filter_b) {
+                                  int rows_total, int step0, float filter_a, float filter_b, float guidance) {
     const int g = threadIdx.x;
     if (g >= groups) return;
     int32_t* p = base + 16 * g;
@@ -616,6 +696,7 @@ __global__ void gen_params_kernel(int32_t* base, int groups, float temperature, 
     p[7] = rows_total;
     p[11] = __builtin_bit_cast(int32_t, filter_a);
     p[12] = __builtin_bit_cast(int32_t, filter_b);
+    p[13] = __builtin_bit_cast(int32_t, guidance);
 }
 
 // dst[b, step, :] = src[b, :]  (optional per-step logits dump of generate)
@@ -704,7 +785,7 @@ int launch_ce_argmax(const float* logits, const int32_t* target, float* row_loss
     return DIMX_OK;
 }
 
-int launch_sample(const SampleArgs& a, hipStream_t s) {
+static int check_sample(const SampleArgs& a) {
     const SampleFilter& filt = a.filt;
     DIMX_REQUIRE(a.logits && a.tokens && a.R > 0, DIMX_ERR_ARG, "sample: bad arguments");
     DIMX_REQUIRE(filt.kind >= DIMX_FILTER_TOP_K && filt.kind <= DIMX_FILTER_TOP_A, DIMX_ERR_ARG, "sample: unknown filter kind %d", filt.kind);
@@ -717,27 +798,54 @@ int launch_sample(const SampleArgs& a, hipStream_t s) {
     DIMX_REQUIRE(!a.hist || (a.step_dev && a.hist_ld >= 1), DIMX_ERR_ARG, "sample: the token history needs the device step counter");
     DIMX_REQUIRE(!a.y_next || (a.x_next && a.y_gamma && a.emb_C % 128 == 0 && a.emb_C <= 2048), DIMX_ERR_ARG,
                  "sample: the fused pre-norm needs the fused embedding and a width of k * 128 <= 2048");
+    return DIMX_OK;
+}
+
+// the kernels' common arguments, in DIMX_SAMPLE_PARAMS' order
+#define DIMX_SAMPLE_LAUNCH_ARGS(sa)                                                                                                      \
+    sa.logits, sa.ld_logits, sa.R, sa.top_k, sa.temperature, sa.noise, sa.seed, sa.step_dev, sa.step_host, sa.tokens, sa.tok_ld, sa.tok_col_from_step, \
+        sa.nslab < 1 ? 1 : sa.nslab, sa.slab_stride, sa.logits_out, sa.logits_out_ld, sa.row0, sa.rows_total, sa.emb_table, sa.emb_C, sa.x_next,  \
+        sa.step_rw, sa.done_ctr, sa.pos_table, sa.pos_scale, sa.pos_rows, sa.dev_params, sa.y_next, sa.y_gamma, sa.y_dtype == DIMX_BF16 ? 1 : 0, \
+        sa.qkv0_table, sa.qkv0_out, sa.qkv0_N, sa.prompt, sa.prompt_ld, sa.prompt_max, sa.prompt_len, sa.prompt_div < 1 ? 1 : sa.prompt_div,     \
+        sa.epoch_rw, sa.filt.a, sa.filt.b, sa.filt.keep_out, sa.hist, sa.hist_ld
+
+int launch_sample(const SampleArgs& a, hipStream_t s) {
+    const SampleFilter& filt = a.filt;
+    DIMX_TRY(check_sample(a));
     const int wpb = a.R <= 1024 ? 1 : 4;  // one row per block for decode-sized batches: all CUs busy
     auto kern = filt.kind == DIMX_FILTER_TOP_P   ? sample_kernel<DIMX_FILTER_TOP_P>
                 : filt.kind == DIMX_FILTER_MIN_P ? sample_kernel<DIMX_FILTER_MIN_P>
                 : filt.kind == DIMX_FILTER_TOP_A ? sample_kernel<DIMX_FILTER_TOP_A>
                                                  : sample_kernel<DIMX_FILTER_TOP_K>;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(a.R, wpb)), dim3(64 * wpb), 0, s, a.logits, a.ld_logits, a.R, a.top_k,
-                       a.temperature, a.noise, a.seed, a.step_dev, a.step_host, a.tokens, a.tok_ld, a.tok_col_from_step,
-                       a.nslab < 1 ? 1 : a.nslab, a.slab_stride, a.logits_out, a.logits_out_ld, a.row0, a.rows_total, a.emb_table,
-                       a.emb_C, a.x_next, a.step_rw, a.done_ctr, a.pos_table, a.pos_scale, a.pos_rows, a.dev_params, a.y_next,
-                       a.y_gamma, a.y_dtype == DIMX_BF16 ? 1 : 0, a.qkv0_table, a.qkv0_out, a.qkv0_N, a.prompt, a.prompt_ld,
-                       a.prompt_max, a.prompt_len, a.prompt_div < 1 ? 1 : a.prompt_div, a.epoch_rw, filt.a, filt.b, filt.keep_out,
-                       a.hist, a.hist_ld);
+    hipLaunchKernelGGL(kern, dim3(ceil_div(a.R, wpb)), dim3(64 * wpb), 0, s, DIMX_SAMPLE_LAUNCH_ARGS(a));
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+// a.R clips: rows [0, R) of a.logits are sampled against rows [0, R) of g.logits_u, and every per-row output of the sampler is
+// written for rows r and r + R (the caller's buffers hold 2R rows); a.rows_total counts clips (the noise rows of an R-row launch)
+int launch_sample_guided(const SampleArgs& a, const GuidedArgs& g, hipStream_t s) {
+    const SampleFilter& filt = a.filt;
+    DIMX_TRY(check_sample(a));
+    DIMX_REQUIRE(g.logits_u && !filt.keep_out, DIMX_ERR_ARG, "sample_guided: no unconditional logits, or keep_out (not written here)");
+    DIMX_REQUIRE(a.dev_params || g.scale - g.scale == 0.f, DIMX_ERR_ARG, "sample_guided: the scale is NaN or infinite");
+    DIMX_REQUIRE(!g.branch_out || a.logits_out_ld >= 1, DIMX_ERR_ARG, "sample_guided: the branch dump needs its step count (logits_out_ld)");
+    const int wpb = a.R <= 1024 ? 1 : 4;
+    auto kern = filt.kind == DIMX_FILTER_TOP_P   ? sample_guided_kernel<DIMX_FILTER_TOP_P>
+                : filt.kind == DIMX_FILTER_MIN_P ? sample_guided_kernel<DIMX_FILTER_MIN_P>
+                : filt.kind == DIMX_FILTER_TOP_A ? sample_guided_kernel<DIMX_FILTER_TOP_A>
+                                                 : sample_guided_kernel<DIMX_FILTER_TOP_K>;
+    hipLaunchKernelGGL(kern, dim3(ceil_div(a.R, wpb)), dim3(64 * wpb), 0, s, DIMX_SAMPLE_LAUNCH_ARGS(a), g.logits_u, g.scale, g.branch_out,
+                       g.tokens_u);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }
 
 int launch_gen_params(int32_t* base, int groups, float temperature, uint64_t seed, int row_off, int rows_total,
-                      hipStream_t s, int step0, float filter_a, float filter_b) {
+                      hipStream_t s, int step0, float filter_a, float filter_b, float guidance) {
     DIMX_REQUIRE(step0 >= 0, DIMX_ERR_ARG, "gen_params: negative first step");
     hipLaunchKernelGGL(gen_params_kernel, dim3(1), dim3(64), 0, s, base, groups, temperature, seed, row_off, rows_total, step0,
-                       filter_a, filter_b);
+                       filter_a, filter_b, guidance);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

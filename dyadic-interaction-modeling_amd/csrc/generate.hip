@@ -128,6 +128,10 @@ struct GenRequest {
     size_t ws_bytes;
     hipStream_t st;
     const BeamCall* beam;   // beam search: the selection and the cache reorder end the step in the sampler's place; nullptr = the sampler
+    // classifier-free guidance (dimx_generate_guided): the step runs 2B rows, the guided sampler ends it; tokens / logits_out hold B rows
+    bool guided = false;
+    float scale = 1.f;
+    float* branch_out = nullptr;   // [2, B, n, V] or nullptr
 };
 
 // what every step of one generate call shares (built once in generate_impl)
@@ -148,6 +152,7 @@ struct StepCtx {
     hipStream_t st;
     int row0, B, grp;
     int clip0, nclip;   // with S samples per clip, rows are samples (row = clip * S + sample)
+    int Bc;             // rows that run the cross sublayer: B, or the conditional half [0, B / 2) of a guided step
     int T, S, DD, heads, D, inner, V, n, Tp;
     int n_keys;   // the cross attention's key bound: T, or what a streaming session sets (gen_run_set_keys)
     size_t es;
@@ -170,7 +175,8 @@ static StepCtx step_ctx(dimx_handle h, const GenCall& gc, const StepRoute& r, in
     c.h = h; c.gc = &gc; c.r = &r; c.st = st;
     c.row0 = row0; c.B = B; c.grp = grp;
     c.T = q.T; c.S = q.S;
-    c.clip0 = row0 / c.S; c.nclip = B / c.S;
+    c.clip0 = row0 / c.S; c.nclip = r.guided ? B / 2 : B / c.S;
+    c.Bc = r.guided ? B / 2 : B;
     c.DD = dg.dim; c.heads = dg.heads; c.D = dg.dim_head; c.inner = c.heads * c.D;
     c.V = dg.num_tokens; c.n = gen_steps(h, c.T); c.Tp = tpad(c.T); c.n_keys = c.T;
     c.es = es_of(h); c.scale = 1.0f / sqrtf((float)c.D);
@@ -216,6 +222,18 @@ static int gen_start(const StepCtx& c) {
     dimx_handle h = c.h;
     const GenScratch& s = c.s;
     const GenPrompt& pr = c.gc->req.pr;
+    if (c.r->guided) {   // both halves start from their clip's token: the launches of a plain start, once per half
+        for (int half = 0; half < 2; ++half) {
+            const size_t r0 = (size_t)half * c.Bc;
+            DIMX_TRY(launch_embed_step(h->dec.tok_emb, c.DD, c.V, c.start, c.tokens, c.n, s.step, s.x + r0 * c.DD, c.Bc, 1, c.st, c.pos,
+                                       c.pos_scale, pr.ld, pr.step0));
+            if (c.r->qkv0)
+                DIMX_TRY(launch_gather_start_rows(c.r->qkv0, 3 * c.inner, c.V, c.start, 1, s.qkv + r0 * 3 * c.inner, c.Bc, c.st, pr.ld,
+                                                  c.r->kv0 ? s.hist + r0 * c.T : nullptr, c.T));
+        }
+        if (c.r->qkv0) return DIMX_OK;
+        return launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s.st_xr, s.y, h->dec.self_[0].ln_g, c.B, c.DD, c.st);
+    }
     DIMX_TRY(launch_embed_step(h->dec.tok_emb, c.DD, c.V, c.start, c.tokens, c.n, s.step, s.x, c.B, c.S, c.st, c.pos, c.pos_scale, pr.ld, pr.step0));
     if (c.r->qkv0)   // the first layer's q/k/v of the start token: a table row into slab 0 (nothing reads y before the layer rewrites it)
         return launch_gather_start_rows(c.r->qkv0, 3 * c.inner, c.V, c.start, c.S, s.qkv, c.B, c.st, pr.ld, c.r->kv0 ? s.hist : nullptr, c.T);
@@ -282,7 +300,7 @@ static DecodeAttnArgs cross_args(const StepCtx& c, int l) {
     ca.dtype = c.h->at;
     ca.q = s.qc; ca.q_ld = c.inner; ca.q_f32 = 1; ca.nslab = 1; ca.slab_stride = s.st_qc;
     ca.kcache = (void*)c.ck[l]; ca.vcache = (void*)c.cv[l]; ca.Tmax = c.Tp;
-    ca.out = s.o; ca.o_ld = c.inner; ca.B = c.S > 1 ? c.nclip : c.B; ca.rows_per_clip = c.S; ca.H = c.heads;
+    ca.out = s.o; ca.o_ld = c.inner; ca.B = c.S > 1 ? c.nclip : c.Bc; ca.rows_per_clip = c.S; ca.H = c.heads;
     ca.n_keys = c.n_keys; ca.kmask = c.ctx_mask; ca.kmask_ld = c.T; ca.scale = c.scale;
     if (c.r->win) { ca.win = 1; ca.lookahead = c.r->lookahead; ca.step = s.step; }
     return ca;
@@ -373,6 +391,23 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         DIMX_TRY(launch_decode_attn(ca, c.st));
         // cross out-projection -> x += . -> LayerNorm (feed-forward input)
         DIMX_TRY(chain_site(c, 3 * l + 1, s.o, inner, &h->dec.cross[l].out, 0, h->dec.ff[l].ln_g, nullptr, nullptr, 0));
+    } else if (r.guided) {
+        // The unconditional rows [Bc, B) are the decoder without its cross sublayers (every cross projection is bias-free: a context
+        // of zero rows gives K = V = 0 and W_o . 0 = 0, dimx/guidance.py): the q projection, the one-query attention and the out
+        // projection run on the conditional rows alone, and no launch reads cross K / V for the others.
+        const int Bc = c.Bc;
+        const size_t es = c.es;
+        DIMX_TRY(launch_decode_attn(sa, c.st));
+        DIMX_TRY(slab_gemm(c, s.o, inner, h->dec.self_[l].out, s.xr, s.st_xr, pending));
+        // folds the self slabs into x for all rows; y is the cross pre-norm, read for the conditional rows only
+        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, *pending, s.st_xr, s.y, h->dec.cross[l].ln_g, B, DD, c.st));
+        DIMX_TRY(slab_gemm_rows(h, Bc, c.st, s.y, DD, h->dec.cross[l].qkv, s.qc, s.st_qc, &ns));
+        ca.nslab = ns;
+        DIMX_TRY(launch_decode_attn(ca, c.st));
+        DIMX_TRY(slab_gemm_rows(h, Bc, c.st, s.o, inner, h->dec.cross[l].out, s.xr, s.st_xr, pending));
+        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, *pending, s.st_xr, s.y, h->dec.ff[l].ln_g, Bc, DD, c.st));
+        DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x + (size_t)Bc * DD, s.xr + (size_t)Bc * DD, 0, s.st_xr, (unsigned char*)s.y + (size_t)Bc * DD * es,
+                                            h->dec.ff[l].ln_g, B - Bc, DD, c.st));
     } else {
         DIMX_TRY(launch_decode_attn(sa, c.st));
         DIMX_TRY(slab_gemm(c, s.o, inner, h->dec.self_[l].out, s.xr, s.st_xr, pending));
@@ -476,6 +511,30 @@ static int finish_sample(const StepCtx& c, int nlg) {
     return launch_sample(sm, c.st);
 }
 
+// The guided sampler in finish_sample's place: one wave per clip forms the guided row from rows b and b + Bc of the logits, samples
+// it as row b of a Bc-row generation, and writes the token's embedding / pre-norm / table rows for both halves
+static int finish_guided(const StepCtx& c, int nlg) {
+    dimx_handle h = c.h;
+    const GenScratch& s = c.s;
+    const GenRequest& q = c.gc->req;
+    const GenPrompt& pr = q.pr;
+    const float* qkv0 = c.r->qkv0;
+    SampleArgs sm;
+    sm.logits = s.logits; sm.ld_logits = c.V; sm.R = c.Bc; sm.nslab = nlg; sm.slab_stride = s.st_lg; sm.row0 = 0; sm.rows_total = c.Bc;
+    sm.top_k = c.gc->top_k; sm.noise = q.noise; sm.filt.kind = h->filter_kind;
+    sm.temperature = q.temperature; sm.seed = q.seed;
+    sm.step_dev = s.step; sm.step_rw = s.step; sm.dev_params = s.step + 2; sm.done_ctr = (unsigned*)(s.step + 8); sm.epoch_rw = s.step + 9;
+    sm.tokens = c.tokens; sm.tok_ld = c.n; sm.tok_col_from_step = 1; sm.logits_out = c.logits_out; sm.logits_out_ld = c.n;
+    sm.emb_table = h->dec.tok_emb; sm.emb_C = c.DD; sm.x_next = s.x; sm.pos_table = c.pos; sm.pos_scale = c.pos_scale; sm.pos_rows = c.n;
+    sm.y_next = qkv0 ? nullptr : s.y; sm.y_gamma = qkv0 ? nullptr : h->dec.self_[0].ln_g; sm.y_dtype = h->at;
+    sm.qkv0_table = qkv0; sm.qkv0_out = s.qkv; sm.qkv0_N = 3 * c.inner;
+    if (c.r->kv0) { sm.hist = s.hist; sm.hist_ld = c.T; }
+    sm.prompt = c.forced; sm.prompt_ld = pr.ld; sm.prompt_max = pr.Pmax; sm.prompt_len = c.forced_len; sm.prompt_div = 1;
+    GuidedArgs g;
+    g.logits_u = s.logits + (size_t)c.Bc * c.V; g.scale = q.scale; g.branch_out = q.branch_out;
+    return launch_sample_guided(sm, g, c.st);
+}
+
 // one decoder step for a clip group: x = emb(token) -> depth x {attention half, feed-forward} -> logits -> sample -> step += 1
 static int gen_step(const StepCtx& c) {
     int pending = 0;  // slabs of the previous residual projection not yet folded into x
@@ -485,7 +544,7 @@ static int gen_step(const StepCtx& c) {
     }
     int nlg = 0;
     DIMX_TRY(logits(c, pending, &nlg));
-    return c.r->beam ? finish_beam(c, nlg) : finish_sample(c, nlg);
+    return c.r->beam ? finish_beam(c, nlg) : c.r->guided ? finish_guided(c, nlg) : finish_sample(c, nlg);
 }
 
 // What the steps of a call launch, decided once: from the handle's switches, the request and the shapes of the call's group 0 of
@@ -505,6 +564,8 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     r.multi_tr = gen_multi_tr(h, q.S);   // consulted on the per-op branch and without the window only
     r.win = h->xwin_on != 0;
     r.lookahead = r.win ? h->xwin_lookahead : 0;
+    r.guided = q.guided;
+    if (r.guided) r.chain = r.defer = r.logits_chain = r.multi_tr = false;   // the per-op step, as a session takes it (no layer kernel either: it needs chain)
     // one group: every projection launch of the generation has R rows, and so has the table's build
     if (G == 1 && qkv0_table_supported(h)) {
         DIMX_TRY(qkv0_table_alloc(h));
@@ -542,6 +603,7 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
     k.filter_kind = h->filter_kind;
     k.beam = q.beam ? *q.beam : BeamCall{};
     k.xwin_on = r.win ? 1 : 0; k.xwin_lookahead = r.lookahead;
+    k.guided = r.guided; k.branch_out = q.branch_out;
     return k;
 }
 
@@ -713,7 +775,7 @@ static int gen_parameters(dimx_handle h, const GenCall& gc, const StepRoute& rou
     // step / done counters = 0; temperature, seed and the sampler's global row window go to device memory so that
     // the captured step graph is independent of them
     DIMX_TRY(launch_gen_params(s.step, dimx_ctx::kMaxGroups, q.temperature, q.seed, h->shard_row_off * q.S,
-                               h->shard_rows_total * q.S, st, q.pr.step0, h->filter_a, h->filter_b));
+                               h->shard_rows_total * q.S, st, q.pr.step0, h->filter_a, h->filter_b, q.guided ? q.scale : 1.f));
     if (route.multi_tr) DIMX_TRY(launch_pack_key_words(q.ctx_mask, q.T, nullptr, q.B, q.T, s.kw, s.kw_cap, st));
     if (!q.beam) return DIMX_OK;
     DIMX_REQUIRE(h->decg.dim_head == 64 && h->decg.depth <= 8 && !h->decg.abs_pos, DIMX_ERR_ARG,
@@ -754,7 +816,8 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     const int top_k = h && h->filter_kind != DIMX_FILTER_TOP_K ? 0 : q.top_k;
     DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
                  "generate: n_samples %d not in {1,2,4,5,8,10}", S);
-    DIMX_TRY(check_common(h, B, T, q.ws, q.ws_bytes, COMP_DEC, S));
+    const int halves = q.guided ? 2 : 1;   // a guided generation decodes every clip twice: 2B rows of self caches, B cross caches
+    DIMX_TRY(check_common(h, B, T, q.ws, q.ws_bytes, COMP_DEC, S * halves));
     DIMX_REQUIRE(pr.tok && q.ctx_mask && q.tokens && T >= 2, DIMX_ERR_ARG, "generate: null argument or T < 2");
     DIMX_REQUIRE(sess || (h->ctx_ready && h->ctx_B == B && h->ctx_T == T && h->ctx_ws == q.ws && h->ctx_for_generate),
                  DIMX_ERR_STATE, "generate: call dimx_encode_ctx(for_generate=1) with the same B, T, ws first");
@@ -762,7 +825,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     CtxPersist& cp = run.cp;
     Arena ar = scratch_arena(h, q.ws, q.ws_bytes, B, T, &cp);
     GenScratch& s = run.s;
-    const int R = B * S;  // sequences generated in this call
+    const int R = B * S * halves;  // rows of the decode step
     plan_gen(h, ar, R, T, s);
     PrefillScratch ps;
     if (pr.step0 > 0) plan_prefill(h, ar, B, pr.step0, T, ps);
@@ -773,7 +836,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     DIMX_TRY(chain_state_ensure(h));
     int G = h->gen_groups < 1 ? 1 : h->gen_groups;
     if (G > B) G = B;
-    if (S > 1 || q.beam || sess) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
+    if (S > 1 || q.beam || sess || q.guided) G = 1;  // samples of a clip stay together (they share the clip's cross K/V pass)
     run.G = G;
     int lo[dimx_ctx::kMaxGroups + 1];
     for (int g = 0; g <= G; ++g) lo[g] = (int)((long)R * g / G);
@@ -1005,6 +1068,28 @@ int dimx_generate_prompted(dimx_handle h, const int32_t* prompt, int ld_prompt, 
         StepRoute route;
         return generate_impl(h, q, false, true, &route);
     }
+    return generate_checked(h, q);
+}
+
+int dimx_generate_guided(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, const uint8_t* ctx_mask,
+                         int B, int T, float scale, float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens,
+                         float* logits_out, float* branch_logits_out, void* ws, size_t ws_bytes, void* stream) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_NO_SESSION(h, "generate_guided");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "generate_guided: guidance is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    DIMX_REQUIRE(scale - scale == 0.f, DIMX_ERR_ARG, "generate_guided: the scale is NaN or infinite");
+    DIMX_REQUIRE(prompt && T >= 2 && Pmax >= 1 && Pmax <= T - 1 && ld_prompt >= Pmax, DIMX_ERR_ARG,
+                 "generate_guided: need 1 <= Pmax <= T - 1 and ld_prompt >= Pmax (Pmax=%d T=%d ld_prompt=%d)", Pmax, T, ld_prompt);
+    DIMX_REQUIRE(B >= 1 && T <= h->d.max_seq_len, DIMX_ERR_ARG, "B=%d T=%d out of range (T <= %d)", B, T, h->d.max_seq_len);
+    const size_t need = dimx_workspace_bytes_guided(h, B, T);
+    DIMX_REQUIRE(ws_bytes >= need, DIMX_ERR_WORKSPACE, "generate_guided: workspace %zu < required %zu (dimx_workspace_bytes_guided)", ws_bytes, need);
+    // the whole prompt goes through forced decode steps (P0 = 1): both halves then see the same tokens by the same launches
+    GenRequest q{{prompt, ld_prompt, Pmax, prompt_len, 0}, ctx_mask, B, T, 1, temperature, top_k, exp_noise, seed,
+                 tokens, logits_out, ws, ws_bytes, (hipStream_t)stream, nullptr};
+    q.guided = true;
+    q.scale = scale;
+    q.branch_out = branch_logits_out;
     return generate_checked(h, q);
 }
 

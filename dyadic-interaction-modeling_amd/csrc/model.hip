@@ -1436,6 +1436,11 @@ size_t dimx_workspace_bytes_prompt(dimx_handle h, int B, int T, int n_samples, i
     return workspace_bytes_prompt(h, B, T, n_samples, P0);
 }
 
+size_t dimx_workspace_bytes_guided(dimx_handle h, int B, int T) {
+    if (!h || B < 1 || T < 2 || T > h->d.max_seq_len) return 0;
+    return workspace_bytes(h, B, T, 2);   // the persistent part (cross K / V) for B clips, the generation scratch (self caches) for 2B rows
+}
+
 int dimx_vq_argmin(dimx_handle h, int which, const float* z, int N, int32_t* idx, float* best_d, float* margin,
                    void* stream) {
     DIMX_REQUIRE(h && (which == 0 || which == 1), DIMX_ERR_ARG, "vq_argmin: bad handle/which");

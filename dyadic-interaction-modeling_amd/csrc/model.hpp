@@ -135,6 +135,8 @@ struct StepRoute {
     const BeamCall* beam = nullptr;
     bool fault_inject = false;     // test hook: the chain kernels are launched with fault = 1
     int G = 1, S = 1;              // clip groups, samples per clip
+    bool guided = false;           // classifier-free guidance: rows [0, R / 2) conditional, [R / 2, R) unconditional (no cross sublayer);
+                                   // the per-op step, and the guided sampler ends it
 };
 
 // Everything a captured step bakes in: the call's pointers and shapes, and the route.  Equality is memberwise.
@@ -151,13 +153,15 @@ struct GraphKey {
     int filter_kind;          // the sampler kernel's instantiation; the filter's real-valued parameters live in device memory
     BeamCall beam;            // beam search: the selection / reorder kernels' buffers, all null = the sampler ends the step
     int xwin_on, xwin_lookahead;   // online generation (dimx_set_cross_lookahead): other launches, and the look-ahead is a kernel argument
+    bool guided;                   // the guided step's launches; the scale lives in device memory
+    const void* branch_out;        // ... and its optional dump of both branches' logits
     bool operator==(const GraphKey& o) const {
         return ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && noise == o.noise && start == o.start && mask == o.mask &&
                tokens == o.tokens && logits_out == o.logits_out && G == o.G && S == o.S && chain == o.chain && defer == o.defer &&
                logits_chain == o.logits_chain && multi_tr == o.multi_tr && fault_inject == o.fault_inject &&
                layer_kernel == o.layer_kernel && qkv0 == o.qkv0 && kv0 == o.kv0 && prompt_len == o.prompt_len &&
                ld_prompt == o.ld_prompt && Pmax == o.Pmax && filter_kind == o.filter_kind && beam == o.beam && xwin_on == o.xwin_on &&
-               xwin_lookahead == o.xwin_lookahead;
+               xwin_lookahead == o.xwin_lookahead && guided == o.guided && branch_out == o.branch_out;
     }
 };
 
@@ -253,6 +257,9 @@ struct dimx_ctx {
     // online fine-tuning (dimx_set_train_lookahead): the same visibility in the decoder cross attention of
     // dimx_train_forward_backward, query row i = step t.  Independent of xwin_*.
     int twin_on = 0, twin_lookahead = 0;
+    // condition dropout of the SLMFT training step (dimx_set_train_cond_keep): [B] keep flags in device memory, read by the step's
+    // kernels (a new draw replays the captured step); nullptr = off
+    const uint8_t* tcond_keep = nullptr;
     // streaming session (stream.hip, dimx_stream_begin .. dimx_stream_end / dimx_stream_abort): one per handle; while it is
     // open the stages that rebuild the context or generate return DIMX_ERR_STATE
     void* stream_sess = nullptr;

@@ -642,4 +642,24 @@ int dimx_op_sample_filtered(const float* logits, int R, int kind, int top_k, flo
     return launch_sample(sm, (hipStream_t)stream);
 }
 
+int dimx_op_sample_guided(const float* cond, const float* uncond, int R, int nslab, long slab_stride, float scale, int kind, int top_k,
+                          float a, float b, float temperature, const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens,
+                          float* guided_out, void* stream) {
+    DIMX_TRY(check_sampler_filter(kind, a, b));
+    DIMX_REQUIRE(cond && uncond && tokens && R > 0, DIMX_ERR_ARG, "op_sample_guided: null argument or R < 1");
+    DIMX_REQUIRE(scale - scale == 0.f, DIMX_ERR_ARG, "op_sample_guided: the scale is NaN or infinite");
+    DIMX_REQUIRE(nslab >= 1 && nslab <= 8 && (nslab == 1 || slab_stride >= (long)R * 512), DIMX_ERR_ARG,
+                 "op_sample_guided: 1 <= nslab <= 8 slabs of at least R * 512 elements each");
+    SampleArgs sm;
+    sm.logits = cond; sm.ld_logits = 512; sm.R = R; sm.nslab = nslab; sm.slab_stride = slab_stride; sm.rows_total = R;
+    sm.tokens = tokens; sm.tok_ld = 1;
+    sm.top_k = kind == DIMX_FILTER_TOP_K ? top_k : 0; sm.temperature = temperature; sm.seed = seed;
+    sm.noise = exp_noise; sm.step_host = exp_noise ? 0 : step;
+    sm.filt = SampleFilter{kind, a, b, nullptr};
+    sm.logits_out = guided_out; sm.logits_out_ld = 1;
+    GuidedArgs g;
+    g.logits_u = uncond; g.scale = scale; g.tokens_u = tokens + R;
+    return launch_sample_guided(sm, g, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -279,10 +279,12 @@ struct StepGraphKey {
     size_t ws_bytes;
     int B, T, at, side;
     int win_on, win_lookahead;   // dimx_set_train_lookahead: a step captured under one setting is never replayed under another
+    const void* cond_keep;       // dimx_set_train_cond_keep: the pointer is a kernel argument, its contents are read on the device
     bool operator==(const StepGraphKey& o) const {
         return params == o.params && grads == o.grads && v_speaker == o.v_speaker && v_audio == o.v_audio && mask == o.mask && z_l == o.z_l &&
                kv_mask == o.kv_mask && loss_out == o.loss_out && logits_out == o.logits_out && ws == o.ws && ws_bytes == o.ws_bytes &&
-               B == o.B && T == o.T && at == o.at && side == o.side && win_on == o.win_on && win_lookahead == o.win_lookahead;
+               B == o.B && T == o.T && at == o.at && side == o.side && win_on == o.win_on && win_lookahead == o.win_lookahead &&
+               cond_keep == o.cond_keep;
     }
 };
 struct TrainState {
@@ -1422,6 +1424,10 @@ static int train_run(dimx_handle h, const float* params, float* grads, const flo
     float* ctx = s.f32((size_t)s.M * DD);
     TR(tr_add_rows(x_s, d.dim, s.p("patch_embed_dec_s"), nullptr, 0.f, T, ctx, DD, s.M, d.dim, st));
     TR(tr_copy_cols(v_audio, d.dim_a, ctx + d.dim, DD, s.M, d.dim_a, 0, st));
+    // condition dropout (dimx_set_train_cond_keep): a dropped clip is trained under the null context -- zero rows after the concat,
+    // before the cross K / V projections read them -- and sends nothing back into its context (below)
+    const uint8_t* cond_keep = h->tcond_keep;
+    if (cond_keep) TR(tr_zero_clip_rows(ctx, cond_keep, B, T, DD, st));
 
     // ---------------- decoder, teacher-forced: inp = z[:, :-1] (ignored -> 0), target = z[:, 1:]
     const std::string dn = "decoder_joint.net.";
@@ -1495,6 +1501,7 @@ static int train_run(dimx_handle h, const float* params, float* grads, const flo
         TR(gemm_f32(s, ohT, Mp, dhT, d.num_tokens, DD, Mp, s.g(dn + "token_emb.emb.weight"), DD, nullptr, nullptr, 0));
         s.ar->off = mark;
     }
+    if (cond_keep) TR(tr_zero_clip_rows(dctx, cond_keep, B, T, DD, st));
     // context -> x_s (+ patch_embed_dec_s) ; the audio half has no parameters behind it
     TR(tr_copy_cols(dctx, DD, dx_s, d.dim, s.M, d.dim, 0, st));
     DIMX_TRY(bias_adjoint(s, dx_s, s.g("patch_embed_dec_s"), s.M, d.dim));
@@ -1842,7 +1849,7 @@ int dimx_train_forward_backward(dimx_handle h, const float* params, float* grads
     DIMX_TRY(state_of(h, &ts));
     hipStream_t st = (hipStream_t)stream;
     const StepGraphKey key{params, grads, v_speaker, v_audio, mask, z_l, kv_mask, loss_out, logits_out, ws, ws_bytes, B, T, h->at, side ? 1 : 0,
-                           h->twin_on, h->twin_lookahead};
+                           h->twin_on, h->twin_lookahead, h->tcond_keep};
     if (train_use_graph(B * T)) {
         if (ts->exec && ts->graph_key == key) {
             ++ts->graph_launches;
@@ -1910,6 +1917,20 @@ int dimx_set_train_lookahead(dimx_handle h, int on, int lookahead) {
                  h->variant);
     h->twin_on = on ? 1 : 0;
     h->twin_lookahead = on ? lookahead : 0;
+    return DIMX_OK;
+}
+
+int dimx_set_train_cond_keep(dimx_handle h, const uint8_t* keep_dev) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_train_cond_keep: condition dropout is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    h->tcond_keep = keep_dev;
+    return DIMX_OK;
+}
+
+int dimx_train_cond_keep(dimx_handle h, const uint8_t** keep_dev) {
+    DIMX_REQUIRE(h && keep_dev, DIMX_ERR_ARG, "train_cond_keep: null argument");
+    *keep_dev = h->tcond_keep;
     return DIMX_OK;
 }
 

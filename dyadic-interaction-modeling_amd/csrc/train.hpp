@@ -120,6 +120,7 @@ int tr_add(float* y, const float* a, long n, hipStream_t s);
 int tr_add_rows(const float* a, int lda, const float* row, const float* table, float scale, int T, float* y, int ldy, int M, int C,
                 hipStream_t s);
 int tr_zero_rows(float* y, const uint8_t* keep, int M, int C, hipStream_t s);
+int tr_zero_clip_rows(float* y, const uint8_t* keep, int B, int T, int C, hipStream_t s);   // y [B * T, C]: clip b's rows = 0 where keep[b] == 0
 int tr_copy_cols(const float* src, int lds_, float* dst, int ldd, int M, int C, int accumulate, hipStream_t s);
 int tr_pos_grad(const float* dx, float* dtable, int B, int T, int C, float scale, hipStream_t s, int accumulate = 0);
 int tr_cross_entropy(const float* logits, const int32_t* target, float* row_loss, float* dlogits, int R, float* loss_out, hipStream_t s);

@@ -639,6 +639,14 @@ __global__ void zero_rows_kernel(float* __restrict__ y, const uint8_t* __restric
         if (!keep[m]) y[i] = 0.f;
     }
 }
+// condition dropout: the T rows of clip b are zeroed where keep[b] == 0 and left as they are otherwise (no rescaling)
+__global__ void zero_clip_rows_kernel(float* __restrict__ y, const uint8_t* __restrict__ keep, int T, int M, int C) {
+    const long total = (long)M * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / C) / T;
+        if (!keep[b]) y[i] = 0.f;
+    }
+}
 // dst[m, 0:C) (+)= src[m, 0:C) with different row strides (context slice / concat)
 __global__ void copy_cols_kernel(const float* __restrict__ src, int lds_, float* __restrict__ dst, int ldd, int M, int C, int accumulate) {
     const long total = (long)M * C;
@@ -1426,6 +1434,12 @@ int tr_add_rows(const float* a, int lda, const float* row, const float* table, f
 }
 int tr_zero_rows(float* y, const uint8_t* keep, int M, int C, hipStream_t s) {
     hipLaunchKernelGGL(zero_rows_kernel, dim3(ew_grid((long)M * C)), dim3(256), 0, s, y, keep, M, C);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+int tr_zero_clip_rows(float* y, const uint8_t* keep, int B, int T, int C, hipStream_t s) {
+    DIMX_REQUIRE(y && keep && B > 0 && T > 0 && C > 0, DIMX_ERR_ARG, "zero_clip_rows: bad arguments");
+    hipLaunchKernelGGL(zero_clip_rows_kernel, dim3(ew_grid((long)B * T * C)), dim3(256), 0, s, y, keep, T, B * T, C);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

@@ -77,9 +77,12 @@ class Engine:
         return self.lib.dimx_missing_weights(self.h)
 
     # ------------------------------------------------------------------ workspace
-    def workspace(self, B, T, n_samples=1, prompt_frames=1):
-        """``prompt_frames`` P0 > 1: room for the prefill of a prompted generation too (dimx_workspace_bytes_prompt)."""
-        if prompt_frames > 1:
+    def workspace(self, B, T, n_samples=1, prompt_frames=1, guided=False):
+        """``prompt_frames`` P0 > 1: room for the prefill of a prompted generation too (dimx_workspace_bytes_prompt).
+        ``guided``: room for a guided generation (dimx_workspace_bytes_guided: 2B rows of self-attention caches)."""
+        if guided:
+            need = max(self.lib.dimx_workspace_bytes_guided(self.h, B, T), self.lib.dimx_workspace_bytes_samples(self.h, B, T, n_samples))
+        elif prompt_frames > 1:
             need = self.lib.dimx_workspace_bytes_prompt(self.h, B, T, n_samples, int(prompt_frames))
         else:
             need = self.lib.dimx_workspace_bytes_samples(self.h, B, T, n_samples)
@@ -161,7 +164,9 @@ class Engine:
         sampler's counter-based generator depends on it); (0, 0) = unsharded."""
         L.check(self.lib.dimx_set_shard(self.h, int(row_offset), int(rows_total)), "dimx_set_shard")
 
-    def encode_ctx(self, v_speaker, v_audio, mask_u8, for_generate, return_x_s=False, n_samples=1, prompt_frames=1):
+    def encode_ctx(self, v_speaker, v_audio, mask_u8, for_generate, return_x_s=False, n_samples=1, prompt_frames=1, guided=False):
+        """``guided``: the context of a ``generate(guidance=)`` call -- the workspace is sized for it (a workspace grown between
+        the two calls would drop the context)."""
         B, T, _ = v_speaker.shape
         v_speaker = v_speaker.to(torch.float32).contiguous()
         v_audio = v_audio.to(torch.float32).contiguous() if v_audio is not None else None
@@ -169,7 +174,7 @@ class Engine:
             raise L.DimxError("encode_ctx: the SLMFT variant needs v_audio")
         self._chk(v_speaker, v_audio, mask_u8)
         x_s = torch.empty(B, T, self.dims.dim, dtype=torch.float32, device=self.device) if return_x_s else None
-        ws, wsb = self.workspace(B, T, n_samples, prompt_frames)   # the generate call that follows must see the same workspace
+        ws, wsb = self.workspace(B, T, n_samples, prompt_frames, guided)   # the generate call that follows must see the same workspace
         L.check(self.lib.dimx_encode_ctx(self.h, L.ptr(v_speaker), L.ptr(v_audio), L.ptr(mask_u8), B, T,
                                          1 if for_generate else 0, L.ptr(x_s), ws, wsb, self._s()),
                 "dimx_encode_ctx")
@@ -191,7 +196,7 @@ class Engine:
                                          L.ptr(x_j), ws, wsb, self._s()), "dimx_slm_encode")
         return x_s, x_l, x_j
 
-    def set_context(self, x, v_audio, which_patch=0, for_generate=False, T=None, n_samples=1, prompt_frames=1):
+    def set_context(self, x, v_audio, which_patch=0, for_generate=False, T=None, n_samples=1, prompt_frames=1, guided=False):
         """context = cat(x[:, :T] + patch_embed_dec_{s|l}, v_audio) + cross K/V; x [B, rows>=T, dim] f32."""
         B, rows, _ = x.shape
         T = T or rows
@@ -199,7 +204,7 @@ class Engine:
         v_audio = v_audio.to(torch.float32).contiguous()
         assert x.stride(2) == 1 and x.stride(1) == x.shape[2], "x rows must be dense"
         ldx_rows = x.stride(0) // x.shape[2]
-        ws, wsb = self.workspace(B, T, n_samples, prompt_frames)
+        ws, wsb = self.workspace(B, T, n_samples, prompt_frames, guided)
         L.check(self.lib.dimx_set_context(self.h, ctypes.c_void_p(x.data_ptr()), ldx_rows, which_patch, L.ptr(v_audio),
                                           B, T, 1 if for_generate else 0, ws, wsb, self._s()), "dimx_set_context")
 
@@ -264,8 +269,15 @@ class Engine:
 
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
                  n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False, filter_logits_fn=None,
-                 filter_kwargs=None, return_scores=False, lookahead=None):
+                 filter_kwargs=None, return_scores=False, lookahead=None, guidance=None, return_branches=False):
         """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
+
+        ``guidance``: classifier-free guidance with this scale (dimx_generate_guided, include/dimx.h; the definition is
+        dimx.guidance): every step samples from cond + (scale - 1) * (cond - uncond), the second branch being the decoder without
+        a context.  None is today's call, launch for launch; 1.0 computes the same tokens by the guided step.  The context must
+        have been built with ``guided=True`` (``encode_ctx`` / ``set_context``).  ``return_logits`` / ``return_scores`` then refer to
+        the GUIDED logits; ``return_branches`` appends both branches' raw logits [2, B, n, 512] to the return value.  A prompt goes
+        through forced decode steps; ``filter_logits_fn`` and ``lookahead`` act as without guidance.  One sample per clip.
 
         ``return_scores``: the return value gains a trailing dimx.scoring.SeqScores (score f64, count int32, both [B*S]): the
         log-likelihood of every sampled sequence under softmax(raw logits) over the columns dimx.scoring.scored_columns names
@@ -295,7 +307,7 @@ class Engine:
             self.set_cross_lookahead(lookahead)
             try:
                 return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt, prompt_len,
-                                     prefill, no_prefill, filter_logits_fn, filter_kwargs, return_scores)
+                                     prefill, no_prefill, filter_logits_fn, filter_kwargs, return_scores, None, guidance, return_branches)
             finally:
                 self.set_cross_lookahead(prev)
         if filter_logits_fn is not None or filter_kwargs:
@@ -304,9 +316,15 @@ class Engine:
                 self.set_sampler_filter(kind, fa, fb)
                 try:
                     return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt,
-                                         prompt_len, prefill, no_prefill, return_scores=return_scores)
+                                         prompt_len, prefill, no_prefill, return_scores=return_scores, guidance=guidance,
+                                         return_branches=return_branches)
                 finally:
                     self.set_sampler_filter(0)
+        if guidance is not None:
+            return self._generate_guided(float(guidance), start, prompt, prompt_len, mask_u8, T, temperature, top_k, noise, seed,
+                                         return_logits, n_samples, return_scores, return_branches)
+        if return_branches:
+            raise ValueError("return_branches needs guidance=")
         if prompt is not None:
             return self._generate_prompted(prompt, prompt_len, prefill, no_prefill, mask_u8, T, temperature, top_k, noise, seed,
                                            return_logits, n_samples, return_scores)
@@ -346,6 +364,36 @@ class Engine:
             first, last = scored_columns(T, tokens.shape[1], mask_u8.sum(1, dtype=torch.int32), plen)
             out += (op_seq_logprob(lg, tokens, first, last, rows_per_clip=n_samples),)
         return out if len(out) > 1 else out[0]
+
+    def _generate_guided(self, scale, start, prompt, prompt_len, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples,
+                         return_scores, return_branches):
+        if n_samples != 1:
+            raise L.DimxError("generate(guidance=): one sample per clip (n_samples = %d)" % n_samples)
+        if prompt is None:
+            prompt = start.reshape(-1, 1)
+        B, Pmax = prompt.shape
+        prompt = prompt.to(torch.int32).contiguous()
+        prompt_len = prompt_len.to(torch.int32).contiguous() if prompt_len is not None else None
+        n, V = self.n_gen(T), self.dims.num_tokens
+        if noise is not None:
+            noise = noise.to(torch.float32).contiguous()
+            assert tuple(noise.shape) == (n, B, V)
+        self._chk(prompt, prompt_len, mask_u8, noise)
+        tokens = torch.empty(B, n, dtype=torch.int32, device=self.device)
+        lg = torch.empty(B, n, V, dtype=torch.float32, device=self.device) if (return_logits or return_scores) else None
+        br = torch.empty(2, B, n, V, dtype=torch.float32, device=self.device) if return_branches else None
+        # the workspace the context was built in (guided=True), never grown here: that would drop the context
+        ws, wsb = self.workspace(B, T, 1)
+        L.check(self.lib.dimx_generate_guided(self.h, L.ptr(prompt), int(prompt.stride(0)), L.ptr(prompt_len), int(Pmax), L.ptr(mask_u8), B, T,
+                                              scale, float(temperature), int(top_k), L.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              L.ptr(tokens), L.ptr(lg), L.ptr(br), ws, wsb, self._s()), "dimx_generate_guided")
+        plen = None
+        if return_scores and Pmax > 1:
+            plen = prompt_len.clamp(1, Pmax) if prompt_len is not None else torch.full((B,), Pmax, dtype=torch.int32, device=self.device)
+        out = self._generated(tokens, lg, mask_u8, T, 1, plen, return_logits, return_scores)
+        if return_branches:
+            out = (out if isinstance(out, tuple) else (out,)) + (br,)
+        return out
 
     def _generate_prompted(self, prompt, prompt_len, prefill, no_prefill, mask_u8, T, temperature, top_k, noise, seed,
                            return_logits, n_samples, return_scores=False):
@@ -961,6 +1009,26 @@ def op_sample(logits, top_k=52, temperature=1.0, noise=None, seed=0, step=0, fil
     L.check(lib.dimx_op_sample(L.ptr(logits.contiguous()), R, top_k, float(temperature), L.ptr(noise), int(seed),
                                int(step), L.ptr(tok), L.stream_ptr(logits.device)), "dimx_op_sample")
     return tok
+
+
+def op_sample_guided(cond, uncond, scale, top_k=52, temperature=1.0, noise=None, seed=0, step=0, filter_logits_fn=None,
+                     filter_kwargs=None, return_guided=True):
+    """One guided sampler launch (dimx_op_sample_guided; the definition is dimx.guidance): cond / uncond [R,512], or
+    [nslab,R,512] split slabs that the kernel adds in slab order; the other arguments as ``op_sample``.  Returns tokens [2R]
+    (row r again at r + R: what the guided step feeds its unconditional half) and, with ``return_guided``, the guided logits
+    [R,512] the kernel sampled from."""
+    lib = L.load()
+    assert cond.shape == uncond.shape and cond.dtype == torch.float32 and uncond.dtype == torch.float32
+    cond, uncond = cond.contiguous(), uncond.contiguous()
+    nslab = cond.shape[0] if cond.dim() == 3 else 1
+    R = cond.shape[-2]
+    kind, top_k, fa, fb = sampling.resolve(filter_logits_fn, filter_kwargs, top_k)
+    tok = torch.empty(2 * R, dtype=torch.int32, device=cond.device)
+    g = torch.empty(R, 512, dtype=torch.float32, device=cond.device) if return_guided else None
+    L.check(lib.dimx_op_sample_guided(L.ptr(cond), L.ptr(uncond), R, nslab, R * 512, float(scale), kind, int(top_k), fa, fb,
+                                      float(temperature), L.ptr(noise), int(seed), int(step), L.ptr(tok), L.ptr(g),
+                                      L.stream_ptr(cond.device)), "dimx_op_sample_guided")
+    return (tok, g) if return_guided else tok
 
 
 def op_chain(x, gamma, a1=None, w1=None, slabs=None, w2=None):

@@ -93,6 +93,9 @@ SIGNATURES = {
                                        c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dimx_generate_beam": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
+    "dimx_workspace_bytes_guided": (c_size_t, [c_void_p, c_int, c_int]),
+    "dimx_generate_guided": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p,
+                                     c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dimx_train_num_params": (c_int, [c_void_p]),
     "dimx_train_total": (c_int64, [c_void_p]),
     "dimx_train_param_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),
@@ -102,6 +105,8 @@ SIGNATURES = {
     "dimx_train_graph_stats": (c_int, [c_void_p, c_void_p]),
     "dimx_set_train_lookahead": (c_int, [c_void_p, c_int, c_int]),
     "dimx_train_lookahead": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "dimx_set_train_cond_keep": (c_int, [c_void_p, c_void_p]),
+    "dimx_train_cond_keep": (c_int, [c_void_p, POINTER(c_void_p)]),
     "dimx_train_legacy_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "dimx_train_legacy_forward_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -240,6 +245,8 @@ SIGNATURES = {
     "dimx_op_beam_reorder": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
+    "dimx_op_sample_guided": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_long, c_float, c_int, c_int, c_float, c_float, c_float,
+                                      c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "dimx_op_sample_filtered": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_uint64, c_uint64,
                                         c_void_p, c_void_p, c_void_p]),
 }

@@ -133,14 +133,22 @@ class SLMFT(_EngineOwner):
         """reference :431-442 -> x_s [B,T,384] (rows of padded frames are unspecified)."""
         return self.engine(v_speaker.device).encode_speaker(v_speaker, self._mask8(mask.bool()))
 
-    def _build_context(self, eng, x_s, v_speaker, x_a, m8, for_generate, n_samples=1, prompt_frames=1):
+    def _build_context(self, eng, x_s, v_speaker, x_a, m8, for_generate, n_samples=1, prompt_frames=1, guided=False):
         # x_s given (the reference's call shape): context straight from it; x_s None + v_speaker: the fused stage that
         # keeps the encoder output inside the workspace (what forward() uses)
         if x_s is not None:
-            eng.set_context(x_s, x_a, which_patch=0, for_generate=for_generate, n_samples=n_samples, prompt_frames=prompt_frames)
+            eng.set_context(x_s, x_a, which_patch=0, for_generate=for_generate, n_samples=n_samples, prompt_frames=prompt_frames,
+                            guided=guided)
         else:
             assert v_speaker is not None, "forward_decoder needs x_s (reference call) or v_speaker= (fused path)"
-            eng.encode_ctx(v_speaker, x_a, m8, for_generate, n_samples=n_samples, prompt_frames=prompt_frames)
+            eng.encode_ctx(v_speaker, x_a, m8, for_generate, n_samples=n_samples, prompt_frames=prompt_frames, guided=guided)
+
+    def _null_context(self, eng, B, T, x_a):
+        """the null context of dimx.guidance: zero rows after the concat [x + patch_embed_dec_s | audio] -- x = -patch_embed_dec_s
+        (x + p is then exactly 0) and zero audio features"""
+        p = self.state_dict()["patch_embed_dec_s"].detach().to(x_a.device, torch.float32)
+        eng.set_context((-p).reshape(1, 1, -1).expand(B, T, -1).contiguous(), torch.zeros_like(x_a, dtype=torch.float32), which_patch=0,
+                        for_generate=False)
 
     @staticmethod
     def _user_seed(seed):
@@ -153,7 +161,7 @@ class SLMFT(_EngineOwner):
     @torch.no_grad()
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
                         seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False, beam_width=0, lookahead=None, window_prefill=False):
+                        filter_kwargs=None, return_scores=False, beam_width=0, lookahead=None, window_prefill=False, guidance=None):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -177,7 +185,14 @@ class SLMFT(_EngineOwner):
         ``lookahead`` L (mode 'val', no beam search): online generation (dimx.online) -- the step that produces frame t+1 sees the
         speaker frames below clamp(t + 2 + L, 1, T) only; a prompt then runs through forced decode steps instead of a prefill,
         unless ``window_prefill`` asks for the prefill under the window (``Engine.generate(prefill="window")``; same definition,
-        other kernels).  None: the whole clip is visible, as in the reference."""
+        other kernels).  None: the whole clip is visible, as in the reference.
+
+        ``guidance`` s (mode 'val', one sample per clip, no beam search): classifier-free guidance (dimx.guidance,
+        ``Engine.generate(guidance=s)``) -- every step samples from cond + (s - 1) * (cond - uncond), uncond being the decoder
+        without a context.  A prompt then runs through forced decode steps; scores are taken under the guided logits.  None
+        is the call without the argument, launch for launch."""
+        if guidance is not None and (mode != "val" or beam_width or int(n_samples) != 1):
+            raise ValueError("guidance applies to mode='val' with one sample per clip and without beam search")
         if beam_width and (mode != "val" or int(n_samples) != int(beam_width)):
             raise ValueError("beam_width applies to mode='val' with n_samples == beam_width")
         if lookahead is not None and (mode != "val" or beam_width):
@@ -199,7 +214,10 @@ class SLMFT(_EngineOwner):
             n_valid = (z_l[:, 1:] != -100).sum().clamp(min=1)
             return row_loss.sum() / n_valid, logits
         plen, p0 = prompt_lengths(mask, prompt_frames, lengths) if prompt_frames > 1 else (None, 1)
-        self._build_context(eng, x_s, v_speaker, x_a, m8, True, n_samples=n_samples, prompt_frames=p0)
+        gkw = {}
+        if guidance is not None:      # the guided step forces the whole prompt: no prefill scratch, 2B rows of self-attention caches
+            p0, gkw = 1, {"guidance": float(guidance)}
+        self._build_context(eng, x_s, v_speaker, x_a, m8, True, n_samples=n_samples, prompt_frames=p0, guided=guidance is not None)
         if beam_width:
             from .scoring import SeqScores, scored_columns
             tokens, score = eng.generate_beam(z_l[:, 0], m8, T, int(beam_width), prompt=z_l[:, :prompt_frames] if prompt_frames > 1 else None,
@@ -219,11 +237,11 @@ class SLMFT(_EngineOwner):
                                prompt=z_l[:, :prompt_frames], prompt_len=plen,
                                prefill=("window", p0) if (window_prefill and lookahead is not None) else p0,
                                filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
-                               lookahead=lookahead)
+                               lookahead=lookahead, **gkw)
         else:
             out = eng.generate(z_l[:, 0], m8, T, temperature, 52, noise, seed_v, n_samples=n_samples,
                                filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
-                               lookahead=lookahead)
+                               lookahead=lookahead, **gkw)
         if return_scores:
             return 0.0, out[0].long(), out[1]
         return 0.0, out.long()
@@ -282,7 +300,8 @@ class SLMFT(_EngineOwner):
         self.listener_vq.eval()
         return self
 
-    def _forward_autograd(self, v_speaker, v_listener, v_audio, mask, kv_mask=None, z_l=None, return_tokens=False, lookahead=None):
+    def _forward_autograd(self, v_speaker, v_listener, v_audio, mask, kv_mask=None, z_l=None, return_tokens=False, lookahead=None,
+                          cond_keep=None):
         """mode='train' with a graph: differentiable cross entropy (dimx.train.slmft_loss on this module's own
         parameters); listener codes and decoded motion come from the HIP engine without a graph.
         ``lookahead`` L: online fine-tuning -- the decoder's cross attention of row t sees the context rows below
@@ -300,7 +319,7 @@ class SLMFT(_EngineOwner):
             kv_mask = None
         P = dict(self.named_parameters())
         l_ce_l, logits = T.slmft_loss(P, self.s2s, v_speaker.float(), v_audio.float(), mask, z_l.long(),
-                                      kv_mask.bool() if kv_mask is not None else None, lookahead=lookahead)
+                                      kv_mask.bool() if kv_mask is not None else None, lookahead=lookahead, cond_keep=cond_keep)
         pred, l_cont_l = None, torch.zeros((), device=v_speaker.device)
         if on_gpu:     # the continuous loss has no gradient path in the reference either (argmax -> one-hot, :454-464)
             with torch.no_grad():
@@ -316,7 +335,8 @@ class SLMFT(_EngineOwner):
     def forward(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                 return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False):
+                filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False,
+                guidance=None):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
@@ -339,7 +359,12 @@ class SLMFT(_EngineOwner):
         ``lookahead`` L (mode 'val', no beam search): online generation (dimx.online; ``forward_decoder``) -- the listener token of
         frame t+1 is drawn from the speaker frames below clamp(t + 2 + L, 1, T).  The tokens are causal in the speaker; ``pred`` is
         still the VQ decoder's rendering of the whole token sequence.  ``window_prefill`` (with ``prompt_frames`` and ``lookahead``): the
-        prompt is prefilled in one pass under the window instead of running through forced decode steps (``forward_decoder``)."""
+        prompt is prefilled in one pass under the window instead of running through forced decode steps (``forward_decoder``).
+
+        ``guidance`` s (mode 'val', ``n_samples`` 1, no beam search): classifier-free guidance (dimx.guidance; ``forward_decoder``):
+        s = 1 is the model, s > 1 makes the listener more reactive to the speaker, s = 0 generates from the listener's prior."""
+        if guidance is not None and (mode != "val" or beam_width is not None or int(n_samples) != 1):
+            raise ValueError("guidance applies to mode='val' with one sample per clip and without beam search")
         if lookahead is not None and (mode != "val" or beam_width is not None):
             raise ValueError("lookahead applies to mode='val' without beam search")
         if beam_width is not None:
@@ -360,13 +385,14 @@ class SLMFT(_EngineOwner):
                                         n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths,
                                         filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
                                         beam_width=beam_width, num_return=num_return, lookahead=lookahead,
-                                        window_prefill=window_prefill)
+                                        window_prefill=window_prefill, guidance=guidance)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                         return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
-                        filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False):
+                        filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False,
+                        guidance=None):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -387,7 +413,7 @@ class SLMFT(_EngineOwner):
                                                          n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
                                                          filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs,
                                                          return_scores=return_scores, beam_width=W, lookahead=lookahead,
-                                                         window_prefill=window_prefill)
+                                                         window_prefill=window_prefill, guidance=guidance)
         finally:
             eng.set_shard(0, 0)
         if W and int(num_return) == 1:    # the best hypothesis is row 0 of its clip
@@ -436,7 +462,7 @@ class SLMFT(_EngineOwner):
             return l_ce_l + l_cont_l, d, pred
 
     @torch.no_grad()
-    def score(self, v_speaker, v_listener, v_audio, mask, z_l=None, lookahead=None, one_pass=False):
+    def score(self, v_speaker, v_listener, v_audio, mask, z_l=None, lookahead=None, one_pass=False, context=None):
         """Teacher-forced log-likelihood of the clip's own listener codes (``forward_vq`` of ``v_listener``) or of given codes
         ``z_l`` [B,T] under the model: one ``decode_tf`` pass with NO random key mask, then dimx_op_seq_logprob on its logits with the
         tokens ``z_l[:, 1:]`` over the columns inside each clip's length -> dimx.scoring.SeqScores [B] (score f64, count int32).
@@ -446,7 +472,15 @@ class SLMFT(_EngineOwner):
         speaker frames below clamp(t + 2 + L, 1, T).  The logits then come from a generation whose every token is forced to ``z_l``
         (a prompt of T-1 tokens through decode steps, no prefill), scored over the same columns.  ``one_pass=True`` takes them from
         one teacher-forced pass under the window instead (``decode_tf(lookahead=L)``, dimx_decode_tf_win): the same definition through
-        other kernels, so the same score within the decode steps' tolerance, not the same bits."""
+        other kernels, so the same score within the decode steps' tolerance, not the same bits.
+
+        ``context="null"``: the same codes under the null context of dimx.guidance (zero rows after the concat: the decoder
+        without its cross sublayers, the listener's prior) -- host code only, ``set_context`` with zero rows and ``decode_tf``.
+        Not with ``lookahead`` (a window over zero rows is the same zero rows)."""
+        if context not in (None, "null"):
+            raise ValueError("score(context=%r): None or 'null'" % (context,))
+        if context == "null" and lookahead is not None:
+            raise ValueError("score(context='null') takes no lookahead")
         from .engine import op_seq_logprob
         from .scoring import scored_columns
         with self.engine_pinned():
@@ -464,10 +498,24 @@ class SLMFT(_EngineOwner):
                     _, logits = eng.generate(None, m8, T, 0.0, 52, None, 0, return_logits=True, prompt=z_l[:, :T - 1], prefill=1,
                                              no_prefill=True, lookahead=lookahead)
             else:
-                self._build_context(eng, None, v_speaker, v_audio, m8, False)
+                if context == "null":
+                    self._null_context(eng, mask.shape[0], T, v_audio)
+                else:
+                    self._build_context(eng, None, v_speaker, v_audio, m8, False)
                 logits, _, _ = eng.decode_tf(z_l, m8, None)
             first, last = scored_columns(T, T - 1, mask.sum(1, dtype=torch.int32))
             return op_seq_logprob(logits, z_l[:, 1:], first, last)
+
+    @torch.no_grad()
+    def pmi(self, v_speaker, v_listener, v_audio, mask, z_l=None):
+        """Per-clip pointwise mutual information between the speaker context and the clip's own listener codes (or given codes
+        ``z_l``), per counted token: ``dimx.guidance.pmi(score(...), score(..., context="null"))`` -> float64 numpy [B].  How much
+        the speaker explains this listener under the model; 0 for a model that ignores its context."""
+        from . import guidance
+        if z_l is None:
+            _, z_l = self.forward_vq(v_speaker, v_listener, mask.bool(), with_speaker=False)
+        return guidance.pmi(self.score(v_speaker, v_listener, v_audio, mask, z_l=z_l),
+                            self.score(v_speaker, v_listener, v_audio, mask, z_l=z_l, context="null"))
 
 
 class SLM(_EngineOwner):

@@ -112,17 +112,21 @@ def online_cross_mask(mask, lookahead):
     return (torch.arange(T, device=mask.device)[None, :] < vis[:, None])[None] & mask.bool()[:, None, :]
 
 
-def slmft_loss(P, dims, v_speaker, v_audio, mask, z_l, kv_mask=None, lookahead=None):
+def slmft_loss(P, dims, v_speaker, v_audio, mask, z_l, kv_mask=None, lookahead=None, cond_keep=None):
     """Differentiable l_ce_l of SLMFT.forward(mode='train').  P: {key: tensor} (parameters carry the graph); z_l [B,T]
     listener codes with -100 on padding (from the frozen VQ-VAE); kv_mask [B,T-1] keep-mask (AutoregressiveWrapper's
     mask_prob draw) or None.  lookahead: an integer L trains under the visibility of an online generation (``online_cross_mask``
     on the decoder's cross attention; the checker of dimx_set_train_lookahead), None = the reference's offline step.
+    cond_keep [B] (bool or 0/1; ``dimx.guidance.cond_keep``): condition dropout -- a clip with keep = 0 is trained under the null
+    context (zero rows after the concat, no rescaling) and sends no gradient into its context; None = every clip keeps its own.
     Returns (loss, logits)."""
     x = v_speaker + P["patch_embed_s"]
     x = xt_encoder(P, "encoder_s.", x, mask, True, dims.enc_depth, dims.heads)
     x = xt_encoder(P, "encoder_joint.", x, mask, True, dims.enc_depth, dims.heads)
     x_s = _ln(x, P["norm_s.weight"], P["norm_s.bias"])
     ctx = torch.cat([x_s + P["patch_embed_dec_s"], v_audio], dim=-1)
+    if cond_keep is not None:
+        ctx = ctx * torch.as_tensor(cond_keep, device=ctx.device).to(ctx.dtype)[:, None, None]
     inp = z_l[:, :-1].clamp(min=0)                                   # pad_value 0 where the target is ignored
     cam = None if lookahead is None else online_cross_mask(mask, lookahead)[:, None]
     logits = xt_decoder_logits(P, "decoder_joint.net.", inp, ctx, mask, kv_mask, dims.dec_depth, dims.heads, cross_attn_mask=cam)

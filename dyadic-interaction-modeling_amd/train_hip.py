@@ -28,11 +28,19 @@ class HipTrainer:
     _LOSS_FLOATS = 2                             # floats the step writes to loss_out
     _UNGRAPHED = None                            # name of a step that is launched kernel by kernel (no graph_stats)
 
-    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=1.0, device=None, lookahead=None):
+    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, clip=1.0, device=None, lookahead=None,
+                 cond_drop=0.0, seed=20260928):
         """AdamW defaults are torch.optim.AdamW's (the reference passes only lr, code/finetune_s2s_pretrain.py:119).
-        lookahead: online fine-tuning (``set_lookahead``); None = the offline step of the reference."""
+        lookahead: online fine-tuning (``set_lookahead``); None = the offline step of the reference.
+        cond_drop: condition dropout (dimx_set_train_cond_keep; the definition is dimx.guidance): every step trains each clip under
+        the null context with this probability, drawn by ``dimx.guidance.cond_keep(seed, step, B, cond_drop)``; 0 = off, the
+        plain step launch for launch.  Only the SLMFT step (this class itself) takes it."""
         self.model = model
         self.lookahead = None
+        self.cond_drop, self.cond_seed = float(cond_drop), int(seed)   # not .seed: the VQ-VAE trainer's dropout seed is a subclass's
+        self._keep = None
+        if self.cond_drop > 0 and type(self) is not HipTrainer:
+            raise L.DimxError("cond_drop: only the SLMFT fine-tuning step (HipTrainer) takes condition dropout")
         self.device = torch.device(device if device is not None else next(model.parameters()).device)
         if self.device.type != "cuda":
             raise L.DimxError("HipTrainer needs the module on a ROCm GPU (model.to('cuda:0')); there is no CPU path")
@@ -220,6 +228,20 @@ class HipTrainer:
         la = self.lookahead
         L.check(self.lib.dimx_set_train_lookahead(self.eng.h, 0 if la is None else 1, 0 if la is None else la), "dimx_set_train_lookahead")
 
+    def _apply_cond_keep(self, B, cond_keep):
+        """the step's keep vector: the given one ([B] bool / 0-1), else this step's draw when ``cond_drop`` > 0, else off.  It lives
+        in one persistent device vector: its address keys the captured step, its contents do not."""
+        if cond_keep is None and self.cond_drop > 0:
+            from . import guidance
+            cond_keep = guidance.cond_keep(self.cond_seed, self.step_count, B, self.cond_drop)
+        if cond_keep is None:
+            L.check(self.lib.dimx_set_train_cond_keep(self.eng.h, None), "dimx_set_train_cond_keep")
+            return
+        if self._keep is None or self._keep.numel() < B:
+            self._keep = torch.ones(max(B, 256), dtype=torch.uint8, device=self.device)
+        self._keep[:B].copy_(torch.as_tensor(cond_keep).reshape(B).to(torch.uint8), non_blocking=True)
+        L.check(self.lib.dimx_set_train_cond_keep(self.eng.h, L.ptr(self._keep)), "dimx_set_train_cond_keep")
+
     def graph_stats(self):
         """(steps replayed from the captured hipGraph, steps launched kernel by kernel, nodes of the captured graph)"""
         if self._UNGRAPHED:
@@ -228,8 +250,10 @@ class HipTrainer:
         L.check(self.lib.dimx_train_graph_stats(self.eng.h, ctypes.cast(out, ctypes.c_void_p)), "dimx_train_graph_stats")
         return int(out[0]), int(out[1]), int(out[2])
 
-    def forward_backward(self, v_speaker, v_listener, v_audio, mask, kv_mask=None, z_l=None, return_logits=False, _alias_logits=False):
+    def forward_backward(self, v_speaker, v_listener, v_audio, mask, kv_mask=None, z_l=None, return_logits=False, _alias_logits=False,
+                         cond_keep=None):
         """loss (0-dim device tensor, mean cross entropy over the valid listener codes) and the gradients in ``self.grads``.
+        cond_keep: [B] keep flags of the condition dropout for this step (None: the trainer's own draw, or off).
         kv_mask: keep-mask [B,T-1] of the mask_prob draw; None draws one like the reference, False disables it.
         return_logits: a tensor of the caller's own (the step writes into a staging buffer that the next call with the same (B, T)
         overwrites -- possibly from a hipGraph replay; only train_step, which consumes the logits at once, takes the alias)."""
@@ -258,6 +282,7 @@ class HipTrainer:
         logits = st["logits"]() if return_logits else None
         ws, wsb = self._workspace(B, T)
         self._apply_lookahead()
+        self._apply_cond_keep(B, cond_keep)
         L.check(self.lib.dimx_train_forward_backward(self.eng.h, L.ptr(self.params), L.ptr(self.grads), L.ptr(v_s), L.ptr(v_a),
                                                      L.ptr(m8), L.ptr(z32), L.ptr(kv8), B, T, L.ptr(self._loss), L.ptr(logits), ws,
                                                      wsb, L.stream_ptr(self.device)), "dimx_train_forward_backward")

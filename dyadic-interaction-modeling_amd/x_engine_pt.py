@@ -210,7 +210,8 @@ def _select(pending, skip_degenerate, world, device):
 
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
-                        select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, window_prefill=False, **forward_kw):
+                        select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, window_prefill=False, guidance=None,
+                        **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -270,7 +271,17 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
     t+1 is drawn from the speaker frames below clamp(t + 2 + L, 1, T).  Selection, metrics and the returned lists are unchanged.
     None (default) is the reference's offline protocol.  Not with ``decode="beam"`` (ValueError).  ``window_prefill`` (with
     ``prompt_frames`` and ``lookahead``): the prompts are prefilled in one pass under the window instead of running through forced
-    decode steps (``SLMFT.forward(window_prefill=True)``)."""
+    decode steps (``SLMFT.forward(window_prefill=True)``).
+
+    ``guidance`` s: every generation is a guided one (dimx.guidance, ``SLMFT.forward(guidance=s)``).  A guided generation draws one
+    sample per clip, so the ``beam_size`` tries are ``beam_size`` passes (the reference's loop) and ``select`` must be "fd"; not with
+    ``decode="beam"`` (ValueError).  None (default) leaves every path as it is."""
+    if guidance is not None:
+        if decode == "beam" or select != "fd":
+            raise ValueError("evaluate_test_epoch(guidance=...) applies to decode='sample' with select='fd': a guided generation "
+                             "draws one sample per clip")
+        batched_samples = False
+        forward_kw = dict(forward_kw, guidance=float(guidance))
     if decode not in ("sample", "beam"):
         raise ValueError("decode=%r: one of 'sample', 'beam'" % (decode,))
     if lookahead is not None:
@@ -778,7 +789,7 @@ def _train_epoch_hip(model, loader, trainer, device, scheduler, print_freq, epoc
 
 
 def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, print_freq=2000, epoch=0, log=print, backward="auto",
-                lookahead=None):
+                lookahead=None, cond_drop=None, seed=20260928):
     """reference code/x_engine_pt.py:9-60: one pass over the loader with zero_grad / forward(mode='train') / backward /
     clip / step (``clip`` None = the reference's default 0., no clipping).
 
@@ -795,15 +806,24 @@ def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, pri
     ``lookahead`` L (SLMFT only): online fine-tuning -- every step trains under the visibility of an online generation with the
     same L (dimx.online: decoder row t sees the context rows below clamp(t + 2 + L, 1, T)), on the HIP step
     (``HipTrainer.set_lookahead``) and on the autograd route (``dimx.train.slmft_loss(lookahead=L)``) alike.  None: the
-    reference's offline step; a ``HipTrainer`` passed as ``optimizer`` then keeps its own setting."""
+    reference's offline step; a ``HipTrainer`` passed as ``optimizer`` then keeps its own setting.
+
+    ``cond_drop`` p (SLMFT only): condition dropout for classifier-free guidance (dimx.guidance) -- every step trains each clip under
+    the null context with probability p, drawn by ``dimx.guidance.cond_keep(seed, step, B, p)``: on the HIP step
+    (``HipTrainer(cond_drop=)``, dimx_set_train_cond_keep) and on the autograd route (``dimx.train.slmft_loss(cond_keep=)``) alike.
+    None: a ``HipTrainer`` passed as ``optimizer`` keeps its own setting, every other route trains without it."""
     from .seq2seq_pretrain import SLMFT
     from .train_hip import HipTrainer
     inner = getattr(model, "module", model)
     if lookahead is not None and not isinstance(inner, SLMFT):
         raise L.DimxError("train_epoch(lookahead=...): online fine-tuning is built for SLMFT, not %s" % type(inner).__name__)
+    if cond_drop is not None and not isinstance(inner, SLMFT):
+        raise L.DimxError("train_epoch(cond_drop=...): condition dropout is built for SLMFT, not %s" % type(inner).__name__)
     if isinstance(optimizer, HipTrainer):
         if lookahead is not None:
             optimizer.set_lookahead(lookahead)
+        if cond_drop is not None:
+            optimizer.cond_drop, optimizer.cond_seed = float(cond_drop), int(seed)
         return _train_epoch_hip(model, loader, optimizer, device, scheduler, print_freq, epoch, log, clip=clip)
     if backward not in ("auto", "hip", "autograd"):
         raise ValueError("backward must be 'auto', 'hip' or 'autograd'")
@@ -812,6 +832,7 @@ def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, pri
         if tr is not None:
             if type(tr) is HipTrainer:        # the cached stand-in follows this call's argument, None included
                 tr.set_lookahead(lookahead)
+                tr.cond_drop, tr.cond_seed = float(cond_drop or 0.0), int(seed)
             return _train_epoch_hip(model, loader, tr, device, scheduler, print_freq, epoch, log,
                                     clip=0.0 if clip is None else clip, optimizer=optimizer)
         if backward == "hip":
@@ -837,10 +858,16 @@ def train_epoch(model, loader, optimizer, device, scheduler=None, clip=None, pri
     for i, batch in enumerate(loader):
         src_s_v, src_s_a, tgt, mask, _, _ = _prepare(batch, device)
         optimizer.zero_grad()
-        if lookahead is None:
+        if lookahead is None and not cond_drop:
             loss, d_step, _ = model(src_s_v, tgt, src_s_a, mask, mode="train")
         else:      # the windowed teacher-forced pass exists with a graph only (SLMFT.forward keeps lookahead for mode='val')
-            loss, d_step, _ = inner._forward_autograd(src_s_v, tgt, src_s_a, mask, lookahead=int(lookahead))
+            keep = None
+            if cond_drop:
+                from .guidance import cond_keep
+                step = (epoch * len(loader) if hasattr(loader, "__len__") else 0) + i
+                keep = torch.from_numpy(cond_keep(seed, step, mask.shape[0], cond_drop)).to(device)
+            loss, d_step, _ = inner._forward_autograd(src_s_v, tgt, src_s_a, mask, lookahead=None if lookahead is None else int(lookahead),
+                                                      cond_keep=keep)
         loss.mean().backward()
         T.all_reduce_grads(params)
         if clip > 0:

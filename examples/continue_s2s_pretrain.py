@@ -55,6 +55,9 @@ def main():
     ap.add_argument("--window-prefill", action="store_true",
                     help="with --lookahead: prefill the prompt in one teacher-forced pass under the window instead of running it through "
                          "forced decode steps (the same definition through other kernels)")
+    ap.add_argument("--guidance", type=float, default=None,
+                    help="classifier-free guidance scale s (dimx.guidance): every step samples from cond + (s - 1) * (cond - uncond); the prompt "
+                         "then runs through forced decode steps.  One sample per clip and pass, --select fd only")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     if args.window_prefill and args.lookahead is None:
@@ -84,7 +87,7 @@ def main():
                                                         prompt_frames=args.prompt_frames, select=args.select,
                                                         consensus_distance=args.consensus_distance, decode=args.decode,
                                                         beam_width=args.beam_width, lookahead=args.lookahead,
-                                                        window_prefill=args.window_prefill, **sampler)
+                                                        window_prefill=args.window_prefill, guidance=args.guidance, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     print_metrics(y_true, y_pred, x)

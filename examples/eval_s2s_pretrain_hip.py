@@ -29,6 +29,7 @@ import dimx  # noqa: E402,F401
 from dimx import lib as L  # noqa: E402
 from dimx.dataset.data_loader import get_vico_dataloaders  # noqa: E402
 from dimx.metrics import ListenerMetrics  # noqa: E402
+from dimx.guidance import pmi  # noqa: E402
 from dimx.scoring import SeqScores, perplexity  # noqa: E402
 from dimx.seq2seq_pretrain import SLMFT  # noqa: E402
 from dimx import sampling  # noqa: E402
@@ -57,6 +58,10 @@ def main():
     ap.add_argument("--lookahead", type=int, default=None,
                     help="online generation: the token of frame t+1 is drawn from the speaker frames below t + 2 + L (0: up to the frame being "
                          "produced, < 0: a reaction delay, > 0: a look-ahead buffer; default: the whole clip is visible, as in the reference)")
+    ap.add_argument("--guidance", type=float, default=None,
+                    help="classifier-free guidance scale s: every step samples from cond + (s - 1) * (cond - uncond), uncond being the decoder "
+                         "without the speaker context (1: the model; > 1: more reactive to the speaker; 0: the listener's prior).  One sample "
+                         "per clip and pass, --select fd only")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -79,17 +84,22 @@ def main():
     t0 = time.time()
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc,
                                                         select=args.select, consensus_distance=args.consensus_distance,
-                                                        decode=args.decode, beam_width=args.beam_width, lookahead=args.lookahead, **sampler)
+                                                        decode=args.decode, beam_width=args.beam_width, lookahead=args.lookahead,
+                                                        guidance=args.guidance, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
-    parts, parts_online = [], []
+    parts, parts_online, parts_null = [], [], []
     for batch in dataset["valid"]:      # teacher-forced: what the model thinks of the ground-truth listener codes
         src_s_v, src_s_a, tgt, mask, _, _ = _prepare(batch, device)
         parts.append(model.score(src_s_v, tgt, src_s_a, mask))
+        parts_null.append(model.score(src_s_v, tgt, src_s_a, mask, context="null"))   # the same codes without the speaker
         if args.lookahead is not None:  # the same codes with the speaker's future withheld
             parts_online.append(model.score(src_s_v, tgt, src_s_a, mask, lookahead=args.lookahead))
     gt = SeqScores(torch.cat([p.score for p in parts]), torch.cat([p.count for p in parts]))
     print("perplexity of the ground-truth listener codes: %.3f over %d tokens" % (perplexity(gt), int(gt.count.sum())))
+    null = SeqScores(torch.cat([p.score for p in parts_null]), torch.cat([p.count for p in parts_null]))
+    print("  under the null context: %.3f; mean PMI of the speaker context and these codes: %.4f nats per token"
+          % (perplexity(null), float(pmi(gt, null).mean())))
     if parts_online:
         on = SeqScores(torch.cat([p.score for p in parts_online]), torch.cat([p.count for p in parts_online]))
         print("perplexity of the ground-truth listener codes, online with lookahead %d: %.3f (offline %.3f)"

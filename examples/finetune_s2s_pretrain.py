@@ -77,16 +77,16 @@ def speaker_main(args):
                 print("saved %s" % out)
 
 
-def validation_perplexity(model, loader, device, lookahead=None):
+def validation_perplexity(model, loader, device, lookahead=None, context=None):
     """teacher-forced perplexity of the validation clips' own listener codes, offline (lookahead None) or under the visibility of
-    an online generation (SLMFT.score)"""
+    an online generation, or under the null context of dimx.guidance (context "null": the decoder without the speaker) (SLMFT.score)"""
     from dimx.scoring import SeqScores, perplexity
     from dimx.x_engine_pt import _prepare
     model.eval()
     score, count = [], []
     for batch in loader:
         src_s_v, src_s_a, tgt, mask, _, _ = _prepare(batch, device)
-        sc = model.score(src_s_v, tgt, src_s_a, mask, lookahead=lookahead)
+        sc = model.score(src_s_v, tgt, src_s_a, mask, lookahead=lookahead, context=context)
         score.append(sc.score.cpu())
         count.append(sc.count.cpu())
     return perplexity(SeqScores(torch.cat(score), torch.cat(count))) if score else float("nan")
@@ -110,7 +110,13 @@ def main():
     ap.add_argument("--lookahead", type=int, default=None,
                     help="listener mode: fine-tune under the visibility of an online generation with this look-ahead "
                          "(0: the frame being produced and its past; negative: a reaction delay; default: offline, the reference)")
+    ap.add_argument("--cond-drop", type=float, default=None,
+                    help="listener mode: condition dropout for classifier-free guidance -- every step trains each clip without its speaker "
+                         "context with this probability (dimx.guidance.cond_keep); the validation perplexity under the null context is printed "
+                         "next to the conditional one")
     args = ap.parse_args()
+    if args.mode == "speaker" and args.cond_drop is not None:
+        ap.error("--cond-drop applies to --mode listener: the DIM-Speaker step takes no condition dropout")
     if args.mode == "speaker" and args.lookahead is not None:
         ap.error("--lookahead applies to --mode listener: the DIM-Speaker step has no online window")
     if args.mode == "speaker":
@@ -131,7 +137,7 @@ def main():
     for epoch in range(args.epochs):
         loss = train_epoch(model, dataset["train"], optimizer, device, scheduler=None, clip=1.0, print_freq=100,
                            epoch=epoch, log=print if rank == 0 else (lambda *_: None), backward=args.backward,
-                           lookahead=args.lookahead)
+                           lookahead=args.lookahead, cond_drop=args.cond_drop)
         y_true, y_pred, x, _ = evaluate_finetune_epoch(model, dataset["valid"], device)
         if rank == 0:
             a, b = print_metrics(y_true, y_pred, x)
@@ -139,6 +145,10 @@ def main():
             if args.lookahead is not None:
                 print("epoch %d: validation perplexity under lookahead %d: %.3f (offline: %.3f)" % (
                     epoch, args.lookahead, validation_perplexity(model, dataset["valid"], device, args.lookahead),
+                    validation_perplexity(model, dataset["valid"], device)))
+            if args.cond_drop is not None:
+                print("epoch %d: validation perplexity under the null context: %.3f (conditional: %.3f)" % (
+                    epoch, validation_perplexity(model, dataset["valid"], device, context="null"),
                     validation_perplexity(model, dataset["valid"], device)))
             if a + b < best:
                 best = a + b

@@ -300,6 +300,30 @@ int dimx_generate_beam(dimx_handle h, const int32_t* prompt, int ld_prompt, cons
                        int32_t* backptr, float* logits_out, void* beam_state, size_t beam_state_bytes, int flags, void* ws, size_t ws_bytes,
                        void* stream);
 
+/* Classifier-free guidance: every step samples from g = c + (scale - 1) * (c - u), c the step's raw logits under the clip's context and
+ * u those of the same decoder WITHOUT a context (the definition is dimx/guidance.py).  Every cross-attention projection of
+ * the decoder is bias-free, so a context of zero rows makes each cross sublayer add exactly 0: the unconditional model is the decoder
+ * with its cross sublayers left out.  scale = 1 is dimx_generate's model (g is c bit for bit), scale > 1 makes the listener follow the
+ * speaker more closely, scale = 0 samples the listener's prior.  The sampler filter, the temperature and the noise act on g as they act
+ * on the raw logits elsewhere; the noise row and the generator counter are those of row b of a B-row generation.
+ * One decode step runs 2B rows: rows [0, B) conditional, rows [B, 2B) unconditional and fed the same tokens.  Projections, self
+ * attention, feed-forward and logits run at 2B rows, the cross sublayer on rows [0, B) only: the unconditional rows have no cross K/V
+ * and no launch reads cross K/V for them.  The step takes the one-kernel-per-op route (no chain or layer kernels); with
+ * dimx_set_cross_lookahead on, the conditional rows run under the window.  Call dimx_encode_ctx(for_generate = 1) first with the same
+ * B, T and ws; dimx_workspace_bytes_guided(h, B, T) sizes ws for both calls (2B self-attention caches, B cross caches; 0 = shape
+ * not supported).
+ *   prompt / ld_prompt / prompt_len / Pmax as in dimx_generate_prompted; the whole prompt goes through forced decode steps (P0 = 1;
+ *            Pmax = 1, ld_prompt = 1: prompt is start[B]).
+ *   tokens   [B, T-1] int32;  logits_out (optional) [B, T-1, 512] f32: every step's GUIDED logits;
+ *   branch_logits_out (optional) [2, B, T-1, 512] f32: every step's c, then every step's u.
+ * The scale lives in device memory: a call with another scale replays the captured step graphs.  Variant 0 (SLMFT) only, one sample
+ * per clip, no beam.  DIMX_ERR_ARG for a NaN or infinite scale, another variant or a bad prompt shape, DIMX_ERR_STATE while a streaming
+ * session is open, DIMX_ERR_WORKSPACE for a ws below dimx_workspace_bytes_guided; nothing is enqueued then. */
+size_t dimx_workspace_bytes_guided(dimx_handle h, int B, int T);
+int dimx_generate_guided(dimx_handle h, const int32_t* prompt, int ld_prompt, const int32_t* prompt_len, int Pmax, const uint8_t* ctx_mask,
+                         int B, int T, float scale, float temperature, int top_k, const float* exp_noise, uint64_t seed, int32_t* tokens,
+                         float* logits_out, float* branch_logits_out, void* ws, size_t ws_bytes, void* stream);
+
 /* In the bf16 mode dimx_generate runs part of the decode step as XCD-local chain kernels (B <= 256, one sample per clip,
  * 256-CU device) that rely on their 256 blocks being co-resident, one per CU.  They verify that and dimx_generate checks
  * their flags BEFORE it returns: with the chain path active the call therefore waits for its own generation to finish
@@ -483,6 +507,18 @@ int dimx_train_graph_stats(dimx_handle h, int64_t* out3);
 int dimx_set_train_lookahead(dimx_handle h, int on, int lookahead);
 /* The handle's current setting (either pointer may be NULL). */
 int dimx_train_lookahead(dimx_handle h, int* on, int* lookahead);
+/* Condition dropout (classifier-free guidance's training side; the definition is dimx/guidance.py): keep_dev [B] uint8 in device
+ * memory, NULL = off.  With a vector set, dimx_train_forward_backward trains clip b under the null context where keep_dev[b] == 0:
+ * its context rows are zeroed after the concat [x_s + patch_embed_dec_s | audio], before the cross K / V projections, and its rows
+ * of the context gradient are zeroed before they reach patch_embed_dec_s and the encoders.  A kept clip is unchanged: there is no
+ * rescaling, and a vector of ones gives the plain step bit for bit.
+ *   - The pointer is handle state of variant 0 only (DIMX_ERR_ARG on a handle of variant 1 or 2) and keys the captured step graph;
+ *     its CONTENTS are read on the device by the step, so a new draw in the same buffer replays the graph.  The buffer must hold B
+ *     entries of the steps that follow and stay valid while it is set.
+ *   - Both numeric modes and both launch paths.  The legacy, SLM, VQ-VAE, converter and speaker steps do not take it. */
+int dimx_set_train_cond_keep(dimx_handle h, const uint8_t* keep_dev);
+/* The handle's current vector (NULL while off). */
+int dimx_train_cond_keep(dimx_handle h, const uint8_t** keep_dev);
 /* The legacy generator's training step (reference loop code/x_engine.py:8-36 over ListenerGenerator.forward,
  * code/seq2seq.py:235-278): handle of variant 1.  The arenas follow dimx_train_param_info of that handle: generator.*, the
  * listener VQ-VAE's DECODER (listener_vq.decoder.*) and the listener-id conditioning (listener_embeddings.weight [100,256],
@@ -1056,6 +1092,15 @@ int dimx_op_sample(const float* logits, int R, int top_k, float temperature, con
 int dimx_op_sample_filtered(const float* logits, int R, int kind, int top_k, float a, float b, float temperature,
                             const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens, uint8_t* keep_out,
                             void* stream);
+/* The guided sampler (classifier-free guidance, dimx/guidance.py): row r is sampled from cond[r] + (scale - 1) * (cond[r] - uncond[r])
+ * formed in f32 (scale = 1: cond[r] bit for bit); filter, temperature, noise and generator as dimx_op_sample_filtered on an R-row
+ * launch.  cond / uncond: nslab slabs [R,512] each, slab_stride elements apart, added in slab order (nslab = 1: plain rows).
+ * tokens [2R]: the token of row r at r and again at r + R, as the guided decode step feeds both halves.  guided_out (optional,
+ * [R,512]): the guided rows.  DIMX_ERR_ARG for a NaN or infinite scale, invalid filter settings or slab arguments; nothing is
+ * enqueued then. */
+int dimx_op_sample_guided(const float* cond, const float* uncond, int R, int nslab, long slab_stride, float scale, int kind, int top_k,
+                          float a, float b, float temperature, const float* exp_noise, uint64_t seed, uint64_t step, int32_t* tokens,
+                          float* guided_out, void* stream);
 
 #ifdef __cplusplus
 }
