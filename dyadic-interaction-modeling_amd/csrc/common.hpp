@@ -394,6 +394,31 @@ struct DecodeAttnArgs {
 };
 int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
 
+// The cross form over an FP8 copy of the context K/V (decode_attn_kv8.hip; dimx/kv8.py): one query row per clip
+struct Kv8AttnArgs {
+    const float* q;        // f32 split-K slabs [nslab][B, q_ld], head h at h*64, summed in slab order
+    int q_ld, nslab;
+    long slab_stride;      // elements between slabs
+    const uint8_t* kcodes; // [B,H,Tmax,64] e4m3fn codes
+    const float* kscale;   // [B,H,Tmax]
+    const uint8_t* vcodes;
+    const float* vscale;
+    int Tmax;
+    void* out;             // [B, o_ld] of out_dtype
+    int out_dtype, o_ld;
+    int B, H;
+    int n_keys;
+    const uint8_t* kmask;  // [B, kmask_ld] optional
+    int kmask_ld;
+    float scale;
+    int force_nsplit;      // tests: waves per (clip, head) (0 = automatic)
+    int win, lookahead;    // the windowed form: keys j < clamp(*step + 2 + lookahead, 1, n_keys)
+    const int32_t* step;
+};
+int launch_decode_attn_kv8(const Kv8AttnArgs& a, hipStream_t s);
+// rows 0 .. T - 1 of every (clip, head) of one cache [B,H,Tp,64] (dtype) -> codes [B,H,Tp,64] / scales [B,H,Tp]
+int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s);
+
 int launch_vq_argmin(const float* z, int N, const float* Et /*[128][512]*/, const float* ee /*[512]*/,
                      int32_t* idx, float* best_d, float* margin, hipStream_t s);
 

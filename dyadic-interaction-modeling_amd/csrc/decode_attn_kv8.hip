@@ -1,0 +1,322 @@
+// decode_attn_kv8.hip -- the decode step's cross attention over an FP8 copy of the context K/V (dimx/kv8.py is the definition).
+//
+// The cross K/V cache of a generation is written once per clip and streamed by every decode step; it is the step's one large HBM
+// stream (decode_attn.hip).  kv8_quant_kernel turns a layer's cache [B, H, Tp, 64] (bf16 / f32) into OCP e4m3fn codes
+// [B, H, Tp, 64] uint8 plus one f32 scale per (clip, head, key) [B, H, Tp], once per generation; decode_attn_kv8_kernel is the
+// one-query cross attention over those codes: decode_attn_body's shape with 16 elements per 16-byte lane load --
+//   4 lanes per key, 16 keys (1 KiB contiguous) per wave-wide load, 4 loads = 64 keys per batch, the next batch in flight while
+//   the current one is consumed, codes unpacked by the hardware convert (v_cvt_pk_f32_fp8).
+// A batch is 64 keys and a wave has 64 lanes, so the scales stay off the key loops: the score loop stores the raw q . codes dots
+// of its batch to the LDS score row, then lane i scales the dot of key j0 + i by kscale (loaded one batch ahead, coalesced) and the
+// softmax scale and applies the mask; the value loop's lane i turns that score into p and stores p * vscale for the batch's
+// fmas while summing the unscaled p.  A wave only ever touches the scores of the batches it scored itself, so the waves of a
+// (clip, head) meet at the three fixed-order reductions (max, sum, output) and nowhere else.  No atomics; repeats are bit-identical.
+#include "common.hpp"
+#include "decode_attn_body.hpp"
+
+namespace dimx {
+namespace {
+
+typedef float f32x2_cv __attribute__((ext_vector_type(2)));
+
+// 16 e4m3fn codes (one 16-byte load) -> 16 floats, element e = byte e
+__device__ __forceinline__ void unpack_fp8x16(const uint4& u, float (&v)[16]) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2_cv lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+        const f32x2_cv hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        v[4 * i] = lo.x; v[4 * i + 1] = lo.y; v[4 * i + 2] = hi.x; v[4 * i + 3] = hi.y;
+    }
+}
+
+__device__ __forceinline__ float group4_sum(float v) {  // the xor 1, 2 butterfly over a key's four lanes
+    v += dpp_f32<DPP_XOR1>(v);
+    v += dpp_f32<DPP_XOR2>(v);
+    return v;
+}
+__device__ __forceinline__ float group4_max(float v) {
+    v = fmaxf(v, dpp_f32<DPP_XOR1>(v));
+    v = fmaxf(v, dpp_f32<DPP_XOR2>(v));
+    return v;
+}
+
+template <typename T> __device__ __forceinline__ void load_row16(const T* p, float (&v)[16]);
+template <> __device__ __forceinline__ void load_row16<float>(const float* p, float (&v)[16]) { load_f32_chunk<16>(p, v); }
+template <> __device__ __forceinline__ void load_row16<bf16>(const bf16* p, float (&v)[16]) {
+    float a[8], b[8];
+    load_chunk<bf16, 8>(p, a);
+    load_chunk<bf16, 8>(p + 8, b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { v[e] = a[e]; v[8 + e] = b[e]; }
+}
+
+// Rows 0 .. T - 1 of every (clip, head) of one cache [BH, Tp, 64] -> codes / scales (dimx/kv8.py quantize): four lanes per row,
+// 16 elements each.  Rows at or past T are neither read nor written.
+template <typename T>
+__global__ __launch_bounds__(256) void kv8_quant_kernel(const T* cache, long rows, int Tp, int Tn, uint8_t* codes, float* scales) {
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long row = tid >> 2;
+    const int ch = (int)(tid & 3);
+    const bool live = row < rows;
+    const long r = live ? row : rows - 1;   // every lane of the wave stays active for the butterfly
+    const long at = (r / Tn) * Tp + r % Tn;
+    float x[16];
+    load_row16<T>(cache + at * 64 + ch * 16, x);
+    float amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) amax = fmaxf(amax, fabsf(x[e]));
+    amax = group4_max(amax);
+    const bool zero = amax < 0x1p-60f;
+    const float scale = zero ? 0.f : __fdiv_rn(amax, 448.f);
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float y[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) y[e] = fminf(fmaxf(__fdiv_rn(x[4 * i + e], zero ? 1.f : scale), -448.f), 448.f);
+        int p = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+        p = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], p, true);
+        w[i] = zero ? 0u : (uint32_t)p;
+    }
+    if (live) {
+        *(uint4*)(codes + at * 64 + ch * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (ch == 0) scales[at] = scale;
+    }
+}
+
+template <typename TO> __device__ __forceinline__ void store_out16(TO* p, const float (&v)[16]);
+template <> __device__ __forceinline__ void store_out16<float>(float* p, const float (&v)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *(float4*)(p + 4 * i) = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+}
+template <> __device__ __forceinline__ void store_out16<bf16>(bf16* p, const float (&v)[16]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        *(uint4*)(p + 8 * i) = make_uint4(pack_bf16x2(v[8 * i], v[8 * i + 1]), pack_bf16x2(v[8 * i + 2], v[8 * i + 3]),
+                                          pack_bf16x2(v[8 * i + 4], v[8 * i + 5]), pack_bf16x2(v[8 * i + 6], v[8 * i + 7]));
+}
+
+// TO: the type of out (the handle's operand type).  NSPLIT (1, 2, 4): waves per (clip, head), batches dealt round-robin, partial
+// (max, sum, output) combined through LDS in wave order.  WIN: the key count is win_keys(*step, lookahead, n_keys); everything
+// below runs on that n as the plain form would with n_keys = n, so the bits are those of the plain form called with n_keys = n.
+// Codes and scales at or past n are never read: loads past it are redirected to row n - 1.
+template <typename TO, int NSPLIT, bool WIN>
+__global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const Kv8AttnArgs a) {
+    constexpr int EPC = 16;          // codes per 16-byte lane load
+    constexpr int LPK = 4;           // lanes per key
+    constexpr int KPI = 16;          // keys per wave-wide load
+    constexpr int U = 4;             // loads per batch
+    constexpr int KB = U * KPI;      // keys per batch == lanes of a wave
+    constexpr int PPB = 4 / NSPLIT;  // (clip, head) pairs per block
+    static_assert(KB == 64, "a batch is one key per lane");
+    __shared__ float sc[PPB][kMaxKeys];
+    __shared__ float red_m[4], red_l[4];
+    __shared__ float red_acc[4][64];
+
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pib = wave / NSPLIT, part = wave % NSPLIT;
+    const int pair = blockIdx.x * PPB + pib;
+    const bool active = pair < a.B * a.H;
+    const int b = active ? pair / a.H : 0, h = active ? pair % a.H : 0;
+    const int sub = lane / LPK, ch = lane % LPK;
+    const int jfirst = part * KB, jstep = NSPLIT * KB;  // this wave's key batches: jfirst, jfirst + jstep, ...
+
+    float qv[EPC];
+    load_f32_slabs<EPC>(a.q + (size_t)b * a.q_ld + h * 64 + ch * EPC, a.nslab, a.slab_stride, qv);
+    int n = a.n_keys;
+    if constexpr (WIN) n = win_keys(*a.step, a.lookahead, a.n_keys);
+    const float scale2 = a.scale * 1.4426950408889634f;
+
+    const size_t row0 = (size_t)(b * a.H + h) * a.Tmax;
+    const uint8_t* kc = a.kcodes + row0 * 64 + ch * EPC;
+    const uint8_t* vc = a.vcodes + row0 * 64 + ch * EPC;
+    const float* ks = a.kscale + row0;
+    const float* vs = a.vscale + row0;
+    const uint8_t* km = a.kmask ? a.kmask + (size_t)b * a.kmask_ld : nullptr;
+    float* s = &sc[pib][0];
+
+    auto load_batch = [&](const uint8_t* base, int j0, uint4 (&r)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * KPI + sub;
+            r[u] = ld_stream(base + (size_t)(j < n ? j : n - 1) * 64);
+        }
+    };
+    auto own = [&](int j0) { return j0 + lane < n ? j0 + lane : n - 1; };   // the key whose score this lane scales in batch j0
+
+    uint4 cur[U] = {}, nxt[U] = {}, vfirst[U] = {};
+    float kcur = 0.f, knxt = 0.f, vcur = 0.f, vnxt = 0.f;
+    bool dcur = false, dnxt = false;   // the lane's own key is masked
+    if (jfirst < n) {
+        load_batch(kc, jfirst, cur);
+        load_batch(vc, jfirst, vfirst);  // the first V batch rides along: short contexts are one latency hop shorter
+        kcur = ks[own(jfirst)];
+        vcur = vs[own(jfirst)];
+        if (km) dcur = km[own(jfirst)] == 0;
+    }
+
+    // ---- scores: raw dots of the batch, then one key per lane scaled and masked
+    float mx = kNegD;
+    for (int j0 = jfirst; j0 < n; j0 += jstep) {
+        if (j0 + jstep < n) {
+            load_batch(kc, j0 + jstep, nxt);
+            knxt = ks[own(j0 + jstep)];
+            if (km) dnxt = km[own(j0 + jstep)] == 0;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * KPI + sub;
+            float kv[EPC];
+            unpack_fp8x16(cur[u], kv);
+            float d = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) d = fmaf(qv[e], kv[e], d);
+            d = group4_sum(d);
+            if (ch == 0 && j < n) s[j] = d;
+        }
+        if (j0 + lane < n) {
+            float sv = (s[j0 + lane] * kcur) * scale2;
+            if (dcur) sv = kNegD;
+            s[j0 + lane] = sv;
+            mx = fmaxf(mx, sv);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        kcur = knxt;
+        dcur = dnxt;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = vfirst[u];
+    mx = wave_max(mx);
+    if (NSPLIT > 1) {
+        if (lane == 0) red_m[wave] = mx;
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < NSPLIT; ++p) mx = fmaxf(mx, red_m[pib * NSPLIT + p]);
+    }
+
+    // ---- o = sum_j p_j vscale_j codes_j, row sum of the unscaled p_j
+    float lsum = 0.f;
+    float acc[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) acc[e] = 0.f;
+    for (int j0 = jfirst; j0 < n; j0 += jstep) {
+        if (j0 + jstep < n) {
+            load_batch(vc, j0 + jstep, nxt);
+            vnxt = vs[own(j0 + jstep)];
+        }
+        if (j0 + lane < n) {
+            const float p = exp2f(s[j0 + lane] - mx);
+            lsum += p;
+            s[j0 + lane] = p * vcur;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * KPI + sub;
+            float vv[EPC];
+            unpack_fp8x16(cur[u], vv);
+            const float p = j < n ? s[j] : 0.f;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) acc[e] = fmaf(p, vv[e], acc[e]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        vcur = vnxt;
+    }
+    lsum = wave_sum_sel<sizeof(TO) == 2>(lsum);
+    if (NSPLIT > 1) {
+        if (lane == 0) red_l[wave] = lsum;
+        __syncthreads();
+        lsum = 0.f;
+#pragma unroll
+        for (int p = 0; p < NSPLIT; ++p) lsum += red_l[pib * NSPLIT + p];
+    }
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {  // xor 4 .. 32 butterfly over the key sub-groups
+        acc[e] += xor_lane_f32<4>(acc[e]);
+        acc[e] += xor_lane_f32<8>(acc[e]);
+        acc[e] += xor_lane_f32<16>(acc[e]);
+        acc[e] += xor_lane_f32<32>(acc[e]);
+    }
+    if (NSPLIT > 1) {  // combine the partial outputs of the pair's waves in wave order
+        if (sub == 0) {
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) red_acc[wave][ch * EPC + e] = acc[e];
+        }
+        __syncthreads();
+        if (part == 0 && sub == 0) {
+#pragma unroll
+            for (int p = 1; p < NSPLIT; ++p)
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) acc[e] += red_acc[pib * NSPLIT + p][ch * EPC + e];
+        }
+    }
+    if (active && part == 0 && sub == 0) {
+        const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) acc[e] *= inv;
+        store_out16<TO>((TO*)a.out + (size_t)b * a.o_ld + h * 64 + ch * EPC, acc);
+    }
+}
+
+}  // namespace
+
+int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s) {
+    DIMX_REQUIRE(dtype == DIMX_BF16 || dtype == DIMX_F32, DIMX_ERR_ARG, "kv8_quantize: dtype %d", dtype);
+    DIMX_REQUIRE(cache && codes && scales, DIMX_ERR_ARG, "kv8_quantize: null operand");
+    DIMX_REQUIRE((uintptr_t)cache % 16 == 0 && (uintptr_t)codes % 16 == 0 && (uintptr_t)scales % 4 == 0, DIMX_ERR_ARG,
+                 "kv8_quantize: misaligned operand (cache / codes 16 bytes, scales 4)");
+    DIMX_REQUIRE(B >= 1 && H >= 1 && T >= 1 && T <= Tp, DIMX_ERR_ARG, "kv8_quantize: B=%d H=%d T=%d Tp=%d (need 1 <= T <= Tp)", B, H, T, Tp);
+    const long rows = (long)B * H * T;
+    const long blocks = (rows * 4 + 255) / 256;
+    DIMX_REQUIRE(blocks <= 0x7fffffffL, DIMX_ERR_ARG, "kv8_quantize: %ld rows", rows);
+    if (dtype == DIMX_BF16)
+        hipLaunchKernelGGL((kv8_quant_kernel<bf16>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16*)cache, rows, Tp, T, codes, scales);
+    else
+        hipLaunchKernelGGL((kv8_quant_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)cache, rows, Tp, T, codes, scales);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+int launch_decode_attn_kv8(const Kv8AttnArgs& a, hipStream_t s) {
+    DIMX_REQUIRE(a.q && a.kcodes && a.kscale && a.vcodes && a.vscale && a.out, DIMX_ERR_ARG, "decode_attn_kv8: null operand");
+    DIMX_REQUIRE(a.out_dtype == DIMX_BF16 || a.out_dtype == DIMX_F32, DIMX_ERR_ARG, "decode_attn_kv8: out_dtype %d", a.out_dtype);
+    DIMX_REQUIRE(a.B >= 1 && a.H >= 1 && a.Tmax >= 1, DIMX_ERR_ARG, "decode_attn_kv8: empty shape");
+    DIMX_REQUIRE(a.n_keys >= 1 && a.n_keys <= a.Tmax && a.n_keys <= kMaxKeys, DIMX_ERR_ARG,
+                 "decode_attn_kv8: n_keys %d outside 1 .. min(Tmax = %d, %d)", a.n_keys, a.Tmax, kMaxKeys);
+    DIMX_REQUIRE(a.nslab >= 1 && a.nslab <= 8 && (a.nslab == 1 || a.slab_stride >= (long)a.B * a.q_ld), DIMX_ERR_ARG,
+                 "decode_attn_kv8: nslab=%d (1..8) with slabs %ld apart", a.nslab, a.slab_stride);
+    const int oal = a.out_dtype == DIMX_BF16 ? 8 : 4;
+    DIMX_REQUIRE(a.q_ld >= a.H * 64 && a.o_ld >= a.H * 64 && a.q_ld % 4 == 0 && a.slab_stride % 4 == 0 && a.o_ld % oal == 0, DIMX_ERR_ARG,
+                 "decode_attn_kv8: q_ld=%d o_ld=%d slab_stride=%ld (rows of at least H*64, 16-byte multiples)", a.q_ld, a.o_ld, a.slab_stride);
+    DIMX_REQUIRE((uintptr_t)a.q % 16 == 0 && (uintptr_t)a.kcodes % 16 == 0 && (uintptr_t)a.vcodes % 16 == 0 && (uintptr_t)a.out % 16 == 0 &&
+                     (uintptr_t)a.kscale % 4 == 0 && (uintptr_t)a.vscale % 4 == 0,
+                 DIMX_ERR_ARG, "decode_attn_kv8: misaligned operand (q / codes / out 16 bytes, scales 4)");
+    DIMX_REQUIRE(a.kmask == nullptr || a.kmask_ld >= a.n_keys, DIMX_ERR_ARG, "decode_attn_kv8: kmask_ld=%d < n_keys=%d", a.kmask_ld, a.n_keys);
+    DIMX_REQUIRE(!a.win || a.step != nullptr, DIMX_ERR_ARG, "decode_attn_kv8: the windowed form needs a step counter");
+    // waves per (clip, head): launch_decode_attn's rule -- on an f32 handle a function of the cache length only, so a shard of a
+    // batch reproduces the whole batch's rows bit for bit
+    const int pairs = a.B * a.H;
+    int nsplit = 1;
+    if (pairs * 2 <= 3072) nsplit = 2;
+    if (pairs * 4 <= 3072) nsplit = 4;
+    if (a.out_dtype != DIMX_BF16) nsplit = a.Tmax >= 1024 ? 4 : (a.Tmax >= 512 ? 2 : 1);
+    if (a.force_nsplit == 1 || a.force_nsplit == 2 || a.force_nsplit == 4) nsplit = a.force_nsplit;
+    dim3 grid(ceil_div(pairs, 4 / nsplit)), block(256);
+#define KV8_LAUNCH(TT, NS, WW) hipLaunchKernelGGL((decode_attn_kv8_kernel<TT, NS, WW>), grid, block, 0, s, a)
+#define KV8_NS(TT, WW)                              \
+    do {                                            \
+        if (nsplit == 4) KV8_LAUNCH(TT, 4, WW);     \
+        else if (nsplit == 2) KV8_LAUNCH(TT, 2, WW); \
+        else KV8_LAUNCH(TT, 1, WW);                 \
+    } while (0)
+    if (a.out_dtype == DIMX_BF16) { if (a.win) KV8_NS(bf16, true); else KV8_NS(bf16, false); }
+    else { if (a.win) KV8_NS(float, true); else KV8_NS(float, false); }
+#undef KV8_NS
+#undef KV8_LAUNCH
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+}  // namespace dimx

@@ -113,6 +113,24 @@ static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream
     return DIMX_OK;
 }
 
+// FP8 cross K/V (dimx_set_cross_kv8; include/dimx.h has the layout): per layer K codes, V codes [B, H, Tp, 64] uint8, K scales,
+// V scales [B, H, Tp] f32, each 256-byte aligned, layers in order
+struct Kv8Layer {
+    uint8_t *kcodes, *vcodes;
+    float *kscale, *vscale;
+};
+static size_t kv8_codes_bytes(dimx_handle h, int B, int T) { return align_up((size_t)B * h->decg.heads * tpad(T) * 64, 256); }
+static size_t kv8_scale_bytes(dimx_handle h, int B, int T) { return align_up((size_t)B * h->decg.heads * tpad(T) * sizeof(float), 256); }
+static size_t kv8_bytes(dimx_handle h, int B, int T) {
+    if (!h || h->variant != 0 || h->decg.dim_head != 64 || B < 1 || T < 2 || T > h->d.max_seq_len || tpad(T) > 2048) return 0;
+    return (size_t)h->decg.depth * 2 * (kv8_codes_bytes(h, B, T) + kv8_scale_bytes(h, B, T));
+}
+static Kv8Layer kv8_layer(dimx_handle h, int B, int T, int l) {
+    const size_t cb = kv8_codes_bytes(h, B, T), sb = kv8_scale_bytes(h, B, T);
+    uint8_t* p = (uint8_t*)h->kv8_buf + (size_t)l * 2 * (cb + sb);
+    return Kv8Layer{p, p + cb, (float*)(p + 2 * cb), (float*)(p + 2 * cb + sb)};
+}
+
 // what a generate call was asked for; the public entry points fill it after their own argument checks
 struct GenRequest {
     GenPrompt pr;
@@ -160,6 +178,7 @@ struct StepCtx {
     const float* pos;   // the legacy decoder's positional embedding or nullptr
     GenScratch s;
     const void *ck[8], *cv[8];   // the group's clips in the context K / V of every layer
+    Kv8Layer kv8[8];             // route kv8: ... and in their FP8 copy
     const int32_t *start, *forced, *forced_len;
     const uint8_t* ctx_mask;
     int32_t* tokens;
@@ -190,6 +209,12 @@ static StepCtx step_ctx(dimx_handle h, const GenCall& gc, const StepRoute& r, in
         c.s.sv[l] = boff(s0.sv[l], (size_t)heads * T * 64 * es);
         c.ck[l] = (unsigned char*)gc.cp.ck[l] + (size_t)c.clip0 * heads * c.Tp * 64 * es;
         c.cv[l] = (unsigned char*)gc.cp.cv[l] + (size_t)c.clip0 * heads * c.Tp * 64 * es;
+        c.kv8[l] = Kv8Layer{};
+        if (r.kv8) {
+            const size_t row0 = (size_t)c.clip0 * heads * c.Tp;
+            const Kv8Layer all = kv8_layer(h, q.B, T, l);
+            c.kv8[l] = Kv8Layer{all.kcodes + row0 * 64, all.vcodes + row0 * 64, all.kscale + row0, all.vscale + row0};
+        }
     }
     c.s.x = s0.x + (size_t)row0 * DD;
     c.s.y = boff(s0.y, DD * es);
@@ -306,6 +331,19 @@ static DecodeAttnArgs cross_args(const StepCtx& c, int l) {
     return ca;
 }
 
+// The step's one-query cross attention: the cache form, or (route kv8) the same arguments over the FP8 copy of the context K/V
+static int cross_attention(const StepCtx& c, int l, const DecodeAttnArgs& ca) {
+    if (!c.r->kv8) return launch_decode_attn(ca, c.st);
+    Kv8AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const float*)ca.q; a.q_ld = ca.q_ld; a.nslab = ca.nslab; a.slab_stride = ca.slab_stride;
+    a.kcodes = c.kv8[l].kcodes; a.kscale = c.kv8[l].kscale; a.vcodes = c.kv8[l].vcodes; a.vscale = c.kv8[l].vscale; a.Tmax = ca.Tmax;
+    a.out = ca.out; a.out_dtype = ca.dtype; a.o_ld = ca.o_ld; a.B = ca.B; a.H = ca.H;
+    a.n_keys = ca.n_keys; a.kmask = ca.kmask; a.kmask_ld = ca.kmask_ld; a.scale = ca.scale;
+    a.win = ca.win; a.lookahead = ca.lookahead; a.step = ca.step;
+    return launch_decode_attn_kv8(a, c.st);
+}
+
 // round 5: the attention half of a layer as one XCD-local launch (chain.hip xcd_layer_kernel; DIMX_NO_LAYER_CHAIN=1: the four
 // launches, for A/B runs).  False when the layer has no deferred-LayerNorm weights.
 static bool layer_args(const StepCtx& c, int l, const DecodeAttnArgs& sa, const DecodeAttnArgs& ca, LayerChainArgs& lc) {
@@ -388,7 +426,7 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         else
             DIMX_TRY(chain_site(c, 3 * l, s.o, inner, &h->dec.self_[l].out, 0, h->dec.cross[l].ln_g, &h->dec.cross[l].qkv, s.qc, inner));
         ca.nslab = 1;
-        DIMX_TRY(launch_decode_attn(ca, c.st));
+        DIMX_TRY(cross_attention(c, l, ca));
         // cross out-projection -> x += . -> LayerNorm (feed-forward input)
         DIMX_TRY(chain_site(c, 3 * l + 1, s.o, inner, &h->dec.cross[l].out, 0, h->dec.ff[l].ln_g, nullptr, nullptr, 0));
     } else if (r.guided) {
@@ -403,7 +441,7 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, *pending, s.st_xr, s.y, h->dec.cross[l].ln_g, B, DD, c.st));
         DIMX_TRY(slab_gemm_rows(h, Bc, c.st, s.y, DD, h->dec.cross[l].qkv, s.qc, s.st_qc, &ns));
         ca.nslab = ns;
-        DIMX_TRY(launch_decode_attn(ca, c.st));
+        DIMX_TRY(cross_attention(c, l, ca));
         DIMX_TRY(slab_gemm_rows(h, Bc, c.st, s.o, inner, h->dec.cross[l].out, s.xr, s.st_xr, pending));
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, *pending, s.st_xr, s.y, h->dec.ff[l].ln_g, Bc, DD, c.st));
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x + (size_t)Bc * DD, s.xr + (size_t)Bc * DD, 0, s.st_xr, (unsigned char*)s.y + (size_t)Bc * DD * es,
@@ -417,7 +455,7 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         } else {
             DIMX_TRY(slab_gemm(c, s.y, DD, h->dec.cross[l].qkv, s.qc, s.st_qc, &ns));
             ca.nslab = ns;
-            DIMX_TRY(launch_decode_attn(ca, c.st));
+            DIMX_TRY(cross_attention(c, l, ca));
         }
         DIMX_TRY(slab_gemm(c, s.o, inner, h->dec.cross[l].out, s.xr, s.st_xr, pending));
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, *pending, s.st_xr, s.y, h->dec.ff[l].ln_g, B, DD, c.st));
@@ -564,6 +602,7 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     r.multi_tr = gen_multi_tr(h, q.S);   // consulted on the per-op branch and without the window only
     r.win = h->xwin_on != 0;
     r.lookahead = r.win ? h->xwin_lookahead : 0;
+    r.kv8 = h->kv8_buf != nullptr;   // the layer kernel streams the caches itself: not taken, exactly as under the window
     r.guided = q.guided;
     if (r.guided) r.chain = r.defer = r.logits_chain = r.multi_tr = false;   // the per-op step, as a session takes it (no layer kernel either: it needs chain)
     // one group: every projection launch of the generation has R rows, and so has the table's build
@@ -576,7 +615,7 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     if (r.qkv0 && h->use_kv0_table && !q.beam && q.pr.step0 == 0 && q.pr.Pmax <= 1 && dg.dim_head == 64 && dg.num_tokens <= 512)
         r.kv0 = h->at == DIMX_BF16 ? h->kv0_image : (const void*)h->qkv0_table;
     // the layer kernel depends on shapes only, so its per-layer support is settled here on the arguments the step will pass
-    if (h->use_layer_chain && r.chain && r.defer && q.S == 1 && 4 * dg.depth + 1 <= kChainSites && !r.win) {
+    if (h->use_layer_chain && r.chain && r.defer && q.S == 1 && 4 * dg.depth + 1 <= kChainSites && !r.win && !r.kv8) {
         const StepCtx c = step_ctx(h, gc, r, 0, rows, 0, q.st);
         for (int l = 0; l < dg.depth; ++l) {
             LayerChainArgs lc;
@@ -604,6 +643,7 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
     k.beam = q.beam ? *q.beam : BeamCall{};
     k.xwin_on = r.win ? 1 : 0; k.xwin_lookahead = r.lookahead;
     k.guided = r.guided; k.branch_out = q.branch_out;
+    k.kv8 = r.kv8 ? h->kv8_buf : nullptr;
     return k;
 }
 
@@ -816,6 +856,12 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     const int top_k = h && h->filter_kind != DIMX_FILTER_TOP_K ? 0 : q.top_k;
     DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
                  "generate: n_samples %d not in {1,2,4,5,8,10}", S);
+    if (h && h->kv8_buf && !sess) {   // FP8 cross K/V: one row per clip, the sampler ends the step; a session does not read the setting
+        DIMX_REQUIRE(S == 1 && !q.beam, DIMX_ERR_ARG, "generate: n_samples > 1 and beam search are not available with dimx_set_cross_kv8");
+        DIMX_REQUIRE(kv8_bytes(h, B, T) != 0, DIMX_ERR_ARG, "generate: B=%d T=%d is not supported with dimx_set_cross_kv8", B, T);
+        DIMX_REQUIRE(h->kv8_bytes >= kv8_bytes(h, B, T), DIMX_ERR_WORKSPACE, "generate: the FP8 cross K/V buffer holds %zu bytes, B=%d T=%d needs %zu (dimx_cross_kv8_bytes)",
+                     h->kv8_bytes, B, T, kv8_bytes(h, B, T));
+    }
     const int halves = q.guided ? 2 : 1;   // a guided generation decodes every clip twice: 2B rows of self caches, B cross caches
     DIMX_TRY(check_common(h, B, T, q.ws, q.ws_bytes, COMP_DEC, S * halves));
     DIMX_REQUIRE(pr.tok && q.ctx_mask && q.tokens && T >= 2, DIMX_ERR_ARG, "generate: null argument or T < 2");
@@ -852,6 +898,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         for (bool& lk : route.layer_kernel) lk = false;
         route.win = true;
         route.lookahead = sess->lookahead;
+        route.kv8 = false;
         run.graphs = false;
     }
     // parameters
@@ -868,6 +915,16 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         DIMX_TRY(gen_prefill(h, cp, s, ps, pr, q.ctx_mask, B, T, S, q.tokens, st, pr.win ? &route.lookahead : nullptr, sess ? sess->n_keys : T));
     }
     if (prefill_only) return DIMX_OK;
+    // FP8 cross K/V: every layer's context K / V -> codes + scales, once per generation, ahead of the first step (the prefill above
+    // read the unquantised caches; the regeneration after a chain fault reuses the codes)
+    if (route.kv8 && !keep_prefill) {
+        const int Tp = tpad(T), heads = h->decg.heads;
+        for (int l = 0; l < h->decg.depth; ++l) {
+            const Kv8Layer kl = kv8_layer(h, B, T, l);
+            DIMX_TRY(launch_kv8_quant(h->at, cp.ck[l], B, heads, Tp, T, kl.kcodes, kl.kscale, st));
+            DIMX_TRY(launch_kv8_quant(h->at, cp.cv[l], B, heads, Tp, T, kl.vcodes, kl.vscale, st));
+        }
+    }
     // start
     DIMX_TRY(gen_groups_fork(h, G, st, run.gs));
     for (int g = 0; g < G; ++g) {
@@ -1151,6 +1208,27 @@ int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
     if (on) *on = h->xwin_on;
     if (lookahead) *lookahead = h->xwin_lookahead;
+    return DIMX_OK;
+}
+
+size_t dimx_cross_kv8_bytes(dimx_handle h, int B, int T) { return kv8_bytes(h, B, T); }
+
+int dimx_set_cross_kv8(dimx_handle h, void* buf, size_t bytes) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_NO_SESSION(h, "set_cross_kv8");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_cross_kv8: FP8 cross K/V is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    DIMX_REQUIRE(buf == nullptr || (h->decg.dim_head == 64 && (uintptr_t)buf % 256 == 0), DIMX_ERR_ARG,
+                 "set_cross_kv8: the buffer must be 256-byte aligned and the decoder's heads 64 wide");
+    h->kv8_buf = buf;
+    h->kv8_bytes = buf ? bytes : 0;
+    return DIMX_OK;
+}
+
+int dimx_cross_kv8(dimx_handle h, void** buf, size_t* bytes) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    if (buf) *buf = h->kv8_buf;
+    if (bytes) *bytes = h->kv8_bytes;
     return DIMX_OK;
 }
 

@@ -424,6 +424,29 @@ int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, in
                              kmask_ld, rows_per_clip, scale, nsplit, 1, lookahead, stream);
 }
 
+/* FP8 cross K/V (decode_attn_kv8.hip): one cache -> codes + per-row scales */
+int dimx_op_kv8_quantize(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, void* stream) {
+    return launch_kv8_quant(dtype, cache, B, H, Tp, T, codes, scales, (hipStream_t)stream);
+}
+
+/* ... and the step's one-query cross attention over them, plain (win = 0) or windowed */
+int dimx_op_decode_attn_kv8(int out_dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, const uint8_t* kcodes,
+                            const float* kscale, const uint8_t* vcodes, const float* vscale, void* out, int o_ld, int B, int H, int Tmax,
+                            const int32_t* step_dev, int n_keys, const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit,
+                            int lookahead, int win, void* stream) {
+    DIMX_REQUIRE(q_is_f32, DIMX_ERR_ARG, "op_decode_attn_kv8: q must be f32 split-K slabs");
+    DIMX_REQUIRE(rows_per_clip <= 1, DIMX_ERR_ARG, "op_decode_attn_kv8: one row per clip (rows_per_clip = %d)", rows_per_clip);
+    DIMX_REQUIRE(!win || step_dev != nullptr, DIMX_ERR_ARG, "op_decode_attn_kv8: the windowed form needs a step counter");
+    Kv8AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const float*)q; a.q_ld = q_ld; a.nslab = nslab; a.slab_stride = slab_stride;
+    a.kcodes = kcodes; a.kscale = kscale; a.vcodes = vcodes; a.vscale = vscale; a.Tmax = Tmax;
+    a.out = out; a.out_dtype = out_dtype; a.o_ld = o_ld; a.B = B; a.H = H;
+    a.n_keys = n_keys; a.kmask = kmask; a.kmask_ld = kmask_ld; a.scale = scale; a.force_nsplit = nsplit;
+    if (win) { a.win = 1; a.lookahead = lookahead; a.step = step_dev; }
+    return launch_decode_attn_kv8(a, (hipStream_t)stream);
+}
+
 /* windowed cross attention for many queries (win_attn.hip): query row i at position t0 + i, keys j < clamp(t0 + i + 2 + lookahead, 1, n_keys) */
 int dimx_op_cross_attn_win(int dtype, const float* q, int ld, const void* kcache, const void* vcache, int Tp, void* out, int o_ld, int B, int H,
                            int Lq, int t0, int n_keys, int lookahead, const uint8_t* kmask, int kmask_ld, float scale, void* stream) {

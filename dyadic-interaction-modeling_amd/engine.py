@@ -267,10 +267,52 @@ class Engine:
         L.check(self.lib.dimx_cross_lookahead(self.h, ctypes.byref(on), ctypes.byref(la)), "dimx_cross_lookahead")
         return la.value if on.value else None
 
+    def cross_kv8_bytes(self, B, T):
+        """Bytes of the FP8 cross K/V buffer of a B x T generation (dimx_cross_kv8_bytes; 0 = shape not supported)."""
+        return int(self.lib.dimx_cross_kv8_bytes(self.h, int(B), int(T)))
+
+    def set_cross_kv8(self, buf=None):
+        """FP8 cross-attention K/V (dimx_set_cross_kv8; the definition is dimx.kv8): with a uint8 device tensor ``buf`` of at least
+        ``cross_kv8_bytes(B, T)`` bytes, this engine's generate calls quantise the context K / V into it once and every decode
+        step's cross attention reads the codes; None switches it off.  ``generate(kv8=True)`` does both around one call."""
+        if buf is None:
+            L.check(self.lib.dimx_set_cross_kv8(self.h, None, 0), "dimx_set_cross_kv8")
+            return
+        assert buf.dtype == torch.uint8 and buf.is_contiguous() and buf.device == self.device
+        L.check(self.lib.dimx_set_cross_kv8(self.h, L.ptr(buf), buf.numel()), "dimx_set_cross_kv8")
+
+    def cross_kv8(self):
+        """(pointer, bytes) of the buffer in force, or None while FP8 cross K/V is off."""
+        p, n = ctypes.c_void_p(None), ctypes.c_size_t(0)
+        L.check(self.lib.dimx_cross_kv8(self.h, ctypes.byref(p), ctypes.byref(n)), "dimx_cross_kv8")
+        return (p.value, n.value) if p.value else None
+
+    def cross_kv8_buffer(self):
+        """The uint8 tensor the last ``generate(kv8=True)`` quantised into (None before the first); ``cross_kv8_layers`` views it."""
+        return getattr(self, "_kv8", None)
+
+    def cross_kv8_layers(self, B, T, buf=None):
+        """Per decoder layer (kcodes, vcodes [B, H, Tp, 64] uint8, kscale, vscale [B, H, Tp] f32): views into ``buf`` (default: the
+        engine's buffer) by the layout of include/dimx.h (dimx.kv8.buffer_layout)."""
+        from . import kv8 as _kv8
+        buf = self.cross_kv8_buffer() if buf is None else buf
+        H, Tp = self.dims.heads, (T + 7) // 8 * 8
+        lay, total = _kv8.buffer_layout(self.dims.dec_depth, B, H, Tp)
+        assert buf.numel() >= total
+        nc, ns = B * H * Tp * 64, B * H * Tp * 4
+        return [(buf[o["kcodes"]:o["kcodes"] + nc].view(B, H, Tp, 64), buf[o["vcodes"]:o["vcodes"] + nc].view(B, H, Tp, 64),
+                 buf[o["kscale"]:o["kscale"] + ns].view(torch.float32).view(B, H, Tp),
+                 buf[o["vscale"]:o["vscale"] + ns].view(torch.float32).view(B, H, Tp)) for o in lay]
+
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
                  n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False, filter_logits_fn=None,
-                 filter_kwargs=None, return_scores=False, lookahead=None, guidance=None, return_branches=False):
+                 filter_kwargs=None, return_scores=False, lookahead=None, guidance=None, return_branches=False, kv8=False):
         """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
+
+        ``kv8``: FP8 cross-attention K/V for this call (``set_cross_kv8``; dimx.kv8): the engine allocates (or reuses) its buffer,
+        sets it for the call and clears the setting afterwards.  Works with ``lookahead``, ``prompt``, ``guidance``,
+        ``filter_logits_fn``, ``return_logits`` and ``return_scores``; ``n_samples > 1`` is refused by the library.  False leaves
+        the engine's setting as it is.
 
         ``guidance``: classifier-free guidance with this scale (dimx_generate_guided, include/dimx.h; the definition is
         dimx.guidance): every step samples from cond + (scale - 1) * (cond - uncond), the second branch being the decoder without
@@ -302,6 +344,21 @@ class Engine:
         ``no_prefill``) unless ``prefill`` is ``"window"`` (P0 by the default rule above) or ``("window", P0)``: then the first P0
         codes are prefilled by one teacher-forced pass under the window (flags bit 1 of dimx_generate_prompted).  With
         the window off that spelling is the plain prefill."""
+        if kv8:
+            B = (prompt if prompt is not None else start).shape[0]
+            need = self.cross_kv8_bytes(B, T)
+            if need == 0:
+                raise L.DimxError("generate(kv8=True): dimx_cross_kv8_bytes(%d, %d) = 0 (shape or variant not supported)" % (B, T))
+            if self.cross_kv8_buffer() is None or self._kv8.numel() < need:
+                self._kv8 = None
+                self._kv8 = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            self.set_cross_kv8(self._kv8)
+            try:
+                return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt, prompt_len,
+                                     prefill, no_prefill, filter_logits_fn, filter_kwargs, return_scores, lookahead, guidance,
+                                     return_branches)
+            finally:
+                self.set_cross_kv8(None)
         if lookahead is not None:
             prev = self.cross_lookahead()
             self.set_cross_lookahead(lookahead)
@@ -1176,6 +1233,40 @@ def op_decode_attn_ex(q, kcache, vcache, scale, n_keys=0, step=None, kmask=None,
                                        1 if step is not None else 0, L.ptr(kcache), L.ptr(vcache), L.ptr(out), H * 64, B, H, Tmax,
                                        L.ptr(step), n_keys, L.ptr(kmask), kld, S, float(scale), nsplit, L.stream_ptr(q.device)),
             "dimx_op_decode_attn_ex")
+    return out
+
+
+def op_kv8_quantize(cache, T=None, codes=None, scales=None):
+    """FP8 cross K/V, the quantiser (dimx_op_kv8_quantize; dimx.kv8.quantize): cache [B, H, Tp, 64] f32 or bf16; rows 0 .. T - 1
+    (default Tp) of every (clip, head) -> (codes [B, H, Tp, 64] uint8, scales [B, H, Tp] f32).  ``codes`` / ``scales``: tensors to
+    write into (rows at or past T are left as they are); default: zero-filled ones."""
+    lib = L.load()
+    B, H, Tp, _ = cache.shape
+    assert cache.shape[3] == 64
+    codes = torch.zeros(B, H, Tp, 64, dtype=torch.uint8, device=cache.device) if codes is None else codes
+    scales = torch.zeros(B, H, Tp, dtype=torch.float32, device=cache.device) if scales is None else scales
+    L.check(lib.dimx_op_kv8_quantize(L.BF16 if cache.dtype == torch.bfloat16 else L.F32, L.ptr(cache), B, H, Tp, Tp if T is None else int(T),
+                                     L.ptr(codes), L.ptr(scales), L.stream_ptr(cache.device)), "dimx_op_kv8_quantize")
+    return codes, scales
+
+
+def op_decode_attn_kv8(q, kcodes, kscale, vcodes, vscale, scale, n_keys, kmask=None, kmask_ld=None, nsplit=0, out_bf16=False, step=None,
+                       lookahead=None, rows_per_clip=1):
+    """The decode step's cross attention over FP8 codes (dimx_op_decode_attn_kv8; dimx.kv8.attention): q [B, q_ld] f32 or split-K
+    slabs [nslab, B, q_ld]; kcodes / vcodes [B, H, Tmax, 64] uint8, kscale / vscale [B, H, Tmax] f32; kmask [B, kmask_ld] uint8 or
+    None -> [B, H*64] f32 (bf16 with ``out_bf16``).  lookahead (int) with step (int32 device scalar): the windowed form, keys
+    j < dimx.online.visible(*step, lookahead, n_keys)."""
+    lib = L.load()
+    B, H, Tmax, _ = kcodes.shape
+    qs = q if q.dim() == 3 else q.unsqueeze(0)
+    nslab, R, q_ld = qs.shape
+    out = torch.empty(R, H * 64, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=q.device)
+    kld = kmask_ld if kmask_ld is not None else (kmask.shape[1] if kmask is not None else 0)
+    L.check(lib.dimx_op_decode_attn_kv8(L.BF16 if out_bf16 else L.F32, L.ptr(qs), q_ld, 1 if q.dtype == torch.float32 else 0, nslab,
+                                        qs.stride(0), L.ptr(kcodes), L.ptr(kscale), L.ptr(vcodes), L.ptr(vscale), L.ptr(out), H * 64, B, H,
+                                        Tmax, L.ptr(step), int(n_keys), L.ptr(kmask), kld, int(rows_per_clip), float(scale), int(nsplit),
+                                        0 if lookahead is None else int(lookahead), 0 if lookahead is None else 1,
+                                        L.stream_ptr(q.device)), "dimx_op_decode_attn_kv8")
     return out
 
 

@@ -1,0 +1,128 @@
+"""FP8 cross-attention K/V for generation: the definition (numpy, no GPU).
+
+The cross K/V cache of a generation is written once per clip and read by every decode step.  ``quantize`` states how a cache row
+[64] becomes 64 OCP ``e4m3fn`` codes and one float32 scale -- one scale per (clip, head, key) -- and ``attention`` what the decode
+step's one-query cross attention computes over such codes.  csrc/decode_attn_kv8.hip follows this file bit for bit (codes, scales)
+or within the step kernels' tolerance (attention); tests/test_kv8_host.py pins the rounding against torch's CPU ``float8_e4m3fn``
+cast.
+
+    amax  = max |x| over the row (float32)
+    scale = float32(amax) / float32(448)              one IEEE float32 division; amax < 2**-60: a zero row, scale 0, codes 0
+    y     = clamp(float32(x) / scale, -448, 448)      IEEE float32 division
+    code  = e4m3fn(y), round to nearest even, subnormals included (spacing 2**-9 below 2**-6)
+
+Codes 0x00 and 0x80 are interchangeable wherever a value rounds to zero.  Non-finite inputs are outside the contract.  The format
+is OCP e4m3fn (bias 7, no infinities, 0x7F / 0xFF NaN, largest finite 448) -- what gfx950 converts in hardware -- not MI300's fnuz.
+"""
+import numpy as np
+
+FP8_MAX = np.float32(448.0)
+ZERO_ROW = np.float32(2.0 ** -60)
+NEG = -float(np.finfo(np.float32).max)   # a masked key's score (the model's mask value)
+
+
+def _decode_table():
+    t = np.zeros(256, dtype=np.float32)
+    for c in range(256):
+        e, m = (c >> 3) & 15, c & 7
+        if e == 15 and m == 7:
+            v = np.nan
+        elif e == 0:
+            v = m * 2.0 ** -9
+        else:
+            v = (1.0 + m / 8.0) * 2.0 ** (e - 7)
+        t[c] = -v if c & 0x80 else v
+    return t
+
+
+DECODE = _decode_table()
+_POS = DECODE[:0x7F].copy()   # the 127 non-negative finite values, ascending: index = code
+
+
+def decode(codes):
+    """uint8 codes -> float32 values (0x7F / 0xFF: NaN)"""
+    return DECODE[np.asarray(codes, dtype=np.uint8)]
+
+
+def encode(y):
+    """float32 values in [-448, 448] -> e4m3fn codes, round to nearest even (negative values that round to zero give 0x80)"""
+    y = np.asarray(y, dtype=np.float32)
+    a = np.abs(y).astype(np.float64)
+    assert np.all(a <= 448.0), "encode: values outside +-448 (or not finite)"
+    _, ex = np.frexp(a)                          # a = f * 2**ex, f in [0.5, 1)
+    e = np.maximum(ex - 1, -6)                   # the binade, subnormals share the first normal binade's spacing
+    sp = np.exp2((e - 3).astype(np.float64))
+    r = np.rint(a / sp) * sp                     # power-of-two scaling is exact; rint rounds half to even
+    code = np.searchsorted(_POS.astype(np.float64), r).astype(np.uint8)
+    assert np.array_equal(_POS[code].astype(np.float64), r)
+    return np.where(np.signbit(y), code | np.uint8(0x80), code).astype(np.uint8)
+
+
+def quantize(rows):
+    """rows [..., 64] float -> (codes uint8 [..., 64], scale float32 [...])"""
+    x = np.asarray(rows).astype(np.float32)
+    assert x.shape[-1] == 64, "quantize: rows of 64 elements"
+    amax = np.max(np.abs(x), axis=-1).astype(np.float32)
+    zero = amax < ZERO_ROW
+    scale = np.where(zero, np.float32(0), amax / FP8_MAX).astype(np.float32)
+    div = np.where(zero, np.float32(1), scale).astype(np.float32)
+    y = (x / div[..., None]).astype(np.float32)
+    y = np.clip(y, -FP8_MAX, FP8_MAX)
+    codes = encode(y)
+    codes = np.where(zero[..., None], np.uint8(0), codes).astype(np.uint8)
+    return codes, scale
+
+
+def dequantize(codes, scale):
+    """float32(decode(code)) * scale -> float32 [..., 64]"""
+    return (decode(codes) * np.asarray(scale, dtype=np.float32)[..., None]).astype(np.float32)
+
+
+def same_codes(a, b):
+    """codes equal except 0x00 / 0x80"""
+    a, b = np.asarray(a, dtype=np.uint8), np.asarray(b, dtype=np.uint8)
+    return (a == b) | (((a | b) & 0x7F) == 0)
+
+
+def attention(q, kcodes, kscale, vcodes, vscale, mask, n, scale=0.125):
+    """The one-query cross attention over the dequantised rows, in float64, with dimx_op_decode_attn_ex's conventions.
+
+    q [B, H, 64]; kcodes / vcodes [B, H, Tp, 64] uint8; kscale / vscale [B, H, Tp] float32; mask [B, >= n] (0 = masked) or None;
+    keys 0 .. n - 1.  Scores are scale * q.k, a masked key scores -FLT_MAX, so a row with every key masked is the mean of V over
+    the n keys.  -> [B, H, 64] float64."""
+    q = np.asarray(q, dtype=np.float64)
+    k = dequantize(np.asarray(kcodes)[:, :, :n], np.asarray(kscale)[:, :, :n]).astype(np.float64)
+    v = dequantize(np.asarray(vcodes)[:, :, :n], np.asarray(vscale)[:, :, :n]).astype(np.float64)
+    s = np.einsum("bhd,bhjd->bhj", q, k) * float(scale)
+    if mask is not None:
+        dead = np.asarray(mask)[:, None, :n] == 0
+        s = np.where(dead, NEG, s)
+    s = s - s.max(-1, keepdims=True)
+    p = np.exp(s)
+    p = p / p.sum(-1, keepdims=True)
+    return np.einsum("bhj,bhjd->bhd", p, v)
+
+
+def buffer_layout(depth, B, H, Tp):
+    """The caller's buffer of dimx_set_cross_kv8 (include/dimx.h): per layer K codes, V codes, K scales, V scales, each 256-byte
+    aligned, layers in order.  -> (list of per-layer dicts of byte offsets, total bytes)"""
+    al = lambda x: (x + 255) // 256 * 256
+    cb, sb = al(B * H * Tp * 64), al(B * H * Tp * 4)
+    off, lay = 0, []
+    for _ in range(depth):
+        lay.append({"kcodes": off, "vcodes": off + cb, "kscale": off + 2 * cb, "vscale": off + 2 * cb + sb})
+        off += 2 * cb + 2 * sb
+    return lay, off
+
+
+def drift(logits_kv8, logits_plain, tokens_kv8=None, tokens_plain=None):
+    """The report's arithmetic (tools/bench_kv8.py): the logit difference of a teacher-forced pair of runs and the share of equal
+    tokens of a free-running pair.  logits [..., V]; tokens integer arrays of one shape."""
+    a, b = np.asarray(logits_kv8, dtype=np.float64), np.asarray(logits_plain, dtype=np.float64)
+    d = np.abs(a - b)
+    out = {"logit_max_abs": float(d.max()), "logit_mean_abs": float(d.mean()),
+           "logit_rel_to_spread": float(d.max() / max(float(b.std()), 1e-30)),
+           "argmax_equal": float((a.argmax(-1) == b.argmax(-1)).mean())}
+    if tokens_kv8 is not None:
+        out["tokens_equal"] = float((np.asarray(tokens_kv8) == np.asarray(tokens_plain)).mean())
+    return out

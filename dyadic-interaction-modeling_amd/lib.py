@@ -63,6 +63,13 @@ SIGNATURES = {
     "dimx_set_sampler_filter": (c_int, [c_void_p, c_int, c_float, c_float]),
     "dimx_set_cross_lookahead": (c_int, [c_void_p, c_int, c_int]),
     "dimx_cross_lookahead": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "dimx_cross_kv8_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "dimx_set_cross_kv8": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "dimx_cross_kv8": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
+    "dimx_op_kv8_quantize": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dimx_op_decode_attn_kv8": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int,
+                                        c_int, c_int, c_void_p]),
     "dimx_stream_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "dimx_stream_begin": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_uint64, c_void_p, c_size_t,
                                   c_void_p]),

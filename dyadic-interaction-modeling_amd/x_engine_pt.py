@@ -211,7 +211,7 @@ def _select(pending, skip_degenerate, world, device):
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
                         select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, window_prefill=False, guidance=None,
-                        **forward_kw):
+                        kv8=False, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -275,7 +275,17 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
 
     ``guidance`` s: every generation is a guided one (dimx.guidance, ``SLMFT.forward(guidance=s)``).  A guided generation draws one
     sample per clip, so the ``beam_size`` tries are ``beam_size`` passes (the reference's loop) and ``select`` must be "fd"; not with
-    ``decode="beam"`` (ValueError).  None (default) leaves every path as it is."""
+    ``decode="beam"`` (ValueError).  None (default) leaves every path as it is.
+
+    ``kv8``: every generation reads an FP8 copy of the context K / V in its decode steps (dimx.kv8, ``SLMFT.forward(kv8=True)``).
+    Such a generation draws one sample per clip too, so the tries are ``beam_size`` passes and ``select`` must be "fd"; not with
+    ``decode="beam"`` (ValueError).  False (default) leaves every path as it is."""
+    if kv8:
+        if decode == "beam" or select != "fd":
+            raise ValueError("evaluate_test_epoch(kv8=True) applies to decode='sample' with select='fd': an FP8 cross K/V generation "
+                             "draws one sample per clip")
+        batched_samples = False
+        forward_kw = dict(forward_kw, kv8=True)
     if guidance is not None:
         if decode == "beam" or select != "fd":
             raise ValueError("evaluate_test_epoch(guidance=...) applies to decode='sample' with select='fd': a guided generation "

@@ -374,6 +374,29 @@ int dimx_set_sampler_filter(dimx_handle h, int kind, float a, float b);
 int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead);
 /* The handle's current setting (either pointer may be NULL). */
 int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
+/* FP8 cross-attention K/V for generation (csrc/decode_attn_kv8.hip; the definition is dimx/kv8.py).  Opt-in handle state, like the
+ * cross-attention window; variant 0 only (DIMX_ERR_ARG otherwise), either numeric mode; DIMX_ERR_STATE while a streaming session is
+ * open (sessions neither read nor change the setting).  With a buffer set, dimx_generate / dimx_generate_prompted /
+ * dimx_generate_guided quantise every layer's context K / V once, ahead of the first decode step, into OCP e4m3fn codes with one f32
+ * scale per (clip, head, key), and every decode step's cross attention streams the codes instead of the caches: half the bytes of
+ * the bf16 caches, a quarter of the f32 ones.
+ *   - The buffer is the caller's: dimx_cross_kv8_bytes(h, B, T) bytes of device memory, 256-byte aligned; the workspace queries
+ *     return what they returned before (the unquantised caches stay: a prompt's prefill, offline or windowed, reads them).
+ *     Layout, with Tp = (T + 7) / 8 * 8, H and depth the decoder's heads and layers, every block rounded up to 256 bytes:
+ *         layer 0: K codes [B, H, Tp, 64] uint8 | V codes [B, H, Tp, 64] uint8 | K scales [B, H, Tp] f32 | V scales [B, H, Tp] f32
+ *         layer 1: the same, ... layer depth - 1.
+ *     Rows t >= T of a (clip, head) are never written and never read.  0 = the shape is not supported.
+ *   - buf = NULL turns it off: every call then launches what it launched before the setting existed, bit for bit.  The pointer is
+ *     part of what keys the captured step graph.
+ *   - The decoder-layer kernel is not taken (as under the window); the chain route and the per-op route stay.  With the window on
+ *     the kv8 cross attention is the windowed one.  In a guided step it runs over the conditional rows only.  The regeneration after
+ *     a chain fault keeps the setting and reuses the codes.
+ *   - n_samples > 1 and dimx_generate_beam return DIMX_ERR_ARG before any launch; a buffer below dimx_cross_kv8_bytes(h, B, T) for
+ *     the call's shape returns DIMX_ERR_WORKSPACE. */
+size_t dimx_cross_kv8_bytes(dimx_handle h, int B, int T);
+int dimx_set_cross_kv8(dimx_handle h, void* buf, size_t bytes);
+/* The handle's current setting (either pointer may be NULL). */
+int dimx_cross_kv8(dimx_handle h, void** buf, size_t* bytes);
 /* Streaming sessions (csrc/stream.hip; the schedule is dimx/stream.py): the speaker arrives in pieces, the listener's
  * tokens leave as soon as they are due.  A session fed a clip in pieces computes what dimx_encode_ctx + dimx_generate under
  * dimx_set_cross_lookahead(1, lookahead) compute on the whole clip: the speaker encoders are causal, so the context rows of the new
@@ -780,6 +803,26 @@ int dimx_op_decode_attn_tab(int dtype, const void* q, int q_ld, int q_is_f32, in
 int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, void* kcache, void* vcache,
                             void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n_keys, const uint8_t* kmask,
                             int kmask_ld, int rows_per_clip, float scale, int nsplit, int lookahead, void* stream);
+/* FP8 cross K/V, the quantiser (csrc/decode_attn_kv8.hip; dimx/kv8.py quantize): cache [B, H, Tp, 64] of dtype (DIMX_F32 / DIMX_BF16),
+ * as dimx_encode_ctx(for_generate = 1) writes a layer's K or V.  Rows 0 .. T - 1 of every (clip, head) become 64 OCP e4m3fn codes
+ * (codes [B, H, Tp, 64] uint8) and one scale (scales [B, H, Tp] f32): scale = amax / 448 (a row with amax < 2^-60: scale 0, codes 0),
+ * code = e4m3fn(clamp(x / scale, +-448)), round to nearest even, both divisions IEEE f32.  Rows at or past T are neither read nor
+ * written.  DIMX_ERR_ARG (nothing launched) for a null or misaligned operand (cache / codes 16 bytes, scales 4) or T outside 1 .. Tp. */
+int dimx_op_kv8_quantize(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, void* stream);
+/* ... and the one-query cross attention over such codes, as dimx_generate launches it with dimx_set_cross_kv8: the arguments of
+ * dimx_op_decode_attn_win with kcodes / kscale / vcodes / vscale ([B, H, Tmax, 64] uint8, [B, H, Tmax] f32) in place of the caches,
+ * out_dtype (DIMX_F32 / DIMX_BF16: the type of out [B, o_ld], the handle's operand type) in place of dtype, and win: 0 = the keys
+ * j < n_keys (step_dev and lookahead unused), 1 = the keys j < clamp(*step_dev + 2 + lookahead, 1, n_keys).  q is f32 split-K slabs
+ * (q_is_f32 must be 1; nslab 1..8, summed in slab order).  Scores are scale * q . (kscale[j] * codes[j]); a masked key scores
+ * -FLT_MAX, a row with every key masked is the mean of the dequantised V over the keys.  Codes and scales at or past the key bound
+ * are never read; the windowed form has the bits of the plain form called with n_keys = that bound; no atomics, repeats are
+ * bit-identical; nsplit = 0 on out_dtype = DIMX_F32 depends on Tmax only.  DIMX_ERR_ARG (nothing launched) for a null or misaligned
+ * operand (q / codes / out 16 bytes, scales 4; q_ld, slab_stride multiples of 4, o_ld of 4 (f32) / 8 (bf16)), n_keys outside
+ * 1 .. min(Tmax, 2048), kmask_ld < n_keys, win without a step counter, or rows_per_clip > 1. */
+int dimx_op_decode_attn_kv8(int out_dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, const uint8_t* kcodes,
+                            const float* kscale, const uint8_t* vcodes, const float* vscale, void* out, int o_ld, int B, int H, int Tmax,
+                            const int32_t* step_dev, int n_keys, const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit,
+                            int lookahead, int win, void* stream);
 /* Append attention (csrc/stream_attn.hip; what a streaming session launches for every encoder layer): the self attention of the c
  * new rows of every clip over a growing K / V cache.  qkv [B*c, ld] f32 (row b*c + i; q | k | v at columns 0, H*64, 2*H*64, ld >= 3*H*64,
  * the layout the q/k/v projection writes), kcache / vcache [B, H, Tmax, 64] of dtype (DIMX_F32 / DIMX_BF16), n0 rows already cached,
