@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libdimx_hip.so")
 SOURCES = ["gemm.hip", "gemm_x3.hip", "gemm256.hip", "norm.hip", "attention.hip", "attention_tr.hip", "mlp_fused.hip", "decode_attn.hip", "vq.hip", "elementwise.hip", "kv_prefill.hip", "chain.hip", "model.hip", "generate.hip", "ops.hip", "stream_attn.hip", "win_attn.hip", "stream.hip",
            "train_kernels.hip", "train_attn.hip", "train_vq.hip", "train.hip", "lstm.hip", "train_lstm.hip", "train_spk.hip", "fd_select.hip", "mesh_metrics.hip",
            "listener_metrics.hip", "kmeans_sid.hip", "seq_score.hip", "beam.hip", "consensus.hip", "retrieval.hip", "decode_attn_kv8.hip"]
-HEADERS = ["common.hpp", "model.hpp", "stages.hpp", "train.hpp", "decode_attn_body.hpp", "online_softmax_body.hpp", "frechet.hpp", "pick_gather.hpp", os.path.join("..", "..", "include", "dimx.h")]
+HEADERS = ["common.hpp", "model.hpp", "stages.hpp", "train.hpp", "decode_attn_body.hpp", "sample_pick.hpp", "online_softmax_body.hpp", "frechet.hpp", "pick_gather.hpp", os.path.join("..", "..", "include", "dimx.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-ffp-contract=on"]
 # per-source additions: beside MFMAs the SLP vectoriser's v_pk_add_f32 / v_pk_mul_f32 cost more than the two scalar instructions

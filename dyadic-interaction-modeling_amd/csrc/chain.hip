@@ -20,6 +20,7 @@
 
 #include "common.hpp"
 #include "decode_attn_body.hpp"
+#include "sample_pick.hpp"
 
 namespace dimx {
 namespace {
@@ -626,6 +627,22 @@ __device__ __forceinline__ void layer_barrier(unsigned* ctr, unsigned target, un
     lds_barrier();
 }
 
+// HEAD: one arrival per block on the parameter block's counter; the last of the launch's blocks advances the step word and the
+// chain epoch (not on a call's first step, whose launch runs the position the words already name) and clears the first-step
+// flag.  Plain stores, visible to the step's later launches across the kernel boundary, as sample_kernel's are.
+__device__ __forceinline__ void head_arrive(int32_t* p, int w_step, int w_epoch, int w_first) {
+    const unsigned prev = atomicAdd((unsigned*)(p + 8), 1u);
+    if (prev == gridDim.x - 1) {
+        p[8] = 0;
+        if (w_first) {
+            p[14] = 0;
+        } else {
+            p[0] = w_step + 1;
+            p[9] = w_epoch + 1;
+        }
+    }
+}
+
 #define LAYER_STAMP(i)                                                              \
     do {                                                                            \
         if (a.prof && threadIdx.x == 0) a.prof[blockIdx.x * 16 + (i)] = wall_clock64(); \
@@ -633,13 +650,31 @@ __device__ __forceinline__ void layer_barrier(unsigned* ctr, unsigned target, un
 
 // TAB0: the first layer's launch when its self attention reads K / V from the table over the token ids (decode_attn_body.hpp,
 // TAB) -- an instantiation of its own, not a branch around two inlined bodies: 13 waves per CU leave no register room for both
-template <int NCB_SO, int NCB_CQ, int NCB_CO, bool TAB0 = false>
+//
+// HEAD (needs TAB0; SampleHeadArgs in common.hpp): stage 0, the sampler of the previous step's logits.  The logits of row b are
+// complete at the kernel boundary behind the final chain launch, and the consumer of row b's token is this CU: wave 0 runs
+// sample_kernel's top-k route for the CU's clip (sample_pick.hpp: one body for both kernels; its candidate lists lie in the
+// score rows, idle until the attention), hands the token to the block through LDS, and the attention waves read q / new k /
+// new v from the token's f32 table row.  No group barrier: the only other product, the embedding row x[b, :], is read by the
+// XCD's other CUs behind barrier 1 (L1-bypassing loads: written during this launch).  The step word, the chain epoch and the
+// first-step flag are read once per block, here; thread 0 of the weight wave arrives on the parameter block's counter inside
+// barrier 1 -- every wave of its block has used the words by then -- and the last arrival of the 256 advances them.
+template <int NCB_SO, int NCB_CQ, int NCB_CO, bool TAB0 = false, bool HEAD = false>
 __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerChainArgs a) {
+    static_assert(!HEAD || TAB0, "the sampling head feeds the table form of the self attention");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ float sm_mr[2 * kGroupRows];
+    __shared__ int sm_tok;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int g = (int)(xcc_id() & (a.fault ? 6u : 7u)), li = blockIdx.x >> 3;
-    const unsigned epoch = (unsigned)((a.step ? *a.step : 0) + a.epoch_add);
+    int w_step = 0, w_epoch = 0, w_first = 1;   // HEAD: the parameter block's words as this block read them
+    if constexpr (HEAD) {
+        w_step = __hip_atomic_load(a.head.params, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w_epoch = __hip_atomic_load(a.head.params + 9, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w_first = __hip_atomic_load(a.head.params + 14, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const int n_self = w_first ? w_step : w_step + 1;   // HEAD: keys of the self attention = the position this launch runs
+    const unsigned epoch = HEAD ? (unsigned)((w_first ? w_epoch : w_epoch + 1) + a.epoch_add) : (unsigned)((a.step ? *a.step : 0) + a.epoch_add);
     const unsigned stamp = epoch + 1u;
     unsigned seen_old = 0;
     if (tid == 0) seen_old = atomicExch(a.seen + g * kGroupCUs + li, stamp);
@@ -647,6 +682,7 @@ __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerCha
     const int nrows = a.B - row0 < kGroupRows ? a.B - row0 : kGroupRows;
     if (nrows <= 0) {  // the whole group leaves (all of its blocks take this branch)
         if (tid == 0 && seen_old == stamp) atomicOr(a.err, 1u);
+        if (HEAD && tid == 0) head_arrive(a.head.params, w_step, w_epoch, w_first);
         return;
     }
     if (tid == 0 && seen_old == stamp) atomicOr(a.err, 1u);  // two blocks claimed the same (XCD, slot): not a bijection
@@ -664,12 +700,40 @@ __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerCha
         const int n0 = li * a.g_so.cols;
         issue_panel_nw<AUX_PLAIN, 1>((const bf16*)a.g_so.W, a.g_so.ldw, n0, n0 + a.g_so.cols - 1, a.g_so.rows_pad, a.g_so.nkt, base + a.off_W1, 0,
                                      lane);
-    } else if (has_clip) {
+    }
+    if constexpr (HEAD) {
+        // ---- stage 0: the token of this CU's clip.  First step of a call: the start token, as the start launches left it in the
+        // history (and its embedding row in x).  Later steps: wave 0 samples the previous step's logits.
+        if (has_clip) {
+            if (w_first) {
+                if (tid == 0) sm_tok = a.head.hist[(size_t)clip * a.head.hist_ld + (w_step < a.head.hist_ld ? w_step : a.head.hist_ld - 1)];
+            } else if (wave == 0) {
+                const int t = sample_head_row(a.head, clip, w_step, sc, (int*)(sc + 128), lane);
+                if (lane == 0) sm_tok = t;
+            }
+        }
+        lds_barrier();   // not __syncthreads: wave 12's weight burst stays in flight
+        LAYER_STAMP(13);
+        if (has_clip) {
+            // a token outside the table cannot leave it (the sampler's history clamp; the token column keeps what was sampled)
+            const unsigned tk = (unsigned)sm_tok < (unsigned)kSampleVocab ? (unsigned)sm_tok : (unsigned)kSampleVocab - 1u;
+            if (!w_first) {   // next input row of the residual stream, one float4 per thread from the block's last waves down
+                const float4* src = (const float4*)(a.head.emb_table + (size_t)tk * C);
+                float4* dst = (float4*)(a.x + (size_t)clip * C);
+                for (int i = kLayerThreads - 1 - tid; i < C / 4; i += kLayerThreads) dst[i] = src[i];
+            }
+            if (wave < kAttnWaves)
+                decode_attn_body<bf16, true, true, 1, kAttnWaves, false, true, false, true>(a.sa, clip, sc, a.sc_stride, nullptr, nullptr, nullptr,
+                                                                                          a.head.qkv0 + (size_t)tk * a.head.qkv0_N, n_self);
+        }
+    } else if (wave != kAttnWaves && has_clip) {
         decode_attn_body<bf16, true, true, 1, kAttnWaves, false, TAB0>(a.sa, clip, sc, a.sc_stride, nullptr, nullptr, nullptr);
     }
     LAYER_STAMP(1);
     target += kGroupCUs;
-    layer_barrier(ctr, target, a.err, [] {});
+    layer_barrier(ctr, target, a.err, [&] {
+        if (HEAD && tid == kAttnWaves * 64) head_arrive(a.head.params, w_step, w_epoch, w_first);
+    });
     LAYER_STAMP(2);
 
     // ---- stage 2: x += o . Wso^T (this CU's column slice of the group's 32 rows), y = bf16(x), partial row sums
@@ -684,7 +748,8 @@ __global__ __launch_bounds__(kLayerThreads) void xcd_layer_kernel(const LayerCha
                 const int e = tid + i * kThreads;
                 const int j = e >> 10, m = (e >> 5) & 31, col = j * 32 + (e & 31);
                 const int mm = m < nrows ? m : nrows - 1, cc = col < a.g_so.cols ? col : a.g_so.cols - 1;
-                xs[i] = a.x[(size_t)(row0 + mm) * C + n0 + cc];
+                const float* xp = a.x + (size_t)(row0 + mm) * C + n0 + cc;
+                xs[i] = HEAD ? ld_sc1_f32(xp) : *xp;   // HEAD: the rows were written by the XCD's other CUs during this launch
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the rows, wave 12: the weight slice
@@ -959,11 +1024,26 @@ int launch_layer_chain(const LayerChainArgs& a0, hipStream_t s) {
                          (uintptr_t)a.sa.tab % 16 == 0,
                      DIMX_ERR_ARG, "layer_chain: table form with rows of %d, K at %d, V at %d, history stride %d", a.sa.tab_ld, a.sa.tab_koff,
                      a.sa.tab_voff, a.sa.hist_ld);
+        if (a.head.on) {   // the sampler of the previous step's logits as the launch's first stage
+            const SampleHeadArgs& hd = a.head;
+            DIMX_REQUIRE(hd.logits && hd.tokens && hd.emb_table && hd.qkv0 && hd.params && hd.hist == a.sa.hist && hd.hist_ld == a.sa.hist_ld &&
+                             hd.nslab >= 1 && hd.ld_logits >= kSampleVocab && hd.tok_ld >= 1 && a.sa.tab_rows == kSampleVocab && a.C % 4 == 0 &&
+                             hd.qkv0_N % 4 == 0 && (uintptr_t)hd.qkv0 % 16 == 0 && (uintptr_t)hd.emb_table % 16 == 0 && (uintptr_t)a.x % 16 == 0 &&
+                             a.sa.q_f32 && (const float*)a.sa.knew - (const float*)a.sa.q + kAttnWaves * 64 <= hd.qkv0_N &&
+                             (const float*)a.sa.vnew - (const float*)a.sa.q + kAttnWaves * 64 <= hd.qkv0_N && (!hd.logits_out || hd.logits_out_ld >= 1),
+                         DIMX_ERR_ARG, "layer_chain: sampling head with a %d-row table, rows of %d, logits stride %d", a.sa.tab_rows, hd.qkv0_N,
+                         hd.ld_logits);
+            (void)hipFuncSetAttribute((const void*)xcd_layer_kernel<2, 1, 2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
+            hipLaunchKernelGGL((xcd_layer_kernel<2, 1, 2, true, true>), dim3(8 * kGroupCUs), dim3(kLayerThreads), lds, s, a);
+            DIMX_HIP(hipGetLastError());
+            return DIMX_OK;
+        }
         (void)hipFuncSetAttribute((const void*)xcd_layer_kernel<2, 1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
         hipLaunchKernelGGL((xcd_layer_kernel<2, 1, 2, true>), dim3(8 * kGroupCUs), dim3(kLayerThreads), lds, s, a);
         DIMX_HIP(hipGetLastError());
         return DIMX_OK;
     }
+    DIMX_REQUIRE(!a.head.on, DIMX_ERR_ARG, "layer_chain: the sampling head needs the table form of the self attention");
     (void)hipFuncSetAttribute((const void*)xcd_layer_kernel<2, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
     hipLaunchKernelGGL((xcd_layer_kernel<2, 1, 2>), dim3(8 * kGroupCUs), dim3(kLayerThreads), lds, s, a);
     DIMX_HIP(hipGetLastError());

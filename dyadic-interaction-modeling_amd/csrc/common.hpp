@@ -465,6 +465,34 @@ struct ChainArgs {
     int fault;  // test hook (dimx_debug_chain_fault): the blocks of XCD 2i+1 claim XCD 2i's slots -- a non-bijective placement
     int offA1, offW1, offRed1, offA2, offW2, offRed2;        // LDS plan, set by the launcher
 };
+// The sampling head of the first layer's launch (chain.hip, xcd_layer_kernel HEAD; needs the table form of its self attention).
+// Layer 0's input is a function of the sampled token alone, and the CU that owns clip b is the consumer of row b's token: one of
+// its waves runs sample_kernel's top-k route (sample_pick.hpp) on the logits the previous step left, and the attention waves take
+// q / new k / new v from row qkv0[token] of the f32 table -- no sampler launch, no copy of that row into slab 0.
+// `params` is the call's parameter block (gen_params_kernel): word 0 the step word, 2.. the sampler's dev_params, 8 the arrival
+// counter, 9 the chain epoch, 14 the first-step flag.  Every block reads words 0 / 9 / 14 once at entry.  Flag set: no logits yet,
+// the head is skipped, the token is hist[b][step], and x is what the start-token launches wrote.  Flag clear: the head samples
+// step `word`, the launch runs position word + 1 at epoch + 1, and the block that arrives last advances both words -- after
+// every block has read them; the step's later launches see the advanced values across the kernel boundary.
+struct SampleHeadArgs {
+    int on;                     // 0 = a launch without the head
+    const float* logits;        // [B, ld_logits] x nslab slabs, added in slab order
+    int ld_logits, nslab;
+    long slab_stride;
+    int top_k;
+    const float* noise;         // [steps, rows_total, 512] or nullptr (the counter-based generator)
+    int row0, rows_total;
+    int32_t* tokens;            // [B, tok_ld], column = the step sampled
+    int tok_ld;
+    float* logits_out;          // [B, logits_out_ld, 512] or nullptr
+    int logits_out_ld;
+    const float* emb_table;     // [512][C] -> x[b, :]
+    const float* qkv0;          // [512][qkv0_N] f32: q | k | v of a token
+    int qkv0_N;
+    int32_t* hist;              // == sa.hist, written at position step + 1
+    int hist_ld;
+    int32_t* params;
+};
 // The attention half of a decoder layer as ONE launch (chain.hip, xcd_layer_kernel; round 5): self attention -> out-projection +
 // residual -> (deferred LayerNorm) cross-q projection -> cross attention -> out-projection + residual.  Clip i of group g is CU
 // slot i of XCD g for both attentions and all three projections split their columns over the XCD's 32 CUs, so every hand-off
@@ -488,7 +516,8 @@ struct LayerChainArgs {
     unsigned* err;
     int fault;
     unsigned long long* prof;       // tuning only: [256][16] phase stamps
-    int sc_stride;                  // floats per (clip, head) score row in LDS
+    SampleHeadArgs head;            // head.on: the sampler of the previous step's logits is this launch's first stage
+    int sc_stride;                // floats per (clip, head) score row in LDS
     int off_base, off_A1, off_W1, off_A2, off_W2, off_W3, off_A3;  // LDS plan (bytes), set by the launcher
 };
 bool layer_chain_supported(const LayerChainArgs& a, int cu_count);

@@ -113,9 +113,14 @@ template <int EPC> __device__ __forceinline__ void load_f32_slabs(const float* p
 // win_keys(step counter, lookahead, n_keys).  Everything below runs on that n as the plain cross form would with n_keys = n --
 // rows at or past n are never addressed (load_batch clamps to n - 1), the mask bias, the wave split and the sums are the same
 // code -- so the result has the bits of the plain form called with n_keys = n.
-template <typename T, bool SELF, bool QF32, int NSPLIT, int NW, bool QSC1 = false, bool TAB = false, bool WIN = false>
+//
+// ROWQ (the table form behind the sampling head of the layer kernel, chain.hip): q / new k / new v are the f32 table row `rowq`
+// of the token the head just sampled (q at 0, k and v at the offsets a.knew / a.vnew have from a.q) instead of row b of slab 0,
+// which on that route nobody fills, and the key count is `n_self`, the step word the block read at entry, not a load of
+// a.step.  One slab, so the values and their conversion order are those of the slab form: same bits.
+template <typename T, bool SELF, bool QF32, int NSPLIT, int NW, bool QSC1 = false, bool TAB = false, bool WIN = false, bool ROWQ = false>
 __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int block_id, float* sc, int sc_stride, float* red_m,
-                                                 float* red_l, float* red_acc) {
+                                                 float* red_l, float* red_acc, const float* rowq = nullptr, int n_self = 0) {
     constexpr int EPC = 16 / sizeof(T);
     constexpr int LPK = 64 / EPC;   // lanes per key: 8 (bf16) / 16 (f32)
     constexpr int KPI = 64 / LPK;   // keys per wave-wide load: 8 / 4
@@ -124,6 +129,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
     constexpr int PPB = NW / NSPLIT; // (clip, head) pairs per block
     static_assert(!TAB || SELF, "the table form is a self-attention form");
     static_assert(!WIN || !SELF, "the windowed form is a cross-attention form");
+    static_assert(!ROWQ || (TAB && QF32 && !QSC1), "the row form rides on the table form with f32 operands");
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pib = wave / NSPLIT, part = wave % NSPLIT;
@@ -152,13 +158,17 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
         load_ids(jfirst + jstep, idb);
     }
     float qv[EPC], knv[EPC], vnv[EPC];
-    if (QSC1)  // one f32 slab, written by other CUs of this XCD during this launch
+    if constexpr (ROWQ) {
+        load_f32_chunk<EPC>(rowq + h * 64 + ch * EPC, qv);
+        load_f32_chunk<EPC>(rowq + ((const float*)a.knew - (const float*)a.q) + h * 64 + ch * EPC, knv);
+        load_f32_chunk<EPC>(rowq + ((const float*)a.vnew - (const float*)a.q) + h * 64 + ch * EPC, vnv);
+    } else if (QSC1)  // one f32 slab, written by other CUs of this XCD during this launch
         load_f32_chunk_sc1<EPC>((const float*)a.q + (size_t)b * a.q_ld + h * 64 + ch * EPC, qv);
     else if (QF32)
         load_f32_slabs<EPC>((const float*)a.q + (size_t)b * a.q_ld + h * 64 + ch * EPC, a.nslab, a.slab_stride, qv);
     else
         load_chunk<T, EPC>((const T*)a.q + (size_t)b * a.q_ld + h * 64 + ch * EPC, qv);
-    if (SELF) {
+    if (SELF && !ROWQ) {
         if (QF32) {
             load_f32_slabs<EPC>((const float*)a.knew + (size_t)b * a.kv_ld + h * 64 + ch * EPC, a.nslab, a.slab_stride, knv);
             load_f32_slabs<EPC>((const float*)a.vnew + (size_t)b * a.kv_ld + h * 64 + ch * EPC, a.nslab, a.slab_stride, vnv);
@@ -168,7 +178,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, int bl
         }
     }
     int n = a.n_keys;
-    if (SELF) n = *a.step;  // keys already in the cache
+    if (SELF) n = ROWQ ? n_self : *a.step;  // keys already in the cache
     if constexpr (WIN) n = win_keys(*a.step, a.lookahead, a.n_keys);
     const float scale2 = a.scale * 1.4426950408889634f;
 

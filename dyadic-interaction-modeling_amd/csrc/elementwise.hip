@@ -2,6 +2,7 @@
 // embedding gathers, context assembly, token bookkeeping, cross-entropy/argmax over the 512-entry
 // vocabulary and the top-k / softmax / noise-argmax sampler of the autoregressive loop.
 #include "common.hpp"
+#include "sample_pick.hpp"
 
 namespace dimx {
 namespace {
@@ -102,20 +103,6 @@ __global__ __launch_bounds__(256) void ce_argmax_kernel(const float* __restrict_
     }
 }
 
-__device__ __forceinline__ uint32_t f32_order_key(float f) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ uint64_t splitmix(uint64_t key, uint64_t ctr) {
-    uint64_t z = key + (ctr + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-constexpr int kSampleVocab = 512;   // rows of the logits / embedding table the sampler is written for (8 x 64 lanes)
-
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
     uint32_t o;
     o = (uint32_t)xor_lane_i32<32>((int)v); v = o < v ? o : v;
@@ -203,6 +190,9 @@ __device__ __forceinline__ void sample_body(const float* __restrict__ logits, in
     float v[8];
     float mx = -3.0e38f;
     int mi = 0;
+    if constexpr (!GUIDED) {
+        sample_load_row(lr, nslab, slab_stride, lane, v, mx, mi);
+    } else {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         v[c] = lr[lane + 64 * c];
@@ -224,6 +214,7 @@ __device__ __forceinline__ void sample_body(const float* __restrict__ logits, in
             mx = v[c];
             mi = lane + 64 * c;
         }
+    }
     }
     if (logits_out) {  // per-step dump of the raw logits: [rows, steps, 512]
         float* lo = logits_out + ((size_t)row * logits_out_ld + (GUIDED && !tok_col_from_step ? 0 : step)) * 512;
@@ -286,100 +277,18 @@ __device__ __forceinline__ void sample_body(const float* __restrict__ logits, in
                     if (e[c] >= lim && key[c] < kmin) kmin = key[c];
                 thr = wave_min_u32(kmin);
             }
-        } else if (top_k > 0 && top_k < 512) {
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t cand = thr | (1u << bit);
-                int cnt = 0;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) cnt += __popcll(__ballot(key[c] >= cand));
-                if (cnt >= top_k) {
-                    thr = cand;
-                    // exactly k keys at or above the candidate: that IS the top-k set (every key >= its minimum is
-                    // already counted), the remaining bits could only tighten the threshold onto that minimum
-                    if (cnt == top_k) break;
-                }
-            }
+        } else {
+            thr = sample_topk_threshold(key, top_k);
         }
         if (keep_out) {   // dimx_op_sample_filtered: the kept set as this launch decided it
 #pragma unroll
             for (int c = 0; c < 8; ++c) keep_out[(size_t)row * 512 + lane + 64 * c] = key[c] >= thr ? 1 : 0;
         }
         if (!greedy) {
-        // Only the <= top_k (+ ties) survivors need a probability and a noise draw: compact them to one per lane
-        // (2 rounds cover up to 128 survivors; more than that -- massive ties -- falls back to the per-element loop).
-        const float inv_t = 1.0f / temperature;
-        int nsurv_lane = 0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) nsurv_lane += key[c] >= thr ? 1 : 0;
-        int incl = nsurv_lane;  // inclusive prefix over lanes
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl_up(incl, o);
-            if (lane >= o) incl += up;
-        }
-        const int total = __shfl(incl, 63);
-        float best = -1.f;
-        int bi = 0x7fffffff;
-        auto score = [&](float pv, float zs, int i) {
-            float q;
-            if (noise) {
-                q = noise[((size_t)step * rows_total + row0 + row) * 512 + i];
-            } else {
-                const uint64_t r = splitmix(seed, ((uint64_t)step * rng_tot + rng_off + row0 + row) * 512 + i);
-                const float u = (float)(r >> 40) * (1.0f / 16777216.0f);
-                q = fmaxf(-log1pf(-u), 9.313225746154785e-10f);
-            }
-            const float sc = (pv / zs) / q;
-            if (sc > best || (sc == best && i < bi)) {
-                best = sc;
-                bi = i;
-            }
-        };
-        if (total <= 128) {
             __shared__ float cand_v[4][128];
             __shared__ int cand_i[4][128];
-            float* cv = cand_v[threadIdx.x >> 6];
-            int* ci = cand_i[threadIdx.x >> 6];
-            int pos = incl - nsurv_lane;
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                if (key[c] >= thr) {
-                    cv[pos] = v[c];
-                    ci[pos] = lane + 64 * c;
-                    ++pos;
-                }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            float pv[2] = {0.f, 0.f};
-            int pi[2] = {0, 0};
-            float zsum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const int k = lane + 64 * r;
-                if (k < total) {
-                    pv[r] = expf((cv[k] - mx) * inv_t);
-                    pi[r] = ci[k];
-                    zsum += pv[r];
-                }
-            }
-            zsum = wave_sum(zsum);
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                if (lane + 64 * r < total) score(pv[r], zsum, pi[r]);
-        } else {
-            float p[8];
-            float zsum = 0.f;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                p[c] = key[c] >= thr ? expf((v[c] - mx) * inv_t) : 0.f;
-                zsum += p[c];
-            }
-            zsum = wave_sum(zsum);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) score(p[c], zsum, lane + 64 * c);
-        }
-        wave_argmax(best, bi);
-        tok = bi;
+            const SampleNoise nz = {noise, seed, step, rows_total, row0, row, rng_tot, rng_off};
+            tok = sample_survivor(v, key, thr, mx, temperature, nz, cand_v[threadIdx.x >> 6], cand_i[threadIdx.x >> 6], lane);
         }  // !greedy
     }
     }  // !forced
@@ -393,7 +302,10 @@ __device__ __forceinline__ void sample_body(const float* __restrict__ logits, in
         if (hist && lane == 0 && (int)step + 1 < hist_ld)
             hist[(size_t)(row + R) * hist_ld + step + 1] = tok < 0 ? 0 : (tok >= kSampleVocab ? kSampleVocab - 1 : tok);
     if (x_next) {  // next step's decoder input: token embedding row (fused embed_step)
-        const float2* src = (const float2*)(emb_table + (size_t)tok * emb_C);
+        // Non-finite logits (a chain fault's garbage, before the call that suffered it regenerates the batch) leave no survivor to win
+        // the arg-max and tok = 0x7fffffff: the token column keeps it, but no table is addressed with it
+        const int tk = tok < 0 ? 0 : (tok >= kSampleVocab ? kSampleVocab - 1 : tok);
+        const float2* src = (const float2*)(emb_table + (size_t)tk * emb_C);
         float2* dst = (float2*)(x_next + (size_t)row * emb_C);
         const bool with_pos = pos_table && (int)step + 1 < pos_rows;   // legacy decoder: + pos_emb[next position] * dim^-0.5
         const float2* pr = with_pos ? (const float2*)(pos_table + (size_t)(step + 1) * emb_C) : nullptr;
@@ -411,7 +323,7 @@ __device__ __forceinline__ void sample_body(const float* __restrict__ logits, in
                 // the first layer's q/k/v of this token is a row of a table (no positional term in this decoder: the layer's
                 // input depends on the token alone).  Its loads go out with the embedding row's, behind the same dependent
                 // hop on the token, and land in slab 0 of the step's q/k/v buffer (the launcher checks qkv0_N <= 12 * 256).
-                const float4* qs = (const float4*)(qkv0_table + (size_t)tok * qkv0_N);
+                const float4* qs = (const float4*)(qkv0_table + (size_t)tk * qkv0_N);
                 float4* qd = (float4*)(qkv0_out + (size_t)row * qkv0_N);
                 const int nq = qkv0_N / 4;
                 float4 w[12];
@@ -697,6 +609,7 @@ __global__ void gen_params_kernel(int32_t* base, int groups, float temperature, 
     p[11] = __builtin_bit_cast(int32_t, filter_a);
     p[12] = __builtin_bit_cast(int32_t, filter_b);
     p[13] = __builtin_bit_cast(int32_t, guidance);
+    p[14] = 1;   // no step of this call has run yet: the sampling head of the first layer's launch (chain.hip) clears it
 }
 
 // dst[b, step, :] = src[b, :]  (optional per-step logits dump of generate)

@@ -396,6 +396,21 @@ static int cross_attention_multi(const StepCtx& c, int l, const DecodeAttnArgs& 
     return launch_attention_tr(ta, c.st);
 }
 
+// Route sample_head: what finish_sample would pass to the sampler launch, for the head of layer 0's launch (the logits are the
+// final chain launch's single slab; the parameter block is the group's 16 words behind s.step)
+static void head_args(const StepCtx& c, SampleHeadArgs& hd) {
+    const GenScratch& s = c.s;
+    const GenRequest& q = c.gc->req;
+    memset(&hd, 0, sizeof(hd));
+    hd.on = 1;
+    hd.logits = s.logits; hd.ld_logits = c.V; hd.nslab = 1; hd.slab_stride = s.st_lg;
+    hd.top_k = c.gc->top_k; hd.noise = q.noise; hd.row0 = c.row0; hd.rows_total = c.gc->R;
+    hd.tokens = c.tokens; hd.tok_ld = c.n; hd.logits_out = c.logits_out; hd.logits_out_ld = c.n;
+    hd.emb_table = c.h->dec.tok_emb; hd.qkv0 = c.r->qkv0; hd.qkv0_N = 3 * c.inner;
+    hd.hist = s.hist; hd.hist_ld = c.T;
+    hd.params = s.step;
+}
+
 // Self attention, cross attention and their out-projections; leaves y = the feed-forward's input.  *pending: the slabs of the
 // previous residual projection not yet folded into x (in: the last layer's feed-forward; the two chain routes fold their own).
 static int attention_half(const StepCtx& c, int l, int* pending) {
@@ -416,6 +431,7 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         LayerChainArgs lc;
         memset(&lc, 0, sizeof(lc));
         DIMX_REQUIRE(layer_args(c, l, sa, ca, lc), DIMX_ERR_STATE, "generate: layer %d lost its layer-kernel weights after the route was resolved", l);
+        if (l == 0 && r.sample_head) head_args(c, lc.head);
         DIMX_TRY(launch_layer_chain(lc, c.st));
     } else if (r.chain) {
         DIMX_TRY(launch_decode_attn(sa, c.st));
@@ -582,6 +598,7 @@ static int gen_step(const StepCtx& c) {
     }
     int nlg = 0;
     DIMX_TRY(logits(c, pending, &nlg));
+    if (c.r->sample_head) return DIMX_OK;   // the next step's first launch samples these logits; the call's last ones: generate_impl
     return c.r->beam ? finish_beam(c, nlg) : c.r->guided ? finish_guided(c, nlg) : finish_sample(c, nlg);
 }
 
@@ -623,6 +640,10 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
             r.layer_kernel[l] = layer_args(c, l, self_args(c, l, 1), cross_args(c, l), lc) && layer_chain_supported(lc, h->cu_count);
         }
     }
+    // The sampler as the head of layer 0's launch: that launch in its table form, the top-k sampler on the final chain launch's one
+    // slab of logits (no to_logits.bias), every row its own clip in one group, and nothing else ending the step or forcing tokens
+    r.sample_head = h->use_sample_head && r.kv0 && r.layer_kernel[0] && r.logits_chain && h->filter_kind == DIMX_FILTER_TOP_K && !q.beam &&
+                    !r.guided && q.pr.step0 == 0 && q.pr.Pmax <= 1 && G == 1 && q.S == 1 && dg.num_tokens == 512 && dg.dim % 4 == 0;
     return DIMX_OK;
 }
 
@@ -637,7 +658,7 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
     k.G = r.G; k.S = r.S;
     k.chain = r.chain; k.defer = r.defer; k.logits_chain = r.logits_chain; k.multi_tr = r.multi_tr; k.fault_inject = r.fault_inject;
     for (int l = 0; l < 8; ++l) k.layer_kernel |= r.layer_kernel[l] ? 1u << l : 0u;
-    k.qkv0 = r.qkv0; k.kv0 = r.kv0;
+    k.qkv0 = r.qkv0; k.kv0 = r.kv0; k.sample_head = r.sample_head;
     k.prompt_len = q.pr.len; k.ld_prompt = q.pr.ld; k.Pmax = q.pr.Pmax;
     k.filter_kind = h->filter_kind;
     k.beam = q.beam ? *q.beam : BeamCall{};
@@ -896,6 +917,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         // the chain kernels answer a fault by a regeneration of the whole call, which a session cannot offer
         route.chain = route.defer = route.logits_chain = route.multi_tr = false;
         for (bool& lk : route.layer_kernel) lk = false;
+        route.sample_head = false;
         route.win = true;
         route.lookahead = sess->lookahead;
         route.kv8 = false;
@@ -906,6 +928,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     // tables
     if (route.qkv0) DIMX_TRY(qkv0_table_build(h, s, R, st, pr.step0));
     if (route.kv0) ++h->kv0_generations;
+    if (route.sample_head) ++h->sample_head_generations;
     // prefill
     if (pr.step0 > 0 && !keep_prefill) {
         // the prefill forms no logits: those columns of logits_out read zero
@@ -969,6 +992,8 @@ static int generate_impl(dimx_handle h, const GenRequest& q, bool keep_prefill, 
     if (prefill_only) return DIMX_OK;
     // steps
     DIMX_TRY(gen_run_steps(h, run, run.nrun));
+    // route sample_head: every step sampled its predecessor's logits; the last step's go through the plain sampler, once
+    if (run.route.sample_head && run.nrun > 0) DIMX_TRY(finish_sample(run.ctx[0], 1));
     // join
     DIMX_TRY(gen_groups_join(h, run.G, q.st, run.gs));
     if (run.route.chain && run.G == 1) {
@@ -1000,9 +1025,10 @@ extern "C" {
 // DIMX_LAYER_PROF=1 (tuning): the phase stamps of the LAST step's layer launches (100 MHz wall clock), mean / max over blocks
 static int print_layer_prof(dimx_handle h) {
     DIMX_HIP(hipEventSynchronize(h->chain_err_ev));
-    static const char* names[13] = {"start", "self attention done", "barrier 1", "rows + W1 landed", "out-proj stored", "barrier 2",
+    static const char* names[14] = {"start", "self attention done", "barrier 1", "rows + W1 landed", "out-proj stored", "barrier 2",
                                     "y rows + W2 landed", "cross-q stored", "barrier 3", "cross attention done", "barrier 4",
-                                    "rows + W3 landed", "out-proj stored"};
+                                    "rows + W3 landed", "out-proj stored", "head done"};
+    static const int order[14] = {0, 13, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12};   // the sampling head's stamp (layer 0) is slot 13
     std::vector<unsigned long long> hp((size_t)8 * 256 * 16);
     DIMX_HIP(hipMemcpy(hp.data(), h->layer_prof_dev, hp.size() * 8, hipMemcpyDeviceToHost));
     for (int l = 0; l < h->decg.depth; ++l) {
@@ -1013,7 +1039,8 @@ static int print_layer_prof(dimx_handle h) {
         if (t0 == ~0ull) continue;
         fprintf(stderr, "dimx layer-kernel stamps, layer %d (us after the first block's start; mean / max over blocks)\n", l);
         double prev = 0;
-        for (int i = 0; i < 13; ++i) {
+        for (int k = 0; k < 14; ++k) {
+            const int i = order[k];
             double sum = 0, mx = 0;
             int n = 0;
             for (int b = 0; b < 256; ++b)
@@ -1235,6 +1262,7 @@ int dimx_cross_kv8(dimx_handle h, void** buf, size_t* bytes) {
 int dimx_chain_faults(dimx_handle h) { return h ? h->chain_faults : 0; }
 int dimx_qkv0_table_builds(dimx_handle h) { return h ? h->qkv0_builds : 0; }
 int dimx_kv0_table_generations(dimx_handle h) { return h ? h->kv0_generations : 0; }
+int dimx_sample_head_generations(dimx_handle h) { return h ? h->sample_head_generations : 0; }
 
 int dimx_debug_chain_fault(dimx_handle h, int n_calls) {
     DIMX_REQUIRE(h && n_calls >= 0, DIMX_ERR_ARG, "debug_chain_fault: bad argument");

@@ -938,6 +938,7 @@ int dimx_create(dimx_handle* h, int device_id, const dimx_dims* dims, int numeri
     c->multi_tr = getenv("DIMX_NO_MULTI_TR") ? 0 : 1;
     c->use_qkv0_table = getenv("DIMX_NO_QKV0_TABLE") ? 0 : 1;
     c->use_kv0_table = getenv("DIMX_NO_KV0_TABLE") ? 0 : 1;
+    c->use_sample_head = getenv("DIMX_NO_SAMPLE_HEAD") ? 0 : 1;
     if (getenv("DIMX_LAYER_PROF")) {
         void* p = nullptr;
         if (hipMalloc(&p, (size_t)8 * 256 * 16 * 8) == hipSuccess) {

@@ -133,6 +133,8 @@ struct StepRoute {
     const float* qkv0 = nullptr;   // the first layer's q/k/v table or nullptr
     const void* kv0 = nullptr;     // the first layer's K / V table (the bf16 image, or the q/k/v table itself in the f32 mode): its self
                                    // attention reads rows of it through the token history and keeps no cache; nullptr = the cache
+    bool sample_head = false;      // the sampler is the first stage of layer 0's launch (chain.hip HEAD): a step is {head + layer 0,
+                                   // ..., logits}, its first step skips the head, and one plain sampler launch ends the call
     const BeamCall* beam = nullptr;
     bool fault_inject = false;     // test hook: the chain kernels are launched with fault = 1
     int G = 1, S = 1;              // clip groups, samples per clip
@@ -149,6 +151,7 @@ struct GraphKey {
     bool chain, defer, logits_chain, multi_tr, fault_inject;
     unsigned layer_kernel;    // bit l = StepRoute::layer_kernel[l]
     const void *qkv0, *kv0;
+    bool sample_head;
     const void* prompt_len;   // prompted generation: the sampler's other prompt arguments (`start` is the prompt itself)
     int ld_prompt, Pmax;
     int filter_kind;          // the sampler kernel's instantiation; the filter's real-valued parameters live in device memory
@@ -161,7 +164,7 @@ struct GraphKey {
         return ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && noise == o.noise && start == o.start && mask == o.mask &&
                tokens == o.tokens && logits_out == o.logits_out && G == o.G && S == o.S && chain == o.chain && defer == o.defer &&
                logits_chain == o.logits_chain && multi_tr == o.multi_tr && fault_inject == o.fault_inject &&
-               layer_kernel == o.layer_kernel && qkv0 == o.qkv0 && kv0 == o.kv0 && prompt_len == o.prompt_len &&
+               layer_kernel == o.layer_kernel && qkv0 == o.qkv0 && kv0 == o.kv0 && sample_head == o.sample_head && prompt_len == o.prompt_len &&
                ld_prompt == o.ld_prompt && Pmax == o.Pmax && filter_kind == o.filter_kind && beam == o.beam && xwin_on == o.xwin_on &&
                xwin_lookahead == o.xwin_lookahead && guided == o.guided && branch_out == o.branch_out && kv8 == o.kv8;
     }
@@ -247,6 +250,10 @@ struct dimx_ctx {
     int use_kv0_table = 1;
     void* kv0_image = nullptr;          // [num_tokens][2 * heads * dim_head] bf16
     int kv0_generations = 0;            // generate calls (regenerations included) that ran the table form
+    // The sampler as the first stage of layer 0's launch (chain.hip, xcd_layer_kernel HEAD): one dependent launch less per token on
+    // the route of the headline (resolve_route has the gate).  DIMX_NO_SAMPLE_HEAD=1: the sampler launch, for A/B runs.
+    int use_sample_head = 1;
+    int sample_head_generations = 0;    // generate calls (regenerations included) whose steps ran the head
     // sampler generator window of a sharded batch (dimx_set_shard): this handle generates clips
     // [shard_row_off, shard_row_off + B) of shard_rows_total (0 = the call's own B)
     int shard_row_off = 0, shard_rows_total = 0;

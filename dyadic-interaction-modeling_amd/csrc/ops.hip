@@ -588,7 +588,8 @@ int dimx_op_gemm_ln(int out_dtype, const void* A, const void* Ws, void* C, int M
 static int op_layer_chain(const float* qkv, int nslab, long slab_stride, void* sk, void* sv, int T, const void* ck, const void* cv,
                           int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq, const float* colsum_cq,
                           const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
-                          int call_index, float scale, void* scratch, void* prof, void* stream, const OpTabArgs* tab) {
+                          int call_index, float scale, void* scratch, void* prof, void* stream, const OpTabArgs* tab,
+                          const SampleHeadArgs* head = nullptr) {
     DIMX_REQUIRE(qkv && sk && sv && ck && cv && w_so && w_cq && colsum_cq && w_co && x && y && o && qc && stats && step && scratch,
                  DIMX_ERR_ARG, "op_layer_chain: null argument");
     constexpr int H = 12, D = 64, inner = H * D, C = 1152;
@@ -619,6 +620,7 @@ static int op_layer_chain(const float* qkv, int nslab, long slab_stride, void* s
     lc.err = lc.counters + 768;
     lc.step = nullptr;          // the counters' epoch is the call index; the self-attention reads its own step pointer (sa.step)
     lc.epoch_add = call_index;
+    if (head) lc.head = *head;  // ... or, with the sampling head, both come from the head's parameter block
     lc.prof = (unsigned long long*)prof;
     lc.sc_stride = ((T > n_keys ? T : n_keys) + 15) / 16 * 16;
     int cu = 0, dev = 0;
@@ -645,6 +647,44 @@ int dimx_op_layer_chain_tab(const float* qkv, int nslab, long slab_stride, void*
     const OpTabArgs t = {tab, tab_ld, tab_koff, tab_voff, tab_rows, hist, hist_ld};
     return op_layer_chain(qkv, nslab, slab_stride, sk, sv, T, ck, cv, Tp, n_keys, kmask, w_so, w_cq, colsum_cq, w_co, x, y, o, qc, stats, B,
                           step, call_index, scale, scratch, prof, stream, &t);
+}
+
+/* the first layer's launch with the sampling head (SampleHeadArgs in common.hpp): `params` is a parameter block of 16 words laid
+ * out as dimx_generate's (0 step, 2 temperature, 4-5 seed, 6 row offset, 7 rows of the whole batch, 8 arrival counter, 9 chain
+ * epoch, 14 first-step flag); the counters' epoch is word 9 (+ 1 when the head runs), so a zeroed scratch wants -1 there (0 with
+ * the flag set).  qkv0 [512][2304] f32: q | k | v of a token; logits [>= B, 512]; emb_table [512][1152]. */
+int dimx_op_layer_chain_head(const float* qkv0, const float* logits, int top_k, const float* exp_noise, int rows_total, int32_t* tokens,
+                             int tok_ld, float* logits_out, const float* emb_table, int32_t* params, void* sk, void* sv, int T, const void* ck,
+                             const void* cv, int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq,
+                             const float* colsum_cq, const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, float scale,
+                             void* scratch, void* prof, const void* tab, int tab_ld, int tab_koff, int tab_voff, int tab_rows, int32_t* hist,
+                             int hist_ld, void* stream) {
+    DIMX_REQUIRE(qkv0 && logits && tokens && emb_table && params && hist && tab, DIMX_ERR_ARG, "op_layer_chain_head: null argument");
+    const OpTabArgs t = {tab, tab_ld, tab_koff, tab_voff, tab_rows, hist, hist_ld};
+    SampleHeadArgs hd;
+    memset(&hd, 0, sizeof(hd));
+    hd.on = 1;
+    hd.logits = logits; hd.ld_logits = 512; hd.nslab = 1; hd.top_k = top_k; hd.noise = exp_noise; hd.rows_total = rows_total;
+    hd.tokens = tokens; hd.tok_ld = tok_ld; hd.logits_out = logits_out; hd.logits_out_ld = tok_ld;
+    hd.emb_table = emb_table; hd.qkv0 = qkv0; hd.qkv0_N = 3 * 12 * 64; hd.hist = hist; hd.hist_ld = hist_ld; hd.params = params;
+    return op_layer_chain(qkv0, 1, 0, sk, sv, T, ck, cv, Tp, n_keys, kmask, w_so, w_cq, colsum_cq, w_co, x, y, o, qc, stats, B, params, 0, scale,
+                          scratch, prof, stream, &t, &hd);
+}
+
+/* the sampler launch of a generation step, on a parameter block as above: token column = the step word, the next history
+ * position, the token's embedding row into x_next and its q/k/v table row into qkv0_out, step word and epoch advanced */
+int dimx_op_sample_step(const float* logits, int R, int top_k, const float* exp_noise, int rows_total, int32_t* tokens, int tok_ld,
+                        float* logits_out, const float* emb_table, int C, float* x_next, const float* qkv0, float* qkv0_out, int qkv0_N,
+                        int32_t* hist, int hist_ld, int32_t* params, void* stream) {
+    DIMX_REQUIRE(logits && tokens && params && R > 0, DIMX_ERR_ARG, "op_sample_step: null argument or R < 1");
+    SampleArgs sm;
+    sm.logits = logits; sm.ld_logits = 512; sm.R = R; sm.nslab = 1; sm.rows_total = rows_total; sm.top_k = top_k; sm.noise = exp_noise;
+    sm.step_dev = params; sm.step_rw = params; sm.dev_params = params + 2; sm.done_ctr = (unsigned*)(params + 8); sm.epoch_rw = params + 9;
+    sm.tokens = tokens; sm.tok_ld = tok_ld; sm.tok_col_from_step = 1; sm.logits_out = logits_out; sm.logits_out_ld = tok_ld;
+    sm.emb_table = emb_table; sm.emb_C = C; sm.x_next = x_next;
+    sm.qkv0_table = qkv0; sm.qkv0_out = qkv0_out; sm.qkv0_N = qkv0_N;
+    sm.hist = hist; sm.hist_ld = hist_ld;
+    return launch_sample(sm, (hipStream_t)stream);
 }
 
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise, uint64_t seed,

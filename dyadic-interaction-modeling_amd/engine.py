@@ -555,6 +555,12 @@ class Engine:
         instead of that layer's cache (0 = the cache: beam search, a prompt, no q/k/v table, or DIMX_NO_KV0_TABLE=1)."""
         return int(self.lib.dimx_kv0_table_generations(self.h))
 
+    def sample_head_generations(self):
+        """how many generations of this handle sampled inside the first decoder layer's launch instead of a sampler launch
+        per step (0 = the sampler launch: any route but the bf16 layer-kernel one with the token table and the top-k
+        filter, or DIMX_NO_SAMPLE_HEAD=1)."""
+        return int(self.lib.dimx_sample_head_generations(self.h))
+
     def debug_chain_fault(self, n_calls=1):
         """test hook: the next n_calls generate() calls run their chain kernels on a non-bijective placement."""
         L.check(self.lib.dimx_debug_chain_fault(self.h, int(n_calls)), "dimx_debug_chain_fault")
@@ -1303,6 +1309,41 @@ def op_layer_chain(qkv, sk, sv, ck, cv, n_keys, kmask, w_so, w_cq, colsum_cq, w_
         L.check(lib.dimx_op_layer_chain(*args, L.stream_ptr(dev)), "dimx_op_layer_chain")
     torch.cuda.synchronize(dev)
     return y, o, qc, stats, int(scratch[768].item())
+
+
+def op_layer_chain_head(qkv0, logits, top_k, noise, rows_total, tokens, emb, params, hist, tab, ck, cv, n_keys, kmask, w_so, w_cq,
+                        colsum_cq, w_co, x, B, scale=0.125, tab_koff=0, tab_voff=768, tab_rows=512, logits_out=None):
+    """The first decoder layer's launch with the sampling head (include/dimx.h dimx_op_layer_chain_head): params is the 16-word
+    int32 parameter block, tokens [rows, n] int32, hist [rows, T] int32, the other operands as op_layer_chain's table form.
+    Synchronises and returns (y, o, qc, stats, flags)."""
+    lib = L.load()
+    dev = x.device
+    rows = x.shape[0]
+    o = torch.empty(rows, 768, dtype=torch.bfloat16, device=dev)
+    qc = torch.empty(rows, 768, dtype=torch.float32, device=dev)
+    y = torch.empty(rows, 1152, dtype=torch.bfloat16, device=dev)
+    stats = torch.zeros(8, 32, 32, 2, dtype=torch.float32, device=dev)
+    scratch = torch.zeros(1024, dtype=torch.int32, device=dev)
+    dummy = torch.zeros(16, dtype=torch.bfloat16, device=dev)   # the table form touches no self-attention cache
+    L.check(lib.dimx_op_layer_chain_head(L.ptr(qkv0), L.ptr(logits), int(top_k), L.ptr(noise), int(rows_total), L.ptr(tokens),
+                                         tokens.stride(0), L.ptr(logits_out), L.ptr(emb), L.ptr(params), L.ptr(dummy), L.ptr(dummy),
+                                         hist.shape[1], L.ptr(ck), L.ptr(cv), ck.shape[2], int(n_keys), L.ptr(kmask), L.ptr(w_so),
+                                         L.ptr(w_cq), L.ptr(colsum_cq), L.ptr(w_co), L.ptr(x), L.ptr(y), L.ptr(o), L.ptr(qc), L.ptr(stats),
+                                         int(B), float(scale), L.ptr(scratch), None, L.ptr(tab), tab.stride(0), int(tab_koff),
+                                         int(tab_voff), int(tab_rows), L.ptr(hist), hist.stride(0), L.stream_ptr(dev)),
+            "dimx_op_layer_chain_head")
+    torch.cuda.synchronize(dev)
+    return y, o, qc, stats, int(scratch[768].item())
+
+
+def op_sample_step(logits, R, top_k, noise, rows_total, tokens, emb, x_next, qkv0, qkv0_out, hist, params, logits_out=None):
+    """The sampler launch of a generation step on a 16-word parameter block (include/dimx.h dimx_op_sample_step)."""
+    lib = L.load()
+    L.check(lib.dimx_op_sample_step(L.ptr(logits), int(R), int(top_k), L.ptr(noise), int(rows_total), L.ptr(tokens), tokens.stride(0),
+                                    L.ptr(logits_out), L.ptr(emb), emb.shape[1], L.ptr(x_next), L.ptr(qkv0), L.ptr(qkv0_out),
+                                    qkv0.shape[1], L.ptr(hist), hist.stride(0), L.ptr(params), L.stream_ptr(logits.device)),
+            "dimx_op_sample_step")
+    torch.cuda.synchronize(logits.device)
 
 
 # ---------------------------------------------------------------- host plumbing of the metric operators

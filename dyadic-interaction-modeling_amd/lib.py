@@ -157,6 +157,7 @@ SIGNATURES = {
     "dimx_chain_faults": (c_int, [c_void_p]),
     "dimx_qkv0_table_builds": (c_int, [c_void_p]),
     "dimx_kv0_table_generations": (c_int, [c_void_p]),
+    "dimx_sample_head_generations": (c_int, [c_void_p]),
     "dimx_lstm_faults": (c_int, [c_void_p]),
     "dimx_mesh_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dimx_op_lstm_layer": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p),
@@ -214,6 +215,12 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                         c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                         c_int, c_void_p]),
+    "dimx_op_layer_chain_head": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "dimx_op_sample_step": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "dimx_op_gemm_ln": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                 c_void_p, c_void_p]),
     "dimx_op_fd_select_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -465,6 +465,12 @@ int dimx_qkv0_table_builds(dimx_handle h);
  * a per-row token history instead of appending to and streaming the layer's cache (same bits); this counts the generations of a
  * handle that did (0 = the cache: see above, or DIMX_NO_KV0_TABLE=1 in the environment at dimx_create). */
 int dimx_kv0_table_generations(dimx_handle h);
+/* And the sampler a launch of its own: the consumer of a row's token is the CU that runs the row's first-layer attention.  On
+ * the bf16 chain route -- the table form above in the decoder-layer kernel, the top-k filter, one sample per clip in one group,
+ * no beam search, guidance or prompt, no to_logits.bias -- the first layer's launch samples the previous step's logits itself
+ * (same tokens and logits), a step is one launch shorter and one plain sampler launch ends the call; this counts the
+ * generations of a handle that ran so (0 = the sampler launch: see above, or DIMX_NO_SAMPLE_HEAD=1 at dimx_create). */
+int dimx_sample_head_generations(dimx_handle h);
 /* Test hook: the next n_calls dimx_generate calls launch their chain kernels with a deliberately non-bijective
  * (XCD, CU slot) placement (the blocks of every odd XCD claim the slots of its even neighbour). */
 int dimx_debug_chain_fault(dimx_handle h, int n_calls);
@@ -909,6 +915,25 @@ int dimx_op_layer_chain_tab(const float* qkv, int nslab, long slab_stride, void*
                             const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, const int32_t* step,
                             int call_index, float scale, void* scratch, void* prof, const void* tab, int tab_ld, int tab_koff,
                             int tab_voff, int tab_rows, const int32_t* hist, int hist_ld, void* stream);
+/* ... with the sampler of the previous step's logits as the launch's first stage (csrc/chain.hip, xcd_layer_kernel HEAD).  `params`
+ * is a parameter block of 16 int32 words laid out as dimx_generate's: 0 the step word, 2 the temperature's bits, 4-5 the seed,
+ * 6 / 7 the row offset and row count of the whole batch (generator window), 8 the arrival counter (0), 9 the chain epoch, 14 the
+ * first-step flag.  Flag clear: row b's token is sampled from logits [>= B, 512] at step = word 0 (top-k filter, injected noise
+ * [steps, rows_total, 512] or the seeded generator), written to tokens[b, step], hist[b, step + 1] and as emb_table [512][1152]
+ * row into x; the self attention runs position step + 1 on q | k | v = row `token` of qkv0 [512][2304] f32, and the launch leaves
+ * words 0 and 9 advanced by one.  Flag set: nothing is sampled, the token is hist[b, step], the words stay and the flag is
+ * cleared.  The group counters' epoch is word 9 (+ 1 with the flag clear): a zeroed scratch wants -1 there (0 with the flag set). */
+int dimx_op_layer_chain_head(const float* qkv0, const float* logits, int top_k, const float* exp_noise, int rows_total, int32_t* tokens,
+                             int tok_ld, float* logits_out, const float* emb_table, int32_t* params, void* sk, void* sv, int T, const void* ck,
+                             const void* cv, int Tp, int n_keys, const uint8_t* kmask, const void* w_so, const void* w_cq,
+                             const float* colsum_cq, const void* w_co, float* x, void* y, void* o, float* qc, float* stats, int B, float scale,
+                             void* scratch, void* prof, const void* tab, int tab_ld, int tab_koff, int tab_voff, int tab_rows, int32_t* hist,
+                             int hist_ld, void* stream);
+/* The sampler launch of a generation step on such a parameter block (what the head replaces): tokens[r, step], hist[r, step + 1],
+ * x_next[r, :] = emb_table[token] (C floats), qkv0_out[r, :] = qkv0[token] (qkv0_N floats), words 0 and 9 advanced by one. */
+int dimx_op_sample_step(const float* logits, int R, int top_k, const float* exp_noise, int rows_total, int32_t* tokens, int tok_ld,
+                        float* logits_out, const float* emb_table, int C, float* x_next, const float* qkv0, float* qkv0_out, int qkv0_N,
+                        int32_t* hist, int hist_ld, int32_t* params, void* stream);
 /* Best-of-S selection by Frechet distance, the selection step of the test-time protocol (csrc/fd_select.hip; reference
  * code/x_engine_pt.py:255-270 around code/metrics/eval_utils.py:6-46).  All pointers are device memory.
  *   y_true f32 [B, L, .]: clip j, frame t starts at y_true + j*yt_clip_stride + t*yt_frame_stride (elements; feature stride 1)
