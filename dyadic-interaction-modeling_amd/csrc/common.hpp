@@ -416,8 +416,31 @@ struct Kv8AttnArgs {
     const int32_t* step;
 };
 int launch_decode_attn_kv8(const Kv8AttnArgs& a, hipStream_t s);
-// rows 0 .. T - 1 of every (clip, head) of one cache [B,H,Tp,64] (dtype) -> codes [B,H,Tp,64] / scales [B,H,Tp]
-int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s);
+// rows 0 .. T - 1 of every (clip, head) of one cache [B,H,Tp,64] (dtype) -> codes [B,H,Tp,64] / scales [B,H,Tp]; cache_T > 0: the
+// cache is [B,H,cache_T,64] (a generation's self caches)
+int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s, int cache_T = 0);
+// The self form over FP8 self-attention caches (decode_attn_kv8.hip; dimx/kv8.py self_step): one launch quantises this step's k / v
+// row, stores it at position n and attends over the rows 0 .. n, the own row taken from registers
+struct Kv8SelfArgs {
+    const float* q;        // f32 split-K slabs [nslab][B, ld]: q | new k | new v of head h at q / knew / vnew + h*64, summed in slab order
+    const float* knew;
+    const float* vnew;
+    int ld, nslab;
+    long slab_stride;      // elements between slabs
+    uint8_t* kcodes;       // [B,H,Tmax,64] e4m3fn codes: rows 0 .. n - 1 are read, row n is written
+    float* kscale;         // [B,H,Tmax]
+    uint8_t* vcodes;
+    float* vscale;
+    int Tmax;
+    void* out;             // [B, o_ld] of out_dtype
+    int out_dtype, o_ld;
+    int B, H;
+    const int32_t* step;   // device scalar: n, the rows already cached; nullptr = n_max
+    int n_max;             // n is clamped to 0 .. n_max (< Tmax): no row at or past Tmax can be addressed whatever *step holds
+    float scale;
+    int force_nsplit;      // tests: waves per (row, head) (0 = automatic)
+};
+int launch_decode_attn_self_kv8(const Kv8SelfArgs& a, hipStream_t s);
 
 int launch_vq_argmin(const float* z, int N, const float* Et /*[128][512]*/, const float* ee /*[512]*/,
                      int32_t* idx, float* best_d, float* margin, hipStream_t s);

@@ -51,18 +51,10 @@ template <> __device__ __forceinline__ void load_row16<bf16>(const bf16* p, floa
     for (int e = 0; e < 8; ++e) { v[e] = a[e]; v[8 + e] = b[e]; }
 }
 
-// Rows 0 .. T - 1 of every (clip, head) of one cache [BH, Tp, 64] -> codes / scales (dimx/kv8.py quantize): four lanes per row,
-// 16 elements each.  Rows at or past T are neither read nor written.
-template <typename T>
-__global__ __launch_bounds__(256) void kv8_quant_kernel(const T* cache, long rows, int Tp, int Tn, uint8_t* codes, float* scales) {
-    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long row = tid >> 2;
-    const int ch = (int)(tid & 3);
-    const bool live = row < rows;
-    const long r = live ? row : rows - 1;   // every lane of the wave stays active for the butterfly
-    const long at = (r / Tn) * Tp + r % Tn;
-    float x[16];
-    load_row16<T>(cache + at * 64 + ch * 16, x);
+// One row of 64 floats held by four neighbouring lanes, 16 elements each -> the lane's 16 codes and the row's scale (dimx/kv8.py
+// quantize).  Every lane of the four must be active (the butterfly).  The one quantiser of this file: kv8_quant_kernel and the self
+// form's append both call it, so their bits cannot differ.
+__device__ __forceinline__ float quant_row16(const float (&x)[16], uint4& codes) {
     float amax = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) amax = fmaxf(amax, fabsf(x[e]));
@@ -79,8 +71,27 @@ __global__ __launch_bounds__(256) void kv8_quant_kernel(const T* cache, long row
         p = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], p, true);
         w[i] = zero ? 0u : (uint32_t)p;
     }
+    codes = make_uint4(w[0], w[1], w[2], w[3]);
+    return scale;
+}
+
+// Rows 0 .. T - 1 of every (clip, head) of one cache [BH, Tp, 64] -> codes / scales (dimx/kv8.py quantize): four lanes per row,
+// 16 elements each.  Rows at or past T are neither read nor written.
+// Tc: the cache's rows per (clip, head) where they differ from the codes' (the generation's self caches are [R, H, T, 64]).
+template <typename T>
+__global__ __launch_bounds__(256) void kv8_quant_kernel(const T* cache, long rows, int Tc, int Tp, int Tn, uint8_t* codes, float* scales) {
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long row = tid >> 2;
+    const int ch = (int)(tid & 3);
+    const bool live = row < rows;
+    const long r = live ? row : rows - 1;   // every lane of the wave stays active for the butterfly
+    const long at = (r / Tn) * Tp + r % Tn;
+    float x[16];
+    load_row16<T>(cache + ((r / Tn) * Tc + r % Tn) * 64 + ch * 16, x);
+    uint4 w;
+    const float scale = quant_row16(x, w);
     if (live) {
-        *(uint4*)(codes + at * 64 + ch * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        *(uint4*)(codes + at * 64 + ch * 16) = w;
         if (ch == 0) scales[at] = scale;
     }
 }
@@ -260,21 +271,239 @@ __global__ __launch_bounds__(256) void decode_attn_kv8_kernel(const Kv8AttnArgs 
     }
 }
 
+// The self form over FP8 self caches (dimx/kv8.py self_step): the kernel above with decode_attn_body's SELF duties.  q and this
+// step's k / v come from the projection's f32 slabs; n = *step rows are cached and the keys are the positions 0 .. n.  Every wave
+// of a (row, head) quantises the new k / v row in registers (quant_row16: each key group of four lanes holds the whole row), so
+// the new row's codes are a uint4 per lane like a loaded one and its scales a float like a loaded one: the batch that contains
+// position n swaps them in where it consumes that key, and the loops below are the cross form's over n + 1 keys.  One wave stores
+// codes and scales at position n; loads are clamped to n - 1 (none at all at n = 0), so no load depends on that store and rows
+// past n are neither read nor written.  n itself is clamped to n_max < Tmax.
+// Four blocks per CU asked for: the new row's registers would otherwise lift the kernel past 128 VGPRs and cost it the fourth wave
+// per SIMD the cross form has (118 .. 122 VGPRs, no scratch, with the bound; 130 .. 136 without).
+template <typename TO, int NSPLIT>
+__global__ __launch_bounds__(256, 4) void decode_attn_self_kv8_kernel(const Kv8SelfArgs a) {
+    constexpr int EPC = 16;          // codes per 16-byte lane load
+    constexpr int LPK = 4;           // lanes per key
+    constexpr int KPI = 16;          // keys per wave-wide load
+    constexpr int U = 4;             // loads per batch
+    constexpr int KB = U * KPI;      // keys per batch == lanes of a wave
+    constexpr int PPB = 4 / NSPLIT;  // (row, head) pairs per block
+    static_assert(KB == 64, "a batch is one key per lane");
+    __shared__ float sc[PPB][kMaxKeys];
+    __shared__ float red_m[4], red_l[4];
+    __shared__ float red_acc[4][64];
+
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pib = wave / NSPLIT, part = wave % NSPLIT;
+    const int pair = blockIdx.x * PPB + pib;
+    const bool active = pair < a.B * a.H;
+    const int b = active ? pair / a.H : 0, h = active ? pair % a.H : 0;
+    const int sub = lane / LPK, ch = lane % LPK;
+    const int jfirst = part * KB, jstep = NSPLIT * KB;  // this wave's key batches: jfirst, jfirst + jstep, ...
+
+    float qv[EPC], knv[EPC], vnv[EPC];
+    const size_t at = (size_t)b * a.ld + h * 64 + ch * EPC;
+    load_f32_slabs<EPC>(a.q + at, a.nslab, a.slab_stride, qv);
+    load_f32_slabs<EPC>(a.knew + at, a.nslab, a.slab_stride, knv);
+    load_f32_slabs<EPC>(a.vnew + at, a.nslab, a.slab_stride, vnv);
+    int n = a.step ? *a.step : a.n_max;  // rows already cached
+    n = n < 0 ? 0 : (n > a.n_max ? a.n_max : n);
+    const int tot = n + 1;
+    const float scale2 = a.scale * 1.4426950408889634f;
+
+    const size_t row0 = (size_t)(b * a.H + h) * a.Tmax;
+    const uint8_t* kc = a.kcodes + row0 * 64 + ch * EPC;
+    const uint8_t* vc = a.vcodes + row0 * 64 + ch * EPC;
+    const float* ks = a.kscale + row0;
+    const float* vs = a.vscale + row0;
+    float* s = &sc[pib][0];
+
+    auto load_batch = [&](const uint8_t* base, int j0, uint4 (&r)[U]) {
+        if (n == 0) return;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * KPI + sub;
+            r[u] = ld_stream(base + (size_t)(j < n ? j : n - 1) * 64);
+        }
+    };
+    // the scale of the key whose score this lane scales in batch j0 (position n: the register one, swapped in at the use)
+    auto load_scale = [&](const float* base, int j0) { return n == 0 ? 0.f : base[j0 + lane < n ? j0 + lane : n - 1]; };
+
+    uint4 cur[U] = {}, nxt[U] = {}, vfirst[U] = {};
+    float kcur = 0.f, knxt = 0.f, vcur = 0.f, vnxt = 0.f;
+    if (jfirst < tot) {
+        load_batch(kc, jfirst, cur);
+        load_batch(vc, jfirst, vfirst);
+        kcur = load_scale(ks, jfirst);
+        vcur = load_scale(vs, jfirst);
+    }
+
+    // ---- this step's row: codes and scales in registers, one store by the pair's first wave
+    uint4 kn8, vn8;
+    const float ksn = quant_row16(knv, kn8);
+    const float vsn = quant_row16(vnv, vn8);
+    if (active && part == 0 && sub == 0) {
+        *(uint4*)(a.kcodes + (row0 + n) * 64 + ch * EPC) = kn8;
+        *(uint4*)(a.vcodes + (row0 + n) * 64 + ch * EPC) = vn8;
+        if (ch == 0) {
+            a.kscale[row0 + n] = ksn;
+            a.vscale[row0 + n] = vsn;
+        }
+    }
+
+    // ---- scores: raw dots of the batch, then one key per lane scaled
+    float mx = kNegD;
+    for (int j0 = jfirst; j0 < tot; j0 += jstep) {
+        if (j0 + jstep < tot) {
+            load_batch(kc, j0 + jstep, nxt);
+            knxt = load_scale(ks, j0 + jstep);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * KPI + sub;
+            float kv[EPC];
+            unpack_fp8x16(j == n ? kn8 : cur[u], kv);
+            float d = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) d = fmaf(qv[e], kv[e], d);
+            d = group4_sum(d);
+            if (ch == 0 && j < tot) s[j] = d;
+        }
+        if (j0 + lane < tot) {
+            const float sv = (s[j0 + lane] * (j0 + lane == n ? ksn : kcur)) * scale2;
+            s[j0 + lane] = sv;
+            mx = fmaxf(mx, sv);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        kcur = knxt;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = vfirst[u];
+    mx = wave_max(mx);
+    if (NSPLIT > 1) {
+        if (lane == 0) red_m[wave] = mx;
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < NSPLIT; ++p) mx = fmaxf(mx, red_m[pib * NSPLIT + p]);
+    }
+
+    // ---- o = sum_j p_j vscale_j codes_j, row sum of the unscaled p_j
+    float lsum = 0.f;
+    float acc[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) acc[e] = 0.f;
+    for (int j0 = jfirst; j0 < tot; j0 += jstep) {
+        if (j0 + jstep < tot) {
+            load_batch(vc, j0 + jstep, nxt);
+            vnxt = load_scale(vs, j0 + jstep);
+        }
+        if (j0 + lane < tot) {
+            const float p = exp2f(s[j0 + lane] - mx);
+            lsum += p;
+            s[j0 + lane] = p * (j0 + lane == n ? vsn : vcur);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * KPI + sub;
+            float vv[EPC];
+            unpack_fp8x16(j == n ? vn8 : cur[u], vv);
+            const float p = j < tot ? s[j] : 0.f;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) acc[e] = fmaf(p, vv[e], acc[e]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        vcur = vnxt;
+    }
+    lsum = wave_sum_sel<sizeof(TO) == 2>(lsum);
+    if (NSPLIT > 1) {
+        if (lane == 0) red_l[wave] = lsum;
+        __syncthreads();
+        lsum = 0.f;
+#pragma unroll
+        for (int p = 0; p < NSPLIT; ++p) lsum += red_l[pib * NSPLIT + p];
+    }
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {  // xor 4 .. 32 butterfly over the key sub-groups
+        acc[e] += xor_lane_f32<4>(acc[e]);
+        acc[e] += xor_lane_f32<8>(acc[e]);
+        acc[e] += xor_lane_f32<16>(acc[e]);
+        acc[e] += xor_lane_f32<32>(acc[e]);
+    }
+    if (NSPLIT > 1) {  // combine the partial outputs of the pair's waves in wave order
+        if (sub == 0) {
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) red_acc[wave][ch * EPC + e] = acc[e];
+        }
+        __syncthreads();
+        if (part == 0 && sub == 0) {
+#pragma unroll
+            for (int p = 1; p < NSPLIT; ++p)
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) acc[e] += red_acc[pib * NSPLIT + p][ch * EPC + e];
+        }
+    }
+    if (active && part == 0 && sub == 0) {
+        const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) acc[e] *= inv;
+        store_out16<TO>((TO*)a.out + (size_t)b * a.o_ld + h * 64 + ch * EPC, acc);
+    }
+}
+
 }  // namespace
 
-int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s) {
+int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s, int cache_T) {
     DIMX_REQUIRE(dtype == DIMX_BF16 || dtype == DIMX_F32, DIMX_ERR_ARG, "kv8_quantize: dtype %d", dtype);
     DIMX_REQUIRE(cache && codes && scales, DIMX_ERR_ARG, "kv8_quantize: null operand");
     DIMX_REQUIRE((uintptr_t)cache % 16 == 0 && (uintptr_t)codes % 16 == 0 && (uintptr_t)scales % 4 == 0, DIMX_ERR_ARG,
                  "kv8_quantize: misaligned operand (cache / codes 16 bytes, scales 4)");
     DIMX_REQUIRE(B >= 1 && H >= 1 && T >= 1 && T <= Tp, DIMX_ERR_ARG, "kv8_quantize: B=%d H=%d T=%d Tp=%d (need 1 <= T <= Tp)", B, H, T, Tp);
+    const int Tc = cache_T > 0 ? cache_T : Tp;
+    DIMX_REQUIRE(T <= Tc, DIMX_ERR_ARG, "kv8_quantize: T=%d rows of a cache that holds %d per (clip, head)", T, Tc);
     const long rows = (long)B * H * T;
     const long blocks = (rows * 4 + 255) / 256;
     DIMX_REQUIRE(blocks <= 0x7fffffffL, DIMX_ERR_ARG, "kv8_quantize: %ld rows", rows);
     if (dtype == DIMX_BF16)
-        hipLaunchKernelGGL((kv8_quant_kernel<bf16>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16*)cache, rows, Tp, T, codes, scales);
+        hipLaunchKernelGGL((kv8_quant_kernel<bf16>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16*)cache, rows, Tc, Tp, T, codes, scales);
     else
-        hipLaunchKernelGGL((kv8_quant_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)cache, rows, Tp, T, codes, scales);
+        hipLaunchKernelGGL((kv8_quant_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)cache, rows, Tc, Tp, T, codes, scales);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+int launch_decode_attn_self_kv8(const Kv8SelfArgs& a, hipStream_t s) {
+    DIMX_REQUIRE(a.q && a.knew && a.vnew && a.kcodes && a.kscale && a.vcodes && a.vscale && a.out, DIMX_ERR_ARG, "decode_attn_self_kv8: null operand");
+    DIMX_REQUIRE(a.out_dtype == DIMX_BF16 || a.out_dtype == DIMX_F32, DIMX_ERR_ARG, "decode_attn_self_kv8: out_dtype %d", a.out_dtype);
+    DIMX_REQUIRE(a.B >= 1 && a.H >= 1 && a.Tmax >= 1, DIMX_ERR_ARG, "decode_attn_self_kv8: empty shape");
+    DIMX_REQUIRE(a.n_max >= 0 && a.n_max < a.Tmax && a.n_max < kMaxKeys, DIMX_ERR_ARG,
+                 "decode_attn_self_kv8: %d cached rows outside 0 .. min(Tmax = %d, %d) - 1", a.n_max, a.Tmax, kMaxKeys);
+    DIMX_REQUIRE(a.nslab >= 1 && a.nslab <= 8 && (a.nslab == 1 || a.slab_stride >= (long)a.B * a.ld), DIMX_ERR_ARG,
+                 "decode_attn_self_kv8: nslab=%d (1..8) with slabs %ld apart", a.nslab, a.slab_stride);
+    const int oal = a.out_dtype == DIMX_BF16 ? 8 : 4;
+    DIMX_REQUIRE(a.ld >= a.H * 64 && a.o_ld >= a.H * 64 && a.ld % 4 == 0 && a.slab_stride % 4 == 0 && a.o_ld % oal == 0, DIMX_ERR_ARG,
+                 "decode_attn_self_kv8: ld=%d o_ld=%d slab_stride=%ld (rows of at least H*64, 16-byte multiples)", a.ld, a.o_ld, a.slab_stride);
+    DIMX_REQUIRE((uintptr_t)a.q % 16 == 0 && (uintptr_t)a.knew % 16 == 0 && (uintptr_t)a.vnew % 16 == 0 && (uintptr_t)a.kcodes % 16 == 0 &&
+                     (uintptr_t)a.vcodes % 16 == 0 && (uintptr_t)a.out % 16 == 0 && (uintptr_t)a.kscale % 4 == 0 && (uintptr_t)a.vscale % 4 == 0,
+                 DIMX_ERR_ARG, "decode_attn_self_kv8: misaligned operand (q / k / v / codes / out 16 bytes, scales 4)");
+    // waves per (row, head): launch_decode_attn's rule -- on an f32 handle a function of the cache length only
+    const int pairs = a.B * a.H;
+    int nsplit = 1;
+    if (pairs * 2 <= 3072) nsplit = 2;
+    if (pairs * 4 <= 3072) nsplit = 4;
+    if (a.out_dtype != DIMX_BF16) nsplit = a.Tmax >= 1024 ? 4 : (a.Tmax >= 512 ? 2 : 1);
+    if (a.force_nsplit == 1 || a.force_nsplit == 2 || a.force_nsplit == 4) nsplit = a.force_nsplit;
+    dim3 grid(ceil_div(pairs, 4 / nsplit)), block(256);
+#define KV8S_NS(TT)                                                                                                       \
+    do {                                                                                                                  \
+        if (nsplit == 4) hipLaunchKernelGGL((decode_attn_self_kv8_kernel<TT, 4>), grid, block, 0, s, a);                  \
+        else if (nsplit == 2) hipLaunchKernelGGL((decode_attn_self_kv8_kernel<TT, 2>), grid, block, 0, s, a);             \
+        else hipLaunchKernelGGL((decode_attn_self_kv8_kernel<TT, 1>), grid, block, 0, s, a);                              \
+    } while (0)
+    if (a.out_dtype == DIMX_BF16) KV8S_NS(bf16);
+    else KV8S_NS(float);
+#undef KV8S_NS
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

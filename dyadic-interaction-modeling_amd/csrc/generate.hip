@@ -125,11 +125,14 @@ static size_t kv8_bytes(dimx_handle h, int B, int T) {
     if (!h || h->variant != 0 || h->decg.dim_head != 64 || B < 1 || T < 2 || T > h->d.max_seq_len || tpad(T) > 2048) return 0;
     return (size_t)h->decg.depth * 2 * (kv8_codes_bytes(h, B, T) + kv8_scale_bytes(h, B, T));
 }
-static Kv8Layer kv8_layer(dimx_handle h, int B, int T, int l) {
+static Kv8Layer kv8_layer_of(dimx_handle h, void* buf, int B, int T, int l) {
     const size_t cb = kv8_codes_bytes(h, B, T), sb = kv8_scale_bytes(h, B, T);
-    uint8_t* p = (uint8_t*)h->kv8_buf + (size_t)l * 2 * (cb + sb);
+    uint8_t* p = (uint8_t*)buf + (size_t)l * 2 * (cb + sb);
     return Kv8Layer{p, p + cb, (float*)(p + 2 * cb), (float*)(p + 2 * cb + sb)};
 }
+static Kv8Layer kv8_layer(dimx_handle h, int B, int T, int l) { return kv8_layer_of(h, h->kv8_buf, B, T, l); }
+// FP8 self K/V (dimx_set_self_kv8): the same layout with the R = B * S sequences of the generation in place of the clips
+static Kv8Layer self_kv8_layer(dimx_handle h, int R, int T, int l) { return kv8_layer_of(h, h->self_kv8_buf, R, T, l); }
 
 // what a generate call was asked for; the public entry points fill it after their own argument checks
 struct GenRequest {
@@ -179,6 +182,7 @@ struct StepCtx {
     GenScratch s;
     const void *ck[8], *cv[8];   // the group's clips in the context K / V of every layer
     Kv8Layer kv8[8];             // route kv8: ... and in their FP8 copy
+    Kv8Layer skv8[8];            // route self_kv8: the group's rows in the FP8 self caches of every layer
     const int32_t *start, *forced, *forced_len;
     const uint8_t* ctx_mask;
     int32_t* tokens;
@@ -214,6 +218,12 @@ static StepCtx step_ctx(dimx_handle h, const GenCall& gc, const StepRoute& r, in
             const size_t row0 = (size_t)c.clip0 * heads * c.Tp;
             const Kv8Layer all = kv8_layer(h, q.B, T, l);
             c.kv8[l] = Kv8Layer{all.kcodes + row0 * 64, all.vcodes + row0 * 64, all.kscale + row0, all.vscale + row0};
+        }
+        c.skv8[l] = Kv8Layer{};
+        if (r.self_kv8) {
+            const size_t at = (size_t)row0 * heads * c.Tp;
+            const Kv8Layer all = self_kv8_layer(h, gc.R, T, l);
+            c.skv8[l] = Kv8Layer{all.kcodes + at * 64, all.vcodes + at * 64, all.kscale + at, all.vscale + at};
         }
     }
     c.s.x = s0.x + (size_t)row0 * DD;
@@ -344,6 +354,20 @@ static int cross_attention(const StepCtx& c, int l, const DecodeAttnArgs& ca) {
     return launch_decode_attn_kv8(a, c.st);
 }
 
+// The step's self attention: the cache (or table) form, or (route self_kv8) the same arguments over the FP8 self caches -- one launch
+// quantises and appends this step's row and attends over the codes.  Layer 0 in its table form has no cache and keeps its launch.
+static int self_attention(const StepCtx& c, int l, const DecodeAttnArgs& sa) {
+    if (!c.r->self_kv8 || sa.tab) return launch_decode_attn(sa, c.st);
+    Kv8SelfArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const float*)sa.q; a.knew = (const float*)sa.knew; a.vnew = (const float*)sa.vnew;
+    a.ld = sa.q_ld; a.nslab = sa.nslab; a.slab_stride = sa.slab_stride;
+    a.kcodes = c.skv8[l].kcodes; a.kscale = c.skv8[l].kscale; a.vcodes = c.skv8[l].vcodes; a.vscale = c.skv8[l].vscale; a.Tmax = c.Tp;
+    a.out = sa.out; a.out_dtype = sa.dtype; a.o_ld = sa.o_ld; a.B = sa.B; a.H = sa.H;
+    a.step = sa.step; a.n_max = (c.n < c.Tp ? c.n : c.Tp) - 1; a.scale = sa.scale;
+    return launch_decode_attn_self_kv8(a, c.st);
+}
+
 // round 5: the attention half of a layer as one XCD-local launch (chain.hip xcd_layer_kernel; DIMX_NO_LAYER_CHAIN=1: the four
 // launches, for A/B runs).  False when the layer has no deferred-LayerNorm weights.
 static bool layer_args(const StepCtx& c, int l, const DecodeAttnArgs& sa, const DecodeAttnArgs& ca, LayerChainArgs& lc) {
@@ -434,7 +458,7 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         if (l == 0 && r.sample_head) head_args(c, lc.head);
         DIMX_TRY(launch_layer_chain(lc, c.st));
     } else if (r.chain) {
-        DIMX_TRY(launch_decode_attn(sa, c.st));
+        DIMX_TRY(self_attention(c, l, sa));
         // self out-projection -> x += . -> LayerNorm -> cross q-projection
         if (r.defer)
             DIMX_TRY(chain_site(c, 3 * l, s.o, inner, &h->dec.self_[l].out, 0, h->dec.cross[l].ln_g, &h->dec.cross[l].q_ln, s.qc, inner,
@@ -463,7 +487,7 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x + (size_t)Bc * DD, s.xr + (size_t)Bc * DD, 0, s.st_xr, (unsigned char*)s.y + (size_t)Bc * DD * es,
                                             h->dec.ff[l].ln_g, B - Bc, DD, c.st));
     } else {
-        DIMX_TRY(launch_decode_attn(sa, c.st));
+        DIMX_TRY(self_attention(c, l, sa));
         DIMX_TRY(slab_gemm(c, s.o, inner, h->dec.self_[l].out, s.xr, s.st_xr, pending));
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, *pending, s.st_xr, s.y, h->dec.cross[l].ln_g, B, DD, c.st));
         if (r.multi_tr && !r.win) {
@@ -620,6 +644,7 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     r.win = h->xwin_on != 0;
     r.lookahead = r.win ? h->xwin_lookahead : 0;
     r.kv8 = h->kv8_buf != nullptr;   // the layer kernel streams the caches itself: not taken, exactly as under the window
+    r.self_kv8 = h->self_kv8_buf != nullptr;   // no layer kernel either: it streams the self caches itself
     r.guided = q.guided;
     if (r.guided) r.chain = r.defer = r.logits_chain = r.multi_tr = false;   // the per-op step, as a session takes it (no layer kernel either: it needs chain)
     // one group: every projection launch of the generation has R rows, and so has the table's build
@@ -632,7 +657,7 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     if (r.qkv0 && h->use_kv0_table && !q.beam && q.pr.step0 == 0 && q.pr.Pmax <= 1 && dg.dim_head == 64 && dg.num_tokens <= 512)
         r.kv0 = h->at == DIMX_BF16 ? h->kv0_image : (const void*)h->qkv0_table;
     // the layer kernel depends on shapes only, so its per-layer support is settled here on the arguments the step will pass
-    if (h->use_layer_chain && r.chain && r.defer && q.S == 1 && 4 * dg.depth + 1 <= kChainSites && !r.win && !r.kv8) {
+    if (h->use_layer_chain && r.chain && r.defer && q.S == 1 && 4 * dg.depth + 1 <= kChainSites && !r.win && !r.kv8 && !r.self_kv8) {
         const StepCtx c = step_ctx(h, gc, r, 0, rows, 0, q.st);
         for (int l = 0; l < dg.depth; ++l) {
             LayerChainArgs lc;
@@ -665,6 +690,7 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
     k.xwin_on = r.win ? 1 : 0; k.xwin_lookahead = r.lookahead;
     k.guided = r.guided; k.branch_out = q.branch_out;
     k.kv8 = r.kv8 ? h->kv8_buf : nullptr;
+    k.self_kv8 = r.self_kv8 ? h->self_kv8_buf : nullptr;
     return k;
 }
 
@@ -883,6 +909,13 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         DIMX_REQUIRE(h->kv8_bytes >= kv8_bytes(h, B, T), DIMX_ERR_WORKSPACE, "generate: the FP8 cross K/V buffer holds %zu bytes, B=%d T=%d needs %zu (dimx_cross_kv8_bytes)",
                      h->kv8_bytes, B, T, kv8_bytes(h, B, T));
     }
+    if (h && h->self_kv8_buf && !sess) {   // FP8 self K/V: rows are sequences, the sampler ends the step; a session does not read the setting
+        DIMX_REQUIRE(!q.beam && !q.guided, DIMX_ERR_ARG, "generate: beam search and guidance are not available with dimx_set_self_kv8");
+        DIMX_REQUIRE(kv8_bytes(h, B * S, T) != 0, DIMX_ERR_ARG, "generate: B=%d n_samples=%d T=%d is not supported with dimx_set_self_kv8", B, S, T);
+        DIMX_REQUIRE(h->self_kv8_bytes >= kv8_bytes(h, B * S, T), DIMX_ERR_WORKSPACE,
+                     "generate: the FP8 self K/V buffer holds %zu bytes, B=%d n_samples=%d T=%d needs %zu (dimx_self_kv8_bytes)", h->self_kv8_bytes, B, S, T,
+                     kv8_bytes(h, B * S, T));
+    }
     const int halves = q.guided ? 2 : 1;   // a guided generation decodes every clip twice: 2B rows of self caches, B cross caches
     DIMX_TRY(check_common(h, B, T, q.ws, q.ws_bytes, COMP_DEC, S * halves));
     DIMX_REQUIRE(pr.tok && q.ctx_mask && q.tokens && T >= 2, DIMX_ERR_ARG, "generate: null argument or T < 2");
@@ -921,6 +954,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         route.win = true;
         route.lookahead = sess->lookahead;
         route.kv8 = false;
+        route.self_kv8 = false;
         run.graphs = false;
     }
     // parameters
@@ -936,6 +970,15 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
             DIMX_HIP(hipMemset2DAsync(q.logits_out, (size_t)n * h->decg.num_tokens * 4, 0, (size_t)pr.step0 * h->decg.num_tokens * 4, R, st));
         DIMX_REQUIRE(!pr.win || route.win, DIMX_ERR_STATE, "generate: a windowed prefill without the cross-attention window");
         DIMX_TRY(gen_prefill(h, cp, s, ps, pr, q.ctx_mask, B, T, S, q.tokens, st, pr.win ? &route.lookahead : nullptr, sess ? sess->n_keys : T));
+    }
+    // FP8 self K/V: the rows 0 .. P0 - 2 the prefill stored in every layer's self cache [R, H, T, 64] -> codes + scales; the steps
+    // append from position P0 - 1 on (the regeneration after a chain fault reuses these rows)
+    if (route.self_kv8 && pr.step0 > 0 && !keep_prefill && !prefill_only) {
+        for (int l = 0; l < h->decg.depth; ++l) {
+            const Kv8Layer kl = self_kv8_layer(h, R, T, l);
+            DIMX_TRY(launch_kv8_quant(h->at, s.sk[l], R, h->decg.heads, tpad(T), pr.step0, kl.kcodes, kl.kscale, st, T));
+            DIMX_TRY(launch_kv8_quant(h->at, s.sv[l], R, h->decg.heads, tpad(T), pr.step0, kl.vcodes, kl.vscale, st, T));
+        }
     }
     if (prefill_only) return DIMX_OK;
     // FP8 cross K/V: every layer's context K / V -> codes + scales, once per generation, ahead of the first step (the prefill above
@@ -1256,6 +1299,27 @@ int dimx_cross_kv8(dimx_handle h, void** buf, size_t* bytes) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
     if (buf) *buf = h->kv8_buf;
     if (bytes) *bytes = h->kv8_bytes;
+    return DIMX_OK;
+}
+
+size_t dimx_self_kv8_bytes(dimx_handle h, int R, int T) { return kv8_bytes(h, R, T); }
+
+int dimx_set_self_kv8(dimx_handle h, void* buf, size_t bytes) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    DIMX_NO_SESSION(h, "set_self_kv8");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_self_kv8: FP8 self K/V is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    DIMX_REQUIRE(buf == nullptr || (h->decg.dim_head == 64 && (uintptr_t)buf % 256 == 0), DIMX_ERR_ARG,
+                 "set_self_kv8: the buffer must be 256-byte aligned and the decoder's heads 64 wide");
+    h->self_kv8_buf = buf;
+    h->self_kv8_bytes = buf ? bytes : 0;
+    return DIMX_OK;
+}
+
+int dimx_self_kv8(dimx_handle h, void** buf, size_t* bytes) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
+    if (buf) *buf = h->self_kv8_buf;
+    if (bytes) *bytes = h->self_kv8_bytes;
     return DIMX_OK;
 }
 

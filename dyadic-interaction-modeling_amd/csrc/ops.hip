@@ -447,6 +447,21 @@ int dimx_op_decode_attn_kv8(int out_dtype, const void* q, int q_ld, int q_is_f32
     return launch_decode_attn_kv8(a, (hipStream_t)stream);
 }
 
+/* the self form over FP8 self caches: quantise and append this step's k / v row at position n, attend over the rows 0 .. n */
+int dimx_op_decode_attn_self_kv8(int out_dtype, const float* qkv, int ld, int nslab, long slab_stride, uint8_t* kcodes, float* kscale,
+                                 uint8_t* vcodes, float* vscale, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n,
+                                 float scale, int nsplit, void* stream) {
+    DIMX_REQUIRE(qkv, DIMX_ERR_ARG, "op_decode_attn_self_kv8: null operand");
+    DIMX_REQUIRE(H >= 1 && ld >= 3 * H * 64, DIMX_ERR_ARG, "op_decode_attn_self_kv8: ld=%d < 3 * H * 64 (rows hold q | k | v)", ld);
+    Kv8SelfArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = qkv; a.knew = qkv + H * 64; a.vnew = qkv + 2 * H * 64; a.ld = ld; a.nslab = nslab; a.slab_stride = slab_stride;
+    a.kcodes = kcodes; a.kscale = kscale; a.vcodes = vcodes; a.vscale = vscale; a.Tmax = Tmax;
+    a.out = out; a.out_dtype = out_dtype; a.o_ld = o_ld; a.B = B; a.H = H;
+    a.step = step_dev; a.n_max = n; a.scale = scale; a.force_nsplit = nsplit;
+    return launch_decode_attn_self_kv8(a, (hipStream_t)stream);
+}
+
 /* windowed cross attention for many queries (win_attn.hip): query row i at position t0 + i, keys j < clamp(t0 + i + 2 + lookahead, 1, n_keys) */
 int dimx_op_cross_attn_win(int dtype, const float* q, int ld, const void* kcache, const void* vcache, int Tp, void* out, int o_ld, int B, int H,
                            int Lq, int t0, int n_keys, int lookahead, const uint8_t* kmask, int kmask_ld, float scale, void* stream) {

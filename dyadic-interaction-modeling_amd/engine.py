@@ -304,10 +304,46 @@ class Engine:
                  buf[o["kscale"]:o["kscale"] + ns].view(torch.float32).view(B, H, Tp),
                  buf[o["vscale"]:o["vscale"] + ns].view(torch.float32).view(B, H, Tp)) for o in lay]
 
+    def self_kv8_bytes(self, R, T):
+        """Bytes of the FP8 self K/V buffer of a generation of R = B * n_samples sequences of T frames (dimx_self_kv8_bytes; 0 = shape
+        not supported)."""
+        return int(self.lib.dimx_self_kv8_bytes(self.h, int(R), int(T)))
+
+    def set_self_kv8(self, buf=None):
+        """FP8 self-attention K/V caches (dimx_set_self_kv8; the definition is dimx.kv8.self_step): with a uint8 device tensor ``buf``
+        of at least ``self_kv8_bytes(B * n_samples, T)`` bytes, every decode step of this engine's generate calls quantises its k / v
+        row into it and attends over the codes; None switches it off.  ``generate(self_kv8=True)`` does both around one call."""
+        if buf is None:
+            L.check(self.lib.dimx_set_self_kv8(self.h, None, 0), "dimx_set_self_kv8")
+            return
+        assert buf.dtype == torch.uint8 and buf.is_contiguous() and buf.device == self.device
+        L.check(self.lib.dimx_set_self_kv8(self.h, L.ptr(buf), buf.numel()), "dimx_set_self_kv8")
+
+    def self_kv8(self):
+        """(pointer, bytes) of the buffer in force, or None while FP8 self K/V is off."""
+        p, n = ctypes.c_void_p(None), ctypes.c_size_t(0)
+        L.check(self.lib.dimx_self_kv8(self.h, ctypes.byref(p), ctypes.byref(n)), "dimx_self_kv8")
+        return (p.value, n.value) if p.value else None
+
+    def self_kv8_buffer(self):
+        """The uint8 tensor the last ``generate(self_kv8=True)`` appended to (None before the first); ``self_kv8_layers`` views it."""
+        return getattr(self, "_skv8", None)
+
+    def self_kv8_layers(self, R, T, buf=None):
+        """Per decoder layer (kcodes, vcodes [R, H, Tp, 64] uint8, kscale, vscale [R, H, Tp] f32): views into ``buf`` (default: the
+        engine's buffer) by dimx.kv8.buffer_layout with the R sequences in place of the clips.  Positions a generation did not reach
+        (and layer 0 where its self attention read the token table) hold what the buffer held before."""
+        return self.cross_kv8_layers(R, T, self.self_kv8_buffer() if buf is None else buf)
+
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
                  n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False, filter_logits_fn=None,
-                 filter_kwargs=None, return_scores=False, lookahead=None, guidance=None, return_branches=False, kv8=False):
+                 filter_kwargs=None, return_scores=False, lookahead=None, guidance=None, return_branches=False, kv8=False, self_kv8=False):
         """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
+
+        ``self_kv8``: FP8 self-attention K/V caches for this call (``set_self_kv8``; dimx.kv8.self_step): the engine allocates (or
+        reuses) its buffer, sets it for the call and clears the setting afterwards.  Any ``n_samples``; works with ``lookahead``,
+        ``prompt``, ``filter_logits_fn``, ``return_logits``, ``return_scores`` and, at one sample per clip, ``kv8``; ``guidance`` is
+        refused by the library.  False leaves the engine's setting as it is.
 
         ``kv8``: FP8 cross-attention K/V for this call (``set_cross_kv8``; dimx.kv8): the engine allocates (or reuses) its buffer,
         sets it for the call and clears the setting afterwards.  Works with ``lookahead``, ``prompt``, ``guidance``,
@@ -344,6 +380,21 @@ class Engine:
         ``no_prefill``) unless ``prefill`` is ``"window"`` (P0 by the default rule above) or ``("window", P0)``: then the first P0
         codes are prefilled by one teacher-forced pass under the window (flags bit 1 of dimx_generate_prompted).  With
         the window off that spelling is the plain prefill."""
+        if self_kv8:
+            R = (prompt if prompt is not None else start).shape[0] * int(n_samples)
+            need = self.self_kv8_bytes(R, T)
+            if need == 0:
+                raise L.DimxError("generate(self_kv8=True): dimx_self_kv8_bytes(%d, %d) = 0 (shape or variant not supported)" % (R, T))
+            if self.self_kv8_buffer() is None or self._skv8.numel() < need:
+                self._skv8 = None
+                self._skv8 = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            self.set_self_kv8(self._skv8)
+            try:
+                return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt, prompt_len,
+                                     prefill, no_prefill, filter_logits_fn, filter_kwargs, return_scores, lookahead, guidance,
+                                     return_branches, kv8)
+            finally:
+                self.set_self_kv8(None)
         if kv8:
             B = (prompt if prompt is not None else start).shape[0]
             need = self.cross_kv8_bytes(B, T)
@@ -1273,6 +1324,25 @@ def op_decode_attn_kv8(q, kcodes, kscale, vcodes, vscale, scale, n_keys, kmask=N
                                         Tmax, L.ptr(step), int(n_keys), L.ptr(kmask), kld, int(rows_per_clip), float(scale), int(nsplit),
                                         0 if lookahead is None else int(lookahead), 0 if lookahead is None else 1,
                                         L.stream_ptr(q.device)), "dimx_op_decode_attn_kv8")
+    return out
+
+
+def op_decode_attn_self_kv8(qkv, kcodes, kscale, vcodes, vscale, scale, n, nsplit=0, out_bf16=False, step=None):
+    """The decode step's self attention over FP8 self caches (dimx_op_decode_attn_self_kv8; dimx.kv8.self_step): qkv [R, ld] f32 or
+    split-K slabs [nslab, R, ld], rows q | k | v (ld >= 3*H*64); kcodes / vcodes [R, H, Tmax, 64] uint8, kscale / vscale [R, H, Tmax]
+    f32 with rows 0 .. n - 1 cached.  Row n of the four arrays is written in place -> [R, H*64] f32 (bf16 with ``out_bf16``).
+    ``step``: an int32 device scalar the kernel reads n from (clamped to 0 .. n); default: a fresh one holding n."""
+    lib = L.load()
+    B, H, Tmax, _ = kcodes.shape
+    qs = qkv if qkv.dim() == 3 else qkv.unsqueeze(0)
+    nslab, R, ld = qs.shape
+    assert qs.dtype == torch.float32 and R == B
+    if step is None:
+        step = torch.tensor([int(n)], dtype=torch.int32, device=qkv.device)
+    out = torch.empty(R, H * 64, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=qkv.device)
+    L.check(lib.dimx_op_decode_attn_self_kv8(L.BF16 if out_bf16 else L.F32, L.ptr(qs), ld, nslab, qs.stride(0), L.ptr(kcodes), L.ptr(kscale),
+                                             L.ptr(vcodes), L.ptr(vscale), L.ptr(out), H * 64, B, H, Tmax, L.ptr(step), int(n), float(scale),
+                                             int(nsplit), L.stream_ptr(qkv.device)), "dimx_op_decode_attn_self_kv8")
     return out
 
 

@@ -4,7 +4,8 @@ The cross K/V cache of a generation is written once per clip and read by every d
 [64] becomes 64 OCP ``e4m3fn`` codes and one float32 scale -- one scale per (clip, head, key) -- and ``attention`` what the decode
 step's one-query cross attention computes over such codes.  csrc/decode_attn_kv8.hip follows this file bit for bit (codes, scales)
 or within the step kernels' tolerance (attention); tests/test_kv8_host.py pins the rounding against torch's CPU ``float8_e4m3fn``
-cast.
+cast.  ``self_step`` is the same for the self-attention caches (dimx_set_self_kv8): the caches that grow by one row per decode step,
+whose new row is quantised by the step itself.
 
     amax  = max |x| over the row (float32)
     scale = float32(amax) / float32(448)              one IEEE float32 division; amax < 2**-60: a zero row, scale 0, codes 0
@@ -103,9 +104,28 @@ def attention(q, kcodes, kscale, vcodes, vscale, mask, n, scale=0.125):
     return np.einsum("bhj,bhjd->bhd", p, v)
 
 
+def self_step(q, k_new, v_new, kcodes, kscale, vcodes, vscale, n, scale=0.125):
+    """One decode step's self attention over FP8 self caches (dimx_set_self_kv8; decode_attn_self_kv8_kernel), in place.
+
+    q, k_new, v_new [R, H, 64]: the float32 sum of the projection's split-K slabs in slab order, in both numeric modes -- never
+    rounded to the cache type.  kcodes / vcodes [R, H, Tp, 64] uint8 and kscale / vscale [R, H, Tp] float32 hold the rows 0 .. n - 1.
+    The new rows go through ``quantize`` and are stored at position n; the result is the float64 softmax attention (scores
+    scale * q.k, no key mask: the self form has none) over the dequantised rows 0 .. n, all n + 1 of them.
+
+    The step's own key and value are the DEQUANTISED ones: the own key carries the same quantisation error as every other key.
+    The output of step t is therefore a function of the buffer's rows <= t alone, and a teacher-forced replay over a finished
+    buffer reproduces every step.  Rows past n are neither read nor written.  -> [R, H, 64] float64."""
+    kc, ksc = quantize(np.asarray(k_new, dtype=np.float32))
+    vc, vsc = quantize(np.asarray(v_new, dtype=np.float32))
+    kcodes[:, :, n], kscale[:, :, n] = kc, ksc
+    vcodes[:, :, n], vscale[:, :, n] = vc, vsc
+    return attention(q, kcodes, kscale, vcodes, vscale, None, n + 1, scale)
+
+
 def buffer_layout(depth, B, H, Tp):
     """The caller's buffer of dimx_set_cross_kv8 (include/dimx.h): per layer K codes, V codes, K scales, V scales, each 256-byte
-    aligned, layers in order.  -> (list of per-layer dicts of byte offsets, total bytes)"""
+    aligned, layers in order.  dimx_set_self_kv8's buffer is the same with the row count R = B * n_samples in place of B.
+    -> (list of per-layer dicts of byte offsets, total bytes)"""
     al = lambda x: (x + 255) // 256 * 256
     cb, sb = al(B * H * Tp * 64), al(B * H * Tp * 4)
     off, lay = 0, []

@@ -211,7 +211,7 @@ def _select(pending, skip_degenerate, world, device):
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
                         select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, window_prefill=False, guidance=None,
-                        kv8=False, **forward_kw):
+                        kv8=False, self_kv8=False, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -279,7 +279,15 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
 
     ``kv8``: every generation reads an FP8 copy of the context K / V in its decode steps (dimx.kv8, ``SLMFT.forward(kv8=True)``).
     Such a generation draws one sample per clip too, so the tries are ``beam_size`` passes and ``select`` must be "fd"; not with
-    ``decode="beam"`` (ValueError).  False (default) leaves every path as it is."""
+    ``decode="beam"`` (ValueError).  False (default) leaves every path as it is.
+
+    ``self_kv8``: every generation keeps its self-attention K / V caches in FP8 (dimx.kv8.self_step, ``SLMFT.forward(self_kv8=True)``).
+    The batched best-of-``beam_size`` pass takes it as it is, with every ``select``; not with ``decode="beam"`` or ``guidance``
+    (ValueError).  False (default) leaves every path as it is."""
+    if self_kv8:
+        if decode == "beam" or guidance is not None:
+            raise ValueError("evaluate_test_epoch(self_kv8=True) applies to decode='sample' without guidance")
+        forward_kw = dict(forward_kw, self_kv8=True)
     if kv8:
         if decode == "beam" or select != "fd":
             raise ValueError("evaluate_test_epoch(kv8=True) applies to decode='sample' with select='fd': an FP8 cross K/V generation "

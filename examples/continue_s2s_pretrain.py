@@ -61,6 +61,9 @@ def main():
     ap.add_argument("--kv8", action="store_true",
                     help="FP8 cross-attention K/V (dimx.kv8): the context K / V are quantised once per generation and the decode steps stream "
                          "the codes.  One sample per clip and pass, --select fd only")
+    ap.add_argument("--self-kv8", action="store_true",
+                    help="FP8 self-attention K/V caches (dimx.kv8.self_step): every decode step quantises its k / v row and attends over the "
+                         "codes.  Any number of samples per clip; not with --decode beam or --guidance")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     if args.window_prefill and args.lookahead is None:
@@ -90,7 +93,7 @@ def main():
                                                         prompt_frames=args.prompt_frames, select=args.select,
                                                         consensus_distance=args.consensus_distance, decode=args.decode,
                                                         beam_width=args.beam_width, lookahead=args.lookahead,
-                                                        window_prefill=args.window_prefill, guidance=args.guidance, kv8=args.kv8, **sampler)
+                                                        window_prefill=args.window_prefill, guidance=args.guidance, kv8=args.kv8, self_kv8=args.self_kv8, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     print_metrics(y_true, y_pred, x)

@@ -397,6 +397,30 @@ size_t dimx_cross_kv8_bytes(dimx_handle h, int B, int T);
 int dimx_set_cross_kv8(dimx_handle h, void* buf, size_t bytes);
 /* The handle's current setting (either pointer may be NULL). */
 int dimx_cross_kv8(dimx_handle h, void** buf, size_t* bytes);
+/* FP8 self-attention K/V caches for generation (csrc/decode_attn_kv8.hip, decode_attn_self_kv8_kernel; the definition is dimx/kv8.py
+ * self_step).  Opt-in handle state like dimx_set_cross_kv8: variant 0 only (DIMX_ERR_ARG otherwise), either numeric mode,
+ * DIMX_ERR_STATE while a streaming session is open (sessions neither read nor change the setting).  With a buffer set, every decode
+ * step of dimx_generate / dimx_generate_prompted quantises its k / v row -- the f32 sum of the projection's split-K slabs, never rounded
+ * to the cache type -- into OCP e4m3fn codes with one f32 scale per (row, head, position), stores it at the step's position and
+ * attends over the codes of the positions so far, its own included: one launch per layer and step.  The output of step t is a
+ * function of the buffer's rows <= t alone.
+ *   - The buffer is the caller's: dimx_self_kv8_bytes(h, R, T) bytes of device memory, 256-byte aligned, R = B * n_samples
+ *     sequences; the layout is dimx_set_cross_kv8's with R in place of B.  The workspace queries return what they returned before
+ *     (the unquantised self caches stay allocated: a prompt's prefill writes them).  Positions a generation has not reached are
+ *     neither read nor written.  0 = the shape is not supported.
+ *   - buf = NULL turns it off: every call then launches what it launched before the setting existed, bit for bit.  The pointer is
+ *     part of what keys the captured step graph.
+ *   - Any n_samples; rows are samples, and with n_samples > 1 the cross attention stays the unquantised multi-query launch.  The
+ *     decoder-layer kernel is not taken.  The first layer keeps its table form where the route has it (that layer has no cache).
+ *     Works with the cross-attention window, the sampler filters, logits_out and prompts; a prefilled prompt's rows 0 .. P0 - 2 are
+ *     quantised from the caches the prefill wrote, one dimx_op_kv8_quantize launch per layer and operand, ahead of the first step.
+ *     Combines with dimx_set_cross_kv8 at one sample per clip.
+ *   - dimx_generate_beam and dimx_generate_guided return DIMX_ERR_ARG before any launch; a buffer below
+ *     dimx_self_kv8_bytes(h, B * n_samples, T) for the call's shape returns DIMX_ERR_WORKSPACE. */
+size_t dimx_self_kv8_bytes(dimx_handle h, int R, int T);
+int dimx_set_self_kv8(dimx_handle h, void* buf, size_t bytes);
+/* The handle's current setting (either pointer may be NULL). */
+int dimx_self_kv8(dimx_handle h, void** buf, size_t* bytes);
 /* Streaming sessions (csrc/stream.hip; the schedule is dimx/stream.py): the speaker arrives in pieces, the listener's
  * tokens leave as soon as they are due.  A session fed a clip in pieces computes what dimx_encode_ctx + dimx_generate under
  * dimx_set_cross_lookahead(1, lookahead) compute on the whole clip: the speaker encoders are causal, so the context rows of the new
@@ -829,6 +853,18 @@ int dimx_op_decode_attn_kv8(int out_dtype, const void* q, int q_ld, int q_is_f32
                             const float* kscale, const uint8_t* vcodes, const float* vscale, void* out, int o_ld, int B, int H, int Tmax,
                             const int32_t* step_dev, int n_keys, const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit,
                             int lookahead, int win, void* stream);
+/* The self attention over FP8 self caches, as dimx_generate launches it with dimx_set_self_kv8 (dimx/kv8.py self_step): qkv is f32
+ * split-K slabs [nslab][B, ld] (nslab 1..8, summed in slab order), row b holding q | k | v at columns 0, H*64, 2*H*64 (ld >= 3*H*64).
+ * The k / v sums are quantised as dimx_op_kv8_quantize quantises a cache row and stored at position n of kcodes / vcodes
+ * [B, H, Tmax, 64] uint8 and kscale / vscale [B, H, Tmax] f32; the output is the softmax attention (scores scale * q . k) over the
+ * dequantised rows 0 .. n, row n from registers.  n is *step_dev clamped to 0 .. n, or n itself with step_dev = NULL, so no position
+ * past the given n is addressed whatever the device word holds.  Rows past n are neither read nor written, every other row is left
+ * as it is; no atomics, repeats are bit-identical; nsplit = 0 on out_dtype = DIMX_F32 depends on Tmax only.  DIMX_ERR_ARG (nothing
+ * launched) for a null or misaligned operand (qkv / codes / out 16 bytes, scales 4; ld, slab_stride multiples of 4, o_ld of 4 (f32) /
+ * 8 (bf16)), n outside 0 .. min(Tmax, 2048) - 1, nslab outside 1..8 or another out_dtype. */
+int dimx_op_decode_attn_self_kv8(int out_dtype, const float* qkv, int ld, int nslab, long slab_stride, uint8_t* kcodes, float* kscale,
+                                 uint8_t* vcodes, float* vscale, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n,
+                                 float scale, int nsplit, void* stream);
 /* Append attention (csrc/stream_attn.hip; what a streaming session launches for every encoder layer): the self attention of the c
  * new rows of every clip over a growing K / V cache.  qkv [B*c, ld] f32 (row b*c + i; q | k | v at columns 0, H*64, 2*H*64, ld >= 3*H*64,
  * the layout the q/k/v projection writes), kcache / vcache [B, H, Tmax, 64] of dtype (DIMX_F32 / DIMX_BF16), n0 rows already cached,
