@@ -299,6 +299,10 @@ void gemm_args_init(GemmArgs& a);
 // plain row-major output helper
 void gemm_set_plain_out(GemmArgs& a, void* C, int ldc);
 int launch_gemm(const GemmArgs& a, hipStream_t s);
+// what launch_gemm would run for `a`, from the launcher's own decision code, without launching (dimx_op_gemm_route): *route =
+// kernel (cfg id 1/3/4/14/34/35/72, 256 = gemm256, 1064 / 1128 = register-staged gemm_kernel 64x64 / 128x128, 2000 = gemm_x3)
+// | stage_out << 16 | vt_pack4 << 17; the launcher's argument errors are returned as they are
+int gemm_route(const GemmArgs& a, int* route);
 // the 256 x 256 phase-pipelined prefill kernel (gemm256.hip): taken by launch_gemm when eligible
 bool gemm256_eligible(const GemmArgs& a);
 int launch_gemm256(const GemmArgs& a, hipStream_t s);

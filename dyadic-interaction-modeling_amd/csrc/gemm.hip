@@ -1283,13 +1283,18 @@ template <typename T, typename OutT, int STAGES> static int launch_ws(const Gemm
     return DIMX_OK;
 }
 
+// one 32-row slice per wave (MI == 1) is where staging pays (128x128 on 8 waves: -12..-39 %); with two slices per
+// wave (the 4-wave 128x128 and the 256-wide tiles) it measured 30-40 % slower than direct stores
+template <int BM, int BN, int WM> constexpr bool glds_stages() { return BM * BN >= 128 * 128 && BM / (WM * 32) == 1; }
+// ... which of launch_by_cfg's tiles is cfg 14 alone: what gemm_route reports as "staged" is stage_out on that cfg
+static inline bool cfg_stages(int cfg) { return cfg == 14; }
+static_assert(glds_stages<128, 128, 4>() && !glds_stages<128, 128, 2>() && !glds_stages<64, 64, 2>(), "cfg_stages() names the staged tiles");
+
 template <typename T, typename OutT, int BM, int BN, int WM, int WN, int STAGES>
 static int launch_glds(const GemmArgs& a, hipStream_t s) {
     const int tiles = ceil_div(a.M, BM) * ceil_div(a.N, BN);
     dim3 grid(tiles * a.splitk), block(WM * WN * 64);
-    // one 32-row slice per wave (MI == 1) is where staging pays (128x128 on 8 waves: -12..-39 %); with two slices per
-    // wave (the 4-wave 128x128 and the 256-wide tiles) it measured 30-40 % slower than direct stores
-    if constexpr (BM * BN >= 128 * 128 && BM / (WM * 32) == 1) {
+    if constexpr (glds_stages<BM, BN, WM>()) {
         if (a.stage_out) {
             hipLaunchKernelGGL((gemm_glds_kernel<T, OutT, BM, BN, WM, WN, STAGES, true>), grid, block, 0, s, a);
             DIMX_HIP(hipGetLastError());
@@ -1348,27 +1353,38 @@ static inline void cfg_tile(int cfg, int& bm, int& bn) {
     }
 }
 
-template <typename T, typename OutT> static int launch_typed(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
+// What launch_typed runs for these arguments, decided on the host in ONE place: the launcher acts on it and gemm_route (the
+// tests' route query) reports it.  simple: 0 = an LDS-DMA kernel of tile `cfg`, else the register-staged gemm_kernel's tile
+// (64 or 128).  On return `a` carries what the launcher sets itself: splitk, stage_out, vt_pack4 (and no residual for slabs).
+struct TypedPlan {
+    int simple, cfg;
+};
+
+static int plan_typed(const GemmArgs& a0, GemmArgs& a, int in_es, int out_es, TypedPlan& p) {
+    a = a0;
     a.splitk = 1;
-    const int bk = 8 * Elem<T>::kPerChunk;
+    a.stage_out = 0;
+    a.vt_pack4 = 0;
+    p.simple = 0;
+    p.cfg = 0;
+    const int bk = 8 * (16 / in_es);
     const long tiles128 = (long)ceil_div(a.M, 128) * ceil_div(a.N, 128);
     const int kext = a.kloop ? a.kloop : a.ldw;
     const bool pipelined = a.conv_T == 0 && a.K % bk == 0 && a.K == kext && !a.force_simple;
     if (!pipelined) {
         // gather / ragged-K path: register-staged kernel
-        if (tiles128 >= 256) return launch_cfg<T, OutT, 128, 128, 2, 2>(a, s);
-        return launch_cfg<T, OutT, 64, 64, 2, 2>(a, s);
+        p.simple = tiles128 >= 256 ? 128 : 64;
+        return DIMX_OK;
     }
     int cfg = a.cfg;
     // measured on MI355X: 128x128 8-wave for large M; bf16 from 288 tiles (the dW of a 1152 x 4608 projection at 4 800 rows:
     // 122.9 us on the 64 x 64 kernel, 80.4 on this one; 228 tiles and fewer: level or behind -- profiles/r03_train_gemm.txt).
     // Small M: 64x64 with a 4-deep ring, loader + consumer waves (34) over the 4-wave kernel (3): qkv 10.3 -> 8.8, ff1 13.1 ->
     // 12.1, ff2 11.9 -> 11.0 us, +1.0..1.5 % end to end on the same box; deeper rings (5, 6, 8 slots) are slower.
-    if (cfg == 0) cfg = tiles128 >= (sizeof(T) == 2 ? 288 : 512) ? 14 : 34;
-    if (a.cfg == 0 && sizeof(T) == 4 && a.out_slabs) cfg = 34;  // f32 slabs: one tile shape whatever M is (see gemm_plan_splits)
+    if (cfg == 0) cfg = tiles128 >= (in_es == 2 ? 288 : 512) ? 14 : 34;
+    if (a.cfg == 0 && in_es == 4 && a.out_slabs) cfg = 34;  // f32 slabs: one tile shape whatever M is (see gemm_plan_splits)
     if (a.cfg == 0 && gemm_use_ws72(a0)) cfg = 72;
-    DIMX_REQUIRE(cfg != 72 || (sizeof(T) == 2 && a.N % 72 == 0 && !a.w_tiled && a.nseg == 1 && a.seg[0].sd == 1 && a.seg[0].sh == 0 &&
+    DIMX_REQUIRE(cfg != 72 || (in_es == 2 && a.N % 72 == 0 && !a.w_tiled && a.nseg == 1 && a.seg[0].sd == 1 && a.seg[0].sh == 0 &&
                                a.seg[0].sb == a.seg[0].st * (long)a.rowT && a.rowadd_mode == 0),
                  DIMX_ERR_ARG, "gemm: cfg 72 needs bf16 operands, N %% 72 == 0 (N=%d) and a plain row-major destination", a.N);
     if (a.out_slabs) {
@@ -1376,11 +1392,7 @@ template <typename T, typename OutT> static int launch_typed(const GemmArgs& a0,
         a.residual = nullptr;
     }
     // large-M outputs leave through LDS as 16-byte row pieces (epilogue_staged) when the output map allows it
-    a.stage_out = 0;
-    a.vt_pack4 = 0;
     if (!a.out_slabs && a.M >= 2048 && (a.rowT == 1 || a.rowT >= 32)) {
-        const int epo = 16 / (int)sizeof(OutT);
-        (void)epo;
         bool ok = a.N % 4 == 0 && (a.nseg == 1 || a.seg_width % 32 == 0), any_row = false, pack = true;
         ok = ok && (!a.bias || ((uintptr_t)a.bias % 16) == 0);
         ok = ok && (!a.residual || (a.ldr % 4 == 0 && ((uintptr_t)a.residual % 16) == 0));
@@ -1392,7 +1404,7 @@ template <typename T, typename OutT> static int launch_typed(const GemmArgs& a0,
                 ok = ok && ((uintptr_t)g.ptr % 16) == 0 && g.sb % 4 == 0 && g.st % 4 == 0 && g.sh % 4 == 0 && g.D % 4 == 0;
             } else {
                 pack = pack && g.st == 1 && a.rowT % 4 == 0 && a.M % 4 == 0 && g.sb % 4 == 0 && g.sd % 4 == 0 &&
-                       g.sh % 4 == 0 && ((uintptr_t)g.ptr % (4 * sizeof(OutT))) == 0;
+                       g.sh % 4 == 0 && ((uintptr_t)g.ptr % (4 * (size_t)out_es)) == 0;
             }
         }
         if (ok && any_row) {
@@ -1400,7 +1412,30 @@ template <typename T, typename OutT> static int launch_typed(const GemmArgs& a0,
             a.vt_pack4 = pack ? 1 : 0;
         }
     }
-    return launch_by_cfg<T, OutT>(a, cfg, s);
+    p.cfg = cfg;
+    return DIMX_OK;
+}
+
+// route words (gemm_route / dimx_op_gemm_route): bits 0..15 the kernel, bit 16 staged epilogue, bit 17 packed V^T stores
+enum { ROUTE_GEMM256 = 256, ROUTE_SIMPLE64 = 1064, ROUTE_SIMPLE128 = 1128, ROUTE_X3 = 2000, ROUTE_STAGED = 1 << 16, ROUTE_PACK4 = 1 << 17 };
+
+static inline bool cfg_known(int cfg) { return cfg == 1 || cfg == 3 || cfg == 4 || cfg == 14 || cfg == 34 || cfg == 35 || cfg == 72; }
+
+template <typename T, typename OutT> static int launch_typed(const GemmArgs& a0, hipStream_t s, int* route) {
+    GemmArgs a;
+    TypedPlan p;
+    DIMX_TRY(plan_typed(a0, a, (int)sizeof(T), (int)sizeof(OutT), p));
+    if (route) {
+        DIMX_REQUIRE(p.simple || (cfg_known(p.cfg) && (p.cfg != 72 || sizeof(T) == 2)), DIMX_ERR_ARG, "gemm: unknown cfg %d", p.cfg);
+        // the staged copy-out exists in the tiles cfg_stages names; on the others stage_out is set and ignored
+        const bool staged = !p.simple && a.stage_out && cfg_stages(p.cfg);
+        *route = (p.simple ? (p.simple == 128 ? ROUTE_SIMPLE128 : ROUTE_SIMPLE64) : p.cfg) | (staged ? ROUTE_STAGED : 0) |
+                 (staged && a.vt_pack4 ? ROUTE_PACK4 : 0);
+        return DIMX_OK;
+    }
+    if (p.simple == 128) return launch_cfg<T, OutT, 128, 128, 2, 2>(a, s);
+    if (p.simple) return launch_cfg<T, OutT, 64, 64, 2, 2>(a, s);
+    return launch_by_cfg<T, OutT>(a, p.cfg, s);
 }
 
 int gemm_plan_splits(const GemmArgs& a) {
@@ -1487,7 +1522,9 @@ static bool gemm_use_ws72(const GemmArgs& a) {
     return ceil_div(a.M, 64) * (a.N / 72) <= 256;
 }
 
-int launch_gemm(const GemmArgs& a, hipStream_t s) {
+// launch_gemm and gemm_route: the argument checks and the kernel choice are this one function; with `route` it stores the route
+// word of the kernel it would launch and launches nothing
+static int gemm_dispatch(const GemmArgs& a, hipStream_t s, int* route) {
     const int epc = a.in_dtype == DIMX_BF16 ? 8 : 4;
     const int bk = 8 * epc;
     const size_t es = dtype_size(a.in_dtype);
@@ -1514,19 +1551,38 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
                      "gemm: block-tiled W needs N %% 8 == 0, K %% %d == 0 and a decode-sized M (N=%d K=%d M=%d)", bk, a.N, a.K, a.M);
     {   // DIMX_GEMM_LOG=1: one line per launch (tools/gemm_in_situ.py pairs them with a kernel trace)
         static const bool log = getenv("DIMX_GEMM_LOG") != nullptr;
-        if (log)
+        if (log && !route)
             fprintf(stderr, "dimx-gemm M=%d N=%d K=%d in=%d out=%d bias=%d res=%d act=%d rowadd=%d nseg=%d slabs=%d big=%d\n", a.M, a.N, a.K,
                     a.in_dtype, a.out_dtype, a.bias ? 1 : 0, a.residual ? 1 : 0, a.act, a.rowadd_mode, a.nseg, a.out_slabs ? 1 : 0,
                     (a.in_dtype == DIMX_BF16 && a.cfg == 0 && gemm256_eligible(a)) ? 1 : 0);
     }
     if (a.in_dtype == DIMX_BF16) {
-        if (a.cfg == 0 && gemm256_eligible(a)) return launch_gemm256(a, s);
-        if (a.out_dtype == DIMX_BF16) return launch_typed<bf16, bf16>(a, s);
-        return launch_typed<bf16, float>(a, s);
+        if (a.cfg == 0 && gemm256_eligible(a)) {
+            if (route) {
+                *route = ROUTE_GEMM256;
+                return DIMX_OK;
+            }
+            return launch_gemm256(a, s);
+        }
+        if (a.out_dtype == DIMX_BF16) return launch_typed<bf16, bf16>(a, s, route);
+        return launch_typed<bf16, float>(a, s, route);
     }
     DIMX_REQUIRE(a.out_dtype == DIMX_F32, DIMX_ERR_ARG, "gemm: f32 inputs produce f32 outputs");
-    if (gemm_use_x3(a)) return launch_gemm_x3(a, s);   // round 6: decode-sized f32 GEMMs on the bf16 matrix cores, f32-equivalent (gemm_x3.hip)
-    return launch_typed<float, float>(a, s);
+    if (gemm_use_x3(a)) {   // round 6: decode-sized f32 GEMMs on the bf16 matrix cores, f32-equivalent (gemm_x3.hip)
+        if (route) {
+            *route = ROUTE_X3;
+            return DIMX_OK;
+        }
+        return launch_gemm_x3(a, s);
+    }
+    return launch_typed<float, float>(a, s, route);
+}
+
+int launch_gemm(const GemmArgs& a, hipStream_t s) { return gemm_dispatch(a, s, nullptr); }
+
+int gemm_route(const GemmArgs& a, int* route) {
+    *route = 0;
+    return gemm_dispatch(a, nullptr, route);
 }
 
 }  // namespace dimx

@@ -569,6 +569,17 @@ __global__ __launch_bounds__(512) void gemm256p2_kernel(const Big a) {
 
 }  // namespace
 
+// epi_tile splits (head, column) ONCE per lane and tile, for the first column of the lane's 16-byte piece; store_chunk reaches the
+// piece's other columns -- 8 of a bf16 destination, and an f32 destination's second pass 32 columns further -- by pointer addition.
+// That is the map's address when heads lie back to back (sh == D, or one head: the address is linear in the column), else only
+// when those columns stay inside the head: D % 8 == 0 for bf16, D % 64 == 0 for f32 (a wave's chunk starts on a multiple of 64).
+// [B, H, Tp, 36] caches passed the former D % 4 alone: bf16 columns 32..39 went to frames t, t + 1 of head 0, f32 pass 1 of head
+// 0's chunk to head 0's next frame instead of head 1.
+static bool gemm256_heads_ok(const OutSeg& s, int seg_width, int es) {
+    if (s.sh == s.D || s.D == seg_width) return true;
+    return s.D % (es == 2 ? 8 : 64) == 0;
+}
+
 // Eligible: bf16 operands, K % 64 == 0, row-contiguous destinations, enough rows to fill the chip.
 bool gemm256_eligible(const GemmArgs& g) {
     if (g.in_dtype != DIMX_BF16 || g.conv_T != 0 || g.out_slabs || g.force_simple) return false;
@@ -595,6 +606,7 @@ bool gemm256_eligible(const GemmArgs& g) {
     for (int i = 0; i < g.nseg; ++i) {
         const OutSeg& s = g.seg[i];
         if (s.sd != 1 || s.D % 4 || s.sb % 4 || s.st % 4 || s.sh % 4 || ((uintptr_t)s.ptr % (4 * es))) return false;
+        if (!gemm256_heads_ok(s, g.nseg > 1 ? g.seg_width : g.N, es)) return false;
     }
     return true;
 }
@@ -678,8 +690,9 @@ int launch_gemm256(const GemmArgs& g, hipStream_t s) { return launch_big(g, g.se
 int launch_gemm256_segs(const GemmArgs& g, const OutSeg* segs, int nseg, int seg_width, hipStream_t s) {
     DIMX_REQUIRE(seg_width % 64 == 0 && seg_width * nseg == g.N, DIMX_ERR_ARG, "gemm256_segs: bad segment width");
     for (int i = 0; i < nseg; ++i)
-        DIMX_REQUIRE(segs[i].sd == 1 && segs[i].D % 8 == 0 && ((uintptr_t)segs[i].ptr % 16) == 0, DIMX_ERR_ARG,
-                     "gemm256_segs: segment %d is not row-contiguous", i);
+        DIMX_REQUIRE(segs[i].sd == 1 && segs[i].D % 8 == 0 && ((uintptr_t)segs[i].ptr % 16) == 0 &&
+                         gemm256_heads_ok(segs[i], seg_width, g.out_dtype == DIMX_BF16 ? 2 : 4),
+                     DIMX_ERR_ARG, "gemm256_segs: segment %d is not row-contiguous, or its heads are narrower than a lane's piece", i);
     return launch_big(g, segs, nseg, seg_width, s);
 }
 

@@ -132,6 +132,94 @@ int dimx_op_gemm_slabs(int in_dtype, int M, int N, int K, int flags) {
     return gemm_plan_splits(g);
 }
 
+}  // extern "C"
+
+/* the GemmArgs of dimx_op_gemm_map / dimx_op_gemm_route: dimx_op_gemm's fields plus the output map and the row add */
+static int gemm_map_args(GemmArgs& g, int in_dtype, int out_dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                         const float* bias, int act, const float* residual, int ldr, int rowT, int nseg, void* const* seg_ptr,
+                         const int64_t* seg_strides, const int32_t* seg_D, const float* rowadd, int ld_rowadd, int rowadd_mode,
+                         float rowadd_scale, int rowadd_off, int rowadd_div, int flags) {
+    DIMX_REQUIRE(A && W && seg_ptr && seg_strides && seg_D, DIMX_ERR_ARG, "op_gemm_map: null operand or map");
+    DIMX_REQUIRE(M > 0 && N > 0 && K > 0 && rowT >= 1, DIMX_ERR_ARG, "op_gemm_map: bad shape (M=%d N=%d K=%d rowT=%d)", M, N, K, rowT);
+    DIMX_REQUIRE(nseg >= 1 && nseg <= 3 && N % nseg == 0 && nseg * (N / nseg) == N, DIMX_ERR_ARG,
+                 "op_gemm_map: %d segments do not divide N=%d", nseg, N);
+    DIMX_REQUIRE(rowadd_mode >= 0 && rowadd_mode <= 3 && (rowadd_mode == 0 || (rowadd && ld_rowadd >= N && rowadd_div >= 1 && rowadd_off >= 0)),
+                 DIMX_ERR_ARG, "op_gemm_map: row-add mode %d needs a table with ld >= N, div >= 1, off >= 0", rowadd_mode);
+    DIMX_REQUIRE(!residual || ldr >= N, DIMX_ERR_ARG, "op_gemm_map: residual row stride %d below N=%d", ldr, N);
+    gemm_args_init(g);
+    g.in_dtype = in_dtype;
+    g.out_dtype = out_dtype;
+    g.A = A;
+    g.lda = lda;
+    g.W = W;
+    g.ldw = ldw;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.bias = bias;
+    g.act = act;
+    g.residual = residual;
+    g.ldr = ldr;
+    g.force_simple = (flags >> 1) & 1;
+    g.cfg = (flags >> 8) & 0xff;
+    if (ldw > K && K % (in_dtype == DIMX_BF16 ? 64 : 32) == 0) g.kloop = K; /* padded row stride, exact k extent */
+    g.rowT = rowT;
+    g.nseg = nseg;
+    g.seg_width = N / nseg;
+    for (int i = 0; i < nseg; ++i) {
+        DIMX_REQUIRE(seg_ptr[i] && seg_D[i] > 0 && g.seg_width % seg_D[i] == 0, DIMX_ERR_ARG,
+                     "op_gemm_map: segment %d is unset or its head width does not divide the segment", i);
+        g.seg[i].ptr = seg_ptr[i];
+        g.seg[i].sb = (long)seg_strides[4 * i + 0];
+        g.seg[i].sh = (long)seg_strides[4 * i + 1];
+        g.seg[i].st = (long)seg_strides[4 * i + 2];
+        g.seg[i].sd = (long)seg_strides[4 * i + 3];
+        g.seg[i].D = seg_D[i];
+    }
+    if (rowadd_mode) {
+        g.rowadd = rowadd;
+        g.ld_rowadd = ld_rowadd;
+        g.rowadd_mode = rowadd_mode;
+        g.rowadd_scale = rowadd_scale;
+        g.rowadd_off = rowadd_off;
+        g.rowadd_div = rowadd_div;
+    }
+    return DIMX_OK;
+}
+
+extern "C" {
+
+int dimx_op_gemm_map(int in_dtype, int out_dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
+                     int act, const float* residual, int ldr, int rowT, int nseg, void* const* seg_ptr, const int64_t* seg_strides,
+                     const int32_t* seg_D, const float* rowadd, int ld_rowadd, int rowadd_mode, float rowadd_scale, int rowadd_off,
+                     int rowadd_div, int flags, void* stream) {
+    GemmArgs g;
+    DIMX_TRY(gemm_map_args(g, in_dtype, out_dtype, A, lda, W, ldw, M, N, K, bias, act, residual, ldr, rowT, nseg, seg_ptr, seg_strides,
+                           seg_D, rowadd, ld_rowadd, rowadd_mode, rowadd_scale, rowadd_off, rowadd_div, flags));
+    return launch_gemm(g, (hipStream_t)stream);
+}
+
+/* what launch_gemm would run for a dimx_op_gemm_map call with these arguments; nothing is read or launched: every pointer is
+ * replaced by a dummy of the same 16-byte alignment (as dimx_op_gemm_slabs plans with dummies) */
+int dimx_op_gemm_route(int in_dtype, int out_dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
+                       int act, const float* residual, int ldr, int rowT, int nseg, void* const* seg_ptr, const int64_t* seg_strides,
+                       const int32_t* seg_D, const float* rowadd, int ld_rowadd, int rowadd_mode, float rowadd_scale, int rowadd_off,
+                       int rowadd_div, int flags) {
+    GemmArgs g;
+    DIMX_TRY(gemm_map_args(g, in_dtype, out_dtype, A, lda, W, ldw, M, N, K, bias, act, residual, ldr, rowT, nseg, seg_ptr, seg_strides,
+                           seg_D, rowadd, ld_rowadd, rowadd_mode, rowadd_scale, rowadd_off, rowadd_div, flags));
+    auto dummy = [](const void* p) -> uintptr_t { return p ? (uintptr_t)256 + ((uintptr_t)p & 15) : 0; };
+    g.A = (const void*)dummy(g.A);
+    g.W = (const void*)dummy(g.W);
+    g.bias = (const float*)dummy(g.bias);
+    g.residual = (const float*)dummy(g.residual);
+    g.rowadd = (const float*)dummy(g.rowadd);
+    for (int i = 0; i < g.nseg; ++i) g.seg[i].ptr = (void*)dummy(g.seg[i].ptr);
+    int route = 0;
+    DIMX_TRY(gemm_route(g, &route));
+    return route;
+}
+
 int dimx_op_gemm_headmajor(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int M, int N, int K,
                            int rowT, int Tp, int nlayers, void* stream) {
     DIMX_REQUIRE(nlayers >= 1 && nlayers <= 4 && N % (nlayers * 128) == 0, DIMX_ERR_ARG, "op_gemm_headmajor: bad shape");

@@ -868,6 +868,55 @@ def op_gemm(a, w, bias=None, act=0, residual=None, bf16=False, out_bf16=False, c
     return out
 
 
+def _gemm_map_args(a, w, segs, rowT, bias, act, residual, bf16, rowadd, rowadd_mode, rowadd_scale, rowadd_off, rowadd_div,
+                   force_simple, cfg):
+    """The argument list dimx_op_gemm_map and dimx_op_gemm_route share (without the stream), and the tensors that must stay alive."""
+    dt = torch.bfloat16 if bf16 else torch.float32
+    a_ = a.to(dt).contiguous()
+    w_ = _pad_k(w.to(dt), 64 if bf16 else 32)
+    (M, K), N = a.shape, w.shape[0]
+    odt = segs[0][0].dtype
+    assert odt in (torch.float32, torch.bfloat16) and all(s[0].dtype == odt and s[0].device == a.device for s in segs)
+    n = len(segs)
+    ptrs = (ctypes.c_void_p * n)(*(s[0].data_ptr() for s in segs))
+    strides = (ctypes.c_int64 * (4 * n))(*(int(v) for s in segs for v in s[1:5]))
+    heads = (ctypes.c_int32 * n)(*(int(s[5]) for s in segs))
+    flags = (2 if force_simple else 0) | (cfg << 8)
+    args = [L.BF16 if bf16 else L.F32, L.BF16 if odt == torch.bfloat16 else L.F32, L.ptr(a_), a_.shape[1], L.ptr(w_), w_.shape[1],
+            M, N, K, L.ptr(bias), act, L.ptr(residual), residual.shape[1] if residual is not None else 0, rowT, n, ptrs, strides, heads,
+            L.ptr(rowadd), rowadd.shape[1] if rowadd is not None else 0, rowadd_mode, float(rowadd_scale), rowadd_off, rowadd_div, flags]
+    return args, (a_, w_, ptrs, strides, heads)
+
+
+def op_gemm_map(a, w, segs, rowT=1, bias=None, act=0, residual=None, bf16=False, rowadd=None, rowadd_mode=0, rowadd_scale=1.0,
+                rowadd_off=0, rowadd_div=1, force_simple=False, cfg=0):
+    """epilogue(a[M,K] @ w[N,K]^T) scattered through an output map (dimx_op_gemm_map): ``segs`` is a list of 1..3 tuples
+    (tensor, sb, sh, st, sd, D) -- the tensor's first element is the segment's base, the strides are in elements -- and row
+    m = b * rowT + t, column nn of segment s lands at base + b*sb + t*st + (nn // D)*sh + (nn % D)*sd.  The destinations' dtype is
+    the output dtype; they are written in place, nothing is returned."""
+    args, keep = _gemm_map_args(a, w, segs, rowT, bias, act, residual, bf16, rowadd, rowadd_mode, rowadd_scale, rowadd_off,
+                                rowadd_div, force_simple, cfg)
+    L.check(L.load().dimx_op_gemm_map(*args, L.stream_ptr(a.device)), "dimx_op_gemm_map")
+    del keep
+
+
+def op_gemm_route(a, w, segs, **kw):
+    """What ``op_gemm_map`` with the same arguments would launch, from the launcher's own decision (dimx_op_gemm_route; nothing
+    runs): (kernel, staged, packed) -- kernel = the LDS-DMA cfg id, 256 for the 256 x 256 kernel, 1064 / 1128 for the
+    register-staged kernel; staged = the through-LDS epilogue; packed = 4-row packed stores of transposed segments."""
+    names = ("rowT", "bias", "act", "residual", "bf16", "rowadd", "rowadd_mode", "rowadd_scale", "rowadd_off", "rowadd_div",
+             "force_simple", "cfg")
+    defaults = dict(zip(names, (1, None, 0, None, False, None, 0, 1.0, 0, 1, False, 0)))
+    assert set(kw) <= set(names), set(kw) - set(names)
+    defaults.update(kw)
+    args, keep = _gemm_map_args(a, w, segs, *(defaults[k] for k in names))
+    word = L.load().dimx_op_gemm_route(*args)
+    del keep
+    if word < 0:
+        L.check(word, "dimx_op_gemm_route")
+    return word & 0xffff, bool(word >> 16 & 1), bool(word >> 17 & 1)
+
+
 def op_lstm_layer(x, w_ih, w_hh, b_ih, b_hh, safe=False, return_faults=False):
     """One bidirectional LSTM layer (csrc/lstm.hip): x [B,T,In] f32; w_ih / w_hh / b_ih / b_hh: pairs (forward, reverse) of
     tensors shaped like torch.nn.LSTM's -> y [B,T,768] f32.  ``safe``: the no-communication path (flags bit 0)."""

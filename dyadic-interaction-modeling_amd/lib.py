@@ -176,6 +176,12 @@ SIGNATURES = {
                              c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "dimx_op_gemm_headmajor": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                        c_int, c_void_p]),
+    "dimx_op_gemm_map": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                 c_int, c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int32), c_void_p, c_int, c_int, c_float,
+                                 c_int, c_int, c_int, c_void_p]),
+    "dimx_op_gemm_route": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                   c_int, c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int32), c_void_p, c_int, c_int, c_float,
+                                   c_int, c_int, c_int]),
     "dimx_op_layernorm": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dimx_op_instnorm": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dimx_op_attention": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -762,6 +762,28 @@ int dimx_op_gemm_slabs(int in_dtype, int M, int N, int K, int flags);
  * `out`.  bf16 with nlayers = 4 is the fused all-layers launch of the 256 x 256 kernel; f32 supports nlayers = 1. */
 int dimx_op_gemm_headmajor(int dtype, const void* A, int lda, const void* W, int ldw, void* out, int M, int N, int K,
                            int rowT, int Tp, int nlayers, void* stream);
+/* dimx_op_gemm with an output map instead of a plain C (the epilogue's scatter as the model's projections use it; unit tests).  Rows
+ * decompose as m = b * rowT + t (the last clip may be partial); the N columns are nseg (1..3) equal segments of N / nseg columns, and element
+ * (m, n) of segment s, nn = n - s * (N / nseg), goes to seg_ptr[s] + b * sb + t * st + (nn / D) * sh + (nn % D) * sd (element strides;
+ * seg_strides = [nseg][4] = {sb, sh, st, sd}, seg_D [nseg], D divides N / nseg).  sd == 1 is a row-contiguous segment, anything
+ * else a transposed one (V^T: st == 1).  Row add (after the activation, before the residual): rowadd_mode 0 none, 1 table row t,
+ * 2 table row b / rowadd_div + rowadd_off, 3 table row rowadd_off; the table is [rows, ld_rowadd] f32 and its row is scaled by
+ * rowadd_scale.  flags: bit 1 and bits 8..15 as in dimx_op_gemm (no conv, no slabs).  DIMX_ERR_ARG for a null operand or segment,
+ * segments that do not divide N, a mode outside 0..3 or a mode without a table, and whatever the launcher itself refuses (cfg 72
+ * with a map, ...); nothing is launched then. */
+int dimx_op_gemm_map(int in_dtype, int out_dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
+                     int act, const float* residual, int ldr, int rowT, int nseg, void* const* seg_ptr, const int64_t* seg_strides,
+                     const int32_t* seg_D, const float* rowadd, int ld_rowadd, int rowadd_mode, float rowadd_scale, int rowadd_off,
+                     int rowadd_div, int flags, void* stream);
+/* What a dimx_op_gemm_map call with these arguments would launch, answered by the launcher's own decision code; nothing is read,
+ * written or launched (only the alignment of the pointers counts).  Returns a negative DIMX_ERR_* as the call would, else the route
+ * word: bits 0..15 the kernel -- the LDS-DMA kernels' cfg id 1 / 3 / 4 / 14 / 34 / 35 / 72, 256 the 256 x 256 kernel, 1064 / 1128 the
+ * register-staged kernel with its 64 x 64 / 128 x 128 tile --, bit 16 the staged (through-LDS) epilogue, bit 17 packed 4-row stores
+ * of transposed segments. */
+int dimx_op_gemm_route(int in_dtype, int out_dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
+                       int act, const float* residual, int ldr, int rowT, int nseg, void* const* seg_ptr, const int64_t* seg_strides,
+                       const int32_t* seg_D, const float* rowadd, int ld_rowadd, int rowadd_mode, float rowadd_scale, int rowadd_off,
+                       int rowadd_div, int flags);
 /* One bidirectional LSTM layer (csrc/lstm.hip; torch.nn.LSTM(batch_first=True, bidirectional=True), eval, zero initial state, gate
  * order i, f, g, o): x [B,T,In] f32 (In % 4 == 0), H = 384, w_ih[d] [4H,In], w_hh[d] [4H,H], b_ih[d] / b_hh[d] [4H] f32 device
  * pointers (d = 0 forward, 1 reverse), y [B,T,2H] f32, forward half first.  No lengths: every clip runs over all T frames.
