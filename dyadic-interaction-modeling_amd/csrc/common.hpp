@@ -418,8 +418,14 @@ struct Kv8AttnArgs {
     int force_nsplit;      // tests: waves per (clip, head) (0 = automatic)
     int win, lookahead;    // the windowed form: keys j < clamp(*step + 2 + lookahead, 1, n_keys)
     const int32_t* step;
+    // the multi-query form only (launch_decode_attn_mq_kv8): rows b*S .. b*S+S-1 of q / out share clip b's codes, scales and mask row
+    int rows_per_clip;     // S in {2, 4, 5, 8, 10}; B counts clips
+    int q_bf16;            // q is one bf16 row array [B*S, q_ld] (a plain projection's output), nslab = 1
+    int exact;             // 0: matrix-core form (q and p * vscale rounded to bf16), 1: exact form (three bf16 planes of each)
 };
 int launch_decode_attn_kv8(const Kv8AttnArgs& a, hipStream_t s);
+// S queries of a clip against that clip's FP8 codes on the matrix cores, the codes read once for all S (dimx/kv8.py attention_rows)
+int launch_decode_attn_mq_kv8(const Kv8AttnArgs& a, hipStream_t s);
 // rows 0 .. T - 1 of every (clip, head) of one cache [B,H,Tp,64] (dtype) -> codes [B,H,Tp,64] / scales [B,H,Tp]; cache_T > 0: the
 // cache is [B,H,cache_T,64] (a generation's self caches)
 int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s, int cache_T = 0);

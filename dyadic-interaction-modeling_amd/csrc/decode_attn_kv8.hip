@@ -11,6 +11,8 @@
 // softmax scale and applies the mask; the value loop's lane i turns that score into p and stores p * vscale for the batch's
 // fmas while summing the unscaled p.  A wave only ever touches the scores of the batches it scored itself, so the waves of a
 // (clip, head) meet at the three fixed-order reductions (max, sum, output) and nowhere else.  No atomics; repeats are bit-identical.
+// decode_attn_mq_kv8_kernel (further down) is the multi-query form for best-of-N generation: the S queries of a clip against that
+// clip's codes on the matrix cores, one wave per (clip, head), the codes read once for all S (dimx/kv8.py attention_rows).
 #include "common.hpp"
 #include "decode_attn_body.hpp"
 
@@ -452,7 +454,270 @@ __global__ __launch_bounds__(256, 4) void decode_attn_self_kv8_kernel(const Kv8S
     }
 }
 
+// ---- the multi-query form (dimx/kv8.py attention_rows): the S <= 16 queries of a clip against that clip's codes on the matrix cores,
+// one wave per (clip, head), the codes read once for all S.  v_mfma_f32_16x16x32_bf16 throughout; a tile is 32 keys:
+//   * load shape: lane (g = lane >> 4, i = lane & 15) loads the 16 codes [16 g, 16 g + 16) of key j0 + 16 t + i (t = 0, 1) -- still 16 keys
+//     x 64 B = 1 KiB per wave-wide load -- and converts them to bf16 in registers (every e4m3fn value is a bf16 value: exact);
+//   * scores transposed, S^T = K . Q^T: the K fragment of k-step s is the lane's codes 8 s .. 8 s + 7, the Q fragment the same
+//     elements of query i's row (rows i >= S are zero), so both operands contract in the same permuted order.  The tile's result has
+//     the query on the lane (column i) and the keys j0 + 16 t + 4 g + r in its registers: kscale, the softmax scale and the mask are
+//     applied to it in f32 (one scale per key, never folded into an operand), the softmax is online over tiles, and the row sum is
+//     accumulated from the unrounded f32 p;
+//   * p * vscale, rounded once to bf16, is ALREADY the B operand of O^T = V^T . P^T with k-slot 8 g + 4 t + r <-> key j0 + 16 t + 4 g + r
+//     (the accumulator-as-operand idiom); V^T's fragment wants one d and eight keys per lane while the codes lie key-major, so the
+//     wave stores its bf16 V tile [32 keys][64 d] to its own LDS rows and reads it back with ds_read_b64_tr_b16 (attention_tr.hip has
+//     the lane map): group g's read t addresses keys 16 t + 4 g .. + 3 of the 16 d of block c and hands lane i column i of them;
+//   * NP = 3 (the exact form): q and p * vscale enter as three bf16 planes each (x = x0 + x1 + x2 exactly, the gemm_x3.hip idea);
+//     a bf16 plane times an exact bf16 code is exact in f32, so the result is the f32 one up to accumulation order.
+// Loads are clamped to row n - 1 and slots at or past n get p = 0, so nothing at or past the bound is read; padded query rows are
+// never stored.  One wave per pair whatever the batch: a slice of clips has the whole batch's bits.  No atomics, no block barrier.
+typedef uint32_t u32x4_mq __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_mq __attribute__((ext_vector_type(2)));
+constexpr int kMqVld = 144;   // bytes per key row of a wave's V tile in LDS: 64 bf16 and 16 bytes of padding
+
+__device__ __forceinline__ void codes_to_bf16x16(const uint4& u, u32x4_mq (&f)[2]) {
+    float v[16];
+    unpack_fp8x16(u, v);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        f[i] = u32x4_mq{pack_bf16x2(v[8 * i], v[8 * i + 1]), pack_bf16x2(v[8 * i + 2], v[8 * i + 3]), pack_bf16x2(v[8 * i + 4], v[8 * i + 5]),
+                        pack_bf16x2(v[8 * i + 6], v[8 * i + 7])};
+}
+// the eight transposing reads of a V tile: t[2 c + tt] = column (lane & 15) of the [4 keys][16 d] block at keys 16 tt + 4 g .., d 16 c ..
+__device__ __forceinline__ void lds_read_v_tr16(uint32_t addr, u32x2_mq (&t)[8]) {
+    asm volatile(
+        "ds_read_b64_tr_b16 %0, %8\n\t"
+        "ds_read_b64_tr_b16 %1, %8 offset:2304\n\t"
+        "ds_read_b64_tr_b16 %2, %8 offset:32\n\t"
+        "ds_read_b64_tr_b16 %3, %8 offset:2336\n\t"
+        "ds_read_b64_tr_b16 %4, %8 offset:64\n\t"
+        "ds_read_b64_tr_b16 %5, %8 offset:2368\n\t"
+        "ds_read_b64_tr_b16 %6, %8 offset:96\n\t"
+        "ds_read_b64_tr_b16 %7, %8 offset:2400\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7])
+        : "v"(addr)
+        : "memory");
+}
+static_assert(16 * kMqVld == 2304, "lds_read_v_tr16's offsets are 16 key rows apart");
+
+// NP bf16 planes of eight floats, plane p in f[p]: x = f[0] + f[1] + .. exactly while the remainders are representable
+template <int NP> __device__ __forceinline__ void bf16_planes8(float (&x)[8], u32x4_mq (&f)[NP]) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t word = pack_bf16x2(x[2 * w], x[2 * w + 1]);
+            f[p][w] = word;
+            if (p + 1 < NP) {
+                x[2 * w] -= bf16_to_f32((uint16_t)(word & 0xffffu));
+                x[2 * w + 1] -= bf16_to_f32((uint16_t)(word >> 16));
+            }
+        }
+}
+
+template <typename TO, int NP>
+__global__ __launch_bounds__(256) void decode_attn_mq_kv8_kernel(const Kv8AttnArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char vt[4][32 * kMqVld];
+    __shared__ __attribute__((aligned(16))) float sl[4][64];   // the tile's K scales | V scales, one per key
+    __shared__ __attribute__((aligned(16))) float sk[4][32];   // the tile's key states: 0 a key, 1 masked, 2 at or past the bound
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pair = blockIdx.x * 4 + wave;
+    if (pair >= a.B * a.H) return;   // whole waves leave; nothing below meets another wave
+    const int b = pair / a.H, h = pair % a.H;
+    const int S = a.rows_per_clip;
+    const int qi = lane & 15, g = lane >> 4;
+    const bool qlive = qi < S;
+    const size_t qrow = (size_t)b * S + (qlive ? qi : 0);
+
+    u32x4_mq qf[NP][2];
+    {
+        float qv[16];
+        if (a.q_bf16) load_row16<bf16>((const bf16*)(const void*)a.q + qrow * a.q_ld + h * 64 + g * 16, qv);
+        else load_f32_slabs<16>(a.q + qrow * a.q_ld + h * 64 + g * 16, a.nslab, a.slab_stride, qv);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float x[8];
+            u32x4_mq f[NP];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = qlive ? qv[8 * i + e] : 0.f;
+            bf16_planes8<NP>(x, f);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) qf[p][i] = f[p];
+        }
+    }
+    int n = a.n_keys;
+    if (a.win) n = win_keys(*a.step, a.lookahead, a.n_keys);
+    const float scale2 = a.scale * 1.4426950408889634f;
+
+    const size_t row0 = (size_t)(b * a.H + h) * a.Tmax;
+    const uint8_t* kc = a.kcodes + row0 * 64 + g * 16;
+    const uint8_t* vc = a.vcodes + row0 * 64 + g * 16;
+    const float* ks = a.kscale + row0;
+    const float* vs = a.vscale + row0;
+    const uint8_t* km = a.kmask ? a.kmask + (size_t)b * a.kmask_ld : nullptr;
+    unsigned char* vrow = &vt[wave][0];
+    const uint32_t vaddr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)vrow + (4 * g + (qi >> 2)) * kMqVld + (qi & 3) * 8;
+
+    auto load_tile = [&](const uint8_t* base, int j0, uint4 (&r)[2]) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int j = j0 + 16 * t + qi;
+            r[t] = ld_stream(base + (size_t)(j < n ? j : n - 1) * 64);
+        }
+    };
+    // lanes 0 .. 31: K scale and state of key j0 + lane; lanes 32 .. 63: V scale of key j0 + lane - 32
+    auto load_side = [&](int j0, float& sc, float& st) {
+        const int j = j0 + (lane & 31), jc = j < n ? j : n - 1;
+        sc = lane < 32 ? ks[jc] : vs[jc];
+        st = j >= n ? 2.f : ((km && lane < 32 && km[jc] == 0) ? 1.f : 0.f);
+    };
+
+    uint4 kcur[2] = {}, vcur[2] = {}, knxt[2] = {}, vnxt[2] = {};
+    float scc = 0.f, scn = 0.f, stc = 2.f, stn = 2.f;
+    load_tile(kc, 0, kcur);
+    load_tile(vc, 0, vcur);
+    load_side(0, scc, stc);
+
+    float m_run = kNegD, lsum = 0.f;
+    f32x4_t o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    for (int j0 = 0; j0 < n; j0 += 32) {
+        if (j0 + 32 < n) {
+            load_tile(kc, j0 + 32, knxt);
+            load_tile(vc, j0 + 32, vnxt);
+            load_side(j0 + 32, scn, stn);
+        }
+        sl[wave][lane] = scc;
+        if (lane < 32) sk[wave][lane] = stc;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {   // the V tile, bf16, key-major
+            u32x4_mq f[2];
+            codes_to_bf16x16(vcur[t], f);
+            unsigned char* p = vrow + (16 * t + qi) * kMqVld + g * 32;
+            *(u32x4_mq*)p = f[0];
+            *(u32x4_mq*)(p + 16) = f[1];
+        }
+        // ---- scores of the tile: S^T[key][query]
+        f32x4_t sacc[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            u32x4_mq kf[2];
+            codes_to_bf16x16(kcur[t], kf);
+            sacc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int p = NP - 1; p >= 0; --p)
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    sacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf[s]), __builtin_bit_cast(bf16x8_t, qf[p][s]),
+                                                                      sacc[t], 0, 0, 0);
+        }
+        float sv[8], vsc[8];
+        bool live[8];
+        float tmax = kNegD;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const float4 k4 = *(const float4*)&sl[wave][16 * t + 4 * g];
+            const float4 v4 = *(const float4*)&sl[wave][32 + 16 * t + 4 * g];
+            const float4 s4 = *(const float4*)&sk[wave][16 * t + 4 * g];
+            const float kk[4] = {k4.x, k4.y, k4.z, k4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float x = (sacc[t][r] * kk[r]) * scale2;
+                if (ss[r] == 1.f) x = kNegD;
+                live[4 * t + r] = ss[r] < 2.f;
+                sv[4 * t + r] = x;
+                vsc[4 * t + r] = vv[r];
+                if (live[4 * t + r]) tmax = fmaxf(tmax, x);
+            }
+        }
+        tmax = fmaxf(tmax, xor_lane_f32<16>(tmax));
+        tmax = fmaxf(tmax, xor_lane_f32<32>(tmax));
+        const float m_new = fmaxf(m_run, tmax);
+        const float alpha = exp2f(m_run - m_new);
+        m_run = m_new;
+        lsum *= alpha;
+        float pv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float p = live[e] ? exp2f(sv[e] - m_new) : 0.f;
+            lsum += p;
+            pv[e] = live[e] ? p * vsc[e] : 0.f;
+        }
+        u32x4_mq pf[NP];
+        bf16_planes8<NP>(pv, pf);
+        // ---- O^T[d][query] += V^T . P^T
+        u32x2_mq tv[8];
+        lds_read_v_tr16(vaddr, tv);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const u32x4_mq vf = {tv[2 * c][0], tv[2 * c][1], tv[2 * c + 1][0], tv[2 * c + 1][1]};
+            o[c] *= alpha;
+#pragma unroll
+            for (int p = NP - 1; p >= 0; --p)
+                o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf), __builtin_bit_cast(bf16x8_t, pf[p]), o[c], 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) { kcur[t] = knxt[t]; vcur[t] = vnxt[t]; }
+        scc = scn;
+        stc = stn;
+    }
+    lsum += xor_lane_f32<16>(lsum);
+    lsum += xor_lane_f32<32>(lsum);
+    const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
+    if (qlive) {   // lane: query qi, d 16 c + 4 g .. + 3
+        TO* op = (TO*)a.out + qrow * a.o_ld + h * 64 + 4 * g;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float r0 = o[c][0] * inv, r1 = o[c][1] * inv, r2 = o[c][2] * inv, r3 = o[c][3] * inv;
+            if constexpr (sizeof(TO) == 2) *(uint2*)(op + 16 * c) = make_uint2(pack_bf16x2(r0, r1), pack_bf16x2(r2, r3));
+            else *(float4*)(op + 16 * c) = make_float4(r0, r1, r2, r3);
+        }
+    }
+}
+
 }  // namespace
+
+int launch_decode_attn_mq_kv8(const Kv8AttnArgs& a, hipStream_t s) {
+    DIMX_REQUIRE(a.q && a.kcodes && a.kscale && a.vcodes && a.vscale && a.out, DIMX_ERR_ARG, "decode_attn_kv8_multi: null operand");
+    DIMX_REQUIRE(a.out_dtype == DIMX_BF16 || a.out_dtype == DIMX_F32, DIMX_ERR_ARG, "decode_attn_kv8_multi: out_dtype %d", a.out_dtype);
+    const int S = a.rows_per_clip;
+    DIMX_REQUIRE(S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG, "decode_attn_kv8_multi: rows_per_clip %d not in {2,4,5,8,10}", S);
+    DIMX_REQUIRE(a.B >= 1 && a.H >= 1 && a.Tmax >= 1, DIMX_ERR_ARG, "decode_attn_kv8_multi: empty shape");
+    DIMX_REQUIRE(a.n_keys >= 1 && a.n_keys <= a.Tmax && a.n_keys <= kMaxKeys, DIMX_ERR_ARG,
+                 "decode_attn_kv8_multi: n_keys %d outside 1 .. min(Tmax = %d, %d)", a.n_keys, a.Tmax, kMaxKeys);
+    const long rows = (long)a.B * S;
+    if (a.q_bf16)
+        DIMX_REQUIRE(a.nslab == 1 && a.q_ld % 8 == 0, DIMX_ERR_ARG, "decode_attn_kv8_multi: bf16 q is one row array (nslab = %d) with q_ld = %d a multiple of 8",
+                     a.nslab, a.q_ld);
+    else
+        DIMX_REQUIRE(a.nslab >= 1 && a.nslab <= 8 && (a.nslab == 1 || a.slab_stride >= rows * a.q_ld) && a.q_ld % 4 == 0 && a.slab_stride % 4 == 0,
+                     DIMX_ERR_ARG, "decode_attn_kv8_multi: nslab=%d (1..8) with slabs %ld apart, q_ld=%d (16-byte multiples)", a.nslab, a.slab_stride, a.q_ld);
+    const int oal = a.out_dtype == DIMX_BF16 ? 8 : 4;
+    DIMX_REQUIRE(a.q_ld >= a.H * 64 && a.o_ld >= a.H * 64 && a.o_ld % oal == 0, DIMX_ERR_ARG,
+                 "decode_attn_kv8_multi: q_ld=%d o_ld=%d (rows of at least H*64, o_ld a 16-byte multiple)", a.q_ld, a.o_ld);
+    DIMX_REQUIRE((uintptr_t)a.q % 16 == 0 && (uintptr_t)a.kcodes % 16 == 0 && (uintptr_t)a.vcodes % 16 == 0 && (uintptr_t)a.out % 16 == 0 &&
+                     (uintptr_t)a.kscale % 4 == 0 && (uintptr_t)a.vscale % 4 == 0,
+                 DIMX_ERR_ARG, "decode_attn_kv8_multi: misaligned operand (q / codes / out 16 bytes, scales 4)");
+    DIMX_REQUIRE(a.kmask == nullptr || a.kmask_ld >= a.n_keys, DIMX_ERR_ARG, "decode_attn_kv8_multi: kmask_ld=%d < n_keys=%d", a.kmask_ld, a.n_keys);
+    DIMX_REQUIRE(!a.win || a.step != nullptr, DIMX_ERR_ARG, "decode_attn_kv8_multi: the windowed form needs a step counter");
+    const long pairs = (long)a.B * a.H;
+    DIMX_REQUIRE(pairs <= 0x7fffffffL && rows * a.q_ld <= 0x7fffffffffL, DIMX_ERR_ARG, "decode_attn_kv8_multi: %ld (clip, head) pairs", pairs);
+    // one wave per (clip, head) in both forms, whatever the batch: a slice of clips reproduces the whole batch's rows bit for bit
+    dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
+#define KV8_MQ(TT)                                                                                    \
+    do {                                                                                              \
+        if (a.exact) hipLaunchKernelGGL((decode_attn_mq_kv8_kernel<TT, 3>), grid, block, 0, s, a);    \
+        else hipLaunchKernelGGL((decode_attn_mq_kv8_kernel<TT, 1>), grid, block, 0, s, a);            \
+    } while (0)
+    if (a.out_dtype == DIMX_BF16) KV8_MQ(bf16);
+    else KV8_MQ(float);
+#undef KV8_MQ
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
 
 int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s, int cache_T) {
     DIMX_REQUIRE(dtype == DIMX_BF16 || dtype == DIMX_F32, DIMX_ERR_ARG, "kv8_quantize: dtype %d", dtype);

@@ -342,7 +342,9 @@ static DecodeAttnArgs cross_args(const StepCtx& c, int l) {
 }
 
 // The step's one-query cross attention: the cache form, or (route kv8) the same arguments over the FP8 copy of the context K/V
-static int cross_attention(const StepCtx& c, int l, const DecodeAttnArgs& ca) {
+// With several samples per clip (route kv8_samples) it is the multi-query launch: ca.B clips of ca.rows_per_clip rows, q as the f32
+// slabs of the projection, or (qb: the bf16 rows of a plain projection) in the operand type; the exact form on an f32 handle.
+static int cross_attention(const StepCtx& c, int l, const DecodeAttnArgs& ca, const void* qb = nullptr) {
     if (!c.r->kv8) return launch_decode_attn(ca, c.st);
     Kv8AttnArgs a;
     memset(&a, 0, sizeof(a));
@@ -351,6 +353,12 @@ static int cross_attention(const StepCtx& c, int l, const DecodeAttnArgs& ca) {
     a.out = ca.out; a.out_dtype = ca.dtype; a.o_ld = ca.o_ld; a.B = ca.B; a.H = ca.H;
     a.n_keys = ca.n_keys; a.kmask = ca.kmask; a.kmask_ld = ca.kmask_ld; a.scale = ca.scale;
     a.win = ca.win; a.lookahead = ca.lookahead; a.step = ca.step;
+    if (c.r->kv8_samples) {
+        a.rows_per_clip = ca.rows_per_clip;
+        a.exact = ca.dtype == DIMX_F32 ? 1 : 0;
+        if (qb) { a.q = (const float*)qb; a.q_bf16 = 1; a.nslab = 1; a.slab_stride = 0; }
+        return launch_decode_attn_mq_kv8(a, c.st);
+    }
     return launch_decode_attn_kv8(a, c.st);
 }
 
@@ -490,7 +498,15 @@ static int attention_half(const StepCtx& c, int l, int* pending) {
         DIMX_TRY(self_attention(c, l, sa));
         DIMX_TRY(slab_gemm(c, s.o, inner, h->dec.self_[l].out, s.xr, s.st_xr, pending));
         DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, *pending, s.st_xr, s.y, h->dec.cross[l].ln_g, B, DD, c.st));
-        if (r.multi_tr && !r.win) {
+        if (r.multi_tr && !r.win && r.kv8_samples) {
+            // the bf16 projection of cross_attention_multi (rows = clips x S: no split-K), then the S queries of a clip over its codes
+            GemmArgs g;
+            gemm_lin(h, s.y, DD, h->dec.cross[l].qkv, B, g);
+            g.out_dtype = h->at;
+            gemm_set_plain_out(g, s.qcb, inner);
+            DIMX_TRY(launch_gemm(g, c.st));
+            DIMX_TRY(cross_attention(c, l, ca, s.qcb));
+        } else if (r.multi_tr && !r.win) {
             DIMX_TRY(cross_attention_multi(c, l, ca));
         } else {
             DIMX_TRY(slab_gemm(c, s.y, DD, h->dec.cross[l].qkv, s.qc, s.st_qc, &ns));
@@ -644,6 +660,7 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     r.win = h->xwin_on != 0;
     r.lookahead = r.win ? h->xwin_lookahead : 0;
     r.kv8 = h->kv8_buf != nullptr;   // the layer kernel streams the caches itself: not taken, exactly as under the window
+    r.kv8_samples = r.kv8 && q.S > 1;   // gen_open let S > 1 through under dimx_set_cross_kv8_samples only
     r.self_kv8 = h->self_kv8_buf != nullptr;   // no layer kernel either: it streams the self caches itself
     r.guided = q.guided;
     if (r.guided) r.chain = r.defer = r.logits_chain = r.multi_tr = false;   // the per-op step, as a session takes it (no layer kernel either: it needs chain)
@@ -690,6 +707,7 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
     k.xwin_on = r.win ? 1 : 0; k.xwin_lookahead = r.lookahead;
     k.guided = r.guided; k.branch_out = q.branch_out;
     k.kv8 = r.kv8 ? h->kv8_buf : nullptr;
+    k.kv8_samples = r.kv8_samples;
     k.self_kv8 = r.self_kv8 ? h->self_kv8_buf : nullptr;
     return k;
 }
@@ -904,7 +922,8 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
                  "generate: n_samples %d not in {1,2,4,5,8,10}", S);
     if (h && h->kv8_buf && !sess) {   // FP8 cross K/V: one row per clip, the sampler ends the step; a session does not read the setting
-        DIMX_REQUIRE(S == 1 && !q.beam, DIMX_ERR_ARG, "generate: n_samples > 1 and beam search are not available with dimx_set_cross_kv8");
+        DIMX_REQUIRE((S == 1 || (h->kv8_samples_on && !q.guided)) && !q.beam, DIMX_ERR_ARG,
+                     "generate: n_samples > 1 and beam search are not available with dimx_set_cross_kv8");
         DIMX_REQUIRE(kv8_bytes(h, B, T) != 0, DIMX_ERR_ARG, "generate: B=%d T=%d is not supported with dimx_set_cross_kv8", B, T);
         DIMX_REQUIRE(h->kv8_bytes >= kv8_bytes(h, B, T), DIMX_ERR_WORKSPACE, "generate: the FP8 cross K/V buffer holds %zu bytes, B=%d T=%d needs %zu (dimx_cross_kv8_bytes)",
                      h->kv8_bytes, B, T, kv8_bytes(h, B, T));
@@ -954,6 +973,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         route.win = true;
         route.lookahead = sess->lookahead;
         route.kv8 = false;
+        route.kv8_samples = false;
         route.self_kv8 = false;
         run.graphs = false;
     }
@@ -1299,6 +1319,21 @@ int dimx_cross_kv8(dimx_handle h, void** buf, size_t* bytes) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
     if (buf) *buf = h->kv8_buf;
     if (bytes) *bytes = h->kv8_bytes;
+    return DIMX_OK;
+}
+
+int dimx_set_cross_kv8_samples(dimx_handle h, int on) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "set_cross_kv8_samples: null handle");
+    DIMX_NO_SESSION(h, "set_cross_kv8_samples");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_cross_kv8_samples: FP8 cross K/V is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    h->kv8_samples_on = on ? 1 : 0;
+    return DIMX_OK;
+}
+
+int dimx_cross_kv8_samples(dimx_handle h, int* on) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "cross_kv8_samples: null handle");
+    if (on) *on = h->kv8_samples_on;
     return DIMX_OK;
 }
 

@@ -130,6 +130,7 @@ struct StepRoute {
     bool win = false;              // online generation: the cross attention's key count follows the step counter
     int lookahead = 0;
     bool kv8 = false;              // the cross attention reads the FP8 copy of the context K/V (dimx_set_cross_kv8; decode_attn_kv8.hip)
+    bool kv8_samples = false;      // kv8 with several samples per clip: the multi-query launch over the codes (dimx_set_cross_kv8_samples)
     bool self_kv8 = false;         // the self attention appends to and reads FP8 self caches (dimx_set_self_kv8; decode_attn_kv8.hip)
     const float* qkv0 = nullptr;   // the first layer's q/k/v table or nullptr
     const void* kv0 = nullptr;     // the first layer's K / V table (the bf16 image, or the q/k/v table itself in the f32 mode): its self
@@ -161,6 +162,7 @@ struct GraphKey {
     bool guided;                   // the guided step's launches; the scale lives in device memory
     const void* branch_out;        // ... and its optional dump of both branches' logits
     const void* kv8;               // the FP8 cross K/V buffer the cross attention's launches read (dimx_set_cross_kv8), nullptr = off
+    bool kv8_samples;              // dimx_set_cross_kv8_samples: the multi-query launch over the codes
     const void* self_kv8;          // the FP8 self K/V buffer the self attention's launches append to and read (dimx_set_self_kv8), nullptr = off
     bool operator==(const GraphKey& o) const {
         return ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && noise == o.noise && start == o.start && mask == o.mask &&
@@ -168,7 +170,7 @@ struct GraphKey {
                logits_chain == o.logits_chain && multi_tr == o.multi_tr && fault_inject == o.fault_inject &&
                layer_kernel == o.layer_kernel && qkv0 == o.qkv0 && kv0 == o.kv0 && sample_head == o.sample_head && prompt_len == o.prompt_len &&
                ld_prompt == o.ld_prompt && Pmax == o.Pmax && filter_kind == o.filter_kind && beam == o.beam && xwin_on == o.xwin_on &&
-               xwin_lookahead == o.xwin_lookahead && guided == o.guided && branch_out == o.branch_out && kv8 == o.kv8 && self_kv8 == o.self_kv8;
+               xwin_lookahead == o.xwin_lookahead && guided == o.guided && branch_out == o.branch_out && kv8 == o.kv8 && kv8_samples == o.kv8_samples && self_kv8 == o.self_kv8;
     }
 };
 
@@ -269,6 +271,7 @@ struct dimx_ctx {
     // decode steps' cross attention reads; nullptr = off
     void* kv8_buf = nullptr;
     size_t kv8_bytes = 0;
+    int kv8_samples_on = 0;   // dimx_set_cross_kv8_samples: generations with n_samples > 1 take the buffer too (decode_attn_mq_kv8_kernel)
     // FP8 self-attention K/V (dimx_set_self_kv8): the caller's buffer every decode step appends its quantised k / v row to and the
     // self attention reads, rows = sequences (clips x samples); nullptr = off
     void* self_kv8_buf = nullptr;

@@ -535,6 +535,23 @@ int dimx_op_decode_attn_kv8(int out_dtype, const void* q, int q_ld, int q_is_f32
     return launch_decode_attn_kv8(a, (hipStream_t)stream);
 }
 
+/* ... and S query rows per clip on the matrix cores (decode_attn_mq_kv8_kernel): q as f32 slabs or bf16 rows, exact = the three-plane form */
+int dimx_op_decode_attn_kv8_multi(int out_dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, const uint8_t* kcodes,
+                                  const float* kscale, const uint8_t* vcodes, const float* vscale, void* out, int o_ld, int B, int H, int Tmax,
+                                  const int32_t* step_dev, int n_keys, const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale,
+                                  int nsplit, int lookahead, int win, int exact, void* stream) {
+    (void)nsplit;   // one wave per (clip, head) in both forms
+    DIMX_REQUIRE(!win || step_dev != nullptr, DIMX_ERR_ARG, "op_decode_attn_kv8_multi: the windowed form needs a step counter");
+    Kv8AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const float*)q; a.q_ld = q_ld; a.nslab = nslab; a.slab_stride = slab_stride; a.q_bf16 = q_is_f32 ? 0 : 1;
+    a.kcodes = kcodes; a.kscale = kscale; a.vcodes = vcodes; a.vscale = vscale; a.Tmax = Tmax;
+    a.out = out; a.out_dtype = out_dtype; a.o_ld = o_ld; a.B = B; a.H = H; a.rows_per_clip = rows_per_clip;
+    a.n_keys = n_keys; a.kmask = kmask; a.kmask_ld = kmask_ld; a.scale = scale; a.exact = exact ? 1 : 0;
+    if (win) { a.win = 1; a.lookahead = lookahead; a.step = step_dev; }
+    return launch_decode_attn_mq_kv8(a, (hipStream_t)stream);
+}
+
 /* the self form over FP8 self caches: quantise and append this step's k / v row at position n, attend over the rows 0 .. n */
 int dimx_op_decode_attn_self_kv8(int out_dtype, const float* qkv, int ld, int nslab, long slab_stride, uint8_t* kcodes, float* kscale,
                                  uint8_t* vcodes, float* vscale, void* out, int o_ld, int B, int H, int Tmax, const int32_t* step_dev, int n,

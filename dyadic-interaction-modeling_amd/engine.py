@@ -287,6 +287,18 @@ class Engine:
         L.check(self.lib.dimx_cross_kv8(self.h, ctypes.byref(p), ctypes.byref(n)), "dimx_cross_kv8")
         return (p.value, n.value) if p.value else None
 
+    def set_cross_kv8_samples(self, on=True):
+        """FP8 cross K/V for best-of-N (dimx_set_cross_kv8_samples; dimx.kv8.attention_rows): with this on and a cross buffer set,
+        generate calls take ``n_samples > 1`` and every layer's multi-query cross attention reads the codes.
+        ``generate(kv8_samples=True)`` sets buffer and flag around one call."""
+        L.check(self.lib.dimx_set_cross_kv8_samples(self.h, 1 if on else 0), "dimx_set_cross_kv8_samples")
+
+    def cross_kv8_samples(self):
+        """The handle's current setting (bool)."""
+        on = ctypes.c_int(0)
+        L.check(self.lib.dimx_cross_kv8_samples(self.h, ctypes.byref(on)), "dimx_cross_kv8_samples")
+        return bool(on.value)
+
     def cross_kv8_buffer(self):
         """The uint8 tensor the last ``generate(kv8=True)`` quantised into (None before the first); ``cross_kv8_layers`` views it."""
         return getattr(self, "_kv8", None)
@@ -337,8 +349,14 @@ class Engine:
 
     def generate(self, start, mask_u8, T, temperature=1.0, top_k=52, noise=None, seed=0, return_logits=False,
                  n_samples=1, prompt=None, prompt_len=None, prefill=None, no_prefill=False, filter_logits_fn=None,
-                 filter_kwargs=None, return_scores=False, lookahead=None, guidance=None, return_branches=False, kv8=False, self_kv8=False):
+                 filter_kwargs=None, return_scores=False, lookahead=None, guidance=None, return_branches=False, kv8=False, self_kv8=False,
+                 kv8_samples=False):
         """n_samples S > 1: S sequences per clip in one pass (rows b*S+s), sharing the clip's context K/V.
+
+        ``kv8_samples``: ``kv8`` for any ``n_samples`` (``set_cross_kv8_samples``; dimx.kv8.attention_rows): the cross buffer and
+        the flag are set for the call and cleared afterwards; with S > 1 every layer's cross attention is the multi-query launch
+        over the codes.  Works with ``self_kv8``, ``lookahead``, ``prompt``, ``filter_logits_fn``, ``return_logits`` and
+        ``return_scores``; ``guidance`` with S > 1 is refused by the library.  ``kv8=True`` alone stays as it is.
 
         ``self_kv8``: FP8 self-attention K/V caches for this call (``set_self_kv8``; dimx.kv8.self_step): the engine allocates (or
         reuses) its buffer, sets it for the call and clears the setting afterwards.  Any ``n_samples``; works with ``lookahead``,
@@ -380,6 +398,14 @@ class Engine:
         ``no_prefill``) unless ``prefill`` is ``"window"`` (P0 by the default rule above) or ``("window", P0)``: then the first P0
         codes are prefilled by one teacher-forced pass under the window (flags bit 1 of dimx_generate_prompted).  With
         the window off that spelling is the plain prefill."""
+        if kv8_samples:
+            self.set_cross_kv8_samples(True)
+            try:
+                return self.generate(start, mask_u8, T, temperature, top_k, noise, seed, return_logits, n_samples, prompt, prompt_len,
+                                     prefill, no_prefill, filter_logits_fn, filter_kwargs, return_scores, lookahead, guidance,
+                                     return_branches, True, self_kv8)
+            finally:
+                self.set_cross_kv8_samples(False)
         if self_kv8:
             R = (prompt if prompt is not None else start).shape[0] * int(n_samples)
             need = self.self_kv8_bytes(R, T)
@@ -1373,6 +1399,32 @@ def op_decode_attn_kv8(q, kcodes, kscale, vcodes, vscale, scale, n_keys, kmask=N
                                         Tmax, L.ptr(step), int(n_keys), L.ptr(kmask), kld, int(rows_per_clip), float(scale), int(nsplit),
                                         0 if lookahead is None else int(lookahead), 0 if lookahead is None else 1,
                                         L.stream_ptr(q.device)), "dimx_op_decode_attn_kv8")
+    return out
+
+
+def op_decode_attn_kv8_multi(q, kcodes, kscale, vcodes, vscale, scale, n_keys, rows_per_clip, kmask=None, kmask_ld=None, out_bf16=False,
+                             step=None, lookahead=None, exact=None, out=None):
+    """S = ``rows_per_clip`` query rows per clip over FP8 codes on the matrix cores (dimx_op_decode_attn_kv8_multi;
+    dimx.kv8.attention_rows): q [B*S, q_ld] f32, split-K slabs [nslab, B*S, q_ld] f32 or one bf16 row array [B*S, q_ld]; rows
+    b*S .. b*S+S-1 share clip b's kcodes / vcodes [B, H, Tmax, 64] uint8, kscale / vscale [B, H, Tmax] f32 and kmask row.
+    ``exact``: True = the exact form (three bf16 planes), False = the matrix-core form (q and p * vscale rounded to bf16); None =
+    what a handle of the output type takes (exact for f32 out).  ``out``: a [>= B*S, o_ld] tensor to write rows 0 .. B*S-1 of
+    (columns past H*64 and rows past B*S are left alone); default a fresh [B*S, H*64].  lookahead with step: the windowed form."""
+    lib = L.load()
+    B, H, Tmax, _ = kcodes.shape
+    qs = q if q.dim() == 3 else q.unsqueeze(0)
+    nslab, R, q_ld = qs.shape
+    if out is None:
+        out = torch.empty(R, H * 64, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=q.device)
+    out_bf16 = out.dtype == torch.bfloat16
+    if exact is None:
+        exact = not out_bf16
+    kld = kmask_ld if kmask_ld is not None else (kmask.shape[1] if kmask is not None else 0)
+    L.check(lib.dimx_op_decode_attn_kv8_multi(L.BF16 if out_bf16 else L.F32, L.ptr(qs), q_ld, 1 if q.dtype == torch.float32 else 0, nslab,
+                                              qs.stride(0), L.ptr(kcodes), L.ptr(kscale), L.ptr(vcodes), L.ptr(vscale), L.ptr(out),
+                                              out.stride(0), B, H, Tmax, L.ptr(step), int(n_keys), L.ptr(kmask), kld, int(rows_per_clip),
+                                              float(scale), 0, 0 if lookahead is None else int(lookahead), 0 if lookahead is None else 1,
+                                              1 if exact else 0, L.stream_ptr(q.device)), "dimx_op_decode_attn_kv8_multi")
     return out
 
 

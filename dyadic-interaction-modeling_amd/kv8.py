@@ -5,7 +5,9 @@ The cross K/V cache of a generation is written once per clip and read by every d
 step's one-query cross attention computes over such codes.  csrc/decode_attn_kv8.hip follows this file bit for bit (codes, scales)
 or within the step kernels' tolerance (attention); tests/test_kv8_host.py pins the rounding against torch's CPU ``float8_e4m3fn``
 cast.  ``self_step`` is the same for the self-attention caches (dimx_set_self_kv8): the caches that grow by one row per decode step,
-whose new row is quantised by the step itself.
+whose new row is quantised by the step itself.  ``attention_rows`` is ``attention`` for best-of-N generation (dimx_set_cross_kv8_samples):
+several query rows per clip over that clip's codes; ``round_bf16`` and ``pv_abs`` state what its matrix-core form rounds and how far
+that can move an output element.
 
     amax  = max |x| over the row (float32)
     scale = float32(amax) / float32(448)              one IEEE float32 division; amax < 2**-60: a zero row, scale 0, codes 0
@@ -102,6 +104,45 @@ def attention(q, kcodes, kscale, vcodes, vscale, mask, n, scale=0.125):
     p = np.exp(s)
     p = p / p.sum(-1, keepdims=True)
     return np.einsum("bhj,bhjd->bhd", p, v)
+
+
+def _rows_softmax(q, kcodes, kscale, vcodes, vscale, mask, n, S, scale):
+    """attention's softmax for S rows per clip: p [B, S, H, n] float64 (rows sum to 1) and the dequantised V [B, H, n, 64] float64"""
+    B = np.asarray(kcodes).shape[0]
+    q = np.asarray(q, dtype=np.float64)
+    assert q.shape[0] == B * S, "q holds rows_per_clip rows per clip"
+    q = q.reshape((B, S) + q.shape[1:])
+    k = dequantize(np.asarray(kcodes)[:, :, :n], np.asarray(kscale)[:, :, :n]).astype(np.float64)
+    v = dequantize(np.asarray(vcodes)[:, :, :n], np.asarray(vscale)[:, :, :n]).astype(np.float64)
+    s = np.einsum("bshd,bhjd->bshj", q, k) * float(scale)
+    if mask is not None:
+        s = np.where(np.asarray(mask)[:, None, None, :n] == 0, NEG, s)
+    p = np.exp(s - s.max(-1, keepdims=True))
+    return p / p.sum(-1, keepdims=True), v
+
+
+def attention_rows(q, kcodes, kscale, vcodes, vscale, mask, n, rows_per_clip, scale=0.125):
+    """The multi-query form (best-of-N generation; decode_attn_mq_kv8_kernel): ``attention`` per row, with the row's clip's codes.
+
+    q [B * S, H, 64] with S = rows_per_clip: rows b*S .. b*S+S-1 share clip b's codes, scales and mask row.  -> [B * S, H, 64]
+    float64.  The exact form of the kernel computes this within the step kernels' f32 tolerance; the matrix-core form computes it
+    at ``round_bf16(q)`` with p * vscale rounded to bf16 (``pv_abs`` bounds what that rounding moves)."""
+    p, v = _rows_softmax(q, kcodes, kscale, vcodes, vscale, mask, n, int(rows_per_clip), scale)
+    return np.einsum("bshj,bhjd->bshd", p, v).reshape((-1,) + v.shape[1:2] + (64,))
+
+
+def round_bf16(x):
+    """float32 values rounded to bfloat16 (round to nearest even), as float32: what the matrix-core form makes of q"""
+    u = np.ascontiguousarray(np.asarray(x, dtype=np.float32)).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32).reshape(np.shape(x))
+
+
+def pv_abs(q, kcodes, kscale, vcodes, vscale, mask, n, rows_per_clip, scale=0.125):
+    """A = sum_j p_j |v_j| / sum_j p_j of ``attention_rows``' softmax, float64 [B * S, H, 64]: the absolute mass of an output
+    element.  Rounding every p_j * vscale_j to bf16 (unit roundoff 2**-8) moves the element by at most 2**-8 * A."""
+    p, v = _rows_softmax(q, kcodes, kscale, vcodes, vscale, mask, n, int(rows_per_clip), scale)
+    return np.einsum("bshj,bhjd->bshd", p, np.abs(v)).reshape((-1,) + v.shape[1:2] + (64,))
 
 
 def self_step(q, k_new, v_new, kcodes, kscale, vcodes, vscale, n, scale=0.125):

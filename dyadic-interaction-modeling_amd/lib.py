@@ -70,6 +70,11 @@ SIGNATURES = {
     "dimx_op_decode_attn_kv8": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int,
                                         c_int, c_int, c_void_p]),
+    "dimx_op_decode_attn_kv8_multi": (c_int, [c_int, c_void_p, c_int, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int,
+                                              c_int, c_int, c_int, c_void_p]),
+    "dimx_set_cross_kv8_samples": (c_int, [c_void_p, c_int]),
+    "dimx_cross_kv8_samples": (c_int, [c_void_p, POINTER(c_int)]),
     "dimx_self_kv8_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "dimx_set_self_kv8": (c_int, [c_void_p, c_void_p, c_size_t]),
     "dimx_self_kv8": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),

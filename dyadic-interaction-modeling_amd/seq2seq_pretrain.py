@@ -162,7 +162,7 @@ class SLMFT(_EngineOwner):
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
                         seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
                         filter_kwargs=None, return_scores=False, beam_width=0, lookahead=None, window_prefill=False, guidance=None,
-                        kv8=False, self_kv8=False):
+                        kv8=False, self_kv8=False, kv8_samples=False):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -199,7 +199,13 @@ class SLMFT(_EngineOwner):
 
         ``self_kv8`` (mode 'val', any ``n_samples``, no beam search, no guidance): FP8 self-attention K/V caches -- every decode step
         quantises its k / v row and attends over the codes (dimx.kv8.self_step, ``Engine.generate(self_kv8=True)``).  False is the
-        call without the argument, launch for launch."""
+        call without the argument, launch for launch.
+
+        ``kv8_samples`` (mode 'val', any ``n_samples``, no beam search, no guidance): ``kv8`` for best-of-N -- the S queries of a clip
+        read that clip's FP8 codes in one multi-query launch per layer (dimx.kv8.attention_rows,
+        ``Engine.generate(kv8_samples=True)``).  False is the call without the argument, launch for launch."""
+        if kv8_samples and (mode != "val" or beam_width or guidance is not None):
+            raise ValueError("kv8_samples applies to mode='val' without beam search and without guidance")
         if self_kv8 and (mode != "val" or beam_width or guidance is not None):
             raise ValueError("self_kv8 applies to mode='val' without beam search and without guidance")
         if guidance is not None and (mode != "val" or beam_width or int(n_samples) != 1):
@@ -234,6 +240,8 @@ class SLMFT(_EngineOwner):
             gkw = dict(gkw, kv8=True)
         if self_kv8:
             gkw = dict(gkw, self_kv8=True)
+        if kv8_samples:
+            gkw = dict(gkw, kv8_samples=True)
         self._build_context(eng, x_s, v_speaker, x_a, m8, True, n_samples=n_samples, prompt_frames=p0, guided=guidance is not None)
         if beam_width:
             from .scoring import SeqScores, scored_columns
@@ -353,7 +361,7 @@ class SLMFT(_EngineOwner):
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                 return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
                 filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False,
-                guidance=None, kv8=False, self_kv8=False):
+                guidance=None, kv8=False, self_kv8=False, kv8_samples=False):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
@@ -385,7 +393,12 @@ class SLMFT(_EngineOwner):
         ``forward_decoder``).
 
         ``self_kv8`` (mode 'val', any ``n_samples``, no beam search, no guidance): FP8 self-attention K/V caches for the generation
-        (dimx.kv8.self_step; ``forward_decoder``) -- the protocol's best-of-N runs take it."""
+        (dimx.kv8.self_step; ``forward_decoder``) -- the protocol's best-of-N runs take it.
+
+        ``kv8_samples`` (mode 'val', any ``n_samples``, no beam search, no guidance): FP8 cross-attention K/V for a best-of-N
+        generation (dimx.kv8.attention_rows; ``forward_decoder``); combines with ``self_kv8``."""
+        if kv8_samples and (mode != "val" or beam_width is not None or guidance is not None):
+            raise ValueError("kv8_samples applies to mode='val' without beam search and without guidance")
         if self_kv8 and (mode != "val" or beam_width is not None or guidance is not None):
             raise ValueError("self_kv8 applies to mode='val' without beam search and without guidance")
         if guidance is not None and (mode != "val" or beam_width is not None or int(n_samples) != 1):
@@ -412,14 +425,15 @@ class SLMFT(_EngineOwner):
                                         n_samples=n_samples, shard=shard, prompt_frames=prompt_frames, lengths=lengths,
                                         filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
                                         beam_width=beam_width, num_return=num_return, lookahead=lookahead,
-                                        window_prefill=window_prefill, guidance=guidance, kv8=kv8, self_kv8=self_kv8)
+                                        window_prefill=window_prefill, guidance=guidance, kv8=kv8, self_kv8=self_kv8,
+                                        kv8_samples=kv8_samples)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                         return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
                         filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False,
-                        guidance=None, kv8=False, self_kv8=False):
+                        guidance=None, kv8=False, self_kv8=False, kv8_samples=False):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -440,7 +454,8 @@ class SLMFT(_EngineOwner):
                                                          n_samples=S, prompt_frames=prompt_frames, lengths=lengths,
                                                          filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs,
                                                          return_scores=return_scores, beam_width=W, lookahead=lookahead,
-                                                         window_prefill=window_prefill, guidance=guidance, kv8=kv8, self_kv8=self_kv8)
+                                                         window_prefill=window_prefill, guidance=guidance, kv8=kv8, self_kv8=self_kv8,
+                                                         kv8_samples=kv8_samples)
         finally:
             eng.set_shard(0, 0)
         if W and int(num_return) == 1:    # the best hypothesis is row 0 of its clip

@@ -211,7 +211,7 @@ def _select(pending, skip_degenerate, world, device):
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
                         select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, window_prefill=False, guidance=None,
-                        kv8=False, self_kv8=False, **forward_kw):
+                        kv8=False, self_kv8=False, kv8_samples=False, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -283,7 +283,15 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
 
     ``self_kv8``: every generation keeps its self-attention K / V caches in FP8 (dimx.kv8.self_step, ``SLMFT.forward(self_kv8=True)``).
     The batched best-of-``beam_size`` pass takes it as it is, with every ``select``; not with ``decode="beam"`` or ``guidance``
-    (ValueError).  False (default) leaves every path as it is."""
+    (ValueError).  False (default) leaves every path as it is.
+
+    ``kv8_samples``: ``kv8`` for the batched pass (dimx.kv8.attention_rows, ``SLMFT.forward(kv8_samples=True)``): the
+    ``beam_size`` tries of a clip stay ONE generation whose multi-query cross attention reads the FP8 codes, with every ``select``
+    and with ``self_kv8``; not with ``decode="beam"`` or ``guidance`` (ValueError).  False (default) leaves every path as it is."""
+    if kv8_samples:
+        if decode == "beam" or guidance is not None:
+            raise ValueError("evaluate_test_epoch(kv8_samples=True) applies to decode='sample' without guidance")
+        forward_kw = dict(forward_kw, kv8_samples=True)
     if self_kv8:
         if decode == "beam" or guidance is not None:
             raise ValueError("evaluate_test_epoch(self_kv8=True) applies to decode='sample' without guidance")

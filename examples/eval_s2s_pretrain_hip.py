@@ -68,6 +68,10 @@ def main():
     ap.add_argument("--self-kv8", action="store_true",
                     help="FP8 self-attention K/V caches (dimx.kv8.self_step): every decode step quantises its k / v row and attends over the "
                          "codes.  Any number of samples per clip; not with --decode beam or --guidance")
+    ap.add_argument("--kv8-samples", action="store_true",
+                    help="FP8 cross-attention K/V for the batched best-of-N pass (dimx.kv8.attention_rows): the tries of a clip stay one "
+                         "generation whose multi-query cross attention reads the codes.  Every --select, with --self-kv8; not with "
+                         "--decode beam or --guidance")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -91,7 +95,8 @@ def main():
     y_true, y_pred, x, data_ids = evaluate_test_epoch(model, dataset["valid"], device, beam_size=args.beam, fd_backend="hip", metrics=acc,
                                                         select=args.select, consensus_distance=args.consensus_distance,
                                                         decode=args.decode, beam_width=args.beam_width, lookahead=args.lookahead,
-                                                        guidance=args.guidance, kv8=args.kv8, self_kv8=args.self_kv8, **sampler)
+                                                        guidance=args.guidance, kv8=args.kv8, self_kv8=args.self_kv8, kv8_samples=args.kv8_samples,
+                                                        **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     parts, parts_online, parts_null = [], [], []

@@ -391,12 +391,25 @@ int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
  *   - The decoder-layer kernel is not taken (as under the window); the chain route and the per-op route stay.  With the window on
  *     the kv8 cross attention is the windowed one.  In a guided step it runs over the conditional rows only.  The regeneration after
  *     a chain fault keeps the setting and reuses the codes.
- *   - n_samples > 1 and dimx_generate_beam return DIMX_ERR_ARG before any launch; a buffer below dimx_cross_kv8_bytes(h, B, T) for
+ *   - n_samples > 1 (without dimx_set_cross_kv8_samples) and dimx_generate_beam return DIMX_ERR_ARG before any launch; a buffer below dimx_cross_kv8_bytes(h, B, T) for
  *     the call's shape returns DIMX_ERR_WORKSPACE. */
 size_t dimx_cross_kv8_bytes(dimx_handle h, int B, int T);
 int dimx_set_cross_kv8(dimx_handle h, void* buf, size_t bytes);
 /* The handle's current setting (either pointer may be NULL). */
 int dimx_cross_kv8(dimx_handle h, void** buf, size_t* bytes);
+/* FP8 cross K/V for best-of-N generation (csrc/decode_attn_kv8.hip, decode_attn_mq_kv8_kernel; the definition is dimx/kv8.py
+ * attention_rows).  A separate opt-in on top of dimx_set_cross_kv8: handle state of variant 0 (DIMX_ERR_ARG otherwise),
+ * default off, DIMX_ERR_STATE while a streaming session is open, part of what keys the captured step graph.  With on != 0 and a cross
+ * buffer set, dimx_generate / dimx_generate_prompted take n_samples in {2, 4, 5, 8, 10}: the quantiser pass is unchanged (one row per
+ * clip; dimx_cross_kv8_bytes(h, B, T) is unchanged), and the cross attention of every layer is dimx_op_decode_attn_kv8_multi -- the S
+ * queries of a clip against that clip's codes, read once for all S -- in its matrix-core form on a bf16 handle (q from a plain bf16
+ * projection) and in its exact form on an f32 handle (q as f32 split-K slabs); windowed when the cross-attention window is on (q as
+ * slabs in both modes).  Works with dimx_set_self_kv8, the sampler filters, prompts (the prefill reads the unquantised caches),
+ * logits_out and the score dumps.  dimx_generate_beam and dimx_generate_guided stay DIMX_ERR_ARG.  With on = 0 every call launches
+ * what it launched before the setting existed, refusals included. */
+int dimx_set_cross_kv8_samples(dimx_handle h, int on);
+/* The handle's current setting. */
+int dimx_cross_kv8_samples(dimx_handle h, int* on);
 /* FP8 self-attention K/V caches for generation (csrc/decode_attn_kv8.hip, decode_attn_self_kv8_kernel; the definition is dimx/kv8.py
  * self_step).  Opt-in handle state like dimx_set_cross_kv8: variant 0 only (DIMX_ERR_ARG otherwise), either numeric mode,
  * DIMX_ERR_STATE while a streaming session is open (sessions neither read nor change the setting).  With a buffer set, every decode
@@ -875,6 +888,22 @@ int dimx_op_decode_attn_kv8(int out_dtype, const void* q, int q_ld, int q_is_f32
                             const float* kscale, const uint8_t* vcodes, const float* vscale, void* out, int o_ld, int B, int H, int Tmax,
                             const int32_t* step_dev, int n_keys, const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale, int nsplit,
                             int lookahead, int win, void* stream);
+/* The multi-query form (dimx/kv8.py attention_rows): the arguments of dimx_op_decode_attn_kv8 with B clips and
+ * rows_per_clip = S in {2, 4, 5, 8, 10} -- rows b*S .. b*S+S-1 of q / out share clip b's codes, scales and mask row -- and exact.
+ * q is f32 split-K slabs [nslab][B*S, q_ld] (q_is_f32 = 1; nslab 1..8, summed in slab order) or one bf16 row array [B*S, q_ld]
+ * (q_is_f32 = 0, nslab = 1, q_ld a multiple of 8).  One wave per (clip, head) on v_mfma_f32_16x16x32_bf16, the codes converted to
+ * bf16 exactly and read once for all S; nsplit is ignored, so a slice of clips returns the whole batch's bits.
+ *   exact = 0, the matrix-core form: two roundings beyond f32 arithmetic, q -> bf16 (RNE of the slab sum) and (p * vscale) -> bf16;
+ *              the K scale is applied to the f32 scores and the row sum is that of the unrounded p.
+ *   exact = 1, the exact form: q and p * vscale enter as three bf16 planes each, so products are exact in f32 and the result is
+ *              within the step kernels' f32 tolerance of the definition.
+ * Conventions, bounds and refusals are dimx_op_decode_attn_kv8's (a masked key scores -FLT_MAX, nothing at or past the key bound is
+ * read, the windowed form has the bits of the plain form at n_keys = the bound, repeats are bit-identical); any other rows_per_clip
+ * is DIMX_ERR_ARG.  Query rows the operand is padded with are never stored. */
+int dimx_op_decode_attn_kv8_multi(int out_dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, const uint8_t* kcodes,
+                                  const float* kscale, const uint8_t* vcodes, const float* vscale, void* out, int o_ld, int B, int H, int Tmax,
+                                  const int32_t* step_dev, int n_keys, const uint8_t* kmask, int kmask_ld, int rows_per_clip, float scale,
+                                  int nsplit, int lookahead, int win, int exact, void* stream);
 /* The self attention over FP8 self caches, as dimx_generate launches it with dimx_set_self_kv8 (dimx/kv8.py self_step): qkv is f32
  * split-K slabs [nslab][B, ld] (nslab 1..8, summed in slab order), row b holding q | k | v at columns 0, H*64, 2*H*64 (ld >= 3*H*64).
  * The k / v sums are quantised as dimx_op_kv8_quantize quantises a cache row and stored at position n of kcodes / vcodes
