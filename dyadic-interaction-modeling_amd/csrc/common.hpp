@@ -429,6 +429,17 @@ int launch_decode_attn_mq_kv8(const Kv8AttnArgs& a, hipStream_t s);
 // rows 0 .. T - 1 of every (clip, head) of one cache [B,H,Tp,64] (dtype) -> codes [B,H,Tp,64] / scales [B,H,Tp]; cache_T > 0: the
 // cache is [B,H,cache_T,64] (a generation's self caches)
 int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, hipStream_t s, int cache_T = 0);
+// rows [n0, n0 + c) of every (clip, head) of the K and V caches of `depth` layers -> their codes / scales, one launch (dimx/kv8.py
+// append; what a streaming session's push issues after it appended the rows).  Rows outside the range are neither read nor written.
+struct Kv8AppendArgs {
+    const void* cache[16];   // [2 l] layer l's K cache, [2 l + 1] its V cache: [B, H, Tc, 64] in dtype
+    uint8_t* codes[16];      // ... their code planes [B, H, Tp, 64]
+    float* scales[16];       // ... and scale planes [B, H, Tp]
+    int dtype, depth;        // DIMX_F32 / DIMX_BF16; 1 .. 8 layers
+    int B, H, Tc, Tp;
+    int n0, c;               // 0 <= n0, 1 <= c, n0 + c <= min(Tc, Tp), Tp <= 2048
+};
+int launch_kv8_append(const Kv8AppendArgs& a, hipStream_t s);
 // The self form over FP8 self-attention caches (decode_attn_kv8.hip; dimx/kv8.py self_step): one launch quantises this step's k / v
 // row, stores it at position n and attends over the rows 0 .. n, the own row taken from registers
 struct Kv8SelfArgs {

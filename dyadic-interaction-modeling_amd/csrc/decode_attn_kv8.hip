@@ -2,7 +2,8 @@
 //
 // The cross K/V cache of a generation is written once per clip and streamed by every decode step; it is the step's one large HBM
 // stream (decode_attn.hip).  kv8_quant_kernel turns a layer's cache [B, H, Tp, 64] (bf16 / f32) into OCP e4m3fn codes
-// [B, H, Tp, 64] uint8 plus one f32 scale per (clip, head, key) [B, H, Tp], once per generation; decode_attn_kv8_kernel is the
+// [B, H, Tp, 64] uint8 plus one f32 scale per (clip, head, key) [B, H, Tp], once per generation (kv8_append_kernel: the rows a
+// streaming session's push appended, K and V of every layer in one launch -- a row's codes depend on that row alone); decode_attn_kv8_kernel is the
 // one-query cross attention over those codes: decode_attn_body's shape with 16 elements per 16-byte lane load --
 //   4 lanes per key, 16 keys (1 KiB contiguous) per wave-wide load, 4 loads = 64 keys per batch, the next batch in flight while
 //   the current one is consumed, codes unpacked by the hardware convert (v_cvt_pk_f32_fp8).
@@ -95,6 +96,32 @@ __global__ __launch_bounds__(256) void kv8_quant_kernel(const T* cache, long row
     if (live) {
         *(uint4*)(codes + at * 64 + ch * 16) = w;
         if (ch == 0) scales[at] = scale;
+    }
+}
+
+// Rows [n0, n0 + c) of every (clip, head) of the K and V caches of every layer -> codes / scales, one launch (a streaming
+// session's push: stream.hip).  blockIdx.y picks the cache (2 l: layer l's K, 2 l + 1: its V), so the pointer loads are
+// scalar; blockIdx.x covers that cache's B * H * c rows, four lanes per row as above.  Rows outside the range are neither read nor
+// written; a wave with fewer live rows than lanes recomputes the last row and stores nothing (the butterfly needs every lane).
+template <typename T>
+__global__ __launch_bounds__(256) void kv8_append_kernel(const Kv8AppendArgs a) {
+    const int which = blockIdx.y;
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long rows = (long)a.B * a.H * a.c;
+    const long row = tid >> 2;
+    const int ch = (int)(tid & 3);
+    const bool live = row < rows;
+    const long r = live ? row : rows - 1;
+    const long pair = r / a.c;
+    const int j = a.n0 + (int)(r % a.c);
+    float x[16];
+    load_row16<T>((const T*)a.cache[which] + (pair * a.Tc + j) * 64 + ch * 16, x);
+    uint4 w;
+    const float scale = quant_row16(x, w);
+    if (live) {
+        const long at = pair * a.Tp + j;
+        *(uint4*)(a.codes[which] + at * 64 + ch * 16) = w;
+        if (ch == 0) a.scales[which][at] = scale;
     }
 }
 
@@ -734,6 +761,30 @@ int launch_kv8_quant(int dtype, const void* cache, int B, int H, int Tp, int T, 
         hipLaunchKernelGGL((kv8_quant_kernel<bf16>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16*)cache, rows, Tc, Tp, T, codes, scales);
     else
         hipLaunchKernelGGL((kv8_quant_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)cache, rows, Tc, Tp, T, codes, scales);
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
+int launch_kv8_append(const Kv8AppendArgs& a, hipStream_t s) {
+    DIMX_REQUIRE(a.dtype == DIMX_BF16 || a.dtype == DIMX_F32, DIMX_ERR_ARG, "kv8_append: dtype %d", a.dtype);
+    DIMX_REQUIRE(a.depth >= 1 && a.depth <= 8, DIMX_ERR_ARG, "kv8_append: depth %d outside 1 .. 8", a.depth);
+    DIMX_REQUIRE(a.B >= 1 && a.H >= 1 && a.c >= 1 && a.n0 >= 0, DIMX_ERR_ARG, "kv8_append: B=%d H=%d n0=%d c=%d (need B, H, c >= 1 and n0 >= 0)", a.B,
+                 a.H, a.n0, a.c);
+    DIMX_REQUIRE(a.Tp >= 1 && a.Tp <= kMaxKeys && a.Tc >= 1, DIMX_ERR_ARG, "kv8_append: Tp=%d outside 1 .. %d or Tc=%d < 1", a.Tp, kMaxKeys, a.Tc);
+    DIMX_REQUIRE((long)a.n0 + a.c <= a.Tc && (long)a.n0 + a.c <= a.Tp, DIMX_ERR_ARG,
+                 "kv8_append: rows %d .. %ld of caches that hold %d and code planes that hold %d per (clip, head)", a.n0, (long)a.n0 + a.c - 1, a.Tc,
+                 a.Tp);
+    for (int i = 0; i < 2 * a.depth; ++i) {
+        DIMX_REQUIRE(a.cache[i] && a.codes[i] && a.scales[i], DIMX_ERR_ARG, "kv8_append: null operand (layer %d %s)", i / 2, i % 2 ? "V" : "K");
+        DIMX_REQUIRE((uintptr_t)a.cache[i] % 16 == 0 && (uintptr_t)a.codes[i] % 16 == 0 && (uintptr_t)a.scales[i] % 4 == 0, DIMX_ERR_ARG,
+                     "kv8_append: misaligned operand (layer %d %s; cache / codes 16 bytes, scales 4)", i / 2, i % 2 ? "V" : "K");
+    }
+    const long rows = (long)a.B * a.H * a.c;
+    const long blocks = (rows * 4 + 255) / 256;
+    DIMX_REQUIRE(blocks <= 0x7fffffffL, DIMX_ERR_ARG, "kv8_append: %ld rows per cache", rows);
+    const dim3 grid((unsigned)blocks, (unsigned)(2 * a.depth)), block(256);
+    if (a.dtype == DIMX_BF16) hipLaunchKernelGGL((kv8_append_kernel<bf16>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((kv8_append_kernel<float>), grid, block, 0, s, a);
     DIMX_HIP(hipGetLastError());
     return DIMX_OK;
 }

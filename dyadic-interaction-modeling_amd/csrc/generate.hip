@@ -113,27 +113,6 @@ static int qkv0_table_build(dimx_handle h, const GenScratch& s, int M, hipStream
     return DIMX_OK;
 }
 
-// FP8 cross K/V (dimx_set_cross_kv8; include/dimx.h has the layout): per layer K codes, V codes [B, H, Tp, 64] uint8, K scales,
-// V scales [B, H, Tp] f32, each 256-byte aligned, layers in order
-struct Kv8Layer {
-    uint8_t *kcodes, *vcodes;
-    float *kscale, *vscale;
-};
-static size_t kv8_codes_bytes(dimx_handle h, int B, int T) { return align_up((size_t)B * h->decg.heads * tpad(T) * 64, 256); }
-static size_t kv8_scale_bytes(dimx_handle h, int B, int T) { return align_up((size_t)B * h->decg.heads * tpad(T) * sizeof(float), 256); }
-static size_t kv8_bytes(dimx_handle h, int B, int T) {
-    if (!h || h->variant != 0 || h->decg.dim_head != 64 || B < 1 || T < 2 || T > h->d.max_seq_len || tpad(T) > 2048) return 0;
-    return (size_t)h->decg.depth * 2 * (kv8_codes_bytes(h, B, T) + kv8_scale_bytes(h, B, T));
-}
-static Kv8Layer kv8_layer_of(dimx_handle h, void* buf, int B, int T, int l) {
-    const size_t cb = kv8_codes_bytes(h, B, T), sb = kv8_scale_bytes(h, B, T);
-    uint8_t* p = (uint8_t*)buf + (size_t)l * 2 * (cb + sb);
-    return Kv8Layer{p, p + cb, (float*)(p + 2 * cb), (float*)(p + 2 * cb + sb)};
-}
-static Kv8Layer kv8_layer(dimx_handle h, int B, int T, int l) { return kv8_layer_of(h, h->kv8_buf, B, T, l); }
-// FP8 self K/V (dimx_set_self_kv8): the same layout with the R = B * S sequences of the generation in place of the clips
-static Kv8Layer self_kv8_layer(dimx_handle h, int R, int T, int l) { return kv8_layer_of(h, h->self_kv8_buf, R, T, l); }
-
 // what a generate call was asked for; the public entry points fill it after their own argument checks
 struct GenRequest {
     GenPrompt pr;
@@ -162,6 +141,10 @@ struct GenCall {
     const GenScratch& s;
     int R;       // sequences of the batch: clips x samples
     int top_k;   // the request's k, 0 under a sampler filter of another kind
+    // the FP8 K/V buffers of the call or nullptr (gen_open): the handle's (dimx_set_cross_kv8, dimx_set_self_kv8) for an offline
+    // call, the session's own (dimx_stream_set_kv8) for a session's
+    void* kv8_buf = nullptr;
+    void* self_kv8_buf = nullptr;
 };
 
 // One clip group's view of a call: rows [row0, row0 + B) of the gc->R sequences.  `s` holds the group's slices of every per-row
@@ -216,13 +199,13 @@ static StepCtx step_ctx(dimx_handle h, const GenCall& gc, const StepRoute& r, in
         c.kv8[l] = Kv8Layer{};
         if (r.kv8) {
             const size_t row0 = (size_t)c.clip0 * heads * c.Tp;
-            const Kv8Layer all = kv8_layer(h, q.B, T, l);
+            const Kv8Layer all = kv8_layer_of(h, gc.kv8_buf, q.B, T, l);
             c.kv8[l] = Kv8Layer{all.kcodes + row0 * 64, all.vcodes + row0 * 64, all.kscale + row0, all.vscale + row0};
         }
         c.skv8[l] = Kv8Layer{};
         if (r.self_kv8) {
             const size_t at = (size_t)row0 * heads * c.Tp;
-            const Kv8Layer all = self_kv8_layer(h, gc.R, T, l);
+            const Kv8Layer all = kv8_layer_of(h, gc.self_kv8_buf, gc.R, T, l);
             c.skv8[l] = Kv8Layer{all.kcodes + at * 64, all.vcodes + at * 64, all.kscale + at, all.vscale + at};
         }
     }
@@ -659,9 +642,9 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     r.multi_tr = gen_multi_tr(h, q.S);   // consulted on the per-op branch and without the window only
     r.win = h->xwin_on != 0;
     r.lookahead = r.win ? h->xwin_lookahead : 0;
-    r.kv8 = h->kv8_buf != nullptr;   // the layer kernel streams the caches itself: not taken, exactly as under the window
+    r.kv8 = gc.kv8_buf != nullptr;   // the layer kernel streams the caches itself: not taken, exactly as under the window
     r.kv8_samples = r.kv8 && q.S > 1;   // gen_open let S > 1 through under dimx_set_cross_kv8_samples only
-    r.self_kv8 = h->self_kv8_buf != nullptr;   // no layer kernel either: it streams the self caches itself
+    r.self_kv8 = gc.self_kv8_buf != nullptr;   // no layer kernel either: it streams the self caches itself
     r.guided = q.guided;
     if (r.guided) r.chain = r.defer = r.logits_chain = r.multi_tr = false;   // the per-op step, as a session takes it (no layer kernel either: it needs chain)
     // one group: every projection launch of the generation has R rows, and so has the table's build
@@ -706,9 +689,9 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
     k.beam = q.beam ? *q.beam : BeamCall{};
     k.xwin_on = r.win ? 1 : 0; k.xwin_lookahead = r.lookahead;
     k.guided = r.guided; k.branch_out = q.branch_out;
-    k.kv8 = r.kv8 ? h->kv8_buf : nullptr;
+    k.kv8 = r.kv8 ? gc.kv8_buf : nullptr;
     k.kv8_samples = r.kv8_samples;
-    k.self_kv8 = r.self_kv8 ? h->self_kv8_buf : nullptr;
+    k.self_kv8 = r.self_kv8 ? gc.self_kv8_buf : nullptr;
     return k;
 }
 
@@ -962,6 +945,10 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     // route
     run.gc.R = R;
     run.gc.top_k = top_k;
+    // the FP8 buffers travel with the call: an offline call reads the handle's two settings and nothing of a session's, a session its
+    // own pair (stream.hip checked their sizes against (B, Tmax)) and nothing of the handle's
+    run.gc.kv8_buf = sess ? sess->kv8_buf : h->kv8_buf;
+    run.gc.self_kv8_buf = sess ? sess->self_kv8_buf : h->self_kv8_buf;
     const GenCall& gc = run.gc;
     StepRoute& route = run.route;
     DIMX_TRY(resolve_route(h, gc, G, lo[1] - lo[0], route));
@@ -972,9 +959,7 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
         route.sample_head = false;
         route.win = true;
         route.lookahead = sess->lookahead;
-        route.kv8 = false;
-        route.kv8_samples = false;
-        route.self_kv8 = false;
+        route.kv8_samples = false;   // kv8 / self_kv8 follow the session's buffers (resolve_route read them from the call)
         run.graphs = false;
     }
     // parameters
@@ -995,18 +980,19 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     // append from position P0 - 1 on (the regeneration after a chain fault reuses these rows)
     if (route.self_kv8 && pr.step0 > 0 && !keep_prefill && !prefill_only) {
         for (int l = 0; l < h->decg.depth; ++l) {
-            const Kv8Layer kl = self_kv8_layer(h, R, T, l);
+            const Kv8Layer kl = kv8_layer_of(h, gc.self_kv8_buf, R, T, l);
             DIMX_TRY(launch_kv8_quant(h->at, s.sk[l], R, h->decg.heads, tpad(T), pr.step0, kl.kcodes, kl.kscale, st, T));
             DIMX_TRY(launch_kv8_quant(h->at, s.sv[l], R, h->decg.heads, tpad(T), pr.step0, kl.vcodes, kl.vscale, st, T));
         }
     }
     if (prefill_only) return DIMX_OK;
     // FP8 cross K/V: every layer's context K / V -> codes + scales, once per generation, ahead of the first step (the prefill above
-    // read the unquantised caches; the regeneration after a chain fault reuses the codes)
-    if (route.kv8 && !keep_prefill) {
+    // read the unquantised caches; the regeneration after a chain fault reuses the codes).  A session's pushes quantise the rows
+    // they append (stream.hip push_rows): nothing here.
+    if (route.kv8 && !keep_prefill && !sess) {
         const int Tp = tpad(T), heads = h->decg.heads;
         for (int l = 0; l < h->decg.depth; ++l) {
-            const Kv8Layer kl = kv8_layer(h, B, T, l);
+            const Kv8Layer kl = kv8_layer_of(h, gc.kv8_buf, B, T, l);
             DIMX_TRY(launch_kv8_quant(h->at, cp.ck[l], B, heads, Tp, T, kl.kcodes, kl.kscale, st));
             DIMX_TRY(launch_kv8_quant(h->at, cp.cv[l], B, heads, Tp, T, kl.vcodes, kl.vscale, st));
         }

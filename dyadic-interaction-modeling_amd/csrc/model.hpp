@@ -285,6 +285,12 @@ struct dimx_ctx {
     // streaming session (stream.hip, dimx_stream_begin .. dimx_stream_end / dimx_stream_abort): one per handle; while it is
     // open the stages that rebuild the context or generate return DIMX_ERR_STATE
     void* stream_sess = nullptr;
+    // FP8 K/V for sessions (dimx_stream_set_kv8): the caller's cross and self buffers the next session begins read; nullptr = that
+    // route off.  Independent of kv8_buf / self_kv8_buf above: sessions ignore those, dimx_generate* ignores these.
+    void* stream_kv8_buf = nullptr;
+    size_t stream_kv8_bytes = 0;
+    void* stream_self_kv8_buf = nullptr;
+    size_t stream_self_kv8_bytes = 0;
     dimx::MeshHead mesh;              // handles created with dimx_dims.mesh_dim > 0
     int lstm_faults = 0;                // LSTM layers whose group kernel reported a fault and that were rerun on the safe path
     int spk_embed_rows = 0;             // rows of speaker_embed.weight as last loaded (the host applies it in inference; the

@@ -517,6 +517,19 @@ int dimx_op_kv8_quantize(int dtype, const void* cache, int B, int H, int Tp, int
     return launch_kv8_quant(dtype, cache, B, H, Tp, T, codes, scales, (hipStream_t)stream);
 }
 
+/* ... rows [n0, n0 + c) of the K and V caches of `depth` layers in one launch; caches / codes / scales: host arrays of 2 * depth
+ * device pointers, K of layer 0, V of layer 0, K of layer 1, ... */
+int dimx_op_kv8_append(int dtype, const void* const* caches, uint8_t* const* codes, float* const* scales, int depth, int B, int H, int Tc, int Tp,
+                       int n0, int c, void* stream) {
+    DIMX_REQUIRE(depth >= 1 && depth <= 8, DIMX_ERR_ARG, "op_kv8_append: depth %d outside 1 .. 8", depth);
+    DIMX_REQUIRE(caches && codes && scales, DIMX_ERR_ARG, "op_kv8_append: null pointer array");
+    Kv8AppendArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < 2 * depth; ++i) { a.cache[i] = caches[i]; a.codes[i] = codes[i]; a.scales[i] = scales[i]; }
+    a.dtype = dtype; a.depth = depth; a.B = B; a.H = H; a.Tc = Tc; a.Tp = Tp; a.n0 = n0; a.c = c;
+    return launch_kv8_append(a, (hipStream_t)stream);
+}
+
 /* ... and the step's one-query cross attention over them, plain (win = 0) or windowed */
 int dimx_op_decode_attn_kv8(int out_dtype, const void* q, int q_ld, int q_is_f32, int nslab, long slab_stride, const uint8_t* kcodes,
                             const float* kscale, const uint8_t* vcodes, const float* vscale, void* out, int o_ld, int B, int H, int Tmax,

@@ -125,7 +125,28 @@ struct GenRun;
 struct GenSessionSpec {   // what a session asks of gen_open in place of the handle's settings
     int lookahead;        // the cross-attention window is on, with this look-ahead
     int n_keys;           // ... and this key bound (the cache length while the session is open)
+    void* kv8_buf;        // dimx_stream_set_kv8: the session's FP8 cross K/V buffer (its pushes quantise the rows they append) or nullptr
+    void* self_kv8_buf;   // ... and its FP8 self K/V buffer or nullptr
 };
+
+// FP8 K/V buffers (dimx_set_cross_kv8, dimx_set_self_kv8, dimx_stream_set_kv8; include/dimx.h has the layout): per layer K codes,
+// V codes [B, H, Tp, 64] uint8, K scales, V scales [B, H, Tp] f32, each 256-byte aligned, layers in order.  B: the clips of the cross
+// buffer, the R = B * S sequences of the self buffer.
+struct Kv8Layer {
+    uint8_t *kcodes, *vcodes;
+    float *kscale, *vscale;
+};
+static inline size_t kv8_codes_bytes(const dimx_ctx* h, int B, int T) { return align_up((size_t)B * h->decg.heads * tpad(T) * 64, 256); }
+static inline size_t kv8_scale_bytes(const dimx_ctx* h, int B, int T) { return align_up((size_t)B * h->decg.heads * tpad(T) * sizeof(float), 256); }
+static inline size_t kv8_bytes(const dimx_ctx* h, int B, int T) {
+    if (!h || h->variant != 0 || h->decg.dim_head != 64 || B < 1 || T < 2 || T > h->d.max_seq_len || tpad(T) > 2048) return 0;
+    return (size_t)h->decg.depth * 2 * (kv8_codes_bytes(h, B, T) + kv8_scale_bytes(h, B, T));
+}
+static inline Kv8Layer kv8_layer_of(const dimx_ctx* h, void* buf, int B, int T, int l) {
+    const size_t cb = kv8_codes_bytes(h, B, T), sb = kv8_scale_bytes(h, B, T);
+    uint8_t* p = (uint8_t*)buf + (size_t)l * 2 * (cb + sb);
+    return Kv8Layer{p, p + cb, (float*)(p + 2 * cb), (float*)(p + 2 * cb + sb)};
+}
 // start [B, ld_prompt]: the first P codes of every clip; P > 1: positions 0 .. P - 2 are prefilled under the session's window
 GenRun* gen_run_new(const int32_t* start, const uint8_t* ctx_mask, int B, int T, float temperature, int top_k, const float* noise,
                     uint64_t seed, int32_t* tokens, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st, int ld_prompt = 1,

@@ -5,7 +5,8 @@
 //   1. runs both causal speaker encoders on the c new rows alone, every layer's self attention over that layer's K / V cache
 //      (stream_attn.hip, append attention) -- row j of a causal encoder depends on the frames <= j only, so these are the rows
 //      dimx_encode_ctx computes for the whole clip;
-//   2. appends the new context rows' cross K / V to the [B, H, Tp, 64] caches the decode step reads;
+//   2. appends the new context rows' cross K / V to the [B, H, Tp, 64] caches the decode step reads -- and, under
+//      dimx_stream_set_kv8, quantises those rows into the session's FP8 buffer in one launch (launch_kv8_append);
 //   3. runs the decode steps that are now due (dimx/stream.py steps_due): step t as soon as the frames 0 .. t + 1 + max(L, 0)
 //      exist.  The window bounds every read below the frames pushed.
 // dimx_stream_end fixes T = the frames pushed and runs the remaining steps with the key bound T.
@@ -39,6 +40,7 @@ struct StreamSession {
     float* logits = nullptr;
     void *ek[2][8], *ev[2][8];   // the per-layer K / V caches of encoder_s / encoder_joint, [B, H, Tmax, 64] in the operand type
     IncScratch inc;
+    void *kv8_buf = nullptr, *self_kv8_buf = nullptr;   // dimx_stream_set_kv8 as it stood at the begin: the session's FP8 buffers or nullptr
     hipEvent_t evt[4] = {};       // dimx_stream_set_events: recorded by every push at its start and after each of its three parts
 };
 
@@ -161,6 +163,19 @@ static int push_rows(dimx_handle h, StreamSession& S, const float* vs, const flo
         }
         DIMX_TRY(launch_gemm(g, st));
     }
+    // FP8 cross K/V (dimx_stream_set_kv8): the rows just appended -> codes + scales, K and V of every layer in one launch.  A row's
+    // codes are a function of that row alone (dimx/kv8.py append), so the buffer holds what quantising the finished caches would.
+    if (S.kv8_buf) {
+        Kv8AppendArgs a;
+        memset(&a, 0, sizeof(a));
+        for (int l = 0; l < h->decg.depth; ++l) {
+            const Kv8Layer kl = kv8_layer_of(h, S.kv8_buf, B, S.Tmax, l);
+            a.cache[2 * l] = S.cp.ck[l]; a.codes[2 * l] = kl.kcodes; a.scales[2 * l] = kl.kscale;
+            a.cache[2 * l + 1] = S.cp.cv[l]; a.codes[2 * l + 1] = kl.vcodes; a.scales[2 * l + 1] = kl.vscale;
+        }
+        a.dtype = h->at; a.depth = h->decg.depth; a.B = B; a.H = heads; a.Tc = Tp; a.Tp = Tp; a.n0 = n0; a.c = c;
+        DIMX_TRY(launch_kv8_append(a, st));
+    }
     return DIMX_OK;
 }
 
@@ -231,6 +246,17 @@ static int stream_open(dimx_handle h, const char* what, bool prompted, const int
     DIMX_REQUIRE(h->encg[0].causal && h->encg[1].causal && h->encg[0].dim_head == 64 && h->encg[1].dim_head == 64 && h->decg.dim_head == 64 &&
                      h->encg[0].dim == h->encg[1].dim && h->encg[0].heads == h->encg[1].heads && h->encg[0].depth <= 8 && h->encg[1].depth <= 8,
                  DIMX_ERR_ARG, "%s: needs causal encoders of one width with 64-wide heads", what);
+    // dimx_stream_set_kv8: the buffers against this session's shape (self: one sequence per clip)
+    if (h->stream_kv8_buf || h->stream_self_kv8_buf) {
+        const size_t need = kv8_bytes(h, B, Tmax);
+        DIMX_REQUIRE(need != 0 && h->decg.depth <= 8, DIMX_ERR_ARG, "%s: B=%d Tmax=%d is not supported with dimx_stream_set_kv8", what, B, Tmax);
+        DIMX_REQUIRE(!h->stream_kv8_buf || h->stream_kv8_bytes >= need, DIMX_ERR_WORKSPACE,
+                     "%s: the FP8 cross K/V buffer holds %zu bytes, B=%d Tmax=%d needs %zu (dimx_cross_kv8_bytes)", what, h->stream_kv8_bytes, B, Tmax,
+                     need);
+        DIMX_REQUIRE(!h->stream_self_kv8_buf || h->stream_self_kv8_bytes >= need, DIMX_ERR_WORKSPACE,
+                     "%s: the FP8 self K/V buffer holds %zu bytes, B=%d Tmax=%d needs %zu (dimx_self_kv8_bytes)", what, h->stream_self_kv8_bytes, B,
+                     Tmax, need);
+    }
     const size_t gen_bytes = gen_part_bytes(h, B, Tmax, prompted);
     StreamSession* S = new StreamSession;
     const size_t own = plan_stream(h, nullptr, 0, B, Tmax, *S, prompted);
@@ -244,6 +270,7 @@ static int stream_open(dimx_handle h, const char* what, bool prompted, const int
         hipStream_t st = (hipStream_t)stream;
         plan_stream(h, (unsigned char*)ws + gen_bytes, ws_bytes - gen_bytes, B, Tmax, *S, prompted);
         S->B = B; S->Tmax = Tmax; S->lookahead = lookahead; S->ws = ws; S->gen_bytes = gen_bytes;
+        S->kv8_buf = h->stream_kv8_buf; S->self_kv8_buf = h->stream_self_kv8_buf;
         (void)scratch_arena(h, ws, gen_bytes, B, Tmax, &S->cp);
         DIMX_HIP(hipMemsetAsync(S->mask, 1, (size_t)B * Tmax, st));   // every pushed frame is a context row
         const int ld = prompted ? Tmax : 1;
@@ -259,7 +286,7 @@ static int stream_open(dimx_handle h, const char* what, bool prompted, const int
         }
         S->frames = F;
         S->run = gen_run_new(S->start, S->mask, B, Tmax, temperature, top_k, noise, seed, S->tokens, S->logits, ws, gen_bytes, st, ld, P);
-        const GenSessionSpec spec{lookahead, Tmax};
+        const GenSessionSpec spec{lookahead, Tmax, S->kv8_buf, S->self_kv8_buf};
         DIMX_TRY(gen_open(h, *S->run, false, false, &spec));   // P > 1: with the windowed prefill of the positions 0 .. P - 2
         S->steps = P - 1;
         return DIMX_OK;
@@ -345,6 +372,39 @@ int dimx_stream_end(dimx_handle h, int32_t* tokens_out, int ld_tok, float* logit
 int dimx_stream_abort(dimx_handle h) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "null handle");
     close_session(h);
+    return DIMX_OK;
+}
+
+int dimx_stream_set_kv8(dimx_handle h, void* cross_buf, size_t cross_bytes, void* self_buf, size_t self_bytes) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "stream_set_kv8: null handle");
+    DIMX_NO_SESSION(h, "stream_set_kv8");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "stream_set_kv8: sessions are implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    DIMX_REQUIRE(((uintptr_t)cross_buf | (uintptr_t)self_buf) % 256 == 0 && h->decg.dim_head == 64, DIMX_ERR_ARG,
+                 "stream_set_kv8: the buffers must be 256-byte aligned and the decoder's heads 64 wide");
+    h->stream_kv8_buf = cross_buf;
+    h->stream_kv8_bytes = cross_buf ? cross_bytes : 0;
+    h->stream_self_kv8_buf = self_buf;
+    h->stream_self_kv8_bytes = self_buf ? self_bytes : 0;
+    return DIMX_OK;
+}
+
+int dimx_stream_kv8(dimx_handle h, void** cross_buf, size_t* cross_bytes, void** self_buf, size_t* self_bytes) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "stream_kv8: null handle");
+    if (cross_buf) *cross_buf = h->stream_kv8_buf;
+    if (cross_bytes) *cross_bytes = h->stream_kv8_bytes;
+    if (self_buf) *self_buf = h->stream_self_kv8_buf;
+    if (self_bytes) *self_bytes = h->stream_self_kv8_bytes;
+    return DIMX_OK;
+}
+
+int dimx_stream_cross_kv(dimx_handle h, int layer, void** k, void** v) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "stream_cross_kv: null handle");
+    DIMX_REQUIRE(h->stream_sess, DIMX_ERR_STATE, "stream_cross_kv: no open session");
+    DIMX_REQUIRE(layer >= 0 && layer < h->decg.depth && layer < 8, DIMX_ERR_ARG, "stream_cross_kv: layer %d of %d", layer, h->decg.depth);
+    const StreamSession& S = *(const StreamSession*)h->stream_sess;
+    if (k) *k = S.cp.ck[layer];
+    if (v) *v = S.cp.cv[layer];
     return DIMX_OK;
 }
 

@@ -481,14 +481,29 @@ class Engine:
         return self._generated(tokens, lg, mask_u8, T, n_samples, None, return_logits, return_scores)
 
     def stream(self, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0, prompt=None, v_speaker=None,
-               v_audio=None):
+               v_audio=None, kv8=False, self_kv8=False):
         """Open a streaming session (dimx_stream_begin, include/dimx.h): B clips in lockstep, at most ``Tmax`` frames,
         ``start`` [B] the listener's first codes, the sampler's arguments as ``generate`` takes them (``noise`` [Tmax-1, B, 512]).
         Returns a StreamSession with a workspace of its own; one session per engine at a time.
 
         ``prompt`` [B, P] with ``v_speaker`` [B, F, 56] and ``v_audio`` [B, F, 768] (``start`` is then ignored and may be None): the
-        session starts from its first P codes and F frames (dimx_stream_begin_prompted; ``dimx.stream.prompt_fits``)."""
-        return StreamSession(self, B, Tmax, start, lookahead, temperature, top_k, noise, seed, prompt, v_speaker, v_audio)
+        session starts from its first P codes and F frames (dimx_stream_begin_prompted; ``dimx.stream.prompt_fits``).
+
+        ``kv8`` / ``self_kv8``: FP8 cross / self K/V for the session (dimx_stream_set_kv8; dimx.kv8 append, self_step):
+        the session allocates and owns the buffers, every push quantises the cross rows it appends, and the steps read codes."""
+        return StreamSession(self, B, Tmax, start, lookahead, temperature, top_k, noise, seed, prompt, v_speaker, v_audio, kv8, self_kv8)
+
+    def stream_set_kv8(self, cross_buf=None, self_buf=None):
+        """The FP8 buffers the next session begins take (dimx_stream_set_kv8): uint8 device tensors or None (that route off)."""
+        self._chk(cross_buf, self_buf)
+        L.check(self.lib.dimx_stream_set_kv8(self.h, L.ptr(cross_buf), cross_buf.numel() if cross_buf is not None else 0, L.ptr(self_buf),
+                                             self_buf.numel() if self_buf is not None else 0), "dimx_stream_set_kv8")
+
+    def stream_kv8(self):
+        """((cross pointer, bytes) or None, (self pointer, bytes) or None): the handle's setting (dimx_stream_kv8)."""
+        cp, cn, sp, sn = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p(), ctypes.c_size_t()
+        L.check(self.lib.dimx_stream_kv8(self.h, ctypes.byref(cp), ctypes.byref(cn), ctypes.byref(sp), ctypes.byref(sn)), "dimx_stream_kv8")
+        return ((cp.value, cn.value) if cp.value else None, (sp.value, sn.value) if sp.value else None)
 
     def _generated(self, tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores):
         """generate()'s return value: tokens[, logits][, SeqScores of the sampled columns (``plen``: effective prompt lengths)]"""
@@ -650,7 +665,7 @@ class StreamSession:
     ``end`` or ``close`` the object may ``begin`` another clip in the same workspace."""
 
     def __init__(self, eng, B, Tmax, start, lookahead=0, temperature=1.0, top_k=52, noise=None, seed=0, prompt=None, v_speaker=None,
-                 v_audio=None):
+                 v_audio=None, kv8=False, self_kv8=False):
         self.eng, self.B, self.Tmax, self.lookahead = eng, int(B), int(Tmax), int(lookahead)
         self._open = False
         lib, dev = eng.lib, eng.device
@@ -661,12 +676,61 @@ class StreamSession:
         self._V = eng.dims.num_tokens
         self._tok = torch.zeros(self.B, self.Tmax - 1, dtype=torch.int32, device=dev)
         self._lg = None
+        # FP8 K/V (dimx_stream_set_kv8): the session owns its buffers, sets them before every begin and clears the setting when it closes
+        self._kv8 = self._skv8 = None
+        if kv8 or self_kv8:
+            need8 = eng.cross_kv8_bytes(self.B, self.Tmax)
+            if need8 == 0:
+                raise L.DimxError("stream(kv8=/self_kv8=): dimx_cross_kv8_bytes(%d, %d) = 0 (shape or variant not supported)" % (B, Tmax))
+            if kv8:
+                self._kv8 = torch.zeros(need8, dtype=torch.uint8, device=dev)
+            if self_kv8:
+                self._skv8 = torch.zeros(eng.self_kv8_bytes(self.B, self.Tmax), dtype=torch.uint8, device=dev)
+        self._ckv = None
         self.begin(start, temperature, top_k, noise, seed, prompt, v_speaker, v_audio)
 
     def _ws_ptr(self):
         base = self._ws.data_ptr()
         aligned = (base + 255) // 256 * 256
         return ctypes.c_void_p(aligned), self._ws.numel() - (aligned - base)
+
+    def _fp8(self):
+        return self._kv8 is not None or self._skv8 is not None
+
+    def _begun(self, call, what):
+        """one begin call between setting the session's FP8 buffers and noting where its plain cross K/V caches lie"""
+        if self._fp8():
+            self.eng.stream_set_kv8(self._kv8, self._skv8)
+        try:
+            L.check(call(), what)
+        except Exception:
+            self._clear_kv8()
+            raise
+        k, v = ctypes.c_void_p(), ctypes.c_void_p()
+        self._ckv = []
+        for l in range(self.eng.dims.dec_depth):
+            L.check(self.eng.lib.dimx_stream_cross_kv(self.eng.h, l, ctypes.byref(k), ctypes.byref(v)), "dimx_stream_cross_kv")
+            self._ckv.append((k.value - self._ws.data_ptr(), v.value - self._ws.data_ptr()))
+
+    def _clear_kv8(self):
+        if self._fp8() and getattr(self.eng, "h", None):
+            self.eng.lib.dimx_stream_set_kv8(self.eng.h, None, 0, None, 0)
+
+    def cross_kv_layers(self):
+        """Per decoder layer (K, V [B, H, Tp, 64] in the engine's operand type): views of the session's plain cross K/V caches in its
+        workspace.  Rows below the frames pushed hold the context rows' projections; they stay after ``end`` until the next begin."""
+        H, Tp = self.eng.dims.heads, (self.Tmax + 7) // 8 * 8
+        dt = torch.bfloat16 if self.eng.mode == L.MODE_PERF_BF16 else torch.float32
+        nb = self.B * H * Tp * 64 * (2 if dt == torch.bfloat16 else 4)
+        return [tuple(self._ws[o:o + nb].view(dt).view(self.B, H, Tp, 64) for o in kv) for kv in self._ckv]
+
+    def cross_kv8_layers(self):
+        """Per decoder layer (kcodes, vcodes, kscale, vscale): views of the session's FP8 cross buffer (Engine.cross_kv8_layers)."""
+        return self.eng.cross_kv8_layers(self.B, self.Tmax, self._kv8)
+
+    def self_kv8_layers(self):
+        """... and of its FP8 self buffer; positions the session did not reach hold what the buffer held before."""
+        return self.eng.cross_kv8_layers(self.B, self.Tmax, self._skv8)
 
     def begin(self, start=None, temperature=1.0, top_k=52, noise=None, seed=0, prompt=None, v_speaker=None, v_audio=None):
         """Start (another) clip: the arguments of Engine.stream; B, Tmax and the look-ahead are the session's."""
@@ -683,9 +747,9 @@ class StreamSession:
         self._noise = noise    # the session reads it at every step
         self._last = (0, 0)    # token columns the last push (or end) emitted
         ws, wsb = self._ws_ptr()
-        L.check(self.eng.lib.dimx_stream_begin(self.eng.h, L.ptr(start), self.B, self.Tmax, self.lookahead, float(temperature), int(top_k),
-                                               L.ptr(self._noise), int(seed) & 0xFFFFFFFFFFFFFFFF, ws, wsb, self.eng._s()),
-                "dimx_stream_begin")
+        self._begun(lambda: self.eng.lib.dimx_stream_begin(self.eng.h, L.ptr(start), self.B, self.Tmax, self.lookahead, float(temperature),
+                                                           int(top_k), L.ptr(self._noise), int(seed) & 0xFFFFFFFFFFFFFFFF, ws, wsb,
+                                                           self.eng._s()), "dimx_stream_begin")
         self._open = True
         self.frames = 0
         self.steps = 0
@@ -711,9 +775,10 @@ class StreamSession:
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.eng.device)
         self._noise = noise
         ws, wsb = self._ws_ptr()
-        L.check(self.eng.lib.dimx_stream_begin_prompted(self.eng.h, L.ptr(prompt), P, P, L.ptr(v_speaker), L.ptr(v_audio), F, self.B, self.Tmax,
-                                                        self.lookahead, float(temperature), int(top_k), L.ptr(self._noise),
-                                                        int(seed) & 0xFFFFFFFFFFFFFFFF, ws, wsb, self.eng._s()), "dimx_stream_begin_prompted")
+        self._begun(lambda: self.eng.lib.dimx_stream_begin_prompted(self.eng.h, L.ptr(prompt), P, P, L.ptr(v_speaker), L.ptr(v_audio), F, self.B,
+                                                                    self.Tmax, self.lookahead, float(temperature), int(top_k),
+                                                                    L.ptr(self._noise), int(seed) & 0xFFFFFFFFFFFFFFFF, ws, wsb,
+                                                                    self.eng._s()), "dimx_stream_begin_prompted")
         self._open = True
         self.frames = F
         self.steps = P - 1
@@ -764,6 +829,7 @@ class StreamSession:
         L.check(self.eng.lib.dimx_stream_end(self.eng.h, L.ptr(self._tok), self.Tmax - 1, L.ptr(lg), ctypes.byref(n_new), self.eng._s()),
                 "dimx_stream_end")
         self._open = False
+        self._clear_kv8()
         return self._took(n_new.value, return_logits)
 
     @property
@@ -804,6 +870,7 @@ class StreamSession:
     def close(self):
         if self._open and getattr(self.eng, "h", None):
             self.eng.lib.dimx_stream_abort(self.eng.h)
+            self._clear_kv8()
         self._open = False
 
     def __enter__(self):
@@ -1380,6 +1447,22 @@ def op_kv8_quantize(cache, T=None, codes=None, scales=None):
     L.check(lib.dimx_op_kv8_quantize(L.BF16 if cache.dtype == torch.bfloat16 else L.F32, L.ptr(cache), B, H, Tp, Tp if T is None else int(T),
                                      L.ptr(codes), L.ptr(scales), L.stream_ptr(cache.device)), "dimx_op_kv8_quantize")
     return codes, scales
+
+
+def op_kv8_append(caches, codes, scales, n0, c):
+    """The incremental quantiser (dimx_op_kv8_append; dimx.kv8.append), one launch: ``caches`` a list of 2 * depth tensors
+    [B, H, Tc, 64] f32 or bf16 -- K of layer 0, V of layer 0, K of layer 1, ... -- whose rows [n0, n0 + c) of every (clip, head) go,
+    quantised, into the same rows of ``codes`` (2 * depth tensors [B, H, Tp, 64] uint8) and ``scales`` ([B, H, Tp] f32), in place."""
+    lib = L.load()
+    n = len(caches)
+    assert n % 2 == 0 and len(codes) == n and len(scales) == n
+    B, H, Tc, _ = caches[0].shape
+    Tp = codes[0].shape[2]
+    for a, cd, sc in zip(caches, codes, scales):
+        assert tuple(a.shape) == (B, H, Tc, 64) and a.dtype == caches[0].dtype and tuple(cd.shape) == (B, H, Tp, 64) and tuple(sc.shape) == (B, H, Tp)
+    arr = lambda ts: (ctypes.c_void_p * n)(*[L.ptr(t).value for t in ts])
+    L.check(lib.dimx_op_kv8_append(L.BF16 if caches[0].dtype == torch.bfloat16 else L.F32, arr(caches), arr(codes), arr(scales), n // 2, B, H,
+                                   Tc, Tp, int(n0), int(c), L.stream_ptr(caches[0].device)), "dimx_op_kv8_append")
 
 
 def op_decode_attn_kv8(q, kcodes, kscale, vcodes, vscale, scale, n_keys, kmask=None, kmask_ld=None, nsplit=0, out_bf16=False, step=None,

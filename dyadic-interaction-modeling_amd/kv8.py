@@ -7,9 +7,9 @@ or within the step kernels' tolerance (attention); tests/test_kv8_host.py pins t
 cast.  ``self_step`` is the same for the self-attention caches (dimx_set_self_kv8): the caches that grow by one row per decode step,
 whose new row is quantised by the step itself.  ``attention_rows`` is ``attention`` for best-of-N generation (dimx_set_cross_kv8_samples):
 several query rows per clip over that clip's codes; ``round_bf16`` and ``pv_abs`` state what its matrix-core form rounds and how far
-that can move an output element.
+that can move an output element.  ``append`` is ``quantize`` for the rows a streaming session's push adds (dimx_stream_set_kv8).
 
-    amax  = max |x| over the row (float32)
+    amax = max |x| over the row (float32)
     scale = float32(amax) / float32(448)              one IEEE float32 division; amax < 2**-60: a zero row, scale 0, codes 0
     y     = clamp(float32(x) / scale, -448, 448)      IEEE float32 division
     code  = e4m3fn(y), round to nearest even, subnormals included (spacing 2**-9 below 2**-6)
@@ -74,6 +74,27 @@ def quantize(rows):
     codes = encode(y)
     codes = np.where(zero[..., None], np.uint8(0), codes).astype(np.uint8)
     return codes, scale
+
+
+def append(kcodes, kscale, rows, n0):
+    """The incremental quantiser (a streaming session under dimx_stream_set_kv8; kv8_append_kernel): ``quantize(rows)`` placed at
+    positions [n0, n0 + c) of the second-to-last axis of the codes and the last axis of the scales.
+
+    kcodes [..., Tp, 64] uint8, kscale [..., Tp] float32, rows [..., c, 64].  Returns the two arrays (copies; the arguments are
+    left as they are) with every other position unchanged.
+
+    Row locality: ``quantize`` gives every row its own scale, so the codes and the scale of cache row j are a function of row j
+    alone.  Quantising the c rows a push appends therefore writes the bits that quantising the finished cache would write at those
+    positions, whatever the chunking; and because the decode step under the window reads rows below its bound only, and those rows
+    never change after they are written, a session's buffer equals the offline buffer on equal rows."""
+    rows = np.asarray(rows)
+    c = rows.shape[-2]
+    kcodes, kscale = np.array(kcodes, dtype=np.uint8), np.array(kscale, dtype=np.float32)
+    assert n0 >= 0 and n0 + c <= kcodes.shape[-2] == kscale.shape[-1], "append: rows [n0, n0 + c) inside the planes"
+    codes, scale = quantize(rows)
+    kcodes[..., n0:n0 + c, :] = codes
+    kscale[..., n0:n0 + c] = scale
+    return kcodes, kscale
 
 
 def dequantize(codes, scale):

@@ -91,6 +91,11 @@ SIGNATURES = {
     "dimx_stream_abort": (c_int, [c_void_p]),
     "dimx_stream_state": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "dimx_stream_set_events": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dimx_stream_set_kv8": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "dimx_stream_kv8": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), POINTER(c_size_t)]),
+    "dimx_stream_cross_kv": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p)]),
+    "dimx_op_kv8_append": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_void_p]),
     "dimx_encode_ctx": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
     "dimx_legacy_speaker_features": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,

@@ -273,20 +273,22 @@ class SLMFT(_EngineOwner):
 
     @torch.no_grad()
     def stream(self, B, Tmax, start, lookahead=0, greedy=False, noise=None, seed=None, temperature=1.0, top_k=52, prompt=None,
-               v_speaker=None, v_audio=None):
+               v_speaker=None, v_audio=None, kv8=False, self_kv8=False):
         """A streaming session (dimx.engine.StreamSession; dimx.stream is the schedule): push the speaker's motion and audio
         frames in pieces, receive the listener tokens as they fall due.  ``start`` [B]: the listener's first codes, the caller's --
         a live system has no ground-truth first code.  The sampler arguments are ``forward_decoder``'s.  Fed a whole clip, the
         session emits the tokens of ``forward(mode='val', lookahead=lookahead)`` with ``start`` = that clip's first code.
         ``prompt`` [B, P] codes with ``v_speaker`` / ``v_audio`` [B, F, .]: the session starts from its first P codes and F frames
         (``Engine.stream``; ``start`` is ignored) -- how a conversation that outlasts a session carries on in the next one.  Nothing
-        was trained on restarted clips: what such a session emits is a definition, not a claim about quality."""
+        was trained on restarted clips: what such a session emits is a definition, not a claim about quality.
+        ``kv8`` / ``self_kv8``: FP8 cross / self K/V for the session (``Engine.stream``): the steps read codes, and what the
+        session emits is ``forward(mode='val', lookahead=lookahead, kv8=True, self_kv8=True)`` up to the rounding of the two encoders."""
         eng = self.engine(start.device)
         if greedy:
             temperature, seed_v = 0.0, 0
         else:
             seed_v = 0 if noise is not None else self._user_seed(seed)
-        return eng.stream(B, Tmax, start, lookahead, temperature, top_k, noise, seed_v, prompt, v_speaker, v_audio)
+        return eng.stream(B, Tmax, start, lookahead, temperature, top_k, noise, seed_v, prompt, v_speaker, v_audio, kv8, self_kv8)
 
     def draw_kv_mask(self, B, T, device, generator=None):
         """AutoregressiveWrapper(mask_prob=0.15) key mask (reference ctor :419): keep-mask [B,T-1]."""

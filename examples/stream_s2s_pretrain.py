@@ -42,7 +42,7 @@ def segments(model, args, v_s, v_a, z_l):
         torch.cuda.synchronize()
         return out, e0.elapsed_time(e1)
 
-    s, t_begin = timed(lambda: model.stream(B, N, z_l[:, 0], lookahead=Lh, greedy=True))
+    s, t_begin = timed(lambda: model.stream(B, N, z_l[:, 0], lookahead=Lh, greedy=True, kv8=args.kv8, self_kv8=args.self_kv8))
     print("session 0: begin %.3f ms" % t_begin)
     codes = z_l[:, :1].to(torch.int32)      # all listener codes so far: position 0 is given, the rest are the sessions' tokens
     fed, k, t_push, t_begins = 0, 0, 0.0, []
@@ -78,6 +78,8 @@ def main():
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--segment", type=int, default=0, help="frames per session (0: one session for the whole clip)")
     ap.add_argument("--carry", type=int, default=0, help="with --segment: frames (and their codes) carried into the next session")
+    ap.add_argument("--kv8", action="store_true", help="FP8 cross K/V in the session (dimx_stream_set_kv8; DESIGN 31)")
+    ap.add_argument("--self-kv8", action="store_true", help="FP8 self K/V in the session")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     dev = torch.device("cuda:0")
@@ -98,7 +100,7 @@ def main():
     total = 0.0
     if args.segment:
         return segments(model, args, v_s, v_a, z_l)
-    with model.stream(B, T, z_l[:, 0], lookahead=Lh, greedy=True) as s:
+    with model.stream(B, T, z_l[:, 0], lookahead=Lh, greedy=True, kv8=args.kv8, self_kv8=args.self_kv8) as s:
         for c in stream.chunks(T, args.chunk):
             n = s.frames
             e0.record()
@@ -112,6 +114,13 @@ def main():
         tail = s.end()
         print("end: %d more tokens, %d in all; pushes took %.1f ms = %.3f ms per frame" % (tail.shape[1], s.steps, total, total / T))
         tokens = s.tokens.long()
+    if args.kv8 or args.self_kv8:
+        # the incremental and the batch encoder agree to about 1e-6, not to the bit, so a code may land on the other side of a rounding
+        # boundary: the comparison with the whole-clip FP8 call is a count, not an equality
+        _, _, _, ref = model(v_s, v_l, v_a, mask, mode="val", greedy=True, lookahead=Lh, return_tokens=True, kv8=args.kv8, self_kv8=args.self_kv8)
+        print("session tokens that differ from forward(mode='val', lookahead=%d, kv8=%s, self_kv8=%s) on the whole clip: %d of %d"
+              % (Lh, args.kv8, args.self_kv8, int((tokens != ref).sum()), tokens.numel()))
+        return
     _, _, _, ref = model(v_s, v_l, v_a, mask, mode="val", greedy=True, lookahead=Lh, return_tokens=True)
     same = bool(torch.equal(tokens, ref))
     print("session tokens equal forward(mode='val', lookahead=%d) on the whole clip: %s" % (Lh, same))

@@ -376,7 +376,7 @@ int dimx_set_cross_lookahead(dimx_handle h, int on, int lookahead);
 int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
 /* FP8 cross-attention K/V for generation (csrc/decode_attn_kv8.hip; the definition is dimx/kv8.py).  Opt-in handle state, like the
  * cross-attention window; variant 0 only (DIMX_ERR_ARG otherwise), either numeric mode; DIMX_ERR_STATE while a streaming session is
- * open (sessions neither read nor change the setting).  With a buffer set, dimx_generate / dimx_generate_prompted /
+ * open (sessions neither read nor change the setting: dimx_stream_set_kv8 is theirs).  With a buffer set, dimx_generate / dimx_generate_prompted /
  * dimx_generate_guided quantise every layer's context K / V once, ahead of the first decode step, into OCP e4m3fn codes with one f32
  * scale per (clip, head, key), and every decode step's cross attention streams the codes instead of the caches: half the bytes of
  * the bf16 caches, a quarter of the f32 ones.
@@ -412,7 +412,7 @@ int dimx_set_cross_kv8_samples(dimx_handle h, int on);
 int dimx_cross_kv8_samples(dimx_handle h, int* on);
 /* FP8 self-attention K/V caches for generation (csrc/decode_attn_kv8.hip, decode_attn_self_kv8_kernel; the definition is dimx/kv8.py
  * self_step).  Opt-in handle state like dimx_set_cross_kv8: variant 0 only (DIMX_ERR_ARG otherwise), either numeric mode,
- * DIMX_ERR_STATE while a streaming session is open (sessions neither read nor change the setting).  With a buffer set, every decode
+ * DIMX_ERR_STATE while a streaming session is open (sessions neither read nor change the setting: dimx_stream_set_kv8 is theirs).  With a buffer set, every decode
  * step of dimx_generate / dimx_generate_prompted quantises its k / v row -- the f32 sum of the projection's split-K slabs, never rounded
  * to the cache type -- into OCP e4m3fn codes with one f32 scale per (row, head, position), stores it at the step's position and
  * attends over the codes of the positions so far, its own included: one launch per layer and step.  The output of step t is a
@@ -491,6 +491,31 @@ int dimx_stream_state(dimx_handle h, int* frames, int* steps, int* open);
  * copy of their tokens.  A push of more than 16 frames interleaves the first two parts per launch group; the second event is then
  * the last group's.  The events must outlive the session or be replaced by NULL.  DIMX_ERR_STATE without an open session. */
 int dimx_stream_set_events(dimx_handle h, void* ev_start, void* ev_encoded, void* ev_appended, void* ev_stepped);
+/* FP8 K/V for streaming sessions (the definition is dimx/kv8.py, append and self_step).  Opt-in handle state that session
+ * begins alone read: the next dimx_stream_begin / dimx_stream_begin_prompted takes cross_buf as the session's FP8 cross K/V buffer
+ * and self_buf as its FP8 self K/V buffer; either may be NULL (that route off), both NULL is a plain session, which launches what
+ * it launched before the setting existed.  Independent of dimx_set_cross_kv8 / dimx_set_self_kv8: sessions keep ignoring those two,
+ * dimx_generate* ignores this one.  Variant 0 only and 256-byte aligned buffers (DIMX_ERR_ARG otherwise); DIMX_ERR_STATE while a
+ * session is open.
+ *   - The buffers are the caller's, of dimx_cross_kv8_bytes(h, B, Tmax) and dimx_self_kv8_bytes(h, B, Tmax) bytes, in
+ *     dimx_set_cross_kv8's layout with Tp = (Tmax + 7) / 8 * 8.  A begin checks them against its (B, Tmax) before it launches
+ *     anything: a shape the size query answers with 0 is DIMX_ERR_ARG, too small a buffer DIMX_ERR_WORKSPACE; no session opens.
+ *     dimx_stream_workspace_bytes returns what it returned before (the unquantised caches stay: the windowed prefill reads them).
+ *   - Cross: every push (and the F given frames of dimx_stream_begin_prompted) quantises the cross K / V rows it appended, K and V of
+ *     all layers in one dimx_op_kv8_append launch ahead of the `ev_appended` event, and every decode step's cross attention is the
+ *     windowed dimx_op_decode_attn_kv8.  A row's codes and scale are a function of that row alone, so the buffer's rows below the
+ *     frames pushed are what dimx_op_kv8_quantize gives on the session's finished caches, whatever the chunking; rows at or past the
+ *     frames pushed are neither read nor written.
+ *   - Self: every decode step is dimx_op_decode_attn_self_kv8, as under dimx_set_self_kv8 (the first layer keeps its table form);
+ *     the rows 0 .. P - 2 a prompted begin's prefill stored are quantised ahead of the first step.
+ *   - dimx_stream_end / dimx_stream_abort leave the buffers and the setting as they are.
+ * dimx_stream_kv8 reads the setting back (any pointer may be NULL). */
+int dimx_stream_set_kv8(dimx_handle h, void* cross_buf, size_t cross_bytes, void* self_buf, size_t self_bytes);
+int dimx_stream_kv8(dimx_handle h, void** cross_buf, size_t* cross_bytes, void** self_buf, size_t* self_bytes);
+/* The open session's unquantised cross K / V caches of decoder layer `layer`: device pointers into its workspace, [B, H, Tp, 64] in
+ * the operand type, rows below the frames pushed valid (tests compare the FP8 buffer with them).  Either pointer may be NULL;
+ * DIMX_ERR_STATE without an open session. */
+int dimx_stream_cross_kv(dimx_handle h, int layer, void** k, void** v);
 /* Decoders without positional embedding (variant 0): the first layer's q/k/v depend on the input token alone, so dimx_generate
  * reads them from a table over the token ids instead of projecting them at every step.  The table is built with the decode
  * step's own kernels (bit-identical rows) on first use and whenever the rows per call, the numeric mode or the decoder weights
@@ -874,6 +899,15 @@ int dimx_op_decode_attn_win(int dtype, const void* q, int q_ld, int q_is_f32, in
  * code = e4m3fn(clamp(x / scale, +-448)), round to nearest even, both divisions IEEE f32.  Rows at or past T are neither read nor
  * written.  DIMX_ERR_ARG (nothing launched) for a null or misaligned operand (cache / codes 16 bytes, scales 4) or T outside 1 .. Tp. */
 int dimx_op_kv8_quantize(int dtype, const void* cache, int B, int H, int Tp, int T, uint8_t* codes, float* scales, void* stream);
+/* ... the incremental form, as a streaming session's push launches it under dimx_stream_set_kv8 (dimx/kv8.py append): rows
+ * [n0, n0 + c) of every (clip, head) of the K and V caches of `depth` layers in one launch, with the quantiser's arithmetic (the
+ * bits dimx_op_kv8_quantize gives those rows).  caches, codes, scales: HOST arrays of 2 * depth device pointers -- K of layer 0,
+ * V of layer 0, K of layer 1, ... -- to caches [B, H, Tc, 64] of dtype, code planes [B, H, Tp, 64] uint8 and scale planes
+ * [B, H, Tp] f32.  Rows outside the range are neither read nor written.  DIMX_ERR_ARG (nothing launched) for another dtype, depth
+ * outside 1 .. 8, c < 1, n0 < 0, n0 + c beyond Tc or Tp, Tp > 2048, a null pointer, caches or codes not 16-byte aligned, scales not
+ * 4-byte aligned. */
+int dimx_op_kv8_append(int dtype, const void* const* caches, uint8_t* const* codes, float* const* scales, int depth, int B, int H, int Tc, int Tp,
+                       int n0, int c, void* stream);
 /* ... and the one-query cross attention over such codes, as dimx_generate launches it with dimx_set_cross_kv8: the arguments of
  * dimx_op_decode_attn_win with kcodes / kscale / vcodes / vscale ([B, H, Tmax, 64] uint8, [B, H, Tmax] f32) in place of the caches,
  * out_dtype (DIMX_F32 / DIMX_BF16: the type of out [B, o_ld], the handle's operand type) in place of dtype, and win: 0 = the keys

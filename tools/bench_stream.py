@@ -19,6 +19,11 @@ One MI355X.  Three measurements, in the order they run:
     ``encode_ctx + generate(lookahead=0)`` on the 300-frame clip at the same B -- of the parent commit when --parent-tree is given
     (a fresh process in that tree), else of this tree -- device-event time, median of 5 calls after 2 warm-up calls.  The session
     loses in total; the ratio is what the per-frame latency costs.
+
+``--kv8 --self-kv8`` (profiles/stream_kv8.txt) measures the FP8 routes of a session (dimx_stream_set_kv8) instead of 2 and
+3: (1) as above; per-push medians as in (2) for bf16 and f32 with FP8 off, FP8 cross K/V and FP8 cross + self K/V -- one warm-up session
+per variant, then the variants' timed sessions alternating, two rounds, all in this process and build; and one long session at
+B = 256, Tmax = 2048, c = 8 in bf16 with FP8 off and with both on, the push time near the start, the middle and the end.
 """
 import argparse
 import json
@@ -155,15 +160,148 @@ def sessions(lines, batches):
     return totals
 
 
+def _timed_session(torch, s, start, v_s, v_a, frames, c, ev, warm):
+    """one session of `frames` frames in pushes of c; -> per push [encoder, append, steps, push] ms (None for a warm-up session)"""
+    parts = []
+    s.begin(start, 0.0)
+    if not warm:
+        s.set_events(ev)
+    for n in range(0, frames, c):
+        s.push(v_s[:, n:n + c], v_a[:, n:n + c])
+        torch.cuda.synchronize()
+        if not warm:
+            parts.append([ev[i].elapsed_time(ev[i + 1]) for i in range(3)] + [ev[0].elapsed_time(ev[3])])
+    s.end()
+    torch.cuda.synchronize()
+    return None if warm else parts
+
+
+def fp8_sessions(lines, batches, variants, long_session):
+    """Measurements of the FP8 routes (dimx_stream_set_kv8): per-push medians of the variants in one process and one build, the
+    variants' timed sessions alternating; then one long session at B = 256, Tmax = 2048, c = 8 in bf16."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import dimx  # noqa: F401
+    from dimx import engine, lib as L, prng, weights
+
+    torch.set_grad_enabled(False)
+    sd = weights.synth_state_dict(weights.slmft_spec(), 20260928)
+    names = [n for n, _ in variants]
+    ROUNDS = 2
+    lines.append("2. per-push latency with FP8 K/V: a %d-frame session per variant after one warm-up session each, lookahead 0, greedy, ms;" % T)
+    lines.append("   the variants' timed sessions alternate (%s), %d rounds; median over the pushes of a variant's %d sessions"
+                 % (" -> ".join(names), ROUNDS, ROUNDS))
+    lines.append("   (whole push: min .. max).  append = the cross K/V projection of the new rows plus, with FP8 cross K/V, their quantisation.")
+    lines.append("   %-5s %4s %2s  %-6s  %9s %9s %9s   %9s %20s   %9s" % ("mode", "B", "c", "fp8", "encoder", "append", "steps", "push", "", "vs off"))
+    for mode in ("bf16", "f32"):
+        e = engine.Engine("cuda:0", L.MODE_PARITY_F32 if mode == "f32" else L.MODE_PERF_BF16)
+        e.load_state_dict(sd)
+        for B in batches:
+            v_s = torch.from_numpy(prng.normal(3, "bs.vs", (B, T, 56))).cuda()
+            v_a = torch.from_numpy(prng.normal(3, "bs.va", (B, T, 768))).cuda()
+            start = torch.from_numpy(prng.integers(3, "bs.z", (B,), 0, 512)).to(torch.int32).cuda()
+            for c in (1, 8):
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                for x in ev:
+                    x.record()
+                sess = {}
+                for name, (kv8, skv8) in variants:
+                    sess[name] = e.stream(B, T, start, lookahead=0, temperature=0.0, kv8=kv8, self_kv8=skv8)
+                    sess[name].close()
+                    _timed_session(torch, sess[name], start, v_s, v_a, T, c, ev, True)
+                parts = {n: [] for n in names}
+                for _ in range(ROUNDS):
+                    for name in names:
+                        parts[name] += _timed_session(torch, sess[name], start, v_s, v_a, T, c, ev, False)
+                base = None
+                for name in names:
+                    p = parts[name]
+                    med = [statistics.median(x[i] for x in p) for i in range(4)]
+                    whole = [x[3] for x in p]
+                    base = med[3] if base is None else base
+                    lines.append("   %-5s %4d %2d  %-6s  %9.3f %9.3f %9.3f   %9.3f (%7.3f .. %7.3f)   %+8.1f %%"
+                                 % (mode, B, c, name, med[0], med[1], med[2], med[3], min(whole), max(whole), 100 * (med[3] - base) / base))
+                    print(lines[-1], flush=True)
+                del sess
+        e.close()
+    if not long_session:
+        return
+    B, Tmax, c = 256, 2048, 8
+    lines.append("")
+    lines.append("3. one long session: bf16, B = %d, Tmax = %d frames pushed %d at a time, lookahead 0, greedy, after one warm-up session of 256 frames;"
+                 % (B, Tmax, c))
+    lines.append("   whole-push ms, median over the pushes whose first frame lies in the range given (every push runs %d steps)" % c)
+    e = engine.Engine("cuda:0", L.MODE_PERF_BF16)
+    e.load_state_dict(sd)
+    CH = 256
+    v_s = torch.from_numpy(prng.normal(3, "bs.vs", (B, CH, 56))).cuda()       # the same 256 frames again and again: the cost does not depend on them
+    v_a = torch.from_numpy(prng.normal(3, "bs.va", (B, CH, 768))).cuda()
+    start = torch.from_numpy(prng.integers(3, "bs.z", (B,), 0, 512)).to(torch.int32).cuda()
+    ranges = [(8, 136), (960, 1088), (1912, 2040)]
+    first = None
+    for name, (kv8, skv8) in (variants[0], variants[-1]):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        for x in ev:
+            x.record()
+        s = e.stream(B, Tmax, start, lookahead=0, temperature=0.0, kv8=kv8, self_kv8=skv8)
+        s.close()
+        _timed_session(torch, s, start, v_s, v_a, CH, c, ev, True)
+        s.begin(start, 0.0)
+        s.set_events(ev)
+        rows = []
+        for n in range(0, Tmax, c):
+            o = n % CH
+            s.push(v_s[:, o:o + c], v_a[:, o:o + c])
+            torch.cuda.synchronize()
+            rows.append((n, [ev[i].elapsed_time(ev[i + 1]) for i in range(3)] + [ev[0].elapsed_time(ev[3])]))
+        s.end()
+        torch.cuda.synchronize()
+        meds = []
+        for lo, hi in ranges:
+            sel = [p for n, p in rows if lo <= n < hi]
+            meds.append([statistics.median(x[i] for x in sel) for i in range(4)])
+        first = meds if first is None else first
+        lines.append("   fp8 %-6s %s   session %9.1f ms" % (name, "   ".join("frames %4d..%4d: push %7.3f (append %6.3f, steps %7.3f)" % (lo, hi, m[3], m[1], m[2])
+                                                                      for (lo, hi), m in zip(ranges, meds)), sum(p[3] for _, p in rows)))
+        if first is not meds:
+            lines.append("   %s against %s: %s" % (name, variants[0][0], ", ".join("frames %d..%d %+.1f %%" % (lo, hi, 100 * (m[3] - f[3]) / f[3])
+                                                                                 for (lo, hi), m, f in zip(ranges, meds, first))))
+        print("\n".join(lines[-2:]), flush=True)
+        del s
+    e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its library built")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_session.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/stream_session.txt, profiles/stream_kv8.txt with --kv8 / --self-kv8")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--batches", default="1,16,256")
     ap.add_argument("--skip-default-path", action="store_true", help="measurements 2 and 3 alone")
+    ap.add_argument("--kv8", action="store_true", help="the FP8 measurements (dimx_stream_set_kv8): FP8 off against FP8 cross K/V ...")
+    ap.add_argument("--self-kv8", action="store_true", help="... and against FP8 cross and self K/V (alone: FP8 off against FP8 self K/V)")
+    ap.add_argument("--no-long-session", action="store_true", help="with --kv8 / --self-kv8: without the B = 256, Tmax = 2048 session")
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
+    if args.kv8 or args.self_kv8:
+        out = args.out or os.path.join(ROOT, "profiles", "stream_kv8.txt")
+        variants = [("off", (False, False))]
+        if args.kv8:
+            variants.append(("cross", (True, False)))
+        if args.self_kv8:
+            variants.append(("both", (True, True)) if args.kv8 else ("self", (False, True)))
+        lines = ["Streaming sessions with FP8 K/V (dimx_stream_set_kv8): measurements of tools/bench_stream.py --kv8 --self-kv8", "=" * 110, ""]
+        if not args.skip_default_path:
+            default_path(lines, args.parent_tree, args.pairs)
+            lines.append("")
+        fp8_sessions(lines, batches, variants, not args.no_long_session)
+        text = "\n".join(lines) + "\n"
+        print(text)
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write(text)
+        return
+    args.out = args.out or os.path.join(ROOT, "profiles", "stream_session.txt")
     lines = ["Streaming sessions (dimx_stream_*): measurements of tools/bench_stream.py", "=" * 84, ""]
     # the fresh processes first: they then never share the GPU with this process's handles
     if not args.skip_default_path:
