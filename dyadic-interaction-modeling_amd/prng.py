@@ -78,6 +78,42 @@ def integers(seed: int, name: str, shape, lo: int, hi: int) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Exp(1) noise of the sampler's on-device generator (csrc/sample_pick.hpp, sample_survivor; include/dimx.h dimx_set_shard)
+# ---------------------------------------------------------------------------------------------------------------------
+SAMPLER_VOCAB = 512
+SAMPLER_NOISE_FLOOR = 2.0 ** -30
+
+
+def sampler_counters(step: int, rows: int, rows_total=None, row_offset: int = 0) -> np.ndarray:
+    """uint64 [rows, 512]: ctr = ((step * rows_total + row_offset + row) * 512 + code) mod 2^64."""
+    rows = int(rows)
+    total = rows if rows_total is None else int(rows_total)
+    first = (int(step) * total + int(row_offset)) & _MASK           # python integers: the product wraps like the device's
+    with np.errstate(over="ignore"):
+        row = np.uint64(first) + np.arange(rows, dtype=np.uint64)[:, None]
+        return row * np.uint64(SAMPLER_VOCAB) + np.arange(SAMPLER_VOCAB, dtype=np.uint64)[None, :]
+
+
+def sampler_uniform(seed: int, step: int, rows: int, rows_total=None, row_offset: int = 0) -> np.ndarray:
+    """float64 [rows, 512], exact: u = (mix(seed + (ctr + 1) * GOLD) >> 40) / 2^24, mix = splitmix64's finaliser."""
+    with np.errstate(over="ignore"):
+        ctr = sampler_counters(step, rows, rows_total, row_offset)
+        r = _mix(np.uint64(int(seed) & _MASK) + (ctr + np.uint64(1)) * _GOLD)
+    return (r >> np.uint64(40)).astype(np.float64) * (1.0 / (1 << 24))
+
+
+def sampler_noise(seed: int, step: int, rows: int, rows_total=None, row_offset: int = 0) -> np.ndarray:
+    """What a seeded sampler call (no noise tensor, seed != 0) divides the probabilities by: float64 [rows, 512],
+        q = max(-log1p(-u), 2^-30),   u = sampler_uniform(...),
+    for the rows [row_offset, row_offset + rows) of a step of ``rows_total`` rows (None: ``rows``).  Counter-based: no state, the
+    rows of a shard or a clip group are the rows of the whole batch.  A generation of S samples per clip numbers its rows
+    (shard_row_offset + b) * S + s out of shard_rows_total * S; ``step`` is the decode step (token column), up to 2^63.
+    The kernel evaluates log1pf in float32; this definition does not restate that rounding (tests leave out the rows whose two best
+    scores it could reorder, dimx.sampling.undecidable)."""
+    return np.maximum(-np.log1p(-sampler_uniform(seed, step, rows, rows_total, row_offset)), SAMPLER_NOISE_FLOOR)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Dropout keep-mask of the VQ-VAE training step (csrc/train_vq.hip mirrors it bit for bit)
 # ---------------------------------------------------------------------------------------------------------------------
 DROPOUT_SITE_ENCODER = 0

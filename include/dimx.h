@@ -152,7 +152,23 @@ int dimx_encode_speaker(dimx_handle h, const float* v_speaker, const uint8_t* ma
 /* Multi-GPU sharding of one evaluation batch: this handle generates clips
  * [row_offset, row_offset + B) of a batch of rows_total clips.  Only the sampler's counter-based generator
  * depends on it (its counter is indexed by the GLOBAL sequence row, so the shards of a batch draw exactly what a
- * single process would draw for the same seed).  rows_total = 0 restores the default (the call's own B). */
+ * single process would draw for the same seed).  rows_total = 0 restores the default (the call's own B).
+ *
+ * The generator (csrc/sample_pick.hpp; the host definition the tests hold every route to is dimx.prng.sampler_noise).  A seeded
+ * sampler call (exp_noise == NULL, seed != 0) at decode step `step` (the token column) divides the probability of code i of
+ * global row g by
+ *     ctr = (step * rows + g) * 512 + i                                     uint64, wraps
+ *     z   = seed + (ctr + 1) * 0x9E3779B97F4A7C15                           uint64, wraps
+ *     z   = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  r = z ^ (z >> 31)    (splitmix64)
+ *     u   = (r >> 40) / 2^24                                                the top 24 bits, exact in f32
+ *     q   = max(-log1p(-u), 2^-30)                                          Exp(1), f32 on the device
+ * and takes token = argmax_i softmax(kept logits / temperature)_i / q_i, the lower index on a tie.  Nothing else is drawn: a forced
+ * (prompted) column consumes no counter, and a prompted or streaming step t draws what dimx_generate draws at step t.
+ * For a generation with S samples per clip, sample s of clip b of this handle is global row g = (row_offset + b) * S + s and
+ * rows = rows_total * S (rows_total = 0: rows = B * S, row_offset = 0); clip groups do not enter (a group's rows keep their
+ * numbers).  A guided generation has S = 1 and draws once per clip, for both branches.  The dimx_op_sample* launches on R rows have
+ * g = the row and rows = R; a parameter block (dimx_op_sample_step, dimx_op_layer_chain_head) carries the window in words 6 / 7:
+ * g = word 6 + row and rows = word 7 (0: the launch's rows_total). */
 int dimx_set_shard(dimx_handle h, int row_offset, int rows_total);
 
 /* Speaker encoder stack + context assembly + cross-attention K/V projection for all decoder
@@ -218,7 +234,8 @@ int dimx_decode_tf_win(dimx_handle h, const int32_t* z_l, const uint8_t* ctx_mas
 /* Autoregressive generation of T-1 tokens from start[B] with KV cache.
  * temperature <= 0 or exp_noise == NULL && seed == 0 -> greedy argmax.
  * exp_noise: [T-1,B,512] f32 Exp(1) samples (token = argmax softmax(top_k(logits)/temp)/noise);
- * if NULL and seed != 0 the noise is drawn on device from a counter-based generator.
+ * if NULL and seed != 0 the noise is drawn on device from a counter-based generator (the formula is stated at dimx_set_shard:
+ * row b*S+s of step t draws counter (t * B*S + b*S + s) * 512 + code, unsharded).
  * n_samples S (1, 2, 4, 5, 8, 10): S independent samples per clip in one pass -- rows b*S+s of tokens /
  * exp_noise / logits_out belong to clip b; the clip's context K/V is streamed once for all S samples (the
  * reference's best-of-10 protocol, code/x_engine_pt.py:257, as one batched generation).  The workspace must
