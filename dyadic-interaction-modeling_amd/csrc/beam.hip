@@ -10,6 +10,8 @@
 //                           registers, row w gets the chunk of row parent[w].  A thread reads and writes only its own addresses, so
 //                           the permutation is in place with no second cache and no ordering between threads.  Clips whose parent
 //                           vector is the identity leave at once.  Token and back-pointer columns < c move the same way.
+//   beam_reorder_kv8_kernel<W>  the same over FP8 self caches (dimx_set_beam_kv8; dimx/kv8.py reorder): a thread owns one of the 4
+//                           chunks of a position's 64 codes, the first chunk's thread also moves the position's scale.
 // No atomics on data (the step word's arrival counter is the sampler's), fixed summation orders: bit-reproducible.
 #include "common.hpp"
 
@@ -216,6 +218,64 @@ template <int W> __global__ __launch_bounds__(kReorderThreads) void beam_reorder
     }
 }
 
+// The FP8 sibling: one thread per 16-byte chunk of the codes of one (plane pair, clip, head, position <= c), 4 chunks per position;
+// the thread of a position's first chunk moves that position's scale (as its 32 bits: a permutation never forms a float) the same
+// way.  Same grid, same step word, same early return, same in-place argument as beam_reorder_kernel.
+template <int W> __global__ __launch_bounds__(kReorderThreads) void beam_reorder_kv8_kernel(BeamReorderKv8Args a) {
+    const int clip = blockIdx.z;
+    int par[W];
+    bool ident = true, valid = true;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        par[w] = a.parent[clip * W + w];
+        ident = ident && par[w] == w;
+        valid = valid && (unsigned)par[w] < (unsigned)W;
+    }
+    if (ident || !valid) return;
+    int c = a.step_dev ? *a.step_dev - a.step_back : a.c_host;
+    c = c < 0 ? -1 : (c > a.Tp - 1 ? a.Tp - 1 : c);
+    const int i = blockIdx.x * kReorderThreads + threadIdx.x;
+    if (i < (c + 1) * 4) {
+        const int b = blockIdx.y / a.H, hd = blockIdx.y - b * a.H;
+        const size_t head16 = (size_t)a.Tp * 4, row16 = (size_t)a.H * head16;
+        uint8_t* codes = a.codes[0];   // by selects, as in beam_reorder_kernel
+        float* scale = a.scale[0];
+#pragma unroll
+        for (int j = 1; j < kBeamKv8Pairs; ++j) {
+            codes = b == j ? a.codes[j] : codes;
+            scale = b == j ? a.scale[j] : scale;
+        }
+        // permute_rows for the chunk and the scale in one select chain (each comparison feeds both and is dead after them)
+        uint4* cb = (uint4*)codes + (size_t)clip * W * row16 + (size_t)hd * head16 + i;
+        int* sb = (int*)scale + ((size_t)clip * W * a.H + hd) * a.Tp + (i >> 2);
+        const size_t srow = (size_t)a.H * a.Tp;
+        const bool first = (i & 3) == 0;
+        uint4 in[W];
+        int sc[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            in[w] = cb[(size_t)w * row16];
+            sc[w] = first ? sb[(size_t)w * srow] : 0;
+        }
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            uint4 o = in[0];
+            int os = sc[0];
+#pragma unroll
+            for (int j = 1; j < W; ++j) {
+                o = pick(par[w] == j, in[j], o);
+                os = pick(par[w] == j, sc[j], os);
+            }
+            cb[(size_t)w * row16] = o;
+            if (first) sb[(size_t)w * srow] = os;
+        }
+    }
+    if (blockIdx.y == 0 && i < c && i < a.tok_ld) {
+        if (a.tokens) permute_rows<W>(a.tokens + (size_t)clip * W * a.tok_ld + i, (size_t)a.tok_ld, par);
+        if (a.backptr) permute_rows<W>(a.backptr + (size_t)clip * W * a.tok_ld + i, (size_t)a.tok_ld, par);
+    }
+}
+
 __global__ void beam_init_kernel(double* cum, int32_t* parent, int R, int W) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
@@ -230,6 +290,10 @@ template <int W> void reorder_launch(const BeamReorderArgs& a, hipStream_t s) {
     const int cpp = 64 * a.es / 16;
     hipLaunchKernelGGL(beam_reorder_kernel<W>, dim3(ceil_div(a.T * cpp, kReorderThreads), a.nbuf * a.H, a.nclip), dim3(kReorderThreads), 0,
                        s, a);
+}
+template <int W> void reorder_kv8_launch(const BeamReorderKv8Args& a, hipStream_t s) {
+    hipLaunchKernelGGL(beam_reorder_kv8_kernel<W>, dim3(ceil_div(a.Tp * 4, kReorderThreads), a.nbuf * a.H, a.nclip), dim3(kReorderThreads),
+                       0, s, a);
 }
 
 }  // namespace
@@ -281,6 +345,30 @@ int launch_beam_reorder(const BeamReorderArgs& a, hipStream_t s) {
     return DIMX_OK;
 }
 
+int launch_beam_reorder_kv8(const BeamReorderKv8Args& a, hipStream_t s) {
+    DIMX_REQUIRE(a.parent && a.nbuf >= 1 && a.nbuf <= kBeamKv8Pairs, DIMX_ERR_ARG, "beam_reorder_kv8: null parents or %d plane pairs (1 .. %d)", a.nbuf,
+                 kBeamKv8Pairs);
+    DIMX_REQUIRE(beam_width_supported(a.W), DIMX_ERR_ARG, "beam_reorder_kv8: width %d not in {1,2,4,5,8,10}", a.W);
+    DIMX_REQUIRE(a.nclip >= 1 && a.H >= 1 && a.Tp >= 1 && (long)a.nbuf * a.H <= 65535 && a.nclip <= 65535, DIMX_ERR_ARG,
+                 "beam_reorder_kv8: clips %d, heads %d or positions %d out of range", a.nclip, a.H, a.Tp);
+    DIMX_REQUIRE(a.step_dev || (a.c_host >= 0 && a.c_host < a.Tp), DIMX_ERR_ARG, "beam_reorder_kv8: c = %d outside [0, %d)", a.c_host, a.Tp);
+    DIMX_REQUIRE((!a.tokens && !a.backptr) || (a.tok_ld >= 1 && a.tok_ld <= a.Tp * 4), DIMX_ERR_ARG, "beam_reorder_kv8: token row stride %d",
+                 a.tok_ld);
+    for (int b = 0; b < a.nbuf; ++b)
+        DIMX_REQUIRE(a.codes[b] && ((uintptr_t)a.codes[b] % 16) == 0 && a.scale[b] && ((uintptr_t)a.scale[b] % 4) == 0, DIMX_ERR_ARG,
+                     "beam_reorder_kv8: plane pair %d is null, its codes not 16-byte or its scales not 4-byte aligned", b);
+    if (a.W == 1) return DIMX_OK;   // one beam per clip: every parent vector is the identity
+    switch (a.W) {
+        case 2: reorder_kv8_launch<2>(a, s); break;
+        case 4: reorder_kv8_launch<4>(a, s); break;
+        case 5: reorder_kv8_launch<5>(a, s); break;
+        case 8: reorder_kv8_launch<8>(a, s); break;
+        default: reorder_kv8_launch<10>(a, s); break;
+    }
+    DIMX_HIP(hipGetLastError());
+    return DIMX_OK;
+}
+
 int launch_beam_init(double* cum, int32_t* parent, int R, int W, hipStream_t s) {
     DIMX_REQUIRE(cum && parent && R >= 1 && W >= 1, DIMX_ERR_ARG, "beam_init: bad arguments");
     hipLaunchKernelGGL(beam_init_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, s, cum, parent, R, W);
@@ -312,4 +400,14 @@ int dimx_op_beam_reorder(void* cache, int dtype, const int32_t* parent, int R, i
     a.nclip = R / W, a.W = W, a.H = H, a.T = T;
     a.parent = parent, a.c_host = c;
     return launch_beam_reorder(a, (hipStream_t)stream);
+}
+
+int dimx_op_beam_reorder_kv8(void* kcodes, void* kscale, const int32_t* parent, int R, int W, int H, int Tp, int c, void* stream) {
+    DIMX_REQUIRE(kcodes && kscale && parent, DIMX_ERR_ARG, "beam_reorder_kv8: null operand");
+    DIMX_REQUIRE(W >= 1 && R >= 1 && R % W == 0, DIMX_ERR_ARG, "beam_reorder_kv8: R=%d is not a positive multiple of W=%d", R, W);
+    BeamReorderKv8Args a;
+    a.codes[0] = (uint8_t*)kcodes, a.scale[0] = (float*)kscale, a.nbuf = 1;
+    a.nclip = R / W, a.W = W, a.H = H, a.Tp = Tp;
+    a.parent = parent, a.c_host = c;
+    return launch_beam_reorder_kv8(a, (hipStream_t)stream);
 }

@@ -710,6 +710,24 @@ struct BeamReorderArgs {
     int tok_ld = 0;
 };
 int launch_beam_reorder(const BeamReorderArgs& a, hipStream_t s);
+// The same permutation over FP8 self caches (dimx_set_self_kv8 under dimx_set_beam_kv8; the definition is dimx/kv8.py reorder): nbuf
+// pairs of a code plane [nclip * W, H, Tp, 64] uint8 and its scale plane [nclip * W, H, Tp] f32 -- the K and the V pair of every
+// layer (stages.hpp kv8_layer_of) -- positions 0 .. c, codes and scale of a position together; the position stride is Tp, not T.
+// Tokens / back-pointers and c as in BeamReorderArgs.  One launch of at most 8 pairs (a decoder of depth 4): 16 pointers, the plain
+// kernel's argument block -- with 32 the W = 8 and W = 10 instantiations run out of scalar registers.
+constexpr int kBeamKv8Pairs = 8;
+struct BeamReorderKv8Args {
+    uint8_t* codes[kBeamKv8Pairs] = {};
+    float* scale[kBeamKv8Pairs] = {};
+    int nbuf = 0, nclip = 0, W = 0, H = 0, Tp = 0;
+    const int32_t* parent = nullptr;
+    const int32_t* step_dev = nullptr;
+    int step_back = 0, c_host = 0;
+    int32_t* tokens = nullptr;
+    int32_t* backptr = nullptr;
+    int tok_ld = 0;
+};
+int launch_beam_reorder_kv8(const BeamReorderKv8Args& a, hipStream_t s);
 // cum[r] = 0 for beam 0 of a clip, -inf for the others; parent[r] = r % W
 int launch_beam_init(double* cum, int32_t* parent, int R, int W, hipStream_t s);
 // the first decoder layer's q/k/v as a table over the token ids (generate.hip qkv0_table_build): id list of the build rounds,

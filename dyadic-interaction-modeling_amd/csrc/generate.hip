@@ -556,6 +556,24 @@ static int finish_beam(const StepCtx& c, int nlg) {
     bs.qkv0_table = c.r->qkv0; bs.qkv0_out = s.qkv; bs.qkv0_N = 3 * c.inner;
     DIMX_TRY(launch_beam_select(bs, c.st));
     if (!c.r->qkv0) DIMX_TRY(launch_add_slabs_layernorm(h->at, s.x, s.xr, 0, s.st_xr, s.y, h->dec.self_[0].ln_g, c.B, c.DD, c.st));
+    if (c.r->self_kv8) {   // every layer's self attention reads the codes (no table form under beam search): they are what moves
+        // one launch holds kBeamKv8Pairs (code plane, scale plane) pairs: the K and V pairs of 4 layers.  A deeper decoder takes a
+        // second launch; the first one moves the token / back-pointer columns
+        constexpr int per = kBeamKv8Pairs / 2;
+        for (int l0 = 0; l0 < depth; l0 += per) {
+            BeamReorderKv8Args bk;
+            const int nl = depth - l0 < per ? depth - l0 : per;
+            for (int l = 0; l < nl; ++l) {
+                bk.codes[2 * l] = c.skv8[l0 + l].kcodes; bk.scale[2 * l] = c.skv8[l0 + l].kscale;
+                bk.codes[2 * l + 1] = c.skv8[l0 + l].vcodes; bk.scale[2 * l + 1] = c.skv8[l0 + l].vscale;
+            }
+            bk.nbuf = 2 * nl; bk.nclip = c.nclip; bk.W = c.S; bk.H = c.heads; bk.Tp = c.Tp;
+            bk.parent = bs.parent; bk.step_dev = s.step; bk.step_back = 1;
+            if (l0 == 0) { bk.tokens = c.tokens; bk.backptr = bs.backptr; bk.tok_ld = n; }
+            DIMX_TRY(launch_beam_reorder_kv8(bk, c.st));
+        }
+        return DIMX_OK;
+    }
     BeamReorderArgs br;
     for (int l = 0; l < depth; ++l) {
         br.buf[2 * l] = s.sk[l];
@@ -643,7 +661,7 @@ static int resolve_route(dimx_handle h, const GenCall& gc, int G, int rows, Step
     r.win = h->xwin_on != 0;
     r.lookahead = r.win ? h->xwin_lookahead : 0;
     r.kv8 = gc.kv8_buf != nullptr;   // the layer kernel streams the caches itself: not taken, exactly as under the window
-    r.kv8_samples = r.kv8 && q.S > 1;   // gen_open let S > 1 through under dimx_set_cross_kv8_samples only
+    r.kv8_samples = r.kv8 && q.S > 1;   // gen_open let S > 1 through under dimx_set_cross_kv8_samples (a beam: dimx_set_beam_kv8) only
     r.self_kv8 = gc.self_kv8_buf != nullptr;   // no layer kernel either: it streams the self caches itself
     r.guided = q.guided;
     if (r.guided) r.chain = r.defer = r.logits_chain = r.multi_tr = false;   // the per-op step, as a session takes it (no layer kernel either: it needs chain)
@@ -692,6 +710,7 @@ static GraphKey graph_key(dimx_handle h, const GenCall& gc, const StepRoute& r) 
     k.kv8 = r.kv8 ? gc.kv8_buf : nullptr;
     k.kv8_samples = r.kv8_samples;
     k.self_kv8 = r.self_kv8 ? gc.self_kv8_buf : nullptr;
+    k.beam_reorder_kv8 = q.beam && r.self_kv8;
     return k;
 }
 
@@ -905,14 +924,15 @@ int gen_open(dimx_handle h, GenRun& run, bool keep_prefill, bool prefill_only, c
     DIMX_REQUIRE(S == 1 || S == 2 || S == 4 || S == 5 || S == 8 || S == 10, DIMX_ERR_ARG,
                  "generate: n_samples %d not in {1,2,4,5,8,10}", S);
     if (h && h->kv8_buf && !sess) {   // FP8 cross K/V: one row per clip, the sampler ends the step; a session does not read the setting
-        DIMX_REQUIRE((S == 1 || (h->kv8_samples_on && !q.guided)) && !q.beam, DIMX_ERR_ARG,
+        // a beam search takes the buffer under dimx_set_beam_kv8 only (its W hypotheses are the multi-query launch's rows)
+        DIMX_REQUIRE(q.beam ? h->beam_kv8_on != 0 : (S == 1 || (h->kv8_samples_on && !q.guided)), DIMX_ERR_ARG,
                      "generate: n_samples > 1 and beam search are not available with dimx_set_cross_kv8");
         DIMX_REQUIRE(kv8_bytes(h, B, T) != 0, DIMX_ERR_ARG, "generate: B=%d T=%d is not supported with dimx_set_cross_kv8", B, T);
         DIMX_REQUIRE(h->kv8_bytes >= kv8_bytes(h, B, T), DIMX_ERR_WORKSPACE, "generate: the FP8 cross K/V buffer holds %zu bytes, B=%d T=%d needs %zu (dimx_cross_kv8_bytes)",
                      h->kv8_bytes, B, T, kv8_bytes(h, B, T));
     }
     if (h && h->self_kv8_buf && !sess) {   // FP8 self K/V: rows are sequences, the sampler ends the step; a session does not read the setting
-        DIMX_REQUIRE(!q.beam && !q.guided, DIMX_ERR_ARG, "generate: beam search and guidance are not available with dimx_set_self_kv8");
+        DIMX_REQUIRE((!q.beam || h->beam_kv8_on) && !q.guided, DIMX_ERR_ARG, "generate: beam search and guidance are not available with dimx_set_self_kv8");
         DIMX_REQUIRE(kv8_bytes(h, B * S, T) != 0, DIMX_ERR_ARG, "generate: B=%d n_samples=%d T=%d is not supported with dimx_set_self_kv8", B, S, T);
         DIMX_REQUIRE(h->self_kv8_bytes >= kv8_bytes(h, B * S, T), DIMX_ERR_WORKSPACE,
                      "generate: the FP8 self K/V buffer holds %zu bytes, B=%d n_samples=%d T=%d needs %zu (dimx_self_kv8_bytes)", h->self_kv8_bytes, B, S, T,
@@ -1320,6 +1340,21 @@ int dimx_set_cross_kv8_samples(dimx_handle h, int on) {
 int dimx_cross_kv8_samples(dimx_handle h, int* on) {
     DIMX_REQUIRE(h, DIMX_ERR_ARG, "cross_kv8_samples: null handle");
     if (on) *on = h->kv8_samples_on;
+    return DIMX_OK;
+}
+
+int dimx_set_beam_kv8(dimx_handle h, int on) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "set_beam_kv8: null handle");
+    DIMX_NO_SESSION(h, "set_beam_kv8");
+    DIMX_REQUIRE(h->variant == 0, DIMX_ERR_ARG, "set_beam_kv8: FP8 K/V is implemented for variant 0 (SLMFT) only; this handle is variant %d",
+                 h->variant);
+    h->beam_kv8_on = on ? 1 : 0;
+    return DIMX_OK;
+}
+
+int dimx_beam_kv8(dimx_handle h, int* on) {
+    DIMX_REQUIRE(h, DIMX_ERR_ARG, "beam_kv8: null handle");
+    if (on) *on = h->beam_kv8_on;
     return DIMX_OK;
 }
 

@@ -164,13 +164,15 @@ struct GraphKey {
     const void* kv8;               // the FP8 cross K/V buffer the cross attention's launches read (dimx_set_cross_kv8), nullptr = off
     bool kv8_samples;              // dimx_set_cross_kv8_samples: the multi-query launch over the codes
     const void* self_kv8;          // the FP8 self K/V buffer the self attention's launches append to and read (dimx_set_self_kv8), nullptr = off
+    bool beam_reorder_kv8;         // a beam step ends in launch_beam_reorder_kv8 on that buffer's planes, not in launch_beam_reorder on the caches
     bool operator==(const GraphKey& o) const {
         return ws == o.ws && B == o.B && T == o.T && top_k == o.top_k && noise == o.noise && start == o.start && mask == o.mask &&
                tokens == o.tokens && logits_out == o.logits_out && G == o.G && S == o.S && chain == o.chain && defer == o.defer &&
                logits_chain == o.logits_chain && multi_tr == o.multi_tr && fault_inject == o.fault_inject &&
                layer_kernel == o.layer_kernel && qkv0 == o.qkv0 && kv0 == o.kv0 && sample_head == o.sample_head && prompt_len == o.prompt_len &&
                ld_prompt == o.ld_prompt && Pmax == o.Pmax && filter_kind == o.filter_kind && beam == o.beam && xwin_on == o.xwin_on &&
-               xwin_lookahead == o.xwin_lookahead && guided == o.guided && branch_out == o.branch_out && kv8 == o.kv8 && kv8_samples == o.kv8_samples && self_kv8 == o.self_kv8;
+               xwin_lookahead == o.xwin_lookahead && guided == o.guided && branch_out == o.branch_out && kv8 == o.kv8 && kv8_samples == o.kv8_samples && self_kv8 == o.self_kv8 &&
+               beam_reorder_kv8 == o.beam_reorder_kv8;
     }
 };
 
@@ -276,6 +278,9 @@ struct dimx_ctx {
     // self attention reads, rows = sequences (clips x samples); nullptr = off
     void* self_kv8_buf = nullptr;
     size_t self_kv8_bytes = 0;
+    // dimx_set_beam_kv8: dimx_generate_beam takes the two buffers above (the cross one through the multi-query launch, the self one
+    // reordered by beam_reorder_kv8_kernel); off = it refuses them
+    int beam_kv8_on = 0;
     // online fine-tuning (dimx_set_train_lookahead): the same visibility in the decoder cross attention of
     // dimx_train_forward_backward, query row i = step t.  Independent of xwin_*.
     int twin_on = 0, twin_lookahead = 0;

@@ -337,6 +337,18 @@ class Engine:
         L.check(self.lib.dimx_self_kv8(self.h, ctypes.byref(p), ctypes.byref(n)), "dimx_self_kv8")
         return (p.value, n.value) if p.value else None
 
+    def set_beam_kv8(self, on=True):
+        """FP8 K/V caches for beam search (dimx_set_beam_kv8; dimx.kv8.reorder): with this on, ``generate_beam`` takes the cross
+        and / or self buffer in force instead of refusing them.  ``generate_beam(beam_kv8=...)`` sets buffers and switch around
+        one call."""
+        L.check(self.lib.dimx_set_beam_kv8(self.h, 1 if on else 0), "dimx_set_beam_kv8")
+
+    def beam_kv8(self):
+        """The handle's current setting (bool)."""
+        on = ctypes.c_int(0)
+        L.check(self.lib.dimx_beam_kv8(self.h, ctypes.byref(on)), "dimx_beam_kv8")
+        return bool(on.value)
+
     def self_kv8_buffer(self):
         """The uint8 tensor the last ``generate(self_kv8=True)`` appended to (None before the first); ``self_kv8_layers`` views it."""
         return getattr(self, "_skv8", None)
@@ -579,15 +591,53 @@ class Engine:
         return self._generated(tokens, lg, mask_u8, T, n_samples, plen, return_logits, return_scores)
 
     def generate_beam(self, start, mask_u8, T, beam_width, prompt=None, prompt_len=None, prefill=None, return_logits=False,
-                      return_backptr=False):
+                      return_backptr=False, beam_kv8=None):
         """Beam search (dimx_generate_beam, csrc/beam.hip; the definition is dimx.beam): W = ``beam_width`` hypotheses per clip in
         one pass (rows b*W + w, sharing the clip's context K/V like ``n_samples``), deterministic, no temperature / filter / seed.
         -> (tokens [B*W, n] int32 -- whole hypotheses, row b*W the best --, scores f64 [B*W], descending within a clip[, logits
         [B*W, n, 512] in the row order each step ran in][, backptr [B*W, n] int32: the row that ran step c on the hypothesis's path]).
         The scored columns are those of dimx.scoring.scored_columns (inside the clip's length, past its prompt); the lengths come
         from ``mask_u8`` on the device.  ``prompt`` / ``prompt_len`` / ``prefill`` as in ``generate``; the context must have been
-        built with ``n_samples=beam_width`` (and ``prompt_frames >= prefill``)."""
+        built with ``n_samples=beam_width`` (and ``prompt_frames >= prefill``).
+
+        ``beam_kv8``: None (today's call), "self", "cross" or True (both): the search runs on FP8 self caches and / or an FP8 copy
+        of the cross K/V (``set_beam_kv8``; dimx.kv8.reorder, self_step, attention_rows).  The engine allocates (or
+        reuses) the buffers ``generate(self_kv8=, kv8_samples=)`` use -- ``self_kv8_bytes(B * W, T)`` / ``cross_kv8_bytes(B, T)`` --
+        sets them and the switch for the call and clears all three afterwards; ``self_kv8_layers(B * W, T)`` / ``cross_kv8_layers(B, T)``
+        view what the search left."""
         W = int(beam_width)
+        if beam_kv8 is not None and beam_kv8 is not False:
+            beam_kv8 = True if beam_kv8 == "both" else beam_kv8     # the command-line spelling of True
+            if beam_kv8 not in (True, "self", "cross"):
+                raise ValueError("beam_kv8=%r: one of None, 'self', 'cross', True" % (beam_kv8,))
+            B = (prompt if prompt is not None else start).shape[0]
+            if beam_kv8 in (True, "self"):
+                need = self.self_kv8_bytes(B * W, T)
+                if need == 0:
+                    raise L.DimxError("generate_beam(beam_kv8=%r): dimx_self_kv8_bytes(%d, %d) = 0 (shape or variant not supported)"
+                                      % (beam_kv8, B * W, T))
+                if self.self_kv8_buffer() is None or self._skv8.numel() < need:
+                    self._skv8 = None
+                    self._skv8 = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            if beam_kv8 in (True, "cross"):
+                need = self.cross_kv8_bytes(B, T)
+                if need == 0:
+                    raise L.DimxError("generate_beam(beam_kv8=%r): dimx_cross_kv8_bytes(%d, %d) = 0 (shape or variant not supported)"
+                                      % (beam_kv8, B, T))
+                if self.cross_kv8_buffer() is None or self._kv8.numel() < need:
+                    self._kv8 = None
+                    self._kv8 = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            try:
+                if beam_kv8 in (True, "self"):
+                    self.set_self_kv8(self._skv8)
+                if beam_kv8 in (True, "cross"):
+                    self.set_cross_kv8(self._kv8)
+                self.set_beam_kv8(True)
+                return self.generate_beam(start, mask_u8, T, W, prompt, prompt_len, prefill, return_logits, return_backptr)
+            finally:
+                self.set_beam_kv8(False)
+                self.set_self_kv8(None)
+                self.set_cross_kv8(None)
         if prompt is None:
             prompt, prompt_len, prefill = start.reshape(-1, 1), None, 1
         B, Pmax = prompt.shape
@@ -1743,6 +1793,23 @@ def op_beam_reorder(cache, parent, c, beam_width):
         L.check(L.load().dimx_op_beam_reorder(L.ptr(cache), L.BF16 if cache.dtype == torch.bfloat16 else L.F32, L.ptr(parent_d), R,
                                               int(beam_width), H, T, int(c), L.stream_ptr(dev)), "dimx_op_beam_reorder")
     return cache
+
+
+def op_beam_reorder_kv8(codes, scale, parent, c, beam_width):
+    """In-place reorder of one FP8 code plane and its scale plane by parent beam (dimx_op_beam_reorder_kv8, csrc/beam.hip; the
+    definition is dimx.kv8.reorder): codes [R, H, Tp, 64] uint8 and scale [R, H, Tp] float32, contiguous, parent [R] int32 -> codes
+    and scale of the positions 0 .. c of row clip*W + w become those of row clip*W + parent[w]; returns ``(codes, scale)``."""
+    if not (torch.is_tensor(codes) and torch.is_tensor(scale) and codes.is_cuda and scale.is_cuda and codes.is_contiguous()
+            and scale.is_contiguous() and codes.dim() == 4 and codes.shape[3] == 64 and codes.dtype == torch.uint8
+            and scale.dtype == torch.float32 and tuple(scale.shape) == tuple(codes.shape[:3]) and scale.device == codes.device):
+        raise L.DimxError("op_beam_reorder_kv8: contiguous CUDA planes codes [R, H, Tp, 64] uint8 and scale [R, H, Tp] float32 expected")
+    dev = codes.device
+    R, H, Tp, _ = (int(v) for v in codes.shape)
+    parent_d = _lens_i32(parent, dev, R, "op_beam_reorder_kv8(parent)")
+    with torch.cuda.device(dev):
+        L.check(L.load().dimx_op_beam_reorder_kv8(L.ptr(codes), L.ptr(scale), L.ptr(parent_d), R, int(beam_width), H, Tp, int(c),
+                                                  L.stream_ptr(dev)), "dimx_op_beam_reorder_kv8")
+    return codes, scale
 
 
 def op_score_select(score, y_pred, lens, tokens=None):

@@ -8,6 +8,7 @@ cast.  ``self_step`` is the same for the self-attention caches (dimx_set_self_kv
 whose new row is quantised by the step itself.  ``attention_rows`` is ``attention`` for best-of-N generation (dimx_set_cross_kv8_samples):
 several query rows per clip over that clip's codes; ``round_bf16`` and ``pv_abs`` state what its matrix-core form rounds and how far
 that can move an output element.  ``append`` is ``quantize`` for the rows a streaming session's push adds (dimx_stream_set_kv8).
+``reorder`` is what a beam step does to the self caches' codes and scales (dimx_set_beam_kv8): a permutation by parent hypothesis.
 
     amax = max |x| over the row (float32)
     scale = float32(amax) / float32(448)              one IEEE float32 division; amax < 2**-60: a zero row, scale 0, codes 0
@@ -182,6 +183,36 @@ def self_step(q, k_new, v_new, kcodes, kscale, vcodes, vscale, n, scale=0.125):
     kcodes[:, :, n], kscale[:, :, n] = kc, ksc
     vcodes[:, :, n], vscale[:, :, n] = vc, vsc
     return attention(q, kcodes, kscale, vcodes, vscale, None, n + 1, scale)
+
+
+def reorder(codes, scale, parent, c, W):
+    """Beam search over FP8 self caches (dimx_set_beam_kv8; beam_reorder_kv8_kernel): what a beam step's reorder does to one code
+    plane and its scale plane.
+
+    codes [R, H, Tp, 64] uint8, scale [R, H, Tp] float32, parent [R] (the step's parent beams, counted within the clip), rows
+    clip * W + w the W hypotheses of a clip.  Row clip * W + w takes the positions 0 .. c of row clip * W + parent[w], codes and scale
+    together; positions > c are unchanged; a clip is untouched if its parents are the identity or if any of them lies outside
+    [0, W).  Returns the two arrays (copies; the arguments are left as they are).
+
+    It is a pure permutation of (codes, scale) pairs, so ``dequantize(reorder(x)) == reorder(dequantize(x))`` bit for bit: after the
+    step a hypothesis's buffer rows ARE its ancestor's, and ``self_step`` on them is what ``self_step`` on the ancestor's buffer
+    is.  That is the whole reason beam search over FP8 caches needs no definition beyond dimx.beam (the search) plus ``self_step``
+    (the attention): nothing is re-quantised, no scale is recomputed, and no value is ever formed from the moved bits."""
+    codes, scale = np.array(codes, dtype=np.uint8, order="C"), np.array(scale, dtype=np.float32, order="C")
+    parent = np.asarray(parent).astype(np.int64).reshape(-1)
+    R, W, c = codes.shape[0], int(W), int(c)
+    assert W >= 1 and R % W == 0 and parent.shape[0] == R and scale.shape == codes.shape[:3], "reorder: R rows of W per clip"
+    assert 0 <= c < codes.shape[2], "reorder: c inside the planes"
+    src_c, src_s = codes.copy(), scale.view(np.uint32).copy()   # the scales as bits: a NaN payload moves unchanged
+    out_s = scale.view(np.uint32)
+    for clip in range(R // W):
+        p = parent[clip * W:(clip + 1) * W]
+        if np.array_equal(p, np.arange(W)) or (p < 0).any() or (p >= W).any():
+            continue
+        for w in range(W):
+            codes[clip * W + w, :, :c + 1] = src_c[clip * W + p[w], :, :c + 1]
+            out_s[clip * W + w, :, :c + 1] = src_s[clip * W + p[w], :, :c + 1]
+    return codes, scale
 
 
 def buffer_layout(depth, B, H, Tp):

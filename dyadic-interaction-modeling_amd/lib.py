@@ -78,6 +78,8 @@ SIGNATURES = {
     "dimx_self_kv8_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "dimx_set_self_kv8": (c_int, [c_void_p, c_void_p, c_size_t]),
     "dimx_self_kv8": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
+    "dimx_set_beam_kv8": (c_int, [c_void_p, c_int]),
+    "dimx_beam_kv8": (c_int, [c_void_p, POINTER(c_int)]),
     "dimx_op_decode_attn_self_kv8": (c_int, [c_int, c_void_p, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p]),
     "dimx_stream_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
@@ -278,6 +280,7 @@ SIGNATURES = {
                                   c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dimx_op_beam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dimx_op_beam_reorder": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dimx_op_beam_reorder_kv8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dimx_op_sample": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p,
                                c_void_p]),
     "dimx_op_sample_guided": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_long, c_float, c_int, c_int, c_float, c_float, c_float,

@@ -162,7 +162,7 @@ class SLMFT(_EngineOwner):
     def forward_decoder(self, x_s, z_l, x_a, mask, mode, v_speaker=None, noise=None, kv_mask=None, greedy=False,
                         seed=None, temperature=1.0, n_samples=1, prompt_frames=1, lengths=None, filter_logits_fn=None,
                         filter_kwargs=None, return_scores=False, beam_width=0, lookahead=None, window_prefill=False, guidance=None,
-                        kv8=False, self_kv8=False, kv8_samples=False):
+                        kv8=False, self_kv8=False, kv8_samples=False, beam_kv8=None):
         """reference :444-452, same positional call: ``forward_decoder(x_s, z_l, x_a, mask, mode)`` with the ``x_s``
         that ``forward_encoder`` returned.  ``forward()`` passes ``x_s=None, v_speaker=...`` instead, which keeps the
         encoder output inside the engine workspace (no round trip through a tensor).
@@ -203,7 +203,13 @@ class SLMFT(_EngineOwner):
 
         ``kv8_samples`` (mode 'val', any ``n_samples``, no beam search, no guidance): ``kv8`` for best-of-N -- the S queries of a clip
         read that clip's FP8 codes in one multi-query launch per layer (dimx.kv8.attention_rows,
-        ``Engine.generate(kv8_samples=True)``).  False is the call without the argument, launch for launch."""
+        ``Engine.generate(kv8_samples=True)``).  False is the call without the argument, launch for launch.
+
+        ``beam_kv8`` (mode 'val', with ``beam_width``, no guidance): "self", "cross" or True (both) -- the beam search runs on FP8
+        self caches and / or an FP8 copy of the cross K/V (dimx.kv8.reorder, ``Engine.generate_beam(beam_kv8=...)``).  None is the
+        call without the argument, launch for launch."""
+        if beam_kv8 and (mode != "val" or not beam_width or guidance is not None):
+            raise ValueError("beam_kv8 applies to mode='val' with beam_width and without guidance")
         if kv8_samples and (mode != "val" or beam_width or guidance is not None):
             raise ValueError("kv8_samples applies to mode='val' without beam search and without guidance")
         if self_kv8 and (mode != "val" or beam_width or guidance is not None):
@@ -246,7 +252,7 @@ class SLMFT(_EngineOwner):
         if beam_width:
             from .scoring import SeqScores, scored_columns
             tokens, score = eng.generate_beam(z_l[:, 0], m8, T, int(beam_width), prompt=z_l[:, :prompt_frames] if prompt_frames > 1 else None,
-                                              prompt_len=plen, prefill=p0)
+                                              prompt_len=plen, prefill=p0, beam_kv8=beam_kv8 or None)
             if not return_scores:
                 return 0.0, tokens.long()
             n = tokens.shape[1]
@@ -363,7 +369,7 @@ class SLMFT(_EngineOwner):
                 noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                 return_tokens=False, n_samples=1, shard=None, z_l=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
                 filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False,
-                guidance=None, kv8=False, self_kv8=False, kv8_samples=False):
+                guidance=None, kv8=False, self_kv8=False, kv8_samples=False, beam_kv8=None):
         """reference :496-514.  In training (``model.train()``, grad enabled, parameters requiring grad) the
         teacher-forced pass returns a loss with an autograd graph; everything else is the HIP inference path.
 
@@ -398,7 +404,12 @@ class SLMFT(_EngineOwner):
         (dimx.kv8.self_step; ``forward_decoder``) -- the protocol's best-of-N runs take it.
 
         ``kv8_samples`` (mode 'val', any ``n_samples``, no beam search, no guidance): FP8 cross-attention K/V for a best-of-N
-        generation (dimx.kv8.attention_rows; ``forward_decoder``); combines with ``self_kv8``."""
+        generation (dimx.kv8.attention_rows; ``forward_decoder``); combines with ``self_kv8``.
+
+        ``beam_kv8`` (mode 'val', with ``beam_width``, no guidance): "self", "cross" or True (both) -- FP8 self caches and / or FP8
+        cross K/V for the beam search (dimx.kv8.reorder; ``forward_decoder``)."""
+        if beam_kv8 and (mode != "val" or beam_width is None or guidance is not None):
+            raise ValueError("beam_kv8 applies to mode='val' with beam_width and without guidance")
         if kv8_samples and (mode != "val" or beam_width is not None or guidance is not None):
             raise ValueError("kv8_samples applies to mode='val' without beam search and without guidance")
         if self_kv8 and (mode != "val" or beam_width is not None or guidance is not None):
@@ -428,14 +439,14 @@ class SLMFT(_EngineOwner):
                                         filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs, return_scores=return_scores,
                                         beam_width=beam_width, num_return=num_return, lookahead=lookahead,
                                         window_prefill=window_prefill, guidance=guidance, kv8=kv8, self_kv8=self_kv8,
-                                        kv8_samples=kv8_samples)
+                                        kv8_samples=kv8_samples, beam_kv8=beam_kv8)
 
     @torch.no_grad()
     def _forward_nograd(self, v_speaker, v_listener, v_audio, mask, mode="train", speaker_ids=None, listener_ids=None,
                         noise=None, kv_mask=None, greedy=False, seed=None, temperature=1.0, batch_row_offset=0,
                         return_tokens=False, n_samples=1, shard=None, prompt_frames=1, lengths=None, filter_logits_fn=None,
                         filter_kwargs=None, return_scores=False, beam_width=None, num_return=1, lookahead=None, window_prefill=False,
-                        guidance=None, kv8=False, self_kv8=False, kv8_samples=False):
+                        guidance=None, kv8=False, self_kv8=False, kv8_samples=False, beam_kv8=None):
         """reference :496-514 -> (total_loss, dict, pred_cont_seq_l [B,T-1,56]).
 
         ``n_samples`` S > 1 (mode 'val' only): S independent generations per clip in ONE pass -- what the
@@ -457,7 +468,7 @@ class SLMFT(_EngineOwner):
                                                          filter_logits_fn=filter_logits_fn, filter_kwargs=filter_kwargs,
                                                          return_scores=return_scores, beam_width=W, lookahead=lookahead,
                                                          window_prefill=window_prefill, guidance=guidance, kv8=kv8, self_kv8=self_kv8,
-                                                         kv8_samples=kv8_samples)
+                                                         kv8_samples=kv8_samples, beam_kv8=beam_kv8)
         finally:
             eng.set_shard(0, 0)
         if W and int(num_return) == 1:    # the best hypothesis is row 0 of its clip

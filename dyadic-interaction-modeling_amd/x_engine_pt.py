@@ -211,7 +211,7 @@ def _select(pending, skip_degenerate, world, device):
 def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=True, skip_degenerate=False,
                         fd_backend="reference", metrics=None, prompt_frames=1, filter_logits_fn=None, filter_kwargs=None,
                         select="fd", decode="sample", beam_width=None, consensus_distance="fd", lookahead=None, window_prefill=False, guidance=None,
-                        kv8=False, self_kv8=False, kv8_samples=False, **forward_kw):
+                        kv8=False, self_kv8=False, kv8_samples=False, beam_kv8=None, **forward_kw):
     """reference code/x_engine_pt.py:232-277 (autoregressive generation, best of ``beam_size`` by FD; a candidate
     replaces the current best only when its FD is strictly smaller, and scipy's "Imaginary component" ValueError on a
     degenerate clip propagates, both as in the reference; ``skip_degenerate=True`` scores such a candidate as inf).
@@ -287,7 +287,15 @@ def evaluate_test_epoch(model, loader, device, beam_size=10, batched_samples=Tru
 
     ``kv8_samples``: ``kv8`` for the batched pass (dimx.kv8.attention_rows, ``SLMFT.forward(kv8_samples=True)``): the
     ``beam_size`` tries of a clip stay ONE generation whose multi-query cross attention reads the FP8 codes, with every ``select``
-    and with ``self_kv8``; not with ``decode="beam"`` or ``guidance`` (ValueError).  False (default) leaves every path as it is."""
+    and with ``self_kv8``; not with ``decode="beam"`` or ``guidance`` (ValueError).  False (default) leaves every path as it is.
+
+    ``beam_kv8``: "self", "cross", "both" or True with ``decode="beam"``: every beam search runs on FP8 self caches and / or an FP8
+    copy of the cross K/V (dimx.kv8.reorder, ``SLMFT.forward(beam_kv8=...)``), with every ``select``; without ``decode="beam"`` or
+    with ``guidance`` it raises ValueError.  None (default) leaves every path as it is."""
+    if beam_kv8:
+        if decode != "beam" or guidance is not None:
+            raise ValueError("evaluate_test_epoch(beam_kv8=...) applies to decode='beam' without guidance")
+        forward_kw = dict(forward_kw, beam_kv8=True if beam_kv8 == "both" else beam_kv8)
     if kv8_samples:
         if decode == "beam" or guidance is not None:
             raise ValueError("evaluate_test_epoch(kv8_samples=True) applies to decode='sample' without guidance")

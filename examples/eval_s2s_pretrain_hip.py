@@ -72,6 +72,10 @@ def main():
                     help="FP8 cross-attention K/V for the batched best-of-N pass (dimx.kv8.attention_rows): the tries of a clip stay one "
                          "generation whose multi-query cross attention reads the codes.  Every --select, with --self-kv8; not with "
                          "--decode beam or --guidance")
+    ap.add_argument("--beam-kv8", choices=("self", "cross", "both"), default=None,
+                    help="FP8 K/V caches for --decode beam (dimx.kv8.reorder): the self caches (codes and scales reordered by parent "
+                         "hypothesis), the cross K/V (the hypotheses of a clip read its codes in one launch), or both.  Every --select; "
+                         "not with --guidance")
     sampling.add_filter_arguments(ap)     # --filter {top_k,top_p,min_p,top_a} --filter-thres --filter-k --min-p --top-a-pow --top-a-ratio
     args = ap.parse_args()
     sampler = sampling.filter_from_args(args)
@@ -96,7 +100,7 @@ def main():
                                                         select=args.select, consensus_distance=args.consensus_distance,
                                                         decode=args.decode, beam_width=args.beam_width, lookahead=args.lookahead,
                                                         guidance=args.guidance, kv8=args.kv8, self_kv8=args.self_kv8, kv8_samples=args.kv8_samples,
-                                                        **sampler)
+                                                        beam_kv8=args.beam_kv8, **sampler)
     torch.cuda.synchronize()
     print("generated %d clips x best-of-%d (selected by %s) in %.2f s" % (len(y_true), args.beam, args.select, time.time() - t0))
     parts, parts_online, parts_null = [], [], []

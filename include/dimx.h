@@ -408,7 +408,7 @@ int dimx_cross_lookahead(dimx_handle h, int* on, int* lookahead);
  *   - The decoder-layer kernel is not taken (as under the window); the chain route and the per-op route stay.  With the window on
  *     the kv8 cross attention is the windowed one.  In a guided step it runs over the conditional rows only.  The regeneration after
  *     a chain fault keeps the setting and reuses the codes.
- *   - n_samples > 1 (without dimx_set_cross_kv8_samples) and dimx_generate_beam return DIMX_ERR_ARG before any launch; a buffer below dimx_cross_kv8_bytes(h, B, T) for
+ *   - n_samples > 1 (without dimx_set_cross_kv8_samples) and dimx_generate_beam (without dimx_set_beam_kv8) return DIMX_ERR_ARG before any launch; a buffer below dimx_cross_kv8_bytes(h, B, T) for
  *     the call's shape returns DIMX_ERR_WORKSPACE. */
 size_t dimx_cross_kv8_bytes(dimx_handle h, int B, int T);
 int dimx_set_cross_kv8(dimx_handle h, void* buf, size_t bytes);
@@ -445,12 +445,29 @@ int dimx_cross_kv8_samples(dimx_handle h, int* on);
  *     Works with the cross-attention window, the sampler filters, logits_out and prompts; a prefilled prompt's rows 0 .. P0 - 2 are
  *     quantised from the caches the prefill wrote, one dimx_op_kv8_quantize launch per layer and operand, ahead of the first step.
  *     Combines with dimx_set_cross_kv8 at one sample per clip.
- *   - dimx_generate_beam and dimx_generate_guided return DIMX_ERR_ARG before any launch; a buffer below
+ *   - dimx_generate_beam (without dimx_set_beam_kv8) and dimx_generate_guided return DIMX_ERR_ARG before any launch; a buffer below
  *     dimx_self_kv8_bytes(h, B * n_samples, T) for the call's shape returns DIMX_ERR_WORKSPACE. */
 size_t dimx_self_kv8_bytes(dimx_handle h, int R, int T);
 int dimx_set_self_kv8(dimx_handle h, void* buf, size_t bytes);
 /* The handle's current setting (either pointer may be NULL). */
 int dimx_self_kv8(dimx_handle h, void** buf, size_t* bytes);
+/* FP8 K/V caches for beam search (csrc/beam.hip, beam_reorder_kv8_kernel; the definition is dimx/kv8.py reorder on top of dimx/beam.py
+ * and self_step).  A separate opt-in on top of dimx_set_cross_kv8 / dimx_set_self_kv8: handle state of variant 0
+ * (DIMX_ERR_ARG otherwise), default off, DIMX_ERR_STATE while a streaming session is open (sessions do not read it).  With on = 0
+ * dimx_generate_beam refuses a handle with either buffer set, exactly as before the setting existed.  With on != 0:
+ *   - a self buffer of dimx_self_kv8_bytes(h, B * beam_width, T) bytes: every layer's self attention of every beam step appends to
+ *     and reads the codes (beam search has no table form of layer 0), a prefilled prompt's rows are quantised once over the B * W
+ *     rows, and the step ends in ONE launch that permutes, by parent hypothesis, positions 0 .. c of every layer's K codes, V
+ *     codes, K scales and V scales (codes and scale of a position move together: a pure permutation, so the rows a hypothesis reads
+ *     afterwards are its ancestor's, bit for bit) and the token / back-pointer columns < c.  The unquantised self caches are not
+ *     reordered: nothing reads them after the prefill's quantisation.
+ *   - a cross buffer of dimx_cross_kv8_bytes(h, B, T) bytes: the W hypotheses of a clip read that clip's codes through the
+ *     multi-query launch of dimx_set_cross_kv8_samples (beam_width = 1: the one-query launch); the cross K/V is never reordered.
+ *   - either buffer alone is valid; with neither the call is the plain one, launch for launch.  The workspace queries are unchanged.
+ * dimx_generate / dimx_generate_prompted / dimx_generate_guided do not read the setting.  Part of what keys the captured step graph. */
+int dimx_set_beam_kv8(dimx_handle h, int on);
+/* The handle's current setting. */
+int dimx_beam_kv8(dimx_handle h, int* on);
 /* Streaming sessions (csrc/stream.hip; the schedule is dimx/stream.py): the speaker arrives in pieces, the listener's
  * tokens leave as soon as they are due.  A session fed a clip in pieces computes what dimx_encode_ctx + dimx_generate under
  * dimx_set_cross_lookahead(1, lookahead) compute on the whole clip: the speaker encoders are causal, so the context rows of the new
@@ -1290,6 +1307,11 @@ int dimx_op_nn_gather(const int32_t* idx, const float* lib_seq, long clip_stride
 int dimx_op_beam_step(const float* logits, const double* cum, const int32_t* mode, const int32_t* forced_tok, int B, int W,
                       int32_t* parent, int32_t* token, double* cum_out, void* stream);
 int dimx_op_beam_reorder(void* cache, int dtype, const int32_t* parent, int R, int W, int H, int T, int c, void* stream);
+/* dimx_op_beam_reorder_kv8: the same permutation of one FP8 code plane kcodes [R, H, Tp, 64] uint8 (16-byte aligned) and its scale
+ *   plane kscale [R, H, Tp] f32 (dimx/kv8.py reorder): codes and scale of the positions 0 .. c of row clip*W + w become those of row
+ *   clip*W + parent[w], in place; positions > c and clips whose parents are the identity (or out of range) are not touched.  One
+ *   launch; W = 1 launches nothing.  The same DIMX_ERR_ARG cases, with c outside [0, Tp). */
+int dimx_op_beam_reorder_kv8(void* kcodes, void* kscale, const int32_t* parent, int R, int W, int H, int Tp, int c, void* stream);
 /* tokens = sampler(logits[R,512]) -- see dimx_generate. */
 int dimx_op_sample(const float* logits, int R, int top_k, float temperature, const float* exp_noise,
                    uint64_t seed, uint64_t step, int32_t* tokens, void* stream);
